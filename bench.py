@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- CG-iteration throughput of the MI355X LS-SVM backend on BASELINE.json's metric.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c5] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" is ONE CG iteration (one implicit kernel-matrix--vector product + the CG vector updates, plus the residual
@@ -19,7 +19,9 @@ Three ways to run N > 1:
     which is how the sharded path runs on a one-GPU box -- n_gpus then still reports the distinct devices).
 
 Prints ONE JSON line on rank 0.  `value` = effective K*d GFLOP/s = 2 * n^2 * d * K / t (n = N_points - 1; full square, no
-symmetry credit); `cg_iters_per_s` is the other half of BASELINE.json's metric.
+symmetry credit); `cg_iters_per_s` is the other half of BASELINE.json's metric.  A plain run measures the headline
+alone (its roofline from the same timed steps); --full adds the legs that take runs or samplers of their own: board power, the native
+and bare-MFMA-loop lines, the other workloads, predict and end-to-end legs, the CPU baseline.
 """
 
 from __future__ import annotations
@@ -373,6 +375,17 @@ def e2e_leg(seed, workdir=None):
     return out
 
 
+def dump_outputs(prob, outdir):
+    """--dump-outputs: what a caller of the timed path receives after its last step -- alpha (N entries: the CG iterate and alpha_N = -sum) and rho from
+    lssvm_mi355_cg_finish, in the workload's dtype (c5: 4 MB).  The inputs are seeded, so two builds can be compared output for output."""
+    import numpy as np
+
+    alpha, rho, _ = prob.cg_finish()
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, "alpha.npy"), alpha)
+    np.save(os.path.join(outdir, "rho.npy"), np.asarray([rho], dtype=alpha.dtype))
+
+
 def free_port() -> int:
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
         s.bind(("127.0.0.1", 0))
@@ -446,7 +459,7 @@ def main():
                     help="TESTING AID for one-GPU boxes: load this library (tests/tools/fake_rccl/librccl.so.1, a stand-in with RCCL's SONAME that accepts several "
                          "ranks per device) into the process before torch and the product library, so that the product's own dlopen(\"librccl.so.1\") resolves to it.  "
                          "The line then names it in config.rccl_library; such a line is a functional check of the RCCL exchange path, never a scaling number")
-    ap.add_argument("--no-other-workloads", action="store_true", help="default run (c5, one GPU): skip the short legs of c2 / c3 / c4 reported as other_workloads")
+    ap.add_argument("--no-other-workloads", action="store_true", help="--full run (c5, one GPU): skip the short legs of c2 / c3 / c4 reported as other_workloads")
     ap.add_argument("--gram-mode", type=int, default=None, choices=[0, 1, 2, 3],
                     help="fp32 only: 3 (library default) = f16x3 where the data passes the representability check, else bf16x6; 2 = f16x3 unchecked; "
                          "1 = bf16x6; 0 = native v_mfma_f32 chains")
@@ -456,6 +469,13 @@ def main():
     ap.add_argument("--no-native-reference", action="store_true", help="skip the extra native v_mfma_f32 run reported beside a bf16x6 headline")
     ap.add_argument("--no-ceiling", action="store_true", help="skip the bare bf16 MFMA loop (about 4 s) whose rate on this device is reported beside roofline.frac")
     ap.add_argument("--seed", type=int, default=42)
+    ap.add_argument("--full", action="store_true",
+                    help="measure more than the headline: board power and throttle residency of the timed region, the native and bare-MFMA-loop lines beside a split-mode "
+                         "headline, the other BASELINE workloads with the predict and end-to-end legs (c5, one GPU) and the CPU baseline (each still subject to its --no-* "
+                         "option).  Without it a run sets up, warms up, times the steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what they computed, as a caller of the path receives it (lssvm_mi355_cg_finish): DIR/alpha.npy (N entries) and "
+                         "DIR/rho.npy, in the workload's dtype (rank 0)")
     args = ap.parse_args()
 
     launched = "WORLD_SIZE" in os.environ
@@ -621,7 +641,7 @@ def main():
     # board power and shader clock of this rank's device while the timed steps run (a host thread reading two sysfs files every 20 ms: the
     # 16-bit tile kernels sit at the board's power cap, DESIGN.md 4.1.0 -- the line should say so for the box it was taken on)
     sampler = None
-    if rank == 0 and devices is None:
+    if args.full and rank == 0 and devices is None:
         from plssvm_amd.hwmon import PowerSampler
 
         sampler = PowerSampler(local_rank)
@@ -701,6 +721,8 @@ def main():
         ranks_agree = all(e == everyone[0] for e in everyone)
         if not ranks_agree:
             print(f"[bench rank {rank}] the ranks DISAGREE on the residuum after the timed steps: {[struct.unpack('<dQ', e) for e in everyone]}", file=sys.stderr, flush=True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(prob, args.dump_outputs)
 
     n = N - 1
     flop_step = 2.0 * n * n * d
@@ -800,7 +822,7 @@ def main():
                          # the same launch priced with the full-square convention of `value` (can exceed the peak when symmetric)
                          "full_square_flop_per_launch": square_launch, "effective_full_square": effective},
         }
-        if bf16x6 and shards == 1 and not args.no_native_reference:
+        if args.full and bf16x6 and shards == 1 and not args.no_native_reference:
             # the same workload on native v_mfma_f32 chains (option gram_mode = 0), reported beside the headline -- never as `value`
             prob.close()
             _capi.set_option("gram_mode", 0)
@@ -822,7 +844,7 @@ def main():
             nat.close()
             _capi.set_option("gram_mode", 3)
             prob = None
-        if bf16x6 and shards == 1 and not args.no_ceiling:
+        if args.full and bf16x6 and shards == 1 and not args.no_ceiling:
             # what a loop of NOTHING BUT the Gram kernel's MFMA instruction sustains on this device, now (the chip lowers its clock under
             # matrix-core load): reported beside roofline.frac, never instead of it -- `peak` stays the nominal figure
             if prob is not None:
@@ -848,7 +870,7 @@ def main():
                 "kernel_vs_bare_register_loop": achieved / regs_tf if regs_tf > 0 else None,
                 "kernel_vs_bare_lds_fed_loop": achieved / lds_tf if lds_tf > 0 else None,
             }
-        if args.workload == "c5" and shards == 1 and not args.no_other_workloads:
+        if args.full and args.workload == "c5" and shards == 1 and not args.no_other_workloads:
             # BASELINE's other single-GPU configs, driver-observed: short legs on the same device after the headline's legs
             if prob is not None:
                 prob.close()
@@ -870,7 +892,7 @@ def main():
                 out["e2e"] = {"error": f"{type(e).__name__}: {e}"}
         # the CPU legs come LAST: the OpenMP runtime's workers keep spinning after a parallel region and would slow the host side of
         # the GPU legs down (measured: 16 ms instead of 2.6 ms per c2 iteration in a native leg that followed them)
-        if not args.no_cpu_baseline and shards == 1:
+        if args.full and not args.no_cpu_baseline and shards == 1:
             line_a, line_b = cpu_baseline(X, y, wl["kernel"], args.cpu_sample_rows, 3)
             out["cpu_baseline"] = line_a
             if line_b is not None:

@@ -74,7 +74,7 @@ print('OK')
 
 def test_bench_json_contract_small_workload():
     env = dict(os.environ)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c2", "--steps", "3", "--warmup", "1", "--cpu-sample-rows", "2048"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c2", "--steps", "3", "--warmup", "1", "--cpu-sample-rows", "2048", "--full"],
                          capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stdout + out.stderr
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
@@ -106,6 +106,25 @@ def test_bench_json_contract_small_workload():
     # value is whole-job: 2 n^2 d per step / ms_per_step
     n, d = 49_999, 128
     assert abs(j["value"] - 2.0 * n * n * d / (j["ms_per_step"] * 1e-3) / 1e9) < 1e-6 * j["value"]
+
+
+def test_bench_plain_run_is_the_headline_and_dumps_its_outputs(tmp_path):
+    """Without --full the line carries the headline and the roofline of its own timed steps, none of the legs that take runs of their own; --dump-outputs
+    writes what cg_finish hands a caller after the last timed step: alpha (N entries, alpha_N = -sum of the others) and rho."""
+    out_dir = tmp_path / "outputs"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c2", "--steps", "4", "--warmup", "1", "--dump-outputs", str(out_dir)],
+                         capture_output=True, text=True, timeout=600, env=dict(os.environ))
+    assert out.returncode == 0, out.stdout + out.stderr
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    j = json.loads(lines[0])
+    assert j["steps"] == 4 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["higher_is_better"] is True and j["dtype"] == "f32" and j["unit"] == "GFLOP/s"
+    assert not {"cpu_baseline", "cpu_baseline_release", "native_f32_path", "other_workloads", "e2e"} & set(j), sorted(j)
+    assert "bare_mfma_loop" not in j["roofline"] and j["roofline"]["board_power"] is None and 0.05 < j["roofline"]["frac"] < 1.0
+    alpha, rho = np.load(out_dir / "alpha.npy"), np.load(out_dir / "rho.npy")
+    assert alpha.dtype == np.float32 and alpha.shape == (50_000,) and rho.dtype == np.float32 and rho.shape == (1,)
+    assert np.all(np.isfinite(alpha)) and np.isfinite(rho[0]) and np.any(alpha[:-1] != 0)
+    assert abs(float(np.sum(alpha, dtype=np.float64))) <= 1e-5 * float(np.sum(np.abs(alpha), dtype=np.float64))
 
 
 def test_bench_rank_path_two_ranks_on_one_device():

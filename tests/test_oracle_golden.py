@@ -1,5 +1,6 @@
 """CPU: the plain-C oracle (oracle/lssvm_oracle.c) against the golden vectors captured from the REFERENCE's own OpenMP
-kernels (tests/golden/make_golden.py) and -- where oracle/_ref was built (this container) -- against that library live.
+kernels (tests/golden/make_golden.py), against that library's stored answers on seeded inputs (tests/golden/make_golden_live_ref.py) and -- where
+oracle/_ref was built -- against the library live.
 This is what pins the oracle."""
 
 import numpy as np
@@ -101,34 +102,64 @@ def test_preconditions(oracle):
         oracle.solve("linear", X, np.ones(3), 1e-3, 0)     # max_iter > 0 (csvm.cpp:78)
 
 
-@pytest.mark.skipif(not ol.have_ref(), reason="oracle/_ref not built (needs /root/reference)")
+class _StoredReference:
+    """The reference library's answers on the inputs of test_oracle_vs_live_reference, as tests/golden/make_golden_live_ref.py stored them: the test
+    runs where oracle/_ref cannot be built."""
+
+    def __init__(self, kernel, dt):
+        import os
+
+        from conftest import HERE
+
+        self.fx = np.load(os.path.join(HERE, "golden", "live_ref_151x23.npz"))
+        self.key = f"{kernel}/{'f32' if dt == np.float32 else 'f64'}"
+
+    def q(self, kernel, X, **kw):
+        return self.fx[self.key + "/q"]
+
+    def matvec(self, kernel, X, q, rhs, ret, QA, cost, add, **kw):
+        return self.fx[self.key + "/matvec"]
+
+    def solve(self, kernel, X, y, eps, max_iter, cost, **kw):
+        alpha = self.fx[self.key + ("/solve_alpha_f64" if X.dtype != self.fx[self.key + "/solve_alpha"].dtype else "/solve_alpha")]
+        return alpha, None, {"iterations": int(self.fx[self.key + "/solve_iterations"])}
+
+    def predict_values(self, kernel, sv, alpha, rho, pts, **kw):
+        return self.fx[self.key + "/predict"], None
+
+
 @pytest.mark.parametrize("kernel", KERNELS)
 @pytest.mark.parametrize("dt", [np.float32, np.float64])
 def test_oracle_vs_live_reference(oracle, kernel, dt):
+    """The oracle against the reference's own OpenMP kernels: their stored answers always, and the library itself where oracle/_ref was built."""
     rng = np.random.default_rng(5)
     X = rng.uniform(-1, 1, size=(151, 23)).astype(dt)
     y = np.where(rng.uniform(size=151) > 0.5, 1, -1).astype(dt)
-    ref = ol.ref()
     kw = dict(degree=3, gamma=1.0 / 23, coef0=0.5)
-    assert np.array_equal(oracle.q(kernel, X, **kw), ref.q(kernel, X, **kw))
-    q = ref.q(kernel, X, **kw)
+    stored = _StoredReference(kernel, dt)
+    tag = "f32" if dt == np.float32 else "f64"
+    assert np.array_equal(stored.fx[f"{tag}/X"], X) and np.array_equal(stored.fx[f"{tag}/y"], y)  # (the fixture was drawn from the same generator)
     rhs = rng.uniform(1, 2, size=150).astype(dt)
-    a = oracle.matvec(kernel, X, q, rhs, np.zeros(150, dt), 2.0, 1.0, 1.0, **kw)
-    b = ref.matvec(kernel, X, q, rhs, np.zeros(150, dt), 2.0, 1.0, 1.0, **kw)
-    assert ol.rel_inf(a, b) < 64 * np.finfo(dt).eps
-    ao, ro, io = oracle.solve(kernel, X, y, 1e-30, 5, cost=1.0, **kw)
-    ar, rr, ir = ref.solve(kernel, X, y, 1e-30, 5, cost=1.0, **kw)
-    assert io["iterations"] == ir["iterations"] == 5
-    if dt == np.float64:
-        assert ol.rel_inf(ao, ar) < 1e-4  # atomics reorder the sums; 5 CG steps on unscaled data amplify 1e-16 to ~1e-6
-    else:
-        # fp32 CG amplifies the atomics' summation-order noise: compare both against the fp64 solve of the same length
-        a64, _, _ = ref.solve(kernel, X.astype(np.float64), y.astype(np.float64), 1e-30, 5, cost=1.0, **kw)
-        assert ol.rel_inf(ao, a64) <= max(10 * ol.rel_inf(ar, a64), 1e-4)
-    sv, al, pts = X[:50], rhs[:50], X[100:120]
-    po, _ = oracle.predict_values(kernel, sv, al, 0.25, pts, **kw)
-    pr, _ = ref.predict_values(kernel, sv, al, 0.25, pts, **kw)
-    assert ol.rel_inf(po, pr) < 64 * np.finfo(dt).eps
+    assert np.array_equal(stored.fx[f"{tag}/rhs"], rhs)
+    for ref in [stored] + ([ol.ref()] if ol.have_ref() else []):
+        assert np.array_equal(oracle.q(kernel, X, **kw), ref.q(kernel, X, **kw))
+        q = ref.q(kernel, X, **kw)
+        a = oracle.matvec(kernel, X, q, rhs, np.zeros(150, dt), 2.0, 1.0, 1.0, **kw)
+        b = ref.matvec(kernel, X, q, rhs, np.zeros(150, dt), 2.0, 1.0, 1.0, **kw)
+        assert ol.rel_inf(a, b) < 64 * np.finfo(dt).eps
+        ao, ro, io = oracle.solve(kernel, X, y, 1e-30, 5, cost=1.0, **kw)
+        ar, rr, ir = ref.solve(kernel, X, y, 1e-30, 5, cost=1.0, **kw)
+        assert io["iterations"] == ir["iterations"] == 5
+        if dt == np.float64:
+            assert ol.rel_inf(ao, ar) < 1e-4  # atomics reorder the sums; 5 CG steps on unscaled data amplify 1e-16 to ~1e-6
+        else:
+            # fp32 CG amplifies the atomics' summation-order noise: compare both against the fp64 solve of the same length
+            a64, _, _ = ref.solve(kernel, X.astype(np.float64), y.astype(np.float64), 1e-30, 5, cost=1.0, **kw)
+            assert ol.rel_inf(ao, a64) <= max(10 * ol.rel_inf(ar, a64), 1e-4)
+        sv, al, pts = X[:50], rhs[:50], X[100:120]
+        po, _ = oracle.predict_values(kernel, sv, al, 0.25, pts, **kw)
+        pr, _ = ref.predict_values(kernel, sv, al, 0.25, pts, **kw)
+        assert ol.rel_inf(po, pr) < 64 * np.finfo(dt).eps
 
 
 @pytest.mark.parametrize("kernel", KERNELS)

@@ -13,7 +13,7 @@ for f in power1_cap power1_cap_max power1_average power1_input energy1_input fre
 done
 echo "--- idle gpu_metrics" >> $out
 xxd -l 16 $dev/gpu_metrics >> $out
-python3 bench.py --workload c5 --steps 40 --warmup 2 --no-cpu-baseline --no-native-reference --no-ceiling --no-other-workloads > gpurun_out/r05_throttle_probe_bench.json 2>/dev/null &
+python3 bench.py --workload c5 --steps 40 --warmup 2 --full --no-cpu-baseline --no-native-reference --no-ceiling --no-other-workloads > ${out%.log}_bench.json 2>/dev/null &
 pid=$!
 sleep 25
 for i in 1 2 3; do
