@@ -515,10 +515,15 @@ class Predictor final : public PredictorBase {
             std::memcpy(&rel2, &host[0], sizeof(float));
             std::memcpy(&rest2, &host[1], sizeof(float));
             std::memcpy(&x2, &host[2], sizeof(float));
-            bool ok = rel2 <= F16_REL2_MAX;
-            if (!ok && rbf) ok = std::isfinite(rel2) && 2.0 * std::sqrt(static_cast<double>(rest2) * static_cast<double>(x2)) <= static_cast<double>(F16_ABS_MAX);
-            info.f16_row_rel_error = std::max(planesS_.f16_row_rel_error, std::sqrt(static_cast<double>(rel2)));
-            if (!ok && opt_.gram_mode != 2) return false;  // the support vectors' planes are f16, this batch needs bf16: one-shot (which splits both sides alike)
+            // the check over BOTH sides, as make_planes runs it for the one-shot call (one set of statistics for the support vectors and the points): the batch's maxima
+            // beside the support vectors' -- the batch alone can pass (and the support vectors alone) where the pair does not, e.g. the rbf bound 2 max|rest| max|x| with the
+            // rest of one side and the norm of the other.  (std::max keeps a batch's NaN: an overflowing plane)
+            rel2 = std::max(rel2, planesS_.f16_rel2);
+            rest2 = std::max(rest2, planesS_.f16_rest2);
+            x2 = std::max(x2, planesS_.f16_x2);
+            const bool ok = f16_planes_pass(rbf, rel2, rest2, x2);
+            info.f16_row_rel_error = std::sqrt(static_cast<double>(rel2));
+            if (!ok && opt_.gram_mode != 2) return false;  // the support vectors' planes are f16, the pair needs bf16: one-shot (which splits both sides alike)
         } else {
             split_bf16_planes(P.data.p, P.ldx, P.dfeat, static_cast<size_t>(P.rows_alloc), planesP.ldx16, planesP.buf.p, static_cast<size_t>(P.rows_alloc) * planesP.ldx16, s);
         }

@@ -325,8 +325,10 @@ void make_planes(const Options &o, const lssvm_params &p, bool rbf_direct, const
         std::memcpy(&rest2, &host[1], sizeof(float));
         std::memcpy(&x2, &host[2], sizeof(float));
         out.f16_row_rel_error = std::sqrt(static_cast<double>(rel2));  // (NaN: an overflowing plane)
-        bool ok = rel2 <= F16_REL2_MAX;  // (false for a NaN: an overflowing plane)
-        if (!ok && p.kernel_type == LSSVM_KERNEL_RBF) ok = std::isfinite(rel2) && 2.0 * std::sqrt(static_cast<double>(rest2) * static_cast<double>(x2)) <= static_cast<double>(F16_ABS_MAX);
+        out.f16_rel2 = rel2;
+        out.f16_rest2 = rest2;
+        out.f16_x2 = x2;
+        const bool ok = f16_planes_pass(p.kernel_type == LSSVM_KERNEL_RBF, rel2, rest2, x2);
         if (const char *dbg = std::getenv("LSSVM_MI355_DEBUG"); dbg != nullptr && dbg[0] == '1') {
             std::fprintf(stderr, "[plssvm_amd] f16 planes: shift %d, max relative representation error of a row %.3g (accepted up to %.3g), max |rest| %.3g, max |x| %.3g -> %s\n", shift,
                          std::sqrt(static_cast<double>(rel2)), std::sqrt(static_cast<double>(F16_REL2_MAX)), std::sqrt(static_cast<double>(rest2)), std::sqrt(static_cast<double>(x2)),

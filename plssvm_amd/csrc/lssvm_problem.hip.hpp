@@ -301,6 +301,8 @@ void shard_blocks(int num_tiles, int world, int rank, bool symmetric, int &begin
 struct PlaneSet {
     DevBuf<float> row_inv_scale;     // f16x3, linear kernel, round 6: 2^-k_i per row where the planes carry a scale PER ROW (empty: one scale for the matrix)
     double f16_row_rel_error = -1.0;  // what the representability check of the f16 planes measured (make_planes), -1 where it did not run
+    float f16_rel2 = 0.0f, f16_rest2 = 0.0f, f16_x2 = 0.0f;  // the check's statistics {max rel^2, max |rest|^2, max |y|^2} over THIS matrix (and M2), where it ran: the resident
+                                                              // predictor combines them with a batch's to decide as the one-shot call does (f16_planes_pass)
     DevBuf<uint16_t> buf;
     int ldx16 = 0;
     int mode = 0;   // 0 none, 1 bf16x6 (three bf16 planes), 2 f16x3 (two f16 planes)
@@ -610,6 +612,12 @@ constexpr int F16_TARGET_EXP = 14;       // f16x3, linear / polynomial: the plan
 constexpr int F16_MAX_SHIFT = 40;        // |k| is clamped here (2^(-2k) must stay a normal float beside gamma)
 constexpr float F16_REL2_MAX = 0x1p-44f; // accepted relative representation error of a row, squared: |x - (hi + mid)| <= 2^-22 |x| in the 2-norm
 constexpr float F16_ABS_MAX = 0x1p-22f;  // rbf: accepted bound on the ABSOLUTE error of the exponent from the representation, 2 max|rest| max|x|
+/* the representability check of make_planes on the statistics of k_split_f16x2: two f16 planes represent the data -- relative error of every row at most 2^-22, or for rbf
+ * an absolute bound on the exponent's error, 2 max|rest| max|x| <= F16_ABS_MAX (false for a NaN: an overflowing plane) */
+inline bool f16_planes_pass(bool rbf, float rel2, float rest2, float x2) {
+    if (rel2 <= F16_REL2_MAX) return true;
+    return rbf && std::isfinite(rel2) && 2.0 * std::sqrt(static_cast<double>(rest2) * static_cast<double>(x2)) <= static_cast<double>(F16_ABS_MAX);
+}
 
 template <typename T>
 T rbf_prescale(const lssvm_params &p, bool fp64_v2);

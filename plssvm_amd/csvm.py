@@ -151,25 +151,36 @@ class MI355CSVM(CSVM):
 
     def predict(self, model: Model, data: DataSet):
         """csvm::predict (csvm.hpp:322-342) with the model RESIDENT in HBM from the first call on (``lssvm_mi355_predictor_*``): later calls with the same model upload only
-        their points.  Same labels as the base class's one-shot ``predict_values``."""
+        their points.  Same labels as the base class's one-shot ``predict_values`` with the state of the moment: the resident predictor is made again (and the old one
+        closed) when this object's options -- or, without options of its own, the process defaults --, the model's parameters, its support-vector array (by identity),
+        ``alpha`` (compared by value, in place edits included) or ``rho`` have changed since it was made.  Editing the support-vector matrix IN PLACE is not detected."""
         if model.num_features() != data.num_features():
             raise InvalidParameterError(f"Number of features per data point ({data.num_features()}) must match the number of features per support vector of the "
                                         f"provided model ({model.num_features()})!")
         t0 = time.perf_counter()
+        sv = model.support_vectors()
+        opts = tuple(self._options.get(n) if self._options is not None else _capi.get_option(n) for n in _capi.OPTION_NAMES)
+        prm = model.params
+        params = (int(prm.kernel_type), prm.degree, prm.gamma, prm.coef0)
         cached = getattr(model, "_predictor", None)
-        if cached is None or cached[0] is not self:
-            cached = (self, backend.Predictor(model.params, model.support_vectors(), model.alpha, float(model.rho), options=self._options))
+        if (cached is None or cached["owner"] is not self or cached["options"] != opts or cached["params"] != params or cached["sv"] is not sv
+                or not np.array_equal(cached["alpha"], model.alpha) or cached["rho"] != float(model.rho)):
+            if cached is not None:
+                cached["predictor"].close()  # (its HBM: nothing else holds it)
+            alpha = np.array(model.alpha, copy=True)
+            cached = {"owner": self, "options": opts, "params": params, "sv": sv, "alpha": alpha, "rho": float(model.rho),
+                      "predictor": backend.Predictor(model.params, sv, alpha, float(model.rho), options=self._options)}
             model._predictor = cached
         t1 = time.perf_counter()
         info = {}
-        values = cached[1].predict(data.data(), info_out=info)
+        values = cached["predictor"].predict(data.data(), info_out=info)
         t2 = time.perf_counter()
         mapper = model.data.mapping
         pos, neg = mapper.label_of(1), mapper.label_of(-1)
         labels = [pos if p else neg for p in (np.asarray(values) > 0).tolist()]  # operators.hpp:180-182 sign, csvm.hpp:337-340
         # where the call's time went, in seconds (the command line's timing block and bench.py's `e2e` print it)
         self.last_predict_phases = {"model_to_hbm_s": t1 - t0, "values_s": t2 - t1, "library_total_ms": float(info.get("total_ms", 0.0)), "kernel_ms": float(info.get("kernel_ms", 0.0)),
-                                    "labels_s": time.perf_counter() - t2}
+                                    "resident": int(info.get("resident", 0)), "labels_s": time.perf_counter() - t2}
         return labels
 
 
