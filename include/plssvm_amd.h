@@ -163,6 +163,23 @@ int lssvm_mi355_solve_multi_f64(const lssvm_params *params, const double *X, siz
                                 double eps, uint64_t max_iter, double *alpha_out, double *rho_out, lssvm_cg_info *info,
                                 const int *devices, int num_devices, const lssvm_mi355_options *options);
 
+/* WEIGHTED LS-SVM (Suykens et al. 2002; no counterpart in the reference, whose Python bindings reject class_weight and sample_weight,
+ * bindings/Python/sklearn.cpp:85-86, :148-150): point i carries a weight w_i > 0 and its own regularisation 1 / (C w_i) -- the primal
+ * minimises 1/2 |w|^2 + 1/2 C sum_i w_i e_i^2, the dual is [0 1^T; 1 K + diag(1 / (C w))] [b; alpha] = [0; y].  b is eliminated through the
+ * last point exactly as in the unweighted solve (csvm.cpp:71-183), which leaves
+ *     Abar(w)_ij = k(x_i,x_j) + delta_ij / (C w_i) + QA_cost(w) - q_i - q_j,   QA_cost(w) = k(x_N,x_N) + 1 / (C w_N);
+ * q, b = y[0..n) - y[n], x0 = 1, the stop test, the refresh every 50th iteration, bias and alpha[N-1] = -sum are those of the unweighted solve.
+ * Every diagonal term is formed as 1 / C is, in the real type: T(1) / (T(C) * T(w_i)).  So w == 1 gives exactly the bits of lssvm_mi355_solve_*
+ * (alpha, rho, iteration count), and w == 2 exactly those of the unweighted solve at cost 2C.
+ * weights: num_points entries, each finite and > 0 (and 1 / (C w_i) finite in the real type); NULL, a NaN, an inf or a weight <= 0 is
+ * LSSVM_ERR_INVALID_ARGUMENT, reported before any device is touched.  Runs on device 0 of the calling process; info may be NULL. */
+int lssvm_mi355_solve_weighted_f32(const lssvm_params *params, const float *X, size_t num_points, size_t num_features, const float *y,
+                                   const double *weights, float eps, uint64_t max_iter, float *alpha_out, float *rho_out,
+                                   lssvm_cg_info *info, const lssvm_mi355_options *options);
+int lssvm_mi355_solve_weighted_f64(const lssvm_params *params, const double *X, size_t num_points, size_t num_features, const double *y,
+                                   const double *weights, double eps, uint64_t max_iter, double *alpha_out, double *rho_out,
+                                   lssvm_cg_info *info, const lssvm_mi355_options *options);
+
 /* csvm::predict_values (csvm.hpp:204, :208; recipe: backends/OpenMP/csvm.cpp:188-227, HIP/predict_kernel.hip.hpp:34-117).
  * w_inout has num_features entries; *w_valid != 0 on entry means it already holds w (linear kernel only), on exit it is
  * set to 1 when w was computed (calculate_w, csvm.cpp:255-280).  out: num_predict_points decision values.  info (may be NULL): the timings of the call. */
@@ -268,10 +285,16 @@ int lssvm_mi355_problem_create_multi(lssvm_mi355_problem **out, const lssvm_para
                                      size_t num_points, size_t num_features, const int *devices, int num_devices, const lssvm_mi355_options *options);
 int lssvm_mi355_problem_destroy(lssvm_mi355_problem *p);
 
-/* read back q (N-1 entries, dtype of the problem) and QA_cost */
+/* read back q (N-1 entries, dtype of the problem) and QA_cost (of the weighted system where weights are set) */
 int lssvm_mi355_problem_get_q(lssvm_mi355_problem *p, void *q_out, double *QA_cost_out);
 
-/* ret[0..N-1) += add * Abar * d (host vectors of the problem's dtype, N-1 entries EACH: the library reads and writes exactly
+/* v: num_points weights, each finite and > 0; NULL = unweighted (today's system).  Takes effect from the next
+ * lssvm_mi355_cg_begin / lssvm_mi355_problem_matvec; rejected between cg_begin and cg_finish.
+ * The weighted system of lssvm_mi355_solve_weighted_* (the same w == 1 guarantee), on any handle: every shard of a
+ * lssvm_mi355_problem_create_multi handle takes the vector, and with one process per GPU (lssvm_shard) every rank must be given the same full vector. */
+int lssvm_mi355_problem_set_weights(lssvm_mi355_problem *p, const double *weights, size_t num_points);
+
+/* ret[0..N-1) += add * Abar * d -- Abar(w) where weights are set -- (host vectors of the problem's dtype, N-1 entries EACH: the library reads and writes exactly
  * num_points - 1 elements of both).  With sharding every rank returns the full vector. */
 int lssvm_mi355_problem_matvec(lssvm_mi355_problem *p, const void *d, void *ret_inout, double add);
 

@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = [
     "lssvm_mi355_abi_version", "lssvm_mi355_device_count", "lssvm_mi355_device_name", "lssvm_mi355_last_error",
     "lssvm_mi355_options_create", "lssvm_mi355_options_set", "lssvm_mi355_options_get", "lssvm_mi355_options_destroy",
     "lssvm_mi355_solve_f32", "lssvm_mi355_solve_f64", "lssvm_mi355_solve_multi_f32", "lssvm_mi355_solve_multi_f64", "lssvm_mi355_predict_values_f32", "lssvm_mi355_predict_values_f64",
+    "lssvm_mi355_solve_weighted_f32", "lssvm_mi355_solve_weighted_f64", "lssvm_mi355_problem_set_weights",
     "lssvm_mi355_predictor_create", "lssvm_mi355_predictor_predict", "lssvm_mi355_predictor_destroy",
     "lssvm_mi355_generate_q_f32", "lssvm_mi355_generate_q_f64", "lssvm_mi355_run_device_kernel_f32", "lssvm_mi355_run_device_kernel_f64",
     "lssvm_mi355_calculate_w_f32", "lssvm_mi355_calculate_w_f64",
@@ -93,6 +94,26 @@ lib = _load()
 lib.lssvm_mi355_last_error.restype = C.c_char_p
 lib.lssvm_mi355_abi_version.restype = C.c_int
 lib.lssvm_mi355_device_count.restype = C.c_int
+
+
+def weighted_entry(name: str):
+    """``lssvm_mi355_solve_weighted_f32 / _f64`` or ``lssvm_mi355_problem_set_weights`` with its argument types (weights are double whatever the real type).
+    Bound at the first call, so that an older build named by PLSSVM_AMD_LIBRARY still serves everything else."""
+    fn = getattr(lib, name)
+    if fn.argtypes is None:
+        if name == "lssvm_mi355_problem_set_weights":
+            fn.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_size_t]
+        else:
+            ct = C.c_float if name.endswith("_f32") else C.c_double
+            fn.argtypes = [C.POINTER(LssvmParams), C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.POINTER(C.c_double), ct, C.c_uint64, C.c_void_p, C.POINTER(ct),
+                           C.POINTER(LssvmCgInfo), C.c_void_p]
+        fn.restype = C.c_int
+    return fn
+
+
+def weights_ptr(w: np.ndarray | None):
+    """The ``const double *weights`` argument: NULL for None."""
+    return None if w is None else w.ctypes.data_as(C.POINTER(C.c_double))
 
 
 def last_error() -> str:

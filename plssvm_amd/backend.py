@@ -42,17 +42,31 @@ def _as_matrix(A, dtype=None) -> np.ndarray:
     return A
 
 
-def solve_system_of_linear_equations(params: Parameter, A, b, eps: float, max_iter: int, devices=None, num_devices: int | None = None, options: Options | None = None):
+def _as_weights(sample_weight, N: int) -> np.ndarray:
+    """The per-point weights of a weighted solve as the library takes them: N doubles, each finite and > 0."""
+    w = np.ascontiguousarray(sample_weight, dtype=np.float64)
+    if w.shape != (N,):
+        raise InvalidParameterError(f"The number of data points ({N}) and the number of weights ({w.size}) must be the same!")
+    if not (np.all(np.isfinite(w)) and np.all(w > 0.0)):
+        raise InvalidParameterError("Every weight of the solve must be finite and greater than 0.0!")
+    return w
+
+
+def solve_system_of_linear_equations(params: Parameter, A, b, eps: float, max_iter: int, devices=None, num_devices: int | None = None, options: Options | None = None,
+                                     sample_weight=None):
     """Returns ``(alpha[N], rho, info)`` -- ``csvm::solve_system_of_linear_equations`` (csvm.hpp:188-192).
 
     ``devices`` (a list of HIP ordinals; the same ordinal may repeat) or ``num_devices`` (0 = every visible device) select the
     single-process multi-device solve ``lssvm_mi355_solve_multi_*``; with neither the solve runs on device 0.  ``options``: this call's own tuning knobs
-    (:class:`Options`); None = the process defaults."""
+    (:class:`Options`); None = the process defaults.  ``sample_weight``: N weights > 0 -- the WEIGHTED LS-SVM system (point i regularised by 1 / (C w_i),
+    ``lssvm_mi355_solve_weighted_*``; on several devices a resident problem with ``lssvm_mi355_problem_set_weights``); None = the unweighted solve."""
     A = _as_matrix(A)
     N, d = A.shape
     b = np.ascontiguousarray(b, dtype=A.dtype)
     if b.shape != (N,):
         raise InvalidParameterError(f"The number of data points in the matrix A ({N}) and the values in the right hand side vector ({b.size}) must be the same!")
+    if sample_weight is not None:
+        return _solve_weighted(params, A, b, _as_weights(sample_weight, N), eps, max_iter, devices, num_devices, options)
     ct = ctype_of(A.dtype)
     alpha = np.zeros(N, dtype=A.dtype)
     rho = ct(0)
@@ -71,6 +85,36 @@ def solve_system_of_linear_equations(params: Parameter, A, b, eps: float, max_it
         check(fn(C.byref(ps), ptr(A), C.c_size_t(N), C.c_size_t(d), ptr(b), ct(eps), C.c_uint64(int(max_iter)), ptr(alpha), C.byref(rho), C.byref(info),
                  dev_arr, C.c_int(ndev), options_ptr(options)))
     return alpha, A.dtype.type(rho.value), info.as_dict()
+
+
+def _solve_weighted(params: Parameter, A: np.ndarray, b: np.ndarray, w: np.ndarray, eps: float, max_iter: int, devices, num_devices, options):
+    N, d = A.shape
+    if devices is None and num_devices in (None, 1):  # device 0 alone (what lssvm_mi355_solve_* and _multi with one device run)
+        ct = ctype_of(A.dtype)
+        alpha = np.zeros(N, dtype=A.dtype)
+        rho = ct(0)
+        info = LssvmCgInfo()
+        fn = _capi.weighted_entry(f"lssvm_mi355_solve_weighted_{suffix_of(A.dtype)}")
+        check(fn(C.byref(_params_struct(params, d)), ptr(A), N, d, ptr(b), _capi.weights_ptr(w), eps, int(max_iter), ptr(alpha), C.byref(rho), C.byref(info),
+                 options_ptr(options)))
+        return alpha, A.dtype.type(rho.value), info.as_dict()
+    # several devices: the recipe of the one-shot solve (capi.hip, solve_one_shot) over a resident problem of all of them
+    if not max_iter > 0:
+        raise InvalidParameterError("The number of CG iterations must be greater than 0!")
+    devs = list(devices) if devices is not None else list(range(int(num_devices)))
+    first = options.get("rebalance_after") if options is not None else _capi.get_option("rebalance_after")
+    with ResidentProblem(params, A, devices=devs, options=options) as prob:
+        prob.set_weights(w)
+        prob.cg_begin(b, eps)
+        if 0 < first < max_iter:
+            prob.cg_step(first)
+            prob.rebalance()
+            prob.cg_step(max_iter - first)
+        else:
+            prob.cg_step(max_iter)
+        alpha, rho, info = prob.cg_finish()
+    info["max_iterations"] = int(max_iter)
+    return alpha, rho, info
 
 
 def generate_q(params: Parameter, data, options: Options | None = None):
@@ -279,6 +323,12 @@ class ResidentProblem:
         qa = C.c_double(0)
         check(lib.lssvm_mi355_problem_get_q(self._h, ptr(q), C.byref(qa)))
         return q, float(qa.value)
+
+    def set_weights(self, weights=None) -> None:
+        """Per-point weights of the weighted LS-SVM system (``lssvm_mi355_problem_set_weights``): ``num_points`` values > 0, or None for the unweighted
+        system.  Takes effect from the next :meth:`cg_begin` / :meth:`matvec`; not between ``cg_begin`` and ``cg_finish``."""
+        w = None if weights is None else _as_weights(weights, self.num_points)
+        check(_capi.weighted_entry("lssvm_mi355_problem_set_weights")(self._h, _capi.weights_ptr(w), 0 if w is None else w.size))
 
     def matvec(self, d, ret, add: float = 1.0):
         d = np.ascontiguousarray(d, dtype=self.dtype)

@@ -149,7 +149,7 @@ lssvm::ProblemBase *impl_of(lssvm_mi355_problem *p) {
 
 template <typename T>
 void solve_one_shot(const lssvm_params *params, const T *X, size_t N, size_t d, const T *y, T eps, uint64_t max_iter, T *alpha_out, T *rho_out, lssvm_cg_info *info,
-                    const int *devices, int num_devices, const lssvm_mi355_options *options) {
+                    const int *devices, int num_devices, const lssvm_mi355_options *options, const double *weights = nullptr) {
     lssvm::check_params(params);
     LSSVM_REQUIRE(X != nullptr && N > 0, "The data must not be empty!");                                                                  // csvm.cpp:73
     LSSVM_REQUIRE(d > 0, "The data points must contain at least one feature!");                                                           // csvm.cpp:74
@@ -157,8 +157,10 @@ void solve_one_shot(const lssvm_params *params, const T *X, size_t N, size_t d, 
     LSSVM_REQUIRE(eps > T(0), "The stopping criterion in the CG algorithm must be greater than 0.0, but is " + std::to_string(eps) + "!");  // csvm.cpp:77
     LSSVM_REQUIRE(max_iter > 0, "The number of CG iterations must be greater than 0!");                                                   // csvm.cpp:78
     LSSVM_REQUIRE(alpha_out != nullptr && rho_out != nullptr, "alpha_out / rho_out must not be NULL");
+    if (weights != nullptr) lssvm::check_weights<T>(weights, N, params->cost);  // (before any device is touched)
     const lssvm::Options opt = options_of(options);
     lssvm::Solver<T> prob(opt, *params, X, LSSVM_MEM_HOST, N, d, lssvm::resolve_devices(devices, num_devices, N), nullptr);
+    if (weights != nullptr) prob.set_weights(weights, N);
     prob.cg_begin(y, static_cast<double>(eps));
     // option rebalance_after (several devices, symmetric variant): the first iterations measure every shard's pace, then the shares follow it (lssvm_mi355_problem_rebalance)
     const uint64_t first = static_cast<uint64_t>(opt.rebalance_after);
@@ -233,6 +235,23 @@ int lssvm_mi355_solve_f64(const lssvm_params *params, const double *X, size_t nu
 int lssvm_mi355_solve_multi_f64(const lssvm_params *params, const double *X, size_t num_points, size_t num_features, const double *y, double eps, uint64_t max_iter,
                                 double *alpha_out, double *rho_out, lssvm_cg_info *info, const int *devices, int num_devices, const lssvm_mi355_options *options) {
     return guarded([&] { solve_one_shot<double>(params, X, num_points, num_features, y, eps, max_iter, alpha_out, rho_out, info, devices, num_devices, options); });
+}
+
+int lssvm_mi355_solve_weighted_f32(const lssvm_params *params, const float *X, size_t num_points, size_t num_features, const float *y, const double *weights, float eps,
+                                   uint64_t max_iter, float *alpha_out, float *rho_out, lssvm_cg_info *info, const lssvm_mi355_options *options) {
+    static const int device0 = 0;
+    return guarded([&] {
+        LSSVM_REQUIRE(weights != nullptr, "weights must not be NULL (lssvm_mi355_solve_f32 is the unweighted solve)");
+        solve_one_shot<float>(params, X, num_points, num_features, y, eps, max_iter, alpha_out, rho_out, info, &device0, 1, options, weights);
+    });
+}
+int lssvm_mi355_solve_weighted_f64(const lssvm_params *params, const double *X, size_t num_points, size_t num_features, const double *y, const double *weights, double eps,
+                                   uint64_t max_iter, double *alpha_out, double *rho_out, lssvm_cg_info *info, const lssvm_mi355_options *options) {
+    static const int device0 = 0;
+    return guarded([&] {
+        LSSVM_REQUIRE(weights != nullptr, "weights must not be NULL (lssvm_mi355_solve_f64 is the unweighted solve)");
+        solve_one_shot<double>(params, X, num_points, num_features, y, eps, max_iter, alpha_out, rho_out, info, &device0, 1, options, weights);
+    });
 }
 
 int lssvm_mi355_predict_values_f32(const lssvm_params *params, const float *sv, size_t nsv, size_t nfeat, const float *alpha, float rho, float *w_inout,
@@ -437,6 +456,9 @@ int lssvm_mi355_problem_destroy(lssvm_mi355_problem *p) {
 }
 int lssvm_mi355_problem_get_q(lssvm_mi355_problem *p, void *q_out, double *QA_cost_out) {
     return guarded([&] { impl_of(p)->get_q(q_out, QA_cost_out); });
+}
+int lssvm_mi355_problem_set_weights(lssvm_mi355_problem *p, const double *weights, size_t num_points) {
+    return guarded([&] { impl_of(p)->set_weights(weights, num_points); });
 }
 int lssvm_mi355_problem_matvec(lssvm_mi355_problem *p, const void *d, void *ret_inout, double add) {
     return guarded([&] { impl_of(p)->matvec(d, ret_inout, add); });

@@ -252,16 +252,24 @@ __global__ void k_reduce_partials_sym(const T *__restrict__ partial, long part_s
     }
 }
 
-/* (Abar v)_i = Kv_i + v_i/C + (QA_cost*S - q.v) - S*q_i, evaluated in double */
-template <typename T>
-__device__ __forceinline__ double abar_row(const T *Kv, const T *v, const T *q, int i, double inv_cost, double QA_cost, double S, double QV) {
-    return static_cast<double>(Kv[i]) + static_cast<double>(v[i]) * inv_cost + (QA_cost * S - QV) - S * static_cast<double>(q[i]);
+/* The diagonal term of Abar: 1/C for every row (the scalar inv_cost), or -- WEIGHTED, weighted LS-SVM (lssvm_mi355_problem_set_weights) -- 1/(C w_i) per
+ * row, read from the replicated vector inv_cw.  A compile-time choice: the argument takes the scalar's slot in the kernel's arguments, and the unweighted
+ * instantiations are the kernels as they were, with no extra read. */
+template <bool WEIGHTED>
+using DiagArg = std::conditional_t<WEIGHTED, const double *__restrict__, double>;
+__device__ __forceinline__ double diag_of(double inv_cost, int) { return inv_cost; }
+__device__ __forceinline__ double diag_of(const double *__restrict__ inv_cw, int i) { return inv_cw[i]; }
+
+/* (Abar v)_i = Kv_i + v_i/C + (QA_cost*S - q.v) - S*q_i, evaluated in double (weighted: v_i/(C w_i)) */
+template <typename T, typename D>
+__device__ __forceinline__ double abar_row(const T *Kv, const T *v, const T *q, int i, D diag, double QA_cost, double S, double QV) {
+    return static_cast<double>(Kv[i]) + static_cast<double>(v[i]) * diag_of(diag, i) + (QA_cost * S - QV) - S * static_cast<double>(q[i]);
 }
 
 /* ret_i += add * (Abar v)_i       (run_device_kernel semantics, csvm.cpp:283-306) */
-template <typename T>
+template <typename T, bool WEIGHTED = false>
 __global__ void k_apply_ret(const T *__restrict__ Kv, const T *__restrict__ v, const T *__restrict__ q, const double *__restrict__ sc, int n,
-                            double inv_cost, double QA_cost, double add, T *__restrict__ ret) {
+                            DiagArg<WEIGHTED> inv_cost, double QA_cost, double add, T *__restrict__ ret) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) {
         const double val = abar_row(Kv, v, q, i, inv_cost, QA_cost, sc[SC_S], sc[SC_QD]);
@@ -270,9 +278,9 @@ __global__ void k_apply_ret(const T *__restrict__ Kv, const T *__restrict__ v, c
 }
 
 /* Ad_i = (Abar d)_i ; part[b][0] = sum d_i Ad_i     (csvm.cpp:131-135).  S = sum d and q.d come as k_update_d's partials (`part_d`). */
-template <typename T>
+template <typename T, bool WEIGHTED = false>
 __global__ __launch_bounds__(RED_THREADS) void k_Ad_and_dAd(const T *__restrict__ Kv, const T *__restrict__ d, const T *__restrict__ q,
-                                                            const double *__restrict__ part_d, double *__restrict__ sc, int n, double inv_cost, double QA_cost,
+                                                            const double *__restrict__ part_d, double *__restrict__ sc, int n, DiagArg<WEIGHTED> inv_cost, double QA_cost,
                                                             T *__restrict__ Ad, double *__restrict__ part) {
     __shared__ double lds[8];
     __shared__ double tot[2];
@@ -329,9 +337,9 @@ __global__ __launch_bounds__(RED_THREADS) void k_update_x_r(T *__restrict__ x, T
 /* (Round 5 also let the block of k_update_x_r that finishes last do k_finish_delta's work -- a ticket, two device-scope fences, a second tree: 2 us SLOWER per
  * iteration than the single-block launch it saves, at every size (profiles/r05_ab_fused_chain.log): a device-scope release writes an XCD's L2 back.  Withdrawn.) */
 /* r_i = b_i - (Abar x)_i ; part = sum r^2       (csvm.cpp:101-107 and the refresh :140-145).  Uses SC_SUMX / SC_QX. */
-template <typename T>
+template <typename T, bool WEIGHTED = false>
 __global__ __launch_bounds__(RED_THREADS) void k_residual(const T *__restrict__ Kv, const T *__restrict__ x, const T *__restrict__ q, const T *__restrict__ b,
-                                                          const double *__restrict__ sc, int n, double inv_cost, double QA_cost, T *__restrict__ r,
+                                                          const double *__restrict__ sc, int n, DiagArg<WEIGHTED> inv_cost, double QA_cost, T *__restrict__ r,
                                                           double *__restrict__ part) {
     __shared__ double lds[8];
     const double S = sc[SC_SUMX], QX = sc[SC_QX];

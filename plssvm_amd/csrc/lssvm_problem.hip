@@ -42,6 +42,20 @@ void check_params(const lssvm_params *params) {
     LSSVM_REQUIRE(params->cost != 0.0 && std::isfinite(1.0 / params->cost), "cost must not be 0.0 since it is 1 / plssvm::cost!");  // svm_kernel.cpp:27
 }
 
+template <typename T>
+void check_weights(const double *weights, size_t num_points, double cost) {
+    LSSVM_REQUIRE(weights != nullptr, "weights must not be NULL");
+    for (size_t i = 0; i < num_points; ++i) {
+        const double w = weights[i];
+        LSSVM_REQUIRE(std::isfinite(w) && w > 0.0, "weight " + std::to_string(i) + " is " + std::to_string(w) + ": every weight must be finite and greater than 0.0!");
+        // (the diagonal term is formed in the real type, as 1 / C is: a weight that is positive in double may not be in float)
+        const T inv = T(1) / (static_cast<T>(cost) * static_cast<T>(w));
+        LSSVM_REQUIRE(static_cast<T>(w) > T(0) && std::isfinite(static_cast<double>(inv)), "weight " + std::to_string(i) + " is " + std::to_string(w) + ": 1 / (C * weight) is not finite in the real type!");
+    }
+}
+template void check_weights<float>(const double *, size_t, double);
+template void check_weights<double>(const double *, size_t, double);
+
 static int device_count_checked() {
     int count = 0;
     const hipError_t err = hipGetDeviceCount(&count);
@@ -953,7 +967,8 @@ Problem<T>::Problem(const Options &opt, const lssvm_params &params, const void *
     std::vector<T> last(num_features);
     LSSVM_HIP_CHECK(hipMemcpyAsync(last.data(), X_.data.p + static_cast<size_t>(n_) * X_.ldx, num_features * sizeof(T), hipMemcpyDeviceToHost, st));
     LSSVM_HIP_CHECK(hipStreamSynchronize(st));
-    QA_cost_ = static_cast<double>(host_self_kernel<T>(params_, last) + T(1) / static_cast<T>(params_.cost));
+    self_last_ = static_cast<double>(host_self_kernel<T>(params_, last));
+    QA_cost_ = static_cast<double>(static_cast<T>(self_last_) + T(1) / static_cast<T>(params_.cost));
 
     // vectors (zero padded to nvec_)
     for (DevBuf<T> *v : { &q_, &b_, &x_, &r_, &d_, &Ad_, &Kv_, &tmp_ }) v->alloc_zero(static_cast<size_t>(nvec_) + TILE, st);
@@ -1248,6 +1263,27 @@ void Problem<T>::enqueue_sum_and_qdot(const T *v_dev, int slot_sum, int slot_q) 
     hipLaunchKernelGGL(k_sum_and_qdot<T>, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, stream_.s, v_dev, q_.p, n_, part(PART_SUMS));
     hipLaunchKernelGGL(k_finish2, dim3(1), dim3(RED_THREADS), 0, stream_.s, part(PART_SUMS), sc_.p, slot_sum, slot_q);
     LSSVM_HIP_CHECK(hipGetLastError());
+}
+
+/* Weighted LS-SVM: Abar(w)_ij = k(x_i,x_j) + delta_ij / (C w_i) + QA_cost(w) - q_i - q_j with QA_cost(w) = k(x_last,x_last) + 1 / (C w_last).  Every diagonal term is
+ * formed as inv_cost_ is, in the real type -- so w = 1 gives today's bits, and w = 2 those of the unweighted system at cost 2C (T(C) * T(2) is exact). */
+template <typename T>
+void Problem<T>::set_weights(const double *weights) {
+    const T cost = static_cast<T>(params_.cost);
+    if (weights == nullptr) {
+        weighted_ = false;
+        inv_cw_.release();
+        QA_cost_ = static_cast<double>(static_cast<T>(self_last_) + T(1) / cost);
+        return;
+    }
+    std::vector<double> inv(static_cast<size_t>(nvec_) + TILE, inv_cost_);
+    for (int i = 0; i < n_; ++i) inv[static_cast<size_t>(i)] = static_cast<double>(T(1) / (cost * static_cast<T>(weights[i])));
+    activate();
+    if (inv_cw_.p == nullptr) inv_cw_.alloc_zero(inv.size(), stream_.s);
+    LSSVM_HIP_CHECK(hipMemcpyAsync(inv_cw_.p, inv.data(), inv.size() * sizeof(double), hipMemcpyHostToDevice, stream_.s));
+    LSSVM_HIP_CHECK(hipStreamSynchronize(stream_.s));
+    QA_cost_ = static_cast<double>(static_cast<T>(self_last_) + T(1) / (cost * static_cast<T>(weights[n_])));
+    weighted_ = true;
 }
 
 template class Problem<float>;

@@ -333,6 +333,9 @@ class Problem {
     void build_shard_lists(hipStream_t st);
     PackDc<T> pack_for_d(bool zero_first);  // what k_update_d needs to pack the records of d_ (dc == NULL: this problem packs per matvec); marks them as present
     void enqueue_sum_and_qdot(const T *v_dev, int slot_sum, int slot_q);
+    /* weighted LS-SVM (lssvm_mi355_problem_set_weights): inv_cw_ and QA_cost_ from the weights of all N points (validated by the caller), or back to the
+     * unweighted system for NULL */
+    void set_weights(const double *weights);
     void drain_events();
     hipStream_t stream() const { return stream_.s; }
     /* tile-kernel passes per row-block band: the feature panels of a wide fp32 linear problem, else 1 */
@@ -429,6 +432,9 @@ class Problem {
     PinnedBuf<double> host_delta_;  // one word: k_finish_delta stores the iteration's delta straight into host memory (no copy kernel per iteration)
     double QA_cost_ = 0.0;
     double inv_cost_ = 1.0;
+    double self_last_ = 0.0;  // k(x_last, x_last) in the real type: QA_cost_ = self_last_ + 1/(C w_last) (set_weights)
+    bool weighted_ = false;   // the O(n) kernels read the diagonal 1/(C w_i) from inv_cw_ (their WEIGHTED instantiations) instead of inv_cost_
+    DevBuf<double> inv_cw_;   // ... replicated on every shard like q_, padded with inv_cost_
     double setup_ms_ = 0.0;
 
     // statistics: HIP events around the tile kernel
@@ -457,6 +463,7 @@ struct ProblemBase {
     int dtype = 0;
     virtual ~ProblemBase() = default;
     virtual void get_q(void *q_out, double *QA_cost_out) = 0;
+    virtual void set_weights(const double *weights, size_t num_points) = 0;  // lssvm_mi355_problem_set_weights
     virtual void matvec(const void *d, void *ret_inout, double add) = 0;
     virtual void cg_begin(const void *y, double eps) = 0;
     virtual void cg_step(uint64_t iterations, int *done_out) = 0;
@@ -531,6 +538,7 @@ class Solver final : public ProblemBase {
     ~Solver() override;
 
     void get_q(void *q_out, double *QA_cost_out) override;
+    void set_weights(const double *weights, size_t num_points) override;
     void matvec(const void *d, void *ret_inout, double add) override;
     void cg_begin(const void *y, double eps) override;
     void cg_step(uint64_t iterations, int *done_out) override;
@@ -569,6 +577,7 @@ class Solver final : public ProblemBase {
     uint64_t iter_ = 0;  // iterations done
     bool converged_ = false;
     bool begun_ = false;
+    bool in_cg_ = false;  // between cg_begin and cg_finish: the weights may not change
     double setup_ms_ = 0.0, cg_wall_ms_ = 0.0;
 };
 
@@ -594,6 +603,9 @@ struct PredictorBase {
 std::unique_ptr<PredictorBase> make_predictor(const Options &opt, const lssvm_params &params, int dtype, const void *sv, size_t nsv, size_t nfeat, const void *alpha, double rho);
 
 void check_params(const lssvm_params *params);
+/* weighted LS-SVM: `weights` holds num_points entries, each finite and > 0, whose diagonal terms 1/(C w_i) are finite in the real type T */
+template <typename T>
+void check_weights(const double *weights, size_t num_points, double cost);
 int select_device_checked(int device);
 /* `num_devices` == 0: automatic (all visible devices, but at least 32 row blocks per device); `devices` may be NULL (0 .. num_devices-1) */
 std::vector<int> resolve_devices(const int *devices, int num_devices, size_t num_points);

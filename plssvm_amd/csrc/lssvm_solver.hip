@@ -147,6 +147,17 @@ void Solver<T>::get_q(void *q_out, double *QA_cost_out) {
     if (QA_cost_out != nullptr) *QA_cost_out = p.QA_cost_;
 }
 
+/* weighted LS-SVM: every shard takes the same diagonal terms and QA_cost (all ranks of a world > 1 are handed the same full vector) */
+template <typename T>
+void Solver<T>::set_weights(const double *weights, size_t num_points) {
+    LSSVM_REQUIRE(!in_cg_, "the weights cannot change between cg_begin and cg_finish");
+    if (weights != nullptr) {
+        LSSVM_REQUIRE(num_points == shards_[0]->N_, "expected " + std::to_string(shards_[0]->N_) + " weights (one per data point), but got " + std::to_string(num_points) + "!");
+        check_weights<T>(weights, num_points, shards_[0]->params_.cost);
+    }
+    for (auto &p : shards_) p->set_weights(weights);
+}
+
 template <typename T>
 void Solver<T>::matvec(const void *d, void *ret_inout, double add) {
     LSSVM_REQUIRE(d != nullptr && ret_inout != nullptr, "The d / ret arrays may not be empty!");              // csvm.cpp:284-286
@@ -162,7 +173,11 @@ void Solver<T>::matvec(const void *d, void *ret_inout, double add) {
     apply_K(Vec::tmp);
     for (auto &p : shards_) {
         p->activate();
-        hipLaunchKernelGGL(k_apply_ret<T>, dim3((p->n_ + 255) / 256), dim3(256), 0, p->stream(), p->Kres_, p->tmp_.p, p->q_.p, p->sc_.p, p->n_, p->inv_cost_, p->QA_cost_, add, p->Ad_.p);
+        if (p->weighted_) {
+            hipLaunchKernelGGL((k_apply_ret<T, true>), dim3((p->n_ + 255) / 256), dim3(256), 0, p->stream(), p->Kres_, p->tmp_.p, p->q_.p, p->sc_.p, p->n_, p->inv_cw_.p, p->QA_cost_, add, p->Ad_.p);
+        } else {
+            hipLaunchKernelGGL(k_apply_ret<T>, dim3((p->n_ + 255) / 256), dim3(256), 0, p->stream(), p->Kres_, p->tmp_.p, p->q_.p, p->sc_.p, p->n_, p->inv_cost_, p->QA_cost_, add, p->Ad_.p);
+        }
         LSSVM_HIP_CHECK(hipGetLastError());
     }
     Problem<T> &p0 = *shards_[0];
@@ -267,7 +282,11 @@ void Solver<T>::cg_begin(const void *y, double eps) {
     for (auto &p : shards_) {
         p->activate();
         hipStream_t st = p->stream();
-        hipLaunchKernelGGL(k_residual<T>, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, st, p->Kres_, p->x_.p, p->q_.p, p->b_.p, p->sc_.p, p->n_, p->inv_cost_, p->QA_cost_, p->r_.p, p->part(PART_RR));
+        if (p->weighted_) {
+            hipLaunchKernelGGL((k_residual<T, true>), dim3(RED_BLOCKS), dim3(RED_THREADS), 0, st, p->Kres_, p->x_.p, p->q_.p, p->b_.p, p->sc_.p, p->n_, p->inv_cw_.p, p->QA_cost_, p->r_.p, p->part(PART_RR));
+        } else {
+            hipLaunchKernelGGL(k_residual<T>, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, st, p->Kres_, p->x_.p, p->q_.p, p->b_.p, p->sc_.p, p->n_, p->inv_cost_, p->QA_cost_, p->r_.p, p->part(PART_RR));
+        }
         hipLaunchKernelGGL(k_finish_delta, dim3(1), dim3(RED_THREADS), 0, st, p->part(PART_RR), p->sc_.p, p->sc_.p + SC_COUNT - 1, 1);  // csvm.cpp:107-108
         // d = r   (csvm.cpp:111), and -- as partial sums that k_Ad_and_dAd finishes for itself -- the sums the next matvec's rank-1 terms need
         hipLaunchKernelGGL(k_update_d<T>, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, st, p->d_.p, p->r_.p, p->q_.p, p->sc_.p, p->n_, 1, p->part(PART_D), pack_with_direction(*p));
@@ -282,6 +301,7 @@ void Solver<T>::cg_begin(const void *y, double eps) {
     delta_before_ = 0.0;
     held_back_ = 0;
     begun_ = true;
+    in_cg_ = true;
     cg_wall_ms_ += now_ms() - t0;
 }
 
@@ -310,7 +330,11 @@ void Solver<T>::cg_step(uint64_t iterations, int *done_out) {
             p->activate();
             hipStream_t st = p->stream();
             // (every kernel of the chain reduces its predecessor's partial sums for itself -- finish2_in_block -- so no single-block kernel stands between them)
-            hipLaunchKernelGGL(k_Ad_and_dAd<T>, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, st, p->Kres_, p->d_.p, p->q_.p, p->part(PART_D), p->sc_.p, p->n_, p->inv_cost_, p->QA_cost_, p->Ad_.p, p->part(PART_DAD));
+            if (p->weighted_) {
+                hipLaunchKernelGGL((k_Ad_and_dAd<T, true>), dim3(RED_BLOCKS), dim3(RED_THREADS), 0, st, p->Kres_, p->d_.p, p->q_.p, p->part(PART_D), p->sc_.p, p->n_, p->inv_cw_.p, p->QA_cost_, p->Ad_.p, p->part(PART_DAD));
+            } else {
+                hipLaunchKernelGGL(k_Ad_and_dAd<T>, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, st, p->Kres_, p->d_.p, p->q_.p, p->part(PART_D), p->sc_.p, p->n_, p->inv_cost_, p->QA_cost_, p->Ad_.p, p->part(PART_DAD));
+            }
             // alpha = delta / d.Ad (csvm.cpp:135) ; x += alpha d ; r -= alpha Ad   (csvm.cpp:138, :148) -- or, every 50th iteration, x only and r = b - A x below (csvm.cpp:140-145)
             hipLaunchKernelGGL(k_update_x_r<T>, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, st, p->x_.p, p->r_.p, p->d_.p, p->Ad_.p, p->part(PART_DAD), p->sc_.p, p->n_, refresh ? 0 : 1, p->part(PART_RR));
             if (refresh) p->enqueue_sum_and_qdot(p->x_.p, SC_SUMX, SC_QX);
@@ -320,7 +344,12 @@ void Solver<T>::cg_step(uint64_t iterations, int *done_out) {
             apply_K(Vec::x);
             for (auto &p : shards_) {
                 p->activate();
-                hipLaunchKernelGGL(k_residual<T>, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, p->stream(), p->Kres_, p->x_.p, p->q_.p, p->b_.p, p->sc_.p, p->n_, p->inv_cost_, p->QA_cost_, p->r_.p, p->part(PART_RR));
+                if (p->weighted_) {
+                    hipLaunchKernelGGL((k_residual<T, true>), dim3(RED_BLOCKS), dim3(RED_THREADS), 0, p->stream(), p->Kres_, p->x_.p, p->q_.p, p->b_.p, p->sc_.p, p->n_, p->inv_cw_.p, p->QA_cost_, p->r_.p,
+                                       p->part(PART_RR));
+                } else {
+                    hipLaunchKernelGGL(k_residual<T>, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, p->stream(), p->Kres_, p->x_.p, p->q_.p, p->b_.p, p->sc_.p, p->n_, p->inv_cost_, p->QA_cost_, p->r_.p, p->part(PART_RR));
+                }
             }
         }
         for (auto &p : shards_) {
@@ -385,6 +414,7 @@ template <typename T>
 void Solver<T>::cg_finish(void *alpha_out, double *rho_out, lssvm_cg_info *info) {
     LSSVM_REQUIRE(begun_, "cg_finish called before cg_begin");
     LSSVM_REQUIRE(alpha_out != nullptr && rho_out != nullptr, "alpha_out / rho_out must not be NULL");
+    in_cg_ = false;
     const double t0 = now_ms();
     // bias = y_last + QA_cost * sum(x) - q^T x ; alpha_N = -sum(x) ; rho = -bias   (csvm.cpp:179-182)
     const bool check = shards_.size() > 1 && exchange_ != Exchange::none;

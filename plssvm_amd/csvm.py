@@ -18,6 +18,10 @@ from .parameter import KernelFunctionType, Parameter
 
 __all__ = ["CSVM", "MI355CSVM", "make_csvm", "BackendType", "TargetPlatform"]
 
+# plssvm::verbosity (logger.hpp), as far as this mirror logs: "full" prints the solve's summary line in fit (csvm.cpp:167-173); "quiet" (default) prints nothing.
+# The reference's Python SVC sets it from its `verbose` keyword (bindings/Python/sklearn.cpp:88-94), plssvm_amd.svc.SVC too.
+verbosity = "quiet"
+
 
 class BackendType(enum.Enum):
     """plssvm::backend_type (backend_types.hpp:30-43) + ``mi355``."""
@@ -72,20 +76,33 @@ class CSVM:
         return self.target_platform
 
     # --- fit / predict / score (csvm.hpp:263-375) ---
-    def fit(self, data: DataSet, epsilon: float = 0.001, max_iter: int | None = None) -> Model:
+    def fit(self, data: DataSet, epsilon: float = 0.001, max_iter: int | None = None, sample_weight=None) -> Model:
+        """csvm::fit (csvm.hpp:263-320).  ``sample_weight`` (no counterpart in the reference): one weight >= 0 per data point, scikit-learn's semantics -- the
+        weighted LS-SVM system (point i regularised by 1 / (C w_i)) over the points of weight > 0; points of weight 0 are left out of the solve and out of the
+        model.  The model is an ordinary one (file format, predict)."""
         if epsilon <= 0.0:
             raise InvalidParameterError(f"epsilon must be less than 0.0, but is {epsilon}!")  # csvm.hpp:283 (message verbatim)
         if max_iter is not None and max_iter <= 0:
             raise InvalidParameterError(f"max_iter must be greater than 0, but is {max_iter}!")  # csvm.hpp:291
         if not data.has_labels():
             raise InvalidParameterError("No labels given for training! Maybe the data is only usable for prediction?")  # csvm.hpp:298
+        weights = None
+        if sample_weight is not None:
+            data, weights = _drop_zero_weights(data, sample_weight)
         if max_iter is None:
             max_iter = data.num_data_points()  # csvm.hpp:269
         params = self.params.resolved(data.num_features())  # csvm.hpp:303-307
         t0 = time.perf_counter()
-        alpha, rho, info = self.solve_system_of_linear_equations(params, data.data(), data.mapped_labels(), epsilon, max_iter)
+        if weights is None:
+            alpha, rho, info = self.solve_system_of_linear_equations(params, data.data(), data.mapped_labels(), epsilon, max_iter)
+        else:
+            alpha, rho, info = self.solve_system_of_linear_equations(params, data.data(), data.mapped_labels(), epsilon, max_iter, sample_weight=weights)
         info["total_runtime_ms"] = (time.perf_counter() - t0) * 1e3  # cg/total_runtime (csvm.hpp:318-320)
         self.last_cg_info = info
+        if verbosity == "full":
+            its = int(info.get("iterations", 0))
+            print(f"Finished after {its}/{int(max_iter)} iterations with a residuum of {info.get('residuum', 0.0)} (target: {info.get('target_residuum', 0.0)}) and an average "
+                  f"iteration time of {info.get('avg_iteration_ms', 0.0):.3f}ms.", flush=True)
         return Model(params, data, alpha=alpha, rho=rho)
 
     def predict(self, model: Model, data: DataSet):
@@ -108,6 +125,24 @@ class CSVM:
         predicted = self.predict(model, data)
         correct = sum(1 for p, c in zip(predicted, data.labels()) if p == c)
         return correct / len(predicted)
+
+
+def _drop_zero_weights(data: DataSet, sample_weight):
+    """``(data of the points of weight > 0, their weights)``: scikit-learn's sample_weight semantics -- finite weights >= 0, a point of weight 0 takes no part."""
+    w = np.asarray(sample_weight, dtype=np.float64)
+    if w.shape != (data.num_data_points(),):
+        raise InvalidParameterError(f"The number of data points ({data.num_data_points()}) and the number of sample weights ({w.size}) must be the same!")
+    if not (np.all(np.isfinite(w)) and np.all(w >= 0.0)):
+        raise InvalidParameterError("Every sample weight must be finite and greater than or equal to 0.0!")
+    keep = np.flatnonzero(w > 0.0)
+    if keep.size == w.size:
+        return data, np.ascontiguousarray(w)
+    labels = data.labels()
+    kept_labels = [labels[i] for i in keep.tolist()]
+    if keep.size < 2 or len(set(kept_labels)) < 2:
+        raise InvalidParameterError(f"The points of weight > 0 ({keep.size} of {w.size}) must include at least two points of two different classes!")
+    kept = DataSet(data.data()[keep], kept_labels, real_type=data.real_type)
+    return kept, np.ascontiguousarray(w[keep])
 
 
 class MI355CSVM(CSVM):
@@ -142,9 +177,9 @@ class MI355CSVM(CSVM):
     def get_option(self, name: str) -> int:
         return self._options.get(name) if self._options is not None else _capi.get_option(name)
 
-    def solve_system_of_linear_equations(self, params, A, b, eps, max_iter):
+    def solve_system_of_linear_equations(self, params, A, b, eps, max_iter, sample_weight=None):
         # all devices of this process behind ONE call (gpu_csvm::solve_system_of_linear_equations_impl, gpu_csvm.hpp:477-654)
-        return backend.solve_system_of_linear_equations(params, A, b, eps, max_iter, num_devices=self.use_devices, options=self._options)
+        return backend.solve_system_of_linear_equations(params, A, b, eps, max_iter, num_devices=self.use_devices, options=self._options, sample_weight=sample_weight)
 
     def predict_values(self, params, support_vectors, alpha, rho, w, predict_points):
         return backend.predict_values(params, support_vectors, alpha, rho, w, predict_points, options=self._options)

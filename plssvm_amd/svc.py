@@ -1,10 +1,14 @@
-"""sklearn-like ``SVC`` on top of CSVM (the reference's bindings/Python/sklearn.cpp): fit(X, y) / predict / score /
-decision_function with the LS-SVM solver; only the parameters the LS-SVM path has are honoured."""
+"""scikit-learn ``SVC`` on top of CSVM, the counterpart of the reference's bindings/Python/sklearn.cpp: the same keywords, parameters and fitted attributes,
+with the LS-SVM solver behind ``fit``.  Beyond the reference: ``class_weight`` and ``sample_weight`` (the weighted LS-SVM system), ``get_params(deep)`` /
+``set_params`` in scikit-learn's contract (``clone``, ``GridSearchCV``, ``Pipeline``), ``dual_coef_`` / ``intercept_`` / ``coef_``, and ``decision_function``.
+
+An estimator that duck-types scikit-learn's protocol: scikit-learn itself is not needed to use it."""
 
 from __future__ import annotations
 
 import numpy as np
 
+from . import csvm as _csvm
 from .csvm import make_csvm
 from .data_set import DataSet
 from .exceptions import InvalidParameterError
@@ -12,12 +16,81 @@ from .parameter import Parameter
 
 __all__ = ["SVC"]
 
+# the keywords of the reference's constructor that it rejects (sklearn.cpp:52, :73-108): the same words here
+_NOT_IMPLEMENTED = ("shrinking", "probability", "cache_size", "decision_function_shape", "break_ties", "random_state")
+# what get_params reports: the reference's keys (sklearn.cpp:208-228) + class_weight + real_type
+_PARAM_NAMES = ("C", "kernel", "degree", "gamma", "coef0", "tol", "verbose", "max_iter", "class_weight", "real_type")
+
+
+def _not_fitted(name):
+    return AttributeError(f"'SVC' object has no attribute '{name}'")
+
+
+def _fitted_attribute(name, doc):
+    def get(self):
+        if self._fit is None:
+            raise _not_fitted(name)
+        return self._fit[name]
+    return property(get, doc=doc)
+
+
+def _not_implemented(name, what="attribute"):
+    def get(self):
+        raise AttributeError(f"'SVC' object has no {what} '{name}' (not implemented)")
+    return property(get)
+
+
+def _set_verbosity(verbose) -> None:
+    _csvm.verbosity = "full" if bool(verbose) else "quiet"  # sklearn.cpp:88-94
+
 
 class SVC:
-    def __init__(self, C=1.0, kernel="rbf", degree=3, gamma="scale_features", coef0=0.0, tol=1e-3, max_iter=-1, real_type=np.float64):
-        self.C, self.kernel, self.degree, self.gamma, self.coef0, self.tol, self.max_iter, self.real_type = C, kernel, degree, gamma, coef0, tol, max_iter, real_type
-        self.model_ = None
+    """C-support vector classification with the LS-SVM solver (two classes).  ``gamma``: a number, or any string for the PLSSVM default 1 / n_features.
+    ``class_weight``: None, ``"balanced"`` (n_samples / (n_classes * count(class))) or a dict {label: weight}; with ``sample_weight`` in ``fit``, point i is
+    regularised by 1 / (C * sample_weight[i] * class_weight[y[i]]) -- the weighted LS-SVM system -- and points of weight 0 take no part."""
+
+    def __init__(self, C=1.0, kernel="rbf", degree=3, gamma="scale_features", coef0=0.0, tol=1e-3, verbose=False, max_iter=-1, class_weight=None, real_type=np.float64,
+                 **kwargs):
+        for name in kwargs:
+            if name in _NOT_IMPLEMENTED:
+                raise AttributeError(f"The '{name}' parameter for a call to the 'SVC' constructor is not implemented yet!")
+            raise TypeError(f"SVC.__init__() got an unexpected keyword argument '{name}'")
+        # stored verbatim: sklearn.base.clone checks that the constructor keeps what get_params hands it
+        self.C, self.kernel, self.degree, self.gamma, self.coef0, self.tol = C, kernel, degree, gamma, coef0, tol
+        self.verbose, self.max_iter, self.class_weight, self.real_type = verbose, max_iter, class_weight, real_type
+        _set_verbosity(verbose)
         self._svm = None
+        self._model = None
+        self._fit = None
+
+    # ------------------------------------------------------------------ parameters (scikit-learn's estimator contract)
+    def get_params(self, deep=True):
+        """Parameters for this estimator (no nested estimators: ``deep`` changes nothing)."""
+        return {name: getattr(self, name) for name in _PARAM_NAMES}
+
+    def set_params(self, **params):
+        """Set the parameters of this estimator; returns self.  An unknown key raises ValueError, the keywords the reference rejects raise AttributeError."""
+        for name in params:
+            if name in _NOT_IMPLEMENTED:
+                raise AttributeError(f"The '{name}' parameter for a call to the 'SVC' constructor is not implemented yet!")
+            if name not in _PARAM_NAMES:
+                raise ValueError(f"Invalid parameter {name!r} for estimator SVC. Valid parameters are: {sorted(_PARAM_NAMES)!r}.")
+        for name, value in params.items():
+            setattr(self, name, value)
+        if "verbose" in params:
+            _set_verbosity(params["verbose"])
+        return self
+
+    _estimator_type = "classifier"  # (scikit-learn before 1.6)
+
+    def __sklearn_tags__(self):
+        """What scikit-learn's tooling asks of an estimator (is_classifier: stratified folds in GridSearchCV, ...); only scikit-learn calls this."""
+        from sklearn.utils import ClassifierTags, Tags, TargetTags
+
+        return Tags(estimator_type="classifier", target_tags=TargetTags(required=True), classifier_tags=ClassifierTags(multi_class=False))
+
+    def __repr__(self):
+        return "SVC(" + ", ".join(f"{k}={v!r}" for k, v in self.get_params().items()) + ")"
 
     def _params(self):
         if self.kernel not in ("linear", "poly", "polynomial", "rbf"):
@@ -25,23 +98,115 @@ class SVC:
         gamma = None if isinstance(self.gamma, str) else float(self.gamma)  # any string = the PLSSVM default 1 / n_features
         return Parameter(kernel_type=self.kernel, degree=self.degree, gamma=gamma, coef0=self.coef0, cost=self.C)
 
-    def fit(self, X, y):
-        self._svm = make_csvm(params=self._params())
-        data = DataSet(X, list(np.asarray(y).tolist()), real_type=self.real_type)
-        self.classes_ = np.array(data.different_labels())
-        self.model_ = self._svm.fit(data, epsilon=self.tol, max_iter=None if self.max_iter is None or self.max_iter < 0 else self.max_iter)
-        self.n_iter_ = int(self._svm.last_cg_info["iterations"])
+    def _class_weight(self, classes, y):
+        """The multiplier of each class (scikit-learn's compute_class_weight)."""
+        cw = self.class_weight
+        if cw is None:
+            return np.ones(len(classes))
+        if isinstance(cw, str):
+            if cw != "balanced":
+                raise InvalidParameterError(f'class_weight must be None, "balanced" or a dict, but is "{cw}"!')
+            counts = np.array([np.count_nonzero(y == c) for c in classes], dtype=np.float64)
+            return y.size / (len(classes) * counts)
+        if isinstance(cw, dict):
+            unknown = [k for k in cw if not np.any(classes == k)]
+            if unknown:
+                raise InvalidParameterError(f"The classes {unknown} of class_weight are not in the training labels {list(classes.tolist())}!")
+            return np.array([float(cw.get(c, 1.0)) for c in classes])
+        raise InvalidParameterError(f'class_weight must be None, "balanced" or a dict, but is {cw!r}!')
+
+    # ------------------------------------------------------------------ fit / predict / score
+    def fit(self, X, y, sample_weight=None):
+        """Fit the SVM model to the training data; ``sample_weight`` (one value >= 0 per point) times the class weight is the point's weight in the solve."""
+        X = np.asarray(X)
+        y = np.asarray(y)
+        if X.ndim != 2 or y.ndim != 1 or y.shape[0] != X.shape[0]:
+            raise InvalidParameterError(f"X must be a matrix and y a vector of as many labels as X has rows, but their shapes are {X.shape} and {y.shape}!")
+        params = self._params()
+        classes = np.array(sorted(set(y.tolist())))  # (the order of DataSet's label mapping)
+        class_weight = self._class_weight(classes, y)
+        weights = None
+        if sample_weight is not None or self.class_weight is not None:
+            sw = np.ones(y.size) if sample_weight is None else np.asarray(sample_weight, dtype=np.float64)
+            if sw.shape != y.shape:
+                raise InvalidParameterError(f"The number of data points ({y.size}) and the number of sample weights ({sw.size}) must be the same!")
+            weights = sw * class_weight[np.searchsorted(classes, y)]
+        svm = make_csvm(params=params)
+        data = DataSet(X, y.tolist(), real_type=self.real_type)
+        max_iter = None if self.max_iter is None or self.max_iter < 0 else self.max_iter
+        model = svm.fit(data, epsilon=self.tol, max_iter=max_iter, sample_weight=weights)
+        support = np.arange(y.size, dtype=np.int32) if weights is None else np.flatnonzero(weights > 0).astype(np.int32)
+        alpha = np.asarray(model.alpha)
+        sv_labels = np.asarray(model.labels())
+        nonzero = alpha != 0  # the reference's counting rule (sklearn.cpp:381-410): support vectors of non-zero weight, per class
+        self._svm, self._model = svm, model
+        self._fit = {
+            "classes_": np.array(data.different_labels()),
+            "class_weight_": class_weight,
+            "fit_status_": 0,
+            "n_features_in_": int(X.shape[1]),
+            "shape_fit_": tuple(int(v) for v in X.shape),
+            "n_iter_": int(svm.last_cg_info["iterations"]),
+            "support_": support,
+            "support_vectors_": model.support_vectors(),
+            "n_support_": np.array([np.count_nonzero(nonzero & (sv_labels == c)) for c in data.different_labels()], dtype=np.int32),
+            "dual_coef_": alpha.reshape(1, -1),
+            "intercept_": np.array([-model.rho], dtype=alpha.dtype),
+        }
         return self
 
+    def __sklearn_is_fitted__(self):
+        return self._fit is not None
+
+    def _check_fitted(self):
+        if self._fit is None:
+            raise AttributeError("This SVC instance is not fitted yet. Call 'fit' with appropriate arguments before using this estimator.")  # sklearn.cpp:236
+
     def decision_function(self, X):
-        m = self.model_
+        """sum_i dual_coef_[0, i] k(support_vectors_[i], x) + intercept_[0] for every row x of X (an extension: the reference's raises)."""
+        self._check_fitted()
+        m = self._model
         values, w = self._svm.predict_values(m.params, m.support_vectors(), m.alpha, float(m.rho), m.w, np.asarray(X, dtype=self.real_type))
         if w is not None:
             m.w = w
         return values
 
     def predict(self, X):
-        return np.where(self.decision_function(X) > 0, self.classes_[1], self.classes_[0])
+        """Perform classification on samples in X."""
+        classes = self.classes_
+        return np.where(self.decision_function(X) > 0, classes[1], classes[0])
 
-    def score(self, X, y):
-        return float(np.mean(self.predict(X) == np.asarray(y)))
+    def score(self, X, y, sample_weight=None):
+        """The (sample_weight-weighted) mean accuracy on the given test data and labels."""
+        return float(np.average(self.predict(X) == np.asarray(y), weights=sample_weight))
+
+    # ------------------------------------------------------------------ fitted attributes
+    classes_ = _fitted_attribute("classes_", "The class labels, ndarray of shape (n_classes,).")
+    class_weight_ = _fitted_attribute("class_weight_", "The multiplier of each class's weights, ndarray of shape (n_classes,).")
+    fit_status_ = _fitted_attribute("fit_status_", "0 if correctly fitted.")
+    n_features_in_ = _fitted_attribute("n_features_in_", "Number of features seen during fit.")
+    shape_fit_ = _fitted_attribute("shape_fit_", "Array dimensions of the training matrix X.")
+    n_iter_ = _fitted_attribute("n_iter_", "CG iterations of the solve.")
+    support_ = _fitted_attribute("support_", "Indices of the support vectors (every point of weight > 0), ndarray of shape (n_SV,).")
+    support_vectors_ = _fitted_attribute("support_vectors_", "Support vectors, ndarray of shape (n_SV, n_features).")
+    n_support_ = _fitted_attribute("n_support_", "Support vectors of non-zero dual coefficient per class, ndarray of shape (n_classes,), int32.")
+    dual_coef_ = _fitted_attribute("dual_coef_", "The dual coefficients alpha, ndarray of shape (1, n_SV).")
+    intercept_ = _fitted_attribute("intercept_", "The constant of the decision function (-rho), ndarray of shape (1,).")
+
+    @property
+    def coef_(self):
+        """The weights w of the features, ndarray of shape (1, n_features): linear kernel only."""
+        if self._fit is None:
+            raise _not_fitted("coef_")
+        if self._model.params.kernel_type != 0:
+            raise AttributeError("coef_ is only available when using a linear kernel")
+        if "coef_" not in self._fit:
+            from .backend import calculate_w
+            self._fit["coef_"] = calculate_w(self._model.support_vectors(), self._model.alpha).reshape(1, -1)
+        return self._fit["coef_"]
+
+    predict_proba = _not_implemented("predict_proba", "function")
+    predict_log_proba = _not_implemented("predict_log_proba", "function")
+    probA_ = _not_implemented("probA_")
+    probB_ = _not_implemented("probB_")
+    feature_names_in_ = _not_implemented("feature_names_in_")
