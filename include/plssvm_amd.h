@@ -102,13 +102,15 @@ typedef struct lssvm_cg_info {
 typedef struct lssvm_predict_info {
     double total_ms;   /* host wall clock of the call: uploads, data preparation, the product, the read-back */
     double setup_ms;   /* ... of which before the product kernel was enqueued (uploads of both point sets, centring, norms, operand planes) */
-    double kernel_ms;  /* device time of the kernel that evaluates the product (HIP events): the rectangular tile kernel, or w.x for the linear kernel */
+    double kernel_ms;  /* device time of the kernel that evaluates the product (HIP events): the rectangular tile kernel, or w.x for the linear kernel;
+                        * predict_values_multi: the sum over the product launches of the call */
     double rbf_exponent_scale; /* as lssvm_cg_info */
     double f16_row_rel_error;  /* as lssvm_cg_info, over support vectors and points */
     int32_t gram_mode;         /* as lssvm_cg_info */
     int32_t rbf_direct;        /* as lssvm_cg_info */
     int32_t resident;          /* lssvm_mi355_predictor_predict: 1 if the batch ran against the RESIDENT support vectors, 0 if it took the one-shot path (same result) */
-    int32_t reserved;
+    int32_t vectors_per_launch; /* lssvm_mi355_predict_values_multi_*: the largest number of weight vectors ONE launch of the product kernel evaluated (2 where the
+                                 * two-vector kernel ran, 1 on the per-vector paths); the single-vector entry points and the predictor write 0 */
 } lssvm_predict_info;
 
 /* ------------------------------------------------------------------------------------------------------------------ */
@@ -191,6 +193,23 @@ int lssvm_mi355_predict_values_f64(const lssvm_params *params, const double *sup
                                    size_t num_features, const double *alpha, double rho, double *w_inout, int *w_valid,
                                    const double *predict_points, size_t num_predict_points, double *out, lssvm_predict_info *info,
                                    const lssvm_mi355_options *options);
+
+/* predict_values for SEVERAL weight vectors over the same support vectors -- a one-vs-all multi-class model: classifier v is (alpha[v], rho[v]).
+ * Layout: alpha is num_vectors x num_support_vectors and out is num_predict_points x num_vectors, both row-major; rho has num_vectors entries; w_inout (linear kernel
+ * only) is num_vectors x num_features with ONE flag *w_valid for all of it.  Column v of out holds exactly the values lssvm_mi355_predict_values_* returns for
+ * alpha[v], rho[v] (the same operations in the same order, bit for bit); what the call saves is the work that does not depend on the weight vector: both point sets
+ * are uploaded and prepared once, and where the call is eligible for the rectangular 256-row kernel -- fp32, rbf / polynomial of degree 2 or 3, at most 128 features,
+ * a split Gram mode, at least 64 row blocks (8065 points) to predict, rbf within the folded form's range -- one pass over the Gram tiles feeds TWO weight vectors
+ * (ceil(num_vectors / 2) launches; lssvm_predict_info.vectors_per_launch == 2).  Everywhere else every vector has a product launch of its own on the shared
+ * preparation (vectors_per_launch == 1).  NULL alpha / rho / out or num_vectors == 0: LSSVM_ERR_INVALID_ARGUMENT, before a device is touched. */
+int lssvm_mi355_predict_values_multi_f32(const lssvm_params *params, const float *support_vectors, size_t num_support_vectors, size_t num_features,
+                                         const float *alpha, const float *rho, size_t num_vectors, float *w_inout, int *w_valid,
+                                         const float *predict_points, size_t num_predict_points, float *out, lssvm_predict_info *info,
+                                         const lssvm_mi355_options *options);
+int lssvm_mi355_predict_values_multi_f64(const lssvm_params *params, const double *support_vectors, size_t num_support_vectors, size_t num_features,
+                                         const double *alpha, const double *rho, size_t num_vectors, double *w_inout, int *w_valid,
+                                         const double *predict_points, size_t num_predict_points, double *out, lssvm_predict_info *info,
+                                         const lssvm_mi355_options *options);
 
 /* The same prediction with the MODEL RESIDENT in HBM across calls (no counterpart in the reference, whose predict_values uploads the support vectors on every call --
  * gpu_csvm.hpp:656-730 -- which is the whole cost of a small batch): `create` uploads the support vectors and prepares them once (centring, norms, operand planes,

@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = [
     "lssvm_mi355_abi_version", "lssvm_mi355_device_count", "lssvm_mi355_device_name", "lssvm_mi355_last_error",
     "lssvm_mi355_options_create", "lssvm_mi355_options_set", "lssvm_mi355_options_get", "lssvm_mi355_options_destroy",
     "lssvm_mi355_solve_f32", "lssvm_mi355_solve_f64", "lssvm_mi355_solve_multi_f32", "lssvm_mi355_solve_multi_f64", "lssvm_mi355_predict_values_f32", "lssvm_mi355_predict_values_f64",
+    "lssvm_mi355_predict_values_multi_f32", "lssvm_mi355_predict_values_multi_f64",
     "lssvm_mi355_solve_weighted_f32", "lssvm_mi355_solve_weighted_f64", "lssvm_mi355_problem_set_weights",
     "lssvm_mi355_predictor_create", "lssvm_mi355_predictor_predict", "lssvm_mi355_predictor_destroy",
     "lssvm_mi355_generate_q_f32", "lssvm_mi355_generate_q_f64", "lssvm_mi355_run_device_kernel_f32", "lssvm_mi355_run_device_kernel_f64",
@@ -63,12 +64,12 @@ class LssvmCgInfo(C.Structure):
 
 
 class LssvmPredictInfo(C.Structure):
-    """``lssvm_predict_info``: the timings of one ``predict_values`` call."""
+    """``lssvm_predict_info``: the timings of one ``predict_values`` call; ``vectors_per_launch``: what ``predict_values_multi`` reports (0 from every other call)."""
     _fields_ = [("total_ms", C.c_double), ("setup_ms", C.c_double), ("kernel_ms", C.c_double), ("rbf_exponent_scale", C.c_double), ("f16_row_rel_error", C.c_double),
-                ("gram_mode", C.c_int32), ("rbf_direct", C.c_int32), ("resident", C.c_int32), ("reserved", C.c_int32)]
+                ("gram_mode", C.c_int32), ("rbf_direct", C.c_int32), ("resident", C.c_int32), ("vectors_per_launch", C.c_int32)]
 
     def as_dict(self):
-        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+        return {name: getattr(self, name) for name, _ in self._fields_}
 
 
 class LssvmModelInfo(C.Structure):
@@ -107,6 +108,16 @@ def weighted_entry(name: str):
             ct = C.c_float if name.endswith("_f32") else C.c_double
             fn.argtypes = [C.POINTER(LssvmParams), C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.POINTER(C.c_double), ct, C.c_uint64, C.c_void_p, C.POINTER(ct),
                            C.POINTER(LssvmCgInfo), C.c_void_p]
+        fn.restype = C.c_int
+    return fn
+
+
+def predict_multi_entry(dtype):
+    """``lssvm_mi355_predict_values_multi_f32 / _f64`` with its argument types.  Bound at the first call, like the weighted entry points."""
+    fn = getattr(lib, f"lssvm_mi355_predict_values_multi_{suffix_of(dtype)}")
+    if fn.argtypes is None:
+        fn.argtypes = [C.POINTER(LssvmParams), C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_size_t,
+                       C.c_void_p, C.POINTER(LssvmPredictInfo), C.c_void_p]
         fn.restype = C.c_int
     return fn
 

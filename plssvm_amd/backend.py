@@ -5,6 +5,7 @@ reference's own (tests/backends/generic_csvm_tests.hpp):
 
     solve_system_of_linear_equations(params, A, b, eps, max_iter)   csvm.hpp:188-192
     predict_values(params, support_vectors, alpha, rho, w, points)  csvm.hpp:204-208
+    predict_values_multi(params, support_vectors, alphas, rhos, ws, points)   the same for k weight vectors over one set of support vectors (one-vs-all)
     generate_q(params, data)                                        gpu_csvm.hpp:349-384 / OpenMP csvm.cpp:232-251
     run_device_kernel(params, q, ret, d, data, QA_cost, add)        gpu_csvm.hpp:431-447 / OpenMP csvm.cpp:283-306
     calculate_w(support_vectors, alpha)                             gpu_csvm.hpp:386-429 / OpenMP csvm.cpp:255-280
@@ -23,7 +24,7 @@ from ._capi import LssvmCgInfo, LssvmParams, LssvmPredictInfo, LssvmShard, Optio
 from .exceptions import InvalidParameterError
 from .parameter import Parameter
 
-__all__ = ["Options", "Predictor", "solve_system_of_linear_equations", "predict_values", "generate_q", "run_device_kernel", "calculate_w", "ResidentProblem",
+__all__ = ["Options", "Predictor", "solve_system_of_linear_equations", "predict_values", "predict_values_multi", "generate_q", "run_device_kernel", "calculate_w", "ResidentProblem",
            "comm_get_unique_id", "comm_init", "comm_destroy"]
 
 
@@ -179,6 +180,40 @@ def predict_values(params: Parameter, support_vectors, alpha, rho: float, w, pre
     ps = _params_struct(params, nf)
     pinfo = LssvmPredictInfo()
     check(fn(C.byref(ps), ptr(sv), C.c_size_t(nsv), C.c_size_t(nf), ptr(alpha), ct(rho), ptr(w_buf), C.byref(w_valid), ptr(pts), C.c_size_t(pts.shape[0]), ptr(out), C.byref(pinfo), options_ptr(options)))
+    if info_out is not None:
+        info_out.update(pinfo.as_dict())
+    return out, (w_buf if w_valid.value else None)
+
+
+def predict_values_multi(params: Parameter, support_vectors, alphas, rhos, ws, predict_points, options: Options | None = None, info_out: dict | None = None):
+    """``predict_values`` for ``k`` weight vectors over the SAME support vectors (``lssvm_mi355_predict_values_multi_*``): ``alphas`` is ``k x num_support_vectors``,
+    ``rhos`` has ``k`` entries, ``ws`` is None or ``k x num_features`` (the cached w of the linear kernel).  Returns ``(values[num_points, k], ws)`` with ``ws`` None for the
+    polynomial / rbf kernels; column ``v`` equals ``predict_values(..., alphas[v], rhos[v], ...)`` bit for bit.  Both point sets are uploaded and prepared once;
+    ``info_out["vectors_per_launch"]`` says whether one pass over the Gram tiles fed two weight vectors (2) or every vector had a launch of its own (1)."""
+    sv = _as_matrix(support_vectors)
+    pts = _as_matrix(predict_points, dtype=sv.dtype)
+    alphas = np.ascontiguousarray(alphas, dtype=sv.dtype)
+    rhos = np.ascontiguousarray(rhos, dtype=sv.dtype)
+    nsv, nf = sv.shape
+    if alphas.ndim != 2 or alphas.shape[0] == 0:
+        raise InvalidParameterError("The weights must be a matrix with one row per weight vector and at least one row!")
+    k = alphas.shape[0]
+    if alphas.shape[1] != nsv:
+        raise InvalidParameterError(f"The number of support vectors ({nsv}) and number of weights ({alphas.shape[1]}) must be the same!")
+    if rhos.shape != (k,):
+        raise InvalidParameterError(f"The number of weight vectors ({k}) and the number of rho values ({rhos.size}) must be the same!")
+    if pts.shape[1] != nf:
+        raise InvalidParameterError(f"The number of features in the support vectors ({nf}) must be the same as in the data points to predict ({pts.shape[1]})!")
+    have_w = ws is not None and np.size(ws) != 0
+    if have_w and np.shape(ws) != (k, nf):
+        raise InvalidParameterError(f"Either w must be empty or contain one row of {nf} values per weight vector ({k}), but its shape is {np.shape(ws)}!")
+    w_valid = C.c_int(1 if have_w else 0)
+    w_buf = np.array(ws, dtype=sv.dtype, copy=True, order="C") if have_w else np.zeros((k, nf), dtype=sv.dtype)
+    out = np.zeros((pts.shape[0], k), dtype=sv.dtype)
+    ps = _params_struct(params, nf)
+    pinfo = LssvmPredictInfo()
+    check(_capi.predict_multi_entry(sv.dtype)(C.byref(ps), ptr(sv), nsv, nf, ptr(alphas), ptr(rhos), k, ptr(w_buf), C.byref(w_valid), ptr(pts), pts.shape[0], ptr(out),
+                                              C.byref(pinfo), options_ptr(options)))
     if info_out is not None:
         info_out.update(pinfo.as_dict())
     return out, (w_buf if w_valid.value else None)

@@ -187,6 +187,18 @@ void generate_q_one_shot(const lssvm_params *params, const T *X, size_t N, size_
     prob.get_q(q_out, nullptr);
 }
 
+/* the arguments of lssvm_mi355_predict_values_multi_* are checked here, before a device is touched */
+template <typename T>
+void predict_values_multi_checked(const lssvm_params *params, const T *sv, size_t nsv, size_t nfeat, const T *alpha, const T *rho, size_t nvec, T *w_inout, int *w_valid,
+                                         const T *points, size_t npoints, T *out, lssvm_predict_info *info, const lssvm_mi355_options *options) {
+    LSSVM_REQUIRE(params != nullptr, "params must not be NULL!");
+    LSSVM_REQUIRE(nvec > 0, "The number of weight vectors must be greater than 0!");
+    LSSVM_REQUIRE(alpha != nullptr, "The number of support vectors and number of weights must be the same!");  // csvm.cpp:192
+    LSSVM_REQUIRE(rho != nullptr, "rho must hold one value per weight vector");
+    LSSVM_REQUIRE(out != nullptr && w_valid != nullptr, "out / w_valid must not be NULL");
+    lssvm::predict_values_multi<T>(options_of(options), *params, sv, nsv, nfeat, alpha, rho, nvec, w_inout, w_valid, points, npoints, out, info);
+}
+
 }  // namespace
 
 extern "C" {
@@ -267,6 +279,16 @@ int lssvm_mi355_predict_values_f64(const lssvm_params *params, const double *sv,
         LSSVM_REQUIRE(params != nullptr, "params must not be NULL!");
         lssvm::predict_values<double>(options_of(options), *params, sv, nsv, nfeat, alpha, rho, w_inout, w_valid, points, npoints, out, info);
     });
+}
+
+static_assert(sizeof(lssvm_predict_info) == 56, "lssvm_predict_info changed: bump PLSSVM_AMD_ABI_VERSION and plssvm_amd/_capi.py (LssvmPredictInfo) with it");
+int lssvm_mi355_predict_values_multi_f32(const lssvm_params *params, const float *sv, size_t nsv, size_t nfeat, const float *alpha, const float *rho, size_t nvec, float *w_inout,
+                                         int *w_valid, const float *points, size_t npoints, float *out, lssvm_predict_info *info, const lssvm_mi355_options *options) {
+    return guarded([&] { predict_values_multi_checked<float>(params, sv, nsv, nfeat, alpha, rho, nvec, w_inout, w_valid, points, npoints, out, info, options); });
+}
+int lssvm_mi355_predict_values_multi_f64(const lssvm_params *params, const double *sv, size_t nsv, size_t nfeat, const double *alpha, const double *rho, size_t nvec, double *w_inout,
+                                         int *w_valid, const double *points, size_t npoints, double *out, lssvm_predict_info *info, const lssvm_mi355_options *options) {
+    return guarded([&] { predict_values_multi_checked<double>(params, sv, nsv, nfeat, alpha, rho, nvec, w_inout, w_valid, points, npoints, out, info, options); });
 }
 
 struct lssvm_mi355_predictor {

@@ -58,6 +58,24 @@ __global__ void k_pack_dc(const float *__restrict__ dvec, const float *__restric
 }
 #endif  // LSSVM_KERNELS_SETUP
 
+/* TWO weight vectors in one record (the rectangular 256-row kernel with NV = 2, predict_values_multi): dc[jt][0..127] = d0 of tile jt, dc[jt][128..255] = d1; folded
+ * != 0: both times 2^c_j -- per vector the value k_pack_dc writes into the first half of its record */
+#ifdef LSSVM_KERNELS_SETUP
+__global__ void k_pack_dc2(const float *__restrict__ dvec0, const float *__restrict__ dvec1, const float *__restrict__ cc, int ncols_padded, float *__restrict__ dc, int folded) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= ncols_padded) return;
+    const int jt = j >> 7, l = j & 127;
+    if (folded) {
+        const float e = __builtin_amdgcn_exp2f((cc != nullptr) ? cc[j] : 0.0f);
+        dc[static_cast<size_t>(jt) * 256 + l] = e * dvec0[j];
+        dc[static_cast<size_t>(jt) * 256 + 128 + l] = e * dvec1[j];
+    } else {
+        dc[static_cast<size_t>(jt) * 256 + l] = dvec0[j];
+        dc[static_cast<size_t>(jt) * 256 + 128 + l] = dvec1[j];
+    }
+}
+#endif  // LSSVM_KERNELS_SETUP
+
 /* operand planes [nplanes][rows][ldx16] (row-major, rows a multiple of 16, ldx16 of 64) -> the same data with every block of 16 rows x 32 features stored
  * as ONE MFMA A fragment (64 lanes x 8 halfs, lane 16 g + r holding features 8 g .. 8 g + 7 of row r), ordered
  * [plane][ldx16 / 64 chunks][rows / 16 blocks][2 k32 steps][64 lanes][8]: the 64-feature chunk OUTERMOST, so that the sixteen row blocks a workgroup
@@ -543,7 +561,7 @@ __global__ void k_calculate_w_stage2(const double *__restrict__ part, int nblock
 }
 /* out_p = w . x_p - rho  (linear predict, csvm.cpp:213): L lanes per point, 16-byte loads, the lanes' partial chains added by a butterfly */
 template <typename T, int L>
-__global__ void k_predict_linear_rows(const T *__restrict__ P, int ldx, int npoints, const T *__restrict__ w, T rho, T *__restrict__ out) {
+__global__ void k_predict_linear_rows(const T *__restrict__ P, int ldx, int npoints, const T *__restrict__ w, T rho, T *__restrict__ out, int out_stride) {
     constexpr int V = 16 / static_cast<int>(sizeof(T));
     using vec = T __attribute__((ext_vector_type(V)));
     const int sub = threadIdx.x % L;
@@ -560,13 +578,13 @@ __global__ void k_predict_linear_rows(const T *__restrict__ P, int ldx, int npoi
     }
 #pragma unroll
     for (int off = L / 2; off > 0; off >>= 1) s += __shfl_xor(s, off);
-    if (p < npoints && sub == 0) out[p] = s - rho;
+    if (p < npoints && sub == 0) out[static_cast<size_t>(p) * out_stride] = s - rho;
 }
-/* out_p = Kv_p - rho */
+/* out_p = Kv_p - rho; values `out_stride` apart: column v of a row-major num_points x num_vectors matrix (predict_values_multi), or 1 */
 template <typename T>
-__global__ void k_sub_rho(const T *__restrict__ Kv, int n, T rho, T *__restrict__ out) {
+__global__ void k_sub_rho(const T *__restrict__ Kv, int n, T rho, T *__restrict__ out, int out_stride) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = Kv[i] - rho;
+    if (i < n) out[static_cast<size_t>(i) * out_stride] = Kv[i] - rho;
 }
 
 }  // namespace lssvm

@@ -57,7 +57,7 @@ static void setup_rect_launch(TileArgs<float> &ta, RectSetup &rs, const PlaneSet
 /* out_p = w . x_p - rho: one pass over the points, HBM bound.  A group of L lanes (a power of two, at most 64) owns a point and reads its row in 16-byte pieces, so
  * that a wave's load instruction covers 1 KiB of consecutive memory wherever a row has at least 16 bytes x L. */
 template <typename T>
-static void launch_predict_linear(const DeviceMatrix<T> &P, const T *w, T rho, T *out, hipStream_t s) {
+static void launch_predict_linear(const DeviceMatrix<T> &P, const T *w, T rho, T *out, hipStream_t s, int out_stride = 1) {
     constexpr int V = 16 / static_cast<int>(sizeof(T));  // elements per 16-byte piece
     const int pieces = P.ldx / V;                         // (ldx is a multiple of the k-chunk: 32 floats / 16 doubles)
     int L = 1;
@@ -65,16 +65,18 @@ static void launch_predict_linear(const DeviceMatrix<T> &P, const T *w, T rho, T
     const int rows_per_block = 256 / L;
     const dim3 grid(static_cast<unsigned>((P.rows + rows_per_block - 1) / rows_per_block));
     switch (L) {
-        case 4: hipLaunchKernelGGL((k_predict_linear_rows<T, 4>), grid, dim3(256), 0, s, P.data.p, P.ldx, P.rows, w, rho, out); break;
-        case 8: hipLaunchKernelGGL((k_predict_linear_rows<T, 8>), grid, dim3(256), 0, s, P.data.p, P.ldx, P.rows, w, rho, out); break;
-        case 16: hipLaunchKernelGGL((k_predict_linear_rows<T, 16>), grid, dim3(256), 0, s, P.data.p, P.ldx, P.rows, w, rho, out); break;
-        case 32: hipLaunchKernelGGL((k_predict_linear_rows<T, 32>), grid, dim3(256), 0, s, P.data.p, P.ldx, P.rows, w, rho, out); break;
-        default: hipLaunchKernelGGL((k_predict_linear_rows<T, 64>), grid, dim3(256), 0, s, P.data.p, P.ldx, P.rows, w, rho, out); break;
+        case 4: hipLaunchKernelGGL((k_predict_linear_rows<T, 4>), grid, dim3(256), 0, s, P.data.p, P.ldx, P.rows, w, rho, out, out_stride); break;
+        case 8: hipLaunchKernelGGL((k_predict_linear_rows<T, 8>), grid, dim3(256), 0, s, P.data.p, P.ldx, P.rows, w, rho, out, out_stride); break;
+        case 16: hipLaunchKernelGGL((k_predict_linear_rows<T, 16>), grid, dim3(256), 0, s, P.data.p, P.ldx, P.rows, w, rho, out, out_stride); break;
+        case 32: hipLaunchKernelGGL((k_predict_linear_rows<T, 32>), grid, dim3(256), 0, s, P.data.p, P.ldx, P.rows, w, rho, out, out_stride); break;
+        default: hipLaunchKernelGGL((k_predict_linear_rows<T, 64>), grid, dim3(256), 0, s, P.data.p, P.ldx, P.rows, w, rho, out, out_stride); break;
     }
 }
 
+/* w_v = sum_i alpha_v,i sv_i for `nvec` weight vectors (alpha [nvec][nsv], w_out [nvec][nfeat]): the support vectors are uploaded once, every vector runs the two stages of
+ * calculate_w on them */
 template <typename T>
-void calculate_w(const T *sv, size_t nsv, size_t nfeat, const T *alpha, T *w_out) {
+static void calculate_w_multi(const T *sv, size_t nsv, size_t nfeat, const T *alpha, size_t nvec, T *w_out) {
     LSSVM_REQUIRE(sv != nullptr && nsv > 0, "The support vectors may not be empty!");                       // csvm.cpp:256
     LSSVM_REQUIRE(nfeat > 0, "Each support vector must at least contain one feature!");                     // csvm.cpp:257
     LSSVM_REQUIRE(alpha != nullptr && w_out != nullptr, "The alpha array may not be empty!");               // csvm.cpp:259
@@ -83,26 +85,36 @@ void calculate_w(const T *sv, size_t nsv, size_t nfeat, const T *alpha, T *w_out
     DeviceMatrix<T> S;
     S.upload(sv, LSSVM_MEM_HOST, nsv, nfeat, 0, s);
     DevBuf<T> a, w;
-    a.alloc_zero(nsv, s);
-    w.alloc_zero(nfeat, s);
-    LSSVM_HIP_CHECK(hipMemcpyAsync(a.p, alpha, nsv * sizeof(T), hipMemcpyHostToDevice, s));
+    a.alloc_zero(nvec * nsv, s);
+    w.alloc_zero(nvec * nfeat, s);
+    LSSVM_HIP_CHECK(hipMemcpyAsync(a.p, alpha, nvec * nsv * sizeof(T), hipMemcpyHostToDevice, s));
     // w[f] = sum_i alpha_i sv[i][f]: partial sums over blocks of 256 support vectors (coalesced across the features), then the blocks in order -- the reference's chain
     // (csvm.cpp:255-280) is one sequential fma chain per feature; 128 threads walking 50 000 rows each took 10 ms where the matrix is read in 10 us
     const int rows_per_block = 256;
     const int nblocks = (S.rows + rows_per_block - 1) / rows_per_block;
     DevBuf<double> part;
     part.alloc_zero(static_cast<size_t>(nblocks) * S.ldx, s);
-    hipLaunchKernelGGL(k_calculate_w_stage1<T>, dim3(nblocks, (S.ldx + 255) / 256), dim3(256), 0, s, S.data.p, S.ldx, S.rows, rows_per_block, a.p, part.p);
-    hipLaunchKernelGGL(k_calculate_w_stage2<T>, dim3((S.dfeat + 255) / 256), dim3(256), 0, s, part.p, nblocks, S.ldx, S.dfeat, w.p);
+    for (size_t v = 0; v < nvec; ++v) {
+        hipLaunchKernelGGL(k_calculate_w_stage1<T>, dim3(nblocks, (S.ldx + 255) / 256), dim3(256), 0, s, S.data.p, S.ldx, S.rows, rows_per_block, a.p + v * nsv, part.p);
+        hipLaunchKernelGGL(k_calculate_w_stage2<T>, dim3((S.dfeat + 255) / 256), dim3(256), 0, s, part.p, nblocks, S.ldx, S.dfeat, w.p + v * nfeat);
+    }
     LSSVM_HIP_CHECK(hipGetLastError());
-    LSSVM_HIP_CHECK(hipMemcpyAsync(w_out, w.p, nfeat * sizeof(T), hipMemcpyDeviceToHost, s));
+    LSSVM_HIP_CHECK(hipMemcpyAsync(w_out, w.p, nvec * nfeat * sizeof(T), hipMemcpyDeviceToHost, s));
     LSSVM_HIP_CHECK(hipStreamSynchronize(s));
 }
-
 template <typename T>
-static void predict_values_impl(const Options &opt, const lssvm_params &params, const T *sv, size_t nsv, size_t nfeat, const T *alpha, T rho, T *w_inout, int *w_valid, const T *points,
-                                size_t npoints, T *out, lssvm_predict_info &info) {
+void calculate_w(const T *sv, size_t nsv, size_t nfeat, const T *alpha, T *w_out) {
+    calculate_w_multi<T>(sv, nsv, nfeat, alpha, 1, w_out);
+}
+
+/* `nvec` weight vectors over the same support vectors: alpha [nvec][nsv], rho [nvec], w_inout [nvec][nfeat], out [npoints][nvec] (nvec = 1: predict_values).  Everything up
+ * to the records of the weight vectors is done once; `repeat`: extra untimed launches of the product in front of the timed one (predict_values' measurement aid). */
+template <typename T>
+static void predict_values_impl(const Options &opt, const lssvm_params &params, const T *sv, size_t nsv, size_t nfeat, const T *alpha, const T *rho, size_t nvec, T *w_inout, int *w_valid,
+                                const T *points, size_t npoints, T *out, lssvm_predict_info &info, int repeat) {
     check_params(&params);
+    LSSVM_REQUIRE(nvec > 0 && rho != nullptr, "predict_values needs at least one weight vector and its rho");
+    LSSVM_REQUIRE(nvec <= static_cast<size_t>(1) << 20, "too many weight vectors");
     LSSVM_REQUIRE(sv != nullptr && nsv > 0, "The support vectors must not be empty!");                       // csvm.cpp:189
     LSSVM_REQUIRE(nfeat > 0, "The support vectors must contain at least one feature!");                      // csvm.cpp:190
     LSSVM_REQUIRE(alpha != nullptr, "The number of support vectors and number of weights must be the same!");  // csvm.cpp:192
@@ -111,12 +123,29 @@ static void predict_values_impl(const Options &opt, const lssvm_params &params, 
     select_device_checked(0);
     hipStream_t s = nullptr;
     const double t0 = now_ms();
-    Event ev_a, ev_b;  // around the kernel that does the product (what the reference times as "predict", gpu_csvm.hpp:656-730, is the whole call: total_ms)
-    ev_a.create(true);
-    ev_b.create(true);
+    // around every launch of the kernel that does the product (what the reference times as "predict", gpu_csvm.hpp:656-730, is the whole call: total_ms)
+    std::vector<Event> evs;
+    const auto timed = [&](auto &&launch) {
+        evs.emplace_back();
+        evs.emplace_back();
+        const size_t k = evs.size() - 2;
+        evs[k].create(true);
+        evs[k + 1].create(true);
+        LSSVM_HIP_CHECK(hipEventRecord(evs[k].e, s));
+        launch();
+        LSSVM_HIP_CHECK(hipEventRecord(evs[k + 1].e, s));
+    };
+    evs.reserve(2 * nvec);
+    const int nv = static_cast<int>(nvec);
     const auto finish_info = [&](double t_kernel_enqueued) {
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, ev_a.e, ev_b.e) == hipSuccess) info.kernel_ms = ms;
+        double sum = 0.0;
+        bool ok = !evs.empty();
+        for (size_t k = 0; k + 1 < evs.size(); k += 2) {
+            float ms = 0.0f;
+            ok = ok && hipEventElapsedTime(&ms, evs[k].e, evs[k + 1].e) == hipSuccess;
+            sum += ms;
+        }
+        if (ok) info.kernel_ms = sum;
         info.total_ms = now_ms() - t0;
         info.setup_ms = t_kernel_enqueued - t0;
     };
@@ -124,24 +153,23 @@ static void predict_values_impl(const Options &opt, const lssvm_params &params, 
     if (params.kernel_type == LSSVM_KERNEL_LINEAR) {
         LSSVM_REQUIRE(w_inout != nullptr, "w must have num_features entries for the linear kernel");
         if (!*w_valid) {  // csvm.cpp:204-207
-            calculate_w<T>(sv, nsv, nfeat, alpha, w_inout);
+            calculate_w_multi<T>(sv, nsv, nfeat, alpha, nvec, w_inout);
             *w_valid = 1;
         }
         DeviceMatrix<T> P;
         P.upload(points, LSSVM_MEM_HOST, npoints, nfeat, 0, s);
         DevBuf<T> w, o;
-        w.alloc_zero(static_cast<size_t>(P.ldx), s);  // (zero padded like the points' rows: the kernel reads whole 16-byte pieces)
-        o.alloc_zero(npoints, s);
-        LSSVM_HIP_CHECK(hipMemcpyAsync(w.p, w_inout, nfeat * sizeof(T), hipMemcpyHostToDevice, s));
+        w.alloc_zero(nvec * static_cast<size_t>(P.ldx), s);  // (zero padded like the points' rows: the kernel reads whole 16-byte pieces)
+        o.alloc_zero(npoints * nvec, s);
+        LSSVM_HIP_CHECK(hipMemcpy2DAsync(w.p, static_cast<size_t>(P.ldx) * sizeof(T), w_inout, nfeat * sizeof(T), nfeat * sizeof(T), nvec, hipMemcpyHostToDevice, s));
         LSSVM_HIP_CHECK(hipStreamSynchronize(s));
         const double t_kernel = now_ms();
-        LSSVM_HIP_CHECK(hipEventRecord(ev_a.e, s));
-        launch_predict_linear<T>(P, w.p, rho, o.p, s);
-        LSSVM_HIP_CHECK(hipEventRecord(ev_b.e, s));
+        for (int v = 0; v < nv; ++v) timed([&] { launch_predict_linear<T>(P, w.p + static_cast<size_t>(v) * P.ldx, rho[v], o.p + v, s, nv); });
         LSSVM_HIP_CHECK(hipGetLastError());
-        LSSVM_HIP_CHECK(hipMemcpyAsync(out, o.p, npoints * sizeof(T), hipMemcpyDeviceToHost, s));
+        LSSVM_HIP_CHECK(hipMemcpyAsync(out, o.p, npoints * nvec * sizeof(T), hipMemcpyDeviceToHost, s));
         LSSVM_HIP_CHECK(hipStreamSynchronize(s));
         finish_info(t_kernel);
+        info.vectors_per_launch = 1;
         return;
     }
 
@@ -219,12 +247,15 @@ static void predict_values_impl(const Options &opt, const lssvm_params &params, 
                              ? static_cast<int>(opt.j_chunk_tiles)
                              : (rect ? static_cast<int>(rect_tiles) : static_cast<int>(std::min<long>(16, std::max<long>(2, (static_cast<long>(num_ib) * num_jt + 2048) / 4096))));
     const int num_jc = (num_jt + jc_tiles - 1) / jc_tiles;
+    // the rectangular 256-row kernel takes the weight vectors two per pass (NV = 2: one evaluation of the Gram tile feeds both), an odd last one alone
+    const int per_launch = (rect && nv >= 2) ? 2 : 1;
+    const size_t part_plane = static_cast<size_t>(num_jc) * P.rows_alloc;
     DevBuf<T> a, partial, Kv, o;
-    a.alloc_zero(S.rows_alloc, s);
-    partial.alloc_zero(static_cast<size_t>(num_jc) * P.rows_alloc, s);
+    a.alloc_zero(nvec * S.rows_alloc, s);  // [nvec][rows_alloc], exact zeros beyond the support vectors
+    partial.alloc_zero(per_launch * part_plane, s);
     Kv.alloc_zero(P.rows_alloc, s);
-    o.alloc_zero(npoints, s);
-    LSSVM_HIP_CHECK(hipMemcpyAsync(a.p, alpha, nsv * sizeof(T), hipMemcpyHostToDevice, s));
+    o.alloc_zero(npoints * nvec, s);
+    LSSVM_HIP_CHECK(hipMemcpy2DAsync(a.p, static_cast<size_t>(S.rows_alloc) * sizeof(T), alpha, nsv * sizeof(T), nsv * sizeof(T), nvec, hipMemcpyHostToDevice, s));
 
     TileArgs<T> ta{};
     ta.Xr = P.data.p;
@@ -235,14 +266,23 @@ static void predict_values_impl(const Options &opt, const lssvm_params &params, 
     // rectangular instance of the tile kernel (full square variant): the v2 kernel when the feature count allows, with the
     // (alpha_j | c_j) records of the support vectors packed for its LDS-DMA
     DevBuf<T> dc;
-    if (v2 && !(std::is_same_v<T, double> && params.kernel_type == LSSVM_KERNEL_POLYNOMIAL && !poly_prescaled)) {
-        dc.alloc_zero(static_cast<size_t>(num_jt) * 256, s);
-        const int ncols = num_jt * TILE;
+    const int ncols = num_jt * TILE;
+    const bool records = v2 && !(std::is_same_v<T, double> && params.kernel_type == LSSVM_KERNEL_POLYNOMIAL && !poly_prescaled);
+    const auto pack_records = [&](int v, int count) {  // the records of the weight vectors v (, v + 1) of the next launch
+        if (!records) return;
         if constexpr (std::is_same_v<T, float>) {
-            enqueue_pack_records(a.p, cS.p, ncols, dc.p, rbf_grid ? 2 : dc_folded, rbf_grid ? eS.p : static_cast<const float *>(nullptr), s);
+            if (count == 2) {
+                enqueue_pack_records2(a.p + static_cast<size_t>(v) * S.rows_alloc, a.p + static_cast<size_t>(v + 1) * S.rows_alloc, cS.p, ncols, dc.p, dc_folded, s);
+            } else {
+                enqueue_pack_records(a.p + static_cast<size_t>(v) * S.rows_alloc, cS.p, ncols, dc.p, rbf_grid ? 2 : dc_folded, rbf_grid ? eS.p : static_cast<const float *>(nullptr), s);
+            }
         } else {
-            enqueue_pack_records(a.p, cS.p, ncols, dc.p, 0, static_cast<const double *>(nullptr), s);
+            enqueue_pack_records(a.p + static_cast<size_t>(v) * S.rows_alloc, cS.p, ncols, dc.p, 0, static_cast<const double *>(nullptr), s);
         }
+    };
+    if (records) {
+        dc.alloc_zero(static_cast<size_t>(num_jt) * 256, s);
+        pack_records(0, per_launch);
     }
     ta.dc = dc.p;
     ta.dc_folded = dc_folded;
@@ -273,23 +313,31 @@ static void predict_values_impl(const Options &opt, const lssvm_params &params, 
     }
     LSSVM_HIP_CHECK(hipStreamSynchronize(s));
     const double t_kernel = now_ms();
-    // (measurement aid: LSSVM_MI355_PREDICT_REPEAT=k in the environment launches the product kernel k times -- it overwrites its slabs, the result is the same -- and times
-    // the LAST launch: what the kernel takes once the chip's clocks have settled, beside the first launch after the set-up's idle gaps that a single call measures)
-    int repeat = 1;
-    if (const char *rep = std::getenv("LSSVM_MI355_PREDICT_REPEAT"); rep != nullptr) repeat = std::min(std::max(std::atoi(rep), 1), 64);
+    // (`repeat` launches of the product kernel -- it overwrites its slabs, the result is the same -- of which the LAST is timed: predict_values' measurement aid)
     for (int k = 0; k + 1 < repeat; ++k) {
         launch_tile_kernel<T>(ta, params.kernel_type, rbf_direct, num_jc, s);
         if (ta.queue != nullptr) std::swap(ta.queue, ta.queue_next);  // (a persistent launch zeroes the OTHER set of counters)
     }
-    LSSVM_HIP_CHECK(hipEventRecord(ev_a.e, s));
-    launch_tile_kernel<T>(ta, params.kernel_type, rbf_direct, num_jc, s);
-    LSSVM_HIP_CHECK(hipEventRecord(ev_b.e, s));
-    hipLaunchKernelGGL(k_reduce_partials<T>, dim3((P.rows_alloc + 255) / 256), dim3(256), 0, s, partial.p, ta.part_stride, num_jc, 0, P.rows_alloc, Kv.p);
-    hipLaunchKernelGGL(k_sub_rho<T>, dim3((P.rows + 255) / 256), dim3(256), 0, s, Kv.p, P.rows, rho, o.p);
+    for (int v = 0; v < nv; v += per_launch) {
+        const int count = std::min(per_launch, nv - v);
+        if (v > 0) {  // (the records of the first launch were packed before the set-up was drained)
+            pack_records(v, count);
+            ta.dvec = a.p + static_cast<size_t>(v) * S.rows_alloc;
+            if (ta.queue != nullptr) std::swap(ta.queue, ta.queue_next);
+        }
+        ta.nvec = count;
+        ta.part_vstride = count == 2 ? static_cast<long>(part_plane) : 0;
+        timed([&] { launch_tile_kernel<T>(ta, params.kernel_type, rbf_direct, num_jc, s); });
+        for (int u = 0; u < count; ++u) {
+            hipLaunchKernelGGL(k_reduce_partials<T>, dim3((P.rows_alloc + 255) / 256), dim3(256), 0, s, partial.p + u * part_plane, ta.part_stride, num_jc, 0, P.rows_alloc, Kv.p);
+            hipLaunchKernelGGL(k_sub_rho<T>, dim3((P.rows + 255) / 256), dim3(256), 0, s, Kv.p, P.rows, rho[v + u], o.p + (v + u), nv);
+        }
+    }
     LSSVM_HIP_CHECK(hipGetLastError());
-    LSSVM_HIP_CHECK(hipMemcpyAsync(out, o.p, npoints * sizeof(T), hipMemcpyDeviceToHost, s));
+    LSSVM_HIP_CHECK(hipMemcpyAsync(out, o.p, npoints * nvec * sizeof(T), hipMemcpyDeviceToHost, s));
     LSSVM_HIP_CHECK(hipStreamSynchronize(s));
     finish_info(t_kernel);
+    info.vectors_per_launch = per_launch;
     info.gram_mode = (planesS.mode != 0 && dc.p != nullptr) ? (rbf_grid ? 3 : planesS.mode) : 0;
     info.rbf_direct = rbf_direct ? 1 : 0;
     info.rbf_exponent_scale = rbf_r2;
@@ -299,25 +347,48 @@ static void predict_values_impl(const Options &opt, const lssvm_params &params, 
 /* csvm::predict_values behind the C ABI.  fp32 rbf with rbf_form 0: where the grid planes chosen from the exponent scale do not represent the data, the call runs
  * again on the formula-exact kernel (as Solver's constructor does for the training problem). */
 template <typename T>
-void predict_values(const Options &opt, const lssvm_params &params, const T *sv, size_t nsv, size_t nfeat, const T *alpha, T rho, T *w_inout, int *w_valid, const T *points,
-                    size_t npoints, T *out, lssvm_predict_info *info) {
-    lssvm_predict_info local{};
+static void predict_values_retrying(const Options &opt, const lssvm_params &params, const T *sv, size_t nsv, size_t nfeat, const T *alpha, const T *rho, size_t nvec, T *w_inout,
+                                    int *w_valid, const T *points, size_t npoints, T *out, lssvm_predict_info &local, int repeat) {
+    local = lssvm_predict_info{};
     local.f16_row_rel_error = -1.0;
     try {
-        predict_values_impl<T>(opt, params, sv, nsv, nfeat, alpha, rho, w_inout, w_valid, points, npoints, out, local);
+        predict_values_impl<T>(opt, params, sv, nsv, nfeat, alpha, rho, nvec, w_inout, w_valid, points, npoints, out, local, repeat);
     } catch (const GridPlanesUnfit &) {
         if (opt.rbf_form != 0) throw;
         Options direct = opt;
         direct.rbf_form = 1;
         local = lssvm_predict_info{};
         local.f16_row_rel_error = -1.0;
-        predict_values_impl<T>(direct, params, sv, nsv, nfeat, alpha, rho, w_inout, w_valid, points, npoints, out, local);
+        predict_values_impl<T>(direct, params, sv, nsv, nfeat, alpha, rho, nvec, w_inout, w_valid, points, npoints, out, local, repeat);
     }
+}
+template <typename T>
+void predict_values(const Options &opt, const lssvm_params &params, const T *sv, size_t nsv, size_t nfeat, const T *alpha, T rho, T *w_inout, int *w_valid, const T *points,
+                    size_t npoints, T *out, lssvm_predict_info *info) {
+    // (measurement aid: LSSVM_MI355_PREDICT_REPEAT=k in the environment launches the product kernel k times and times the LAST launch: what the kernel takes once the
+    // chip's clocks have settled, beside the first launch after the set-up's idle gaps that a single call measures)
+    int repeat = 1;
+    if (const char *rep = std::getenv("LSSVM_MI355_PREDICT_REPEAT"); rep != nullptr) repeat = std::min(std::max(std::atoi(rep), 1), 64);
+    lssvm_predict_info local{};
+    predict_values_retrying<T>(opt, params, sv, nsv, nfeat, alpha, &rho, 1, w_inout, w_valid, points, npoints, out, local, repeat);
+    local.vectors_per_launch = 0;  // (vectors_per_launch is predict_values_multi's report)
+    if (info != nullptr) *info = local;
+}
+/* the GridPlanesUnfit retry applies to the whole call: every weight vector runs on the same kernel */
+template <typename T>
+void predict_values_multi(const Options &opt, const lssvm_params &params, const T *sv, size_t nsv, size_t nfeat, const T *alpha, const T *rho, size_t nvec, T *w_inout, int *w_valid,
+                          const T *points, size_t npoints, T *out, lssvm_predict_info *info) {
+    lssvm_predict_info local{};
+    predict_values_retrying<T>(opt, params, sv, nsv, nfeat, alpha, rho, nvec, w_inout, w_valid, points, npoints, out, local, 1);
     if (info != nullptr) *info = local;
 }
 
 template void predict_values<float>(const Options &, const lssvm_params &, const float *, size_t, size_t, const float *, float, float *, int *, const float *, size_t, float *, lssvm_predict_info *);
 template void predict_values<double>(const Options &, const lssvm_params &, const double *, size_t, size_t, const double *, double, double *, int *, const double *, size_t, double *, lssvm_predict_info *);
+template void predict_values_multi<float>(const Options &, const lssvm_params &, const float *, size_t, size_t, const float *, const float *, size_t, float *, int *, const float *, size_t, float *,
+                                          lssvm_predict_info *);
+template void predict_values_multi<double>(const Options &, const lssvm_params &, const double *, size_t, size_t, const double *, const double *, size_t, double *, int *, const double *, size_t,
+                                           double *, lssvm_predict_info *);
 template void calculate_w<float>(const float *, size_t, size_t, const float *, float *);
 template void calculate_w<double>(const double *, size_t, size_t, const double *, double *);
 
@@ -572,7 +643,7 @@ class Predictor final : public PredictorBase {
         launch_tile_kernel<float>(ta, params_.kernel_type, false, num_jc, s);
         LSSVM_HIP_CHECK(hipEventRecord(ev_b.e, s));
         hipLaunchKernelGGL(k_reduce_partials<float>, dim3((P.rows_alloc + 255) / 256), dim3(256), 0, s, partial.p, ta.part_stride, num_jc, 0, P.rows_alloc, Kv.p);
-        hipLaunchKernelGGL(k_sub_rho<float>, dim3((P.rows + 255) / 256), dim3(256), 0, s, Kv.p, P.rows, rho_, o.p);
+        hipLaunchKernelGGL(k_sub_rho<float>, dim3((P.rows + 255) / 256), dim3(256), 0, s, Kv.p, P.rows, rho_, o.p, 1);
         LSSVM_HIP_CHECK(hipGetLastError());
         lap("product, row sums");
         LSSVM_HIP_CHECK(hipMemcpyAsync(out, o.p, npoints * sizeof(float), mem_kind == LSSVM_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));

@@ -1314,6 +1314,10 @@ void enqueue_pack_records(const float *dvec, const float *cc, int ncols_padded, 
     hipLaunchKernelGGL(k_pack_dc, dim3((ncols_padded + 255) / 256), dim3(256), 0, s, dvec, cc, ncols_padded, dc, folded, static_cast<float *>(nullptr), 0, efac);
     LSSVM_HIP_CHECK(hipGetLastError());
 }
+void enqueue_pack_records2(const float *dvec0, const float *dvec1, const float *cc, int ncols_padded, float *dc, int folded, hipStream_t s) {
+    hipLaunchKernelGGL(k_pack_dc2, dim3((ncols_padded + 255) / 256), dim3(256), 0, s, dvec0, dvec1, cc, ncols_padded, dc, folded);
+    LSSVM_HIP_CHECK(hipGetLastError());
+}
 void enqueue_pack_records(const double *dvec, const double *cc, int ncols_padded, double *dc, int, const double *, hipStream_t s) {
     hipLaunchKernelGGL(k_pack_dc_f64, dim3((ncols_padded + 255) / 256), dim3(256), 0, s, dvec, cc, ncols_padded, dc, static_cast<double *>(nullptr), 0);
     LSSVM_HIP_CHECK(hipGetLastError());

@@ -588,6 +588,11 @@ void measure_bf16_mfma_ceiling(int device, int b_from_lds, double settle_ms, dou
 template <typename T>
 void predict_values(const Options &opt, const lssvm_params &params, const T *sv, size_t nsv, size_t nfeat, const T *alpha, T rho, T *w_inout, int *w_valid, const T *points,
                     size_t npoints, T *out, lssvm_predict_info *info);
+/* predict_values for `nvec` weight vectors over the SAME support vectors (a one-vs-all model): alpha [nvec][nsv], rho [nvec], w_inout [nvec][nfeat] (linear kernel),
+ * out [npoints][nvec]; column v holds the bits predict_values gives for (alpha[v], rho[v]).  Both point sets are uploaded and prepared once. */
+template <typename T>
+void predict_values_multi(const Options &opt, const lssvm_params &params, const T *sv, size_t nsv, size_t nfeat, const T *alpha, const T *rho, size_t nvec, T *w_inout, int *w_valid,
+                          const T *points, size_t npoints, T *out, lssvm_predict_info *info);
 template <typename T>
 void calculate_w(const T *sv, size_t nsv, size_t nfeat, const T *alpha, T *w_out);
 
@@ -653,6 +658,8 @@ void set_plane_args(TileArgs<float> &a, const lssvm_params &p, const PlaneSet &c
 std::vector<int2> xcd_lane_order(const std::vector<std::vector<int2>> &by_chunk);
 void enqueue_pack_records(const float *dvec, const float *cc, int ncols_padded, float *dc, int folded, const float *efac, hipStream_t s);
 void enqueue_pack_records(const double *dvec, const double *cc, int ncols_padded, double *dc, int folded, const double *efac, hipStream_t s);
+/* the records of TWO weight vectors for the rectangular 256-row kernel's NV = 2 instance: (d0 | d1), folded: both times 2^c_j (k_pack_dc2) */
+void enqueue_pack_records2(const float *dvec0, const float *dvec1, const float *cc, int ncols_padded, float *dc, int folded, hipStream_t s);
 void enqueue_planes_fragment_major(const uint16_t *planes, size_t plane_elems, int rows_alloc, int ldx16, int nplanes, uint16_t *frag, hipStream_t s);
 
 }  // namespace lssvm

@@ -48,9 +48,14 @@ __device__ unsigned long long *lssvm_item_trace = nullptr;  // [num_items][8]: e
  * RECT (round 6): the RECTANGULAR product of predict_values (rows = the points to predict, columns = the support vectors; reference shape
  * include/plssvm/backends/HIP/predict_kernel.hip.hpp:63-117) -- the same eight waves on one column stream, the same MFMA groups and LDS image, but every tile of the
  * item's column chunk is evaluated in full (no diagonal), and there are no mirrored column sums: no d_i, no column butterflies, no records to flush; the epilogue is
- * the kernel function and one fma per element. */
-template <int KT, int NK64, int PL, int HALF, int LAGT, bool RECT = false>
+ * the kernel function and one fma per element.
+ * NV (rectangular instance only): weight vectors per pass -- a one-vs-all model of k classes is k weight vectors over the SAME support vectors, and everything of a
+ * tile but the last fma is the same for all of them.  NV = 2: the record of a column tile carries (alpha0_j e_j | alpha1_j e_j) (k_pack_dc2; the rectangular
+ * instance never reads the record's second half otherwise), the epilogue evaluates the kernel function once and feeds two fma chains, the row sums of vector v go
+ * to plane v of `partial` (TileArgs::part_vstride apart).  Per vector the chain of operations is the one of NV = 1. */
+template <int KT, int NK64, int PL, int HALF, int LAGT, bool RECT = false, int NV = 1>
 __device__ __forceinline__ void pair_body(const TileArgs<float> &a, const int item_pos) {
+    static_assert(NV == 1 || (NV == 2 && RECT), "two weight vectors per pass: the rectangular instance only (their records take the place of the e_j the mirrored column sums read)");
     static_assert(PL == 3 || PL == 2, "three bf16 planes (bf16x6) or two f16 planes (f16x3)");
     static_assert(NK64 <= 2, "the hand-scheduled groups assume the 256-register budget of two waves per SIMD");
     static_assert(KT != KT_RBF, "rbf runs here with BOTH exponent terms folded (KT_RBFF, see below) or on grid planes (KT_RBFG); the unfolded form stays on the 128-row kernels");
@@ -152,9 +157,11 @@ __device__ __forceinline__ void pair_body(const TileArgs<float> &a, const int it
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) rd_off[kk] = r * 128 + (((4 * kk + g) ^ ((r >> 1) & 7)) << 4);
 
-    float rowpart[8];
+    float rowpart[NV][8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) rowpart[i] = 0.0f;
+    for (int v = 0; v < NV; ++v)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) rowpart[v][i] = 0.0f;
     f32x4 acc[2][8];
     const f32x4 civ0[2] = { { 0.f, 0.f, 0.f, 0.f }, { 0.f, 0.f, 0.f, 0.f } };  // (operands of the group dispatcher that no group of this kernel reads)
 
@@ -354,13 +361,21 @@ __device__ __forceinline__ void pair_body(const TileArgs<float> &a, const int it
             const float *dcr = reinterpret_cast<const float *>(dcs + (t % V2_DC_SLOTS) * 1024);
 #pragma unroll
             for (int cb = 0; cb < 8; ++cb) {
-                const float djv = dcr[cb * 16 + r];
+                float djv[NV];
+#pragma unroll
+                for (int v = 0; v < NV; ++v) djv[v] = dcr[v * TILE + cb * 16 + r];
 #pragma unroll
                 for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const float kv = apply_kernel_function<v2_base_kt(KT), v2_degree_class(KT)>(acc[rb][cb][e], a);
-                        rowpart[4 * rb + e] = fmaf(kv, djv, rowpart[4 * rb + e]);
+#pragma unroll
+                        for (int v = 0; v < NV; ++v) {
+                            rowpart[v][4 * rb + e] = fmaf(kv, djv[v], rowpart[v][4 * rb + e]);
+                            // scalar v_fma_f32, not v_pk_fma_f32 (which -O3 forms from adjacent chains and which costs more than two scalar ones beside the
+                            // other waves' MFMAs): every chain's value passes through an empty statement the vectoriser cannot see into.  Same bits either way.
+                            if constexpr (NV > 1) asm("" : "+v"(rowpart[v][4 * rb + e]));
+                        }
                     }
             }
         } else if (!LSSVM_DBG(a, 4)) {  // ablation bit 4: no epilogue
@@ -385,7 +400,7 @@ __device__ __forceinline__ void pair_body(const TileArgs<float> &a, const int it
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const float kv = apply_kernel_function<v2_base_kt(KT), v2_degree_class(KT)>(GRID ? acc[rb][cb][e] * a.gamma : acc[rb][cb][e], a);  // (grid planes: the chain carries sigma^2, gamma = sigma^-2)
-                        rowpart[4 * rb + e] = fmaf(kv, djv, rowpart[4 * rb + e]);
+                        rowpart[0][4 * rb + e] = fmaf(kv, djv, rowpart[0][4 * rb + e]);
                         kvp[e & 1] = kv;
                         if (e & 1) {
                             const f32x2 dip = { di[rb][e - 1], di[rb][e] };
@@ -431,33 +446,37 @@ __device__ __forceinline__ void pair_body(const TileArgs<float> &a, const int it
 
     // every lane group owns its rows: reduce over the 16 columns of the group and store
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
+    for (int vi = 0; vi < NV * 8; ++vi) {
         // sum over the 16 columns of the lane group on the vector ALU (DPP: xor 1, xor 2 inside the quads, then the mirrored half row and the
         // mirrored row, which pair quads / halves whose sums are already uniform) -- no LDS round trips at the end of a work item
-        float v = rowpart[i];
+        float v = rowpart[vi >> 3][vi & 7];
         v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));   // quad_perm [1, 0, 3, 2]
         v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));   // quad_perm [2, 3, 0, 1]
         v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));  // row_half_mirror
         v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));  // row_mirror
         if constexpr (KT == KT_LINEAR && F16) v *= a.out_scale;
-        rowpart[i] = v;
+        rowpart[vi >> 3][vi & 7] = v;
     }
     if constexpr (KT == KT_RBFF) {  // the row's folded factor e_i
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb) {
             const f32x4 ei = *reinterpret_cast<const f32x4 *>(cis + wave * 32 + 16 * rb + 4 * g);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) rowpart[4 * rb + e] *= ei[e];
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int v = 0; v < NV; ++v) rowpart[v][4 * rb + e] *= ei[e];
         }
     }
     if constexpr (GRID) {  // the row's folded factor E_i, once per work item
 #pragma unroll
-        for (int i = 0; i < 8; ++i) rowpart[i] *= a.er[row0 + wave * 32 + 16 * (i >> 2) + 4 * g + (i & 3)];
+        for (int i = 0; i < 8; ++i) rowpart[0][i] *= a.er[row0 + wave * 32 + 16 * (i >> 2) + 4 * g + (i & 3)];
     }
     if (r == 0) {
         float *dst = a.partial + static_cast<size_t>(jc) * a.part_stride + ibl * TILE + wave * 32 + 4 * g;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) dst[16 * (i >> 2) + (i & 3)] = rowpart[i];
+        for (int v = 0; v < NV; ++v)
+#pragma unroll
+            for (int i = 0; i < 8; ++i) dst[(NV > 1 ? static_cast<size_t>(v) * a.part_vstride : 0) + 16 * (i >> 2) + (i & 3)] = rowpart[v][i];
     }
 #ifdef LSSVM_ITEM_TRACE
     LSSVM_TRACE(4);
@@ -491,14 +510,14 @@ __global__ __launch_bounds__(PR_THREADS, 2) LSSVM_HAND_VGPR_CAP void tile_matvec
 
 /* The rectangular instance (predict_values): one work item = a pair of row blocks of the points x a chunk of the support vectors' column tiles; the item list covers the
  * whole rectangle (Problem-less: lssvm_problem.hip, predict_values_impl builds it), persistent launches as above. */
-template <int KT, int NK64, int PL>
+template <int KT, int NK64, int PL, int NV = 1>
 __global__ __launch_bounds__(PR_THREADS, 2) LSSVM_HAND_VGPR_CAP void tile_matvec_f32_pair_rect(const TileArgs<float> a) {
     const bool first_half = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6) < 4;
     for_each_work_item(a, [&](const auto &ai, int pos) {
         if (first_half) {
-            pair_body<KT, NK64, PL, 0, 0, true>(ai, pos);
+            pair_body<KT, NK64, PL, 0, 0, true, NV>(ai, pos);
         } else {
-            pair_body<KT, NK64, PL, 1, 0, true>(ai, pos);
+            pair_body<KT, NK64, PL, 1, 0, true, NV>(ai, pos);
         }
     });
 }

@@ -51,6 +51,8 @@ void launch_split_tile_kernel(const TileArgs<float> &a, int kernel_type, dim3 gr
 void launch_f16_tile_kernel(const TileArgs<float> &a, int kernel_type, dim3 grid, hipStream_t s);
 /* both split kernels with 256-row workgroups on block pairs (tile_launch_f32d.hip): symmetric variant, <= 128 features per pass */
 void launch_pair_tile_kernel(const TileArgs<float> &a, int kernel_type, hipStream_t s);
+/* the RECTANGULAR 256-row kernel with two weight vectors per pass (tile_launch_f32d2.hip; TileArgs::nvec == 2, reached through launch_pair_tile_kernel) */
+void launch_rect2_tile_kernel(const TileArgs<float> &a, int kernel_type, hipStream_t s);
 /* rbf / polynomial on more features than a row panel in registers holds (tile_launch_f32x.hip): feature panels inside a tile */
 void launch_wide_tile_kernel(const TileArgs<float> &a, int kernel_type, dim3 grid, hipStream_t s);
 /* fp64 rbf / polynomial on more than 256 features (tile_launch_f64x.hip): feature panels of 64 inside a sub-tile */

@@ -109,6 +109,11 @@ void launch_pair_tile_kernel(const TileArgs<float> &a, int kernel_type, hipStrea
     if (a.items == nullptr || a.num_items <= 0) return;
     if (a.Xr16f == nullptr) throw Error(LSSVM_ERR_INTERNAL, "the 256-row tile kernel needs the fragment-major row planes");
     if (a.rect != 0) {
+        if (a.nvec == 2) {
+            launch_rect2_tile_kernel(a, kernel_type, s);
+            return;
+        }
+        if (a.nvec > 2) throw Error(LSSVM_ERR_INTERNAL, "the rectangular 256-row tile kernel evaluates at most two weight vectors per pass");
         if (a.planes_f16 != 0) {
             launch_rect<2>(a, kernel_type, s);
         } else {

@@ -59,6 +59,23 @@ class CSVM:
     def predict_values(self, params, support_vectors, alpha, rho, w, predict_points):
         raise NotImplementedError
 
+    # --- several classifiers over one data set (one-vs-all, plssvm_amd.multiclass): defaults on top of the two boundary methods ---
+    def solve_systems_of_linear_equations(self, params, A, B, eps, max_iter, sample_weight=None):
+        """One solve per row of ``B`` (``k x N`` right-hand sides) on the same matrix: ``(alphas[k, N], rhos[k], [info, ...])``."""
+        B = np.asarray(B)
+        if B.ndim != 2 or B.shape[0] == 0:
+            raise InvalidParameterError("The right-hand sides must be a matrix with one row per system and at least one row!")
+        kw = {} if sample_weight is None else {"sample_weight": sample_weight}
+        solved = [self.solve_system_of_linear_equations(params, A, b, eps, max_iter, **kw) for b in B]
+        return np.stack([np.asarray(s[0]) for s in solved]), np.array([s[1] for s in solved]), [s[2] for s in solved]
+
+    def predict_values_multi(self, params, support_vectors, alphas, rhos, ws, predict_points):
+        """``predict_values`` per row of ``alphas``: ``(values[n, k], ws[k, d] or None)``."""
+        alphas = np.asarray(alphas)
+        done = [self.predict_values(params, support_vectors, alphas[v], float(rhos[v]), None if ws is None else ws[v], predict_points) for v in range(alphas.shape[0])]
+        values = np.stack([np.asarray(d[0]) for d in done], axis=1)
+        return values, (None if any(d[1] is None for d in done) else np.stack([np.asarray(d[1]) for d in done]))
+
     def get_params(self):
         return self.params
 
@@ -183,6 +200,42 @@ class MI355CSVM(CSVM):
 
     def predict_values(self, params, support_vectors, alpha, rho, w, predict_points):
         return backend.predict_values(params, support_vectors, alpha, rho, w, predict_points, options=self._options)
+
+    def solve_systems_of_linear_equations(self, params, A, B, eps, max_iter, sample_weight=None):
+        """The systems one after the other on ONE resident problem: the data is uploaded and prepared (q, operand planes) once, the weights are set once, and every
+        right-hand side runs the recipe of the one-shot solve (begin / step / finish) on it -- the same alpha, rho and iteration count as a fresh one-shot solve.
+        Several devices: the base class's loop of one-shot solves."""
+        if self.use_devices != 1:
+            return super().solve_systems_of_linear_equations(params, A, B, eps, max_iter, sample_weight=sample_weight)
+        A = backend._as_matrix(A)
+        N = A.shape[0]
+        B = np.ascontiguousarray(B, dtype=A.dtype)
+        if B.ndim != 2 or B.shape[0] == 0 or B.shape[1] != N:
+            raise InvalidParameterError(f"The number of data points in the matrix A ({N}) and the values in every right hand side vector ({B.shape[-1] if B.ndim else 0}) must be the same!")
+        if not eps > 0.0:
+            raise InvalidParameterError(f"The stopping criterion in the CG algorithm must be greater than 0.0, but is {eps}!")
+        if not max_iter > 0:
+            raise InvalidParameterError("The number of CG iterations must be greater than 0!")
+        first = self.get_option("rebalance_after")
+        alphas, rhos, infos = np.zeros_like(B), np.zeros(B.shape[0], dtype=A.dtype), []
+        with backend.ResidentProblem(params, A, devices=[0], options=self._options) as prob:  # (device 0 alone, as the one-shot solve creates it)
+            if sample_weight is not None:
+                prob.set_weights(sample_weight)
+            for c, b in enumerate(B):
+                prob.cg_begin(b, eps)
+                if 0 < first < max_iter:  # (one device: rebalance has nothing to move; the split keeps the sequence of calls the one-shot solve makes)
+                    prob.cg_step(first)
+                    prob.rebalance()
+                    prob.cg_step(max_iter - first)
+                else:
+                    prob.cg_step(max_iter)
+                alphas[c], rhos[c], info = prob.cg_finish()
+                info["max_iterations"] = int(max_iter)
+                infos.append(info)
+        return alphas, rhos, infos
+
+    def predict_values_multi(self, params, support_vectors, alphas, rhos, ws, predict_points):
+        return backend.predict_values_multi(params, support_vectors, alphas, rhos, ws, predict_points, options=self._options)
 
     def predict(self, model: Model, data: DataSet):
         """csvm::predict (csvm.hpp:322-342) with the model RESIDENT in HBM from the first call on (``lssvm_mi355_predictor_*``): later calls with the same model upload only

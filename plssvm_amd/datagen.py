@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import numpy as np
 
-__all__ = ["make_blobs_pm1", "generate_libsvm_file"]
+__all__ = ["make_blobs_pm1", "make_blobs_multiclass", "generate_libsvm_file"]
 
 
 def make_blobs_pm1(num_points: int, num_features: int, seed: int = 42, dtype=np.float32, chunk: int = 65536):
@@ -43,6 +43,19 @@ def make_blobs_pm1(num_points: int, num_features: int, seed: int = 42, dtype=np.
         X[start:stop] = (X[start:stop].astype(np.float64) * scale + shift).astype(dtype)
     np.clip(X, -1.0, 1.0, out=X)
     return X, y
+
+
+def make_blobs_multiclass(num_points: int, num_features: int, num_classes: int, seed: int = 42, dtype=np.float32):
+    """Return ``(X[num_points, num_features], y[num_points] in {0 .. num_classes - 1})``: the recipe above with ``num_classes`` centres ~ U(-10, 10)^d, point ``i`` of
+    class ``i % num_classes`` (balanced classes) = its centre + N(0, 1), per-feature min-max scaling of the whole set to [-1, 1]."""
+    rng = np.random.default_rng(seed)
+    centres = rng.uniform(-10.0, 10.0, size=(num_classes, num_features))
+    y = np.arange(num_points) % num_classes
+    X = centres[y] + rng.standard_normal(size=(num_points, num_features))
+    lo, hi = X.min(axis=0), X.max(axis=0)
+    span = np.where(hi > lo, hi - lo, 1.0)
+    X = np.clip((X - lo) * (2.0 / span) - 1.0, -1.0, 1.0)
+    return X.astype(dtype), y.astype(np.int64)
 
 
 def generate_libsvm_file(filename, num_points: int, num_features: int, seed: int = 42) -> None:

@@ -1,6 +1,7 @@
 """scikit-learn ``SVC`` on top of CSVM, the counterpart of the reference's bindings/Python/sklearn.cpp: the same keywords, parameters and fitted attributes,
 with the LS-SVM solver behind ``fit``.  Beyond the reference: ``class_weight`` and ``sample_weight`` (the weighted LS-SVM system), ``get_params(deep)`` /
-``set_params`` in scikit-learn's contract (``clone``, ``GridSearchCV``, ``Pipeline``), ``dual_coef_`` / ``intercept_`` / ``coef_``, and ``decision_function``.
+``set_params`` in scikit-learn's contract (``clone``, ``GridSearchCV``, ``Pipeline``), ``dual_coef_`` / ``intercept_`` / ``coef_``, ``decision_function``, and more
+than two classes (one-vs-all, :mod:`plssvm_amd.multiclass`).
 
 An estimator that duck-types scikit-learn's protocol: scikit-learn itself is not needed to use it."""
 
@@ -9,6 +10,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import csvm as _csvm
+from . import multiclass as _multiclass
 from .csvm import make_csvm
 from .data_set import DataSet
 from .exceptions import InvalidParameterError
@@ -45,7 +47,10 @@ def _set_verbosity(verbose) -> None:
 
 
 class SVC:
-    """C-support vector classification with the LS-SVM solver (two classes).  ``gamma``: a number, or any string for the PLSSVM default 1 / n_features.
+    """C-support vector classification with the LS-SVM solver.  ``gamma``: a number, or any string for the PLSSVM default 1 / n_features.
+    More than two classes are classified ONE-VS-ALL -- unlike scikit-learn's ``SVC``, which trains one-vs-one: one classifier per class (that class against the rest) over
+    the same training points, the predicted class is the one of the largest decision value (ties: the lowest class index).  The fitted attributes then have one row per
+    class: ``dual_coef_ (k, n_SV)``, ``intercept_ (k,)``, ``coef_ (k, n_features)``, ``n_iter_ (k,)``, ``decision_function(X) (n, k)`` (scikit-learn's "ovr" shape).
     ``class_weight``: None, ``"balanced"`` (n_samples / (n_classes * count(class))) or a dict {label: weight}; with ``sample_weight`` in ``fit``, point i is
     regularised by 1 / (C * sample_weight[i] * class_weight[y[i]]) -- the weighted LS-SVM system -- and points of weight 0 take no part."""
 
@@ -87,7 +92,7 @@ class SVC:
         """What scikit-learn's tooling asks of an estimator (is_classifier: stratified folds in GridSearchCV, ...); only scikit-learn calls this."""
         from sklearn.utils import ClassifierTags, Tags, TargetTags
 
-        return Tags(estimator_type="classifier", target_tags=TargetTags(required=True), classifier_tags=ClassifierTags(multi_class=False))
+        return Tags(estimator_type="classifier", target_tags=TargetTags(required=True), classifier_tags=ClassifierTags(multi_class=True))
 
     def __repr__(self):
         return "SVC(" + ", ".join(f"{k}={v!r}" for k, v in self.get_params().items()) + ")"
@@ -132,6 +137,8 @@ class SVC:
                 raise InvalidParameterError(f"The number of data points ({y.size}) and the number of sample weights ({sw.size}) must be the same!")
             weights = sw * class_weight[np.searchsorted(classes, y)]
         svm = make_csvm(params=params)
+        if len(classes) > 2:
+            return self._fit_one_vs_all(svm, params, X, y, classes, class_weight, weights)
         data = DataSet(X, y.tolist(), real_type=self.real_type)
         max_iter = None if self.max_iter is None or self.max_iter < 0 else self.max_iter
         model = svm.fit(data, epsilon=self.tol, max_iter=max_iter, sample_weight=weights)
@@ -155,6 +162,29 @@ class SVC:
         }
         return self
 
+    def _fit_one_vs_all(self, svm, params, X, y, classes, class_weight, weights):
+        """More than two classes: one classifier per class on the same points (plssvm_amd.multiclass)."""
+        max_iter = None if self.max_iter is None or self.max_iter < 0 else self.max_iter
+        model = _multiclass.fit_one_vs_all(svm, params, np.ascontiguousarray(X, dtype=self.real_type), y, classes, self.tol, max_iter, weights)
+        support = np.arange(y.size, dtype=np.int32) if weights is None else np.flatnonzero(weights > 0).astype(np.int32)
+        sv_labels = y[support]
+        nonzero = np.any(model.alpha != 0, axis=0)  # a support vector counts where ANY classifier gives it a non-zero coefficient
+        self._svm, self._model = svm, model
+        self._fit = {
+            "classes_": classes,
+            "class_weight_": class_weight,
+            "fit_status_": 0,
+            "n_features_in_": int(X.shape[1]),
+            "shape_fit_": tuple(int(v) for v in X.shape),
+            "n_iter_": np.array([int(info["iterations"]) for info in model.infos], dtype=np.int64),
+            "support_": support,
+            "support_vectors_": model.support_vectors,
+            "n_support_": np.array([np.count_nonzero(nonzero & (sv_labels == c)) for c in classes], dtype=np.int32),
+            "dual_coef_": model.alpha,
+            "intercept_": -model.rho,
+        }
+        return self
+
     def __sklearn_is_fitted__(self):
         return self._fit is not None
 
@@ -163,9 +193,12 @@ class SVC:
             raise AttributeError("This SVC instance is not fitted yet. Call 'fit' with appropriate arguments before using this estimator.")  # sklearn.cpp:236
 
     def decision_function(self, X):
-        """sum_i dual_coef_[0, i] k(support_vectors_[i], x) + intercept_[0] for every row x of X (an extension: the reference's raises)."""
+        """sum_i dual_coef_[0, i] k(support_vectors_[i], x) + intercept_[0] for every row x of X (an extension: the reference's raises); more than two classes: shape
+        (n, n_classes), column c the value of classifier c (class c against the rest)."""
         self._check_fitted()
         m = self._model
+        if isinstance(m, _multiclass.OneVsAllModel):
+            return _multiclass.decision_values(self._svm, m, X)
         values, w = self._svm.predict_values(m.params, m.support_vectors(), m.alpha, float(m.rho), m.w, np.asarray(X, dtype=self.real_type))
         if w is not None:
             m.w = w
@@ -174,6 +207,8 @@ class SVC:
     def predict(self, X):
         """Perform classification on samples in X."""
         classes = self.classes_
+        if len(classes) > 2:
+            return _multiclass.predict_classes(classes, self.decision_function(X))
         return np.where(self.decision_function(X) > 0, classes[1], classes[0])
 
     def score(self, X, y, sample_weight=None):
@@ -186,22 +221,25 @@ class SVC:
     fit_status_ = _fitted_attribute("fit_status_", "0 if correctly fitted.")
     n_features_in_ = _fitted_attribute("n_features_in_", "Number of features seen during fit.")
     shape_fit_ = _fitted_attribute("shape_fit_", "Array dimensions of the training matrix X.")
-    n_iter_ = _fitted_attribute("n_iter_", "CG iterations of the solve.")
+    n_iter_ = _fitted_attribute("n_iter_", "CG iterations of the solve; more than two classes: of every classifier's solve, int ndarray of shape (n_classes,).")
     support_ = _fitted_attribute("support_", "Indices of the support vectors (every point of weight > 0), ndarray of shape (n_SV,).")
     support_vectors_ = _fitted_attribute("support_vectors_", "Support vectors, ndarray of shape (n_SV, n_features).")
     n_support_ = _fitted_attribute("n_support_", "Support vectors of non-zero dual coefficient per class, ndarray of shape (n_classes,), int32.")
-    dual_coef_ = _fitted_attribute("dual_coef_", "The dual coefficients alpha, ndarray of shape (1, n_SV).")
-    intercept_ = _fitted_attribute("intercept_", "The constant of the decision function (-rho), ndarray of shape (1,).")
+    dual_coef_ = _fitted_attribute("dual_coef_", "The dual coefficients alpha, ndarray of shape (1, n_SV); more than two classes: (n_classes, n_SV), row c = class c against the rest.")
+    intercept_ = _fitted_attribute("intercept_", "The constant of the decision function (-rho), ndarray of shape (1,); more than two classes: (n_classes,).")
 
     @property
     def coef_(self):
-        """The weights w of the features, ndarray of shape (1, n_features): linear kernel only."""
+        """The weights w of the features, ndarray of shape (1, n_features) -- more than two classes: (n_classes, n_features): linear kernel only."""
         if self._fit is None:
             raise _not_fitted("coef_")
         if self._model.params.kernel_type != 0:
             raise AttributeError("coef_ is only available when using a linear kernel")
         if "coef_" not in self._fit:
             from .backend import calculate_w
+            if isinstance(self._model, _multiclass.OneVsAllModel):
+                self._fit["coef_"] = np.stack([calculate_w(self._model.support_vectors, a) for a in self._model.alpha])
+                return self._fit["coef_"]
             self._fit["coef_"] = calculate_w(self._model.support_vectors(), self._model.alpha).reshape(1, -1)
         return self._fit["coef_"]
 
