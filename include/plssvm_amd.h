@@ -110,7 +110,7 @@ typedef struct lssvm_predict_info {
     int32_t rbf_direct;        /* as lssvm_cg_info */
     int32_t resident;          /* lssvm_mi355_predictor_predict: 1 if the batch ran against the RESIDENT support vectors, 0 if it took the one-shot path (same result) */
     int32_t vectors_per_launch; /* lssvm_mi355_predict_values_multi_*: the largest number of weight vectors ONE launch of the product kernel evaluated (2 where the
-                                 * two-vector kernel ran, 1 on the per-vector paths); the single-vector entry points and the predictor write 0 */
+                                 * two-vector kernel ran, 1 on the per-vector paths), lssvm_mi355_predictor_predict_multi alike; the single-vector entry points and lssvm_mi355_predictor_predict write 0 */
 } lssvm_predict_info;
 
 /* ------------------------------------------------------------------------------------------------------------------ */
@@ -225,6 +225,24 @@ int lssvm_mi355_predictor_create(lssvm_mi355_predictor **out, const lssvm_params
                                  size_t num_features, const void *alpha, double rho, const lssvm_mi355_options *options);
 int lssvm_mi355_predictor_predict(lssvm_mi355_predictor *predictor, const void *predict_points, int mem_kind, size_t num_predict_points, void *out, lssvm_predict_info *info);
 int lssvm_mi355_predictor_destroy(lssvm_mi355_predictor *predictor);
+
+/* The resident predictor of a ONE-VS-ALL model: num_vectors weight vectors over the same support vectors (alphas is num_vectors x num_support_vectors row-major,
+ * rhos has num_vectors entries, of type double whatever the dtype).  `create_multi` prepares the support vectors once, keeps the alpha matrix in HBM and packs the
+ * column records of every launch group there and then -- pairs (0,1), (2,3), ... and an odd last vector alone; the linear kernel: one w per vector --, so a batch
+ * pays for its own upload and preparation (once, whatever num_vectors is) and for the product launches only.  lssvm_mi355_predictor_create is the num_vectors == 1
+ * case of the same object; `destroy` is shared.
+ * `predict_multi` works on any handle and writes num_predict_points x num_vectors values row-major, as lssvm_mi355_predict_values_multi_* does; column v holds
+ * exactly the bits a single-vector predictor of (alphas[v], rhos[v]) with the same options returns.  Per batch the product runs on the rectangular 256-row kernel with
+ * two vectors per pass under that kernel's conditions (lssvm_mi355_predict_values_multi_*), otherwise on the 128-row full-square kernels -- two vectors per pass for
+ * the polynomial kernel and for rbf within the folded form's range, one per launch for rbf beyond it; lssvm_predict_info.vectors_per_launch reports the largest
+ * number of vectors one product launch evaluated (2 or 1; the linear kernel: 1).  Models and batches outside the resident form (see above) go through
+ * lssvm_mi355_predict_values_multi_* inside the predictor: resident == 0, the same values as that call.
+ * lssvm_mi355_predictor_predict on a handle of more than one vector is LSSVM_ERR_INVALID_ARGUMENT; so are num_vectors == 0 and NULL alphas / rhos, before a
+ * device is touched. */
+int lssvm_mi355_predictor_create_multi(lssvm_mi355_predictor **out, const lssvm_params *params, int dtype, const void *support_vectors, size_t num_support_vectors,
+                                       size_t num_features, const void *alphas, const double *rhos, size_t num_vectors, const lssvm_mi355_options *options);
+int lssvm_mi355_predictor_predict_multi(lssvm_mi355_predictor *predictor, const void *predict_points, int mem_kind, size_t num_predict_points, void *out,
+                                        lssvm_predict_info *info);
 
 /* ------------------------------------------------------------------------------------------------------------------ */
 /* fine-grained entry points for kernel-level parity tests: the protected members the reference's backend tests re-export  */

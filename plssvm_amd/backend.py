@@ -221,15 +221,34 @@ def predict_values_multi(params: Parameter, support_vectors, alphas, rhos, ws, p
 
 class Predictor:
     """A model resident in HBM across predict calls (``lssvm_mi355_predictor_*``): the support vectors are uploaded and prepared once, every :meth:`predict` uploads only
-    its batch of points.  Same values as :func:`predict_values`; ``info_out["resident"]`` says whether a batch ran against the resident form or took the one-shot path."""
+    its batch of points.  Same values as :func:`predict_values`; ``info_out["resident"]`` says whether a batch ran against the resident form or took the one-shot path.
 
-    def __init__(self, params: Parameter, support_vectors, alpha, rho: float, options: Options | None = None):
+    A ONE-VS-ALL model: ``alpha`` of shape ``(k, num_support_vectors)`` with ``rho`` of shape ``(k,)`` (``lssvm_mi355_predictor_create_multi``).  :meth:`predict` then
+    returns ``(num_points, k)`` and :meth:`predict_device` writes ``num_points`` x ``k`` values row-major, column ``v`` the bits of a predictor of ``(alpha[v], rho[v])``;
+    ``info_out["vectors_per_launch"]`` says whether one pass over the Gram tiles fed two weight vectors (2) or every vector had a launch of its own (1)."""
+
+    def __init__(self, params: Parameter, support_vectors, alpha, rho, options: Options | None = None):
         sv = _as_matrix(support_vectors)
         alpha = np.ascontiguousarray(alpha, dtype=sv.dtype)
-        if alpha.size != sv.shape[0]:
-            raise InvalidParameterError(f"The number of support vectors ({sv.shape[0]}) and number of weights ({alpha.size}) must be the same!")
         self.dtype, self.num_features = sv.dtype, int(sv.shape[1])
         self._h = C.c_void_p(None)
+        if alpha.ndim == 2:
+            k = alpha.shape[0]
+            if k == 0:
+                raise InvalidParameterError("The weights must be a matrix with one row per weight vector and at least one row!")
+            if alpha.shape[1] != sv.shape[0]:
+                raise InvalidParameterError(f"The number of support vectors ({sv.shape[0]}) and number of weights ({alpha.shape[1]}) must be the same!")
+            rhos = np.ascontiguousarray(rho, dtype=np.float64)
+            if rhos.shape != (k,):
+                raise InvalidParameterError(f"The number of weight vectors ({k}) and the number of rho values ({rhos.size}) must be the same!")
+            self.num_vectors = int(k)
+            ps = _params_struct(params, sv.shape[1])
+            check(_capi.predictor_multi_entry("lssvm_mi355_predictor_create_multi")(C.byref(self._h), C.byref(ps), _capi.dtype_code(sv.dtype), ptr(sv), sv.shape[0], sv.shape[1], ptr(alpha),
+                                                                                    rhos.ctypes.data_as(C.POINTER(C.c_double)), k, options_ptr(options)))
+            return
+        if alpha.size != sv.shape[0]:
+            raise InvalidParameterError(f"The number of support vectors ({sv.shape[0]}) and number of weights ({alpha.size}) must be the same!")
+        self.num_vectors = None  # (one weight vector: the values are a vector, not a matrix of one column)
         ps = _params_struct(params, sv.shape[1])
         check(lib.lssvm_mi355_predictor_create(C.byref(self._h), C.byref(ps), C.c_int(_capi.dtype_code(sv.dtype)), ptr(sv), C.c_size_t(sv.shape[0]), C.c_size_t(sv.shape[1]), ptr(alpha),
                                                C.c_double(float(rho)), options_ptr(options)))
@@ -238,18 +257,26 @@ class Predictor:
         pts = _as_matrix(predict_points, dtype=self.dtype)
         if pts.shape[1] != self.num_features:
             raise InvalidParameterError(f"The number of features in the support vectors ({self.num_features}) must be the same as in the data points to predict ({pts.shape[1]})!")
-        out = np.zeros(pts.shape[0], dtype=self.dtype)
         pinfo = LssvmPredictInfo()
-        check(lib.lssvm_mi355_predictor_predict(self._h, ptr(pts), C.c_int(_capi.LSSVM_MEM_HOST), C.c_size_t(pts.shape[0]), ptr(out), C.byref(pinfo)))
+        if self.num_vectors is None:
+            out = np.zeros(pts.shape[0], dtype=self.dtype)
+            check(lib.lssvm_mi355_predictor_predict(self._h, ptr(pts), C.c_int(_capi.LSSVM_MEM_HOST), C.c_size_t(pts.shape[0]), ptr(out), C.byref(pinfo)))
+        else:
+            out = np.zeros((pts.shape[0], self.num_vectors), dtype=self.dtype)
+            check(_capi.predictor_multi_entry("lssvm_mi355_predictor_predict_multi")(self._h, ptr(pts), _capi.LSSVM_MEM_HOST, pts.shape[0], ptr(out), C.byref(pinfo)))
         if info_out is not None:
             info_out.update(pinfo.as_dict())
         return out
 
     def predict_device(self, points_ptr: int, num_points: int, out_ptr: int, info_out: dict | None = None) -> None:
         """The same with the batch AND the values in memory of device 0 (``LSSVM_MEM_DEVICE``): ``points_ptr`` -> ``num_points`` x ``num_features`` row-major of the predictor's
-        dtype (e.g. a contiguous torch tensor's ``data_ptr()``, complete when the call is made), ``out_ptr`` -> ``num_points`` values, written when the call returns."""
+        dtype (e.g. a contiguous torch tensor's ``data_ptr()``, complete when the call is made), ``out_ptr`` -> ``num_points`` values (a one-vs-all model: ``num_points`` x
+        ``k``, row-major), written when the call returns."""
         pinfo = LssvmPredictInfo()
-        check(lib.lssvm_mi355_predictor_predict(self._h, C.c_void_p(int(points_ptr)), C.c_int(_capi.LSSVM_MEM_DEVICE), C.c_size_t(int(num_points)), C.c_void_p(int(out_ptr)), C.byref(pinfo)))
+        if self.num_vectors is None:
+            check(lib.lssvm_mi355_predictor_predict(self._h, C.c_void_p(int(points_ptr)), C.c_int(_capi.LSSVM_MEM_DEVICE), C.c_size_t(int(num_points)), C.c_void_p(int(out_ptr)), C.byref(pinfo)))
+        else:
+            check(_capi.predictor_multi_entry("lssvm_mi355_predictor_predict_multi")(self._h, int(points_ptr), _capi.LSSVM_MEM_DEVICE, int(num_points), int(out_ptr), C.byref(pinfo)))
         if info_out is not None:
             info_out.update(pinfo.as_dict())
 

@@ -302,7 +302,22 @@ int lssvm_mi355_predictor_create(lssvm_mi355_predictor **out, const lssvm_params
         lssvm::check_params(params);
         LSSVM_REQUIRE(dtype == LSSVM_DTYPE_F32 || dtype == LSSVM_DTYPE_F64, "dtype must be LSSVM_DTYPE_F32 or LSSVM_DTYPE_F64");
         auto h = std::make_unique<lssvm_mi355_predictor>();
-        h->impl = lssvm::make_predictor(options_of(options), *params, dtype, support_vectors, num_support_vectors, num_features, alpha, rho);
+        h->impl = lssvm::make_predictor(options_of(options), *params, dtype, support_vectors, num_support_vectors, num_features, alpha, &rho, 1);
+        *out = h.release();
+    });
+}
+int lssvm_mi355_predictor_create_multi(lssvm_mi355_predictor **out, const lssvm_params *params, int dtype, const void *support_vectors, size_t num_support_vectors,
+                                       size_t num_features, const void *alphas, const double *rhos, size_t num_vectors, const lssvm_mi355_options *options) {
+    return guarded([&] {
+        LSSVM_REQUIRE(out != nullptr, "out must not be NULL");
+        *out = nullptr;
+        lssvm::check_params(params);
+        LSSVM_REQUIRE(dtype == LSSVM_DTYPE_F32 || dtype == LSSVM_DTYPE_F64, "dtype must be LSSVM_DTYPE_F32 or LSSVM_DTYPE_F64");
+        LSSVM_REQUIRE(num_vectors > 0, "The number of weight vectors must be greater than 0!");
+        LSSVM_REQUIRE(alphas != nullptr, "The number of support vectors and number of weights must be the same!");  // csvm.cpp:192
+        LSSVM_REQUIRE(rhos != nullptr, "rhos must hold one value per weight vector");
+        auto h = std::make_unique<lssvm_mi355_predictor>();
+        h->impl = lssvm::make_predictor(options_of(options), *params, dtype, support_vectors, num_support_vectors, num_features, alphas, rhos, num_vectors);
         *out = h.release();
     });
 }
@@ -310,7 +325,15 @@ int lssvm_mi355_predictor_predict(lssvm_mi355_predictor *predictor, const void *
     return guarded([&] {
         LSSVM_REQUIRE(predictor != nullptr, "predictor handle must not be NULL");
         LSSVM_REQUIRE(mem_kind == LSSVM_MEM_HOST || mem_kind == LSSVM_MEM_DEVICE, "invalid mem_kind");
-        predictor->impl->predict(predict_points, mem_kind, num_predict_points, out, info);
+        predictor->impl->predict(predict_points, mem_kind, num_predict_points, out, info, false);
+    });
+}
+int lssvm_mi355_predictor_predict_multi(lssvm_mi355_predictor *predictor, const void *predict_points, int mem_kind, size_t num_predict_points, void *out,
+                                        lssvm_predict_info *info) {
+    return guarded([&] {
+        LSSVM_REQUIRE(predictor != nullptr, "predictor handle must not be NULL");
+        LSSVM_REQUIRE(mem_kind == LSSVM_MEM_HOST || mem_kind == LSSVM_MEM_DEVICE, "invalid mem_kind");
+        predictor->impl->predict(predict_points, mem_kind, num_predict_points, out, info, true);
     });
 }
 int lssvm_mi355_predictor_destroy(lssvm_mi355_predictor *predictor) {

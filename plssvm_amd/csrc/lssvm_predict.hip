@@ -107,6 +107,34 @@ void calculate_w(const T *sv, size_t nsv, size_t nfeat, const T *alpha, T *w_out
     calculate_w_multi<T>(sv, nsv, nfeat, alpha, 1, w_out);
 }
 
+/* device time of the product launches of a call (what the reference times as "predict", gpu_csvm.hpp:656-730, is the whole call: total_ms): an event pair around each
+ * launch, summed when the stream has drained.  `capacity`: the launches to come -- the events must not move once recorded */
+struct LaunchTimer {
+    std::vector<Event> evs;
+    explicit LaunchTimer(size_t capacity) { evs.reserve(2 * capacity); }
+    template <typename F>
+    void timed(hipStream_t s, F &&launch) {
+        evs.emplace_back();
+        evs.emplace_back();
+        const size_t k = evs.size() - 2;
+        evs[k].create(true);
+        evs[k + 1].create(true);
+        LSSVM_HIP_CHECK(hipEventRecord(evs[k].e, s));
+        launch();
+        LSSVM_HIP_CHECK(hipEventRecord(evs[k + 1].e, s));
+    }
+    void sum_into(lssvm_predict_info &info) const {
+        double sum = 0.0;
+        bool ok = !evs.empty();
+        for (size_t k = 0; k + 1 < evs.size(); k += 2) {
+            float ms = 0.0f;
+            ok = ok && hipEventElapsedTime(&ms, evs[k].e, evs[k + 1].e) == hipSuccess;
+            sum += ms;
+        }
+        if (ok) info.kernel_ms = sum;
+    }
+};
+
 /* `nvec` weight vectors over the same support vectors: alpha [nvec][nsv], rho [nvec], w_inout [nvec][nfeat], out [npoints][nvec] (nvec = 1: predict_values).  Everything up
  * to the records of the weight vectors is done once; `repeat`: extra untimed launches of the product in front of the timed one (predict_values' measurement aid). */
 template <typename T>
@@ -123,29 +151,11 @@ static void predict_values_impl(const Options &opt, const lssvm_params &params, 
     select_device_checked(0);
     hipStream_t s = nullptr;
     const double t0 = now_ms();
-    // around every launch of the kernel that does the product (what the reference times as "predict", gpu_csvm.hpp:656-730, is the whole call: total_ms)
-    std::vector<Event> evs;
-    const auto timed = [&](auto &&launch) {
-        evs.emplace_back();
-        evs.emplace_back();
-        const size_t k = evs.size() - 2;
-        evs[k].create(true);
-        evs[k + 1].create(true);
-        LSSVM_HIP_CHECK(hipEventRecord(evs[k].e, s));
-        launch();
-        LSSVM_HIP_CHECK(hipEventRecord(evs[k + 1].e, s));
-    };
-    evs.reserve(2 * nvec);
+    LaunchTimer timer(nvec);  // around every launch of the kernel that does the product
+    const auto timed = [&](auto &&launch) { timer.timed(s, launch); };
     const int nv = static_cast<int>(nvec);
     const auto finish_info = [&](double t_kernel_enqueued) {
-        double sum = 0.0;
-        bool ok = !evs.empty();
-        for (size_t k = 0; k + 1 < evs.size(); k += 2) {
-            float ms = 0.0f;
-            ok = ok && hipEventElapsedTime(&ms, evs[k].e, evs[k + 1].e) == hipSuccess;
-            sum += ms;
-        }
-        if (ok) info.kernel_ms = sum;
+        timer.sum_into(info);
         info.total_ms = now_ms() - t0;
         info.setup_ms = t_kernel_enqueued - t0;
     };
@@ -393,28 +403,35 @@ template void calculate_w<float>(const float *, size_t, size_t, const float *, f
 template void calculate_w<double>(const double *, size_t, size_t, const double *, double *);
 
 /* ------------------------------------------------------------------ the resident predictor ------------------------------------------------------------------ */
+/* `nvec_` weight vectors over the same support vectors (lssvm_mi355_predictor_create: one; _create_multi: a one-vs-all model's k).  Everything that does not depend on
+ * the weight vector is held once; per vector the alpha row, the packed column records of its launch group and, for the linear kernel, w. */
 template <typename T>
 class Predictor final : public PredictorBase {
   public:
-    Predictor(const Options &opt, const lssvm_params &params, const T *sv, size_t nsv, size_t nfeat, const T *alpha, T rho) :
-        opt_(opt), params_(params), nsv_(nsv), nfeat_(nfeat), rho_(rho) {
+    Predictor(const Options &opt, const lssvm_params &params, const T *sv, size_t nsv, size_t nfeat, const T *alpha, const double *rho, size_t nvec) :
+        opt_(opt), params_(params), nsv_(nsv), nfeat_(nfeat), nvec_(nvec) {
         dtype = std::is_same_v<T, float> ? LSSVM_DTYPE_F32 : LSSVM_DTYPE_F64;
         check_params(&params_);
+        LSSVM_REQUIRE(nvec > 0 && rho != nullptr, "a predictor needs at least one weight vector and its rho");
+        LSSVM_REQUIRE(nvec <= static_cast<size_t>(1) << 20, "too many weight vectors");
         LSSVM_REQUIRE(sv != nullptr && nsv > 0, "The support vectors must not be empty!");   // csvm.cpp:189
         LSSVM_REQUIRE(nfeat > 0, "The support vectors must contain at least one feature!");  // csvm.cpp:190
         LSSVM_REQUIRE(alpha != nullptr, "The number of support vectors and number of weights must be the same!");
+        rho_.resize(nvec);
+        for (size_t v = 0; v < nvec; ++v) rho_[v] = static_cast<T>(rho[v]);
         select_device_checked(0);
         hipStream_t s = nullptr;
         if (params_.kernel_type == LSSVM_KERNEL_LINEAR) {
-            // the linear kernel predicts through w = sum_i alpha_i sv_i (csvm.cpp:204-213): computed once, resident zero padded like a row of points
-            w_host_.assign(nfeat, T(0));
-            calculate_w<T>(sv, nsv, nfeat, alpha, w_host_.data());
-            w_.alloc_zero(static_cast<size_t>(padded_features<T>(nfeat)), s);
-            LSSVM_HIP_CHECK(hipMemcpyAsync(w_.p, w_host_.data(), nfeat * sizeof(T), hipMemcpyHostToDevice, s));
+            // the linear kernel predicts through w = sum_i alpha_i sv_i (csvm.cpp:204-213): computed once per vector, resident zero padded like a row of points
+            w_host_.assign(nvec * nfeat, T(0));
+            calculate_w_multi<T>(sv, nsv, nfeat, alpha, nvec, w_host_.data());
+            ldw_ = static_cast<size_t>(padded_features<T>(nfeat));
+            w_.alloc_zero(nvec * ldw_, s);
+            LSSVM_HIP_CHECK(hipMemcpy2DAsync(w_.p, ldw_ * sizeof(T), w_host_.data(), nfeat * sizeof(T), nfeat * sizeof(T), nvec, hipMemcpyHostToDevice, s));
             LSSVM_HIP_CHECK(hipStreamSynchronize(s));
             return;
         }
-        alpha_host_.assign(alpha, alpha + nsv);
+        alpha_host_.assign(alpha, alpha + nvec * nsv);
         if constexpr (std::is_same_v<T, float>) prepare_resident(sv, s);
         // the one-shot path's input: a host copy where nothing is resident; a resident model keeps its support vectors as they came in HBM and fetches them if a batch ever asks
         if (!resident_) {
@@ -427,11 +444,12 @@ class Predictor final : public PredictorBase {
         }
     }
 
-    void predict(const void *points_v, int mem_kind, size_t npoints, void *out_v, lssvm_predict_info *info) override {
+    void predict(const void *points_v, int mem_kind, size_t npoints, void *out_v, lssvm_predict_info *info, bool multi) override {
         const T *points = static_cast<const T *>(points_v);
         T *out = static_cast<T *>(out_v);
         LSSVM_REQUIRE(points != nullptr && npoints > 0, "The data points to predict must not be empty!");  // csvm.cpp:194
         LSSVM_REQUIRE(out != nullptr, "out must not be NULL");
+        LSSVM_REQUIRE(multi || nvec_ == 1, "this predictor holds more than one weight vector: use lssvm_mi355_predictor_predict_multi");
         lssvm_predict_info local{};
         local.f16_row_rel_error = -1.0;
         bool done = false;
@@ -445,19 +463,27 @@ class Predictor final : public PredictorBase {
             // what the resident form does not cover (fp64, more than 128 features, exponent scales beyond the norm expansion, a batch whose planes fail the f16 check or
             // that lies further from the support vectors' centre than the form chosen for them allows): the one-shot path, same result
             int w_valid = 0;
-            std::vector<T> w_tmp(nfeat_);
+            std::vector<T> w_tmp(nvec_ * nfeat_);
             if (sv_host_.empty()) fetch_support_vectors();
+            const auto one_shot = [&](const T *pts, T *values) {
+                if (multi) {
+                    predict_values_multi<T>(opt_, params_, sv_host_.data(), nsv_, nfeat_, alpha_host_.data(), rho_.data(), nvec_, w_tmp.data(), &w_valid, pts, npoints, values, &local);
+                } else {
+                    predict_values<T>(opt_, params_, sv_host_.data(), nsv_, nfeat_, alpha_host_.data(), rho_[0], w_tmp.data(), &w_valid, pts, npoints, values, &local);
+                }
+            };
             if (mem_kind == LSSVM_MEM_DEVICE) {  // (the one-shot entry point takes host buffers: a batch in HBM makes the round trip here -- the rare path)
                 select_device_checked(0);
-                std::vector<T> points_host(npoints * nfeat_), out_host(npoints);
+                std::vector<T> points_host(npoints * nfeat_), out_host(npoints * nvec_);
                 LSSVM_HIP_CHECK(hipMemcpy(points_host.data(), points, points_host.size() * sizeof(T), hipMemcpyDeviceToHost));
-                predict_values<T>(opt_, params_, sv_host_.data(), nsv_, nfeat_, alpha_host_.data(), rho_, w_tmp.data(), &w_valid, points_host.data(), npoints, out_host.data(), &local);
-                LSSVM_HIP_CHECK(hipMemcpy(out, out_host.data(), npoints * sizeof(T), hipMemcpyHostToDevice));
+                one_shot(points_host.data(), out_host.data());
+                LSSVM_HIP_CHECK(hipMemcpy(out, out_host.data(), out_host.size() * sizeof(T), hipMemcpyHostToDevice));
             } else {
-                predict_values<T>(opt_, params_, sv_host_.data(), nsv_, nfeat_, alpha_host_.data(), rho_, w_tmp.data(), &w_valid, points, npoints, out, &local);
+                one_shot(points, out);
             }
             local.resident = 0;
         }
+        if (!multi) local.vectors_per_launch = 0;  // (vectors_per_launch is the multi calls' report)
         if (info != nullptr) *info = local;
     }
 
@@ -466,26 +492,23 @@ class Predictor final : public PredictorBase {
         select_device_checked(0);
         hipStream_t s = nullptr;
         const double t0 = now_ms();
-        Event ev_a, ev_b;
-        ev_a.create(true);
-        ev_b.create(true);
+        const int nv = static_cast<int>(nvec_);
+        LaunchTimer timer(nvec_);
         DeviceMatrix<T> P;
         P.upload(points, mem_kind, npoints, nfeat_, 0, s);
         DevBuf<T> o;
-        o.alloc_zero(npoints, s);
+        o.alloc_zero(npoints * nvec_, s);
         LSSVM_HIP_CHECK(hipStreamSynchronize(s));
         const double t_kernel = now_ms();
-        LSSVM_HIP_CHECK(hipEventRecord(ev_a.e, s));
-        launch_predict_linear<T>(P, w_.p, rho_, o.p, s);
-        LSSVM_HIP_CHECK(hipEventRecord(ev_b.e, s));
+        for (int v = 0; v < nv; ++v) timer.timed(s, [&] { launch_predict_linear<T>(P, w_.p + static_cast<size_t>(v) * ldw_, rho_[static_cast<size_t>(v)], o.p + v, s, nv); });
         LSSVM_HIP_CHECK(hipGetLastError());
-        LSSVM_HIP_CHECK(hipMemcpyAsync(out, o.p, npoints * sizeof(T), mem_kind == LSSVM_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+        LSSVM_HIP_CHECK(hipMemcpyAsync(out, o.p, npoints * nvec_ * sizeof(T), mem_kind == LSSVM_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
         LSSVM_HIP_CHECK(hipStreamSynchronize(s));
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, ev_a.e, ev_b.e) == hipSuccess) info.kernel_ms = ms;
+        timer.sum_into(info);
         info.total_ms = now_ms() - t0;
         info.setup_ms = t_kernel - t0;
         info.resident = 1;
+        info.vectors_per_launch = 1;
     }
 
     /* fp32, rbf / polynomial, at most 128 features, a split Gram mode: the support vectors' side of the product, once */
@@ -511,15 +534,25 @@ class Predictor final : public PredictorBase {
         make_planes(opt_, params_, false, S_, nullptr, planesS_, nullptr, s);
         if (planesS_.mode == 0) return;
         num_jt_ = S_.rows_alloc / TILE;
-        a_.alloc_zero(S_.rows_alloc, s);
-        LSSVM_HIP_CHECK(hipMemcpyAsync(a_.p, alpha_host_.data(), nsv_ * sizeof(float), hipMemcpyHostToDevice, s));
-        // the (alpha_j | c_j) records: folded for rbf while the exponent terms stay small -- decided per batch from ITS exponent scale too, so both forms are kept
+        const size_t ra = static_cast<size_t>(S_.rows_alloc);
+        a_.alloc_zero(nvec_ * ra, s);  // [nvec][rows_alloc], exact zeros beyond the support vectors
+        LSSVM_HIP_CHECK(hipMemcpy2DAsync(a_.p, ra * sizeof(float), alpha_host_.data(), nsv_ * sizeof(float), nsv_ * sizeof(float), nvec_, hipMemcpyHostToDevice, s));
+        // The column records of every launch group, once.  Per pair (0,1), (2,3), ... the (alpha0_j | alpha1_j) record of the two-vector kernels -- folded for rbf, the
+        // form they exist in; per vector the (alpha_j | c_j) record of the one-vector kernels: for rbf every vector's (the only form an unfolded batch can use: that
+        // kernel reads c_j from the record's second half; a batch's OWN exponent scale decides between the forms), otherwise only that of the vector no pair holds
+        // (nvec odd; nvec == 1: the single-vector predictor's), and for rbf that vector's folded one-vector record as well.
         const int ncols = num_jt_ * TILE;
-        dc_.alloc_zero(static_cast<size_t>(num_jt_) * 256, s);
-        enqueue_pack_records(a_.p, cS_.p, ncols, dc_.p, 0, static_cast<const float *>(nullptr), s);
-        if (rbf && opt_.rbf_fold != 0) {
-            dc_folded_.alloc_zero(static_cast<size_t>(num_jt_) * 256, s);
-            enqueue_pack_records(a_.p, cS_.p, ncols, dc_folded_.p, 1, static_cast<const float *>(nullptr), s);
+        rec_ = static_cast<size_t>(num_jt_) * 256;
+        const bool fold = rbf && opt_.rbf_fold != 0;
+        dc_.alloc_zero(nvec_ * rec_, s);
+        for (size_t v = rbf ? 0 : nvec_ - nvec_ % 2; v < nvec_; ++v) enqueue_pack_records(a_.p + v * ra, cS_.p, ncols, dc_.p + v * rec_, 0, static_cast<const float *>(nullptr), s);
+        if (fold && nvec_ % 2 == 1) {
+            dc_folded_.alloc_zero(rec_, s);
+            enqueue_pack_records(a_.p + (nvec_ - 1) * ra, cS_.p, ncols, dc_folded_.p, 1, static_cast<const float *>(nullptr), s);
+        }
+        if (nvec_ >= 2 && (!rbf || fold)) {
+            dc2_.alloc_zero((nvec_ / 2) * rec_, s);
+            for (size_t g = 0; g < nvec_ / 2; ++g) enqueue_pack_records2(a_.p + 2 * g * ra, a_.p + (2 * g + 1) * ra, cS_.p, ncols, dc2_.p + g * rec_, fold ? 1 : 0, s);
         }
         LSSVM_HIP_CHECK(hipGetLastError());
         LSSVM_HIP_CHECK(hipStreamSynchronize(s));
@@ -600,7 +633,7 @@ class Predictor final : public PredictorBase {
         }
         lap("operand planes");
         const int num_ib = P.rows_alloc / TILE;
-        const bool folded = rbf && dc_folded_.p != nullptr && r2 <= FOLD_MAX_R2;
+        const bool folded = rbf && opt_.rbf_fold != 0 && r2 <= FOLD_MAX_R2;
         const bool poly_generic = params_.kernel_type == LSSVM_KERNEL_POLYNOMIAL && params_.degree != 2 && params_.degree != 3;
         const bool rbf_ok = !rbf || (folded && r2 <= 2.0 * PAIR_FOLD_MAX_C);
         const bool rect = !poly_generic && rbf_ok && opt_.mfma_shape >= 3 && num_ib >= PAIR_MIN_TILES;
@@ -608,17 +641,20 @@ class Predictor final : public PredictorBase {
         const int jc_tiles = opt_.j_chunk_tiles > 0 ? static_cast<int>(opt_.j_chunk_tiles)
                                                    : (rect ? static_cast<int>(rect_tiles) : static_cast<int>(std::min<long>(16, std::max<long>(2, (static_cast<long>(num_ib) * num_jt_ + 2048) / 4096))));
         const int num_jc = (num_jt_ + jc_tiles - 1) / jc_tiles;
+        // Two weight vectors per product launch wherever a pair record exists in the form this batch needs: the rectangular 256-row kernel under its conditions, the
+        // 128-row full-square kernels otherwise (polynomial of any degree, folded rbf).  Unfolded rbf keeps c_j in the record's second half: one vector per launch.
+        const int nv = static_cast<int>(nvec_);
+        const int per_launch = (nv >= 2 && dc2_.p != nullptr && (!rbf || folded)) ? 2 : 1;
+        const size_t part_plane = static_cast<size_t>(num_jc) * P.rows_alloc;
         DevBuf<float> partial, Kv, o;
-        partial.alloc_zero(static_cast<size_t>(num_jc) * P.rows_alloc, s);
+        partial.alloc_zero(per_launch * part_plane, s);
         Kv.alloc_zero(P.rows_alloc, s);
-        o.alloc_zero(npoints, s);
+        o.alloc_zero(npoints * nvec_, s);
         TileArgs<float> ta{};
         ta.Xr = P.data.p;
         ta.Xc = S_.data.p;
         ta.cr = cP.p;
         ta.cc = cS_.p;
-        ta.dvec = a_.p;
-        ta.dc = folded ? dc_folded_.p : dc_.p;
         ta.dc_folded = folded ? 1 : 0;
         ta.partial = partial.p;
         ta.part_stride = P.rows_alloc;
@@ -633,24 +669,35 @@ class Predictor final : public PredictorBase {
         set_launch_options(ta, opt_);
         RectSetup rect_setup;
         if (rect) setup_rect_launch(ta, rect_setup, planesP, P.rows_alloc, num_ib, num_jc, s);
-        Event ev_a, ev_b;
-        ev_a.create(true);
-        ev_b.create(true);
+        LaunchTimer timer(nvec_);
         LSSVM_HIP_CHECK(hipStreamSynchronize(s));
         lap(rect ? "slabs, 256-row launch set up" : "slabs");
         const double t_kernel = now_ms();
-        LSSVM_HIP_CHECK(hipEventRecord(ev_a.e, s));
-        launch_tile_kernel<float>(ta, params_.kernel_type, false, num_jc, s);
-        LSSVM_HIP_CHECK(hipEventRecord(ev_b.e, s));
-        hipLaunchKernelGGL(k_reduce_partials<float>, dim3((P.rows_alloc + 255) / 256), dim3(256), 0, s, partial.p, ta.part_stride, num_jc, 0, P.rows_alloc, Kv.p);
-        hipLaunchKernelGGL(k_sub_rho<float>, dim3((P.rows + 255) / 256), dim3(256), 0, s, Kv.p, P.rows, rho_, o.p, 1);
+        for (int v = 0; v < nv; v += per_launch) {
+            const int count = std::min(per_launch, nv - v);
+            if (v > 0 && ta.queue != nullptr) std::swap(ta.queue, ta.queue_next);  // (a persistent launch zeroes the OTHER set of counters)
+            ta.dvec = a_.p + static_cast<size_t>(v) * S_.rows_alloc;
+            if (count == 2) {
+                ta.dc = dc2_.p + static_cast<size_t>(v / 2) * rec_;
+            } else if (folded) {  // (folded and alone: the vector no pair holds)
+                ta.dc = dc_folded_.p;
+            } else {
+                ta.dc = dc_.p + static_cast<size_t>(v) * rec_;
+            }
+            ta.nvec = count;
+            ta.part_vstride = count == 2 ? static_cast<long>(part_plane) : 0;
+            timer.timed(s, [&] { launch_tile_kernel<float>(ta, params_.kernel_type, false, num_jc, s); });
+            for (int u = 0; u < count; ++u) {
+                hipLaunchKernelGGL(k_reduce_partials<float>, dim3((P.rows_alloc + 255) / 256), dim3(256), 0, s, partial.p + u * part_plane, ta.part_stride, num_jc, 0, P.rows_alloc, Kv.p);
+                hipLaunchKernelGGL(k_sub_rho<float>, dim3((P.rows + 255) / 256), dim3(256), 0, s, Kv.p, P.rows, rho_[static_cast<size_t>(v + u)], o.p + (v + u), nv);
+            }
+        }
         LSSVM_HIP_CHECK(hipGetLastError());
         lap("product, row sums");
-        LSSVM_HIP_CHECK(hipMemcpyAsync(out, o.p, npoints * sizeof(float), mem_kind == LSSVM_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+        LSSVM_HIP_CHECK(hipMemcpyAsync(out, o.p, npoints * nvec_ * sizeof(float), mem_kind == LSSVM_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
         LSSVM_HIP_CHECK(hipStreamSynchronize(s));
         lap("values downloaded");
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, ev_a.e, ev_b.e) == hipSuccess) info.kernel_ms = ms;
+        timer.sum_into(info);
         info.total_ms = now_ms() - t0;
         info.setup_ms = t_kernel - t0;
         info.gram_mode = planesS_.mode;
@@ -658,28 +705,33 @@ class Predictor final : public PredictorBase {
         info.rbf_exponent_scale = r2;
         if (info.f16_row_rel_error < 0.0) info.f16_row_rel_error = planesS_.f16_row_rel_error;
         info.resident = 1;
+        info.vectors_per_launch = per_launch;
         return true;
     }
 
     Options opt_;
     lssvm_params params_;
-    size_t nsv_, nfeat_;
-    T rho_;
+    size_t nsv_, nfeat_, nvec_;
+    std::vector<T> rho_;
     std::vector<T> sv_host_, alpha_host_, w_host_;  // the one-shot path's inputs
-    DevBuf<T> w_;
+    DevBuf<T> w_;                                   // linear kernel: [nvec][ldw_]
+    size_t ldw_ = 0;
     // fp32 resident form
     bool resident_ = false;
     DeviceMatrix<float> S_;
-    DevBuf<float> mean_, cS_, a_, dc_, dc_folded_, raw_;
+    DevBuf<float> mean_, cS_, a_, raw_;
+    DevBuf<float> dc_, dc_folded_, dc2_;  // column records: [nvec][rec_] per vector, the folded one of an unpaired last vector, [nvec / 2][rec_] per pair
+    size_t rec_ = 0;
     PlaneSet planesS_;
     double r2_sv_ = 0.0;
     float scale_ = 1.0f;
     int num_jt_ = 0;
 };
 
-std::unique_ptr<PredictorBase> make_predictor(const Options &opt, const lssvm_params &params, int dtype, const void *sv, size_t nsv, size_t nfeat, const void *alpha, double rho) {
-    if (dtype == LSSVM_DTYPE_F32) return std::make_unique<Predictor<float>>(opt, params, static_cast<const float *>(sv), nsv, nfeat, static_cast<const float *>(alpha), static_cast<float>(rho));
-    return std::make_unique<Predictor<double>>(opt, params, static_cast<const double *>(sv), nsv, nfeat, static_cast<const double *>(alpha), rho);
+std::unique_ptr<PredictorBase> make_predictor(const Options &opt, const lssvm_params &params, int dtype, const void *sv, size_t nsv, size_t nfeat, const void *alpha, const double *rho,
+                                              size_t nvec) {
+    if (dtype == LSSVM_DTYPE_F32) return std::make_unique<Predictor<float>>(opt, params, static_cast<const float *>(sv), nsv, nfeat, static_cast<const float *>(alpha), rho, nvec);
+    return std::make_unique<Predictor<double>>(opt, params, static_cast<const double *>(sv), nsv, nfeat, static_cast<const double *>(alpha), rho, nvec);
 }
 
 }  // namespace lssvm

@@ -603,9 +603,14 @@ void calculate_w(const T *sv, size_t nsv, size_t nfeat, const T *alpha, T *w_out
 struct PredictorBase {
     int dtype = 0;
     virtual ~PredictorBase() = default;
-    virtual void predict(const void *points, int mem_kind, size_t npoints, void *out, lssvm_predict_info *info) = 0;  // points AND out of mem_kind
+    /* points AND out of mem_kind; out [npoints][the predictor's number of weight vectors].  `multi`: the call is lssvm_mi355_predictor_predict_multi -- the same values, and info->vectors_per_launch
+     * reports the largest number of vectors one product launch evaluated; without it (lssvm_mi355_predictor_predict) that field is 0 and a predictor of several
+     * vectors refuses the call */
+    virtual void predict(const void *points, int mem_kind, size_t npoints, void *out, lssvm_predict_info *info, bool multi) = 0;
 };
-std::unique_ptr<PredictorBase> make_predictor(const Options &opt, const lssvm_params &params, int dtype, const void *sv, size_t nsv, size_t nfeat, const void *alpha, double rho);
+/* alpha [nvec][nsv], rho [nvec] */
+std::unique_ptr<PredictorBase> make_predictor(const Options &opt, const lssvm_params &params, int dtype, const void *sv, size_t nsv, size_t nfeat, const void *alpha, const double *rho,
+                                              size_t nvec);
 
 void check_params(const lssvm_params *params);
 /* weighted LS-SVM: `weights` holds num_points entries, each finite and > 0, whose diagonal terms 1/(C w_i) are finite in the real type T */

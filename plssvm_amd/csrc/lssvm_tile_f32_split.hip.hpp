@@ -47,10 +47,17 @@ __device__ __forceinline__ f32x4 plane_mfma(const bf16x8 &av, const bf16x8 &bv, 
  * the result has col = l & 15, row = 4 (l >> 4) + reg.
  * A step (= one plane of one 64-feature chunk) is processed in four groups mm = (k32 step kk = mm >> 1, column half cbh = mm & 1) of four column
  * blocks each, so that the B fragments stay double buffered in 2 x 16 registers and the hand-over sits in the middle of a step as before.
+ *
+ * NV (full-square variant only): weight vectors per pass, as pair_body's NV (lssvm_tile_f32_pair.hip.hpp) -- the resident predictor's batches below the rectangular
+ * 256-row kernel's 64 row blocks.  NV = 2: the record of a column tile carries (d0_j | d1_j) (k_pack_dc2; folded rbf: both times 2^c_j), the kernel function is
+ * evaluated once per element and feeds two scalar fma chains, and the row sums of vector v go to plane v of `partial` (TileArgs::part_vstride apart).  Per vector
+ * the chain of operations is the one of NV = 1.  Only where the full-square kernel does not read the record's second half itself: not the unfolded rbf form (c_j)
+ * and not the grid planes (sigma^2 ch_j).
  */
-template <int KT, int NK64, bool SYM, bool HAND, int PL>
+template <int KT, int NK64, bool SYM, bool HAND, int PL, int NV = 1>
 __device__ __forceinline__ void s6w_body(const TileArgs<float> &a) {
     static_assert(PL == 3 || PL == 2, "three bf16 planes (bf16x6) or two f16 planes (f16x3)");
+    static_assert(NV == 1 || (NV == 2 && !SYM && KT != KT_RBF && KT != KT_RBFG), "two weight vectors per pass: full square, and the second half of the record must be free");
     constexpr bool F16 = PL == 2;
     // KT_RBFG ("grid planes", round 5; f16, hand-scheduled groups only): THREE column planes (h | s1 | s2, all carrying the scale sigma) and FOUR phases per tile, each
     // over all 64-feature chunks:   0: h x h      1: h x (s1, s2)      2: s1 x (h, s1)      3: s2 x h      (column plane x row planes)
@@ -195,9 +202,11 @@ __device__ __forceinline__ void s6w_body(const TileArgs<float> &a) {
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) rd_off[kk] = r * 128 + (((4 * kk + g) ^ ((r >> 1) & 7)) << 4);
 
-    float rowpart[8];
+    float rowpart[NV][8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) rowpart[i] = 0.0f;
+    for (int v = 0; v < NV; ++v)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) rowpart[v][i] = 0.0f;
     f32x4 acc[2][8];
     f32x4 civ0[2] = { { 0.f, 0.f, 0.f, 0.f }, { 0.f, 0.f, 0.f, 0.f } };  // KT_RBFF: c_i of the wave's two row blocks, the C operand of the first MFMAs
     bool padcol[8] = { false, false, false, false, false, false, false, false };
@@ -439,7 +448,9 @@ __device__ __forceinline__ void s6w_body(const TileArgs<float> &a) {
                 const float *dcr = reinterpret_cast<const float *>(dcs + (t % V2_DC_SLOTS) * 1024);  // the record stays valid until tile t + 4 is announced
 #pragma unroll
                 for (int cb = 0; cb < 8; ++cb) {
-                    const float djv = dcr[cb * 16 + r];
+                    float djv[NV];
+#pragma unroll
+                    for (int v = 0; v < NV; ++v) djv[v] = dcr[v * TILE + cb * 16 + r];
 #pragma unroll
                     for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
@@ -449,10 +460,15 @@ __device__ __forceinline__ void s6w_body(const TileArgs<float> &a) {
                                 if (padcol[cb]) kv = 0.0f;
                             }
                             if (LSSVM_DBG(a, 256)) {  // bit 256: no fmas (one add keeps the value alive)
-                                rowpart[4 * rb + e] += kv;
+                                rowpart[0][4 * rb + e] += kv;
                                 continue;
                             }
-                            rowpart[4 * rb + e] = fmaf(kv, djv, rowpart[4 * rb + e]);
+#pragma unroll
+                            for (int v = 0; v < NV; ++v) {
+                                rowpart[v][4 * rb + e] = fmaf(kv, djv[v], rowpart[v][4 * rb + e]);
+                                // (two vectors: scalar v_fma_f32 chains, as in pair_body -- every chain's value passes through an empty statement the vectoriser cannot see into)
+                                if constexpr (NV > 1) asm("" : "+v"(rowpart[v][4 * rb + e]));
+                            }
                             // column sums: rows (e, e + 1) of a block as ONE v_pk_fma_f32 (the row sums above are packed by the compiler itself;
                             // these it leaves scalar -- eight dependent chains of eight -- unless the pairs are spelled out)
                             if constexpr (COLS) {
@@ -508,20 +524,23 @@ __device__ __forceinline__ void s6w_body(const TileArgs<float> &a) {
 
     // every lane group owns its rows: reduce over the 16 columns of the group and store
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        float v = rowpart[i];
+    for (int vi = 0; vi < NV * 8; ++vi) {
+        const int i = vi & 7;
+        float v = rowpart[vi >> 3][i];
         v += __shfl_xor(v, 8);
         v += __shfl_xor(v, 4);
         v += __shfl_xor(v, 2);
         v += __shfl_xor(v, 1);
         if constexpr (KT == KT_LINEAR && F16) v *= a.out_scale;
         if constexpr (GRID) v *= a.er[row0 + wave * 32 + 16 * (i >> 2) + 4 * g + (i & 3)];  // the row's folded factor E_i, once per work item
-        rowpart[i] = v;
+        rowpart[vi >> 3][i] = v;
     }
     if (r == 0) {
         float *dst = a.partial + static_cast<size_t>(jc) * a.part_stride + ibl * TILE + wave * 32 + 4 * g;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) dst[16 * (i >> 2) + (i & 3)] = rowpart[i];
+        for (int v = 0; v < NV; ++v)
+#pragma unroll
+            for (int i = 0; i < 8; ++i) dst[(NV > 1 ? static_cast<size_t>(v) * a.part_vstride : 0) + 16 * (i >> 2) + (i & 3)] = rowpart[v][i];
     }
 }
 
@@ -544,6 +563,17 @@ template <int KT, int NK64, bool SYM>
 __global__ __launch_bounds__(TILE_THREADS, 2) LSSVM_HAND_VGPR_CAP void tile_matvec_f32_s6h(const TileArgs<float> a) {
     static_assert(NK64 <= 2, "the hand-scheduled groups assume the 256-register budget of two waves per SIMD");
     s6w_body<KT, NK64, SYM, true, 3>(a);
+}
+/* two weight vectors per pass (NV = 2, full square only; tile_launch_f32v2.hip): hand-scheduled groups, and the compiler-scheduled ones for the run-time integer power */
+template <int KT, int NK64>
+__global__ __launch_bounds__(TILE_THREADS, 2) LSSVM_HAND_VGPR_CAP void tile_matvec_f32_s6h_nv2(const TileArgs<float> a) {
+    static_assert(NK64 <= 2, "the hand-scheduled groups assume the 256-register budget of two waves per SIMD");
+    s6w_body<KT, NK64, false, true, 3, 2>(a);
+}
+template <int KT, int NK64>
+__global__ __launch_bounds__(TILE_THREADS, 2) void tile_matvec_f32_s6w_nv2(const TileArgs<float> a) {
+    static_assert(NK64 <= 2, "two weight vectors per pass: at most 128 features");
+    s6w_body<KT, NK64, false, false, 3, 2>(a);
 }
 /* "f16x3": the same kernels on TWO f16 planes (x = hi + mid, 11 + 11 significant bits, k_split_f16x2) and the three plane products
  * hi*hi + hi*mid + mid*hi on v_mfma_f32_16x16x32_f16 -- half the matrix-core work of bf16x6 and two thirds of its column stream.  What is
@@ -573,6 +603,16 @@ template <int KT, int NK64, bool SYM>
 __global__ __launch_bounds__(TILE_THREADS, 2) LSSVM_HAND_VGPR_CAP void tile_matvec_f32_f3h(const TileArgs<float> a) {
     static_assert(NK64 <= F16_HAND_MAX_NK64, "the hand-scheduled groups assume the 256-register budget of two waves per SIMD");
     s6w_body<KT, NK64, SYM, true, 2>(a);
+}
+template <int KT, int NK64>
+__global__ __launch_bounds__(TILE_THREADS, 2) LSSVM_HAND_VGPR_CAP void tile_matvec_f32_f3h_nv2(const TileArgs<float> a) {
+    static_assert(NK64 <= F16_HAND_MAX_NK64, "the hand-scheduled groups assume the 256-register budget of two waves per SIMD");
+    s6w_body<KT, NK64, false, true, 2, 2>(a);
+}
+template <int KT, int NK64>
+__global__ __launch_bounds__(TILE_THREADS, 2) void tile_matvec_f32_f3w_nv2(const TileArgs<float> a) {
+    static_assert(NK64 <= 2, "two weight vectors per pass: at most 128 features");
+    s6w_body<KT, NK64, false, false, 2, 2>(a);
 }
 
 }  // namespace lssvm

@@ -232,6 +232,8 @@ void launch_f16_tile_kernel_sym(const TileArgs<float> &a, int kernel_type, hipSt
 void launch_f16_tile_kernel(const TileArgs<float> &a, int kernel_type, dim3 grid, hipStream_t s) {
     if (a.items != nullptr) {
         launch_f16_tile_kernel_sym(a, kernel_type, s);
+    } else if (a.nvec == 2) {
+        launch_nv2_tile_kernel(a, kernel_type, grid, s);
     } else {
         launch_f3<false>(a, kernel_type, grid, s);
     }

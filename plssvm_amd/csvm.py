@@ -237,6 +237,26 @@ class MI355CSVM(CSVM):
     def predict_values_multi(self, params, support_vectors, alphas, rhos, ws, predict_points):
         return backend.predict_values_multi(params, support_vectors, alphas, rhos, ws, predict_points, options=self._options)
 
+    def decision_values_resident(self, model, X):
+        """The decision values ``f[i, c]`` of a :class:`plssvm_amd.multiclass.OneVsAllModel` with the model RESIDENT in HBM from the first call on
+        (``lssvm_mi355_predictor_create_multi``): later calls with the same model upload only their points.  The predictor is cached on the model and made again (the old
+        one closed) under the rule of :meth:`predict`: another backend object, changed option values, kernel parameters, another support-vector array (by identity),
+        ``alpha`` (by value) or ``rho``."""
+        sv = model.support_vectors
+        opts = tuple(self._options.get(n) if self._options is not None else _capi.get_option(n) for n in _capi.OPTION_NAMES)
+        prm = model.params
+        params = (int(prm.kernel_type), prm.degree, prm.gamma, prm.coef0)
+        cached = getattr(model, "_predictor", None)
+        if (cached is None or cached["owner"] is not self or cached["options"] != opts or cached["params"] != params or cached["sv"] is not sv
+                or not np.array_equal(cached["alpha"], model.alpha) or not np.array_equal(cached["rho"], model.rho)):
+            if cached is not None:
+                cached["predictor"].close()  # (its HBM: nothing else holds it)
+            alpha, rho = np.array(model.alpha, copy=True), np.array(model.rho, copy=True)
+            cached = {"owner": self, "options": opts, "params": params, "sv": sv, "alpha": alpha, "rho": rho,
+                      "predictor": backend.Predictor(model.params, sv, alpha, rho, options=self._options)}
+            model._predictor = cached
+        return cached["predictor"].predict(np.asarray(X, dtype=sv.dtype))
+
     def predict(self, model: Model, data: DataSet):
         """csvm::predict (csvm.hpp:322-342) with the model RESIDENT in HBM from the first call on (``lssvm_mi355_predictor_*``): later calls with the same model upload only
         their points.  Same labels as the base class's one-shot ``predict_values`` with the state of the moment: the resident predictor is made again (and the old one

@@ -3,7 +3,8 @@
 A model of ``k`` classes is ``k`` binary classifiers over the SAME training points: classifier ``c`` is trained on ``y = +1`` for class ``c`` and ``-1`` for every
 other class, with the same point weights in every classifier.  Its decision value is ``f_c(x) = sum_i alpha[c, i] k(x_i, x) - rho[c]``; the predicted class is
 ``classes[argmax_c f_c(x)]``, ties to the lowest index.  All ``k`` weight vectors share their support vectors, which is what the backend's
-``solve_systems_of_linear_equations`` (one resident problem) and ``predict_values_multi`` (one preparation, two weight vectors per pass over the Gram tiles) use.
+``solve_systems_of_linear_equations`` (one resident problem), ``predict_values_multi`` (one preparation, two weight vectors per pass over the Gram tiles) and the
+resident predictor of a one-vs-all model (``MI355CSVM.decision_values_resident``: the model stays in HBM across calls) use.
 """
 
 from __future__ import annotations
@@ -57,7 +58,11 @@ def fit_one_vs_all(svm, params, X, y, classes, epsilon: float, max_iter: int | N
 
 
 def decision_values(svm, model: OneVsAllModel, X) -> np.ndarray:
-    """``f[i, c]`` of every row of ``X``: shape ``(n, k)``."""
+    """``f[i, c]`` of every row of ``X``: shape ``(n, k)``.  A backend object that offers ``decision_values_resident`` (the MI355X backend) keeps the model in HBM across
+    calls; every other one runs its ``predict_values_multi``."""
+    resident = getattr(svm, "decision_values_resident", None)
+    if resident is not None:
+        return resident(model, X)
     values, w = svm.predict_values_multi(model.params, model.support_vectors, model.alpha, model.rho, model.w, np.asarray(X, dtype=model.support_vectors.dtype))
     if w is not None:
         model.w = w
