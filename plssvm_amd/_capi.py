@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = [
     "lssvm_mi355_calculate_w_f32", "lssvm_mi355_calculate_w_f64",
     "lssvm_mi355_shard_blocks", "lssvm_mi355_set_shard_weights", "lssvm_mi355_problem_rebalance", "lssvm_mi355_comm_get_unique_id", "lssvm_mi355_comm_init", "lssvm_mi355_comm_destroy",
     "lssvm_mi355_problem_create", "lssvm_mi355_problem_create_multi", "lssvm_mi355_problem_ipc_export", "lssvm_mi355_problem_ipc_connect", "lssvm_mi355_problem_destroy", "lssvm_mi355_problem_get_q", "lssvm_mi355_problem_matvec",
+    "lssvm_mi355_problem_matvec_pair", "lssvm_mi355_problem_solve_lockstep",
     "lssvm_mi355_cg_begin", "lssvm_mi355_cg_step", "lssvm_mi355_cg_finish", "lssvm_mi355_problem_synchronize", "lssvm_mi355_problem_info",
     "lssvm_mi355_measure_bf16_mfma_ceiling", "lssvm_mi355_comm_library_path", "lssvm_mi355_set_io_threads", "lssvm_mi355_set_option", "lssvm_mi355_get_option",
     "lssvm_mi355_libsvm_open", "lssvm_mi355_libsvm_fill_f32", "lssvm_mi355_libsvm_fill_f64", "lssvm_mi355_libsvm_close",
@@ -130,6 +131,18 @@ def predictor_multi_entry(name: str):
             fn.argtypes = [C.POINTER(C.c_void_p), C.POINTER(LssvmParams), C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.POINTER(C.c_double), C.c_size_t, C.c_void_p]
         else:
             fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.POINTER(LssvmPredictInfo)]
+        fn.restype = C.c_int
+    return fn
+
+
+def lockstep_entry(name: str):
+    """``lssvm_mi355_problem_solve_lockstep`` / ``lssvm_mi355_problem_matvec_pair`` with its argument types.  Bound at the first call, like the weighted entry points."""
+    fn = getattr(lib, name)
+    if fn.argtypes is None:
+        if name == "lssvm_mi355_problem_solve_lockstep":
+            fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_uint64, C.c_void_p, C.POINTER(C.c_double), C.POINTER(LssvmCgInfo), C.POINTER(C.c_uint64)]
+        else:
+            fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(C.c_int)]
         fn.restype = C.c_int
     return fn
 

@@ -400,6 +400,34 @@ class ResidentProblem:
         check(lib.lssvm_mi355_problem_matvec(self._h, ptr(d), ptr(out), C.c_double(add)))
         return out
 
+    def matvec_pair(self, d0, d1, ret0, ret1, add: float = 1.0):
+        """:meth:`matvec` for two vectors (``lssvm_mi355_problem_matvec_pair``): returns ``(out0, out1, two_vector)`` -- each result the bits of :meth:`matvec` for that
+        vector; ``two_vector`` says whether one pass over the Gram tiles served both (fp64, one device, the symmetric resident-row-panel kernel) or two single passes ran."""
+        ds = [np.ascontiguousarray(d, dtype=self.dtype) for d in (d0, d1)]
+        outs = [np.array(ret, dtype=self.dtype, copy=True) for ret in (ret0, ret1)]
+        for v in ds + outs:
+            if not (v.ndim == 1 and v.size == self.num_points - 1):
+                raise InvalidParameterError(f"Sizes mismatch!: {v.size} != {self.num_points - 1}")
+        two = C.c_int(0)
+        check(_capi.lockstep_entry("lssvm_mi355_problem_matvec_pair")(self._h, ptr(ds[0]), ptr(ds[1]), ptr(outs[0]), ptr(outs[1]), add, C.byref(two)))
+        return outs[0], outs[1], bool(two.value)
+
+    def solve_lockstep(self, B, eps: float, max_iter: int):
+        """``k`` right-hand sides (``B``: ``k x num_points``) in lockstep on this problem (``lssvm_mi355_problem_solve_lockstep``): every one runs the recipe of
+        :meth:`cg_begin` / :meth:`cg_step` / :meth:`cg_finish`, and where the two-vector kernel applies one pass over the Gram tiles serves two of them per iteration.
+        Returns ``(alphas[k, num_points], rhos[k], infos, passes)`` -- per right-hand side the bits of a one-shot solve; ``passes = (two-vector, single-vector)`` Gram
+        passes."""
+        B = np.ascontiguousarray(B, dtype=self.dtype)
+        if B.ndim != 2 or B.shape[0] == 0 or B.shape[1] != self.num_points:
+            raise InvalidParameterError(f"The number of data points in the matrix A ({self.num_points}) and the values in every right hand side vector ({B.shape[-1] if B.ndim else 0}) must be the same!")
+        k = B.shape[0]
+        alphas = np.zeros_like(B)
+        rhos = np.zeros(k, dtype=np.float64)
+        infos = (LssvmCgInfo * k)()
+        passes = (C.c_uint64 * 2)()
+        check(_capi.lockstep_entry("lssvm_mi355_problem_solve_lockstep")(self._h, ptr(B), k, eps, int(max_iter), ptr(alphas), rhos.ctypes.data_as(C.POINTER(C.c_double)), infos, passes))
+        return alphas, rhos.astype(self.dtype), [info.as_dict() for info in infos], (int(passes[0]), int(passes[1]))
+
     def cg_begin(self, y, eps: float):
         y = np.ascontiguousarray(y, dtype=self.dtype)
         if y.size != self.num_points:

@@ -508,6 +508,27 @@ int lssvm_mi355_problem_set_weights(lssvm_mi355_problem *p, const double *weight
 int lssvm_mi355_problem_matvec(lssvm_mi355_problem *p, const void *d, void *ret_inout, double add) {
     return guarded([&] { impl_of(p)->matvec(d, ret_inout, add); });
 }
+int lssvm_mi355_problem_matvec_pair(lssvm_mi355_problem *p, const void *d0, const void *d1, void *ret0_inout, void *ret1_inout, double add, int *two_vector_out) {
+    return guarded([&] {
+        LSSVM_REQUIRE(p != nullptr, "problem handle must not be NULL");
+        LSSVM_REQUIRE(d0 != nullptr && d1 != nullptr && ret0_inout != nullptr && ret1_inout != nullptr, "The d / ret arrays may not be empty!");  // csvm.cpp:284-286
+        LSSVM_REQUIRE(add == 1.0 || add == -1.0, "add must either be -1.0 or 1.0, but is " + std::to_string(add) + "!");                       // svm_kernel.cpp:28
+        impl_of(p)->matvec_pair(d0, d1, ret0_inout, ret1_inout, add, two_vector_out);
+    });
+}
+int lssvm_mi355_problem_solve_lockstep(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out,
+                                       lssvm_cg_info *infos_out, uint64_t passes_out[2]) {
+    return guarded([&] {
+        // (before any device work; the solver repeats the tests that need the real type)
+        LSSVM_REQUIRE(p != nullptr, "problem handle must not be NULL");
+        LSSVM_REQUIRE(num_rhs > 0, "The number of right hand sides must be greater than 0!");
+        LSSVM_REQUIRE(Y != nullptr, "The number of data points in the matrix A and the values in the right hand side vector must be the same!");  // csvm.cpp:76
+        LSSVM_REQUIRE(eps > 0.0, "The stopping criterion in the CG algorithm must be greater than 0.0, but is " + std::to_string(eps) + "!");      // csvm.cpp:77
+        LSSVM_REQUIRE(max_iter > 0, "The number of CG iterations must be greater than 0!");                                                      // csvm.cpp:78
+        LSSVM_REQUIRE(alphas_out != nullptr && rhos_out != nullptr, "alpha_out / rho_out must not be NULL");
+        impl_of(p)->solve_lockstep(Y, num_rhs, eps, max_iter, alphas_out, rhos_out, infos_out, passes_out);
+    });
+}
 int lssvm_mi355_cg_begin(lssvm_mi355_problem *p, const void *y, double eps) {
     return guarded([&] { impl_of(p)->cg_begin(y, eps); });
 }

@@ -134,6 +134,20 @@ __global__ void k_pack_dc_f64(const double *__restrict__ dvec, const double *__r
     dc[static_cast<size_t>(st) * 128 + l] = dvec[j];
     dc[static_cast<size_t>(st) * 128 + 64 + l] = (cc != nullptr) ? cc[j] : 0.0;
 }
+/* ... of its two-vector instance: dc[st][0..63] = d0, dc[st][64..127] = d1, dc[st][128..191] = c; clears both result vectors, as k_pack_dc_f64 does for one */
+__global__ void k_pack_dc2_f64(const double *__restrict__ dvec0, const double *__restrict__ dvec1, const double *__restrict__ cc, int ncols_padded, double *__restrict__ dc,
+                               double *__restrict__ zero0, double *__restrict__ zero1, int nzero) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < nzero) {
+        zero0[j] = 0.0;
+        zero1[j] = 0.0;
+    }
+    if (j >= ncols_padded) return;
+    const int st = j >> 6, l = j & 63;
+    dc[static_cast<size_t>(st) * 192 + l] = dvec0[j];
+    dc[static_cast<size_t>(st) * 192 + 64 + l] = dvec1[j];
+    dc[static_cast<size_t>(st) * 192 + 128 + l] = (cc != nullptr) ? cc[j] : 0.0;
+}
 #endif  // LSSVM_KERNELS_SETUP
 
 /* =====================================================================================================================

@@ -1260,9 +1260,102 @@ PackDc<T> Problem<T>::pack_for_d(bool zero_first) {
 
 template <typename T>
 void Problem<T>::enqueue_sum_and_qdot(const T *v_dev, int slot_sum, int slot_q) {
-    hipLaunchKernelGGL(k_sum_and_qdot<T>, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, stream_.s, v_dev, q_.p, n_, part(PART_SUMS));
-    hipLaunchKernelGGL(k_finish2, dim3(1), dim3(RED_THREADS), 0, stream_.s, part(PART_SUMS), sc_.p, slot_sum, slot_q);
+    enqueue_sum_and_qdot(v_dev, part(PART_SUMS), sc_.p, slot_sum, slot_q);
+}
+template <typename T>
+void Problem<T>::enqueue_sum_and_qdot(const T *v_dev, double *part_sums, double *sc, int slot_sum, int slot_q) {
+    hipLaunchKernelGGL(k_sum_and_qdot<T>, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, stream_.s, v_dev, q_.p, n_, part_sums);
+    hipLaunchKernelGGL(k_finish2, dim3(1), dim3(RED_THREADS), 0, stream_.s, part_sums, sc, slot_sum, slot_q);
     LSSVM_HIP_CHECK(hipGetLastError());
+}
+
+/* ------------------------------------------------------------------ lanes ------------------------------------------------------------------ */
+template <typename T>
+typename Problem<T>::Lane &Problem<T>::lane(size_t k) {
+    activate();
+    while (lanes_.size() <= k) {
+        auto l = std::make_unique<Lane>();
+        for (DevBuf<T> *v : { &l->b, &l->x, &l->r, &l->d, &l->Ad, &l->Kv }) v->alloc_zero(static_cast<size_t>(nvec_) + TILE, stream_.s);  // (as the problem's own vectors)
+        l->y.alloc_zero(N_, stream_.s);
+        l->part.alloc_zero(static_cast<size_t>(PART_REGIONS) * RED_BLOCKS * 2, stream_.s);
+        l->sc.alloc_zero(SC_COUNT, stream_.s);
+        l->host_sc.alloc(SC_COUNT);
+        l->host_delta.alloc_mapped(1);
+        lanes_.push_back(std::move(l));
+    }
+    return *lanes_[k];
+}
+
+/* The (kernel function, chunk count) instantiations of the two-vector kernel that are dispatched: those whose pass was measured to take less than two single-vector
+ * passes by more than the single-vector kernel's own run-to-run spread (tests/tools/lockstep_timing.py, profiles/lockstep_f64.json).  All 60 do: 0.507 ... 0.596 of two
+ * passes at 30 000 points, the worst ratio + spread 0.667 (linear, one chunk) -- an instantiation that stops doing so is named here and falls back to two single passes. */
+static bool pair_kernel_routed(int /*kernel_type*/, int /*degree*/, int /*kchunks*/) {
+    return true;
+}
+
+template <typename T>
+bool Problem<T>::pair_kernel_applies() const {
+    if constexpr (std::is_same_v<T, double>) {
+        return world_ == 1 && sym_ && dc_.p != nullptr && !wide_nl_ && !wide_linear_ && num_ib_ > 0
+               && pair_kernel_routed(tile_params_.kernel_type, tile_params_.degree, X_.ldx / F64_KC);
+    } else {
+        return false;
+    }
+}
+
+template <typename T>
+void Problem<T>::enqueue_apply_K_lanes(const T *v0, T *Kv0, const T *v1, T *Kv1, hipEvent_t ev_begin, hipEvent_t ev_end) {
+    if constexpr (std::is_same_v<T, double>) {
+        LSSVM_REQUIRE(pair_kernel_applies(), "no two-vector tile kernel on this problem");
+        hipStream_t st = stream_.s;
+        const int ncols = num_tiles_ * TILE;
+        const int nzero = static_cast<int>(nvec_);  // (the symmetric variant ADDS rows and mirrored columns into K*v)
+        const int nthreads = std::max(ncols, nzero);
+        TileArgs<T> a = tile_args(v0);
+        if (v1 != nullptr) {
+            if (pair_dc_.p == nullptr) {
+                pair_dc_.alloc_zero(static_cast<size_t>(num_tiles_) * 2 * 192, st);  // (d0_j | d1_j | c_j): 192 reals per 64-column sub-tile
+                pair_partial_.alloc_zero(2 * partial_.count, st);
+                pair_colslab_.alloc_zero(2 * colslab_.count, st);
+            }
+            hipLaunchKernelGGL(k_pack_dc2_f64, dim3((nthreads + 255) / 256), dim3(256), 0, st, v0, v1, c_.p, ncols, pair_dc_.p, Kv0, Kv1, nzero);
+            a.nvec = 2;
+            a.dvec1 = v1;
+            a.dc = pair_dc_.p;
+            a.partial = pair_partial_.p;
+            a.part_vstride = static_cast<long>(partial_.count);
+            a.colslab = pair_colslab_.p;
+            a.colslab_vstride = static_cast<long>(colslab_.count);
+        } else {
+            d_packed_ = false;  // (dc_ is about to hold another vector's records)
+            hipLaunchKernelGGL(k_pack_dc_f64, dim3((nthreads + 255) / 256), dim3(256), 0, st, v0, c_.p, ncols, dc_.p, Kv0, nzero);
+        }
+        const int nrows = num_ib_ * TILE;
+        T *const Kv[2] = { Kv0, Kv1 };
+        const int nv = v1 != nullptr ? 2 : 1;
+        if (ev_begin != nullptr) LSSVM_HIP_CHECK(hipEventRecord(ev_begin, st));
+        // the band loop of enqueue_apply_K_local (no feature panels here); every reduction runs per vector on that vector's planes, into that vector's K*v
+        for (const Band &band : bands_) {
+            TileArgs<T> ab = a;
+            ab.items = items_.p + band.item_begin;
+            ab.num_items = band.item_count;
+            ab.pair_origin = band.pair_origin;
+            launch_tile_kernel<T>(ab, tile_params_.kernel_type, rbf_direct_, num_jc_, st);
+            if (&band == &bands_.back() && ev_end != nullptr) LSSVM_HIP_CHECK(hipEventRecord(ev_end, st));
+            if (band.ib_end > 1) {
+                for (int u = 0; u < nv; ++u) {
+                    hipLaunchKernelGGL((k_reduce_colslab<T, 64>), dim3(2 * (band.ib_end - 1)), dim3(1024), 0, st, a.colslab + u * a.colslab_vstride, band.pair_origin, band.ib_begin, band.ib_end, 1, Kv[u]);
+                }
+            }
+        }
+        for (int u = 0; u < nv; ++u) {
+            hipLaunchKernelGGL(k_reduce_partials_sym<T>, dim3((nrows + 255) / 256), dim3(256), 0, st, a.partial + u * a.part_vstride, a.part_stride, jc_tiles_, jc_head_tiles_, jc_head_count_, ib_begin_, nrows, Kv[u], 1);
+        }
+        LSSVM_HIP_CHECK(hipGetLastError());
+    } else {
+        (void) v0, (void) Kv0, (void) v1, (void) Kv1, (void) ev_begin, (void) ev_end;
+        throw Error(LSSVM_ERR_INTERNAL, "lanes exist in fp64 only");
+    }
 }
 
 /* Weighted LS-SVM: Abar(w)_ij = k(x_i,x_j) + delta_ij / (C w_i) + QA_cost(w) - q_i - q_j with QA_cost(w) = k(x_last,x_last) + 1 / (C w_last).  Every diagonal term is

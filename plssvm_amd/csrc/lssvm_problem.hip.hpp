@@ -333,6 +333,7 @@ class Problem {
     void build_shard_lists(hipStream_t st);
     PackDc<T> pack_for_d(bool zero_first);  // what k_update_d needs to pack the records of d_ (dc == NULL: this problem packs per matvec); marks them as present
     void enqueue_sum_and_qdot(const T *v_dev, int slot_sum, int slot_q);
+    void enqueue_sum_and_qdot(const T *v_dev, double *part_sums, double *sc, int slot_sum, int slot_q);  // ... into a lane's partial sums and scalars
     /* weighted LS-SVM (lssvm_mi355_problem_set_weights): inv_cw_ and QA_cost_ from the weights of all N points (validated by the caller), or back to the
      * unweighted system for NULL */
     void set_weights(const double *weights);
@@ -363,6 +364,22 @@ class Problem {
             return dc_.p != nullptr ? 130e12 * sym : 45e12;
         }
     }
+
+    /* ---- lanes (Solver<T>::solve_lockstep, matvec_pair): the CG state of ONE right-hand side beside the problem's own -- the vectors b, x, r, d, Ad, K*v, the scalars and
+     * partial-sum slots, a mapped host word for its delta.  Allocated on first use, freed with the problem; the single-vector members below are not involved. ---- */
+    struct Lane {
+        DevBuf<T> y, b, x, r, d, Ad, Kv;
+        DevBuf<double> part, sc;
+        double *part_of(PartSet s) const { return part.p + static_cast<size_t>(s) * RED_BLOCKS * 2; }
+        PinnedBuf<double> host_sc, host_delta;
+    };
+    Lane &lane(size_t k);
+    /* where one Gram pass can serve two vectors: the fp64 symmetric v2 kernel on an unsharded problem without feature panels -- and only the (kernel function, chunk
+     * count) instantiations whose two-vector pass was measured faster than two single passes (profiles/lockstep_f64.json) */
+    bool pair_kernel_applies() const;
+    /* Kv0 <- K * v0 and, with v1, Kv1 <- K * v1 from ONE pass of the two-vector kernel (pair_kernel_applies; the caller falls back to two calls elsewhere); without v1
+     * today's single-vector pass.  Each result has the bits enqueue_apply_K_local gives for that vector.  `ev`: HIP events around the tile-kernel launches, or NULL. */
+    void enqueue_apply_K_lanes(const T *v0, T *Kv0, const T *v1, T *Kv1, hipEvent_t ev_begin, hipEvent_t ev_end);
 
   private:
     friend class Solver<T>;
@@ -409,6 +426,8 @@ class Problem {
     T *Kres_ = nullptr;  // the exchanged K * v the O(n) kernels read: Kv_ itself, or Ksum_ when peer kernels do the exchange
     DevBuf<T> partial_;
     DevBuf<T> dc_;  // v2 kernels: packed (d_j | c_j) records
+    std::vector<std::unique_ptr<Lane>> lanes_;
+    DevBuf<T> pair_dc_, pair_partial_, pair_colslab_;  // two-vector passes: (d0_j | d1_j | c_j) records, and both vectors' planes of the row slabs / the column slab
     bool d_packed_ = false;  // dc_ holds the records of d_ and K*v is cleared: k_update_d left them (pack_for_d), the next implicit matvec of d_ launches no k_pack_dc
     // symmetric variant
     bool sym_ = false;
@@ -465,6 +484,9 @@ struct ProblemBase {
     virtual void get_q(void *q_out, double *QA_cost_out) = 0;
     virtual void set_weights(const double *weights, size_t num_points) = 0;  // lssvm_mi355_problem_set_weights
     virtual void matvec(const void *d, void *ret_inout, double add) = 0;
+    virtual void matvec_pair(const void *d0, const void *d1, void *ret0_inout, void *ret1_inout, double add, int *two_vector_out) = 0;  // lssvm_mi355_problem_matvec_pair
+    virtual void solve_lockstep(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out,
+                                uint64_t *passes_out) = 0;  // lssvm_mi355_problem_solve_lockstep
     virtual void cg_begin(const void *y, double eps) = 0;
     virtual void cg_step(uint64_t iterations, int *done_out) = 0;
     virtual void cg_finish(void *alpha_out, double *rho_out, lssvm_cg_info *info) = 0;
@@ -540,6 +562,8 @@ class Solver final : public ProblemBase {
     void get_q(void *q_out, double *QA_cost_out) override;
     void set_weights(const double *weights, size_t num_points) override;
     void matvec(const void *d, void *ret_inout, double add) override;
+    void matvec_pair(const void *d0, const void *d1, void *ret0_inout, void *ret1_inout, double add, int *two_vector_out) override;
+    void solve_lockstep(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out) override;
     void cg_begin(const void *y, double eps) override;
     void cg_step(uint64_t iterations, int *done_out) override;
     int rebalance(const double *weights, int count) override;
@@ -556,6 +580,10 @@ class Solver final : public ProblemBase {
     void exchange();
     void sync_all();
     PackDc<T> pack_with_direction(Problem<T> &p);
+    void describe_path(lssvm_cg_info *info);
+    bool lanes_apply() const;  // the lockstep driver runs on lanes of shard 0: one unsharded device without an exchange, where the two-vector kernel applies
+    void solve_in_sequence(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out);
+    void solve_on_lanes(const T *Y, size_t num_rhs, double eps, uint64_t max_iter, T *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out);
     T *vec_of(Problem<T> &p, Vec which) const { return which == Vec::d ? p.d_.p : (which == Vec::x ? p.x_.p : p.tmp_.p); }
 
     Options opt_{};

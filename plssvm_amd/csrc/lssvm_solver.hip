@@ -447,6 +447,274 @@ void Solver<T>::cg_finish(void *alpha_out, double *rho_out, lssvm_cg_info *info)
     if (info != nullptr) fill_info(info);
 }
 
+/* ------------------------------------------------------------------ two vectors per Gram pass: matvec_pair, the lockstep CG ------------------------------------------------------------------ */
+template <typename T>
+bool Solver<T>::lanes_apply() const {
+    return shards_.size() == 1 && world_ == 1 && exchange_ == Exchange::none && shards_[0]->pair_kernel_applies();
+}
+
+template <typename T>
+void Solver<T>::matvec_pair(const void *d0, const void *d1, void *ret0_inout, void *ret1_inout, double add, int *two_vector_out) {
+    LSSVM_REQUIRE(d0 != nullptr && d1 != nullptr && ret0_inout != nullptr && ret1_inout != nullptr, "The d / ret arrays may not be empty!");  // csvm.cpp:284-286
+    LSSVM_REQUIRE(add == 1.0 || add == -1.0, "add must either be -1.0 or 1.0, but is " + std::to_string(add) + "!");                       // svm_kernel.cpp:28
+    LSSVM_REQUIRE(!in_cg_, "matvec_pair cannot run between cg_begin and cg_finish");
+    if (two_vector_out != nullptr) *two_vector_out = 0;
+    if (!lanes_apply()) {  // two single passes
+        matvec(d0, ret0_inout, add);
+        matvec(d1, ret1_inout, add);
+        return;
+    }
+    // the statements of matvec() per vector on two lanes (d <- d_u zero padded, Ad <- ret_u), around ONE pass of the two-vector kernel
+    Problem<T> &p = *shards_[0];
+    typename Problem<T>::Lane *lane[2] = { &p.lane(0), &p.lane(1) };
+    const void *d[2] = { d0, d1 };
+    void *ret[2] = { ret0_inout, ret1_inout };
+    const size_t bytes = static_cast<size_t>(p.n_) * sizeof(T);
+    hipStream_t st = p.stream();
+    for (int u = 0; u < 2; ++u) {
+        LSSVM_HIP_CHECK(hipMemcpyAsync(lane[u]->d.p, d[u], bytes, hipMemcpyHostToDevice, st));
+        LSSVM_HIP_CHECK(hipMemcpyAsync(lane[u]->Ad.p, ret[u], bytes, hipMemcpyHostToDevice, st));
+        p.enqueue_sum_and_qdot(lane[u]->d.p, lane[u]->part_of(PART_SUMS), lane[u]->sc.p, SC_S, SC_QD);
+    }
+    p.enqueue_apply_K_lanes(lane[0]->d.p, lane[0]->Kv.p, lane[1]->d.p, lane[1]->Kv.p, nullptr, nullptr);
+    for (int u = 0; u < 2; ++u) {
+        const typename Problem<T>::Lane &l = *lane[u];
+        if (p.weighted_) {
+            hipLaunchKernelGGL((k_apply_ret<T, true>), dim3((p.n_ + 255) / 256), dim3(256), 0, st, l.Kv.p, l.d.p, p.q_.p, l.sc.p, p.n_, p.inv_cw_.p, p.QA_cost_, add, l.Ad.p);
+        } else {
+            hipLaunchKernelGGL(k_apply_ret<T>, dim3((p.n_ + 255) / 256), dim3(256), 0, st, l.Kv.p, l.d.p, p.q_.p, l.sc.p, p.n_, p.inv_cost_, p.QA_cost_, add, l.Ad.p);
+        }
+        LSSVM_HIP_CHECK(hipGetLastError());
+        LSSVM_HIP_CHECK(hipMemcpyAsync(ret[u], l.Ad.p, bytes, hipMemcpyDeviceToHost, st));
+    }
+    sync_all();
+    if (two_vector_out != nullptr) *two_vector_out = 1;
+}
+
+template <typename T>
+void Solver<T>::solve_lockstep(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out) {
+    LSSVM_REQUIRE(Y != nullptr, "The right hand side vector must not be empty!");
+    LSSVM_REQUIRE(num_rhs > 0, "The number of right hand sides must be greater than 0!");
+    LSSVM_REQUIRE(static_cast<T>(eps) > T(0), "The stopping criterion in the CG algorithm must be greater than 0.0, but is " + std::to_string(eps) + "!");  // csvm.cpp:77
+    LSSVM_REQUIRE(max_iter > 0, "The number of CG iterations must be greater than 0!");                                                                   // csvm.cpp:78
+    LSSVM_REQUIRE(alphas_out != nullptr && rhos_out != nullptr, "alpha_out / rho_out must not be NULL");
+    LSSVM_REQUIRE(!in_cg_, "solve_lockstep cannot run between cg_begin and cg_finish");
+    if (passes_out != nullptr) passes_out[0] = passes_out[1] = 0;
+    if (lanes_apply()) {
+        solve_on_lanes(static_cast<const T *>(Y), num_rhs, eps, max_iter, static_cast<T *>(alphas_out), rhos_out, infos_out, passes_out);
+    } else {
+        solve_in_sequence(Y, num_rhs, eps, max_iter, alphas_out, rhos_out, infos_out, passes_out);
+    }
+}
+
+/* Where no Gram pass can serve two vectors: today's sequence, one right-hand side after the other.  Nothing is enqueued ahead of a stop test (as on the lanes), so a
+ * solve takes exactly 1 + it + it / 50 single-vector passes; the bits are those of the one-shot solve either way. */
+template <typename T>
+void Solver<T>::solve_in_sequence(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out) {
+    const double t_call = now_ms();
+    const size_t N = shards_[0]->N_;
+    const int64_t ahead = opt_.enqueue_ahead_below_us;
+    opt_.enqueue_ahead_below_us = 0;
+    try {
+        for (size_t c = 0; c < num_rhs; ++c) {
+            cg_begin(static_cast<const T *>(Y) + c * N, eps);
+            cg_step(max_iter, nullptr);
+            lssvm_cg_info info{};
+            cg_finish(static_cast<T *>(alphas_out) + c * N, rhos_out + c, &info);
+            info.max_iterations = max_iter;
+            info.total_ms = now_ms() - t_call;
+            if (passes_out != nullptr) passes_out[1] += info.matvec_launches;
+            if (infos_out != nullptr) infos_out[c] = info;
+        }
+    } catch (...) {
+        opt_.enqueue_ahead_below_us = ahead;
+        in_cg_ = false;
+        throw;
+    }
+    opt_.enqueue_ahead_below_us = ahead;
+}
+
+/* The recipe of cg_begin / cg_step / cg_finish for every right-hand side, each on a lane of shard 0 with the O(n) kernels of the single solve on that lane's pointers --
+ * so every recurrence has the bits of the one-shot solve -- all lanes advancing one iteration per step.  In every step the lanes still active are paired afresh for the
+ * implicit matvec: ceil(active / 2) Gram passes, an odd lane taking the single-vector pass.  The host waits for the step's deltas before it enqueues the next step. */
+template <typename T>
+void Solver<T>::solve_on_lanes(const T *Y, size_t num_rhs, double eps, uint64_t max_iter, T *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out) {
+    using Lane = typename Problem<T>::Lane;
+    const double t_call = now_ms();
+    Problem<T> &p = *shards_[0];
+    p.activate();
+    hipStream_t st = p.stream();
+    const size_t N = p.N_;
+    const int n = p.n_;
+    const dim3 gn((n + 255) / 256), bn(256), gr(RED_BLOCKS), br(RED_THREADS);
+    struct State {
+        Lane *lane = nullptr;
+        double y_last = 0.0, delta0 = 0.0, delta = 0.0;
+        uint64_t matvecs = 0, timed = 0;
+        double kernel_ms = 0.0;
+        bool converged = false;
+    };
+    std::vector<State> state(num_rhs);
+    for (size_t c = 0; c < num_rhs; ++c) state[c].lane = &p.lane(c);
+    std::vector<size_t> active(num_rhs);
+    for (size_t c = 0; c < num_rhs; ++c) active[c] = c;
+    uint64_t passes[2] = { 0, 0 };
+
+    // one Gram pass per pair of active lanes (`x`: of their x, else of their d) into their K*v; HIP events around every pass, read back after the step's wait
+    struct Timed {
+        Event a, b;
+        size_t lane0 = 0, lane1 = 0;
+        bool two = false;
+    };
+    std::vector<Timed> timers(2 * ((num_rhs + 1) / 2));  // (a step with a residual refresh makes two rounds of passes before its wait)
+    for (Timed &t : timers) {
+        t.a.create(true);
+        t.b.create(true);
+    }
+    size_t timers_used = 0;
+    const auto apply_K = [&](bool x) {
+        for (size_t k = 0; k < active.size(); k += 2) {
+            State &s0 = state[active[k]];
+            State *s1 = k + 1 < active.size() ? &state[active[k + 1]] : nullptr;
+            Timed &t = timers[timers_used++];
+            t.lane0 = active[k];
+            t.two = s1 != nullptr;
+            t.lane1 = t.two ? active[k + 1] : 0;
+            p.enqueue_apply_K_lanes(x ? s0.lane->x.p : s0.lane->d.p, s0.lane->Kv.p, t.two ? (x ? s1->lane->x.p : s1->lane->d.p) : nullptr, t.two ? s1->lane->Kv.p : nullptr, t.a.e, t.b.e);
+            ++passes[t.two ? 0 : 1];
+            ++s0.matvecs;
+            if (t.two) ++s1->matvecs;
+        }
+    };
+    const auto read_timers = [&] {  // (the stream has been waited for)
+        for (size_t k = 0; k < timers_used; ++k) {
+            float ms = 0.0f;
+            if (hipEventElapsedTime(&ms, timers[k].a.e, timers[k].b.e) != hipSuccess) continue;
+            for (int u = 0; u < (timers[k].two ? 2 : 1); ++u) {
+                State &s = state[u == 0 ? timers[k].lane0 : timers[k].lane1];
+                s.kernel_ms += ms;
+                ++s.timed;
+            }
+        }
+        timers_used = 0;
+    };
+    const auto enqueue_residual = [&](const Lane &l) {
+        if (p.weighted_) {
+            hipLaunchKernelGGL((k_residual<T, true>), gr, br, 0, st, l.Kv.p, l.x.p, p.q_.p, l.b.p, l.sc.p, n, p.inv_cw_.p, p.QA_cost_, l.r.p, l.part_of(PART_RR));
+        } else {
+            hipLaunchKernelGGL(k_residual<T>, gr, br, 0, st, l.Kv.p, l.x.p, p.q_.p, l.b.p, l.sc.p, n, p.inv_cost_, p.QA_cost_, l.r.p, l.part_of(PART_RR));
+        }
+    };
+    const auto wait_for_deltas = [&] {
+        LSSVM_HIP_CHECK(hipGetLastError());
+        LSSVM_HIP_CHECK(hipEventRecord(ev_delta_.e, st));
+        LSSVM_HIP_CHECK(hipEventSynchronize(ev_delta_.e));
+        read_timers();
+    };
+
+    in_cg_ = true;  // (the weights may not change, and no other solve may begin on this handle)
+    try {
+        // ---- cg_begin per lane: b = y - y_last, x = 1, r = b - A x, delta0, d = r ----
+        for (size_t c : active) {
+            State &s = state[c];
+            const Lane &l = *s.lane;
+            s.y_last = static_cast<double>(Y[c * N + N - 1]);
+            LSSVM_HIP_CHECK(hipMemcpyAsync(l.y.p, Y + c * N, N * sizeof(T), hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_make_b<T>, gn, bn, 0, st, l.y.p, n, l.b.p);
+            hipLaunchKernelGGL(k_fill<T>, gn, bn, 0, st, l.x.p, n, T(1));
+            p.enqueue_sum_and_qdot(l.x.p, l.part_of(PART_SUMS), l.sc.p, SC_SUMX, SC_QX);
+        }
+        apply_K(true);
+        for (size_t c : active) {
+            const Lane &l = *state[c].lane;
+            enqueue_residual(l);
+            hipLaunchKernelGGL(k_finish_delta, dim3(1), br, 0, st, l.part_of(PART_RR), l.sc.p, l.host_delta.dev, 1);
+            hipLaunchKernelGGL(k_update_d<T>, gr, br, 0, st, l.d.p, l.r.p, p.q_.p, l.sc.p, n, 1, l.part_of(PART_D), PackDc<T>{});  // (the records are packed per pass, for the pair of the step)
+        }
+        wait_for_deltas();
+        for (size_t c : active) {
+            State &s = state[c];
+            s.delta0 = s.delta = static_cast<double>(static_cast<T>(*static_cast<volatile double *>(s.lane->host_delta.p)));
+        }
+
+        // ---- cg_step: one iteration of every active lane per step ----
+        for (uint64_t iter = 0; !active.empty(); ++iter) {
+            const bool refresh = iter % 50 == 49;
+            apply_K(false);
+            for (size_t c : active) {
+                const Lane &l = *state[c].lane;
+                if (p.weighted_) {
+                    hipLaunchKernelGGL((k_Ad_and_dAd<T, true>), gr, br, 0, st, l.Kv.p, l.d.p, p.q_.p, l.part_of(PART_D), l.sc.p, n, p.inv_cw_.p, p.QA_cost_, l.Ad.p, l.part_of(PART_DAD));
+                } else {
+                    hipLaunchKernelGGL(k_Ad_and_dAd<T>, gr, br, 0, st, l.Kv.p, l.d.p, p.q_.p, l.part_of(PART_D), l.sc.p, n, p.inv_cost_, p.QA_cost_, l.Ad.p, l.part_of(PART_DAD));
+                }
+                hipLaunchKernelGGL(k_update_x_r<T>, gr, br, 0, st, l.x.p, l.r.p, l.d.p, l.Ad.p, l.part_of(PART_DAD), l.sc.p, n, refresh ? 0 : 1, l.part_of(PART_RR));
+                if (refresh) p.enqueue_sum_and_qdot(l.x.p, l.part_of(PART_SUMS), l.sc.p, SC_SUMX, SC_QX);
+            }
+            if (refresh) {
+                apply_K(true);
+                for (size_t c : active) enqueue_residual(*state[c].lane);
+            }
+            for (size_t c : active) {
+                const Lane &l = *state[c].lane;
+                hipLaunchKernelGGL(k_finish_delta, dim3(1), br, 0, st, l.part_of(PART_RR), l.sc.p, l.host_delta.dev, 0);
+            }
+            wait_for_deltas();
+            // the stop test in the real type, before the direction update (csvm.cpp:155-158); a lane that meets it, or has done max_iter iterations, leaves
+            std::vector<size_t> staying;
+            for (size_t c : active) {
+                State &s = state[c];
+                const Lane &l = *s.lane;
+                s.delta = static_cast<double>(static_cast<T>(*static_cast<volatile double *>(l.host_delta.p)));
+                const T target = static_cast<T>(eps) * static_cast<T>(eps) * static_cast<T>(s.delta0);
+                s.converged = static_cast<T>(s.delta) <= target;
+                if (!s.converged && iter + 1 < max_iter) {
+                    hipLaunchKernelGGL(k_update_d<T>, gr, br, 0, st, l.d.p, l.r.p, p.q_.p, l.sc.p, n, 0, l.part_of(PART_D), PackDc<T>{});
+                    staying.push_back(c);
+                    continue;
+                }
+                // cg_finish: bias = y_last + QA_cost * sum(x) - q^T x ; alpha_N = -sum(x) ; rho = -bias   (csvm.cpp:179-182)
+                p.enqueue_sum_and_qdot(l.x.p, l.part_of(PART_SUMS), l.sc.p, SC_SUMX, SC_QX);
+                LSSVM_HIP_CHECK(hipMemcpyAsync(l.host_sc.p, l.sc.p, SC_COUNT * sizeof(double), hipMemcpyDeviceToHost, st));
+                T *alpha = alphas_out + c * N;
+                LSSVM_HIP_CHECK(hipMemcpyAsync(alpha, l.x.p, static_cast<size_t>(n) * sizeof(T), hipMemcpyDeviceToHost, st));
+                LSSVM_HIP_CHECK(hipStreamSynchronize(st));
+                alpha[n] = -static_cast<T>(l.host_sc.p[SC_SUMX]);
+                rhos_out[c] = static_cast<double>(-static_cast<T>(s.y_last + p.QA_cost_ * l.host_sc.p[SC_SUMX] - l.host_sc.p[SC_QX]));
+                if (infos_out != nullptr) {
+                    // what cg_finish reports for a one-shot solve, with this lane's counters; total_ms: from the start of the call until the lane left
+                    lssvm_cg_info info{};
+                    info.iterations = iter + 1;
+                    info.max_iterations = max_iter;
+                    info.residuum = s.delta;
+                    info.initial_residuum = s.delta0;
+                    info.target_residuum = static_cast<double>(target);
+                    info.epsilon = eps;
+                    info.total_ms = now_ms() - t_call;
+                    info.avg_iteration_ms = info.total_ms / static_cast<double>(iter + 1);
+                    info.converged = s.converged ? 1 : 0;
+                    describe_path(&info);
+                    info.matvec_launches = s.matvecs;
+                    info.matvec_timed = s.timed;
+                    info.matvec_kernel_ms_total = s.kernel_ms;
+                    info.matvec_kernel_ms = s.timed > 0 ? s.kernel_ms / static_cast<double>(s.timed) : 0.0;
+                    infos_out[c] = info;
+                }
+            }
+            LSSVM_HIP_CHECK(hipGetLastError());
+            active.swap(staying);
+        }
+    } catch (...) {
+        in_cg_ = false;
+        throw;
+    }
+    in_cg_ = false;
+    if (passes_out != nullptr) {
+        passes_out[0] = passes[0];
+        passes_out[1] = passes[1];
+    }
+}
+
 template <typename T>
 void Solver<T>::synchronize() {
     sync_all();
@@ -455,7 +723,6 @@ void Solver<T>::synchronize() {
 template <typename T>
 void Solver<T>::fill_info(lssvm_cg_info *info) {
     std::memset(info, 0, sizeof(*info));
-    const Problem<T> &p0 = *shards_[0];
     info->iterations = iter_;
     info->max_iterations = 0;
     info->residuum = delta_;
@@ -464,6 +731,14 @@ void Solver<T>::fill_info(lssvm_cg_info *info) {
     info->epsilon = eps_;
     info->avg_iteration_ms = iter_ > 0 ? cg_wall_ms_ / static_cast<double>(iter_) : 0.0;
     info->total_ms = cg_wall_ms_;
+    info->converged = converged_ ? 1 : 0;
+    describe_path(info);
+}
+
+/* the fields of lssvm_cg_info that describe the problem, its kernel path and the tile-kernel times of the handle's own (single-vector) CG state */
+template <typename T>
+void Solver<T>::describe_path(lssvm_cg_info *info) {
+    const Problem<T> &p0 = *shards_[0];
     info->setup_ms = setup_ms_;
     // the tile kernel of the slowest shard sets the pace of a sharded matvec.  WHICH shard is reported is decided once per cg_begin (the first call that finds timed
     // matvecs) and kept, so that the differences of (matvec_kernel_ms_total, matvec_timed) between two calls always belong to one shard
@@ -486,7 +761,6 @@ void Solver<T>::fill_info(lssvm_cg_info *info) {
     info->f16_row_rel_error = p0.f16_row_rel_error_;
     info->matvec_launches = p0.matvec_launches_;
     info->devices_used = world_;
-    info->converged = converged_ ? 1 : 0;
     info->symmetric = p0.sym_ ? 1 : 0;
     info->gram_mode = (p0.planes_.mode != 0 && p0.dc_.p != nullptr) ? (p0.rbf_grid_ ? 3 : p0.planes_.mode) : 0;  // (a split kernel is dispatched only where both exist; 3: rbf on grid planes)
     info->local_devices = static_cast<int32_t>(shards_.size());

@@ -206,20 +206,30 @@ __global__ __launch_bounds__(TILE_THREADS, 1) void tile_matvec_f64(const TileArg
  *   costs 9 % of the matrix-core rate, one v_fma_f64 15 %), so the chunk loop consists of MFMAs, LDS reads with immediate
  *   offsets, LDS-DMA with scalar base addresses and scalar instructions only, the accumulators start from the constant 0 as
  *   the C operand of the first MFMA, and the polynomial kernel runs on data pre-scaled by sqrt(gamma).
+ *   NV = 2 (symmetric variant only; the lockstep CG over several right-hand sides): TWO vectors per pass.  The kernel value of an element is computed once and
+ *   enters one fma chain per vector for the row sums and one per vector for the mirrored column sums; each vector's chains, butterflies and slab order are those of
+ *   NV = 1, so its K v has the bits of a single-vector pass whatever its partner is.  The record of a sub-tile is (d0_j | d1_j | c_j), 1.5 KiB (k_pack_dc2_f64); the
+ *   second vector's d_i (TileArgs::dvec1), column sums and slabs (part_vstride, colslab_vstride) are second planes of the same arrays.  Everything of the second
+ *   vector stands in `if constexpr (NV == 2)`: the NV = 1 instantiations are the code they were.
  * ===================================================================================================================== */
 constexpr int V2D_RING = 4;
 constexpr int V2D_SLOT_BYTES = 64 * 128;  // 8 KiB
 constexpr int V2D_DC_SLOTS = 4;           // (64 d_j | 64 c_j) doubles = 1 KiB per sub-tile
 constexpr size_t V2D_LDS_BYTES = static_cast<size_t>(V2D_RING) * V2D_SLOT_BYTES + V2D_DC_SLOTS * 1024 + (2 * TILE + 2 * 4 * 64) * sizeof(double);  // ring + records + cis, dis, colred
+constexpr size_t V2D_LDS_BYTES_NV2 = static_cast<size_t>(V2D_RING) * V2D_SLOT_BYTES + V2D_DC_SLOTS * 1536 + (3 * TILE + 2 * 2 * 4 * 64) * sizeof(double);  // NV = 2: records of 1.5 KiB, two dis, two colred (49 KiB: two workgroups per CU)
 
-template <int KT, int NKC, bool SYM>
+template <int KT, int NKC, bool SYM, int NV = 1>
 __global__ __launch_bounds__(TILE_THREADS, (NKC <= 4 ? 2 : 1)) void tile_matvec_f64_v2(const TileArgs<double> a) {
+    static_assert(NV == 1 || (NV == 2 && SYM), "two vectors per pass: the symmetric variant only");
+    constexpr int REC_BYTES = NV * 512 + 512;  // a sub-tile's record: 64 d_j per vector, then 64 c_j
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     char *ring = smem_raw;
     char *dcs = smem_raw + V2D_RING * V2D_SLOT_BYTES;
-    double *cis = reinterpret_cast<double *>(dcs + V2D_DC_SLOTS * 1024);  // [128] c_i of the row panel (rbf)
-    double *dis = cis + TILE;                                              // [128] d_i of the row panel (SYM)
-    double *colred = dis + TILE;                                           // [2][4 waves][64] column sums of a sub-tile (SYM)
+    double *cis = reinterpret_cast<double *>(dcs + V2D_DC_SLOTS * REC_BYTES);  // [128] c_i of the row panel (rbf)
+    double *dis = cis + TILE;                                                   // [128] d_i of the row panel (SYM)
+    double *colred = dis + TILE;                                                // [2][4 waves][64] column sums of a sub-tile (SYM)
+    [[maybe_unused]] double *dis1 = colred + 2 * 4 * 64;                        // NV = 2: the second vector's d_i ...
+    [[maybe_unused]] double *colred1 = dis1 + TILE;                             // ... and column sums
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -261,6 +271,9 @@ __global__ __launch_bounds__(TILE_THREADS, (NKC <= 4 ? 2 : 1)) void tile_matvec_
     }
     if constexpr (SYM) {
         if (tid < TILE) dis[tid] = a.dvec[row0 + tid];
+        if constexpr (NV == 2) {
+            if (tid < TILE) dis1[tid] = a.dvec1[row0 + tid];
+        }
     }
 #pragma unroll
     for (int rb = 0; rb < 2; ++rb)
@@ -280,7 +293,7 @@ __global__ __launch_bounds__(TILE_THREADS, (NKC <= 4 ? 2 : 1)) void tile_matvec_
     }
     const unsigned ring_lds = static_cast<unsigned>(reinterpret_cast<size_t>(ring));  // the low half of a generic LDS address is the LDS address
     const unsigned dma_lds = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(ring_lds + static_cast<unsigned>(wave) * 2048u)));  // this wave's quarter of ring slot 0
-    const unsigned dc_lds = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(ring_lds + V2D_RING * V2D_SLOT_BYTES + static_cast<unsigned>(wave) * 256u)));
+    const unsigned dc_lds = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(ring_lds + V2D_RING * V2D_SLOT_BYTES + static_cast<unsigned>(wave) * static_cast<unsigned>(REC_BYTES / 4))));
     auto issue_chunk = [&](int step) {
         if (LSSVM_DBG(a, 16) && step > 2) return;  // ablation: no DMA after the prologue
         const int t = step / NKC;
@@ -291,9 +304,10 @@ __global__ __launch_bounds__(TILE_THREADS, (NKC <= 4 ? 2 : 1)) void tile_matvec_
         lds_dma16<1024>(dma_off[1], base, slot);
     };
     auto issue_dc = [&](int t) {
-        if (lane < 16) {
-            const char *src = sgpr_ptr(a.dc + static_cast<size_t>(st_begin + t) * 128) + __builtin_amdgcn_readfirstlane(wave * 256);
-            lds_dma16<0>(16u * (lane_off(threadIdx.x) & 15u), sgpr_ptr(src), static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(dc_lds + static_cast<unsigned>(t % V2D_DC_SLOTS) * 1024u))));
+        // each wave fetches its quarter of the record: 16 lanes x 16 bytes (NV = 2: 24 lanes), lane-linear in LDS
+        if (lane < REC_BYTES / 64) {
+            const char *src = sgpr_ptr(a.dc + static_cast<size_t>(st_begin + t) * (REC_BYTES / 8)) + __builtin_amdgcn_readfirstlane(wave * (REC_BYTES / 4));
+            lds_dma16<0>(16u * (lane_off(threadIdx.x) & (NV == 2 ? 31u : 15u)), sgpr_ptr(src), static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(dc_lds + static_cast<unsigned>(t % V2D_DC_SLOTS) * static_cast<unsigned>(REC_BYTES)))));
         }
     };
 
@@ -314,6 +328,13 @@ __global__ __launch_bounds__(TILE_THREADS, (NKC <= 4 ? 2 : 1)) void tile_matvec_
     f64x4 acc[2][4];
     double dj[4], cj[4];
     bool padcol[4] = { false, false, false, false };
+    [[maybe_unused]] double rowpart1[2][4], dj1[4];  // NV = 2: the second vector's row sums and d_j
+    if constexpr (NV == 2) {
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) rowpart1[rb][i] = 0.0;
+    }
 
     // ---- prologue: chunks 0, 1, 2 (each preceded by the record of the sub-tile that starts with it) ----
     issue_dc(0);
@@ -374,18 +395,23 @@ __global__ __launch_bounds__(TILE_THREADS, (NKC <= 4 ? 2 : 1)) void tile_matvec_
             // (an explicit GLOBAL pointer: through the generic one the store is a flat_store, which counts in lgkmcnt as well and completes out of order)
             auto *rec = (__attribute__((address_space(1))) double *) (a.colslab + (rec0 + st_begin + t) * 64);  // uniform base + 32-bit lane offset
             rec[static_cast<unsigned>(tid)] = (cr_[tid] + cr_[64 + tid]) + (cr_[128 + tid] + cr_[192 + tid]);
+            if constexpr (NV == 2) {
+                const double *cr1_ = colred1 + (t & 1) * 256;
+                auto *rec1 = (__attribute__((address_space(1))) double *) (a.colslab + a.colslab_vstride + (rec0 + st_begin + t) * 64);
+                rec1[static_cast<unsigned>(tid)] = (cr1_[tid] + cr1_[64 + tid]) + (cr1_[128 + tid] + cr1_[192 + tid]);
+            }
         }
     };
 
     auto tile_body = [&](int t, auto checked) {
         const int s0 = t * NKC;
         const bool tile_sym = SYM && (st_begin + t < 2 * ib);
-        const double *dcr = reinterpret_cast<const double *>(dcs + (t % V2D_DC_SLOTS) * 1024);
+        const double *dcr = reinterpret_cast<const double *>(dcs + (t % V2D_DC_SLOTS) * REC_BYTES);
         // rbf: the accumulators start at c_i + c_j; the other kernels start the chain with the constant 0 as the C operand of the
         // first MFMA (no register initialisation: 64 v_mov per sub-tile would cost as much matrix-core time as the cube)
         if constexpr (KT == KT_RBF) {
 #pragma unroll
-            for (int cb = 0; cb < 4; ++cb) cj[cb] = dcr[64 + cb * 16 + r];
+            for (int cb = 0; cb < 4; ++cb) cj[cb] = dcr[NV * 64 + cb * 16 + r];
 #pragma unroll
             for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
@@ -438,6 +464,7 @@ __global__ __launch_bounds__(TILE_THREADS, (NKC <= 4 ? 2 : 1)) void tile_matvec_
 #pragma unroll
             for (int cb = 0; cb < 4; ++cb) {
                 dj[cb] = dcr[cb * 16 + r];
+                if constexpr (NV == 2) dj1[cb] = dcr[64 + cb * 16 + r];
                 if constexpr (KT == KT_POLY) padcol[cb] = (a.degree < 0) && ((st_begin + t) * 64 + cb * 16 + r >= a.ncols_valid);
             }
             if constexpr (v2_base_kt(KT) == KT_POLY) {
@@ -453,12 +480,15 @@ __global__ __launch_bounds__(TILE_THREADS, (NKC <= 4 ? 2 : 1)) void tile_matvec_
             auto epilogue = [&](auto with_cols) {
                 constexpr bool COLS = decltype(with_cols)::value;
                 double colacc[4] = { 0.0, 0.0, 0.0, 0.0 };
+                [[maybe_unused]] double colacc1[4] = { 0.0, 0.0, 0.0, 0.0 };
 #pragma unroll
                 for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         double di = 0.0;
                         if constexpr (COLS) di = dis[wave * 32 + rb * 16 + q + 4 * i];
+                        [[maybe_unused]] double di1 = 0.0;
+                        if constexpr (NV == 2) di1 = dis1[wave * 32 + rb * 16 + q + 4 * i];
 #pragma unroll
                         for (int cb = 0; cb < 4; ++cb) {
                             double kv;
@@ -475,6 +505,10 @@ __global__ __launch_bounds__(TILE_THREADS, (NKC <= 4 ? 2 : 1)) void tile_matvec_
                             }
                             rowpart[rb][i] = fma(kv, dj[cb], rowpart[rb][i]);
                             if constexpr (COLS) colacc[cb] = fma(kv, di, colacc[cb]);
+                            if constexpr (NV == 2) {  // kv is shared; the second vector has fma chains of its own, those of a single-vector pass
+                                rowpart1[rb][i] = fma(kv, dj1[cb], rowpart1[rb][i]);
+                                colacc1[cb] = fma(kv, di1, colacc1[cb]);
+                            }
                         }
                     }
                 if constexpr (COLS) {
@@ -483,6 +517,7 @@ __global__ __launch_bounds__(TILE_THREADS, (NKC <= 4 ? 2 : 1)) void tile_matvec_
                     // is an LDS round trip per step and, with a store branch per column block, serialised them) for all four blocks at once;
                     // the sums come out one column per lane (block q in lane group q), so the store is one instruction of the whole wave
                     cw[lane] = column_sums_of_4_blocks(colacc);
+                    if constexpr (NV == 2) colred1[(t & 1) * 256 + wave * 64 + lane] = column_sums_of_4_blocks(colacc1);
                 }
             };
             // (ONE epilogue per instantiation: with a branch between a column-sum and a row-only variant the compiler gave the eight row sums
@@ -526,6 +561,26 @@ __global__ __launch_bounds__(TILE_THREADS, (NKC <= 4 ? 2 : 1)) void tile_matvec_
         for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
             for (int i = 0; i < 4; ++i) dst[rb * 16 + 4 * i] = rowpart[rb][i];
+    }
+    if constexpr (NV == 2) {  // the second vector's row sums: the same butterfly, into its plane of the row slabs
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                double v = rowpart1[rb][i];
+                v += __shfl_xor(v, 8);
+                v += __shfl_xor(v, 4);
+                v += __shfl_xor(v, 2);
+                v += __shfl_xor(v, 1);
+                rowpart1[rb][i] = v;
+            }
+        if (r == 0) {
+            double *dst = a.partial + a.part_vstride + static_cast<size_t>(jc) * a.part_stride + ibl * TILE + wave * 32 + q;
+#pragma unroll
+            for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) dst[rb * 16 + 4 * i] = rowpart1[rb][i];
+        }
     }
 }
 }  // namespace lssvm

@@ -89,7 +89,10 @@ struct TileArgs {
     T gamma;          // polynomial: gamma ; rbf fp64: 2 * gamma ; rbf fp32: unused (folded into the pre-scaled data) ; direct rbf: -gamma*log2(e)
     T coef0;          // polynomial
     long part_vstride; // rectangular 256-row kernel with two weight vectors per pass: elements between the two vectors' planes of `partial` (>= num_jc * part_stride)
-    int nvec;         // host side only: weight vectors this launch evaluates (0 / 1 = one; 2 = the two-vector instance of the rectangular 256-row kernel or of the 128-row full-square split kernels, records from k_pack_dc2)
+    int nvec;         // host side only: weight vectors this launch evaluates (0 / 1 = one; 2 = the two-vector instance of the rectangular 256-row kernel or of the 128-row full-square split kernels, records from k_pack_dc2;
+                      // fp64: of the symmetric v2 kernel, records from k_pack_dc2_f64)
+    const T *dvec1;   // fp64 symmetric v2 kernel with two vectors per pass: the second vector (its d_i; its d_j travel in the records)
+    long colslab_vstride;  // ... elements between the two vectors' planes of `colslab`
 };
 
 /* What k_update_d needs to leave the NEXT implicit matvec's column records behind (k_pack_dc / k_pack_dc_f64 folded into it, round 5: one launch less per CG

@@ -59,5 +59,7 @@ void launch_nv2_tile_kernel(const TileArgs<float> &a, int kernel_type, dim3 grid
 void launch_wide_tile_kernel(const TileArgs<float> &a, int kernel_type, dim3 grid, hipStream_t s);
 /* fp64 rbf / polynomial on more than 256 features (tile_launch_f64x.hip): feature panels of 64 inside a sub-tile */
 void launch_wide_tile_kernel_f64(const TileArgs<double> &a, int kernel_type, dim3 grid, hipStream_t s);
+/* the fp64 symmetric v2 kernel with two vectors per pass (tile_launch_f64_sym2a.hip / _sym2b.hip; TileArgs::nvec == 2, reached through launch_tile_kernel<double>) */
+void launch_v2d_sym2(const TileArgs<double> &a, int kernel_type, hipStream_t s);
 
 }  // namespace lssvm

@@ -202,9 +202,10 @@ class MI355CSVM(CSVM):
         return backend.predict_values(params, support_vectors, alpha, rho, w, predict_points, options=self._options)
 
     def solve_systems_of_linear_equations(self, params, A, B, eps, max_iter, sample_weight=None):
-        """The systems one after the other on ONE resident problem: the data is uploaded and prepared (q, operand planes) once, the weights are set once, and every
-        right-hand side runs the recipe of the one-shot solve (begin / step / finish) on it -- the same alpha, rho and iteration count as a fresh one-shot solve.
-        Several devices: the base class's loop of one-shot solves."""
+        """The systems in LOCKSTEP on ONE resident problem (``ResidentProblem.solve_lockstep``): the data is uploaded and prepared (q, operand planes) once, the weights are
+        set once, and every right-hand side runs the recipe of the one-shot solve (begin / step / finish) on it -- the same alpha, rho and iteration count as a fresh
+        one-shot solve.  In fp64 on the symmetric resident-row-panel kernel one pass over the Gram tiles serves two right-hand sides per iteration; elsewhere they are solved
+        one after the other.  Several devices: the base class's loop of one-shot solves."""
         if self.use_devices != 1:
             return super().solve_systems_of_linear_equations(params, A, B, eps, max_iter, sample_weight=sample_weight)
         A = backend._as_matrix(A)
@@ -216,22 +217,10 @@ class MI355CSVM(CSVM):
             raise InvalidParameterError(f"The stopping criterion in the CG algorithm must be greater than 0.0, but is {eps}!")
         if not max_iter > 0:
             raise InvalidParameterError("The number of CG iterations must be greater than 0!")
-        first = self.get_option("rebalance_after")
-        alphas, rhos, infos = np.zeros_like(B), np.zeros(B.shape[0], dtype=A.dtype), []
         with backend.ResidentProblem(params, A, devices=[0], options=self._options) as prob:  # (device 0 alone, as the one-shot solve creates it)
             if sample_weight is not None:
                 prob.set_weights(sample_weight)
-            for c, b in enumerate(B):
-                prob.cg_begin(b, eps)
-                if 0 < first < max_iter:  # (one device: rebalance has nothing to move; the split keeps the sequence of calls the one-shot solve makes)
-                    prob.cg_step(first)
-                    prob.rebalance()
-                    prob.cg_step(max_iter - first)
-                else:
-                    prob.cg_step(max_iter)
-                alphas[c], rhos[c], info = prob.cg_finish()
-                info["max_iterations"] = int(max_iter)
-                infos.append(info)
+            alphas, rhos, infos, _ = prob.solve_lockstep(B, eps, max_iter)  # (one device: option rebalance_after has nothing to move)
         return alphas, rhos, infos
 
     def predict_values_multi(self, params, support_vectors, alphas, rhos, ws, predict_points):
