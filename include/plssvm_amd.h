@@ -182,6 +182,38 @@ int lssvm_mi355_solve_weighted_f64(const lssvm_params *params, const double *X, 
                                    const double *weights, double eps, uint64_t max_iter, double *alpha_out, double *rho_out,
                                    lssvm_cg_info *info, const lssvm_mi355_options *options);
 
+/* MIXED-PRECISION REFINEMENT (no counterpart in the reference): the fp64 system solved to the fp64 stop test, with the CG iterations run in fp32 on the
+ * matrix-core kernels.  The fp64 problem supplies only the TRUE residual r = b - A x (one fp64 Gram pass per outer step); every outer step solves
+ * A e = r / max|r| by the fp32 CG (x0 = 0) on the data rounded to float, to a tolerance derived from what is still missing, and accepts x + max|r| e only if
+ * the true residual fell to at most half.  A step that does not (a system whose ridge lies below fp32's resolution, a non-finite inner result) is discarded,
+ * and the plain fp64 CG finishes the solve from the current (x, r).  b, x0 = 1, the stop test r^T r <= eps^2 delta0 -- here on the true residual --, bias,
+ * alpha[N-1] and rho are those of lssvm_mi355_solve_f64.  max_iter bounds the fp32 iterations plus the fp64 iterations of a take-over (the outer residual
+ * passes do not count, as the refresh passes of the plain solve do not); a solve that exhausts it returns converged = 0 with the current x.
+ * Y: num_rhs right-hand sides of N values each (one-vs-all); every one runs the scheme on its own, the outer fp64 passes of two that are due together share
+ * one pass of the two-vector kernel where that applies (passes_out = {two-vector, single-vector} fp64 passes of the call), and column c of the result has the
+ * bits of the call with that right-hand side alone.  weights: NULL, or num_points weights as for lssvm_mi355_solve_weighted_f64.
+ * Where X does not survive the rounding to float (an entry that is not finite afterwards) or an option leaves no fp32 problem, the call IS the plain fp64
+ * solve (lssvm_mi355_solve_f64 / _solve_weighted_f64, several right-hand sides: lssvm_mi355_problem_solve_lockstep) and reports refined = 0.
+ * Device 0; deterministic (fixed-order reductions).  The gain grows with the iteration count; a solve of a handful of iterations has none. */
+typedef struct lssvm_refine_info {
+    int32_t  refined;            /* 1: the refinement ran; 0: the plain fp64 solve ran instead (see above) */
+    int32_t  took_over_f64;      /* 1: a step was rejected and fp64 CG finished the solve */
+    uint64_t outer_steps;        /* accepted + the rejected one */
+    uint64_t inner_iterations;   /* fp32 CG iterations, all steps */
+    uint64_t f64_cg_iterations;  /* of the take-over */
+    uint64_t f64_passes;         /* fp64 Gram passes this right-hand side took part in (1 + outer_steps + the take-over's) */
+    uint64_t f32_passes;         /* fp32 Gram passes */
+    double   initial_residuum, residuum, target_residuum;  /* true fp64 r^T r */
+    double   f64_ms, f32_ms, total_ms;                     /* host wall clock: fp64 passes and take-over | fp32 solves | since the call began */
+    int32_t  inner_gram_mode, inner_rbf_direct;            /* what the fp32 problem chose (lssvm_cg_info) */
+} lssvm_refine_info;
+int lssvm_mi355_solve_refined_f64(const lssvm_params *params, const double *X, size_t num_points, size_t num_features,
+                                  const double *Y /* num_rhs x N */, size_t num_rhs, const double *weights /* N or NULL */,
+                                  double eps, uint64_t max_iter, double *alphas_out /* num_rhs x N */, double *rhos_out,
+                                  lssvm_cg_info *infos_out /* num_rhs, may be NULL */, lssvm_refine_info *refine_out /* num_rhs, may be NULL */,
+                                  uint64_t passes_out[2] /* may be NULL: two-vector / single fp64 passes of the call */,
+                                  const lssvm_mi355_options *options);
+
 /* csvm::predict_values (csvm.hpp:204, :208; recipe: backends/OpenMP/csvm.cpp:188-227, HIP/predict_kernel.hip.hpp:34-117).
  * w_inout has num_features entries; *w_valid != 0 on entry means it already holds w (linear kernel only), on exit it is
  * set to 1 when w was computed (calculate_w, csvm.cpp:255-280).  out: num_predict_points decision values.  info (may be NULL): the timings of the call. */

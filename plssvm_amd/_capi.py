@@ -31,7 +31,7 @@ EXPORTED_SYMBOLS = [
     "lssvm_mi355_options_create", "lssvm_mi355_options_set", "lssvm_mi355_options_get", "lssvm_mi355_options_destroy",
     "lssvm_mi355_solve_f32", "lssvm_mi355_solve_f64", "lssvm_mi355_solve_multi_f32", "lssvm_mi355_solve_multi_f64", "lssvm_mi355_predict_values_f32", "lssvm_mi355_predict_values_f64",
     "lssvm_mi355_predict_values_multi_f32", "lssvm_mi355_predict_values_multi_f64",
-    "lssvm_mi355_solve_weighted_f32", "lssvm_mi355_solve_weighted_f64", "lssvm_mi355_problem_set_weights",
+    "lssvm_mi355_solve_weighted_f32", "lssvm_mi355_solve_weighted_f64", "lssvm_mi355_problem_set_weights", "lssvm_mi355_solve_refined_f64",
     "lssvm_mi355_predictor_create", "lssvm_mi355_predictor_predict", "lssvm_mi355_predictor_destroy", "lssvm_mi355_predictor_create_multi", "lssvm_mi355_predictor_predict_multi",
     "lssvm_mi355_generate_q_f32", "lssvm_mi355_generate_q_f64", "lssvm_mi355_run_device_kernel_f32", "lssvm_mi355_run_device_kernel_f64",
     "lssvm_mi355_calculate_w_f32", "lssvm_mi355_calculate_w_f64",
@@ -68,6 +68,16 @@ class LssvmPredictInfo(C.Structure):
     """``lssvm_predict_info``: the timings of one ``predict_values`` call; ``vectors_per_launch``: what ``predict_values_multi`` reports (0 from every other call)."""
     _fields_ = [("total_ms", C.c_double), ("setup_ms", C.c_double), ("kernel_ms", C.c_double), ("rbf_exponent_scale", C.c_double), ("f16_row_rel_error", C.c_double),
                 ("gram_mode", C.c_int32), ("rbf_direct", C.c_int32), ("resident", C.c_int32), ("vectors_per_launch", C.c_int32)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class LssvmRefineInfo(C.Structure):
+    """``lssvm_refine_info``: what the mixed-precision refinement (``lssvm_mi355_solve_refined_f64``) did for one right-hand side."""
+    _fields_ = [("refined", C.c_int32), ("took_over_f64", C.c_int32), ("outer_steps", C.c_uint64), ("inner_iterations", C.c_uint64), ("f64_cg_iterations", C.c_uint64),
+                ("f64_passes", C.c_uint64), ("f32_passes", C.c_uint64), ("initial_residuum", C.c_double), ("residuum", C.c_double), ("target_residuum", C.c_double),
+                ("f64_ms", C.c_double), ("f32_ms", C.c_double), ("total_ms", C.c_double), ("inner_gram_mode", C.c_int32), ("inner_rbf_direct", C.c_int32)]
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
@@ -143,6 +153,16 @@ def lockstep_entry(name: str):
             fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_uint64, C.c_void_p, C.POINTER(C.c_double), C.POINTER(LssvmCgInfo), C.POINTER(C.c_uint64)]
         else:
             fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(C.c_int)]
+        fn.restype = C.c_int
+    return fn
+
+
+def refined_entry():
+    """``lssvm_mi355_solve_refined_f64`` with its argument types.  Bound at the first call, like the weighted entry points."""
+    fn = lib.lssvm_mi355_solve_refined_f64
+    if fn.argtypes is None:
+        fn.argtypes = [C.POINTER(LssvmParams), C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.c_double, C.c_uint64, C.c_void_p,
+                       C.POINTER(C.c_double), C.POINTER(LssvmCgInfo), C.POINTER(LssvmRefineInfo), C.POINTER(C.c_uint64), C.c_void_p]
         fn.restype = C.c_int
     return fn
 

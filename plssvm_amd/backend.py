@@ -24,7 +24,7 @@ from ._capi import LssvmCgInfo, LssvmParams, LssvmPredictInfo, LssvmShard, Optio
 from .exceptions import InvalidParameterError
 from .parameter import Parameter
 
-__all__ = ["Options", "Predictor", "solve_system_of_linear_equations", "predict_values", "predict_values_multi", "generate_q", "run_device_kernel", "calculate_w", "ResidentProblem",
+__all__ = ["Options", "Predictor", "solve_system_of_linear_equations", "solve_refined", "predict_values", "predict_values_multi", "generate_q", "run_device_kernel", "calculate_w", "ResidentProblem",
            "comm_get_unique_id", "comm_init", "comm_destroy"]
 
 
@@ -116,6 +116,39 @@ def _solve_weighted(params: Parameter, A: np.ndarray, b: np.ndarray, w: np.ndarr
         alpha, rho, info = prob.cg_finish()
     info["max_iterations"] = int(max_iter)
     return alpha, rho, info
+
+
+def solve_refined(params: Parameter, A, B, eps: float, max_iter: int, sample_weight=None, options: Options | None = None, passes_out: list | None = None):
+    """The float64 system(s) solved to the float64 stop test by MIXED-PRECISION REFINEMENT (``lssvm_mi355_solve_refined_f64``): the CG iterations run in float32 on the
+    matrix-core kernels, the float64 problem supplies the true residual once per outer step, and a step that does not halve it hands the solve to the plain float64 CG.
+    ``B``: one right-hand side ``(N,)`` or ``k`` of them ``(k, N)``.  Returns ``(alphas, rhos, infos, refine_infos)`` -- ``alphas`` shaped like ``B``, ``rhos`` a scalar or
+    ``(k,)``, one ``lssvm_cg_info`` and one ``lssvm_refine_info`` dict per right-hand side (a single dict each for a single right-hand side).  Column ``c`` of a call with
+    several right-hand sides has the bits of the call with ``B[c]`` alone.  Device 0; ``A`` must be float64 (a float32 matrix has nothing to refine).  ``passes_out``: a list
+    that receives the call's ``(two-vector, single-vector)`` float64 Gram passes."""
+    A = _as_matrix(A)
+    if A.dtype != np.float64:
+        raise InvalidParameterError(f"solve_refined refines a float64 system; the data is {A.dtype} (solve_system_of_linear_equations solves it as it is)")
+    N, d = A.shape
+    B = np.ascontiguousarray(B, dtype=np.float64)
+    single = B.ndim == 1
+    B2 = B.reshape(1, -1) if single else B
+    if B2.ndim != 2 or B2.shape[0] == 0 or B2.shape[1] != N:
+        raise InvalidParameterError(f"The number of data points in the matrix A ({N}) and the values in every right hand side vector ({B2.shape[-1] if B2.ndim else 0}) must be the same!")
+    k = B2.shape[0]
+    w = None if sample_weight is None else _as_weights(sample_weight, N)
+    alphas = np.zeros_like(B2)
+    rhos = np.zeros(k, dtype=np.float64)
+    infos = (LssvmCgInfo * k)()
+    refine = (_capi.LssvmRefineInfo * k)()
+    passes = (C.c_uint64 * 2)()
+    check(_capi.refined_entry()(C.byref(_params_struct(params, d)), ptr(A), N, d, ptr(B2), k, _capi.weights_ptr(w), eps, int(max_iter), ptr(alphas),
+                                rhos.ctypes.data_as(C.POINTER(C.c_double)), infos, refine, passes, options_ptr(options)))
+    if passes_out is not None:
+        passes_out[:] = [int(passes[0]), int(passes[1])]
+    info_dicts, refine_dicts = [i.as_dict() for i in infos], [r.as_dict() for r in refine]
+    if single:
+        return alphas[0], np.float64(rhos[0]), info_dicts[0], refine_dicts[0]
+    return alphas, rhos, info_dicts, refine_dicts
 
 
 def generate_q(params: Parameter, data, options: Options | None = None):

@@ -266,6 +266,25 @@ int lssvm_mi355_solve_weighted_f64(const lssvm_params *params, const double *X, 
     });
 }
 
+static_assert(sizeof(lssvm_refine_info) == 104, "lssvm_refine_info changed: plssvm_amd/_capi.py (LssvmRefineInfo) changes with it");
+int lssvm_mi355_solve_refined_f64(const lssvm_params *params, const double *X, size_t num_points, size_t num_features, const double *Y, size_t num_rhs, const double *weights, double eps,
+                                  uint64_t max_iter, double *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, lssvm_refine_info *refine_out, uint64_t passes_out[2],
+                                  const lssvm_mi355_options *options) {
+    return guarded([&] {
+        // (all before a device is touched)
+        lssvm::check_params(params);
+        LSSVM_REQUIRE(X != nullptr && num_points > 0, "The data must not be empty!");                                                                  // csvm.cpp:73
+        LSSVM_REQUIRE(num_features > 0, "The data points must contain at least one feature!");                                                        // csvm.cpp:74
+        LSSVM_REQUIRE(num_rhs > 0, "The number of right hand sides must be greater than 0!");
+        LSSVM_REQUIRE(Y != nullptr, "The number of data points in the matrix A and the values in the right hand side vector must be the same!");      // csvm.cpp:76
+        LSSVM_REQUIRE(eps > 0.0, "The stopping criterion in the CG algorithm must be greater than 0.0, but is " + std::to_string(eps) + "!");          // csvm.cpp:77
+        LSSVM_REQUIRE(max_iter > 0, "The number of CG iterations must be greater than 0!");                                                           // csvm.cpp:78
+        LSSVM_REQUIRE(alphas_out != nullptr && rhos_out != nullptr, "alpha_out / rho_out must not be NULL");
+        if (weights != nullptr) lssvm::check_weights<double>(weights, num_points, params->cost);
+        lssvm::solve_refined_f64(options_of(options), *params, X, num_points, num_features, Y, num_rhs, weights, eps, max_iter, alphas_out, rhos_out, infos_out, refine_out, passes_out);
+    });
+}
+
 int lssvm_mi355_predict_values_f32(const lssvm_params *params, const float *sv, size_t nsv, size_t nfeat, const float *alpha, float rho, float *w_inout,
                                    int *w_valid, const float *points, size_t npoints, float *out, lssvm_predict_info *info, const lssvm_mi355_options *options) {
     return guarded([&] {

@@ -458,6 +458,79 @@ __global__ __launch_bounds__(RED_THREADS) void k_update_d(T *__restrict__ d, con
     }
 }
 
+/* ---- mixed-precision refinement (lssvm_refine.hip): the fp64 residual goes down to the fp32 solve scaled by its largest entry, the fp32 correction comes back up ---- */
+
+/* part[b][0] = max |v_i| over the block's grid-stride slice (a maximum has no order: the same bits however it is reduced; part[b][1] = 0) */
+template <typename T>
+__global__ __launch_bounds__(RED_THREADS) void k_absmax(const T *__restrict__ v, int n, double *__restrict__ part) {
+    __shared__ double lds[4];
+    double m = 0.0;
+    for (int i = blockIdx.x * RED_THREADS + threadIdx.x; i < n; i += RED_BLOCKS * RED_THREADS) m = fmax(m, fabs(static_cast<double>(v[i])));
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_down(m, off));
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        part[blockIdx.x * 2 + 0] = fmax(fmax(lds[0], lds[1]), fmax(lds[2], lds[3]));
+        part[blockIdx.x * 2 + 1] = 0.0;
+    }
+}
+/* ... k_absmax's RED_BLOCKS partials, reduced by every block of the consuming kernel for itself (as finish2_in_block does for sums) */
+__device__ __forceinline__ double absmax_in_block(const double *__restrict__ part, double *lds /* [5] */) {
+    double m = part[threadIdx.x * 2];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_down(m, off));
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) lds[4] = fmax(fmax(lds[0], lds[1]), fmax(lds[2], lds[3]));
+    __syncthreads();
+    return lds[4];
+}
+
+/* b_i = r0_i = TO(r_i / s), x0_i = 0 with s = max |r| (k_absmax's partials): the right-hand side, the first residual and the start vector of the inner solve written
+ * straight into its vectors; part = sum b_i^2, its delta0 (k_finish_delta), so that the solve begins without a Gram pass -- k_update_d then copies d = r0 */
+template <typename TI, typename TO>
+__global__ __launch_bounds__(RED_THREADS) void k_scale_down(const TI *__restrict__ r, const double *__restrict__ part_max, int n, TO *__restrict__ b, TO *__restrict__ r0,
+                                                            TO *__restrict__ x0, double *__restrict__ part) {
+    __shared__ double lds[8];
+    const double s = absmax_in_block(part_max, lds);
+    __syncthreads();  // (lds is reused by block_reduce)
+    double acc[2] = { 0.0, 0.0 };
+    for (int i = blockIdx.x * RED_THREADS + threadIdx.x; i < n; i += RED_BLOCKS * RED_THREADS) {
+        const TO bi = static_cast<TO>(static_cast<double>(r[i]) / s);
+        b[i] = bi;
+        r0[i] = bi;
+        x0[i] = TO(0);
+        acc[0] += static_cast<double>(bi) * static_cast<double>(bi);
+    }
+    block_reduce<2>(acc, lds);
+    if (threadIdx.x == 0) {
+        part[blockIdx.x * 2 + 0] = acc[0];
+        part[blockIdx.x * 2 + 1] = 0.0;
+    }
+}
+
+/* x_try_i = x_i + s * TX(e_i) with the same s ; part = (sum x_try, sum q x_try): what k_sum_and_qdot would leave for x_try (SC_SUMX / SC_QX of the residual that follows) */
+template <typename TX, typename TE>
+__global__ __launch_bounds__(RED_THREADS) void k_axpy_up(const TX *__restrict__ x, const TE *__restrict__ e, const double *__restrict__ part_max, const TX *__restrict__ q, int n,
+                                                         TX *__restrict__ x_try, double *__restrict__ part) {
+    __shared__ double lds[8];
+    const double s = absmax_in_block(part_max, lds);
+    __syncthreads();
+    double acc[2] = { 0.0, 0.0 };
+    for (int i = blockIdx.x * RED_THREADS + threadIdx.x; i < n; i += RED_BLOCKS * RED_THREADS) {
+        const TX xt = static_cast<TX>(static_cast<double>(x[i]) + s * static_cast<double>(e[i]));
+        x_try[i] = xt;
+        acc[0] += static_cast<double>(xt);
+        acc[1] += static_cast<double>(xt) * static_cast<double>(q[i]);
+    }
+    block_reduce<2>(acc, lds);
+    if (threadIdx.x == 0) {
+        part[blockIdx.x * 2 + 0] = acc[0];
+        part[blockIdx.x * 2 + 1] = acc[1];
+    }
+}
+
 template <typename T>
 __global__ void k_fill(T *__restrict__ v, int n, T value) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;

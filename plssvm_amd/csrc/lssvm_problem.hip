@@ -1268,6 +1268,11 @@ void Problem<T>::enqueue_sum_and_qdot(const T *v_dev, double *part_sums, double 
     hipLaunchKernelGGL(k_finish2, dim3(1), dim3(RED_THREADS), 0, stream_.s, part_sums, sc, slot_sum, slot_q);
     LSSVM_HIP_CHECK(hipGetLastError());
 }
+template <typename T>
+void Problem<T>::enqueue_finish2(const double *part_sums, double *sc, int slot_sum, int slot_q) {
+    hipLaunchKernelGGL(k_finish2, dim3(1), dim3(RED_THREADS), 0, stream_.s, part_sums, sc, slot_sum, slot_q);
+    LSSVM_HIP_CHECK(hipGetLastError());
+}
 
 /* ------------------------------------------------------------------ lanes ------------------------------------------------------------------ */
 template <typename T>

@@ -83,6 +83,11 @@ constexpr double RBF_GRID_MAX_R2 = 4096.0;    // rbf_form 0: grid planes (KT_RBF
                                               // terms |h||s| ~ R2 sqrt(d) 2^-12 (7 eps of a row's summands at R2 = 12 600, d = 128 in the model of tests/tools/grid_planes_model.py)
 constexpr double RBF_DIRECT_ABOVE = 32.0;     // rbf_form 0: the formula-exact kernel above this exponent scale 2 gamma log2(e) max|x - mean|^2 (absolute error of the
                                               // matrix-core exponent ~ 2^-24 x that; [-1, 1]-scaled data with gamma = 1 / num_features has <= 3)
+/* mixed-precision refinement (lssvm_refine.hip): the constants of its CPU model */
+constexpr double REFINE_INNER_EPS_MIN = 0x1p-16;  // the inner fp32 solve is never asked for more than this (relative to its right-hand side): below it fp32's own residual stalls
+constexpr double REFINE_INNER_EPS_MAX = 0x1p-4;   // ... nor for less: a step must pay for its fp64 pass
+constexpr double REFINE_ACCEPT_RATIO = 0.5;       // a step is accepted if the true residual's norm fell to at most this share; otherwise fp64 CG takes over
+constexpr uint64_t REFINE_INNER_CAP = 200;        // iterations of ONE inner solve at most
 constexpr int LINEAR_IN_TILE_BELOW = 10000;   // fp32 linear kernel on more than 256 features and fewer points than this: ONE launch of the polynomial tile kernels with degree 1
                                               // instead of launch-bound feature-panel passes (Problem<float>::tile_params_)
 constexpr int LINEAR_PANEL_FEATURES = 128;    // linear kernel beyond this many features: one pass of the <= 128-feature kernels per feature panel (fp32 f16x3: beats the
@@ -316,6 +321,7 @@ struct PlaneSet {
  * shards are driven by Solver<T>.  Replaces gpu_csvm::setup_data_on_device / generate_q / run_device_kernel (gpu_csvm.hpp:302-447). */
 template <typename T>
 class Solver;
+struct Refiner;  // lssvm_refine.hip
 
 template <typename T>
 class Problem {
@@ -334,6 +340,7 @@ class Problem {
     PackDc<T> pack_for_d(bool zero_first);  // what k_update_d needs to pack the records of d_ (dc == NULL: this problem packs per matvec); marks them as present
     void enqueue_sum_and_qdot(const T *v_dev, int slot_sum, int slot_q);
     void enqueue_sum_and_qdot(const T *v_dev, double *part_sums, double *sc, int slot_sum, int slot_q);  // ... into a lane's partial sums and scalars
+    void enqueue_finish2(const double *part_sums, double *sc, int slot_sum, int slot_q);  // ... its second half alone: the partial sums are there already (k_axpy_up)
     /* weighted LS-SVM (lssvm_mi355_problem_set_weights): inv_cw_ and QA_cost_ from the weights of all N points (validated by the caller), or back to the
      * unweighted system for NULL */
     void set_weights(const double *weights);
@@ -383,6 +390,7 @@ class Problem {
 
   private:
     friend class Solver<T>;
+    friend struct Refiner;
     TileArgs<T> tile_args(const T *v_dev) const;
 
     Options opt_{};
@@ -565,6 +573,11 @@ class Solver final : public ProblemBase {
     void matvec_pair(const void *d0, const void *d1, void *ret0_inout, void *ret1_inout, double add, int *two_vector_out) override;
     void solve_lockstep(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out) override;
     void cg_begin(const void *y, double eps) override;
+    /* cg_begin for the inner solve of the mixed-precision refinement: A e = r / max|r| from e = 0 -- b, the first residual and delta0 = b^T b come from ONE O(n) kernel
+     * over the outer fp64 residual `r_dev` (device 0, complete when the call is made; `absmax_part_dev`: k_absmax's partials of it), no Gram pass.  cg_step follows as
+     * after cg_begin; the solution is the device vector x_dev() */
+    void cg_begin_from_zero(const double *r_dev, const double *absmax_part_dev, double eps);
+    const T *x_dev() const { return shards_[0]->x_.p; }
     void cg_step(uint64_t iterations, int *done_out) override;
     int rebalance(const double *weights, int count) override;
     void cg_finish(void *alpha_out, double *rho_out, lssvm_cg_info *info) override;
@@ -574,6 +587,7 @@ class Solver final : public ProblemBase {
     void ipc_connect(const void *blobs, size_t total_bytes) override;
 
   private:
+    friend struct Refiner;
     enum class Exchange { none, process_rccl, local_rccl, peer, process_peer };
     enum class Vec { d, x, tmp };
     void apply_K(Vec which);  // every shard: Kres_ <- K * v (all rows)
@@ -611,6 +625,13 @@ class Solver final : public ProblemBase {
 
 /* measurement utility (mfma_ceiling.hip): TFLOP/s and held clock of a bare v_mfma_f32_16x16x32_bf16 loop on `device` */
 void measure_bf16_mfma_ceiling(int device, int b_from_lds, double settle_ms, double *tflops_out, double *clock_ghz_out, double *nominal_tflops_out);
+
+/* k_finish_delta on `s` (the kernel is defined by lssvm_solver.hip): delta <- the sum of `part`, published to `host_delta` */
+void enqueue_finish_delta(const double *part, double *sc, double *host_delta, int is_initial, hipStream_t s);
+
+/* lssvm_mi355_solve_refined_f64 (lssvm_refine.hip); the arguments have been checked */
+void solve_refined_f64(const Options &opt, const lssvm_params &params, const double *X, size_t num_points, size_t num_features, const double *Y, size_t num_rhs, const double *weights,
+                       double eps, uint64_t max_iter, double *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, lssvm_refine_info *refine_out, uint64_t *passes_out);
 
 /* one-shot helpers used by the C ABI */
 template <typename T>

@@ -305,6 +305,45 @@ void Solver<T>::cg_begin(const void *y, double eps) {
     cg_wall_ms_ += now_ms() - t0;
 }
 
+void enqueue_finish_delta(const double *part, double *sc, double *host_delta, int is_initial, hipStream_t s) {
+    hipLaunchKernelGGL(k_finish_delta, dim3(1), dim3(RED_THREADS), 0, s, part, sc, host_delta, is_initial);
+    LSSVM_HIP_CHECK(hipGetLastError());
+}
+
+/* The inner solve of the mixed-precision refinement begins: cg_begin's statements for b = r / max|r| and x = 0, where r = b - A x is b itself -- no Gram pass. */
+template <typename T>
+void Solver<T>::cg_begin_from_zero(const double *r_dev, const double *absmax_part_dev, double eps) {
+    LSSVM_REQUIRE(r_dev != nullptr && absmax_part_dev != nullptr, "The right hand side vector must not be empty!");
+    LSSVM_REQUIRE(static_cast<T>(eps) > T(0), "The stopping criterion in the CG algorithm must be greater than 0.0, but is " + std::to_string(eps) + "!");  // csvm.cpp:77
+    LSSVM_REQUIRE(shards_.size() == 1 && world_ == 1, "the inner solve of the refinement runs on one device");
+    const double t0 = now_ms();
+    eps_ = eps;
+    info_shard_ = -1;
+    iter_ = 0;
+    converged_ = false;
+    cg_wall_ms_ = 0.0;
+    y_last_ = 0.0;
+    Problem<T> &p = *shards_[0];
+    p.activate();
+    p.matvec_ms_ = p.pace_ms0_ = 0.0;
+    p.matvec_launches_ = 0;
+    p.matvec_timed_ = p.pace_timed0_ = 0;
+    hipStream_t st = p.stream();
+    hipLaunchKernelGGL((k_scale_down<double, T>), dim3(RED_BLOCKS), dim3(RED_THREADS), 0, st, r_dev, absmax_part_dev, p.n_, p.b_.p, p.r_.p, p.x_.p, p.part(PART_RR));
+    hipLaunchKernelGGL(k_finish_delta, dim3(1), dim3(RED_THREADS), 0, st, p.part(PART_RR), p.sc_.p, p.sc_.p + SC_COUNT - 1, 1);
+    hipLaunchKernelGGL(k_update_d<T>, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, st, p.d_.p, p.r_.p, p.q_.p, p.sc_.p, p.n_, 1, p.part(PART_D), pack_with_direction(p));  // d = r
+    LSSVM_HIP_CHECK(hipGetLastError());
+    LSSVM_HIP_CHECK(hipMemcpyAsync(p.host_sc_.p, p.sc_.p, SC_COUNT * sizeof(double), hipMemcpyDeviceToHost, st));
+    sync_all();
+    delta0_ = static_cast<double>(static_cast<T>(p.host_sc_.p[SC_DELTA0]));
+    delta_ = delta0_;
+    delta_before_ = 0.0;
+    held_back_ = 0;
+    begun_ = true;
+    in_cg_ = true;
+    cg_wall_ms_ += now_ms() - t0;
+}
+
 template <typename T>
 void Solver<T>::cg_step(uint64_t iterations, int *done_out) {
     LSSVM_REQUIRE(begun_, "cg_step called before cg_begin");

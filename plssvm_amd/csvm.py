@@ -165,14 +165,22 @@ def _drop_zero_weights(data: DataSet, sample_weight):
 class MI355CSVM(CSVM):
     """The MI355X backend (counterpart of plssvm::hip::csvm, HIP/csvm.hpp:39-99, csvm.hip.cpp:47-85)."""
 
-    def __init__(self, target=TargetPlatform.AUTOMATIC, params: Parameter | None = None, num_devices: int = 1, **kwargs):
-        """``num_devices``: devices ONE solve is sharded over -- 1 (default) = device 0 only, k = devices 0 .. k-1 (gpu_csvm.hpp:283-299),
+    def __init__(self, target=TargetPlatform.AUTOMATIC, params: Parameter | None = None, num_devices: int = 1, solver: str = "cg", **kwargs):
+        """``solver``: ``"cg"`` (default) = the CG of the data's real type; ``"refined"`` = float64 data on ONE device is solved by mixed-precision refinement
+        (``backend.solve_refined``: float32 CG iterations on the matrix cores inside a float64 residual loop, same stop test; the gain grows with the iteration
+        count) and ``last_refine_info`` keeps the per-solve reports -- float32 data or several devices solve as with ``"cg"`` and leave it None.
+
+        ``num_devices``: devices ONE solve is sharded over -- 1 (default) = device 0 only, k = devices 0 .. k-1 (gpu_csvm.hpp:283-299),
         0 = automatic (every visible device, at least 4096 points each, as the reference's backends take every device they find,
         csvm.hip.cpp:66-75).  Several devices are OPT-IN: results then depend on the device count through the order of the sums, the exchange
         bootstraps RCCL inside the process, and that path has not run on a multi-GPU box yet."""
         if isinstance(target, Parameter):
             target, params = TargetPlatform.AUTOMATIC, target
+        if solver not in ("cg", "refined"):
+            raise InvalidParameterError(f"solver must be 'cg' or 'refined', but is {solver!r}!")
         super().__init__(params, **kwargs)
+        self.solver = solver
+        self.last_refine_info = None
         if target not in (TargetPlatform.AUTOMATIC, TargetPlatform.GPU_AMD):
             raise BackendError(f"Invalid target platform '{target.value}' for the MI355 backend!")
         self.target_platform = TargetPlatform.GPU_AMD
@@ -195,8 +203,17 @@ class MI355CSVM(CSVM):
         return self._options.get(name) if self._options is not None else _capi.get_option(name)
 
     def solve_system_of_linear_equations(self, params, A, b, eps, max_iter, sample_weight=None):
+        self.last_refine_info = None
+        if self._refines(A):
+            alpha, rho, info, refine = backend.solve_refined(params, A, b, eps, max_iter, sample_weight=sample_weight, options=self._options)
+            self.last_refine_info = [refine]
+            return alpha, rho, info
         # all devices of this process behind ONE call (gpu_csvm::solve_system_of_linear_equations_impl, gpu_csvm.hpp:477-654)
         return backend.solve_system_of_linear_equations(params, A, b, eps, max_iter, num_devices=self.use_devices, options=self._options, sample_weight=sample_weight)
+
+    def _refines(self, A) -> bool:
+        """solver="refined" applies: float64 data on one device."""
+        return self.solver == "refined" and self.use_devices == 1 and backend._as_matrix(A).dtype == np.float64
 
     def predict_values(self, params, support_vectors, alpha, rho, w, predict_points):
         return backend.predict_values(params, support_vectors, alpha, rho, w, predict_points, options=self._options)
@@ -206,8 +223,16 @@ class MI355CSVM(CSVM):
         set once, and every right-hand side runs the recipe of the one-shot solve (begin / step / finish) on it -- the same alpha, rho and iteration count as a fresh
         one-shot solve.  In fp64 on the symmetric resident-row-panel kernel one pass over the Gram tiles serves two right-hand sides per iteration; elsewhere they are solved
         one after the other.  Several devices: the base class's loop of one-shot solves."""
+        self.last_refine_info = None
         if self.use_devices != 1:
             return super().solve_systems_of_linear_equations(params, A, B, eps, max_iter, sample_weight=sample_weight)
+        if self._refines(A):
+            B = np.asarray(B)
+            if B.ndim != 2 or B.shape[0] == 0:
+                raise InvalidParameterError("The right-hand sides must be a matrix with one row per system and at least one row!")
+            alphas, rhos, infos, refine = backend.solve_refined(params, A, B, eps, max_iter, sample_weight=sample_weight, options=self._options)
+            self.last_refine_info = refine
+            return alphas, rhos, infos
         A = backend._as_matrix(A)
         N = A.shape[0]
         B = np.ascontiguousarray(B, dtype=A.dtype)
