@@ -17,8 +17,8 @@
 
 #include "lssvm_device_common.hip.hpp"
 
-/* The kernels that are not templates are DEFINED by the one translation unit that launches them: lssvm_problem.hip (data set-up, record packing, k_finish2)
- * defines LSSVM_KERNELS_SETUP before it includes this header, lssvm_solver.hip (k_finish_delta) LSSVM_KERNELS_CG.  The templates are instantiated where they are used. */
+/* The kernels that are not templates are DEFINED by the one translation unit that launches them: lssvm_problem.hip (data set-up, record packing)
+ * defines LSSVM_KERNELS_SETUP before it includes this header, lssvm_solver.hip (k_finish2, k_finish_delta) LSSVM_KERNELS_CG.  The templates are instantiated where they are used. */
 
 namespace lssvm {
 
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(RED_THREADS) void k_sum_and_qdot(const T *__restric
 }
 
 /* single block: out[slot0] = sum part[.][0], out[slot1] = sum part[.][1]  (fixed tree order) */
-#ifdef LSSVM_KERNELS_SETUP
+#ifdef LSSVM_KERNELS_CG
 __global__ __launch_bounds__(RED_THREADS) void k_finish2(const double *__restrict__ part, double *__restrict__ sc, int slot0, int slot1) {
     __shared__ double lds[8];
     double acc[2] = { part[threadIdx.x * 2 + 0], part[threadIdx.x * 2 + 1] };
@@ -218,7 +218,7 @@ __global__ __launch_bounds__(RED_THREADS) void k_finish2(const double *__restric
         if (slot1 >= 0) sc[slot1] = acc[1];
     }
 }
-#endif  // LSSVM_KERNELS_SETUP
+#endif  // LSSVM_KERNELS_CG
 
 /* Kv[row_begin + i] = sum over column chunks of partial[c][i], chunks in ascending order (rows of this device only) */
 template <typename T>

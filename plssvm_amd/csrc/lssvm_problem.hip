@@ -826,7 +826,7 @@ void Problem<T>::reshard(const std::vector<double> &weights) {
     opt_.shard_weights = weights;
     choose_shard_geometry();
     build_shard_lists(stream_.s);
-    d_packed_ = false;  // (the records of d_ are shard independent, but K*v is cleared again by the next matvec: the plain path)
+    d_packed_ = false;  // (the records of d are shard independent, but K*v is cleared again by the next matvec: the plain path)
     pace_ms0_ = matvec_ms_;  // the pace of the NEW share is measured from here on; the counters lssvm_cg_info reports keep running
     pace_timed0_ = matvec_timed_;
     LSSVM_HIP_CHECK(hipStreamSynchronize(stream_.s));
@@ -971,13 +971,9 @@ Problem<T>::Problem(const Options &opt, const lssvm_params &params, const void *
     QA_cost_ = static_cast<double>(static_cast<T>(self_last_) + T(1) / static_cast<T>(params_.cost));
 
     // vectors (zero padded to nvec_)
-    for (DevBuf<T> *v : { &q_, &b_, &x_, &r_, &d_, &Ad_, &Kv_, &tmp_ }) v->alloc_zero(static_cast<size_t>(nvec_) + TILE, st);
+    for (DevBuf<T> *v : { &q_, &Kv_, &tmp_ }) v->alloc_zero(static_cast<size_t>(nvec_) + TILE, st);
     Kres_ = Kv_.p;
-    ylast_.alloc_zero(num_points, st);
-    part_.alloc_zero(static_cast<size_t>(PART_REGIONS) * RED_BLOCKS * 2, st);  // (four sets of partial sums: a kernel reduces its predecessor's while it writes its own)
-    sc_.alloc_zero(SC_COUNT, st);
-    host_sc_.alloc(SC_COUNT);
-    host_delta_.alloc_mapped(1);
+    own_.alloc(static_cast<size_t>(nvec_) + TILE, num_points, false, st);
 
     lap("QA_cost, vectors");
     // q from the raw (un-centred) data: bit-compatible fma chains (q_kernel.cpp:18-55)
@@ -1150,7 +1146,7 @@ void Problem<T>::enqueue_apply_K_local(const T *v_dev, bool zero_first) {
             v_dev = vs_.p;
         }
     }
-    const bool prepacked = d_packed_ && v_dev == d_.p;  // k_update_d has left the records of d_ and cleared K*v (pack_for_d)
+    const bool prepacked = d_packed_ && v_dev == own_.d.p;  // k_update_d has left the records of the own state's d and cleared K*v (pack_for_d)
     d_packed_ = false;                                  // (either they are consumed now, or dc_ is about to hold another vector's)
     const bool pack = dc_.p != nullptr && num_ib_ > 0 && !prepacked;
     if (clear && !pack && !prepacked) LSSVM_HIP_CHECK(hipMemsetAsync(Kv_.p, 0, static_cast<size_t>(nvec_) * sizeof(T), st));
@@ -1258,35 +1254,13 @@ PackDc<T> Problem<T>::pack_for_d(bool zero_first) {
     return pk;
 }
 
-template <typename T>
-void Problem<T>::enqueue_sum_and_qdot(const T *v_dev, int slot_sum, int slot_q) {
-    enqueue_sum_and_qdot(v_dev, part(PART_SUMS), sc_.p, slot_sum, slot_q);
-}
-template <typename T>
-void Problem<T>::enqueue_sum_and_qdot(const T *v_dev, double *part_sums, double *sc, int slot_sum, int slot_q) {
-    hipLaunchKernelGGL(k_sum_and_qdot<T>, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, stream_.s, v_dev, q_.p, n_, part_sums);
-    hipLaunchKernelGGL(k_finish2, dim3(1), dim3(RED_THREADS), 0, stream_.s, part_sums, sc, slot_sum, slot_q);
-    LSSVM_HIP_CHECK(hipGetLastError());
-}
-template <typename T>
-void Problem<T>::enqueue_finish2(const double *part_sums, double *sc, int slot_sum, int slot_q) {
-    hipLaunchKernelGGL(k_finish2, dim3(1), dim3(RED_THREADS), 0, stream_.s, part_sums, sc, slot_sum, slot_q);
-    LSSVM_HIP_CHECK(hipGetLastError());
-}
-
 /* ------------------------------------------------------------------ lanes ------------------------------------------------------------------ */
 template <typename T>
-typename Problem<T>::Lane &Problem<T>::lane(size_t k) {
+CgState<T> &Problem<T>::lane(size_t k) {
     activate();
     while (lanes_.size() <= k) {
-        auto l = std::make_unique<Lane>();
-        for (DevBuf<T> *v : { &l->b, &l->x, &l->r, &l->d, &l->Ad, &l->Kv }) v->alloc_zero(static_cast<size_t>(nvec_) + TILE, stream_.s);  // (as the problem's own vectors)
-        l->y.alloc_zero(N_, stream_.s);
-        l->part.alloc_zero(static_cast<size_t>(PART_REGIONS) * RED_BLOCKS * 2, stream_.s);
-        l->sc.alloc_zero(SC_COUNT, stream_.s);
-        l->host_sc.alloc(SC_COUNT);
-        l->host_delta.alloc_mapped(1);
-        lanes_.push_back(std::move(l));
+        lanes_.push_back(std::make_unique<CgState<T>>());
+        lanes_.back()->alloc(static_cast<size_t>(nvec_) + TILE, N_, true, stream_.s);  // (as the problem's own vectors)
     }
     return *lanes_[k];
 }

@@ -274,6 +274,17 @@ struct PinnedBuf {
     }
 };
 
+/* `ref` <- `value` when the scope ends, however it ends: the handle's busy flag, an option changed for one call */
+template <typename V>
+struct SetOnExit {
+    V &ref;
+    V value;
+    SetOnExit(V &r, V v) : ref(r), value(v) {}
+    SetOnExit(const SetOnExit &) = delete;
+    SetOnExit &operator=(const SetOnExit &) = delete;
+    ~SetOnExit() { ref = value; }
+};
+
 /* ------------------------------------------------------------------ tile kernel launch ------------------------------------------------------------------ */
 template <typename T>
 void launch_tile_kernel(TileArgs<T> &a, int kernel_type, bool rbf_direct, int num_jc, hipStream_t s);
@@ -321,7 +332,29 @@ struct PlaneSet {
  * shards are driven by Solver<T>.  Replaces gpu_csvm::setup_data_on_device / generate_q / run_device_kernel (gpu_csvm.hpp:302-447). */
 template <typename T>
 class Solver;
-struct Refiner;  // lssvm_refine.hip
+template <typename T>
+class CgSteps;
+
+/* The CG state of ONE right-hand side on one device: the vectors y, b, x, r, d, Ad, the scalars and the four sets of partial sums, the host copies of the scalars and a
+ * mapped host word for the iteration's delta (k_finish_delta stores its 8 bytes straight into host memory: no copy per iteration).  A problem has one of its own (the
+ * single solve: its K*v is the problem's exchanged vector, `Kv` stays empty) and one per lane (solve_lockstep, matvec_pair, the refinement: each with a K*v of its own). */
+template <typename T>
+struct CgState {
+    DevBuf<T> y, b, x, r, d, Ad, Kv;
+    DevBuf<double> part, sc;
+    double *part_of(PartSet s) const { return part.p + static_cast<size_t>(s) * RED_BLOCKS * 2; }  // (lssvm_types.hpp)
+    PinnedBuf<double> host_sc, host_delta;
+    double delta_on_host() const { return *static_cast<volatile double *>(host_delta.p); }  // (behind an event of the stream)
+    void alloc(size_t vec_len, size_t num_points, bool own_Kv, hipStream_t s) {
+        for (DevBuf<T> *v : { &b, &x, &r, &d, &Ad }) v->alloc_zero(vec_len, s);
+        if (own_Kv) Kv.alloc_zero(vec_len, s);
+        y.alloc_zero(num_points, s);
+        part.alloc_zero(static_cast<size_t>(PART_REGIONS) * RED_BLOCKS * 2, s);  // (four sets of partial sums: a kernel reduces its predecessor's while it writes its own)
+        sc.alloc_zero(SC_COUNT, s);
+        host_sc.alloc(SC_COUNT);
+        host_delta.alloc_mapped(1);
+    }
+};
 
 template <typename T>
 class Problem {
@@ -337,10 +370,7 @@ class Problem {
     void reshard(const std::vector<double> &weights);  // new shares of the triangle (lssvm_mi355_problem_rebalance): the data, the vectors and the CG state stay
     void choose_shard_geometry();
     void build_shard_lists(hipStream_t st);
-    PackDc<T> pack_for_d(bool zero_first);  // what k_update_d needs to pack the records of d_ (dc == NULL: this problem packs per matvec); marks them as present
-    void enqueue_sum_and_qdot(const T *v_dev, int slot_sum, int slot_q);
-    void enqueue_sum_and_qdot(const T *v_dev, double *part_sums, double *sc, int slot_sum, int slot_q);  // ... into a lane's partial sums and scalars
-    void enqueue_finish2(const double *part_sums, double *sc, int slot_sum, int slot_q);  // ... its second half alone: the partial sums are there already (k_axpy_up)
+    PackDc<T> pack_for_d(bool zero_first);  // what k_update_d needs to pack the records of the own state's d (dc == NULL: this problem packs per matvec); marks them as present
     /* weighted LS-SVM (lssvm_mi355_problem_set_weights): inv_cw_ and QA_cost_ from the weights of all N points (validated by the caller), or back to the
      * unweighted system for NULL */
     void set_weights(const double *weights);
@@ -372,15 +402,9 @@ class Problem {
         }
     }
 
-    /* ---- lanes (Solver<T>::solve_lockstep, matvec_pair): the CG state of ONE right-hand side beside the problem's own -- the vectors b, x, r, d, Ad, K*v, the scalars and
-     * partial-sum slots, a mapped host word for its delta.  Allocated on first use, freed with the problem; the single-vector members below are not involved. ---- */
-    struct Lane {
-        DevBuf<T> y, b, x, r, d, Ad, Kv;
-        DevBuf<double> part, sc;
-        double *part_of(PartSet s) const { return part.p + static_cast<size_t>(s) * RED_BLOCKS * 2; }
-        PinnedBuf<double> host_sc, host_delta;
-    };
-    Lane &lane(size_t k);
+    /* ---- lanes (Solver<T>::solve_lockstep, matvec_pair, the refinement): CG states beside the problem's own, each with its K*v.  Allocated on first use, freed with the
+     * problem; the own state is not involved. ---- */
+    CgState<T> &lane(size_t k);
     /* where one Gram pass can serve two vectors: the fp64 symmetric v2 kernel on an unsharded problem without feature panels -- and only the (kernel function, chunk
      * count) instantiations whose two-vector pass was measured faster than two single passes (profiles/lockstep_f64.json) */
     bool pair_kernel_applies() const;
@@ -390,7 +414,7 @@ class Problem {
 
   private:
     friend class Solver<T>;
-    friend struct Refiner;
+    friend class CgSteps<T>;
     TileArgs<T> tile_args(const T *v_dev) const;
 
     Options opt_{};
@@ -430,13 +454,14 @@ class Problem {
 
     DeviceMatrix<T> X_;
     DevBuf<T> c_;  // -0.5 |x|^2 (rbf, centred data)
-    DevBuf<T> q_, b_, x_, r_, d_, Ad_, Kv_, Ksum_, tmp_, ylast_;
+    DevBuf<T> q_, Kv_, Ksum_, tmp_;
+    CgState<T> own_;     // the CG state of the single solve (cg_begin / cg_step / cg_finish, matvec); its K*v is Kres_
     T *Kres_ = nullptr;  // the exchanged K * v the O(n) kernels read: Kv_ itself, or Ksum_ when peer kernels do the exchange
     DevBuf<T> partial_;
     DevBuf<T> dc_;  // v2 kernels: packed (d_j | c_j) records
-    std::vector<std::unique_ptr<Lane>> lanes_;
+    std::vector<std::unique_ptr<CgState<T>>> lanes_;
     DevBuf<T> pair_dc_, pair_partial_, pair_colslab_;  // two-vector passes: (d0_j | d1_j | c_j) records, and both vectors' planes of the row slabs / the column slab
-    bool d_packed_ = false;  // dc_ holds the records of d_ and K*v is cleared: k_update_d left them (pack_for_d), the next implicit matvec of d_ launches no k_pack_dc
+    bool d_packed_ = false;  // dc_ holds the records of own_.d and K*v is cleared: k_update_d left them (pack_for_d), the next implicit matvec of that d launches no k_pack_dc
     // symmetric variant
     bool sym_ = false;
     DevBuf<int2> items_;
@@ -453,10 +478,6 @@ class Problem {
         long pair_origin;           // record index of (ib_begin, 0) in the packed triangle: ib_begin (ib_begin - 1) / 2
     };
     std::vector<Band> bands_;
-    DevBuf<double> part_, sc_;
-    double *part(PartSet s) const { return part_.p + static_cast<size_t>(s) * RED_BLOCKS * 2; }  // (lssvm_types.hpp)
-    PinnedBuf<double> host_sc_;  // SC_COUNT doubles
-    PinnedBuf<double> host_delta_;  // one word: k_finish_delta stores the iteration's delta straight into host memory (no copy kernel per iteration)
     double QA_cost_ = 0.0;
     double inv_cost_ = 1.0;
     double self_last_ = 0.0;  // k(x_last, x_last) in the real type: QA_cost_ = self_last_ + 1/(C w_last) (set_weights)
@@ -484,6 +505,66 @@ class Problem {
     std::vector<EvPair> events_;
     Event ev_ready_, ev_consumed_;  // peer exchange: partial vector written / all partial vectors read
 };
+
+/* ------------------------------------------------------------------ the CG recipe, step by step ------------------------------------------------------------------ */
+/* CgSteps<T>: the O(n) steps of the reference's CG recipe (csvm.cpp:71-183) on ONE CG state of ONE problem -- its stream, q, n, QA_cost and diagonal term.  Every step
+ * only enqueues (finish_now excepted); a step that reads K * v is handed the pointer to it.  The drivers -- the sharded single solve, the lanes, the refinement -- decide
+ * when the Gram passes run and where the host waits; which O(n) kernel runs on which arguments is written here and nowhere else, so their recurrences have the same
+ * bits.  Defined by lssvm_solver.hip. */
+template <typename T>
+class CgSteps {
+  public:
+    using State = CgState<T>;
+    explicit CgSteps(Problem<T> &p) : p_(p) {}
+    hipStream_t stream() const { return p_.stream_.s; }
+    int n() const { return p_.n_; }
+    size_t num_points() const { return p_.N_; }
+    const T *q() const { return p_.q_.p; }
+    T *Kres() const { return p_.Kres_; }  // where the problem's own pass (enqueue_apply_K_local + the exchange) leaves K * v
+
+    /* sc[slot_sum] = sum v, sc[slot_q] = q^T v; finish_sums: its second half alone, the partial sums are in PART_SUMS already (k_axpy_up) */
+    void sum_and_qdot(const State &s, const T *v, int slot_sum, int slot_q) const;
+    void finish_sums(const State &s, int slot_sum, int slot_q) const;
+    /* b = y - y_last, x = 1 and the sums of x that r = b - A x needs (csvm.cpp:89-95); K * x and `residual` follow */
+    void begin(const State &s, const T *y_host) const;
+    /* b = r = r_dev / max|r_dev|, x = 0, the partial sums of r^T r (the inner solve of the refinement: no Gram pass) */
+    void begin_from_zero(const State &s, const double *r_dev, const double *absmax_part_dev) const;
+    /* r_out = b - A x with Kv = K * x and the sums of x in the scalars; the partial sums of r_out^T r_out into `part`   (csvm.cpp:101-107, :140-145) */
+    void residual(const State &s, const T *Kv, const T *x, T *r_out, PartSet part) const;
+    /* delta = the sum of `part`, published to `host_delta`   (csvm.cpp:107-108, :152-153) */
+    void finish_delta(const State &s, PartSet part, double *host_delta, bool initial) const;
+    /* d = r (initial) or beta d + r, and -- as partial sums that Ad_and_dAd finishes for itself -- the sums the next matvec's rank-1 terms need   (csvm.cpp:111, :161-163) */
+    void update_d(const State &s, bool initial, const PackDc<T> &pack = PackDc<T>{}) const;
+    /* one iteration up to its delta, with Kv = K * d: Ad = A d, alpha = delta / d.Ad, x += alpha d, r -= alpha Ad -- or with `refresh`, every 50th iteration, x only and
+     * its sums: K * x and `residual` follow   (csvm.cpp:131-148) */
+    void advance(const State &s, const T *Kv, bool refresh) const;
+    /* Ad += add * A v with Kv = K * v and the sums of v in SC_S / SC_QD   (csvm.cpp:283-306) */
+    void apply_ret(const State &s, const T *Kv, const T *v, double add) const;
+    /* the sums of x and the scalars to the host, x to alpha_out (where given); after the stream has been waited for, read_solution: alpha_N = -sum(x),
+     * rho = -bias = -(y_last + QA_cost * sum(x) - q^T x)   (csvm.cpp:179-182).  finish_now: both around a wait for the stream */
+    void enqueue_finish(const State &s, T *alpha_out) const;
+    void read_solution(const State &s, double y_last, T *alpha_out, double *rho_out) const;
+    void finish_now(const State &s, double y_last, T *alpha_out, double *rho_out) const;
+
+  private:
+    template <typename Launch>
+    void with_diag(Launch &&launch) const;  // the one place that chooses between the weighted and the unweighted instantiation of a kernel
+    Problem<T> &p_;
+};
+
+/* the fields of lssvm_cg_info that describe how a solve went (describe_path fills in where it ran) */
+inline void fill_cg_outcome(lssvm_cg_info *info, uint64_t iterations, uint64_t max_iterations, double residuum, double initial_residuum, double target_residuum, double epsilon,
+                            double total_ms, bool converged) {
+    info->iterations = iterations;
+    info->max_iterations = max_iterations;
+    info->residuum = residuum;
+    info->initial_residuum = initial_residuum;
+    info->target_residuum = target_residuum;
+    info->epsilon = epsilon;
+    info->total_ms = total_ms;
+    info->avg_iteration_ms = iterations > 0 ? total_ms / static_cast<double>(iterations) : 0.0;
+    info->converged = converged ? 1 : 0;
+}
 
 /* ------------------------------------------------------------------ the resident problem (what a C handle points to) ------------------------------------------------------------------ */
 struct ProblemBase {
@@ -577,7 +658,7 @@ class Solver final : public ProblemBase {
      * over the outer fp64 residual `r_dev` (device 0, complete when the call is made; `absmax_part_dev`: k_absmax's partials of it), no Gram pass.  cg_step follows as
      * after cg_begin; the solution is the device vector x_dev() */
     void cg_begin_from_zero(const double *r_dev, const double *absmax_part_dev, double eps);
-    const T *x_dev() const { return shards_[0]->x_.p; }
+    const T *x_dev() const { return shards_[0]->own_.x.p; }
     void cg_step(uint64_t iterations, int *done_out) override;
     int rebalance(const double *weights, int count) override;
     void cg_finish(void *alpha_out, double *rho_out, lssvm_cg_info *info) override;
@@ -586,8 +667,17 @@ class Solver final : public ProblemBase {
     void ipc_export(void *blob_out, size_t blob_bytes) override;
     void ipc_connect(const void *blobs, size_t total_bytes) override;
 
+    /* for a driver that runs on lanes of shard 0 (the lockstep solve here, the refinement in lssvm_refine.hip) */
+    Problem<T> &shard0() { return *shards_[0]; }
+    bool lanes_apply() const;  // one unsharded device without an exchange, where the two-vector kernel applies
+    void wait_for_deltas();    // the host waits for what shard 0's stream holds: the deltas of the step are in their host words
+    /* until the returned object goes: no other solve may begin on this handle, and its weights stay */
+    [[nodiscard]] SetOnExit<bool> hold_busy() {
+        in_cg_ = true;
+        return SetOnExit<bool>(in_cg_, false);
+    }
+
   private:
-    friend struct Refiner;
     enum class Exchange { none, process_rccl, local_rccl, peer, process_peer };
     enum class Vec { d, x, tmp };
     void apply_K(Vec which);  // every shard: Kres_ <- K * v (all rows)
@@ -595,10 +685,11 @@ class Solver final : public ProblemBase {
     void sync_all();
     PackDc<T> pack_with_direction(Problem<T> &p);
     void describe_path(lssvm_cg_info *info);
-    bool lanes_apply() const;  // the lockstep driver runs on lanes of shard 0: one unsharded device without an exchange, where the two-vector kernel applies
+    void reset_cg(double eps, double y_last);  // cg_begin, cg_begin_from_zero: the host's counters and scalars of a new solve
+    void read_delta0(double t0);               // ... and their end: delta0 is read, the handle is between begin and finish
     void solve_in_sequence(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out);
     void solve_on_lanes(const T *Y, size_t num_rhs, double eps, uint64_t max_iter, T *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out);
-    T *vec_of(Problem<T> &p, Vec which) const { return which == Vec::d ? p.d_.p : (which == Vec::x ? p.x_.p : p.tmp_.p); }
+    T *vec_of(Problem<T> &p, Vec which) const { return which == Vec::d ? p.own_.d.p : (which == Vec::x ? p.own_.x.p : p.tmp_.p); }
 
     Options opt_{};
     std::vector<std::unique_ptr<Problem<T>>> shards_;
@@ -625,9 +716,6 @@ class Solver final : public ProblemBase {
 
 /* measurement utility (mfma_ceiling.hip): TFLOP/s and held clock of a bare v_mfma_f32_16x16x32_bf16 loop on `device` */
 void measure_bf16_mfma_ceiling(int device, int b_from_lds, double settle_ms, double *tflops_out, double *clock_ghz_out, double *nominal_tflops_out);
-
-/* k_finish_delta on `s` (the kernel is defined by lssvm_solver.hip): delta <- the sum of `part`, published to `host_delta` */
-void enqueue_finish_delta(const double *part, double *sc, double *host_delta, int is_initial, hipStream_t s);
 
 /* lssvm_mi355_solve_refined_f64 (lssvm_refine.hip); the arguments have been checked */
 void solve_refined_f64(const Options &opt, const lssvm_params &params, const double *X, size_t num_points, size_t num_features, const double *Y, size_t num_rhs, const double *weights,

@@ -5,7 +5,7 @@
  * (Solver<float>::cg_begin_from_zero, then cg_step as ever); x + max|r| e is kept if the true residual's norm fell to at most REFINE_ACCEPT_RATIO, else the plain fp64 CG
  * continues from the (x, r) before that step.  Every right-hand side lives on a lane of P64; the outer passes of two right-hand sides that are due together share one
  * pass of the two-vector kernel, which leaves each the bits of its own pass -- so a column of a multi call has the bits of the single call.  No tile kernel is involved
- * beyond being launched; the O(n) kernels are those of the CG loop plus k_absmax, k_scale_down and k_axpy_up (lssvm_kernels.hip.hpp).  Compiled for gfx950 only.
+ * beyond being launched; the CG recipe is CgSteps' (lssvm_solver.hip), the kernels launched here are the refinement's own, k_absmax and k_axpy_up.  Compiled for gfx950 only.
  */
 #include "lssvm_problem.hip.hpp"
 
@@ -17,11 +17,12 @@
 namespace lssvm {
 
 struct Refiner {
-    using Lane = Problem<double>::Lane;
+    using Lane = CgState<double>;
 
     Solver<double> &s64;
     Solver<float> &s32;
     Problem<double> &p;
+    const CgSteps<double> cg;
     const bool lanes;  // the right-hand sides advance together on lanes and pair their outer passes; else one after the other on lane 0 with the problem's own pass
     const double eps;
     const uint64_t max_iter;
@@ -42,13 +43,13 @@ struct Refiner {
     std::vector<Rhs> rhs;
 
     Refiner(Solver<double> &a, Solver<float> &b, size_t num_rhs, double eps_, uint64_t max_iter_, double t_call_) :
-        s64(a), s32(b), p(*a.shards_[0]), lanes(a.lanes_apply()), eps(eps_), max_iter(max_iter_), t_call(t_call_), rhs(num_rhs) {
+        s64(a), s32(b), p(a.shard0()), cg(p), lanes(a.lanes_apply()), eps(eps_), max_iter(max_iter_), t_call(t_call_), rhs(num_rhs) {
         p.activate();
-        st = p.stream();
-        n = p.n_;
+        st = cg.stream();
+        n = cg.n();
         for (size_t c = 0; c < num_rhs; ++c) {
             rhs[c].lane = &p.lane(lanes ? c : 0);
-            rhs[c].Kv = lanes ? rhs[c].lane->Kv.p : p.Kres_;
+            rhs[c].Kv = lanes ? rhs[c].lane->Kv.p : cg.Kres();
         }
     }
 
@@ -62,59 +63,40 @@ struct Refiner {
             if (lanes) {
                 p.enqueue_apply_K_lanes(which(*r0.lane), r0.Kv, r1 != nullptr ? which(*r1->lane) : nullptr, r1 != nullptr ? r1->Kv : nullptr, nullptr, nullptr);
             } else {
-                p.enqueue_apply_K_local(which(*r0.lane), false);  // (into p.Kres_: `who` is a single right-hand side here)
+                p.enqueue_apply_K_local(which(*r0.lane), false);  // (into cg.Kres(): `who` is a single right-hand side here)
             }
             ++passes[r1 != nullptr ? 0 : 1];
             ++r0.f64_passes;
             if (r1 != nullptr) ++r1->f64_passes;
         }
     }
-    void residual(const Rhs &r, const double *x, double *r_out, PartSet part) {
-        const Lane &l = *r.lane;
-        const dim3 gr(RED_BLOCKS), br(RED_THREADS);
-        if (p.weighted_) {
-            hipLaunchKernelGGL((k_residual<double, true>), gr, br, 0, st, r.Kv, x, p.q_.p, l.b.p, l.sc.p, n, p.inv_cw_.p, p.QA_cost_, r_out, l.part_of(part));
-        } else {
-            hipLaunchKernelGGL(k_residual<double>, gr, br, 0, st, r.Kv, x, p.q_.p, l.b.p, l.sc.p, n, p.inv_cost_, p.QA_cost_, r_out, l.part_of(part));
-        }
-        LSSVM_HIP_CHECK(hipGetLastError());
-    }
     void wait() {
-        LSSVM_HIP_CHECK(hipGetLastError());
-        LSSVM_HIP_CHECK(hipEventRecord(s64.ev_delta_.e, st));
-        LSSVM_HIP_CHECK(hipEventSynchronize(s64.ev_delta_.e));
+        s64.wait_for_deltas();
         p.drain_events();
     }
-    void hold(bool on) { s64.in_cg_ = on; }  // between begin and finish no other solve may begin on the fp64 problem, and its weights stay
-    static double delta_of(const Lane &l) { return *static_cast<volatile double *>(l.host_delta.p); }
 
     /* step 2: b = y - y_last, x = 1, r = b - A x, delta0, target; the largest |r_i| for the first step */
     void begin(const std::vector<size_t> &who, const double *Y) {
         const double t0 = now_ms();
-        const size_t N = p.N_;
-        const dim3 gn((n + 255) / 256), bn(256), gr(RED_BLOCKS), br(RED_THREADS);
+        const size_t N = cg.num_points();
+        const dim3 gr(RED_BLOCKS), br(RED_THREADS);
         for (size_t c : who) {
-            Rhs &r = rhs[c];
-            const Lane &l = *r.lane;
-            r.y_last = Y[c * N + N - 1];
-            LSSVM_HIP_CHECK(hipMemcpyAsync(l.y.p, Y + c * N, N * sizeof(double), hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(k_make_b<double>, gn, bn, 0, st, l.y.p, n, l.b.p);
-            hipLaunchKernelGGL(k_fill<double>, gn, bn, 0, st, l.x.p, n, 1.0);
-            p.enqueue_sum_and_qdot(l.x.p, l.part_of(PART_SUMS), l.sc.p, SC_SUMX, SC_QX);
+            rhs[c].y_last = Y[c * N + N - 1];
+            cg.begin(*rhs[c].lane, Y + c * N);
         }
         apply_K(who, [](const Lane &l) { return l.x.p; });
         for (size_t c : who) {
             const Rhs &r = rhs[c];
             const Lane &l = *r.lane;
-            residual(r, l.x.p, l.r.p, PART_RR);
-            enqueue_finish_delta(l.part_of(PART_RR), l.sc.p, l.host_delta.dev, 1, st);
+            cg.residual(l, r.Kv, l.x.p, l.r.p, PART_RR);
+            cg.finish_delta(l, PART_RR, l.host_delta.dev, true);
             hipLaunchKernelGGL(k_absmax<double>, gr, br, 0, st, l.r.p, n, l.part_of(PART_D));
         }
         wait();
         const double ms = now_ms() - t0;
         for (size_t c : who) {
             Rhs &r = rhs[c];
-            r.delta0 = r.rr = delta_of(*r.lane);
+            r.delta0 = r.rr = r.lane->delta_on_host();
             r.target = eps * eps * r.delta0;
             r.f64_ms += ms;
         }
@@ -151,8 +133,8 @@ struct Refiner {
                 r.f32_passes += inner.matvec_launches;
                 r.f32_ms += now_ms() - t0;
                 p.activate();
-                hipLaunchKernelGGL((k_axpy_up<double, float>), gr, br, 0, st, l.x.p, s32.x_dev(), l.part_of(PART_D), p.q_.p, n, l.d.p, l.part_of(PART_SUMS));
-                p.enqueue_finish2(l.part_of(PART_SUMS), l.sc.p, SC_SUMX, SC_QX);
+                hipLaunchKernelGGL((k_axpy_up<double, float>), gr, br, 0, st, l.x.p, s32.x_dev(), l.part_of(PART_D), cg.q(), n, l.d.p, l.part_of(PART_SUMS));
+                cg.finish_sums(l, SC_SUMX, SC_QX);
                 if (due.size() > 1) LSSVM_HIP_CHECK(hipStreamSynchronize(st));  // (the next inner solve overwrites e)
             }
             // the true residuals r_try = b - A x_try (into l.Ad), two right-hand sides per fp64 pass
@@ -161,8 +143,8 @@ struct Refiner {
             for (size_t c : due) {
                 const Rhs &r = rhs[c];
                 const Lane &l = *r.lane;
-                residual(r, l.d.p, l.Ad.p, PART_DAD);
-                enqueue_finish_delta(l.part_of(PART_DAD), l.sc.p, l.host_delta.dev, 0, st);
+                cg.residual(l, r.Kv, l.d.p, l.Ad.p, PART_DAD);
+                cg.finish_delta(l, PART_DAD, l.host_delta.dev, false);
                 hipLaunchKernelGGL(k_absmax<double>, gr, br, 0, st, l.Ad.p, n, l.part_of(PART_D));
             }
             wait();
@@ -170,7 +152,7 @@ struct Refiner {
             for (size_t c : due) {
                 Rhs &r = rhs[c];
                 const Lane &l = *r.lane;
-                const double rr_try = delta_of(l);
+                const double rr_try = l.delta_on_host();
                 ++r.outer;
                 r.f64_ms += ms;
                 if (std::isfinite(rr_try) && std::sqrt(rr_try) <= REFINE_ACCEPT_RATIO * std::sqrt(r.rr)) {
@@ -192,31 +174,24 @@ struct Refiner {
     void take_over(Rhs &r) {
         const double t0 = now_ms();
         const Lane &l = *r.lane;
-        const dim3 gr(RED_BLOCKS), br(RED_THREADS);
         const std::vector<size_t> me{ static_cast<size_t>(&r - rhs.data()) };
-        enqueue_finish_delta(l.part_of(PART_RR), l.sc.p, l.host_delta.dev, 0, st);
-        hipLaunchKernelGGL(k_update_d<double>, gr, br, 0, st, l.d.p, l.r.p, p.q_.p, l.sc.p, n, 1, l.part_of(PART_D), PackDc<double>{});
+        cg.finish_delta(l, PART_RR, l.host_delta.dev, false);
+        cg.update_d(l, true);
         const uint64_t budget = r.budget_left(max_iter);
         for (uint64_t it = 0; it < budget; ++it) {
             const bool refresh = it % 50 == 49;
             apply_K(me, [](const Lane &ln) { return ln.d.p; });
-            if (p.weighted_) {
-                hipLaunchKernelGGL((k_Ad_and_dAd<double, true>), gr, br, 0, st, r.Kv, l.d.p, p.q_.p, l.part_of(PART_D), l.sc.p, n, p.inv_cw_.p, p.QA_cost_, l.Ad.p, l.part_of(PART_DAD));
-            } else {
-                hipLaunchKernelGGL(k_Ad_and_dAd<double>, gr, br, 0, st, r.Kv, l.d.p, p.q_.p, l.part_of(PART_D), l.sc.p, n, p.inv_cost_, p.QA_cost_, l.Ad.p, l.part_of(PART_DAD));
-            }
-            hipLaunchKernelGGL(k_update_x_r<double>, gr, br, 0, st, l.x.p, l.r.p, l.d.p, l.Ad.p, l.part_of(PART_DAD), l.sc.p, n, refresh ? 0 : 1, l.part_of(PART_RR));
+            cg.advance(l, r.Kv, refresh);
             if (refresh) {
-                p.enqueue_sum_and_qdot(l.x.p, l.part_of(PART_SUMS), l.sc.p, SC_SUMX, SC_QX);
                 apply_K(me, [](const Lane &ln) { return ln.x.p; });
-                residual(r, l.x.p, l.r.p, PART_RR);
+                cg.residual(l, r.Kv, l.x.p, l.r.p, PART_RR);
             }
-            enqueue_finish_delta(l.part_of(PART_RR), l.sc.p, l.host_delta.dev, 0, st);
+            cg.finish_delta(l, PART_RR, l.host_delta.dev, false);
             wait();
-            r.rr = delta_of(l);
+            r.rr = l.delta_on_host();
             ++r.f64_it;
             if (r.rr <= r.target) break;  // csvm.cpp:155-158: tested BEFORE the direction update
-            hipLaunchKernelGGL(k_update_d<double>, gr, br, 0, st, l.d.p, l.r.p, p.q_.p, l.sc.p, n, 0, l.part_of(PART_D), PackDc<double>{});
+            cg.update_d(l, false);
         }
         r.f64_ms += now_ms() - t0;
     }
@@ -224,29 +199,11 @@ struct Refiner {
     /* step 5: cg_finish on the lane's x */
     void finish(size_t c, double *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, lssvm_refine_info *refine_out, const lssvm_cg_info &path64, const lssvm_cg_info &path32) {
         const Rhs &r = rhs[c];
-        const Lane &l = *r.lane;
-        const size_t N = p.N_;
-        p.enqueue_sum_and_qdot(l.x.p, l.part_of(PART_SUMS), l.sc.p, SC_SUMX, SC_QX);
-        LSSVM_HIP_CHECK(hipMemcpyAsync(l.host_sc.p, l.sc.p, SC_COUNT * sizeof(double), hipMemcpyDeviceToHost, st));
-        double *alpha = alphas_out + c * N;
-        LSSVM_HIP_CHECK(hipMemcpyAsync(alpha, l.x.p, static_cast<size_t>(n) * sizeof(double), hipMemcpyDeviceToHost, st));
-        LSSVM_HIP_CHECK(hipStreamSynchronize(st));
-        // bias = y_last + QA_cost * sum(x) - q^T x ; alpha_N = -sum(x) ; rho = -bias   (csvm.cpp:179-182)
-        alpha[n] = -l.host_sc.p[SC_SUMX];
-        rhos_out[c] = -(r.y_last + p.QA_cost_ * l.host_sc.p[SC_SUMX] - l.host_sc.p[SC_QX]);
+        cg.finish_now(*r.lane, r.y_last, alphas_out + c * cg.num_points(), rhos_out + c);
         const double total_ms = now_ms() - t_call;
-        const bool converged = r.rr <= r.target;
         if (infos_out != nullptr) {
             lssvm_cg_info info = path64;  // the fp64 problem's description; the Gram mode is the inner solve's
-            info.iterations = r.inner + r.f64_it;
-            info.max_iterations = max_iter;
-            info.residuum = r.rr;
-            info.initial_residuum = r.delta0;
-            info.target_residuum = r.target;
-            info.epsilon = eps;
-            info.total_ms = total_ms;
-            info.avg_iteration_ms = info.iterations > 0 ? total_ms / static_cast<double>(info.iterations) : 0.0;
-            info.converged = converged ? 1 : 0;
+            fill_cg_outcome(&info, r.inner + r.f64_it, max_iter, r.rr, r.delta0, r.target, eps, total_ms, r.rr <= r.target);
             info.setup_ms = path64.setup_ms + path32.setup_ms;
             info.matvec_launches = r.f64_passes + r.f32_passes;
             info.gram_mode = path32.gram_mode;
@@ -345,25 +302,19 @@ void solve_refined_f64(const Options &opt, const lssvm_params &params, const dou
     s64.fill_info(&path64);
     s32->fill_info(&path32);
     Refiner ref(s64, *s32, num_rhs, eps, max_iter, t_call);
-    ref.hold(true);
-    try {
-        std::vector<std::vector<size_t>> groups;
-        if (ref.lanes) {
-            groups.emplace_back();
-            for (size_t c = 0; c < num_rhs; ++c) groups[0].push_back(c);
-        } else {
-            for (size_t c = 0; c < num_rhs; ++c) groups.push_back({ c });
-        }
-        for (const auto &who : groups) {
-            ref.begin(who, Y);
-            ref.refine(who);
-            for (size_t c : who) ref.finish(c, alphas_out, rhos_out, infos_out, refine_out, path64, path32);
-        }
-    } catch (...) {
-        ref.hold(false);
-        throw;
+    const SetOnExit<bool> busy = s64.hold_busy();  // between begin and finish no other solve may begin on the fp64 problem, and its weights stay
+    std::vector<std::vector<size_t>> groups;
+    if (ref.lanes) {
+        groups.emplace_back();
+        for (size_t c = 0; c < num_rhs; ++c) groups[0].push_back(c);
+    } else {
+        for (size_t c = 0; c < num_rhs; ++c) groups.push_back({ c });
     }
-    ref.hold(false);
+    for (const auto &who : groups) {
+        ref.begin(who, Y);
+        ref.refine(who);
+        for (size_t c : who) ref.finish(c, alphas_out, rhos_out, infos_out, refine_out, path64, path32);
+    }
     if (passes_out != nullptr) {
         passes_out[0] = ref.passes[0];
         passes_out[1] = ref.passes[1];

@@ -13,6 +13,106 @@
 
 namespace lssvm {
 
+/* ------------------------------------------------------------------ CgSteps: the O(n) steps of the CG recipe ------------------------------------------------------------------ */
+/* launch(weighted, diag): `weighted` a std::bool_constant that names the instantiation, `diag` the argument that goes with it (kernels' DiagArg) */
+template <typename T>
+template <typename Launch>
+void CgSteps<T>::with_diag(Launch &&launch) const {
+    if (p_.weighted_) {
+        launch(std::true_type{}, static_cast<const double *>(p_.inv_cw_.p));
+    } else {
+        launch(std::false_type{}, p_.inv_cost_);
+    }
+    LSSVM_HIP_CHECK(hipGetLastError());
+}
+
+template <typename T>
+void CgSteps<T>::sum_and_qdot(const State &s, const T *v, int slot_sum, int slot_q) const {
+    hipLaunchKernelGGL(k_sum_and_qdot<T>, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, stream(), v, q(), n(), s.part_of(PART_SUMS));
+    finish_sums(s, slot_sum, slot_q);
+}
+template <typename T>
+void CgSteps<T>::finish_sums(const State &s, int slot_sum, int slot_q) const {
+    hipLaunchKernelGGL(k_finish2, dim3(1), dim3(RED_THREADS), 0, stream(), s.part_of(PART_SUMS), s.sc.p, slot_sum, slot_q);
+    LSSVM_HIP_CHECK(hipGetLastError());
+}
+
+template <typename T>
+void CgSteps<T>::begin(const State &s, const T *y_host) const {
+    LSSVM_HIP_CHECK(hipMemcpyAsync(s.y.p, y_host, num_points() * sizeof(T), hipMemcpyHostToDevice, stream()));
+    const dim3 gn((n() + 255) / 256), bn(256);
+    hipLaunchKernelGGL(k_make_b<T>, gn, bn, 0, stream(), s.y.p, n(), s.b.p);  // csvm.cpp:89-91
+    hipLaunchKernelGGL(k_fill<T>, gn, bn, 0, stream(), s.x.p, n(), T(1));     // csvm.cpp:95
+    sum_and_qdot(s, s.x.p, SC_SUMX, SC_QX);
+}
+
+template <typename T>
+void CgSteps<T>::begin_from_zero(const State &s, const double *r_dev, const double *absmax_part_dev) const {
+    hipLaunchKernelGGL((k_scale_down<double, T>), dim3(RED_BLOCKS), dim3(RED_THREADS), 0, stream(), r_dev, absmax_part_dev, n(), s.b.p, s.r.p, s.x.p, s.part_of(PART_RR));
+    LSSVM_HIP_CHECK(hipGetLastError());
+}
+
+template <typename T>
+void CgSteps<T>::residual(const State &s, const T *Kv, const T *x, T *r_out, PartSet part) const {
+    with_diag([&](auto weighted, auto diag) {
+        hipLaunchKernelGGL((k_residual<T, decltype(weighted)::value>), dim3(RED_BLOCKS), dim3(RED_THREADS), 0, stream(), Kv, x, q(), s.b.p, s.sc.p, n(), diag, p_.QA_cost_, r_out, s.part_of(part));
+    });
+}
+
+template <typename T>
+void CgSteps<T>::finish_delta(const State &s, PartSet part, double *host_delta, bool initial) const {
+    hipLaunchKernelGGL(k_finish_delta, dim3(1), dim3(RED_THREADS), 0, stream(), s.part_of(part), s.sc.p, host_delta, initial ? 1 : 0);
+    LSSVM_HIP_CHECK(hipGetLastError());
+}
+
+template <typename T>
+void CgSteps<T>::update_d(const State &s, bool initial, const PackDc<T> &pack) const {
+    hipLaunchKernelGGL(k_update_d<T>, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, stream(), s.d.p, s.r.p, q(), s.sc.p, n(), initial ? 1 : 0, s.part_of(PART_D), pack);
+    LSSVM_HIP_CHECK(hipGetLastError());
+}
+
+template <typename T>
+void CgSteps<T>::advance(const State &s, const T *Kv, bool refresh) const {
+    // (every kernel of the chain reduces its predecessor's partial sums for itself -- finish2_in_block -- so no single-block kernel stands between them)
+    with_diag([&](auto weighted, auto diag) {
+        hipLaunchKernelGGL((k_Ad_and_dAd<T, decltype(weighted)::value>), dim3(RED_BLOCKS), dim3(RED_THREADS), 0, stream(), Kv, s.d.p, q(), s.part_of(PART_D), s.sc.p, n(), diag, p_.QA_cost_, s.Ad.p,
+                           s.part_of(PART_DAD));
+    });
+    hipLaunchKernelGGL(k_update_x_r<T>, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, stream(), s.x.p, s.r.p, s.d.p, s.Ad.p, s.part_of(PART_DAD), s.sc.p, n(), refresh ? 0 : 1, s.part_of(PART_RR));
+    LSSVM_HIP_CHECK(hipGetLastError());
+    if (refresh) sum_and_qdot(s, s.x.p, SC_SUMX, SC_QX);
+}
+
+template <typename T>
+void CgSteps<T>::apply_ret(const State &s, const T *Kv, const T *v, double add) const {
+    with_diag([&](auto weighted, auto diag) {
+        hipLaunchKernelGGL((k_apply_ret<T, decltype(weighted)::value>), dim3((n() + 255) / 256), dim3(256), 0, stream(), Kv, v, q(), s.sc.p, n(), diag, p_.QA_cost_, add, s.Ad.p);
+    });
+}
+
+template <typename T>
+void CgSteps<T>::enqueue_finish(const State &s, T *alpha_out) const {
+    sum_and_qdot(s, s.x.p, SC_SUMX, SC_QX);
+    LSSVM_HIP_CHECK(hipMemcpyAsync(s.host_sc.p, s.sc.p, SC_COUNT * sizeof(double), hipMemcpyDeviceToHost, stream()));
+    if (alpha_out != nullptr) LSSVM_HIP_CHECK(hipMemcpyAsync(alpha_out, s.x.p, static_cast<size_t>(n()) * sizeof(T), hipMemcpyDeviceToHost, stream()));
+}
+template <typename T>
+void CgSteps<T>::read_solution(const State &s, double y_last, T *alpha_out, double *rho_out) const {
+    const T sum_x = static_cast<T>(s.host_sc.p[SC_SUMX]);
+    const T bias = static_cast<T>(y_last + p_.QA_cost_ * s.host_sc.p[SC_SUMX] - s.host_sc.p[SC_QX]);
+    alpha_out[n()] = -sum_x;
+    *rho_out = static_cast<double>(-bias);
+}
+template <typename T>
+void CgSteps<T>::finish_now(const State &s, double y_last, T *alpha_out, double *rho_out) const {
+    enqueue_finish(s, alpha_out);
+    LSSVM_HIP_CHECK(hipStreamSynchronize(stream()));
+    read_solution(s, y_last, alpha_out, rho_out);
+}
+
+template class CgSteps<float>;
+template class CgSteps<double>;
+
 /* ------------------------------------------------------------------ Solver: CG over the shards of this process ------------------------------------------------------------------ */
 template <typename T>
 Solver<T>::Solver(const Options &opt, const lssvm_params &params, const void *X, int mem_kind, size_t num_points, size_t num_features, const std::vector<int> &devices, const lssvm_shard *shard) :
@@ -165,24 +265,19 @@ void Solver<T>::matvec(const void *d, void *ret_inout, double add) {
     const size_t bytes = static_cast<size_t>(shards_[0]->n_) * sizeof(T);
     for (auto &p : shards_) {
         p->activate();
-        // tmp_ <- d (zero padded), Ad_ <- ret
+        // tmp_ <- d (zero padded), Ad <- ret
         LSSVM_HIP_CHECK(hipMemcpyAsync(p->tmp_.p, d, bytes, hipMemcpyHostToDevice, p->stream()));
-        LSSVM_HIP_CHECK(hipMemcpyAsync(p->Ad_.p, ret_inout, bytes, hipMemcpyHostToDevice, p->stream()));
-        p->enqueue_sum_and_qdot(p->tmp_.p, SC_S, SC_QD);
+        LSSVM_HIP_CHECK(hipMemcpyAsync(p->own_.Ad.p, ret_inout, bytes, hipMemcpyHostToDevice, p->stream()));
+        CgSteps<T>(*p).sum_and_qdot(p->own_, p->tmp_.p, SC_S, SC_QD);
     }
     apply_K(Vec::tmp);
     for (auto &p : shards_) {
         p->activate();
-        if (p->weighted_) {
-            hipLaunchKernelGGL((k_apply_ret<T, true>), dim3((p->n_ + 255) / 256), dim3(256), 0, p->stream(), p->Kres_, p->tmp_.p, p->q_.p, p->sc_.p, p->n_, p->inv_cw_.p, p->QA_cost_, add, p->Ad_.p);
-        } else {
-            hipLaunchKernelGGL(k_apply_ret<T>, dim3((p->n_ + 255) / 256), dim3(256), 0, p->stream(), p->Kres_, p->tmp_.p, p->q_.p, p->sc_.p, p->n_, p->inv_cost_, p->QA_cost_, add, p->Ad_.p);
-        }
-        LSSVM_HIP_CHECK(hipGetLastError());
+        CgSteps<T>(*p).apply_ret(p->own_, p->Kres_, p->tmp_.p, add);
     }
     Problem<T> &p0 = *shards_[0];
     p0.activate();
-    LSSVM_HIP_CHECK(hipMemcpyAsync(ret_inout, p0.Ad_.p, bytes, hipMemcpyDeviceToHost, p0.stream()));
+    LSSVM_HIP_CHECK(hipMemcpyAsync(ret_inout, p0.own_.Ad.p, bytes, hipMemcpyDeviceToHost, p0.stream()));
     sync_all();
 }
 
@@ -254,49 +349,27 @@ int Solver<T>::rebalance(const double *weights, int count) {
 }
 
 template <typename T>
-void Solver<T>::cg_begin(const void *y, double eps) {
-    LSSVM_REQUIRE(y != nullptr, "The right hand side vector must not be empty!");
-    LSSVM_REQUIRE(static_cast<T>(eps) > T(0), "The stopping criterion in the CG algorithm must be greater than 0.0, but is " + std::to_string(eps) + "!");  // csvm.cpp:77
-    const double t0 = now_ms();
+void Solver<T>::reset_cg(double eps, double y_last) {
     eps_ = eps;
+    y_last_ = y_last;
     info_shard_ = -1;
     iter_ = 0;
     converged_ = false;
     cg_wall_ms_ = 0.0;
-    const size_t N = shards_[0]->N_;
-    y_last_ = static_cast<double>(static_cast<const T *>(y)[N - 1]);
     for (auto &p : shards_) {
-        p->activate();
         p->matvec_ms_ = p->pace_ms0_ = 0.0;
         p->matvec_launches_ = 0;
         p->matvec_timed_ = p->pace_timed0_ = 0;
-        hipStream_t st = p->stream();
-        LSSVM_HIP_CHECK(hipMemcpyAsync(p->ylast_.p, y, N * sizeof(T), hipMemcpyHostToDevice, st));
-        const dim3 gn((p->n_ + 255) / 256), bn(256);
-        hipLaunchKernelGGL(k_make_b<T>, gn, bn, 0, st, p->ylast_.p, p->n_, p->b_.p);        // csvm.cpp:89-91
-        hipLaunchKernelGGL(k_fill<T>, gn, bn, 0, st, p->x_.p, p->n_, T(1));                // csvm.cpp:95
-        p->enqueue_sum_and_qdot(p->x_.p, SC_SUMX, SC_QX);
     }
-    // r = b - A x   (csvm.cpp:101-104)
-    apply_K(Vec::x);
-    for (auto &p : shards_) {
-        p->activate();
-        hipStream_t st = p->stream();
-        if (p->weighted_) {
-            hipLaunchKernelGGL((k_residual<T, true>), dim3(RED_BLOCKS), dim3(RED_THREADS), 0, st, p->Kres_, p->x_.p, p->q_.p, p->b_.p, p->sc_.p, p->n_, p->inv_cw_.p, p->QA_cost_, p->r_.p, p->part(PART_RR));
-        } else {
-            hipLaunchKernelGGL(k_residual<T>, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, st, p->Kres_, p->x_.p, p->q_.p, p->b_.p, p->sc_.p, p->n_, p->inv_cost_, p->QA_cost_, p->r_.p, p->part(PART_RR));
-        }
-        hipLaunchKernelGGL(k_finish_delta, dim3(1), dim3(RED_THREADS), 0, st, p->part(PART_RR), p->sc_.p, p->sc_.p + SC_COUNT - 1, 1);  // csvm.cpp:107-108
-        // d = r   (csvm.cpp:111), and -- as partial sums that k_Ad_and_dAd finishes for itself -- the sums the next matvec's rank-1 terms need
-        hipLaunchKernelGGL(k_update_d<T>, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, st, p->d_.p, p->r_.p, p->q_.p, p->sc_.p, p->n_, 1, p->part(PART_D), pack_with_direction(*p));
-        LSSVM_HIP_CHECK(hipGetLastError());
-    }
+}
+
+template <typename T>
+void Solver<T>::read_delta0(double t0) {
     Problem<T> &p0 = *shards_[0];
     p0.activate();
-    LSSVM_HIP_CHECK(hipMemcpyAsync(p0.host_sc_.p, p0.sc_.p, SC_COUNT * sizeof(double), hipMemcpyDeviceToHost, p0.stream()));
+    LSSVM_HIP_CHECK(hipMemcpyAsync(p0.own_.host_sc.p, p0.own_.sc.p, SC_COUNT * sizeof(double), hipMemcpyDeviceToHost, p0.stream()));
     sync_all();
-    delta0_ = static_cast<double>(static_cast<T>(p0.host_sc_.p[SC_DELTA0]));
+    delta0_ = static_cast<double>(static_cast<T>(p0.own_.host_sc.p[SC_DELTA0]));
     delta_ = delta0_;
     delta_before_ = 0.0;
     held_back_ = 0;
@@ -305,9 +378,26 @@ void Solver<T>::cg_begin(const void *y, double eps) {
     cg_wall_ms_ += now_ms() - t0;
 }
 
-void enqueue_finish_delta(const double *part, double *sc, double *host_delta, int is_initial, hipStream_t s) {
-    hipLaunchKernelGGL(k_finish_delta, dim3(1), dim3(RED_THREADS), 0, s, part, sc, host_delta, is_initial);
-    LSSVM_HIP_CHECK(hipGetLastError());
+template <typename T>
+void Solver<T>::cg_begin(const void *y, double eps) {
+    LSSVM_REQUIRE(y != nullptr, "The right hand side vector must not be empty!");
+    LSSVM_REQUIRE(static_cast<T>(eps) > T(0), "The stopping criterion in the CG algorithm must be greater than 0.0, but is " + std::to_string(eps) + "!");  // csvm.cpp:77
+    const double t0 = now_ms();
+    reset_cg(eps, static_cast<double>(static_cast<const T *>(y)[shards_[0]->N_ - 1]));
+    for (auto &p : shards_) {
+        p->activate();
+        CgSteps<T>(*p).begin(p->own_, static_cast<const T *>(y));
+    }
+    // r = b - A x   (csvm.cpp:101-104)
+    apply_K(Vec::x);
+    for (auto &p : shards_) {
+        p->activate();
+        const CgSteps<T> cg(*p);
+        cg.residual(p->own_, p->Kres_, p->own_.x.p, p->own_.r.p, PART_RR);
+        cg.finish_delta(p->own_, PART_RR, p->own_.sc.p + SC_COUNT - 1, true);  // (delta0 is read with the scalars: read_delta0)
+        cg.update_d(p->own_, true, pack_with_direction(*p));
+    }
+    read_delta0(t0);
 }
 
 /* The inner solve of the mixed-precision refinement begins: cg_begin's statements for b = r / max|r| and x = 0, where r = b - A x is b itself -- no Gram pass. */
@@ -317,31 +407,14 @@ void Solver<T>::cg_begin_from_zero(const double *r_dev, const double *absmax_par
     LSSVM_REQUIRE(static_cast<T>(eps) > T(0), "The stopping criterion in the CG algorithm must be greater than 0.0, but is " + std::to_string(eps) + "!");  // csvm.cpp:77
     LSSVM_REQUIRE(shards_.size() == 1 && world_ == 1, "the inner solve of the refinement runs on one device");
     const double t0 = now_ms();
-    eps_ = eps;
-    info_shard_ = -1;
-    iter_ = 0;
-    converged_ = false;
-    cg_wall_ms_ = 0.0;
-    y_last_ = 0.0;
+    reset_cg(eps, 0.0);
     Problem<T> &p = *shards_[0];
     p.activate();
-    p.matvec_ms_ = p.pace_ms0_ = 0.0;
-    p.matvec_launches_ = 0;
-    p.matvec_timed_ = p.pace_timed0_ = 0;
-    hipStream_t st = p.stream();
-    hipLaunchKernelGGL((k_scale_down<double, T>), dim3(RED_BLOCKS), dim3(RED_THREADS), 0, st, r_dev, absmax_part_dev, p.n_, p.b_.p, p.r_.p, p.x_.p, p.part(PART_RR));
-    hipLaunchKernelGGL(k_finish_delta, dim3(1), dim3(RED_THREADS), 0, st, p.part(PART_RR), p.sc_.p, p.sc_.p + SC_COUNT - 1, 1);
-    hipLaunchKernelGGL(k_update_d<T>, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, st, p.d_.p, p.r_.p, p.q_.p, p.sc_.p, p.n_, 1, p.part(PART_D), pack_with_direction(p));  // d = r
-    LSSVM_HIP_CHECK(hipGetLastError());
-    LSSVM_HIP_CHECK(hipMemcpyAsync(p.host_sc_.p, p.sc_.p, SC_COUNT * sizeof(double), hipMemcpyDeviceToHost, st));
-    sync_all();
-    delta0_ = static_cast<double>(static_cast<T>(p.host_sc_.p[SC_DELTA0]));
-    delta_ = delta0_;
-    delta_before_ = 0.0;
-    held_back_ = 0;
-    begun_ = true;
-    in_cg_ = true;
-    cg_wall_ms_ += now_ms() - t0;
+    const CgSteps<T> cg(p);
+    cg.begin_from_zero(p.own_, r_dev, absmax_part_dev);
+    cg.finish_delta(p.own_, PART_RR, p.own_.sc.p + SC_COUNT - 1, true);
+    cg.update_d(p.own_, true, pack_with_direction(p));
+    read_delta0(t0);
 }
 
 template <typename T>
@@ -354,9 +427,7 @@ void Solver<T>::cg_step(uint64_t iterations, int *done_out) {
     const auto enqueue_direction_update = [&] {  // d = beta d + r   (csvm.cpp:161-163), and the sums the next matvec needs
         for (auto &p : shards_) {
             p->activate();
-            hipStream_t st = p->stream();
-            hipLaunchKernelGGL(k_update_d<T>, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, st, p->d_.p, p->r_.p, p->q_.p, p->sc_.p, p->n_, 0, p->part(PART_D), pack_with_direction(*p));
-            LSSVM_HIP_CHECK(hipGetLastError());
+            CgSteps<T>(*p).update_d(p->own_, false, pack_with_direction(*p));
         }
     };
     bool matvec_enqueued = false;  // A d of the coming iteration is in the queue already (enqueued ahead of the previous stop test)
@@ -367,36 +438,20 @@ void Solver<T>::cg_step(uint64_t iterations, int *done_out) {
         const bool refresh = iter_ % 50 == 49;
         for (auto &p : shards_) {
             p->activate();
-            hipStream_t st = p->stream();
-            // (every kernel of the chain reduces its predecessor's partial sums for itself -- finish2_in_block -- so no single-block kernel stands between them)
-            if (p->weighted_) {
-                hipLaunchKernelGGL((k_Ad_and_dAd<T, true>), dim3(RED_BLOCKS), dim3(RED_THREADS), 0, st, p->Kres_, p->d_.p, p->q_.p, p->part(PART_D), p->sc_.p, p->n_, p->inv_cw_.p, p->QA_cost_, p->Ad_.p, p->part(PART_DAD));
-            } else {
-                hipLaunchKernelGGL(k_Ad_and_dAd<T>, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, st, p->Kres_, p->d_.p, p->q_.p, p->part(PART_D), p->sc_.p, p->n_, p->inv_cost_, p->QA_cost_, p->Ad_.p, p->part(PART_DAD));
-            }
-            // alpha = delta / d.Ad (csvm.cpp:135) ; x += alpha d ; r -= alpha Ad   (csvm.cpp:138, :148) -- or, every 50th iteration, x only and r = b - A x below (csvm.cpp:140-145)
-            hipLaunchKernelGGL(k_update_x_r<T>, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, st, p->x_.p, p->r_.p, p->d_.p, p->Ad_.p, p->part(PART_DAD), p->sc_.p, p->n_, refresh ? 0 : 1, p->part(PART_RR));
-            if (refresh) p->enqueue_sum_and_qdot(p->x_.p, SC_SUMX, SC_QX);
-            LSSVM_HIP_CHECK(hipGetLastError());
+            CgSteps<T>(*p).advance(p->own_, p->Kres_, refresh);
         }
-        if (refresh) {
+        if (refresh) {  // r = b - A x   (csvm.cpp:140-145)
             apply_K(Vec::x);
             for (auto &p : shards_) {
                 p->activate();
-                if (p->weighted_) {
-                    hipLaunchKernelGGL((k_residual<T, true>), dim3(RED_BLOCKS), dim3(RED_THREADS), 0, p->stream(), p->Kres_, p->x_.p, p->q_.p, p->b_.p, p->sc_.p, p->n_, p->inv_cw_.p, p->QA_cost_, p->r_.p,
-                                       p->part(PART_RR));
-                } else {
-                    hipLaunchKernelGGL(k_residual<T>, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, p->stream(), p->Kres_, p->x_.p, p->q_.p, p->b_.p, p->sc_.p, p->n_, p->inv_cost_, p->QA_cost_, p->r_.p, p->part(PART_RR));
-                }
+                CgSteps<T>(*p).residual(p->own_, p->Kres_, p->own_.x.p, p->own_.r.p, PART_RR);
             }
         }
         for (auto &p : shards_) {
             p->activate();
             // the stop test needs delta on the host: shard 0's kernel stores its 8 bytes straight into mapped host memory (all shards hold the same
             // bits); the others publish into a spare device word
-            hipLaunchKernelGGL(k_finish_delta, dim3(1), dim3(RED_THREADS), 0, p->stream(), p->part(PART_RR), p->sc_.p, p.get() == &p0 ? p0.host_delta_.dev : p->sc_.p + SC_COUNT - 1, 0);  // csvm.cpp:152-153
-            LSSVM_HIP_CHECK(hipGetLastError());
+            CgSteps<T>(*p).finish_delta(p->own_, PART_RR, p.get() == &p0 ? p0.own_.host_delta.dev : p->own_.sc.p + SC_COUNT - 1, false);  // csvm.cpp:152-153
         }
         p0.activate();
         LSSVM_HIP_CHECK(hipEventRecord(ev_delta_.e, p0.stream()));
@@ -433,7 +488,7 @@ void Solver<T>::cg_step(uint64_t iterations, int *done_out) {
         for (auto &p : shards_) p->drain_events();
         ++iter_;
         delta_before_ = delta_;
-        delta_ = static_cast<double>(static_cast<T>(*static_cast<volatile double *>(p0.host_delta_.p)));
+        delta_ = static_cast<double>(static_cast<T>(p0.own_.delta_on_host()));
         if (static_cast<T>(delta_) <= target) {  // csvm.cpp:155-158: tested BEFORE the direction update
             converged_ = true;
             if (ahead) sync_all();  // let the discarded work drain
@@ -455,33 +510,26 @@ void Solver<T>::cg_finish(void *alpha_out, double *rho_out, lssvm_cg_info *info)
     LSSVM_REQUIRE(alpha_out != nullptr && rho_out != nullptr, "alpha_out / rho_out must not be NULL");
     in_cg_ = false;
     const double t0 = now_ms();
-    // bias = y_last + QA_cost * sum(x) - q^T x ; alpha_N = -sum(x) ; rho = -bias   (csvm.cpp:179-182)
+    Problem<T> &p0 = *shards_[0];
     const bool check = shards_.size() > 1 && exchange_ != Exchange::none;
     for (auto &p : shards_) {
-        if (p.get() != shards_[0].get() && !check) continue;
+        if (p.get() != &p0 && !check) continue;
         p->activate();
-        p->enqueue_sum_and_qdot(p->x_.p, SC_SUMX, SC_QX);
-        LSSVM_HIP_CHECK(hipMemcpyAsync(p->host_sc_.p, p->sc_.p, SC_COUNT * sizeof(double), hipMemcpyDeviceToHost, p->stream()));
+        CgSteps<T>(*p).enqueue_finish(p->own_, p.get() == &p0 ? static_cast<T *>(alpha_out) : nullptr);
     }
-    Problem<T> &p0 = *shards_[0];
-    p0.activate();
-    LSSVM_HIP_CHECK(hipMemcpyAsync(alpha_out, p0.x_.p, static_cast<size_t>(p0.n_) * sizeof(T), hipMemcpyDeviceToHost, p0.stream()));
     sync_all();
     if (check) {
         // every shard ran the same O(n) kernels on the same exchanged vectors: their scalars must agree to the bit
         for (auto &p : shards_) {
             for (int slot : { static_cast<int>(SC_DELTA), static_cast<int>(SC_SUMX), static_cast<int>(SC_QX) }) {
-                if (std::memcmp(&p->host_sc_.p[slot], &p0.host_sc_.p[slot], sizeof(double)) != 0) {
+                if (std::memcmp(&p->own_.host_sc.p[slot], &p0.own_.host_sc.p[slot], sizeof(double)) != 0) {
                     throw Error(LSSVM_ERR_INTERNAL, "the shards of the solve diverged: device " + std::to_string(p->device_) + " holds another CG scalar than device "
                                                         + std::to_string(p0.device_));
                 }
             }
         }
     }
-    const T sum_x = static_cast<T>(p0.host_sc_.p[SC_SUMX]);
-    const T bias = static_cast<T>(y_last_ + p0.QA_cost_ * p0.host_sc_.p[SC_SUMX] - p0.host_sc_.p[SC_QX]);
-    static_cast<T *>(alpha_out)[p0.n_] = -sum_x;
-    *rho_out = static_cast<double>(-bias);
+    CgSteps<T>(p0).read_solution(p0.own_, y_last_, static_cast<T *>(alpha_out), rho_out);
     cg_wall_ms_ += now_ms() - t0;
     if (info != nullptr) fill_info(info);
 }
@@ -490,6 +538,13 @@ void Solver<T>::cg_finish(void *alpha_out, double *rho_out, lssvm_cg_info *info)
 template <typename T>
 bool Solver<T>::lanes_apply() const {
     return shards_.size() == 1 && world_ == 1 && exchange_ == Exchange::none && shards_[0]->pair_kernel_applies();
+}
+
+template <typename T>
+void Solver<T>::wait_for_deltas() {
+    LSSVM_HIP_CHECK(hipGetLastError());
+    LSSVM_HIP_CHECK(hipEventRecord(ev_delta_.e, shards_[0]->stream()));
+    LSSVM_HIP_CHECK(hipEventSynchronize(ev_delta_.e));
 }
 
 template <typename T>
@@ -505,26 +560,20 @@ void Solver<T>::matvec_pair(const void *d0, const void *d1, void *ret0_inout, vo
     }
     // the statements of matvec() per vector on two lanes (d <- d_u zero padded, Ad <- ret_u), around ONE pass of the two-vector kernel
     Problem<T> &p = *shards_[0];
-    typename Problem<T>::Lane *lane[2] = { &p.lane(0), &p.lane(1) };
+    const CgSteps<T> cg(p);
+    const CgState<T> *lane[2] = { &p.lane(0), &p.lane(1) };
     const void *d[2] = { d0, d1 };
     void *ret[2] = { ret0_inout, ret1_inout };
     const size_t bytes = static_cast<size_t>(p.n_) * sizeof(T);
-    hipStream_t st = p.stream();
     for (int u = 0; u < 2; ++u) {
-        LSSVM_HIP_CHECK(hipMemcpyAsync(lane[u]->d.p, d[u], bytes, hipMemcpyHostToDevice, st));
-        LSSVM_HIP_CHECK(hipMemcpyAsync(lane[u]->Ad.p, ret[u], bytes, hipMemcpyHostToDevice, st));
-        p.enqueue_sum_and_qdot(lane[u]->d.p, lane[u]->part_of(PART_SUMS), lane[u]->sc.p, SC_S, SC_QD);
+        LSSVM_HIP_CHECK(hipMemcpyAsync(lane[u]->d.p, d[u], bytes, hipMemcpyHostToDevice, p.stream()));
+        LSSVM_HIP_CHECK(hipMemcpyAsync(lane[u]->Ad.p, ret[u], bytes, hipMemcpyHostToDevice, p.stream()));
+        cg.sum_and_qdot(*lane[u], lane[u]->d.p, SC_S, SC_QD);
     }
     p.enqueue_apply_K_lanes(lane[0]->d.p, lane[0]->Kv.p, lane[1]->d.p, lane[1]->Kv.p, nullptr, nullptr);
     for (int u = 0; u < 2; ++u) {
-        const typename Problem<T>::Lane &l = *lane[u];
-        if (p.weighted_) {
-            hipLaunchKernelGGL((k_apply_ret<T, true>), dim3((p.n_ + 255) / 256), dim3(256), 0, st, l.Kv.p, l.d.p, p.q_.p, l.sc.p, p.n_, p.inv_cw_.p, p.QA_cost_, add, l.Ad.p);
-        } else {
-            hipLaunchKernelGGL(k_apply_ret<T>, dim3((p.n_ + 255) / 256), dim3(256), 0, st, l.Kv.p, l.d.p, p.q_.p, l.sc.p, p.n_, p.inv_cost_, p.QA_cost_, add, l.Ad.p);
-        }
-        LSSVM_HIP_CHECK(hipGetLastError());
-        LSSVM_HIP_CHECK(hipMemcpyAsync(ret[u], l.Ad.p, bytes, hipMemcpyDeviceToHost, st));
+        cg.apply_ret(*lane[u], lane[u]->Kv.p, lane[u]->d.p, add);
+        LSSVM_HIP_CHECK(hipMemcpyAsync(ret[u], lane[u]->Ad.p, bytes, hipMemcpyDeviceToHost, p.stream()));
     }
     sync_all();
     if (two_vector_out != nullptr) *two_vector_out = 1;
@@ -552,42 +601,33 @@ template <typename T>
 void Solver<T>::solve_in_sequence(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out) {
     const double t_call = now_ms();
     const size_t N = shards_[0]->N_;
-    const int64_t ahead = opt_.enqueue_ahead_below_us;
+    const SetOnExit<int64_t> restore(opt_.enqueue_ahead_below_us, opt_.enqueue_ahead_below_us);
+    const SetOnExit<bool> release(in_cg_, false);  // (a solve that threw between cg_begin and cg_finish does not keep the handle)
     opt_.enqueue_ahead_below_us = 0;
-    try {
-        for (size_t c = 0; c < num_rhs; ++c) {
-            cg_begin(static_cast<const T *>(Y) + c * N, eps);
-            cg_step(max_iter, nullptr);
-            lssvm_cg_info info{};
-            cg_finish(static_cast<T *>(alphas_out) + c * N, rhos_out + c, &info);
-            info.max_iterations = max_iter;
-            info.total_ms = now_ms() - t_call;
-            if (passes_out != nullptr) passes_out[1] += info.matvec_launches;
-            if (infos_out != nullptr) infos_out[c] = info;
-        }
-    } catch (...) {
-        opt_.enqueue_ahead_below_us = ahead;
-        in_cg_ = false;
-        throw;
+    for (size_t c = 0; c < num_rhs; ++c) {
+        cg_begin(static_cast<const T *>(Y) + c * N, eps);
+        cg_step(max_iter, nullptr);
+        lssvm_cg_info info{};
+        cg_finish(static_cast<T *>(alphas_out) + c * N, rhos_out + c, &info);
+        info.max_iterations = max_iter;
+        info.total_ms = now_ms() - t_call;
+        if (passes_out != nullptr) passes_out[1] += info.matvec_launches;
+        if (infos_out != nullptr) infos_out[c] = info;
     }
-    opt_.enqueue_ahead_below_us = ahead;
 }
 
-/* The recipe of cg_begin / cg_step / cg_finish for every right-hand side, each on a lane of shard 0 with the O(n) kernels of the single solve on that lane's pointers --
- * so every recurrence has the bits of the one-shot solve -- all lanes advancing one iteration per step.  In every step the lanes still active are paired afresh for the
+/* The recipe of cg_begin / cg_step / cg_finish for every right-hand side, each on a lane of shard 0 with the steps of the single solve on that lane's state -- so every
+ * recurrence has the bits of the one-shot solve -- all lanes advancing one iteration per step.  In every step the lanes still active are paired afresh for the
  * implicit matvec: ceil(active / 2) Gram passes, an odd lane taking the single-vector pass.  The host waits for the step's deltas before it enqueues the next step. */
 template <typename T>
 void Solver<T>::solve_on_lanes(const T *Y, size_t num_rhs, double eps, uint64_t max_iter, T *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out) {
-    using Lane = typename Problem<T>::Lane;
     const double t_call = now_ms();
     Problem<T> &p = *shards_[0];
     p.activate();
-    hipStream_t st = p.stream();
+    const CgSteps<T> cg(p);
     const size_t N = p.N_;
-    const int n = p.n_;
-    const dim3 gn((n + 255) / 256), bn(256), gr(RED_BLOCKS), br(RED_THREADS);
     struct State {
-        Lane *lane = nullptr;
+        const CgState<T> *lane = nullptr;
         double y_last = 0.0, delta0 = 0.0, delta = 0.0;
         uint64_t matvecs = 0, timed = 0;
         double kernel_ms = 0.0;
@@ -637,117 +677,66 @@ void Solver<T>::solve_on_lanes(const T *Y, size_t num_rhs, double eps, uint64_t 
         }
         timers_used = 0;
     };
-    const auto enqueue_residual = [&](const Lane &l) {
-        if (p.weighted_) {
-            hipLaunchKernelGGL((k_residual<T, true>), gr, br, 0, st, l.Kv.p, l.x.p, p.q_.p, l.b.p, l.sc.p, n, p.inv_cw_.p, p.QA_cost_, l.r.p, l.part_of(PART_RR));
-        } else {
-            hipLaunchKernelGGL(k_residual<T>, gr, br, 0, st, l.Kv.p, l.x.p, p.q_.p, l.b.p, l.sc.p, n, p.inv_cost_, p.QA_cost_, l.r.p, l.part_of(PART_RR));
-        }
-    };
-    const auto wait_for_deltas = [&] {
-        LSSVM_HIP_CHECK(hipGetLastError());
-        LSSVM_HIP_CHECK(hipEventRecord(ev_delta_.e, st));
-        LSSVM_HIP_CHECK(hipEventSynchronize(ev_delta_.e));
-        read_timers();
-    };
 
-    in_cg_ = true;  // (the weights may not change, and no other solve may begin on this handle)
-    try {
-        // ---- cg_begin per lane: b = y - y_last, x = 1, r = b - A x, delta0, d = r ----
-        for (size_t c : active) {
-            State &s = state[c];
-            const Lane &l = *s.lane;
-            s.y_last = static_cast<double>(Y[c * N + N - 1]);
-            LSSVM_HIP_CHECK(hipMemcpyAsync(l.y.p, Y + c * N, N * sizeof(T), hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(k_make_b<T>, gn, bn, 0, st, l.y.p, n, l.b.p);
-            hipLaunchKernelGGL(k_fill<T>, gn, bn, 0, st, l.x.p, n, T(1));
-            p.enqueue_sum_and_qdot(l.x.p, l.part_of(PART_SUMS), l.sc.p, SC_SUMX, SC_QX);
-        }
-        apply_K(true);
-        for (size_t c : active) {
-            const Lane &l = *state[c].lane;
-            enqueue_residual(l);
-            hipLaunchKernelGGL(k_finish_delta, dim3(1), br, 0, st, l.part_of(PART_RR), l.sc.p, l.host_delta.dev, 1);
-            hipLaunchKernelGGL(k_update_d<T>, gr, br, 0, st, l.d.p, l.r.p, p.q_.p, l.sc.p, n, 1, l.part_of(PART_D), PackDc<T>{});  // (the records are packed per pass, for the pair of the step)
-        }
-        wait_for_deltas();
-        for (size_t c : active) {
-            State &s = state[c];
-            s.delta0 = s.delta = static_cast<double>(static_cast<T>(*static_cast<volatile double *>(s.lane->host_delta.p)));
-        }
-
-        // ---- cg_step: one iteration of every active lane per step ----
-        for (uint64_t iter = 0; !active.empty(); ++iter) {
-            const bool refresh = iter % 50 == 49;
-            apply_K(false);
-            for (size_t c : active) {
-                const Lane &l = *state[c].lane;
-                if (p.weighted_) {
-                    hipLaunchKernelGGL((k_Ad_and_dAd<T, true>), gr, br, 0, st, l.Kv.p, l.d.p, p.q_.p, l.part_of(PART_D), l.sc.p, n, p.inv_cw_.p, p.QA_cost_, l.Ad.p, l.part_of(PART_DAD));
-                } else {
-                    hipLaunchKernelGGL(k_Ad_and_dAd<T>, gr, br, 0, st, l.Kv.p, l.d.p, p.q_.p, l.part_of(PART_D), l.sc.p, n, p.inv_cost_, p.QA_cost_, l.Ad.p, l.part_of(PART_DAD));
-                }
-                hipLaunchKernelGGL(k_update_x_r<T>, gr, br, 0, st, l.x.p, l.r.p, l.d.p, l.Ad.p, l.part_of(PART_DAD), l.sc.p, n, refresh ? 0 : 1, l.part_of(PART_RR));
-                if (refresh) p.enqueue_sum_and_qdot(l.x.p, l.part_of(PART_SUMS), l.sc.p, SC_SUMX, SC_QX);
-            }
-            if (refresh) {
-                apply_K(true);
-                for (size_t c : active) enqueue_residual(*state[c].lane);
-            }
-            for (size_t c : active) {
-                const Lane &l = *state[c].lane;
-                hipLaunchKernelGGL(k_finish_delta, dim3(1), br, 0, st, l.part_of(PART_RR), l.sc.p, l.host_delta.dev, 0);
-            }
-            wait_for_deltas();
-            // the stop test in the real type, before the direction update (csvm.cpp:155-158); a lane that meets it, or has done max_iter iterations, leaves
-            std::vector<size_t> staying;
-            for (size_t c : active) {
-                State &s = state[c];
-                const Lane &l = *s.lane;
-                s.delta = static_cast<double>(static_cast<T>(*static_cast<volatile double *>(l.host_delta.p)));
-                const T target = static_cast<T>(eps) * static_cast<T>(eps) * static_cast<T>(s.delta0);
-                s.converged = static_cast<T>(s.delta) <= target;
-                if (!s.converged && iter + 1 < max_iter) {
-                    hipLaunchKernelGGL(k_update_d<T>, gr, br, 0, st, l.d.p, l.r.p, p.q_.p, l.sc.p, n, 0, l.part_of(PART_D), PackDc<T>{});
-                    staying.push_back(c);
-                    continue;
-                }
-                // cg_finish: bias = y_last + QA_cost * sum(x) - q^T x ; alpha_N = -sum(x) ; rho = -bias   (csvm.cpp:179-182)
-                p.enqueue_sum_and_qdot(l.x.p, l.part_of(PART_SUMS), l.sc.p, SC_SUMX, SC_QX);
-                LSSVM_HIP_CHECK(hipMemcpyAsync(l.host_sc.p, l.sc.p, SC_COUNT * sizeof(double), hipMemcpyDeviceToHost, st));
-                T *alpha = alphas_out + c * N;
-                LSSVM_HIP_CHECK(hipMemcpyAsync(alpha, l.x.p, static_cast<size_t>(n) * sizeof(T), hipMemcpyDeviceToHost, st));
-                LSSVM_HIP_CHECK(hipStreamSynchronize(st));
-                alpha[n] = -static_cast<T>(l.host_sc.p[SC_SUMX]);
-                rhos_out[c] = static_cast<double>(-static_cast<T>(s.y_last + p.QA_cost_ * l.host_sc.p[SC_SUMX] - l.host_sc.p[SC_QX]));
-                if (infos_out != nullptr) {
-                    // what cg_finish reports for a one-shot solve, with this lane's counters; total_ms: from the start of the call until the lane left
-                    lssvm_cg_info info{};
-                    info.iterations = iter + 1;
-                    info.max_iterations = max_iter;
-                    info.residuum = s.delta;
-                    info.initial_residuum = s.delta0;
-                    info.target_residuum = static_cast<double>(target);
-                    info.epsilon = eps;
-                    info.total_ms = now_ms() - t_call;
-                    info.avg_iteration_ms = info.total_ms / static_cast<double>(iter + 1);
-                    info.converged = s.converged ? 1 : 0;
-                    describe_path(&info);
-                    info.matvec_launches = s.matvecs;
-                    info.matvec_timed = s.timed;
-                    info.matvec_kernel_ms_total = s.kernel_ms;
-                    info.matvec_kernel_ms = s.timed > 0 ? s.kernel_ms / static_cast<double>(s.timed) : 0.0;
-                    infos_out[c] = info;
-                }
-            }
-            LSSVM_HIP_CHECK(hipGetLastError());
-            active.swap(staying);
-        }
-    } catch (...) {
-        in_cg_ = false;
-        throw;
+    const SetOnExit<bool> busy = hold_busy();  // (the weights may not change, and no other solve may begin on this handle)
+    // ---- cg_begin per lane: b = y - y_last, x = 1, r = b - A x, delta0, d = r ----
+    for (size_t c : active) {
+        state[c].y_last = static_cast<double>(Y[c * N + N - 1]);
+        cg.begin(*state[c].lane, Y + c * N);
     }
-    in_cg_ = false;
+    apply_K(true);
+    for (size_t c : active) {
+        const CgState<T> &l = *state[c].lane;
+        cg.residual(l, l.Kv.p, l.x.p, l.r.p, PART_RR);
+        cg.finish_delta(l, PART_RR, l.host_delta.dev, true);
+        cg.update_d(l, true);  // (the records are packed per pass, for the pair of the step)
+    }
+    wait_for_deltas();
+    read_timers();
+    for (size_t c : active) state[c].delta0 = state[c].delta = static_cast<double>(static_cast<T>(state[c].lane->delta_on_host()));
+
+    // ---- cg_step: one iteration of every active lane per step ----
+    for (uint64_t iter = 0; !active.empty(); ++iter) {
+        const bool refresh = iter % 50 == 49;
+        apply_K(false);
+        for (size_t c : active) cg.advance(*state[c].lane, state[c].lane->Kv.p, refresh);
+        if (refresh) {
+            apply_K(true);
+            for (size_t c : active) {
+                const CgState<T> &l = *state[c].lane;
+                cg.residual(l, l.Kv.p, l.x.p, l.r.p, PART_RR);
+            }
+        }
+        for (size_t c : active) cg.finish_delta(*state[c].lane, PART_RR, state[c].lane->host_delta.dev, false);
+        wait_for_deltas();
+        read_timers();
+        // the stop test in the real type, before the direction update (csvm.cpp:155-158); a lane that meets it, or has done max_iter iterations, leaves
+        std::vector<size_t> staying;
+        for (size_t c : active) {
+            State &s = state[c];
+            s.delta = static_cast<double>(static_cast<T>(s.lane->delta_on_host()));
+            const T target = static_cast<T>(eps) * static_cast<T>(eps) * static_cast<T>(s.delta0);
+            s.converged = static_cast<T>(s.delta) <= target;
+            if (!s.converged && iter + 1 < max_iter) {
+                cg.update_d(*s.lane, false);
+                staying.push_back(c);
+                continue;
+            }
+            cg.finish_now(*s.lane, s.y_last, alphas_out + c * N, rhos_out + c);
+            if (infos_out != nullptr) {
+                // what cg_finish reports for a one-shot solve, with this lane's counters; total_ms: from the start of the call until the lane left
+                lssvm_cg_info info{};
+                fill_cg_outcome(&info, iter + 1, max_iter, s.delta, s.delta0, static_cast<double>(target), eps, now_ms() - t_call, s.converged);
+                describe_path(&info);
+                info.matvec_launches = s.matvecs;
+                info.matvec_timed = s.timed;
+                info.matvec_kernel_ms_total = s.kernel_ms;
+                info.matvec_kernel_ms = s.timed > 0 ? s.kernel_ms / static_cast<double>(s.timed) : 0.0;
+                infos_out[c] = info;
+            }
+        }
+        active.swap(staying);
+    }
     if (passes_out != nullptr) {
         passes_out[0] = passes[0];
         passes_out[1] = passes[1];
@@ -762,15 +751,7 @@ void Solver<T>::synchronize() {
 template <typename T>
 void Solver<T>::fill_info(lssvm_cg_info *info) {
     std::memset(info, 0, sizeof(*info));
-    info->iterations = iter_;
-    info->max_iterations = 0;
-    info->residuum = delta_;
-    info->initial_residuum = delta0_;
-    info->target_residuum = static_cast<double>(static_cast<T>(eps_) * static_cast<T>(eps_) * static_cast<T>(delta0_));
-    info->epsilon = eps_;
-    info->avg_iteration_ms = iter_ > 0 ? cg_wall_ms_ / static_cast<double>(iter_) : 0.0;
-    info->total_ms = cg_wall_ms_;
-    info->converged = converged_ ? 1 : 0;
+    fill_cg_outcome(info, iter_, 0, delta_, delta0_, static_cast<double>(static_cast<T>(eps_) * static_cast<T>(eps_) * static_cast<T>(delta0_)), eps_, cg_wall_ms_, converged_);
     describe_path(info);
 }
 
