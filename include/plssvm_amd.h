@@ -276,6 +276,22 @@ int lssvm_mi355_predictor_create_multi(lssvm_mi355_predictor **out, const lssvm_
 int lssvm_mi355_predictor_predict_multi(lssvm_mi355_predictor *predictor, const void *predict_points, int mem_kind, size_t num_predict_points, void *out,
                                         lssvm_predict_info *info);
 
+/* The same handle, running against a resident form WHEREVER THE LIBRARY HAS ONE: the fp32 form of `create` / `create_multi` above and, in addition, an fp64 form for
+ * rbf / polynomial models (gamma > 0) of at most 256 padded features with tile_kernel != 1.  (`create` / `create_multi` keep their documented routing: an fp64 model
+ * of these kernels takes the one-shot path there.)  Arguments, their validation and the error texts are those of `create_multi`, refused before a device is touched;
+ * num_vectors == 1 gives the handle of one vector.  `predict`, `predict_multi` and `destroy` work on the handle as on any other.
+ * The fp64 form uploads the support vectors once and prepares them as lssvm_mi355_predict_values_f64 prepares them per call (rbf: centred by their column means and
+ * scaled, norms; polynomial: scaled by sqrt(gamma)), keeps the alpha matrix in HBM and packs the records of every launch group: a pair record for (0,1), (2,3), ...,
+ * the single-vector record for an odd last vector.  A batch is padded, centred (with the support vectors' means), scaled and chunked as the one-shot call does it and
+ * runs one launch of the full-square two-vector fp64 kernel per pair: the kernel value of an element is computed once, each vector's sums are the chains of a
+ * single-vector launch.  Every value has the bits of lssvm_mi355_predict_values_f64 for that (alphas[v], rhos[v]) with the same options.  fp64 rbf has no direct
+ * form and no plane check, so this form never declines a batch and keeps no host copy of the support vectors.  lssvm_predict_info.resident and .vectors_per_launch
+ * report as for fp32: 2 where a pair launch ran, 1 for a `predict_multi` call of one-vector launches, 0 from `predict`.  An fp32 model's handle is
+ * indistinguishable from a `create_multi` handle; outside both forms (fp64 beyond 256 features, tile_kernel = 1, fp32 beyond 128 features) the handle does what a
+ * `create_multi` handle does, resident == 0. */
+int lssvm_mi355_predictor_create_resident(lssvm_mi355_predictor **out, const lssvm_params *params, int dtype, const void *support_vectors, size_t num_support_vectors,
+                                          size_t num_features, const void *alphas, const double *rhos, size_t num_vectors, const lssvm_mi355_options *options);
+
 /* ------------------------------------------------------------------------------------------------------------------ */
 /* fine-grained entry points for kernel-level parity tests: the protected members the reference's backend tests re-export  */
 /* (tests/backends/HIP/mock_hip_csvm.hpp:22-44): generate_q, run_device_kernel, calculate_w                           */

@@ -258,9 +258,13 @@ class Predictor:
 
     A ONE-VS-ALL model: ``alpha`` of shape ``(k, num_support_vectors)`` with ``rho`` of shape ``(k,)`` (``lssvm_mi355_predictor_create_multi``).  :meth:`predict` then
     returns ``(num_points, k)`` and :meth:`predict_device` writes ``num_points`` x ``k`` values row-major, column ``v`` the bits of a predictor of ``(alpha[v], rho[v])``;
-    ``info_out["vectors_per_launch"]`` says whether one pass over the Gram tiles fed two weight vectors (2) or every vector had a launch of its own (1)."""
+    ``info_out["vectors_per_launch"]`` says whether one pass over the Gram tiles fed two weight vectors (2) or every vector had a launch of its own (1).
 
-    def __init__(self, params: Parameter, support_vectors, alpha, rho, options: Options | None = None):
+    ``every_form=True`` creates the model through ``lssvm_mi355_predictor_create_resident``, for a vector or a matrix of weights: every resident form the library has,
+    which adds the float64 one (rbf / polynomial, at most 256 features, two weight vectors per pass).  The default keeps the routing of ``_create`` / ``_create_multi``,
+    where a float64 rbf / polynomial model takes the one-shot path.  The values are the same bits either way."""
+
+    def __init__(self, params: Parameter, support_vectors, alpha, rho, options: Options | None = None, every_form: bool = False):
         sv = _as_matrix(support_vectors)
         alpha = np.ascontiguousarray(alpha, dtype=sv.dtype)
         self.dtype, self.num_features = sv.dtype, int(sv.shape[1])
@@ -275,14 +279,17 @@ class Predictor:
             if rhos.shape != (k,):
                 raise InvalidParameterError(f"The number of weight vectors ({k}) and the number of rho values ({rhos.size}) must be the same!")
             self.num_vectors = int(k)
-            ps = _params_struct(params, sv.shape[1])
-            check(_capi.predictor_multi_entry("lssvm_mi355_predictor_create_multi")(C.byref(self._h), C.byref(ps), _capi.dtype_code(sv.dtype), ptr(sv), sv.shape[0], sv.shape[1], ptr(alpha),
-                                                                                    rhos.ctypes.data_as(C.POINTER(C.c_double)), k, options_ptr(options)))
-            return
-        if alpha.size != sv.shape[0]:
-            raise InvalidParameterError(f"The number of support vectors ({sv.shape[0]}) and number of weights ({alpha.size}) must be the same!")
-        self.num_vectors = None  # (one weight vector: the values are a vector, not a matrix of one column)
+        else:
+            if alpha.size != sv.shape[0]:
+                raise InvalidParameterError(f"The number of support vectors ({sv.shape[0]}) and number of weights ({alpha.size}) must be the same!")
+            self.num_vectors = None  # (one weight vector: the values are a vector, not a matrix of one column)
+            k, rhos = 1, np.array([float(rho)], dtype=np.float64)  # (every_form: a handle of one vector, used through lssvm_mi355_predictor_predict like any other)
         ps = _params_struct(params, sv.shape[1])
+        if alpha.ndim == 2 or every_form:
+            create = "lssvm_mi355_predictor_create_resident" if every_form else "lssvm_mi355_predictor_create_multi"
+            check(_capi.predictor_multi_entry(create)(C.byref(self._h), C.byref(ps), _capi.dtype_code(sv.dtype), ptr(sv), sv.shape[0], sv.shape[1], ptr(alpha),
+                                                      rhos.ctypes.data_as(C.POINTER(C.c_double)), k, options_ptr(options)))
+            return
         check(lib.lssvm_mi355_predictor_create(C.byref(self._h), C.byref(ps), C.c_int(_capi.dtype_code(sv.dtype)), ptr(sv), C.c_size_t(sv.shape[0]), C.c_size_t(sv.shape[1]), ptr(alpha),
                                                C.c_double(float(rho)), options_ptr(options)))
 

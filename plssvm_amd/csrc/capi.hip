@@ -325,8 +325,9 @@ int lssvm_mi355_predictor_create(lssvm_mi355_predictor **out, const lssvm_params
         *out = h.release();
     });
 }
-int lssvm_mi355_predictor_create_multi(lssvm_mi355_predictor **out, const lssvm_params *params, int dtype, const void *support_vectors, size_t num_support_vectors,
-                                       size_t num_features, const void *alphas, const double *rhos, size_t num_vectors, const lssvm_mi355_options *options) {
+/* _create_multi and _create_resident: one validation, one set of error texts; `every_form`: every resident form the library has (the fp64 one as well) */
+static int create_predictor_of_vectors(lssvm_mi355_predictor **out, const lssvm_params *params, int dtype, const void *support_vectors, size_t num_support_vectors, size_t num_features,
+                                       const void *alphas, const double *rhos, size_t num_vectors, const lssvm_mi355_options *options, bool every_form) {
     return guarded([&] {
         LSSVM_REQUIRE(out != nullptr, "out must not be NULL");
         *out = nullptr;
@@ -336,9 +337,17 @@ int lssvm_mi355_predictor_create_multi(lssvm_mi355_predictor **out, const lssvm_
         LSSVM_REQUIRE(alphas != nullptr, "The number of support vectors and number of weights must be the same!");  // csvm.cpp:192
         LSSVM_REQUIRE(rhos != nullptr, "rhos must hold one value per weight vector");
         auto h = std::make_unique<lssvm_mi355_predictor>();
-        h->impl = lssvm::make_predictor(options_of(options), *params, dtype, support_vectors, num_support_vectors, num_features, alphas, rhos, num_vectors);
+        h->impl = lssvm::make_predictor(options_of(options), *params, dtype, support_vectors, num_support_vectors, num_features, alphas, rhos, num_vectors, every_form);
         *out = h.release();
     });
+}
+int lssvm_mi355_predictor_create_multi(lssvm_mi355_predictor **out, const lssvm_params *params, int dtype, const void *support_vectors, size_t num_support_vectors,
+                                       size_t num_features, const void *alphas, const double *rhos, size_t num_vectors, const lssvm_mi355_options *options) {
+    return create_predictor_of_vectors(out, params, dtype, support_vectors, num_support_vectors, num_features, alphas, rhos, num_vectors, options, false);
+}
+int lssvm_mi355_predictor_create_resident(lssvm_mi355_predictor **out, const lssvm_params *params, int dtype, const void *support_vectors, size_t num_support_vectors,
+                                          size_t num_features, const void *alphas, const double *rhos, size_t num_vectors, const lssvm_mi355_options *options) {
+    return create_predictor_of_vectors(out, params, dtype, support_vectors, num_support_vectors, num_features, alphas, rhos, num_vectors, options, true);
 }
 int lssvm_mi355_predictor_predict(lssvm_mi355_predictor *predictor, const void *predict_points, int mem_kind, size_t num_predict_points, void *out, lssvm_predict_info *info) {
     return guarded([&] {

@@ -404,11 +404,13 @@ template void calculate_w<double>(const double *, size_t, size_t, const double *
 
 /* ------------------------------------------------------------------ the resident predictor ------------------------------------------------------------------ */
 /* `nvec_` weight vectors over the same support vectors (lssvm_mi355_predictor_create: one; _create_multi: a one-vs-all model's k).  Everything that does not depend on
- * the weight vector is held once; per vector the alpha row, the packed column records of its launch group and, for the linear kernel, w. */
+ * the weight vector is held once; per vector the alpha row, the packed column records of its launch group and, for the linear kernel, w.
+ * `every_form` (lssvm_mi355_predictor_create_resident): fp64 rbf / polynomial models on at most 256 padded features are resident as well (prepare_resident_f64); without
+ * it an fp64 model of these kernels goes through the one-shot path, as _create / _create_multi document. */
 template <typename T>
 class Predictor final : public PredictorBase {
   public:
-    Predictor(const Options &opt, const lssvm_params &params, const T *sv, size_t nsv, size_t nfeat, const T *alpha, const double *rho, size_t nvec) :
+    Predictor(const Options &opt, const lssvm_params &params, const T *sv, size_t nsv, size_t nfeat, const T *alpha, const double *rho, size_t nvec, bool every_form) :
         opt_(opt), params_(params), nsv_(nsv), nfeat_(nfeat), nvec_(nvec) {
         dtype = std::is_same_v<T, float> ? LSSVM_DTYPE_F32 : LSSVM_DTYPE_F64;
         check_params(&params_);
@@ -432,7 +434,12 @@ class Predictor final : public PredictorBase {
             return;
         }
         alpha_host_.assign(alpha, alpha + nvec * nsv);
-        if constexpr (std::is_same_v<T, float>) prepare_resident(sv, s);
+        if constexpr (std::is_same_v<T, float>) {
+            prepare_resident(sv, s);
+        } else {
+            if (every_form) prepare_resident_f64(sv, s);
+            if (resident_) std::vector<T>().swap(alpha_host_);  // (the fp64 form never declines a batch: the one-shot path's inputs are not needed)
+        }
         // the one-shot path's input: a host copy where nothing is resident; a resident model keeps its support vectors as they came in HBM and fetches them if a batch ever asks
         if (!resident_) {
             sv_host_.assign(sv, sv + nsv * nfeat);
@@ -458,9 +465,11 @@ class Predictor final : public PredictorBase {
             done = true;
         } else if constexpr (std::is_same_v<T, float>) {
             if (resident_) done = predict_resident(points, mem_kind, npoints, out, local);
+        } else {
+            if (resident_) done = predict_resident_f64(points, mem_kind, npoints, out, local);
         }
         if (!done) {
-            // what the resident form does not cover (fp64, more than 128 features, exponent scales beyond the norm expansion, a batch whose planes fail the f16 check or
+            // what the resident form does not cover (fp64 outside lssvm_mi355_predictor_create_resident or beyond 256 features, fp32 on more than 128 features, exponent scales beyond the norm expansion, a batch whose planes fail the f16 check or
             // that lies further from the support vectors' centre than the form chosen for them allows): the one-shot path, same result
             int w_valid = 0;
             std::vector<T> w_tmp(nvec_ * nfeat_);
@@ -709,6 +718,114 @@ class Predictor final : public PredictorBase {
         return true;
     }
 
+    /* fp64, rbf / polynomial (gamma > 0) on the one-pass v2 kernel (at most 256 padded features, tile_kernel != 1): the support vectors' side of the product, once,
+     * prepared as predict_values_impl<double> prepares it -- the same padding, centre, scale and records, so that a batch's values have the one-shot call's bits.  fp64
+     * rbf has no direct form and no plane check: this form never declines a batch and keeps no host copy of the support vectors. */
+    void prepare_resident_f64(const double *sv, hipStream_t s) {
+        const bool rbf = params_.kernel_type == LSSVM_KERNEL_RBF;
+        if (!(rbf || params_.kernel_type == LSSVM_KERNEL_POLYNOMIAL) || !(params_.gamma > 0.0)) return;
+        if (!v2_eligible_f64(opt_, padded_features<double>(nfeat_))) return;
+        S64_.upload(sv, LSSVM_MEM_HOST, nsv_, nfeat_, 0, s);
+        const dim3 cgrid((S64_.dfeat + 255) / 256, S64_.rows);
+        if (rbf) {
+            scale64_ = rbf_prescale<double>(params_, true);
+            column_means<double>(S64_, mean64_, s);
+            hipLaunchKernelGGL(k_center<double>, cgrid, dim3(256), 0, s, S64_.data.p, S64_.ldx, S64_.dfeat, S64_.rows, mean64_.p, scale64_);
+            LSSVM_HIP_CHECK(hipGetLastError());
+            half_neg_norms<double>(S64_, cS64_, s);
+        } else {  // the polynomial runs on data that carries sqrt(gamma), with gamma = 1 in the launch arguments
+            scale64_ = std::sqrt(params_.gamma);
+            hipLaunchKernelGGL(k_center<double>, cgrid, dim3(256), 0, s, S64_.data.p, S64_.ldx, S64_.dfeat, S64_.rows, static_cast<const double *>(nullptr), scale64_);
+            LSSVM_HIP_CHECK(hipGetLastError());
+        }
+        num_jt_ = S64_.rows_alloc / TILE;
+        const size_t ra = static_cast<size_t>(S64_.rows_alloc);
+        a64_.alloc_zero(nvec_ * ra, s);  // [nvec][rows_alloc], exact zeros beyond the support vectors
+        LSSVM_HIP_CHECK(hipMemcpy2DAsync(a64_.p, ra * sizeof(double), alpha_host_.data(), nsv_ * sizeof(double), nsv_ * sizeof(double), nvec_, hipMemcpyHostToDevice, s));
+        // The column records of every launch group, once: per pair (0,1), (2,3), ... the (d0_j | d1_j | c_j) record of the two-vector kernel, and the single-vector
+        // (d_j | c_j) record of the vector no pair holds (nvec odd; nvec == 1).  Every (kernel function, chunk count) instantiation of the two-vector kernel takes less
+        // than two single-vector launches (profiles/predictor_f64.json, launch_level: 0.46 ... 0.58 of two), so every pair is launched as a pair.
+        const int ncols = num_jt_ * TILE;
+        rec_ = static_cast<size_t>(num_jt_) * 256;
+        rec2_ = static_cast<size_t>(num_jt_) * 2 * 192;
+        if (nvec_ % 2 == 1) {
+            dc64_.alloc_zero(rec_, s);
+            enqueue_pack_records(a64_.p + (nvec_ - 1) * ra, cS64_.p, ncols, dc64_.p, 0, static_cast<const double *>(nullptr), s);
+        }
+        if (nvec_ >= 2) {
+            dc2_64_.alloc_zero((nvec_ / 2) * rec2_, s);
+            for (size_t g = 0; g < nvec_ / 2; ++g) enqueue_pack_records2(a64_.p + 2 * g * ra, a64_.p + (2 * g + 1) * ra, cS64_.p, ncols, dc2_64_.p + g * rec2_, s);
+        }
+        LSSVM_HIP_CHECK(hipGetLastError());
+        LSSVM_HIP_CHECK(hipStreamSynchronize(s));
+        resident_ = true;
+    }
+
+    /* a batch of points against the resident fp64 support vectors: the steps of predict_values_impl<double> from the points' upload on */
+    bool predict_resident_f64(const double *points, int mem_kind, size_t npoints, double *out, lssvm_predict_info &info) {
+        select_device_checked(0);
+        hipStream_t s = nullptr;
+        const double t0 = now_ms();
+        const bool rbf = params_.kernel_type == LSSVM_KERNEL_RBF;
+        DeviceMatrix<double> P;
+        P.upload(points, mem_kind, npoints, nfeat_, static_cast<size_t>(round_up(static_cast<long>(npoints), 2 * TILE)), s);
+        DevBuf<double> cP;
+        // (against the SUPPORT VECTORS' means and with their scale: what center_columns(S, &P, ...) does in the one-shot call)
+        hipLaunchKernelGGL(k_center<double>, dim3((P.dfeat + 255) / 256, P.rows), dim3(256), 0, s, P.data.p, P.ldx, P.dfeat, P.rows, rbf ? mean64_.p : static_cast<const double *>(nullptr), scale64_);
+        LSSVM_HIP_CHECK(hipGetLastError());
+        if (rbf) half_neg_norms<double>(P, cP, s);
+        const int num_ib = P.rows_alloc / TILE;
+        const int jc_tiles = opt_.j_chunk_tiles > 0 ? static_cast<int>(opt_.j_chunk_tiles) : static_cast<int>(std::min<long>(16, std::max<long>(2, (static_cast<long>(num_ib) * num_jt_ + 2048) / 4096)));
+        const int num_jc = (num_jt_ + jc_tiles - 1) / jc_tiles;
+        const int nv = static_cast<int>(nvec_);
+        const int per_launch = nv >= 2 ? 2 : 1;
+        const size_t part_plane = static_cast<size_t>(num_jc) * P.rows_alloc;
+        DevBuf<double> partial, Kv, o;
+        partial.alloc_zero(per_launch * part_plane, s);
+        Kv.alloc_zero(P.rows_alloc, s);
+        o.alloc_zero(npoints * nvec_, s);
+        TileArgs<double> ta{};
+        ta.Xr = P.data.p;
+        ta.Xc = S64_.data.p;
+        ta.cr = cP.p;
+        ta.cc = cS64_.p;
+        ta.partial = partial.p;
+        ta.part_stride = P.rows_alloc;
+        ta.ldx = S64_.ldx;
+        ta.kchunks = S64_.ldx / F64_KC;
+        ta.num_ib = num_ib;
+        ta.num_jt = num_jt_;
+        ta.jc_tiles = jc_tiles;
+        ta.ncols_valid = S64_.rows;
+        set_kernel_scalars(ta, params_, false);
+        if (!rbf) ta.gamma = 1.0;
+        set_launch_options(ta, opt_);
+        LaunchTimer timer(nvec_);
+        LSSVM_HIP_CHECK(hipStreamSynchronize(s));
+        const double t_kernel = now_ms();
+        for (int v = 0; v < nv; v += per_launch) {
+            const int count = std::min(per_launch, nv - v);
+            ta.dvec = a64_.p + static_cast<size_t>(v) * S64_.rows_alloc;
+            ta.dc = count == 2 ? dc2_64_.p + static_cast<size_t>(v / 2) * rec2_ : dc64_.p;  // (alone: the vector no pair holds)
+            ta.nvec = count;
+            ta.part_vstride = count == 2 ? static_cast<long>(part_plane) : 0;
+            timer.timed(s, [&] { launch_tile_kernel<double>(ta, params_.kernel_type, false, num_jc, s); });
+            for (int u = 0; u < count; ++u) {
+                hipLaunchKernelGGL(k_reduce_partials<double>, dim3((P.rows_alloc + 255) / 256), dim3(256), 0, s, partial.p + u * part_plane, ta.part_stride, num_jc, 0, P.rows_alloc, Kv.p);
+                hipLaunchKernelGGL(k_sub_rho<double>, dim3((P.rows + 255) / 256), dim3(256), 0, s, Kv.p, P.rows, rho_[static_cast<size_t>(v + u)], o.p + (v + u), nv);
+            }
+        }
+        LSSVM_HIP_CHECK(hipGetLastError());
+        LSSVM_HIP_CHECK(hipMemcpyAsync(out, o.p, npoints * nvec_ * sizeof(double), mem_kind == LSSVM_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+        LSSVM_HIP_CHECK(hipStreamSynchronize(s));
+        timer.sum_into(info);
+        info.total_ms = now_ms() - t0;
+        info.setup_ms = t_kernel - t0;
+        info.resident = 1;
+        info.vectors_per_launch = per_launch;
+        return true;
+    }
+
     Options opt_;
     lssvm_params params_;
     size_t nsv_, nfeat_, nvec_;
@@ -726,12 +843,18 @@ class Predictor final : public PredictorBase {
     double r2_sv_ = 0.0;
     float scale_ = 1.0f;
     int num_jt_ = 0;
+    // fp64 resident form (lssvm_mi355_predictor_create_resident)
+    DeviceMatrix<double> S64_;
+    DevBuf<double> mean64_, cS64_, a64_;
+    DevBuf<double> dc64_, dc2_64_;  // column records: [rec_] of the vector no pair holds, [nvec / 2][rec2_] per pair
+    size_t rec2_ = 0;
+    double scale64_ = 1.0;
 };
 
 std::unique_ptr<PredictorBase> make_predictor(const Options &opt, const lssvm_params &params, int dtype, const void *sv, size_t nsv, size_t nfeat, const void *alpha, const double *rho,
-                                              size_t nvec) {
-    if (dtype == LSSVM_DTYPE_F32) return std::make_unique<Predictor<float>>(opt, params, static_cast<const float *>(sv), nsv, nfeat, static_cast<const float *>(alpha), rho, nvec);
-    return std::make_unique<Predictor<double>>(opt, params, static_cast<const double *>(sv), nsv, nfeat, static_cast<const double *>(alpha), rho, nvec);
+                                              size_t nvec, bool every_form) {
+    if (dtype == LSSVM_DTYPE_F32) return std::make_unique<Predictor<float>>(opt, params, static_cast<const float *>(sv), nsv, nfeat, static_cast<const float *>(alpha), rho, nvec, every_form);
+    return std::make_unique<Predictor<double>>(opt, params, static_cast<const double *>(sv), nsv, nfeat, static_cast<const double *>(alpha), rho, nvec, every_form);
 }
 
 }  // namespace lssvm

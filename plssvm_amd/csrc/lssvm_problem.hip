@@ -1394,6 +1394,10 @@ void enqueue_pack_records(const double *dvec, const double *cc, int ncols_padded
     hipLaunchKernelGGL(k_pack_dc_f64, dim3((ncols_padded + 255) / 256), dim3(256), 0, s, dvec, cc, ncols_padded, dc, static_cast<double *>(nullptr), 0);
     LSSVM_HIP_CHECK(hipGetLastError());
 }
+void enqueue_pack_records2(const double *dvec0, const double *dvec1, const double *cc, int ncols_padded, double *dc, hipStream_t s) {
+    hipLaunchKernelGGL(k_pack_dc2_f64, dim3((ncols_padded + 255) / 256), dim3(256), 0, s, dvec0, dvec1, cc, ncols_padded, dc, static_cast<double *>(nullptr), static_cast<double *>(nullptr), 0);
+    LSSVM_HIP_CHECK(hipGetLastError());
+}
 void enqueue_planes_fragment_major(const uint16_t *planes, size_t plane_elems, int rows_alloc, int ldx16, int nplanes, uint16_t *frag, hipStream_t s) {
     const size_t pieces = static_cast<size_t>(nplanes) * rows_alloc * (ldx16 / 8);
     hipLaunchKernelGGL(k_planes_fragment_major, dim3(static_cast<unsigned>((pieces + 255) / 256)), dim3(256), 0, s, planes, plane_elems, rows_alloc, ldx16, nplanes, frag);

@@ -745,9 +745,9 @@ struct PredictorBase {
      * vectors refuses the call */
     virtual void predict(const void *points, int mem_kind, size_t npoints, void *out, lssvm_predict_info *info, bool multi) = 0;
 };
-/* alpha [nvec][nsv], rho [nvec] */
+/* alpha [nvec][nsv], rho [nvec]; `every_form`: every resident form the library has (lssvm_mi355_predictor_create_resident: the fp64 one as well) */
 std::unique_ptr<PredictorBase> make_predictor(const Options &opt, const lssvm_params &params, int dtype, const void *sv, size_t nsv, size_t nfeat, const void *alpha, const double *rho,
-                                              size_t nvec);
+                                              size_t nvec, bool every_form = false);
 
 void check_params(const lssvm_params *params);
 /* weighted LS-SVM: `weights` holds num_points entries, each finite and > 0, whose diagonal terms 1/(C w_i) are finite in the real type T */
@@ -802,6 +802,8 @@ void enqueue_pack_records(const float *dvec, const float *cc, int ncols_padded, 
 void enqueue_pack_records(const double *dvec, const double *cc, int ncols_padded, double *dc, int folded, const double *efac, hipStream_t s);
 /* the records of TWO weight vectors for the rectangular 256-row kernel's NV = 2 instance: (d0 | d1), folded: both times 2^c_j (k_pack_dc2) */
 void enqueue_pack_records2(const float *dvec0, const float *dvec1, const float *cc, int ncols_padded, float *dc, int folded, hipStream_t s);
+/* ... and for the fp64 v2 kernel's NV = 2 instance: (d0 | d1 | c), 192 reals per 64-column sub-tile (k_pack_dc2_f64, nothing cleared) */
+void enqueue_pack_records2(const double *dvec0, const double *dvec1, const double *cc, int ncols_padded, double *dc, hipStream_t s);
 void enqueue_planes_fragment_major(const uint16_t *planes, size_t plane_elems, int rows_alloc, int ldx16, int nplanes, uint16_t *frag, hipStream_t s);
 
 }  // namespace lssvm

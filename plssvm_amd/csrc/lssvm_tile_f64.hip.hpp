@@ -206,8 +206,9 @@ __global__ __launch_bounds__(TILE_THREADS, 1) void tile_matvec_f64(const TileArg
  *   costs 9 % of the matrix-core rate, one v_fma_f64 15 %), so the chunk loop consists of MFMAs, LDS reads with immediate
  *   offsets, LDS-DMA with scalar base addresses and scalar instructions only, the accumulators start from the constant 0 as
  *   the C operand of the first MFMA, and the polynomial kernel runs on data pre-scaled by sqrt(gamma).
- *   NV = 2 (symmetric variant only; the lockstep CG over several right-hand sides): TWO vectors per pass.  The kernel value of an element is computed once and
- *   enters one fma chain per vector for the row sums and one per vector for the mirrored column sums; each vector's chains, butterflies and slab order are those of
+ *   NV = 2 (symmetric: the lockstep CG over several right-hand sides; full square: the resident predictor of a one-vs-all model): TWO vectors per pass.  The kernel
+ *   value of an element is computed once and enters one fma chain per vector for the row sums and (symmetric) one per vector for the mirrored column sums; the full
+ *   square has no d_i, column sums or column slabs for either vector, and its record index starts at sub-tile 0.  Each vector's chains, butterflies and slab order are those of
  *   NV = 1, so its K v has the bits of a single-vector pass whatever its partner is.  The record of a sub-tile is (d0_j | d1_j | c_j), 1.5 KiB (k_pack_dc2_f64); the
  *   second vector's d_i (TileArgs::dvec1), column sums and slabs (part_vstride, colslab_vstride) are second planes of the same arrays.  Everything of the second
  *   vector stands in `if constexpr (NV == 2)`: the NV = 1 instantiations are the code they were.
@@ -220,7 +221,7 @@ constexpr size_t V2D_LDS_BYTES_NV2 = static_cast<size_t>(V2D_RING) * V2D_SLOT_BY
 
 template <int KT, int NKC, bool SYM, int NV = 1>
 __global__ __launch_bounds__(TILE_THREADS, (NKC <= 4 ? 2 : 1)) void tile_matvec_f64_v2(const TileArgs<double> a) {
-    static_assert(NV == 1 || (NV == 2 && SYM), "two vectors per pass: the symmetric variant only");
+    static_assert(NV == 1 || NV == 2, "one or two vectors per pass");
     constexpr int REC_BYTES = NV * 512 + 512;  // a sub-tile's record: 64 d_j per vector, then 64 c_j
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     char *ring = smem_raw;
@@ -488,7 +489,7 @@ __global__ __launch_bounds__(TILE_THREADS, (NKC <= 4 ? 2 : 1)) void tile_matvec_
                         double di = 0.0;
                         if constexpr (COLS) di = dis[wave * 32 + rb * 16 + q + 4 * i];
                         [[maybe_unused]] double di1 = 0.0;
-                        if constexpr (NV == 2) di1 = dis1[wave * 32 + rb * 16 + q + 4 * i];
+                        if constexpr (COLS && NV == 2) di1 = dis1[wave * 32 + rb * 16 + q + 4 * i];
 #pragma unroll
                         for (int cb = 0; cb < 4; ++cb) {
                             double kv;
@@ -507,7 +508,7 @@ __global__ __launch_bounds__(TILE_THREADS, (NKC <= 4 ? 2 : 1)) void tile_matvec_
                             if constexpr (COLS) colacc[cb] = fma(kv, di, colacc[cb]);
                             if constexpr (NV == 2) {  // kv is shared; the second vector has fma chains of its own, those of a single-vector pass
                                 rowpart1[rb][i] = fma(kv, dj1[cb], rowpart1[rb][i]);
-                                colacc1[cb] = fma(kv, di1, colacc1[cb]);
+                                if constexpr (COLS) colacc1[cb] = fma(kv, di1, colacc1[cb]);
                             }
                         }
                     }
@@ -517,7 +518,7 @@ __global__ __launch_bounds__(TILE_THREADS, (NKC <= 4 ? 2 : 1)) void tile_matvec_
                     // is an LDS round trip per step and, with a store branch per column block, serialised them) for all four blocks at once;
                     // the sums come out one column per lane (block q in lane group q), so the store is one instruction of the whole wave
                     cw[lane] = column_sums_of_4_blocks(colacc);
-                    if constexpr (NV == 2) colred1[(t & 1) * 256 + wave * 64 + lane] = column_sums_of_4_blocks(colacc1);
+                    if constexpr (COLS && NV == 2) colred1[(t & 1) * 256 + wave * 64 + lane] = column_sums_of_4_blocks(colacc1);
                 }
             };
             // (ONE epilogue per instantiation: with a branch between a column-sum and a row-only variant the compiler gave the eight row sums

@@ -61,5 +61,7 @@ void launch_wide_tile_kernel(const TileArgs<float> &a, int kernel_type, dim3 gri
 void launch_wide_tile_kernel_f64(const TileArgs<double> &a, int kernel_type, dim3 grid, hipStream_t s);
 /* the fp64 symmetric v2 kernel with two vectors per pass (tile_launch_f64_sym2a.hip / _sym2b.hip; TileArgs::nvec == 2, reached through launch_tile_kernel<double>) */
 void launch_v2d_sym2(const TileArgs<double> &a, int kernel_type, hipStream_t s);
+/* ... and its full-square counterpart (tile_launch_f64_full2a.hip / _full2b.hip; TileArgs::items == nullptr): rbf and polynomial, `grid` from finish_mapping */
+void launch_v2d_full2(const TileArgs<double> &a, int kernel_type, dim3 grid, hipStream_t s);
 
 }  // namespace lssvm

@@ -6,11 +6,12 @@
 
 #include "lssvm_tile_f64.hip.hpp"
 
-/* This source is compiled as FOUR translation units (tile_launch_f64_sym.hip: LSSVM_TU_HALF 1 = the symmetric instantiations, tile_launch_f64_full.hip:
+/* This source is compiled as SIX translation units (tile_launch_f64_sym.hip: LSSVM_TU_HALF 1 = the symmetric instantiations, tile_launch_f64_full.hip:
  * LSSVM_TU_HALF 2 = the full-square ones, the generic kernel and the entry point, tile_launch_f64_sym2a.hip / _sym2b.hip: LSSVM_TU_HALF 3 / 4 = the symmetric
- * instantiations with two vectors per pass for 1 ... 6 / 7 ... 16 chunks), so that the build spreads over more cores. */
+ * instantiations with two vectors per pass for 1 ... 6 / 7 ... 16 chunks, tile_launch_f64_full2a.hip / _full2b.hip: LSSVM_TU_HALF 5 / 6 = the full-square
+ * instantiations with two vectors per pass, split alike), so that the build spreads over more cores. */
 #ifndef LSSVM_TU_HALF
-#error "compile tile_launch_f64_sym.hip / tile_launch_f64_full.hip / tile_launch_f64_sym2a.hip / tile_launch_f64_sym2b.hip"
+#error "compile tile_launch_f64_sym.hip / _full.hip / _sym2a.hip / _sym2b.hip / _full2a.hip / _full2b.hip"
 #endif
 
 namespace lssvm {
@@ -89,6 +90,58 @@ void launch_v2d_sym2(const TileArgs<double> &a, int kernel_type, hipStream_t s) 
 #else
 void launch_v2d_sym2_wide(const TileArgs<double> &a, int kernel_type, hipStream_t s) { launch_v2d_sym2_here(a, kernel_type, s); }
 #endif
+#elif LSSVM_TU_HALF == 5 || LSSVM_TU_HALF == 6
+/* two vectors per pass on the full square (the resident fp64 predictor: rows = points, columns = support vectors): rbf and polynomial -- the linear kernel predicts
+ * through w -- for every chunk count the single-vector kernel has */
+template <int KT>
+static void launch_v2d_full_kt2(const TileArgs<double> &a, dim3 grid, hipStream_t s) {
+    const dim3 block(TILE_THREADS);
+    switch (a.kchunks) {
+#if LSSVM_TU_HALF == 5
+        case 1: hipLaunchKernelGGL((tile_matvec_f64_v2<KT, 1, false, 2>), grid, block, V2D_LDS_BYTES_NV2, s, a); break;
+        case 2: hipLaunchKernelGGL((tile_matvec_f64_v2<KT, 2, false, 2>), grid, block, V2D_LDS_BYTES_NV2, s, a); break;
+        case 3: hipLaunchKernelGGL((tile_matvec_f64_v2<KT, 3, false, 2>), grid, block, V2D_LDS_BYTES_NV2, s, a); break;
+        case 4: hipLaunchKernelGGL((tile_matvec_f64_v2<KT, 4, false, 2>), grid, block, V2D_LDS_BYTES_NV2, s, a); break;
+        case 5: hipLaunchKernelGGL((tile_matvec_f64_v2<KT, 5, false, 2>), grid, block, V2D_LDS_BYTES_NV2, s, a); break;
+        case 6: hipLaunchKernelGGL((tile_matvec_f64_v2<KT, 6, false, 2>), grid, block, V2D_LDS_BYTES_NV2, s, a); break;
+#else
+        case 7: hipLaunchKernelGGL((tile_matvec_f64_v2<KT, 7, false, 2>), grid, block, V2D_LDS_BYTES_NV2, s, a); break;
+        case 8: hipLaunchKernelGGL((tile_matvec_f64_v2<KT, 8, false, 2>), grid, block, V2D_LDS_BYTES_NV2, s, a); break;
+        case 10: hipLaunchKernelGGL((tile_matvec_f64_v2<KT, 10, false, 2>), grid, block, V2D_LDS_BYTES_NV2, s, a); break;
+        case 12: hipLaunchKernelGGL((tile_matvec_f64_v2<KT, 12, false, 2>), grid, block, V2D_LDS_BYTES_NV2, s, a); break;
+        case 14: hipLaunchKernelGGL((tile_matvec_f64_v2<KT, 14, false, 2>), grid, block, V2D_LDS_BYTES_NV2, s, a); break;
+        case 16: hipLaunchKernelGGL((tile_matvec_f64_v2<KT, 16, false, 2>), grid, block, V2D_LDS_BYTES_NV2, s, a); break;
+#endif
+        default: throw Error(LSSVM_ERR_INTERNAL, "no two-vector v2 tile kernel for this number of k-chunks");
+    }
+}
+static void launch_v2d_full2_here(const TileArgs<double> &a, int kernel_type, dim3 grid, hipStream_t s) {
+    switch (kernel_type) {
+        case KT_LINEAR: throw Error(LSSVM_ERR_INTERNAL, "no two-vector fp64 tile kernel for the full square of the linear kernel");
+        case KT_POLY:
+            if (a.degree == 3) {
+                launch_v2d_full_kt2<KT_POLY3>(a, grid, s);
+            } else if (a.degree == 2) {
+                launch_v2d_full_kt2<KT_POLY2>(a, grid, s);
+            } else {
+                launch_v2d_full_kt2<KT_POLY>(a, grid, s);
+            }
+            break;
+        default: launch_v2d_full_kt2<KT_RBF>(a, grid, s); break;
+    }
+}
+void launch_v2d_full2_wide(const TileArgs<double> &a, int kernel_type, dim3 grid, hipStream_t s);  // tile_launch_f64_full2b.hip: 7 ... 16 chunks
+#if LSSVM_TU_HALF == 5
+void launch_v2d_full2(const TileArgs<double> &a, int kernel_type, dim3 grid, hipStream_t s) {
+    if (a.kchunks > 6) {
+        launch_v2d_full2_wide(a, kernel_type, grid, s);
+    } else {
+        launch_v2d_full2_here(a, kernel_type, grid, s);
+    }
+}
+#else
+void launch_v2d_full2_wide(const TileArgs<double> &a, int kernel_type, dim3 grid, hipStream_t s) { launch_v2d_full2_here(a, kernel_type, grid, s); }
+#endif
 #elif LSSVM_TU_HALF == 1
 void launch_v2d_sym(const TileArgs<double> &a, int kernel_type, hipStream_t s) {
     const dim3 sgrid(static_cast<unsigned>(a.num_items));
@@ -118,9 +171,12 @@ void launch_tile_kernel<double>(TileArgs<double> &a, int kernel_type, bool /*rbf
         return;
     }
     if (a.dc != nullptr) {  // the records exist only where the v2 kernel was chosen when the data was prepared; V2D_LDS_BYTES < 64 KiB
-        if (a.nvec == 2) {  // two vectors per pass exist for the symmetric variant only (Problem<double>::enqueue_apply_K_lanes asks for nothing else)
-            if (a.items == nullptr) throw Error(LSSVM_ERR_INTERNAL, "no two-vector fp64 tile kernel for the full square");
-            launch_v2d_sym2(a, kernel_type, s);
+        if (a.nvec == 2) {  // two vectors per pass: the symmetric variant (Problem<double>::enqueue_apply_K_lanes), the full square (the resident Predictor<double>)
+            if (a.items == nullptr) {
+                launch_v2d_full2(a, kernel_type, grid, s);
+            } else {
+                launch_v2d_sym2(a, kernel_type, s);
+            }
         } else if (a.items != nullptr) {
             launch_v2d_sym(a, kernel_type, s);
         } else {

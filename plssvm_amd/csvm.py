@@ -253,7 +253,7 @@ class MI355CSVM(CSVM):
 
     def decision_values_resident(self, model, X):
         """The decision values ``f[i, c]`` of a :class:`plssvm_amd.multiclass.OneVsAllModel` with the model RESIDENT in HBM from the first call on
-        (``lssvm_mi355_predictor_create_multi``): later calls with the same model upload only their points.  The predictor is cached on the model and made again (the old
+        (``lssvm_mi355_predictor_create_resident``: every resident form the library has, float64 included): later calls with the same model upload only their points.  The predictor is cached on the model and made again (the old
         one closed) under the rule of :meth:`predict`: another backend object, changed option values, kernel parameters, another support-vector array (by identity),
         ``alpha`` (by value) or ``rho``."""
         sv = model.support_vectors
@@ -267,7 +267,7 @@ class MI355CSVM(CSVM):
                 cached["predictor"].close()  # (its HBM: nothing else holds it)
             alpha, rho = np.array(model.alpha, copy=True), np.array(model.rho, copy=True)
             cached = {"owner": self, "options": opts, "params": params, "sv": sv, "alpha": alpha, "rho": rho,
-                      "predictor": backend.Predictor(model.params, sv, alpha, rho, options=self._options)}
+                      "predictor": backend.Predictor(model.params, sv, alpha, rho, options=self._options, every_form=True)}
             model._predictor = cached
         return cached["predictor"].predict(np.asarray(X, dtype=sv.dtype))
 
@@ -291,7 +291,7 @@ class MI355CSVM(CSVM):
                 cached["predictor"].close()  # (its HBM: nothing else holds it)
             alpha = np.array(model.alpha, copy=True)
             cached = {"owner": self, "options": opts, "params": params, "sv": sv, "alpha": alpha, "rho": float(model.rho),
-                      "predictor": backend.Predictor(model.params, sv, alpha, float(model.rho), options=self._options)}
+                      "predictor": backend.Predictor(model.params, sv, alpha, float(model.rho), options=self._options, every_form=True)}
             model._predictor = cached
         t1 = time.perf_counter()
         info = {}
