@@ -276,9 +276,11 @@ int lssvm_mi355_predictor_create_multi(lssvm_mi355_predictor **out, const lssvm_
 int lssvm_mi355_predictor_predict_multi(lssvm_mi355_predictor *predictor, const void *predict_points, int mem_kind, size_t num_predict_points, void *out,
                                         lssvm_predict_info *info);
 
-/* The same handle, running against a resident form WHEREVER THE LIBRARY HAS ONE: the fp32 form of `create` / `create_multi` above and, in addition, an fp64 form for
- * rbf / polynomial models (gamma > 0) of at most 256 padded features with tile_kernel != 1.  (`create` / `create_multi` keep their documented routing: an fp64 model
- * of these kernels takes the one-shot path there.)  Arguments, their validation and the error texts are those of `create_multi`, refused before a device is touched;
+/* The same handle, running against a resident form WHEREVER THE LIBRARY HAS ONE: the fp32 form of `create` / `create_multi` above; in addition an fp64 form for
+ * rbf / polynomial models (gamma > 0) of at most 256 padded features with tile_kernel != 1; and the fp32 form for rbf / polynomial models of MORE than 128 features,
+ * as far as the one-pass split kernels reach (features padded to 64: polynomial up to 512 on f16 planes, rbf and every model on bf16 planes up to 384).
+ * (`create` / `create_multi` keep their documented routing: an fp64 model of these kernels, and an fp32 model beyond 128 features, take the one-shot path there.)
+ * Arguments, their validation and the error texts are those of `create_multi`, refused before a device is touched;
  * num_vectors == 1 gives the handle of one vector.  `predict`, `predict_multi` and `destroy` work on the handle as on any other.
  * The fp64 form uploads the support vectors once and prepares them as lssvm_mi355_predict_values_f64 prepares them per call (rbf: centred by their column means and
  * scaled, norms; polynomial: scaled by sqrt(gamma)), keeps the alpha matrix in HBM and packs the records of every launch group: a pair record for (0,1), (2,3), ...,
@@ -286,9 +288,15 @@ int lssvm_mi355_predictor_predict_multi(lssvm_mi355_predictor *predictor, const 
  * runs one launch of the full-square two-vector fp64 kernel per pair: the kernel value of an element is computed once, each vector's sums are the chains of a
  * single-vector launch.  Every value has the bits of lssvm_mi355_predict_values_f64 for that (alphas[v], rhos[v]) with the same options.  fp64 rbf has no direct
  * form and no plane check, so this form never declines a batch and keeps no host copy of the support vectors.  lssvm_predict_info.resident and .vectors_per_launch
- * report as for fp32: 2 where a pair launch ran, 1 for a `predict_multi` call of one-vector launches, 0 from `predict`.  An fp32 model's handle is
- * indistinguishable from a `create_multi` handle; outside both forms (fp64 beyond 256 features, tile_kernel = 1, fp32 beyond 128 features) the handle does what a
- * `create_multi` handle does, resident == 0. */
+ * report as for fp32: 2 where a pair launch ran, 1 for a `predict_multi` call of one-vector launches, 0 from `predict`.
+ * The wide fp32 form prepares the support vectors as the form of `create_multi` does (centre, norms, operand planes, the records of every launch group) and declines
+ * what that form declines (gram_mode 0, tile_kernel 1, rbf_form 1 / 3, exponent scales beyond the norm expansion, a batch that fails the f16 check beside f16 planes:
+ * the one-shot path, resident == 0, its values).  A batch always runs on the 128-row full-square kernels, its row slabs reduced over the column chunks of the one-shot
+ * call: two weight vectors per launch for the polynomial kernel and for rbf within the folded form's range, one for rbf beyond it.  Every column has the bits of a
+ * single-vector handle of (alphas[v], rhos[v]); rbf values are those of lssvm_mi355_predict_values_multi_f32, polynomial values differ from it by the rounding of the
+ * planes' power-of-two scale (taken from the support vectors alone here, from both sides there).
+ * An fp32 model of at most 128 features gives a handle indistinguishable from a `create_multi` handle; outside all forms (fp64 beyond 256 features, fp32 beyond the
+ * one-pass split kernels -- the feature-panel kernels --, tile_kernel = 1) the handle does what a `create_multi` handle does, resident == 0. */
 int lssvm_mi355_predictor_create_resident(lssvm_mi355_predictor **out, const lssvm_params *params, int dtype, const void *support_vectors, size_t num_support_vectors,
                                           size_t num_features, const void *alphas, const double *rhos, size_t num_vectors, const lssvm_mi355_options *options);
 

@@ -261,8 +261,10 @@ class Predictor:
     ``info_out["vectors_per_launch"]`` says whether one pass over the Gram tiles fed two weight vectors (2) or every vector had a launch of its own (1).
 
     ``every_form=True`` creates the model through ``lssvm_mi355_predictor_create_resident``, for a vector or a matrix of weights: every resident form the library has,
-    which adds the float64 one (rbf / polynomial, at most 256 features, two weight vectors per pass).  The default keeps the routing of ``_create`` / ``_create_multi``,
-    where a float64 rbf / polynomial model takes the one-shot path.  The values are the same bits either way."""
+    which adds the float64 one (rbf / polynomial, at most 256 features, two weight vectors per pass) and the float32 one beyond 128 features (rbf up to 384 features,
+    polynomial up to 512 on f16 planes and 384 on bf16 planes; two weight vectors per pass).  The default keeps the routing of ``_create`` / ``_create_multi``, where a
+    float64 rbf / polynomial model and a float32 model of more than 128 features take the one-shot path.  Float64 and rbf values are the same bits either way; a wide
+    float32 polynomial model's differ from the one-shot call's by the rounding of the operand planes' scale (a few eps of the summand scale)."""
 
     def __init__(self, params: Parameter, support_vectors, alpha, rho, options: Options | None = None, every_form: bool = False):
         sv = _as_matrix(support_vectors)

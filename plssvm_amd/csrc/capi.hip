@@ -325,7 +325,7 @@ int lssvm_mi355_predictor_create(lssvm_mi355_predictor **out, const lssvm_params
         *out = h.release();
     });
 }
-/* _create_multi and _create_resident: one validation, one set of error texts; `every_form`: every resident form the library has (the fp64 one as well) */
+/* _create_multi and _create_resident: one validation, one set of error texts; `every_form`: every resident form the library has (the fp64 one and the fp32 one beyond 128 features as well) */
 static int create_predictor_of_vectors(lssvm_mi355_predictor **out, const lssvm_params *params, int dtype, const void *support_vectors, size_t num_support_vectors, size_t num_features,
                                        const void *alphas, const double *rhos, size_t num_vectors, const lssvm_mi355_options *options, bool every_form) {
     return guarded([&] {

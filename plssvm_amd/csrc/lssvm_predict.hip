@@ -405,8 +405,9 @@ template void calculate_w<double>(const double *, size_t, size_t, const double *
 /* ------------------------------------------------------------------ the resident predictor ------------------------------------------------------------------ */
 /* `nvec_` weight vectors over the same support vectors (lssvm_mi355_predictor_create: one; _create_multi: a one-vs-all model's k).  Everything that does not depend on
  * the weight vector is held once; per vector the alpha row, the packed column records of its launch group and, for the linear kernel, w.
- * `every_form` (lssvm_mi355_predictor_create_resident): fp64 rbf / polynomial models on at most 256 padded features are resident as well (prepare_resident_f64); without
- * it an fp64 model of these kernels goes through the one-shot path, as _create / _create_multi document. */
+ * `every_form` (lssvm_mi355_predictor_create_resident): fp64 rbf / polynomial models on at most 256 padded features are resident as well (prepare_resident_f64), and so
+ * are fp32 models of 129 ... 512 features on the one-pass split kernels (prepare_resident); without it such a model goes through the one-shot path, as _create /
+ * _create_multi document. */
 template <typename T>
 class Predictor final : public PredictorBase {
   public:
@@ -435,7 +436,7 @@ class Predictor final : public PredictorBase {
         }
         alpha_host_.assign(alpha, alpha + nvec * nsv);
         if constexpr (std::is_same_v<T, float>) {
-            prepare_resident(sv, s);
+            prepare_resident(sv, s, every_form);
         } else {
             if (every_form) prepare_resident_f64(sv, s);
             if (resident_) std::vector<T>().swap(alpha_host_);  // (the fp64 form never declines a batch: the one-shot path's inputs are not needed)
@@ -469,8 +470,10 @@ class Predictor final : public PredictorBase {
             if (resident_) done = predict_resident_f64(points, mem_kind, npoints, out, local);
         }
         if (!done) {
-            // what the resident form does not cover (fp64 outside lssvm_mi355_predictor_create_resident or beyond 256 features, fp32 on more than 128 features, exponent scales beyond the norm expansion, a batch whose planes fail the f16 check or
-            // that lies further from the support vectors' centre than the form chosen for them allows): the one-shot path, same result
+            // what the resident form does not cover (outside lssvm_mi355_predictor_create_resident: fp64, and fp32 on more than 128 features; with it: fp64 beyond 256
+            // features and fp32 beyond the one-pass split kernels' 512 / 384; gram_mode 0, tile_kernel 1, rbf_form 1 / 3; exponent scales beyond the norm expansion; a
+            // batch whose planes fail the f16 check or that lies further from the support vectors' centre than the form chosen for them allows): the one-shot path,
+            // same result
             int w_valid = 0;
             std::vector<T> w_tmp(nvec_ * nfeat_);
             if (sv_host_.empty()) fetch_support_vectors();
@@ -520,9 +523,11 @@ class Predictor final : public PredictorBase {
         info.vectors_per_launch = 1;
     }
 
-    /* fp32, rbf / polynomial, at most 128 features, a split Gram mode: the support vectors' side of the product, once */
-    void prepare_resident(const float *sv, hipStream_t s) {
-        if (round_up(static_cast<long>(nfeat_), 64) > 128 || opt_.gram_mode == 0 || opt_.tile_kernel == 1) return;
+    /* fp32, rbf / polynomial, a split Gram mode: the support vectors' side of the product, once.  At most 128 features -- or, `every_form`, every width the one-shot
+     * call runs on the one-pass split kernels (v2_eligible and not wide_nonlinear: the 128-row full-square kernels with the row panel in registers). */
+    void prepare_resident(const float *sv, hipStream_t s, bool every_form) {
+        const bool beyond128 = round_up(static_cast<long>(nfeat_), 64) > 128;
+        if ((beyond128 && (!every_form || wide_nonlinear(opt_, params_, false, nfeat_))) || opt_.gram_mode == 0 || opt_.tile_kernel == 1) return;
         if (params_.kernel_type == LSSVM_KERNEL_RBF && (opt_.rbf_form == 1 || opt_.rbf_form == 3)) return;  // (the direct kernel / the grid planes asked for: the one-shot path has them)
         S_.upload(sv, LSSVM_MEM_HOST, nsv_, nfeat_, 0, s);
         if (!v2_eligible(opt_, S_.ldx, false)) return;
@@ -553,13 +558,16 @@ class Predictor final : public PredictorBase {
         const int ncols = num_jt_ * TILE;
         rec_ = static_cast<size_t>(num_jt_) * 256;
         const bool fold = rbf && opt_.rbf_fold != 0;
+        // (beyond 128 features a pair exists only where its launch is dispatched -- wide_pair_routed --; elsewhere every vector keeps the records of a launch of its own)
+        const bool pairs = nvec_ >= 2 && (!rbf || fold) && (planesS_.ldx16 <= 128 || wide_pair_routed(planesS_.mode, params_.kernel_type, params_.degree, planesS_.ldx16 / 64));
+        folded_first_ = pairs ? nvec_ - 1 : 0;
         dc_.alloc_zero(nvec_ * rec_, s);
-        for (size_t v = rbf ? 0 : nvec_ - nvec_ % 2; v < nvec_; ++v) enqueue_pack_records(a_.p + v * ra, cS_.p, ncols, dc_.p + v * rec_, 0, static_cast<const float *>(nullptr), s);
-        if (fold && nvec_ % 2 == 1) {
-            dc_folded_.alloc_zero(rec_, s);
-            enqueue_pack_records(a_.p + (nvec_ - 1) * ra, cS_.p, ncols, dc_folded_.p, 1, static_cast<const float *>(nullptr), s);
+        for (size_t v = (rbf || !pairs) ? 0 : nvec_ - nvec_ % 2; v < nvec_; ++v) enqueue_pack_records(a_.p + v * ra, cS_.p, ncols, dc_.p + v * rec_, 0, static_cast<const float *>(nullptr), s);
+        if (fold && (nvec_ % 2 == 1 || !pairs)) {
+            dc_folded_.alloc_zero((nvec_ - folded_first_) * rec_, s);
+            for (size_t v = folded_first_; v < nvec_; ++v) enqueue_pack_records(a_.p + v * ra, cS_.p, ncols, dc_folded_.p + (v - folded_first_) * rec_, 1, static_cast<const float *>(nullptr), s);
         }
-        if (nvec_ >= 2 && (!rbf || fold)) {
+        if (pairs) {
             dc2_.alloc_zero((nvec_ / 2) * rec_, s);
             for (size_t g = 0; g < nvec_ / 2; ++g) enqueue_pack_records2(a_.p + 2 * g * ra, a_.p + (2 * g + 1) * ra, cS_.p, ncols, dc2_.p + g * rec_, fold ? 1 : 0, s);
         }
@@ -645,7 +653,8 @@ class Predictor final : public PredictorBase {
         const bool folded = rbf && opt_.rbf_fold != 0 && r2 <= FOLD_MAX_R2;
         const bool poly_generic = params_.kernel_type == LSSVM_KERNEL_POLYNOMIAL && params_.degree != 2 && params_.degree != 3;
         const bool rbf_ok = !rbf || (folded && r2 <= 2.0 * PAIR_FOLD_MAX_C);
-        const bool rect = !poly_generic && rbf_ok && opt_.mfma_shape >= 3 && num_ib >= PAIR_MIN_TILES;
+        // (the rectangular 256-row kernel exists up to 128 features; wider models take the 128-row full-square kernels at every batch size, as in the one-shot call)
+        const bool rect = planesS_.ldx16 <= 128 && !poly_generic && rbf_ok && opt_.mfma_shape >= 3 && num_ib >= PAIR_MIN_TILES;
         const long rect_tiles = std::min<long>(64, std::max<long>(4, (static_cast<long>(num_ib / 2) * num_jt_ + 1024) / 2048));
         const int jc_tiles = opt_.j_chunk_tiles > 0 ? static_cast<int>(opt_.j_chunk_tiles)
                                                    : (rect ? static_cast<int>(rect_tiles) : static_cast<int>(std::min<long>(16, std::max<long>(2, (static_cast<long>(num_ib) * num_jt_ + 2048) / 4096))));
@@ -688,8 +697,8 @@ class Predictor final : public PredictorBase {
             ta.dvec = a_.p + static_cast<size_t>(v) * S_.rows_alloc;
             if (count == 2) {
                 ta.dc = dc2_.p + static_cast<size_t>(v / 2) * rec_;
-            } else if (folded) {  // (folded and alone: the vector no pair holds)
-                ta.dc = dc_folded_.p;
+            } else if (folded) {  // (folded and alone: the vector no pair holds -- or, where pairs are not dispatched, every vector)
+                ta.dc = dc_folded_.p + (static_cast<size_t>(v) - folded_first_) * rec_;
             } else {
                 ta.dc = dc_.p + static_cast<size_t>(v) * rec_;
             }
@@ -839,6 +848,7 @@ class Predictor final : public PredictorBase {
     DevBuf<float> mean_, cS_, a_, raw_;
     DevBuf<float> dc_, dc_folded_, dc2_;  // column records: [nvec][rec_] per vector, the folded one of an unpaired last vector, [nvec / 2][rec_] per pair
     size_t rec_ = 0;
+    size_t folded_first_ = 0;             // the vector dc_folded_ starts with (the last one; 0 where no pair launch is dispatched and every vector has one)
     PlaneSet planesS_;
     double r2_sv_ = 0.0;
     float scale_ = 1.0f;

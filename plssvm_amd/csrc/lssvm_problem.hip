@@ -122,6 +122,17 @@ bool wide_nonlinear(const Options &o, const lssvm_params &p, bool rbf_direct, si
     return nonlinear && o.gram_mode != 0 && o.tile_kernel != 1 && round_up(static_cast<long>(num_features), 64) > one_pass_limit;
 }
 
+/* The resident fp32 predictor beyond 128 features (Predictor<float>, lssvm_predict.hip): whether a pair of weight vectors is dispatched as ONE launch of the wide
+ * two-vector kernels (tile_launch_f32v2w.hip) -- by plane kind (PlaneSet::mode: 1 bf16x6, 2 f16x3), kernel function (polynomial: its degree selects the instantiation)
+ * and the number of 64-feature chunks.  The project's routing condition: a pair launch is dispatched where it was measured to take less than two single-vector launches
+ * by more than the single-vector kernel's own run-to-run spread (tests/tools/predictor_f32_wide_timing.py, profiles/predictor_f32_wide.json); an instantiation that
+ * fails it is named here and served by two single-vector launches on the same resident data.  None is named: all 38 meet it at 4 096 points x 30 000 support vectors
+ * -- 0.49 ... 0.53 of two launches, the worst ratio + spread 0.60 (bf16x6, polynomial of degree 2, three chunks) -- and are dispatched. */
+bool wide_pair_routed(int plane_mode, int kernel_type, int /*degree*/, int nk64) {
+    const int max_nk64 = (plane_mode == 2 && kernel_type != LSSVM_KERNEL_RBF) ? 8 : 6;  // (what tile_launch_f32v2w.hip instantiates)
+    return (plane_mode == 1 || plane_mode == 2) && nk64 >= 3 && nk64 <= max_nk64;
+}
+
 /* first row block of rank r when the lower triangle is dealt by equal area: tiles * sqrt(r / world), rounded to an EVEN block index -- the
  * 256-row workgroups of lssvm_tile_f32_pair.hip.hpp work on the block pairs (2p, 2p + 1), which must not straddle two devices (every symmetric
  * partition follows the rule, whichever kernel runs: one partition per problem shape) */

@@ -782,6 +782,7 @@ template <typename T>
 T rbf_prescale(const lssvm_params &p, bool fp64_v2);
 bool wide_nonlinear_f64(const Options &o, const lssvm_params &p, size_t num_features);
 bool wide_nonlinear(const Options &o, const lssvm_params &p, bool rbf_direct, size_t num_features);
+bool wide_pair_routed(int plane_mode, int kernel_type, int degree, int nk64);  // the resident fp32 predictor beyond 128 features: one two-vector launch for a pair?
 template <typename T>
 void set_kernel_scalars(TileArgs<T> &a, const lssvm_params &p, bool rbf_direct);
 template <typename T>

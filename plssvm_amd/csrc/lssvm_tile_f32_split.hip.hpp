@@ -575,6 +575,13 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void tile_matvec_f32_s6w_nv2(const
     static_assert(NK64 <= 2, "two weight vectors per pass: at most 128 features");
     s6w_body<KT, NK64, false, false, 3, 2>(a);
 }
+/* ... and beyond 128 features (tile_launch_f32v2w.hip: the resident predictor of a wide one-vs-all model): the compiler-scheduled groups, one workgroup per CU like
+ * tile_matvec_f32_s6w beyond two chunks.  The row panel is the single-vector kernel's; the second vector costs eight more accumulators of row sums. */
+template <int KT, int NK64>
+__global__ __launch_bounds__(TILE_THREADS, 1) void tile_matvec_f32_s6w_nv2w(const TileArgs<float> a) {
+    static_assert(NK64 > 2 && NK64 <= 6, "the wide two-vector bf16x6 kernel: 3 ... 6 chunks of 64 features");
+    s6w_body<KT, NK64, false, false, 3, 2>(a);
+}
 /* "f16x3": the same kernels on TWO f16 planes (x = hi + mid, 11 + 11 significant bits, k_split_f16x2) and the three plane products
  * hi*hi + hi*mid + mid*hi on v_mfma_f32_16x16x32_f16 -- half the matrix-core work of bf16x6 and two thirds of its column stream.  What is
  * dropped (mid*mid and the split remainder) is below 2^-23 |x||y| per product while the planes stay in f16's normal range, which the set-up
@@ -612,6 +619,11 @@ __global__ __launch_bounds__(TILE_THREADS, 2) LSSVM_HAND_VGPR_CAP void tile_matv
 template <int KT, int NK64>
 __global__ __launch_bounds__(TILE_THREADS, 2) void tile_matvec_f32_f3w_nv2(const TileArgs<float> a) {
     static_assert(NK64 <= 2, "two weight vectors per pass: at most 128 features");
+    s6w_body<KT, NK64, false, false, 2, 2>(a);
+}
+template <int KT, int NK64>
+__global__ __launch_bounds__(TILE_THREADS, 1) void tile_matvec_f32_f3w_nv2w(const TileArgs<float> a) {
+    static_assert(NK64 > 2 && NK64 <= f16_max_nk64(KT), "the wide two-vector f16x3 kernel: 3 chunks of 64 features up to the row panel the register file holds");
     s6w_body<KT, NK64, false, false, 2, 2>(a);
 }
 

@@ -55,6 +55,8 @@ void launch_pair_tile_kernel(const TileArgs<float> &a, int kernel_type, hipStrea
 void launch_rect2_tile_kernel(const TileArgs<float> &a, int kernel_type, hipStream_t s);
 /* the 128-row full-square split kernels with two weight vectors per pass (tile_launch_f32v2.hip; TileArgs::nvec == 2, reached through the two launchers above) */
 void launch_nv2_tile_kernel(const TileArgs<float> &a, int kernel_type, dim3 grid, hipStream_t s);
+/* ... beyond 128 features (tile_launch_f32v2w.hip; reached through launch_nv2_tile_kernel) */
+void launch_nv2_wide_tile_kernel(const TileArgs<float> &a, int kernel_type, dim3 grid, hipStream_t s);
 /* rbf / polynomial on more features than a row panel in registers holds (tile_launch_f32x.hip): feature panels inside a tile */
 void launch_wide_tile_kernel(const TileArgs<float> &a, int kernel_type, dim3 grid, hipStream_t s);
 /* fp64 rbf / polynomial on more than 256 features (tile_launch_f64x.hip): feature panels of 64 inside a sub-tile */

@@ -1,7 +1,7 @@
 /*
  * tile_launch_f32v2.hip -- instantiates and launches the 128-row full-square split tile kernels (lssvm_tile_f32_split.hip.hpp) with TWO weight vectors per pass
  * (NV = 2: the resident predictor of a one-vs-all model on batches below the rectangular 256-row kernel's 64 row blocks).  Both plane kinds (f16x3, bf16x6), one and
- * two 64-feature chunks; the polynomial forms and rbf with folded records -- the forms whose kernel leaves the second half of the column record free for the second
+ * two 64-feature chunks (more: tile_launch_f32v2w.hip, reached through the entry point below); the polynomial forms and rbf with folded records -- the forms whose kernel leaves the second half of the column record free for the second
  * vector.  A translation unit of its own, so that it builds beside the single-vector instantiations.  Compiled for gfx950 only.
  */
 #include "tile_launch.hip.hpp"
@@ -65,7 +65,9 @@ static void launch_nv2(const TileArgs<float> &a, int kernel_type, dim3 grid, hip
 void launch_nv2_tile_kernel(const TileArgs<float> &a, int kernel_type, dim3 grid, hipStream_t s) {
     if (a.items != nullptr) throw Error(LSSVM_ERR_INTERNAL, "two weight vectors per pass: the full-square variant only");
     if (a.part_vstride <= 0) throw Error(LSSVM_ERR_INTERNAL, "two weight vectors per pass need the second plane of the row slabs (TileArgs::part_vstride)");
-    if (a.planes_f16 != 0) {
+    if (a.nk64 > 2) {  // beyond 128 features: the one-workgroup-per-CU instantiations of tile_launch_f32v2w.hip
+        launch_nv2_wide_tile_kernel(a, kernel_type, grid, s);
+    } else if (a.planes_f16 != 0) {
         launch_nv2<2>(a, kernel_type, grid, s);
     } else {
         launch_nv2<3>(a, kernel_type, grid, s);
