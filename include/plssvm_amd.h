@@ -393,7 +393,8 @@ int lssvm_mi355_problem_matvec(lssvm_mi355_problem *p, const void *d, void *ret_
 
 /* lssvm_mi355_problem_matvec for TWO vectors: ret_u[0..N-1) += add * Abar * d_u.  Each result has the bits lssvm_mi355_problem_matvec gives for that vector, whatever its
  * partner is.  *two_vector_out (may be NULL) = 1 if ONE pass over the Gram tiles served both -- fp64, one device, symmetric = 1, at most 256 features on the resident-row-panel
- * kernel -- and 0 where the call ran two single passes (everywhere else).  Rejected between cg_begin and cg_finish. */
+ * kernel; fp32, one device, symmetric = 1, 129 ... 512 features (bf16x6 planes and rbf: ... 384) on the one-pass split kernels, polynomial or rbf with folded records --
+ * and 0 where the call ran two single passes (everywhere else).  Rejected between cg_begin and cg_finish. */
 int lssvm_mi355_problem_matvec_pair(lssvm_mi355_problem *p, const void *d0, const void *d1, void *ret0_inout, void *ret1_inout, double add, int *two_vector_out);
 
 /* num_rhs right-hand sides (Y: num_rhs x N row-major, the problem's dtype) on one resident problem, in LOCKSTEP: every right-hand side runs the recipe of
@@ -404,8 +405,9 @@ int lssvm_mi355_problem_matvec_pair(lssvm_mi355_problem *p, const void *d0, cons
  * 1 + it + it / 50.  The time fields differ from a one-shot solve's: total_ms of infos_out[c] is the wall clock from the start of the CALL until right-hand side c left,
  * avg_iteration_ms that over its iterations, and matvec_kernel_ms the average over the passes it took part in (a two-vector pass counts in full for both).
  * passes_out (may be NULL): [0] two-vector Gram passes, [1] single-vector Gram passes.  Weights set with lssvm_mi355_problem_set_weights are honoured.  Rejected between
- * cg_begin and cg_finish.  Elsewhere -- fp32, several devices or ranks, symmetric = 0, tile_kernel = 1, more than 256 features -- the right-hand sides are solved one after
- * the other and passes_out[0] is 0. */
+ * cg_begin and cg_finish.  Elsewhere -- several devices or ranks, symmetric = 0, tile_kernel = 1, fp64 on more than 256 features, fp32 outside the range
+ * lssvm_mi355_problem_matvec_pair names (at most 128 features, gram_mode = 0, unfolded rbf, the panel kernels) -- the right-hand sides are solved one after the other and
+ * passes_out[0] is 0. */
 int lssvm_mi355_problem_solve_lockstep(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out /* num_rhs x N */,
                                        double *rhos_out, lssvm_cg_info *infos_out /* num_rhs, may be NULL */, uint64_t passes_out[2]);
 

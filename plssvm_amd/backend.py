@@ -444,7 +444,8 @@ class ResidentProblem:
 
     def matvec_pair(self, d0, d1, ret0, ret1, add: float = 1.0):
         """:meth:`matvec` for two vectors (``lssvm_mi355_problem_matvec_pair``): returns ``(out0, out1, two_vector)`` -- each result the bits of :meth:`matvec` for that
-        vector; ``two_vector`` says whether one pass over the Gram tiles served both (fp64, one device, the symmetric resident-row-panel kernel) or two single passes ran."""
+        vector; ``two_vector`` says whether one pass over the Gram tiles served both (one device; fp64: the symmetric resident-row-panel kernel; fp32: the symmetric one-pass split kernels on 129 ... 512 features, polynomial or rbf with folded
+        records) or two single passes ran."""
         ds = [np.ascontiguousarray(d, dtype=self.dtype) for d in (d0, d1)]
         outs = [np.array(ret, dtype=self.dtype, copy=True) for ret in (ret0, ret1)]
         for v in ds + outs:
@@ -456,7 +457,8 @@ class ResidentProblem:
 
     def solve_lockstep(self, B, eps: float, max_iter: int):
         """``k`` right-hand sides (``B``: ``k x num_points``) in lockstep on this problem (``lssvm_mi355_problem_solve_lockstep``): every one runs the recipe of
-        :meth:`cg_begin` / :meth:`cg_step` / :meth:`cg_finish`, and where the two-vector kernel applies one pass over the Gram tiles serves two of them per iteration.
+        :meth:`cg_begin` / :meth:`cg_step` / :meth:`cg_finish`, and where the two-vector kernel applies (fp64, and fp32 on 129 ... 512 features: see :meth:`matvec_pair`)
+        one pass over the Gram tiles serves two of them per iteration.
         Returns ``(alphas[k, num_points], rhos[k], infos, passes)`` -- per right-hand side the bits of a one-shot solve; ``passes = (two-vector, single-vector)`` Gram
         passes."""
         B = np.ascontiguousarray(B, dtype=self.dtype)

@@ -378,5 +378,8 @@ constexpr int V2_RING = 4;                       // chunk slots in LDS
 constexpr int V2_SLOT_BYTES = TILE * 32 * 4;     // 16 KiB
 constexpr int V2_DC_SLOTS = 4;                   // ring of per-tile (d_j | c_j) records, 1 KiB each
 constexpr size_t V2_LDS_BYTES = static_cast<size_t>(V2_RING) * V2_SLOT_BYTES + V2_DC_SLOTS * 1024 + (2 * TILE + 2 * 4 * TILE) * sizeof(float);  // ring + records + cis, dis, colred
+/* ... of the symmetric split kernels with two vectors per pass (s6w_body<..., SYM, ..., NV = 2>): record slots of 1.5 KiB, two planes of dis and of colred */
+constexpr int V2S_REC_SLOT_BYTES = 1536;
+constexpr size_t V2S_LDS_BYTES = static_cast<size_t>(V2_RING) * V2_SLOT_BYTES + V2_DC_SLOTS * V2S_REC_SLOT_BYTES + (TILE + 2 * TILE + 2 * 2 * 4 * TILE) * sizeof(float);  // ring + records + cis, 2 dis, 2 colred
 
 }  // namespace lssvm

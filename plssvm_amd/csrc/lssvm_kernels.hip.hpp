@@ -76,6 +76,32 @@ __global__ void k_pack_dc2(const float *__restrict__ dvec0, const float *__restr
 }
 #endif  // LSSVM_KERNELS_SETUP
 
+/* ... for the SYMMETRIC 128-row split kernels with two vectors per pass (Problem<float>::enqueue_apply_K_lanes): the mirrored column sums of folded rbf need the
+ * column's factor beside both vectors' halves, so folded != 0 writes records of 384 floats, dc[jt][0..127] = 2^c_j d0, dc[jt][128..255] = 2^c_j d1, dc[jt][256..383] = 2^c_j;
+ * folded == 0 (polynomial forms): k_pack_dc2's 256.  Per vector the statements of k_pack_dc; clears both result vectors, as k_pack_dc does for one */
+#ifdef LSSVM_KERNELS_SETUP
+__global__ void k_pack_dc2_sym(const float *__restrict__ dvec0, const float *__restrict__ dvec1, const float *__restrict__ cc, int ncols_padded, float *__restrict__ dc, int folded,
+                               float *__restrict__ zero0, float *__restrict__ zero1, int nzero) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < nzero) {
+        zero0[j] = 0.0f;
+        zero1[j] = 0.0f;
+    }
+    if (j >= ncols_padded) return;
+    const int jt = j >> 7, l = j & 127;
+    if (folded) {
+        const float c = (cc != nullptr) ? cc[j] : 0.0f;
+        const float e = __builtin_amdgcn_exp2f(c);
+        dc[static_cast<size_t>(jt) * 384 + l] = e * dvec0[j];
+        dc[static_cast<size_t>(jt) * 384 + 128 + l] = e * dvec1[j];
+        dc[static_cast<size_t>(jt) * 384 + 256 + l] = e;
+    } else {
+        dc[static_cast<size_t>(jt) * 256 + l] = dvec0[j];
+        dc[static_cast<size_t>(jt) * 256 + 128 + l] = dvec1[j];
+    }
+}
+#endif  // LSSVM_KERNELS_SETUP
+
 /* operand planes [nplanes][rows][ldx16] (row-major, rows a multiple of 16, ldx16 of 64) -> the same data with every block of 16 rows x 32 features stored
  * as ONE MFMA A fragment (64 lanes x 8 halfs, lane 16 g + r holding features 8 g .. 8 g + 7 of row r), ordered
  * [plane][ldx16 / 64 chunks][rows / 16 blocks][2 k32 steps][64 lanes][8]: the 64-feature chunk OUTERMOST, so that the sixteen row blocks a workgroup

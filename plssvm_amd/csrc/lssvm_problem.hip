@@ -133,6 +133,16 @@ bool wide_pair_routed(int plane_mode, int kernel_type, int /*degree*/, int nk64)
     return (plane_mode == 1 || plane_mode == 2) && nk64 >= 3 && nk64 <= max_nk64;
 }
 
+/* The lockstep CG in fp32 on 129 ... 512 features (Problem<float>::pair_kernel_applies): whether a pair of right-hand sides is dispatched as ONE launch of the symmetric
+ * two-vector kernels (tile_launch_f32v2ws.hip) -- same arguments, same routing condition as wide_pair_routed, measured by tests/tools/lockstep_f32_wide_timing.py
+ * (profiles/lockstep_f32_wide.json) against two single-vector symmetric passes of the build before.  An instantiation that fails the condition, or that the compiler
+ * does not fit into the register file without scratch, is named here and takes two single passes.  None is named: all 38 compile without scratch and meet the condition
+ * at 30 000 points -- 0.50 ... 0.54 of two passes, the worst ratio + spread 0.66 (f16x3, folded rbf, four chunks) -- and are dispatched. */
+bool sym_pair_routed(int plane_mode, int kernel_type, int /*degree*/, int nk64) {
+    const int max_nk64 = (plane_mode == 2 && kernel_type != LSSVM_KERNEL_RBF) ? 8 : 6;  // (what tile_launch_f32v2ws.hip instantiates)
+    return (plane_mode == 1 || plane_mode == 2) && nk64 >= 3 && nk64 <= max_nk64;
+}
+
 /* first row block of rank r when the lower triangle is dealt by equal area: tiles * sqrt(r / world), rounded to an EVEN block index -- the
  * 256-row workgroups of lssvm_tile_f32_pair.hip.hpp work on the block pairs (2p, 2p + 1), which must not straddle two devices (every symmetric
  * partition follows the rule, whichever kernel runs: one partition per problem shape) */
@@ -1289,13 +1299,19 @@ bool Problem<T>::pair_kernel_applies() const {
         return world_ == 1 && sym_ && dc_.p != nullptr && !wide_nl_ && !wide_linear_ && num_ib_ > 0
                && pair_kernel_routed(tile_params_.kernel_type, tile_params_.degree, X_.ldx / F64_KC);
     } else {
-        return false;
+        // the symmetric one-pass 128-row split kernels beyond 128 features: the polynomial forms (the linear kernel where it runs as the polynomial of degree 1) and
+        // rbf with folded records -- the forms s6w_body<..., SYM, ..., NV = 2> has
+        const bool poly = tile_params_.kernel_type == LSSVM_KERNEL_POLYNOMIAL && tile_params_.degree >= 0;
+        const bool rbf_folded = tile_params_.kernel_type == LSSVM_KERNEL_RBF && dc_folded_;
+        return world_ == 1 && sym_ && dc_.p != nullptr && num_ib_ > 0 && !pair_ && !wide_nl_ && !wide_linear_ && !rbf_direct_ && !rbf_grid_ && !row_scaled_
+               && (planes_.mode == 1 || planes_.mode == 2) && planes_.ldx16 / 64 >= 3 && (poly || rbf_folded)
+               && sym_pair_routed(planes_.mode, tile_params_.kernel_type, tile_params_.degree, planes_.ldx16 / 64);
     }
 }
 
 template <typename T>
 void Problem<T>::enqueue_apply_K_lanes(const T *v0, T *Kv0, const T *v1, T *Kv1, hipEvent_t ev_begin, hipEvent_t ev_end) {
-    if constexpr (std::is_same_v<T, double>) {
+    {
         LSSVM_REQUIRE(pair_kernel_applies(), "no two-vector tile kernel on this problem");
         hipStream_t st = stream_.s;
         const int ncols = num_tiles_ * TILE;
@@ -1304,11 +1320,16 @@ void Problem<T>::enqueue_apply_K_lanes(const T *v0, T *Kv0, const T *v1, T *Kv1,
         TileArgs<T> a = tile_args(v0);
         if (v1 != nullptr) {
             if (pair_dc_.p == nullptr) {
-                pair_dc_.alloc_zero(static_cast<size_t>(num_tiles_) * 2 * 192, st);  // (d0_j | d1_j | c_j): 192 reals per 64-column sub-tile
+                // fp64: (d0_j | d1_j | c_j), 192 reals per 64-column sub-tile; fp32: (w0_j | w1_j | e_j), 384 per column tile (folded rbf; the polynomial forms use 256 of them)
+                pair_dc_.alloc_zero(static_cast<size_t>(num_tiles_) * 2 * 192, st);
                 pair_partial_.alloc_zero(2 * partial_.count, st);
                 pair_colslab_.alloc_zero(2 * colslab_.count, st);
             }
-            hipLaunchKernelGGL(k_pack_dc2_f64, dim3((nthreads + 255) / 256), dim3(256), 0, st, v0, v1, c_.p, ncols, pair_dc_.p, Kv0, Kv1, nzero);
+            if constexpr (std::is_same_v<T, float>) {
+                hipLaunchKernelGGL(k_pack_dc2_sym, dim3((nthreads + 255) / 256), dim3(256), 0, st, v0, v1, c_.p, ncols, pair_dc_.p, a.dc_folded, Kv0, Kv1, nzero);
+            } else {
+                hipLaunchKernelGGL(k_pack_dc2_f64, dim3((nthreads + 255) / 256), dim3(256), 0, st, v0, v1, c_.p, ncols, pair_dc_.p, Kv0, Kv1, nzero);
+            }
             a.nvec = 2;
             a.dvec1 = v1;
             a.dc = pair_dc_.p;
@@ -1318,7 +1339,11 @@ void Problem<T>::enqueue_apply_K_lanes(const T *v0, T *Kv0, const T *v1, T *Kv1,
             a.colslab_vstride = static_cast<long>(colslab_.count);
         } else {
             d_packed_ = false;  // (dc_ is about to hold another vector's records)
-            hipLaunchKernelGGL(k_pack_dc_f64, dim3((nthreads + 255) / 256), dim3(256), 0, st, v0, c_.p, ncols, dc_.p, Kv0, nzero);
+            if constexpr (std::is_same_v<T, float>) {
+                hipLaunchKernelGGL(k_pack_dc, dim3((nthreads + 255) / 256), dim3(256), 0, st, v0, c_.p, ncols, dc_.p, a.dc_folded, Kv0, nzero, static_cast<const float *>(nullptr));
+            } else {
+                hipLaunchKernelGGL(k_pack_dc_f64, dim3((nthreads + 255) / 256), dim3(256), 0, st, v0, c_.p, ncols, dc_.p, Kv0, nzero);
+            }
         }
         const int nrows = num_ib_ * TILE;
         T *const Kv[2] = { Kv0, Kv1 };
@@ -1334,7 +1359,11 @@ void Problem<T>::enqueue_apply_K_lanes(const T *v0, T *Kv0, const T *v1, T *Kv1,
             if (&band == &bands_.back() && ev_end != nullptr) LSSVM_HIP_CHECK(hipEventRecord(ev_end, st));
             if (band.ib_end > 1) {
                 for (int u = 0; u < nv; ++u) {
-                    hipLaunchKernelGGL((k_reduce_colslab<T, 64>), dim3(2 * (band.ib_end - 1)), dim3(1024), 0, st, a.colslab + u * a.colslab_vstride, band.pair_origin, band.ib_begin, band.ib_end, 1, Kv[u]);
+                    if constexpr (std::is_same_v<T, float>) {  // (records per column tile; fp64: per 64-column sub-tile)
+                        hipLaunchKernelGGL((k_reduce_colslab<T, 128>), dim3(band.ib_end - 1), dim3(1024), 0, st, a.colslab + u * a.colslab_vstride, band.pair_origin, band.ib_begin, band.ib_end, 1, Kv[u], static_cast<const T *>(nullptr));
+                    } else {
+                        hipLaunchKernelGGL((k_reduce_colslab<T, 64>), dim3(2 * (band.ib_end - 1)), dim3(1024), 0, st, a.colslab + u * a.colslab_vstride, band.pair_origin, band.ib_begin, band.ib_end, 1, Kv[u]);
+                    }
                 }
             }
         }
@@ -1342,9 +1371,6 @@ void Problem<T>::enqueue_apply_K_lanes(const T *v0, T *Kv0, const T *v1, T *Kv1,
             hipLaunchKernelGGL(k_reduce_partials_sym<T>, dim3((nrows + 255) / 256), dim3(256), 0, st, a.partial + u * a.part_vstride, a.part_stride, jc_tiles_, jc_head_tiles_, jc_head_count_, ib_begin_, nrows, Kv[u], 1);
         }
         LSSVM_HIP_CHECK(hipGetLastError());
-    } else {
-        (void) v0, (void) Kv0, (void) v1, (void) Kv1, (void) ev_begin, (void) ev_end;
-        throw Error(LSSVM_ERR_INTERNAL, "lanes exist in fp64 only");
     }
 }
 

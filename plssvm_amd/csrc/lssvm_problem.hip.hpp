@@ -406,7 +406,8 @@ class Problem {
      * problem; the own state is not involved. ---- */
     CgState<T> &lane(size_t k);
     /* where one Gram pass can serve two vectors: the fp64 symmetric v2 kernel on an unsharded problem without feature panels -- and only the (kernel function, chunk
-     * count) instantiations whose two-vector pass was measured faster than two single passes (profiles/lockstep_f64.json) */
+     * count) instantiations whose two-vector pass was measured faster than two single passes (profiles/lockstep_f64.json); fp32: the symmetric one-pass 128-row split
+     * kernels on 129 ... 512 features, polynomial or rbf with folded records (sym_pair_routed, profiles/lockstep_f32_wide.json) */
     bool pair_kernel_applies() const;
     /* Kv0 <- K * v0 and, with v1, Kv1 <- K * v1 from ONE pass of the two-vector kernel (pair_kernel_applies; the caller falls back to two calls elsewhere); without v1
      * today's single-vector pass.  Each result has the bits enqueue_apply_K_local gives for that vector.  `ev`: HIP events around the tile-kernel launches, or NULL. */
@@ -460,7 +461,7 @@ class Problem {
     DevBuf<T> partial_;
     DevBuf<T> dc_;  // v2 kernels: packed (d_j | c_j) records
     std::vector<std::unique_ptr<CgState<T>>> lanes_;
-    DevBuf<T> pair_dc_, pair_partial_, pair_colslab_;  // two-vector passes: (d0_j | d1_j | c_j) records, and both vectors' planes of the row slabs / the column slab
+    DevBuf<T> pair_dc_, pair_partial_, pair_colslab_;  // two-vector passes: (d0_j | d1_j | c_j) records (fp32: k_pack_dc2_sym's), and both vectors' planes of the row slabs / the column slab
     bool d_packed_ = false;  // dc_ holds the records of own_.d and K*v is cleared: k_update_d left them (pack_for_d), the next implicit matvec of that d launches no k_pack_dc
     // symmetric variant
     bool sym_ = false;
@@ -783,6 +784,7 @@ T rbf_prescale(const lssvm_params &p, bool fp64_v2);
 bool wide_nonlinear_f64(const Options &o, const lssvm_params &p, size_t num_features);
 bool wide_nonlinear(const Options &o, const lssvm_params &p, bool rbf_direct, size_t num_features);
 bool wide_pair_routed(int plane_mode, int kernel_type, int degree, int nk64);  // the resident fp32 predictor beyond 128 features: one two-vector launch for a pair?
+bool sym_pair_routed(int plane_mode, int kernel_type, int degree, int nk64);   // the fp32 lockstep CG on 129 ... 512 features: one symmetric two-vector launch for a pair of right-hand sides?
 template <typename T>
 void set_kernel_scalars(TileArgs<T> &a, const lssvm_params &p, bool rbf_direct);
 template <typename T>

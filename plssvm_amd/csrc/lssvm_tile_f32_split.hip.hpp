@@ -53,11 +53,22 @@ __device__ __forceinline__ f32x4 plane_mfma(const bf16x8 &av, const bf16x8 &bv, 
  * evaluated once per element and feeds two scalar fma chains, and the row sums of vector v go to plane v of `partial` (TileArgs::part_vstride apart).  Per vector
  * the chain of operations is the one of NV = 1.  Only where the full-square kernel does not read the record's second half itself: not the unfolded rbf form (c_j)
  * and not the grid planes (sigma^2 ch_j).
+ *
+ * NV = 2 in the SYMMETRIC variant (compiler-scheduled groups beyond 128 features, tile_launch_f32v2ws.hip: the lockstep CG's pair of right-hand sides): the polynomial
+ * forms and folded rbf.  The second vector's d_i is a second plane of `dis` (TileArgs::dvec1), its mirrored column sums a second plane of `colred` and of the slab
+ * (TileArgs::colslab_vstride).  Folded rbf multiplies a column sum by the column's factor 2^c_j, which then has no free half of the record to sit in: its record
+ * is (2^c_j d0_j | 2^c_j d1_j | 2^c_j), 384 floats, fetched by 24 lanes of the ONE LDS-DMA instruction per wave (k_pack_dc2_sym) -- the counted waits stay.  The
+ * record slots are 1.5 KiB apart for every such instance (V2S_LDS_BYTES); the single-vector kernels keep their image byte for byte.
  */
 template <int KT, int NK64, bool SYM, bool HAND, int PL, int NV = 1>
 __device__ __forceinline__ void s6w_body(const TileArgs<float> &a) {
     static_assert(PL == 3 || PL == 2, "three bf16 planes (bf16x6) or two f16 planes (f16x3)");
-    static_assert(NV == 1 || (NV == 2 && !SYM && KT != KT_RBF && KT != KT_RBFG), "two weight vectors per pass: full square, and the second half of the record must be free");
+    static_assert(NV == 1 || (NV == 2 && KT != KT_RBF && KT != KT_RBFG), "two weight vectors per pass: the second half of the record must be free");
+    static_assert(NV == 1 || !SYM || (!HAND && (KT == KT_POLY || KT == KT_POLY2 || KT == KT_POLY3 || KT == KT_RBFF)),
+                  "two weight vectors per symmetric pass: compiler-scheduled groups, polynomial forms and folded rbf");
+    constexpr bool V2S = SYM && NV == 2;
+    constexpr int REC_FLOATS = (V2S && KT == KT_RBFF) ? 384 : 256;  // a column tile's record: (d_j | c_j), (d0_j | d1_j), or -- two vectors, symmetric, folded rbf -- (w0_j | w1_j | e_j)
+    constexpr int REC_SLOT = V2S ? V2S_REC_SLOT_BYTES : 1024;       // bytes between the record slots in LDS
     constexpr bool F16 = PL == 2;
     // KT_RBFG ("grid planes", round 5; f16, hand-scheduled groups only): THREE column planes (h | s1 | s2, all carrying the scale sigma) and FOUR phases per tile, each
     // over all 64-feature chunks:   0: h x h      1: h x (s1, s2)      2: s1 x (h, s1)      3: s2 x h      (column plane x row planes)
@@ -87,10 +98,10 @@ __device__ __forceinline__ void s6w_body(const TileArgs<float> &a) {
     };
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     char *ring = smem_raw;                                                          // [V2_RING][128 rows][128 B]
-    char *dcs = smem_raw + V2_RING * V2_SLOT_BYTES;                                 // [V2_DC_SLOTS][256 floats]
-    float *cis = reinterpret_cast<float *>(dcs + V2_DC_SLOTS * 1024);               // [128] c_i of the row panel (rbf)
-    float *dis = cis + TILE;                                                        // [128] d_i of the row panel (SYM)
-    float *colred = dis + TILE;                                                     // [2][4 waves][128] column sums of a tile (SYM)
+    char *dcs = smem_raw + V2_RING * V2_SLOT_BYTES;                                 // [V2_DC_SLOTS][256 floats] (V2S: slots of 384 floats)
+    float *cis = reinterpret_cast<float *>(dcs + V2_DC_SLOTS * REC_SLOT);           // [128] c_i of the row panel (rbf)
+    float *dis = cis + TILE;                                                        // [128] d_i of the row panel (SYM; V2S: [2 vectors][128])
+    float *colred = dis + (V2S ? 2 : 1) * TILE;                                     // [2][4 waves][128] column sums of a tile (SYM; V2S: [2 vectors][2][4 waves][128])
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -132,6 +143,9 @@ __device__ __forceinline__ void s6w_body(const TileArgs<float> &a) {
     }
     if constexpr (SYM) {
         if (tid < TILE) dis[tid] = GRID ? a.dvec[row0 + tid] * a.er[row0 + tid] : a.dvec[row0 + tid];  // (grid planes: the row's folded factor E_i rides on d_i)
+        if constexpr (V2S) {
+            if (tid >= TILE) dis[tid] = a.dvec1[row0 + tid - TILE];
+        }
     }
     // make the compiler retire these ordinary loads HERE, before any LDS-DMA is in flight
 #pragma unroll
@@ -151,7 +165,7 @@ __device__ __forceinline__ void s6w_body(const TileArgs<float> &a) {
     }
     const unsigned ring_lds = static_cast<unsigned>(reinterpret_cast<size_t>(ring));  // the low half of a generic LDS address is the LDS address
     const unsigned dma_lds = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(ring_lds + static_cast<unsigned>(wave) * 4096u)));  // this wave's quarter of ring slot 0
-    const unsigned dc_lds = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(ring_lds + V2_RING * V2_SLOT_BYTES + static_cast<unsigned>(wave) * 256u)));  // this wave's quarter of record slot 0
+    const unsigned dc_lds = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(ring_lds + V2_RING * V2_SLOT_BYTES + static_cast<unsigned>(wave) * static_cast<unsigned>(REC_FLOATS))));  // this wave's quarter of record slot 0
     auto issue_chunk = [&](int step) {
         if (LSSVM_DBG(a, 16) && step > 3) return;  // ablation: no DMA after the prologue
         const int t = LSSVM_DBG(a, 1) ? 0 : step / NKC;  // ablation bit 1: always the same (L2-resident) tile
@@ -189,9 +203,10 @@ __device__ __forceinline__ void s6w_body(const TileArgs<float> &a) {
         }
     };
     auto issue_dc = [&](int t) {
-        if (lane < 16) {
-            const char *src = sgpr_ptr(a.dc + static_cast<size_t>(jt_begin + t) * 256) + __builtin_amdgcn_readfirstlane(wave * 256);
-            lds_dma16<0>(16u * (lane_off(threadIdx.x) & 15u), sgpr_ptr(src), static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(dc_lds + static_cast<unsigned>(t % V2_DC_SLOTS) * 1024u))));
+        // each wave fetches its quarter of the record: 16 lanes x 16 bytes (records of 384 floats: 24 lanes), lane-linear in LDS
+        if (lane < REC_FLOATS / 16) {
+            const char *src = sgpr_ptr(a.dc + static_cast<size_t>(jt_begin + t) * REC_FLOATS) + __builtin_amdgcn_readfirstlane(wave * REC_FLOATS);
+            lds_dma16<0>(16u * (lane_off(threadIdx.x) & (REC_FLOATS == 384 ? 31u : 15u)), sgpr_ptr(src), static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(dc_lds + static_cast<unsigned>(t % V2_DC_SLOTS) * static_cast<unsigned>(REC_SLOT)))));
         }
     };
 
@@ -278,7 +293,15 @@ __device__ __forceinline__ void s6w_body(const TileArgs<float> &a) {
     };
 
     auto flush_cols = [&](int t) {
-        if (tid < TILE) {
+        if constexpr (V2S) {
+            // waves 0, 1: the first vector's 128 columns; waves 2, 3: the second vector's, from its plane of colred into its plane of the slab (per vector the sum below)
+            const int v = wave >> 1;
+            const float *cr_ = colred + v * 1024 + (t & 1) * 512;
+            const int c = tid & (TILE - 1);
+            const float sum = (cr_[c] + cr_[128 + c]) + (cr_[256 + c] + cr_[384 + c]);
+            auto *rec = (__attribute__((address_space(1))) float *) const_cast<char *>(sgpr_ptr(a.colslab + static_cast<size_t>(v) * a.colslab_vstride + (rec0 + jt_begin + t) * TILE));
+            rec[lane_off(static_cast<unsigned>(c))] = sum;
+        } else if (tid < TILE) {
             const float *cr_ = colred + (t & 1) * 512;
             const float sum = (cr_[tid] + cr_[128 + tid]) + (cr_[256 + tid] + cr_[384 + tid]);
             // uniform base in SGPRs + 32-bit lane offset (a 64-bit per-lane pointer would be hoisted out of the tile loop and spilled)
@@ -294,7 +317,7 @@ __device__ __forceinline__ void s6w_body(const TileArgs<float> &a) {
         {
             // (d_j is read from the record in the epilogue, c_j only here: neither lives in registers across the MFMA steps -- this kernel
             // has no register to spare, and a scratch reload in the loop drains the LDS-DMA queue with its vmcnt(0))
-            const float *dcr = reinterpret_cast<const float *>(dcs + (t % V2_DC_SLOTS) * 1024);
+            const float *dcr = reinterpret_cast<const float *>(dcs + (t % V2_DC_SLOTS) * REC_SLOT);
             if constexpr (KT == KT_POLY) {
 #pragma unroll
                 for (int cb = 0; cb < 8; ++cb) padcol[cb] = (a.degree < 0) && ((jt_begin + t) * TILE + cb * 16 + r >= a.ncols_valid);
@@ -436,16 +459,19 @@ __device__ __forceinline__ void s6w_body(const TileArgs<float> &a) {
         if (!LSSVM_DBG(a, 4)) {
             auto epilogue = [&](auto with_cols) {
                 constexpr bool COLS = decltype(with_cols)::value;
-                f32x4 di[2];
+                constexpr int NC = SYM ? NV : 1;  // vectors with mirrored column sums
+                f32x4 di[NC][2];
                 using f32x2 = float __attribute__((ext_vector_type(2)));
-                float colacc[8];
-                f32x2 colacc2[8] = {};  // even / odd rows of the lane's four, added at the end
+                float colacc[NC][8];
+                f32x2 colacc2[NC][8] = {};  // even / odd rows of the lane's four, added at the end
                 f32x2 kvp = { 0.f, 0.f };
                 if constexpr (COLS) {
 #pragma unroll
-                    for (int rb = 0; rb < 2; ++rb) di[rb] = *reinterpret_cast<const f32x4 *>(dis + wave * 32 + 16 * rb + 4 * g);
+                    for (int v = 0; v < NC; ++v)
+#pragma unroll
+                        for (int rb = 0; rb < 2; ++rb) di[v][rb] = *reinterpret_cast<const f32x4 *>(dis + v * TILE + wave * 32 + 16 * rb + 4 * g);
                 }
-                const float *dcr = reinterpret_cast<const float *>(dcs + (t % V2_DC_SLOTS) * 1024);  // the record stays valid until tile t + 4 is announced
+                const float *dcr = reinterpret_cast<const float *>(dcs + (t % V2_DC_SLOTS) * REC_SLOT);  // the record stays valid until tile t + 4 is announced
 #pragma unroll
                 for (int cb = 0; cb < 8; ++cb) {
                     float djv[NV];
@@ -474,29 +500,45 @@ __device__ __forceinline__ void s6w_body(const TileArgs<float> &a) {
                             if constexpr (COLS) {
                                 kvp[e & 1] = kv;
                                 if (e & 1) {
-                                    const f32x2 dip = { di[rb][e - 1], di[rb][e] };
-                                    colacc2[cb] = __builtin_elementwise_fma(kvp, dip, colacc2[cb]);
+#pragma unroll
+                                    for (int v = 0; v < NC; ++v) {
+                                        const f32x2 dip = { di[v][rb][e - 1], di[v][rb][e] };
+                                        colacc2[v][cb] = __builtin_elementwise_fma(kvp, dip, colacc2[v][cb]);
+                                    }
                                 }
                             }
                         }
-                }
-                if constexpr (COLS) {
+                    if constexpr (COLS && V2S) {  // (two vectors: a block's pair of sums is folded as soon as the block is done -- 16 registers less across the epilogue)
 #pragma unroll
-                    for (int cb = 0; cb < 8; ++cb) colacc[cb] = colacc2[cb][0] + colacc2[cb][1];
+                        for (int v = 0; v < NC; ++v) {
+                            colacc[v][cb] = colacc2[v][cb][0] + colacc2[v][cb][1];
+                            asm("" : "+v"(colacc[v][cb]));
+                        }
+                    }
+                }
+                if constexpr (COLS && !V2S) {
+#pragma unroll
+                    for (int v = 0; v < NC; ++v)
+#pragma unroll
+                        for (int cb = 0; cb < 8; ++cb) colacc[v][cb] = colacc2[v][cb][0] + colacc2[v][cb][1];
                 }
                 if constexpr (COLS) {
                     // the four lane groups hold different rows of the same column: two butterfly steps on the vector ALU (no LDS round trips) for
                     // all eight blocks at once (column_sums_of_8_blocks: 6 swaps + 6 adds); the sums come out one column per lane -- block q in
                     // lane group q of colacc[0], block 4 + q in colacc[4] -- so the record's factor and the store are two instructions of the
                     // whole wave and the epilogue is a single basic block without a branch
-                    float *cw = colred + (t & 1) * 512 + wave * 128;
-                    column_sums_of_8_blocks(colacc);
+                    // (two vectors: the same steps per vector, into that vector's plane of colred; the factor sits behind BOTH vectors' halves of the record)
 #pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        float v = colacc[4 * h];
-                        if constexpr (KT == KT_RBFF) v *= dcr[128 + 64 * h + lane];  // K_ij = 2^acc * 2^c_j: the column's factor once per column
-                        if constexpr (KT == KT_LINEAR && F16) v *= a.out_scale;  // planes pre-scaled by 2^k: undo 2^(2k) (exact)
-                        cw[64 * h + lane] = v;
+                    for (int u = 0; u < NC; ++u) {
+                        float *cw = colred + u * 1024 + (t & 1) * 512 + wave * 128;
+                        column_sums_of_8_blocks(colacc[u]);
+#pragma unroll
+                        for (int h = 0; h < 2; ++h) {
+                            float v = colacc[u][4 * h];
+                            if constexpr (KT == KT_RBFF) v *= dcr[NC * TILE + 64 * h + lane];  // K_ij = 2^acc * 2^c_j: the column's factor once per column
+                            if constexpr (KT == KT_LINEAR && F16) v *= a.out_scale;  // planes pre-scaled by 2^k: undo 2^(2k) (exact)
+                            cw[64 * h + lane] = v;
+                        }
                     }
                 }
             };
@@ -582,6 +624,12 @@ __global__ __launch_bounds__(TILE_THREADS, 1) void tile_matvec_f32_s6w_nv2w(cons
     static_assert(NK64 > 2 && NK64 <= 6, "the wide two-vector bf16x6 kernel: 3 ... 6 chunks of 64 features");
     s6w_body<KT, NK64, false, false, 3, 2>(a);
 }
+/* ... and its symmetric counterpart (tile_launch_f32v2ws.hip: two right-hand sides of the lockstep CG per pass; V2S_LDS_BYTES of dynamic LDS) */
+template <int KT, int NK64>
+__global__ __launch_bounds__(TILE_THREADS, 1) void tile_matvec_f32_s6w_nv2s(const TileArgs<float> a) {
+    static_assert(NK64 > 2 && NK64 <= 6, "the wide two-vector bf16x6 kernel: 3 ... 6 chunks of 64 features");
+    s6w_body<KT, NK64, true, false, 3, 2>(a);
+}
 /* "f16x3": the same kernels on TWO f16 planes (x = hi + mid, 11 + 11 significant bits, k_split_f16x2) and the three plane products
  * hi*hi + hi*mid + mid*hi on v_mfma_f32_16x16x32_f16 -- half the matrix-core work of bf16x6 and two thirds of its column stream.  What is
  * dropped (mid*mid and the split remainder) is below 2^-23 |x||y| per product while the planes stay in f16's normal range, which the set-up
@@ -625,6 +673,11 @@ template <int KT, int NK64>
 __global__ __launch_bounds__(TILE_THREADS, 1) void tile_matvec_f32_f3w_nv2w(const TileArgs<float> a) {
     static_assert(NK64 > 2 && NK64 <= f16_max_nk64(KT), "the wide two-vector f16x3 kernel: 3 chunks of 64 features up to the row panel the register file holds");
     s6w_body<KT, NK64, false, false, 2, 2>(a);
+}
+template <int KT, int NK64>
+__global__ __launch_bounds__(TILE_THREADS, 1) void tile_matvec_f32_f3w_nv2s(const TileArgs<float> a) {
+    static_assert(NK64 > 2 && NK64 <= f16_max_nk64(KT), "the wide two-vector f16x3 kernel: 3 chunks of 64 features up to the row panel the register file holds");
+    s6w_body<KT, NK64, true, false, 2, 2>(a);
 }
 
 }  // namespace lssvm

@@ -90,8 +90,9 @@ struct TileArgs {
     T coef0;          // polynomial
     long part_vstride; // rectangular 256-row kernel with two weight vectors per pass: elements between the two vectors' planes of `partial` (>= num_jc * part_stride)
     int nvec;         // host side only: weight vectors this launch evaluates (0 / 1 = one; 2 = the two-vector instance of the rectangular 256-row kernel or of the 128-row full-square split kernels, records from k_pack_dc2;
-                      // fp64: of the symmetric v2 kernel, records from k_pack_dc2_f64)
-    const T *dvec1;   // fp64 symmetric v2 kernel with two vectors per pass: the second vector (its d_i; its d_j travel in the records)
+                      // with a work-item list, fp32: of the symmetric 128-row split kernels beyond 128 features, records from k_pack_dc2_sym; fp64: of the symmetric v2 kernel,
+                      // records from k_pack_dc2_f64)
+    const T *dvec1;   // symmetric kernels with two vectors per pass (fp64 v2, fp32 128-row split): the second vector (its d_i; its d_j travel in the records)
     long colslab_vstride;  // ... elements between the two vectors' planes of `colslab`
 };
 

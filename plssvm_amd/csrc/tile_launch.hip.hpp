@@ -57,6 +57,9 @@ void launch_rect2_tile_kernel(const TileArgs<float> &a, int kernel_type, hipStre
 void launch_nv2_tile_kernel(const TileArgs<float> &a, int kernel_type, dim3 grid, hipStream_t s);
 /* ... beyond 128 features (tile_launch_f32v2w.hip; reached through launch_nv2_tile_kernel) */
 void launch_nv2_wide_tile_kernel(const TileArgs<float> &a, int kernel_type, dim3 grid, hipStream_t s);
+/* the 128-row SYMMETRIC split kernels with two vectors per pass, 129 ... 512 features (tile_launch_f32v2ws.hip, built as its _f16 / _bf16 halves; TileArgs::nvec == 2 with a work-item list, reached
+ * through launch_tile_kernel<float>) */
+void launch_nv2_sym_wide_tile_kernel(const TileArgs<float> &a, int kernel_type, hipStream_t s);
 /* rbf / polynomial on more features than a row panel in registers holds (tile_launch_f32x.hip): feature panels inside a tile */
 void launch_wide_tile_kernel(const TileArgs<float> &a, int kernel_type, dim3 grid, hipStream_t s);
 /* fp64 rbf / polynomial on more than 256 features (tile_launch_f64x.hip): feature panels of 64 inside a sub-tile */

@@ -221,8 +221,8 @@ class MI355CSVM(CSVM):
     def solve_systems_of_linear_equations(self, params, A, B, eps, max_iter, sample_weight=None):
         """The systems in LOCKSTEP on ONE resident problem (``ResidentProblem.solve_lockstep``): the data is uploaded and prepared (q, operand planes) once, the weights are
         set once, and every right-hand side runs the recipe of the one-shot solve (begin / step / finish) on it -- the same alpha, rho and iteration count as a fresh
-        one-shot solve.  In fp64 on the symmetric resident-row-panel kernel one pass over the Gram tiles serves two right-hand sides per iteration; elsewhere they are solved
-        one after the other.  Several devices: the base class's loop of one-shot solves."""
+        one-shot solve.  In fp64 on the symmetric resident-row-panel kernel, and in fp32 on 129 ... 512 features (polynomial, or rbf with folded records, on the symmetric
+        one-pass split kernels), one pass over the Gram tiles serves two right-hand sides per iteration; elsewhere they are solved one after the other.  Several devices: the base class's loop of one-shot solves."""
         self.last_refine_info = None
         if self.use_devices != 1:
             return super().solve_systems_of_linear_equations(params, A, B, eps, max_iter, sample_weight=sample_weight)
