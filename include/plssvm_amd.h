@@ -411,6 +411,45 @@ int lssvm_mi355_problem_matvec_pair(lssvm_mi355_problem *p, const void *d0, cons
 int lssvm_mi355_problem_solve_lockstep(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out /* num_rhs x N */,
                                        double *rhos_out, lssvm_cg_info *infos_out /* num_rhs, may be NULL */, uint64_t passes_out[2]);
 
+/* COST PATH (no counterpart in the reference): the solutions of ONE right-hand side for EVERY cost of a grid from one multi-shift CG sequence -- one pass over the
+ * Gram tiles per iteration for the whole grid instead of one per cost, as many iterations as the hardest (largest) cost alone needs.  For fixed data and kernel
+ * function the cost enters the reduced system only as a shift: Abar(C) = A0 + sigma M with sigma = 1 / C, A0 v = K v + (k_NN S - q.v) 1 - S q (S = sum v) and
+ * M = I + 1 1^T.  With P = M^(-1/2) = I - theta 1 1^T, theta = (1 - 1 / sqrt(N)) / (N - 1), the systems (P A0 P + sigma_s I) z_s = P b are shifted systems of one
+ * matrix and one right-hand side; they share the Krylov space of the seed sigma_0 = min sigma_s, whose CG iteration (from z = 0) is run, and every other cost follows
+ * by scalar recurrences and two vector updates.  x_s = P z_s; alpha_s[N-1] = -sum x_s and rho_s = -(y_N + (k_NN + sigma_s) sum x_s - q.x_s).
+ * THE STOP TEST IS NOT THE ONE OF lssvm_mi355_solve_*.  Those start from x0 = 1 and stop at |r|^2 <= eps^2 |b - A 1|^2 in the plain 2-norm.  The path starts from
+ * x0 = 0 and stops cost s at |P r_s|^2 <= eps^2 |P b|^2: the residual in the norm of M^-1, relative to the right-hand side in that norm.  DO NOT CARRY AN eps OVER FROM
+ * lssvm_mi355_solve_*: the same eps asks the path for an accuracy that can be ORDERS OF MAGNITUDE stricter.  |b - A 1| is large where the Gram matrix has large row
+ * sums, so the one-shot test is met early: measured on 50 000 x 128 rbf blobs, one-shot solves at eps 1e-3 ... 1e-6 stopped after a handful of iterations with true
+ * residuals of 1e-2 ... 1 in the path's measure (above 1 at C = 0.1), where the path goes on until it reaches eps itself -- and takes a multiple of the time at the
+ * same eps.  Choose the path's eps as the relative residual that is wanted; iteration counts of the two are not comparable.
+ * The residual of a cost is known through the recurrence only (zeta_s^2 r^T r).  With verify != 0 the call evaluates the TRUE residual b - Abar(sigma_s) x_s of every
+ * cost afterwards, one Gram pass per cost -- two costs per pass where lssvm_mi355_problem_matvec_pair has a two-vector pass -- and reports it in the same norm;
+ * verified = 1 where true_residuum <= 4 target_residuum (twice the norm).  Nothing is repaired or hidden: in float, a system whose ridge lies below float's
+ * resolution (the linear kernel on few features at large costs) drifts, and the caller sees converged = 1, verified = 0 and both numbers.
+ * y: N values of the problem's dtype.  costs: num_costs values (1 ... 64), each finite and > 0, in any order, duplicates allowed; row s of alphas_out
+ * (num_costs x N, the problem's dtype), rhos_out[s] and infos_out[s] belong to costs[s].  The cost of the problem's lssvm_params is ignored, and the problem is left
+ * as it was.  passes_out (may be NULL): [0] Gram passes of the iteration (= the seed's iterations), [1] Gram passes of the verification.  Deterministic: fixed-order
+ * reductions, the same bits for the same arguments, and a permuted cost list gives the permuted rows.  max_iter bounds the iterations; costs still active then come
+ * back with converged = 0 and their current iterate.
+ * LSSVM_ERR_INVALID_ARGUMENT: a problem on several devices or ranks, weights set on the problem, a call between cg_begin and cg_finish; and, before any device
+ * work, num_costs == 0 or > 64, a cost that is not finite and > 0, eps <= 0 (or not finite), max_iter == 0, a NULL y / costs / alphas_out / rhos_out / infos_out. */
+typedef struct lssvm_path_info {
+    uint64_t iterations;                                   /* at which this cost froze (max_iter where it did not) */
+    int32_t  converged, verified;
+    double   initial_residuum, residuum, target_residuum;  /* squared, as lssvm_cg_info: |P b|^2, zeta_s^2 |r|^2 when it froze, eps^2 |P b|^2 */
+    double   true_residuum;                                /* |P (b - Abar(sigma_s) x_s)|^2; -1 without verify */
+} lssvm_path_info;
+int lssvm_mi355_problem_solve_cost_path(lssvm_mi355_problem *p, const void *y, const double *costs, size_t num_costs, double eps, uint64_t max_iter, int verify,
+                                        void *alphas_out /* num_costs x N */, double *rhos_out, lssvm_path_info *infos_out, uint64_t passes_out[2]);
+/* one-shot: create the problem on device 0 (as lssvm_mi355_solve_*), solve the path, destroy it; params->cost is ignored */
+int lssvm_mi355_solve_cost_path_f32(const lssvm_params *params, const float *X, size_t num_points, size_t num_features, const float *y, const double *costs,
+                                    size_t num_costs, double eps, uint64_t max_iter, int verify, float *alphas_out, double *rhos_out,
+                                    lssvm_path_info *infos_out, uint64_t passes_out[2], const lssvm_mi355_options *options);
+int lssvm_mi355_solve_cost_path_f64(const lssvm_params *params, const double *X, size_t num_points, size_t num_features, const double *y, const double *costs,
+                                    size_t num_costs, double eps, uint64_t max_iter, int verify, double *alphas_out, double *rhos_out,
+                                    lssvm_path_info *infos_out, uint64_t passes_out[2], const lssvm_mi355_options *options);
+
 /* CG, csvm.cpp:89-111: b = y[0..n) - y[n], x = 1, r = b - A x, delta0, d = r */
 int lssvm_mi355_cg_begin(lssvm_mi355_problem *p, const void *y, double eps);
 /* run at most `iterations` further CG iterations (csvm.cpp:125-166); stops early when delta <= eps^2 delta0.

@@ -39,6 +39,7 @@ EXPORTED_SYMBOLS = [
     "lssvm_mi355_shard_blocks", "lssvm_mi355_set_shard_weights", "lssvm_mi355_problem_rebalance", "lssvm_mi355_comm_get_unique_id", "lssvm_mi355_comm_init", "lssvm_mi355_comm_destroy",
     "lssvm_mi355_problem_create", "lssvm_mi355_problem_create_multi", "lssvm_mi355_problem_ipc_export", "lssvm_mi355_problem_ipc_connect", "lssvm_mi355_problem_destroy", "lssvm_mi355_problem_get_q", "lssvm_mi355_problem_matvec",
     "lssvm_mi355_problem_matvec_pair", "lssvm_mi355_problem_solve_lockstep",
+    "lssvm_mi355_problem_solve_cost_path", "lssvm_mi355_solve_cost_path_f32", "lssvm_mi355_solve_cost_path_f64",
     "lssvm_mi355_cg_begin", "lssvm_mi355_cg_step", "lssvm_mi355_cg_finish", "lssvm_mi355_problem_synchronize", "lssvm_mi355_problem_info",
     "lssvm_mi355_measure_bf16_mfma_ceiling", "lssvm_mi355_comm_library_path", "lssvm_mi355_set_io_threads", "lssvm_mi355_set_option", "lssvm_mi355_get_option",
     "lssvm_mi355_libsvm_open", "lssvm_mi355_libsvm_fill_f32", "lssvm_mi355_libsvm_fill_f64", "lssvm_mi355_libsvm_close",
@@ -79,6 +80,15 @@ class LssvmRefineInfo(C.Structure):
     _fields_ = [("refined", C.c_int32), ("took_over_f64", C.c_int32), ("outer_steps", C.c_uint64), ("inner_iterations", C.c_uint64), ("f64_cg_iterations", C.c_uint64),
                 ("f64_passes", C.c_uint64), ("f32_passes", C.c_uint64), ("initial_residuum", C.c_double), ("residuum", C.c_double), ("target_residuum", C.c_double),
                 ("f64_ms", C.c_double), ("f32_ms", C.c_double), ("total_ms", C.c_double), ("inner_gram_mode", C.c_int32), ("inner_rbf_direct", C.c_int32)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class LssvmPathInfo(C.Structure):
+    """``lssvm_path_info``: how one cost of a cost path (``lssvm_mi355_problem_solve_cost_path``) went; the residua are squared norms, ``true_residuum`` -1 without verify."""
+    _fields_ = [("iterations", C.c_uint64), ("converged", C.c_int32), ("verified", C.c_int32), ("initial_residuum", C.c_double), ("residuum", C.c_double),
+                ("target_residuum", C.c_double), ("true_residuum", C.c_double)]
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
@@ -164,6 +174,22 @@ def refined_entry():
     if fn.argtypes is None:
         fn.argtypes = [C.POINTER(LssvmParams), C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.c_double, C.c_uint64, C.c_void_p,
                        C.POINTER(C.c_double), C.POINTER(LssvmCgInfo), C.POINTER(LssvmRefineInfo), C.POINTER(C.c_uint64), C.c_void_p]
+        fn.restype = C.c_int
+    return fn
+
+
+PATH_MAX_COSTS = 64
+
+
+def cost_path_entry(name: str):
+    """``lssvm_mi355_problem_solve_cost_path`` / ``lssvm_mi355_solve_cost_path_f32 / _f64`` with its argument types.  Bound at the first call, like the weighted entry points."""
+    fn = getattr(lib, name)
+    if fn.argtypes is None:
+        tail = [C.c_void_p, C.POINTER(C.c_double), C.c_size_t, C.c_double, C.c_uint64, C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(LssvmPathInfo), C.POINTER(C.c_uint64)]
+        if name == "lssvm_mi355_problem_solve_cost_path":
+            fn.argtypes = [C.c_void_p] + tail
+        else:
+            fn.argtypes = [C.POINTER(LssvmParams), C.c_void_p, C.c_size_t, C.c_size_t] + tail + [C.c_void_p]
         fn.restype = C.c_int
     return fn
 

@@ -24,7 +24,7 @@ from ._capi import LssvmCgInfo, LssvmParams, LssvmPredictInfo, LssvmShard, Optio
 from .exceptions import InvalidParameterError
 from .parameter import Parameter
 
-__all__ = ["Options", "Predictor", "solve_system_of_linear_equations", "solve_refined", "predict_values", "predict_values_multi", "generate_q", "run_device_kernel", "calculate_w", "ResidentProblem",
+__all__ = ["Options", "Predictor", "solve_system_of_linear_equations", "solve_refined", "solve_cost_path", "predict_values", "predict_values_multi", "generate_q", "run_device_kernel", "calculate_w", "ResidentProblem",
            "comm_get_unique_id", "comm_init", "comm_destroy"]
 
 
@@ -149,6 +149,50 @@ def solve_refined(params: Parameter, A, B, eps: float, max_iter: int, sample_wei
     if single:
         return alphas[0], np.float64(rhos[0]), info_dicts[0], refine_dicts[0]
     return alphas, rhos, info_dicts, refine_dicts
+
+
+def _cost_path_arguments(y, N: int, dtype, costs, eps: float, max_iter: int):
+    """The arguments of a cost path as the library takes them, checked as it checks them (so that a bad one never reaches a device): ``(y, costs)``."""
+    y = np.ascontiguousarray(y, dtype=dtype)
+    if y.shape != (N,):
+        raise InvalidParameterError(f"The number of data points in the matrix A ({N}) and the values in the right hand side vector ({y.size}) must be the same!")
+    costs = np.ascontiguousarray(costs, dtype=np.float64)
+    if costs.ndim != 1 or costs.size == 0:
+        raise InvalidParameterError("The number of costs must be greater than 0!")
+    if costs.size > _capi.PATH_MAX_COSTS:
+        raise InvalidParameterError(f"A cost path takes at most {_capi.PATH_MAX_COSTS} costs, but got {costs.size}!")
+    if not (np.all(np.isfinite(costs)) and np.all(costs > 0.0)):
+        raise InvalidParameterError("Every cost of the path must be finite and greater than 0.0!")
+    if not (np.isfinite(eps) and eps > 0.0):
+        raise InvalidParameterError(f"The stopping criterion in the CG algorithm must be greater than 0.0, but is {eps}!")
+    if not int(max_iter) > 0:
+        raise InvalidParameterError("The number of CG iterations must be greater than 0!")
+    return y, costs
+
+
+def _cost_path_call(fn, head, y, costs, N: int, dtype, eps: float, max_iter: int, verify: bool, tail=()):
+    m = costs.size
+    alphas = np.zeros((m, N), dtype=dtype)
+    rhos = np.zeros(m, dtype=np.float64)
+    infos = (_capi.LssvmPathInfo * m)()
+    passes = (C.c_uint64 * 2)()
+    check(fn(*head, ptr(y), costs.ctypes.data_as(C.POINTER(C.c_double)), m, float(eps), int(max_iter), 1 if verify else 0, ptr(alphas), rhos.ctypes.data_as(C.POINTER(C.c_double)),
+             infos, passes, *tail))
+    return alphas, rhos.astype(dtype), [i.as_dict() for i in infos], (int(passes[0]), int(passes[1]))
+
+
+def solve_cost_path(params: Parameter, A, b, costs, eps: float, max_iter: int, verify: bool = True, options: Options | None = None):
+    """ONE right-hand side solved for EVERY cost of ``costs`` by one multi-shift CG sequence (``lssvm_mi355_solve_cost_path_*``): one pass over the Gram tiles per
+    iteration serves the whole grid.  ``params.cost`` is ignored.  Returns ``(alphas[m, N], rhos[m], infos, passes)``: row ``s`` belongs to ``costs[s]``, ``infos`` one
+    ``lssvm_path_info`` dict per cost, ``passes = (Gram passes of the iteration, of the verification)``.  The stop test is the path's own -- the residual in the norm of
+    M^-1 = (I + 1 1^T)^-1 relative to the right-hand side in that norm, from x0 = 0 -- not that of :func:`solve_system_of_linear_equations`; with ``verify`` the true
+    residual of every cost is evaluated afterwards and reported (``true_residuum``, ``verified``).  Device 0; deterministic."""
+    A = _as_matrix(A)
+    N, d = A.shape
+    y, costs = _cost_path_arguments(b, N, A.dtype, costs, eps, max_iter)
+    ps = _params_struct(params, d)
+    fn = _capi.cost_path_entry(f"lssvm_mi355_solve_cost_path_{suffix_of(A.dtype)}")
+    return _cost_path_call(fn, (C.byref(ps), ptr(A), N, d), y, costs, N, A.dtype, eps, max_iter, verify, tail=(options_ptr(options),))
 
 
 def generate_q(params: Parameter, data, options: Options | None = None):
@@ -471,6 +515,13 @@ class ResidentProblem:
         passes = (C.c_uint64 * 2)()
         check(_capi.lockstep_entry("lssvm_mi355_problem_solve_lockstep")(self._h, ptr(B), k, eps, int(max_iter), ptr(alphas), rhos.ctypes.data_as(C.POINTER(C.c_double)), infos, passes))
         return alphas, rhos.astype(self.dtype), [info.as_dict() for info in infos], (int(passes[0]), int(passes[1]))
+
+    def solve_cost_path(self, y, costs, eps: float, max_iter: int, verify: bool = True):
+        """:func:`solve_cost_path` on this resident problem (``lssvm_mi355_problem_solve_cost_path``): every cost of ``costs`` from one multi-shift CG sequence on the
+        problem's own single-vector pass.  The problem's own cost is ignored and the problem is left as it was.  Not on a problem of several devices or ranks, not with
+        weights set, not between :meth:`cg_begin` and :meth:`cg_finish`."""
+        y, costs = _cost_path_arguments(y, self.num_points, self.dtype, costs, eps, max_iter)
+        return _cost_path_call(_capi.cost_path_entry("lssvm_mi355_problem_solve_cost_path"), (self._h,), y, costs, self.num_points, self.dtype, eps, max_iter, verify)
 
     def cg_begin(self, y, eps: float):
         y = np.ascontiguousarray(y, dtype=self.dtype)

@@ -179,6 +179,22 @@ void solve_one_shot(const lssvm_params *params, const T *X, size_t N, size_t d, 
     if (info != nullptr) *info = local;
 }
 
+/* lssvm_mi355_solve_cost_path_*: every argument is checked before a device is touched; the problem is created at the first cost (the path ignores it) */
+template <typename T>
+void cost_path_one_shot(const lssvm_params *params, const T *X, size_t N, size_t d, const T *y, const double *costs, size_t num_costs, double eps, uint64_t max_iter, int verify,
+                        T *alphas_out, double *rhos_out, lssvm_path_info *infos_out, uint64_t *passes_out, const lssvm_mi355_options *options) {
+    LSSVM_REQUIRE(params != nullptr, "params must not be NULL!");
+    lssvm::check_cost_path_arguments(y, costs, num_costs, eps, max_iter, alphas_out, rhos_out, infos_out);
+    lssvm_params with_cost = *params;
+    with_cost.cost = costs[0];
+    lssvm::check_params(&with_cost);
+    LSSVM_REQUIRE(X != nullptr && N > 0, "The data must not be empty!");                // csvm.cpp:73
+    LSSVM_REQUIRE(d > 0, "The data points must contain at least one feature!");         // csvm.cpp:74
+    static const int device0 = 0;
+    lssvm::Solver<T> prob(options_of(options), with_cost, X, LSSVM_MEM_HOST, N, d, lssvm::resolve_devices(&device0, 1, N), nullptr);
+    prob.solve_cost_path(y, costs, num_costs, eps, max_iter, verify != 0, alphas_out, rhos_out, infos_out, passes_out);
+}
+
 template <typename T>
 void generate_q_one_shot(const lssvm_params *params, const T *X, size_t N, size_t d, T *q_out, const lssvm_mi355_options *options) {
     lssvm::check_params(params);
@@ -556,6 +572,25 @@ int lssvm_mi355_problem_solve_lockstep(lssvm_mi355_problem *p, const void *Y, si
         LSSVM_REQUIRE(alphas_out != nullptr && rhos_out != nullptr, "alpha_out / rho_out must not be NULL");
         impl_of(p)->solve_lockstep(Y, num_rhs, eps, max_iter, alphas_out, rhos_out, infos_out, passes_out);
     });
+}
+static_assert(sizeof(lssvm_path_info) == 48, "lssvm_path_info changed: plssvm_amd/_capi.py (LssvmPathInfo) changes with it");
+int lssvm_mi355_problem_solve_cost_path(lssvm_mi355_problem *p, const void *y, const double *costs, size_t num_costs, double eps, uint64_t max_iter, int verify, void *alphas_out,
+                                        double *rhos_out, lssvm_path_info *infos_out, uint64_t passes_out[2]) {
+    return guarded([&] {
+        LSSVM_REQUIRE(p != nullptr, "problem handle must not be NULL");
+        lssvm::check_cost_path_arguments(y, costs, num_costs, eps, max_iter, alphas_out, rhos_out, infos_out);  // (before any device work)
+        impl_of(p)->solve_cost_path(y, costs, num_costs, eps, max_iter, verify != 0, alphas_out, rhos_out, infos_out, passes_out);
+    });
+}
+int lssvm_mi355_solve_cost_path_f32(const lssvm_params *params, const float *X, size_t num_points, size_t num_features, const float *y, const double *costs, size_t num_costs, double eps,
+                                    uint64_t max_iter, int verify, float *alphas_out, double *rhos_out, lssvm_path_info *infos_out, uint64_t passes_out[2],
+                                    const lssvm_mi355_options *options) {
+    return guarded([&] { cost_path_one_shot<float>(params, X, num_points, num_features, y, costs, num_costs, eps, max_iter, verify, alphas_out, rhos_out, infos_out, passes_out, options); });
+}
+int lssvm_mi355_solve_cost_path_f64(const lssvm_params *params, const double *X, size_t num_points, size_t num_features, const double *y, const double *costs, size_t num_costs, double eps,
+                                    uint64_t max_iter, int verify, double *alphas_out, double *rhos_out, lssvm_path_info *infos_out, uint64_t passes_out[2],
+                                    const lssvm_mi355_options *options) {
+    return guarded([&] { cost_path_one_shot<double>(params, X, num_points, num_features, y, costs, num_costs, eps, max_iter, verify, alphas_out, rhos_out, infos_out, passes_out, options); });
 }
 int lssvm_mi355_cg_begin(lssvm_mi355_problem *p, const void *y, double eps) {
     return guarded([&] { impl_of(p)->cg_begin(y, eps); });

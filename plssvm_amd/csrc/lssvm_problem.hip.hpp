@@ -577,6 +577,8 @@ struct ProblemBase {
     virtual void matvec_pair(const void *d0, const void *d1, void *ret0_inout, void *ret1_inout, double add, int *two_vector_out) = 0;  // lssvm_mi355_problem_matvec_pair
     virtual void solve_lockstep(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out,
                                 uint64_t *passes_out) = 0;  // lssvm_mi355_problem_solve_lockstep
+    virtual void solve_cost_path(const void *y, const double *costs, size_t num_costs, double eps, uint64_t max_iter, bool verify, void *alphas_out, double *rhos_out,
+                                 lssvm_path_info *infos_out, uint64_t *passes_out) = 0;  // lssvm_mi355_problem_solve_cost_path
     virtual void cg_begin(const void *y, double eps) = 0;
     virtual void cg_step(uint64_t iterations, int *done_out) = 0;
     virtual void cg_finish(void *alpha_out, double *rho_out, lssvm_cg_info *info) = 0;
@@ -654,6 +656,9 @@ class Solver final : public ProblemBase {
     void matvec(const void *d, void *ret_inout, double add) override;
     void matvec_pair(const void *d0, const void *d1, void *ret0_inout, void *ret1_inout, double add, int *two_vector_out) override;
     void solve_lockstep(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out) override;
+    /* every cost of a grid from ONE multi-shift CG sequence on this problem's single-vector pass (lssvm_path.hip) */
+    void solve_cost_path(const void *y, const double *costs, size_t num_costs, double eps, uint64_t max_iter, bool verify, void *alphas_out, double *rhos_out, lssvm_path_info *infos_out,
+                         uint64_t *passes_out) override;
     void cg_begin(const void *y, double eps) override;
     /* cg_begin for the inner solve of the mixed-precision refinement: A e = r / max|r| from e = 0 -- b, the first residual and delta0 = b^T b come from ONE O(n) kernel
      * over the outer fp64 residual `r_dev` (device 0, complete when the call is made; `absmax_part_dev`: k_absmax's partials of it), no Gram pass.  cg_step follows as
@@ -721,6 +726,10 @@ void measure_bf16_mfma_ceiling(int device, int b_from_lds, double settle_ms, dou
 /* lssvm_mi355_solve_refined_f64 (lssvm_refine.hip); the arguments have been checked */
 void solve_refined_f64(const Options &opt, const lssvm_params &params, const double *X, size_t num_points, size_t num_features, const double *Y, size_t num_rhs, const double *weights,
                        double eps, uint64_t max_iter, double *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, lssvm_refine_info *refine_out, uint64_t *passes_out);
+
+/* the arguments of lssvm_mi355_problem_solve_cost_path / lssvm_mi355_solve_cost_path_* that need no device: checked before one is touched (lssvm_path.hip) */
+constexpr size_t PATH_MAX_COSTS = 64;
+void check_cost_path_arguments(const void *y, const double *costs, size_t num_costs, double eps, uint64_t max_iter, const void *alphas_out, const double *rhos_out, const lssvm_path_info *infos_out);
 
 /* one-shot helpers used by the C ABI */
 template <typename T>

@@ -7,6 +7,7 @@ from __future__ import annotations
 import enum
 import sys
 import time
+from dataclasses import replace
 
 import numpy as np
 
@@ -76,6 +77,22 @@ class CSVM:
         values = np.stack([np.asarray(d[0]) for d in done], axis=1)
         return values, (None if any(d[1] is None for d in done) else np.stack([np.asarray(d[1]) for d in done]))
 
+    def solve_cost_path(self, params, A, b, costs, eps, max_iter):
+        """One right-hand side for every cost of ``costs``: ``(alphas[m, N], rhos[m], [info, ...])``.  The default is one solve per cost; a backend with a cost path
+        (the MI355X backend) serves the whole grid from one Krylov sequence."""
+        solved = []
+        for cost in costs:
+            at_cost = replace(params, cost=float(cost))
+            solved.append(self.solve_system_of_linear_equations(at_cost, A, b, eps, max_iter))
+        return np.stack([np.asarray(s[0]) for s in solved]), np.array([s[1] for s in solved]), [s[2] for s in solved]
+
+    def solve_cost_paths(self, params, A, B, costs, eps, max_iter):
+        """:meth:`solve_cost_path` for every row of ``B`` (``k x N`` right-hand sides, one-vs-all) on the same matrix: a list of k ``(alphas[m, N], rhos[m], [info, ...])``."""
+        B = np.asarray(B)
+        if B.ndim != 2 or B.shape[0] == 0:
+            raise InvalidParameterError("The right-hand sides must be a matrix with one row per system and at least one row!")
+        return [self.solve_cost_path(params, A, b, costs, eps, max_iter) for b in B]
+
     def get_params(self):
         return self.params
 
@@ -122,6 +139,28 @@ class CSVM:
                   f"iteration time of {info.get('avg_iteration_ms', 0.0):.3f}ms.", flush=True)
         return Model(params, data, alpha=alpha, rho=rho)
 
+    def fit_cost_path(self, data: DataSet, costs, epsilon: float = 0.001, max_iter: int | None = None) -> list:
+        """``fit`` for every cost of ``costs`` (no counterpart in the reference): one :class:`Model` per cost, in the order of ``costs``, each with its ``params.cost``
+        set; this object's own cost is ignored.  The models share the data set, so they share their support vectors.  ``last_cg_info`` keeps the list of per-cost
+        reports."""
+        if epsilon <= 0.0:
+            raise InvalidParameterError(f"epsilon must be less than 0.0, but is {epsilon}!")  # csvm.hpp:283 (message verbatim)
+        if max_iter is not None and max_iter <= 0:
+            raise InvalidParameterError(f"max_iter must be greater than 0, but is {max_iter}!")  # csvm.hpp:291
+        if not data.has_labels():
+            raise InvalidParameterError("No labels given for training! Maybe the data is only usable for prediction?")  # csvm.hpp:298
+        costs = _checked_costs(costs)
+        if max_iter is None:
+            max_iter = data.num_data_points()  # csvm.hpp:269
+        params = self.params.resolved(data.num_features())
+        alphas, rhos, infos = self.solve_cost_path(params, data.data(), data.mapped_labels(), costs, epsilon, max_iter)
+        self.last_cg_info = infos
+        models = []
+        for s, cost in enumerate(costs):
+            at_cost = replace(params, cost=float(cost))
+            models.append(Model(at_cost, data, alpha=np.asarray(alphas[s]), rho=rhos[s]))
+        return models
+
     def predict(self, model: Model, data: DataSet):
         if model.num_features() != data.num_features():
             raise InvalidParameterError(f"Number of features per data point ({data.num_features()}) must match the number of features per support vector of the "
@@ -142,6 +181,16 @@ class CSVM:
         predicted = self.predict(model, data)
         correct = sum(1 for p, c in zip(predicted, data.labels()) if p == c)
         return correct / len(predicted)
+
+
+def _checked_costs(costs) -> list:
+    """The costs of a cost path as a list of floats: at least one, each finite and > 0."""
+    costs = [float(c) for c in np.asarray(costs, dtype=np.float64).reshape(-1)]
+    if not costs:
+        raise InvalidParameterError("The number of costs must be greater than 0!")
+    if not all(np.isfinite(c) and c > 0.0 for c in costs):
+        raise InvalidParameterError("Every cost of the path must be finite and greater than 0.0!")
+    return costs
 
 
 def _drop_zero_weights(data: DataSet, sample_weight):
@@ -210,6 +259,37 @@ class MI355CSVM(CSVM):
             return alpha, rho, info
         # all devices of this process behind ONE call (gpu_csvm::solve_system_of_linear_equations_impl, gpu_csvm.hpp:477-654)
         return backend.solve_system_of_linear_equations(params, A, b, eps, max_iter, num_devices=self.use_devices, options=self._options, sample_weight=sample_weight)
+
+    def solve_cost_path(self, params, A, b, costs, eps, max_iter):
+        """Every cost from ONE multi-shift CG sequence on device 0 (``backend.solve_cost_path``): one pass over the Gram tiles per iteration for the whole grid.  The stop
+        test is the path's own (``include/plssvm_amd.h``); every cost's true residual is verified and reported in its info.  A backend object of several devices raises, as the library does: the path does not run on a sharded problem."""
+        self._one_device_path()
+        alphas, rhos, infos, passes = backend.solve_cost_path(params, A, b, costs, eps, max_iter, verify=True, options=self._options)
+        for info in infos:
+            info["path_passes"] = passes
+        return alphas, rhos, infos
+
+    def solve_cost_paths(self, params, A, B, costs, eps, max_iter):
+        """One cost path per row of ``B`` on ONE resident problem (``ResidentProblem.solve_cost_path``): the data is uploaded and prepared (q, operand planes) once for all
+        the right-hand sides, as :meth:`solve_systems_of_linear_equations` does.  Each path gives the bits of a one-shot :meth:`solve_cost_path`."""
+        self._one_device_path()
+        A = backend._as_matrix(A)
+        B = np.ascontiguousarray(B, dtype=A.dtype)
+        if B.ndim != 2 or B.shape[0] == 0 or B.shape[1] != A.shape[0]:
+            raise InvalidParameterError(f"The number of data points in the matrix A ({A.shape[0]}) and the values in every right hand side vector ({B.shape[-1] if B.ndim else 0}) must be the same!")
+        solved = []
+        with backend.ResidentProblem(params, A, devices=[0], options=self._options) as prob:  # (device 0 alone, as the one-shot path creates it)
+            for b in B:
+                alphas, rhos, infos, passes = prob.solve_cost_path(b, costs, eps, max_iter, verify=True)
+                for info in infos:
+                    info["path_passes"] = passes
+                solved.append((alphas, rhos, infos))
+        return solved
+
+    def _one_device_path(self) -> None:
+        if self.use_devices != 1:
+            raise InvalidParameterError(f"The cost path runs on one device, but this backend object shards a solve over {'every visible device' if self.use_devices == 0 else self.use_devices}"
+                                        f"{'' if self.use_devices == 0 else ' devices'} (num_devices={self.use_devices})!")
 
     def _refines(self, A) -> bool:
         """solver="refined" applies: float64 data on one device."""

@@ -16,7 +16,7 @@ from .data_set import DataSet
 from .exceptions import InvalidParameterError
 from .parameter import Parameter
 
-__all__ = ["SVC"]
+__all__ = ["SVC", "fit_cost_path", "cost_path_scores"]
 
 # the keywords of the reference's constructor that it rejects (sklearn.cpp:52, :73-108): the same words here
 _NOT_IMPLEMENTED = ("shrinking", "probability", "cache_size", "decision_function_shape", "break_ties", "random_state")
@@ -142,6 +142,10 @@ class SVC:
         data = DataSet(X, y.tolist(), real_type=self.real_type)
         max_iter = None if self.max_iter is None or self.max_iter < 0 else self.max_iter
         model = svm.fit(data, epsilon=self.tol, max_iter=max_iter, sample_weight=weights)
+        return self._set_binary_fit(svm, model, data, X, y, class_weight, weights, int(svm.last_cg_info["iterations"]))
+
+    def _set_binary_fit(self, svm, model, data, X, y, class_weight, weights, n_iter):
+        """The fitted state of a two-class model (``fit``, and ``fit_cost_path`` for each cost)."""
         support = np.arange(y.size, dtype=np.int32) if weights is None else np.flatnonzero(weights > 0).astype(np.int32)
         alpha = np.asarray(model.alpha)
         sv_labels = np.asarray(model.labels())
@@ -153,7 +157,7 @@ class SVC:
             "fit_status_": 0,
             "n_features_in_": int(X.shape[1]),
             "shape_fit_": tuple(int(v) for v in X.shape),
-            "n_iter_": int(svm.last_cg_info["iterations"]),
+            "n_iter_": n_iter,
             "support_": support,
             "support_vectors_": model.support_vectors(),
             "n_support_": np.array([np.count_nonzero(nonzero & (sv_labels == c)) for c in data.different_labels()], dtype=np.int32),
@@ -166,6 +170,10 @@ class SVC:
         """More than two classes: one classifier per class on the same points (plssvm_amd.multiclass)."""
         max_iter = None if self.max_iter is None or self.max_iter < 0 else self.max_iter
         model = _multiclass.fit_one_vs_all(svm, params, np.ascontiguousarray(X, dtype=self.real_type), y, classes, self.tol, max_iter, weights)
+        return self._set_one_vs_all_fit(svm, model, X, y, classes, class_weight, weights)
+
+    def _set_one_vs_all_fit(self, svm, model, X, y, classes, class_weight, weights):
+        """The fitted state of a one-vs-all model (``fit``, and ``fit_cost_path`` for each cost)."""
         support = np.arange(y.size, dtype=np.int32) if weights is None else np.flatnonzero(weights > 0).astype(np.int32)
         sv_labels = y[support]
         nonzero = np.any(model.alpha != 0, axis=0)  # a support vector counts where ANY classifier gives it a non-zero coefficient
@@ -248,3 +256,67 @@ class SVC:
     probA_ = _not_implemented("probA_")
     probB_ = _not_implemented("probB_")
     feature_names_in_ = _not_implemented("feature_names_in_")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the cost path: every C of a grid from one Krylov sequence (MI355CSVM.solve_cost_path)
+# ---------------------------------------------------------------------------------------------------------------------
+def _cost_path_inputs(estimator, X, y, Cs):
+    if not isinstance(estimator, SVC):
+        raise InvalidParameterError("estimator must be a plssvm_amd.svc.SVC")
+    if estimator.class_weight is not None:
+        raise InvalidParameterError("the cost path solves the unweighted system: class_weight must be None")
+    X, y = np.asarray(X), np.asarray(y)
+    if X.ndim != 2 or y.ndim != 1 or y.shape[0] != X.shape[0]:
+        raise InvalidParameterError(f"X must be a matrix and y a vector of as many labels as X has rows, but their shapes are {X.shape} and {y.shape}!")
+    return X, y, _csvm._checked_costs(Cs)
+
+
+def fit_cost_path(estimator, X, y, Cs):
+    """``estimator`` fitted for every ``C`` of ``Cs``: a list of fitted :class:`SVC` clones (``estimator``'s parameters with ``C`` replaced), in the order of ``Cs``.  Two
+    classes: ONE call of the backend's cost path -- every cost from one multi-shift CG sequence, one pass over the Gram tiles per iteration for the whole grid.  More than
+    two classes (one-vs-all): one path per class on ONE resident problem (the data uploaded and prepared once, ``MI355CSVM.solve_cost_paths``).  ``tol`` is the path's stop test (the residual in the norm of (I + 1 1^T)^-1 relative to
+    the right-hand side, from x0 = 0), not that of ``fit``; ``estimator.C`` is ignored and ``estimator`` itself stays unfitted.  ``class_weight`` must be None."""
+    X, y, Cs = _cost_path_inputs(estimator, X, y, Cs)
+    params = estimator._params()
+    classes = np.array(sorted(set(y.tolist())))
+    class_weight = np.ones(len(classes))
+    max_iter = None if estimator.max_iter is None or estimator.max_iter < 0 else estimator.max_iter
+    svm = make_csvm(params=params)
+    clones = [SVC(**{**estimator.get_params(), "C": C}) for C in Cs]
+    if len(classes) > 2:
+        Xr = np.ascontiguousarray(X, dtype=estimator.real_type)
+        resolved = params.resolved(Xr.shape[1])
+        B = _multiclass.one_vs_all_targets(classes, y, Xr.dtype)
+        solved = svm.solve_cost_paths(resolved, Xr, B, Cs, estimator.tol, Xr.shape[0] if max_iter is None else max_iter)  # [class] -> (alphas[m, N], rhos[m], infos[m])
+        for s, (C, clone) in enumerate(zip(Cs, clones)):
+            at_cost = Parameter(kernel_type=resolved.kernel_type, degree=resolved.degree, gamma=resolved.gamma, coef0=resolved.coef0, cost=C)
+            model = _multiclass.OneVsAllModel(at_cost, classes, Xr, np.stack([np.asarray(c[0][s]) for c in solved]), np.array([c[1][s] for c in solved]), [c[2][s] for c in solved])
+            clone._set_one_vs_all_fit(svm, model, X, y, classes, class_weight, None)
+        return clones
+    data = DataSet(X, y.tolist(), real_type=estimator.real_type)
+    models = svm.fit_cost_path(data, Cs, epsilon=estimator.tol, max_iter=max_iter)
+    for clone, model, info in zip(clones, models, svm.last_cg_info):
+        clone._set_binary_fit(svm, model, data, X, y, class_weight, None, int(info["iterations"]))
+    return clones
+
+
+def cost_path_scores(estimator, X, y, Cs, X_val, y_val):
+    """The validation accuracy of a TWO-class ``estimator`` at every ``C`` of ``Cs``: one cost path (:func:`fit_cost_path`), then ONE resident predictor over all the
+    models -- they share their support vectors, so the predictor takes their weight vectors two per pass over the Gram tiles.  Returns ``(scores[m], fitted clones)``."""
+    if not isinstance(estimator, SVC):
+        raise InvalidParameterError("estimator must be a plssvm_amd.svc.SVC")
+    num_classes = len(set(np.asarray(y).reshape(-1).tolist()))
+    if num_classes != 2:  # (before anything is fitted)
+        raise InvalidParameterError(f"cost_path_scores scores two-class models, but the labels have {num_classes} classes")
+    y_val = np.asarray(y_val)
+    clones = fit_cost_path(estimator, X, y, Cs)  # (checks its inputs)
+    classes = clones[0].classes_
+    models = [c._model for c in clones]
+    alphas = np.stack([np.asarray(m.alpha) for m in models])
+    rhos = np.array([float(m.rho) for m in models], dtype=np.float64)
+    from . import backend
+    with backend.Predictor(models[0].params, models[0].support_vectors(), alphas, rhos, options=getattr(clones[0]._svm, "_options", None)) as predictor:
+        values = predictor.predict(np.asarray(X_val, dtype=estimator.real_type))  # [n_val, m]
+    predicted = np.where(values > 0, classes[1], classes[0])
+    return np.array([float(np.mean(predicted[:, s] == y_val)) for s in range(len(Cs))]), clones
