@@ -135,6 +135,138 @@ struct LaunchTimer {
     }
 };
 
+/* The end of every predict call, linear or not: the values to the caller (to HBM for a batch that came from there), the stream drained, the call's times.  `lap`: see
+ * ProductStage::run. */
+static constexpr auto no_lap = [](const char *) {};
+template <typename T, typename Lap>
+static void finish_predict(const LaunchTimer &timer, const DevBuf<T> &o, T *out, int mem_kind, hipStream_t s, double t0, double t_kernel, int per_launch, lssvm_predict_info &info,
+                           Lap &&lap) {
+    LSSVM_HIP_CHECK(hipGetLastError());
+    lap("product, row sums");
+    LSSVM_HIP_CHECK(hipMemcpyAsync(out, o.p, o.count * sizeof(T), mem_kind == LSSVM_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    LSSVM_HIP_CHECK(hipStreamSynchronize(s));
+    lap("values downloaded");
+    timer.sum_into(info);
+    info.total_ms = now_ms() - t0;
+    info.setup_ms = t_kernel - t0;
+    info.vectors_per_launch = per_launch;
+}
+
+/* ------------------------------------------------------------------ the product stage ------------------------------------------------------------------ */
+/* Round 6: from 64 row blocks of points on, on at most 128 features, the RECTANGULAR 256-row kernel (tile_matvec_f32_pair_rect, lssvm_tile_f32_pair.hip.hpp) -- eight
+ * waves of a pair of row blocks share one stream of the support vectors' planes, in persistent launches that draw their items from per-XCD counters, like the
+ * training matvec's kernel; the 128-row full-square kernels ran this product at 0.49 of the 16-bit peak where the solve's kernel reaches 0.57 (200 000 points x
+ * 50 000 support vectors x 128).  The conditions of Problem<float>'s pair_ that every caller shares (split planes are the caller's
+ * to check): no run-time integer power, rbf with both exponent terms folded (`rbf_folded` records and |c| = r2 / 2 <= PAIR_FOLD_MAX_C). */
+static bool rect_kernel_applies(const Options &opt, const lssvm_params &params, int ldx16, bool rbf_folded, double r2, int num_ib) {
+    const bool poly_generic = params.kernel_type == LSSVM_KERNEL_POLYNOMIAL && params.degree != 2 && params.degree != 3;
+    const bool rbf_ok = params.kernel_type != LSSVM_KERNEL_RBF || (rbf_folded && r2 <= 2.0 * PAIR_FOLD_MAX_C);
+    return ldx16 <= 128 && !poly_generic && rbf_ok && opt.mfma_shape >= 3 && num_ib >= PAIR_MIN_TILES;
+}
+
+/* column tiles per work item of a rectangular product and the column chunks they make: the option, or automatically about 4096 work items (see Problem<T>'s
+ * constructor); 256-row items (`rect`): about eight per CU, at most 64 tiles */
+struct ColumnChunks {
+    int jc_tiles, num_jc;
+};
+static ColumnChunks column_chunks(const Options &opt, bool rect, int num_ib, int num_jt) {
+    long tiles = static_cast<long>(opt.j_chunk_tiles);
+    if (tiles <= 0) {
+        tiles = rect ? std::min<long>(64, std::max<long>(4, (static_cast<long>(num_ib / 2) * num_jt + 1024) / 2048))
+                     : std::min<long>(16, std::max<long>(2, (static_cast<long>(num_ib) * num_jt + 2048) / 4096));
+    }
+    const int jc_tiles = static_cast<int>(tiles);
+    return { jc_tiles, (num_jt + jc_tiles - 1) / jc_tiles };
+}
+
+/* out[p][v] = sum_j alpha_v,j k(sv_j, p) - rho[v] for `nvec` weight vectors: the rectangular instance of the tile kernels behind the one-shot call and both resident
+ * predictors.  Rows = the points P (padded to whole pairs of row blocks), columns = the support vectors S, both prepared by the caller.  The stage owns the slabs of
+ * partial row sums, the values and the launches' timer; a caller sets the operand-specific launch arguments on what args() returns and calls run() once.
+ * `records(v, count) -> const T *`: the column records of the launch group that starts at weight vector v and holds `count` (1 or 2) vectors, NULL for a kernel that
+ * reads none.  A caller that packs records on the stream does so inside the callable: args() asks for group 0 -- in front of whatever the caller enqueues next and of the
+ * drain that precedes the timed region --, run() for every later group immediately in front of its launch. */
+template <typename T>
+struct ProductStage {
+    const Options &opt;
+    const DeviceMatrix<T> &P, &S;
+    const bool rect;  // the rectangular 256-row kernel: the caller's decision (rect_kernel_applies) and the caller's setup_rect_launch
+    const T *const alpha, *const rho;  // [nvec][S.rows_alloc] in HBM, exact zeros beyond the support vectors; [nvec] on the host
+    const int nv, per_launch, num_ib, num_jt;
+    const ColumnChunks chunks;
+    const size_t part_plane;
+    const hipStream_t s;
+    const double t0;    // the caller's start of the call
+    LaunchTimer timer;  // around every launch of the kernel that does the product, and nothing else
+    DevBuf<T> partial, Kv, o;
+
+    ProductStage(const Options &options, const DeviceMatrix<T> &points, const DeviceMatrix<T> &svs, bool rect256, const T *alphas, const T *rhos, size_t nvec, int vectors_per_launch,
+                 hipStream_t stream, double t_begin) :
+        opt(options), P(points), S(svs), rect(rect256), alpha(alphas), rho(rhos), nv(static_cast<int>(nvec)), per_launch(vectors_per_launch), num_ib(points.rows_alloc / TILE),
+        num_jt(svs.rows_alloc / TILE), chunks(column_chunks(options, rect256, num_ib, num_jt)), part_plane(static_cast<size_t>(chunks.num_jc) * points.rows_alloc), s(stream), t0(t_begin), timer(nvec) {
+        partial.alloc_zero(per_launch * part_plane, s);
+        Kv.alloc_zero(P.rows_alloc, s);
+        o.alloc_zero(static_cast<size_t>(P.rows) * nvec, s);
+    }
+
+    /* the launch arguments every caller shares: both sides (`cr` / `cc`: their rbf norms), the slabs, the geometry, the kernel's scalars, and group 0's vector and records */
+    template <typename Records>
+    TileArgs<T> args(const lssvm_params &params, bool rbf_direct, const T *cr, const T *cc, Records &&records) const {
+        TileArgs<T> ta{};
+        ta.Xr = P.data.p;
+        ta.Xc = S.data.p;
+        ta.cr = cr;
+        ta.cc = cc;
+        ta.dvec = alpha;
+        ta.dc = records(0, std::min(per_launch, nv));
+        ta.partial = partial.p;
+        ta.part_stride = P.rows_alloc;
+        ta.ldx = S.ldx;
+        ta.kchunks = S.ldx / kchunk_of<T>();
+        ta.num_ib = num_ib;
+        ta.num_jt = num_jt;
+        ta.jc_tiles = chunks.jc_tiles;
+        ta.ncols_valid = S.rows;
+        set_kernel_scalars(ta, params, rbf_direct);
+        set_launch_options(ta, opt);
+        return ta;
+    }
+
+    /* The launch groups in order, each followed by its vectors' row sums, then the end of the call (finish_predict).  `repeat`: extra untimed launches of group 0 in
+     * front of the timed one -- the product overwrites its slabs, the result is the same -- (predict_values' measurement aid).  `lap(label)`: called where the set-up,
+     * the product and the download end (the resident fp32 form's LSSVM_MI355_DEBUG laps). */
+    template <typename Records, typename Lap>
+    void run(TileArgs<T> &ta, int kernel_type, bool rbf_direct, Records &&records, T *out, int mem_kind, lssvm_predict_info &info, Lap &&lap, int repeat = 1) {
+        const int num_jc = chunks.num_jc;
+        const auto launch = [&] { launch_tile_kernel<T>(ta, kernel_type, rbf_direct, num_jc, s); };
+        const auto next_counters = [&] {  // (a persistent launch zeroes the OTHER set of counters)
+            if (ta.queue != nullptr) std::swap(ta.queue, ta.queue_next);
+        };
+        LSSVM_HIP_CHECK(hipStreamSynchronize(s));
+        lap(rect ? "slabs, 256-row launch set up" : "slabs");
+        const double t_kernel = now_ms();
+        for (int k = 0; k + 1 < repeat; ++k) {
+            launch();
+            next_counters();
+        }
+        for (int v = 0; v < nv; v += per_launch) {
+            const int count = std::min(per_launch, nv - v);
+            if (v > 0) {  // (group 0: set by args())
+                ta.dc = records(v, count);
+                ta.dvec = alpha + static_cast<size_t>(v) * S.rows_alloc;
+                next_counters();
+            }
+            ta.nvec = count;
+            ta.part_vstride = count == 2 ? static_cast<long>(part_plane) : 0;
+            timer.timed(s, launch);
+            for (int u = 0; u < count; ++u) {
+                hipLaunchKernelGGL(k_reduce_partials<T>, dim3((P.rows_alloc + 255) / 256), dim3(256), 0, s, partial.p + u * part_plane, ta.part_stride, num_jc, 0, P.rows_alloc, Kv.p);
+                hipLaunchKernelGGL(k_sub_rho<T>, dim3((P.rows + 255) / 256), dim3(256), 0, s, Kv.p, P.rows, rho[v + u], o.p + (v + u), nv);
+            }
+        }
+        finish_predict(timer, o, out, mem_kind, s, t0, t_kernel, per_launch, info, lap);
+    }
+};
+
 /* `nvec` weight vectors over the same support vectors: alpha [nvec][nsv], rho [nvec], w_inout [nvec][nfeat], out [npoints][nvec] (nvec = 1: predict_values).  Everything up
  * to the records of the weight vectors is done once; `repeat`: extra untimed launches of the product in front of the timed one (predict_values' measurement aid). */
 template <typename T>
@@ -151,14 +283,7 @@ static void predict_values_impl(const Options &opt, const lssvm_params &params, 
     select_device_checked(0);
     hipStream_t s = nullptr;
     const double t0 = now_ms();
-    LaunchTimer timer(nvec);  // around every launch of the kernel that does the product
-    const auto timed = [&](auto &&launch) { timer.timed(s, launch); };
     const int nv = static_cast<int>(nvec);
-    const auto finish_info = [&](double t_kernel_enqueued) {
-        timer.sum_into(info);
-        info.total_ms = now_ms() - t0;
-        info.setup_ms = t_kernel_enqueued - t0;
-    };
 
     if (params.kernel_type == LSSVM_KERNEL_LINEAR) {
         LSSVM_REQUIRE(w_inout != nullptr, "w must have num_features entries for the linear kernel");
@@ -166,6 +291,7 @@ static void predict_values_impl(const Options &opt, const lssvm_params &params, 
             calculate_w_multi<T>(sv, nsv, nfeat, alpha, nvec, w_inout);
             *w_valid = 1;
         }
+        LaunchTimer timer(nvec);
         DeviceMatrix<T> P;
         P.upload(points, LSSVM_MEM_HOST, npoints, nfeat, 0, s);
         DevBuf<T> w, o;
@@ -174,12 +300,8 @@ static void predict_values_impl(const Options &opt, const lssvm_params &params, 
         LSSVM_HIP_CHECK(hipMemcpy2DAsync(w.p, static_cast<size_t>(P.ldx) * sizeof(T), w_inout, nfeat * sizeof(T), nfeat * sizeof(T), nvec, hipMemcpyHostToDevice, s));
         LSSVM_HIP_CHECK(hipStreamSynchronize(s));
         const double t_kernel = now_ms();
-        for (int v = 0; v < nv; ++v) timed([&] { launch_predict_linear<T>(P, w.p + static_cast<size_t>(v) * P.ldx, rho[v], o.p + v, s, nv); });
-        LSSVM_HIP_CHECK(hipGetLastError());
-        LSSVM_HIP_CHECK(hipMemcpyAsync(out, o.p, npoints * nvec * sizeof(T), hipMemcpyDeviceToHost, s));
-        LSSVM_HIP_CHECK(hipStreamSynchronize(s));
-        finish_info(t_kernel);
-        info.vectors_per_launch = 1;
+        for (int v = 0; v < nv; ++v) timer.timed(s, [&] { launch_predict_linear<T>(P, w.p + static_cast<size_t>(v) * P.ldx, rho[v], o.p + v, s, nv); });
+        finish_predict(timer, o, out, LSSVM_MEM_HOST, s, t0, t_kernel, 1, info, no_lap);
         return;
     }
 
@@ -238,48 +360,23 @@ static void predict_values_impl(const Options &opt, const lssvm_params &params, 
     }
     interleave_features<T>(S, s);
     interleave_features<T>(P, s);
-    const int num_jt = S.rows_alloc / TILE;
-    const int num_ib = P.rows_alloc / TILE;
-    // Round 6: from 64 row blocks of points on, on at most 128 features, the RECTANGULAR 256-row kernel (tile_matvec_f32_pair_rect, lssvm_tile_f32_pair.hip.hpp) -- eight
-    // waves of a pair of row blocks share one stream of the support vectors' planes, in persistent launches that draw their items from per-XCD counters, like the
-    // training matvec's kernel; the 128-row full-square kernels ran this product at 0.49 of the 16-bit peak where the solve's kernel reaches 0.57 (200 000 points x
-    // 50 000 support vectors x 128, gpurun_out/r06_bench_default_1.json).  Same conditions as Problem<float>'s pair_: a split mode, no run-time integer power, rbf
-    // with both exponent terms folded (|c| <= PAIR_FOLD_MAX_C).
-    bool rect = false;
+    bool rect = false;  // (the rectangular 256-row kernel: here only beside the one-pass split kernels on the norm expansion)
     if constexpr (std::is_same_v<T, float>) {
-        const bool poly_generic = params.kernel_type == LSSVM_KERNEL_POLYNOMIAL && params.degree != 2 && params.degree != 3;
-        const bool rbf_ok = params.kernel_type != LSSVM_KERNEL_RBF || (dc_folded != 0 && rbf_r2 <= 2.0 * PAIR_FOLD_MAX_C);
-        rect = v2 && !wide && !rbf_grid && !rbf_direct && planesS.mode != 0 && planesS.ldx16 <= 128 && !poly_generic && rbf_ok && opt.mfma_shape >= 3 && num_ib >= PAIR_MIN_TILES;
+        rect = v2 && !wide && !rbf_grid && !rbf_direct && planesS.mode != 0 && rect_kernel_applies(opt, params, planesS.ldx16, dc_folded != 0, rbf_r2, P.rows_alloc / TILE);
     }
-    // column tiles per work item: the option, or automatically about 4096 work items (see Problem<T>'s constructor); 256-row items: about eight per CU, at most 64 tiles
-    const long rect_tiles = std::min<long>(64, std::max<long>(4, (static_cast<long>(num_ib / 2) * num_jt + 1024) / 2048));
-    const int jc_tiles = opt.j_chunk_tiles > 0
-                             ? static_cast<int>(opt.j_chunk_tiles)
-                             : (rect ? static_cast<int>(rect_tiles) : static_cast<int>(std::min<long>(16, std::max<long>(2, (static_cast<long>(num_ib) * num_jt + 2048) / 4096))));
-    const int num_jc = (num_jt + jc_tiles - 1) / jc_tiles;
     // the rectangular 256-row kernel takes the weight vectors two per pass (NV = 2: one evaluation of the Gram tile feeds both), an odd last one alone
     const int per_launch = (rect && nv >= 2) ? 2 : 1;
-    const size_t part_plane = static_cast<size_t>(num_jc) * P.rows_alloc;
-    DevBuf<T> a, partial, Kv, o;
+    DevBuf<T> a, dc;
     a.alloc_zero(nvec * S.rows_alloc, s);  // [nvec][rows_alloc], exact zeros beyond the support vectors
-    partial.alloc_zero(per_launch * part_plane, s);
-    Kv.alloc_zero(P.rows_alloc, s);
-    o.alloc_zero(npoints * nvec, s);
+    ProductStage<T> stage(opt, P, S, rect, a.p, rho, nvec, per_launch, s, t0);
     LSSVM_HIP_CHECK(hipMemcpy2DAsync(a.p, static_cast<size_t>(S.rows_alloc) * sizeof(T), alpha, nsv * sizeof(T), nsv * sizeof(T), nvec, hipMemcpyHostToDevice, s));
-
-    TileArgs<T> ta{};
-    ta.Xr = P.data.p;
-    ta.Xc = S.data.p;
-    ta.cr = cP.p;
-    ta.cc = cS.p;
-    ta.dvec = a.p;
     // rectangular instance of the tile kernel (full square variant): the v2 kernel when the feature count allows, with the
-    // (alpha_j | c_j) records of the support vectors packed for its LDS-DMA
-    DevBuf<T> dc;
-    const int ncols = num_jt * TILE;
+    // (alpha_j | c_j) records of the support vectors packed for its LDS-DMA -- one buffer, packed anew for every launch group
+    const int ncols = stage.num_jt * TILE;
     const bool records = v2 && !(std::is_same_v<T, double> && params.kernel_type == LSSVM_KERNEL_POLYNOMIAL && !poly_prescaled);
-    const auto pack_records = [&](int v, int count) {  // the records of the weight vectors v (, v + 1) of the next launch
-        if (!records) return;
+    if (records) dc.alloc_zero(static_cast<size_t>(stage.num_jt) * 256, s);
+    const auto pack_records = [&](int v, int count) -> const T * {  // the records of the weight vectors v (, v + 1) of the next launch
+        if (!records) return nullptr;
         if constexpr (std::is_same_v<T, float>) {
             if (count == 2) {
                 enqueue_pack_records2(a.p + static_cast<size_t>(v) * S.rows_alloc, a.p + static_cast<size_t>(v + 1) * S.rows_alloc, cS.p, ncols, dc.p, dc_folded, s);
@@ -289,23 +386,10 @@ static void predict_values_impl(const Options &opt, const lssvm_params &params, 
         } else {
             enqueue_pack_records(a.p + static_cast<size_t>(v) * S.rows_alloc, cS.p, ncols, dc.p, 0, static_cast<const double *>(nullptr), s);
         }
+        return dc.p;
     };
-    if (records) {
-        dc.alloc_zero(static_cast<size_t>(num_jt) * 256, s);
-        pack_records(0, per_launch);
-    }
-    ta.dc = dc.p;
+    TileArgs<T> ta = stage.args(params, rbf_direct, cP.p, cS.p, pack_records);
     ta.dc_folded = dc_folded;
-    ta.partial = partial.p;
-    ta.part_stride = P.rows_alloc;
-    ta.ldx = S.ldx;
-    ta.kchunks = S.ldx / kchunk_of<T>();
-    ta.ib_begin = 0;
-    ta.num_ib = num_ib;
-    ta.num_jt = num_jt;
-    ta.jc_tiles = jc_tiles;
-    ta.ncols_valid = S.rows;
-    set_kernel_scalars(ta, params, rbf_direct);
     if (poly_prescaled) ta.gamma = T(1);
     if constexpr (std::is_same_v<T, float>) {
         if (planesS.mode != 0) set_plane_args(ta, params, planesS, planesP, static_cast<size_t>(S.rows_alloc), static_cast<size_t>(P.rows_alloc));
@@ -316,38 +400,11 @@ static void predict_values_impl(const Options &opt, const lssvm_params &params, 
         }
     }
     ta.wide_panels = wide ? 1 : 0;
-    set_launch_options(ta, opt);
     RectSetup rect_setup;
     if constexpr (std::is_same_v<T, float>) {
-        if (rect) setup_rect_launch(ta, rect_setup, planesP, P.rows_alloc, num_ib, num_jc, s);
+        if (rect) setup_rect_launch(ta, rect_setup, planesP, P.rows_alloc, stage.num_ib, stage.chunks.num_jc, s);
     }
-    LSSVM_HIP_CHECK(hipStreamSynchronize(s));
-    const double t_kernel = now_ms();
-    // (`repeat` launches of the product kernel -- it overwrites its slabs, the result is the same -- of which the LAST is timed: predict_values' measurement aid)
-    for (int k = 0; k + 1 < repeat; ++k) {
-        launch_tile_kernel<T>(ta, params.kernel_type, rbf_direct, num_jc, s);
-        if (ta.queue != nullptr) std::swap(ta.queue, ta.queue_next);  // (a persistent launch zeroes the OTHER set of counters)
-    }
-    for (int v = 0; v < nv; v += per_launch) {
-        const int count = std::min(per_launch, nv - v);
-        if (v > 0) {  // (the records of the first launch were packed before the set-up was drained)
-            pack_records(v, count);
-            ta.dvec = a.p + static_cast<size_t>(v) * S.rows_alloc;
-            if (ta.queue != nullptr) std::swap(ta.queue, ta.queue_next);
-        }
-        ta.nvec = count;
-        ta.part_vstride = count == 2 ? static_cast<long>(part_plane) : 0;
-        timed([&] { launch_tile_kernel<T>(ta, params.kernel_type, rbf_direct, num_jc, s); });
-        for (int u = 0; u < count; ++u) {
-            hipLaunchKernelGGL(k_reduce_partials<T>, dim3((P.rows_alloc + 255) / 256), dim3(256), 0, s, partial.p + u * part_plane, ta.part_stride, num_jc, 0, P.rows_alloc, Kv.p);
-            hipLaunchKernelGGL(k_sub_rho<T>, dim3((P.rows + 255) / 256), dim3(256), 0, s, Kv.p, P.rows, rho[v + u], o.p + (v + u), nv);
-        }
-    }
-    LSSVM_HIP_CHECK(hipGetLastError());
-    LSSVM_HIP_CHECK(hipMemcpyAsync(out, o.p, npoints * nvec * sizeof(T), hipMemcpyDeviceToHost, s));
-    LSSVM_HIP_CHECK(hipStreamSynchronize(s));
-    finish_info(t_kernel);
-    info.vectors_per_launch = per_launch;
+    stage.run(ta, params.kernel_type, rbf_direct, pack_records, out, LSSVM_MEM_HOST, info, no_lap, repeat);
     info.gram_mode = (planesS.mode != 0 && dc.p != nullptr) ? (rbf_grid ? 3 : planesS.mode) : 0;
     info.rbf_direct = rbf_direct ? 1 : 0;
     info.rbf_exponent_scale = rbf_r2;
@@ -403,141 +460,59 @@ template void calculate_w<float>(const float *, size_t, size_t, const float *, f
 template void calculate_w<double>(const double *, size_t, size_t, const double *, double *);
 
 /* ------------------------------------------------------------------ the resident predictor ------------------------------------------------------------------ */
-/* `nvec_` weight vectors over the same support vectors (lssvm_mi355_predictor_create: one; _create_multi: a one-vs-all model's k).  Everything that does not depend on
- * the weight vector is held once; per vector the alpha row, the packed column records of its launch group and, for the linear kernel, w.
- * `every_form` (lssvm_mi355_predictor_create_resident): fp64 rbf / polynomial models on at most 256 padded features are resident as well (prepare_resident_f64), and so
- * are fp32 models of 129 ... 512 features on the one-pass split kernels (prepare_resident); without it such a model goes through the one-shot path, as _create /
- * _create_multi document. */
+/* what every form of a predictor knows of its model: `nvec` weight vectors over the same `nsv` support vectors */
 template <typename T>
-class Predictor final : public PredictorBase {
+struct PredictModel {
+    Options opt;
+    lssvm_params params;
+    size_t nsv, nfeat, nvec;
+    std::vector<T> rho;
+};
+
+/* The resident forms of an rbf / polynomial model, one type per real type: everything of the support vectors' side of the product that does not depend on the batch,
+ * held in HBM -- per weight vector the alpha row and the packed column records of its launch group.  prepare(): false = this model has no resident form (nothing is
+ * kept); predict(): a batch of points through the product stage, false = this batch needs the one-shot path. */
+class ResidentF32 {
   public:
-    Predictor(const Options &opt, const lssvm_params &params, const T *sv, size_t nsv, size_t nfeat, const T *alpha, const double *rho, size_t nvec, bool every_form) :
-        opt_(opt), params_(params), nsv_(nsv), nfeat_(nfeat), nvec_(nvec) {
-        dtype = std::is_same_v<T, float> ? LSSVM_DTYPE_F32 : LSSVM_DTYPE_F64;
-        check_params(&params_);
-        LSSVM_REQUIRE(nvec > 0 && rho != nullptr, "a predictor needs at least one weight vector and its rho");
-        LSSVM_REQUIRE(nvec <= static_cast<size_t>(1) << 20, "too many weight vectors");
-        LSSVM_REQUIRE(sv != nullptr && nsv > 0, "The support vectors must not be empty!");   // csvm.cpp:189
-        LSSVM_REQUIRE(nfeat > 0, "The support vectors must contain at least one feature!");  // csvm.cpp:190
-        LSSVM_REQUIRE(alpha != nullptr, "The number of support vectors and number of weights must be the same!");
-        rho_.resize(nvec);
-        for (size_t v = 0; v < nvec; ++v) rho_[v] = static_cast<T>(rho[v]);
-        select_device_checked(0);
-        hipStream_t s = nullptr;
-        if (params_.kernel_type == LSSVM_KERNEL_LINEAR) {
-            // the linear kernel predicts through w = sum_i alpha_i sv_i (csvm.cpp:204-213): computed once per vector, resident zero padded like a row of points
-            w_host_.assign(nvec * nfeat, T(0));
-            calculate_w_multi<T>(sv, nsv, nfeat, alpha, nvec, w_host_.data());
-            ldw_ = static_cast<size_t>(padded_features<T>(nfeat));
-            w_.alloc_zero(nvec * ldw_, s);
-            LSSVM_HIP_CHECK(hipMemcpy2DAsync(w_.p, ldw_ * sizeof(T), w_host_.data(), nfeat * sizeof(T), nfeat * sizeof(T), nvec, hipMemcpyHostToDevice, s));
-            LSSVM_HIP_CHECK(hipStreamSynchronize(s));
-            return;
-        }
-        alpha_host_.assign(alpha, alpha + nvec * nsv);
-        if constexpr (std::is_same_v<T, float>) {
-            prepare_resident(sv, s, every_form);
-        } else {
-            if (every_form) prepare_resident_f64(sv, s);
-            if (resident_) std::vector<T>().swap(alpha_host_);  // (the fp64 form never declines a batch: the one-shot path's inputs are not needed)
-        }
-        // the one-shot path's input: a host copy where nothing is resident; a resident model keeps its support vectors as they came in HBM and fetches them if a batch ever asks
-        if (!resident_) {
-            sv_host_.assign(sv, sv + nsv * nfeat);
-            S_.data.release();  // (whatever prepare_resident had built before it found the model outside the resident form)
-            raw_.release();
-            planesS_.buf.release();
-            cS_.release();
-            mean_.release();
-        }
+    static constexpr bool declines_batches = true;  // (the one-shot path's inputs stay needed: alpha on the host, the support vectors through fetch_support_vectors)
+
+    bool prepare(const PredictModel<float> &m, const float *sv, const float *alpha, bool every_form, hipStream_t s) {
+        const bool resident = prepare_or_decline(m, sv, alpha, every_form, s);
+        if (!resident) reset();
+        return resident;
     }
 
-    void predict(const void *points_v, int mem_kind, size_t npoints, void *out_v, lssvm_predict_info *info, bool multi) override {
-        const T *points = static_cast<const T *>(points_v);
-        T *out = static_cast<T *>(out_v);
-        LSSVM_REQUIRE(points != nullptr && npoints > 0, "The data points to predict must not be empty!");  // csvm.cpp:194
-        LSSVM_REQUIRE(out != nullptr, "out must not be NULL");
-        LSSVM_REQUIRE(multi || nvec_ == 1, "this predictor holds more than one weight vector: use lssvm_mi355_predictor_predict_multi");
-        lssvm_predict_info local{};
-        local.f16_row_rel_error = -1.0;
-        bool done = false;
-        if (params_.kernel_type == LSSVM_KERNEL_LINEAR) {
-            predict_linear(points, mem_kind, npoints, out, local);
-            done = true;
-        } else if constexpr (std::is_same_v<T, float>) {
-            if (resident_) done = predict_resident(points, mem_kind, npoints, out, local);
-        } else {
-            if (resident_) done = predict_resident_f64(points, mem_kind, npoints, out, local);
-        }
-        if (!done) {
-            // what the resident form does not cover (outside lssvm_mi355_predictor_create_resident: fp64, and fp32 on more than 128 features; with it: fp64 beyond 256
-            // features and fp32 beyond the one-pass split kernels' 512 / 384; gram_mode 0, tile_kernel 1, rbf_form 1 / 3; exponent scales beyond the norm expansion; a
-            // batch whose planes fail the f16 check or that lies further from the support vectors' centre than the form chosen for them allows): the one-shot path,
-            // same result
-            int w_valid = 0;
-            std::vector<T> w_tmp(nvec_ * nfeat_);
-            if (sv_host_.empty()) fetch_support_vectors();
-            const auto one_shot = [&](const T *pts, T *values) {
-                if (multi) {
-                    predict_values_multi<T>(opt_, params_, sv_host_.data(), nsv_, nfeat_, alpha_host_.data(), rho_.data(), nvec_, w_tmp.data(), &w_valid, pts, npoints, values, &local);
-                } else {
-                    predict_values<T>(opt_, params_, sv_host_.data(), nsv_, nfeat_, alpha_host_.data(), rho_[0], w_tmp.data(), &w_valid, pts, npoints, values, &local);
-                }
-            };
-            if (mem_kind == LSSVM_MEM_DEVICE) {  // (the one-shot entry point takes host buffers: a batch in HBM makes the round trip here -- the rare path)
-                select_device_checked(0);
-                std::vector<T> points_host(npoints * nfeat_), out_host(npoints * nvec_);
-                LSSVM_HIP_CHECK(hipMemcpy(points_host.data(), points, points_host.size() * sizeof(T), hipMemcpyDeviceToHost));
-                one_shot(points_host.data(), out_host.data());
-                LSSVM_HIP_CHECK(hipMemcpy(out, out_host.data(), out_host.size() * sizeof(T), hipMemcpyHostToDevice));
-            } else {
-                one_shot(points, out);
-            }
-            local.resident = 0;
-        }
-        if (!multi) local.vectors_per_launch = 0;  // (vectors_per_launch is the multi calls' report)
-        if (info != nullptr) *info = local;
+    /* the support vectors back on the host, as they came (a resident model keeps no host copy until a batch needs the one-shot path) */
+    void fetch_support_vectors(const PredictModel<float> &m, std::vector<float> &sv_host) const {
+        select_device_checked(0);
+        const float *src = raw_.p != nullptr ? raw_.p : S_.data.p;
+        LSSVM_REQUIRE(src != nullptr, "the predictor holds no support vectors");
+        sv_host.resize(m.nsv * m.nfeat);
+        LSSVM_HIP_CHECK(hipMemcpy2D(sv_host.data(), m.nfeat * sizeof(float), src, static_cast<size_t>(S_.ldx) * sizeof(float), m.nfeat * sizeof(float), m.nsv, hipMemcpyDeviceToHost));
     }
 
   private:
-    void predict_linear(const T *points, int mem_kind, size_t npoints, T *out, lssvm_predict_info &info) {
-        select_device_checked(0);
-        hipStream_t s = nullptr;
-        const double t0 = now_ms();
-        const int nv = static_cast<int>(nvec_);
-        LaunchTimer timer(nvec_);
-        DeviceMatrix<T> P;
-        P.upload(points, mem_kind, npoints, nfeat_, 0, s);
-        DevBuf<T> o;
-        o.alloc_zero(npoints * nvec_, s);
-        LSSVM_HIP_CHECK(hipStreamSynchronize(s));
-        const double t_kernel = now_ms();
-        for (int v = 0; v < nv; ++v) timer.timed(s, [&] { launch_predict_linear<T>(P, w_.p + static_cast<size_t>(v) * ldw_, rho_[static_cast<size_t>(v)], o.p + v, s, nv); });
-        LSSVM_HIP_CHECK(hipGetLastError());
-        LSSVM_HIP_CHECK(hipMemcpyAsync(out, o.p, npoints * nvec_ * sizeof(T), mem_kind == LSSVM_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
-        LSSVM_HIP_CHECK(hipStreamSynchronize(s));
-        timer.sum_into(info);
-        info.total_ms = now_ms() - t0;
-        info.setup_ms = t_kernel - t0;
-        info.resident = 1;
-        info.vectors_per_launch = 1;
+    /* whatever prepare_or_decline had built before it found the model outside the resident form */
+    void reset() {
+        for (DevBuf<float> *b : { &S_.data, &mean_, &cS_, &a_, &raw_, &dc_, &dc_folded_, &dc2_ }) b->release();
+        planesS_.buf.release();
     }
 
     /* fp32, rbf / polynomial, a split Gram mode: the support vectors' side of the product, once.  At most 128 features -- or, `every_form`, every width the one-shot
      * call runs on the one-pass split kernels (v2_eligible and not wide_nonlinear: the 128-row full-square kernels with the row panel in registers). */
-    void prepare_resident(const float *sv, hipStream_t s, bool every_form) {
-        const bool beyond128 = round_up(static_cast<long>(nfeat_), 64) > 128;
-        if ((beyond128 && (!every_form || wide_nonlinear(opt_, params_, false, nfeat_))) || opt_.gram_mode == 0 || opt_.tile_kernel == 1) return;
-        if (params_.kernel_type == LSSVM_KERNEL_RBF && (opt_.rbf_form == 1 || opt_.rbf_form == 3)) return;  // (the direct kernel / the grid planes asked for: the one-shot path has them)
-        S_.upload(sv, LSSVM_MEM_HOST, nsv_, nfeat_, 0, s);
-        if (!v2_eligible(opt_, S_.ldx, false)) return;
-        const bool rbf = params_.kernel_type == LSSVM_KERNEL_RBF;
+    bool prepare_or_decline(const PredictModel<float> &m, const float *sv, const float *alpha, bool every_form, hipStream_t s) {
+        const bool beyond128 = round_up(static_cast<long>(m.nfeat), 64) > 128;
+        if ((beyond128 && (!every_form || wide_nonlinear(m.opt, m.params, false, m.nfeat))) || m.opt.gram_mode == 0 || m.opt.tile_kernel == 1) return false;
+        if (m.params.kernel_type == LSSVM_KERNEL_RBF && (m.opt.rbf_form == 1 || m.opt.rbf_form == 3)) return false;  // (the direct kernel / the grid planes asked for: the one-shot path has them)
+        S_.upload(sv, LSSVM_MEM_HOST, m.nsv, m.nfeat, 0, s);
+        if (!v2_eligible(m.opt, S_.ldx, false)) return false;
+        const bool rbf = m.params.kernel_type == LSSVM_KERNEL_RBF;
         if (rbf) {
             column_means<float>(S_, mean_, s);
             const double sq = max_centred_sqnorm<float>(S_, mean_, s);
-            r2_sv_ = 2.0 * static_cast<double>(static_cast<float>(params_.gamma)) * 1.4426950408889634 * sq;
-            if (!(r2_sv_ <= RBF_DIRECT_ABOVE) && opt_.rbf_form != 2) return;  // (beyond the norm expansion's range: grid planes or the direct kernel, one-shot)
-            scale_ = rbf_prescale<float>(params_, false);
+            r2_sv_ = 2.0 * static_cast<double>(static_cast<float>(m.params.gamma)) * 1.4426950408889634 * sq;
+            if (!(r2_sv_ <= RBF_DIRECT_ABOVE) && m.opt.rbf_form != 2) return false;  // (beyond the norm expansion's range: grid planes or the direct kernel, one-shot)
+            scale_ = rbf_prescale<float>(m.params, false);
             // S_ is centred and scaled in place below: the support vectors as they came stay beside it (the one-shot path's input, should a batch need it)
             raw_.alloc_zero(S_.data.count, s);
             LSSVM_HIP_CHECK(hipMemcpyAsync(raw_.p, S_.data.p, S_.data.count * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -545,50 +520,40 @@ class Predictor final : public PredictorBase {
             LSSVM_HIP_CHECK(hipGetLastError());
             half_neg_norms<float>(S_, cS_, s);
         }
-        make_planes(opt_, params_, false, S_, nullptr, planesS_, nullptr, s);
-        if (planesS_.mode == 0) return;
-        num_jt_ = S_.rows_alloc / TILE;
+        make_planes(m.opt, m.params, false, S_, nullptr, planesS_, nullptr, s);
+        if (planesS_.mode == 0) return false;
+        const int num_jt = S_.rows_alloc / TILE;
         const size_t ra = static_cast<size_t>(S_.rows_alloc);
-        a_.alloc_zero(nvec_ * ra, s);  // [nvec][rows_alloc], exact zeros beyond the support vectors
-        LSSVM_HIP_CHECK(hipMemcpy2DAsync(a_.p, ra * sizeof(float), alpha_host_.data(), nsv_ * sizeof(float), nsv_ * sizeof(float), nvec_, hipMemcpyHostToDevice, s));
+        a_.alloc_zero(m.nvec * ra, s);  // [nvec][rows_alloc], exact zeros beyond the support vectors
+        LSSVM_HIP_CHECK(hipMemcpy2DAsync(a_.p, ra * sizeof(float), alpha, m.nsv * sizeof(float), m.nsv * sizeof(float), m.nvec, hipMemcpyHostToDevice, s));
         // The column records of every launch group, once.  Per pair (0,1), (2,3), ... the (alpha0_j | alpha1_j) record of the two-vector kernels -- folded for rbf, the
         // form they exist in; per vector the (alpha_j | c_j) record of the one-vector kernels: for rbf every vector's (the only form an unfolded batch can use: that
         // kernel reads c_j from the record's second half; a batch's OWN exponent scale decides between the forms), otherwise only that of the vector no pair holds
         // (nvec odd; nvec == 1: the single-vector predictor's), and for rbf that vector's folded one-vector record as well.
-        const int ncols = num_jt_ * TILE;
-        rec_ = static_cast<size_t>(num_jt_) * 256;
-        const bool fold = rbf && opt_.rbf_fold != 0;
+        const int ncols = num_jt * TILE;
+        rec_ = static_cast<size_t>(num_jt) * 256;
+        const bool fold = rbf && m.opt.rbf_fold != 0;
         // (beyond 128 features a pair exists only where its launch is dispatched -- wide_pair_routed --; elsewhere every vector keeps the records of a launch of its own)
-        const bool pairs = nvec_ >= 2 && (!rbf || fold) && (planesS_.ldx16 <= 128 || wide_pair_routed(planesS_.mode, params_.kernel_type, params_.degree, planesS_.ldx16 / 64));
-        folded_first_ = pairs ? nvec_ - 1 : 0;
-        dc_.alloc_zero(nvec_ * rec_, s);
-        for (size_t v = (rbf || !pairs) ? 0 : nvec_ - nvec_ % 2; v < nvec_; ++v) enqueue_pack_records(a_.p + v * ra, cS_.p, ncols, dc_.p + v * rec_, 0, static_cast<const float *>(nullptr), s);
-        if (fold && (nvec_ % 2 == 1 || !pairs)) {
-            dc_folded_.alloc_zero((nvec_ - folded_first_) * rec_, s);
-            for (size_t v = folded_first_; v < nvec_; ++v) enqueue_pack_records(a_.p + v * ra, cS_.p, ncols, dc_folded_.p + (v - folded_first_) * rec_, 1, static_cast<const float *>(nullptr), s);
+        const bool pairs = m.nvec >= 2 && (!rbf || fold) && (planesS_.ldx16 <= 128 || wide_pair_routed(planesS_.mode, m.params.kernel_type, m.params.degree, planesS_.ldx16 / 64));
+        folded_first_ = pairs ? m.nvec - 1 : 0;
+        dc_.alloc_zero(m.nvec * rec_, s);
+        for (size_t v = (rbf || !pairs) ? 0 : m.nvec - m.nvec % 2; v < m.nvec; ++v) enqueue_pack_records(a_.p + v * ra, cS_.p, ncols, dc_.p + v * rec_, 0, static_cast<const float *>(nullptr), s);
+        if (fold && (m.nvec % 2 == 1 || !pairs)) {
+            dc_folded_.alloc_zero((m.nvec - folded_first_) * rec_, s);
+            for (size_t v = folded_first_; v < m.nvec; ++v) enqueue_pack_records(a_.p + v * ra, cS_.p, ncols, dc_folded_.p + (v - folded_first_) * rec_, 1, static_cast<const float *>(nullptr), s);
         }
         if (pairs) {
-            dc2_.alloc_zero((nvec_ / 2) * rec_, s);
-            for (size_t g = 0; g < nvec_ / 2; ++g) enqueue_pack_records2(a_.p + 2 * g * ra, a_.p + (2 * g + 1) * ra, cS_.p, ncols, dc2_.p + g * rec_, fold ? 1 : 0, s);
+            dc2_.alloc_zero((m.nvec / 2) * rec_, s);
+            for (size_t g = 0; g < m.nvec / 2; ++g) enqueue_pack_records2(a_.p + 2 * g * ra, a_.p + (2 * g + 1) * ra, cS_.p, ncols, dc2_.p + g * rec_, fold ? 1 : 0, s);
         }
         LSSVM_HIP_CHECK(hipGetLastError());
         LSSVM_HIP_CHECK(hipStreamSynchronize(s));
-        resident_ = true;
+        return true;
     }
 
-    /* the support vectors back on the host, as they came (a resident model keeps no host copy until a batch needs the one-shot path) */
-    void fetch_support_vectors() {
-        if constexpr (std::is_same_v<T, float>) {
-            select_device_checked(0);
-            const float *src = raw_.p != nullptr ? raw_.p : S_.data.p;
-            LSSVM_REQUIRE(src != nullptr, "the predictor holds no support vectors");
-            sv_host_.resize(nsv_ * nfeat_);
-            LSSVM_HIP_CHECK(hipMemcpy2D(sv_host_.data(), nfeat_ * sizeof(float), src, static_cast<size_t>(S_.ldx) * sizeof(float), nfeat_ * sizeof(float), nsv_, hipMemcpyDeviceToHost));
-        }
-    }
-
-    /* a batch of points against the resident support vectors; false = this batch needs the one-shot path */
-    bool predict_resident(const float *points, int mem_kind, size_t npoints, float *out, lssvm_predict_info &info) {
+  public:
+    /* a batch of points against the resident support vectors; false = this batch needs the one-shot path (decided before the product stage allocates anything) */
+    bool predict(const PredictModel<float> &m, const float *points, int mem_kind, size_t npoints, float *out, lssvm_predict_info &info) const {
         select_device_checked(0);
         hipStream_t s = nullptr;
         const double t0 = now_ms();
@@ -602,16 +567,16 @@ class Predictor final : public PredictorBase {
             std::fprintf(stderr, "[plssvm_amd] predictor: %-28s %8.3f ms\n", what, t - t_last);
             t_last = t;
         };
-        const bool rbf = params_.kernel_type == LSSVM_KERNEL_RBF;
+        const bool rbf = m.params.kernel_type == LSSVM_KERNEL_RBF;
         DeviceMatrix<float> P;
-        P.upload(points, mem_kind, npoints, nfeat_, static_cast<size_t>(round_up(static_cast<long>(npoints), 2 * TILE)), s);
+        P.upload(points, mem_kind, npoints, m.nfeat, static_cast<size_t>(round_up(static_cast<long>(npoints), 2 * TILE)), s);
         lap(mem_kind == LSSVM_MEM_DEVICE ? "points copied in HBM" : "points uploaded");
         DevBuf<float> cP;
         double r2 = r2_sv_;
         if (rbf) {
             const double sq = max_centred_sqnorm<float>(P, mean_, s);  // (against the SUPPORT VECTORS' means: the centre the resident side was prepared with)
-            r2 = std::max(r2, 2.0 * static_cast<double>(static_cast<float>(params_.gamma)) * 1.4426950408889634 * sq);
-            if (!(r2 <= RBF_DIRECT_ABOVE) && opt_.rbf_form != 2) return false;  // this batch reaches beyond the norm expansion's range
+            r2 = std::max(r2, 2.0 * static_cast<double>(static_cast<float>(m.params.gamma)) * 1.4426950408889634 * sq);
+            if (!(r2 <= RBF_DIRECT_ABOVE) && m.opt.rbf_form != 2) return false;  // this batch reaches beyond the norm expansion's range
             hipLaunchKernelGGL(k_center<float>, dim3((P.dfeat + 255) / 256, P.rows), dim3(256), 0, s, P.data.p, P.ldx, P.dfeat, P.rows, mean_.p, scale_);
             LSSVM_HIP_CHECK(hipGetLastError());
             half_neg_norms<float>(P, cP, s);
@@ -644,206 +609,38 @@ class Predictor final : public PredictorBase {
             x2 = std::max(x2, planesS_.f16_x2);
             const bool ok = f16_planes_pass(rbf, rel2, rest2, x2);
             info.f16_row_rel_error = std::sqrt(static_cast<double>(rel2));
-            if (!ok && opt_.gram_mode != 2) return false;  // the support vectors' planes are f16, the pair needs bf16: one-shot (which splits both sides alike)
+            if (!ok && m.opt.gram_mode != 2) return false;  // the support vectors' planes are f16, the pair needs bf16: one-shot (which splits both sides alike)
         } else {
             split_bf16_planes(P.data.p, P.ldx, P.dfeat, static_cast<size_t>(P.rows_alloc), planesP.ldx16, planesP.buf.p, static_cast<size_t>(P.rows_alloc) * planesP.ldx16, s);
         }
         lap("operand planes");
-        const int num_ib = P.rows_alloc / TILE;
-        const bool folded = rbf && opt_.rbf_fold != 0 && r2 <= FOLD_MAX_R2;
-        const bool poly_generic = params_.kernel_type == LSSVM_KERNEL_POLYNOMIAL && params_.degree != 2 && params_.degree != 3;
-        const bool rbf_ok = !rbf || (folded && r2 <= 2.0 * PAIR_FOLD_MAX_C);
+        const bool folded = rbf && m.opt.rbf_fold != 0 && r2 <= FOLD_MAX_R2;
         // (the rectangular 256-row kernel exists up to 128 features; wider models take the 128-row full-square kernels at every batch size, as in the one-shot call)
-        const bool rect = planesS_.ldx16 <= 128 && !poly_generic && rbf_ok && opt_.mfma_shape >= 3 && num_ib >= PAIR_MIN_TILES;
-        const long rect_tiles = std::min<long>(64, std::max<long>(4, (static_cast<long>(num_ib / 2) * num_jt_ + 1024) / 2048));
-        const int jc_tiles = opt_.j_chunk_tiles > 0 ? static_cast<int>(opt_.j_chunk_tiles)
-                                                   : (rect ? static_cast<int>(rect_tiles) : static_cast<int>(std::min<long>(16, std::max<long>(2, (static_cast<long>(num_ib) * num_jt_ + 2048) / 4096))));
-        const int num_jc = (num_jt_ + jc_tiles - 1) / jc_tiles;
+        const bool rect = rect_kernel_applies(m.opt, m.params, planesS_.ldx16, folded, r2, P.rows_alloc / TILE);
         // Two weight vectors per product launch wherever a pair record exists in the form this batch needs: the rectangular 256-row kernel under its conditions, the
         // 128-row full-square kernels otherwise (polynomial of any degree, folded rbf).  Unfolded rbf keeps c_j in the record's second half: one vector per launch.
-        const int nv = static_cast<int>(nvec_);
-        const int per_launch = (nv >= 2 && dc2_.p != nullptr && (!rbf || folded)) ? 2 : 1;
-        const size_t part_plane = static_cast<size_t>(num_jc) * P.rows_alloc;
-        DevBuf<float> partial, Kv, o;
-        partial.alloc_zero(per_launch * part_plane, s);
-        Kv.alloc_zero(P.rows_alloc, s);
-        o.alloc_zero(npoints * nvec_, s);
-        TileArgs<float> ta{};
-        ta.Xr = P.data.p;
-        ta.Xc = S_.data.p;
-        ta.cr = cP.p;
-        ta.cc = cS_.p;
+        const int per_launch = (m.nvec >= 2 && dc2_.p != nullptr && (!rbf || folded)) ? 2 : 1;
+        ProductStage<float> stage(m.opt, P, S_, rect, a_.p, m.rho.data(), m.nvec, per_launch, s, t0);
+        const auto records = [&](int v, int count) -> const float * {
+            if (count == 2) return dc2_.p + static_cast<size_t>(v / 2) * rec_;
+            if (folded) return dc_folded_.p + (static_cast<size_t>(v) - folded_first_) * rec_;  // (folded and alone: the vector no pair holds -- or, where pairs are not dispatched, every vector)
+            return dc_.p + static_cast<size_t>(v) * rec_;
+        };
+        TileArgs<float> ta = stage.args(m.params, false, cP.p, cS_.p, records);
         ta.dc_folded = folded ? 1 : 0;
-        ta.partial = partial.p;
-        ta.part_stride = P.rows_alloc;
-        ta.ldx = S_.ldx;
-        ta.kchunks = S_.ldx / F32_KC;
-        ta.num_ib = num_ib;
-        ta.num_jt = num_jt_;
-        ta.jc_tiles = jc_tiles;
-        ta.ncols_valid = S_.rows;
-        set_kernel_scalars(ta, params_, false);
-        set_plane_args(ta, params_, planesS_, planesP, static_cast<size_t>(S_.rows_alloc), static_cast<size_t>(P.rows_alloc));
-        set_launch_options(ta, opt_);
+        set_plane_args(ta, m.params, planesS_, planesP, static_cast<size_t>(S_.rows_alloc), static_cast<size_t>(P.rows_alloc));
         RectSetup rect_setup;
-        if (rect) setup_rect_launch(ta, rect_setup, planesP, P.rows_alloc, num_ib, num_jc, s);
-        LaunchTimer timer(nvec_);
-        LSSVM_HIP_CHECK(hipStreamSynchronize(s));
-        lap(rect ? "slabs, 256-row launch set up" : "slabs");
-        const double t_kernel = now_ms();
-        for (int v = 0; v < nv; v += per_launch) {
-            const int count = std::min(per_launch, nv - v);
-            if (v > 0 && ta.queue != nullptr) std::swap(ta.queue, ta.queue_next);  // (a persistent launch zeroes the OTHER set of counters)
-            ta.dvec = a_.p + static_cast<size_t>(v) * S_.rows_alloc;
-            if (count == 2) {
-                ta.dc = dc2_.p + static_cast<size_t>(v / 2) * rec_;
-            } else if (folded) {  // (folded and alone: the vector no pair holds -- or, where pairs are not dispatched, every vector)
-                ta.dc = dc_folded_.p + (static_cast<size_t>(v) - folded_first_) * rec_;
-            } else {
-                ta.dc = dc_.p + static_cast<size_t>(v) * rec_;
-            }
-            ta.nvec = count;
-            ta.part_vstride = count == 2 ? static_cast<long>(part_plane) : 0;
-            timer.timed(s, [&] { launch_tile_kernel<float>(ta, params_.kernel_type, false, num_jc, s); });
-            for (int u = 0; u < count; ++u) {
-                hipLaunchKernelGGL(k_reduce_partials<float>, dim3((P.rows_alloc + 255) / 256), dim3(256), 0, s, partial.p + u * part_plane, ta.part_stride, num_jc, 0, P.rows_alloc, Kv.p);
-                hipLaunchKernelGGL(k_sub_rho<float>, dim3((P.rows + 255) / 256), dim3(256), 0, s, Kv.p, P.rows, rho_[static_cast<size_t>(v + u)], o.p + (v + u), nv);
-            }
-        }
-        LSSVM_HIP_CHECK(hipGetLastError());
-        lap("product, row sums");
-        LSSVM_HIP_CHECK(hipMemcpyAsync(out, o.p, npoints * nvec_ * sizeof(float), mem_kind == LSSVM_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
-        LSSVM_HIP_CHECK(hipStreamSynchronize(s));
-        lap("values downloaded");
-        timer.sum_into(info);
-        info.total_ms = now_ms() - t0;
-        info.setup_ms = t_kernel - t0;
+        if (rect) setup_rect_launch(ta, rect_setup, planesP, P.rows_alloc, stage.num_ib, stage.chunks.num_jc, s);
+        stage.run(ta, m.params.kernel_type, false, records, out, mem_kind, info, lap);
         info.gram_mode = planesS_.mode;
         info.rbf_direct = 0;
         info.rbf_exponent_scale = r2;
         if (info.f16_row_rel_error < 0.0) info.f16_row_rel_error = planesS_.f16_row_rel_error;
         info.resident = 1;
-        info.vectors_per_launch = per_launch;
         return true;
     }
 
-    /* fp64, rbf / polynomial (gamma > 0) on the one-pass v2 kernel (at most 256 padded features, tile_kernel != 1): the support vectors' side of the product, once,
-     * prepared as predict_values_impl<double> prepares it -- the same padding, centre, scale and records, so that a batch's values have the one-shot call's bits.  fp64
-     * rbf has no direct form and no plane check: this form never declines a batch and keeps no host copy of the support vectors. */
-    void prepare_resident_f64(const double *sv, hipStream_t s) {
-        const bool rbf = params_.kernel_type == LSSVM_KERNEL_RBF;
-        if (!(rbf || params_.kernel_type == LSSVM_KERNEL_POLYNOMIAL) || !(params_.gamma > 0.0)) return;
-        if (!v2_eligible_f64(opt_, padded_features<double>(nfeat_))) return;
-        S64_.upload(sv, LSSVM_MEM_HOST, nsv_, nfeat_, 0, s);
-        const dim3 cgrid((S64_.dfeat + 255) / 256, S64_.rows);
-        if (rbf) {
-            scale64_ = rbf_prescale<double>(params_, true);
-            column_means<double>(S64_, mean64_, s);
-            hipLaunchKernelGGL(k_center<double>, cgrid, dim3(256), 0, s, S64_.data.p, S64_.ldx, S64_.dfeat, S64_.rows, mean64_.p, scale64_);
-            LSSVM_HIP_CHECK(hipGetLastError());
-            half_neg_norms<double>(S64_, cS64_, s);
-        } else {  // the polynomial runs on data that carries sqrt(gamma), with gamma = 1 in the launch arguments
-            scale64_ = std::sqrt(params_.gamma);
-            hipLaunchKernelGGL(k_center<double>, cgrid, dim3(256), 0, s, S64_.data.p, S64_.ldx, S64_.dfeat, S64_.rows, static_cast<const double *>(nullptr), scale64_);
-            LSSVM_HIP_CHECK(hipGetLastError());
-        }
-        num_jt_ = S64_.rows_alloc / TILE;
-        const size_t ra = static_cast<size_t>(S64_.rows_alloc);
-        a64_.alloc_zero(nvec_ * ra, s);  // [nvec][rows_alloc], exact zeros beyond the support vectors
-        LSSVM_HIP_CHECK(hipMemcpy2DAsync(a64_.p, ra * sizeof(double), alpha_host_.data(), nsv_ * sizeof(double), nsv_ * sizeof(double), nvec_, hipMemcpyHostToDevice, s));
-        // The column records of every launch group, once: per pair (0,1), (2,3), ... the (d0_j | d1_j | c_j) record of the two-vector kernel, and the single-vector
-        // (d_j | c_j) record of the vector no pair holds (nvec odd; nvec == 1).  Every (kernel function, chunk count) instantiation of the two-vector kernel takes less
-        // than two single-vector launches (profiles/predictor_f64.json, launch_level: 0.46 ... 0.58 of two), so every pair is launched as a pair.
-        const int ncols = num_jt_ * TILE;
-        rec_ = static_cast<size_t>(num_jt_) * 256;
-        rec2_ = static_cast<size_t>(num_jt_) * 2 * 192;
-        if (nvec_ % 2 == 1) {
-            dc64_.alloc_zero(rec_, s);
-            enqueue_pack_records(a64_.p + (nvec_ - 1) * ra, cS64_.p, ncols, dc64_.p, 0, static_cast<const double *>(nullptr), s);
-        }
-        if (nvec_ >= 2) {
-            dc2_64_.alloc_zero((nvec_ / 2) * rec2_, s);
-            for (size_t g = 0; g < nvec_ / 2; ++g) enqueue_pack_records2(a64_.p + 2 * g * ra, a64_.p + (2 * g + 1) * ra, cS64_.p, ncols, dc2_64_.p + g * rec2_, s);
-        }
-        LSSVM_HIP_CHECK(hipGetLastError());
-        LSSVM_HIP_CHECK(hipStreamSynchronize(s));
-        resident_ = true;
-    }
-
-    /* a batch of points against the resident fp64 support vectors: the steps of predict_values_impl<double> from the points' upload on */
-    bool predict_resident_f64(const double *points, int mem_kind, size_t npoints, double *out, lssvm_predict_info &info) {
-        select_device_checked(0);
-        hipStream_t s = nullptr;
-        const double t0 = now_ms();
-        const bool rbf = params_.kernel_type == LSSVM_KERNEL_RBF;
-        DeviceMatrix<double> P;
-        P.upload(points, mem_kind, npoints, nfeat_, static_cast<size_t>(round_up(static_cast<long>(npoints), 2 * TILE)), s);
-        DevBuf<double> cP;
-        // (against the SUPPORT VECTORS' means and with their scale: what center_columns(S, &P, ...) does in the one-shot call)
-        hipLaunchKernelGGL(k_center<double>, dim3((P.dfeat + 255) / 256, P.rows), dim3(256), 0, s, P.data.p, P.ldx, P.dfeat, P.rows, rbf ? mean64_.p : static_cast<const double *>(nullptr), scale64_);
-        LSSVM_HIP_CHECK(hipGetLastError());
-        if (rbf) half_neg_norms<double>(P, cP, s);
-        const int num_ib = P.rows_alloc / TILE;
-        const int jc_tiles = opt_.j_chunk_tiles > 0 ? static_cast<int>(opt_.j_chunk_tiles) : static_cast<int>(std::min<long>(16, std::max<long>(2, (static_cast<long>(num_ib) * num_jt_ + 2048) / 4096)));
-        const int num_jc = (num_jt_ + jc_tiles - 1) / jc_tiles;
-        const int nv = static_cast<int>(nvec_);
-        const int per_launch = nv >= 2 ? 2 : 1;
-        const size_t part_plane = static_cast<size_t>(num_jc) * P.rows_alloc;
-        DevBuf<double> partial, Kv, o;
-        partial.alloc_zero(per_launch * part_plane, s);
-        Kv.alloc_zero(P.rows_alloc, s);
-        o.alloc_zero(npoints * nvec_, s);
-        TileArgs<double> ta{};
-        ta.Xr = P.data.p;
-        ta.Xc = S64_.data.p;
-        ta.cr = cP.p;
-        ta.cc = cS64_.p;
-        ta.partial = partial.p;
-        ta.part_stride = P.rows_alloc;
-        ta.ldx = S64_.ldx;
-        ta.kchunks = S64_.ldx / F64_KC;
-        ta.num_ib = num_ib;
-        ta.num_jt = num_jt_;
-        ta.jc_tiles = jc_tiles;
-        ta.ncols_valid = S64_.rows;
-        set_kernel_scalars(ta, params_, false);
-        if (!rbf) ta.gamma = 1.0;
-        set_launch_options(ta, opt_);
-        LaunchTimer timer(nvec_);
-        LSSVM_HIP_CHECK(hipStreamSynchronize(s));
-        const double t_kernel = now_ms();
-        for (int v = 0; v < nv; v += per_launch) {
-            const int count = std::min(per_launch, nv - v);
-            ta.dvec = a64_.p + static_cast<size_t>(v) * S64_.rows_alloc;
-            ta.dc = count == 2 ? dc2_64_.p + static_cast<size_t>(v / 2) * rec2_ : dc64_.p;  // (alone: the vector no pair holds)
-            ta.nvec = count;
-            ta.part_vstride = count == 2 ? static_cast<long>(part_plane) : 0;
-            timer.timed(s, [&] { launch_tile_kernel<double>(ta, params_.kernel_type, false, num_jc, s); });
-            for (int u = 0; u < count; ++u) {
-                hipLaunchKernelGGL(k_reduce_partials<double>, dim3((P.rows_alloc + 255) / 256), dim3(256), 0, s, partial.p + u * part_plane, ta.part_stride, num_jc, 0, P.rows_alloc, Kv.p);
-                hipLaunchKernelGGL(k_sub_rho<double>, dim3((P.rows + 255) / 256), dim3(256), 0, s, Kv.p, P.rows, rho_[static_cast<size_t>(v + u)], o.p + (v + u), nv);
-            }
-        }
-        LSSVM_HIP_CHECK(hipGetLastError());
-        LSSVM_HIP_CHECK(hipMemcpyAsync(out, o.p, npoints * nvec_ * sizeof(double), mem_kind == LSSVM_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
-        LSSVM_HIP_CHECK(hipStreamSynchronize(s));
-        timer.sum_into(info);
-        info.total_ms = now_ms() - t0;
-        info.setup_ms = t_kernel - t0;
-        info.resident = 1;
-        info.vectors_per_launch = per_launch;
-        return true;
-    }
-
-    Options opt_;
-    lssvm_params params_;
-    size_t nsv_, nfeat_, nvec_;
-    std::vector<T> rho_;
-    std::vector<T> sv_host_, alpha_host_, w_host_;  // the one-shot path's inputs
-    DevBuf<T> w_;                                   // linear kernel: [nvec][ldw_]
-    size_t ldw_ = 0;
-    // fp32 resident form
-    bool resident_ = false;
+  private:
     DeviceMatrix<float> S_;
     DevBuf<float> mean_, cS_, a_, raw_;
     DevBuf<float> dc_, dc_folded_, dc2_;  // column records: [nvec][rec_] per vector, the folded one of an unpaired last vector, [nvec / 2][rec_] per pair
@@ -852,13 +649,198 @@ class Predictor final : public PredictorBase {
     PlaneSet planesS_;
     double r2_sv_ = 0.0;
     float scale_ = 1.0f;
-    int num_jt_ = 0;
-    // fp64 resident form (lssvm_mi355_predictor_create_resident)
-    DeviceMatrix<double> S64_;
-    DevBuf<double> mean64_, cS64_, a64_;
-    DevBuf<double> dc64_, dc2_64_;  // column records: [rec_] of the vector no pair holds, [nvec / 2][rec2_] per pair
+};
+
+/* (lssvm_mi355_predictor_create_resident only: `every_form`) */
+class ResidentF64 {
+  public:
+    static constexpr bool declines_batches = false;
+
+    /* fp64, rbf / polynomial (gamma > 0) on the one-pass v2 kernel (at most 256 padded features, tile_kernel != 1): the support vectors' side of the product, once,
+     * prepared as predict_values_impl<double> prepares it -- the same padding, centre, scale and records, so that a batch's values have the one-shot call's bits.  fp64
+     * rbf has no direct form and no plane check: this form never declines a batch and keeps no host copy of the support vectors. */
+    bool prepare(const PredictModel<double> &m, const double *sv, const double *alpha, bool every_form, hipStream_t s) {
+        const bool rbf = m.params.kernel_type == LSSVM_KERNEL_RBF;
+        if (!every_form || !(rbf || m.params.kernel_type == LSSVM_KERNEL_POLYNOMIAL) || !(m.params.gamma > 0.0)) return false;
+        if (!v2_eligible_f64(m.opt, padded_features<double>(m.nfeat))) return false;
+        S_.upload(sv, LSSVM_MEM_HOST, m.nsv, m.nfeat, 0, s);
+        const dim3 cgrid((S_.dfeat + 255) / 256, S_.rows);
+        if (rbf) {
+            scale_ = rbf_prescale<double>(m.params, true);
+            column_means<double>(S_, mean_, s);
+            hipLaunchKernelGGL(k_center<double>, cgrid, dim3(256), 0, s, S_.data.p, S_.ldx, S_.dfeat, S_.rows, mean_.p, scale_);
+            LSSVM_HIP_CHECK(hipGetLastError());
+            half_neg_norms<double>(S_, cS_, s);
+        } else {  // the polynomial runs on data that carries sqrt(gamma), with gamma = 1 in the launch arguments
+            scale_ = std::sqrt(m.params.gamma);
+            hipLaunchKernelGGL(k_center<double>, cgrid, dim3(256), 0, s, S_.data.p, S_.ldx, S_.dfeat, S_.rows, static_cast<const double *>(nullptr), scale_);
+            LSSVM_HIP_CHECK(hipGetLastError());
+        }
+        const int num_jt = S_.rows_alloc / TILE;
+        const size_t ra = static_cast<size_t>(S_.rows_alloc);
+        a_.alloc_zero(m.nvec * ra, s);  // [nvec][rows_alloc], exact zeros beyond the support vectors
+        LSSVM_HIP_CHECK(hipMemcpy2DAsync(a_.p, ra * sizeof(double), alpha, m.nsv * sizeof(double), m.nsv * sizeof(double), m.nvec, hipMemcpyHostToDevice, s));
+        // The column records of every launch group, once: per pair (0,1), (2,3), ... the (d0_j | d1_j | c_j) record of the two-vector kernel, and the single-vector
+        // (d_j | c_j) record of the vector no pair holds (nvec odd; nvec == 1).  Every (kernel function, chunk count) instantiation of the two-vector kernel takes less
+        // than two single-vector launches (profiles/predictor_f64.json, launch_level: 0.46 ... 0.58 of two), so every pair is launched as a pair.
+        const int ncols = num_jt * TILE;
+        rec2_ = static_cast<size_t>(num_jt) * 2 * 192;
+        if (m.nvec % 2 == 1) {
+            dc_.alloc_zero(static_cast<size_t>(num_jt) * 256, s);
+            enqueue_pack_records(a_.p + (m.nvec - 1) * ra, cS_.p, ncols, dc_.p, 0, static_cast<const double *>(nullptr), s);
+        }
+        if (m.nvec >= 2) {
+            dc2_.alloc_zero((m.nvec / 2) * rec2_, s);
+            for (size_t g = 0; g < m.nvec / 2; ++g) enqueue_pack_records2(a_.p + 2 * g * ra, a_.p + (2 * g + 1) * ra, cS_.p, ncols, dc2_.p + g * rec2_, s);
+        }
+        LSSVM_HIP_CHECK(hipGetLastError());
+        LSSVM_HIP_CHECK(hipStreamSynchronize(s));
+        return true;
+    }
+
+    /* a batch of points against the resident fp64 support vectors, prepared as predict_values_impl<double> prepares its points */
+    bool predict(const PredictModel<double> &m, const double *points, int mem_kind, size_t npoints, double *out, lssvm_predict_info &info) const {
+        select_device_checked(0);
+        hipStream_t s = nullptr;
+        const double t0 = now_ms();
+        const bool rbf = m.params.kernel_type == LSSVM_KERNEL_RBF;
+        DeviceMatrix<double> P;
+        P.upload(points, mem_kind, npoints, m.nfeat, static_cast<size_t>(round_up(static_cast<long>(npoints), 2 * TILE)), s);
+        DevBuf<double> cP;
+        // (against the SUPPORT VECTORS' means and with their scale: what center_columns(S, &P, ...) does in the one-shot call)
+        hipLaunchKernelGGL(k_center<double>, dim3((P.dfeat + 255) / 256, P.rows), dim3(256), 0, s, P.data.p, P.ldx, P.dfeat, P.rows, rbf ? mean_.p : static_cast<const double *>(nullptr), scale_);
+        LSSVM_HIP_CHECK(hipGetLastError());
+        if (rbf) half_neg_norms<double>(P, cP, s);
+        ProductStage<double> stage(m.opt, P, S_, false, a_.p, m.rho.data(), m.nvec, m.nvec >= 2 ? 2 : 1, s, t0);
+        const auto records = [&](int v, int count) -> const double * {
+            return count == 2 ? dc2_.p + static_cast<size_t>(v / 2) * rec2_ : dc_.p;  // (alone: the vector no pair holds)
+        };
+        TileArgs<double> ta = stage.args(m.params, false, cP.p, cS_.p, records);
+        if (!rbf) ta.gamma = 1.0;
+        stage.run(ta, m.params.kernel_type, false, records, out, mem_kind, info, no_lap);
+        info.resident = 1;
+        return true;
+    }
+
+  private:
+    DeviceMatrix<double> S_;
+    DevBuf<double> mean_, cS_, a_;
+    DevBuf<double> dc_, dc2_;  // column records: [num_jt][256] of the vector no pair holds, [nvec / 2][rec2_] per pair
     size_t rec2_ = 0;
-    double scale64_ = 1.0;
+    double scale_ = 1.0;
+};
+
+/* `nvec` weight vectors over the same support vectors (lssvm_mi355_predictor_create: one; _create_multi: a one-vs-all model's k).  The linear kernel keeps w per vector;
+ * an rbf / polynomial model keeps its real type's resident form where it has one, and the one-shot path's inputs where a batch may need them.
+ * `every_form` (lssvm_mi355_predictor_create_resident): fp64 rbf / polynomial models on at most 256 padded features are resident as well (ResidentF64), and so are fp32
+ * models of 129 ... 512 features on the one-pass split kernels (ResidentF32); without it such a model goes through the one-shot path, as _create / _create_multi
+ * document. */
+template <typename T>
+class Predictor final : public PredictorBase {
+    using Resident = std::conditional_t<std::is_same_v<T, float>, ResidentF32, ResidentF64>;
+
+  public:
+    Predictor(const Options &opt, const lssvm_params &params, const T *sv, size_t nsv, size_t nfeat, const T *alpha, const double *rho, size_t nvec, bool every_form) :
+        m_{ opt, params, nsv, nfeat, nvec, {} } {
+        dtype = std::is_same_v<T, float> ? LSSVM_DTYPE_F32 : LSSVM_DTYPE_F64;
+        check_params(&m_.params);
+        LSSVM_REQUIRE(nvec > 0 && rho != nullptr, "a predictor needs at least one weight vector and its rho");
+        LSSVM_REQUIRE(nvec <= static_cast<size_t>(1) << 20, "too many weight vectors");
+        LSSVM_REQUIRE(sv != nullptr && nsv > 0, "The support vectors must not be empty!");   // csvm.cpp:189
+        LSSVM_REQUIRE(nfeat > 0, "The support vectors must contain at least one feature!");  // csvm.cpp:190
+        LSSVM_REQUIRE(alpha != nullptr, "The number of support vectors and number of weights must be the same!");
+        m_.rho.resize(nvec);
+        for (size_t v = 0; v < nvec; ++v) m_.rho[v] = static_cast<T>(rho[v]);
+        select_device_checked(0);
+        hipStream_t s = nullptr;
+        if (params.kernel_type == LSSVM_KERNEL_LINEAR) {
+            // the linear kernel predicts through w = sum_i alpha_i sv_i (csvm.cpp:204-213): computed once per vector, resident zero padded like a row of points
+            std::vector<T> w_host(nvec * nfeat, T(0));
+            calculate_w_multi<T>(sv, nsv, nfeat, alpha, nvec, w_host.data());
+            ldw_ = static_cast<size_t>(padded_features<T>(nfeat));
+            w_.alloc_zero(nvec * ldw_, s);
+            LSSVM_HIP_CHECK(hipMemcpy2DAsync(w_.p, ldw_ * sizeof(T), w_host.data(), nfeat * sizeof(T), nfeat * sizeof(T), nvec, hipMemcpyHostToDevice, s));
+            LSSVM_HIP_CHECK(hipStreamSynchronize(s));
+            return;
+        }
+        resident_ = resident_form_.prepare(m_, sv, alpha, every_form, s);
+        // the one-shot path's inputs: host copies where nothing is resident; a resident model that may decline a batch keeps alpha, leaves its support vectors as they
+        // came in HBM and fetches them if a batch ever asks
+        if (!resident_ || Resident::declines_batches) alpha_host_.assign(alpha, alpha + nvec * nsv);
+        if (!resident_) sv_host_.assign(sv, sv + nsv * nfeat);
+    }
+
+    void predict(const void *points_v, int mem_kind, size_t npoints, void *out_v, lssvm_predict_info *info, bool multi) override {
+        const T *points = static_cast<const T *>(points_v);
+        T *out = static_cast<T *>(out_v);
+        LSSVM_REQUIRE(points != nullptr && npoints > 0, "The data points to predict must not be empty!");  // csvm.cpp:194
+        LSSVM_REQUIRE(out != nullptr, "out must not be NULL");
+        LSSVM_REQUIRE(multi || m_.nvec == 1, "this predictor holds more than one weight vector: use lssvm_mi355_predictor_predict_multi");
+        lssvm_predict_info local{};
+        local.f16_row_rel_error = -1.0;
+        bool done = false;
+        if (m_.params.kernel_type == LSSVM_KERNEL_LINEAR) {
+            predict_linear(points, mem_kind, npoints, out, local);
+            done = true;
+        } else if (resident_) {
+            done = resident_form_.predict(m_, points, mem_kind, npoints, out, local);
+        }
+        if (!done) {
+            // what the resident form does not cover (outside lssvm_mi355_predictor_create_resident: fp64, and fp32 on more than 128 features; with it: fp64 beyond 256
+            // features and fp32 beyond the one-pass split kernels' 512 / 384; gram_mode 0, tile_kernel 1, rbf_form 1 / 3; exponent scales beyond the norm expansion; a
+            // batch whose planes fail the f16 check or that lies further from the support vectors' centre than the form chosen for them allows): the one-shot path,
+            // same result
+            int w_valid = 0;
+            std::vector<T> w_tmp(m_.nvec * m_.nfeat);
+            if constexpr (Resident::declines_batches) {
+                if (sv_host_.empty()) resident_form_.fetch_support_vectors(m_, sv_host_);
+            }
+            const auto one_shot = [&](const T *pts, T *values) {
+                if (multi) {
+                    predict_values_multi<T>(m_.opt, m_.params, sv_host_.data(), m_.nsv, m_.nfeat, alpha_host_.data(), m_.rho.data(), m_.nvec, w_tmp.data(), &w_valid, pts, npoints, values, &local);
+                } else {
+                    predict_values<T>(m_.opt, m_.params, sv_host_.data(), m_.nsv, m_.nfeat, alpha_host_.data(), m_.rho[0], w_tmp.data(), &w_valid, pts, npoints, values, &local);
+                }
+            };
+            if (mem_kind == LSSVM_MEM_DEVICE) {  // (the one-shot entry point takes host buffers: a batch in HBM makes the round trip here -- the rare path)
+                select_device_checked(0);
+                std::vector<T> points_host(npoints * m_.nfeat), out_host(npoints * m_.nvec);
+                LSSVM_HIP_CHECK(hipMemcpy(points_host.data(), points, points_host.size() * sizeof(T), hipMemcpyDeviceToHost));
+                one_shot(points_host.data(), out_host.data());
+                LSSVM_HIP_CHECK(hipMemcpy(out, out_host.data(), out_host.size() * sizeof(T), hipMemcpyHostToDevice));
+            } else {
+                one_shot(points, out);
+            }
+            local.resident = 0;
+        }
+        if (!multi) local.vectors_per_launch = 0;  // (vectors_per_launch is the multi calls' report)
+        if (info != nullptr) *info = local;
+    }
+
+  private:
+    void predict_linear(const T *points, int mem_kind, size_t npoints, T *out, lssvm_predict_info &info) {
+        select_device_checked(0);
+        hipStream_t s = nullptr;
+        const double t0 = now_ms();
+        const int nv = static_cast<int>(m_.nvec);
+        LaunchTimer timer(m_.nvec);
+        DeviceMatrix<T> P;
+        P.upload(points, mem_kind, npoints, m_.nfeat, 0, s);
+        DevBuf<T> o;
+        o.alloc_zero(npoints * m_.nvec, s);
+        LSSVM_HIP_CHECK(hipStreamSynchronize(s));
+        const double t_kernel = now_ms();
+        for (int v = 0; v < nv; ++v) timer.timed(s, [&] { launch_predict_linear<T>(P, w_.p + static_cast<size_t>(v) * ldw_, m_.rho[static_cast<size_t>(v)], o.p + v, s, nv); });
+        finish_predict(timer, o, out, mem_kind, s, t0, t_kernel, 1, info, no_lap);
+        info.resident = 1;
+    }
+
+    PredictModel<T> m_;
+    std::vector<T> sv_host_, alpha_host_;  // the one-shot path's inputs
+    DevBuf<T> w_;                          // linear kernel: [nvec][ldw_]
+    size_t ldw_ = 0;
+    bool resident_ = false;
+    Resident resident_form_;
 };
 
 std::unique_ptr<PredictorBase> make_predictor(const Options &opt, const lssvm_params &params, int dtype, const void *sv, size_t nsv, size_t nfeat, const void *alpha, const double *rho,

@@ -509,7 +509,7 @@ __global__ __launch_bounds__(PR_THREADS, 2) LSSVM_HAND_VGPR_CAP void tile_matvec
 }
 
 /* The rectangular instance (predict_values): one work item = a pair of row blocks of the points x a chunk of the support vectors' column tiles; the item list covers the
- * whole rectangle (Problem-less: lssvm_problem.hip, predict_values_impl builds it), persistent launches as above. */
+ * whole rectangle (Problem-less: lssvm_predict.hip, setup_rect_launch builds it), persistent launches as above. */
 template <int KT, int NK64, int PL, int NV = 1>
 __global__ __launch_bounds__(PR_THREADS, 2) LSSVM_HAND_VGPR_CAP void tile_matvec_f32_pair_rect(const TileArgs<float> a) {
     const bool first_half = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6) < 4;
