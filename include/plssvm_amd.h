@@ -450,6 +450,53 @@ int lssvm_mi355_solve_cost_path_f64(const lssvm_params *params, const double *X,
                                     size_t num_costs, double eps, uint64_t max_iter, int verify, double *alphas_out, double *rhos_out,
                                     lssvm_path_info *infos_out, uint64_t passes_out[2], const lssvm_mi355_options *options);
 
+/* Nystrom-preconditioned CG on a resident problem (opt-in).  With n = N - 1, sigma = 1 / C, E = [I_n | -1] and H = K + sigma I the reduced
+ * matrix of the recipe is the congruence Abar = E H E^T.  From `rank` = m landmark points the library forms K_Nm and K_mm, factors L L^T = K_mm + nu I on the host in
+ * double (nu starts at eps64 trace(K_mm) and is raised tenfold, six times at most, while the factorisation fails), B_f = K_Nm L^-T, Bhat = [E B_f | sqrt(sigma) 1]
+ * (n x (m + 1), stored once in the problem's dtype) and G = Bhat^T Bhat + sigma I (double; factored and inverted on the host).  The preconditioner is
+ * P = E (B_f B_f^T + sigma I) E^T = Bhat Bhat^T + sigma I, symmetric positive definite by construction, applied as z = r - Bhat G^-1 Bhat^T r = sigma P^-1 r (PCG does
+ * not see the factor).  It uses the cost of the problem's lssvm_params.  It pays where the kernel matrix has spectral decay and COSTS iterations where it has none and
+ * the rank is small (README.md has both kinds of row): nothing selects it automatically.
+ * build_preconditioner: 1 <= rank <= min(N - 1, 512).  landmarks: `rank` distinct indices < N (the last point is allowed), or NULL for the library's choice -- the first
+ * `rank` entries of a Fisher-Yates shuffle of 0 ... N-1 (for i = 0 ... rank-1: swap entry i with entry i + next() mod (N - i)), next() = splitmix64 from the state
+ * 0x243F6A8885A308D3: the same landmarks for the same N.  Building again replaces the preconditioner; lssvm_mi355_problem_destroy frees it.  info may be NULL.
+ * precond_landmarks: the `rank` landmarks in use.  precond_apply: host vectors of n = N - 1 entries of the problem's dtype, z = r - Bhat G^-1 Bhat^T r (the operator alone).
+ * solve_pcg: the right-hand sides of Y (num_rhs x N) one after the other on the ONE preconditioner, in the frame of lssvm_mi355_solve_*: x0 = 1, r0 = b - Abar 1, stop at
+ * |r|^2 <= eps^2 |r0|^2 on the unpreconditioned recurrence residual (so eps means what it means there, and iteration counts compare), the true residual every 50th
+ * iteration; alpha_N and rho as lssvm_mi355_cg_finish forms them.  Row c of alphas_out (num_rhs x N), rhos_out[c], infos_out[c] belong to right-hand side c.  One Gram
+ * pass per iteration (plus the refreshes); the problem is left as it was.  Deterministic: fixed-order reductions, the same bits for the same arguments.
+ * LSSVM_ERR_INVALID_ARGUMENT: a problem on several devices or ranks, weights set on the problem, a call between cg_begin and cg_finish, solve_pcg / precond_apply /
+ * precond_landmarks without a preconditioner; a rank outside its range, duplicate or out-of-range landmarks; eps <= 0 (or not finite), max_iter == 0, num_rhs == 0, a NULL
+ * Y / alphas_out / rhos_out / infos_out / r / z_out / out.  LSSVM_ERR_INTERNAL: K_mm + nu I could not be factored. */
+typedef struct lssvm_precond_info {
+    uint64_t rank;
+    double   jitter;           /* nu */
+    double   build_ms;         /* the whole call */
+    double   host_ms;          /* of which the factorisations and inverses on the host */
+    uint64_t device_bytes;     /* what the preconditioner keeps in device memory */
+} lssvm_precond_info;
+typedef struct lssvm_pcg_info {
+    uint64_t iterations, gram_passes;
+    int32_t  converged, rank;
+    double   initial_residuum, residuum, target_residuum;  /* squared, as lssvm_cg_info: |r0|^2, |r|^2, eps^2 |r0|^2 */
+    double   jitter;           /* nu of the preconditioner */
+    double   build_ms;         /* of the preconditioner in use (paid once, whatever the number of solves) */
+    double   apply_ms;         /* device time of applying the preconditioner, average per iteration */
+    double   total_ms;         /* this right-hand side */
+} lssvm_pcg_info;
+int lssvm_mi355_problem_build_preconditioner(lssvm_mi355_problem *p, uint64_t rank, const uint64_t *landmarks /* NULL: the library's choice */, lssvm_precond_info *info);
+int lssvm_mi355_problem_precond_landmarks(lssvm_mi355_problem *p, uint64_t *out /* rank */);
+int lssvm_mi355_problem_precond_apply(lssvm_mi355_problem *p, const void *r, void *z_out);
+int lssvm_mi355_problem_solve_pcg(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out /* num_rhs x N */,
+                                  double *rhos_out, lssvm_pcg_info *infos_out);
+/* one-shot: create the problem on device 0 (as lssvm_mi355_solve_*), build the preconditioner (landmarks as above), solve every right-hand side, destroy it */
+int lssvm_mi355_solve_pcg_f32(const lssvm_params *params, const float *X, size_t num_points, size_t num_features, const float *Y, size_t num_rhs, uint64_t rank,
+                              const uint64_t *landmarks, double eps, uint64_t max_iter, float *alphas_out, double *rhos_out, lssvm_pcg_info *infos_out,
+                              const lssvm_mi355_options *options);
+int lssvm_mi355_solve_pcg_f64(const lssvm_params *params, const double *X, size_t num_points, size_t num_features, const double *Y, size_t num_rhs, uint64_t rank,
+                              const uint64_t *landmarks, double eps, uint64_t max_iter, double *alphas_out, double *rhos_out, lssvm_pcg_info *infos_out,
+                              const lssvm_mi355_options *options);
+
 /* CG, csvm.cpp:89-111: b = y[0..n) - y[n], x = 1, r = b - A x, delta0, d = r */
 int lssvm_mi355_cg_begin(lssvm_mi355_problem *p, const void *y, double eps);
 /* run at most `iterations` further CG iterations (csvm.cpp:125-166); stops early when delta <= eps^2 delta0.

@@ -40,6 +40,8 @@ EXPORTED_SYMBOLS = [
     "lssvm_mi355_problem_create", "lssvm_mi355_problem_create_multi", "lssvm_mi355_problem_ipc_export", "lssvm_mi355_problem_ipc_connect", "lssvm_mi355_problem_destroy", "lssvm_mi355_problem_get_q", "lssvm_mi355_problem_matvec",
     "lssvm_mi355_problem_matvec_pair", "lssvm_mi355_problem_solve_lockstep",
     "lssvm_mi355_problem_solve_cost_path", "lssvm_mi355_solve_cost_path_f32", "lssvm_mi355_solve_cost_path_f64",
+    "lssvm_mi355_problem_build_preconditioner", "lssvm_mi355_problem_precond_landmarks", "lssvm_mi355_problem_precond_apply", "lssvm_mi355_problem_solve_pcg",
+    "lssvm_mi355_solve_pcg_f32", "lssvm_mi355_solve_pcg_f64",
     "lssvm_mi355_cg_begin", "lssvm_mi355_cg_step", "lssvm_mi355_cg_finish", "lssvm_mi355_problem_synchronize", "lssvm_mi355_problem_info",
     "lssvm_mi355_measure_bf16_mfma_ceiling", "lssvm_mi355_comm_library_path", "lssvm_mi355_set_io_threads", "lssvm_mi355_set_option", "lssvm_mi355_get_option",
     "lssvm_mi355_libsvm_open", "lssvm_mi355_libsvm_fill_f32", "lssvm_mi355_libsvm_fill_f64", "lssvm_mi355_libsvm_close",
@@ -89,6 +91,23 @@ class LssvmPathInfo(C.Structure):
     """``lssvm_path_info``: how one cost of a cost path (``lssvm_mi355_problem_solve_cost_path``) went; the residua are squared norms, ``true_residuum`` -1 without verify."""
     _fields_ = [("iterations", C.c_uint64), ("converged", C.c_int32), ("verified", C.c_int32), ("initial_residuum", C.c_double), ("residuum", C.c_double),
                 ("target_residuum", C.c_double), ("true_residuum", C.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class LssvmPrecondInfo(C.Structure):
+    """``lssvm_precond_info``: what building the Nystrom preconditioner of a problem took (``lssvm_mi355_problem_build_preconditioner``)."""
+    _fields_ = [("rank", C.c_uint64), ("jitter", C.c_double), ("build_ms", C.c_double), ("host_ms", C.c_double), ("device_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class LssvmPcgInfo(C.Structure):
+    """``lssvm_pcg_info``: how one right-hand side of ``lssvm_mi355_problem_solve_pcg`` went; the residua are squared norms as in ``lssvm_cg_info``."""
+    _fields_ = [("iterations", C.c_uint64), ("gram_passes", C.c_uint64), ("converged", C.c_int32), ("rank", C.c_int32), ("initial_residuum", C.c_double),
+                ("residuum", C.c_double), ("target_residuum", C.c_double), ("jitter", C.c_double), ("build_ms", C.c_double), ("apply_ms", C.c_double), ("total_ms", C.c_double)]
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
@@ -190,6 +209,30 @@ def cost_path_entry(name: str):
             fn.argtypes = [C.c_void_p] + tail
         else:
             fn.argtypes = [C.POINTER(LssvmParams), C.c_void_p, C.c_size_t, C.c_size_t] + tail + [C.c_void_p]
+        fn.restype = C.c_int
+    return fn
+
+
+PRECOND_MAX_RANK = 512
+
+
+def pcg_entry(name: str):
+    """The entry points of the Nystrom preconditioner and of PCG (``lssvm_mi355_problem_build_preconditioner`` ... ``lssvm_mi355_solve_pcg_f32 / _f64``) with their
+    argument types.  Bound at the first call, like the weighted entry points."""
+    fn = getattr(lib, name)
+    if fn.argtypes is None:
+        solve = [C.c_void_p, C.c_size_t]
+        tail = [C.c_double, C.c_uint64, C.c_void_p, C.POINTER(C.c_double), C.POINTER(LssvmPcgInfo)]
+        if name == "lssvm_mi355_problem_build_preconditioner":
+            fn.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(LssvmPrecondInfo)]
+        elif name == "lssvm_mi355_problem_precond_landmarks":
+            fn.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        elif name == "lssvm_mi355_problem_precond_apply":
+            fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        elif name == "lssvm_mi355_problem_solve_pcg":
+            fn.argtypes = [C.c_void_p] + solve + tail
+        else:
+            fn.argtypes = [C.POINTER(LssvmParams), C.c_void_p, C.c_size_t, C.c_size_t] + solve + [C.c_uint64, C.POINTER(C.c_uint64)] + tail + [C.c_void_p]
         fn.restype = C.c_int
     return fn
 

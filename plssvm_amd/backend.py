@@ -24,7 +24,7 @@ from ._capi import LssvmCgInfo, LssvmParams, LssvmPredictInfo, LssvmShard, Optio
 from .exceptions import InvalidParameterError
 from .parameter import Parameter
 
-__all__ = ["Options", "Predictor", "solve_system_of_linear_equations", "solve_refined", "solve_cost_path", "predict_values", "predict_values_multi", "generate_q", "run_device_kernel", "calculate_w", "ResidentProblem",
+__all__ = ["Options", "Predictor", "solve_system_of_linear_equations", "solve_refined", "solve_cost_path", "solve_pcg", "predict_values", "predict_values_multi", "generate_q", "run_device_kernel", "calculate_w", "ResidentProblem",
            "comm_get_unique_id", "comm_init", "comm_destroy"]
 
 
@@ -193,6 +193,56 @@ def solve_cost_path(params: Parameter, A, b, costs, eps: float, max_iter: int, v
     ps = _params_struct(params, d)
     fn = _capi.cost_path_entry(f"lssvm_mi355_solve_cost_path_{suffix_of(A.dtype)}")
     return _cost_path_call(fn, (C.byref(ps), ptr(A), N, d), y, costs, N, A.dtype, eps, max_iter, verify, tail=(options_ptr(options),))
+
+
+def _pcg_arguments(B, N: int, dtype, eps: float, max_iter: int):
+    """The right-hand sides of a PCG solve as the library takes them (``k x N``), checked as it checks them: ``(B2, single)``."""
+    B = np.ascontiguousarray(B, dtype=dtype)
+    single = B.ndim == 1
+    B2 = B.reshape(1, -1) if single else B
+    if B2.ndim != 2 or B2.shape[0] == 0 or B2.shape[1] != N:
+        raise InvalidParameterError(f"The number of data points in the matrix A ({N}) and the values in every right hand side vector ({B2.shape[-1] if B2.ndim else 0}) must be the same!")
+    if not (np.isfinite(eps) and eps > 0.0):
+        raise InvalidParameterError(f"The stopping criterion in the CG algorithm must be greater than 0.0, but is {eps}!")
+    if not int(max_iter) > 0:
+        raise InvalidParameterError("The number of CG iterations must be greater than 0!")
+    return B2, single
+
+
+def _landmarks_argument(rank: int, landmarks):
+    """``(rank, array or None, pointer or NULL)`` of a preconditioner's landmarks: ``landmarks`` given -> its length is the rank."""
+    if landmarks is None:
+        return int(rank), None, None
+    lm = np.ascontiguousarray(landmarks, dtype=np.uint64)
+    if lm.ndim != 1 or lm.size == 0:
+        raise InvalidParameterError("The landmarks must be a non-empty list of point indices!")
+    return int(lm.size), lm, lm.ctypes.data_as(C.POINTER(C.c_uint64))
+
+
+def _pcg_call(fn, head, middle, B2, single: bool, N: int, dtype, eps: float, max_iter: int, tail=()):
+    k = B2.shape[0]
+    alphas = np.zeros((k, N), dtype=dtype)
+    rhos = np.zeros(k, dtype=np.float64)
+    infos = (_capi.LssvmPcgInfo * k)()
+    check(fn(*head, ptr(B2), k, *middle, float(eps), int(max_iter), ptr(alphas), rhos.ctypes.data_as(C.POINTER(C.c_double)), infos, *tail))
+    dicts = [i.as_dict() for i in infos]
+    if single:
+        return alphas[0], np.dtype(dtype).type(rhos[0]), dicts[0]
+    return alphas, rhos.astype(dtype), dicts
+
+
+def solve_pcg(params: Parameter, A, B, eps: float, max_iter: int, rank: int = 256, landmarks=None, options: Options | None = None):
+    """The system(s) solved by CG preconditioned with a Nystrom approximation of ``rank`` landmarks (``lssvm_mi355_solve_pcg_*``; opt-in: it pays where the kernel matrix
+    has spectral decay and costs iterations where it has none).  ``B``: one right-hand side ``(N,)`` or ``k`` of them ``(k, N)``, solved one after the other on ONE
+    preconditioner.  ``landmarks``: distinct point indices (their number is the rank) or None for the library's fixed choice.  The stop test is that of
+    :func:`solve_system_of_linear_equations`.  Returns ``(alphas, rhos, infos)`` shaped like ``B`` (``infos``: ``lssvm_pcg_info`` dicts).  Device 0; deterministic."""
+    A = _as_matrix(A)
+    N, d = A.shape
+    B2, single = _pcg_arguments(B, N, A.dtype, eps, max_iter)
+    rank, lm, lm_ptr = _landmarks_argument(rank, landmarks)
+    ps = _params_struct(params, d)
+    fn = _capi.pcg_entry(f"lssvm_mi355_solve_pcg_{suffix_of(A.dtype)}")
+    return _pcg_call(fn, (C.byref(ps), ptr(A), N, d), (rank, lm_ptr), B2, single, N, A.dtype, eps, max_iter, tail=(options_ptr(options),))
 
 
 def generate_q(params: Parameter, data, options: Options | None = None):
@@ -522,6 +572,37 @@ class ResidentProblem:
         weights set, not between :meth:`cg_begin` and :meth:`cg_finish`."""
         y, costs = _cost_path_arguments(y, self.num_points, self.dtype, costs, eps, max_iter)
         return _cost_path_call(_capi.cost_path_entry("lssvm_mi355_problem_solve_cost_path"), (self._h,), y, costs, self.num_points, self.dtype, eps, max_iter, verify)
+
+    def build_preconditioner(self, rank: int = 256, landmarks=None):
+        """The Nystrom preconditioner of this problem at its own cost (``lssvm_mi355_problem_build_preconditioner``): ``rank`` landmarks of the library's fixed choice, or
+        the given distinct point indices (their number is the rank).  Building again replaces it.  Returns the ``lssvm_precond_info`` dict.  Not on a problem of several
+        devices or ranks, not with weights set, not between :meth:`cg_begin` and :meth:`cg_finish`."""
+        rank, lm, lm_ptr = _landmarks_argument(rank, landmarks)
+        info = _capi.LssvmPrecondInfo()
+        check(_capi.pcg_entry("lssvm_mi355_problem_build_preconditioner")(self._h, rank, lm_ptr, C.byref(info)))
+        self._precond_rank = rank
+        return info.as_dict()
+
+    def precond_landmarks(self):
+        """The landmarks of the preconditioner in use (``lssvm_mi355_problem_precond_landmarks``)."""
+        out = np.zeros(max(int(getattr(self, "_precond_rank", 0)), 1), dtype=np.uint64)
+        check(_capi.pcg_entry("lssvm_mi355_problem_precond_landmarks")(self._h, out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return out
+
+    def precond_apply(self, r):
+        """``z = r - Bhat G^-1 Bhat^T r = P^-1 r / C`` for a vector of ``num_points - 1`` entries: the preconditioner alone (``lssvm_mi355_problem_precond_apply``)."""
+        r = np.ascontiguousarray(r, dtype=self.dtype)
+        if not (r.ndim == 1 and r.size == self.num_points - 1):
+            raise InvalidParameterError(f"Sizes mismatch!: {r.size} != {self.num_points - 1}")
+        z = np.zeros_like(r)
+        check(_capi.pcg_entry("lssvm_mi355_problem_precond_apply")(self._h, ptr(r), ptr(z)))
+        return z
+
+    def solve_pcg(self, B, eps: float, max_iter: int):
+        """:func:`solve_pcg` on this resident problem and the preconditioner :meth:`build_preconditioner` left (``lssvm_mi355_problem_solve_pcg``): one right-hand side
+        ``(num_points,)`` or ``k`` of them, one after the other.  Returns ``(alphas, rhos, infos)`` shaped like ``B``; the problem is left as it was."""
+        B2, single = _pcg_arguments(B, self.num_points, self.dtype, eps, max_iter)
+        return _pcg_call(_capi.pcg_entry("lssvm_mi355_problem_solve_pcg"), (self._h,), (), B2, single, self.num_points, self.dtype, eps, max_iter)
 
     def cg_begin(self, y, eps: float):
         y = np.ascontiguousarray(y, dtype=self.dtype)

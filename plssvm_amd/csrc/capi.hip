@@ -195,6 +195,21 @@ void cost_path_one_shot(const lssvm_params *params, const T *X, size_t N, size_t
     prob.solve_cost_path(y, costs, num_costs, eps, max_iter, verify != 0, alphas_out, rhos_out, infos_out, passes_out);
 }
 
+/* lssvm_mi355_solve_pcg_*: every argument that needs no device is checked before one is touched; problem, preconditioner and solves on device 0 */
+template <typename T>
+void pcg_one_shot(const lssvm_params *params, const T *X, size_t N, size_t d, const T *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, double eps, uint64_t max_iter,
+                  T *alphas_out, double *rhos_out, lssvm_pcg_info *infos_out, const lssvm_mi355_options *options) {
+    lssvm::check_params(params);
+    lssvm::check_pcg_arguments(Y, num_rhs, eps, max_iter, alphas_out, rhos_out, infos_out);
+    LSSVM_REQUIRE(X != nullptr && N > 0, "The data must not be empty!");         // csvm.cpp:73
+    LSSVM_REQUIRE(d > 0, "The data points must contain at least one feature!");  // csvm.cpp:74
+    lssvm::check_precond_rank(rank, N);
+    static const int device0 = 0;
+    lssvm::Solver<T> prob(options_of(options), *params, X, LSSVM_MEM_HOST, N, d, lssvm::resolve_devices(&device0, 1, N), nullptr);
+    prob.build_preconditioner(rank, landmarks, nullptr);
+    prob.solve_pcg(Y, num_rhs, eps, max_iter, alphas_out, rhos_out, infos_out);
+}
+
 template <typename T>
 void generate_q_one_shot(const lssvm_params *params, const T *X, size_t N, size_t d, T *q_out, const lssvm_mi355_options *options) {
     lssvm::check_params(params);
@@ -591,6 +606,42 @@ int lssvm_mi355_solve_cost_path_f64(const lssvm_params *params, const double *X,
                                     uint64_t max_iter, int verify, double *alphas_out, double *rhos_out, lssvm_path_info *infos_out, uint64_t passes_out[2],
                                     const lssvm_mi355_options *options) {
     return guarded([&] { cost_path_one_shot<double>(params, X, num_points, num_features, y, costs, num_costs, eps, max_iter, verify, alphas_out, rhos_out, infos_out, passes_out, options); });
+}
+static_assert(sizeof(lssvm_precond_info) == 40 && sizeof(lssvm_pcg_info) == 80, "lssvm_precond_info / lssvm_pcg_info changed: plssvm_amd/_capi.py (LssvmPrecondInfo, LssvmPcgInfo) changes with them");
+int lssvm_mi355_problem_build_preconditioner(lssvm_mi355_problem *p, uint64_t rank, const uint64_t *landmarks, lssvm_precond_info *info) {
+    return guarded([&] {
+        LSSVM_REQUIRE(p != nullptr, "problem handle must not be NULL");
+        LSSVM_REQUIRE(rank >= 1 && rank <= static_cast<uint64_t>(lssvm::PRECOND_MAX_RANK),
+                      "The rank of the preconditioner must lie in [1, " + std::to_string(lssvm::PRECOND_MAX_RANK) + "], but is " + std::to_string(rank) + "!");  // (before any device work; N: the solver)
+        impl_of(p)->build_preconditioner(rank, landmarks, info);
+    });
+}
+int lssvm_mi355_problem_precond_landmarks(lssvm_mi355_problem *p, uint64_t *out) {
+    return guarded([&] {
+        LSSVM_REQUIRE(p != nullptr, "problem handle must not be NULL");
+        impl_of(p)->precond_landmarks(out);
+    });
+}
+int lssvm_mi355_problem_precond_apply(lssvm_mi355_problem *p, const void *r, void *z_out) {
+    return guarded([&] {
+        LSSVM_REQUIRE(p != nullptr, "problem handle must not be NULL");
+        impl_of(p)->precond_apply(r, z_out);
+    });
+}
+int lssvm_mi355_problem_solve_pcg(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_pcg_info *infos_out) {
+    return guarded([&] {
+        LSSVM_REQUIRE(p != nullptr, "problem handle must not be NULL");
+        lssvm::check_pcg_arguments(Y, num_rhs, eps, max_iter, alphas_out, rhos_out, infos_out);  // (before any device work)
+        impl_of(p)->solve_pcg(Y, num_rhs, eps, max_iter, alphas_out, rhos_out, infos_out);
+    });
+}
+int lssvm_mi355_solve_pcg_f32(const lssvm_params *params, const float *X, size_t num_points, size_t num_features, const float *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks,
+                              double eps, uint64_t max_iter, float *alphas_out, double *rhos_out, lssvm_pcg_info *infos_out, const lssvm_mi355_options *options) {
+    return guarded([&] { pcg_one_shot<float>(params, X, num_points, num_features, Y, num_rhs, rank, landmarks, eps, max_iter, alphas_out, rhos_out, infos_out, options); });
+}
+int lssvm_mi355_solve_pcg_f64(const lssvm_params *params, const double *X, size_t num_points, size_t num_features, const double *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks,
+                              double eps, uint64_t max_iter, double *alphas_out, double *rhos_out, lssvm_pcg_info *infos_out, const lssvm_mi355_options *options) {
+    return guarded([&] { pcg_one_shot<double>(params, X, num_points, num_features, Y, num_rhs, rank, landmarks, eps, max_iter, alphas_out, rhos_out, infos_out, options); });
 }
 int lssvm_mi355_cg_begin(lssvm_mi355_problem *p, const void *y, double eps) {
     return guarded([&] { impl_of(p)->cg_begin(y, eps); });

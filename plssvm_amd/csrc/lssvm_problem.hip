@@ -1012,7 +1012,9 @@ Problem<T>::Problem(const Options &opt, const lssvm_params &params, const void *
     lap("q");
     // rbf on the matrix cores: centre the data, then c_i = -|x_i|^2 / 2
     if (params_.kernel_type == LSSVM_KERNEL_RBF && !rbf_direct_) {
-        center_columns<T>(X_, nullptr, rbf_prescale<T>(params_, v2_eligible_f64(opt_, X_.ldx) || wide_nl_), st);
+        const T prescale = rbf_prescale<T>(params_, v2_eligible_f64(opt_, X_.ldx) || wide_nl_);
+        center_columns<T>(X_, nullptr, prescale, st);
+        x_scale_ = static_cast<double>(prescale);
         half_neg_norms<T>(X_, c_, st);
     }
     lap("centring, norms");
@@ -1025,6 +1027,7 @@ Problem<T>::Problem(const Options &opt, const lssvm_params &params, const void *
                                static_cast<const T *>(nullptr), static_cast<T>(std::sqrt(params_.gamma)));
             LSSVM_HIP_CHECK(hipGetLastError());
             poly_prescaled_ = true;
+            x_scale_ = static_cast<double>(static_cast<T>(std::sqrt(params_.gamma)));
         }
     }
     if constexpr (std::is_same_v<T, float>) {

@@ -451,6 +451,8 @@ class Problem {
     bool wide_nl_ = false;         // fp32 rbf / polynomial on more features than the one-pass split kernels take: feature panels inside a tile (lssvm_tile_f32_wide.hip.hpp)
     bool wide_linear_ = false;     // linear kernel over feature panels, one tile-kernel pass per panel: fp32 f16x3 beyond linear_panel_features, fp64 beyond 256 features
     bool poly_prescaled_ = false;  // fp64 polynomial on the v2 kernel: X_ carries sqrt(gamma), the kernel sees gamma = 1
+    double x_scale_ = 1.0;         // the factor X_ was multiplied by in place after q was computed (rbf off the direct form: rbf_prescale, on centred data; poly_prescaled_:
+                                   // sqrt(gamma)): what reads X_ directly -- the landmark block of the preconditioner, lssvm_precond.hip -- evaluates with gamma / x_scale_^2
     PlaneSet planes_;              // fp32 split kernels: X as three bf16 planes (bf16x6) or two f16 planes (f16x3), [planes][rows_alloc][ldx16]
 
     DeviceMatrix<T> X_;
@@ -567,6 +569,23 @@ inline void fill_cg_outcome(lssvm_cg_info *info, uint64_t iterations, uint64_t m
     info->converged = converged ? 1 : 0;
 }
 
+/* ------------------------------------------------------------------ the Nystrom preconditioner of a problem (lssvm_precond.hip) ------------------------------------------------------------------ */
+constexpr int PRECOND_MAX_RANK = 512;
+/* P = Bhat Bhat^T + sigma I with Bhat = [E K_Nm L^-T | sqrt(sigma) 1], n x (rank + 1), and what applying P^-1 r ~ r - Bhat G^-1 Bhat^T r needs, G = Bhat^T Bhat + sigma I.
+ * Bhat is stored COLUMN by column (column j: ldn reals, exact zeros from row n on), so that both apply kernels stream it in 16-byte pieces along a column. */
+template <typename T>
+struct Precond {
+    int rank = 0, cols = 0;           // landmarks m, columns m + 1
+    size_t ldn = 0;                   // reals between two columns: n rounded up to 256
+    std::vector<uint64_t> landmarks;  // the points in use
+    DevBuf<T> Bhat;                   // [cols][ldn]
+    DevBuf<double> Ginv;              // [cols][cols], symmetric to the bit
+    DevBuf<double> tpart, s;          // the apply's RED_BLOCKS x cols partial sums of Bhat^T r, and s = G^-1 Bhat^T r as ceil(cols / 32) shares of cols doubles (added by the last kernel)
+    DevBuf<double> part_rz;           // RED_BLOCKS x 2 partial sums of r.z
+    DevBuf<T> r_io, z_io;             // lssvm_mi355_problem_precond_apply: the caller's vector and the result
+    double sigma = 0.0, jitter = 0.0, build_ms = 0.0;
+};
+
 /* ------------------------------------------------------------------ the resident problem (what a C handle points to) ------------------------------------------------------------------ */
 struct ProblemBase {
     int dtype = 0;
@@ -579,6 +598,11 @@ struct ProblemBase {
                                 uint64_t *passes_out) = 0;  // lssvm_mi355_problem_solve_lockstep
     virtual void solve_cost_path(const void *y, const double *costs, size_t num_costs, double eps, uint64_t max_iter, bool verify, void *alphas_out, double *rhos_out,
                                  lssvm_path_info *infos_out, uint64_t *passes_out) = 0;  // lssvm_mi355_problem_solve_cost_path
+    /* the Nystrom preconditioner and PCG on it (lssvm_precond.hip) */
+    virtual void build_preconditioner(uint64_t rank, const uint64_t *landmarks, lssvm_precond_info *info) = 0;  // lssvm_mi355_problem_build_preconditioner
+    virtual void precond_landmarks(uint64_t *out) = 0;                                                          // lssvm_mi355_problem_precond_landmarks
+    virtual void precond_apply(const void *r, void *z_out) = 0;                                                 // lssvm_mi355_problem_precond_apply
+    virtual void solve_pcg(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_pcg_info *infos_out) = 0;  // lssvm_mi355_problem_solve_pcg
     virtual void cg_begin(const void *y, double eps) = 0;
     virtual void cg_step(uint64_t iterations, int *done_out) = 0;
     virtual void cg_finish(void *alpha_out, double *rho_out, lssvm_cg_info *info) = 0;
@@ -659,6 +683,11 @@ class Solver final : public ProblemBase {
     /* every cost of a grid from ONE multi-shift CG sequence on this problem's single-vector pass (lssvm_path.hip) */
     void solve_cost_path(const void *y, const double *costs, size_t num_costs, double eps, uint64_t max_iter, bool verify, void *alphas_out, double *rhos_out, lssvm_path_info *infos_out,
                          uint64_t *passes_out) override;
+    /* the Nystrom preconditioner of this problem and the reference recipe's CG preconditioned with it (lssvm_precond.hip) */
+    void build_preconditioner(uint64_t rank, const uint64_t *landmarks, lssvm_precond_info *info) override;
+    void precond_landmarks(uint64_t *out) override;
+    void precond_apply(const void *r, void *z_out) override;
+    void solve_pcg(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_pcg_info *infos_out) override;
     void cg_begin(const void *y, double eps) override;
     /* cg_begin for the inner solve of the mixed-precision refinement: A e = r / max|r| from e = 0 -- b, the first residual and delta0 = b^T b come from ONE O(n) kernel
      * over the outer fp64 residual `r_dev` (device 0, complete when the call is made; `absmax_part_dev`: k_absmax's partials of it), no Gram pass.  cg_step follows as
@@ -695,6 +724,8 @@ class Solver final : public ProblemBase {
     void read_delta0(double t0);               // ... and their end: delta0 is read, the handle is between begin and finish
     void solve_in_sequence(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out);
     void solve_on_lanes(const T *Y, size_t num_rhs, double eps, uint64_t max_iter, T *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out);
+    Problem<T> &precond_problem(const char *what);                        // the checks every preconditioner entry point shares; shard 0
+    void enqueue_precond_apply(const T *r, T *z, double *part_rz) const;  // z = r - Bhat G^-1 Bhat^T r and the partial sums of r.z
     T *vec_of(Problem<T> &p, Vec which) const { return which == Vec::d ? p.own_.d.p : (which == Vec::x ? p.own_.x.p : p.tmp_.p); }
 
     Options opt_{};
@@ -702,6 +733,7 @@ class Solver final : public ProblemBase {
     Exchange exchange_ = Exchange::none;
     std::shared_ptr<LocalComms> local_comms_;
     std::unique_ptr<IpcPeers> ipc_;  // Exchange::process_peer
+    std::unique_ptr<Precond<T>> precond_;  // lssvm_mi355_problem_build_preconditioner (none until then)
     uint64_t xseq_ = 0;              // implicit matvecs exchanged so far
     Event ev_delta_;                 // shard 0's stream: delta of the iteration is on the host
     int world_ = 1;  // shards of the problem in total (all processes)
@@ -726,6 +758,10 @@ void measure_bf16_mfma_ceiling(int device, int b_from_lds, double settle_ms, dou
 /* lssvm_mi355_solve_refined_f64 (lssvm_refine.hip); the arguments have been checked */
 void solve_refined_f64(const Options &opt, const lssvm_params &params, const double *X, size_t num_points, size_t num_features, const double *Y, size_t num_rhs, const double *weights,
                        double eps, uint64_t max_iter, double *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, lssvm_refine_info *refine_out, uint64_t *passes_out);
+
+/* the arguments of lssvm_mi355_problem_solve_pcg / lssvm_mi355_solve_pcg_* and of the preconditioner's rank that need no device (lssvm_precond.hip) */
+void check_pcg_arguments(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, const void *alphas_out, const double *rhos_out, const lssvm_pcg_info *infos_out);
+void check_precond_rank(uint64_t rank, size_t num_points);
 
 /* the arguments of lssvm_mi355_problem_solve_cost_path / lssvm_mi355_solve_cost_path_* that need no device: checked before one is touched (lssvm_path.hip) */
 constexpr size_t PATH_MAX_COSTS = 64;

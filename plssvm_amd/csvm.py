@@ -214,10 +214,13 @@ def _drop_zero_weights(data: DataSet, sample_weight):
 class MI355CSVM(CSVM):
     """The MI355X backend (counterpart of plssvm::hip::csvm, HIP/csvm.hpp:39-99, csvm.hip.cpp:47-85)."""
 
-    def __init__(self, target=TargetPlatform.AUTOMATIC, params: Parameter | None = None, num_devices: int = 1, solver: str = "cg", **kwargs):
+    def __init__(self, target=TargetPlatform.AUTOMATIC, params: Parameter | None = None, num_devices: int = 1, solver: str = "cg", precond_rank: int = 256, **kwargs):
         """``solver``: ``"cg"`` (default) = the CG of the data's real type; ``"refined"`` = float64 data on ONE device is solved by mixed-precision refinement
         (``backend.solve_refined``: float32 CG iterations on the matrix cores inside a float64 residual loop, same stop test; the gain grows with the iteration
-        count) and ``last_refine_info`` keeps the per-solve reports -- float32 data or several devices solve as with ``"cg"`` and leave it None.
+        count) and ``last_refine_info`` keeps the per-solve reports -- float32 data or several devices solve as with ``"cg"`` and leave it None;
+        ``"pcg"`` = CG preconditioned with a Nystrom approximation of ``precond_rank`` landmarks (``backend.solve_pcg``), same stop test, built once per
+        data set and shared by all right-hand sides -- opt-in: it saves iterations where the kernel matrix has spectral decay and costs some where it has none; one device
+        and no sample weights (both raise).
 
         ``num_devices``: devices ONE solve is sharded over -- 1 (default) = device 0 only, k = devices 0 .. k-1 (gpu_csvm.hpp:283-299),
         0 = automatic (every visible device, at least 4096 points each, as the reference's backends take every device they find,
@@ -225,10 +228,13 @@ class MI355CSVM(CSVM):
         bootstraps RCCL inside the process, and that path has not run on a multi-GPU box yet."""
         if isinstance(target, Parameter):
             target, params = TargetPlatform.AUTOMATIC, target
-        if solver not in ("cg", "refined"):
-            raise InvalidParameterError(f"solver must be 'cg' or 'refined', but is {solver!r}!")
+        if solver not in ("cg", "refined", "pcg"):
+            raise InvalidParameterError(f"solver must be 'cg' or 'refined' or 'pcg', but is {solver!r}!")
+        if solver == "pcg" and not (isinstance(precond_rank, (int, np.integer)) and 1 <= int(precond_rank) <= _capi.PRECOND_MAX_RANK):
+            raise InvalidParameterError(f"precond_rank must lie in [1, {_capi.PRECOND_MAX_RANK}], but is {precond_rank!r}!")
         super().__init__(params, **kwargs)
         self.solver = solver
+        self.precond_rank = int(precond_rank) if solver == "pcg" else None
         self.last_refine_info = None
         if target not in (TargetPlatform.AUTOMATIC, TargetPlatform.GPU_AMD):
             raise BackendError(f"Invalid target platform '{target.value}' for the MI355 backend!")
@@ -253,6 +259,9 @@ class MI355CSVM(CSVM):
 
     def solve_system_of_linear_equations(self, params, A, b, eps, max_iter, sample_weight=None):
         self.last_refine_info = None
+        if self.solver == "pcg":
+            self._pcg_applies(sample_weight)
+            return backend.solve_pcg(params, A, b, eps, max_iter, rank=self._pcg_rank(A), options=self._options)
         if self._refines(A):
             alpha, rho, info, refine = backend.solve_refined(params, A, b, eps, max_iter, sample_weight=sample_weight, options=self._options)
             self.last_refine_info = [refine]
@@ -291,6 +300,17 @@ class MI355CSVM(CSVM):
             raise InvalidParameterError(f"The cost path runs on one device, but this backend object shards a solve over {'every visible device' if self.use_devices == 0 else self.use_devices}"
                                         f"{'' if self.use_devices == 0 else ' devices'} (num_devices={self.use_devices})!")
 
+    def _pcg_applies(self, sample_weight) -> None:
+        if self.use_devices != 1:
+            raise InvalidParameterError(f"solver='pcg' runs on one device, but this backend object shards a solve over {'every visible device' if self.use_devices == 0 else self.use_devices}"
+                                        f"{'' if self.use_devices == 0 else ' devices'} (num_devices={self.use_devices})!")
+        if sample_weight is not None:
+            raise InvalidParameterError("solver='pcg' solves the unweighted system: sample weights need solver='cg'!")
+
+    def _pcg_rank(self, A) -> int:
+        """``precond_rank``, but never more landmarks than the reduced system has rows."""
+        return max(1, min(self.precond_rank, backend._as_matrix(A).shape[0] - 1))
+
     def _refines(self, A) -> bool:
         """solver="refined" applies: float64 data on one device."""
         return self.solver == "refined" and self.use_devices == 1 and backend._as_matrix(A).dtype == np.float64
@@ -304,6 +324,12 @@ class MI355CSVM(CSVM):
         one-shot solve.  In fp64 on the symmetric resident-row-panel kernel, and in fp32 on 129 ... 512 features (polynomial, or rbf with folded records, on the symmetric
         one-pass split kernels), one pass over the Gram tiles serves two right-hand sides per iteration; elsewhere they are solved one after the other.  Several devices: the base class's loop of one-shot solves."""
         self.last_refine_info = None
+        if self.solver == "pcg":  # ONE preconditioner for all right-hand sides
+            self._pcg_applies(sample_weight)
+            B = np.asarray(B)
+            if B.ndim != 2 or B.shape[0] == 0:
+                raise InvalidParameterError("The right-hand sides must be a matrix with one row per system and at least one row!")
+            return backend.solve_pcg(params, A, B, eps, max_iter, rank=self._pcg_rank(A), options=self._options)
         if self.use_devices != 1:
             return super().solve_systems_of_linear_equations(params, A, B, eps, max_iter, sample_weight=sample_weight)
         if self._refines(A):
