@@ -497,6 +497,43 @@ int lssvm_mi355_solve_pcg_f64(const lssvm_params *params, const double *X, size_
                               const uint64_t *landmarks, double eps, uint64_t max_iter, double *alphas_out, double *rhos_out, lssvm_pcg_info *infos_out,
                               const lssvm_mi355_options *options);
 
+/* Fixed-size (reduced, "subset of regressors") LS-SVM on a resident problem (opt-in): the decision function is expanded over `rank` = m landmark
+ * points only, f(x) = sum_j beta_j k(x, x_L[j]) + b, and minimises  1/2 beta^T K_mm beta + C/2 sum_i (y_i - Phi_i beta - b)^2  with Phi = K(X, X_L) (N x m, evaluated in
+ * double from the problem's resident data exactly as the preconditioner above evaluates K_Nm) and K_mm = Phi[L, :].  No CG: the device forms, slab of `slab_rows` rows by
+ * slab, the lower triangle of St = Pt^T Pt for Pt = [Phi | 1 | y_0 ... y_{k-1}] (N x (m + 1 + k)) on v_mfma_f64_16x16x4_f64; the host solves in double, with sigma = 1 / C,
+ *   S = St[:m,:m], s = St[m,:m], t_c = St[m+1+c,:m], eta_c = St[m+1+c,m]:   M = S - s s^T / N + sigma K_mm,   (M + nu I) beta_c = t_c - s eta_c / N,
+ *   b_c = (eta_c - s^T beta_c) / N,   rho_c = -b_c.
+ * nu follows the preconditioner's rule on M (eps64 trace(M), tenfold while the factorisation fails, six times at most) and is reported as `jitter`: the conditioning of
+ * M grows with the rank and is the method's limit (README.md).  One St and one factorisation serve all num_rhs right-hand sides; row c of the results has the bits of the
+ * call with right-hand side c alone: the order in which an entry of St is summed depends on N and slab_rows only.  The result is an ordinary model of m support vectors
+ * (the landmark rows, alpha = beta, rho); it trades accuracy for size, nothing selects it automatically.
+ * rank: 1 <= rank <= min(N, 1024).  landmarks: as for the preconditioner (`rank` distinct indices < N, or NULL for the library's rule).  slab_rows: a multiple of 256,
+ * 0 = the library's default (65 536); it bounds the work space (about slab_rows x (rank + 1 + num_rhs) doubles).  betas_out is DOUBLE whatever the problem's dtype (a
+ * float model rounds it afterwards).  landmarks_out and info may be NULL.  It uses the cost of the problem's lssvm_params.  The problem is left as it was and keeps its
+ * preconditioner.  Deterministic: fixed-order sums without atomics, the same bits for the same arguments.
+ * LSSVM_ERR_INVALID_ARGUMENT, all before a device is touched: a problem on several devices or ranks, weights set on the problem, a call between cg_begin and cg_finish;
+ * rank 0, beyond 1024 or beyond N; duplicate or out-of-range landmarks; slab_rows no multiple of 256; num_rhs == 0; a NULL Y / betas_out / rhos_out.
+ * LSSVM_ERR_INTERNAL: M + nu I could not be factored. */
+typedef struct lssvm_reduced_info {
+    uint64_t rank, slabs;
+    double   jitter;           /* nu */
+    double   landmark_ms;      /* device time of Phi, the 1 and y columns and K_mm, all slabs */
+    double   gram_ms;          /* device time of St, all slabs */
+    double   host_ms;          /* the factorisation and the solves on the host */
+    double   total_ms;         /* the whole call */
+    uint64_t workspace_bytes;  /* device memory held during the call */
+} lssvm_reduced_info;
+int lssvm_mi355_problem_fit_reduced(lssvm_mi355_problem *p, const void *Y /* num_rhs x N, the problem's dtype */, size_t num_rhs, uint64_t rank,
+                                    const uint64_t *landmarks /* NULL: the preconditioner's rule */, uint64_t slab_rows, double *betas_out /* num_rhs x rank */,
+                                    double *rhos_out, uint64_t *landmarks_out /* rank */, lssvm_reduced_info *info);
+/* one-shot: create the problem on device 0 (as lssvm_mi355_solve_*), fit, destroy it */
+int lssvm_mi355_fit_reduced_f32(const lssvm_params *params, const float *X, size_t num_points, size_t num_features, const float *Y, size_t num_rhs, uint64_t rank,
+                                const uint64_t *landmarks, uint64_t slab_rows, double *betas_out, double *rhos_out, uint64_t *landmarks_out, lssvm_reduced_info *info,
+                                const lssvm_mi355_options *options);
+int lssvm_mi355_fit_reduced_f64(const lssvm_params *params, const double *X, size_t num_points, size_t num_features, const double *Y, size_t num_rhs, uint64_t rank,
+                                const uint64_t *landmarks, uint64_t slab_rows, double *betas_out, double *rhos_out, uint64_t *landmarks_out, lssvm_reduced_info *info,
+                                const lssvm_mi355_options *options);
+
 /* CG, csvm.cpp:89-111: b = y[0..n) - y[n], x = 1, r = b - A x, delta0, d = r */
 int lssvm_mi355_cg_begin(lssvm_mi355_problem *p, const void *y, double eps);
 /* run at most `iterations` further CG iterations (csvm.cpp:125-166); stops early when delta <= eps^2 delta0.

@@ -49,6 +49,16 @@ int lssvm_mi355_problem_rebalance(lssvm_mi355_problem *p, const double *weights,
  * at most 32.  For the tests that a written file does not depend on the thread count. */
 int lssvm_mi355_set_io_threads(int threads);
 
+/* The operator of the fixed-size model alone (lssvm_mi355_problem_fit_reduced): St = Pt^T Pt for Pt = [Phi | 1 | y_0 ... y_{k-1}], as the device sums
+ * it, (rank + 1 + num_rhs)^2 doubles row-major with BOTH triangles (the upper one is the host's copy of the lower).  Arguments and refusals as there. */
+int lssvm_mi355_problem_landmark_gram(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, double *gram_out);
+
+/* Measurement aid of tests/tools/reduced_timing.py: G = Bhat^T Bhat of the fp64 problem's preconditioner (its own Bhat buffer, rank + 1 columns) `repeats` times by
+ * the preconditioner's scalar kernel (parent_ms_out[r]) and by the fixed-size model's matrix-core kernels (mfma_ms_out[r]: partial tiles and their sum), device time of
+ * repeat r each, after one untimed run of both.  *max_diff_out (may be NULL): the largest |difference| of the two results over the lower triangle, relative to the largest
+ * |entry|.  Refused without a preconditioner and on an fp32 problem. */
+int lssvm_mi355_problem_time_gram_kernels(lssvm_mi355_problem *p, int repeats, double *parent_ms_out, double *mfma_ms_out, double *max_diff_out);
+
 /* option names understood by lssvm_mi355_set_option / _get_option besides the fourteen documented in plssvm_amd.h:
  *   "force_collective" 1 = run the per-matvec RCCL collective even with a world of 1 (testing aid; default 0)
  *   "skip_collective"  1 = problems created with world > 1 need no communicator and do NOT exchange their partial K*v (testing aid:

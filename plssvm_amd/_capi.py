@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = [
     "lssvm_mi355_problem_solve_cost_path", "lssvm_mi355_solve_cost_path_f32", "lssvm_mi355_solve_cost_path_f64",
     "lssvm_mi355_problem_build_preconditioner", "lssvm_mi355_problem_precond_landmarks", "lssvm_mi355_problem_precond_apply", "lssvm_mi355_problem_solve_pcg",
     "lssvm_mi355_solve_pcg_f32", "lssvm_mi355_solve_pcg_f64",
+    "lssvm_mi355_problem_fit_reduced", "lssvm_mi355_fit_reduced_f32", "lssvm_mi355_fit_reduced_f64", "lssvm_mi355_problem_landmark_gram", "lssvm_mi355_problem_time_gram_kernels",
     "lssvm_mi355_cg_begin", "lssvm_mi355_cg_step", "lssvm_mi355_cg_finish", "lssvm_mi355_problem_synchronize", "lssvm_mi355_problem_info",
     "lssvm_mi355_measure_bf16_mfma_ceiling", "lssvm_mi355_comm_library_path", "lssvm_mi355_set_io_threads", "lssvm_mi355_set_option", "lssvm_mi355_get_option",
     "lssvm_mi355_libsvm_open", "lssvm_mi355_libsvm_fill_f32", "lssvm_mi355_libsvm_fill_f64", "lssvm_mi355_libsvm_close",
@@ -108,6 +109,15 @@ class LssvmPcgInfo(C.Structure):
     """``lssvm_pcg_info``: how one right-hand side of ``lssvm_mi355_problem_solve_pcg`` went; the residua are squared norms as in ``lssvm_cg_info``."""
     _fields_ = [("iterations", C.c_uint64), ("gram_passes", C.c_uint64), ("converged", C.c_int32), ("rank", C.c_int32), ("initial_residuum", C.c_double),
                 ("residuum", C.c_double), ("target_residuum", C.c_double), ("jitter", C.c_double), ("build_ms", C.c_double), ("apply_ms", C.c_double), ("total_ms", C.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class LssvmReducedInfo(C.Structure):
+    """``lssvm_reduced_info``: what fitting a fixed-size model took (``lssvm_mi355_problem_fit_reduced``); ``jitter``: the nu added to the diagonal of M."""
+    _fields_ = [("rank", C.c_uint64), ("slabs", C.c_uint64), ("jitter", C.c_double), ("landmark_ms", C.c_double), ("gram_ms", C.c_double), ("host_ms", C.c_double),
+                ("total_ms", C.c_double), ("workspace_bytes", C.c_uint64)]
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
@@ -233,6 +243,28 @@ def pcg_entry(name: str):
             fn.argtypes = [C.c_void_p] + solve + tail
         else:
             fn.argtypes = [C.POINTER(LssvmParams), C.c_void_p, C.c_size_t, C.c_size_t] + solve + [C.c_uint64, C.POINTER(C.c_uint64)] + tail + [C.c_void_p]
+        fn.restype = C.c_int
+    return fn
+
+
+REDUCED_MAX_RANK = 1024
+
+
+def reduced_entry(name: str):
+    """The entry points of the fixed-size model (``lssvm_mi355_problem_fit_reduced``, ``lssvm_mi355_fit_reduced_f32 / _f64``, and the test aids
+    ``lssvm_mi355_problem_landmark_gram`` / ``_time_gram_kernels``) with their argument types.  Bound at the first call, like the weighted entry points."""
+    fn = getattr(lib, name)
+    if fn.argtypes is None:
+        common = [C.c_void_p, C.c_size_t, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint64]  # Y, num_rhs, rank, landmarks, slab_rows
+        outs = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(LssvmReducedInfo)]
+        if name == "lssvm_mi355_problem_fit_reduced":
+            fn.argtypes = [C.c_void_p] + common + outs
+        elif name == "lssvm_mi355_problem_landmark_gram":
+            fn.argtypes = [C.c_void_p] + common + [C.POINTER(C.c_double)]
+        elif name == "lssvm_mi355_problem_time_gram_kernels":
+            fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        else:
+            fn.argtypes = [C.POINTER(LssvmParams), C.c_void_p, C.c_size_t, C.c_size_t] + common + outs + [C.c_void_p]
         fn.restype = C.c_int
     return fn
 

@@ -24,7 +24,7 @@ from ._capi import LssvmCgInfo, LssvmParams, LssvmPredictInfo, LssvmShard, Optio
 from .exceptions import InvalidParameterError
 from .parameter import Parameter
 
-__all__ = ["Options", "Predictor", "solve_system_of_linear_equations", "solve_refined", "solve_cost_path", "solve_pcg", "predict_values", "predict_values_multi", "generate_q", "run_device_kernel", "calculate_w", "ResidentProblem",
+__all__ = ["Options", "Predictor", "solve_system_of_linear_equations", "solve_refined", "solve_cost_path", "solve_pcg", "fit_reduced", "predict_values", "predict_values_multi", "generate_q", "run_device_kernel", "calculate_w", "ResidentProblem",
            "comm_get_unique_id", "comm_init", "comm_destroy"]
 
 
@@ -243,6 +243,51 @@ def solve_pcg(params: Parameter, A, B, eps: float, max_iter: int, rank: int = 25
     ps = _params_struct(params, d)
     fn = _capi.pcg_entry(f"lssvm_mi355_solve_pcg_{suffix_of(A.dtype)}")
     return _pcg_call(fn, (C.byref(ps), ptr(A), N, d), (rank, lm_ptr), B2, single, N, A.dtype, eps, max_iter, tail=(options_ptr(options),))
+
+
+def _reduced_arguments(Y, N: int, dtype, rank, landmarks, slab_rows):
+    """The arguments of a fixed-size fit as the library takes them, checked as it checks them: ``(Y2, single, rank, landmarks array or None, pointer or NULL, slab_rows)``."""
+    Y = np.ascontiguousarray(Y, dtype=dtype)
+    single = Y.ndim == 1
+    Y2 = Y.reshape(1, -1) if single else Y
+    if Y2.ndim != 2 or Y2.shape[0] == 0 or Y2.shape[1] != N:
+        raise InvalidParameterError(f"The number of data points in the matrix A ({N}) and the values in every right hand side vector ({Y2.shape[-1] if Y2.ndim else 0}) must be the same!")
+    if landmarks is None and not isinstance(rank, (int, np.integer)):
+        raise InvalidParameterError(f"The rank of the reduced model must be an integer, but is {rank!r}!")
+    rank, lm, lm_ptr = _landmarks_argument(rank, landmarks)
+    most = min(N, _capi.REDUCED_MAX_RANK)
+    if not 1 <= rank <= most:
+        raise InvalidParameterError(f"The rank of the reduced model must lie in [1, {most}], but is {rank}!")
+    if not (isinstance(slab_rows, (int, np.integer)) and slab_rows >= 0 and slab_rows % 256 == 0):
+        raise InvalidParameterError(f"slab_rows must be a multiple of 256 (0: the library's default), but is {slab_rows!r}!")
+    return Y2, single, rank, lm, lm_ptr, int(slab_rows)
+
+
+def _reduced_call(fn, head, Y2, single: bool, rank: int, lm_ptr, slab_rows: int, tail=()):
+    k = Y2.shape[0]
+    betas = np.zeros((k, rank), dtype=np.float64)
+    rhos = np.zeros(k, dtype=np.float64)
+    used = np.zeros(rank, dtype=np.uint64)
+    info = _capi.LssvmReducedInfo()
+    dp = C.POINTER(C.c_double)
+    check(fn(*head, ptr(Y2), k, rank, lm_ptr, slab_rows, betas.ctypes.data_as(dp), rhos.ctypes.data_as(dp), used.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(info), *tail))
+    if single:
+        return betas[0], float(rhos[0]), used, info.as_dict()
+    return betas, rhos, used, info.as_dict()
+
+
+def fit_reduced(params: Parameter, A, Y, rank: int, landmarks=None, slab_rows: int = 0, options: Options | None = None):
+    """The fixed-size (reduced) LS-SVM over ``rank`` landmark points (``lssvm_mi355_fit_reduced_*``; opt-in: it trades accuracy for a model of ``rank`` support vectors):
+    ``f(x) = sum_j beta_j k(x, x_L[j]) - rho`` minimises ``1/2 beta^T K_mm beta + C/2 sum_i (y_i - f(x_i))^2``.  ``Y``: one right-hand side ``(N,)`` or ``k`` of them
+    ``(k, N)`` -- one landmark block, one Gram matrix and one factorisation serve all.  ``landmarks``: distinct point indices (their number is the rank) or None for the
+    preconditioner's fixed rule.  ``slab_rows``: rows of the landmark block held at a time (a multiple of 256; 0: 65 536).  Returns ``(betas, rhos, landmarks, info)``,
+    ``betas`` and ``rhos`` float64 whatever the data's type and shaped like ``Y``; ``info``: the ``lssvm_reduced_info`` dict.  Device 0; deterministic; no CG."""
+    A = _as_matrix(A)
+    N, d = A.shape
+    Y2, single, rank, _, lm_ptr, slab_rows = _reduced_arguments(Y, N, A.dtype, rank, landmarks, slab_rows)
+    ps = _params_struct(params, d)
+    fn = _capi.reduced_entry(f"lssvm_mi355_fit_reduced_{suffix_of(A.dtype)}")
+    return _reduced_call(fn, (C.byref(ps), ptr(A), N, d), Y2, single, rank, lm_ptr, slab_rows, tail=(options_ptr(options),))
 
 
 def generate_q(params: Parameter, data, options: Options | None = None):
@@ -603,6 +648,29 @@ class ResidentProblem:
         ``(num_points,)`` or ``k`` of them, one after the other.  Returns ``(alphas, rhos, infos)`` shaped like ``B``; the problem is left as it was."""
         B2, single = _pcg_arguments(B, self.num_points, self.dtype, eps, max_iter)
         return _pcg_call(_capi.pcg_entry("lssvm_mi355_problem_solve_pcg"), (self._h,), (), B2, single, self.num_points, self.dtype, eps, max_iter)
+
+    def fit_reduced(self, Y, rank: int, landmarks=None, slab_rows: int = 0):
+        """:func:`fit_reduced` on this resident problem at its own cost (``lssvm_mi355_problem_fit_reduced``).  The problem is left as it was and keeps its preconditioner.
+        Not on a problem of several devices or ranks, not with weights set, not between :meth:`cg_begin` and :meth:`cg_finish`."""
+        Y2, single, rank, _, lm_ptr, slab_rows = _reduced_arguments(Y, self.num_points, self.dtype, rank, landmarks, slab_rows)
+        return _reduced_call(_capi.reduced_entry("lssvm_mi355_problem_fit_reduced"), (self._h,), Y2, single, rank, lm_ptr, slab_rows)
+
+    def landmark_gram(self, Y, rank: int, landmarks=None, slab_rows: int = 0):
+        """The operator of :meth:`fit_reduced` alone (a test aid, ``lssvm_mi355_problem_landmark_gram``): ``[Phi | 1 | Y]^T [Phi | 1 | Y]`` as the device sums it,
+        ``(rank + 1 + k, rank + 1 + k)`` float64, both triangles."""
+        Y2, _, rank, _, lm_ptr, slab_rows = _reduced_arguments(Y, self.num_points, self.dtype, rank, landmarks, slab_rows)
+        cols = rank + 1 + Y2.shape[0]
+        out = np.zeros((cols, cols), dtype=np.float64)
+        check(_capi.reduced_entry("lssvm_mi355_problem_landmark_gram")(self._h, ptr(Y2), Y2.shape[0], rank, lm_ptr, slab_rows, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def time_gram_kernels(self, repeats: int = 10):
+        """A measurement aid (``lssvm_mi355_problem_time_gram_kernels``): ``Bhat^T Bhat`` of this fp64 problem's preconditioner by the preconditioner's own kernel and by the
+        matrix-core kernels of :meth:`fit_reduced`: ``(parent_ms[repeats], mfma_ms[repeats], largest relative difference of the two results)``."""
+        parent, mfma, diff = np.zeros(int(repeats)), np.zeros(int(repeats)), C.c_double(0)
+        dp = C.POINTER(C.c_double)
+        check(_capi.reduced_entry("lssvm_mi355_problem_time_gram_kernels")(self._h, int(repeats), parent.ctypes.data_as(dp), mfma.ctypes.data_as(dp), C.byref(diff)))
+        return parent, mfma, float(diff.value)
 
     def cg_begin(self, y, eps: float):
         y = np.ascontiguousarray(y, dtype=self.dtype)

@@ -210,6 +210,21 @@ void pcg_one_shot(const lssvm_params *params, const T *X, size_t N, size_t d, co
     prob.solve_pcg(Y, num_rhs, eps, max_iter, alphas_out, rhos_out, infos_out);
 }
 
+/* lssvm_mi355_fit_reduced_*: every argument that needs no device is checked before one is touched; problem and fit on device 0 */
+template <typename T>
+void fit_reduced_one_shot(const lssvm_params *params, const T *X, size_t N, size_t d, const T *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows,
+                          double *betas_out, double *rhos_out, uint64_t *landmarks_out, lssvm_reduced_info *info, const lssvm_mi355_options *options) {
+    lssvm::check_params(params);
+    LSSVM_REQUIRE(X != nullptr && N > 0, "The data must not be empty!");         // csvm.cpp:73
+    LSSVM_REQUIRE(d > 0, "The data points must contain at least one feature!");  // csvm.cpp:74
+    lssvm::check_reduced_arguments(Y, num_rhs, rank, slab_rows, N);
+    LSSVM_REQUIRE(betas_out != nullptr && rhos_out != nullptr, "betas_out / rhos_out must not be NULL");
+    if (landmarks != nullptr) (void) lssvm::resolve_landmarks(landmarks, static_cast<size_t>(rank), N);
+    static const int device0 = 0;
+    lssvm::Solver<T> prob(options_of(options), *params, X, LSSVM_MEM_HOST, N, d, lssvm::resolve_devices(&device0, 1, N), nullptr);
+    prob.fit_reduced(Y, num_rhs, rank, landmarks, slab_rows, betas_out, rhos_out, landmarks_out, info);
+}
+
 template <typename T>
 void generate_q_one_shot(const lssvm_params *params, const T *X, size_t N, size_t d, T *q_out, const lssvm_mi355_options *options) {
     lssvm::check_params(params);
@@ -642,6 +657,38 @@ int lssvm_mi355_solve_pcg_f32(const lssvm_params *params, const float *X, size_t
 int lssvm_mi355_solve_pcg_f64(const lssvm_params *params, const double *X, size_t num_points, size_t num_features, const double *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks,
                               double eps, uint64_t max_iter, double *alphas_out, double *rhos_out, lssvm_pcg_info *infos_out, const lssvm_mi355_options *options) {
     return guarded([&] { pcg_one_shot<double>(params, X, num_points, num_features, Y, num_rhs, rank, landmarks, eps, max_iter, alphas_out, rhos_out, infos_out, options); });
+}
+static_assert(sizeof(lssvm_reduced_info) == 64, "lssvm_reduced_info changed: plssvm_amd/_capi.py (LssvmReducedInfo) changes with it");
+int lssvm_mi355_problem_fit_reduced(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, double *betas_out, double *rhos_out,
+                                    uint64_t *landmarks_out, lssvm_reduced_info *info) {
+    return guarded([&] {
+        LSSVM_REQUIRE(p != nullptr, "problem handle must not be NULL");
+        lssvm::check_reduced_arguments(Y, num_rhs, rank, slab_rows, 0);  // (before any device work; N and the landmarks: the solver, before it touches the device)
+        LSSVM_REQUIRE(betas_out != nullptr && rhos_out != nullptr, "betas_out / rhos_out must not be NULL");
+        impl_of(p)->fit_reduced(Y, num_rhs, rank, landmarks, slab_rows, betas_out, rhos_out, landmarks_out, info);
+    });
+}
+int lssvm_mi355_problem_landmark_gram(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, double *gram_out) {
+    return guarded([&] {
+        LSSVM_REQUIRE(p != nullptr, "problem handle must not be NULL");
+        lssvm::check_reduced_arguments(Y, num_rhs, rank, slab_rows, 0);
+        LSSVM_REQUIRE(gram_out != nullptr, "gram_out must not be NULL");
+        impl_of(p)->landmark_gram(Y, num_rhs, rank, landmarks, slab_rows, gram_out);
+    });
+}
+int lssvm_mi355_problem_time_gram_kernels(lssvm_mi355_problem *p, int repeats, double *parent_ms_out, double *mfma_ms_out, double *max_diff_out) {
+    return guarded([&] {
+        LSSVM_REQUIRE(p != nullptr, "problem handle must not be NULL");
+        impl_of(p)->time_gram_kernels(repeats, parent_ms_out, mfma_ms_out, max_diff_out);
+    });
+}
+int lssvm_mi355_fit_reduced_f32(const lssvm_params *params, const float *X, size_t num_points, size_t num_features, const float *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks,
+                                uint64_t slab_rows, double *betas_out, double *rhos_out, uint64_t *landmarks_out, lssvm_reduced_info *info, const lssvm_mi355_options *options) {
+    return guarded([&] { fit_reduced_one_shot<float>(params, X, num_points, num_features, Y, num_rhs, rank, landmarks, slab_rows, betas_out, rhos_out, landmarks_out, info, options); });
+}
+int lssvm_mi355_fit_reduced_f64(const lssvm_params *params, const double *X, size_t num_points, size_t num_features, const double *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks,
+                                uint64_t slab_rows, double *betas_out, double *rhos_out, uint64_t *landmarks_out, lssvm_reduced_info *info, const lssvm_mi355_options *options) {
+    return guarded([&] { fit_reduced_one_shot<double>(params, X, num_points, num_features, Y, num_rhs, rank, landmarks, slab_rows, betas_out, rhos_out, landmarks_out, info, options); });
 }
 int lssvm_mi355_cg_begin(lssvm_mi355_problem *p, const void *y, double eps) {
     return guarded([&] { impl_of(p)->cg_begin(y, eps); });

@@ -1,0 +1,114 @@
+/*
+ * lssvm_landmark.hip.hpp -- the landmark block K_Nm of a resident problem in double, shared by the Nystrom preconditioner (lssvm_precond.hip) and the fixed-size
+ * model (lssvm_reduced.hip), and the host pieces both use (the factorisation, the library's landmark rule).
+ */
+#pragma once
+
+#include "lssvm_problem.hip.hpp"
+
+#include <cstdint>
+#include <vector>
+
+namespace lssvm {
+
+template <typename T>
+struct PcVec;
+template <>
+struct PcVec<float> {
+    using type = f32x4;
+    static constexpr int n = 4;
+};
+template <>
+struct PcVec<double> {
+    using type = f64x2;
+    static constexpr int n = 2;
+};
+
+/* Kd[l][i - row0] = k(x_i, x_lm[l]) for the points row0 <= i < N of this launch's row blocks (exact zeros from N on) and a tile of 16 landmarks, in double: the
+ * landmarks' features go through LDS in chunks of 32, a thread walks its own row in 16-byte pieces.  `gamma`: the kernel function's, divided by the square of the
+ * factor X_ carries.  `ldN`: doubles between two landmarks' columns; the grid's x extent times 256 rows are written from column offset 0 on. */
+template <typename T>
+__global__ __launch_bounds__(256) void k_landmark_block(const T *__restrict__ X, int ldx, int N, int row0, const int *__restrict__ lm, int m, int kernel_type, int degree, double gamma,
+                                                        double coef0, double *__restrict__ Kd, size_t ldN) {
+    constexpr int FC = 32, V = PcVec<T>::n;
+    __shared__ T xl[16][FC];
+    const int local = blockIdx.x * 256 + threadIdx.x;
+    const int i = row0 + local;
+    const int l0 = blockIdx.y * 16;
+    const T *xi = X + static_cast<size_t>(min(i, N - 1)) * ldx;
+    double acc[16];
+#pragma unroll
+    for (int l = 0; l < 16; ++l) acc[l] = 0.0;
+    for (int f0 = 0; f0 < ldx; f0 += FC) {  // (ldx is a multiple of the k-chunk: 32 in fp32, 16 in fp64)
+        __syncthreads();
+        for (int e = threadIdx.x; e < 16 * FC; e += 256) {
+            const int l = e / FC, f = e % FC;
+            xl[l][f] = (l0 + l < m && f0 + f < ldx) ? X[static_cast<size_t>(lm[l0 + l]) * ldx + f0 + f] : T(0);
+        }
+        __syncthreads();
+        const int fend = min(FC, ldx - f0);
+        for (int f = 0; f < fend; f += V) {
+            const typename PcVec<T>::type v = *reinterpret_cast<const typename PcVec<T>::type *>(xi + f0 + f);
+#pragma unroll
+            for (int u = 0; u < V; ++u) {
+                const double a = static_cast<double>(v[u]);
+#pragma unroll
+                for (int l = 0; l < 16; ++l) {
+                    const double b = static_cast<double>(xl[l][f + u]);
+                    if (kernel_type == LSSVM_KERNEL_RBF) {
+                        acc[l] += (a - b) * (a - b);
+                    } else {
+                        acc[l] += a * b;
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int l = 0; l < 16; ++l) {
+        if (l0 + l >= m) continue;
+        double k;
+        if (kernel_type == LSSVM_KERNEL_RBF) {
+            k = exp(-gamma * acc[l]);
+        } else if (kernel_type == LSSVM_KERNEL_POLYNOMIAL) {
+            const double base = gamma * acc[l] + coef0;
+            k = 1.0;
+            for (int e = 0; e < abs(degree); ++e) k *= base;
+            if (degree < 0) k = 1.0 / k;
+        } else {
+            k = gamma * acc[l];
+        }
+        Kd[static_cast<size_t>(l0 + l) * ldN + local] = i < N ? k : 0.0;
+    }
+}
+
+/* G[j][k] = sum over i of Bhat[j][i] Bhat[k][i] for one 16 x 16 tile on or below the diagonal: ONE thread owns an entry and adds its products for i ascending, in
+ * double -- a single fixed-order sum per entry, no partial sums to combine and no atomics.  64 rows of both column groups go through LDS per step. */
+template <typename T>
+__global__ __launch_bounds__(256) void k_precond_gram(const T *__restrict__ Bhat, size_t ldn, int cols, double *__restrict__ G, int ldg) {
+    if (blockIdx.y > blockIdx.x) return;
+    __shared__ double A[16][65], B[16][65];
+    const int tj = threadIdx.x / 16, tk = threadIdx.x % 16;
+    const int j0 = blockIdx.x * 16, k0 = blockIdx.y * 16;
+    const int lr = threadIdx.x / 16, lc = (threadIdx.x % 16) * 4;
+    double acc = 0.0;
+    for (size_t i0 = 0; i0 < ldn; i0 += 64) {
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            A[lr][lc + u] = j0 + lr < cols ? static_cast<double>(Bhat[static_cast<size_t>(j0 + lr) * ldn + i0 + lc + u]) : 0.0;
+            B[lr][lc + u] = k0 + lr < cols ? static_cast<double>(Bhat[static_cast<size_t>(k0 + lr) * ldn + i0 + lc + u]) : 0.0;
+        }
+        __syncthreads();
+#pragma unroll 16
+        for (int c = 0; c < 64; ++c) acc += A[tj][c] * B[tk][c];
+    }
+    G[static_cast<size_t>(j0 + tj) * ldg + k0 + tk] = acc;
+}
+
+/* A = L L^T in place (lower triangle; the upper one is left alone); false at a pivot that is not positive and finite   (lssvm_precond.hip) */
+bool cholesky_lower(std::vector<double> &A, int m);
+/* the library's own landmarks: the first `rank` entries of a Fisher-Yates shuffle of 0 ... N-1 driven by splitmix64 from a fixed state (include/plssvm_amd.h) */
+std::vector<uint64_t> default_landmarks(size_t N, size_t rank);
+
+}  // namespace lssvm

@@ -14,7 +14,7 @@
  * every 50th iteration.  Ad, alpha, x and r are the recipe's own kernels (k_Ad_and_dAd, k_update_x_r, k_residual: alpha's numerator r.z stands in the scalar slot they
  * read); only the direction update is new.  The Gram pass is launched, not changed.  Compiled for gfx950 only.
  */
-#include "lssvm_problem.hip.hpp"
+#include "lssvm_landmark.hip.hpp"
 
 #include "lssvm_kernels.hip.hpp"
 
@@ -34,76 +34,9 @@ constexpr int PC_COLS_PER_WAVE = (PC_MAX_COLS + PC_WAVES - 1) / PC_WAVES;  // 33
 constexpr int PC_COLS_PER_ROUND = (PC_COLS_PER_WAVE + 1) / 2;              // (a) takes them in two rounds of 17
 constexpr int PC_SOLVE_COLS = 32;                             // columns of Bhat per block of k_precond_solve
 
-template <typename T>
-struct PcVec;
-template <>
-struct PcVec<float> {
-    using type = f32x4;
-    static constexpr int n = 4;
-};
-template <>
-struct PcVec<double> {
-    using type = f64x2;
-    static constexpr int n = 2;
-};
-
 /* ---------------------------------------------------------------- the build ---------------------------------------------------------------- */
 
-/* Kd[l][i] = k(x_i, x_lm[l]) for the points i < N (zeros up to ldN) and a tile of 16 landmarks, in double: the landmarks' features go through LDS in chunks of 32, a
- * thread walks its own row in 16-byte pieces.  `gamma`: the kernel function's, divided by the square of the factor X_ carries. */
-template <typename T>
-__global__ __launch_bounds__(256) void k_landmark_block(const T *__restrict__ X, int ldx, int N, const int *__restrict__ lm, int m, int kernel_type, int degree, double gamma, double coef0,
-                                                        double *__restrict__ Kd, size_t ldN) {
-    constexpr int FC = 32, V = PcVec<T>::n;
-    __shared__ T xl[16][FC];
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const int l0 = blockIdx.y * 16;
-    const T *xi = X + static_cast<size_t>(min(i, N - 1)) * ldx;
-    double acc[16];
-#pragma unroll
-    for (int l = 0; l < 16; ++l) acc[l] = 0.0;
-    for (int f0 = 0; f0 < ldx; f0 += FC) {  // (ldx is a multiple of the k-chunk: 32 in fp32, 16 in fp64)
-        __syncthreads();
-        for (int e = threadIdx.x; e < 16 * FC; e += 256) {
-            const int l = e / FC, f = e % FC;
-            xl[l][f] = (l0 + l < m && f0 + f < ldx) ? X[static_cast<size_t>(lm[l0 + l]) * ldx + f0 + f] : T(0);
-        }
-        __syncthreads();
-        const int fend = min(FC, ldx - f0);
-        for (int f = 0; f < fend; f += V) {
-            const typename PcVec<T>::type v = *reinterpret_cast<const typename PcVec<T>::type *>(xi + f0 + f);
-#pragma unroll
-            for (int u = 0; u < V; ++u) {
-                const double a = static_cast<double>(v[u]);
-#pragma unroll
-                for (int l = 0; l < 16; ++l) {
-                    const double b = static_cast<double>(xl[l][f + u]);
-                    if (kernel_type == LSSVM_KERNEL_RBF) {
-                        acc[l] += (a - b) * (a - b);
-                    } else {
-                        acc[l] += a * b;
-                    }
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int l = 0; l < 16; ++l) {
-        if (l0 + l >= m) continue;
-        double k;
-        if (kernel_type == LSSVM_KERNEL_RBF) {
-            k = exp(-gamma * acc[l]);
-        } else if (kernel_type == LSSVM_KERNEL_POLYNOMIAL) {
-            const double base = gamma * acc[l] + coef0;
-            k = 1.0;
-            for (int e = 0; e < abs(degree); ++e) k *= base;
-            if (degree < 0) k = 1.0 / k;
-        } else {
-            k = gamma * acc[l];
-        }
-        Kd[static_cast<size_t>(l0 + l) * ldN + i] = i < N ? k : 0.0;
-    }
-}
+/* (K_Nm itself: k_landmark_block, lssvm_landmark.hip.hpp) */
 
 /* Kmm[k][l] = Kd[l][lm[k]] */
 __global__ void k_gather_kmm(const double *__restrict__ Kd, size_t ldN, const int *__restrict__ lm, int m, double *__restrict__ Kmm) {
@@ -130,29 +63,7 @@ __global__ __launch_bounds__(256) void k_make_bhat(const double *__restrict__ Bf
     Bhat[static_cast<size_t>(k) * ldn + i] = static_cast<T>(v);
 }
 
-/* G[j][k] = sum over i of Bhat[j][i] Bhat[k][i] for one 16 x 16 tile on or below the diagonal: ONE thread owns an entry and adds its products for i ascending, in
- * double -- a single fixed-order sum per entry, no partial sums to combine and no atomics.  64 rows of both column groups go through LDS per step. */
-template <typename T>
-__global__ __launch_bounds__(256) void k_precond_gram(const T *__restrict__ Bhat, size_t ldn, int cols, double *__restrict__ G, int ldg) {
-    if (blockIdx.y > blockIdx.x) return;
-    __shared__ double A[16][65], B[16][65];
-    const int tj = threadIdx.x / 16, tk = threadIdx.x % 16;
-    const int j0 = blockIdx.x * 16, k0 = blockIdx.y * 16;
-    const int lr = threadIdx.x / 16, lc = (threadIdx.x % 16) * 4;
-    double acc = 0.0;
-    for (size_t i0 = 0; i0 < ldn; i0 += 64) {
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            A[lr][lc + u] = j0 + lr < cols ? static_cast<double>(Bhat[static_cast<size_t>(j0 + lr) * ldn + i0 + lc + u]) : 0.0;
-            B[lr][lc + u] = k0 + lr < cols ? static_cast<double>(Bhat[static_cast<size_t>(k0 + lr) * ldn + i0 + lc + u]) : 0.0;
-        }
-        __syncthreads();
-#pragma unroll 16
-        for (int c = 0; c < 64; ++c) acc += A[tj][c] * B[tk][c];
-    }
-    G[static_cast<size_t>(j0 + tj) * ldg + k0 + tk] = acc;
-}
+/* (G = Bhat^T Bhat: k_precond_gram, lssvm_landmark.hip.hpp) */
 
 /* ---------------------------------------------------------------- the apply ---------------------------------------------------------------- */
 
@@ -324,25 +235,6 @@ __global__ __launch_bounds__(RED_THREADS) void k_pcg_update_d(T *__restrict__ d,
 
 /* ---------------------------------------------------------------- host: dense factorisations in double (<= 513 x 513, row major) ---------------------------------------------------------------- */
 
-/* A = L L^T in place (lower triangle; the upper one is left alone); false at a pivot that is not positive and finite */
-bool cholesky_lower(std::vector<double> &A, int m) {
-    for (int i = 0; i < m; ++i) {
-        double *ai = &A[static_cast<size_t>(i) * m];
-        for (int j = 0; j <= i; ++j) {
-            const double *aj = &A[static_cast<size_t>(j) * m];
-            double s = ai[j];
-            for (int k = 0; k < j; ++k) s -= ai[k] * aj[k];
-            if (j < i) {
-                ai[j] = s / aj[j];
-            } else {
-                if (!(s > 0.0) || !std::isfinite(s)) return false;
-                ai[i] = std::sqrt(s);
-            }
-        }
-    }
-    return true;
-}
-
 /* L^-1 (lower triangular) of the lower triangle of L, row by row: row i = (e_i - sum over k < i of L[i][k] row k) / L[i][i] */
 std::vector<double> invert_lower(const std::vector<double> &L, int m) {
     std::vector<double> inv(static_cast<size_t>(m) * m, 0.0);
@@ -377,6 +269,27 @@ std::vector<double> inverse_from_lower_inverse(const std::vector<double> &inv, i
     return out;
 }
 
+}  // namespace
+
+/* A = L L^T in place (lower triangle; the upper one is left alone); false at a pivot that is not positive and finite */
+bool cholesky_lower(std::vector<double> &A, int m) {
+    for (int i = 0; i < m; ++i) {
+        double *ai = &A[static_cast<size_t>(i) * m];
+        for (int j = 0; j <= i; ++j) {
+            const double *aj = &A[static_cast<size_t>(j) * m];
+            double s = ai[j];
+            for (int k = 0; k < j; ++k) s -= ai[k] * aj[k];
+            if (j < i) {
+                ai[j] = s / aj[j];
+            } else {
+                if (!(s > 0.0) || !std::isfinite(s)) return false;
+                ai[i] = std::sqrt(s);
+            }
+        }
+    }
+    return true;
+}
+
 /* the library's own landmarks: the first `rank` entries of a Fisher-Yates shuffle of 0 ... N-1 driven by splitmix64 from a fixed state (include/plssvm_amd.h) */
 std::vector<uint64_t> default_landmarks(size_t N, size_t rank) {
     std::vector<uint64_t> perm(N);
@@ -393,7 +306,15 @@ std::vector<uint64_t> default_landmarks(size_t N, size_t rank) {
     return perm;
 }
 
-}  // namespace
+std::vector<uint64_t> resolve_landmarks(const uint64_t *landmarks, size_t rank, size_t N) {
+    if (landmarks == nullptr) return default_landmarks(N, rank);
+    std::vector<uint64_t> lm(landmarks, landmarks + rank);
+    std::vector<uint64_t> sorted(lm);
+    std::sort(sorted.begin(), sorted.end());
+    LSSVM_REQUIRE(sorted.back() < N, "Every landmark must be the index of a data point (< " + std::to_string(N) + "), but one is " + std::to_string(sorted.back()) + "!");
+    LSSVM_REQUIRE(std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end(), "The landmarks must be distinct!");
+    return lm;
+}
 
 void check_pcg_arguments(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, const void *alphas_out, const double *rhos_out, const lssvm_pcg_info *infos_out) {
     LSSVM_REQUIRE(Y != nullptr, "The right hand side vector must not be empty!");
@@ -423,16 +344,7 @@ void Solver<T>::build_preconditioner(uint64_t rank, const uint64_t *landmarks, l
     const size_t N = p.N_;
     check_precond_rank(rank, N);
     const int m = static_cast<int>(rank), cols = m + 1, n = p.n_;
-    std::vector<uint64_t> lm;
-    if (landmarks != nullptr) {
-        lm.assign(landmarks, landmarks + m);
-        std::vector<uint64_t> sorted(lm);
-        std::sort(sorted.begin(), sorted.end());
-        LSSVM_REQUIRE(sorted.back() < N, "Every landmark must be the index of a data point (< " + std::to_string(N) + "), but one is " + std::to_string(sorted.back()) + "!");
-        LSSVM_REQUIRE(std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end(), "The landmarks must be distinct!");
-    } else {
-        lm = default_landmarks(N, static_cast<size_t>(m));
-    }
+    const std::vector<uint64_t> lm = resolve_landmarks(landmarks, static_cast<size_t>(m), N);
 
     const double t0 = now_ms();
     const SetOnExit<bool> busy = hold_busy();
@@ -457,7 +369,7 @@ void Solver<T>::build_preconditioner(uint64_t rank, const uint64_t *landmarks, l
     const lssvm_params &prm = p.params_;
     const double scale2 = p.x_scale_ * p.x_scale_;
     const double gamma = prm.kernel_type == LSSVM_KERNEL_LINEAR ? 1.0 / scale2 : static_cast<double>(static_cast<T>(prm.gamma)) / scale2;
-    hipLaunchKernelGGL(k_landmark_block<T>, dim3(static_cast<unsigned>(ldN / 256), (m + 15) / 16), dim3(256), 0, st, p.X_.data.p, p.X_.ldx, static_cast<int>(N), lm_dev.p, m, prm.kernel_type,
+    hipLaunchKernelGGL(k_landmark_block<T>, dim3(static_cast<unsigned>(ldN / 256), (m + 15) / 16), dim3(256), 0, st, p.X_.data.p, p.X_.ldx, static_cast<int>(N), 0, lm_dev.p, m, prm.kernel_type,
                        prm.degree, gamma, static_cast<double>(static_cast<T>(prm.coef0)), Kd.p, ldN);
     Kmm_dev.alloc_zero(static_cast<size_t>(m) * m, st);
     hipLaunchKernelGGL(k_gather_kmm, dim3((m * m + 255) / 256), dim3(256), 0, st, Kd.p, ldN, lm_dev.p, m, Kmm_dev.p);

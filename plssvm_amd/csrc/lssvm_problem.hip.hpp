@@ -603,6 +603,11 @@ struct ProblemBase {
     virtual void precond_landmarks(uint64_t *out) = 0;                                                          // lssvm_mi355_problem_precond_landmarks
     virtual void precond_apply(const void *r, void *z_out) = 0;                                                 // lssvm_mi355_problem_precond_apply
     virtual void solve_pcg(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_pcg_info *infos_out) = 0;  // lssvm_mi355_problem_solve_pcg
+    /* the fixed-size model (lssvm_reduced.hip) */
+    virtual void fit_reduced(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, double *betas_out, double *rhos_out,
+                             uint64_t *landmarks_out, lssvm_reduced_info *info) = 0;  // lssvm_mi355_problem_fit_reduced
+    virtual void landmark_gram(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, double *gram_out) = 0;  // lssvm_mi355_problem_landmark_gram
+    virtual void time_gram_kernels(int repeats, double *parent_ms_out, double *mfma_ms_out, double *max_diff_out) = 0;  // lssvm_mi355_problem_time_gram_kernels
     virtual void cg_begin(const void *y, double eps) = 0;
     virtual void cg_step(uint64_t iterations, int *done_out) = 0;
     virtual void cg_finish(void *alpha_out, double *rho_out, lssvm_cg_info *info) = 0;
@@ -688,6 +693,11 @@ class Solver final : public ProblemBase {
     void precond_landmarks(uint64_t *out) override;
     void precond_apply(const void *r, void *z_out) override;
     void solve_pcg(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_pcg_info *infos_out) override;
+    /* the fixed-size model over m landmarks: [Phi | 1 | Y]^T [Phi | 1 | Y] on the fp64 matrix cores, slab by slab, and the host's solve (lssvm_reduced.hip) */
+    void fit_reduced(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, double *betas_out, double *rhos_out, uint64_t *landmarks_out,
+                     lssvm_reduced_info *info) override;
+    void landmark_gram(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, double *gram_out) override;
+    void time_gram_kernels(int repeats, double *parent_ms_out, double *mfma_ms_out, double *max_diff_out) override;
     void cg_begin(const void *y, double eps) override;
     /* cg_begin for the inner solve of the mixed-precision refinement: A e = r / max|r| from e = 0 -- b, the first residual and delta0 = b^T b come from ONE O(n) kernel
      * over the outer fp64 residual `r_dev` (device 0, complete when the call is made; `absmax_part_dev`: k_absmax's partials of it), no Gram pass.  cg_step follows as
@@ -726,6 +736,9 @@ class Solver final : public ProblemBase {
     void solve_on_lanes(const T *Y, size_t num_rhs, double eps, uint64_t max_iter, T *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out);
     Problem<T> &precond_problem(const char *what);                        // the checks every preconditioner entry point shares; shard 0
     void enqueue_precond_apply(const T *r, T *z, double *part_rz) const;  // z = r - Bhat G^-1 Bhat^T r and the partial sums of r.z
+    /* what fit_reduced and landmark_gram share: the checks, the slabs, St (cols x cols, both triangles) and K_mm (rank x rank) on the host */
+    void reduced_gram(const char *what, const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, std::vector<uint64_t> &lm_out,
+                      std::vector<double> &gram_out, std::vector<double> &kmm_out, lssvm_reduced_info &info);
     T *vec_of(Problem<T> &p, Vec which) const { return which == Vec::d ? p.own_.d.p : (which == Vec::x ? p.own_.x.p : p.tmp_.p); }
 
     Options opt_{};
@@ -762,6 +775,13 @@ void solve_refined_f64(const Options &opt, const lssvm_params &params, const dou
 /* the arguments of lssvm_mi355_problem_solve_pcg / lssvm_mi355_solve_pcg_* and of the preconditioner's rank that need no device (lssvm_precond.hip) */
 void check_pcg_arguments(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, const void *alphas_out, const double *rhos_out, const lssvm_pcg_info *infos_out);
 void check_precond_rank(uint64_t rank, size_t num_points);
+/* the caller's `rank` landmarks checked (distinct, < num_points), or the library's own for NULL (lssvm_precond.hip) */
+std::vector<uint64_t> resolve_landmarks(const uint64_t *landmarks, size_t rank, size_t num_points);
+
+/* the arguments of lssvm_mi355_problem_fit_reduced / _landmark_gram / lssvm_mi355_fit_reduced_* that need no device (lssvm_reduced.hip); num_points 0: not known yet */
+constexpr int REDUCED_MAX_RANK = 1024;
+constexpr uint64_t REDUCED_DEFAULT_SLAB_ROWS = 65536;
+void check_reduced_arguments(const void *Y, size_t num_rhs, uint64_t rank, uint64_t slab_rows, size_t num_points);
 
 /* the arguments of lssvm_mi355_problem_solve_cost_path / lssvm_mi355_solve_cost_path_* that need no device: checked before one is touched (lssvm_path.hip) */
 constexpr size_t PATH_MAX_COSTS = 64;

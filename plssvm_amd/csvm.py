@@ -161,6 +161,31 @@ class CSVM:
             models.append(Model(at_cost, data, alpha=np.asarray(alphas[s]), rho=rhos[s]))
         return models
 
+    def solve_reduced_systems(self, params, A, Y, rank, landmarks=None):
+        """The fixed-size model of every row of ``Y`` over the same landmarks: ``(betas[k, m] float64, rhos[k] float64, landmarks[m], info)``.  Boundary of
+        :meth:`fit_reduced`; the MI355X backend implements it."""
+        raise NotImplementedError
+
+    def fit_reduced(self, data: DataSet, rank: int, landmarks=None) -> Model:
+        """A fixed-size (reduced) LS-SVM model of ``rank`` support vectors (no counterpart in the reference): the decision function is expanded over
+        ``rank`` landmark points only -- the library's fixed choice (the preconditioner's rule) or the distinct point indices ``landmarks``, whose number is then the rank --
+        and fitted to ALL points by one pass over the N x rank kernel block and a dense solve, without CG.  The model is an ordinary :class:`Model` whose data set is
+        the landmark rows of ``data`` (file format, predict, score); it trades accuracy for size.  A two-class model file groups its support vectors by class, so the
+        landmarks must hold points of both classes.  ``last_cg_info`` keeps the ``lssvm_reduced_info`` report with ``iterations`` = 0."""
+        if not data.has_labels():
+            raise InvalidParameterError("No labels given for training! Maybe the data is only usable for prediction?")  # csvm.hpp:298
+        labels = data.labels()
+        if landmarks is not None:
+            _check_landmark_classes(data, landmarks)  # (before anything is computed)
+        params = self.params.resolved(data.num_features())
+        t0 = time.perf_counter()
+        betas, rhos, used, info = self.solve_reduced_systems(params, data.data(), data.mapped_labels().reshape(1, -1), rank, landmarks)
+        info = dict(info, iterations=0, landmarks=np.asarray(used), total_runtime_ms=(time.perf_counter() - t0) * 1e3)
+        self.last_cg_info = info
+        rows = _check_landmark_classes(data, used)
+        reduced = DataSet(data.data()[rows], [labels[i] for i in rows.tolist()], real_type=data.real_type)
+        return Model(params, reduced, alpha=np.asarray(betas[0]).astype(data.real_type), rho=rhos[0])
+
     def predict(self, model: Model, data: DataSet):
         if model.num_features() != data.num_features():
             raise InvalidParameterError(f"Number of features per data point ({data.num_features()}) must match the number of features per support vector of the "
@@ -191,6 +216,27 @@ def _checked_costs(costs) -> list:
     if not all(np.isfinite(c) and c > 0.0 for c in costs):
         raise InvalidParameterError("Every cost of the path must be finite and greater than 0.0!")
     return costs
+
+
+def _check_landmark_classes(data: DataSet, landmarks) -> np.ndarray:
+    """The landmarks of a two-class fixed-size model as row indices; raises where they are no valid list of rows or miss one of the two classes."""
+    try:
+        rows = np.asarray(landmarks).astype(np.int64).reshape(-1)
+    except (TypeError, ValueError):
+        raise InvalidParameterError("The landmarks must be a non-empty list of point indices!") from None
+    if rows.size == 0 or np.asarray(landmarks).ndim != 1:
+        raise InvalidParameterError("The landmarks must be a non-empty list of point indices!")
+    N = data.num_data_points()
+    if rows.min() < 0 or rows.max() >= N:
+        raise InvalidParameterError(f"Every landmark must be the index of a data point (< {N}), but one is {int(rows.max() if rows.max() >= N else rows.min())}!")
+    if np.unique(rows).size != rows.size:
+        raise InvalidParameterError("The landmarks must be distinct!")
+    y = data.mapped_labels()[rows]
+    for sign in (-1, 1):
+        if not np.any(y == sign):
+            raise InvalidParameterError(f'The landmarks hold no point of the class "{data.mapping.label_of(sign)}": a model file groups its support vectors by class, '
+                                        "so the landmarks of a two-class model must include both classes!")
+    return rows
 
 
 def _drop_zero_weights(data: DataSet, sample_weight):
@@ -294,6 +340,14 @@ class MI355CSVM(CSVM):
                     info["path_passes"] = passes
                 solved.append((alphas, rhos, infos))
         return solved
+
+    def solve_reduced_systems(self, params, A, Y, rank, landmarks=None):
+        """``backend.fit_reduced`` on device 0: one landmark block, one Gram matrix on the fp64 matrix cores and one factorisation for all rows of ``Y``.  A backend object of
+        several devices raises, as the library does on a sharded problem."""
+        if self.use_devices != 1:
+            raise InvalidParameterError(f"The reduced model is fitted on one device, but this backend object shards a solve over {'every visible device' if self.use_devices == 0 else self.use_devices}"
+                                        f"{'' if self.use_devices == 0 else ' devices'} (num_devices={self.use_devices})!")
+        return backend.fit_reduced(params, A, Y, rank, landmarks=landmarks, options=self._options)
 
     def _one_device_path(self) -> None:
         if self.use_devices != 1:

@@ -301,6 +301,53 @@ def fit_cost_path(estimator, X, y, Cs):
     return clones
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# the fixed-size model: `rank` landmark points as the only support vectors (CSVM.fit_reduced)
+# ---------------------------------------------------------------------------------------------------------------------
+def fit_reduced(estimator, X, y, rank, landmarks=None):
+    """A fitted clone of ``estimator`` whose model has ``rank`` support vectors only (the fixed-size LS-SVM, :meth:`plssvm_amd.csvm.CSVM.fit_reduced`): the library's fixed
+    choice of landmark points or the distinct row indices ``landmarks`` (their number is then the rank).  Two classes and one-vs-all alike; one landmark block, one Gram
+    matrix and one factorisation serve all classes.  No CG runs: ``tol`` and ``max_iter`` play no part and ``n_iter_`` is 0.  ``support_`` holds the landmarks,
+    ``dual_coef_`` has shape ``(n_classifiers, rank)``.  ``class_weight`` must be None; ``estimator`` itself stays unfitted."""
+    if not isinstance(estimator, SVC):
+        raise InvalidParameterError("estimator must be a plssvm_amd.svc.SVC")
+    if estimator.class_weight is not None:
+        raise InvalidParameterError("the reduced model is fitted to the unweighted objective: class_weight must be None")
+    X, y = np.asarray(X), np.asarray(y)
+    if X.ndim != 2 or y.ndim != 1 or y.shape[0] != X.shape[0]:
+        raise InvalidParameterError(f"X must be a matrix and y a vector of as many labels as X has rows, but their shapes are {X.shape} and {y.shape}!")
+    params = estimator._params()
+    classes = np.array(sorted(set(y.tolist())))
+    class_weight = np.ones(len(classes))
+    svm = make_csvm(params=params)
+    clone = SVC(**estimator.get_params())
+    if len(classes) > 2:
+        Xr = np.ascontiguousarray(X, dtype=estimator.real_type)
+        resolved = params.resolved(Xr.shape[1])
+        betas, rhos, used, info = svm.solve_reduced_systems(resolved, Xr, _multiclass.one_vs_all_targets(classes, y, Xr.dtype), rank, landmarks)
+        rows = np.asarray(used).astype(np.int64)
+        infos = [dict(info, iterations=0) for _ in classes]
+        model = _multiclass.OneVsAllModel(resolved, classes, np.ascontiguousarray(Xr[rows]), np.asarray(betas).astype(Xr.dtype), np.asarray(rhos).astype(Xr.dtype), infos)
+        nonzero = np.any(model.alpha != 0, axis=0)
+        clone._svm, clone._model = svm, model
+        clone._fit = {
+            "classes_": classes, "class_weight_": class_weight, "fit_status_": 0, "n_features_in_": int(X.shape[1]), "shape_fit_": tuple(int(v) for v in X.shape),
+            "n_iter_": np.zeros(len(classes), dtype=np.int64), "support_": rows.astype(np.int32), "support_vectors_": model.support_vectors,
+            "n_support_": np.array([np.count_nonzero(nonzero & (y[rows] == c)) for c in classes], dtype=np.int32), "dual_coef_": model.alpha, "intercept_": -model.rho,
+        }
+        return clone
+    data = DataSet(X, y.tolist(), real_type=estimator.real_type)
+    model = svm.fit_reduced(data, rank, landmarks)
+    clone._set_binary_fit(svm, model, model.data, X, y, class_weight, None, 0)
+    clone._fit["support_"] = _landmarks_of(svm, landmarks)
+    return clone
+
+
+def _landmarks_of(svm, landmarks):
+    """The rows a reduced two-class fit used: the caller's, or the library's own for the training set's size (read back from the backend's report)."""
+    return np.asarray(svm.last_cg_info["landmarks"] if landmarks is None else landmarks).astype(np.int32)
+
+
 def cost_path_scores(estimator, X, y, Cs, X_val, y_val):
     """The validation accuracy of a TWO-class ``estimator`` at every ``C`` of ``Cs``: one cost path (:func:`fit_cost_path`), then ONE resident predictor over all the
     models -- they share their support vectors, so the predictor takes their weight vectors two per pass over the Gram tiles.  Returns ``(scores[m], fitted clones)``."""
