@@ -534,6 +534,43 @@ int lssvm_mi355_fit_reduced_f64(const lssvm_params *params, const double *X, siz
                                 const uint64_t *landmarks, uint64_t slab_rows, double *betas_out, double *rhos_out, uint64_t *landmarks_out, lssvm_reduced_info *info,
                                 const lssvm_mi355_options *options);
 
+/* Exact leave-one-out scores of the fixed-size model over a grid of costs (opt-in) -- leave-one-out with the landmark set held fixed.  The fit
+ * above is a linear smoother with an unpenalised intercept: with Phic = Phi - 1 s^T / N (column-centred) and M_s + nu I = L L^T, the matrix fit_reduced factors at the
+ * cost C_s,
+ *   h_ii = 1 / N + |L^-1 (phi_i - s / N)|^2,   f_c(x_i) = (phi_i - s / N) beta_c + eta_c / N,   f_c^(-i)(x_i) = y_ic - (y_ic - f_c(x_i)) / (1 - h_ii)
+ * where f_c^(-i) is the model refitted without point i on the SAME landmarks: an identity, not an approximation.  h does not depend on y, so one leverage vector serves
+ * all right-hand sides.  Pass 1 is the pass of lssvm_mi355_problem_fit_reduced; per cost the host forms M_s (the jitter rule per cost), L_s, V_s = L_s^-1 and beta, rho
+ * exactly as fit_reduced does: betas and rhos of cost s have the bits of fit_reduced on a problem created with that cost.  Pass 2 evaluates the Phi slabs again (the same
+ * kernels, the same bits) and per slab and cost forms the N x m x m product Phic V_s^T on v_mfma_f64_16x16x4_f64 without storing it: only its rows' squared norms, the
+ * fitted values and the leave-one-out values leave the device.  No atomics; the order of every sum depends on the rank only, so h is the same to the bit for any num_rhs,
+ * column c of a call has the bits of the call with that right-hand side alone, and a cost has the bits of the call with that cost alone.
+ * costs: 1 <= num_costs <= 64, each finite and > 0; the cost of the problem's lssvm_params is IGNORED.  Every output is double.  betas_out: num_costs x num_rhs x rank;
+ * rhos_out, press_out (sum_i (y_ic - loo_ic)^2, summed in row order on the host) and loo_errors_out (the number of i with sign(loo_ic) != sign(y_ic), sign(0) = 0):
+ * num_costs x num_rhs; leverage_out: num_costs x N; fitted_out and loo_out: num_costs x num_rhs x N.  leverage_out, fitted_out, loo_out, press_out, loo_errors_out,
+ * landmarks_out and infos may be NULL.  The problem is left as it was and keeps its preconditioner.  Refusals: those of lssvm_mi355_problem_fit_reduced and a bad cost
+ * grid, all LSSVM_ERR_INVALID_ARGUMENT before a device is touched. */
+typedef struct lssvm_reduced_loo_info {
+    double cost;
+    double jitter;        /* nu of this cost */
+    double max_leverage;  /* the largest h_ii */
+    double landmark_ms;   /* device time of Phi, the 1 and y columns and K_mm: both passes, all slabs (the same figure for every cost) */
+    double gram_ms;       /* device time of St, all slabs (the same figure for every cost) */
+    double leverage_ms;   /* device time of this cost's leverage kernel, all slabs */
+    double host_ms;       /* this cost's factorisation, inverse and solves on the host */
+} lssvm_reduced_loo_info;
+int lssvm_mi355_problem_fit_reduced_loo(lssvm_mi355_problem *p, const void *Y /* num_rhs x N, the problem's dtype */, size_t num_rhs, uint64_t rank, const uint64_t *landmarks,
+                                        uint64_t slab_rows, const double *costs, size_t num_costs, double *betas_out, double *rhos_out, double *leverage_out, double *fitted_out,
+                                        double *loo_out, double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out, lssvm_reduced_loo_info *infos /* num_costs */);
+/* one-shot: create the problem on device 0 (as lssvm_mi355_solve_*), fit, destroy it */
+int lssvm_mi355_fit_reduced_loo_f32(const lssvm_params *params, const float *X, size_t num_points, size_t num_features, const float *Y, size_t num_rhs, uint64_t rank,
+                                    const uint64_t *landmarks, uint64_t slab_rows, const double *costs, size_t num_costs, double *betas_out, double *rhos_out, double *leverage_out,
+                                    double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out, lssvm_reduced_loo_info *infos,
+                                    const lssvm_mi355_options *options);
+int lssvm_mi355_fit_reduced_loo_f64(const lssvm_params *params, const double *X, size_t num_points, size_t num_features, const double *Y, size_t num_rhs, uint64_t rank,
+                                    const uint64_t *landmarks, uint64_t slab_rows, const double *costs, size_t num_costs, double *betas_out, double *rhos_out, double *leverage_out,
+                                    double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out, lssvm_reduced_loo_info *infos,
+                                    const lssvm_mi355_options *options);
+
 /* CG, csvm.cpp:89-111: b = y[0..n) - y[n], x = 1, r = b - A x, delta0, d = r */
 int lssvm_mi355_cg_begin(lssvm_mi355_problem *p, const void *y, double eps);
 /* run at most `iterations` further CG iterations (csvm.cpp:125-166); stops early when delta <= eps^2 delta0.

@@ -53,6 +53,19 @@ int lssvm_mi355_set_io_threads(int threads);
  * it, (rank + 1 + num_rhs)^2 doubles row-major with BOTH triangles (the upper one is the host's copy of the lower).  Arguments and refusals as there. */
 int lssvm_mi355_problem_landmark_gram(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, double *gram_out);
 
+/* The operator of the leave-one-out pass alone (lssvm_mi355_problem_fit_reduced_loo) on the caller's operands, apart from any conditioning: for every
+ * point i, with phic_i = phi_i - shift (phi_i: row i of Phi = K(X, X_L) as the problem evaluates it),
+ *   h_out[i] = |V phic_i|^2   (the 1 / N of the leverage left out),     f_out[c * N + i] = phic_i . B_extra[:, c]   (the mean of y left out)
+ * V: rank x rank row major, only its LOWER triangle counts -- whatever stands above the diagonal is never used: column blocks above the diagonal of V^T are not read, the
+ * blocks on it are masked.  B_extra: rank x k row major (NULL with k = 0; then f_out may be NULL).  Arguments and refusals as for lssvm_mi355_problem_landmark_gram. */
+int lssvm_mi355_problem_reduced_leverage(lssvm_mi355_problem *p, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *V, const double *shift,
+                                         const double *B_extra, size_t k, double *h_out, double *f_out);
+
+/* Measurement aid of tests/tools/reduced_loo_timing.py: on ONE slab of this problem (its first min(N, slab_rows) points, `rank` landmarks by the library's rule, an
+ * identity V, k columns of ones) the Gram kernels of the fixed-size fit (gram_ms_out[r]: partial tiles and their sum over rank + 1 + k columns) and the leverage kernel
+ * (leverage_ms_out[r]), device time of repeat r each after one untimed run of both. */
+int lssvm_mi355_problem_time_leverage_kernel(lssvm_mi355_problem *p, uint64_t rank, uint64_t slab_rows, size_t k, int repeats, double *gram_ms_out, double *leverage_ms_out);
+
 /* Measurement aid of tests/tools/reduced_timing.py: G = Bhat^T Bhat of the fp64 problem's preconditioner (its own Bhat buffer, rank + 1 columns) `repeats` times by
  * the preconditioner's scalar kernel (parent_ms_out[r]) and by the fixed-size model's matrix-core kernels (mfma_ms_out[r]: partial tiles and their sum), device time of
  * repeat r each, after one untimed run of both.  *max_diff_out (may be NULL): the largest |difference| of the two results over the lower triangle, relative to the largest

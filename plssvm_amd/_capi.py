@@ -43,6 +43,7 @@ EXPORTED_SYMBOLS = [
     "lssvm_mi355_problem_build_preconditioner", "lssvm_mi355_problem_precond_landmarks", "lssvm_mi355_problem_precond_apply", "lssvm_mi355_problem_solve_pcg",
     "lssvm_mi355_solve_pcg_f32", "lssvm_mi355_solve_pcg_f64",
     "lssvm_mi355_problem_fit_reduced", "lssvm_mi355_fit_reduced_f32", "lssvm_mi355_fit_reduced_f64", "lssvm_mi355_problem_landmark_gram", "lssvm_mi355_problem_time_gram_kernels",
+    "lssvm_mi355_problem_fit_reduced_loo", "lssvm_mi355_fit_reduced_loo_f32", "lssvm_mi355_fit_reduced_loo_f64", "lssvm_mi355_problem_reduced_leverage", "lssvm_mi355_problem_time_leverage_kernel",
     "lssvm_mi355_cg_begin", "lssvm_mi355_cg_step", "lssvm_mi355_cg_finish", "lssvm_mi355_problem_synchronize", "lssvm_mi355_problem_info",
     "lssvm_mi355_measure_bf16_mfma_ceiling", "lssvm_mi355_comm_library_path", "lssvm_mi355_set_io_threads", "lssvm_mi355_set_option", "lssvm_mi355_get_option",
     "lssvm_mi355_libsvm_open", "lssvm_mi355_libsvm_fill_f32", "lssvm_mi355_libsvm_fill_f64", "lssvm_mi355_libsvm_close",
@@ -263,6 +264,38 @@ def reduced_entry(name: str):
             fn.argtypes = [C.c_void_p] + common + [C.POINTER(C.c_double)]
         elif name == "lssvm_mi355_problem_time_gram_kernels":
             fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        else:
+            fn.argtypes = [C.POINTER(LssvmParams), C.c_void_p, C.c_size_t, C.c_size_t] + common + outs + [C.c_void_p]
+        fn.restype = C.c_int
+    return fn
+
+
+class LssvmReducedLooInfo(C.Structure):
+    """``lssvm_reduced_loo_info``: one cost of ``lssvm_mi355_problem_fit_reduced_loo``."""
+    _fields_ = [("cost", C.c_double), ("jitter", C.c_double), ("max_leverage", C.c_double), ("landmark_ms", C.c_double), ("gram_ms", C.c_double), ("leverage_ms", C.c_double),
+                ("host_ms", C.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+REDUCED_LOO_MAX_COSTS = 64
+
+
+def reduced_loo_entry(name: str):
+    """The entry points of the leave-one-out scores of the fixed-size model (``lssvm_mi355_problem_fit_reduced_loo``, ``lssvm_mi355_fit_reduced_loo_f32 / _f64`` and the
+    test aids ``lssvm_mi355_problem_reduced_leverage`` / ``_time_leverage_kernel``) with their argument types.  Bound at the first call."""
+    fn = getattr(lib, name)
+    if fn.argtypes is None:
+        dp, up = C.POINTER(C.c_double), C.POINTER(C.c_uint64)
+        common = [C.c_void_p, C.c_size_t, C.c_uint64, up, C.c_uint64, dp, C.c_size_t]  # Y, num_rhs, rank, landmarks, slab_rows, costs, num_costs
+        outs = [dp, dp, dp, dp, dp, dp, up, up, C.POINTER(LssvmReducedLooInfo)]  # betas, rhos, leverage, fitted, loo, press, loo_errors, landmarks, infos
+        if name == "lssvm_mi355_problem_fit_reduced_loo":
+            fn.argtypes = [C.c_void_p] + common + outs
+        elif name == "lssvm_mi355_problem_reduced_leverage":
+            fn.argtypes = [C.c_void_p, C.c_uint64, up, C.c_uint64, dp, dp, dp, C.c_size_t, dp, dp]
+        elif name == "lssvm_mi355_problem_time_leverage_kernel":
+            fn.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, dp, dp]
         else:
             fn.argtypes = [C.POINTER(LssvmParams), C.c_void_p, C.c_size_t, C.c_size_t] + common + outs + [C.c_void_p]
         fn.restype = C.c_int

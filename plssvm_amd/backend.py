@@ -24,7 +24,7 @@ from ._capi import LssvmCgInfo, LssvmParams, LssvmPredictInfo, LssvmShard, Optio
 from .exceptions import InvalidParameterError
 from .parameter import Parameter
 
-__all__ = ["Options", "Predictor", "solve_system_of_linear_equations", "solve_refined", "solve_cost_path", "solve_pcg", "fit_reduced", "predict_values", "predict_values_multi", "generate_q", "run_device_kernel", "calculate_w", "ResidentProblem",
+__all__ = ["Options", "Predictor", "solve_system_of_linear_equations", "solve_refined", "solve_cost_path", "solve_pcg", "fit_reduced", "fit_reduced_loo", "predict_values", "predict_values_multi", "generate_q", "run_device_kernel", "calculate_w", "ResidentProblem",
            "comm_get_unique_id", "comm_init", "comm_destroy"]
 
 
@@ -288,6 +288,51 @@ def fit_reduced(params: Parameter, A, Y, rank: int, landmarks=None, slab_rows: i
     ps = _params_struct(params, d)
     fn = _capi.reduced_entry(f"lssvm_mi355_fit_reduced_{suffix_of(A.dtype)}")
     return _reduced_call(fn, (C.byref(ps), ptr(A), N, d), Y2, single, rank, lm_ptr, slab_rows, tail=(options_ptr(options),))
+
+
+def _reduced_loo_costs(costs):
+    """The cost grid of the leave-one-out scores, checked as the library checks it."""
+    try:
+        costs = np.ascontiguousarray(costs, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise InvalidParameterError("The costs must be a list of numbers!") from None
+    if costs.ndim != 1 or not 1 <= costs.size <= _capi.REDUCED_LOO_MAX_COSTS:
+        raise InvalidParameterError(f"The leave-one-out scores take between 1 and {_capi.REDUCED_LOO_MAX_COSTS} costs, but got {costs.size if costs.ndim == 1 else costs.shape}!")
+    if not (np.all(np.isfinite(costs)) and np.all(costs > 0.0)):
+        raise InvalidParameterError("Every cost must be finite and greater than 0!")
+    return costs
+
+
+def _reduced_loo_call(fn, head, Y2, single: bool, N: int, rank: int, lm_ptr, slab_rows: int, costs, tail=()):
+    k, S = Y2.shape[0], costs.size
+    betas, rhos = np.zeros((S, k, rank)), np.zeros((S, k))
+    leverage, fitted, loo = np.zeros((S, N)), np.zeros((S, k, N)), np.zeros((S, k, N))
+    press, errors, used = np.zeros((S, k)), np.zeros((S, k), dtype=np.uint64), np.zeros(rank, dtype=np.uint64)
+    infos = (_capi.LssvmReducedLooInfo * S)()
+    dp, up = C.POINTER(C.c_double), C.POINTER(C.c_uint64)
+    check(fn(*head, ptr(Y2), k, rank, lm_ptr, slab_rows, costs.ctypes.data_as(dp), S, betas.ctypes.data_as(dp), rhos.ctypes.data_as(dp), leverage.ctypes.data_as(dp),
+             fitted.ctypes.data_as(dp), loo.ctypes.data_as(dp), press.ctypes.data_as(dp), errors.ctypes.data_as(up), used.ctypes.data_as(up), infos, *tail))
+    report = {"costs": costs.copy(), "leverage": leverage, "fitted": fitted[:, 0] if single else fitted, "loo": loo[:, 0] if single else loo,
+              "press": press[:, 0] if single else press, "loo_errors": errors[:, 0] if single else errors, "max_leverage": np.array([i.max_leverage for i in infos]),
+              "jitter": np.array([i.jitter for i in infos]), "infos": [i.as_dict() for i in infos]}
+    return (betas[:, 0], rhos[:, 0], used, report) if single else (betas, rhos, used, report)
+
+
+def fit_reduced_loo(params: Parameter, A, Y, rank: int, costs, landmarks=None, slab_rows: int = 0, options: Options | None = None):
+    """:func:`fit_reduced` at every cost of ``costs`` with its exact leave-one-out values -- leave-one-out with the landmark set held fixed
+    (``lssvm_mi355_fit_reduced_loo_*``).  The fit is a linear smoother, so the model refitted without point ``i`` predicts
+    ``y_i - (y_i - f(x_i)) / (1 - h_ii)`` at ``x_i``: one more pass over the landmark block per cost gives the leverages ``h`` and these values for ALL ``N`` points, without
+    a validation split and without a refit.  ``params.cost`` is ignored; 1 to 64 costs.  Returns ``(betas[S, k, rank], rhos[S, k], landmarks, report)`` (the ``k`` axis
+    dropped for a single right-hand side ``(N,)``); ``betas[s]`` / ``rhos[s]`` have the bits of :func:`fit_reduced` at ``costs[s]``.  ``report``: ``leverage[S, N]``,
+    ``fitted`` / ``loo`` ``[S, k, N]``, ``press[S, k]`` (sum of squared leave-one-out residuals), ``loo_errors[S, k]`` (points whose leave-one-out value has another sign than
+    ``y``), ``max_leverage[S]``, ``jitter[S]``, ``infos`` (``lssvm_reduced_loo_info`` dicts).  Everything float64.  Device 0; deterministic."""
+    A = _as_matrix(A)
+    N, d = A.shape
+    Y2, single, rank, _, lm_ptr, slab_rows = _reduced_arguments(Y, N, A.dtype, rank, landmarks, slab_rows)
+    costs = _reduced_loo_costs(costs)
+    ps = _params_struct(params, d)
+    fn = _capi.reduced_loo_entry(f"lssvm_mi355_fit_reduced_loo_{suffix_of(A.dtype)}")
+    return _reduced_loo_call(fn, (C.byref(ps), ptr(A), N, d), Y2, single, N, rank, lm_ptr, slab_rows, costs, tail=(options_ptr(options),))
 
 
 def generate_q(params: Parameter, data, options: Options | None = None):
@@ -663,6 +708,41 @@ class ResidentProblem:
         out = np.zeros((cols, cols), dtype=np.float64)
         check(_capi.reduced_entry("lssvm_mi355_problem_landmark_gram")(self._h, ptr(Y2), Y2.shape[0], rank, lm_ptr, slab_rows, out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
+
+    def fit_reduced_loo(self, Y, rank: int, costs, landmarks=None, slab_rows: int = 0):
+        """:func:`fit_reduced_loo` on this resident problem (``lssvm_mi355_problem_fit_reduced_loo``): leave-one-out with the landmark set held fixed, at every cost of
+        ``costs``.  The problem's own cost is ignored; the problem is left as it was and keeps its preconditioner.  Refused where :meth:`fit_reduced` is."""
+        Y2, single, rank, _, lm_ptr, slab_rows = _reduced_arguments(Y, self.num_points, self.dtype, rank, landmarks, slab_rows)
+        costs = _reduced_loo_costs(costs)
+        return _reduced_loo_call(_capi.reduced_loo_entry("lssvm_mi355_problem_fit_reduced_loo"), (self._h,), Y2, single, self.num_points, rank, lm_ptr, slab_rows, costs)
+
+    def reduced_leverage(self, V, shift, B_extra=None, landmarks=None, slab_rows: int = 0):
+        """The operator of :meth:`fit_reduced_loo` alone on the caller's operands (a test aid, ``lssvm_mi355_problem_reduced_leverage``): with ``phic_i = phi_i - shift``,
+        ``h[i] = |V phic_i|^2`` for the LOWER triangle of ``V`` (rank x rank; what stands above the diagonal is never used) and ``f[c, i] = phic_i . B_extra[:, c]``
+        (``B_extra``: rank x k or None).  Returns ``(h[N], f[k, N])``, float64."""
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        if V.ndim != 2 or V.shape[0] != V.shape[1]:
+            raise InvalidParameterError(f"V must be a square matrix, but its shape is {V.shape}!")
+        rank = V.shape[0]
+        _, _, rank, _, lm_ptr, slab_rows = _reduced_arguments(np.zeros(self.num_points, dtype=self.dtype), self.num_points, self.dtype, rank if landmarks is None else None, landmarks, slab_rows)
+        shift = np.ascontiguousarray(shift, dtype=np.float64)
+        extra = np.zeros((rank, 0)) if B_extra is None else np.ascontiguousarray(B_extra, dtype=np.float64)
+        if V.shape[0] != rank or shift.shape != (rank,) or extra.ndim != 2 or extra.shape[0] != rank:
+            raise InvalidParameterError(f"V, shift and B_extra must have {rank} rows, but their shapes are {V.shape}, {shift.shape} and {extra.shape}!")
+        k = extra.shape[1]
+        h, f = np.zeros(self.num_points), np.zeros((k, self.num_points))
+        dp = C.POINTER(C.c_double)
+        check(_capi.reduced_loo_entry("lssvm_mi355_problem_reduced_leverage")(self._h, rank, lm_ptr, slab_rows, V.ctypes.data_as(dp), shift.ctypes.data_as(dp),
+                                                                                 extra.ctypes.data_as(dp) if k else None, k, h.ctypes.data_as(dp), f.ctypes.data_as(dp) if k else None))
+        return h, f
+
+    def time_leverage_kernel(self, rank: int, k: int = 1, slab_rows: int = 0, repeats: int = 10):
+        """A measurement aid (``lssvm_mi355_problem_time_leverage_kernel``): on one slab of this problem, the Gram kernels of :meth:`fit_reduced` and the leverage kernel of
+        :meth:`fit_reduced_loo`: ``(gram_ms[repeats], leverage_ms[repeats])``."""
+        gram, lev = np.zeros(int(repeats)), np.zeros(int(repeats))
+        dp = C.POINTER(C.c_double)
+        check(_capi.reduced_loo_entry("lssvm_mi355_problem_time_leverage_kernel")(self._h, int(rank), int(slab_rows), int(k), int(repeats), gram.ctypes.data_as(dp), lev.ctypes.data_as(dp)))
+        return gram, lev
 
     def time_gram_kernels(self, repeats: int = 10):
         """A measurement aid (``lssvm_mi355_problem_time_gram_kernels``): ``Bhat^T Bhat`` of this fp64 problem's preconditioner by the preconditioner's own kernel and by the

@@ -225,6 +225,23 @@ void fit_reduced_one_shot(const lssvm_params *params, const T *X, size_t N, size
     prob.fit_reduced(Y, num_rhs, rank, landmarks, slab_rows, betas_out, rhos_out, landmarks_out, info);
 }
 
+/* lssvm_mi355_fit_reduced_loo_*: likewise */
+template <typename T>
+void fit_reduced_loo_one_shot(const lssvm_params *params, const T *X, size_t N, size_t d, const T *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows,
+                              const double *costs, size_t num_costs, double *betas_out, double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out, double *press_out,
+                              uint64_t *loo_errors_out, uint64_t *landmarks_out, lssvm_reduced_loo_info *infos, const lssvm_mi355_options *options) {
+    lssvm::check_params(params);
+    LSSVM_REQUIRE(X != nullptr && N > 0, "The data must not be empty!");         // csvm.cpp:73
+    LSSVM_REQUIRE(d > 0, "The data points must contain at least one feature!");  // csvm.cpp:74
+    lssvm::check_reduced_arguments(Y, num_rhs, rank, slab_rows, N);
+    lssvm::check_reduced_loo_costs(costs, num_costs);
+    LSSVM_REQUIRE(betas_out != nullptr && rhos_out != nullptr, "betas_out / rhos_out must not be NULL");
+    if (landmarks != nullptr) (void) lssvm::resolve_landmarks(landmarks, static_cast<size_t>(rank), N);
+    static const int device0 = 0;
+    lssvm::Solver<T> prob(options_of(options), *params, X, LSSVM_MEM_HOST, N, d, lssvm::resolve_devices(&device0, 1, N), nullptr);
+    prob.fit_reduced_loo(Y, num_rhs, rank, landmarks, slab_rows, costs, num_costs, betas_out, rhos_out, leverage_out, fitted_out, loo_out, press_out, loo_errors_out, landmarks_out, infos);
+}
+
 template <typename T>
 void generate_q_one_shot(const lssvm_params *params, const T *X, size_t N, size_t d, T *q_out, const lssvm_mi355_options *options) {
     lssvm::check_params(params);
@@ -689,6 +706,49 @@ int lssvm_mi355_fit_reduced_f32(const lssvm_params *params, const float *X, size
 int lssvm_mi355_fit_reduced_f64(const lssvm_params *params, const double *X, size_t num_points, size_t num_features, const double *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks,
                                 uint64_t slab_rows, double *betas_out, double *rhos_out, uint64_t *landmarks_out, lssvm_reduced_info *info, const lssvm_mi355_options *options) {
     return guarded([&] { fit_reduced_one_shot<double>(params, X, num_points, num_features, Y, num_rhs, rank, landmarks, slab_rows, betas_out, rhos_out, landmarks_out, info, options); });
+}
+static_assert(sizeof(lssvm_reduced_loo_info) == 56, "lssvm_reduced_loo_info changed: plssvm_amd/_capi.py (LssvmReducedLooInfo) changes with it");
+int lssvm_mi355_problem_fit_reduced_loo(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *costs, size_t num_costs,
+                                        double *betas_out, double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out,
+                                        uint64_t *landmarks_out, lssvm_reduced_loo_info *infos) {
+    return guarded([&] {
+        LSSVM_REQUIRE(p != nullptr, "problem handle must not be NULL");
+        lssvm::check_reduced_arguments(Y, num_rhs, rank, slab_rows, 0);  // (before any device work; N and the landmarks: the solver, before it touches the device)
+        lssvm::check_reduced_loo_costs(costs, num_costs);
+        LSSVM_REQUIRE(betas_out != nullptr && rhos_out != nullptr, "betas_out / rhos_out must not be NULL");
+        impl_of(p)->fit_reduced_loo(Y, num_rhs, rank, landmarks, slab_rows, costs, num_costs, betas_out, rhos_out, leverage_out, fitted_out, loo_out, press_out, loo_errors_out, landmarks_out, infos);
+    });
+}
+int lssvm_mi355_fit_reduced_loo_f32(const lssvm_params *params, const float *X, size_t num_points, size_t num_features, const float *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks,
+                                    uint64_t slab_rows, const double *costs, size_t num_costs, double *betas_out, double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out,
+                                    double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out, lssvm_reduced_loo_info *infos, const lssvm_mi355_options *options) {
+    return guarded([&] {
+        fit_reduced_loo_one_shot<float>(params, X, num_points, num_features, Y, num_rhs, rank, landmarks, slab_rows, costs, num_costs, betas_out, rhos_out, leverage_out, fitted_out, loo_out,
+                                        press_out, loo_errors_out, landmarks_out, infos, options);
+    });
+}
+int lssvm_mi355_fit_reduced_loo_f64(const lssvm_params *params, const double *X, size_t num_points, size_t num_features, const double *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks,
+                                    uint64_t slab_rows, const double *costs, size_t num_costs, double *betas_out, double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out,
+                                    double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out, lssvm_reduced_loo_info *infos, const lssvm_mi355_options *options) {
+    return guarded([&] {
+        fit_reduced_loo_one_shot<double>(params, X, num_points, num_features, Y, num_rhs, rank, landmarks, slab_rows, costs, num_costs, betas_out, rhos_out, leverage_out, fitted_out, loo_out,
+                                         press_out, loo_errors_out, landmarks_out, infos, options);
+    });
+}
+int lssvm_mi355_problem_reduced_leverage(lssvm_mi355_problem *p, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *V, const double *shift, const double *B_extra, size_t k,
+                                         double *h_out, double *f_out) {
+    return guarded([&] {
+        LSSVM_REQUIRE(p != nullptr, "problem handle must not be NULL");
+        LSSVM_REQUIRE(V != nullptr && shift != nullptr && h_out != nullptr, "V / shift / h_out must not be NULL");
+        lssvm::check_reduced_arguments(V, 1, rank, slab_rows, 0);
+        impl_of(p)->reduced_leverage(rank, landmarks, slab_rows, V, shift, B_extra, k, h_out, f_out);
+    });
+}
+int lssvm_mi355_problem_time_leverage_kernel(lssvm_mi355_problem *p, uint64_t rank, uint64_t slab_rows, size_t k, int repeats, double *gram_ms_out, double *leverage_ms_out) {
+    return guarded([&] {
+        LSSVM_REQUIRE(p != nullptr, "problem handle must not be NULL");
+        impl_of(p)->time_leverage_kernel(rank, slab_rows, k, repeats, gram_ms_out, leverage_ms_out);
+    });
 }
 int lssvm_mi355_cg_begin(lssvm_mi355_problem *p, const void *y, double eps) {
     return guarded([&] { impl_of(p)->cg_begin(y, eps); });

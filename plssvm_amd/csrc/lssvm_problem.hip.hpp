@@ -608,6 +608,13 @@ struct ProblemBase {
                              uint64_t *landmarks_out, lssvm_reduced_info *info) = 0;  // lssvm_mi355_problem_fit_reduced
     virtual void landmark_gram(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, double *gram_out) = 0;  // lssvm_mi355_problem_landmark_gram
     virtual void time_gram_kernels(int repeats, double *parent_ms_out, double *mfma_ms_out, double *max_diff_out) = 0;  // lssvm_mi355_problem_time_gram_kernels
+    /* exact leave-one-out scores of the fixed-size model over a cost grid (lssvm_reduced.hip) */
+    virtual void fit_reduced_loo(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *costs, size_t num_costs, double *betas_out,
+                                 double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out,
+                                 lssvm_reduced_loo_info *infos) = 0;  // lssvm_mi355_problem_fit_reduced_loo
+    virtual void reduced_leverage(uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *V, const double *shift, const double *B_extra, size_t k, double *h_out,
+                                  double *f_out) = 0;  // lssvm_mi355_problem_reduced_leverage
+    virtual void time_leverage_kernel(uint64_t rank, uint64_t slab_rows, size_t k, int repeats, double *gram_ms_out, double *leverage_ms_out) = 0;  // lssvm_mi355_problem_time_leverage_kernel
     virtual void cg_begin(const void *y, double eps) = 0;
     virtual void cg_step(uint64_t iterations, int *done_out) = 0;
     virtual void cg_finish(void *alpha_out, double *rho_out, lssvm_cg_info *info) = 0;
@@ -665,6 +672,8 @@ struct LocalComms {
 };
 std::shared_ptr<LocalComms> local_comms_for(const std::vector<int> &devices);  // lssvm_exchange.hip
 
+struct LeverageArgs;  // what a leave-one-out pass of the fixed-size model works on (lssvm_reduced.hip)
+
 /* Solver<T>: the CG driver (csvm.cpp:71-183 / gpu_csvm.hpp:477-654) over the shards that live in THIS process:
  *   - one shard, world 1: single GPU;
  *   - one shard, rank r of a world of processes: one process per GPU (torchrun), exchange = the process communicator (RCCL);
@@ -698,6 +707,13 @@ class Solver final : public ProblemBase {
                      lssvm_reduced_info *info) override;
     void landmark_gram(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, double *gram_out) override;
     void time_gram_kernels(int repeats, double *parent_ms_out, double *mfma_ms_out, double *max_diff_out) override;
+    /* leave-one-out with the landmark set held fixed, every cost of a grid: pass 1 is reduced_gram, pass 2 the leverage kernel per slab and cost */
+    void fit_reduced_loo(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *costs, size_t num_costs, double *betas_out,
+                         double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out,
+                         lssvm_reduced_loo_info *infos) override;
+    void reduced_leverage(uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *V, const double *shift, const double *B_extra, size_t k, double *h_out,
+                          double *f_out) override;
+    void time_leverage_kernel(uint64_t rank, uint64_t slab_rows, size_t k, int repeats, double *gram_ms_out, double *leverage_ms_out) override;
     void cg_begin(const void *y, double eps) override;
     /* cg_begin for the inner solve of the mixed-precision refinement: A e = r / max|r| from e = 0 -- b, the first residual and delta0 = b^T b come from ONE O(n) kernel
      * over the outer fp64 residual `r_dev` (device 0, complete when the call is made; `absmax_part_dev`: k_absmax's partials of it), no Gram pass.  cg_step follows as
@@ -739,6 +755,8 @@ class Solver final : public ProblemBase {
     /* what fit_reduced and landmark_gram share: the checks, the slabs, St (cols x cols, both triangles) and K_mm (rank x rank) on the host */
     void reduced_gram(const char *what, const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, std::vector<uint64_t> &lm_out,
                       std::vector<double> &gram_out, std::vector<double> &kmm_out, lssvm_reduced_info &info);
+    /* pass 2 of fit_reduced_loo, and all of reduced_leverage: the Phi slabs again, the leverage kernel per slab and operand (lssvm_reduced.hip) */
+    void leverage_pass(const std::vector<uint64_t> &lm, uint64_t slab_rows, LeverageArgs &args);
     T *vec_of(Problem<T> &p, Vec which) const { return which == Vec::d ? p.own_.d.p : (which == Vec::x ? p.own_.x.p : p.tmp_.p); }
 
     Options opt_{};
@@ -782,6 +800,9 @@ std::vector<uint64_t> resolve_landmarks(const uint64_t *landmarks, size_t rank, 
 constexpr int REDUCED_MAX_RANK = 1024;
 constexpr uint64_t REDUCED_DEFAULT_SLAB_ROWS = 65536;
 void check_reduced_arguments(const void *Y, size_t num_rhs, uint64_t rank, uint64_t slab_rows, size_t num_points);
+/* the cost grid of lssvm_mi355_problem_fit_reduced_loo / lssvm_mi355_fit_reduced_loo_*: 1 ... REDUCED_LOO_MAX_COSTS costs, each finite and positive */
+constexpr size_t REDUCED_LOO_MAX_COSTS = 64;
+void check_reduced_loo_costs(const double *costs, size_t num_costs);
 
 /* the arguments of lssvm_mi355_problem_solve_cost_path / lssvm_mi355_solve_cost_path_* that need no device: checked before one is touched (lssvm_path.hip) */
 constexpr size_t PATH_MAX_COSTS = 64;

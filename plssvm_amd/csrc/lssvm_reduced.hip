@@ -11,6 +11,12 @@
  * 64 x 64 each as sixteen accumulators of v_mfma_f64_16x16x4_f64.  k_reduced_sum adds the partial tiles to the running St in ascending row order.  RG_RANGE is a
  * constant: the order in which an entry is summed depends on N and slab_rows only, never on the number of columns -- so row c of a call with k right-hand sides has the
  * bits of the call with that right-hand side alone.  No atomics, no scratch.  Compiled for gfx950 only.
+ *
+ * Exact leave-one-out scores over a cost grid (lssvm_mi355_problem_fit_reduced_loo, _reduced_leverage, lssvm_mi355_fit_reduced_loo_*), leave-one-out
+ * with the landmark set held fixed: the fit is a linear smoother, so with M + nu I = L L^T, V = L^-1 and Phic = Phi - 1 s^T / N the leverage is h_ii = 1 / N + |V phic_i|^2
+ * and the model refitted without point i predicts y_i - (y_i - f(x_i)) / (1 - h_ii) at x_i.  Pass 1 is reduced_gram; per cost the host factors (factor_reduced,
+ * solve_reduced: the code of fit_reduced) and inverts L; pass 2 evaluates the slabs again and k_reduced_leverage forms Phic [V^T | beta] on the matrix cores per slab and
+ * cost, keeping only the rows' squared norms, the fitted and the leave-one-out values.
  */
 #include "lssvm_landmark.hip.hpp"
 
@@ -194,7 +200,257 @@ float elapsed_ms(const Event &a, const Event &b) {
     return ms;
 }
 
+/* ---- the host's part of a fit, in double, shared by fit_reduced and fit_reduced_loo: M = S - s s^T / N + sigma K_mm (lower triangle), (M + nu I) = L L^T,
+ * (M + nu I) beta_c = t_c - s eta_c / N, b_c = (eta_c - s^T beta_c) / N ---- */
+double factor_reduced(const std::vector<double> &St, const std::vector<double> &Kmm, int m, int cols, double Nd, double sigma, std::vector<double> &L) {
+    const double *s = &St[static_cast<size_t>(m) * cols];
+    std::vector<double> M(static_cast<size_t>(m) * m, 0.0);
+    double trace = 0.0;
+    for (int j = 0; j < m; ++j) {
+        for (int l = 0; l <= j; ++l) M[static_cast<size_t>(j) * m + l] = St[static_cast<size_t>(j) * cols + l] - s[j] * s[l] / Nd + sigma * Kmm[static_cast<size_t>(j) * m + l];
+        trace += M[static_cast<size_t>(j) * m + j];
+    }
+    LSSVM_REQUIRE(std::isfinite(trace) && trace > 0.0, "the matrix of the reduced model has no positive finite trace");
+    double nu = DBL_EPSILON * trace;
+    bool factored = false;
+    for (int attempt = 0; attempt < 7 && !factored; ++attempt, nu *= factored ? 1.0 : 10.0) {
+        L = M;
+        for (int j = 0; j < m; ++j) L[static_cast<size_t>(j) * m + j] += nu;
+        factored = cholesky_lower(L, m);
+    }
+    if (!factored) throw Error(LSSVM_ERR_INTERNAL, "the matrix of the reduced model could not be factored (jitter up to " + std::to_string(nu / 10.0) + ")");
+    return nu;
+}
+
+void solve_reduced(const std::vector<double> &St, const std::vector<double> &L, int m, int k, int cols, double Nd, double *betas_out, double *rhos_out) {
+    const double *s = &St[static_cast<size_t>(m) * cols];
+    std::vector<double> z(static_cast<size_t>(m));
+    for (int c = 0; c < k; ++c) {
+        const double *t = &St[static_cast<size_t>(m + 1 + c) * cols];
+        const double eta = t[m];
+        for (int j = 0; j < m; ++j) {  // L z = t_c - s eta_c / N
+            double v = t[j] - s[j] * eta / Nd;
+            for (int l = 0; l < j; ++l) v -= L[static_cast<size_t>(j) * m + l] * z[l];
+            z[j] = v / L[static_cast<size_t>(j) * m + j];
+        }
+        double *beta = betas_out + static_cast<size_t>(c) * m;
+        for (int j = m - 1; j >= 0; --j) {  // L^T beta = z
+            double v = z[j];
+            for (int l = j + 1; l < m; ++l) v -= L[static_cast<size_t>(l) * m + j] * beta[l];
+            beta[j] = v / L[static_cast<size_t>(j) * m + j];
+        }
+        double sb = 0.0;
+        for (int j = 0; j < m; ++j) sb += s[j] * beta[j];
+        rhos_out[c] = -((eta - sb) / Nd);
+    }
+}
+
+/* row n of `out` (ldb doubles apart, zeros beyond the diagonal) = row n of V = L^-1 by forward substitution, row by row: V[n][:] = (e_n - sum_{l < n} L[n][l] V[l][:]) / L[n][n],
+ * the l ascending for every entry */
+void invert_lower(const std::vector<double> &L, int m, double *out, size_t ldb) {
+    for (int n = 0; n < m; ++n) {
+        double *vn = out + static_cast<size_t>(n) * ldb;
+        std::fill(vn, vn + ldb, 0.0);
+        vn[n] = 1.0;
+        for (int l = 0; l < n; ++l) {
+            const double f = L[static_cast<size_t>(n) * m + l];
+            const double *vl = out + static_cast<size_t>(l) * ldb;
+            for (int j = 0; j <= l; ++j) vn[j] -= f * vl[j];
+        }
+        const double d = L[static_cast<size_t>(n) * m + n];
+        for (int j = 0; j <= n; ++j) vn[j] /= d;
+    }
+}
+
+/* ---- the leave-one-out pass ---- */
+constexpr int LV_LSA = RG_TW + 16;  // doubles between two columns of Phi in LDS: the four k-rows of an MFMA's A fragments start 32 banks apart
+
+/* One workgroup: 128 rows of the column-major `slab` (as k_reduced_gram takes it: ld doubles between columns, rows padded to 256 with zeros) times ALL columns of the operand
+ * Bt -- row n of Bt (ldb doubles apart, ldb >= m rounded up to 16) is column n of the m x (m + k) matrix B of the header: row n of V = L^-1 for n < m, beta_{n-m} from m on.
+ * T = (Phi - 1 shift^T) B is accumulated in 128 x 128 tiles (four waves of 64 x 64, sixteen accumulators of v_mfma_f64_16x16x4_f64 each, as k_reduced_gram) over the
+ * column blocks of B in ascending order and never stored: the squares of the columns below m are added to the row's running sum, the columns from m on are the fitted
+ * values.  Phi goes through LDS with `shift` SUBTRACTED ON THE WAY (centring after the product would cancel for nearly constant kernels), a step is 16 columns of Phi;
+ * Bt through LDS as k_reduced_gram's operands.  A column block wholly inside V^T contracts over j < 128 (bk + 1) only (V is lower triangular: the blocks above the diagonal
+ * are never read), any other over j < m rounded up to 16; an entry V[n][j] with j > n is replaced by 0 as it is staged, whatever the buffer holds.  Columns of Phi from m
+ * on and rows of Bt from m + k on count as zeros and are never read.
+ * A row's sum of squares: per column block a lane's four column tiles in ascending order, then the sixteen lanes that share the row (xor 1, 2, 4, 8), the blocks one
+ * behind the other in LDS (the sums are not held in registers across a block), at the end the two column waves -- an order that depends on m only. A row's values depend on that row, Bt, shift and ybar only.  No atomics, no scratch.
+ * h_out[i] = inv_n + sum; f_out[c ldo + i] = T[i][m + c] + ybar[c] (ybar NULL: 0); loo_out[c ldo + i] = y - (y - f) / (1 - h) with y = ycols[c ld + i] (loo_out NULL:
+ * not formed).  Rows from `rows` on write nothing. */
+__global__ __launch_bounds__(256, 2) void k_reduced_leverage(const double *__restrict__ slab, size_t ld, int rows, int m, int k, const double *__restrict__ Bt, int ldb,
+                                                             const double *__restrict__ shift, const double *__restrict__ ybar, double inv_n, const double *__restrict__ ycols,
+                                                             double *__restrict__ h_out, double *f_out, double *__restrict__ loo_out, size_t ldo) {
+    __shared__ __attribute__((aligned(16))) double As[RG_KC * LV_LSA];
+    __shared__ __attribute__((aligned(16))) double Bs[RG_TW * RG_LS];
+    __shared__ double hs[3 * RG_TW];  // the rows' sums of squares of the two column waves, then h
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int wr = wave >> 1, wc = wave & 1;
+    const int r = lane & 15, qd = lane >> 4;
+    const int row0 = blockIdx.x * RG_TW;
+    const int nblocks = (m + k + RG_TW - 1) / RG_TW;
+    const int m16 = (m + RG_KC - 1) / RG_KC * RG_KC;
+
+    // staging of Phi: thread -> (column akk of the step, rows 2 aseg + 32 p, 2 aseg + 32 p + 1 of the workgroup's 128)
+    const int akk = tid >> 4, aseg = tid & 15;
+    const double *Ag = slab + static_cast<size_t>(akk) * ld + row0 + 2 * aseg;
+    const int a_lds = akk * LV_LSA + 2 * aseg;
+    // staging of Bt: thread -> (row srow + 32 p of the column block, columns 2 sseg, 2 sseg + 1 of the step), as k_reduced_gram
+    const int srow = tid >> 3, sseg = tid & 7;
+    const int b_lds = srow * RG_LS + 2 * sseg;
+    const f64x2 zero2 = { 0.0, 0.0 };
+    f64x2 sa[4], sb[4];
+
+    // lane 16 qd of a wave owns the sums of the wave's rows qd + 4 i + 16 mt: nobody else touches them before the barrier behind the last block
+    double *hrow = hs + wc * RG_TW + wr * 64 + qd;
+    if (r == 0) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) hrow[4 * e] = 0.0;
+    }
+
+    const double *Ab = As + qd * LV_LSA + wr * 64 + r;
+    const double *Bb = Bs + (wc * 64 + r) * RG_LS + qd;
+
+    for (int bk = 0; bk < nblocks; ++bk) {
+        const int nsteps = ((bk + 1) * RG_TW <= m ? (bk + 1) * RG_TW : m16) / RG_KC;
+        const int n0 = bk * RG_TW + srow;  // this thread's rows of Bt: n0 + 32 p
+        auto stage_load = [&](int s) {
+            const int j = s * RG_KC + akk;
+            const bool a_in = j < m;
+            const double sh = a_in ? shift[j] : 0.0;
+            const double *a = Ag + static_cast<size_t>(s) * RG_KC * ld;
+            const int jb = s * RG_KC + 2 * sseg;
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                f64x2 v = a_in ? *reinterpret_cast<const f64x2 *>(a + 32 * p) : zero2;
+                if (a_in) {
+                    v[0] -= sh;
+                    v[1] -= sh;
+                }
+                sa[p] = v;
+                const int n = n0 + 32 * p;
+                const int last = n < m ? n : m16;  // the last column of Bt's row that counts: the diagonal for a row of V, all of them for a beta
+                f64x2 w = n < m + k ? *reinterpret_cast<const f64x2 *>(Bt + static_cast<size_t>(n) * ldb + jb) : zero2;
+                if (jb > last) w[0] = 0.0;
+                if (jb + 1 > last) w[1] = 0.0;
+                sb[p] = w;
+            }
+        };
+        auto stage_store = [&]() {
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                *reinterpret_cast<f64x2 *>(As + a_lds + 32 * p) = sa[p];
+                *reinterpret_cast<f64x2 *>(Bs + b_lds + p * 32 * RG_LS) = sb[p];
+            }
+        };
+
+        f64x4 acc[4][4];
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) {
+                acc[mt][nt] = f64x4{ 0.0, 0.0, 0.0, 0.0 };
+                // the start values live in the accumulators' OWN registers (C == D for every MFMA of a chain), as in k_reduced_gram
+                asm volatile("" : "+v"(acc[mt][nt]));
+            }
+
+        stage_load(0);  // (the barrier that ended the block before lets every wave write: all of them have read its last step)
+        stage_store();
+        __syncthreads();
+        for (int s = 0; s < nsteps; ++s) {
+            const bool has_next = s + 1 < nsteps;
+            if (has_next) stage_load(s + 1);
+#pragma unroll
+            for (int ks = 0; ks < RG_KC / 4; ++ks) {
+                double av[4], bv[4];
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    av[t] = Ab[ks * 4 * LV_LSA + t * 16];
+                    bv[t] = Bb[t * 16 * RG_LS + ks * 4];
+                }
+#pragma unroll
+                for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                    for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[mt], bv[nt], acc[mt][nt], 0, 0, 0);
+            }
+            __syncthreads();  // (every wave has read this step)
+            if (has_next) {
+                stage_store();
+                __syncthreads();
+            }
+        }
+
+        // a lane holds rows qd + 4 i of its four row tiles and column r of its four column tiles
+        const int nw = bk * RG_TW + wc * 64 + r;  // its columns: nw + 16 nt
+        if (bk * RG_TW < m) {
+            // the squares of the columns of V^T: the lane's four columns in ascending order, the sixteen lanes of a row (xor 1, 2, 4, 8), then behind the blocks before
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    double v = 0.0;
+#pragma unroll
+                    for (int nt = 0; nt < 4; ++nt) v += nw + 16 * nt < m ? acc[mt][nt][i] * acc[mt][nt][i] : 0.0;
+                    v += __shfl_xor(v, 1);
+                    v += __shfl_xor(v, 2);
+                    v += __shfl_xor(v, 4);
+                    v += __shfl_xor(v, 8);
+                    if (r == 0) hrow[4 * i + 16 * mt] += v;
+                }
+        }
+        if ((bk + 1) * RG_TW > m) {
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) {
+                const int c = nw + 16 * nt - m;
+                if (c >= 0 && c < k) {
+                    const double yb = ybar != nullptr ? ybar[c] : 0.0;
+#pragma unroll
+                    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            const int row = row0 + wr * 64 + mt * 16 + qd + 4 * i;
+                            if (row < rows) f_out[static_cast<size_t>(c) * ldo + row] = acc[mt][nt][i] + yb;
+                        }
+                }
+            }
+        }
+    }
+
+    __syncthreads();  // (and this workgroup's f_out is visible to all of it)
+    const int lrow = tid & (RG_TW - 1);
+    if (tid < RG_TW) {
+        const double h = inv_n + (hs[tid] + hs[RG_TW + tid]);
+        hs[2 * RG_TW + tid] = h;
+        if (row0 + tid < rows) h_out[row0 + tid] = h;
+    }
+    __syncthreads();
+    if (loo_out != nullptr && row0 + lrow < rows) {
+        const double h = hs[2 * RG_TW + lrow];
+        for (int c = tid >> 7; c < k; c += 2) {
+            const double y = ycols[static_cast<size_t>(c) * ld + row0 + lrow];
+            const double f = f_out[static_cast<size_t>(c) * ldo + row0 + lrow];
+            loo_out[static_cast<size_t>(c) * ldo + row0 + lrow] = y - (y - f) / (1.0 - h);
+        }
+    }
+}
+
 }  // namespace
+
+/* what a leave-one-out pass works on: `num_ops` operands on the device (Bt of k_reduced_leverage, op_stride doubles apart; ybar: num_ops x k or NULL), and where its results go */
+struct LeverageArgs {
+    int m = 0, k = 0, ldb = 0;
+    size_t num_ops = 0, op_stride = 0;
+    const double *Bt_dev = nullptr, *shift_dev = nullptr, *ybar_dev = nullptr;
+    double inv_n = 0.0;
+    const void *Y = nullptr;                                             // the host's right-hand sides (k x N, the problem's type), or NULL: no leave-one-out values
+    double *h_out = nullptr, *f_out = nullptr, *loo_out = nullptr;       // num_ops x N, num_ops x k x N, num_ops x k x N; each may be NULL
+    double *press = nullptr;                                             // num_ops x k, or NULL
+    uint64_t *errors = nullptr;                                          // num_ops x k, or NULL
+    std::vector<double> max_leverage, leverage_ms;                       // per operand
+    double landmark_ms = 0.0;
+    uint64_t slabs = 0;
+};
 
 void check_reduced_arguments(const void *Y, size_t num_rhs, uint64_t rank, uint64_t slab_rows, size_t num_points) {
     LSSVM_REQUIRE(Y != nullptr, "The right hand side vector must not be empty!");
@@ -300,52 +556,306 @@ void Solver<T>::fit_reduced(const void *Y, size_t num_rhs, uint64_t rank, const 
     lssvm_reduced_info info{};
     reduced_gram("fit_reduced", Y, num_rhs, rank, landmarks, slab_rows, lm, St, Kmm, info);
 
-    // ---- the host's part, in double: M = S - s s^T / N + sigma K_mm (lower triangle), (M + nu I) beta_c = t_c - s eta_c / N, b_c = (eta_c - s^T beta_c) / N ----
+    // ---- the host's part, in double (factor_reduced, solve_reduced: shared with fit_reduced_loo) ----
     const double t_host = now_ms();
     const int m = static_cast<int>(rank), k = static_cast<int>(num_rhs), cols = m + 1 + k;
     const double Nd = static_cast<double>(shards_[0]->N_), sigma = 1.0 / shards_[0]->params_.cost;  // (in double, whatever the real type: the host's part is the formulation's)
-    const double *s = &St[static_cast<size_t>(m) * cols];
-    std::vector<double> M(static_cast<size_t>(m) * m, 0.0);
-    double trace = 0.0;
-    for (int j = 0; j < m; ++j) {
-        for (int l = 0; l <= j; ++l) M[static_cast<size_t>(j) * m + l] = St[static_cast<size_t>(j) * cols + l] - s[j] * s[l] / Nd + sigma * Kmm[static_cast<size_t>(j) * m + l];
-        trace += M[static_cast<size_t>(j) * m + j];
-    }
-    LSSVM_REQUIRE(std::isfinite(trace) && trace > 0.0, "the matrix of the reduced model has no positive finite trace");
-    double nu = DBL_EPSILON * trace;
     std::vector<double> L;
-    bool factored = false;
-    for (int attempt = 0; attempt < 7 && !factored; ++attempt, nu *= factored ? 1.0 : 10.0) {
-        L = M;
-        for (int j = 0; j < m; ++j) L[static_cast<size_t>(j) * m + j] += nu;
-        factored = cholesky_lower(L, m);
-    }
-    if (!factored) throw Error(LSSVM_ERR_INTERNAL, "the matrix of the reduced model could not be factored (jitter up to " + std::to_string(nu / 10.0) + ")");
-    std::vector<double> z(static_cast<size_t>(m));
-    for (int c = 0; c < k; ++c) {
-        const double *t = &St[static_cast<size_t>(m + 1 + c) * cols];
-        const double eta = t[m];
-        for (int j = 0; j < m; ++j) {  // L z = t_c - s eta_c / N
-            double v = t[j] - s[j] * eta / Nd;
-            for (int l = 0; l < j; ++l) v -= L[static_cast<size_t>(j) * m + l] * z[l];
-            z[j] = v / L[static_cast<size_t>(j) * m + j];
-        }
-        double *beta = betas_out + static_cast<size_t>(c) * m;
-        for (int j = m - 1; j >= 0; --j) {  // L^T beta = z
-            double v = z[j];
-            for (int l = j + 1; l < m; ++l) v -= L[static_cast<size_t>(l) * m + j] * beta[l];
-            beta[j] = v / L[static_cast<size_t>(j) * m + j];
-        }
-        double sb = 0.0;
-        for (int j = 0; j < m; ++j) sb += s[j] * beta[j];
-        rhos_out[c] = -((eta - sb) / Nd);
-    }
+    const double nu = factor_reduced(St, Kmm, m, cols, Nd, sigma, L);
+    solve_reduced(St, L, m, k, cols, Nd, betas_out, rhos_out);
     if (landmarks_out != nullptr) std::copy(lm.begin(), lm.end(), landmarks_out);
     if (info_out != nullptr) {
         info.jitter = nu;
         info.host_ms = now_ms() - t_host;
         info.total_ms = now_ms() - t0;
         *info_out = info;
+    }
+}
+
+void check_reduced_loo_costs(const double *costs, size_t num_costs) {
+    LSSVM_REQUIRE(costs != nullptr, "costs must not be NULL");
+    LSSVM_REQUIRE(num_costs >= 1 && num_costs <= REDUCED_LOO_MAX_COSTS,
+                  "The leave-one-out scores take between 1 and " + std::to_string(REDUCED_LOO_MAX_COSTS) + " costs, but got " + std::to_string(num_costs) + "!");
+    for (size_t s = 0; s < num_costs; ++s)
+        LSSVM_REQUIRE(std::isfinite(costs[s]) && costs[s] > 0.0, "Every cost must be finite and greater than 0, but cost " + std::to_string(s) + " is " + std::to_string(costs[s]) + "!");
+}
+
+/* The Phi slabs once more (the kernels and arguments of reduced_gram: the same bits) and, per slab, k_reduced_leverage once per operand; h, f and loo of the slab go to the
+ * caller's arrays, the sums over the points are formed here in row order.  The caller has made the checks that need no device. */
+template <typename T>
+void Solver<T>::leverage_pass(const std::vector<uint64_t> &lm, uint64_t slab_rows, LeverageArgs &a) {
+    Problem<T> &p = *shards_[0];
+    const size_t N = p.N_;
+    const int m = a.m, k = a.k;
+    const bool with_y = a.Y != nullptr;
+    const int cols = with_y ? m + 1 + k : m;
+    hipStream_t st = p.stream();
+    const size_t N256 = static_cast<size_t>(round_up(static_cast<long>(N), 256));
+    const size_t ld = std::min<size_t>(slab_rows == 0 ? REDUCED_DEFAULT_SLAB_ROWS : slab_rows, N256);
+    const int slabs = static_cast<int>((N + ld - 1) / ld);
+
+    std::vector<int> lm_host(lm.begin(), lm.end());
+    DevBuf<int> lm_dev;
+    DevBuf<T> Y_dev;
+    DevBuf<double> slab, h_dev, f_dev, loo_dev;
+    lm_dev.alloc_zero(static_cast<size_t>(m), st);
+    LSSVM_HIP_CHECK(hipMemcpyAsync(lm_dev.p, lm_host.data(), static_cast<size_t>(m) * sizeof(int), hipMemcpyHostToDevice, st));
+    if (with_y) {
+        Y_dev.alloc_zero(static_cast<size_t>(k) * N, st);
+        LSSVM_HIP_CHECK(hipMemcpyAsync(Y_dev.p, a.Y, static_cast<size_t>(k) * N * sizeof(T), hipMemcpyHostToDevice, st));
+        loo_dev.alloc_zero(static_cast<size_t>(k) * ld, st);
+    }
+    slab.alloc_zero(static_cast<size_t>(cols) * ld, st);
+    h_dev.alloc_zero(ld, st);
+    f_dev.alloc_zero(static_cast<size_t>(std::max(k, 1)) * ld, st);
+    std::vector<double> h_host(ld), f_host(static_cast<size_t>(k) * ld), loo_host(with_y ? static_cast<size_t>(k) * ld : 0);
+
+    const lssvm_params &prm = p.params_;
+    const double scale2 = p.x_scale_ * p.x_scale_;
+    const double gamma = prm.kernel_type == LSSVM_KERNEL_LINEAR ? 1.0 / scale2 : static_cast<double>(static_cast<T>(prm.gamma)) / scale2;
+    Event ev[2];
+    for (Event &e : ev) e.create(true);
+    a.max_leverage.assign(a.num_ops, 0.0);
+    a.leverage_ms.assign(a.num_ops, 0.0);
+    a.landmark_ms = 0.0;
+    a.slabs = static_cast<uint64_t>(slabs);
+    if (a.press != nullptr) std::fill(a.press, a.press + a.num_ops * k, 0.0);
+    if (a.errors != nullptr) std::fill(a.errors, a.errors + a.num_ops * k, uint64_t{ 0 });
+    const T *Yh = static_cast<const T *>(a.Y);
+    for (int s = 0; s < slabs; ++s) {
+        const size_t row0 = static_cast<size_t>(s) * ld;
+        const int rows = static_cast<int>(std::min(ld, N - row0)), rows256 = round_up(rows, 256);
+        LSSVM_HIP_CHECK(hipEventRecord(ev[0].e, st));
+        hipLaunchKernelGGL(k_landmark_block<T>, dim3(rows256 / 256, (m + 15) / 16), dim3(256), 0, st, p.X_.data.p, p.X_.ldx, static_cast<int>(N), static_cast<int>(row0), lm_dev.p, m,
+                           prm.kernel_type, prm.degree, gamma, static_cast<double>(static_cast<T>(prm.coef0)), slab.p, ld);
+        if (with_y) hipLaunchKernelGGL(k_reduced_aux<T>, dim3(rows256 / 256, 1 + k), dim3(256), 0, st, Y_dev.p, N, row0, slab.p + static_cast<size_t>(m) * ld, ld);
+        LSSVM_HIP_CHECK(hipGetLastError());
+        LSSVM_HIP_CHECK(hipEventRecord(ev[1].e, st));
+        LSSVM_HIP_CHECK(hipEventSynchronize(ev[1].e));
+        a.landmark_ms += elapsed_ms(ev[0], ev[1]);
+        for (size_t o = 0; o < a.num_ops; ++o) {
+            LSSVM_HIP_CHECK(hipEventRecord(ev[0].e, st));
+            hipLaunchKernelGGL(k_reduced_leverage, dim3(rows256 / RG_TW), dim3(256), 0, st, slab.p, ld, rows, m, k, a.Bt_dev + o * a.op_stride, a.ldb, a.shift_dev,
+                               a.ybar_dev != nullptr ? a.ybar_dev + o * k : nullptr, a.inv_n, with_y ? slab.p + static_cast<size_t>(m + 1) * ld : nullptr, h_dev.p, f_dev.p,
+                               with_y ? loo_dev.p : nullptr, ld);
+            LSSVM_HIP_CHECK(hipGetLastError());
+            LSSVM_HIP_CHECK(hipEventRecord(ev[1].e, st));
+            LSSVM_HIP_CHECK(hipMemcpyAsync(h_host.data(), h_dev.p, static_cast<size_t>(rows) * sizeof(double), hipMemcpyDeviceToHost, st));
+            for (int c = 0; c < k; ++c) {
+                LSSVM_HIP_CHECK(hipMemcpyAsync(&f_host[static_cast<size_t>(c) * ld], f_dev.p + static_cast<size_t>(c) * ld, static_cast<size_t>(rows) * sizeof(double), hipMemcpyDeviceToHost, st));
+                if (with_y)
+                    LSSVM_HIP_CHECK(hipMemcpyAsync(&loo_host[static_cast<size_t>(c) * ld], loo_dev.p + static_cast<size_t>(c) * ld, static_cast<size_t>(rows) * sizeof(double), hipMemcpyDeviceToHost, st));
+            }
+            LSSVM_HIP_CHECK(hipStreamSynchronize(st));
+            a.leverage_ms[o] += elapsed_ms(ev[0], ev[1]);
+            for (int i = 0; i < rows; ++i) a.max_leverage[o] = std::max(a.max_leverage[o], h_host[i]);
+            if (a.h_out != nullptr) std::copy(h_host.begin(), h_host.begin() + rows, a.h_out + o * N + row0);
+            for (int c = 0; c < k; ++c) {
+                const size_t oc = o * k + c;
+                if (a.f_out != nullptr) std::copy(&f_host[static_cast<size_t>(c) * ld], &f_host[static_cast<size_t>(c) * ld] + rows, a.f_out + oc * N + row0);
+                if (!with_y) continue;
+                const double *loo = &loo_host[static_cast<size_t>(c) * ld];
+                if (a.loo_out != nullptr) std::copy(loo, loo + rows, a.loo_out + oc * N + row0);
+                double press = a.press != nullptr ? a.press[oc] : 0.0;
+                uint64_t errors = 0;
+                for (int i = 0; i < rows; ++i) {
+                    const double y = static_cast<double>(Yh[static_cast<size_t>(c) * N + row0 + i]), d = y - loo[i];
+                    press += d * d;
+                    errors += ((loo[i] > 0.0) - (loo[i] < 0.0)) != ((y > 0.0) - (y < 0.0)) ? 1 : 0;
+                }
+                if (a.press != nullptr) a.press[oc] = press;
+                if (a.errors != nullptr) a.errors[oc] += errors;
+            }
+        }
+    }
+}
+
+template <typename T>
+void Solver<T>::fit_reduced_loo(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *costs, size_t num_costs, double *betas_out,
+                                double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out,
+                                lssvm_reduced_loo_info *infos) {
+    LSSVM_REQUIRE(betas_out != nullptr && rhos_out != nullptr, "betas_out / rhos_out must not be NULL");
+    check_reduced_loo_costs(costs, num_costs);
+    std::vector<uint64_t> lm;
+    std::vector<double> St, Kmm;
+    lssvm_reduced_info info{};
+    reduced_gram("fit_reduced_loo", Y, num_rhs, rank, landmarks, slab_rows, lm, St, Kmm, info);  // pass 1, and every other check that needs no device
+
+    const int m = static_cast<int>(rank), k = static_cast<int>(num_rhs), cols = m + 1 + k;
+    Problem<T> &p = *shards_[0];
+    const double Nd = static_cast<double>(p.N_);
+    const SetOnExit<bool> busy = hold_busy();
+    p.activate();
+    hipStream_t st = p.stream();
+    LeverageArgs a;
+    a.m = m;
+    a.k = k;
+    a.ldb = round_up(m, RG_KC);
+    a.num_ops = num_costs;
+    a.op_stride = static_cast<size_t>(m + k) * a.ldb;
+    DevBuf<double> Bt_dev, shift_dev, ybar_dev;
+    Bt_dev.alloc_zero(a.num_ops * a.op_stride, st);
+    shift_dev.alloc_zero(static_cast<size_t>(m), st);
+    ybar_dev.alloc_zero(a.num_ops * k, st);
+
+    // ---- per cost, on the host in double: M_s, L_s, beta and rho as fit_reduced forms them, V_s = L_s^-1; the operand of the cost goes to the device once ----
+    const double *s_row = &St[static_cast<size_t>(m) * cols];
+    std::vector<double> shift(static_cast<size_t>(m)), ybar(a.num_ops * k), Bt(a.op_stride), L, nus(num_costs), host_ms(num_costs);
+    for (int j = 0; j < m; ++j) shift[j] = s_row[j] / Nd;
+    for (size_t s = 0; s < num_costs; ++s) {
+        const double t_host = now_ms();
+        nus[s] = factor_reduced(St, Kmm, m, cols, Nd, 1.0 / costs[s], L);
+        double *betas = betas_out + s * k * m;
+        solve_reduced(St, L, m, k, cols, Nd, betas, rhos_out + s * k);
+        invert_lower(L, m, Bt.data(), static_cast<size_t>(a.ldb));
+        for (int c = 0; c < k; ++c) {
+            double *row = &Bt[static_cast<size_t>(m + c) * a.ldb];
+            std::fill(row, row + a.ldb, 0.0);
+            std::copy(betas + static_cast<size_t>(c) * m, betas + static_cast<size_t>(c + 1) * m, row);
+            ybar[s * k + c] = St[static_cast<size_t>(m + 1 + c) * cols + m] / Nd;
+        }
+        host_ms[s] = now_ms() - t_host;
+        LSSVM_HIP_CHECK(hipMemcpyAsync(Bt_dev.p + s * a.op_stride, Bt.data(), a.op_stride * sizeof(double), hipMemcpyHostToDevice, st));
+        LSSVM_HIP_CHECK(hipStreamSynchronize(st));  // (Bt is filled again for the next cost)
+    }
+    LSSVM_HIP_CHECK(hipMemcpyAsync(shift_dev.p, shift.data(), shift.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    LSSVM_HIP_CHECK(hipMemcpyAsync(ybar_dev.p, ybar.data(), ybar.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    LSSVM_HIP_CHECK(hipStreamSynchronize(st));
+
+    a.Bt_dev = Bt_dev.p;
+    a.shift_dev = shift_dev.p;
+    a.ybar_dev = ybar_dev.p;
+    a.inv_n = 1.0 / Nd;
+    a.Y = Y;
+    a.h_out = leverage_out;
+    a.f_out = fitted_out;
+    a.loo_out = loo_out;
+    a.press = press_out;
+    a.errors = loo_errors_out;
+    leverage_pass(lm, slab_rows, a);
+
+    if (landmarks_out != nullptr) std::copy(lm.begin(), lm.end(), landmarks_out);
+    if (infos != nullptr) {
+        for (size_t s = 0; s < num_costs; ++s) {
+            infos[s] = lssvm_reduced_loo_info{};
+            infos[s].cost = costs[s];
+            infos[s].jitter = nus[s];
+            infos[s].max_leverage = a.max_leverage[s];
+            infos[s].landmark_ms = info.landmark_ms + a.landmark_ms;
+            infos[s].gram_ms = info.gram_ms;
+            infos[s].leverage_ms = a.leverage_ms[s];
+            infos[s].host_ms = host_ms[s];
+        }
+    }
+}
+
+template <typename T>
+void Solver<T>::reduced_leverage(uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *V, const double *shift, const double *B_extra, size_t num_extra, double *h_out,
+                                 double *f_out) {
+    // ---- everything that needs no device (as reduced_gram) ----
+    const char *what = "reduced_leverage";
+    LSSVM_REQUIRE(shards_.size() == 1 && world_ == 1 && exchange_ == Exchange::none, std::string("the reduced model (") + what + ") is fitted on a problem of one device and one rank");
+    Problem<T> &p = *shards_[0];
+    LSSVM_REQUIRE(!p.weighted_, std::string("the reduced model (") + what + ") is fitted to the unweighted objective: the problem has weights set (lssvm_mi355_problem_set_weights(p, NULL, 0) removes them)");
+    LSSVM_REQUIRE(!in_cg_, std::string(what) + " cannot run between cg_begin and cg_finish");
+    check_reduced_arguments(V, 1, rank, slab_rows, p.N_);
+    LSSVM_REQUIRE(V != nullptr && shift != nullptr && h_out != nullptr, "V / shift / h_out must not be NULL");
+    LSSVM_REQUIRE(num_extra <= 4096 && (num_extra == 0 || (B_extra != nullptr && f_out != nullptr)), "at most 4096 extra columns; B_extra / f_out must not be NULL where there are some");
+    const int m = static_cast<int>(rank), k = static_cast<int>(num_extra);
+    const std::vector<uint64_t> lm = resolve_landmarks(landmarks, static_cast<size_t>(m), p.N_);
+
+    const SetOnExit<bool> busy = hold_busy();
+    p.activate();
+    hipStream_t st = p.stream();
+    LeverageArgs a;
+    a.m = m;
+    a.k = k;
+    a.ldb = round_up(m, RG_KC);
+    a.num_ops = 1;
+    a.op_stride = static_cast<size_t>(m + k) * a.ldb;
+    std::vector<double> Bt(a.op_stride, 0.0);
+    for (int n = 0; n < m; ++n) std::copy(V + static_cast<size_t>(n) * m, V + static_cast<size_t>(n + 1) * m, &Bt[static_cast<size_t>(n) * a.ldb]);  // (as given, what stands above the diagonal too: the kernel masks it)
+    for (int c = 0; c < k; ++c)
+        for (int j = 0; j < m; ++j) Bt[static_cast<size_t>(m + c) * a.ldb + j] = B_extra[static_cast<size_t>(j) * k + c];
+    DevBuf<double> Bt_dev, shift_dev;
+    Bt_dev.alloc_zero(a.op_stride, st);
+    shift_dev.alloc_zero(static_cast<size_t>(m), st);
+    LSSVM_HIP_CHECK(hipMemcpyAsync(Bt_dev.p, Bt.data(), Bt.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    LSSVM_HIP_CHECK(hipMemcpyAsync(shift_dev.p, shift, static_cast<size_t>(m) * sizeof(double), hipMemcpyHostToDevice, st));
+    LSSVM_HIP_CHECK(hipStreamSynchronize(st));
+    a.Bt_dev = Bt_dev.p;
+    a.shift_dev = shift_dev.p;
+    a.h_out = h_out;
+    a.f_out = f_out;
+    leverage_pass(lm, slab_rows, a);
+}
+
+template <typename T>
+void Solver<T>::time_leverage_kernel(uint64_t rank, uint64_t slab_rows, size_t num_extra, int repeats, double *gram_ms_out, double *leverage_ms_out) {
+    const char *what = "time_leverage_kernel";
+    LSSVM_REQUIRE(shards_.size() == 1 && world_ == 1 && exchange_ == Exchange::none, std::string("the reduced model (") + what + ") is fitted on a problem of one device and one rank");
+    Problem<T> &p = *shards_[0];
+    LSSVM_REQUIRE(!in_cg_, std::string(what) + " cannot run between cg_begin and cg_finish");
+    LSSVM_REQUIRE(repeats >= 1 && repeats <= 1000 && gram_ms_out != nullptr && leverage_ms_out != nullptr, "repeats must lie in [1, 1000]; gram_ms_out / leverage_ms_out must not be NULL");
+    LSSVM_REQUIRE(num_extra >= 1 && num_extra <= 64, "between 1 and 64 extra columns");
+    const size_t N = p.N_;
+    check_reduced_arguments(gram_ms_out, 1, rank, slab_rows, N);
+    const int m = static_cast<int>(rank), k = static_cast<int>(num_extra), cols = m + 1 + k;
+    const std::vector<uint64_t> lm = resolve_landmarks(nullptr, static_cast<size_t>(m), N);
+
+    const SetOnExit<bool> busy = hold_busy();
+    p.activate();
+    hipStream_t st = p.stream();
+    const size_t N256 = static_cast<size_t>(round_up(static_cast<long>(N), 256));
+    const size_t ld = std::min<size_t>(slab_rows == 0 ? REDUCED_DEFAULT_SLAB_ROWS : slab_rows, N256);
+    const int rows = static_cast<int>(std::min(ld, N)), rows256 = round_up(rows, 256);
+    const int nt = tiles_of(cols), ntri = nt * (nt + 1) / 2, max_chunks = static_cast<int>((ld + RG_RANGE - 1) / RG_RANGE), ldb = round_up(m, RG_KC);
+    std::vector<int> lm_host(lm.begin(), lm.end());
+    std::vector<double> Bt(static_cast<size_t>(m + k) * ldb, 0.0);
+    for (int n = 0; n < m + k; ++n)
+        for (int j = 0; j < m; ++j) Bt[static_cast<size_t>(n) * ldb + j] = n >= m || n == j ? 1.0 : 0.0;
+    std::vector<T> Yh(static_cast<size_t>(k) * N, T(1));
+    DevBuf<int> lm_dev;
+    DevBuf<T> Y_dev;
+    DevBuf<double> slab, part, St_dev, Bt_dev, shift_dev, h_dev, f_dev, loo_dev;
+    lm_dev.alloc_zero(static_cast<size_t>(m), st);
+    LSSVM_HIP_CHECK(hipMemcpyAsync(lm_dev.p, lm_host.data(), static_cast<size_t>(m) * sizeof(int), hipMemcpyHostToDevice, st));
+    Y_dev.alloc_zero(Yh.size(), st);
+    LSSVM_HIP_CHECK(hipMemcpyAsync(Y_dev.p, Yh.data(), Yh.size() * sizeof(T), hipMemcpyHostToDevice, st));
+    slab.alloc_zero(static_cast<size_t>(cols) * ld, st);
+    part.alloc_zero(static_cast<size_t>(ntri) * max_chunks * RG_TILE, st);
+    St_dev.alloc_zero(static_cast<size_t>(ntri) * RG_TILE, st);
+    Bt_dev.alloc_zero(Bt.size(), st);
+    LSSVM_HIP_CHECK(hipMemcpyAsync(Bt_dev.p, Bt.data(), Bt.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    shift_dev.alloc_zero(static_cast<size_t>(m), st);
+    h_dev.alloc_zero(ld, st);
+    f_dev.alloc_zero(static_cast<size_t>(k) * ld, st);
+    loo_dev.alloc_zero(static_cast<size_t>(k) * ld, st);
+    const lssvm_params &prm = p.params_;
+    const double scale2 = p.x_scale_ * p.x_scale_;
+    const double gamma = prm.kernel_type == LSSVM_KERNEL_LINEAR ? 1.0 / scale2 : static_cast<double>(static_cast<T>(prm.gamma)) / scale2;
+    hipLaunchKernelGGL(k_landmark_block<T>, dim3(rows256 / 256, (m + 15) / 16), dim3(256), 0, st, p.X_.data.p, p.X_.ldx, static_cast<int>(N), 0, lm_dev.p, m, prm.kernel_type, prm.degree,
+                       gamma, static_cast<double>(static_cast<T>(prm.coef0)), slab.p, ld);
+    hipLaunchKernelGGL(k_reduced_aux<T>, dim3(rows256 / 256, 1 + k), dim3(256), 0, st, Y_dev.p, N, size_t{ 0 }, slab.p + static_cast<size_t>(m) * ld, ld);
+    LSSVM_HIP_CHECK(hipGetLastError());
+    Event ev[2];
+    for (Event &e : ev) e.create(true);
+    for (int rep = -1; rep < repeats; ++rep) {  // (-1: the untimed run)
+        LSSVM_HIP_CHECK(hipMemsetAsync(St_dev.p, 0, St_dev.count * sizeof(double), st));
+        LSSVM_HIP_CHECK(hipEventRecord(ev[0].e, st));
+        enqueue_gram(slab.p, ld, cols, rows256, max_chunks, part.p, St_dev.p, st);
+        LSSVM_HIP_CHECK(hipEventRecord(ev[1].e, st));
+        LSSVM_HIP_CHECK(hipEventSynchronize(ev[1].e));
+        if (rep >= 0) gram_ms_out[rep] = elapsed_ms(ev[0], ev[1]);
+    }
+    for (int rep = -1; rep < repeats; ++rep) {
+        LSSVM_HIP_CHECK(hipEventRecord(ev[0].e, st));
+        hipLaunchKernelGGL(k_reduced_leverage, dim3(rows256 / RG_TW), dim3(256), 0, st, slab.p, ld, rows, m, k, Bt_dev.p, ldb, shift_dev.p, static_cast<const double *>(nullptr), 1.0 / static_cast<double>(N),
+                           slab.p + static_cast<size_t>(m + 1) * ld, h_dev.p, f_dev.p, loo_dev.p, ld);
+        LSSVM_HIP_CHECK(hipGetLastError());
+        LSSVM_HIP_CHECK(hipEventRecord(ev[1].e, st));
+        LSSVM_HIP_CHECK(hipEventSynchronize(ev[1].e));
+        if (rep >= 0) leverage_ms_out[rep] = elapsed_ms(ev[0], ev[1]);
     }
 }
 
@@ -412,6 +922,16 @@ template void Solver<float>::landmark_gram(const void *, size_t, uint64_t, const
 template void Solver<double>::landmark_gram(const void *, size_t, uint64_t, const uint64_t *, uint64_t, double *);
 template void Solver<float>::fit_reduced(const void *, size_t, uint64_t, const uint64_t *, uint64_t, double *, double *, uint64_t *, lssvm_reduced_info *);
 template void Solver<double>::fit_reduced(const void *, size_t, uint64_t, const uint64_t *, uint64_t, double *, double *, uint64_t *, lssvm_reduced_info *);
+template void Solver<float>::leverage_pass(const std::vector<uint64_t> &, uint64_t, LeverageArgs &);
+template void Solver<double>::leverage_pass(const std::vector<uint64_t> &, uint64_t, LeverageArgs &);
+template void Solver<float>::fit_reduced_loo(const void *, size_t, uint64_t, const uint64_t *, uint64_t, const double *, size_t, double *, double *, double *, double *, double *, double *, uint64_t *,
+                                             uint64_t *, lssvm_reduced_loo_info *);
+template void Solver<double>::fit_reduced_loo(const void *, size_t, uint64_t, const uint64_t *, uint64_t, const double *, size_t, double *, double *, double *, double *, double *, double *, uint64_t *,
+                                              uint64_t *, lssvm_reduced_loo_info *);
+template void Solver<float>::reduced_leverage(uint64_t, const uint64_t *, uint64_t, const double *, const double *, const double *, size_t, double *, double *);
+template void Solver<double>::reduced_leverage(uint64_t, const uint64_t *, uint64_t, const double *, const double *, const double *, size_t, double *, double *);
+template void Solver<float>::time_leverage_kernel(uint64_t, uint64_t, size_t, int, double *, double *);
+template void Solver<double>::time_leverage_kernel(uint64_t, uint64_t, size_t, int, double *, double *);
 template void Solver<float>::time_gram_kernels(int, double *, double *, double *);
 template void Solver<double>::time_gram_kernels(int, double *, double *, double *);
 

@@ -186,6 +186,34 @@ class CSVM:
         reduced = DataSet(data.data()[rows], [labels[i] for i in rows.tolist()], real_type=data.real_type)
         return Model(params, reduced, alpha=np.asarray(betas[0]).astype(data.real_type), rho=rhos[0])
 
+    def solve_reduced_loo_systems(self, params, A, Y, rank, costs, landmarks=None):
+        """The fixed-size models of every row of ``Y`` at every cost of ``costs`` with their leave-one-out report: ``(betas[S, k, m], rhos[S, k], landmarks[m], report)``.
+        Boundary of :meth:`fit_reduced_path`; the MI355X backend implements it."""
+        raise NotImplementedError
+
+    def fit_reduced_path(self, data: DataSet, rank: int, costs, landmarks=None):
+        """:meth:`fit_reduced` for every cost of ``costs`` together with exact leave-one-out scores -- leave-one-out with the landmark set held fixed (no counterpart in
+        the reference).  Returns ``(models, report)``: one ordinary :class:`Model` per cost, in the order of ``costs``, each with its ``params.cost``
+        set and equal to what :meth:`fit_reduced` gives at that cost; this object's own cost is ignored.  ``report`` (float64, over ALL training points, no validation split
+        and no refit): ``costs``, ``leverage[S, N]``, ``fitted[S, N]``, ``loo[S, N]`` (the value the model refitted without point i has at point i), ``press[S]``,
+        ``loo_errors[S]``, ``loo_accuracy[S]`` = 1 - loo_errors / N, ``max_leverage[S]``, ``jitter[S]``, ``infos``.  ``last_cg_info`` keeps the per-cost reports."""
+        if not data.has_labels():
+            raise InvalidParameterError("No labels given for training! Maybe the data is only usable for prediction?")  # csvm.hpp:298
+        labels = data.labels()
+        if landmarks is not None:
+            _check_landmark_classes(data, landmarks)  # (before anything is computed)
+        costs = _checked_costs(costs)
+        params = self.params.resolved(data.num_features())
+        betas, rhos, used, report = self.solve_reduced_loo_systems(params, data.data(), data.mapped_labels().reshape(1, -1), rank, costs, landmarks)
+        rows = _check_landmark_classes(data, used)
+        reduced = DataSet(data.data()[rows], [labels[i] for i in rows.tolist()], real_type=data.real_type)
+        models = [Model(replace(params, cost=float(cost)), reduced, alpha=np.asarray(betas[s][0]).astype(data.real_type), rho=rhos[s][0]) for s, cost in enumerate(costs)]
+        report = {name: (value[:, 0] if name in ("fitted", "loo", "press", "loo_errors") else value) for name, value in report.items()}
+        report["landmarks"] = np.asarray(used)
+        report["loo_accuracy"] = 1.0 - report["loo_errors"].astype(np.float64) / data.num_data_points()
+        self.last_cg_info = [dict(info, iterations=0) for info in report["infos"]]
+        return models, report
+
     def predict(self, model: Model, data: DataSet):
         if model.num_features() != data.num_features():
             raise InvalidParameterError(f"Number of features per data point ({data.num_features()}) must match the number of features per support vector of the "
@@ -348,6 +376,14 @@ class MI355CSVM(CSVM):
             raise InvalidParameterError(f"The reduced model is fitted on one device, but this backend object shards a solve over {'every visible device' if self.use_devices == 0 else self.use_devices}"
                                         f"{'' if self.use_devices == 0 else ' devices'} (num_devices={self.use_devices})!")
         return backend.fit_reduced(params, A, Y, rank, landmarks=landmarks, options=self._options)
+
+    def solve_reduced_loo_systems(self, params, A, Y, rank, costs, landmarks=None):
+        """``backend.fit_reduced_loo`` on device 0: one landmark block and one Gram matrix for all costs and rows of ``Y``, then one leverage pass per cost on the fp64
+        matrix cores.  A backend object of several devices raises, as :meth:`solve_reduced_systems` does."""
+        if self.use_devices != 1:
+            raise InvalidParameterError(f"The reduced model is fitted on one device, but this backend object shards a solve over {'every visible device' if self.use_devices == 0 else self.use_devices}"
+                                        f"{'' if self.use_devices == 0 else ' devices'} (num_devices={self.use_devices})!")
+        return backend.fit_reduced_loo(params, A, Y, rank, costs, landmarks=landmarks, options=self._options)
 
     def _one_device_path(self) -> None:
         if self.use_devices != 1:

@@ -348,6 +348,51 @@ def _landmarks_of(svm, landmarks):
     return np.asarray(svm.last_cg_info["landmarks"] if landmarks is None else landmarks).astype(np.int32)
 
 
+def fit_reduced_cv(estimator, X, y, rank, Cs, landmarks=None):
+    """The exact leave-one-out accuracy of the fixed-size model of ``estimator`` at every ``C`` of ``Cs`` -- leave-one-out with the landmark set held fixed
+    (:meth:`plssvm_amd.csvm.CSVM.fit_reduced_path`).  Returns ``(loo_accuracy[len(Cs)], fitted clones)``: the clones are what :func:`fit_reduced`
+    gives at each ``C``, the accuracy is over ALL training points, each predicted by the model refitted without it -- no validation split, no refit, one more pass over the
+    landmark block per cost.  Two classes: the sign of the leave-one-out value; more (one-vs-all): the argmax over the classes' leave-one-out values, compared with the
+    label.  ``estimator.C`` is ignored, ``class_weight`` must be None, ``estimator`` itself stays unfitted."""
+    if not isinstance(estimator, SVC):
+        raise InvalidParameterError("estimator must be a plssvm_amd.svc.SVC")
+    if estimator.class_weight is not None:
+        raise InvalidParameterError("the reduced model is fitted to the unweighted objective: class_weight must be None")
+    X, y = np.asarray(X), np.asarray(y)
+    if X.ndim != 2 or y.ndim != 1 or y.shape[0] != X.shape[0]:
+        raise InvalidParameterError(f"X must be a matrix and y a vector of as many labels as X has rows, but their shapes are {X.shape} and {y.shape}!")
+    Cs = _csvm._checked_costs(Cs)
+    params = estimator._params()
+    classes = np.array(sorted(set(y.tolist())))
+    class_weight = np.ones(len(classes))
+    svm = make_csvm(params=params)
+    clones = [SVC(**{**estimator.get_params(), "C": C}) for C in Cs]
+    if len(classes) > 2:
+        Xr = np.ascontiguousarray(X, dtype=estimator.real_type)
+        resolved = params.resolved(Xr.shape[1])
+        betas, rhos, used, report = svm.solve_reduced_loo_systems(resolved, Xr, _multiclass.one_vs_all_targets(classes, y, Xr.dtype), rank, Cs, landmarks)
+        rows = np.asarray(used).astype(np.int64)
+        scores = np.array([float(np.mean(classes[np.argmax(report["loo"][s], axis=0)] == y)) for s in range(len(Cs))])
+        for s, (C, clone) in enumerate(zip(Cs, clones)):
+            at_cost = Parameter(kernel_type=resolved.kernel_type, degree=resolved.degree, gamma=resolved.gamma, coef0=resolved.coef0, cost=C)
+            infos = [dict(report["infos"][s], iterations=0) for _ in classes]
+            model = _multiclass.OneVsAllModel(at_cost, classes, np.ascontiguousarray(Xr[rows]), np.asarray(betas[s]).astype(Xr.dtype), np.asarray(rhos[s]).astype(Xr.dtype), infos)
+            nonzero = np.any(model.alpha != 0, axis=0)
+            clone._svm, clone._model = svm, model
+            clone._fit = {
+                "classes_": classes, "class_weight_": class_weight, "fit_status_": 0, "n_features_in_": int(X.shape[1]), "shape_fit_": tuple(int(v) for v in X.shape),
+                "n_iter_": np.zeros(len(classes), dtype=np.int64), "support_": rows.astype(np.int32), "support_vectors_": model.support_vectors,
+                "n_support_": np.array([np.count_nonzero(nonzero & (y[rows] == c)) for c in classes], dtype=np.int32), "dual_coef_": model.alpha, "intercept_": -model.rho,
+            }
+        return scores, clones
+    data = DataSet(X, y.tolist(), real_type=estimator.real_type)
+    models, report = svm.fit_reduced_path(data, rank, Cs, landmarks)
+    for clone, model in zip(clones, models):
+        clone._set_binary_fit(svm, model, model.data, X, y, class_weight, None, 0)
+        clone._fit["support_"] = np.asarray(report["landmarks"]).astype(np.int32)
+    return np.asarray(report["loo_accuracy"], dtype=np.float64), clones
+
+
 def cost_path_scores(estimator, X, y, Cs, X_val, y_val):
     """The validation accuracy of a TWO-class ``estimator`` at every ``C`` of ``Cs``: one cost path (:func:`fit_cost_path`), then ONE resident predictor over all the
     models -- they share their support vectors, so the predictor takes their weight vectors two per pass over the Gram tiles.  Returns ``(scores[m], fitted clones)``."""
