@@ -179,6 +179,19 @@ void solve_one_shot(const lssvm_params *params, const T *X, size_t N, size_t d, 
     if (info != nullptr) *info = local;
 }
 
+/* what the one-shot entry points ask of the data before a device is touched */
+void check_data(const void *X, size_t N, size_t d) {
+    LSSVM_REQUIRE(X != nullptr && N > 0, "The data must not be empty!");         // csvm.cpp:73
+    LSSVM_REQUIRE(d > 0, "The data points must contain at least one feature!");  // csvm.cpp:74
+}
+
+/* the problem of a one-shot entry point that runs on device 0 alone (the cost path, PCG, the fixed-size fits); the caller has made every check that needs no device */
+template <typename T>
+lssvm::Solver<T> device0_solver(const lssvm_mi355_options *options, const lssvm_params &params, const T *X, size_t N, size_t d) {
+    static const int device0 = 0;
+    return lssvm::Solver<T>(options_of(options), params, X, LSSVM_MEM_HOST, N, d, lssvm::resolve_devices(&device0, 1, N), nullptr);
+}
+
 /* lssvm_mi355_solve_cost_path_*: every argument is checked before a device is touched; the problem is created at the first cost (the path ignores it) */
 template <typename T>
 void cost_path_one_shot(const lssvm_params *params, const T *X, size_t N, size_t d, const T *y, const double *costs, size_t num_costs, double eps, uint64_t max_iter, int verify,
@@ -188,10 +201,8 @@ void cost_path_one_shot(const lssvm_params *params, const T *X, size_t N, size_t
     lssvm_params with_cost = *params;
     with_cost.cost = costs[0];
     lssvm::check_params(&with_cost);
-    LSSVM_REQUIRE(X != nullptr && N > 0, "The data must not be empty!");                // csvm.cpp:73
-    LSSVM_REQUIRE(d > 0, "The data points must contain at least one feature!");         // csvm.cpp:74
-    static const int device0 = 0;
-    lssvm::Solver<T> prob(options_of(options), with_cost, X, LSSVM_MEM_HOST, N, d, lssvm::resolve_devices(&device0, 1, N), nullptr);
+    check_data(X, N, d);
+    lssvm::Solver<T> prob = device0_solver<T>(options, with_cost, X, N, d);
     prob.solve_cost_path(y, costs, num_costs, eps, max_iter, verify != 0, alphas_out, rhos_out, infos_out, passes_out);
 }
 
@@ -201,11 +212,9 @@ void pcg_one_shot(const lssvm_params *params, const T *X, size_t N, size_t d, co
                   T *alphas_out, double *rhos_out, lssvm_pcg_info *infos_out, const lssvm_mi355_options *options) {
     lssvm::check_params(params);
     lssvm::check_pcg_arguments(Y, num_rhs, eps, max_iter, alphas_out, rhos_out, infos_out);
-    LSSVM_REQUIRE(X != nullptr && N > 0, "The data must not be empty!");         // csvm.cpp:73
-    LSSVM_REQUIRE(d > 0, "The data points must contain at least one feature!");  // csvm.cpp:74
+    check_data(X, N, d);
     lssvm::check_precond_rank(rank, N);
-    static const int device0 = 0;
-    lssvm::Solver<T> prob(options_of(options), *params, X, LSSVM_MEM_HOST, N, d, lssvm::resolve_devices(&device0, 1, N), nullptr);
+    lssvm::Solver<T> prob = device0_solver<T>(options, *params, X, N, d);
     prob.build_preconditioner(rank, landmarks, nullptr);
     prob.solve_pcg(Y, num_rhs, eps, max_iter, alphas_out, rhos_out, infos_out);
 }
@@ -215,13 +224,11 @@ template <typename T>
 void fit_reduced_one_shot(const lssvm_params *params, const T *X, size_t N, size_t d, const T *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows,
                           double *betas_out, double *rhos_out, uint64_t *landmarks_out, lssvm_reduced_info *info, const lssvm_mi355_options *options) {
     lssvm::check_params(params);
-    LSSVM_REQUIRE(X != nullptr && N > 0, "The data must not be empty!");         // csvm.cpp:73
-    LSSVM_REQUIRE(d > 0, "The data points must contain at least one feature!");  // csvm.cpp:74
+    check_data(X, N, d);
     lssvm::check_reduced_arguments(Y, num_rhs, rank, slab_rows, N);
     LSSVM_REQUIRE(betas_out != nullptr && rhos_out != nullptr, "betas_out / rhos_out must not be NULL");
     if (landmarks != nullptr) (void) lssvm::resolve_landmarks(landmarks, static_cast<size_t>(rank), N);
-    static const int device0 = 0;
-    lssvm::Solver<T> prob(options_of(options), *params, X, LSSVM_MEM_HOST, N, d, lssvm::resolve_devices(&device0, 1, N), nullptr);
+    lssvm::Solver<T> prob = device0_solver<T>(options, *params, X, N, d);
     prob.fit_reduced(Y, num_rhs, rank, landmarks, slab_rows, betas_out, rhos_out, landmarks_out, info);
 }
 
@@ -231,14 +238,12 @@ void fit_reduced_loo_one_shot(const lssvm_params *params, const T *X, size_t N, 
                               const double *costs, size_t num_costs, double *betas_out, double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out, double *press_out,
                               uint64_t *loo_errors_out, uint64_t *landmarks_out, lssvm_reduced_loo_info *infos, const lssvm_mi355_options *options) {
     lssvm::check_params(params);
-    LSSVM_REQUIRE(X != nullptr && N > 0, "The data must not be empty!");         // csvm.cpp:73
-    LSSVM_REQUIRE(d > 0, "The data points must contain at least one feature!");  // csvm.cpp:74
+    check_data(X, N, d);
     lssvm::check_reduced_arguments(Y, num_rhs, rank, slab_rows, N);
     lssvm::check_reduced_loo_costs(costs, num_costs);
     LSSVM_REQUIRE(betas_out != nullptr && rhos_out != nullptr, "betas_out / rhos_out must not be NULL");
     if (landmarks != nullptr) (void) lssvm::resolve_landmarks(landmarks, static_cast<size_t>(rank), N);
-    static const int device0 = 0;
-    lssvm::Solver<T> prob(options_of(options), *params, X, LSSVM_MEM_HOST, N, d, lssvm::resolve_devices(&device0, 1, N), nullptr);
+    lssvm::Solver<T> prob = device0_solver<T>(options, *params, X, N, d);
     prob.fit_reduced_loo(Y, num_rhs, rank, landmarks, slab_rows, costs, num_costs, betas_out, rhos_out, leverage_out, fitted_out, loo_out, press_out, loo_errors_out, landmarks_out, infos);
 }
 

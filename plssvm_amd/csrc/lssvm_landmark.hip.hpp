@@ -82,6 +82,50 @@ __global__ __launch_bounds__(256) void k_landmark_block(const T *__restrict__ X,
     }
 }
 
+/* Kmm[k][l] = slab[l][lm[k] - row0] for the landmarks that lie in the rows [row0, row0 + rows) of this column-major slab of the block (ld doubles between two columns); a
+ * copy, no arithmetic.  The whole block at once: row0 = 0, rows = ld.  (static: a kernel that is no template cannot be inline, and both units that include this launch it) */
+static __global__ void k_gather_kmm(const double *__restrict__ slab, size_t ld, int row0, int rows, const int *__restrict__ lm, int m, double *__restrict__ Kmm) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= m * m) return;
+    const int r = lm[e / m] - row0;
+    if (r >= 0 && r < rows) Kmm[e] = slab[static_cast<size_t>(e % m) * ld + r];
+}
+
+/* The landmark block K(X, X_L) of a problem's resident data: the landmarks' indices on the device and the kernel function's scalars for the data AS X_ HOLDS IT --
+ * x' = x_scale (x - mean) leaves rbf distances and inner products scaled by x_scale^2, so gamma is divided by that; gamma and coef0 are the ones the problem's real type
+ * holds.  The ONE place this rule stands: the preconditioner, the fixed-size fit and its leave-one-out pass evaluate the block through it, so their bits agree. */
+template <typename T>
+class LandmarkBlock {
+  public:
+    /* enqueues the upload of the indices on `st`; the problem outlives the block */
+    LandmarkBlock(const Problem<T> &p, const std::vector<uint64_t> &landmarks, hipStream_t st) :
+        p_(p), st_(st), m_(static_cast<int>(landmarks.size())), lm_host_(landmarks.begin(), landmarks.end()) {
+        const double scale2 = p.x_scale_ * p.x_scale_;
+        gamma_ = p.params_.kernel_type == LSSVM_KERNEL_LINEAR ? 1.0 / scale2 : static_cast<double>(static_cast<T>(p.params_.gamma)) / scale2;
+        coef0_ = static_cast<double>(static_cast<T>(p.params_.coef0));
+        lm_dev_.alloc_zero(static_cast<size_t>(m_), st);
+        LSSVM_HIP_CHECK(hipMemcpyAsync(lm_dev_.p, lm_host_.data(), static_cast<size_t>(m_) * sizeof(int), hipMemcpyHostToDevice, st));
+    }
+    /* out[l][i - row0] = k(x_i, x_lm[l]) for row0 <= i < row0 + rows256 (a multiple of 256; exact zeros from point N on), `ld` doubles between two landmarks' columns */
+    void enqueue(size_t row0, int rows256, double *out, size_t ld) const {
+        hipLaunchKernelGGL(k_landmark_block<T>, dim3(rows256 / 256, (m_ + 15) / 16), dim3(256), 0, st_, p_.X_.data.p, p_.X_.ldx, static_cast<int>(p_.N_), static_cast<int>(row0), lm_dev_.p, m_,
+                           p_.params_.kernel_type, p_.params_.degree, gamma_, coef0_, out, ld);
+    }
+    /* K_mm's rows of the landmarks among the `rows` points from row0 on, out of the slab `enqueue` filled */
+    void enqueue_gather_kmm(const double *slab, size_t ld, size_t row0, int rows, double *Kmm) const {
+        hipLaunchKernelGGL(k_gather_kmm, dim3((m_ * m_ + 255) / 256), dim3(256), 0, st_, slab, ld, static_cast<int>(row0), rows, lm_dev_.p, m_, Kmm);
+    }
+    size_t device_bytes() const { return lm_dev_.count * sizeof(int); }
+
+  private:
+    const Problem<T> &p_;
+    hipStream_t st_;
+    int m_;
+    std::vector<int> lm_host_;  // (the source of the asynchronous upload)
+    DevBuf<int> lm_dev_;
+    double gamma_ = 0.0, coef0_ = 0.0;
+};
+
 /* G[j][k] = sum over i of Bhat[j][i] Bhat[k][i] for one 16 x 16 tile on or below the diagonal: ONE thread owns an entry and adds its products for i ascending, in
  * double -- a single fixed-order sum per entry, no partial sums to combine and no atomics.  64 rows of both column groups go through LDS per step. */
 template <typename T>
@@ -108,6 +152,9 @@ __global__ __launch_bounds__(256) void k_precond_gram(const T *__restrict__ Bhat
 
 /* A = L L^T in place (lower triangle; the upper one is left alone); false at a pivot that is not positive and finite   (lssvm_precond.hip) */
 bool cholesky_lower(std::vector<double> &A, int m);
+/* L L^T = M + nu I for the lower triangle of the m x m matrix M (row major): nu = eps64 trace(M), tenfold while the factorisation fails, seven attempts; returns the nu
+ * that let it factor.  `subject` names M in the two refusals (no positive finite trace; not factored)   (lssvm_precond.hip) */
+double cholesky_with_jitter(const std::vector<double> &M, int m, const char *subject, std::vector<double> &L);
 /* the library's own landmarks: the first `rank` entries of a Fisher-Yates shuffle of 0 ... N-1 driven by splitmix64 from a fixed state (include/plssvm_amd.h) */
 std::vector<uint64_t> default_landmarks(size_t N, size_t rank);
 

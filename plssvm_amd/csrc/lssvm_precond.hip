@@ -36,13 +36,7 @@ constexpr int PC_SOLVE_COLS = 32;                             // columns of Bhat
 
 /* ---------------------------------------------------------------- the build ---------------------------------------------------------------- */
 
-/* (K_Nm itself: k_landmark_block, lssvm_landmark.hip.hpp) */
-
-/* Kmm[k][l] = Kd[l][lm[k]] */
-__global__ void k_gather_kmm(const double *__restrict__ Kd, size_t ldN, const int *__restrict__ lm, int m, double *__restrict__ Kmm) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < m * m) Kmm[e] = Kd[static_cast<size_t>(e % m) * ldN + lm[e / m]];
-}
+/* (K_Nm itself and K_mm out of it: LandmarkBlock, lssvm_landmark.hip.hpp) */
 
 /* Bf[k][i] = sum over l <= k of Kd[l][i] Linv[k][l]: column k of K_Nm L^-T (Linv = L^-1, lower triangular, row major), l ascending */
 __global__ __launch_bounds__(256) void k_nystrom_factor(const double *__restrict__ Kd, size_t ldN, const double *__restrict__ Linv, int m, double *__restrict__ Bf) {
@@ -235,8 +229,9 @@ __global__ __launch_bounds__(RED_THREADS) void k_pcg_update_d(T *__restrict__ d,
 
 /* ---------------------------------------------------------------- host: dense factorisations in double (<= 513 x 513, row major) ---------------------------------------------------------------- */
 
-/* L^-1 (lower triangular) of the lower triangle of L, row by row: row i = (e_i - sum over k < i of L[i][k] row k) / L[i][i] */
-std::vector<double> invert_lower(const std::vector<double> &L, int m) {
+/* L^-1 (lower triangular) of the lower triangle of L, row by row: row i = (e_i - sum over k < i of L[i][k] row k) * (1 / L[i][i]).
+ * NOT to be merged with invert_lower_rows (lssvm_reduced.hip), which DIVIDES by L[i][i]: either change moves the bits of every preconditioned solve or of every leverage. */
+std::vector<double> invert_lower_by_reciprocal(const std::vector<double> &L, int m) {
     std::vector<double> inv(static_cast<size_t>(m) * m, 0.0);
     for (int i = 0; i < m; ++i) {
         double *ri = &inv[static_cast<size_t>(i) * m];
@@ -288,6 +283,21 @@ bool cholesky_lower(std::vector<double> &A, int m) {
         }
     }
     return true;
+}
+
+double cholesky_with_jitter(const std::vector<double> &M, int m, const char *subject, std::vector<double> &L) {
+    double trace = 0.0;
+    for (int k = 0; k < m; ++k) trace += M[static_cast<size_t>(k) * m + k];
+    LSSVM_REQUIRE(std::isfinite(trace) && trace > 0.0, std::string(subject) + " has no positive finite trace");
+    double nu = DBL_EPSILON * trace;
+    bool factored = false;
+    for (int attempt = 0; attempt < 7 && !factored; ++attempt, nu *= factored ? 1.0 : 10.0) {
+        L = M;
+        for (int k = 0; k < m; ++k) L[static_cast<size_t>(k) * m + k] += nu;
+        factored = cholesky_lower(L, m);
+    }
+    if (!factored) throw Error(LSSVM_ERR_INTERNAL, std::string(subject) + " could not be factored (jitter up to " + std::to_string(nu / 10.0) + ")");
+    return nu;
 }
 
 /* the library's own landmarks: the first `rank` entries of a Fisher-Yates shuffle of 0 ... N-1 driven by splitmix64 from a fixed state (include/plssvm_amd.h) */
@@ -359,41 +369,22 @@ void Solver<T>::build_preconditioner(uint64_t rank, const uint64_t *landmarks, l
     const size_t ldN = static_cast<size_t>(round_up(static_cast<long>(N), 256));
 
     // ---- the landmark block K_Nm (all N points) from the resident data, and K_mm out of it ----
-    std::vector<int> lm_host(lm.begin(), lm.end());
-    DevBuf<int> lm_dev;
-    lm_dev.alloc_zero(static_cast<size_t>(m), st);
-    LSSVM_HIP_CHECK(hipMemcpyAsync(lm_dev.p, lm_host.data(), static_cast<size_t>(m) * sizeof(int), hipMemcpyHostToDevice, st));
+    const LandmarkBlock<T> block(p, lm, st);
     DevBuf<double> Kd, Bf, Kmm_dev, Linv_dev, G_dev;
     Kd.alloc_zero(static_cast<size_t>(m) * ldN, st);
-    // the kernel function on the data as X_ holds it: x' = x_scale (x - mean) leaves rbf distances and inner products scaled by x_scale^2
-    const lssvm_params &prm = p.params_;
-    const double scale2 = p.x_scale_ * p.x_scale_;
-    const double gamma = prm.kernel_type == LSSVM_KERNEL_LINEAR ? 1.0 / scale2 : static_cast<double>(static_cast<T>(prm.gamma)) / scale2;
-    hipLaunchKernelGGL(k_landmark_block<T>, dim3(static_cast<unsigned>(ldN / 256), (m + 15) / 16), dim3(256), 0, st, p.X_.data.p, p.X_.ldx, static_cast<int>(N), 0, lm_dev.p, m, prm.kernel_type,
-                       prm.degree, gamma, static_cast<double>(static_cast<T>(prm.coef0)), Kd.p, ldN);
+    block.enqueue(0, static_cast<int>(ldN), Kd.p, ldN);  // (one slab of all the rows)
     Kmm_dev.alloc_zero(static_cast<size_t>(m) * m, st);
-    hipLaunchKernelGGL(k_gather_kmm, dim3((m * m + 255) / 256), dim3(256), 0, st, Kd.p, ldN, lm_dev.p, m, Kmm_dev.p);
+    block.enqueue_gather_kmm(Kd.p, ldN, 0, static_cast<int>(ldN), Kmm_dev.p);
     LSSVM_HIP_CHECK(hipGetLastError());
     std::vector<double> Kmm(static_cast<size_t>(m) * m);
     LSSVM_HIP_CHECK(hipMemcpyAsync(Kmm.data(), Kmm_dev.p, Kmm.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     LSSVM_HIP_CHECK(hipStreamSynchronize(st));
 
-    // ---- L L^T = K_mm + nu I on the host: nu from eps64 trace(K_mm), tenfold while the factorisation fails ----
+    // ---- L L^T = K_mm + nu I on the host ----
     double host_ms = 0.0, t_host = now_ms();
-    double trace = 0.0;
-    for (int k = 0; k < m; ++k) trace += Kmm[static_cast<size_t>(k) * m + k];
-    LSSVM_REQUIRE(std::isfinite(trace) && trace > 0.0, "the kernel matrix of the landmarks has no positive finite trace");
-    double nu = DBL_EPSILON * trace;
     std::vector<double> L;
-    bool factored = false;
-    for (int attempt = 0; attempt < 7 && !factored; ++attempt, nu *= factored ? 1.0 : 10.0) {
-        L = Kmm;
-        for (int k = 0; k < m; ++k) L[static_cast<size_t>(k) * m + k] += nu;
-        factored = cholesky_lower(L, m);
-    }
-    if (!factored) throw Error(LSSVM_ERR_INTERNAL, "the kernel matrix of the landmarks could not be factored (jitter up to " + std::to_string(nu / 10.0) + ")");
-    pc->jitter = nu;
-    const std::vector<double> Linv = invert_lower(L, m);
+    pc->jitter = cholesky_with_jitter(Kmm, m, "the kernel matrix of the landmarks", L);
+    const std::vector<double> Linv = invert_lower_by_reciprocal(L, m);
     host_ms += now_ms() - t_host;
 
     // ---- B_f = K_Nm L^-T, Bhat = [E B_f | sqrt(sigma) 1] in the real type ----
@@ -419,7 +410,7 @@ void Solver<T>::build_preconditioner(uint64_t rank, const uint64_t *landmarks, l
         G[static_cast<size_t>(j) * cols + j] += pc->sigma;
     }
     if (!cholesky_lower(G, cols)) throw Error(LSSVM_ERR_INTERNAL, "Bhat^T Bhat + sigma I could not be factored");
-    const std::vector<double> Ginv = inverse_from_lower_inverse(invert_lower(G, cols), cols);
+    const std::vector<double> Ginv = inverse_from_lower_inverse(invert_lower_by_reciprocal(G, cols), cols);
     host_ms += now_ms() - t_host;
     pc->Ginv.alloc_zero(Ginv.size(), st);
     LSSVM_HIP_CHECK(hipMemcpyAsync(pc->Ginv.p, Ginv.data(), Ginv.size() * sizeof(double), hipMemcpyHostToDevice, st));

@@ -256,6 +256,12 @@ struct Event {
     }
     void create(bool timing) { LSSVM_HIP_CHECK(hipEventCreateWithFlags(&e, timing ? hipEventDefault : hipEventDisableTiming)); }
 };
+/* milliseconds between two timing events the stream has passed */
+inline float elapsed_ms(const Event &a, const Event &b) {
+    float ms = 0.0f;
+    LSSVM_HIP_CHECK(hipEventElapsedTime(&ms, a.e, b.e));
+    return ms;
+}
 template <typename U>
 struct PinnedBuf {
     U *p = nullptr;
@@ -334,6 +340,8 @@ template <typename T>
 class Solver;
 template <typename T>
 class CgSteps;
+template <typename T>
+class LandmarkBlock;  // K(X, X_L) of a resident problem (lssvm_landmark.hip.hpp)
 
 /* The CG state of ONE right-hand side on one device: the vectors y, b, x, r, d, Ad, the scalars and the four sets of partial sums, the host copies of the scalars and a
  * mapped host word for the iteration's delta (k_finish_delta stores its 8 bytes straight into host memory: no copy per iteration).  A problem has one of its own (the
@@ -416,6 +424,7 @@ class Problem {
   private:
     friend class Solver<T>;
     friend class CgSteps<T>;
+    friend class LandmarkBlock<T>;
     TileArgs<T> tile_args(const T *v_dev) const;
 
     Options opt_{};
@@ -752,6 +761,7 @@ class Solver final : public ProblemBase {
     void solve_on_lanes(const T *Y, size_t num_rhs, double eps, uint64_t max_iter, T *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out);
     Problem<T> &precond_problem(const char *what);                        // the checks every preconditioner entry point shares; shard 0
     void enqueue_precond_apply(const T *r, T *z, double *part_rz) const;  // z = r - Bhat G^-1 Bhat^T r and the partial sums of r.z
+    Problem<T> &reduced_problem(const char *what, bool unweighted_only);  // the checks every entry point of the fixed-size model shares; shard 0 (lssvm_reduced.hip)
     /* what fit_reduced and landmark_gram share: the checks, the slabs, St (cols x cols, both triangles) and K_mm (rank x rank) on the host */
     void reduced_gram(const char *what, const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, std::vector<uint64_t> &lm_out,
                       std::vector<double> &gram_out, std::vector<double> &kmm_out, lssvm_reduced_info &info);

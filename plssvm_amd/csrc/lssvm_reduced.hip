@@ -21,7 +21,6 @@
 #include "lssvm_landmark.hip.hpp"
 
 #include <algorithm>
-#include <cfloat>
 #include <cmath>
 
 namespace lssvm {
@@ -43,14 +42,6 @@ __global__ __launch_bounds__(256) void k_reduced_aux(const T *__restrict__ Y, si
     double v = 0.0;
     if (i < N) v = c == 0 ? 1.0 : static_cast<double>(Y[static_cast<size_t>(c - 1) * N + i]);
     out[static_cast<size_t>(c) * ld + local] = v;
-}
-
-/* Kmm[k][l] = Phi[lm[k]][l] for the landmarks that lie in this slab's rows */
-__global__ void k_reduced_gather_kmm(const double *__restrict__ slab, size_t ld, int row0, int rows, const int *__restrict__ lm, int m, double *__restrict__ Kmm) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= m * m) return;
-    const int r = lm[e / m] - row0;
-    if (r >= 0 && r < rows) Kmm[e] = slab[static_cast<size_t>(e % m) * ld + r];
 }
 
 /* part[tile][chunk] = A^T B over the rows [chunk RG_RANGE, min((chunk + 1) RG_RANGE, rows)) of the slab, A = the columns 128 bj ... and B = the columns 128 bk ... of the
@@ -194,10 +185,54 @@ void unpack_tiles(const std::vector<double> &tiles, int cols, std::vector<double
     }
 }
 
-float elapsed_ms(const Event &a, const Event &b) {
-    float ms = 0.0f;
-    LSSVM_HIP_CHECK(hipEventElapsedTime(&ms, a.e, b.e));
-    return ms;
+/* rows of a slab (= doubles between two of its columns: at most N rounded up to 256) and how many slabs cover the N points; slab s holds the rows(s) points from row0(s)
+ * on, in rows256(s) <= ld rows */
+struct SlabPlan {
+    size_t N, ld;
+    int slabs;
+    SlabPlan(size_t num_points, uint64_t slab_rows) :
+        N(num_points), ld(std::min<size_t>(slab_rows == 0 ? REDUCED_DEFAULT_SLAB_ROWS : slab_rows, static_cast<size_t>(round_up(static_cast<long>(num_points), 256)))),
+        slabs(static_cast<int>((N + ld - 1) / ld)) {}
+    size_t row0(int s) const { return static_cast<size_t>(s) * ld; }
+    int rows(int s) const { return static_cast<int>(std::min(ld, N - row0(s))); }
+    int rows256(int s) const { return round_up(rows(s), 256); }  // (<= ld: ld is a multiple of 256)
+};
+
+/* the k right-hand sides (k x N, the problem's type) on the device, or none of them for Y = NULL */
+template <typename T>
+struct RhsOnDevice {
+    DevBuf<T> Y;
+    int k = 0;
+    RhsOnDevice(const void *Y_host, int num_rhs, size_t N, hipStream_t st) {
+        if (Y_host == nullptr) return;
+        k = num_rhs;
+        Y.alloc_zero(static_cast<size_t>(k) * N, st);
+        LSSVM_HIP_CHECK(hipMemcpyAsync(Y.p, Y_host, static_cast<size_t>(k) * N * sizeof(T), hipMemcpyHostToDevice, st));
+    }
+};
+
+/* slab s of Pt into `slab`: the m columns of Phi and, where there are right-hand sides, the [1 | Y] columns behind them */
+template <typename T>
+void enqueue_slab(const LandmarkBlock<T> &block, int m, const SlabPlan &plan, int s, const RhsOnDevice<T> &rhs, double *slab, hipStream_t st) {
+    block.enqueue(plan.row0(s), plan.rows256(s), slab, plan.ld);
+    if (rhs.Y.p != nullptr)
+        hipLaunchKernelGGL(k_reduced_aux<T>, dim3(plan.rows256(s) / 256, 1 + rhs.k), dim3(256), 0, st, rhs.Y.p, plan.N, plan.row0(s), slab + static_cast<size_t>(m) * plan.ld, plan.ld);
+}
+
+/* the timing aids: one untimed run of `launch`, then `repeats` runs between two events; `before` is enqueued ahead of each, outside the timed span */
+template <typename Before, typename Launch>
+void timed_repeats(hipStream_t st, int repeats, double *out_ms, Before before, Launch launch) {
+    Event ev[2];
+    for (Event &e : ev) e.create(true);
+    for (int rep = -1; rep < repeats; ++rep) {  // (-1: the untimed run)
+        before();
+        LSSVM_HIP_CHECK(hipEventRecord(ev[0].e, st));
+        launch();
+        LSSVM_HIP_CHECK(hipGetLastError());
+        LSSVM_HIP_CHECK(hipEventRecord(ev[1].e, st));
+        LSSVM_HIP_CHECK(hipEventSynchronize(ev[1].e));
+        if (rep >= 0) out_ms[rep] = elapsed_ms(ev[0], ev[1]);
+    }
 }
 
 /* ---- the host's part of a fit, in double, shared by fit_reduced and fit_reduced_loo: M = S - s s^T / N + sigma K_mm (lower triangle), (M + nu I) = L L^T,
@@ -205,21 +240,9 @@ float elapsed_ms(const Event &a, const Event &b) {
 double factor_reduced(const std::vector<double> &St, const std::vector<double> &Kmm, int m, int cols, double Nd, double sigma, std::vector<double> &L) {
     const double *s = &St[static_cast<size_t>(m) * cols];
     std::vector<double> M(static_cast<size_t>(m) * m, 0.0);
-    double trace = 0.0;
-    for (int j = 0; j < m; ++j) {
+    for (int j = 0; j < m; ++j)
         for (int l = 0; l <= j; ++l) M[static_cast<size_t>(j) * m + l] = St[static_cast<size_t>(j) * cols + l] - s[j] * s[l] / Nd + sigma * Kmm[static_cast<size_t>(j) * m + l];
-        trace += M[static_cast<size_t>(j) * m + j];
-    }
-    LSSVM_REQUIRE(std::isfinite(trace) && trace > 0.0, "the matrix of the reduced model has no positive finite trace");
-    double nu = DBL_EPSILON * trace;
-    bool factored = false;
-    for (int attempt = 0; attempt < 7 && !factored; ++attempt, nu *= factored ? 1.0 : 10.0) {
-        L = M;
-        for (int j = 0; j < m; ++j) L[static_cast<size_t>(j) * m + j] += nu;
-        factored = cholesky_lower(L, m);
-    }
-    if (!factored) throw Error(LSSVM_ERR_INTERNAL, "the matrix of the reduced model could not be factored (jitter up to " + std::to_string(nu / 10.0) + ")");
-    return nu;
+    return cholesky_with_jitter(M, m, "the matrix of the reduced model", L);
 }
 
 void solve_reduced(const std::vector<double> &St, const std::vector<double> &L, int m, int k, int cols, double Nd, double *betas_out, double *rhos_out) {
@@ -246,8 +269,10 @@ void solve_reduced(const std::vector<double> &St, const std::vector<double> &L, 
 }
 
 /* row n of `out` (ldb doubles apart, zeros beyond the diagonal) = row n of V = L^-1 by forward substitution, row by row: V[n][:] = (e_n - sum_{l < n} L[n][l] V[l][:]) / L[n][n],
- * the l ascending for every entry */
-void invert_lower(const std::vector<double> &L, int m, double *out, size_t ldb) {
+ * the l ascending for every entry.
+ * NOT to be merged with invert_lower_by_reciprocal (lssvm_precond.hip), which multiplies by 1 / L[n][n]: either change moves the bits of every leverage or of every
+ * preconditioned solve. */
+void invert_lower_rows(const std::vector<double> &L, int m, double *out, size_t ldb) {
     for (int n = 0; n < m; ++n) {
         double *vn = out + static_cast<size_t>(n) * ldb;
         std::fill(vn, vn + ldb, 0.0);
@@ -437,11 +462,11 @@ __global__ __launch_bounds__(256, 2) void k_reduced_leverage(const double *__res
 
 }  // namespace
 
-/* what a leave-one-out pass works on: `num_ops` operands on the device (Bt of k_reduced_leverage, op_stride doubles apart; ybar: num_ops x k or NULL), and where its results go */
+/* what a leave-one-out pass works on: `num_ops` operands on the device (Bt of k_reduced_leverage, op_stride doubles apart; ybar: num_ops x k or none), and where its results go */
 struct LeverageArgs {
-    int m = 0, k = 0, ldb = 0;
-    size_t num_ops = 0, op_stride = 0;
-    const double *Bt_dev = nullptr, *shift_dev = nullptr, *ybar_dev = nullptr;
+    const int m, k, ldb;
+    const size_t num_ops, op_stride;
+    DevBuf<double> Bt, shift, ybar;
     double inv_n = 0.0;
     const void *Y = nullptr;                                             // the host's right-hand sides (k x N, the problem's type), or NULL: no leave-one-out values
     double *h_out = nullptr, *f_out = nullptr, *loo_out = nullptr;       // num_ops x N, num_ops x k x N, num_ops x k x N; each may be NULL
@@ -449,7 +474,31 @@ struct LeverageArgs {
     uint64_t *errors = nullptr;                                          // num_ops x k, or NULL
     std::vector<double> max_leverage, leverage_ms;                       // per operand
     double landmark_ms = 0.0;
-    uint64_t slabs = 0;
+
+    /* the operands as zeros on the device */
+    LeverageArgs(int rank, int num_cols, size_t operands, bool with_ybar, hipStream_t stream) :
+        m(rank), k(num_cols), ldb(round_up(rank, RG_KC)), num_ops(operands), op_stride(static_cast<size_t>(rank + num_cols) * ldb), st(stream) {
+        Bt.alloc_zero(num_ops * op_stride, st);
+        shift.alloc_zero(static_cast<size_t>(m), st);
+        if (with_ybar) ybar.alloc_zero(num_ops * k, st);
+    }
+    /* operand o <- the host's m + k rows of ldb doubles; asynchronous: the rows stay as they are until the stream has been synchronised */
+    void upload_operand(size_t o, const double *Bt_host) {
+        LSSVM_HIP_CHECK(hipMemcpyAsync(Bt.p + o * op_stride, Bt_host, op_stride * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    /* shift (m) and, where the pass takes one, ybar (num_ops x k); returns when these and the operands are on the device */
+    void upload_shift(const double *shift_host, const double *ybar_host) {
+        LSSVM_HIP_CHECK(hipMemcpyAsync(shift.p, shift_host, static_cast<size_t>(m) * sizeof(double), hipMemcpyHostToDevice, st));
+        if (ybar_host != nullptr) LSSVM_HIP_CHECK(hipMemcpyAsync(ybar.p, ybar_host, ybar.count * sizeof(double), hipMemcpyHostToDevice, st));
+        LSSVM_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    /* k_reduced_leverage for operand o on `rows` rows of a slab (ld doubles between its columns; its [1 | Y] columns stand behind Phi where `loo` is given) */
+    void enqueue(size_t o, const double *slab, size_t ld, int rows, double *h, double *f, double *loo) const {
+        hipLaunchKernelGGL(k_reduced_leverage, dim3(round_up(rows, 256) / RG_TW), dim3(256), 0, st, slab, ld, rows, m, k, Bt.p + o * op_stride, ldb, shift.p, ybar.p != nullptr ? ybar.p + o * k : nullptr,
+                           inv_n, loo != nullptr ? slab + static_cast<size_t>(m + 1) * ld : nullptr, h, f, loo, ld);
+        LSSVM_HIP_CHECK(hipGetLastError());
+    }
+    hipStream_t st;
 };
 
 void check_reduced_arguments(const void *Y, size_t num_rhs, uint64_t rank, uint64_t slab_rows, size_t num_points) {
@@ -461,13 +510,20 @@ void check_reduced_arguments(const void *Y, size_t num_rhs, uint64_t rank, uint6
 }
 
 template <typename T>
+Problem<T> &Solver<T>::reduced_problem(const char *what, bool unweighted_only) {
+    LSSVM_REQUIRE(shards_.size() == 1 && world_ == 1 && exchange_ == Exchange::none, std::string("the reduced model (") + what + ") is fitted on a problem of one device and one rank");
+    Problem<T> &p = *shards_[0];
+    LSSVM_REQUIRE(!unweighted_only || !p.weighted_,
+                  std::string("the reduced model (") + what + ") is fitted to the unweighted objective: the problem has weights set (lssvm_mi355_problem_set_weights(p, NULL, 0) removes them)");
+    LSSVM_REQUIRE(!in_cg_, std::string(what) + " cannot run between cg_begin and cg_finish");
+    return p;
+}
+
+template <typename T>
 void Solver<T>::reduced_gram(const char *what, const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, std::vector<uint64_t> &lm,
                              std::vector<double> &gram, std::vector<double> &Kmm, lssvm_reduced_info &info) {
     // ---- everything that needs no device ----
-    LSSVM_REQUIRE(shards_.size() == 1 && world_ == 1 && exchange_ == Exchange::none, std::string("the reduced model (") + what + ") is fitted on a problem of one device and one rank");
-    Problem<T> &p = *shards_[0];
-    LSSVM_REQUIRE(!p.weighted_, std::string("the reduced model (") + what + ") is fitted to the unweighted objective: the problem has weights set (lssvm_mi355_problem_set_weights(p, NULL, 0) removes them)");
-    LSSVM_REQUIRE(!in_cg_, std::string(what) + " cannot run between cg_begin and cg_finish");
+    Problem<T> &p = reduced_problem(what, true);
     const size_t N = p.N_;
     check_reduced_arguments(Y, num_rhs, rank, slab_rows, N);
     LSSVM_REQUIRE(num_rhs <= 4096, "at most 4096 right hand sides per call");
@@ -478,43 +534,29 @@ void Solver<T>::reduced_gram(const char *what, const void *Y, size_t num_rhs, ui
     const SetOnExit<bool> busy = hold_busy();
     p.activate();
     hipStream_t st = p.stream();
-    const size_t N256 = static_cast<size_t>(round_up(static_cast<long>(N), 256));
-    const size_t ld = std::min<size_t>(slab_rows == 0 ? REDUCED_DEFAULT_SLAB_ROWS : slab_rows, N256);  // rows of a slab = doubles between two columns
-    const int slabs = static_cast<int>((N + ld - 1) / ld);
+    const SlabPlan plan(N, slab_rows);
+    const size_t ld = plan.ld;
     const int nt = tiles_of(cols), ntri = nt * (nt + 1) / 2;
     const int max_chunks = static_cast<int>((ld + RG_RANGE - 1) / RG_RANGE);
 
-    std::vector<int> lm_host(lm.begin(), lm.end());
-    DevBuf<int> lm_dev;
-    DevBuf<T> Y_dev;
+    const LandmarkBlock<T> block(p, lm, st);
+    const RhsOnDevice<T> rhs(Y, k, N, st);
     DevBuf<double> slab, part, St_dev, Kmm_dev;
-    lm_dev.alloc_zero(static_cast<size_t>(m), st);
-    LSSVM_HIP_CHECK(hipMemcpyAsync(lm_dev.p, lm_host.data(), static_cast<size_t>(m) * sizeof(int), hipMemcpyHostToDevice, st));
-    Y_dev.alloc_zero(static_cast<size_t>(k) * N, st);
-    LSSVM_HIP_CHECK(hipMemcpyAsync(Y_dev.p, Y, static_cast<size_t>(k) * N * sizeof(T), hipMemcpyHostToDevice, st));
     slab.alloc_zero(static_cast<size_t>(cols) * ld, st);
     part.alloc_zero(static_cast<size_t>(ntri) * max_chunks * RG_TILE, st);
     St_dev.alloc_zero(static_cast<size_t>(ntri) * RG_TILE, st);
     Kmm_dev.alloc_zero(static_cast<size_t>(m) * m, st);
 
-    // the kernel function on the data as X_ holds it (build_preconditioner): x' = x_scale (x - mean) leaves rbf distances and inner products scaled by x_scale^2
-    const lssvm_params &prm = p.params_;
-    const double scale2 = p.x_scale_ * p.x_scale_;
-    const double gamma = prm.kernel_type == LSSVM_KERNEL_LINEAR ? 1.0 / scale2 : static_cast<double>(static_cast<T>(prm.gamma)) / scale2;
     Event ev[3];
     for (Event &e : ev) e.create(true);
     double landmark_ms = 0.0, gram_ms = 0.0;
-    for (int s = 0; s < slabs; ++s) {
-        const size_t row0 = static_cast<size_t>(s) * ld;
-        const int rows = static_cast<int>(std::min(ld, N - row0)), rows256 = round_up(rows, 256);  // (rows256 <= ld: ld is a multiple of 256)
+    for (int s = 0; s < plan.slabs; ++s) {
         LSSVM_HIP_CHECK(hipEventRecord(ev[0].e, st));
-        hipLaunchKernelGGL(k_landmark_block<T>, dim3(rows256 / 256, (m + 15) / 16), dim3(256), 0, st, p.X_.data.p, p.X_.ldx, static_cast<int>(N), static_cast<int>(row0), lm_dev.p, m,
-                           prm.kernel_type, prm.degree, gamma, static_cast<double>(static_cast<T>(prm.coef0)), slab.p, ld);
-        hipLaunchKernelGGL(k_reduced_aux<T>, dim3(rows256 / 256, 1 + k), dim3(256), 0, st, Y_dev.p, N, row0, slab.p + static_cast<size_t>(m) * ld, ld);
-        hipLaunchKernelGGL(k_reduced_gather_kmm, dim3((m * m + 255) / 256), dim3(256), 0, st, slab.p, ld, static_cast<int>(row0), rows, lm_dev.p, m, Kmm_dev.p);
+        enqueue_slab(block, m, plan, s, rhs, slab.p, st);
+        block.enqueue_gather_kmm(slab.p, ld, plan.row0(s), plan.rows(s), Kmm_dev.p);
         LSSVM_HIP_CHECK(hipGetLastError());
         LSSVM_HIP_CHECK(hipEventRecord(ev[1].e, st));
-        enqueue_gram(slab.p, ld, cols, rows256, max_chunks, part.p, St_dev.p, st);
+        enqueue_gram(slab.p, ld, cols, plan.rows256(s), max_chunks, part.p, St_dev.p, st);
         LSSVM_HIP_CHECK(hipEventRecord(ev[2].e, st));
         LSSVM_HIP_CHECK(hipEventSynchronize(ev[2].e));
         landmark_ms += elapsed_ms(ev[0], ev[1]);
@@ -529,11 +571,11 @@ void Solver<T>::reduced_gram(const char *what, const void *Y, size_t num_rhs, ui
 
     info = lssvm_reduced_info{};
     info.rank = static_cast<uint64_t>(m);
-    info.slabs = static_cast<uint64_t>(slabs);
+    info.slabs = static_cast<uint64_t>(plan.slabs);
     info.landmark_ms = landmark_ms;
     info.gram_ms = gram_ms;
     info.total_ms = now_ms() - t0;
-    info.workspace_bytes = (slab.count + part.count + St_dev.count + Kmm_dev.count) * sizeof(double) + Y_dev.count * sizeof(T) + lm_dev.count * sizeof(int);
+    info.workspace_bytes = (slab.count + part.count + St_dev.count + Kmm_dev.count) * sizeof(double) + rhs.Y.count * sizeof(T) + block.device_bytes();
 }
 
 template <typename T>
@@ -590,55 +632,38 @@ void Solver<T>::leverage_pass(const std::vector<uint64_t> &lm, uint64_t slab_row
     const bool with_y = a.Y != nullptr;
     const int cols = with_y ? m + 1 + k : m;
     hipStream_t st = p.stream();
-    const size_t N256 = static_cast<size_t>(round_up(static_cast<long>(N), 256));
-    const size_t ld = std::min<size_t>(slab_rows == 0 ? REDUCED_DEFAULT_SLAB_ROWS : slab_rows, N256);
-    const int slabs = static_cast<int>((N + ld - 1) / ld);
+    const SlabPlan plan(N, slab_rows);
+    const size_t ld = plan.ld;
 
-    std::vector<int> lm_host(lm.begin(), lm.end());
-    DevBuf<int> lm_dev;
-    DevBuf<T> Y_dev;
+    const LandmarkBlock<T> block(p, lm, st);
+    const RhsOnDevice<T> rhs(a.Y, k, N, st);
     DevBuf<double> slab, h_dev, f_dev, loo_dev;
-    lm_dev.alloc_zero(static_cast<size_t>(m), st);
-    LSSVM_HIP_CHECK(hipMemcpyAsync(lm_dev.p, lm_host.data(), static_cast<size_t>(m) * sizeof(int), hipMemcpyHostToDevice, st));
-    if (with_y) {
-        Y_dev.alloc_zero(static_cast<size_t>(k) * N, st);
-        LSSVM_HIP_CHECK(hipMemcpyAsync(Y_dev.p, a.Y, static_cast<size_t>(k) * N * sizeof(T), hipMemcpyHostToDevice, st));
-        loo_dev.alloc_zero(static_cast<size_t>(k) * ld, st);
-    }
+    if (with_y) loo_dev.alloc_zero(static_cast<size_t>(k) * ld, st);
     slab.alloc_zero(static_cast<size_t>(cols) * ld, st);
     h_dev.alloc_zero(ld, st);
     f_dev.alloc_zero(static_cast<size_t>(std::max(k, 1)) * ld, st);
     std::vector<double> h_host(ld), f_host(static_cast<size_t>(k) * ld), loo_host(with_y ? static_cast<size_t>(k) * ld : 0);
 
-    const lssvm_params &prm = p.params_;
-    const double scale2 = p.x_scale_ * p.x_scale_;
-    const double gamma = prm.kernel_type == LSSVM_KERNEL_LINEAR ? 1.0 / scale2 : static_cast<double>(static_cast<T>(prm.gamma)) / scale2;
     Event ev[2];
     for (Event &e : ev) e.create(true);
     a.max_leverage.assign(a.num_ops, 0.0);
     a.leverage_ms.assign(a.num_ops, 0.0);
     a.landmark_ms = 0.0;
-    a.slabs = static_cast<uint64_t>(slabs);
     if (a.press != nullptr) std::fill(a.press, a.press + a.num_ops * k, 0.0);
     if (a.errors != nullptr) std::fill(a.errors, a.errors + a.num_ops * k, uint64_t{ 0 });
     const T *Yh = static_cast<const T *>(a.Y);
-    for (int s = 0; s < slabs; ++s) {
-        const size_t row0 = static_cast<size_t>(s) * ld;
-        const int rows = static_cast<int>(std::min(ld, N - row0)), rows256 = round_up(rows, 256);
+    for (int s = 0; s < plan.slabs; ++s) {
+        const size_t row0 = plan.row0(s);
+        const int rows = plan.rows(s);
         LSSVM_HIP_CHECK(hipEventRecord(ev[0].e, st));
-        hipLaunchKernelGGL(k_landmark_block<T>, dim3(rows256 / 256, (m + 15) / 16), dim3(256), 0, st, p.X_.data.p, p.X_.ldx, static_cast<int>(N), static_cast<int>(row0), lm_dev.p, m,
-                           prm.kernel_type, prm.degree, gamma, static_cast<double>(static_cast<T>(prm.coef0)), slab.p, ld);
-        if (with_y) hipLaunchKernelGGL(k_reduced_aux<T>, dim3(rows256 / 256, 1 + k), dim3(256), 0, st, Y_dev.p, N, row0, slab.p + static_cast<size_t>(m) * ld, ld);
+        enqueue_slab(block, m, plan, s, rhs, slab.p, st);
         LSSVM_HIP_CHECK(hipGetLastError());
         LSSVM_HIP_CHECK(hipEventRecord(ev[1].e, st));
         LSSVM_HIP_CHECK(hipEventSynchronize(ev[1].e));
         a.landmark_ms += elapsed_ms(ev[0], ev[1]);
         for (size_t o = 0; o < a.num_ops; ++o) {
             LSSVM_HIP_CHECK(hipEventRecord(ev[0].e, st));
-            hipLaunchKernelGGL(k_reduced_leverage, dim3(rows256 / RG_TW), dim3(256), 0, st, slab.p, ld, rows, m, k, a.Bt_dev + o * a.op_stride, a.ldb, a.shift_dev,
-                               a.ybar_dev != nullptr ? a.ybar_dev + o * k : nullptr, a.inv_n, with_y ? slab.p + static_cast<size_t>(m + 1) * ld : nullptr, h_dev.p, f_dev.p,
-                               with_y ? loo_dev.p : nullptr, ld);
-            LSSVM_HIP_CHECK(hipGetLastError());
+            a.enqueue(o, slab.p, ld, rows, h_dev.p, f_dev.p, loo_dev.p);
             LSSVM_HIP_CHECK(hipEventRecord(ev[1].e, st));
             LSSVM_HIP_CHECK(hipMemcpyAsync(h_host.data(), h_dev.p, static_cast<size_t>(rows) * sizeof(double), hipMemcpyDeviceToHost, st));
             for (int c = 0; c < k; ++c) {
@@ -687,16 +712,7 @@ void Solver<T>::fit_reduced_loo(const void *Y, size_t num_rhs, uint64_t rank, co
     const SetOnExit<bool> busy = hold_busy();
     p.activate();
     hipStream_t st = p.stream();
-    LeverageArgs a;
-    a.m = m;
-    a.k = k;
-    a.ldb = round_up(m, RG_KC);
-    a.num_ops = num_costs;
-    a.op_stride = static_cast<size_t>(m + k) * a.ldb;
-    DevBuf<double> Bt_dev, shift_dev, ybar_dev;
-    Bt_dev.alloc_zero(a.num_ops * a.op_stride, st);
-    shift_dev.alloc_zero(static_cast<size_t>(m), st);
-    ybar_dev.alloc_zero(a.num_ops * k, st);
+    LeverageArgs a(m, k, num_costs, true, st);
 
     // ---- per cost, on the host in double: M_s, L_s, beta and rho as fit_reduced forms them, V_s = L_s^-1; the operand of the cost goes to the device once ----
     const double *s_row = &St[static_cast<size_t>(m) * cols];
@@ -707,7 +723,7 @@ void Solver<T>::fit_reduced_loo(const void *Y, size_t num_rhs, uint64_t rank, co
         nus[s] = factor_reduced(St, Kmm, m, cols, Nd, 1.0 / costs[s], L);
         double *betas = betas_out + s * k * m;
         solve_reduced(St, L, m, k, cols, Nd, betas, rhos_out + s * k);
-        invert_lower(L, m, Bt.data(), static_cast<size_t>(a.ldb));
+        invert_lower_rows(L, m, Bt.data(), static_cast<size_t>(a.ldb));
         for (int c = 0; c < k; ++c) {
             double *row = &Bt[static_cast<size_t>(m + c) * a.ldb];
             std::fill(row, row + a.ldb, 0.0);
@@ -715,16 +731,11 @@ void Solver<T>::fit_reduced_loo(const void *Y, size_t num_rhs, uint64_t rank, co
             ybar[s * k + c] = St[static_cast<size_t>(m + 1 + c) * cols + m] / Nd;
         }
         host_ms[s] = now_ms() - t_host;
-        LSSVM_HIP_CHECK(hipMemcpyAsync(Bt_dev.p + s * a.op_stride, Bt.data(), a.op_stride * sizeof(double), hipMemcpyHostToDevice, st));
+        a.upload_operand(s, Bt.data());
         LSSVM_HIP_CHECK(hipStreamSynchronize(st));  // (Bt is filled again for the next cost)
     }
-    LSSVM_HIP_CHECK(hipMemcpyAsync(shift_dev.p, shift.data(), shift.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    LSSVM_HIP_CHECK(hipMemcpyAsync(ybar_dev.p, ybar.data(), ybar.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    LSSVM_HIP_CHECK(hipStreamSynchronize(st));
+    a.upload_shift(shift.data(), ybar.data());
 
-    a.Bt_dev = Bt_dev.p;
-    a.shift_dev = shift_dev.p;
-    a.ybar_dev = ybar_dev.p;
     a.inv_n = 1.0 / Nd;
     a.Y = Y;
     a.h_out = leverage_out;
@@ -753,11 +764,7 @@ template <typename T>
 void Solver<T>::reduced_leverage(uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *V, const double *shift, const double *B_extra, size_t num_extra, double *h_out,
                                  double *f_out) {
     // ---- everything that needs no device (as reduced_gram) ----
-    const char *what = "reduced_leverage";
-    LSSVM_REQUIRE(shards_.size() == 1 && world_ == 1 && exchange_ == Exchange::none, std::string("the reduced model (") + what + ") is fitted on a problem of one device and one rank");
-    Problem<T> &p = *shards_[0];
-    LSSVM_REQUIRE(!p.weighted_, std::string("the reduced model (") + what + ") is fitted to the unweighted objective: the problem has weights set (lssvm_mi355_problem_set_weights(p, NULL, 0) removes them)");
-    LSSVM_REQUIRE(!in_cg_, std::string(what) + " cannot run between cg_begin and cg_finish");
+    Problem<T> &p = reduced_problem("reduced_leverage", true);
     check_reduced_arguments(V, 1, rank, slab_rows, p.N_);
     LSSVM_REQUIRE(V != nullptr && shift != nullptr && h_out != nullptr, "V / shift / h_out must not be NULL");
     LSSVM_REQUIRE(num_extra <= 4096 && (num_extra == 0 || (B_extra != nullptr && f_out != nullptr)), "at most 4096 extra columns; B_extra / f_out must not be NULL where there are some");
@@ -766,25 +773,13 @@ void Solver<T>::reduced_leverage(uint64_t rank, const uint64_t *landmarks, uint6
 
     const SetOnExit<bool> busy = hold_busy();
     p.activate();
-    hipStream_t st = p.stream();
-    LeverageArgs a;
-    a.m = m;
-    a.k = k;
-    a.ldb = round_up(m, RG_KC);
-    a.num_ops = 1;
-    a.op_stride = static_cast<size_t>(m + k) * a.ldb;
+    LeverageArgs a(m, k, 1, false, p.stream());
     std::vector<double> Bt(a.op_stride, 0.0);
     for (int n = 0; n < m; ++n) std::copy(V + static_cast<size_t>(n) * m, V + static_cast<size_t>(n + 1) * m, &Bt[static_cast<size_t>(n) * a.ldb]);  // (as given, what stands above the diagonal too: the kernel masks it)
     for (int c = 0; c < k; ++c)
         for (int j = 0; j < m; ++j) Bt[static_cast<size_t>(m + c) * a.ldb + j] = B_extra[static_cast<size_t>(j) * k + c];
-    DevBuf<double> Bt_dev, shift_dev;
-    Bt_dev.alloc_zero(a.op_stride, st);
-    shift_dev.alloc_zero(static_cast<size_t>(m), st);
-    LSSVM_HIP_CHECK(hipMemcpyAsync(Bt_dev.p, Bt.data(), Bt.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    LSSVM_HIP_CHECK(hipMemcpyAsync(shift_dev.p, shift, static_cast<size_t>(m) * sizeof(double), hipMemcpyHostToDevice, st));
-    LSSVM_HIP_CHECK(hipStreamSynchronize(st));
-    a.Bt_dev = Bt_dev.p;
-    a.shift_dev = shift_dev.p;
+    a.upload_operand(0, Bt.data());
+    a.upload_shift(shift, nullptr);
     a.h_out = h_out;
     a.f_out = f_out;
     leverage_pass(lm, slab_rows, a);
@@ -792,10 +787,7 @@ void Solver<T>::reduced_leverage(uint64_t rank, const uint64_t *landmarks, uint6
 
 template <typename T>
 void Solver<T>::time_leverage_kernel(uint64_t rank, uint64_t slab_rows, size_t num_extra, int repeats, double *gram_ms_out, double *leverage_ms_out) {
-    const char *what = "time_leverage_kernel";
-    LSSVM_REQUIRE(shards_.size() == 1 && world_ == 1 && exchange_ == Exchange::none, std::string("the reduced model (") + what + ") is fitted on a problem of one device and one rank");
-    Problem<T> &p = *shards_[0];
-    LSSVM_REQUIRE(!in_cg_, std::string(what) + " cannot run between cg_begin and cg_finish");
+    Problem<T> &p = reduced_problem("time_leverage_kernel", false);  // (the aid times kernels on the data: the weights do not enter)
     LSSVM_REQUIRE(repeats >= 1 && repeats <= 1000 && gram_ms_out != nullptr && leverage_ms_out != nullptr, "repeats must lie in [1, 1000]; gram_ms_out / leverage_ms_out must not be NULL");
     LSSVM_REQUIRE(num_extra >= 1 && num_extra <= 64, "between 1 and 64 extra columns");
     const size_t N = p.N_;
@@ -806,57 +798,30 @@ void Solver<T>::time_leverage_kernel(uint64_t rank, uint64_t slab_rows, size_t n
     const SetOnExit<bool> busy = hold_busy();
     p.activate();
     hipStream_t st = p.stream();
-    const size_t N256 = static_cast<size_t>(round_up(static_cast<long>(N), 256));
-    const size_t ld = std::min<size_t>(slab_rows == 0 ? REDUCED_DEFAULT_SLAB_ROWS : slab_rows, N256);
-    const int rows = static_cast<int>(std::min(ld, N)), rows256 = round_up(rows, 256);
-    const int nt = tiles_of(cols), ntri = nt * (nt + 1) / 2, max_chunks = static_cast<int>((ld + RG_RANGE - 1) / RG_RANGE), ldb = round_up(m, RG_KC);
-    std::vector<int> lm_host(lm.begin(), lm.end());
-    std::vector<double> Bt(static_cast<size_t>(m + k) * ldb, 0.0);
-    for (int n = 0; n < m + k; ++n)
-        for (int j = 0; j < m; ++j) Bt[static_cast<size_t>(n) * ldb + j] = n >= m || n == j ? 1.0 : 0.0;
-    std::vector<T> Yh(static_cast<size_t>(k) * N, T(1));
-    DevBuf<int> lm_dev;
-    DevBuf<T> Y_dev;
-    DevBuf<double> slab, part, St_dev, Bt_dev, shift_dev, h_dev, f_dev, loo_dev;
-    lm_dev.alloc_zero(static_cast<size_t>(m), st);
-    LSSVM_HIP_CHECK(hipMemcpyAsync(lm_dev.p, lm_host.data(), static_cast<size_t>(m) * sizeof(int), hipMemcpyHostToDevice, st));
-    Y_dev.alloc_zero(Yh.size(), st);
-    LSSVM_HIP_CHECK(hipMemcpyAsync(Y_dev.p, Yh.data(), Yh.size() * sizeof(T), hipMemcpyHostToDevice, st));
+    const SlabPlan plan(N, slab_rows);  // (the first slab alone)
+    const size_t ld = plan.ld;
+    const int nt = tiles_of(cols), ntri = nt * (nt + 1) / 2, max_chunks = static_cast<int>((ld + RG_RANGE - 1) / RG_RANGE);
+    const std::vector<T> Yh(static_cast<size_t>(k) * N, T(1));
+    const LandmarkBlock<T> block(p, lm, st);
+    const RhsOnDevice<T> rhs(Yh.data(), k, N, st);
+    DevBuf<double> slab, part, St_dev, h_dev, f_dev, loo_dev;
     slab.alloc_zero(static_cast<size_t>(cols) * ld, st);
     part.alloc_zero(static_cast<size_t>(ntri) * max_chunks * RG_TILE, st);
     St_dev.alloc_zero(static_cast<size_t>(ntri) * RG_TILE, st);
-    Bt_dev.alloc_zero(Bt.size(), st);
-    LSSVM_HIP_CHECK(hipMemcpyAsync(Bt_dev.p, Bt.data(), Bt.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    shift_dev.alloc_zero(static_cast<size_t>(m), st);
+    LeverageArgs a(m, k, 1, false, st);  // V = I, every extra column of ones, shift = 0
+    std::vector<double> Bt(a.op_stride, 0.0);
+    for (int n = 0; n < m + k; ++n)
+        for (int j = 0; j < m; ++j) Bt[static_cast<size_t>(n) * a.ldb + j] = n >= m || n == j ? 1.0 : 0.0;
+    a.upload_operand(0, Bt.data());
+    a.inv_n = 1.0 / static_cast<double>(N);
     h_dev.alloc_zero(ld, st);
     f_dev.alloc_zero(static_cast<size_t>(k) * ld, st);
     loo_dev.alloc_zero(static_cast<size_t>(k) * ld, st);
-    const lssvm_params &prm = p.params_;
-    const double scale2 = p.x_scale_ * p.x_scale_;
-    const double gamma = prm.kernel_type == LSSVM_KERNEL_LINEAR ? 1.0 / scale2 : static_cast<double>(static_cast<T>(prm.gamma)) / scale2;
-    hipLaunchKernelGGL(k_landmark_block<T>, dim3(rows256 / 256, (m + 15) / 16), dim3(256), 0, st, p.X_.data.p, p.X_.ldx, static_cast<int>(N), 0, lm_dev.p, m, prm.kernel_type, prm.degree,
-                       gamma, static_cast<double>(static_cast<T>(prm.coef0)), slab.p, ld);
-    hipLaunchKernelGGL(k_reduced_aux<T>, dim3(rows256 / 256, 1 + k), dim3(256), 0, st, Y_dev.p, N, size_t{ 0 }, slab.p + static_cast<size_t>(m) * ld, ld);
+    enqueue_slab(block, m, plan, 0, rhs, slab.p, st);
     LSSVM_HIP_CHECK(hipGetLastError());
-    Event ev[2];
-    for (Event &e : ev) e.create(true);
-    for (int rep = -1; rep < repeats; ++rep) {  // (-1: the untimed run)
-        LSSVM_HIP_CHECK(hipMemsetAsync(St_dev.p, 0, St_dev.count * sizeof(double), st));
-        LSSVM_HIP_CHECK(hipEventRecord(ev[0].e, st));
-        enqueue_gram(slab.p, ld, cols, rows256, max_chunks, part.p, St_dev.p, st);
-        LSSVM_HIP_CHECK(hipEventRecord(ev[1].e, st));
-        LSSVM_HIP_CHECK(hipEventSynchronize(ev[1].e));
-        if (rep >= 0) gram_ms_out[rep] = elapsed_ms(ev[0], ev[1]);
-    }
-    for (int rep = -1; rep < repeats; ++rep) {
-        LSSVM_HIP_CHECK(hipEventRecord(ev[0].e, st));
-        hipLaunchKernelGGL(k_reduced_leverage, dim3(rows256 / RG_TW), dim3(256), 0, st, slab.p, ld, rows, m, k, Bt_dev.p, ldb, shift_dev.p, static_cast<const double *>(nullptr), 1.0 / static_cast<double>(N),
-                           slab.p + static_cast<size_t>(m + 1) * ld, h_dev.p, f_dev.p, loo_dev.p, ld);
-        LSSVM_HIP_CHECK(hipGetLastError());
-        LSSVM_HIP_CHECK(hipEventRecord(ev[1].e, st));
-        LSSVM_HIP_CHECK(hipEventSynchronize(ev[1].e));
-        if (rep >= 0) leverage_ms_out[rep] = elapsed_ms(ev[0], ev[1]);
-    }
+    timed_repeats(st, repeats, gram_ms_out, [&] { LSSVM_HIP_CHECK(hipMemsetAsync(St_dev.p, 0, St_dev.count * sizeof(double), st)); },
+                  [&] { enqueue_gram(slab.p, ld, cols, plan.rows256(0), max_chunks, part.p, St_dev.p, st); });
+    timed_repeats(st, repeats, leverage_ms_out, [] {}, [&] { a.enqueue(0, slab.p, ld, plan.rows(0), h_dev.p, f_dev.p, loo_dev.p); });
 }
 
 template <typename T>
@@ -878,24 +843,9 @@ void Solver<T>::time_gram_kernels(int repeats, double *parent_ms_out, double *mf
         G_dev.alloc_zero(static_cast<size_t>(ldg) * ldg, st);
         part.alloc_zero(static_cast<size_t>(ntri) * max_chunks * RG_TILE, st);
         St_dev.alloc_zero(static_cast<size_t>(ntri) * RG_TILE, st);
-        Event ev[2];
-        for (Event &e : ev) e.create(true);
-        for (int rep = -1; rep < repeats; ++rep) {  // (-1: the untimed run)
-            LSSVM_HIP_CHECK(hipEventRecord(ev[0].e, st));
-            hipLaunchKernelGGL(k_precond_gram<T>, dim3(tiles16, tiles16), dim3(256), 0, st, pc.Bhat.p, pc.ldn, cols, G_dev.p, ldg);
-            LSSVM_HIP_CHECK(hipGetLastError());
-            LSSVM_HIP_CHECK(hipEventRecord(ev[1].e, st));
-            LSSVM_HIP_CHECK(hipEventSynchronize(ev[1].e));
-            if (rep >= 0) parent_ms_out[rep] = elapsed_ms(ev[0], ev[1]);
-        }
-        for (int rep = -1; rep < repeats; ++rep) {
-            LSSVM_HIP_CHECK(hipMemsetAsync(St_dev.p, 0, St_dev.count * sizeof(double), st));
-            LSSVM_HIP_CHECK(hipEventRecord(ev[0].e, st));
-            enqueue_gram(pc.Bhat.p, pc.ldn, cols, rows, max_chunks, part.p, St_dev.p, st);
-            LSSVM_HIP_CHECK(hipEventRecord(ev[1].e, st));
-            LSSVM_HIP_CHECK(hipEventSynchronize(ev[1].e));
-            if (rep >= 0) mfma_ms_out[rep] = elapsed_ms(ev[0], ev[1]);
-        }
+        timed_repeats(st, repeats, parent_ms_out, [] {}, [&] { hipLaunchKernelGGL(k_precond_gram<T>, dim3(tiles16, tiles16), dim3(256), 0, st, pc.Bhat.p, pc.ldn, cols, G_dev.p, ldg); });
+        timed_repeats(st, repeats, mfma_ms_out, [&] { LSSVM_HIP_CHECK(hipMemsetAsync(St_dev.p, 0, St_dev.count * sizeof(double), st)); },
+                      [&] { enqueue_gram(pc.Bhat.p, pc.ldn, cols, rows, max_chunks, part.p, St_dev.p, st); });
         if (max_diff_out != nullptr) {
             std::vector<double> Gpad(static_cast<size_t>(ldg) * ldg), tiles(static_cast<size_t>(ntri) * RG_TILE), G;
             LSSVM_HIP_CHECK(hipMemcpyAsync(Gpad.data(), G_dev.p, Gpad.size() * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -914,16 +864,10 @@ void Solver<T>::time_gram_kernels(int repeats, double *parent_ms_out, double *mf
     }
 }
 
-template void Solver<float>::reduced_gram(const char *, const void *, size_t, uint64_t, const uint64_t *, uint64_t, std::vector<uint64_t> &, std::vector<double> &, std::vector<double> &,
-                                          lssvm_reduced_info &);
-template void Solver<double>::reduced_gram(const char *, const void *, size_t, uint64_t, const uint64_t *, uint64_t, std::vector<uint64_t> &, std::vector<double> &, std::vector<double> &,
-                                           lssvm_reduced_info &);
 template void Solver<float>::landmark_gram(const void *, size_t, uint64_t, const uint64_t *, uint64_t, double *);
 template void Solver<double>::landmark_gram(const void *, size_t, uint64_t, const uint64_t *, uint64_t, double *);
 template void Solver<float>::fit_reduced(const void *, size_t, uint64_t, const uint64_t *, uint64_t, double *, double *, uint64_t *, lssvm_reduced_info *);
 template void Solver<double>::fit_reduced(const void *, size_t, uint64_t, const uint64_t *, uint64_t, double *, double *, uint64_t *, lssvm_reduced_info *);
-template void Solver<float>::leverage_pass(const std::vector<uint64_t> &, uint64_t, LeverageArgs &);
-template void Solver<double>::leverage_pass(const std::vector<uint64_t> &, uint64_t, LeverageArgs &);
 template void Solver<float>::fit_reduced_loo(const void *, size_t, uint64_t, const uint64_t *, uint64_t, const double *, size_t, double *, double *, double *, double *, double *, double *, uint64_t *,
                                              uint64_t *, lssvm_reduced_loo_info *);
 template void Solver<double>::fit_reduced_loo(const void *, size_t, uint64_t, const uint64_t *, uint64_t, const double *, size_t, double *, double *, double *, double *, double *, double *, uint64_t *,
@@ -936,3 +880,4 @@ template void Solver<float>::time_gram_kernels(int, double *, double *, double *
 template void Solver<double>::time_gram_kernels(int, double *, double *, double *);
 
 }  // namespace lssvm
+
