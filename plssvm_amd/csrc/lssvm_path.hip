@@ -10,7 +10,8 @@
  * THE STOP TEST IS NOT THE REFERENCE RECIPE'S.  cg_begin / cg_step start from x0 = 1 and stop at |r|^2 <= eps^2 |b - A 1|^2 in the 2-norm.  The path starts from
  * x0 = 0 and freezes shift s at zeta_s^2 |r|^2 <= eps^2 |P b|^2: the residual of cost s in the norm of M^-1, relative to the right-hand side in that norm.
  *
- * The kernels launched here are the path's own (below); the Gram pass is launched, not changed.  Compiled for gfx950 only.
+ * The kernels launched here are the path's own (below); the Gram pass is launched, not changed -- the verification's too (enqueue_apply_K_lanes where the two-vector
+ * kernel applies: the same walk over the row-block bands, Problem::enqueue_sym_walk, so a verified residual is that of the pass the iteration ran).  Compiled for gfx950 only.
  */
 #include "lssvm_problem.hip.hpp"
 

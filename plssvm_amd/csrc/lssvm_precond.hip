@@ -11,8 +11,8 @@
  * column, so (a) and (c) each read it exactly once, 16 bytes per lane along a column.  Every reduction has a fixed order: the same bits for the same arguments.
  *
  * PCG keeps the frame of cg_begin / cg_step: x0 = 1, r0 = b - Abar 1, the stop test |r|^2 <= eps^2 |r0|^2 on the unpreconditioned recurrence residual, the true residual
- * every 50th iteration.  Ad, alpha, x and r are the recipe's own kernels (k_Ad_and_dAd, k_update_x_r, k_residual: alpha's numerator r.z stands in the scalar slot they
- * read); only the direction update is new.  The Gram pass is launched, not changed.  Compiled for gfx950 only.
+ * every 50th iteration.  Ad, alpha, x and r are the recipe's own steps (CgSteps::advance and ::residual, which launch the recipe's kernels: alpha's numerator r.z stands in the
+ * scalar set advance is handed); only the direction update is launched here.  The Gram pass (Problem::enqueue_apply_K_local) is launched, not changed.  Compiled for gfx950 only.
  */
 #include "lssvm_landmark.hip.hpp"
 
@@ -537,11 +537,8 @@ void Solver<T>::solve_pcg(const void *Y, size_t num_rhs, double eps, uint64_t ma
             const bool refresh = iterations % 50 == 49;
             p.enqueue_apply_K_local(s.d.p, false);
             ++gram_passes;
-            hipLaunchKernelGGL((k_Ad_and_dAd<T, false>), gr, br, 0, st, p.Kres_, s.d.p, q, s.part_of(PART_D), s.sc.p, n, p.inv_cost_, p.QA_cost_, s.Ad.p, s.part_of(PART_DAD));
-            hipLaunchKernelGGL(k_update_x_r<T>, gr, br, 0, st, s.x.p, s.r.p, s.d.p, s.Ad.p, s.part_of(PART_DAD), sc_now, n, refresh ? 0 : 1, s.part_of(PART_RR));
-            LSSVM_HIP_CHECK(hipGetLastError());
+            cg.advance(s, p.Kres_, refresh, sc_now);  // (alpha's numerator is r.z of this iteration's set)
             if (refresh) {  // r = b - Abar x
-                cg.sum_and_qdot(s, s.x.p, SC_SUMX, SC_QX);
                 p.enqueue_apply_K_local(s.x.p, false);
                 ++gram_passes;
                 cg.residual(s, p.Kres_, s.x.p, s.r.p, PART_RR);

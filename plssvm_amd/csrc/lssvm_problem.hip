@@ -1142,6 +1142,72 @@ void Problem<T>::drain_events() {
     }
 }
 
+/* the single-vector records of a problem's pass: rbf on grid planes carries E_j, the other forms the folded or plain (d_j | c_j) */
+template <typename T>
+void Problem<T>::enqueue_pack_dc(const T *v, T *zero, int nzero) {
+    const int ncols = num_tiles_ * TILE;
+    const int nthreads = std::max(ncols, nzero);
+    if constexpr (std::is_same_v<T, float>) {
+        hipLaunchKernelGGL(k_pack_dc, dim3((nthreads + 255) / 256), dim3(256), 0, stream_.s, v, c_.p, ncols, dc_.p, rbf_grid_ ? 2 : (dc_folded_ ? 1 : 0), zero, nzero, rbf_grid_ ? efac_.p : static_cast<const float *>(nullptr));
+    } else {
+        hipLaunchKernelGGL(k_pack_dc_f64, dim3((nthreads + 255) / 256), dim3(256), 0, stream_.s, v, c_.p, ncols, dc_.p, zero, nzero);
+    }
+}
+
+template <typename T>
+template <typename Around>
+void Problem<T>::enqueue_sym_walk(const TileArgs<T> &a, int nv, T *const *Kv, int npanels, Around &&around) {
+    hipStream_t st = stream_.s;
+    const int nrows = num_ib_ * TILE;
+    // wide linear problems: one pass per panel of LINEAR_PANEL_FEATURES features, every pass ADDS its K_p * v (rows and mirrored columns) into K*v
+    const int panel_features = LINEAR_PANEL_FEATURES;
+    for (int panel = 0; panel < npanels; ++panel) {
+        TileArgs<T> ap = a;
+        if constexpr (std::is_same_v<T, float>) {
+            if (wide_linear_) {
+                if (ap.Xr16f != nullptr) ap.Xr16f += static_cast<size_t>(panel) * (panel_features / 64) * (X_.rows_alloc / 16) * 1024;  // (the 64-feature chunk is the outermost index of a plane)
+                ap.Xr16 += static_cast<size_t>(panel) * panel_features;
+                ap.Xc16 += static_cast<size_t>(panel) * panel_features;
+                ap.nk64 = std::min(panel_features, planes_.ldx16 - panel * panel_features) / 64;
+            }
+        } else {
+            if (wide_linear_) {  // (row-major fp64 data: a panel is a column range of X, the row stride stays)
+                ap.Xr += static_cast<size_t>(panel) * panel_features;
+                ap.Xc += static_cast<size_t>(panel) * panel_features;
+                ap.kchunks = std::min(panel_features, X_.ldx - panel * panel_features) / F64_KC;
+            }
+        }
+        for (const Band &band : bands_) {
+            TileArgs<T> ab = ap;
+            ab.items = items_.p + band.item_begin;
+            ab.num_items = band.item_count;
+            ab.pair_origin = band.pair_origin;
+            if (queue_.p != nullptr && band.item_count > queue_min_items_) {  // (a launch of no more items than CUs: one workgroup per item, no counters -- 2 % faster there)
+                ab.queue = queue_.p + 256 * queue_set_;
+                ab.queue_next = queue_.p + 256 * (1 - queue_set_);
+                ab.queue_grid = queue_min_items_;
+                queue_set_ ^= 1;
+            }
+            around([&]() { launch_tile_kernel<T>(ab, tile_params_.kernel_type, rbf_direct_, num_jc_, st); }, panel == 0 && &band == &bands_.front(), panel == npanels - 1 && &band == &bands_.back());
+            // fold the band's mirrored column sums into K*v before the next band re-uses the slab
+            if (band.ib_end > 1) {
+                for (int u = 0; u < nv; ++u) {
+                    if constexpr (std::is_same_v<T, float>) {
+                        // (block pairs: one record per pair and column tile, kept as the record of the pair's second -- odd -- block)
+                        hipLaunchKernelGGL((k_reduce_colslab<T, 128>), dim3(band.ib_end - 1), dim3(1024), 0, st, a.colslab + u * a.colslab_vstride, band.pair_origin, band.ib_begin, pair_ ? round_up(band.ib_end, 2) : band.ib_end, pair_ ? 2 : 1, Kv[u], rbf_grid_ ? efac_.p : static_cast<const T *>(nullptr));
+                    } else {  // fp64: records per 64-column sub-tile
+                        hipLaunchKernelGGL((k_reduce_colslab<T, 64>), dim3(2 * (band.ib_end - 1)), dim3(1024), 0, st, a.colslab + u * a.colslab_vstride, band.pair_origin, band.ib_begin, band.ib_end, 1, Kv[u]);
+                    }
+                }
+            }
+        }
+        // rows of this device's blocks: the slabs of the column chunks that exist for each block, added on top
+        for (int u = 0; u < nv; ++u) {
+            hipLaunchKernelGGL(k_reduce_partials_sym<T>, dim3((nrows + 255) / 256), dim3(256), 0, st, a.partial + u * a.part_vstride, a.part_stride, jc_tiles_, jc_head_tiles_, jc_head_count_, ib_begin_, nrows, Kv[u], 1);
+        }
+    }
+}
+
 template <typename T>
 void Problem<T>::enqueue_apply_K_local(const T *v_dev, bool zero_first) {
     // this shard's part of the implicit K * v: tile kernel over its row blocks (band by band), slabs added in a fixed order
@@ -1176,71 +1242,20 @@ void Problem<T>::enqueue_apply_K_local(const T *v_dev, bool zero_first) {
     if (clear && !pack && !prepacked) LSSVM_HIP_CHECK(hipMemsetAsync(Kv_.p, 0, static_cast<size_t>(nvec_) * sizeof(T), st));
     if (num_ib_ <= 0) return;
     TileArgs<T> a = tile_args(v_dev);
-    if (pack) {  // v2 kernels: pack (d_j | c_j) records for the LDS-DMA
-        const int ncols = num_tiles_ * TILE;
-        const int nzero = clear ? static_cast<int>(nvec_) : 0;
-        const int nthreads = std::max(ncols, nzero);
-        if constexpr (std::is_same_v<T, float>) {
-            hipLaunchKernelGGL(k_pack_dc, dim3((nthreads + 255) / 256), dim3(256), 0, st, v_dev, c_.p, ncols, dc_.p, rbf_grid_ ? 2 : a.dc_folded, Kv_.p, nzero, rbf_grid_ ? efac_.p : static_cast<const float *>(nullptr));
-        } else {
-            hipLaunchKernelGGL(k_pack_dc_f64, dim3((nthreads + 255) / 256), dim3(256), 0, st, v_dev, c_.p, ncols, dc_.p, Kv_.p, nzero);
-        }
-    }
-    const int nrows = num_ib_ * TILE;
-    // wide linear problems: one pass per panel of 512 features, every pass ADDS its K_p * v (rows and mirrored columns) into K*v
-    const int npanels = passes_per_matvec();
-    const int panel_features = LINEAR_PANEL_FEATURES;
+    if (pack) enqueue_pack_dc(v_dev, Kv_.p, clear ? static_cast<int>(nvec_) : 0);  // v2 kernels: (d_j | c_j) records for the LDS-DMA
     if (sym_) {
-        bool first = true;
-        for (int panel = 0; panel < npanels; ++panel) {
-            TileArgs<T> ap = a;
-            if constexpr (std::is_same_v<T, float>) {
-                if (wide_linear_) {
-                    if (ap.Xr16f != nullptr) ap.Xr16f += static_cast<size_t>(panel) * (panel_features / 64) * (X_.rows_alloc / 16) * 1024;  // (the 64-feature chunk is the outermost index of a plane)
-                    ap.Xr16 += static_cast<size_t>(panel) * panel_features;
-                    ap.Xc16 += static_cast<size_t>(panel) * panel_features;
-                    ap.nk64 = std::min(panel_features, planes_.ldx16 - panel * panel_features) / 64;
-                }
-            } else {
-                if (wide_linear_) {  // (row-major fp64 data: a panel is a column range of X, the row stride stays)
-                    ap.Xr += static_cast<size_t>(panel) * panel_features;
-                    ap.Xc += static_cast<size_t>(panel) * panel_features;
-                    ap.kchunks = std::min(panel_features, X_.ldx - panel * panel_features) / F64_KC;
-                }
+        T *const Kv[1] = { Kv_.p };
+        // (sampled events around every band launch of every feature panel; the matvec is counted once, at its first launch)
+        enqueue_sym_walk(a, 1, Kv, passes_per_matvec(), [&](auto &&launch, bool first, bool) {
+            EvPair *ev = free_event();
+            if (ev != nullptr) LSSVM_HIP_CHECK(hipEventRecord(ev->a.e, st));
+            launch();
+            if (ev != nullptr) {
+                LSSVM_HIP_CHECK(hipEventRecord(ev->b.e, st));
+                ev->pending = true;
+                ev->first_of_matvec = first;
             }
-            for (const Band &band : bands_) {
-                TileArgs<T> ab = ap;
-                ab.items = items_.p + band.item_begin;
-                ab.num_items = band.item_count;
-                ab.pair_origin = band.pair_origin;
-                if (queue_.p != nullptr && band.item_count > queue_min_items_) {  // (a launch of no more items than CUs: one workgroup per item, no counters -- 2 % faster there)
-                    ab.queue = queue_.p + 256 * queue_set_;
-                    ab.queue_next = queue_.p + 256 * (1 - queue_set_);
-                    ab.queue_grid = queue_min_items_;
-                    queue_set_ ^= 1;
-                }
-                EvPair *ev = free_event();
-                if (ev != nullptr) LSSVM_HIP_CHECK(hipEventRecord(ev->a.e, st));
-                launch_tile_kernel<T>(ab, tile_params_.kernel_type, rbf_direct_, num_jc_, st);
-                if (ev != nullptr) {
-                    LSSVM_HIP_CHECK(hipEventRecord(ev->b.e, st));
-                    ev->pending = true;
-                    ev->first_of_matvec = first;
-                }
-                first = false;
-                // fold the band's mirrored column sums into K*v before the next band re-uses the slab
-                if (band.ib_end > 1) {
-                    if constexpr (std::is_same_v<T, float>) {
-                        // (block pairs: one record per pair and column tile, kept as the record of the pair's second -- odd -- block)
-                        hipLaunchKernelGGL((k_reduce_colslab<T, 128>), dim3(band.ib_end - 1), dim3(1024), 0, st, colslab_.p, band.pair_origin, band.ib_begin, pair_ ? round_up(band.ib_end, 2) : band.ib_end, pair_ ? 2 : 1, Kv_.p, rbf_grid_ ? efac_.p : static_cast<const T *>(nullptr));
-                    } else {  // fp64: records per 64-column sub-tile
-                        hipLaunchKernelGGL((k_reduce_colslab<T, 64>), dim3(2 * (band.ib_end - 1)), dim3(1024), 0, st, colslab_.p, band.pair_origin, band.ib_begin, band.ib_end, 1, Kv_.p);
-                    }
-                }
-            }
-            // rows of this device's blocks: the slabs of the column chunks that exist for each block, added on top
-            hipLaunchKernelGGL(k_reduce_partials_sym<T>, dim3((nrows + 255) / 256), dim3(256), 0, st, partial_.p, a.part_stride, jc_tiles_, jc_head_tiles_, jc_head_count_, ib_begin_, nrows, Kv_.p, 1);
-        }
+        });
     } else {
         EvPair *ev = free_event();
         if (ev != nullptr) LSSVM_HIP_CHECK(hipEventRecord(ev->a.e, st));
@@ -1250,6 +1265,7 @@ void Problem<T>::enqueue_apply_K_local(const T *v_dev, bool zero_first) {
             ev->pending = true;
             ev->first_of_matvec = true;
         }
+        const int nrows = num_ib_ * TILE;
         hipLaunchKernelGGL(k_reduce_partials<T>, dim3((nrows + 255) / 256), dim3(256), 0, st, partial_.p, a.part_stride, num_jc_, ib_begin_ * TILE, nrows, Kv_.p);
     }
     if constexpr (std::is_same_v<T, float>) {
@@ -1314,67 +1330,43 @@ bool Problem<T>::pair_kernel_applies() const {
 
 template <typename T>
 void Problem<T>::enqueue_apply_K_lanes(const T *v0, T *Kv0, const T *v1, T *Kv1, hipEvent_t ev_begin, hipEvent_t ev_end) {
-    {
-        LSSVM_REQUIRE(pair_kernel_applies(), "no two-vector tile kernel on this problem");
-        hipStream_t st = stream_.s;
+    LSSVM_REQUIRE(pair_kernel_applies(), "no two-vector tile kernel on this problem");
+    hipStream_t st = stream_.s;
+    const int nzero = static_cast<int>(nvec_);  // (the symmetric variant ADDS rows and mirrored columns into K*v)
+    TileArgs<T> a = tile_args(v0);
+    if (v1 != nullptr) {
+        if (pair_dc_.p == nullptr) {
+            // fp64: (d0_j | d1_j | c_j), 192 reals per 64-column sub-tile; fp32: (w0_j | w1_j | e_j), 384 per column tile (folded rbf; the polynomial forms use 256 of them)
+            pair_dc_.alloc_zero(static_cast<size_t>(num_tiles_) * 2 * 192, st);
+            pair_partial_.alloc_zero(2 * partial_.count, st);
+            pair_colslab_.alloc_zero(2 * colslab_.count, st);
+        }
         const int ncols = num_tiles_ * TILE;
-        const int nzero = static_cast<int>(nvec_);  // (the symmetric variant ADDS rows and mirrored columns into K*v)
         const int nthreads = std::max(ncols, nzero);
-        TileArgs<T> a = tile_args(v0);
-        if (v1 != nullptr) {
-            if (pair_dc_.p == nullptr) {
-                // fp64: (d0_j | d1_j | c_j), 192 reals per 64-column sub-tile; fp32: (w0_j | w1_j | e_j), 384 per column tile (folded rbf; the polynomial forms use 256 of them)
-                pair_dc_.alloc_zero(static_cast<size_t>(num_tiles_) * 2 * 192, st);
-                pair_partial_.alloc_zero(2 * partial_.count, st);
-                pair_colslab_.alloc_zero(2 * colslab_.count, st);
-            }
-            if constexpr (std::is_same_v<T, float>) {
-                hipLaunchKernelGGL(k_pack_dc2_sym, dim3((nthreads + 255) / 256), dim3(256), 0, st, v0, v1, c_.p, ncols, pair_dc_.p, a.dc_folded, Kv0, Kv1, nzero);
-            } else {
-                hipLaunchKernelGGL(k_pack_dc2_f64, dim3((nthreads + 255) / 256), dim3(256), 0, st, v0, v1, c_.p, ncols, pair_dc_.p, Kv0, Kv1, nzero);
-            }
-            a.nvec = 2;
-            a.dvec1 = v1;
-            a.dc = pair_dc_.p;
-            a.partial = pair_partial_.p;
-            a.part_vstride = static_cast<long>(partial_.count);
-            a.colslab = pair_colslab_.p;
-            a.colslab_vstride = static_cast<long>(colslab_.count);
+        if constexpr (std::is_same_v<T, float>) {
+            hipLaunchKernelGGL(k_pack_dc2_sym, dim3((nthreads + 255) / 256), dim3(256), 0, st, v0, v1, c_.p, ncols, pair_dc_.p, a.dc_folded, Kv0, Kv1, nzero);
         } else {
-            d_packed_ = false;  // (dc_ is about to hold another vector's records)
-            if constexpr (std::is_same_v<T, float>) {
-                hipLaunchKernelGGL(k_pack_dc, dim3((nthreads + 255) / 256), dim3(256), 0, st, v0, c_.p, ncols, dc_.p, a.dc_folded, Kv0, nzero, static_cast<const float *>(nullptr));
-            } else {
-                hipLaunchKernelGGL(k_pack_dc_f64, dim3((nthreads + 255) / 256), dim3(256), 0, st, v0, c_.p, ncols, dc_.p, Kv0, nzero);
-            }
+            hipLaunchKernelGGL(k_pack_dc2_f64, dim3((nthreads + 255) / 256), dim3(256), 0, st, v0, v1, c_.p, ncols, pair_dc_.p, Kv0, Kv1, nzero);
         }
-        const int nrows = num_ib_ * TILE;
-        T *const Kv[2] = { Kv0, Kv1 };
-        const int nv = v1 != nullptr ? 2 : 1;
-        if (ev_begin != nullptr) LSSVM_HIP_CHECK(hipEventRecord(ev_begin, st));
-        // the band loop of enqueue_apply_K_local (no feature panels here); every reduction runs per vector on that vector's planes, into that vector's K*v
-        for (const Band &band : bands_) {
-            TileArgs<T> ab = a;
-            ab.items = items_.p + band.item_begin;
-            ab.num_items = band.item_count;
-            ab.pair_origin = band.pair_origin;
-            launch_tile_kernel<T>(ab, tile_params_.kernel_type, rbf_direct_, num_jc_, st);
-            if (&band == &bands_.back() && ev_end != nullptr) LSSVM_HIP_CHECK(hipEventRecord(ev_end, st));
-            if (band.ib_end > 1) {
-                for (int u = 0; u < nv; ++u) {
-                    if constexpr (std::is_same_v<T, float>) {  // (records per column tile; fp64: per 64-column sub-tile)
-                        hipLaunchKernelGGL((k_reduce_colslab<T, 128>), dim3(band.ib_end - 1), dim3(1024), 0, st, a.colslab + u * a.colslab_vstride, band.pair_origin, band.ib_begin, band.ib_end, 1, Kv[u], static_cast<const T *>(nullptr));
-                    } else {
-                        hipLaunchKernelGGL((k_reduce_colslab<T, 64>), dim3(2 * (band.ib_end - 1)), dim3(1024), 0, st, a.colslab + u * a.colslab_vstride, band.pair_origin, band.ib_begin, band.ib_end, 1, Kv[u]);
-                    }
-                }
-            }
-        }
-        for (int u = 0; u < nv; ++u) {
-            hipLaunchKernelGGL(k_reduce_partials_sym<T>, dim3((nrows + 255) / 256), dim3(256), 0, st, a.partial + u * a.part_vstride, a.part_stride, jc_tiles_, jc_head_tiles_, jc_head_count_, ib_begin_, nrows, Kv[u], 1);
-        }
-        LSSVM_HIP_CHECK(hipGetLastError());
+        a.nvec = 2;
+        a.dvec1 = v1;
+        a.dc = pair_dc_.p;
+        a.partial = pair_partial_.p;
+        a.part_vstride = static_cast<long>(partial_.count);
+        a.colslab = pair_colslab_.p;
+        a.colslab_vstride = static_cast<long>(colslab_.count);
+    } else {
+        d_packed_ = false;  // (dc_ is about to hold another vector's records)
+        enqueue_pack_dc(v0, Kv0, nzero);
     }
+    T *const Kv[2] = { Kv0, Kv1 };
+    if (ev_begin != nullptr) LSSVM_HIP_CHECK(hipEventRecord(ev_begin, st));
+    // every reduction runs per vector on that vector's planes, into that vector's K*v (no feature panels where the pair kernel applies)
+    enqueue_sym_walk(a, v1 != nullptr ? 2 : 1, Kv, 1, [&](auto &&launch, bool, bool last) {
+        launch();
+        if (last && ev_end != nullptr) LSSVM_HIP_CHECK(hipEventRecord(ev_end, st));
+    });
+    LSSVM_HIP_CHECK(hipGetLastError());
 }
 
 /* Weighted LS-SVM: Abar(w)_ij = k(x_i,x_j) + delta_ij / (C w_i) + QA_cost(w) - q_i - q_j with QA_cost(w) = k(x_last,x_last) + 1 / (C w_last).  Every diagonal term is

@@ -373,7 +373,8 @@ class Problem {
     Problem &operator=(const Problem &) = delete;
 
     void activate() const { LSSVM_HIP_CHECK(hipSetDevice(device_)); }
-    /* Kv_ <- this shard's part of K * v (complete for a world of one): tile kernel + fixed-order reductions */
+    /* Kv_ <- this shard's part of K * v (complete for a world of one): tile kernel + fixed-order reductions.  The symmetric variant is one call of enqueue_sym_walk,
+     * with sampled HIP events around every band launch (matvec_ms_) */
     void enqueue_apply_K_local(const T *v_dev, bool zero_first);
     void reshard(const std::vector<double> &weights);  // new shares of the triangle (lssvm_mi355_problem_rebalance): the data, the vectors and the CG state stay
     void choose_shard_geometry();
@@ -418,7 +419,8 @@ class Problem {
      * kernels on 129 ... 512 features, polynomial or rbf with folded records (sym_pair_routed, profiles/lockstep_f32_wide.json) */
     bool pair_kernel_applies() const;
     /* Kv0 <- K * v0 and, with v1, Kv1 <- K * v1 from ONE pass of the two-vector kernel (pair_kernel_applies; the caller falls back to two calls elsewhere); without v1
-     * today's single-vector pass.  Each result has the bits enqueue_apply_K_local gives for that vector.  `ev`: HIP events around the tile-kernel launches, or NULL. */
+     * today's single-vector pass.  Each result has the bits enqueue_apply_K_local gives for that vector: both are enqueue_sym_walk on the arguments of that vector.
+     * `ev`: HIP events around the tile-kernel launches (before the first band's, after the last band's), or NULL. */
     void enqueue_apply_K_lanes(const T *v0, T *Kv0, const T *v1, T *Kv1, hipEvent_t ev_begin, hipEvent_t ev_end);
 
   private:
@@ -426,6 +428,14 @@ class Problem {
     friend class CgSteps<T>;
     friend class LandmarkBlock<T>;
     TileArgs<T> tile_args(const T *v_dev) const;
+    /* dc_ <- the single-vector records of v, and `zero[0 .. nzero)` cleared by the same kernel: the one k_pack_dc / k_pack_dc_f64 launch of a problem */
+    void enqueue_pack_dc(const T *v, T *zero, int nzero);
+    /* The symmetric pass over the row-block bands, the one walk behind enqueue_apply_K_local and enqueue_apply_K_lanes: per feature panel (`npanels`: wide_linear_, else
+     * 1) and band the tile kernel on `a` with the band's work items, then per vector u < nv the band's mirrored column sums (a.colslab + u * a.colslab_vstride) folded
+     * into Kv[u]; after a panel's bands the row slabs (a.partial + u * a.part_vstride) added into Kv[u].  around(launch, first, last) runs every tile launch -- it calls
+     * launch() once, with whatever timing the caller keeps around it; first / last: the first / last tile launch of the walk. */
+    template <typename Around>
+    void enqueue_sym_walk(const TileArgs<T> &a, int nv, T *const *Kv, int npanels, Around &&around);
 
     Options opt_{};
     lssvm_params params_{};
@@ -520,7 +530,7 @@ class Problem {
 
 /* ------------------------------------------------------------------ the CG recipe, step by step ------------------------------------------------------------------ */
 /* CgSteps<T>: the O(n) steps of the reference's CG recipe (csvm.cpp:71-183) on ONE CG state of ONE problem -- its stream, q, n, QA_cost and diagonal term.  Every step
- * only enqueues (finish_now excepted); a step that reads K * v is handed the pointer to it.  The drivers -- the sharded single solve, the lanes, the refinement -- decide
+ * only enqueues (finish_now excepted); a step that reads K * v is handed the pointer to it.  The drivers -- the sharded single solve, the lanes, the refinement, PCG -- decide
  * when the Gram passes run and where the host waits; which O(n) kernel runs on which arguments is written here and nowhere else, so their recurrences have the same
  * bits.  Defined by lssvm_solver.hip. */
 template <typename T>
@@ -548,8 +558,9 @@ class CgSteps {
     /* d = r (initial) or beta d + r, and -- as partial sums that Ad_and_dAd finishes for itself -- the sums the next matvec's rank-1 terms need   (csvm.cpp:111, :161-163) */
     void update_d(const State &s, bool initial, const PackDc<T> &pack = PackDc<T>{}) const;
     /* one iteration up to its delta, with Kv = K * d: Ad = A d, alpha = delta / d.Ad, x += alpha d, r -= alpha Ad -- or with `refresh`, every 50th iteration, x only and
-     * its sums: K * x and `residual` follow   (csvm.cpp:131-148) */
-    void advance(const State &s, const T *Kv, bool refresh) const;
+     * its sums: K * x and `residual` follow   (csvm.cpp:131-148).  `sc_alpha`: the scalar set alpha is formed in (SC_DELTA read, SC_DAD / SC_ALPHA written) where that is
+     * not the state's own -- PCG keeps alpha's numerator r.z in two sets used in turn (lssvm_precond.hip) */
+    void advance(const State &s, const T *Kv, bool refresh, double *sc_alpha = nullptr) const;
     /* Ad += add * A v with Kv = K * v and the sums of v in SC_S / SC_QD   (csvm.cpp:283-306) */
     void apply_ret(const State &s, const T *Kv, const T *v, double add) const;
     /* the sums of x and the scalars to the host, x to alpha_out (where given); after the stream has been waited for, read_solution: alpha_N = -sum(x),

@@ -72,13 +72,13 @@ void CgSteps<T>::update_d(const State &s, bool initial, const PackDc<T> &pack) c
 }
 
 template <typename T>
-void CgSteps<T>::advance(const State &s, const T *Kv, bool refresh) const {
+void CgSteps<T>::advance(const State &s, const T *Kv, bool refresh, double *sc_alpha) const {
     // (every kernel of the chain reduces its predecessor's partial sums for itself -- finish2_in_block -- so no single-block kernel stands between them)
     with_diag([&](auto weighted, auto diag) {
         hipLaunchKernelGGL((k_Ad_and_dAd<T, decltype(weighted)::value>), dim3(RED_BLOCKS), dim3(RED_THREADS), 0, stream(), Kv, s.d.p, q(), s.part_of(PART_D), s.sc.p, n(), diag, p_.QA_cost_, s.Ad.p,
                            s.part_of(PART_DAD));
     });
-    hipLaunchKernelGGL(k_update_x_r<T>, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, stream(), s.x.p, s.r.p, s.d.p, s.Ad.p, s.part_of(PART_DAD), s.sc.p, n(), refresh ? 0 : 1, s.part_of(PART_RR));
+    hipLaunchKernelGGL(k_update_x_r<T>, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, stream(), s.x.p, s.r.p, s.d.p, s.Ad.p, s.part_of(PART_DAD), sc_alpha != nullptr ? sc_alpha : s.sc.p, n(), refresh ? 0 : 1, s.part_of(PART_RR));
     LSSVM_HIP_CHECK(hipGetLastError());
     if (refresh) sum_and_qdot(s, s.x.p, SC_SUMX, SC_QX);
 }

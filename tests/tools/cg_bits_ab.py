@@ -11,11 +11,18 @@ Bits.  Per (real type, kernel function, weighted, shape) -- fp32 / fp64; linear,
 solve; cg_begin / cg_step / cg_finish cut into several calls across the refresh of iteration 50; matvec with add = +1 / -1; matvec_pair; solve_lockstep for k = 1, 2, 3, 7;
 the same solve sharded over [0, 0] (two shards of one device: the peer exchange); in fp64 solve_refined for k = 1 and 3.  Once: the refinement's take-over case (linear
 400 x 8, C = 1e8) and its fall-back for data beyond float32.  Where two devices are visible, the two-device solve over both exchanges; else that is recorded as not run.
+For a change to the Gram pass's walk over the row-block bands or to PCG's use of the recipe (gram_pass_cases; --out profiles/gram_pass_bits.json): solve_pcg one-shot and
+resident, k = 1 and 3, rank 32, 60 forced iterations (across the refresh of iteration 50), and solve_cost_path with verify over 5 costs -- fp32 / fp64, rbf / polynomial,
+300 x 20 and 700 x 20; matvec, matvec_pair and solve_lockstep k = 1, 2, 3 at 300 x 200 fp32 (the two-vector symmetric split kernel); with colslab_band_mb = 1 (two bands)
+5 900 x 20 fp64 and 8 400 x 192 fp32: matvec, matvec_pair, six cg_step iterations, lockstep k = 3; the linear kernel over feature panels: 300 x 300 fp64, 300 x 200 fp32
+(and 300 x 300 fp32, which runs as ONE launch of the polynomial kernel of degree 1), matvec and twelve iterations.
 Timing (--timing).  Host wall clock of the whole call, medians over rounds x reps samples per library and the parent's spread (max - min) / median:
   a  10 000 x 32 rbf fp32, 200 iterations forced (eps 1e-30): short matvecs, the host's launch sequence and the enqueue-ahead path dominate
   b  50 000 x 128 rbf fp32, eps 1e-3
   c  solve_lockstep, 100 000 x 64 polynomial degree 3 fp64, k = 4, eps 1e-3 (problem set-up included)
   d  solve_refined, 50 000 x 128 rbf, eps 1e-10, C = 1
+  e  solve_pcg, 50 000 x 32 rbf fp32, rank 256, eps 1e-3 (problem set-up and the preconditioner's build included)
+  f  solve_lockstep, 30 000 x 192 polynomial degree 3 fp32, k = 4, eps 1e-3 (problem set-up included)
 Condition per shape: median(new) <= median(parent) * (1 + spread(parent)).
 Child processes alternate between the two libraries (PLSSVM_AMD_LIBRARY).  Every child runs under a time limit of its own; a child that fails ends the run: nothing more
 is started on the device.  The tool exits non-zero on any difference / any shape over its bound, after it has written --out.
@@ -133,7 +140,100 @@ def bits_child() -> None:
             alphas, rhos, infos, ris = backend.solve_refined(Parameter(kernel_type="linear", gamma=1.0 / 20, cost=1.0), X, np.stack([y, -y])[:k], 1e-6, 300)
             assert all(r["refined"] == 0 for r in ris), ris
             out[f"refined: data beyond float32 falls back, k = {k}"] = several(alphas, rhos, infos)
+    gram_pass_cases(out)
     print("RESULT " + json.dumps(out), flush=True)
+
+
+def gram_pass_cases(out) -> None:
+    """What runs the band walk of the Gram pass or PCG's recipe steps and the cases above do not reach (see the module's docstring)."""
+    import numpy as np
+
+    from plssvm_amd import _capi, backend
+    from plssvm_amd.datagen import make_blobs_multiclass
+    from plssvm_amd.multiclass import one_vs_all_targets
+    from plssvm_amd.parameter import Parameter
+
+    def param(kernel, features):
+        name, degree = KERNELS[kernel]
+        return Parameter(kernel_type=name, degree=degree, gamma=1.0 / features, coef0=0.5, cost=COST)
+
+    def case(points, features, dt, classes=3):
+        X, y = make_blobs_multiclass(points, features, classes, seed=7, dtype=dt)
+        rng = np.random.default_rng(3)
+        return X, one_vs_all_targets(np.arange(classes), y, np.float64).astype(dt), [rng.standard_normal(points - 1).astype(dt) for _ in range(4)]
+
+    def lockstep(prob, B, eps, max_iter):
+        alphas, rhos, infos, passes = prob.solve_lockstep(B, eps, max_iter)
+        return digest(alphas, np.asarray(rhos, dtype=np.float64), np.array([i["residuum"] for i in infos]), np.array([i["iterations"] for i in infos], dtype=np.uint64),
+                      np.array(passes, dtype=np.uint64))
+
+    def matvecs(prob, key, vecs):
+        v0, v1, r0, r1 = vecs
+        out[f"{key}: matvec"] = digest(prob.matvec(v0, r0, 1.0))
+        m0, m1, two = prob.matvec_pair(v0, v1, r0, r1, -1.0)
+        out[f"{key}: matvec_pair"] = digest(m0, m1, np.uint64(two))
+
+    def cg_steps(prob, b, steps):
+        prob.cg_begin(b, 1e-30)
+        for _ in range(steps):
+            prob.cg_step(1)
+        alpha, rho, info = prob.cg_finish()
+        return digest(alpha, np.float64(rho), np.float64(info["residuum"]), np.uint64(info["iterations"]))
+
+    def pcg(res, k):  # (alphas, rhos, infos) of solve_pcg, one right-hand side or several
+        alphas, rhos, infos = res
+        infos = [infos] if k == 1 else infos
+        return digest(alphas, np.asarray(rhos, dtype=np.float64), np.array([i["residuum"] for i in infos]), np.array([[i["iterations"], i["gram_passes"]] for i in infos], dtype=np.uint64))
+
+    def path(res):
+        alphas, rhos, infos, passes = res
+        return digest(alphas, np.asarray(rhos, dtype=np.float64), np.array([[i["residuum"], i["true_residuum"]] for i in infos]), np.array([i["iterations"] for i in infos], dtype=np.uint64),
+                      np.array(passes, dtype=np.uint64))
+
+    # PCG across the refresh of iteration 50 (60 iterations forced), and the cost path with its verification passes
+    for dt in (np.float32, np.float64):
+        for points, features in SHAPES[1:]:
+            X, B, _ = case(points, features, dt)
+            for kernel in ("rbf", "poly3"):
+                key = f"{np.dtype(dt).name} {kernel} {points}x{features}"
+                p = param(kernel, features)
+                costs = [0.5, 3.0, 20.0, 100.0, 1000.0]
+                eps = 1e-8 if dt == np.float64 else 1e-3
+                for k in (1, 3):
+                    out[f"{key}: solve_pcg one-shot, rank 32, k = {k}"] = pcg(backend.solve_pcg(p, X, B[0] if k == 1 else B[:k], 1e-30, 60, rank=32), k)
+                out[f"{key}: solve_cost_path one-shot, 5 costs, verify"] = path(backend.solve_cost_path(p, X, B[0], costs, eps, points, verify=True))
+                with backend.ResidentProblem(p, X) as prob:
+                    prob.build_preconditioner(32)
+                    for k in (1, 3):
+                        out[f"{key}: solve_pcg resident, rank 32, k = {k}"] = pcg(prob.solve_pcg(B[0] if k == 1 else B[:k], 1e-30, 60), k)
+                    out[f"{key}: solve_cost_path resident, 5 costs, verify"] = path(prob.solve_cost_path(B[0], costs, eps, points, verify=True))
+    # fp32 beyond 128 features: the two-vector symmetric split kernel
+    X, B, vecs = case(300, 200, np.float32)
+    for kernel in ("poly3", "rbf"):
+        key = f"float32 {kernel} 300x200"
+        with backend.ResidentProblem(param(kernel, 200), X) as prob:
+            matvecs(prob, key, vecs)
+            for k in (1, 2, 3):
+                out[f"{key}: solve_lockstep k = {k}"] = lockstep(prob, B[:k], 1e-3, 300)
+    # more than one row-block band under the lanes (colslab_band_mb = 1: tests/test_gpu_lockstep_bands.py has the arithmetic of the two shapes)
+    for dt, points, features in ((np.float64, 5900, 20), (np.float32, 8400, 192)):
+        X, B, vecs = case(points, features, dt)
+        for kernel in ("poly3", "rbf"):
+            key = f"{np.dtype(dt).name} {kernel} {points}x{features} colslab_band_mb 1"
+            with backend.ResidentProblem(param(kernel, features), X, options=_capi.Options(colslab_band_mb=1)) as prob:
+                matvecs(prob, key, vecs)
+                out[f"{key}: cg_begin / 6 x cg_step / cg_finish"] = cg_steps(prob, B[0], 6)
+                out[f"{key}: solve_lockstep k = 3, 6 iterations"] = lockstep(prob, B, 1e-30, 6)
+                out[f"{key}: tile launches per matvec"] = str(prob.info()["tile_launches_per_matvec"])
+    # the linear kernel over feature panels: fp64 beyond 256 features; fp32 beyond 128 -- but below 10 000 points only up to 256, beyond that one launch of the polynomial
+    # kernel of degree 1 takes over (300 x 300), so 300 x 200 is the fp32 shape with the panel loop inside
+    for dt, points, features in ((np.float32, 300, 300), (np.float32, 300, 200), (np.float64, 300, 300)):
+        X, B, vecs = case(points, features, dt)
+        key = f"{np.dtype(dt).name} linear {points}x{features}"
+        with backend.ResidentProblem(param("linear", features), X) as prob:
+            matvecs(prob, key, vecs)
+            out[f"{key}: cg_begin / 12 x cg_step / cg_finish"] = cg_steps(prob, B[0], 12)
+            out[f"{key}: tile launches per matvec"] = str(prob.info()["tile_launches_per_matvec"])
 
 
 def timing_child(reps: int) -> None:
@@ -173,6 +273,13 @@ def timing_child(reps: int) -> None:
             prob.solve_lockstep(B, 1e-3, 100_000)
 
     timed("c_solve_lockstep_100000x64_poly3_f64_k4", lockstep)
+    X, y = make_blobs_pm1(50_000, 32, seed=42, dtype=np.float32)
+    p = Parameter(kernel_type="rbf", gamma=1.0 / 32, cost=1.0)
+    timed("e_solve_pcg_50000x32_rbf_f32_rank256_eps1e-3", lambda: backend.solve_pcg(p, X, y, 1e-3, 50_000, rank=256))
+    X, labels = make_blobs_multiclass(30_000, 192, 4, seed=42, dtype=np.float32)
+    B = one_vs_all_targets(np.arange(4), labels, np.float64).astype(np.float32)
+    p = Parameter(kernel_type="polynomial", degree=3, gamma=1.0 / 192, coef0=0.0, cost=1.0)
+    timed("f_solve_lockstep_30000x192_poly3_f32_k4", lockstep)
     print("RESULT " + json.dumps(out), flush=True)
 
 
