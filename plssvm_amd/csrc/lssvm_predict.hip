@@ -30,14 +30,14 @@ static void setup_rect_launch(TileArgs<float> &ta, RectSetup &rs, const PlaneSet
     rs.frag.alloc_zero(static_cast<size_t>(planesP.nplanes) * plane_elems, s);
     enqueue_planes_fragment_major(planesP.buf.p, plane_elems, rows_alloc, planesP.ldx16, planesP.nplanes, rs.frag.p, s);
     const int pairs = num_ib / 2;
-    std::vector<std::vector<int2>> by_chunk(static_cast<size_t>(num_jc));
+    std::vector<std::vector<WorkItem>> by_chunk(static_cast<size_t>(num_jc));
     for (int jc = 0; jc < num_jc; ++jc) {
         by_chunk[static_cast<size_t>(jc)].reserve(static_cast<size_t>(pairs));
-        for (int pr = 0; pr < pairs; ++pr) by_chunk[static_cast<size_t>(jc)].push_back(make_int2(2 * pr, jc));
+        for (int pr = 0; pr < pairs; ++pr) by_chunk[static_cast<size_t>(jc)].push_back({ 2 * pr, jc });
     }
-    const std::vector<int2> items = xcd_lane_order(by_chunk);
+    const std::vector<WorkItem> items = xcd_lane_order(by_chunk);
     rs.items.alloc_zero(items.size(), s);
-    LSSVM_HIP_CHECK(hipMemcpyAsync(rs.items.p, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice, s));
+    LSSVM_HIP_CHECK(hipMemcpyAsync(rs.items.p, items.data(), items.size() * sizeof(WorkItem), hipMemcpyHostToDevice, s));
     LSSVM_HIP_CHECK(hipStreamSynchronize(s));  // `items` goes out of scope
     int cus = 256;
     LSSVM_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, 0));
@@ -164,21 +164,6 @@ static bool rect_kernel_applies(const Options &opt, const lssvm_params &params, 
     return ldx16 <= 128 && !poly_generic && rbf_ok && opt.mfma_shape >= 3 && num_ib >= PAIR_MIN_TILES;
 }
 
-/* column tiles per work item of a rectangular product and the column chunks they make: the option, or automatically about 4096 work items (see Problem<T>'s
- * constructor); 256-row items (`rect`): about eight per CU, at most 64 tiles */
-struct ColumnChunks {
-    int jc_tiles, num_jc;
-};
-static ColumnChunks column_chunks(const Options &opt, bool rect, int num_ib, int num_jt) {
-    long tiles = static_cast<long>(opt.j_chunk_tiles);
-    if (tiles <= 0) {
-        tiles = rect ? std::min<long>(64, std::max<long>(4, (static_cast<long>(num_ib / 2) * num_jt + 1024) / 2048))
-                     : std::min<long>(16, std::max<long>(2, (static_cast<long>(num_ib) * num_jt + 2048) / 4096));
-    }
-    const int jc_tiles = static_cast<int>(tiles);
-    return { jc_tiles, (num_jt + jc_tiles - 1) / jc_tiles };
-}
-
 /* out[p][v] = sum_j alpha_v,j k(sv_j, p) - rho[v] for `nvec` weight vectors: the rectangular instance of the tile kernels behind the one-shot call and both resident
  * predictors.  Rows = the points P (padded to whole pairs of row blocks), columns = the support vectors S, both prepared by the caller.  The stage owns the slabs of
  * partial row sums, the values and the launches' timer; a caller sets the operand-specific launch arguments on what args() returns and calls run() once.
@@ -192,7 +177,7 @@ struct ProductStage {
     const bool rect;  // the rectangular 256-row kernel: the caller's decision (rect_kernel_applies) and the caller's setup_rect_launch
     const T *const alpha, *const rho;  // [nvec][S.rows_alloc] in HBM, exact zeros beyond the support vectors; [nvec] on the host
     const int nv, per_launch, num_ib, num_jt;
-    const ColumnChunks chunks;
+    const int jc_tiles, num_jc;  // column tiles per work item (product_chunk_tiles, lssvm_geometry.cpp) and the column chunks they make
     const size_t part_plane;
     const hipStream_t s;
     const double t0;    // the caller's start of the call
@@ -202,7 +187,7 @@ struct ProductStage {
     ProductStage(const Options &options, const DeviceMatrix<T> &points, const DeviceMatrix<T> &svs, bool rect256, const T *alphas, const T *rhos, size_t nvec, int vectors_per_launch,
                  hipStream_t stream, double t_begin) :
         opt(options), P(points), S(svs), rect(rect256), alpha(alphas), rho(rhos), nv(static_cast<int>(nvec)), per_launch(vectors_per_launch), num_ib(points.rows_alloc / TILE),
-        num_jt(svs.rows_alloc / TILE), chunks(column_chunks(options, rect256, num_ib, num_jt)), part_plane(static_cast<size_t>(chunks.num_jc) * points.rows_alloc), s(stream), t0(t_begin), timer(nvec) {
+        num_jt(svs.rows_alloc / TILE), jc_tiles(product_chunk_tiles(geometry_options(options), rect256, num_ib, num_jt)), num_jc(num_chunks(num_jt, jc_tiles, 0, 0)), part_plane(static_cast<size_t>(num_jc) * points.rows_alloc), s(stream), t0(t_begin), timer(nvec) {
         partial.alloc_zero(per_launch * part_plane, s);
         Kv.alloc_zero(P.rows_alloc, s);
         o.alloc_zero(static_cast<size_t>(P.rows) * nvec, s);
@@ -224,7 +209,7 @@ struct ProductStage {
         ta.kchunks = S.ldx / kchunk_of<T>();
         ta.num_ib = num_ib;
         ta.num_jt = num_jt;
-        ta.jc_tiles = chunks.jc_tiles;
+        ta.jc_tiles = jc_tiles;
         ta.ncols_valid = S.rows;
         set_kernel_scalars(ta, params, rbf_direct);
         set_launch_options(ta, opt);
@@ -236,7 +221,6 @@ struct ProductStage {
      * the product and the download end (the resident fp32 form's LSSVM_MI355_DEBUG laps). */
     template <typename Records, typename Lap>
     void run(TileArgs<T> &ta, int kernel_type, bool rbf_direct, Records &&records, T *out, int mem_kind, lssvm_predict_info &info, Lap &&lap, int repeat = 1) {
-        const int num_jc = chunks.num_jc;
         const auto launch = [&] { launch_tile_kernel<T>(ta, kernel_type, rbf_direct, num_jc, s); };
         const auto next_counters = [&] {  // (a persistent launch zeroes the OTHER set of counters)
             if (ta.queue != nullptr) std::swap(ta.queue, ta.queue_next);
@@ -402,7 +386,7 @@ static void predict_values_impl(const Options &opt, const lssvm_params &params, 
     ta.wide_panels = wide ? 1 : 0;
     RectSetup rect_setup;
     if constexpr (std::is_same_v<T, float>) {
-        if (rect) setup_rect_launch(ta, rect_setup, planesP, P.rows_alloc, stage.num_ib, stage.chunks.num_jc, s);
+        if (rect) setup_rect_launch(ta, rect_setup, planesP, P.rows_alloc, stage.num_ib, stage.num_jc, s);
     }
     stage.run(ta, params.kernel_type, rbf_direct, pack_records, out, LSSVM_MEM_HOST, info, no_lap, repeat);
     info.gram_mode = (planesS.mode != 0 && dc.p != nullptr) ? (rbf_grid ? 3 : planesS.mode) : 0;
@@ -630,7 +614,7 @@ class ResidentF32 {
         ta.dc_folded = folded ? 1 : 0;
         set_plane_args(ta, m.params, planesS_, planesP, static_cast<size_t>(S_.rows_alloc), static_cast<size_t>(P.rows_alloc));
         RectSetup rect_setup;
-        if (rect) setup_rect_launch(ta, rect_setup, planesP, P.rows_alloc, stage.num_ib, stage.chunks.num_jc, s);
+        if (rect) setup_rect_launch(ta, rect_setup, planesP, P.rows_alloc, stage.num_ib, stage.num_jc, s);
         stage.run(ta, m.params.kernel_type, false, records, out, mem_kind, info, lap);
         info.gram_mode = planesS_.mode;
         info.rbf_direct = 0;

@@ -55,7 +55,7 @@ struct Options {
                                  // (x_i - x_j)^2 kernel on the vector ALU, 2 always the norm expansion on the matrix cores
     int64_t rbf_fold = 1;        // fp32 rbf on the split kernels: 1 = folded column records (2^c_j d_j | 2^c_j), accumulators start from c_i as the C
                                  // operand of their first MFMA (default, while the exponent scale stays below 200); 0 = start values c_i + c_j by vector adds
-    int64_t j_chunk_tiles = 0;   // 128-column tiles per work item; 0 = automatic (see Problem<T>'s constructor)
+    int64_t j_chunk_tiles = 0;   // 128-column tiles per work item; 0 = automatic (shard_chunks / product_chunk_tiles, lssvm_geometry.cpp)
     std::vector<double> shard_weights;  // symmetric variant, several ranks: rank r's share of the triangle's area is weight[r] / sum (empty or of another length: equal shares); lssvm_mi355_set_shard_weights
     int64_t j_chunk_head = 1;    // 256-row workgroups: 0 = none; 1 = chosen by the replayed dispatch (with j_chunk_tiles = 0; default); 1024 count + tiles = the first `count` column chunks have `tiles` tiles
     int64_t symmetric = 1;         // 1: evaluate only the tiles on/below the diagonal and mirror them, 0: full square
@@ -92,10 +92,6 @@ constexpr int LINEAR_IN_TILE_BELOW = 10000;   // fp32 linear kernel on more than
                                               // instead of launch-bound feature-panel passes (Problem<float>::tile_params_)
 constexpr int LINEAR_PANEL_FEATURES = 128;    // linear kernel beyond this many features: one pass of the <= 128-feature kernels per feature panel (fp32 f16x3: beats the
                                               // wider one-wave kernels by 5 ... 12 % at every width measured; fp64: 64- and 256-feature panels within 2 %)
-constexpr int ITEM_ORDER = 3;                 // symmetric variant: the work items of a column chunk on ONE XCD at a time (list position 8 k + x = lane x; the hardware deals
-                                              // workgroups round-robin over the 8 XCDs), the items cut short by the diagonal last, longest first.  Against plain
-                                              // column-chunk major order (1): bit-identical results, fabric traffic 116 -> 97 GB per matvec at 1 000 000 x 128, time -0.3 %
-                                              // (profiles/r04_ab_xcd_item_order.log)
 /* process-wide DEFAULTS (lssvm_mi355_set_option); every problem / solve that is not handed options of its own (lssvm_mi355_options, ABI 4) takes a snapshot when it is
  * created.  The defaults are read and written under options_mutex() only: options_snapshot() for readers. */
 Options &options();
@@ -104,6 +100,8 @@ inline Options options_snapshot() {
     const std::lock_guard<std::mutex> lock(options_mutex());
     return options();
 }
+/* what the work-item geometry reads of them (lssvm_geometry.hpp; the shard weights and the item order travel as arguments) */
+inline GeometryOptions geometry_options(const Options &o) { return { o.j_chunk_tiles, o.j_chunk_head, o.colslab_band_mb, o.colslab_limit_mb }; }
 /* fp32 rbf, rbf_form 0 (automatic): the grid planes were chosen from the exponent scale but do not represent THIS data -- the owner of the problem builds it again
  * with the formula-exact kernel (Solver's constructor, predict_values); with an explicit rbf_form = 3 the error reaches the caller */
 struct GridPlanesUnfit : Error {
@@ -316,8 +314,6 @@ void split_f16_planes(const float *X, int ldx, int dfeat, size_t rows, int ldx16
                       float *row_inv_scale = nullptr);  // row_inv_scale != NULL: a power-of-two scale per ROW, its inverse stored there  // tile_launch_f32h.hip
 void absmax_f32(const float *X, int ldx, int dfeat, size_t rows, unsigned *out, hipStream_t s);  // tile_launch_f32h.hip
 bool v2_eligible_f64(const Options &o, int ldx);
-int sym_block_boundary(int num_tiles, int r, int world, const std::vector<double> *weights = nullptr);
-void shard_blocks(int num_tiles, int world, int rank, bool symmetric, int &begin, int &end, const std::vector<double> *weights = nullptr);
 
 /* fp32: a data matrix once more as operand planes of the split tile kernels (make_planes in lssvm_problem.hip) */
 struct PlaneSet {
@@ -907,7 +903,6 @@ void make_planes(const Options &o, const lssvm_params &p, bool rbf_direct, const
 bool rbf_wants_grid_planes(const Options &o, const lssvm_params &p, size_t num_features, double r2);
 float make_grid_planes(const DeviceMatrix<float> &M, double r2_in, PlaneSet &out, float *chg, DevBuf<float> &efac, hipStream_t s, bool wide_nl);
 void set_plane_args(TileArgs<float> &a, const lssvm_params &p, const PlaneSet &cols, const PlaneSet &rows, size_t col_rows_alloc, size_t row_rows_alloc);
-std::vector<int2> xcd_lane_order(const std::vector<std::vector<int2>> &by_chunk);
 void enqueue_pack_records(const float *dvec, const float *cc, int ncols_padded, float *dc, int folded, const float *efac, hipStream_t s);
 void enqueue_pack_records(const double *dvec, const double *cc, int ncols_padded, double *dc, int folded, const double *efac, hipStream_t s);
 /* the records of TWO weight vectors for the rectangular 256-row kernel's NV = 2 instance: (d0 | d1), folded: both times 2^c_j (k_pack_dc2) */

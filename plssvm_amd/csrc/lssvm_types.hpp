@@ -6,6 +6,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "lssvm_geometry.hpp"  // TILE, the column chunks (chunk_begin / chunk_len) and the host's work-item geometry
+
 #include <cstddef>
 #include <cstdint>
 
@@ -21,7 +23,6 @@ constexpr int KT_RBFF = 5;   // bf16x6 16x16x32 kernels only: rbf with the FOLDE
 constexpr int KT_RBFG = 6;   // f16 kernels of s6w_body only (round 5): rbf on GRID planes -- x = h + s1 + s2 with h on a grid of spacing g, so that the accumulator, started from
                              // sigma^2 (ch_i + ch_j) and fed the h.h products first, holds -|h_i - h_j|^2 / 2 EXACTLY before the small terms arrive
 
-constexpr int TILE = 128;          // rows / columns of one workgroup tile of the implicit matrix
 constexpr int TILE_THREADS = 256;  // 4 wave64 arranged 2 x 2, each owning a 64 x 64 sub-tile
 
 using f32x4 = float __attribute__((ext_vector_type(4)));
@@ -78,7 +79,7 @@ struct TileArgs {
     int jc_tiles;     // column tiles per work item
     int num_jc;       // number of column chunks = ceil(num_jt / jc_tiles); with a head (below): jc_head_count + ceil((num_jt - head tiles) / jc_tiles)
     int jc_head_tiles;  // 256-row workgroups only (0 elsewhere): the FIRST jc_head_count column chunks have this many tiles instead of jc_tiles -- short items that
-    int jc_head_count;  // every row pair has, dispatched last: they fill the final dispatch round of a small launch (chunk_begin / chunk_len below)
+    int jc_head_count;  // every row pair has, dispatched last: they fill the final dispatch round of a small launch (chunk_begin / chunk_len, lssvm_geometry.hpp)
     int row_pair;     // host side only: != 0 selects the 256-row-workgroup kernels (items = block pairs, lssvm_tile_f32_pair.hip.hpp)
     int rect;         // host side only: with row_pair, != 0 selects the RECTANGULAR 256-row kernel of predict_values (every tile in full, no mirrored column sums)
     int pair_lag;     // host side only: steps the second half of such a workgroup runs behind the first
@@ -106,12 +107,7 @@ struct PackDc {
     T *zero = nullptr;
     int ncols = 0, nzero = 0, folded = 0;
 };
-/* column chunk jc of a launch covers the tiles [chunk_begin, chunk_begin + chunk_len): a head of `head_count` short chunks, then chunks of `tiles` */
-__host__ __device__ inline int chunk_begin(int jc, int tiles, int head_tiles, int head_count) {
-    return jc < head_count ? jc * head_tiles : head_count * head_tiles + (jc - head_count) * tiles;
-}
-__host__ __device__ inline int chunk_len(int jc, int tiles, int head_tiles, int head_count) { return jc < head_count ? head_tiles : tiles; }
-/* number of chunks that begin at or before tile `last` */
+/* number of chunks (chunk_begin / chunk_len: lssvm_geometry.hpp) that begin at or before tile `last` */
 __host__ __device__ inline int chunks_upto(int last, int tiles, int head_tiles, int head_count) {
     const int head = head_count * head_tiles;
     return last < head ? last / head_tiles + 1 : head_count + (last - head) / tiles + 1;

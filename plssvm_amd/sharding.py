@@ -5,14 +5,14 @@ through the host (include/plssvm/backends/gpu_csvm.hpp:283-299, :449-475).  Here
 contiguous run of 128-row blocks of the implicit matrix for all three kernels; the data matrix is replicated.  Default
 (symmetric variant: only the tiles on/below the diagonal are evaluated): blocks dealt by equal AREA, one RCCL all-reduce of
 the partial K*d vectors per implicit matvec.  Full-square variant: equal runs of blocks, one all-gather of the K*d slices.
-This module holds the partition arithmetic (identical to ``Problem<T>``'s constructor in plssvm_amd/csrc/lssvm_problem.hip),
+This module holds the partition arithmetic (identical to ``shard_blocks`` in plssvm_amd/csrc/lssvm_geometry.cpp),
 the flop accounting bench.py uses, and the bootstrap of the library's RCCL communicator over an existing
 ``torch.distributed`` process group.
 """
 
 from __future__ import annotations
 
-TILE = 128  # rows per block of the tile kernel (plssvm_amd/csrc/lssvm_types.hpp)
+TILE = 128  # rows per block of the tile kernel (plssvm_amd/csrc/lssvm_geometry.hpp)
 
 __all__ = ["TILE", "row_block_partition", "sym_block_partition", "work_share", "triangle_share", "padded_vector_length", "exchange_unique_id", "init_library_communicator", "connect_peers"]
 
@@ -37,7 +37,7 @@ def row_block_partition(n: int, world: int):
 def sym_block_partition(n: int, world: int, weights=None):
     """Symmetric variant (only the tiles on/below the diagonal are evaluated): row block ``ib`` costs ``ib + 1`` tiles, so the
     blocks are dealt by equal AREA -- boundary of rank r = tiles * sqrt(r / world) rounded to an EVEN block index (the 256-row
-    workgroups of the tile kernel work on block pairs; ``sym_block_boundary`` in plssvm_amd/csrc/lssvm_problem.hip).  ``weights``
+    workgroups of the tile kernel work on block pairs; ``sym_block_boundary`` in plssvm_amd/csrc/lssvm_geometry.cpp).  ``weights``
     (one positive number per rank; ``lssvm_mi355_set_shard_weights``): rank r gets ``weights[r] / sum`` of the area instead of ``1 / world``
     -- devices of unequal pace.  Returns ``[(block_begin, block_end), ...]``."""
     import math

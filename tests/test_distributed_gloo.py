@@ -152,7 +152,7 @@ def test_symmetric_partition_is_a_balanced_cover(n, world):
 @pytest.mark.parametrize("n", [1, 127, 128, 129, 390, 4095, 49_999, 999_999])
 @pytest.mark.parametrize("world", [1, 2, 3, 8])
 def test_the_librarys_own_partition_equals_the_python_restatement(n, world):
-    """lssvm_mi355_shard_blocks is the function Problem<T> partitions with (plssvm_amd/csrc/lssvm_problem.hip: shard_blocks); the Python
+    """lssvm_mi355_shard_blocks is the function Problem<T> partitions with (plssvm_amd/csrc/lssvm_geometry.cpp: shard_blocks); the Python
     copy in plssvm_amd/sharding.py (used for bench.py's flop accounting and by the gloo tests above) must agree with it block for block."""
     from plssvm_amd import _capi
 
