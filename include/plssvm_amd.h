@@ -571,6 +571,47 @@ int lssvm_mi355_fit_reduced_loo_f64(const lssvm_params *params, const double *X,
                                     double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out, lssvm_reduced_loo_info *infos,
                                     const lssvm_mi355_options *options);
 
+/* Landmark selection on a resident problem (opt-in): the pivots of a partial Cholesky factorisation of the kernel matrix, chosen greedily or
+ * at random in proportion to the residual diagonal (randomly pivoted Cholesky).  The result is a list of point indices for the `landmarks` argument of the entry points
+ * above; nothing else changes, and nothing selects it automatically.  Neither rule dominates the other or the fixed shuffle (README.md has the rows of all three kinds).
+ * Candidates cand[0 ... n): pool == 0: all N points in order; else the first `pool` entries of the library's fixed shuffle (as for the preconditioner above), in that
+ * order -- pool bounds the work space, rank x ld(n) doubles with ld(n) = n rounded up to 256.  Everything is double whatever the problem's dtype; k is evaluated from
+ * the problem's resident data exactly as the preconditioner evaluates K_Nm.
+ *   d_i = k(x_i, x_i), d0 = max d_i; S = the sum of the sums of d over blocks of 256 candidates, blocks ascending.
+ *   for j = 0 ... rank-1:  choose the pivot p
+ *       GREEDY:      the largest d_i, among equal values the smallest candidate position;
+ *       RPCHOLESKY:  u = (next() >> 11) 2^-53 with next() = splitmix64 from the state 0x243F6A8885A308D3 ^ seed, t = u S; the first block whose inclusive prefix of the
+ *                    block sums exceeds t, inside it the first position whose running sum (ascending) exceeds the remainder; the greedy pivot if rounding leaves none
+ *                    or the hit has d = 0;
+ *     stop with rank_found = j if d_p <= max(tol, 64 eps64) d0 (the rank is exhausted: a linear kernel on 5 features after 5 pivots);
+ *     c_i = k(x_i, x_p) - sum_{t<j} F[t][i] F[t][p] (t ascending), F[j][i] = c_i / sqrt(d_p), d_i <- max(d_i - F[j][i]^2, 0), d_p <- 0.
+ * landmarks_out: the pivots as point indices in the order they were chosen, UINT64_MAX from rank_found on.  trace_out (rank doubles or NULL): S after step j (the
+ * trace of the Nystrom residual K - K[:, P] K[P, P]^-1 K[P, :] over the candidates); from rank_found on the value at the stop.  residual_out (N doubles or NULL): the
+ * final d of every candidate, NaN for points that were not candidates.  1 <= rank <= min(candidates, 1024).  One launch pair per step on the problem's stream, no
+ * host round trip between steps; fixed-order reductions without atomics: the same bits for the same arguments.  The problem is left as it was and keeps its
+ * preconditioner.
+ * LSSVM_ERR_INVALID_ARGUMENT, all before a device is touched: a problem on several devices or ranks, weights set on the problem, a call between cg_begin and cg_finish;
+ * rank 0 or beyond its bound; 0 < pool < rank or pool > N; an unknown method; a negative or non-finite tol; a NULL landmarks_out. */
+#define LSSVM_LANDMARKS_GREEDY 1
+#define LSSVM_LANDMARKS_RPCHOLESKY 2
+typedef struct lssvm_landmark_select_info {
+    uint64_t rank_found, candidates;
+    double   trace0;        /* S before the first step */
+    double   trace;         /* S after the last step taken */
+    double   max_residual;  /* the largest d_i left */
+    double   select_ms;     /* the whole call */
+    double   device_bytes;  /* work space held during the call */
+} lssvm_landmark_select_info;
+int lssvm_mi355_problem_select_landmarks(lssvm_mi355_problem *p, uint64_t rank, int method, uint64_t pool, uint64_t seed, double tol, uint64_t *landmarks_out /* rank */,
+                                         double *trace_out /* rank or NULL */, double *residual_out /* N or NULL */, lssvm_landmark_select_info *info);
+/* one-shot: create the problem on device 0 (as lssvm_mi355_solve_*), select, destroy it */
+int lssvm_mi355_select_landmarks_f32(const lssvm_params *params, const float *X, size_t num_points, size_t num_features, uint64_t rank, int method, uint64_t pool,
+                                     uint64_t seed, double tol, uint64_t *landmarks_out, double *trace_out, double *residual_out, lssvm_landmark_select_info *info,
+                                     const lssvm_mi355_options *options);
+int lssvm_mi355_select_landmarks_f64(const lssvm_params *params, const double *X, size_t num_points, size_t num_features, uint64_t rank, int method, uint64_t pool,
+                                     uint64_t seed, double tol, uint64_t *landmarks_out, double *trace_out, double *residual_out, lssvm_landmark_select_info *info,
+                                     const lssvm_mi355_options *options);
+
 /* CG, csvm.cpp:89-111: b = y[0..n) - y[n], x = 1, r = b - A x, delta0, d = r */
 int lssvm_mi355_cg_begin(lssvm_mi355_problem *p, const void *y, double eps);
 /* run at most `iterations` further CG iterations (csvm.cpp:125-166); stops early when delta <= eps^2 delta0.

@@ -44,6 +44,7 @@ EXPORTED_SYMBOLS = [
     "lssvm_mi355_solve_pcg_f32", "lssvm_mi355_solve_pcg_f64",
     "lssvm_mi355_problem_fit_reduced", "lssvm_mi355_fit_reduced_f32", "lssvm_mi355_fit_reduced_f64", "lssvm_mi355_problem_landmark_gram", "lssvm_mi355_problem_time_gram_kernels",
     "lssvm_mi355_problem_fit_reduced_loo", "lssvm_mi355_fit_reduced_loo_f32", "lssvm_mi355_fit_reduced_loo_f64", "lssvm_mi355_problem_reduced_leverage", "lssvm_mi355_problem_time_leverage_kernel",
+    "lssvm_mi355_problem_select_landmarks", "lssvm_mi355_select_landmarks_f32", "lssvm_mi355_select_landmarks_f64",
     "lssvm_mi355_cg_begin", "lssvm_mi355_cg_step", "lssvm_mi355_cg_finish", "lssvm_mi355_problem_synchronize", "lssvm_mi355_problem_info",
     "lssvm_mi355_measure_bf16_mfma_ceiling", "lssvm_mi355_comm_library_path", "lssvm_mi355_set_io_threads", "lssvm_mi355_set_option", "lssvm_mi355_get_option",
     "lssvm_mi355_libsvm_open", "lssvm_mi355_libsvm_fill_f32", "lssvm_mi355_libsvm_fill_f64", "lssvm_mi355_libsvm_close",
@@ -298,6 +299,34 @@ def reduced_loo_entry(name: str):
             fn.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, dp, dp]
         else:
             fn.argtypes = [C.POINTER(LssvmParams), C.c_void_p, C.c_size_t, C.c_size_t] + common + outs + [C.c_void_p]
+        fn.restype = C.c_int
+    return fn
+
+
+class LssvmLandmarkSelectInfo(C.Structure):
+    """``lssvm_landmark_select_info``: how a landmark selection went (``lssvm_mi355_problem_select_landmarks``); the traces are sums of the residual diagonal."""
+    _fields_ = [("rank_found", C.c_uint64), ("candidates", C.c_uint64), ("trace0", C.c_double), ("trace", C.c_double), ("max_residual", C.c_double), ("select_ms", C.c_double),
+                ("device_bytes", C.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+SELECT_MAX_RANK = 1024
+LANDMARK_METHODS = {"greedy": 1, "rpcholesky": 2}  # LSSVM_LANDMARKS_GREEDY, LSSVM_LANDMARKS_RPCHOLESKY
+
+
+def select_entry(name: str):
+    """The entry points of the landmark selection (``lssvm_mi355_problem_select_landmarks``, ``lssvm_mi355_select_landmarks_f32 / _f64``) with their argument types.
+    Bound at the first call, like the weighted entry points."""
+    fn = getattr(lib, name)
+    if fn.argtypes is None:
+        dp, up = C.POINTER(C.c_double), C.POINTER(C.c_uint64)
+        common = [C.c_uint64, C.c_int, C.c_uint64, C.c_uint64, C.c_double, up, dp, dp, C.POINTER(LssvmLandmarkSelectInfo)]  # rank, method, pool, seed, tol, the outputs
+        if name == "lssvm_mi355_problem_select_landmarks":
+            fn.argtypes = [C.c_void_p] + common
+        else:
+            fn.argtypes = [C.POINTER(LssvmParams), C.c_void_p, C.c_size_t, C.c_size_t] + common + [C.c_void_p]
         fn.restype = C.c_int
     return fn
 

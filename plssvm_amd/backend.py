@@ -24,7 +24,7 @@ from ._capi import LssvmCgInfo, LssvmParams, LssvmPredictInfo, LssvmShard, Optio
 from .exceptions import InvalidParameterError
 from .parameter import Parameter
 
-__all__ = ["Options", "Predictor", "solve_system_of_linear_equations", "solve_refined", "solve_cost_path", "solve_pcg", "fit_reduced", "fit_reduced_loo", "predict_values", "predict_values_multi", "generate_q", "run_device_kernel", "calculate_w", "ResidentProblem",
+__all__ = ["Options", "Predictor", "solve_system_of_linear_equations", "solve_refined", "solve_cost_path", "solve_pcg", "fit_reduced", "fit_reduced_loo", "select_landmarks", "predict_values", "predict_values_multi", "generate_q", "run_device_kernel", "calculate_w", "ResidentProblem",
            "comm_get_unique_id", "comm_init", "comm_destroy"]
 
 
@@ -219,6 +219,53 @@ def _landmarks_argument(rank: int, landmarks):
     return int(lm.size), lm, lm.ctypes.data_as(C.POINTER(C.c_uint64))
 
 
+def _select_arguments(N: int, rank, method, pool, seed, tol):
+    """The arguments of a landmark selection as the library takes them, checked as it checks them: ``(rank, method code, pool, seed, tol)``."""
+    code = _capi.LANDMARK_METHODS.get(method) if isinstance(method, str) else None
+    if code is None:
+        raise InvalidParameterError(f"The landmark rule must be one of {sorted(_capi.LANDMARK_METHODS)}, but is {method!r}!")
+    for name, value in (("rank", rank), ("pool", pool), ("seed", seed)):
+        if not (isinstance(value, (int, np.integer)) and not isinstance(value, bool) and 0 <= int(value) < 2 ** 64):
+            raise InvalidParameterError(f"{name} must be a non-negative integer, but is {value!r}!")
+    rank, pool = int(rank), int(pool)
+    if pool > N or 0 < pool < rank:
+        raise InvalidParameterError(f"The candidate pool must be 0 (all {N} points) or lie in [rank, {N}], but is {pool} at rank {rank}!")
+    most = min(pool if pool > 0 else N, _capi.SELECT_MAX_RANK)
+    if not 1 <= rank <= most:
+        raise InvalidParameterError(f"The number of landmarks to select must lie in [1, {most}], but is {rank}!")
+    try:
+        tol = float(tol)
+    except (TypeError, ValueError):
+        raise InvalidParameterError(f"The tolerance of the landmark selection must be a number, but is {tol!r}!") from None
+    if not (np.isfinite(tol) and tol >= 0.0):
+        raise InvalidParameterError(f"The tolerance of the landmark selection must be finite and not negative, but is {tol}!")
+    return rank, code, pool, int(seed), tol
+
+
+def _select_call(fn, head, N: int, rank: int, code: int, pool: int, seed: int, tol: float, tail=()):
+    lm = np.zeros(rank, dtype=np.uint64)
+    trace, residual = np.zeros(rank), np.zeros(N)
+    info = _capi.LssvmLandmarkSelectInfo()
+    dp = C.POINTER(C.c_double)
+    check(fn(*head, rank, code, pool, seed, tol, lm.ctypes.data_as(C.POINTER(C.c_uint64)), trace.ctypes.data_as(dp), residual.ctypes.data_as(dp), C.byref(info), *tail))
+    return lm[:int(info.rank_found)].copy(), trace, residual, info.as_dict()
+
+
+def select_landmarks(params: Parameter, A, rank: int, method: str = "rpcholesky", pool: int = 0, seed: int = 0, tol: float = 0.0, options: Options | None = None):
+    """``rank`` landmarks chosen from the data by a pivoted partial Cholesky factorisation of the kernel matrix (``lssvm_mi355_select_landmarks_*``; opt-in, DESIGN.md
+    section 14).  ``method``: ``"greedy"`` (the largest residual diagonal entry) or ``"rpcholesky"`` (at random in proportion to the residual diagonal, from ``seed``);
+    neither dominates the other or the fixed rule.  ``pool``: 0 = every point is a candidate, else the first ``pool`` points of the library's fixed shuffle (it bounds the
+    work space, ``rank x pool`` doubles).  ``tol``: stop once the pivot's residual falls to ``max(tol, 64 eps64)`` times the largest diagonal entry.  Returns
+    ``(landmarks[:rank_found], trace[rank], residual[N], info)``: the indices for the ``landmarks`` argument of :func:`solve_pcg` / :func:`fit_reduced`, the trace of the
+    Nystrom residual after every step, the final residual diagonal (NaN outside the pool) and the ``lssvm_landmark_select_info`` dict.  Device 0; deterministic."""
+    A = _as_matrix(A)
+    N, d = A.shape
+    rank, code, pool, seed, tol = _select_arguments(N, rank, method, pool, seed, tol)
+    ps = _params_struct(params, d)
+    fn = _capi.select_entry(f"lssvm_mi355_select_landmarks_{suffix_of(A.dtype)}")
+    return _select_call(fn, (C.byref(ps), ptr(A), N, d), N, rank, code, pool, seed, tol, tail=(options_ptr(options),))
+
+
 def _pcg_call(fn, head, middle, B2, single: bool, N: int, dtype, eps: float, max_iter: int, tail=()):
     k = B2.shape[0]
     alphas = np.zeros((k, N), dtype=dtype)
@@ -234,11 +281,16 @@ def _pcg_call(fn, head, middle, B2, single: bool, N: int, dtype, eps: float, max
 def solve_pcg(params: Parameter, A, B, eps: float, max_iter: int, rank: int = 256, landmarks=None, options: Options | None = None):
     """The system(s) solved by CG preconditioned with a Nystrom approximation of ``rank`` landmarks (``lssvm_mi355_solve_pcg_*``; opt-in: it pays where the kernel matrix
     has spectral decay and costs iterations where it has none).  ``B``: one right-hand side ``(N,)`` or ``k`` of them ``(k, N)``, solved one after the other on ONE
-    preconditioner.  ``landmarks``: distinct point indices (their number is the rank) or None for the library's fixed choice.  The stop test is that of
+    preconditioner.  ``landmarks``: distinct point indices (their number is the rank), None for the library's fixed choice, or ``"greedy"`` / ``"rpcholesky"`` for
+    ``rank`` points chosen by :func:`select_landmarks` (fewer where the kernel matrix's rank is exhausted first).  The stop test is that of
     :func:`solve_system_of_linear_equations`.  Returns ``(alphas, rhos, infos)`` shaped like ``B`` (``infos``: ``lssvm_pcg_info`` dicts).  Device 0; deterministic."""
     A = _as_matrix(A)
     N, d = A.shape
     B2, single = _pcg_arguments(B, N, A.dtype, eps, max_iter)
+    if isinstance(landmarks, str):  # a selection rule: one resident problem selects, builds and solves (the data is uploaded once)
+        with ResidentProblem(params, A, options=options) as prob:
+            prob.build_preconditioner(rank, landmarks)
+            return prob.solve_pcg(B, eps, max_iter)
     rank, lm, lm_ptr = _landmarks_argument(rank, landmarks)
     ps = _params_struct(params, d)
     fn = _capi.pcg_entry(f"lssvm_mi355_solve_pcg_{suffix_of(A.dtype)}")
@@ -279,11 +331,14 @@ def _reduced_call(fn, head, Y2, single: bool, rank: int, lm_ptr, slab_rows: int,
 def fit_reduced(params: Parameter, A, Y, rank: int, landmarks=None, slab_rows: int = 0, options: Options | None = None):
     """The fixed-size (reduced) LS-SVM over ``rank`` landmark points (``lssvm_mi355_fit_reduced_*``; opt-in: it trades accuracy for a model of ``rank`` support vectors):
     ``f(x) = sum_j beta_j k(x, x_L[j]) - rho`` minimises ``1/2 beta^T K_mm beta + C/2 sum_i (y_i - f(x_i))^2``.  ``Y``: one right-hand side ``(N,)`` or ``k`` of them
-    ``(k, N)`` -- one landmark block, one Gram matrix and one factorisation serve all.  ``landmarks``: distinct point indices (their number is the rank) or None for the
-    preconditioner's fixed rule.  ``slab_rows``: rows of the landmark block held at a time (a multiple of 256; 0: 65 536).  Returns ``(betas, rhos, landmarks, info)``,
+    ``(k, N)`` -- one landmark block, one Gram matrix and one factorisation serve all.  ``landmarks``: distinct point indices (their number is the rank), None for the
+    preconditioner's fixed rule, or ``"greedy"`` / ``"rpcholesky"`` for ``rank`` points chosen by :func:`select_landmarks`.  ``slab_rows``: rows of the landmark block held at a time (a multiple of 256; 0: 65 536).  Returns ``(betas, rhos, landmarks, info)``,
     ``betas`` and ``rhos`` float64 whatever the data's type and shaped like ``Y``; ``info``: the ``lssvm_reduced_info`` dict.  Device 0; deterministic; no CG."""
     A = _as_matrix(A)
     N, d = A.shape
+    if isinstance(landmarks, str):  # a selection rule (:func:`select_landmarks`): one resident problem selects and fits
+        with ResidentProblem(params, A, options=options) as prob:
+            return prob.fit_reduced(Y, rank, landmarks, slab_rows)
     Y2, single, rank, _, lm_ptr, slab_rows = _reduced_arguments(Y, N, A.dtype, rank, landmarks, slab_rows)
     ps = _params_struct(params, d)
     fn = _capi.reduced_entry(f"lssvm_mi355_fit_reduced_{suffix_of(A.dtype)}")
@@ -328,6 +383,9 @@ def fit_reduced_loo(params: Parameter, A, Y, rank: int, costs, landmarks=None, s
     ``y``), ``max_leverage[S]``, ``jitter[S]``, ``infos`` (``lssvm_reduced_loo_info`` dicts).  Everything float64.  Device 0; deterministic."""
     A = _as_matrix(A)
     N, d = A.shape
+    if isinstance(landmarks, str):  # a selection rule (:func:`select_landmarks`): one resident problem selects and fits
+        with ResidentProblem(params, A, options=options) as prob:
+            return prob.fit_reduced_loo(Y, rank, costs, landmarks, slab_rows)
     Y2, single, rank, _, lm_ptr, slab_rows = _reduced_arguments(Y, N, A.dtype, rank, landmarks, slab_rows)
     costs = _reduced_loo_costs(costs)
     ps = _params_struct(params, d)
@@ -663,11 +721,23 @@ class ResidentProblem:
         y, costs = _cost_path_arguments(y, self.num_points, self.dtype, costs, eps, max_iter)
         return _cost_path_call(_capi.cost_path_entry("lssvm_mi355_problem_solve_cost_path"), (self._h,), y, costs, self.num_points, self.dtype, eps, max_iter, verify)
 
+    def select_landmarks(self, rank: int, method: str = "rpcholesky", pool: int = 0, seed: int = 0, tol: float = 0.0):
+        """:func:`select_landmarks` on this resident problem (``lssvm_mi355_problem_select_landmarks``): ``(landmarks[:rank_found], trace, residual, info)``.  The problem
+        is left as it was and keeps its preconditioner.  Not on a problem of several devices or ranks, not with weights set, not between :meth:`cg_begin` and
+        :meth:`cg_finish`."""
+        rank, code, pool, seed, tol = _select_arguments(self.num_points, rank, method, pool, seed, tol)
+        return _select_call(_capi.select_entry("lssvm_mi355_problem_select_landmarks"), (self._h,), self.num_points, rank, code, pool, seed, tol)
+
+    def _selected(self, rank, landmarks):
+        """``landmarks`` as the entry points that consume them take it: a selection rule's name becomes the indices :meth:`select_landmarks` finds for ``rank`` (fewer where
+        the rank is exhausted first); everything else passes through."""
+        return self.select_landmarks(rank, method=landmarks)[0] if isinstance(landmarks, str) else landmarks
+
     def build_preconditioner(self, rank: int = 256, landmarks=None):
         """The Nystrom preconditioner of this problem at its own cost (``lssvm_mi355_problem_build_preconditioner``): ``rank`` landmarks of the library's fixed choice, or
-        the given distinct point indices (their number is the rank).  Building again replaces it.  Returns the ``lssvm_precond_info`` dict.  Not on a problem of several
+        the given distinct point indices (their number is the rank), or ``"greedy"`` / ``"rpcholesky"``: ``rank`` points of :meth:`select_landmarks`.  Building again replaces it.  Returns the ``lssvm_precond_info`` dict.  Not on a problem of several
         devices or ranks, not with weights set, not between :meth:`cg_begin` and :meth:`cg_finish`."""
-        rank, lm, lm_ptr = _landmarks_argument(rank, landmarks)
+        rank, lm, lm_ptr = _landmarks_argument(rank, self._selected(rank, landmarks))
         info = _capi.LssvmPrecondInfo()
         check(_capi.pcg_entry("lssvm_mi355_problem_build_preconditioner")(self._h, rank, lm_ptr, C.byref(info)))
         self._precond_rank = rank
@@ -697,7 +767,7 @@ class ResidentProblem:
     def fit_reduced(self, Y, rank: int, landmarks=None, slab_rows: int = 0):
         """:func:`fit_reduced` on this resident problem at its own cost (``lssvm_mi355_problem_fit_reduced``).  The problem is left as it was and keeps its preconditioner.
         Not on a problem of several devices or ranks, not with weights set, not between :meth:`cg_begin` and :meth:`cg_finish`."""
-        Y2, single, rank, _, lm_ptr, slab_rows = _reduced_arguments(Y, self.num_points, self.dtype, rank, landmarks, slab_rows)
+        Y2, single, rank, _, lm_ptr, slab_rows = _reduced_arguments(Y, self.num_points, self.dtype, rank, self._selected(rank, landmarks), slab_rows)
         return _reduced_call(_capi.reduced_entry("lssvm_mi355_problem_fit_reduced"), (self._h,), Y2, single, rank, lm_ptr, slab_rows)
 
     def landmark_gram(self, Y, rank: int, landmarks=None, slab_rows: int = 0):
@@ -712,7 +782,7 @@ class ResidentProblem:
     def fit_reduced_loo(self, Y, rank: int, costs, landmarks=None, slab_rows: int = 0):
         """:func:`fit_reduced_loo` on this resident problem (``lssvm_mi355_problem_fit_reduced_loo``): leave-one-out with the landmark set held fixed, at every cost of
         ``costs``.  The problem's own cost is ignored; the problem is left as it was and keeps its preconditioner.  Refused where :meth:`fit_reduced` is."""
-        Y2, single, rank, _, lm_ptr, slab_rows = _reduced_arguments(Y, self.num_points, self.dtype, rank, landmarks, slab_rows)
+        Y2, single, rank, _, lm_ptr, slab_rows = _reduced_arguments(Y, self.num_points, self.dtype, rank, self._selected(rank, landmarks), slab_rows)
         costs = _reduced_loo_costs(costs)
         return _reduced_loo_call(_capi.reduced_loo_entry("lssvm_mi355_problem_fit_reduced_loo"), (self._h,), Y2, single, self.num_points, rank, lm_ptr, slab_rows, costs)
 

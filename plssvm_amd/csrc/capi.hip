@@ -247,6 +247,17 @@ void fit_reduced_loo_one_shot(const lssvm_params *params, const T *X, size_t N, 
     prob.fit_reduced_loo(Y, num_rhs, rank, landmarks, slab_rows, costs, num_costs, betas_out, rhos_out, leverage_out, fitted_out, loo_out, press_out, loo_errors_out, landmarks_out, infos);
 }
 
+/* lssvm_mi355_select_landmarks_*: likewise */
+template <typename T>
+void select_landmarks_one_shot(const lssvm_params *params, const T *X, size_t N, size_t d, uint64_t rank, int method, uint64_t pool, uint64_t seed, double tol, uint64_t *landmarks_out,
+                               double *trace_out, double *residual_out, lssvm_landmark_select_info *info, const lssvm_mi355_options *options) {
+    lssvm::check_params(params);
+    check_data(X, N, d);
+    (void) lssvm::check_select_arguments(rank, method, pool, tol, landmarks_out, N);
+    lssvm::Solver<T> prob = device0_solver<T>(options, *params, X, N, d);
+    prob.select_landmarks(rank, method, pool, seed, tol, landmarks_out, trace_out, residual_out, info);
+}
+
 template <typename T>
 void generate_q_one_shot(const lssvm_params *params, const T *X, size_t N, size_t d, T *q_out, const lssvm_mi355_options *options) {
     lssvm::check_params(params);
@@ -713,6 +724,24 @@ int lssvm_mi355_fit_reduced_f64(const lssvm_params *params, const double *X, siz
     return guarded([&] { fit_reduced_one_shot<double>(params, X, num_points, num_features, Y, num_rhs, rank, landmarks, slab_rows, betas_out, rhos_out, landmarks_out, info, options); });
 }
 static_assert(sizeof(lssvm_reduced_loo_info) == 56, "lssvm_reduced_loo_info changed: plssvm_amd/_capi.py (LssvmReducedLooInfo) changes with it");
+static_assert(sizeof(lssvm_landmark_select_info) == 56, "lssvm_landmark_select_info changed: plssvm_amd/_capi.py (LssvmLandmarkSelectInfo) changes with it");
+int lssvm_mi355_problem_select_landmarks(lssvm_mi355_problem *p, uint64_t rank, int method, uint64_t pool, uint64_t seed, double tol, uint64_t *landmarks_out, double *trace_out,
+                                         double *residual_out, lssvm_landmark_select_info *info) {
+    return guarded([&] {
+        LSSVM_REQUIRE(p != nullptr, "problem handle must not be NULL");
+        (void) lssvm::check_select_arguments(rank, method, pool, tol, landmarks_out, 0);  // (before any device work; N: the solver)
+        impl_of(p)->select_landmarks(rank, method, pool, seed, tol, landmarks_out, trace_out, residual_out, info);
+    });
+}
+int lssvm_mi355_select_landmarks_f32(const lssvm_params *params, const float *X, size_t num_points, size_t num_features, uint64_t rank, int method, uint64_t pool, uint64_t seed, double tol,
+                                     uint64_t *landmarks_out, double *trace_out, double *residual_out, lssvm_landmark_select_info *info, const lssvm_mi355_options *options) {
+    return guarded([&] { select_landmarks_one_shot<float>(params, X, num_points, num_features, rank, method, pool, seed, tol, landmarks_out, trace_out, residual_out, info, options); });
+}
+int lssvm_mi355_select_landmarks_f64(const lssvm_params *params, const double *X, size_t num_points, size_t num_features, uint64_t rank, int method, uint64_t pool, uint64_t seed, double tol,
+                                     uint64_t *landmarks_out, double *trace_out, double *residual_out, lssvm_landmark_select_info *info, const lssvm_mi355_options *options) {
+    return guarded([&] { select_landmarks_one_shot<double>(params, X, num_points, num_features, rank, method, pool, seed, tol, landmarks_out, trace_out, residual_out, info, options); });
+}
+
 int lssvm_mi355_problem_fit_reduced_loo(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *costs, size_t num_costs,
                                         double *betas_out, double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out,
                                         uint64_t *landmarks_out, lssvm_reduced_loo_info *infos) {

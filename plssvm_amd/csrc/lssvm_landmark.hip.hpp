@@ -24,6 +24,23 @@ struct PcVec<double> {
     static constexpr int n = 2;
 };
 
+/* k(a, b) from the sum over the features (ascending) of (a_f - b_f)^2 (rbf) or a_f b_f (polynomial, linear): the one epilogue of the landmark block and of the
+ * landmark selection's columns (lssvm_select.hip) */
+__device__ __forceinline__ double landmark_kernel_value(int kernel_type, int degree, double gamma, double coef0, double acc) {
+    double k;
+    if (kernel_type == LSSVM_KERNEL_RBF) {
+        k = exp(-gamma * acc);
+    } else if (kernel_type == LSSVM_KERNEL_POLYNOMIAL) {
+        const double base = gamma * acc + coef0;
+        k = 1.0;
+        for (int e = 0; e < abs(degree); ++e) k *= base;
+        if (degree < 0) k = 1.0 / k;
+    } else {
+        k = gamma * acc;
+    }
+    return k;
+}
+
 /* Kd[l][i - row0] = k(x_i, x_lm[l]) for the points row0 <= i < N of this launch's row blocks (exact zeros from N on) and a tile of 16 landmarks, in double: the
  * landmarks' features go through LDS in chunks of 32, a thread walks its own row in 16-byte pieces.  `gamma`: the kernel function's, divided by the square of the
  * factor X_ carries.  `ldN`: doubles between two landmarks' columns; the grid's x extent times 256 rows are written from column offset 0 on. */
@@ -67,24 +84,14 @@ __global__ __launch_bounds__(256) void k_landmark_block(const T *__restrict__ X,
 #pragma unroll
     for (int l = 0; l < 16; ++l) {
         if (l0 + l >= m) continue;
-        double k;
-        if (kernel_type == LSSVM_KERNEL_RBF) {
-            k = exp(-gamma * acc[l]);
-        } else if (kernel_type == LSSVM_KERNEL_POLYNOMIAL) {
-            const double base = gamma * acc[l] + coef0;
-            k = 1.0;
-            for (int e = 0; e < abs(degree); ++e) k *= base;
-            if (degree < 0) k = 1.0 / k;
-        } else {
-            k = gamma * acc[l];
-        }
+        const double k = landmark_kernel_value(kernel_type, degree, gamma, coef0, acc[l]);
         Kd[static_cast<size_t>(l0 + l) * ldN + local] = i < N ? k : 0.0;
     }
 }
 
 /* Kmm[k][l] = slab[l][lm[k] - row0] for the landmarks that lie in the rows [row0, row0 + rows) of this column-major slab of the block (ld doubles between two columns); a
  * copy, no arithmetic.  The whole block at once: row0 = 0, rows = ld.  (static: a kernel that is no template cannot be inline, and both units that include this launch it) */
-static __global__ void k_gather_kmm(const double *__restrict__ slab, size_t ld, int row0, int rows, const int *__restrict__ lm, int m, double *__restrict__ Kmm) {
+[[maybe_unused]] static __global__ void k_gather_kmm(const double *__restrict__ slab, size_t ld, int row0, int rows, const int *__restrict__ lm, int m, double *__restrict__ Kmm) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= m * m) return;
     const int r = lm[e / m] - row0;
@@ -100,9 +107,7 @@ class LandmarkBlock {
     /* enqueues the upload of the indices on `st`; the problem outlives the block */
     LandmarkBlock(const Problem<T> &p, const std::vector<uint64_t> &landmarks, hipStream_t st) :
         p_(p), st_(st), m_(static_cast<int>(landmarks.size())), lm_host_(landmarks.begin(), landmarks.end()) {
-        const double scale2 = p.x_scale_ * p.x_scale_;
-        gamma_ = p.params_.kernel_type == LSSVM_KERNEL_LINEAR ? 1.0 / scale2 : static_cast<double>(static_cast<T>(p.params_.gamma)) / scale2;
-        coef0_ = static_cast<double>(static_cast<T>(p.params_.coef0));
+        kernel_scalars(p, gamma_, coef0_);
         lm_dev_.alloc_zero(static_cast<size_t>(m_), st);
         LSSVM_HIP_CHECK(hipMemcpyAsync(lm_dev_.p, lm_host_.data(), static_cast<size_t>(m_) * sizeof(int), hipMemcpyHostToDevice, st));
     }
@@ -116,6 +121,12 @@ class LandmarkBlock {
         hipLaunchKernelGGL(k_gather_kmm, dim3((m_ * m_ + 255) / 256), dim3(256), 0, st_, slab, ld, static_cast<int>(row0), rows, lm_dev_.p, m_, Kmm);
     }
     size_t device_bytes() const { return lm_dev_.count * sizeof(int); }
+    /* gamma and coef0 for the data as X_ holds it (the rule above); the landmark selection evaluates its columns with them (lssvm_select.hip) */
+    static void kernel_scalars(const Problem<T> &p, double &gamma, double &coef0) {
+        const double scale2 = p.x_scale_ * p.x_scale_;
+        gamma = p.params_.kernel_type == LSSVM_KERNEL_LINEAR ? 1.0 / scale2 : static_cast<double>(static_cast<T>(p.params_.gamma)) / scale2;
+        coef0 = static_cast<double>(static_cast<T>(p.params_.coef0));
+    }
 
   private:
     const Problem<T> &p_;

@@ -631,6 +631,9 @@ struct ProblemBase {
     virtual void reduced_leverage(uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *V, const double *shift, const double *B_extra, size_t k, double *h_out,
                                   double *f_out) = 0;  // lssvm_mi355_problem_reduced_leverage
     virtual void time_leverage_kernel(uint64_t rank, uint64_t slab_rows, size_t k, int repeats, double *gram_ms_out, double *leverage_ms_out) = 0;  // lssvm_mi355_problem_time_leverage_kernel
+    /* landmark selection: the pivots of a greedy or randomly pivoted partial Cholesky factorisation (lssvm_select.hip) */
+    virtual void select_landmarks(uint64_t rank, int method, uint64_t pool, uint64_t seed, double tol, uint64_t *landmarks_out, double *trace_out, double *residual_out,
+                                  lssvm_landmark_select_info *info) = 0;  // lssvm_mi355_problem_select_landmarks
     virtual void cg_begin(const void *y, double eps) = 0;
     virtual void cg_step(uint64_t iterations, int *done_out) = 0;
     virtual void cg_finish(void *alpha_out, double *rho_out, lssvm_cg_info *info) = 0;
@@ -730,6 +733,9 @@ class Solver final : public ProblemBase {
     void reduced_leverage(uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *V, const double *shift, const double *B_extra, size_t k, double *h_out,
                           double *f_out) override;
     void time_leverage_kernel(uint64_t rank, uint64_t slab_rows, size_t k, int repeats, double *gram_ms_out, double *leverage_ms_out) override;
+    /* the pivots of a partial Cholesky factorisation of K over the candidates, one launch pair per step on shard 0's stream (lssvm_select.hip) */
+    void select_landmarks(uint64_t rank, int method, uint64_t pool, uint64_t seed, double tol, uint64_t *landmarks_out, double *trace_out, double *residual_out,
+                          lssvm_landmark_select_info *info) override;
     void cg_begin(const void *y, double eps) override;
     /* cg_begin for the inner solve of the mixed-precision refinement: A e = r / max|r| from e = 0 -- b, the first residual and delta0 = b^T b come from ONE O(n) kernel
      * over the outer fp64 residual `r_dev` (device 0, complete when the call is made; `absmax_part_dev`: k_absmax's partials of it), no Gram pass.  cg_step follows as
@@ -820,6 +826,10 @@ void check_reduced_arguments(const void *Y, size_t num_rhs, uint64_t rank, uint6
 /* the cost grid of lssvm_mi355_problem_fit_reduced_loo / lssvm_mi355_fit_reduced_loo_*: 1 ... REDUCED_LOO_MAX_COSTS costs, each finite and positive */
 constexpr size_t REDUCED_LOO_MAX_COSTS = 64;
 void check_reduced_loo_costs(const double *costs, size_t num_costs);
+
+/* the arguments of lssvm_mi355_problem_select_landmarks / lssvm_mi355_select_landmarks_* that need no device (lssvm_select.hip); returns the number of candidates */
+constexpr int SELECT_MAX_RANK = 1024;
+size_t check_select_arguments(uint64_t rank, int method, uint64_t pool, double tol, const uint64_t *landmarks_out, size_t num_points);
 
 /* the arguments of lssvm_mi355_problem_solve_cost_path / lssvm_mi355_solve_cost_path_* that need no device: checked before one is touched (lssvm_path.hip) */
 constexpr size_t PATH_MAX_COSTS = 64;

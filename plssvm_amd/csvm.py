@@ -168,14 +168,15 @@ class CSVM:
 
     def fit_reduced(self, data: DataSet, rank: int, landmarks=None) -> Model:
         """A fixed-size (reduced) LS-SVM model of ``rank`` support vectors (no counterpart in the reference): the decision function is expanded over
-        ``rank`` landmark points only -- the library's fixed choice (the preconditioner's rule) or the distinct point indices ``landmarks``, whose number is then the rank --
+        ``rank`` landmark points only -- the library's fixed choice (the preconditioner's rule), the distinct point indices ``landmarks``, whose number is then the rank, or
+        ``"greedy"`` / ``"rpcholesky"`` for ``rank`` points selected from the data (``backend.select_landmarks``; fewer where the kernel matrix's rank is exhausted first) --
         and fitted to ALL points by one pass over the N x rank kernel block and a dense solve, without CG.  The model is an ordinary :class:`Model` whose data set is
         the landmark rows of ``data`` (file format, predict, score); it trades accuracy for size.  A two-class model file groups its support vectors by class, so the
         landmarks must hold points of both classes.  ``last_cg_info`` keeps the ``lssvm_reduced_info`` report with ``iterations`` = 0."""
         if not data.has_labels():
             raise InvalidParameterError("No labels given for training! Maybe the data is only usable for prediction?")  # csvm.hpp:298
         labels = data.labels()
-        if landmarks is not None:
+        if landmarks is not None and not isinstance(landmarks, str):  # (a selection rule's points are checked once they are known)
             _check_landmark_classes(data, landmarks)  # (before anything is computed)
         params = self.params.resolved(data.num_features())
         t0 = time.perf_counter()
@@ -200,7 +201,7 @@ class CSVM:
         if not data.has_labels():
             raise InvalidParameterError("No labels given for training! Maybe the data is only usable for prediction?")  # csvm.hpp:298
         labels = data.labels()
-        if landmarks is not None:
+        if landmarks is not None and not isinstance(landmarks, str):  # (a selection rule's points are checked once they are known)
             _check_landmark_classes(data, landmarks)  # (before anything is computed)
         costs = _checked_costs(costs)
         params = self.params.resolved(data.num_features())
@@ -288,13 +289,15 @@ def _drop_zero_weights(data: DataSet, sample_weight):
 class MI355CSVM(CSVM):
     """The MI355X backend (counterpart of plssvm::hip::csvm, HIP/csvm.hpp:39-99, csvm.hip.cpp:47-85)."""
 
-    def __init__(self, target=TargetPlatform.AUTOMATIC, params: Parameter | None = None, num_devices: int = 1, solver: str = "cg", precond_rank: int = 256, **kwargs):
+    def __init__(self, target=TargetPlatform.AUTOMATIC, params: Parameter | None = None, num_devices: int = 1, solver: str = "cg", precond_rank: int = 256, precond_landmarks=None,
+                 **kwargs):
         """``solver``: ``"cg"`` (default) = the CG of the data's real type; ``"refined"`` = float64 data on ONE device is solved by mixed-precision refinement
         (``backend.solve_refined``: float32 CG iterations on the matrix cores inside a float64 residual loop, same stop test; the gain grows with the iteration
         count) and ``last_refine_info`` keeps the per-solve reports -- float32 data or several devices solve as with ``"cg"`` and leave it None;
         ``"pcg"`` = CG preconditioned with a Nystrom approximation of ``precond_rank`` landmarks (``backend.solve_pcg``), same stop test, built once per
         data set and shared by all right-hand sides -- opt-in: it saves iterations where the kernel matrix has spectral decay and costs some where it has none; one device
-        and no sample weights (both raise).
+        and no sample weights (both raise).  ``precond_landmarks``: None = the library's fixed choice of landmarks, ``"greedy"`` / ``"rpcholesky"`` = ``precond_rank`` points
+        selected from the data (``backend.select_landmarks``).
 
         ``num_devices``: devices ONE solve is sharded over -- 1 (default) = device 0 only, k = devices 0 .. k-1 (gpu_csvm.hpp:283-299),
         0 = automatic (every visible device, at least 4096 points each, as the reference's backends take every device they find,
@@ -306,9 +309,12 @@ class MI355CSVM(CSVM):
             raise InvalidParameterError(f"solver must be 'cg' or 'refined' or 'pcg', but is {solver!r}!")
         if solver == "pcg" and not (isinstance(precond_rank, (int, np.integer)) and 1 <= int(precond_rank) <= _capi.PRECOND_MAX_RANK):
             raise InvalidParameterError(f"precond_rank must lie in [1, {_capi.PRECOND_MAX_RANK}], but is {precond_rank!r}!")
+        if precond_landmarks is not None and precond_landmarks not in _capi.LANDMARK_METHODS:
+            raise InvalidParameterError(f"precond_landmarks must be None or one of {sorted(_capi.LANDMARK_METHODS)}, but is {precond_landmarks!r}!")
         super().__init__(params, **kwargs)
         self.solver = solver
         self.precond_rank = int(precond_rank) if solver == "pcg" else None
+        self.precond_landmarks = precond_landmarks if solver == "pcg" else None
         self.last_refine_info = None
         if target not in (TargetPlatform.AUTOMATIC, TargetPlatform.GPU_AMD):
             raise BackendError(f"Invalid target platform '{target.value}' for the MI355 backend!")
@@ -335,7 +341,7 @@ class MI355CSVM(CSVM):
         self.last_refine_info = None
         if self.solver == "pcg":
             self._pcg_applies(sample_weight)
-            return backend.solve_pcg(params, A, b, eps, max_iter, rank=self._pcg_rank(A), options=self._options)
+            return backend.solve_pcg(params, A, b, eps, max_iter, rank=self._pcg_rank(A), landmarks=self.precond_landmarks, options=self._options)
         if self._refines(A):
             alpha, rho, info, refine = backend.solve_refined(params, A, b, eps, max_iter, sample_weight=sample_weight, options=self._options)
             self.last_refine_info = [refine]
@@ -419,7 +425,7 @@ class MI355CSVM(CSVM):
             B = np.asarray(B)
             if B.ndim != 2 or B.shape[0] == 0:
                 raise InvalidParameterError("The right-hand sides must be a matrix with one row per system and at least one row!")
-            return backend.solve_pcg(params, A, B, eps, max_iter, rank=self._pcg_rank(A), options=self._options)
+            return backend.solve_pcg(params, A, B, eps, max_iter, rank=self._pcg_rank(A), landmarks=self.precond_landmarks, options=self._options)
         if self.use_devices != 1:
             return super().solve_systems_of_linear_equations(params, A, B, eps, max_iter, sample_weight=sample_weight)
         if self._refines(A):

@@ -306,7 +306,8 @@ def fit_cost_path(estimator, X, y, Cs):
 # ---------------------------------------------------------------------------------------------------------------------
 def fit_reduced(estimator, X, y, rank, landmarks=None):
     """A fitted clone of ``estimator`` whose model has ``rank`` support vectors only (the fixed-size LS-SVM, :meth:`plssvm_amd.csvm.CSVM.fit_reduced`): the library's fixed
-    choice of landmark points or the distinct row indices ``landmarks`` (their number is then the rank).  Two classes and one-vs-all alike; one landmark block, one Gram
+    choice of landmark points, the distinct row indices ``landmarks`` (their number is then the rank), or ``"greedy"`` / ``"rpcholesky"`` for ``rank`` points selected from the
+    data (``backend.select_landmarks``).  Two classes and one-vs-all alike; one landmark block, one Gram
     matrix and one factorisation serve all classes.  No CG runs: ``tol`` and ``max_iter`` play no part and ``n_iter_`` is 0.  ``support_`` holds the landmarks,
     ``dual_coef_`` has shape ``(n_classifiers, rank)``.  ``class_weight`` must be None; ``estimator`` itself stays unfitted."""
     if not isinstance(estimator, SVC):
@@ -344,8 +345,8 @@ def fit_reduced(estimator, X, y, rank, landmarks=None):
 
 
 def _landmarks_of(svm, landmarks):
-    """The rows a reduced two-class fit used: the caller's, or the library's own for the training set's size (read back from the backend's report)."""
-    return np.asarray(svm.last_cg_info["landmarks"] if landmarks is None else landmarks).astype(np.int32)
+    """The rows a reduced two-class fit used: the caller's, or the library's own or selected ones (read back from the backend's report)."""
+    return np.asarray(svm.last_cg_info["landmarks"] if landmarks is None or isinstance(landmarks, str) else landmarks).astype(np.int32)
 
 
 def fit_reduced_cv(estimator, X, y, rank, Cs, landmarks=None):
