@@ -571,6 +571,47 @@ int lssvm_mi355_fit_reduced_loo_f64(const lssvm_params *params, const double *X,
                                     double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out, lssvm_reduced_loo_info *infos,
                                     const lssvm_mi355_options *options);
 
+/* The two fits above with their dense steps on the device (opt-in).  The entry points mirror the six above argument for argument and add one trailing
+ * `dense` (may be NULL; the leave-one-out forms: num_costs records).  Where the host forms download St and K_mm and run scalar loops on one host thread, these keep both
+ * on the device: per cost and jitter attempt one kernel assembles the lower triangle of M + nu I = S - s s^T / N + sigma K_mm + nu I and the right-hand sides
+ * t_c - s eta_c / N, a blocked left-looking Cholesky factorisation (block width `block`; per block column an update on v_mfma_f64_16x16x4_f64, the diagonal block factored
+ * in LDS, a panel solve against it) gives L, one workgroup per right-hand side solves L z = rhs, L^T beta = z and forms rho, and -- leave-one-out only -- V = L^-1 is formed
+ * row block by row block with triangular solves against the diagonal blocks (no inverted block is multiplied in) straight into the leverage kernel's operand.  Only the
+ * betas, the rhos and one status word per attempt come back.  A pivot that is not positive and finite ends the attempt: every later kernel of it returns at once, the host
+ * reads the word and retries with the tenfold nu, seven attempts as above, the same refusal after the last.  nu's start value is eps64 trace(M) taken on the host in the
+ * host path's order: where no retry happens `jitter` has the host path's bits.  Deterministic: no atomics, every sum in a fixed order, the same bits for the same arguments;
+ * row c of a call has the bits of the call with that right-hand side alone, a cost the bits of the call with that cost alone, betas and rhos of a leave-one-out cost the
+ * bits of lssvm_mi355_problem_fit_reduced_dev at that cost.  The results are NOT the host path's bits (another order of the sums), and on a numerically singular M the
+ * number of jitter retries may differ from the host path's.  `host_ms` of the info records then holds what is left on the host (the trace, the waits, the copies of
+ * betas and rhos).  Refusals: those of the host forms, all before a device is touched.  Nothing selects these automatically. */
+typedef struct lssvm_dense_info {
+    uint64_t rank, block;  /* m and the block width of the factorisation */
+    uint64_t attempts;     /* factorisations tried: 1 + the jitter retries */
+    uint64_t launches;     /* kernels launched by the last attempt */
+    double   jitter;       /* nu of the last attempt */
+    double   assemble_ms, factor_ms, solve_ms, invert_ms; /* device time between events, last attempt (invert_ms: 0 without leave-one-out) */
+} lssvm_dense_info;
+int lssvm_mi355_problem_fit_reduced_dev(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, double *betas_out,
+                                        double *rhos_out, uint64_t *landmarks_out, lssvm_reduced_info *info, lssvm_dense_info *dense);
+int lssvm_mi355_fit_reduced_dev_f32(const lssvm_params *params, const float *X, size_t num_points, size_t num_features, const float *Y, size_t num_rhs, uint64_t rank,
+                                    const uint64_t *landmarks, uint64_t slab_rows, double *betas_out, double *rhos_out, uint64_t *landmarks_out, lssvm_reduced_info *info,
+                                    const lssvm_mi355_options *options, lssvm_dense_info *dense);
+int lssvm_mi355_fit_reduced_dev_f64(const lssvm_params *params, const double *X, size_t num_points, size_t num_features, const double *Y, size_t num_rhs, uint64_t rank,
+                                    const uint64_t *landmarks, uint64_t slab_rows, double *betas_out, double *rhos_out, uint64_t *landmarks_out, lssvm_reduced_info *info,
+                                    const lssvm_mi355_options *options, lssvm_dense_info *dense);
+int lssvm_mi355_problem_fit_reduced_loo_dev(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows,
+                                            const double *costs, size_t num_costs, double *betas_out, double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out,
+                                            double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out, lssvm_reduced_loo_info *infos,
+                                            lssvm_dense_info *dense /* num_costs */);
+int lssvm_mi355_fit_reduced_loo_dev_f32(const lssvm_params *params, const float *X, size_t num_points, size_t num_features, const float *Y, size_t num_rhs, uint64_t rank,
+                                        const uint64_t *landmarks, uint64_t slab_rows, const double *costs, size_t num_costs, double *betas_out, double *rhos_out,
+                                        double *leverage_out, double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out,
+                                        lssvm_reduced_loo_info *infos, const lssvm_mi355_options *options, lssvm_dense_info *dense);
+int lssvm_mi355_fit_reduced_loo_dev_f64(const lssvm_params *params, const double *X, size_t num_points, size_t num_features, const double *Y, size_t num_rhs, uint64_t rank,
+                                        const uint64_t *landmarks, uint64_t slab_rows, const double *costs, size_t num_costs, double *betas_out, double *rhos_out,
+                                        double *leverage_out, double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out,
+                                        lssvm_reduced_loo_info *infos, const lssvm_mi355_options *options, lssvm_dense_info *dense);
+
 /* Landmark selection on a resident problem (opt-in): the pivots of a partial Cholesky factorisation of the kernel matrix, chosen greedily or
  * at random in proportion to the residual diagonal (randomly pivoted Cholesky).  The result is a list of point indices for the `landmarks` argument of the entry points
  * above; nothing else changes, and nothing selects it automatically.  Neither rule dominates the other or the fixed shuffle (README.md has the rows of all three kinds).

@@ -72,6 +72,17 @@ int lssvm_mi355_problem_time_leverage_kernel(lssvm_mi355_problem *p, uint64_t ra
  * |entry|.  Refused without a preconditioner and on an fp32 problem. */
 int lssvm_mi355_problem_time_gram_kernels(lssvm_mi355_problem *p, int repeats, double *parent_ms_out, double *mfma_ms_out, double *max_diff_out);
 
+/* The dense SPD toolbox of the device-factored fixed-size fits alone (lssvm_mi355_problem_fit_reduced_dev), on the caller's HOST arrays: upload, the
+ * toolbox's kernels on device 0, download; everything row major float64, 1 <= m <= 1024, ms_out (may be NULL): device time of the kernels between two events.
+ *   _cholesky      L L^T = A + nu I from the LOWER triangle of A (m x m; what stands above the diagonal is never read).  L_out: m x m, exact zeros above the diagonal.
+ *                  *status_out: 0, or 1 + the column whose pivot was not positive and finite (L_out is then all zeros); the call returns LSSVM_SUCCESS either way.
+ *   _solve         L z = b_c, L^T x_c = z for the k rows b_c of B (k x m; 1 <= k <= 4096) and the lower triangle of L: X_out k x m.  Row c does not depend on k.
+ *   _invert_lower  V = L^-1 by block rows, triangular solves against the diagonal blocks: V_out m x m, exact zeros above the diagonal.
+ * LSSVM_ERR_INVALID_ARGUMENT before a device is touched: m outside 1 ... 1024, k outside 1 ... 4096, a NULL A / L / B / L_out / X_out / V_out / status_out. */
+int lssvm_mi355_dense_cholesky(const double *A, size_t m, double nu, double *L_out, uint64_t *status_out, double *ms_out);
+int lssvm_mi355_dense_solve(const double *L, size_t m, const double *B, size_t k, double *X_out, double *ms_out);
+int lssvm_mi355_dense_invert_lower(const double *L, size_t m, double *V_out, double *ms_out);
+
 /* option names understood by lssvm_mi355_set_option / _get_option besides the fourteen documented in plssvm_amd.h:
  *   "force_collective" 1 = run the per-matvec RCCL collective even with a world of 1 (testing aid; default 0)
  *   "skip_collective"  1 = problems created with world > 1 need no communicator and do NOT exchange their partial K*v (testing aid:

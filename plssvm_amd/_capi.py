@@ -44,6 +44,9 @@ EXPORTED_SYMBOLS = [
     "lssvm_mi355_solve_pcg_f32", "lssvm_mi355_solve_pcg_f64",
     "lssvm_mi355_problem_fit_reduced", "lssvm_mi355_fit_reduced_f32", "lssvm_mi355_fit_reduced_f64", "lssvm_mi355_problem_landmark_gram", "lssvm_mi355_problem_time_gram_kernels",
     "lssvm_mi355_problem_fit_reduced_loo", "lssvm_mi355_fit_reduced_loo_f32", "lssvm_mi355_fit_reduced_loo_f64", "lssvm_mi355_problem_reduced_leverage", "lssvm_mi355_problem_time_leverage_kernel",
+    "lssvm_mi355_problem_fit_reduced_dev", "lssvm_mi355_fit_reduced_dev_f32", "lssvm_mi355_fit_reduced_dev_f64",
+    "lssvm_mi355_problem_fit_reduced_loo_dev", "lssvm_mi355_fit_reduced_loo_dev_f32", "lssvm_mi355_fit_reduced_loo_dev_f64",
+    "lssvm_mi355_dense_cholesky", "lssvm_mi355_dense_solve", "lssvm_mi355_dense_invert_lower",
     "lssvm_mi355_problem_select_landmarks", "lssvm_mi355_select_landmarks_f32", "lssvm_mi355_select_landmarks_f64",
     "lssvm_mi355_cg_begin", "lssvm_mi355_cg_step", "lssvm_mi355_cg_finish", "lssvm_mi355_problem_synchronize", "lssvm_mi355_problem_info",
     "lssvm_mi355_measure_bf16_mfma_ceiling", "lssvm_mi355_comm_library_path", "lssvm_mi355_set_io_threads", "lssvm_mi355_set_option", "lssvm_mi355_get_option",
@@ -249,7 +252,31 @@ def pcg_entry(name: str):
     return fn
 
 
+class LssvmDenseInfo(C.Structure):
+    """``lssvm_dense_info``: the dense steps of one device-factored fit or of one cost of a device-factored leave-one-out grid (``lssvm_mi355_problem_fit_reduced_dev``)."""
+    _fields_ = [("rank", C.c_uint64), ("block", C.c_uint64), ("attempts", C.c_uint64), ("launches", C.c_uint64), ("jitter", C.c_double), ("assemble_ms", C.c_double),
+                ("factor_ms", C.c_double), ("solve_ms", C.c_double), ("invert_ms", C.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 REDUCED_MAX_RANK = 1024
+DENSE_BLOCK = 64  # lssvm::DENSE_BLOCK (plssvm_amd/csrc/lssvm_dense.hip.hpp): the block width of the device's factorisation, solves and inverse
+FACTOR_CHOICES = ("host", "device")
+
+
+def factor_on_device(factor) -> bool:
+    """The ``factor=`` keyword of the fixed-size fits: ``"host"`` (the default) or ``"device"``; anything else is refused before any library call."""
+    if not isinstance(factor, str) or factor not in FACTOR_CHOICES:
+        raise InvalidParameterError(f'factor must be "host" or "device", but is {factor!r}!')
+    return factor == "device"
+
+
+def factor_keyword(factor) -> dict:
+    """``factor`` as a keyword for the backend boundary of ``plssvm_amd.csvm`` -- only where it is not the default, so that a backend object written before the keyword
+    existed still serves the default."""
+    return {} if factor == "host" else {"factor": factor}
 
 
 def reduced_entry(name: str):
@@ -259,8 +286,13 @@ def reduced_entry(name: str):
     if fn.argtypes is None:
         common = [C.c_void_p, C.c_size_t, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint64]  # Y, num_rhs, rank, landmarks, slab_rows
         outs = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(LssvmReducedInfo)]
+        dense = [C.POINTER(LssvmDenseInfo)]
         if name == "lssvm_mi355_problem_fit_reduced":
             fn.argtypes = [C.c_void_p] + common + outs
+        elif name == "lssvm_mi355_problem_fit_reduced_dev":
+            fn.argtypes = [C.c_void_p] + common + outs + dense
+        elif name.startswith("lssvm_mi355_fit_reduced_dev_"):
+            fn.argtypes = [C.POINTER(LssvmParams), C.c_void_p, C.c_size_t, C.c_size_t] + common + outs + [C.c_void_p] + dense
         elif name == "lssvm_mi355_problem_landmark_gram":
             fn.argtypes = [C.c_void_p] + common + [C.POINTER(C.c_double)]
         elif name == "lssvm_mi355_problem_time_gram_kernels":
@@ -291,14 +323,34 @@ def reduced_loo_entry(name: str):
         dp, up = C.POINTER(C.c_double), C.POINTER(C.c_uint64)
         common = [C.c_void_p, C.c_size_t, C.c_uint64, up, C.c_uint64, dp, C.c_size_t]  # Y, num_rhs, rank, landmarks, slab_rows, costs, num_costs
         outs = [dp, dp, dp, dp, dp, dp, up, up, C.POINTER(LssvmReducedLooInfo)]  # betas, rhos, leverage, fitted, loo, press, loo_errors, landmarks, infos
+        dense = [C.POINTER(LssvmDenseInfo)]
         if name == "lssvm_mi355_problem_fit_reduced_loo":
             fn.argtypes = [C.c_void_p] + common + outs
+        elif name == "lssvm_mi355_problem_fit_reduced_loo_dev":
+            fn.argtypes = [C.c_void_p] + common + outs + dense
+        elif name.startswith("lssvm_mi355_fit_reduced_loo_dev_"):
+            fn.argtypes = [C.POINTER(LssvmParams), C.c_void_p, C.c_size_t, C.c_size_t] + common + outs + [C.c_void_p] + dense
         elif name == "lssvm_mi355_problem_reduced_leverage":
             fn.argtypes = [C.c_void_p, C.c_uint64, up, C.c_uint64, dp, dp, dp, C.c_size_t, dp, dp]
         elif name == "lssvm_mi355_problem_time_leverage_kernel":
             fn.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, dp, dp]
         else:
             fn.argtypes = [C.POINTER(LssvmParams), C.c_void_p, C.c_size_t, C.c_size_t] + common + outs + [C.c_void_p]
+        fn.restype = C.c_int
+    return fn
+
+
+def dense_entry(name: str):
+    """The testing aids of the dense toolbox (``lssvm_mi355_dense_cholesky`` / ``_solve`` / ``_invert_lower``; include/plssvm_amd_testing.h) with their argument types."""
+    fn = getattr(lib, name)
+    if fn.argtypes is None:
+        dp = C.POINTER(C.c_double)
+        if name == "lssvm_mi355_dense_cholesky":
+            fn.argtypes = [dp, C.c_size_t, C.c_double, dp, C.POINTER(C.c_uint64), dp]
+        elif name == "lssvm_mi355_dense_solve":
+            fn.argtypes = [dp, C.c_size_t, dp, C.c_size_t, dp, dp]
+        else:
+            fn.argtypes = [dp, C.c_size_t, dp, dp]
         fn.restype = C.c_int
     return fn
 

@@ -315,34 +315,47 @@ def _reduced_arguments(Y, N: int, dtype, rank, landmarks, slab_rows):
     return Y2, single, rank, lm, lm_ptr, int(slab_rows)
 
 
-def _reduced_call(fn, head, Y2, single: bool, rank: int, lm_ptr, slab_rows: int, tail=()):
+def _reduced_entry(name: str, on_device: bool, suffix: str = ""):
+    """``lssvm_mi355_<name><suffix>`` or, for ``factor="device"``, its ``_dev`` form."""
+    entry = _capi.reduced_loo_entry if "loo" in name else _capi.reduced_entry
+    return entry(f"lssvm_mi355_{name}{'_dev' if on_device else ''}{suffix}")
+
+
+def _reduced_call(fn, head, Y2, single: bool, rank: int, lm_ptr, slab_rows: int, tail=(), on_device: bool = False):
     k = Y2.shape[0]
     betas = np.zeros((k, rank), dtype=np.float64)
     rhos = np.zeros(k, dtype=np.float64)
     used = np.zeros(rank, dtype=np.uint64)
     info = _capi.LssvmReducedInfo()
     dp = C.POINTER(C.c_double)
+    dense = _capi.LssvmDenseInfo()
+    if on_device:
+        tail = tuple(tail) + (C.byref(dense),)
     check(fn(*head, ptr(Y2), k, rank, lm_ptr, slab_rows, betas.ctypes.data_as(dp), rhos.ctypes.data_as(dp), used.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(info), *tail))
+    report = dict(dense.as_dict(), **info.as_dict()) if on_device else info.as_dict()  # (rank and jitter are the same in both records)
     if single:
-        return betas[0], float(rhos[0]), used, info.as_dict()
-    return betas, rhos, used, info.as_dict()
+        return betas[0], float(rhos[0]), used, report
+    return betas, rhos, used, report
 
 
-def fit_reduced(params: Parameter, A, Y, rank: int, landmarks=None, slab_rows: int = 0, options: Options | None = None):
+def fit_reduced(params: Parameter, A, Y, rank: int, landmarks=None, slab_rows: int = 0, options: Options | None = None, factor: str = "host"):
     """The fixed-size (reduced) LS-SVM over ``rank`` landmark points (``lssvm_mi355_fit_reduced_*``; opt-in: it trades accuracy for a model of ``rank`` support vectors):
     ``f(x) = sum_j beta_j k(x, x_L[j]) - rho`` minimises ``1/2 beta^T K_mm beta + C/2 sum_i (y_i - f(x_i))^2``.  ``Y``: one right-hand side ``(N,)`` or ``k`` of them
     ``(k, N)`` -- one landmark block, one Gram matrix and one factorisation serve all.  ``landmarks``: distinct point indices (their number is the rank), None for the
     preconditioner's fixed rule, or ``"greedy"`` / ``"rpcholesky"`` for ``rank`` points chosen by :func:`select_landmarks`.  ``slab_rows``: rows of the landmark block held at a time (a multiple of 256; 0: 65 536).  Returns ``(betas, rhos, landmarks, info)``,
-    ``betas`` and ``rhos`` float64 whatever the data's type and shaped like ``Y``; ``info``: the ``lssvm_reduced_info`` dict.  Device 0; deterministic; no CG."""
+    ``betas`` and ``rhos`` float64 whatever the data's type and shaped like ``Y``; ``info``: the ``lssvm_reduced_info`` dict.  Device 0; deterministic; no CG.
+    ``factor="device"`` (opt-in; ``lssvm_mi355_fit_reduced_dev_*``): assembly, factorisation and solves run on the device instead of one host
+    thread -- not the host path's bits -- and ``info`` gains the ``lssvm_dense_info`` fields (``block``, ``attempts``, ``launches``, ``assemble_ms`` ...)."""
+    on_device = _capi.factor_on_device(factor)
     A = _as_matrix(A)
     N, d = A.shape
     if isinstance(landmarks, str):  # a selection rule (:func:`select_landmarks`): one resident problem selects and fits
         with ResidentProblem(params, A, options=options) as prob:
-            return prob.fit_reduced(Y, rank, landmarks, slab_rows)
+            return prob.fit_reduced(Y, rank, landmarks, slab_rows, factor=factor)
     Y2, single, rank, _, lm_ptr, slab_rows = _reduced_arguments(Y, N, A.dtype, rank, landmarks, slab_rows)
     ps = _params_struct(params, d)
-    fn = _capi.reduced_entry(f"lssvm_mi355_fit_reduced_{suffix_of(A.dtype)}")
-    return _reduced_call(fn, (C.byref(ps), ptr(A), N, d), Y2, single, rank, lm_ptr, slab_rows, tail=(options_ptr(options),))
+    fn = _reduced_entry("fit_reduced", on_device, f"_{suffix_of(A.dtype)}")
+    return _reduced_call(fn, (C.byref(ps), ptr(A), N, d), Y2, single, rank, lm_ptr, slab_rows, tail=(options_ptr(options),), on_device=on_device)
 
 
 def _reduced_loo_costs(costs):
@@ -358,39 +371,47 @@ def _reduced_loo_costs(costs):
     return costs
 
 
-def _reduced_loo_call(fn, head, Y2, single: bool, N: int, rank: int, lm_ptr, slab_rows: int, costs, tail=()):
+def _reduced_loo_call(fn, head, Y2, single: bool, N: int, rank: int, lm_ptr, slab_rows: int, costs, tail=(), on_device: bool = False):
     k, S = Y2.shape[0], costs.size
     betas, rhos = np.zeros((S, k, rank)), np.zeros((S, k))
     leverage, fitted, loo = np.zeros((S, N)), np.zeros((S, k, N)), np.zeros((S, k, N))
     press, errors, used = np.zeros((S, k)), np.zeros((S, k), dtype=np.uint64), np.zeros(rank, dtype=np.uint64)
     infos = (_capi.LssvmReducedLooInfo * S)()
     dp, up = C.POINTER(C.c_double), C.POINTER(C.c_uint64)
+    dense = (_capi.LssvmDenseInfo * S)()
+    if on_device:
+        tail = tuple(tail) + (dense,)
     check(fn(*head, ptr(Y2), k, rank, lm_ptr, slab_rows, costs.ctypes.data_as(dp), S, betas.ctypes.data_as(dp), rhos.ctypes.data_as(dp), leverage.ctypes.data_as(dp),
              fitted.ctypes.data_as(dp), loo.ctypes.data_as(dp), press.ctypes.data_as(dp), errors.ctypes.data_as(up), used.ctypes.data_as(up), infos, *tail))
     report = {"costs": costs.copy(), "leverage": leverage, "fitted": fitted[:, 0] if single else fitted, "loo": loo[:, 0] if single else loo,
               "press": press[:, 0] if single else press, "loo_errors": errors[:, 0] if single else errors, "max_leverage": np.array([i.max_leverage for i in infos]),
-              "jitter": np.array([i.jitter for i in infos]), "infos": [i.as_dict() for i in infos]}
+              "jitter": np.array([i.jitter for i in infos]),
+              "infos": [dict(dn.as_dict(), **i.as_dict()) if on_device else i.as_dict() for i, dn in zip(infos, dense)]}
     return (betas[:, 0], rhos[:, 0], used, report) if single else (betas, rhos, used, report)
 
 
-def fit_reduced_loo(params: Parameter, A, Y, rank: int, costs, landmarks=None, slab_rows: int = 0, options: Options | None = None):
+def fit_reduced_loo(params: Parameter, A, Y, rank: int, costs, landmarks=None, slab_rows: int = 0, options: Options | None = None, factor: str = "host"):
     """:func:`fit_reduced` at every cost of ``costs`` with its exact leave-one-out values -- leave-one-out with the landmark set held fixed
     (``lssvm_mi355_fit_reduced_loo_*``).  The fit is a linear smoother, so the model refitted without point ``i`` predicts
     ``y_i - (y_i - f(x_i)) / (1 - h_ii)`` at ``x_i``: one more pass over the landmark block per cost gives the leverages ``h`` and these values for ALL ``N`` points, without
     a validation split and without a refit.  ``params.cost`` is ignored; 1 to 64 costs.  Returns ``(betas[S, k, rank], rhos[S, k], landmarks, report)`` (the ``k`` axis
     dropped for a single right-hand side ``(N,)``); ``betas[s]`` / ``rhos[s]`` have the bits of :func:`fit_reduced` at ``costs[s]``.  ``report``: ``leverage[S, N]``,
     ``fitted`` / ``loo`` ``[S, k, N]``, ``press[S, k]`` (sum of squared leave-one-out residuals), ``loo_errors[S, k]`` (points whose leave-one-out value has another sign than
-    ``y``), ``max_leverage[S]``, ``jitter[S]``, ``infos`` (``lssvm_reduced_loo_info`` dicts).  Everything float64.  Device 0; deterministic."""
+    ``y``), ``max_leverage[S]``, ``jitter[S]``, ``infos`` (``lssvm_reduced_loo_info`` dicts).  Everything float64.  Device 0; deterministic.
+    ``factor="device"`` (opt-in; ``lssvm_mi355_fit_reduced_loo_dev_*``): per cost the assembly, the factorisation, the solves and the triangular
+    inverse run on the device and the leverage kernel's operand never leaves it -- not the host path's bits; ``betas[s]`` / ``rhos[s]`` then have the bits of
+    :func:`fit_reduced` with ``factor="device"`` at ``costs[s]``, and every dict of ``infos`` gains the ``lssvm_dense_info`` fields."""
+    on_device = _capi.factor_on_device(factor)
     A = _as_matrix(A)
     N, d = A.shape
     if isinstance(landmarks, str):  # a selection rule (:func:`select_landmarks`): one resident problem selects and fits
         with ResidentProblem(params, A, options=options) as prob:
-            return prob.fit_reduced_loo(Y, rank, costs, landmarks, slab_rows)
+            return prob.fit_reduced_loo(Y, rank, costs, landmarks, slab_rows, factor=factor)
     Y2, single, rank, _, lm_ptr, slab_rows = _reduced_arguments(Y, N, A.dtype, rank, landmarks, slab_rows)
     costs = _reduced_loo_costs(costs)
     ps = _params_struct(params, d)
-    fn = _capi.reduced_loo_entry(f"lssvm_mi355_fit_reduced_loo_{suffix_of(A.dtype)}")
-    return _reduced_loo_call(fn, (C.byref(ps), ptr(A), N, d), Y2, single, N, rank, lm_ptr, slab_rows, costs, tail=(options_ptr(options),))
+    fn = _reduced_entry("fit_reduced_loo", on_device, f"_{suffix_of(A.dtype)}")
+    return _reduced_loo_call(fn, (C.byref(ps), ptr(A), N, d), Y2, single, N, rank, lm_ptr, slab_rows, costs, tail=(options_ptr(options),), on_device=on_device)
 
 
 def generate_q(params: Parameter, data, options: Options | None = None):
@@ -764,11 +785,13 @@ class ResidentProblem:
         B2, single = _pcg_arguments(B, self.num_points, self.dtype, eps, max_iter)
         return _pcg_call(_capi.pcg_entry("lssvm_mi355_problem_solve_pcg"), (self._h,), (), B2, single, self.num_points, self.dtype, eps, max_iter)
 
-    def fit_reduced(self, Y, rank: int, landmarks=None, slab_rows: int = 0):
-        """:func:`fit_reduced` on this resident problem at its own cost (``lssvm_mi355_problem_fit_reduced``).  The problem is left as it was and keeps its preconditioner.
+    def fit_reduced(self, Y, rank: int, landmarks=None, slab_rows: int = 0, factor: str = "host"):
+        """:func:`fit_reduced` on this resident problem at its own cost (``lssvm_mi355_problem_fit_reduced``; ``factor="device"``: ``lssvm_mi355_problem_fit_reduced_dev``).
+        The problem is left as it was and keeps its preconditioner.
         Not on a problem of several devices or ranks, not with weights set, not between :meth:`cg_begin` and :meth:`cg_finish`."""
+        on_device = _capi.factor_on_device(factor)
         Y2, single, rank, _, lm_ptr, slab_rows = _reduced_arguments(Y, self.num_points, self.dtype, rank, self._selected(rank, landmarks), slab_rows)
-        return _reduced_call(_capi.reduced_entry("lssvm_mi355_problem_fit_reduced"), (self._h,), Y2, single, rank, lm_ptr, slab_rows)
+        return _reduced_call(_reduced_entry("problem_fit_reduced", on_device), (self._h,), Y2, single, rank, lm_ptr, slab_rows, on_device=on_device)
 
     def landmark_gram(self, Y, rank: int, landmarks=None, slab_rows: int = 0):
         """The operator of :meth:`fit_reduced` alone (a test aid, ``lssvm_mi355_problem_landmark_gram``): ``[Phi | 1 | Y]^T [Phi | 1 | Y]`` as the device sums it,
@@ -779,12 +802,14 @@ class ResidentProblem:
         check(_capi.reduced_entry("lssvm_mi355_problem_landmark_gram")(self._h, ptr(Y2), Y2.shape[0], rank, lm_ptr, slab_rows, out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
 
-    def fit_reduced_loo(self, Y, rank: int, costs, landmarks=None, slab_rows: int = 0):
-        """:func:`fit_reduced_loo` on this resident problem (``lssvm_mi355_problem_fit_reduced_loo``): leave-one-out with the landmark set held fixed, at every cost of
-        ``costs``.  The problem's own cost is ignored; the problem is left as it was and keeps its preconditioner.  Refused where :meth:`fit_reduced` is."""
+    def fit_reduced_loo(self, Y, rank: int, costs, landmarks=None, slab_rows: int = 0, factor: str = "host"):
+        """:func:`fit_reduced_loo` on this resident problem (``lssvm_mi355_problem_fit_reduced_loo``; ``factor="device"``: ``lssvm_mi355_problem_fit_reduced_loo_dev``):
+        leave-one-out with the landmark set held fixed, at every cost of ``costs``.  The problem's own cost is ignored; the problem is left as it was and keeps its
+        preconditioner.  Refused where :meth:`fit_reduced` is."""
+        on_device = _capi.factor_on_device(factor)
         Y2, single, rank, _, lm_ptr, slab_rows = _reduced_arguments(Y, self.num_points, self.dtype, rank, self._selected(rank, landmarks), slab_rows)
         costs = _reduced_loo_costs(costs)
-        return _reduced_loo_call(_capi.reduced_loo_entry("lssvm_mi355_problem_fit_reduced_loo"), (self._h,), Y2, single, self.num_points, rank, lm_ptr, slab_rows, costs)
+        return _reduced_loo_call(_reduced_entry("problem_fit_reduced_loo", on_device), (self._h,), Y2, single, self.num_points, rank, lm_ptr, slab_rows, costs, on_device=on_device)
 
     def reduced_leverage(self, V, shift, B_extra=None, landmarks=None, slab_rows: int = 0):
         """The operator of :meth:`fit_reduced_loo` alone on the caller's operands (a test aid, ``lssvm_mi355_problem_reduced_leverage``): with ``phic_i = phi_i - shift``,

@@ -4,6 +4,7 @@
  * stores the message in a thread-local string (lssvm_mi355_last_error).
  */
 #include "lssvm_problem.hip.hpp"
+#include "lssvm_dense.hip.hpp"
 
 #include <dlfcn.h>
 #include <cstdlib>
@@ -222,21 +223,27 @@ void pcg_one_shot(const lssvm_params *params, const T *X, size_t N, size_t d, co
 /* lssvm_mi355_fit_reduced_*: every argument that needs no device is checked before one is touched; problem and fit on device 0 */
 template <typename T>
 void fit_reduced_one_shot(const lssvm_params *params, const T *X, size_t N, size_t d, const T *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows,
-                          double *betas_out, double *rhos_out, uint64_t *landmarks_out, lssvm_reduced_info *info, const lssvm_mi355_options *options) {
+                          double *betas_out, double *rhos_out, uint64_t *landmarks_out, lssvm_reduced_info *info, const lssvm_mi355_options *options, bool on_device = false,
+                          lssvm_dense_info *dense = nullptr) {
     lssvm::check_params(params);
     check_data(X, N, d);
     lssvm::check_reduced_arguments(Y, num_rhs, rank, slab_rows, N);
     LSSVM_REQUIRE(betas_out != nullptr && rhos_out != nullptr, "betas_out / rhos_out must not be NULL");
     if (landmarks != nullptr) (void) lssvm::resolve_landmarks(landmarks, static_cast<size_t>(rank), N);
     lssvm::Solver<T> prob = device0_solver<T>(options, *params, X, N, d);
-    prob.fit_reduced(Y, num_rhs, rank, landmarks, slab_rows, betas_out, rhos_out, landmarks_out, info);
+    if (on_device) {
+        prob.fit_reduced_dev(Y, num_rhs, rank, landmarks, slab_rows, betas_out, rhos_out, landmarks_out, info, dense);
+    } else {
+        prob.fit_reduced(Y, num_rhs, rank, landmarks, slab_rows, betas_out, rhos_out, landmarks_out, info);
+    }
 }
 
 /* lssvm_mi355_fit_reduced_loo_*: likewise */
 template <typename T>
 void fit_reduced_loo_one_shot(const lssvm_params *params, const T *X, size_t N, size_t d, const T *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows,
                               const double *costs, size_t num_costs, double *betas_out, double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out, double *press_out,
-                              uint64_t *loo_errors_out, uint64_t *landmarks_out, lssvm_reduced_loo_info *infos, const lssvm_mi355_options *options) {
+                              uint64_t *loo_errors_out, uint64_t *landmarks_out, lssvm_reduced_loo_info *infos, const lssvm_mi355_options *options, bool on_device = false,
+                              lssvm_dense_info *dense = nullptr) {
     lssvm::check_params(params);
     check_data(X, N, d);
     lssvm::check_reduced_arguments(Y, num_rhs, rank, slab_rows, N);
@@ -244,7 +251,12 @@ void fit_reduced_loo_one_shot(const lssvm_params *params, const T *X, size_t N, 
     LSSVM_REQUIRE(betas_out != nullptr && rhos_out != nullptr, "betas_out / rhos_out must not be NULL");
     if (landmarks != nullptr) (void) lssvm::resolve_landmarks(landmarks, static_cast<size_t>(rank), N);
     lssvm::Solver<T> prob = device0_solver<T>(options, *params, X, N, d);
-    prob.fit_reduced_loo(Y, num_rhs, rank, landmarks, slab_rows, costs, num_costs, betas_out, rhos_out, leverage_out, fitted_out, loo_out, press_out, loo_errors_out, landmarks_out, infos);
+    if (on_device) {
+        prob.fit_reduced_loo_dev(Y, num_rhs, rank, landmarks, slab_rows, costs, num_costs, betas_out, rhos_out, leverage_out, fitted_out, loo_out, press_out, loo_errors_out, landmarks_out, infos,
+                                 dense);
+    } else {
+        prob.fit_reduced_loo(Y, num_rhs, rank, landmarks, slab_rows, costs, num_costs, betas_out, rhos_out, leverage_out, fitted_out, loo_out, press_out, loo_errors_out, landmarks_out, infos);
+    }
 }
 
 /* lssvm_mi355_select_landmarks_*: likewise */
@@ -767,6 +779,80 @@ int lssvm_mi355_fit_reduced_loo_f64(const lssvm_params *params, const double *X,
     return guarded([&] {
         fit_reduced_loo_one_shot<double>(params, X, num_points, num_features, Y, num_rhs, rank, landmarks, slab_rows, costs, num_costs, betas_out, rhos_out, leverage_out, fitted_out, loo_out,
                                          press_out, loo_errors_out, landmarks_out, infos, options);
+    });
+}
+/* the same six with the dense steps on the device (lssvm_dense.hip): the checks of the host forms, in their order */
+static_assert(sizeof(lssvm_dense_info) == 72, "lssvm_dense_info changed: plssvm_amd/_capi.py (LssvmDenseInfo) changes with it");
+int lssvm_mi355_problem_fit_reduced_dev(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, double *betas_out, double *rhos_out,
+                                        uint64_t *landmarks_out, lssvm_reduced_info *info, lssvm_dense_info *dense) {
+    return guarded([&] {
+        LSSVM_REQUIRE(p != nullptr, "problem handle must not be NULL");
+        lssvm::check_reduced_arguments(Y, num_rhs, rank, slab_rows, 0);
+        LSSVM_REQUIRE(betas_out != nullptr && rhos_out != nullptr, "betas_out / rhos_out must not be NULL");
+        impl_of(p)->fit_reduced_dev(Y, num_rhs, rank, landmarks, slab_rows, betas_out, rhos_out, landmarks_out, info, dense);
+    });
+}
+int lssvm_mi355_fit_reduced_dev_f32(const lssvm_params *params, const float *X, size_t num_points, size_t num_features, const float *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks,
+                                    uint64_t slab_rows, double *betas_out, double *rhos_out, uint64_t *landmarks_out, lssvm_reduced_info *info, const lssvm_mi355_options *options,
+                                    lssvm_dense_info *dense) {
+    return guarded([&] { fit_reduced_one_shot<float>(params, X, num_points, num_features, Y, num_rhs, rank, landmarks, slab_rows, betas_out, rhos_out, landmarks_out, info, options, true, dense); });
+}
+int lssvm_mi355_fit_reduced_dev_f64(const lssvm_params *params, const double *X, size_t num_points, size_t num_features, const double *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks,
+                                    uint64_t slab_rows, double *betas_out, double *rhos_out, uint64_t *landmarks_out, lssvm_reduced_info *info, const lssvm_mi355_options *options,
+                                    lssvm_dense_info *dense) {
+    return guarded([&] { fit_reduced_one_shot<double>(params, X, num_points, num_features, Y, num_rhs, rank, landmarks, slab_rows, betas_out, rhos_out, landmarks_out, info, options, true, dense); });
+}
+int lssvm_mi355_problem_fit_reduced_loo_dev(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *costs,
+                                            size_t num_costs, double *betas_out, double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out, double *press_out,
+                                            uint64_t *loo_errors_out, uint64_t *landmarks_out, lssvm_reduced_loo_info *infos, lssvm_dense_info *dense) {
+    return guarded([&] {
+        LSSVM_REQUIRE(p != nullptr, "problem handle must not be NULL");
+        lssvm::check_reduced_arguments(Y, num_rhs, rank, slab_rows, 0);
+        lssvm::check_reduced_loo_costs(costs, num_costs);
+        LSSVM_REQUIRE(betas_out != nullptr && rhos_out != nullptr, "betas_out / rhos_out must not be NULL");
+        impl_of(p)->fit_reduced_loo_dev(Y, num_rhs, rank, landmarks, slab_rows, costs, num_costs, betas_out, rhos_out, leverage_out, fitted_out, loo_out, press_out, loo_errors_out, landmarks_out,
+                                        infos, dense);
+    });
+}
+int lssvm_mi355_fit_reduced_loo_dev_f32(const lssvm_params *params, const float *X, size_t num_points, size_t num_features, const float *Y, size_t num_rhs, uint64_t rank,
+                                        const uint64_t *landmarks, uint64_t slab_rows, const double *costs, size_t num_costs, double *betas_out, double *rhos_out, double *leverage_out,
+                                        double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out, lssvm_reduced_loo_info *infos,
+                                        const lssvm_mi355_options *options, lssvm_dense_info *dense) {
+    return guarded([&] {
+        fit_reduced_loo_one_shot<float>(params, X, num_points, num_features, Y, num_rhs, rank, landmarks, slab_rows, costs, num_costs, betas_out, rhos_out, leverage_out, fitted_out, loo_out,
+                                        press_out, loo_errors_out, landmarks_out, infos, options, true, dense);
+    });
+}
+int lssvm_mi355_fit_reduced_loo_dev_f64(const lssvm_params *params, const double *X, size_t num_points, size_t num_features, const double *Y, size_t num_rhs, uint64_t rank,
+                                        const uint64_t *landmarks, uint64_t slab_rows, const double *costs, size_t num_costs, double *betas_out, double *rhos_out, double *leverage_out,
+                                        double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out, lssvm_reduced_loo_info *infos,
+                                        const lssvm_mi355_options *options, lssvm_dense_info *dense) {
+    return guarded([&] {
+        fit_reduced_loo_one_shot<double>(params, X, num_points, num_features, Y, num_rhs, rank, landmarks, slab_rows, costs, num_costs, betas_out, rhos_out, leverage_out, fitted_out, loo_out,
+                                         press_out, loo_errors_out, landmarks_out, infos, options, true, dense);
+    });
+}
+/* the dense toolbox alone on host arrays (include/plssvm_amd_testing.h): every refusal before a device is touched */
+int lssvm_mi355_dense_cholesky(const double *A, size_t m, double nu, double *L_out, uint64_t *status_out, double *ms_out) {
+    return guarded([&] {
+        LSSVM_REQUIRE(m >= 1 && m <= static_cast<size_t>(lssvm::DENSE_MAX_RANK), "m must lie in [1, 1024], but is " + std::to_string(m) + "!");
+        LSSVM_REQUIRE(A != nullptr && L_out != nullptr && status_out != nullptr, "A / L_out / status_out must not be NULL");
+        lssvm::dense_cholesky_aid(A, static_cast<int>(m), nu, L_out, status_out, ms_out);
+    });
+}
+int lssvm_mi355_dense_solve(const double *L, size_t m, const double *B, size_t k, double *X_out, double *ms_out) {
+    return guarded([&] {
+        LSSVM_REQUIRE(m >= 1 && m <= static_cast<size_t>(lssvm::DENSE_MAX_RANK), "m must lie in [1, 1024], but is " + std::to_string(m) + "!");
+        LSSVM_REQUIRE(k >= 1 && k <= 4096, "k must lie in [1, 4096], but is " + std::to_string(k) + "!");
+        LSSVM_REQUIRE(L != nullptr && B != nullptr && X_out != nullptr, "L / B / X_out must not be NULL");
+        lssvm::dense_solve_aid(L, static_cast<int>(m), B, static_cast<int>(k), X_out, ms_out);
+    });
+}
+int lssvm_mi355_dense_invert_lower(const double *L, size_t m, double *V_out, double *ms_out) {
+    return guarded([&] {
+        LSSVM_REQUIRE(m >= 1 && m <= static_cast<size_t>(lssvm::DENSE_MAX_RANK), "m must lie in [1, 1024], but is " + std::to_string(m) + "!");
+        LSSVM_REQUIRE(L != nullptr && V_out != nullptr, "L / V_out must not be NULL");
+        lssvm::dense_invert_lower_aid(L, static_cast<int>(m), V_out, ms_out);
     });
 }
 int lssvm_mi355_problem_reduced_leverage(lssvm_mi355_problem *p, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *V, const double *shift, const double *B_extra, size_t k,

@@ -630,6 +630,12 @@ struct ProblemBase {
                                  lssvm_reduced_loo_info *infos) = 0;  // lssvm_mi355_problem_fit_reduced_loo
     virtual void reduced_leverage(uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *V, const double *shift, const double *B_extra, size_t k, double *h_out,
                                   double *f_out) = 0;  // lssvm_mi355_problem_reduced_leverage
+    /* both fits with the dense steps on the device (lssvm_dense.hip); `dense`: one record, or num_costs of them, or NULL */
+    virtual void fit_reduced_dev(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, double *betas_out, double *rhos_out,
+                                 uint64_t *landmarks_out, lssvm_reduced_info *info, lssvm_dense_info *dense) = 0;  // lssvm_mi355_problem_fit_reduced_dev
+    virtual void fit_reduced_loo_dev(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *costs, size_t num_costs, double *betas_out,
+                                     double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out,
+                                     lssvm_reduced_loo_info *infos, lssvm_dense_info *dense) = 0;  // lssvm_mi355_problem_fit_reduced_loo_dev
     virtual void time_leverage_kernel(uint64_t rank, uint64_t slab_rows, size_t k, int repeats, double *gram_ms_out, double *leverage_ms_out) = 0;  // lssvm_mi355_problem_time_leverage_kernel
     /* landmark selection: the pivots of a greedy or randomly pivoted partial Cholesky factorisation (lssvm_select.hip) */
     virtual void select_landmarks(uint64_t rank, int method, uint64_t pool, uint64_t seed, double tol, uint64_t *landmarks_out, double *trace_out, double *residual_out,
@@ -692,6 +698,10 @@ struct LocalComms {
 std::shared_ptr<LocalComms> local_comms_for(const std::vector<int> &devices);  // lssvm_exchange.hip
 
 struct LeverageArgs;  // what a leave-one-out pass of the fixed-size model works on (lssvm_reduced.hip)
+/* what reduced_gram leaves on the device for the device-factored fits instead of releasing it: St as k_reduced_sum's packed 128 x 128 tiles, K_mm rank x rank */
+struct ReducedOnDevice {
+    DevBuf<double> St, Kmm;
+};
 
 /* Solver<T>: the CG driver (csvm.cpp:71-183 / gpu_csvm.hpp:477-654) over the shards that live in THIS process:
  *   - one shard, world 1: single GPU;
@@ -733,6 +743,12 @@ class Solver final : public ProblemBase {
     void reduced_leverage(uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *V, const double *shift, const double *B_extra, size_t k, double *h_out,
                           double *f_out) override;
     void time_leverage_kernel(uint64_t rank, uint64_t slab_rows, size_t k, int repeats, double *gram_ms_out, double *leverage_ms_out) override;
+    /* fit_reduced and fit_reduced_loo with assembly, factorisation, solves and the triangular inverse on the device (lssvm_dense.hip) */
+    void fit_reduced_dev(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, double *betas_out, double *rhos_out, uint64_t *landmarks_out,
+                         lssvm_reduced_info *info, lssvm_dense_info *dense) override;
+    void fit_reduced_loo_dev(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *costs, size_t num_costs, double *betas_out,
+                             double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out,
+                             lssvm_reduced_loo_info *infos, lssvm_dense_info *dense) override;
     /* the pivots of a partial Cholesky factorisation of K over the candidates, one launch pair per step on shard 0's stream (lssvm_select.hip) */
     void select_landmarks(uint64_t rank, int method, uint64_t pool, uint64_t seed, double tol, uint64_t *landmarks_out, double *trace_out, double *residual_out,
                           lssvm_landmark_select_info *info) override;
@@ -777,7 +793,7 @@ class Solver final : public ProblemBase {
     Problem<T> &reduced_problem(const char *what, bool unweighted_only);  // the checks every entry point of the fixed-size model shares; shard 0 (lssvm_reduced.hip)
     /* what fit_reduced and landmark_gram share: the checks, the slabs, St (cols x cols, both triangles) and K_mm (rank x rank) on the host */
     void reduced_gram(const char *what, const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, std::vector<uint64_t> &lm_out,
-                      std::vector<double> &gram_out, std::vector<double> &kmm_out, lssvm_reduced_info &info);
+                      std::vector<double> &gram_out, std::vector<double> &kmm_out, lssvm_reduced_info &info, ReducedOnDevice *keep = nullptr);
     /* pass 2 of fit_reduced_loo, and all of reduced_leverage: the Phi slabs again, the leverage kernel per slab and operand (lssvm_reduced.hip) */
     void leverage_pass(const std::vector<uint64_t> &lm, uint64_t slab_rows, LeverageArgs &args);
     T *vec_of(Problem<T> &p, Vec which) const { return which == Vec::d ? p.own_.d.p : (which == Vec::x ? p.own_.x.p : p.tmp_.p); }

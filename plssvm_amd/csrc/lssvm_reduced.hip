@@ -18,9 +18,11 @@
  * solve_reduced: the code of fit_reduced) and inverts L; pass 2 evaluates the slabs again and k_reduced_leverage forms Phic [V^T | beta] on the matrix cores per slab and
  * cost, keeping only the rows' squared norms, the fitted and the leave-one-out values.
  */
+#include "lssvm_dense.hip.hpp"
 #include "lssvm_landmark.hip.hpp"
 
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 
 namespace lssvm {
@@ -32,6 +34,7 @@ constexpr int RG_KC = 16;                  // rows of Pt per step
 constexpr int RG_LS = RG_KC + 2;           // doubles between two columns in LDS: 144 bytes, conflict-free ds_read_b64 (as the fp64 tile kernels)
 constexpr int RG_RANGE = 2048;             // rows of a slab per workgroup: a CONSTANT (see above)
 constexpr int RG_TILE = RG_TW * RG_TW;     // entries of a tile
+static_assert(RG_TW == DENSE_ST_TILE, "k_dense_assemble (lssvm_dense.hip) reads St as the tiles k_reduced_sum leaves");
 
 /* the 1 column and the y columns of Pt beside Phi, in double: column c of `out` (ld doubles apart) is 1 (c = 0) or right-hand side c - 1; exact zeros from row N on */
 template <typename T>
@@ -287,6 +290,79 @@ void invert_lower_rows(const std::vector<double> &L, int m, double *out, size_t 
     }
 }
 
+/* ---- the same steps on the device (lssvm_dense.hip) ---- */
+/* trace(M) from the host copies, with factor_reduced's expression and cholesky_with_jitter's order: where no attempt fails, nu has the host path's bits */
+double reduced_trace(const std::vector<double> &St, const std::vector<double> &Kmm, int m, int cols, double Nd, double sigma) {
+    const double *s = &St[static_cast<size_t>(m) * cols];
+    std::vector<double> diag(static_cast<size_t>(m));
+    for (int j = 0; j < m; ++j) diag[j] = St[static_cast<size_t>(j) * cols + j] - s[j] * s[j] / Nd + sigma * Kmm[static_cast<size_t>(j) * m + j];
+    double trace = 0.0;
+    for (int k = 0; k < m; ++k) trace += diag[k];
+    return trace;
+}
+
+/* what one cost needs on the device besides St and K_mm, held over the costs of a grid */
+struct DenseFit {
+    DenseSpd dense;
+    DenseStopwatch watch;
+    DevBuf<double> betas, rhos;
+    std::vector<double> betas_host, rhos_host;  // where an attempt's results land before it is known to have factored
+    const int m, k;
+    hipStream_t st;
+    DenseFit(int rank, int num_rhs, hipStream_t stream) :
+        dense(rank, num_rhs, stream), watch(stream), betas_host(static_cast<size_t>(num_rhs) * rank), rhos_host(static_cast<size_t>(num_rhs)), m(rank), k(num_rhs), st(stream) {
+        betas.alloc_zero(static_cast<size_t>(k) * m, st);
+        rhos.alloc_zero(static_cast<size_t>(k), st);
+    }
+    size_t device_bytes() const { return dense.device_bytes() + (betas.count + rhos.count) * sizeof(double); }
+
+    /* One cost: the jitter rule of cholesky_with_jitter, each attempt assemble -> factor -> solve (-> invert into the operand Bt_op: rows of V, the betas behind them, ldb
+     * doubles apart) and ONE wait, at which betas (k x m), rhos (k) and the status word come back.  Fills `d` (may be NULL); returns nu. */
+    double run(const ReducedOnDevice &dev, const std::vector<double> &St, const std::vector<double> &Kmm, int cols, double Nd, double sigma, double *Bt_op, int ldb, double *betas_out,
+               double *rhos_out, lssvm_dense_info *d, double *device_ms_out) {
+        const double trace = reduced_trace(St, Kmm, m, cols, Nd, sigma);
+        LSSVM_REQUIRE(std::isfinite(trace) && trace > 0.0, "the matrix of the reduced model has no positive finite trace");
+        double nu = DBL_EPSILON * trace;
+        for (int attempt = 0; attempt < 7; ++attempt, nu *= 10.0) {
+            dense.begin_attempt();
+            watch.mark(0);
+            dense.enqueue_assemble(dev.St.p, dev.Kmm.p, k, Nd, sigma, nu);
+            watch.mark(1);
+            dense.enqueue_factor();
+            watch.mark(2);
+            dense.enqueue_solve(k, betas.p, static_cast<size_t>(m), Bt_op != nullptr ? Bt_op + static_cast<size_t>(m) * ldb : nullptr, static_cast<size_t>(ldb), true, Nd, rhos.p);
+            watch.mark(3);
+            if (Bt_op != nullptr) {
+                dense.enqueue_invert(Bt_op, ldb);
+                watch.mark(4);
+            }
+            LSSVM_HIP_CHECK(hipMemcpyAsync(betas_host.data(), betas.p, betas.count * sizeof(double), hipMemcpyDeviceToHost, st));
+            LSSVM_HIP_CHECK(hipMemcpyAsync(rhos_host.data(), rhos.p, rhos.count * sizeof(double), hipMemcpyDeviceToHost, st));
+            if (dense.status() != 0) continue;  // (the wait; a failed attempt's kernels have all returned at once and written nothing)
+            // the caller's arrays are written only now: where every attempt fails they stay as they were, as on the host path
+            std::copy(betas_host.begin(), betas_host.end(), betas_out);
+            std::copy(rhos_host.begin(), rhos_host.end(), rhos_out);
+            DenseTimes t;
+            watch.read(Bt_op != nullptr, t);
+            if (device_ms_out != nullptr) *device_ms_out = t.assemble_ms + t.factor_ms + t.solve_ms + t.invert_ms;
+            if (d != nullptr) {
+                *d = lssvm_dense_info{};
+                d->rank = static_cast<uint64_t>(m);
+                d->block = DENSE_BLOCK;
+                d->attempts = static_cast<uint64_t>(attempt + 1);
+                d->launches = dense.launches();
+                d->jitter = nu;
+                d->assemble_ms = t.assemble_ms;
+                d->factor_ms = t.factor_ms;
+                d->solve_ms = t.solve_ms;
+                d->invert_ms = t.invert_ms;
+            }
+            return nu;
+        }
+        throw Error(LSSVM_ERR_INTERNAL, "the matrix of the reduced model could not be factored (jitter up to " + std::to_string(nu / 10.0) + ")");
+    }
+};
+
 /* ---- the leave-one-out pass ---- */
 constexpr int LV_LSA = RG_TW + 16;  // doubles between two columns of Phi in LDS: the four k-rows of an MFMA's A fragments start 32 banks apart
 
@@ -521,7 +597,7 @@ Problem<T> &Solver<T>::reduced_problem(const char *what, bool unweighted_only) {
 
 template <typename T>
 void Solver<T>::reduced_gram(const char *what, const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, std::vector<uint64_t> &lm,
-                             std::vector<double> &gram, std::vector<double> &Kmm, lssvm_reduced_info &info) {
+                             std::vector<double> &gram, std::vector<double> &Kmm, lssvm_reduced_info &info, ReducedOnDevice *keep) {
     // ---- everything that needs no device ----
     Problem<T> &p = reduced_problem(what, true);
     const size_t N = p.N_;
@@ -576,6 +652,12 @@ void Solver<T>::reduced_gram(const char *what, const void *Y, size_t num_rhs, ui
     info.gram_ms = gram_ms;
     info.total_ms = now_ms() - t0;
     info.workspace_bytes = (slab.count + part.count + St_dev.count + Kmm_dev.count) * sizeof(double) + rhs.Y.count * sizeof(T) + block.device_bytes();
+    if (keep != nullptr) {  // the device-factored fits go on with both where they lie
+        std::swap(keep->St.p, St_dev.p);
+        std::swap(keep->St.count, St_dev.count);
+        std::swap(keep->Kmm.p, Kmm_dev.p);
+        std::swap(keep->Kmm.count, Kmm_dev.count);
+    }
 }
 
 template <typename T>
@@ -610,6 +692,37 @@ void Solver<T>::fit_reduced(const void *Y, size_t num_rhs, uint64_t rank, const 
         info.jitter = nu;
         info.host_ms = now_ms() - t_host;
         info.total_ms = now_ms() - t0;
+        *info_out = info;
+    }
+}
+
+/* fit_reduced with the host's part on the device: St and K_mm stay where reduced_gram summed them */
+template <typename T>
+void Solver<T>::fit_reduced_dev(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, double *betas_out, double *rhos_out, uint64_t *landmarks_out,
+                                lssvm_reduced_info *info_out, lssvm_dense_info *dense_out) {
+    LSSVM_REQUIRE(betas_out != nullptr && rhos_out != nullptr, "betas_out / rhos_out must not be NULL");
+    const double t0 = now_ms();
+    std::vector<uint64_t> lm;
+    std::vector<double> St, Kmm;
+    lssvm_reduced_info info{};
+    ReducedOnDevice dev;
+    reduced_gram("fit_reduced", Y, num_rhs, rank, landmarks, slab_rows, lm, St, Kmm, info, &dev);
+
+    const double t_dense = now_ms();
+    const int m = static_cast<int>(rank), k = static_cast<int>(num_rhs), cols = m + 1 + k;
+    Problem<T> &p = *shards_[0];
+    const double Nd = static_cast<double>(p.N_), sigma = 1.0 / p.params_.cost;
+    const SetOnExit<bool> busy = hold_busy();
+    p.activate();
+    DenseFit fit(m, k, p.stream());
+    double device_ms = 0.0;
+    const double nu = fit.run(dev, St, Kmm, cols, Nd, sigma, nullptr, 0, betas_out, rhos_out, dense_out, &device_ms);
+    if (landmarks_out != nullptr) std::copy(lm.begin(), lm.end(), landmarks_out);
+    if (info_out != nullptr) {
+        info.jitter = nu;
+        info.host_ms = std::max(0.0, now_ms() - t_dense - device_ms);
+        info.total_ms = now_ms() - t0;
+        info.workspace_bytes += fit.device_bytes();
         *info_out = info;
     }
 }
@@ -760,6 +873,65 @@ void Solver<T>::fit_reduced_loo(const void *Y, size_t num_rhs, uint64_t rank, co
     }
 }
 
+/* fit_reduced_loo with the per-cost steps on the device: nothing of size m^2 crosses the bus per cost, the operand of the leverage kernel is written where it is read */
+template <typename T>
+void Solver<T>::fit_reduced_loo_dev(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *costs, size_t num_costs, double *betas_out,
+                                    double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out,
+                                    lssvm_reduced_loo_info *infos, lssvm_dense_info *dense_out) {
+    LSSVM_REQUIRE(betas_out != nullptr && rhos_out != nullptr, "betas_out / rhos_out must not be NULL");
+    check_reduced_loo_costs(costs, num_costs);
+    std::vector<uint64_t> lm;
+    std::vector<double> St, Kmm;
+    lssvm_reduced_info info{};
+    ReducedOnDevice dev;
+    reduced_gram("fit_reduced_loo", Y, num_rhs, rank, landmarks, slab_rows, lm, St, Kmm, info, &dev);  // pass 1, and every other check that needs no device
+
+    const int m = static_cast<int>(rank), k = static_cast<int>(num_rhs), cols = m + 1 + k;
+    Problem<T> &p = *shards_[0];
+    const double Nd = static_cast<double>(p.N_);
+    const SetOnExit<bool> busy = hold_busy();
+    p.activate();
+    hipStream_t st = p.stream();
+    LeverageArgs a(m, k, num_costs, true, st);
+    DenseFit fit(m, k, st);
+
+    const double *s_row = &St[static_cast<size_t>(m) * cols];
+    std::vector<double> shift(static_cast<size_t>(m)), ybar(a.num_ops * k), nus(num_costs), host_ms(num_costs);
+    for (int j = 0; j < m; ++j) shift[j] = s_row[j] / Nd;
+    for (size_t s = 0; s < num_costs; ++s) {
+        const double t_cost = now_ms();
+        double device_ms = 0.0;
+        nus[s] = fit.run(dev, St, Kmm, cols, Nd, 1.0 / costs[s], a.Bt.p + s * a.op_stride, a.ldb, betas_out + s * k * m, rhos_out + s * k, dense_out != nullptr ? dense_out + s : nullptr,
+                         &device_ms);
+        for (int c = 0; c < k; ++c) ybar[s * k + c] = St[static_cast<size_t>(m + 1 + c) * cols + m] / Nd;
+        host_ms[s] = std::max(0.0, now_ms() - t_cost - device_ms);
+    }
+    a.upload_shift(shift.data(), ybar.data());
+
+    a.inv_n = 1.0 / Nd;
+    a.Y = Y;
+    a.h_out = leverage_out;
+    a.f_out = fitted_out;
+    a.loo_out = loo_out;
+    a.press = press_out;
+    a.errors = loo_errors_out;
+    leverage_pass(lm, slab_rows, a);
+
+    if (landmarks_out != nullptr) std::copy(lm.begin(), lm.end(), landmarks_out);
+    if (infos != nullptr) {
+        for (size_t s = 0; s < num_costs; ++s) {
+            infos[s] = lssvm_reduced_loo_info{};
+            infos[s].cost = costs[s];
+            infos[s].jitter = nus[s];
+            infos[s].max_leverage = a.max_leverage[s];
+            infos[s].landmark_ms = info.landmark_ms + a.landmark_ms;
+            infos[s].gram_ms = info.gram_ms;
+            infos[s].leverage_ms = a.leverage_ms[s];
+            infos[s].host_ms = host_ms[s];
+        }
+    }
+}
+
 template <typename T>
 void Solver<T>::reduced_leverage(uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *V, const double *shift, const double *B_extra, size_t num_extra, double *h_out,
                                  double *f_out) {
@@ -872,6 +1044,12 @@ template void Solver<float>::fit_reduced_loo(const void *, size_t, uint64_t, con
                                              uint64_t *, lssvm_reduced_loo_info *);
 template void Solver<double>::fit_reduced_loo(const void *, size_t, uint64_t, const uint64_t *, uint64_t, const double *, size_t, double *, double *, double *, double *, double *, double *, uint64_t *,
                                               uint64_t *, lssvm_reduced_loo_info *);
+template void Solver<float>::fit_reduced_dev(const void *, size_t, uint64_t, const uint64_t *, uint64_t, double *, double *, uint64_t *, lssvm_reduced_info *, lssvm_dense_info *);
+template void Solver<double>::fit_reduced_dev(const void *, size_t, uint64_t, const uint64_t *, uint64_t, double *, double *, uint64_t *, lssvm_reduced_info *, lssvm_dense_info *);
+template void Solver<float>::fit_reduced_loo_dev(const void *, size_t, uint64_t, const uint64_t *, uint64_t, const double *, size_t, double *, double *, double *, double *, double *, double *, uint64_t *,
+                                                 uint64_t *, lssvm_reduced_loo_info *, lssvm_dense_info *);
+template void Solver<double>::fit_reduced_loo_dev(const void *, size_t, uint64_t, const uint64_t *, uint64_t, const double *, size_t, double *, double *, double *, double *, double *, double *, uint64_t *,
+                                                  uint64_t *, lssvm_reduced_loo_info *, lssvm_dense_info *);
 template void Solver<float>::reduced_leverage(uint64_t, const uint64_t *, uint64_t, const double *, const double *, const double *, size_t, double *, double *);
 template void Solver<double>::reduced_leverage(uint64_t, const uint64_t *, uint64_t, const double *, const double *, const double *, size_t, double *, double *);
 template void Solver<float>::time_leverage_kernel(uint64_t, uint64_t, size_t, int, double *, double *);

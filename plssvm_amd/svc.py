@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import _capi
 from . import csvm as _csvm
 from . import multiclass as _multiclass
 from .csvm import make_csvm
@@ -304,12 +305,14 @@ def fit_cost_path(estimator, X, y, Cs):
 # ---------------------------------------------------------------------------------------------------------------------
 # the fixed-size model: `rank` landmark points as the only support vectors (CSVM.fit_reduced)
 # ---------------------------------------------------------------------------------------------------------------------
-def fit_reduced(estimator, X, y, rank, landmarks=None):
+def fit_reduced(estimator, X, y, rank, landmarks=None, factor="host"):
     """A fitted clone of ``estimator`` whose model has ``rank`` support vectors only (the fixed-size LS-SVM, :meth:`plssvm_amd.csvm.CSVM.fit_reduced`): the library's fixed
     choice of landmark points, the distinct row indices ``landmarks`` (their number is then the rank), or ``"greedy"`` / ``"rpcholesky"`` for ``rank`` points selected from the
     data (``backend.select_landmarks``).  Two classes and one-vs-all alike; one landmark block, one Gram
     matrix and one factorisation serve all classes.  No CG runs: ``tol`` and ``max_iter`` play no part and ``n_iter_`` is 0.  ``support_`` holds the landmarks,
-    ``dual_coef_`` has shape ``(n_classifiers, rank)``.  ``class_weight`` must be None; ``estimator`` itself stays unfitted."""
+    ``dual_coef_`` has shape ``(n_classifiers, rank)``.  ``class_weight`` must be None; ``estimator`` itself stays unfitted.  ``factor="device"`` (opt-in): the dense
+    solve on the device instead of one host thread (not the same bits)."""
+    _capi.factor_on_device(factor)
     if not isinstance(estimator, SVC):
         raise InvalidParameterError("estimator must be a plssvm_amd.svc.SVC")
     if estimator.class_weight is not None:
@@ -325,7 +328,7 @@ def fit_reduced(estimator, X, y, rank, landmarks=None):
     if len(classes) > 2:
         Xr = np.ascontiguousarray(X, dtype=estimator.real_type)
         resolved = params.resolved(Xr.shape[1])
-        betas, rhos, used, info = svm.solve_reduced_systems(resolved, Xr, _multiclass.one_vs_all_targets(classes, y, Xr.dtype), rank, landmarks)
+        betas, rhos, used, info = svm.solve_reduced_systems(resolved, Xr, _multiclass.one_vs_all_targets(classes, y, Xr.dtype), rank, landmarks, **_capi.factor_keyword(factor))
         rows = np.asarray(used).astype(np.int64)
         infos = [dict(info, iterations=0) for _ in classes]
         model = _multiclass.OneVsAllModel(resolved, classes, np.ascontiguousarray(Xr[rows]), np.asarray(betas).astype(Xr.dtype), np.asarray(rhos).astype(Xr.dtype), infos)
@@ -338,7 +341,7 @@ def fit_reduced(estimator, X, y, rank, landmarks=None):
         }
         return clone
     data = DataSet(X, y.tolist(), real_type=estimator.real_type)
-    model = svm.fit_reduced(data, rank, landmarks)
+    model = svm.fit_reduced(data, rank, landmarks, **_capi.factor_keyword(factor))
     clone._set_binary_fit(svm, model, model.data, X, y, class_weight, None, 0)
     clone._fit["support_"] = _landmarks_of(svm, landmarks)
     return clone
@@ -349,12 +352,14 @@ def _landmarks_of(svm, landmarks):
     return np.asarray(svm.last_cg_info["landmarks"] if landmarks is None or isinstance(landmarks, str) else landmarks).astype(np.int32)
 
 
-def fit_reduced_cv(estimator, X, y, rank, Cs, landmarks=None):
+def fit_reduced_cv(estimator, X, y, rank, Cs, landmarks=None, factor="host"):
     """The exact leave-one-out accuracy of the fixed-size model of ``estimator`` at every ``C`` of ``Cs`` -- leave-one-out with the landmark set held fixed
     (:meth:`plssvm_amd.csvm.CSVM.fit_reduced_path`).  Returns ``(loo_accuracy[len(Cs)], fitted clones)``: the clones are what :func:`fit_reduced`
     gives at each ``C``, the accuracy is over ALL training points, each predicted by the model refitted without it -- no validation split, no refit, one more pass over the
     landmark block per cost.  Two classes: the sign of the leave-one-out value; more (one-vs-all): the argmax over the classes' leave-one-out values, compared with the
-    label.  ``estimator.C`` is ignored, ``class_weight`` must be None, ``estimator`` itself stays unfitted."""
+    label.  ``estimator.C`` is ignored, ``class_weight`` must be None, ``estimator`` itself stays unfitted.  ``factor="device"`` (opt-in): each cost's factorisation,
+    inverse and solves on the device (not the same bits)."""
+    _capi.factor_on_device(factor)
     if not isinstance(estimator, SVC):
         raise InvalidParameterError("estimator must be a plssvm_amd.svc.SVC")
     if estimator.class_weight is not None:
@@ -371,7 +376,7 @@ def fit_reduced_cv(estimator, X, y, rank, Cs, landmarks=None):
     if len(classes) > 2:
         Xr = np.ascontiguousarray(X, dtype=estimator.real_type)
         resolved = params.resolved(Xr.shape[1])
-        betas, rhos, used, report = svm.solve_reduced_loo_systems(resolved, Xr, _multiclass.one_vs_all_targets(classes, y, Xr.dtype), rank, Cs, landmarks)
+        betas, rhos, used, report = svm.solve_reduced_loo_systems(resolved, Xr, _multiclass.one_vs_all_targets(classes, y, Xr.dtype), rank, Cs, landmarks, **_capi.factor_keyword(factor))
         rows = np.asarray(used).astype(np.int64)
         scores = np.array([float(np.mean(classes[np.argmax(report["loo"][s], axis=0)] == y)) for s in range(len(Cs))])
         for s, (C, clone) in enumerate(zip(Cs, clones)):
@@ -387,7 +392,7 @@ def fit_reduced_cv(estimator, X, y, rank, Cs, landmarks=None):
             }
         return scores, clones
     data = DataSet(X, y.tolist(), real_type=estimator.real_type)
-    models, report = svm.fit_reduced_path(data, rank, Cs, landmarks)
+    models, report = svm.fit_reduced_path(data, rank, Cs, landmarks, **_capi.factor_keyword(factor))
     for clone, model in zip(clones, models):
         clone._set_binary_fit(svm, model, model.data, X, y, class_weight, None, 0)
         clone._fit["support_"] = np.asarray(report["landmarks"]).astype(np.int32)
