@@ -612,6 +612,47 @@ int lssvm_mi355_fit_reduced_loo_dev_f64(const lssvm_params *params, const double
                                         double *leverage_out, double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out,
                                         lssvm_reduced_loo_info *infos, const lssvm_mi355_options *options, lssvm_dense_info *dense);
 
+/* The two fits above with per-point weights w_i >= 0 (opt-in): the model minimises  1/2 beta^T K_mm beta + C/2 sum_i w_i (y_i - Phi_i beta - b)^2.
+ * With W = sum_i w_i these are the normal equations above with St = Pt^T diag(w) Pt and W wherever N stands (K_mm is not weighted):
+ *   M = S - s s^T / W + sigma K_mm,   (M + nu I) beta_c = t_c - s eta_c / W,   b_c = (eta_c - s^T beta_c) / W,
+ * and the weighted fit is still a linear smoother, so the leave-one-out values stay exact:
+ *   h_ii = w_i (1 / W + |L^-1 (phi_i - s / W)|^2),   f_c^(-i)(x_i) = y_ic - (y_ic - f_c(x_i)) / (1 - h_ii).
+ * A point of weight 0 takes no part in the fit: its h is 0 and its leave-one-out value IS the fitted value f_c(x_i) (written as such, not through the expression) -- the
+ * prediction of a model that never saw it, so one call scores a validation mask.  A landmark of weight 0 is a basis centre like any other.
+ * The device multiplies both operands of the Gram pass by q_i = sqrt(w_i) as it stages them (q is formed on the host with sqrt() and uploaded once per call; the slab itself
+ * stays unscaled, no pass over it is added); the leverage kernel multiplies by w_i.  W is the host's sum of the weights in index order, in double.
+ * weights: N doubles on the HOST whatever the problem's dtype, each finite and >= 0, W finite and > 0.  NULL: the unweighted model, the call then has the bits of the
+ * unweighted entry point of the same `factor`.  They are the only source of weights: a problem with weights set (lssvm_mi355_problem_set_weights) is refused as above.
+ * factor: 0 = the dense steps on the host (lssvm_mi355_problem_fit_reduced / _loo), 1 = on the device (_dev); `dense` may be NULL and is ignored for factor 0.
+ * press_out is sum_i w_i (y_ic - loo_ic)^2, loo_errors_out counts the sign mismatches over the points with w_i > 0, max_leverage is taken over all points.
+ * The guarantees of the unweighted forms carry over: fixed-order sums without atomics and the same bits for the same arguments; row c of a call with k right-hand sides
+ * has the bits of the call with that right-hand side alone; a cost has the bits of the call with that cost alone; betas and rhos of a leave-one-out cost have the bits of
+ * lssvm_mi355_problem_fit_reduced_weighted at that cost with the same `factor`.  With every weight 1.0 each output has the bits of the unweighted entry point (q = 1,
+ * W = N, every product exact).  The landmark rules ignore the weights.
+ * LSSVM_ERR_INVALID_ARGUMENT, all before a device is touched: the refusals of the unweighted forms; a weight that is negative, NaN or infinite; W == 0 or not finite; a
+ * factor other than 0 or 1. */
+int lssvm_mi355_problem_fit_reduced_weighted(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, const double *weights /* N, or NULL */, uint64_t rank,
+                                             const uint64_t *landmarks, uint64_t slab_rows, int factor, double *betas_out, double *rhos_out, uint64_t *landmarks_out,
+                                             lssvm_reduced_info *info, lssvm_dense_info *dense);
+int lssvm_mi355_fit_reduced_weighted_f32(const lssvm_params *params, const float *X, size_t num_points, size_t num_features, const float *Y, size_t num_rhs, const double *weights,
+                                         uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, int factor, double *betas_out, double *rhos_out, uint64_t *landmarks_out,
+                                         lssvm_reduced_info *info, lssvm_dense_info *dense, const lssvm_mi355_options *options);
+int lssvm_mi355_fit_reduced_weighted_f64(const lssvm_params *params, const double *X, size_t num_points, size_t num_features, const double *Y, size_t num_rhs, const double *weights,
+                                         uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, int factor, double *betas_out, double *rhos_out, uint64_t *landmarks_out,
+                                         lssvm_reduced_info *info, lssvm_dense_info *dense, const lssvm_mi355_options *options);
+int lssvm_mi355_problem_fit_reduced_loo_weighted(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, const double *weights /* N, or NULL */, uint64_t rank,
+                                                 const uint64_t *landmarks, uint64_t slab_rows, const double *costs, size_t num_costs, int factor, double *betas_out,
+                                                 double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out,
+                                                 uint64_t *landmarks_out, lssvm_reduced_loo_info *infos, lssvm_dense_info *dense /* num_costs */);
+int lssvm_mi355_fit_reduced_loo_weighted_f32(const lssvm_params *params, const float *X, size_t num_points, size_t num_features, const float *Y, size_t num_rhs, const double *weights,
+                                             uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *costs, size_t num_costs, int factor, double *betas_out,
+                                             double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out,
+                                             uint64_t *landmarks_out, lssvm_reduced_loo_info *infos, lssvm_dense_info *dense, const lssvm_mi355_options *options);
+int lssvm_mi355_fit_reduced_loo_weighted_f64(const lssvm_params *params, const double *X, size_t num_points, size_t num_features, const double *Y, size_t num_rhs, const double *weights,
+                                             uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *costs, size_t num_costs, int factor, double *betas_out,
+                                             double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out,
+                                             uint64_t *landmarks_out, lssvm_reduced_loo_info *infos, lssvm_dense_info *dense, const lssvm_mi355_options *options);
+
 /* Landmark selection on a resident problem (opt-in): the pivots of a partial Cholesky factorisation of the kernel matrix, chosen greedily or
  * at random in proportion to the residual diagonal (randomly pivoted Cholesky).  The result is a list of point indices for the `landmarks` argument of the entry points
  * above; nothing else changes, and nothing selects it automatically.  Neither rule dominates the other or the fixed shuffle (README.md has the rows of all three kinds).

@@ -52,6 +52,10 @@ int lssvm_mi355_set_io_threads(int threads);
 /* The operator of the fixed-size model alone (lssvm_mi355_problem_fit_reduced): St = Pt^T Pt for Pt = [Phi | 1 | y_0 ... y_{k-1}], as the device sums
  * it, (rank + 1 + num_rhs)^2 doubles row-major with BOTH triangles (the upper one is the host's copy of the lower).  Arguments and refusals as there. */
 int lssvm_mi355_problem_landmark_gram(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, double *gram_out);
+/* ... and of the weighted model (lssvm_mi355_problem_fit_reduced_weighted): St = Pt^T diag(w) Pt alone, both operands scaled by sqrt(w_i) as they
+ * are staged.  weights NULL: the call above.  Arguments and refusals as there. */
+int lssvm_mi355_problem_landmark_gram_weighted(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, const double *weights, uint64_t rank, const uint64_t *landmarks,
+                                               uint64_t slab_rows, double *gram_out);
 
 /* The operator of the leave-one-out pass alone (lssvm_mi355_problem_fit_reduced_loo) on the caller's operands, apart from any conditioning: for every
  * point i, with phic_i = phi_i - shift (phi_i: row i of Phi = K(X, X_L) as the problem evaluates it),

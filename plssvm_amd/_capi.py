@@ -46,6 +46,9 @@ EXPORTED_SYMBOLS = [
     "lssvm_mi355_problem_fit_reduced_loo", "lssvm_mi355_fit_reduced_loo_f32", "lssvm_mi355_fit_reduced_loo_f64", "lssvm_mi355_problem_reduced_leverage", "lssvm_mi355_problem_time_leverage_kernel",
     "lssvm_mi355_problem_fit_reduced_dev", "lssvm_mi355_fit_reduced_dev_f32", "lssvm_mi355_fit_reduced_dev_f64",
     "lssvm_mi355_problem_fit_reduced_loo_dev", "lssvm_mi355_fit_reduced_loo_dev_f32", "lssvm_mi355_fit_reduced_loo_dev_f64",
+    "lssvm_mi355_problem_fit_reduced_weighted", "lssvm_mi355_fit_reduced_weighted_f32", "lssvm_mi355_fit_reduced_weighted_f64",
+    "lssvm_mi355_problem_fit_reduced_loo_weighted", "lssvm_mi355_fit_reduced_loo_weighted_f32", "lssvm_mi355_fit_reduced_loo_weighted_f64",
+    "lssvm_mi355_problem_landmark_gram_weighted",
     "lssvm_mi355_dense_cholesky", "lssvm_mi355_dense_solve", "lssvm_mi355_dense_invert_lower",
     "lssvm_mi355_problem_select_landmarks", "lssvm_mi355_select_landmarks_f32", "lssvm_mi355_select_landmarks_f64",
     "lssvm_mi355_cg_begin", "lssvm_mi355_cg_step", "lssvm_mi355_cg_finish", "lssvm_mi355_problem_synchronize", "lssvm_mi355_problem_info",
@@ -351,6 +354,28 @@ def dense_entry(name: str):
             fn.argtypes = [dp, C.c_size_t, dp, C.c_size_t, dp, dp]
         else:
             fn.argtypes = [dp, C.c_size_t, dp, dp]
+        fn.restype = C.c_int
+    return fn
+
+
+def reduced_weighted_entry(name: str):
+    """The weighted entry points of the fixed-size model (``lssvm_mi355_problem_fit_reduced_weighted``, ``_fit_reduced_loo_weighted``, their one-shot forms and the test
+    aid ``lssvm_mi355_problem_landmark_gram_weighted``) with their argument types.  Bound at the first call."""
+    fn = getattr(lib, name)
+    if fn.argtypes is None:
+        dp, up = C.POINTER(C.c_double), C.POINTER(C.c_uint64)
+        common = [C.c_void_p, C.c_size_t, dp, C.c_uint64, up, C.c_uint64]  # Y, num_rhs, weights, rank, landmarks, slab_rows
+        if "loo" in name:
+            # costs, num_costs, factor, betas, rhos, leverage, fitted, loo, press, loo_errors, landmarks, infos, dense
+            common += [dp, C.c_size_t, C.c_int, dp, dp, dp, dp, dp, dp, up, up, C.POINTER(LssvmReducedLooInfo), C.POINTER(LssvmDenseInfo)]
+        elif name == "lssvm_mi355_problem_landmark_gram_weighted":
+            common += [dp]
+        else:
+            common += [C.c_int, dp, dp, up, C.POINTER(LssvmReducedInfo), C.POINTER(LssvmDenseInfo)]  # factor, betas, rhos, landmarks, info, dense
+        if "problem" in name:
+            fn.argtypes = [C.c_void_p] + common
+        else:
+            fn.argtypes = [C.POINTER(LssvmParams), C.c_void_p, C.c_size_t, C.c_size_t] + common + [C.c_void_p]
         fn.restype = C.c_int
     return fn
 

@@ -315,13 +315,35 @@ def _reduced_arguments(Y, N: int, dtype, rank, landmarks, slab_rows):
     return Y2, single, rank, lm, lm_ptr, int(slab_rows)
 
 
-def _reduced_entry(name: str, on_device: bool, suffix: str = ""):
-    """``lssvm_mi355_<name><suffix>`` or, for ``factor="device"``, its ``_dev`` form."""
+def _reduced_weights(sample_weight, N: int):
+    """The per-point weights of a weighted fixed-size fit as the library takes them, checked as it checks them: N doubles, each finite and >= 0, their sum > 0 -- or
+    None.  (Exact zeros are allowed here, unlike in the full solve: such a point takes no part in the fit.)"""
+    if sample_weight is None:
+        return None
+    try:
+        w = np.ascontiguousarray(sample_weight, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise InvalidParameterError("The weights must be a list of numbers!") from None
+    if w.shape != (N,):
+        raise InvalidParameterError(f"The number of data points ({N}) and the number of weights ({w.size}) must be the same!")
+    if not (np.all(np.isfinite(w)) and np.all(w >= 0.0)):
+        raise InvalidParameterError("Every weight of the reduced model must be finite and not less than 0.0!")
+    with np.errstate(over="ignore"):
+        total = float(w.sum())
+    if not (np.isfinite(total) and total > 0.0):
+        raise InvalidParameterError(f"The weights of the reduced model must have a finite sum greater than 0.0, but it is {total}!")
+    return w
+
+
+def _reduced_entry(name: str, on_device: bool, suffix: str = "", weighted: bool = False):
+    """``lssvm_mi355_<name><suffix>`` or, for ``factor="device"``, its ``_dev`` form; with weights the ``_weighted`` form, which takes the factor as an argument."""
+    if weighted:
+        return _capi.reduced_weighted_entry(f"lssvm_mi355_{name}_weighted{suffix}")
     entry = _capi.reduced_loo_entry if "loo" in name else _capi.reduced_entry
     return entry(f"lssvm_mi355_{name}{'_dev' if on_device else ''}{suffix}")
 
 
-def _reduced_call(fn, head, Y2, single: bool, rank: int, lm_ptr, slab_rows: int, tail=(), on_device: bool = False):
+def _reduced_call(fn, head, Y2, single: bool, rank: int, lm_ptr, slab_rows: int, tail=(), on_device: bool = False, weights=None):
     k = Y2.shape[0]
     betas = np.zeros((k, rank), dtype=np.float64)
     rhos = np.zeros(k, dtype=np.float64)
@@ -329,33 +351,41 @@ def _reduced_call(fn, head, Y2, single: bool, rank: int, lm_ptr, slab_rows: int,
     info = _capi.LssvmReducedInfo()
     dp = C.POINTER(C.c_double)
     dense = _capi.LssvmDenseInfo()
-    if on_device:
-        tail = tuple(tail) + (C.byref(dense),)
-    check(fn(*head, ptr(Y2), k, rank, lm_ptr, slab_rows, betas.ctypes.data_as(dp), rhos.ctypes.data_as(dp), used.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(info), *tail))
+    if weights is not None:  # (``fn`` is the weighted entry point)
+        check(fn(*head, ptr(Y2), k, weights.ctypes.data_as(dp), rank, lm_ptr, slab_rows, int(on_device), betas.ctypes.data_as(dp), rhos.ctypes.data_as(dp),
+                 used.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(info), C.byref(dense), *tail))
+    else:
+        if on_device:
+            tail = tuple(tail) + (C.byref(dense),)
+        check(fn(*head, ptr(Y2), k, rank, lm_ptr, slab_rows, betas.ctypes.data_as(dp), rhos.ctypes.data_as(dp), used.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(info), *tail))
     report = dict(dense.as_dict(), **info.as_dict()) if on_device else info.as_dict()  # (rank and jitter are the same in both records)
     if single:
         return betas[0], float(rhos[0]), used, report
     return betas, rhos, used, report
 
 
-def fit_reduced(params: Parameter, A, Y, rank: int, landmarks=None, slab_rows: int = 0, options: Options | None = None, factor: str = "host"):
+def fit_reduced(params: Parameter, A, Y, rank: int, landmarks=None, slab_rows: int = 0, options: Options | None = None, factor: str = "host", sample_weight=None):
     """The fixed-size (reduced) LS-SVM over ``rank`` landmark points (``lssvm_mi355_fit_reduced_*``; opt-in: it trades accuracy for a model of ``rank`` support vectors):
     ``f(x) = sum_j beta_j k(x, x_L[j]) - rho`` minimises ``1/2 beta^T K_mm beta + C/2 sum_i (y_i - f(x_i))^2``.  ``Y``: one right-hand side ``(N,)`` or ``k`` of them
     ``(k, N)`` -- one landmark block, one Gram matrix and one factorisation serve all.  ``landmarks``: distinct point indices (their number is the rank), None for the
     preconditioner's fixed rule, or ``"greedy"`` / ``"rpcholesky"`` for ``rank`` points chosen by :func:`select_landmarks`.  ``slab_rows``: rows of the landmark block held at a time (a multiple of 256; 0: 65 536).  Returns ``(betas, rhos, landmarks, info)``,
     ``betas`` and ``rhos`` float64 whatever the data's type and shaped like ``Y``; ``info``: the ``lssvm_reduced_info`` dict.  Device 0; deterministic; no CG.
     ``factor="device"`` (opt-in; ``lssvm_mi355_fit_reduced_dev_*``): assembly, factorisation and solves run on the device instead of one host
-    thread -- not the host path's bits -- and ``info`` gains the ``lssvm_dense_info`` fields (``block``, ``attempts``, ``launches``, ``assemble_ms`` ...)."""
+    thread -- not the host path's bits -- and ``info`` gains the ``lssvm_dense_info`` fields (``block``, ``attempts``, ``launches``, ``assemble_ms`` ...).
+    ``sample_weight`` (``lssvm_mi355_fit_reduced_weighted_*``): ``N`` weights ``w_i >= 0`` with a positive sum for the objective
+    ``1/2 beta^T K_mm beta + C/2 sum_i w_i (y_i - f(x_i))^2``; a point of weight 0 takes no part in the fit.  None: the unweighted entry point, as before.  The landmark
+    rules ignore the weights."""
     on_device = _capi.factor_on_device(factor)
     A = _as_matrix(A)
     N, d = A.shape
+    w = _reduced_weights(sample_weight, N)
     if isinstance(landmarks, str):  # a selection rule (:func:`select_landmarks`): one resident problem selects and fits
         with ResidentProblem(params, A, options=options) as prob:
-            return prob.fit_reduced(Y, rank, landmarks, slab_rows, factor=factor)
+            return prob.fit_reduced(Y, rank, landmarks, slab_rows, factor=factor, sample_weight=w)
     Y2, single, rank, _, lm_ptr, slab_rows = _reduced_arguments(Y, N, A.dtype, rank, landmarks, slab_rows)
     ps = _params_struct(params, d)
-    fn = _reduced_entry("fit_reduced", on_device, f"_{suffix_of(A.dtype)}")
-    return _reduced_call(fn, (C.byref(ps), ptr(A), N, d), Y2, single, rank, lm_ptr, slab_rows, tail=(options_ptr(options),), on_device=on_device)
+    fn = _reduced_entry("fit_reduced", on_device, f"_{suffix_of(A.dtype)}", weighted=w is not None)
+    return _reduced_call(fn, (C.byref(ps), ptr(A), N, d), Y2, single, rank, lm_ptr, slab_rows, tail=(options_ptr(options),), on_device=on_device, weights=w)
 
 
 def _reduced_loo_costs(costs):
@@ -371,7 +401,7 @@ def _reduced_loo_costs(costs):
     return costs
 
 
-def _reduced_loo_call(fn, head, Y2, single: bool, N: int, rank: int, lm_ptr, slab_rows: int, costs, tail=(), on_device: bool = False):
+def _reduced_loo_call(fn, head, Y2, single: bool, N: int, rank: int, lm_ptr, slab_rows: int, costs, tail=(), on_device: bool = False, weights=None):
     k, S = Y2.shape[0], costs.size
     betas, rhos = np.zeros((S, k, rank)), np.zeros((S, k))
     leverage, fitted, loo = np.zeros((S, N)), np.zeros((S, k, N)), np.zeros((S, k, N))
@@ -379,10 +409,14 @@ def _reduced_loo_call(fn, head, Y2, single: bool, N: int, rank: int, lm_ptr, sla
     infos = (_capi.LssvmReducedLooInfo * S)()
     dp, up = C.POINTER(C.c_double), C.POINTER(C.c_uint64)
     dense = (_capi.LssvmDenseInfo * S)()
-    if on_device:
-        tail = tuple(tail) + (dense,)
-    check(fn(*head, ptr(Y2), k, rank, lm_ptr, slab_rows, costs.ctypes.data_as(dp), S, betas.ctypes.data_as(dp), rhos.ctypes.data_as(dp), leverage.ctypes.data_as(dp),
-             fitted.ctypes.data_as(dp), loo.ctypes.data_as(dp), press.ctypes.data_as(dp), errors.ctypes.data_as(up), used.ctypes.data_as(up), infos, *tail))
+    outs = (betas.ctypes.data_as(dp), rhos.ctypes.data_as(dp), leverage.ctypes.data_as(dp), fitted.ctypes.data_as(dp), loo.ctypes.data_as(dp), press.ctypes.data_as(dp),
+            errors.ctypes.data_as(up), used.ctypes.data_as(up), infos)
+    if weights is not None:  # (``fn`` is the weighted entry point)
+        check(fn(*head, ptr(Y2), k, weights.ctypes.data_as(dp), rank, lm_ptr, slab_rows, costs.ctypes.data_as(dp), S, int(on_device), *outs, dense, *tail))
+    else:
+        if on_device:
+            tail = tuple(tail) + (dense,)
+        check(fn(*head, ptr(Y2), k, rank, lm_ptr, slab_rows, costs.ctypes.data_as(dp), S, *outs, *tail))
     report = {"costs": costs.copy(), "leverage": leverage, "fitted": fitted[:, 0] if single else fitted, "loo": loo[:, 0] if single else loo,
               "press": press[:, 0] if single else press, "loo_errors": errors[:, 0] if single else errors, "max_leverage": np.array([i.max_leverage for i in infos]),
               "jitter": np.array([i.jitter for i in infos]),
@@ -390,7 +424,8 @@ def _reduced_loo_call(fn, head, Y2, single: bool, N: int, rank: int, lm_ptr, sla
     return (betas[:, 0], rhos[:, 0], used, report) if single else (betas, rhos, used, report)
 
 
-def fit_reduced_loo(params: Parameter, A, Y, rank: int, costs, landmarks=None, slab_rows: int = 0, options: Options | None = None, factor: str = "host"):
+def fit_reduced_loo(params: Parameter, A, Y, rank: int, costs, landmarks=None, slab_rows: int = 0, options: Options | None = None, factor: str = "host",
+                    sample_weight=None):
     """:func:`fit_reduced` at every cost of ``costs`` with its exact leave-one-out values -- leave-one-out with the landmark set held fixed
     (``lssvm_mi355_fit_reduced_loo_*``).  The fit is a linear smoother, so the model refitted without point ``i`` predicts
     ``y_i - (y_i - f(x_i)) / (1 - h_ii)`` at ``x_i``: one more pass over the landmark block per cost gives the leverages ``h`` and these values for ALL ``N`` points, without
@@ -400,18 +435,22 @@ def fit_reduced_loo(params: Parameter, A, Y, rank: int, costs, landmarks=None, s
     ``y``), ``max_leverage[S]``, ``jitter[S]``, ``infos`` (``lssvm_reduced_loo_info`` dicts).  Everything float64.  Device 0; deterministic.
     ``factor="device"`` (opt-in; ``lssvm_mi355_fit_reduced_loo_dev_*``): per cost the assembly, the factorisation, the solves and the triangular
     inverse run on the device and the leverage kernel's operand never leaves it -- not the host path's bits; ``betas[s]`` / ``rhos[s]`` then have the bits of
-    :func:`fit_reduced` with ``factor="device"`` at ``costs[s]``, and every dict of ``infos`` gains the ``lssvm_dense_info`` fields."""
+    :func:`fit_reduced` with ``factor="device"`` at ``costs[s]``, and every dict of ``infos`` gains the ``lssvm_dense_info`` fields.
+    ``sample_weight`` (``lssvm_mi355_fit_reduced_loo_weighted_*``): the weights of :func:`fit_reduced`; then ``h_ii = w_i (1 / W + ...)``,
+    ``press`` is ``sum_i w_i (y_i - loo_i)^2`` and ``loo_errors`` counts over the points with ``w_i > 0``.  A point of weight 0 has leverage 0 and its ``loo`` value is
+    the prediction of a model that never saw it: one call scores a validation mask."""
     on_device = _capi.factor_on_device(factor)
     A = _as_matrix(A)
     N, d = A.shape
+    w = _reduced_weights(sample_weight, N)
     if isinstance(landmarks, str):  # a selection rule (:func:`select_landmarks`): one resident problem selects and fits
         with ResidentProblem(params, A, options=options) as prob:
-            return prob.fit_reduced_loo(Y, rank, costs, landmarks, slab_rows, factor=factor)
+            return prob.fit_reduced_loo(Y, rank, costs, landmarks, slab_rows, factor=factor, sample_weight=w)
     Y2, single, rank, _, lm_ptr, slab_rows = _reduced_arguments(Y, N, A.dtype, rank, landmarks, slab_rows)
     costs = _reduced_loo_costs(costs)
     ps = _params_struct(params, d)
-    fn = _reduced_entry("fit_reduced_loo", on_device, f"_{suffix_of(A.dtype)}")
-    return _reduced_loo_call(fn, (C.byref(ps), ptr(A), N, d), Y2, single, N, rank, lm_ptr, slab_rows, costs, tail=(options_ptr(options),), on_device=on_device)
+    fn = _reduced_entry("fit_reduced_loo", on_device, f"_{suffix_of(A.dtype)}", weighted=w is not None)
+    return _reduced_loo_call(fn, (C.byref(ps), ptr(A), N, d), Y2, single, N, rank, lm_ptr, slab_rows, costs, tail=(options_ptr(options),), on_device=on_device, weights=w)
 
 
 def generate_q(params: Parameter, data, options: Options | None = None):
@@ -785,13 +824,16 @@ class ResidentProblem:
         B2, single = _pcg_arguments(B, self.num_points, self.dtype, eps, max_iter)
         return _pcg_call(_capi.pcg_entry("lssvm_mi355_problem_solve_pcg"), (self._h,), (), B2, single, self.num_points, self.dtype, eps, max_iter)
 
-    def fit_reduced(self, Y, rank: int, landmarks=None, slab_rows: int = 0, factor: str = "host"):
+    def fit_reduced(self, Y, rank: int, landmarks=None, slab_rows: int = 0, factor: str = "host", sample_weight=None):
         """:func:`fit_reduced` on this resident problem at its own cost (``lssvm_mi355_problem_fit_reduced``; ``factor="device"``: ``lssvm_mi355_problem_fit_reduced_dev``).
         The problem is left as it was and keeps its preconditioner.
-        Not on a problem of several devices or ranks, not with weights set, not between :meth:`cg_begin` and :meth:`cg_finish`."""
+        Not on a problem of several devices or ranks, not with weights set, not between :meth:`cg_begin` and :meth:`cg_finish`.
+        ``sample_weight`` (``lssvm_mi355_problem_fit_reduced_weighted``): the weights of :func:`fit_reduced` -- the keyword is the only source of weights, :meth:`set_weights`
+        is not consulted (and still refused)."""
         on_device = _capi.factor_on_device(factor)
+        w = _reduced_weights(sample_weight, self.num_points)
         Y2, single, rank, _, lm_ptr, slab_rows = _reduced_arguments(Y, self.num_points, self.dtype, rank, self._selected(rank, landmarks), slab_rows)
-        return _reduced_call(_reduced_entry("problem_fit_reduced", on_device), (self._h,), Y2, single, rank, lm_ptr, slab_rows, on_device=on_device)
+        return _reduced_call(_reduced_entry("problem_fit_reduced", on_device, weighted=w is not None), (self._h,), Y2, single, rank, lm_ptr, slab_rows, on_device=on_device, weights=w)
 
     def landmark_gram(self, Y, rank: int, landmarks=None, slab_rows: int = 0):
         """The operator of :meth:`fit_reduced` alone (a test aid, ``lssvm_mi355_problem_landmark_gram``): ``[Phi | 1 | Y]^T [Phi | 1 | Y]`` as the device sums it,
@@ -802,14 +844,28 @@ class ResidentProblem:
         check(_capi.reduced_entry("lssvm_mi355_problem_landmark_gram")(self._h, ptr(Y2), Y2.shape[0], rank, lm_ptr, slab_rows, out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
 
-    def fit_reduced_loo(self, Y, rank: int, costs, landmarks=None, slab_rows: int = 0, factor: str = "host"):
+    def landmark_gram_weighted(self, Y, rank: int, sample_weight, landmarks=None, slab_rows: int = 0):
+        """The operator of the weighted :meth:`fit_reduced` alone (a test aid, ``lssvm_mi355_problem_landmark_gram_weighted``): ``[Phi | 1 | Y]^T diag(w) [Phi | 1 | Y]``
+        as the device sums it, ``(rank + 1 + k, rank + 1 + k)`` float64, both triangles."""
+        w = _reduced_weights(sample_weight, self.num_points)
+        Y2, _, rank, _, lm_ptr, slab_rows = _reduced_arguments(Y, self.num_points, self.dtype, rank, landmarks, slab_rows)
+        cols = rank + 1 + Y2.shape[0]
+        out = np.zeros((cols, cols), dtype=np.float64)
+        dp = C.POINTER(C.c_double)
+        check(_capi.reduced_weighted_entry("lssvm_mi355_problem_landmark_gram_weighted")(self._h, ptr(Y2), Y2.shape[0], None if w is None else w.ctypes.data_as(dp), rank, lm_ptr, slab_rows,
+                                                                                          out.ctypes.data_as(dp)))
+        return out
+
+    def fit_reduced_loo(self, Y, rank: int, costs, landmarks=None, slab_rows: int = 0, factor: str = "host", sample_weight=None):
         """:func:`fit_reduced_loo` on this resident problem (``lssvm_mi355_problem_fit_reduced_loo``; ``factor="device"``: ``lssvm_mi355_problem_fit_reduced_loo_dev``):
         leave-one-out with the landmark set held fixed, at every cost of ``costs``.  The problem's own cost is ignored; the problem is left as it was and keeps its
-        preconditioner.  Refused where :meth:`fit_reduced` is."""
+        preconditioner.  Refused where :meth:`fit_reduced` is.  ``sample_weight`` (``lssvm_mi355_problem_fit_reduced_loo_weighted``): as for :func:`fit_reduced_loo`."""
         on_device = _capi.factor_on_device(factor)
+        w = _reduced_weights(sample_weight, self.num_points)
         Y2, single, rank, _, lm_ptr, slab_rows = _reduced_arguments(Y, self.num_points, self.dtype, rank, self._selected(rank, landmarks), slab_rows)
         costs = _reduced_loo_costs(costs)
-        return _reduced_loo_call(_reduced_entry("problem_fit_reduced_loo", on_device), (self._h,), Y2, single, self.num_points, rank, lm_ptr, slab_rows, costs, on_device=on_device)
+        return _reduced_loo_call(_reduced_entry("problem_fit_reduced_loo", on_device, weighted=w is not None), (self._h,), Y2, single, self.num_points, rank, lm_ptr, slab_rows, costs,
+                                 on_device=on_device, weights=w)
 
     def reduced_leverage(self, V, shift, B_extra=None, landmarks=None, slab_rows: int = 0):
         """The operator of :meth:`fit_reduced_loo` alone on the caller's operands (a test aid, ``lssvm_mi355_problem_reduced_leverage``): with ``phic_i = phi_i - shift``,

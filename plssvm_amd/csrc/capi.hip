@@ -224,17 +224,18 @@ void pcg_one_shot(const lssvm_params *params, const T *X, size_t N, size_t d, co
 template <typename T>
 void fit_reduced_one_shot(const lssvm_params *params, const T *X, size_t N, size_t d, const T *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows,
                           double *betas_out, double *rhos_out, uint64_t *landmarks_out, lssvm_reduced_info *info, const lssvm_mi355_options *options, bool on_device = false,
-                          lssvm_dense_info *dense = nullptr) {
+                          lssvm_dense_info *dense = nullptr, const double *weights = nullptr) {
     lssvm::check_params(params);
     check_data(X, N, d);
     lssvm::check_reduced_arguments(Y, num_rhs, rank, slab_rows, N);
     LSSVM_REQUIRE(betas_out != nullptr && rhos_out != nullptr, "betas_out / rhos_out must not be NULL");
     if (landmarks != nullptr) (void) lssvm::resolve_landmarks(landmarks, static_cast<size_t>(rank), N);
+    if (weights != nullptr) (void) lssvm::check_reduced_weights(weights, N);
     lssvm::Solver<T> prob = device0_solver<T>(options, *params, X, N, d);
     if (on_device) {
-        prob.fit_reduced_dev(Y, num_rhs, rank, landmarks, slab_rows, betas_out, rhos_out, landmarks_out, info, dense);
+        prob.fit_reduced_dev(Y, num_rhs, rank, landmarks, slab_rows, betas_out, rhos_out, landmarks_out, info, dense, weights);
     } else {
-        prob.fit_reduced(Y, num_rhs, rank, landmarks, slab_rows, betas_out, rhos_out, landmarks_out, info);
+        prob.fit_reduced(Y, num_rhs, rank, landmarks, slab_rows, betas_out, rhos_out, landmarks_out, info, weights);
     }
 }
 
@@ -243,19 +244,21 @@ template <typename T>
 void fit_reduced_loo_one_shot(const lssvm_params *params, const T *X, size_t N, size_t d, const T *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows,
                               const double *costs, size_t num_costs, double *betas_out, double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out, double *press_out,
                               uint64_t *loo_errors_out, uint64_t *landmarks_out, lssvm_reduced_loo_info *infos, const lssvm_mi355_options *options, bool on_device = false,
-                              lssvm_dense_info *dense = nullptr) {
+                              lssvm_dense_info *dense = nullptr, const double *weights = nullptr) {
     lssvm::check_params(params);
     check_data(X, N, d);
     lssvm::check_reduced_arguments(Y, num_rhs, rank, slab_rows, N);
     lssvm::check_reduced_loo_costs(costs, num_costs);
     LSSVM_REQUIRE(betas_out != nullptr && rhos_out != nullptr, "betas_out / rhos_out must not be NULL");
     if (landmarks != nullptr) (void) lssvm::resolve_landmarks(landmarks, static_cast<size_t>(rank), N);
+    if (weights != nullptr) (void) lssvm::check_reduced_weights(weights, N);
     lssvm::Solver<T> prob = device0_solver<T>(options, *params, X, N, d);
     if (on_device) {
         prob.fit_reduced_loo_dev(Y, num_rhs, rank, landmarks, slab_rows, costs, num_costs, betas_out, rhos_out, leverage_out, fitted_out, loo_out, press_out, loo_errors_out, landmarks_out, infos,
-                                 dense);
+                                 dense, weights);
     } else {
-        prob.fit_reduced_loo(Y, num_rhs, rank, landmarks, slab_rows, costs, num_costs, betas_out, rhos_out, leverage_out, fitted_out, loo_out, press_out, loo_errors_out, landmarks_out, infos);
+        prob.fit_reduced_loo(Y, num_rhs, rank, landmarks, slab_rows, costs, num_costs, betas_out, rhos_out, leverage_out, fitted_out, loo_out, press_out, loo_errors_out, landmarks_out, infos,
+                             weights);
     }
 }
 
@@ -830,6 +833,86 @@ int lssvm_mi355_fit_reduced_loo_dev_f64(const lssvm_params *params, const double
     return guarded([&] {
         fit_reduced_loo_one_shot<double>(params, X, num_points, num_features, Y, num_rhs, rank, landmarks, slab_rows, costs, num_costs, betas_out, rhos_out, leverage_out, fitted_out, loo_out,
                                          press_out, loo_errors_out, landmarks_out, infos, options, true, dense);
+    });
+}
+/* the weighted forms: the checks of the unweighted forms in their order, then `factor`; the weights need N: the solver checks them before it touches
+ * the device.  weights NULL: the unweighted entry point's call */
+int lssvm_mi355_problem_fit_reduced_weighted(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, const double *weights, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows,
+                                             int factor, double *betas_out, double *rhos_out, uint64_t *landmarks_out, lssvm_reduced_info *info, lssvm_dense_info *dense) {
+    return guarded([&] {
+        LSSVM_REQUIRE(p != nullptr, "problem handle must not be NULL");
+        lssvm::check_reduced_arguments(Y, num_rhs, rank, slab_rows, 0);
+        LSSVM_REQUIRE(betas_out != nullptr && rhos_out != nullptr, "betas_out / rhos_out must not be NULL");
+        lssvm::check_reduced_factor(factor);
+        if (factor == 1) {
+            impl_of(p)->fit_reduced_dev(Y, num_rhs, rank, landmarks, slab_rows, betas_out, rhos_out, landmarks_out, info, dense, weights);
+        } else {
+            impl_of(p)->fit_reduced(Y, num_rhs, rank, landmarks, slab_rows, betas_out, rhos_out, landmarks_out, info, weights);
+        }
+    });
+}
+int lssvm_mi355_fit_reduced_weighted_f32(const lssvm_params *params, const float *X, size_t num_points, size_t num_features, const float *Y, size_t num_rhs, const double *weights,
+                                         uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, int factor, double *betas_out, double *rhos_out, uint64_t *landmarks_out,
+                                         lssvm_reduced_info *info, lssvm_dense_info *dense, const lssvm_mi355_options *options) {
+    return guarded([&] {
+        lssvm::check_reduced_factor(factor);
+        fit_reduced_one_shot<float>(params, X, num_points, num_features, Y, num_rhs, rank, landmarks, slab_rows, betas_out, rhos_out, landmarks_out, info, options, factor == 1, dense, weights);
+    });
+}
+int lssvm_mi355_fit_reduced_weighted_f64(const lssvm_params *params, const double *X, size_t num_points, size_t num_features, const double *Y, size_t num_rhs, const double *weights,
+                                         uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, int factor, double *betas_out, double *rhos_out, uint64_t *landmarks_out,
+                                         lssvm_reduced_info *info, lssvm_dense_info *dense, const lssvm_mi355_options *options) {
+    return guarded([&] {
+        lssvm::check_reduced_factor(factor);
+        fit_reduced_one_shot<double>(params, X, num_points, num_features, Y, num_rhs, rank, landmarks, slab_rows, betas_out, rhos_out, landmarks_out, info, options, factor == 1, dense, weights);
+    });
+}
+int lssvm_mi355_problem_fit_reduced_loo_weighted(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, const double *weights, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows,
+                                                 const double *costs, size_t num_costs, int factor, double *betas_out, double *rhos_out, double *leverage_out, double *fitted_out,
+                                                 double *loo_out, double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out, lssvm_reduced_loo_info *infos,
+                                                 lssvm_dense_info *dense) {
+    return guarded([&] {
+        LSSVM_REQUIRE(p != nullptr, "problem handle must not be NULL");
+        lssvm::check_reduced_arguments(Y, num_rhs, rank, slab_rows, 0);
+        lssvm::check_reduced_loo_costs(costs, num_costs);
+        LSSVM_REQUIRE(betas_out != nullptr && rhos_out != nullptr, "betas_out / rhos_out must not be NULL");
+        lssvm::check_reduced_factor(factor);
+        if (factor == 1) {
+            impl_of(p)->fit_reduced_loo_dev(Y, num_rhs, rank, landmarks, slab_rows, costs, num_costs, betas_out, rhos_out, leverage_out, fitted_out, loo_out, press_out, loo_errors_out,
+                                            landmarks_out, infos, dense, weights);
+        } else {
+            impl_of(p)->fit_reduced_loo(Y, num_rhs, rank, landmarks, slab_rows, costs, num_costs, betas_out, rhos_out, leverage_out, fitted_out, loo_out, press_out, loo_errors_out,
+                                        landmarks_out, infos, weights);
+        }
+    });
+}
+int lssvm_mi355_fit_reduced_loo_weighted_f32(const lssvm_params *params, const float *X, size_t num_points, size_t num_features, const float *Y, size_t num_rhs, const double *weights,
+                                             uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *costs, size_t num_costs, int factor, double *betas_out,
+                                             double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out,
+                                             uint64_t *landmarks_out, lssvm_reduced_loo_info *infos, lssvm_dense_info *dense, const lssvm_mi355_options *options) {
+    return guarded([&] {
+        lssvm::check_reduced_factor(factor);
+        fit_reduced_loo_one_shot<float>(params, X, num_points, num_features, Y, num_rhs, rank, landmarks, slab_rows, costs, num_costs, betas_out, rhos_out, leverage_out, fitted_out, loo_out,
+                                        press_out, loo_errors_out, landmarks_out, infos, options, factor == 1, dense, weights);
+    });
+}
+int lssvm_mi355_fit_reduced_loo_weighted_f64(const lssvm_params *params, const double *X, size_t num_points, size_t num_features, const double *Y, size_t num_rhs, const double *weights,
+                                             uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *costs, size_t num_costs, int factor, double *betas_out,
+                                             double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out,
+                                             uint64_t *landmarks_out, lssvm_reduced_loo_info *infos, lssvm_dense_info *dense, const lssvm_mi355_options *options) {
+    return guarded([&] {
+        lssvm::check_reduced_factor(factor);
+        fit_reduced_loo_one_shot<double>(params, X, num_points, num_features, Y, num_rhs, rank, landmarks, slab_rows, costs, num_costs, betas_out, rhos_out, leverage_out, fitted_out, loo_out,
+                                         press_out, loo_errors_out, landmarks_out, infos, options, factor == 1, dense, weights);
+    });
+}
+int lssvm_mi355_problem_landmark_gram_weighted(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, const double *weights, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows,
+                                               double *gram_out) {
+    return guarded([&] {
+        LSSVM_REQUIRE(p != nullptr, "problem handle must not be NULL");
+        lssvm::check_reduced_arguments(Y, num_rhs, rank, slab_rows, 0);
+        LSSVM_REQUIRE(gram_out != nullptr, "gram_out must not be NULL");
+        impl_of(p)->landmark_gram(Y, num_rhs, rank, landmarks, slab_rows, gram_out, weights);
     });
 }
 /* the dense toolbox alone on host arrays (include/plssvm_amd_testing.h): every refusal before a device is touched */

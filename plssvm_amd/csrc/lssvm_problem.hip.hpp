@@ -621,21 +621,22 @@ struct ProblemBase {
     virtual void solve_pcg(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_pcg_info *infos_out) = 0;  // lssvm_mi355_problem_solve_pcg
     /* the fixed-size model (lssvm_reduced.hip) */
     virtual void fit_reduced(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, double *betas_out, double *rhos_out,
-                             uint64_t *landmarks_out, lssvm_reduced_info *info) = 0;  // lssvm_mi355_problem_fit_reduced
-    virtual void landmark_gram(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, double *gram_out) = 0;  // lssvm_mi355_problem_landmark_gram
+                             uint64_t *landmarks_out, lssvm_reduced_info *info, const double *weights = nullptr) = 0;  // lssvm_mi355_problem_fit_reduced
+    virtual void landmark_gram(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, double *gram_out, const double *weights = nullptr) = 0;  // lssvm_mi355_problem_landmark_gram
     virtual void time_gram_kernels(int repeats, double *parent_ms_out, double *mfma_ms_out, double *max_diff_out) = 0;  // lssvm_mi355_problem_time_gram_kernels
     /* exact leave-one-out scores of the fixed-size model over a cost grid (lssvm_reduced.hip) */
     virtual void fit_reduced_loo(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *costs, size_t num_costs, double *betas_out,
                                  double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out,
-                                 lssvm_reduced_loo_info *infos) = 0;  // lssvm_mi355_problem_fit_reduced_loo
+                                 lssvm_reduced_loo_info *infos, const double *weights = nullptr) = 0;  // lssvm_mi355_problem_fit_reduced_loo
     virtual void reduced_leverage(uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *V, const double *shift, const double *B_extra, size_t k, double *h_out,
                                   double *f_out) = 0;  // lssvm_mi355_problem_reduced_leverage
+    /* `weights` in the five above: N doubles on the host, each finite and >= 0 with a positive sum, for the weighted objective -- or NULL */
     /* both fits with the dense steps on the device (lssvm_dense.hip); `dense`: one record, or num_costs of them, or NULL */
     virtual void fit_reduced_dev(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, double *betas_out, double *rhos_out,
-                                 uint64_t *landmarks_out, lssvm_reduced_info *info, lssvm_dense_info *dense) = 0;  // lssvm_mi355_problem_fit_reduced_dev
+                                 uint64_t *landmarks_out, lssvm_reduced_info *info, lssvm_dense_info *dense, const double *weights = nullptr) = 0;  // lssvm_mi355_problem_fit_reduced_dev
     virtual void fit_reduced_loo_dev(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *costs, size_t num_costs, double *betas_out,
                                      double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out,
-                                     lssvm_reduced_loo_info *infos, lssvm_dense_info *dense) = 0;  // lssvm_mi355_problem_fit_reduced_loo_dev
+                                     lssvm_reduced_loo_info *infos, lssvm_dense_info *dense, const double *weights = nullptr) = 0;  // lssvm_mi355_problem_fit_reduced_loo_dev
     virtual void time_leverage_kernel(uint64_t rank, uint64_t slab_rows, size_t k, int repeats, double *gram_ms_out, double *leverage_ms_out) = 0;  // lssvm_mi355_problem_time_leverage_kernel
     /* landmark selection: the pivots of a greedy or randomly pivoted partial Cholesky factorisation (lssvm_select.hip) */
     virtual void select_landmarks(uint64_t rank, int method, uint64_t pool, uint64_t seed, double tol, uint64_t *landmarks_out, double *trace_out, double *residual_out,
@@ -733,22 +734,22 @@ class Solver final : public ProblemBase {
     void solve_pcg(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_pcg_info *infos_out) override;
     /* the fixed-size model over m landmarks: [Phi | 1 | Y]^T [Phi | 1 | Y] on the fp64 matrix cores, slab by slab, and the host's solve (lssvm_reduced.hip) */
     void fit_reduced(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, double *betas_out, double *rhos_out, uint64_t *landmarks_out,
-                     lssvm_reduced_info *info) override;
-    void landmark_gram(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, double *gram_out) override;
+                     lssvm_reduced_info *info, const double *weights = nullptr) override;
+    void landmark_gram(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, double *gram_out, const double *weights = nullptr) override;
     void time_gram_kernels(int repeats, double *parent_ms_out, double *mfma_ms_out, double *max_diff_out) override;
     /* leave-one-out with the landmark set held fixed, every cost of a grid: pass 1 is reduced_gram, pass 2 the leverage kernel per slab and cost */
     void fit_reduced_loo(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *costs, size_t num_costs, double *betas_out,
                          double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out,
-                         lssvm_reduced_loo_info *infos) override;
+                         lssvm_reduced_loo_info *infos, const double *weights = nullptr) override;
     void reduced_leverage(uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *V, const double *shift, const double *B_extra, size_t k, double *h_out,
                           double *f_out) override;
     void time_leverage_kernel(uint64_t rank, uint64_t slab_rows, size_t k, int repeats, double *gram_ms_out, double *leverage_ms_out) override;
     /* fit_reduced and fit_reduced_loo with assembly, factorisation, solves and the triangular inverse on the device (lssvm_dense.hip) */
     void fit_reduced_dev(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, double *betas_out, double *rhos_out, uint64_t *landmarks_out,
-                         lssvm_reduced_info *info, lssvm_dense_info *dense) override;
+                         lssvm_reduced_info *info, lssvm_dense_info *dense, const double *weights = nullptr) override;
     void fit_reduced_loo_dev(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *costs, size_t num_costs, double *betas_out,
                              double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out,
-                             lssvm_reduced_loo_info *infos, lssvm_dense_info *dense) override;
+                             lssvm_reduced_loo_info *infos, lssvm_dense_info *dense, const double *weights = nullptr) override;
     /* the pivots of a partial Cholesky factorisation of K over the candidates, one launch pair per step on shard 0's stream (lssvm_select.hip) */
     void select_landmarks(uint64_t rank, int method, uint64_t pool, uint64_t seed, double tol, uint64_t *landmarks_out, double *trace_out, double *residual_out,
                           lssvm_landmark_select_info *info) override;
@@ -791,9 +792,11 @@ class Solver final : public ProblemBase {
     Problem<T> &precond_problem(const char *what);                        // the checks every preconditioner entry point shares; shard 0
     void enqueue_precond_apply(const T *r, T *z, double *part_rz) const;  // z = r - Bhat G^-1 Bhat^T r and the partial sums of r.z
     Problem<T> &reduced_problem(const char *what, bool unweighted_only);  // the checks every entry point of the fixed-size model shares; shard 0 (lssvm_reduced.hip)
-    /* what fit_reduced and landmark_gram share: the checks, the slabs, St (cols x cols, both triangles) and K_mm (rank x rank) on the host */
+    /* what fit_reduced and landmark_gram share: the checks, the slabs, St (cols x cols, both triangles) and K_mm (rank x rank) on the host.  `weights` (N doubles on the
+     * host, or NULL): St = Pt^T diag(w) Pt; `total_out`: what stands for N in the host's formulas -- the sum of the weights, N without them */
     void reduced_gram(const char *what, const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, std::vector<uint64_t> &lm_out,
-                      std::vector<double> &gram_out, std::vector<double> &kmm_out, lssvm_reduced_info &info, ReducedOnDevice *keep = nullptr);
+                      std::vector<double> &gram_out, std::vector<double> &kmm_out, lssvm_reduced_info &info, ReducedOnDevice *keep = nullptr, const double *weights = nullptr,
+                      double *total_out = nullptr);
     /* pass 2 of fit_reduced_loo, and all of reduced_leverage: the Phi slabs again, the leverage kernel per slab and operand (lssvm_reduced.hip) */
     void leverage_pass(const std::vector<uint64_t> &lm, uint64_t slab_rows, LeverageArgs &args);
     T *vec_of(Problem<T> &p, Vec which) const { return which == Vec::d ? p.own_.d.p : (which == Vec::x ? p.own_.x.p : p.tmp_.p); }
@@ -839,6 +842,9 @@ std::vector<uint64_t> resolve_landmarks(const uint64_t *landmarks, size_t rank, 
 constexpr int REDUCED_MAX_RANK = 1024;
 constexpr uint64_t REDUCED_DEFAULT_SLAB_ROWS = 65536;
 void check_reduced_arguments(const void *Y, size_t num_rhs, uint64_t rank, uint64_t slab_rows, size_t num_points);
+/* the weights of the weighted forms: each finite and >= 0, their sum (in index order: what is returned) finite and > 0; and their `factor`: 0 or 1 */
+double check_reduced_weights(const double *weights, size_t num_points);
+void check_reduced_factor(int factor);
 /* the cost grid of lssvm_mi355_problem_fit_reduced_loo / lssvm_mi355_fit_reduced_loo_*: 1 ... REDUCED_LOO_MAX_COSTS costs, each finite and positive */
 constexpr size_t REDUCED_LOO_MAX_COSTS = 64;
 void check_reduced_loo_costs(const double *costs, size_t num_costs);

@@ -17,6 +17,10 @@
  * and the model refitted without point i predicts y_i - (y_i - f(x_i)) / (1 - h_ii) at x_i.  Pass 1 is reduced_gram; per cost the host factors (factor_reduced,
  * solve_reduced: the code of fit_reduced) and inverts L; pass 2 evaluates the slabs again and k_reduced_leverage forms Phic [V^T | beta] on the matrix cores per slab and
  * cost, keeping only the rows' squared norms, the fitted and the leave-one-out values.
+ *
+ * Per-point weights w_i >= 0 (lssvm_mi355_problem_fit_reduced_weighted, _fit_reduced_loo_weighted, _landmark_gram_weighted): St = Pt^T diag(w) Pt and
+ * W = sum w_i wherever N stands.  k_reduced_gram<true> multiplies both staged operands by sqrt(w_i) (formed on the host, uploaded once per call; the slab stays unscaled),
+ * k_reduced_leverage multiplies by w_i; everything between them takes W as the double it took N as.  Without weights every call launches what it launched before.
  */
 #include "lssvm_dense.hip.hpp"
 #include "lssvm_landmark.hip.hpp"
@@ -51,8 +55,14 @@ __global__ __launch_bounds__(256) void k_reduced_aux(const T *__restrict__ Y, si
  * column-major `slab` (ld doubles between two columns; columns from `cols` on count as zeros and are never read; `rows` is a multiple of RG_KC), for tile = (bj, bk),
  * bk <= bj.  Both operands go through LDS: eight threads load the 16 rows of a column of a step as one 128-byte line, the fragments are read as in tile_matvec_f64
  * (lane 16 q + r: column r of the block, row q of the k-step).  A diagonal tile stages and reads ONE operand.  The result of a lane: column r of B, rows q + 4 i of A.
- * Two waves per SIMD (at most 256 registers): the other workgroup of the CU computes while this one waits at its barriers. */
-__global__ __launch_bounds__(256, 2) void k_reduced_gram(const double *__restrict__ slab, size_t ld, int cols, int rows, int max_chunks, double *__restrict__ part) {
+ * Two waves per SIMD (at most 256 registers): the other workgroup of the CU computes while this one waits at its barriers.
+ * WEIGHTED: the result is A^T diag(w) B.  `q` holds sqrt(w) for the slab's rows (indexed like them, zeros from row N on) and BOTH operands are
+ * multiplied by it between stage_load and stage_store -- one f64x2 of q per step and thread, one product per staged pair; the slab stays as it is.  sqrt(w) on both sides
+ * and not w on one: a diagonal tile keeps its single operand, and every partial tile is a Gram matrix (its diagonal a sum of squares), which the Cholesky factorisation
+ * behind it rests on.  The `false` instantiation is the kernel as it was: q is not read. */
+template <bool WEIGHTED>
+__global__ __launch_bounds__(256, 2) void k_reduced_gram(const double *__restrict__ slab, size_t ld, int cols, int rows, int max_chunks, double *__restrict__ part,
+                                                         const double *__restrict__ q) {
     __shared__ __attribute__((aligned(16))) double As[RG_TW * RG_LS];
     __shared__ __attribute__((aligned(16))) double Bs_own[RG_TW * RG_LS];
 
@@ -86,8 +96,11 @@ __global__ __launch_bounds__(256, 2) void k_reduced_gram(const double *__restric
     }
     const int lds_w = srow * RG_LS + 2 * sseg;
     f64x2 sa[4], sb[4];
+    f64x2 sq = { 0.0, 0.0 };  // WEIGHTED: sqrt(w) of the step's rows 2 sseg, 2 sseg + 1
     const f64x2 zero2 = { 0.0, 0.0 };
+    const double *qg = WEIGHTED ? q + row_begin + 2 * sseg : nullptr;
     auto stage_load = [&](int s) {
+        if constexpr (WEIGHTED) sq = *reinterpret_cast<const f64x2 *>(qg + s * RG_KC);
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
             sa[p] = a_in[p] ? *reinterpret_cast<const f64x2 *>(Ag[p] + s * RG_KC) : zero2;
@@ -95,6 +108,13 @@ __global__ __launch_bounds__(256, 2) void k_reduced_gram(const double *__restric
         }
     };
     auto stage_store = [&]() {
+        if constexpr (WEIGHTED) {  // (here and not behind the loads: the step's MFMAs stand between a load and its first use)
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                sa[p] *= sq;
+                if (!diag) sb[p] *= sq;
+            }
+        }
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
             *reinterpret_cast<f64x2 *>(As + lds_w + p * 32 * RG_LS) = sa[p];
@@ -162,10 +182,14 @@ __global__ __launch_bounds__(256) void k_reduced_sum(const double *__restrict__ 
 
 int tiles_of(int cols) { return (cols + RG_TW - 1) / RG_TW; }
 
-/* St of one slab into the running sum: `rows` (a multiple of 256) rows of the column-major slab */
-void enqueue_gram(const double *slab, size_t ld, int cols, int rows, int max_chunks, double *part, double *St, hipStream_t st) {
+/* St of one slab into the running sum: `rows` (a multiple of 256) rows of the column-major slab; `q`: sqrt(w) of these rows (`rows` doubles) for the weighted sum, or NULL */
+void enqueue_gram(const double *slab, size_t ld, int cols, int rows, int max_chunks, double *part, double *St, hipStream_t st, const double *q = nullptr) {
     const int nt = tiles_of(cols), ntri = nt * (nt + 1) / 2, chunks = (rows + RG_RANGE - 1) / RG_RANGE;
-    hipLaunchKernelGGL(k_reduced_gram, dim3(ntri, chunks), dim3(256), 0, st, slab, ld, cols, rows, max_chunks, part);
+    if (q != nullptr) {
+        hipLaunchKernelGGL(k_reduced_gram<true>, dim3(ntri, chunks), dim3(256), 0, st, slab, ld, cols, rows, max_chunks, part, q);
+    } else {
+        hipLaunchKernelGGL(k_reduced_gram<false>, dim3(ntri, chunks), dim3(256), 0, st, slab, ld, cols, rows, max_chunks, part, q);
+    }
     hipLaunchKernelGGL(k_reduced_sum, dim3(RG_TILE / 256, ntri), dim3(256), 0, st, part, chunks, max_chunks, St);
     LSSVM_HIP_CHECK(hipGetLastError());
 }
@@ -377,10 +401,12 @@ constexpr int LV_LSA = RG_TW + 16;  // doubles between two columns of Phi in LDS
  * A row's sum of squares: per column block a lane's four column tiles in ascending order, then the sixteen lanes that share the row (xor 1, 2, 4, 8), the blocks one
  * behind the other in LDS (the sums are not held in registers across a block), at the end the two column waves -- an order that depends on m only. A row's values depend on that row, Bt, shift and ybar only.  No atomics, no scratch.
  * h_out[i] = inv_n + sum; f_out[c ldo + i] = T[i][m + c] + ybar[c] (ybar NULL: 0); loo_out[c ldo + i] = y - (y - f) / (1 - h) with y = ycols[c ld + i] (loo_out NULL:
- * not formed).  Rows from `rows` on write nothing. */
+ * not formed).  Rows from `rows` on write nothing.
+ * `w` (NULL: the unweighted model, the expressions above): the rows' weights, indexed like the slab's rows; then h_out[i] = w[i] (inv_n + sum) with
+ * inv_n = 1 / sum of the weights, and a row of weight 0 -- h = 0, it took no part in the fit -- gets loo = f itself (y - (y - f) / 1 rounds twice). */
 __global__ __launch_bounds__(256, 2) void k_reduced_leverage(const double *__restrict__ slab, size_t ld, int rows, int m, int k, const double *__restrict__ Bt, int ldb,
                                                              const double *__restrict__ shift, const double *__restrict__ ybar, double inv_n, const double *__restrict__ ycols,
-                                                             double *__restrict__ h_out, double *f_out, double *__restrict__ loo_out, size_t ldo) {
+                                                             double *__restrict__ h_out, double *f_out, double *__restrict__ loo_out, size_t ldo, const double *__restrict__ w) {
     __shared__ __attribute__((aligned(16))) double As[RG_KC * LV_LSA];
     __shared__ __attribute__((aligned(16))) double Bs[RG_TW * RG_LS];
     __shared__ double hs[3 * RG_TW];  // the rows' sums of squares of the two column waves, then h
@@ -521,17 +547,18 @@ __global__ __launch_bounds__(256, 2) void k_reduced_leverage(const double *__res
     __syncthreads();  // (and this workgroup's f_out is visible to all of it)
     const int lrow = tid & (RG_TW - 1);
     if (tid < RG_TW) {
-        const double h = inv_n + (hs[tid] + hs[RG_TW + tid]);
+        const double h = w != nullptr ? w[row0 + tid] * (inv_n + (hs[tid] + hs[RG_TW + tid])) : inv_n + (hs[tid] + hs[RG_TW + tid]);
         hs[2 * RG_TW + tid] = h;
         if (row0 + tid < rows) h_out[row0 + tid] = h;
     }
     __syncthreads();
     if (loo_out != nullptr && row0 + lrow < rows) {
         const double h = hs[2 * RG_TW + lrow];
+        const bool left_out = w != nullptr && w[row0 + lrow] == 0.0;
         for (int c = tid >> 7; c < k; c += 2) {
             const double y = ycols[static_cast<size_t>(c) * ld + row0 + lrow];
             const double f = f_out[static_cast<size_t>(c) * ldo + row0 + lrow];
-            loo_out[static_cast<size_t>(c) * ldo + row0 + lrow] = y - (y - f) / (1.0 - h);
+            loo_out[static_cast<size_t>(c) * ldo + row0 + lrow] = left_out ? f : y - (y - f) / (1.0 - h);
         }
     }
 }
@@ -545,6 +572,7 @@ struct LeverageArgs {
     DevBuf<double> Bt, shift, ybar;
     double inv_n = 0.0;
     const void *Y = nullptr;                                             // the host's right-hand sides (k x N, the problem's type), or NULL: no leave-one-out values
+    const double *w = nullptr;                                           // the host's N weights (inv_n is then 1 / their sum), or NULL: the unweighted model
     double *h_out = nullptr, *f_out = nullptr, *loo_out = nullptr;       // num_ops x N, num_ops x k x N, num_ops x k x N; each may be NULL
     double *press = nullptr;                                             // num_ops x k, or NULL
     uint64_t *errors = nullptr;                                          // num_ops x k, or NULL
@@ -569,9 +597,9 @@ struct LeverageArgs {
         LSSVM_HIP_CHECK(hipStreamSynchronize(st));
     }
     /* k_reduced_leverage for operand o on `rows` rows of a slab (ld doubles between its columns; its [1 | Y] columns stand behind Phi where `loo` is given) */
-    void enqueue(size_t o, const double *slab, size_t ld, int rows, double *h, double *f, double *loo) const {
+    void enqueue(size_t o, const double *slab, size_t ld, int rows, double *h, double *f, double *loo, const double *w_dev = nullptr) const {
         hipLaunchKernelGGL(k_reduced_leverage, dim3(round_up(rows, 256) / RG_TW), dim3(256), 0, st, slab, ld, rows, m, k, Bt.p + o * op_stride, ldb, shift.p, ybar.p != nullptr ? ybar.p + o * k : nullptr,
-                           inv_n, loo != nullptr ? slab + static_cast<size_t>(m + 1) * ld : nullptr, h, f, loo, ld);
+                           inv_n, loo != nullptr ? slab + static_cast<size_t>(m + 1) * ld : nullptr, h, f, loo, ld, w_dev);
         LSSVM_HIP_CHECK(hipGetLastError());
     }
     hipStream_t st;
@@ -585,6 +613,33 @@ void check_reduced_arguments(const void *Y, size_t num_rhs, uint64_t rank, uint6
     LSSVM_REQUIRE(slab_rows % 256 == 0, "slab_rows must be a multiple of 256 (0: the library's default), but is " + std::to_string(slab_rows) + "!");
 }
 
+double check_reduced_weights(const double *weights, size_t num_points) {
+    double total = 0.0;
+    for (size_t i = 0; i < num_points; ++i) {
+        LSSVM_REQUIRE(std::isfinite(weights[i]) && weights[i] >= 0.0,
+                      "Every weight of the reduced model must be finite and not less than 0.0, but weight " + std::to_string(i) + " is " + std::to_string(weights[i]) + "!");
+        total += weights[i];
+    }
+    LSSVM_REQUIRE(std::isfinite(total) && total > 0.0, "The weights of the reduced model must have a finite sum greater than 0.0, but it is " + std::to_string(total) + "!");
+    return total;
+}
+
+void check_reduced_factor(int factor) { LSSVM_REQUIRE(factor == 0 || factor == 1, "factor must be 0 (the host) or 1 (the device), but is " + std::to_string(factor) + "!"); }
+
+namespace {
+
+/* `values` (N doubles, or their square roots: std::sqrt on the host, correctly rounded, so that the device takes none) on the device behind each other as the slabs' rows
+ * are, zeros from row N on */
+void upload_per_row(const double *values, bool take_sqrt, const SlabPlan &plan, DevBuf<double> &out, hipStream_t st) {
+    std::vector<double> host(static_cast<size_t>(plan.slabs) * plan.ld, 0.0);
+    for (size_t i = 0; i < plan.N; ++i) host[i] = take_sqrt ? std::sqrt(values[i]) : values[i];
+    out.alloc_zero(host.size(), st);
+    LSSVM_HIP_CHECK(hipMemcpyAsync(out.p, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    LSSVM_HIP_CHECK(hipStreamSynchronize(st));  // (`host` goes)
+}
+
+}  // namespace
+
 template <typename T>
 Problem<T> &Solver<T>::reduced_problem(const char *what, bool unweighted_only) {
     LSSVM_REQUIRE(shards_.size() == 1 && world_ == 1 && exchange_ == Exchange::none, std::string("the reduced model (") + what + ") is fitted on a problem of one device and one rank");
@@ -597,7 +652,7 @@ Problem<T> &Solver<T>::reduced_problem(const char *what, bool unweighted_only) {
 
 template <typename T>
 void Solver<T>::reduced_gram(const char *what, const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, std::vector<uint64_t> &lm,
-                             std::vector<double> &gram, std::vector<double> &Kmm, lssvm_reduced_info &info, ReducedOnDevice *keep) {
+                             std::vector<double> &gram, std::vector<double> &Kmm, lssvm_reduced_info &info, ReducedOnDevice *keep, const double *weights, double *total_out) {
     // ---- everything that needs no device ----
     Problem<T> &p = reduced_problem(what, true);
     const size_t N = p.N_;
@@ -605,6 +660,9 @@ void Solver<T>::reduced_gram(const char *what, const void *Y, size_t num_rhs, ui
     LSSVM_REQUIRE(num_rhs <= 4096, "at most 4096 right hand sides per call");
     const int m = static_cast<int>(rank), k = static_cast<int>(num_rhs), cols = m + 1 + k;
     lm = resolve_landmarks(landmarks, static_cast<size_t>(m), N);
+    // what stands for N in the host's formulas: the sum of the weights in index order, N itself without weights
+    const double total = weights != nullptr ? check_reduced_weights(weights, N) : static_cast<double>(N);
+    if (total_out != nullptr) *total_out = total;
 
     const double t0 = now_ms();
     const SetOnExit<bool> busy = hold_busy();
@@ -617,11 +675,12 @@ void Solver<T>::reduced_gram(const char *what, const void *Y, size_t num_rhs, ui
 
     const LandmarkBlock<T> block(p, lm, st);
     const RhsOnDevice<T> rhs(Y, k, N, st);
-    DevBuf<double> slab, part, St_dev, Kmm_dev;
+    DevBuf<double> slab, part, St_dev, Kmm_dev, q_dev;
     slab.alloc_zero(static_cast<size_t>(cols) * ld, st);
     part.alloc_zero(static_cast<size_t>(ntri) * max_chunks * RG_TILE, st);
     St_dev.alloc_zero(static_cast<size_t>(ntri) * RG_TILE, st);
     Kmm_dev.alloc_zero(static_cast<size_t>(m) * m, st);
+    if (weights != nullptr) upload_per_row(weights, true, plan, q_dev, st);
 
     Event ev[3];
     for (Event &e : ev) e.create(true);
@@ -632,7 +691,7 @@ void Solver<T>::reduced_gram(const char *what, const void *Y, size_t num_rhs, ui
         block.enqueue_gather_kmm(slab.p, ld, plan.row0(s), plan.rows(s), Kmm_dev.p);
         LSSVM_HIP_CHECK(hipGetLastError());
         LSSVM_HIP_CHECK(hipEventRecord(ev[1].e, st));
-        enqueue_gram(slab.p, ld, cols, plan.rows256(s), max_chunks, part.p, St_dev.p, st);
+        enqueue_gram(slab.p, ld, cols, plan.rows256(s), max_chunks, part.p, St_dev.p, st, q_dev.p != nullptr ? q_dev.p + plan.row0(s) : nullptr);
         LSSVM_HIP_CHECK(hipEventRecord(ev[2].e, st));
         LSSVM_HIP_CHECK(hipEventSynchronize(ev[2].e));
         landmark_ms += elapsed_ms(ev[0], ev[1]);
@@ -651,7 +710,7 @@ void Solver<T>::reduced_gram(const char *what, const void *Y, size_t num_rhs, ui
     info.landmark_ms = landmark_ms;
     info.gram_ms = gram_ms;
     info.total_ms = now_ms() - t0;
-    info.workspace_bytes = (slab.count + part.count + St_dev.count + Kmm_dev.count) * sizeof(double) + rhs.Y.count * sizeof(T) + block.device_bytes();
+    info.workspace_bytes = (slab.count + part.count + St_dev.count + Kmm_dev.count + q_dev.count) * sizeof(double) + rhs.Y.count * sizeof(T) + block.device_bytes();
     if (keep != nullptr) {  // the device-factored fits go on with both where they lie
         std::swap(keep->St.p, St_dev.p);
         std::swap(keep->St.count, St_dev.count);
@@ -661,29 +720,30 @@ void Solver<T>::reduced_gram(const char *what, const void *Y, size_t num_rhs, ui
 }
 
 template <typename T>
-void Solver<T>::landmark_gram(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, double *gram_out) {
+void Solver<T>::landmark_gram(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, double *gram_out, const double *weights) {
     LSSVM_REQUIRE(gram_out != nullptr, "gram_out must not be NULL");
     std::vector<uint64_t> lm;
     std::vector<double> gram, Kmm;
     lssvm_reduced_info info{};
-    reduced_gram("landmark_gram", Y, num_rhs, rank, landmarks, slab_rows, lm, gram, Kmm, info);
+    reduced_gram("landmark_gram", Y, num_rhs, rank, landmarks, slab_rows, lm, gram, Kmm, info, nullptr, weights);
     std::copy(gram.begin(), gram.end(), gram_out);
 }
 
 template <typename T>
 void Solver<T>::fit_reduced(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, double *betas_out, double *rhos_out, uint64_t *landmarks_out,
-                            lssvm_reduced_info *info_out) {
+                            lssvm_reduced_info *info_out, const double *weights) {
     LSSVM_REQUIRE(betas_out != nullptr && rhos_out != nullptr, "betas_out / rhos_out must not be NULL");
     const double t0 = now_ms();
     std::vector<uint64_t> lm;
     std::vector<double> St, Kmm;
     lssvm_reduced_info info{};
-    reduced_gram("fit_reduced", Y, num_rhs, rank, landmarks, slab_rows, lm, St, Kmm, info);
+    double Nd = 0.0;  // N, or the sum of the weights
+    reduced_gram("fit_reduced", Y, num_rhs, rank, landmarks, slab_rows, lm, St, Kmm, info, nullptr, weights, &Nd);
 
     // ---- the host's part, in double (factor_reduced, solve_reduced: shared with fit_reduced_loo) ----
     const double t_host = now_ms();
     const int m = static_cast<int>(rank), k = static_cast<int>(num_rhs), cols = m + 1 + k;
-    const double Nd = static_cast<double>(shards_[0]->N_), sigma = 1.0 / shards_[0]->params_.cost;  // (in double, whatever the real type: the host's part is the formulation's)
+    const double sigma = 1.0 / shards_[0]->params_.cost;  // (in double, whatever the real type: the host's part is the formulation's)
     std::vector<double> L;
     const double nu = factor_reduced(St, Kmm, m, cols, Nd, sigma, L);
     solve_reduced(St, L, m, k, cols, Nd, betas_out, rhos_out);
@@ -699,19 +759,20 @@ void Solver<T>::fit_reduced(const void *Y, size_t num_rhs, uint64_t rank, const 
 /* fit_reduced with the host's part on the device: St and K_mm stay where reduced_gram summed them */
 template <typename T>
 void Solver<T>::fit_reduced_dev(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, double *betas_out, double *rhos_out, uint64_t *landmarks_out,
-                                lssvm_reduced_info *info_out, lssvm_dense_info *dense_out) {
+                                lssvm_reduced_info *info_out, lssvm_dense_info *dense_out, const double *weights) {
     LSSVM_REQUIRE(betas_out != nullptr && rhos_out != nullptr, "betas_out / rhos_out must not be NULL");
     const double t0 = now_ms();
     std::vector<uint64_t> lm;
     std::vector<double> St, Kmm;
     lssvm_reduced_info info{};
     ReducedOnDevice dev;
-    reduced_gram("fit_reduced", Y, num_rhs, rank, landmarks, slab_rows, lm, St, Kmm, info, &dev);
+    double Nd = 0.0;  // N, or the sum of the weights
+    reduced_gram("fit_reduced", Y, num_rhs, rank, landmarks, slab_rows, lm, St, Kmm, info, &dev, weights, &Nd);
 
     const double t_dense = now_ms();
     const int m = static_cast<int>(rank), k = static_cast<int>(num_rhs), cols = m + 1 + k;
     Problem<T> &p = *shards_[0];
-    const double Nd = static_cast<double>(p.N_), sigma = 1.0 / p.params_.cost;
+    const double sigma = 1.0 / p.params_.cost;
     const SetOnExit<bool> busy = hold_busy();
     p.activate();
     DenseFit fit(m, k, p.stream());
@@ -750,7 +811,8 @@ void Solver<T>::leverage_pass(const std::vector<uint64_t> &lm, uint64_t slab_row
 
     const LandmarkBlock<T> block(p, lm, st);
     const RhsOnDevice<T> rhs(a.Y, k, N, st);
-    DevBuf<double> slab, h_dev, f_dev, loo_dev;
+    DevBuf<double> slab, h_dev, f_dev, loo_dev, w_dev;
+    if (a.w != nullptr) upload_per_row(a.w, false, plan, w_dev, st);
     if (with_y) loo_dev.alloc_zero(static_cast<size_t>(k) * ld, st);
     slab.alloc_zero(static_cast<size_t>(cols) * ld, st);
     h_dev.alloc_zero(ld, st);
@@ -776,7 +838,7 @@ void Solver<T>::leverage_pass(const std::vector<uint64_t> &lm, uint64_t slab_row
         a.landmark_ms += elapsed_ms(ev[0], ev[1]);
         for (size_t o = 0; o < a.num_ops; ++o) {
             LSSVM_HIP_CHECK(hipEventRecord(ev[0].e, st));
-            a.enqueue(o, slab.p, ld, rows, h_dev.p, f_dev.p, loo_dev.p);
+            a.enqueue(o, slab.p, ld, rows, h_dev.p, f_dev.p, loo_dev.p, w_dev.p != nullptr ? w_dev.p + row0 : nullptr);
             LSSVM_HIP_CHECK(hipEventRecord(ev[1].e, st));
             LSSVM_HIP_CHECK(hipMemcpyAsync(h_host.data(), h_dev.p, static_cast<size_t>(rows) * sizeof(double), hipMemcpyDeviceToHost, st));
             for (int c = 0; c < k; ++c) {
@@ -798,8 +860,14 @@ void Solver<T>::leverage_pass(const std::vector<uint64_t> &lm, uint64_t slab_row
                 uint64_t errors = 0;
                 for (int i = 0; i < rows; ++i) {
                     const double y = static_cast<double>(Yh[static_cast<size_t>(c) * N + row0 + i]), d = y - loo[i];
-                    press += d * d;
-                    errors += ((loo[i] > 0.0) - (loo[i] < 0.0)) != ((y > 0.0) - (y < 0.0)) ? 1 : 0;
+                    const bool wrong = ((loo[i] > 0.0) - (loo[i] < 0.0)) != ((y > 0.0) - (y < 0.0));
+                    if (a.w != nullptr) {  // sum_i w_i d_i^2; the errors over the points that took part in the fit
+                        press += a.w[row0 + i] * (d * d);
+                        errors += wrong && a.w[row0 + i] > 0.0 ? 1 : 0;
+                    } else {
+                        press += d * d;
+                        errors += wrong ? 1 : 0;
+                    }
                 }
                 if (a.press != nullptr) a.press[oc] = press;
                 if (a.errors != nullptr) a.errors[oc] += errors;
@@ -811,17 +879,17 @@ void Solver<T>::leverage_pass(const std::vector<uint64_t> &lm, uint64_t slab_row
 template <typename T>
 void Solver<T>::fit_reduced_loo(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *costs, size_t num_costs, double *betas_out,
                                 double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out,
-                                lssvm_reduced_loo_info *infos) {
+                                lssvm_reduced_loo_info *infos, const double *weights) {
     LSSVM_REQUIRE(betas_out != nullptr && rhos_out != nullptr, "betas_out / rhos_out must not be NULL");
     check_reduced_loo_costs(costs, num_costs);
     std::vector<uint64_t> lm;
     std::vector<double> St, Kmm;
     lssvm_reduced_info info{};
-    reduced_gram("fit_reduced_loo", Y, num_rhs, rank, landmarks, slab_rows, lm, St, Kmm, info);  // pass 1, and every other check that needs no device
+    double Nd = 0.0;  // N, or the sum of the weights
+    reduced_gram("fit_reduced_loo", Y, num_rhs, rank, landmarks, slab_rows, lm, St, Kmm, info, nullptr, weights, &Nd);  // pass 1, and every other check that needs no device
 
     const int m = static_cast<int>(rank), k = static_cast<int>(num_rhs), cols = m + 1 + k;
     Problem<T> &p = *shards_[0];
-    const double Nd = static_cast<double>(p.N_);
     const SetOnExit<bool> busy = hold_busy();
     p.activate();
     hipStream_t st = p.stream();
@@ -851,6 +919,7 @@ void Solver<T>::fit_reduced_loo(const void *Y, size_t num_rhs, uint64_t rank, co
 
     a.inv_n = 1.0 / Nd;
     a.Y = Y;
+    a.w = weights;
     a.h_out = leverage_out;
     a.f_out = fitted_out;
     a.loo_out = loo_out;
@@ -877,18 +946,18 @@ void Solver<T>::fit_reduced_loo(const void *Y, size_t num_rhs, uint64_t rank, co
 template <typename T>
 void Solver<T>::fit_reduced_loo_dev(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *costs, size_t num_costs, double *betas_out,
                                     double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out,
-                                    lssvm_reduced_loo_info *infos, lssvm_dense_info *dense_out) {
+                                    lssvm_reduced_loo_info *infos, lssvm_dense_info *dense_out, const double *weights) {
     LSSVM_REQUIRE(betas_out != nullptr && rhos_out != nullptr, "betas_out / rhos_out must not be NULL");
     check_reduced_loo_costs(costs, num_costs);
     std::vector<uint64_t> lm;
     std::vector<double> St, Kmm;
     lssvm_reduced_info info{};
     ReducedOnDevice dev;
-    reduced_gram("fit_reduced_loo", Y, num_rhs, rank, landmarks, slab_rows, lm, St, Kmm, info, &dev);  // pass 1, and every other check that needs no device
+    double Nd = 0.0;  // N, or the sum of the weights
+    reduced_gram("fit_reduced_loo", Y, num_rhs, rank, landmarks, slab_rows, lm, St, Kmm, info, &dev, weights, &Nd);  // pass 1, and every other check that needs no device
 
     const int m = static_cast<int>(rank), k = static_cast<int>(num_rhs), cols = m + 1 + k;
     Problem<T> &p = *shards_[0];
-    const double Nd = static_cast<double>(p.N_);
     const SetOnExit<bool> busy = hold_busy();
     p.activate();
     hipStream_t st = p.stream();
@@ -910,6 +979,7 @@ void Solver<T>::fit_reduced_loo_dev(const void *Y, size_t num_rhs, uint64_t rank
 
     a.inv_n = 1.0 / Nd;
     a.Y = Y;
+    a.w = weights;
     a.h_out = leverage_out;
     a.f_out = fitted_out;
     a.loo_out = loo_out;
@@ -1036,20 +1106,20 @@ void Solver<T>::time_gram_kernels(int repeats, double *parent_ms_out, double *mf
     }
 }
 
-template void Solver<float>::landmark_gram(const void *, size_t, uint64_t, const uint64_t *, uint64_t, double *);
-template void Solver<double>::landmark_gram(const void *, size_t, uint64_t, const uint64_t *, uint64_t, double *);
-template void Solver<float>::fit_reduced(const void *, size_t, uint64_t, const uint64_t *, uint64_t, double *, double *, uint64_t *, lssvm_reduced_info *);
-template void Solver<double>::fit_reduced(const void *, size_t, uint64_t, const uint64_t *, uint64_t, double *, double *, uint64_t *, lssvm_reduced_info *);
+template void Solver<float>::landmark_gram(const void *, size_t, uint64_t, const uint64_t *, uint64_t, double *, const double *);
+template void Solver<double>::landmark_gram(const void *, size_t, uint64_t, const uint64_t *, uint64_t, double *, const double *);
+template void Solver<float>::fit_reduced(const void *, size_t, uint64_t, const uint64_t *, uint64_t, double *, double *, uint64_t *, lssvm_reduced_info *, const double *);
+template void Solver<double>::fit_reduced(const void *, size_t, uint64_t, const uint64_t *, uint64_t, double *, double *, uint64_t *, lssvm_reduced_info *, const double *);
 template void Solver<float>::fit_reduced_loo(const void *, size_t, uint64_t, const uint64_t *, uint64_t, const double *, size_t, double *, double *, double *, double *, double *, double *, uint64_t *,
-                                             uint64_t *, lssvm_reduced_loo_info *);
+                                             uint64_t *, lssvm_reduced_loo_info *, const double *);
 template void Solver<double>::fit_reduced_loo(const void *, size_t, uint64_t, const uint64_t *, uint64_t, const double *, size_t, double *, double *, double *, double *, double *, double *, uint64_t *,
-                                              uint64_t *, lssvm_reduced_loo_info *);
-template void Solver<float>::fit_reduced_dev(const void *, size_t, uint64_t, const uint64_t *, uint64_t, double *, double *, uint64_t *, lssvm_reduced_info *, lssvm_dense_info *);
-template void Solver<double>::fit_reduced_dev(const void *, size_t, uint64_t, const uint64_t *, uint64_t, double *, double *, uint64_t *, lssvm_reduced_info *, lssvm_dense_info *);
+                                              uint64_t *, lssvm_reduced_loo_info *, const double *);
+template void Solver<float>::fit_reduced_dev(const void *, size_t, uint64_t, const uint64_t *, uint64_t, double *, double *, uint64_t *, lssvm_reduced_info *, lssvm_dense_info *, const double *);
+template void Solver<double>::fit_reduced_dev(const void *, size_t, uint64_t, const uint64_t *, uint64_t, double *, double *, uint64_t *, lssvm_reduced_info *, lssvm_dense_info *, const double *);
 template void Solver<float>::fit_reduced_loo_dev(const void *, size_t, uint64_t, const uint64_t *, uint64_t, const double *, size_t, double *, double *, double *, double *, double *, double *, uint64_t *,
-                                                 uint64_t *, lssvm_reduced_loo_info *, lssvm_dense_info *);
+                                                 uint64_t *, lssvm_reduced_loo_info *, lssvm_dense_info *, const double *);
 template void Solver<double>::fit_reduced_loo_dev(const void *, size_t, uint64_t, const uint64_t *, uint64_t, const double *, size_t, double *, double *, double *, double *, double *, double *, uint64_t *,
-                                                  uint64_t *, lssvm_reduced_loo_info *, lssvm_dense_info *);
+                                                  uint64_t *, lssvm_reduced_loo_info *, lssvm_dense_info *, const double *);
 template void Solver<float>::reduced_leverage(uint64_t, const uint64_t *, uint64_t, const double *, const double *, const double *, size_t, double *, double *);
 template void Solver<double>::reduced_leverage(uint64_t, const uint64_t *, uint64_t, const double *, const double *, const double *, size_t, double *, double *);
 template void Solver<float>::time_leverage_kernel(uint64_t, uint64_t, size_t, int, double *, double *);

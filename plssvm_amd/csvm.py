@@ -161,19 +161,21 @@ class CSVM:
             models.append(Model(at_cost, data, alpha=np.asarray(alphas[s]), rho=rhos[s]))
         return models
 
-    def solve_reduced_systems(self, params, A, Y, rank, landmarks=None, factor="host"):
+    def solve_reduced_systems(self, params, A, Y, rank, landmarks=None, factor="host", sample_weight=None):
         """The fixed-size model of every row of ``Y`` over the same landmarks: ``(betas[k, m] float64, rhos[k] float64, landmarks[m], info)``.  Boundary of
         :meth:`fit_reduced`; the MI355X backend implements it."""
         raise NotImplementedError
 
-    def fit_reduced(self, data: DataSet, rank: int, landmarks=None, factor: str = "host") -> Model:
+    def fit_reduced(self, data: DataSet, rank: int, landmarks=None, factor: str = "host", sample_weight=None) -> Model:
         """A fixed-size (reduced) LS-SVM model of ``rank`` support vectors (no counterpart in the reference): the decision function is expanded over
         ``rank`` landmark points only -- the library's fixed choice (the preconditioner's rule), the distinct point indices ``landmarks``, whose number is then the rank, or
         ``"greedy"`` / ``"rpcholesky"`` for ``rank`` points selected from the data (``backend.select_landmarks``; fewer where the kernel matrix's rank is exhausted first) --
         and fitted to ALL points by one pass over the N x rank kernel block and a dense solve, without CG.  The model is an ordinary :class:`Model` whose data set is
         the landmark rows of ``data`` (file format, predict, score); it trades accuracy for size.  A two-class model file groups its support vectors by class, so the
         landmarks must hold points of both classes.  ``last_cg_info`` keeps the ``lssvm_reduced_info`` report with ``iterations`` = 0.  ``factor="device"`` (opt-in;
-        DESIGN.md section 15) runs the dense solve on the device instead of one host thread: not the same bits, and the report gains the ``lssvm_dense_info`` fields."""
+        DESIGN.md section 15) runs the dense solve on the device instead of one host thread: not the same bits, and the report gains the ``lssvm_dense_info`` fields.
+        ``sample_weight``: one weight >= 0 per data point with a positive sum, the weight of the point's squared error; unlike :meth:`fit` nothing
+        is dropped -- a point of weight 0 takes no part in the fit but may still be a landmark.  The landmark rules ignore the weights."""
         _capi.factor_on_device(factor)
         if not data.has_labels():
             raise InvalidParameterError("No labels given for training! Maybe the data is only usable for prediction?")  # csvm.hpp:298
@@ -182,26 +184,30 @@ class CSVM:
             _check_landmark_classes(data, landmarks)  # (before anything is computed)
         params = self.params.resolved(data.num_features())
         t0 = time.perf_counter()
-        betas, rhos, used, info = self.solve_reduced_systems(params, data.data(), data.mapped_labels().reshape(1, -1), rank, landmarks, **_capi.factor_keyword(factor))
+        betas, rhos, used, info = self.solve_reduced_systems(params, data.data(), data.mapped_labels().reshape(1, -1), rank, landmarks, **_capi.factor_keyword(factor),
+                                                              **_weight_keyword(sample_weight))
         info = dict(info, iterations=0, landmarks=np.asarray(used), total_runtime_ms=(time.perf_counter() - t0) * 1e3)
         self.last_cg_info = info
         rows = _check_landmark_classes(data, used)
         reduced = DataSet(data.data()[rows], [labels[i] for i in rows.tolist()], real_type=data.real_type)
         return Model(params, reduced, alpha=np.asarray(betas[0]).astype(data.real_type), rho=rhos[0])
 
-    def solve_reduced_loo_systems(self, params, A, Y, rank, costs, landmarks=None, factor="host"):
+    def solve_reduced_loo_systems(self, params, A, Y, rank, costs, landmarks=None, factor="host", sample_weight=None):
         """The fixed-size models of every row of ``Y`` at every cost of ``costs`` with their leave-one-out report: ``(betas[S, k, m], rhos[S, k], landmarks[m], report)``.
         Boundary of :meth:`fit_reduced_path`; the MI355X backend implements it."""
         raise NotImplementedError
 
-    def fit_reduced_path(self, data: DataSet, rank: int, costs, landmarks=None, factor: str = "host"):
+    def fit_reduced_path(self, data: DataSet, rank: int, costs, landmarks=None, factor: str = "host", sample_weight=None):
         """:meth:`fit_reduced` for every cost of ``costs`` together with exact leave-one-out scores -- leave-one-out with the landmark set held fixed (no counterpart in
         the reference).  Returns ``(models, report)``: one ordinary :class:`Model` per cost, in the order of ``costs``, each with its ``params.cost``
         set and equal to what :meth:`fit_reduced` gives at that cost; this object's own cost is ignored.  ``report`` (float64, over ALL training points, no validation split
         and no refit): ``costs``, ``leverage[S, N]``, ``fitted[S, N]``, ``loo[S, N]`` (the value the model refitted without point i has at point i), ``press[S]``,
         ``loo_errors[S]``, ``loo_accuracy[S]`` = 1 - loo_errors / N, ``max_leverage[S]``, ``jitter[S]``, ``infos``.  ``last_cg_info`` keeps the per-cost reports.
         ``factor="device"`` (opt-in): each cost's factorisation, inverse and solves run on the device; the models then equal what :meth:`fit_reduced`
-        gives with ``factor="device"``."""
+        gives with ``factor="device"``.
+        ``sample_weight``: the weights of :meth:`fit_reduced`; then ``press`` is weighted, ``loo_errors`` counts the points of positive weight and
+        ``loo_accuracy`` is the weighted mean of the correct leave-one-out signs.  A point of weight 0 has leverage 0 and its ``loo`` value is the prediction of a model
+        that never saw it."""
         _capi.factor_on_device(factor)
         if not data.has_labels():
             raise InvalidParameterError("No labels given for training! Maybe the data is only usable for prediction?")  # csvm.hpp:298
@@ -210,13 +216,17 @@ class CSVM:
             _check_landmark_classes(data, landmarks)  # (before anything is computed)
         costs = _checked_costs(costs)
         params = self.params.resolved(data.num_features())
-        betas, rhos, used, report = self.solve_reduced_loo_systems(params, data.data(), data.mapped_labels().reshape(1, -1), rank, costs, landmarks, **_capi.factor_keyword(factor))
+        betas, rhos, used, report = self.solve_reduced_loo_systems(params, data.data(), data.mapped_labels().reshape(1, -1), rank, costs, landmarks, **_capi.factor_keyword(factor),
+                                                                    **_weight_keyword(sample_weight))
         rows = _check_landmark_classes(data, used)
         reduced = DataSet(data.data()[rows], [labels[i] for i in rows.tolist()], real_type=data.real_type)
         models = [Model(replace(params, cost=float(cost)), reduced, alpha=np.asarray(betas[s][0]).astype(data.real_type), rho=rhos[s][0]) for s, cost in enumerate(costs)]
         report = {name: (value[:, 0] if name in ("fitted", "loo", "press", "loo_errors") else value) for name, value in report.items()}
         report["landmarks"] = np.asarray(used)
         report["loo_accuracy"] = 1.0 - report["loo_errors"].astype(np.float64) / data.num_data_points()
+        if sample_weight is not None:
+            correct = np.sign(report["loo"]) == np.sign(np.asarray(data.mapped_labels(), dtype=np.float64))[None, :]
+            report["loo_accuracy"] = np.array([float(np.average(row, weights=np.asarray(sample_weight, dtype=np.float64))) for row in correct])
         self.last_cg_info = [dict(info, iterations=0) for info in report["infos"]]
         return models, report
 
@@ -271,6 +281,12 @@ def _check_landmark_classes(data: DataSet, landmarks) -> np.ndarray:
             raise InvalidParameterError(f'The landmarks hold no point of the class "{data.mapping.label_of(sign)}": a model file groups its support vectors by class, '
                                         "so the landmarks of a two-class model must include both classes!")
     return rows
+
+
+def _weight_keyword(sample_weight) -> dict:
+    """``sample_weight`` as a keyword for the backend boundary of the fixed-size fits -- only where there are weights, so that a backend object written before the
+    keyword existed still serves the unweighted fit."""
+    return {} if sample_weight is None else {"sample_weight": sample_weight}
 
 
 def _drop_zero_weights(data: DataSet, sample_weight):
@@ -380,21 +396,21 @@ class MI355CSVM(CSVM):
                 solved.append((alphas, rhos, infos))
         return solved
 
-    def solve_reduced_systems(self, params, A, Y, rank, landmarks=None, factor="host"):
+    def solve_reduced_systems(self, params, A, Y, rank, landmarks=None, factor="host", sample_weight=None):
         """``backend.fit_reduced`` on device 0: one landmark block, one Gram matrix on the fp64 matrix cores and one factorisation for all rows of ``Y``.  A backend object of
         several devices raises, as the library does on a sharded problem."""
         if self.use_devices != 1:
             raise InvalidParameterError(f"The reduced model is fitted on one device, but this backend object shards a solve over {'every visible device' if self.use_devices == 0 else self.use_devices}"
                                         f"{'' if self.use_devices == 0 else ' devices'} (num_devices={self.use_devices})!")
-        return backend.fit_reduced(params, A, Y, rank, landmarks=landmarks, options=self._options, factor=factor)
+        return backend.fit_reduced(params, A, Y, rank, landmarks=landmarks, options=self._options, factor=factor, sample_weight=sample_weight)
 
-    def solve_reduced_loo_systems(self, params, A, Y, rank, costs, landmarks=None, factor="host"):
+    def solve_reduced_loo_systems(self, params, A, Y, rank, costs, landmarks=None, factor="host", sample_weight=None):
         """``backend.fit_reduced_loo`` on device 0: one landmark block and one Gram matrix for all costs and rows of ``Y``, then one leverage pass per cost on the fp64
         matrix cores.  A backend object of several devices raises, as :meth:`solve_reduced_systems` does."""
         if self.use_devices != 1:
             raise InvalidParameterError(f"The reduced model is fitted on one device, but this backend object shards a solve over {'every visible device' if self.use_devices == 0 else self.use_devices}"
                                         f"{'' if self.use_devices == 0 else ' devices'} (num_devices={self.use_devices})!")
-        return backend.fit_reduced_loo(params, A, Y, rank, costs, landmarks=landmarks, options=self._options, factor=factor)
+        return backend.fit_reduced_loo(params, A, Y, rank, costs, landmarks=landmarks, options=self._options, factor=factor, sample_weight=sample_weight)
 
     def _one_device_path(self) -> None:
         if self.use_devices != 1:

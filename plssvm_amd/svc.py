@@ -317,18 +317,34 @@ def fit_reduced(estimator, X, y, rank, landmarks=None, factor="host"):
         raise InvalidParameterError("estimator must be a plssvm_amd.svc.SVC")
     if estimator.class_weight is not None:
         raise InvalidParameterError("the reduced model is fitted to the unweighted objective: class_weight must be None")
+    return _fit_reduced(estimator, X, y, rank, landmarks, factor, weighted=False)
+
+
+def _reduced_point_weights(estimator, classes, y, sample_weight):
+    """``(class_weight_, the points' weights)`` of the weighted fixed-size fits, computed as :meth:`SVC.fit` computes them: ``sample_weight x class_weight[y]``."""
+    class_weight = estimator._class_weight(classes, y)
+    sw = np.ones(y.size) if sample_weight is None else np.asarray(sample_weight, dtype=np.float64)
+    if sw.shape != y.shape:
+        raise InvalidParameterError(f"The number of data points ({y.size}) and the number of sample weights ({sw.size}) must be the same!")
+    return class_weight, sw * class_weight[np.searchsorted(classes, y)]
+
+
+def _fit_reduced(estimator, X, y, rank, landmarks, factor, weighted, sample_weight=None):
+    """What :func:`fit_reduced` and :func:`fit_reduced_weighted` share."""
     X, y = np.asarray(X), np.asarray(y)
     if X.ndim != 2 or y.ndim != 1 or y.shape[0] != X.shape[0]:
         raise InvalidParameterError(f"X must be a matrix and y a vector of as many labels as X has rows, but their shapes are {X.shape} and {y.shape}!")
     params = estimator._params()
     classes = np.array(sorted(set(y.tolist())))
-    class_weight = np.ones(len(classes))
+    class_weight, weights = _reduced_point_weights(estimator, classes, y, sample_weight) if weighted else (np.ones(len(classes)), None)
+    weight_keyword = _csvm._weight_keyword(weights)
     svm = make_csvm(params=params)
     clone = SVC(**estimator.get_params())
     if len(classes) > 2:
         Xr = np.ascontiguousarray(X, dtype=estimator.real_type)
         resolved = params.resolved(Xr.shape[1])
-        betas, rhos, used, info = svm.solve_reduced_systems(resolved, Xr, _multiclass.one_vs_all_targets(classes, y, Xr.dtype), rank, landmarks, **_capi.factor_keyword(factor))
+        betas, rhos, used, info = svm.solve_reduced_systems(resolved, Xr, _multiclass.one_vs_all_targets(classes, y, Xr.dtype), rank, landmarks, **_capi.factor_keyword(factor),
+                                                            **weight_keyword)
         rows = np.asarray(used).astype(np.int64)
         infos = [dict(info, iterations=0) for _ in classes]
         model = _multiclass.OneVsAllModel(resolved, classes, np.ascontiguousarray(Xr[rows]), np.asarray(betas).astype(Xr.dtype), np.asarray(rhos).astype(Xr.dtype), infos)
@@ -341,10 +357,21 @@ def fit_reduced(estimator, X, y, rank, landmarks=None, factor="host"):
         }
         return clone
     data = DataSet(X, y.tolist(), real_type=estimator.real_type)
-    model = svm.fit_reduced(data, rank, landmarks, **_capi.factor_keyword(factor))
+    model = svm.fit_reduced(data, rank, landmarks, **_capi.factor_keyword(factor), **weight_keyword)
     clone._set_binary_fit(svm, model, model.data, X, y, class_weight, None, 0)
     clone._fit["support_"] = _landmarks_of(svm, landmarks)
     return clone
+
+
+def fit_reduced_weighted(estimator, X, y, rank, sample_weight=None, landmarks=None, factor="host"):
+    """:func:`fit_reduced` for the weighted objective ``1/2 beta^T K_mm beta + C/2 sum_i w_i (y_i - f(x_i))^2``.  ``estimator.class_weight`` is
+    honoured exactly as :meth:`SVC.fit` honours it: ``w_i = sample_weight[i] x class_weight[y[i]]`` (``sample_weight`` None: ones), and ``class_weight_`` of the clone
+    holds the multipliers.  One-vs-all uses the same weights for every classifier, so one Gram matrix and one factorisation still serve all classes.  A point of weight 0
+    takes no part in the fit (it may still be a landmark); the weights must have a positive sum.  The landmark rules ignore the weights."""
+    _capi.factor_on_device(factor)
+    if not isinstance(estimator, SVC):
+        raise InvalidParameterError("estimator must be a plssvm_amd.svc.SVC")
+    return _fit_reduced(estimator, X, y, rank, landmarks, factor, weighted=True, sample_weight=sample_weight)
 
 
 def _landmarks_of(svm, landmarks):
@@ -364,21 +391,28 @@ def fit_reduced_cv(estimator, X, y, rank, Cs, landmarks=None, factor="host"):
         raise InvalidParameterError("estimator must be a plssvm_amd.svc.SVC")
     if estimator.class_weight is not None:
         raise InvalidParameterError("the reduced model is fitted to the unweighted objective: class_weight must be None")
+    return _fit_reduced_cv(estimator, X, y, rank, Cs, landmarks, factor, weighted=False)
+
+
+def _fit_reduced_cv(estimator, X, y, rank, Cs, landmarks, factor, weighted, sample_weight=None):
+    """What :func:`fit_reduced_cv` and :func:`fit_reduced_cv_weighted` share."""
     X, y = np.asarray(X), np.asarray(y)
     if X.ndim != 2 or y.ndim != 1 or y.shape[0] != X.shape[0]:
         raise InvalidParameterError(f"X must be a matrix and y a vector of as many labels as X has rows, but their shapes are {X.shape} and {y.shape}!")
     Cs = _csvm._checked_costs(Cs)
     params = estimator._params()
     classes = np.array(sorted(set(y.tolist())))
-    class_weight = np.ones(len(classes))
+    class_weight, weights = _reduced_point_weights(estimator, classes, y, sample_weight) if weighted else (np.ones(len(classes)), None)
+    weight_keyword = _csvm._weight_keyword(weights)
     svm = make_csvm(params=params)
     clones = [SVC(**{**estimator.get_params(), "C": C}) for C in Cs]
     if len(classes) > 2:
         Xr = np.ascontiguousarray(X, dtype=estimator.real_type)
         resolved = params.resolved(Xr.shape[1])
-        betas, rhos, used, report = svm.solve_reduced_loo_systems(resolved, Xr, _multiclass.one_vs_all_targets(classes, y, Xr.dtype), rank, Cs, landmarks, **_capi.factor_keyword(factor))
+        betas, rhos, used, report = svm.solve_reduced_loo_systems(resolved, Xr, _multiclass.one_vs_all_targets(classes, y, Xr.dtype), rank, Cs, landmarks, **_capi.factor_keyword(factor),
+                                                                  **weight_keyword)
         rows = np.asarray(used).astype(np.int64)
-        scores = np.array([float(np.mean(classes[np.argmax(report["loo"][s], axis=0)] == y)) for s in range(len(Cs))])
+        scores = np.array([float(np.average(classes[np.argmax(report["loo"][s], axis=0)] == y, weights=weights)) for s in range(len(Cs))])
         for s, (C, clone) in enumerate(zip(Cs, clones)):
             at_cost = Parameter(kernel_type=resolved.kernel_type, degree=resolved.degree, gamma=resolved.gamma, coef0=resolved.coef0, cost=C)
             infos = [dict(report["infos"][s], iterations=0) for _ in classes]
@@ -392,11 +426,21 @@ def fit_reduced_cv(estimator, X, y, rank, Cs, landmarks=None, factor="host"):
             }
         return scores, clones
     data = DataSet(X, y.tolist(), real_type=estimator.real_type)
-    models, report = svm.fit_reduced_path(data, rank, Cs, landmarks, **_capi.factor_keyword(factor))
+    models, report = svm.fit_reduced_path(data, rank, Cs, landmarks, **_capi.factor_keyword(factor), **weight_keyword)
     for clone, model in zip(clones, models):
         clone._set_binary_fit(svm, model, model.data, X, y, class_weight, None, 0)
         clone._fit["support_"] = np.asarray(report["landmarks"]).astype(np.int32)
     return np.asarray(report["loo_accuracy"], dtype=np.float64), clones
+
+
+def fit_reduced_cv_weighted(estimator, X, y, rank, Cs, sample_weight=None, landmarks=None, factor="host"):
+    """:func:`fit_reduced_cv` under the weighting the model will be used with: the weights are those of :func:`fit_reduced_weighted`
+    (``sample_weight x class_weight[y]``), the clones are what it gives at each ``C`` and carry ``class_weight_``, and the score is the WEIGHTED leave-one-out accuracy
+    ``np.average(correct, weights=w)``.  A point of weight 0 does not count in the score; its leave-one-out value is the prediction of a model that never saw it."""
+    _capi.factor_on_device(factor)
+    if not isinstance(estimator, SVC):
+        raise InvalidParameterError("estimator must be a plssvm_amd.svc.SVC")
+    return _fit_reduced_cv(estimator, X, y, rank, Cs, landmarks, factor, weighted=True, sample_weight=sample_weight)
 
 
 def cost_path_scores(estimator, X, y, Cs, X_val, y_val):
