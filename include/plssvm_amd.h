@@ -653,6 +653,57 @@ int lssvm_mi355_fit_reduced_loo_weighted_f64(const lssvm_params *params, const d
                                              double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out,
                                              uint64_t *landmarks_out, lssvm_reduced_loo_info *infos, lssvm_dense_info *dense, const lssvm_mi355_options *options);
 
+/* The leave-one-out scores above over a grid of kernel widths AND costs in one call on one resident problem (opt-in), for rbf and polynomial
+ * problems.  Cell (g, s) is lssvm_mi355_problem_fit_reduced_loo_weighted at the cost C_s on the SAME held data with the kernel's gamma replaced by gamma_g.  What the
+ * kernel value of a (point, landmark) pair is made from -- D = sum_f (a_f - b_f)^2 (rbf) or sum_f a_f b_f (polynomial) over the held features -- does not depend on gamma:
+ * per slab and pass D is formed ONCE into a work space of slab_rows x rank doubles, and per gamma one elementwise kernel writes Phi = k(gamma'_g, D) from it, with
+ * gamma'_g = (gamma_g rounded to the problem's dtype) / x_scale^2, the rule every landmark block follows.  The Gram pass then adds into that gamma's own St, and the dense
+ * steps and the leverage kernel per (gamma, cost) are those of the calls above (`factor`: 0 host, 1 device).
+ * product: 0 ("ordered") forms D with the loop of the calls above -- with one gamma equal to the problem's own, every output has the BITS of
+ * lssvm_mi355_problem_fit_reduced_loo_weighted with the same `factor`.  1 ("matrix") forms the dot products x_i . x_l on v_mfma_f64_16x16x4_f64 (both operands staged
+ * through LDS and converted to double on the way; the contraction runs over the held features in steps of 16) and, for rbf, D = n_i + n_l - 2 x_i . x_l with the rows'
+ * squared norms n (double, summed ascending, once per call), clamped at 0 and exactly 0 where i is the landmark itself (K_mm's diagonal is exactly 1).  Not the ordered
+ * path's bits: |dD| <= (ldx + 4) eps64 (n_i + n_l + 2 sum_f |a_f b_f|) for rbf -- the expansion cancels where a point is close to a landmark relative to their norms;
+ * centred data (what an rbf problem off the direct form holds) keeps the norms small -- and (ldx + 2) eps64 sum_f |a_f b_f| for the dot products.
+ * The cost AND the gamma of the problem's lssvm_params are ignored by the fit, but its gamma still decides how the problem holds its data (x_scale, the direct form;
+ * DESIGN.md section 12): create the problem with a gamma from the grid.  Landmarks are the caller's, or the library's fixed rule; none of them depends on gamma.
+ * gammas: each finite and > 0.  num_gammas x num_costs <= 64: the operands of all cells stay on the device during pass 2 (0.5 GB at rank 1 024, the bound of the cost
+ * grid above), and beside them the St tiles and K_mm of every gamma from pass 1 until that gamma's cells are factored (about 14 MB per gamma at rank 1 024: up to 0.9 GB
+ * more at 64 gammas).  Every output of the leave-one-out call gains a
+ * leading gamma dimension: betas_out num_gammas x num_costs x num_rhs x rank; rhos_out, press_out, loo_errors_out num_gammas x num_costs x num_rhs; leverage_out
+ * num_gammas x num_costs x N; fitted_out, loo_out num_gammas x num_costs x num_rhs x N; infos and dense (may be NULL; ignored for factor 0) num_gammas x num_costs.
+ * weights may be NULL.  Deterministic, no atomics: the same bits for the same arguments; a gamma of a grid has the bits of the call with that gamma alone, a cost the bits
+ * of the call with that cost alone, column c the bits of the call with that right-hand side alone.  The problem is left as it was and keeps its preconditioner.
+ * LSSVM_ERR_INVALID_ARGUMENT, all before a device is touched: the refusals of lssvm_mi355_problem_fit_reduced_loo_weighted; num_gammas == 0 or a NULL gammas; a gamma that
+ * is not finite and > 0; num_gammas x num_costs > 64; a product other than 0 or 1; a problem with the linear kernel (it has no gamma to vary). */
+typedef struct lssvm_reduced_grid_info {
+    double cost;
+    double jitter;         /* nu of this cell */
+    double max_leverage;   /* the largest h_ii of this cell */
+    double landmark_ms;    /* accumulate_ms + values_ms: the device time of this gamma's Phi, both passes */
+    double gram_ms;        /* device time of this gamma's K_mm and St, all slabs (the same figure for every cost) */
+    double leverage_ms;    /* device time of this cell's leverage kernel, all slabs */
+    double host_ms;        /* this cell's dense steps on the host (factor 1: what is left on the host) */
+    double gamma;
+    double accumulate_ms;  /* device time of D, both passes, all slabs (and of the norms): the same figure in every record */
+    double values_ms;      /* device time of the kernel values of this gamma, both passes, all slabs (the same figure for every cost) */
+} lssvm_reduced_grid_info;
+int lssvm_mi355_problem_fit_reduced_grid(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, const double *weights /* N, or NULL */, uint64_t rank, const uint64_t *landmarks,
+                                         uint64_t slab_rows, const double *gammas, size_t num_gammas, const double *costs, size_t num_costs, int factor, int product,
+                                         double *betas_out, double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out, double *press_out,
+                                         uint64_t *loo_errors_out, uint64_t *landmarks_out, lssvm_reduced_grid_info *infos, lssvm_dense_info *dense);
+/* one-shot: create the problem on device 0 from `params` (as lssvm_mi355_solve_*), fit, destroy it */
+int lssvm_mi355_fit_reduced_grid_f32(const lssvm_params *params, const float *X, size_t num_points, size_t num_features, const float *Y, size_t num_rhs, const double *weights,
+                                     uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *gammas, size_t num_gammas, const double *costs, size_t num_costs,
+                                     int factor, int product, double *betas_out, double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out, double *press_out,
+                                     uint64_t *loo_errors_out, uint64_t *landmarks_out, lssvm_reduced_grid_info *infos, lssvm_dense_info *dense,
+                                     const lssvm_mi355_options *options);
+int lssvm_mi355_fit_reduced_grid_f64(const lssvm_params *params, const double *X, size_t num_points, size_t num_features, const double *Y, size_t num_rhs, const double *weights,
+                                     uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *gammas, size_t num_gammas, const double *costs, size_t num_costs,
+                                     int factor, int product, double *betas_out, double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out, double *press_out,
+                                     uint64_t *loo_errors_out, uint64_t *landmarks_out, lssvm_reduced_grid_info *infos, lssvm_dense_info *dense,
+                                     const lssvm_mi355_options *options);
+
 /* Landmark selection on a resident problem (opt-in): the pivots of a partial Cholesky factorisation of the kernel matrix, chosen greedily or
  * at random in proportion to the residual diagonal (randomly pivoted Cholesky).  The result is a list of point indices for the `landmarks` argument of the entry points
  * above; nothing else changes, and nothing selects it automatically.  Neither rule dominates the other or the fixed shuffle (README.md has the rows of all three kinds).

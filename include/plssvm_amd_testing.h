@@ -65,6 +65,12 @@ int lssvm_mi355_problem_landmark_gram_weighted(lssvm_mi355_problem *p, const voi
 int lssvm_mi355_problem_reduced_leverage(lssvm_mi355_problem *p, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *V, const double *shift,
                                          const double *B_extra, size_t k, double *h_out, double *f_out);
 
+/* The operator of the (gamma, cost) grid alone (lssvm_mi355_problem_fit_reduced_grid), apart from any fit: D_out[l * N + i] = what the kernel value
+ * of (point i, landmark l) is made from on the data as the problem holds it -- sum_f (a_f - b_f)^2 (rbf) or sum_f a_f b_f (polynomial, linear) -- for all N points, rank x N
+ * doubles, in slabs of the library's default size.  product: 0 = the ordered loop of the landmark block, 1 = the dot products on the matrix cores (and the norm expansion
+ * for rbf).  landmarks: `rank` distinct indices < N, or NULL for the library's rule.  Refusals as for lssvm_mi355_problem_landmark_gram, and a product other than 0 or 1. */
+int lssvm_mi355_problem_landmark_acc(lssvm_mi355_problem *p, const uint64_t *landmarks, uint64_t rank, int product, double *D_out);
+
 /* Measurement aid of tests/tools/reduced_loo_timing.py: on ONE slab of this problem (its first min(N, slab_rows) points, `rank` landmarks by the library's rule, an
  * identity V, k columns of ones) the Gram kernels of the fixed-size fit (gram_ms_out[r]: partial tiles and their sum over rank + 1 + k columns) and the leverage kernel
  * (leverage_ms_out[r]), device time of repeat r each after one untimed run of both. */

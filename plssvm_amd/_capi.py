@@ -49,6 +49,7 @@ EXPORTED_SYMBOLS = [
     "lssvm_mi355_problem_fit_reduced_weighted", "lssvm_mi355_fit_reduced_weighted_f32", "lssvm_mi355_fit_reduced_weighted_f64",
     "lssvm_mi355_problem_fit_reduced_loo_weighted", "lssvm_mi355_fit_reduced_loo_weighted_f32", "lssvm_mi355_fit_reduced_loo_weighted_f64",
     "lssvm_mi355_problem_landmark_gram_weighted",
+    "lssvm_mi355_problem_fit_reduced_grid", "lssvm_mi355_fit_reduced_grid_f32", "lssvm_mi355_fit_reduced_grid_f64", "lssvm_mi355_problem_landmark_acc",
     "lssvm_mi355_dense_cholesky", "lssvm_mi355_dense_solve", "lssvm_mi355_dense_invert_lower",
     "lssvm_mi355_problem_select_landmarks", "lssvm_mi355_select_landmarks_f32", "lssvm_mi355_select_landmarks_f64",
     "lssvm_mi355_cg_begin", "lssvm_mi355_cg_step", "lssvm_mi355_cg_finish", "lssvm_mi355_problem_synchronize", "lssvm_mi355_problem_info",
@@ -376,6 +377,46 @@ def reduced_weighted_entry(name: str):
             fn.argtypes = [C.c_void_p] + common
         else:
             fn.argtypes = [C.POINTER(LssvmParams), C.c_void_p, C.c_size_t, C.c_size_t] + common + [C.c_void_p]
+        fn.restype = C.c_int
+    return fn
+
+
+class LssvmReducedGridInfo(C.Structure):
+    """``lssvm_reduced_grid_info``: one (gamma, cost) cell of ``lssvm_mi355_problem_fit_reduced_grid``."""
+    _fields_ = [("cost", C.c_double), ("jitter", C.c_double), ("max_leverage", C.c_double), ("landmark_ms", C.c_double), ("gram_ms", C.c_double), ("leverage_ms", C.c_double),
+                ("host_ms", C.c_double), ("gamma", C.c_double), ("accumulate_ms", C.c_double), ("values_ms", C.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+REDUCED_GRID_MAX_CELLS = 64
+PRODUCT_CHOICES = ("ordered", "matrix")  # the `product` argument of the grid: 0, 1
+
+
+def product_argument(product) -> int:
+    """The ``product=`` keyword of the (gamma, cost) grid: ``"ordered"`` or ``"matrix"`` (the default); anything else is refused before any library call."""
+    if not isinstance(product, str) or product not in PRODUCT_CHOICES:
+        raise InvalidParameterError(f'product must be "ordered" or "matrix", but is {product!r}!')
+    return PRODUCT_CHOICES.index(product)
+
+
+def reduced_grid_entry(name: str):
+    """The entry points of the (gamma, cost) grid of the fixed-size model (``lssvm_mi355_problem_fit_reduced_grid``, ``lssvm_mi355_fit_reduced_grid_f32 / _f64`` and the
+    test aid ``lssvm_mi355_problem_landmark_acc``) with their argument types.  Bound at the first call."""
+    fn = getattr(lib, name)
+    if fn.argtypes is None:
+        dp, up = C.POINTER(C.c_double), C.POINTER(C.c_uint64)
+        if name == "lssvm_mi355_problem_landmark_acc":
+            fn.argtypes = [C.c_void_p, up, C.c_uint64, C.c_int, dp]
+        else:
+            # Y, num_rhs, weights, rank, landmarks, slab_rows, gammas, num_gammas, costs, num_costs, factor, product, then the outputs of the leave-one-out call
+            common = [C.c_void_p, C.c_size_t, dp, C.c_uint64, up, C.c_uint64, dp, C.c_size_t, dp, C.c_size_t, C.c_int, C.c_int,
+                      dp, dp, dp, dp, dp, dp, up, up, C.POINTER(LssvmReducedGridInfo), C.POINTER(LssvmDenseInfo)]
+            if "problem" in name:
+                fn.argtypes = [C.c_void_p] + common
+            else:
+                fn.argtypes = [C.POINTER(LssvmParams), C.c_void_p, C.c_size_t, C.c_size_t] + common + [C.c_void_p]
         fn.restype = C.c_int
     return fn
 

@@ -24,7 +24,7 @@ from ._capi import LssvmCgInfo, LssvmParams, LssvmPredictInfo, LssvmShard, Optio
 from .exceptions import InvalidParameterError
 from .parameter import Parameter
 
-__all__ = ["Options", "Predictor", "solve_system_of_linear_equations", "solve_refined", "solve_cost_path", "solve_pcg", "fit_reduced", "fit_reduced_loo", "select_landmarks", "predict_values", "predict_values_multi", "generate_q", "run_device_kernel", "calculate_w", "ResidentProblem",
+__all__ = ["Options", "Predictor", "solve_system_of_linear_equations", "solve_refined", "solve_cost_path", "solve_pcg", "fit_reduced", "fit_reduced_loo", "fit_reduced_grid", "select_landmarks", "predict_values", "predict_values_multi", "generate_q", "run_device_kernel", "calculate_w", "ResidentProblem",
            "comm_get_unique_id", "comm_init", "comm_destroy"]
 
 
@@ -453,6 +453,72 @@ def fit_reduced_loo(params: Parameter, A, Y, rank: int, costs, landmarks=None, s
     return _reduced_loo_call(fn, (C.byref(ps), ptr(A), N, d), Y2, single, N, rank, lm_ptr, slab_rows, costs, tail=(options_ptr(options),), on_device=on_device, weights=w)
 
 
+def _reduced_grid_gammas(gammas, num_costs: int):
+    """The gammas of the (gamma, cost) grid, checked as the library checks them."""
+    try:
+        gammas = np.ascontiguousarray(gammas, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise InvalidParameterError("The gammas must be a list of numbers!") from None
+    if gammas.ndim != 1 or gammas.size < 1:
+        raise InvalidParameterError(f"The grid takes at least 1 gamma, but got {gammas.size if gammas.ndim == 1 else gammas.shape}!")
+    if not (np.all(np.isfinite(gammas)) and np.all(gammas > 0.0)):
+        raise InvalidParameterError("Every gamma must be finite and greater than 0!")
+    if gammas.size * num_costs > _capi.REDUCED_GRID_MAX_CELLS:
+        raise InvalidParameterError(f"The grid takes at most {_capi.REDUCED_GRID_MAX_CELLS} (gamma, cost) cells, but got {gammas.size} x {num_costs}!")
+    return gammas
+
+
+def _reduced_grid_kernel(params: Parameter):
+    """The grid's refusal of a kernel function without a gamma, as the library words it."""
+    if int(params.kernel_type) == 0:
+        raise InvalidParameterError("The linear kernel has no gamma to vary: the (gamma, cost) grid takes an rbf or a polynomial problem!")
+
+
+def _reduced_grid_call(fn, head, Y2, single: bool, N: int, rank: int, lm_ptr, slab_rows: int, gammas, costs, on_device: bool, product: int, weights, tail=()):
+    k, G, S = Y2.shape[0], gammas.size, costs.size
+    betas, rhos = np.zeros((G, S, k, rank)), np.zeros((G, S, k))
+    leverage, fitted, loo = np.zeros((G, S, N)), np.zeros((G, S, k, N)), np.zeros((G, S, k, N))
+    press, errors, used = np.zeros((G, S, k)), np.zeros((G, S, k), dtype=np.uint64), np.zeros(rank, dtype=np.uint64)
+    infos = (_capi.LssvmReducedGridInfo * (G * S))()
+    dense = (_capi.LssvmDenseInfo * (G * S))()
+    dp, up = C.POINTER(C.c_double), C.POINTER(C.c_uint64)
+    check(fn(*head, ptr(Y2), k, _capi.weights_ptr(weights), rank, lm_ptr, slab_rows, gammas.ctypes.data_as(dp), G, costs.ctypes.data_as(dp), S, int(on_device), product,
+             betas.ctypes.data_as(dp), rhos.ctypes.data_as(dp), leverage.ctypes.data_as(dp), fitted.ctypes.data_as(dp), loo.ctypes.data_as(dp), press.ctypes.data_as(dp),
+             errors.ctypes.data_as(up), used.ctypes.data_as(up), infos, dense, *tail))
+    cells = [[dict(dense[g * S + s].as_dict(), **infos[g * S + s].as_dict()) if on_device else infos[g * S + s].as_dict() for s in range(S)] for g in range(G)]
+    report = {"gammas": gammas.copy(), "costs": costs.copy(), "leverage": leverage, "fitted": fitted[:, :, 0] if single else fitted, "loo": loo[:, :, 0] if single else loo,
+              "press": press[:, :, 0] if single else press, "loo_errors": errors[:, :, 0] if single else errors,
+              "max_leverage": np.array([[c["max_leverage"] for c in row] for row in cells]), "jitter": np.array([[c["jitter"] for c in row] for row in cells]), "infos": cells}
+    return (betas[:, :, 0], rhos[:, :, 0], used, report) if single else (betas, rhos, used, report)
+
+
+def fit_reduced_grid(params: Parameter, A, Y, rank: int, gammas, costs, landmarks=None, slab_rows: int = 0, options: Options | None = None, factor: str = "host",
+                     sample_weight=None, product: str = "matrix"):
+    """:func:`fit_reduced_loo` at every kernel width of ``gammas`` AND every cost of ``costs`` in one call on one resident problem (``lssvm_mi355_fit_reduced_grid_*``;
+    DESIGN.md section 17), for rbf and polynomial kernels.  The sums over the features behind every kernel value do not depend on gamma: they are formed once per slab
+    and pass and shared by all gammas.  ``params.cost`` and ``params.gamma`` are ignored by the fit, but ``params.gamma`` still decides how the problem holds its data:
+    pass a gamma from the grid.  ``gammas.size * costs.size <= 64``.  ``product="matrix"`` (the default) forms the dot products on the fp64 matrix cores (rbf: through the
+    norm expansion ``n_i + n_l - 2 x_i . x_l``); ``product="ordered"`` runs the loop of :func:`fit_reduced_loo` -- with the one gamma of ``params`` it returns that
+    call's bits.  Returns ``(betas[G, S, k, rank], rhos[G, S, k], landmarks, report)`` (the ``k`` axis dropped for a single right-hand side); ``report`` as for
+    :func:`fit_reduced_loo` with a leading gamma axis on every array, ``gammas``, and ``infos[g][s]`` (``lssvm_reduced_grid_info`` dicts).  ``factor`` and
+    ``sample_weight``: as for :func:`fit_reduced_loo`."""
+    on_device = _capi.factor_on_device(factor)
+    code = _capi.product_argument(product)
+    A = _as_matrix(A)
+    N, d = A.shape
+    w = _reduced_weights(sample_weight, N)
+    if isinstance(landmarks, str):  # a selection rule (:func:`select_landmarks`): one resident problem selects and fits
+        with ResidentProblem(params, A, options=options) as prob:
+            return prob.fit_reduced_grid(Y, rank, gammas, costs, landmarks, sample_weight=w, factor=factor, product=product, slab_rows=slab_rows)
+    Y2, single, rank, _, lm_ptr, slab_rows = _reduced_arguments(Y, N, A.dtype, rank, landmarks, slab_rows)
+    costs = _reduced_loo_costs(costs)
+    gammas = _reduced_grid_gammas(gammas, costs.size)
+    _reduced_grid_kernel(params)
+    ps = _params_struct(params, d)
+    fn = _capi.reduced_grid_entry(f"lssvm_mi355_fit_reduced_grid_{suffix_of(A.dtype)}")
+    return _reduced_grid_call(fn, (C.byref(ps), ptr(A), N, d), Y2, single, N, rank, lm_ptr, slab_rows, gammas, costs, on_device, code, w, tail=(options_ptr(options),))
+
+
 def generate_q(params: Parameter, data, options: Options | None = None):
     data = _as_matrix(data)
     N, d = data.shape
@@ -866,6 +932,30 @@ class ResidentProblem:
         costs = _reduced_loo_costs(costs)
         return _reduced_loo_call(_reduced_entry("problem_fit_reduced_loo", on_device, weighted=w is not None), (self._h,), Y2, single, self.num_points, rank, lm_ptr, slab_rows, costs,
                                  on_device=on_device, weights=w)
+
+    def fit_reduced_grid(self, Y, rank: int, gammas, costs, landmarks=None, sample_weight=None, factor: str = "host", product: str = "matrix", slab_rows: int = 0):
+        """:func:`fit_reduced_grid` on this resident problem (``lssvm_mi355_problem_fit_reduced_grid``): leave-one-out with the landmark set held fixed at every
+        ``(gamma, cost)`` of the grid, the feature sums behind Phi formed once per slab and pass.  The problem's own cost and gamma are ignored by the fit (its gamma
+        decided how it holds its data when it was created); ``landmarks="greedy"`` / ``"rpcholesky"`` select with the problem's own gamma.  The problem is left as it
+        was and keeps its preconditioner.  Refused where :meth:`fit_reduced` is, and on a linear-kernel problem."""
+        on_device = _capi.factor_on_device(factor)
+        code = _capi.product_argument(product)
+        _reduced_grid_kernel(self.params)
+        w = _reduced_weights(sample_weight, self.num_points)
+        costs = _reduced_loo_costs(costs)
+        gammas = _reduced_grid_gammas(gammas, costs.size)
+        Y2, single, rank, _, lm_ptr, slab_rows = _reduced_arguments(Y, self.num_points, self.dtype, rank, self._selected(rank, landmarks), slab_rows)
+        return _reduced_grid_call(_capi.reduced_grid_entry("lssvm_mi355_problem_fit_reduced_grid"), (self._h,), Y2, single, self.num_points, rank, lm_ptr, slab_rows, gammas, costs,
+                                  on_device, code, w)
+
+    def landmark_acc(self, rank: int, landmarks=None, product: str = "matrix"):
+        """The operator of :meth:`fit_reduced_grid` alone (a test aid, ``lssvm_mi355_problem_landmark_acc``): ``D[l, i]`` = the sum over the held features of
+        ``(a_f - b_f)^2`` (rbf) or ``a_f b_f`` (polynomial, linear) for landmark ``l`` and point ``i``, ``(rank, num_points)`` float64."""
+        code = _capi.product_argument(product)
+        _, _, rank, _, lm_ptr, _ = _reduced_arguments(np.zeros(self.num_points, dtype=self.dtype), self.num_points, self.dtype, rank, landmarks, 0)
+        out = np.zeros((rank, self.num_points), dtype=np.float64)
+        check(_capi.reduced_grid_entry("lssvm_mi355_problem_landmark_acc")(self._h, lm_ptr, rank, code, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
 
     def reduced_leverage(self, V, shift, B_extra=None, landmarks=None, slab_rows: int = 0):
         """The operator of :meth:`fit_reduced_loo` alone on the caller's operands (a test aid, ``lssvm_mi355_problem_reduced_leverage``): with ``phic_i = phi_i - shift``,

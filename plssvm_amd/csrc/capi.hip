@@ -262,6 +262,27 @@ void fit_reduced_loo_one_shot(const lssvm_params *params, const T *X, size_t N, 
     }
 }
 
+/* lssvm_mi355_fit_reduced_grid_*: likewise; the problem is created with the gamma of `params` (it decides how the data is held, not the fit) */
+template <typename T>
+void fit_reduced_grid_one_shot(const lssvm_params *params, const T *X, size_t N, size_t d, const T *Y, size_t num_rhs, const double *weights, uint64_t rank, const uint64_t *landmarks,
+                               uint64_t slab_rows, const double *gammas, size_t num_gammas, const double *costs, size_t num_costs, int factor, int product, double *betas_out,
+                               double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out,
+                               lssvm_reduced_grid_info *infos, lssvm_dense_info *dense, const lssvm_mi355_options *options) {
+    lssvm::check_reduced_factor(factor);
+    lssvm::check_params(params);
+    check_data(X, N, d);
+    lssvm::check_reduced_arguments(Y, num_rhs, rank, slab_rows, N);
+    lssvm::check_reduced_loo_costs(costs, num_costs);
+    lssvm::check_reduced_grid_arguments(gammas, num_gammas, num_costs, product);
+    lssvm::check_reduced_grid_kernel(params->kernel_type);
+    LSSVM_REQUIRE(betas_out != nullptr && rhos_out != nullptr, "betas_out / rhos_out must not be NULL");
+    if (landmarks != nullptr) (void) lssvm::resolve_landmarks(landmarks, static_cast<size_t>(rank), N);
+    if (weights != nullptr) (void) lssvm::check_reduced_weights(weights, N);
+    lssvm::Solver<T> prob = device0_solver<T>(options, *params, X, N, d);
+    prob.fit_reduced_grid(Y, num_rhs, weights, rank, landmarks, slab_rows, gammas, num_gammas, costs, num_costs, factor, product, betas_out, rhos_out, leverage_out, fitted_out, loo_out,
+                          press_out, loo_errors_out, landmarks_out, infos, dense);
+}
+
 /* lssvm_mi355_select_landmarks_*: likewise */
 template <typename T>
 void select_landmarks_one_shot(const lssvm_params *params, const T *X, size_t N, size_t d, uint64_t rank, int method, uint64_t pool, uint64_t seed, double tol, uint64_t *landmarks_out,
@@ -904,6 +925,50 @@ int lssvm_mi355_fit_reduced_loo_weighted_f64(const lssvm_params *params, const d
         lssvm::check_reduced_factor(factor);
         fit_reduced_loo_one_shot<double>(params, X, num_points, num_features, Y, num_rhs, rank, landmarks, slab_rows, costs, num_costs, betas_out, rhos_out, leverage_out, fitted_out, loo_out,
                                          press_out, loo_errors_out, landmarks_out, infos, options, factor == 1, dense, weights);
+    });
+}
+/* the (gamma, cost) grid: the checks of the weighted leave-one-out form in their order, then the grid's own */
+static_assert(sizeof(lssvm_reduced_grid_info) == 80, "lssvm_reduced_grid_info changed: plssvm_amd/_capi.py (LssvmReducedGridInfo) changes with it");
+int lssvm_mi355_problem_fit_reduced_grid(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, const double *weights, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows,
+                                         const double *gammas, size_t num_gammas, const double *costs, size_t num_costs, int factor, int product, double *betas_out, double *rhos_out,
+                                         double *leverage_out, double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out,
+                                         lssvm_reduced_grid_info *infos, lssvm_dense_info *dense) {
+    return guarded([&] {
+        LSSVM_REQUIRE(p != nullptr, "problem handle must not be NULL");
+        lssvm::check_reduced_arguments(Y, num_rhs, rank, slab_rows, 0);
+        lssvm::check_reduced_loo_costs(costs, num_costs);
+        LSSVM_REQUIRE(betas_out != nullptr && rhos_out != nullptr, "betas_out / rhos_out must not be NULL");
+        lssvm::check_reduced_factor(factor);
+        lssvm::check_reduced_grid_arguments(gammas, num_gammas, num_costs, product);
+        impl_of(p)->fit_reduced_grid(Y, num_rhs, weights, rank, landmarks, slab_rows, gammas, num_gammas, costs, num_costs, factor, product, betas_out, rhos_out, leverage_out, fitted_out,
+                                     loo_out, press_out, loo_errors_out, landmarks_out, infos, dense);
+    });
+}
+int lssvm_mi355_fit_reduced_grid_f32(const lssvm_params *params, const float *X, size_t num_points, size_t num_features, const float *Y, size_t num_rhs, const double *weights, uint64_t rank,
+                                     const uint64_t *landmarks, uint64_t slab_rows, const double *gammas, size_t num_gammas, const double *costs, size_t num_costs, int factor, int product,
+                                     double *betas_out, double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out,
+                                     uint64_t *landmarks_out, lssvm_reduced_grid_info *infos, lssvm_dense_info *dense, const lssvm_mi355_options *options) {
+    return guarded([&] {
+        fit_reduced_grid_one_shot<float>(params, X, num_points, num_features, Y, num_rhs, weights, rank, landmarks, slab_rows, gammas, num_gammas, costs, num_costs, factor, product, betas_out,
+                                         rhos_out, leverage_out, fitted_out, loo_out, press_out, loo_errors_out, landmarks_out, infos, dense, options);
+    });
+}
+int lssvm_mi355_fit_reduced_grid_f64(const lssvm_params *params, const double *X, size_t num_points, size_t num_features, const double *Y, size_t num_rhs, const double *weights, uint64_t rank,
+                                     const uint64_t *landmarks, uint64_t slab_rows, const double *gammas, size_t num_gammas, const double *costs, size_t num_costs, int factor, int product,
+                                     double *betas_out, double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out,
+                                     uint64_t *landmarks_out, lssvm_reduced_grid_info *infos, lssvm_dense_info *dense, const lssvm_mi355_options *options) {
+    return guarded([&] {
+        fit_reduced_grid_one_shot<double>(params, X, num_points, num_features, Y, num_rhs, weights, rank, landmarks, slab_rows, gammas, num_gammas, costs, num_costs, factor, product, betas_out,
+                                          rhos_out, leverage_out, fitted_out, loo_out, press_out, loo_errors_out, landmarks_out, infos, dense, options);
+    });
+}
+int lssvm_mi355_problem_landmark_acc(lssvm_mi355_problem *p, const uint64_t *landmarks, uint64_t rank, int product, double *D_out) {
+    return guarded([&] {
+        LSSVM_REQUIRE(p != nullptr, "problem handle must not be NULL");
+        LSSVM_REQUIRE(D_out != nullptr, "D_out must not be NULL");
+        lssvm::check_reduced_arguments(D_out, 1, rank, 0, 0);
+        LSSVM_REQUIRE(product == 0 || product == 1, "product must be 0 (ordered) or 1 (matrix), but is " + std::to_string(product) + "!");
+        impl_of(p)->landmark_acc(landmarks, rank, product, D_out);
     });
 }
 int lssvm_mi355_problem_landmark_gram_weighted(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, const double *weights, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows,

@@ -41,12 +41,14 @@ __device__ __forceinline__ double landmark_kernel_value(int kernel_type, int deg
     return k;
 }
 
-/* Kd[l][i - row0] = k(x_i, x_lm[l]) for the points row0 <= i < N of this launch's row blocks (exact zeros from N on) and a tile of 16 landmarks, in double: the
- * landmarks' features go through LDS in chunks of 32, a thread walks its own row in 16-byte pieces.  `gamma`: the kernel function's, divided by the square of the
- * factor X_ carries.  `ldN`: doubles between two landmarks' columns; the grid's x extent times 256 rows are written from column offset 0 on. */
-template <typename T>
-__global__ __launch_bounds__(256) void k_landmark_block(const T *__restrict__ X, int ldx, int N, int row0, const int *__restrict__ lm, int m, int kernel_type, int degree, double gamma,
-                                                        double coef0, double *__restrict__ Kd, size_t ldN) {
+/* The body of k_landmark_block and of k_landmark_acc, shared whole so that both walk THE SAME loop (same order, same LDS staging, same bits of acc): for the points
+ * row0 <= i < N of this launch's row blocks and a tile of 16 landmarks, acc[l] = the sum over the features (ascending) of (a_f - b_f)^2 (rbf) or a_f b_f (polynomial,
+ * linear), in double -- the landmarks' features go through LDS in chunks of 32, a thread walks its own row in 16-byte pieces.  VALUES: out[l][i - row0] =
+ * landmark_kernel_value(acc[l]); else acc[l] itself.  Exact zeros from point N on.  (The kernel's whole body and not the loop alone: with the loop cut out on its own the
+ * compiler schedules k_landmark_block differently; this way its instructions are the ones it had.) */
+template <typename T, bool VALUES>
+__device__ __forceinline__ void landmark_block_body(const T *__restrict__ X, int ldx, int N, int row0, const int *__restrict__ lm, int m, int kernel_type, int degree, double gamma,
+                                                    double coef0, double *__restrict__ Kd, size_t ldN) {
     constexpr int FC = 32, V = PcVec<T>::n;
     __shared__ T xl[16][FC];
     const int local = blockIdx.x * 256 + threadIdx.x;
@@ -84,9 +86,26 @@ __global__ __launch_bounds__(256) void k_landmark_block(const T *__restrict__ X,
 #pragma unroll
     for (int l = 0; l < 16; ++l) {
         if (l0 + l >= m) continue;
-        const double k = landmark_kernel_value(kernel_type, degree, gamma, coef0, acc[l]);
+        const double k = VALUES ? landmark_kernel_value(kernel_type, degree, gamma, coef0, acc[l]) : acc[l];
         Kd[static_cast<size_t>(l0 + l) * ldN + local] = i < N ? k : 0.0;
     }
+}
+
+/* Kd[l][i - row0] = k(x_i, x_lm[l]) for the points row0 <= i < N of this launch's row blocks (exact zeros from N on) and a tile of 16 landmarks, in double.  `gamma`: the
+ * kernel function's, divided by the square of the factor X_ carries.  `ldN`: doubles between two landmarks' columns; the grid's x extent times 256 rows are written from
+ * column offset 0 on. */
+template <typename T>
+__global__ __launch_bounds__(256) void k_landmark_block(const T *__restrict__ X, int ldx, int N, int row0, const int *__restrict__ lm, int m, int kernel_type, int degree, double gamma,
+                                                        double coef0, double *__restrict__ Kd, size_t ldN) {
+    landmark_block_body<T, true>(X, ldx, N, row0, lm, m, kernel_type, degree, gamma, coef0, Kd, ldN);
+}
+
+/* D[l][i - row0] = the sum k_landmark_block hands to landmark_kernel_value, stored instead (exact zeros from N on): what every gamma of a grid shares (lssvm_reduced.hip;
+ * DESIGN.md section 17).  k_kernel_values on it gives k_landmark_block's bits.  Grid and layout as k_landmark_block. */
+template <typename T>
+__global__ __launch_bounds__(256) void k_landmark_acc(const T *__restrict__ X, int ldx, int N, int row0, const int *__restrict__ lm, int m, int kernel_type, double *__restrict__ D,
+                                                      size_t ldN) {
+    landmark_block_body<T, false>(X, ldx, N, row0, lm, m, kernel_type, 0, 0.0, 0.0, D, ldN);
 }
 
 /* Kmm[k][l] = slab[l][lm[k] - row0] for the landmarks that lie in the rows [row0, row0 + rows) of this column-major slab of the block (ld doubles between two columns); a
@@ -122,11 +141,14 @@ class LandmarkBlock {
     }
     size_t device_bytes() const { return lm_dev_.count * sizeof(int); }
     /* gamma and coef0 for the data as X_ holds it (the rule above); the landmark selection evaluates its columns with them (lssvm_select.hip) */
-    static void kernel_scalars(const Problem<T> &p, double &gamma, double &coef0) {
+    static void kernel_scalars(const Problem<T> &p, double &gamma, double &coef0) { kernel_scalars(p, p.params_.gamma, gamma, coef0); }
+    /* the same rule for a gamma that is not the problem's own: a grid of them on one resident problem (lssvm_reduced.hip) */
+    static void kernel_scalars(const Problem<T> &p, double gamma_in, double &gamma, double &coef0) {
         const double scale2 = p.x_scale_ * p.x_scale_;
-        gamma = p.params_.kernel_type == LSSVM_KERNEL_LINEAR ? 1.0 / scale2 : static_cast<double>(static_cast<T>(p.params_.gamma)) / scale2;
+        gamma = p.params_.kernel_type == LSSVM_KERNEL_LINEAR ? 1.0 / scale2 : static_cast<double>(static_cast<T>(gamma_in)) / scale2;
         coef0 = static_cast<double>(static_cast<T>(p.params_.coef0));
     }
+    const int *landmarks_dev() const { return lm_dev_.p; }
 
   private:
     const Problem<T> &p_;

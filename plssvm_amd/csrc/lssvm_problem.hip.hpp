@@ -338,6 +338,8 @@ template <typename T>
 class CgSteps;
 template <typename T>
 class LandmarkBlock;  // K(X, X_L) of a resident problem (lssvm_landmark.hip.hpp)
+template <typename T>
+struct GridSlabs;  // what the slabs of a (gamma, cost) grid are made from: the sums every gamma shares (lssvm_reduced.hip)
 
 /* The CG state of ONE right-hand side on one device: the vectors y, b, x, r, d, Ad, the scalars and the four sets of partial sums, the host copies of the scalars and a
  * mapped host word for the iteration's delta (k_finish_delta stores its 8 bytes straight into host memory: no copy per iteration).  A problem has one of its own (the
@@ -423,6 +425,7 @@ class Problem {
     friend class Solver<T>;
     friend class CgSteps<T>;
     friend class LandmarkBlock<T>;
+    friend struct GridSlabs<T>;
     TileArgs<T> tile_args(const T *v_dev) const;
     /* dc_ <- the single-vector records of v, and `zero[0 .. nzero)` cleared by the same kernel: the one k_pack_dc / k_pack_dc_f64 launch of a problem */
     void enqueue_pack_dc(const T *v, T *zero, int nzero);
@@ -638,6 +641,12 @@ struct ProblemBase {
                                      double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out,
                                      lssvm_reduced_loo_info *infos, lssvm_dense_info *dense, const double *weights = nullptr) = 0;  // lssvm_mi355_problem_fit_reduced_loo_dev
     virtual void time_leverage_kernel(uint64_t rank, uint64_t slab_rows, size_t k, int repeats, double *gram_ms_out, double *leverage_ms_out) = 0;  // lssvm_mi355_problem_time_leverage_kernel
+    /* the leave-one-out scores over a (gamma, cost) grid on this one problem (lssvm_reduced.hip); every output leads with the gamma dimension */
+    virtual void fit_reduced_grid(const void *Y, size_t num_rhs, const double *weights, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *gammas, size_t num_gammas,
+                                  const double *costs, size_t num_costs, int factor, int product, double *betas_out, double *rhos_out, double *leverage_out, double *fitted_out,
+                                  double *loo_out, double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out, lssvm_reduced_grid_info *infos,
+                                  lssvm_dense_info *dense) = 0;  // lssvm_mi355_problem_fit_reduced_grid
+    virtual void landmark_acc(const uint64_t *landmarks, uint64_t rank, int product, double *D_out) = 0;  // lssvm_mi355_problem_landmark_acc
     /* landmark selection: the pivots of a greedy or randomly pivoted partial Cholesky factorisation (lssvm_select.hip) */
     virtual void select_landmarks(uint64_t rank, int method, uint64_t pool, uint64_t seed, double tol, uint64_t *landmarks_out, double *trace_out, double *residual_out,
                                   lssvm_landmark_select_info *info) = 0;  // lssvm_mi355_problem_select_landmarks
@@ -744,6 +753,11 @@ class Solver final : public ProblemBase {
     void reduced_leverage(uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *V, const double *shift, const double *B_extra, size_t k, double *h_out,
                           double *f_out) override;
     void time_leverage_kernel(uint64_t rank, uint64_t slab_rows, size_t k, int repeats, double *gram_ms_out, double *leverage_ms_out) override;
+    /* fit_reduced_loo at every gamma of a grid: the feature sums behind Phi are formed once per slab and pass and shared by the gammas */
+    void fit_reduced_grid(const void *Y, size_t num_rhs, const double *weights, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *gammas, size_t num_gammas,
+                          const double *costs, size_t num_costs, int factor, int product, double *betas_out, double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out,
+                          double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out, lssvm_reduced_grid_info *infos, lssvm_dense_info *dense) override;
+    void landmark_acc(const uint64_t *landmarks, uint64_t rank, int product, double *D_out) override;
     /* fit_reduced and fit_reduced_loo with assembly, factorisation, solves and the triangular inverse on the device (lssvm_dense.hip) */
     void fit_reduced_dev(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, double *betas_out, double *rhos_out, uint64_t *landmarks_out,
                          lssvm_reduced_info *info, lssvm_dense_info *dense, const double *weights = nullptr) override;
@@ -798,7 +812,7 @@ class Solver final : public ProblemBase {
                       std::vector<double> &gram_out, std::vector<double> &kmm_out, lssvm_reduced_info &info, ReducedOnDevice *keep = nullptr, const double *weights = nullptr,
                       double *total_out = nullptr);
     /* pass 2 of fit_reduced_loo, and all of reduced_leverage: the Phi slabs again, the leverage kernel per slab and operand (lssvm_reduced.hip) */
-    void leverage_pass(const std::vector<uint64_t> &lm, uint64_t slab_rows, LeverageArgs &args);
+    void leverage_pass(const std::vector<uint64_t> &lm, uint64_t slab_rows, LeverageArgs &args, GridSlabs<T> *grid = nullptr);
     T *vec_of(Problem<T> &p, Vec which) const { return which == Vec::d ? p.own_.d.p : (which == Vec::x ? p.own_.x.p : p.tmp_.p); }
 
     Options opt_{};
@@ -848,6 +862,11 @@ void check_reduced_factor(int factor);
 /* the cost grid of lssvm_mi355_problem_fit_reduced_loo / lssvm_mi355_fit_reduced_loo_*: 1 ... REDUCED_LOO_MAX_COSTS costs, each finite and positive */
 constexpr size_t REDUCED_LOO_MAX_COSTS = 64;
 void check_reduced_loo_costs(const double *costs, size_t num_costs);
+/* what lssvm_mi355_problem_fit_reduced_grid / lssvm_mi355_fit_reduced_grid_* add to those: the gammas (each finite and > 0), at most REDUCED_GRID_MAX_CELLS (gamma, cost)
+ * cells, `product` 0 or 1, and a kernel function that has a gamma to vary */
+constexpr size_t REDUCED_GRID_MAX_CELLS = 64;
+void check_reduced_grid_arguments(const double *gammas, size_t num_gammas, size_t num_costs, int product);
+void check_reduced_grid_kernel(int kernel_type);
 
 /* the arguments of lssvm_mi355_problem_select_landmarks / lssvm_mi355_select_landmarks_* that need no device (lssvm_select.hip); returns the number of candidates */
 constexpr int SELECT_MAX_RANK = 1024;

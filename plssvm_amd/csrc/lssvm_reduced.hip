@@ -21,6 +21,11 @@
  * Per-point weights w_i >= 0 (lssvm_mi355_problem_fit_reduced_weighted, _fit_reduced_loo_weighted, _landmark_gram_weighted): St = Pt^T diag(w) Pt and
  * W = sum w_i wherever N stands.  k_reduced_gram<true> multiplies both staged operands by sqrt(w_i) (formed on the host, uploaded once per call; the slab stays unscaled),
  * k_reduced_leverage multiplies by w_i; everything between them takes W as the double it took N as.  Without weights every call launches what it launched before.
+ *
+ * The leave-one-out scores over a (gamma, cost) grid on one problem (lssvm_mi355_problem_fit_reduced_grid, _landmark_acc, lssvm_mi355_fit_reduced_grid_*; DESIGN.md
+ * section 17): what a kernel value is made from, D = sum_f (a_f - b_f)^2 or sum_f a_f b_f, does not depend on gamma.  GridSlabs forms it once per slab and pass --
+ * k_landmark_acc (the loop of k_landmark_block) or k_landmark_product (the dot products on v_mfma_f64_16x16x4_f64, the norm expansion for rbf) -- and k_kernel_values
+ * writes the Phi columns of a gamma from it; the Gram pass, the dense steps and the leverage kernel per (gamma, cost) are the ones above.
  */
 #include "lssvm_dense.hip.hpp"
 #include "lssvm_landmark.hip.hpp"
@@ -28,6 +33,8 @@
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
+#include <memory>
+#include <optional>
 
 namespace lssvm {
 
@@ -314,6 +321,22 @@ void invert_lower_rows(const std::vector<double> &L, int m, double *out, size_t 
     }
 }
 
+/* One cost of a leave-one-out grid on the host, in double: M, L, beta and rho as fit_reduced forms them, V = L^-1; fills the cost's betas (k x m), rhos (k), ybar (k) and
+ * the leverage kernel's operand Bt (m rows of V, then the betas; ldb doubles apart); returns nu.  Shared by fit_reduced_loo and fit_reduced_grid. */
+double host_operand(const std::vector<double> &St, const std::vector<double> &Kmm, int m, int k, int cols, double Nd, double cost, int ldb, double *betas, double *rhos,
+                    std::vector<double> &L, std::vector<double> &Bt, double *ybar) {
+    const double nu = factor_reduced(St, Kmm, m, cols, Nd, 1.0 / cost, L);
+    solve_reduced(St, L, m, k, cols, Nd, betas, rhos);
+    invert_lower_rows(L, m, Bt.data(), static_cast<size_t>(ldb));
+    for (int c = 0; c < k; ++c) {
+        double *row = &Bt[static_cast<size_t>(m + c) * ldb];
+        std::fill(row, row + ldb, 0.0);
+        std::copy(betas + static_cast<size_t>(c) * m, betas + static_cast<size_t>(c + 1) * m, row);
+        ybar[c] = St[static_cast<size_t>(m + 1 + c) * cols + m] / Nd;
+    }
+    return nu;
+}
+
 /* ---- the same steps on the device (lssvm_dense.hip) ---- */
 /* trace(M) from the host copies, with factor_reduced's expression and cholesky_with_jitter's order: where no attempt fails, nu has the host path's bits */
 double reduced_trace(const std::vector<double> &St, const std::vector<double> &Kmm, int m, int cols, double Nd, double sigma) {
@@ -563,6 +586,167 @@ __global__ __launch_bounds__(256, 2) void k_reduced_leverage(const double *__res
     }
 }
 
+/* ---- what every gamma of a (gamma, cost) grid shares ---- */
+template <typename T>
+struct PairOf;
+template <>
+struct PairOf<float> {
+    using type = float __attribute__((ext_vector_type(2)));
+};
+template <>
+struct PairOf<double> {
+    using type = f64x2;
+};
+
+/* n[i] = the sum over the ldx held features (ascending) of x_if^2, in double: the squared norms k_landmark_product expands the rbf distance with */
+template <typename T>
+__global__ __launch_bounds__(256) void k_row_norms(const T *__restrict__ X, int ldx, size_t N, double *__restrict__ n) {
+    const size_t i = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= N) return;
+    const T *xi = X + i * ldx;
+    double acc = 0.0;
+    for (int f = 0; f < ldx; ++f) {
+        const double a = static_cast<double>(xi[f]);
+        acc += a * a;
+    }
+    n[i] = acc;
+}
+
+/* D[l][i - row0] of k_landmark_acc with the dot products x_i . x_lm[l] on v_mfma_f64_16x16x4_f64: one workgroup owns 128 landmarks (blockIdx.y) x 128 rows of the slab
+ * (blockIdx.x), the four waves hold 64 x 64 each as sixteen accumulators, exactly as k_reduced_gram.  The contraction runs over the ldx held features in steps of RG_KC = 16
+ * (ldx is a multiple of 16); both operands go through LDS in k_reduced_gram's layout (RG_LS doubles between two points), converted to double as they are staged: eight
+ * threads load the 16 features of a point as one 64-byte (fp32) or 128-byte (fp64) line.  The A operand are the landmarks' rows, gathered through lm[], the B operand the
+ * slab's rows: a lane holds landmarks qd + 4 i of its four landmark tiles and row r of its four row tiles, so sixteen lanes write 128 contiguous bytes of a column of D.
+ * Landmarks from m on and rows from N on count as zeros and are never read; landmarks from m on are not written, rows from N on are written as zeros.
+ * rbf: D = n_i + n_l - 2 x_i . x_l with `norms` of k_row_norms, clamped at 0, and EXACTLY 0 where i == lm[l] (the expansion leaves a rounding there; K_mm's diagonal is
+ * exactly 1, as on the ordered path).  Any other kernel type: the dot product.  No atomics, no scratch; the order of every sum depends on ldx only. */
+template <typename T>
+__global__ __launch_bounds__(256, 2) void k_landmark_product(const T *__restrict__ X, int ldx, int N, int row0, const int *__restrict__ lm, int m, int kernel_type,
+                                                             const double *__restrict__ norms, double *__restrict__ D, size_t ldN) {
+    using pair = typename PairOf<T>::type;
+    __shared__ __attribute__((aligned(16))) double As[RG_TW * RG_LS];
+    __shared__ __attribute__((aligned(16))) double Bs[RG_TW * RG_LS];
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int wr = wave >> 1, wc = wave & 1;
+    const int r = lane & 15, qd = lane >> 4;
+    const int l0 = blockIdx.y * RG_TW;             // the workgroup's first landmark
+    const int local0 = blockIdx.x * RG_TW;         // ... and first row of the slab
+    const int nsteps = ldx / RG_KC;
+
+    // staging: thread -> (point srow [+ 32 p] of the tile, features 2 sseg, 2 sseg + 1 of the step), as k_reduced_gram
+    const int srow = tid >> 3, sseg = tid & 7;
+    const T *Ag[4], *Bg[4];
+    bool a_in[4], b_in[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const int la = l0 + srow + 32 * p, ib = row0 + local0 + srow + 32 * p;
+        a_in[p] = la < m;
+        b_in[p] = ib < N;
+        Ag[p] = X + static_cast<size_t>(a_in[p] ? lm[la] : 0) * ldx + 2 * sseg;
+        Bg[p] = X + static_cast<size_t>(b_in[p] ? ib : 0) * ldx + 2 * sseg;
+    }
+    const int lds_w = srow * RG_LS + 2 * sseg;
+    f64x2 sa[4], sb[4];
+    const f64x2 zero2 = { 0.0, 0.0 };
+    auto stage_load = [&](int s) {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            sa[p] = zero2;
+            sb[p] = zero2;
+            if (a_in[p]) {
+                const pair v = *reinterpret_cast<const pair *>(Ag[p] + s * RG_KC);
+                sa[p] = f64x2{ static_cast<double>(v[0]), static_cast<double>(v[1]) };
+            }
+            if (b_in[p]) {
+                const pair v = *reinterpret_cast<const pair *>(Bg[p] + s * RG_KC);
+                sb[p] = f64x2{ static_cast<double>(v[0]), static_cast<double>(v[1]) };
+            }
+        }
+    };
+    auto stage_store = [&]() {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            *reinterpret_cast<f64x2 *>(As + lds_w + p * 32 * RG_LS) = sa[p];
+            *reinterpret_cast<f64x2 *>(Bs + lds_w + p * 32 * RG_LS) = sb[p];
+        }
+    };
+
+    f64x4 acc[4][4];
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+            acc[mt][nt] = f64x4{ 0.0, 0.0, 0.0, 0.0 };
+            // the start values live in the accumulators' OWN registers (C == D for every MFMA of a chain), as in k_reduced_gram
+            asm volatile("" : "+v"(acc[mt][nt]));
+        }
+
+    if (nsteps > 0) {
+        stage_load(0);
+        stage_store();
+    }
+    __syncthreads();
+    const double *Ab = As + (wr * 64 + r) * RG_LS + qd;
+    const double *Bb = Bs + (wc * 64 + r) * RG_LS + qd;
+    for (int s = 0; s < nsteps; ++s) {
+        const bool has_next = s + 1 < nsteps;
+        if (has_next) stage_load(s + 1);
+#pragma unroll
+        for (int ks = 0; ks < RG_KC / 4; ++ks) {
+            double av[4], bv[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                av[t] = Ab[t * 16 * RG_LS + ks * 4];
+                bv[t] = Bb[t * 16 * RG_LS + ks * 4];
+            }
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[mt], bv[nt], acc[mt][nt], 0, 0, 0);
+        }
+        __syncthreads();  // (every wave has read this step)
+        if (has_next) {
+            stage_store();
+            __syncthreads();
+        }
+    }
+
+    // a lane holds landmarks l0 + wr 64 + mt 16 + qd + 4 i and rows local0 + wc 64 + nt 16 + r
+    const bool rbf = kernel_type == LSSVM_KERNEL_RBF;
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+        const int local = local0 + wc * 64 + nt * 16 + r;
+        const int row = row0 + local;
+        const bool row_in = row < N;
+        const double ni = rbf && row_in ? norms[row] : 0.0;
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int l = l0 + wr * 64 + mt * 16 + qd + 4 * i;
+                if (l >= m) continue;
+                double d = acc[mt][nt][i];
+                if (rbf) {
+                    const int at = lm[l];
+                    d = fmax((ni + norms[at]) - 2.0 * d, 0.0);
+                    if (at == row) d = 0.0;
+                }
+                D[static_cast<size_t>(l) * ldN + local] = row_in ? d : 0.0;
+            }
+    }
+}
+
+/* Phi[l][i] = k from D[l][i] (landmark_kernel_value: the epilogue of k_landmark_block) for the rows row0 + i < N of a slab, EXACT zeros from N on (exp(0) is 1, not 0);
+ * `gamma`: the kernel function's for the data as X_ holds it (LandmarkBlock::kernel_scalars).  One thread per entry; the grid's x extent times 256 rows, m columns. */
+__global__ __launch_bounds__(256) void k_kernel_values(const double *__restrict__ D, size_t ld, int N, int row0, int kernel_type, int degree, double gamma, double coef0,
+                                                       double *__restrict__ Phi) {
+    const int local = blockIdx.x * 256 + threadIdx.x;
+    const size_t at = static_cast<size_t>(blockIdx.y) * ld + local;
+    Phi[at] = row0 + local < N ? landmark_kernel_value(kernel_type, degree, gamma, coef0, D[at]) : 0.0;
+}
+
 }  // namespace
 
 /* what a leave-one-out pass works on: `num_ops` operands on the device (Bt of k_reduced_leverage, op_stride doubles apart; ybar: num_ops x k or none), and where its results go */
@@ -579,26 +763,27 @@ struct LeverageArgs {
     std::vector<double> max_leverage, leverage_ms;                       // per operand
     double landmark_ms = 0.0;
 
-    /* the operands as zeros on the device */
-    LeverageArgs(int rank, int num_cols, size_t operands, bool with_ybar, hipStream_t stream) :
+    /* the operands as zeros on the device; `shifts`: how many shift vectors of m doubles the pass takes (one per gamma of a grid: the operands are shared out evenly
+     * among them, in order) */
+    LeverageArgs(int rank, int num_cols, size_t operands, bool with_ybar, hipStream_t stream, size_t shifts = 1) :
         m(rank), k(num_cols), ldb(round_up(rank, RG_KC)), num_ops(operands), op_stride(static_cast<size_t>(rank + num_cols) * ldb), st(stream) {
         Bt.alloc_zero(num_ops * op_stride, st);
-        shift.alloc_zero(static_cast<size_t>(m), st);
+        shift.alloc_zero(shifts * static_cast<size_t>(m), st);
         if (with_ybar) ybar.alloc_zero(num_ops * k, st);
     }
     /* operand o <- the host's m + k rows of ldb doubles; asynchronous: the rows stay as they are until the stream has been synchronised */
     void upload_operand(size_t o, const double *Bt_host) {
         LSSVM_HIP_CHECK(hipMemcpyAsync(Bt.p + o * op_stride, Bt_host, op_stride * sizeof(double), hipMemcpyHostToDevice, st));
     }
-    /* shift (m) and, where the pass takes one, ybar (num_ops x k); returns when these and the operands are on the device */
+    /* shift (m per shift vector) and, where the pass takes one, ybar (num_ops x k); returns when these and the operands are on the device */
     void upload_shift(const double *shift_host, const double *ybar_host) {
-        LSSVM_HIP_CHECK(hipMemcpyAsync(shift.p, shift_host, static_cast<size_t>(m) * sizeof(double), hipMemcpyHostToDevice, st));
+        LSSVM_HIP_CHECK(hipMemcpyAsync(shift.p, shift_host, shift.count * sizeof(double), hipMemcpyHostToDevice, st));
         if (ybar_host != nullptr) LSSVM_HIP_CHECK(hipMemcpyAsync(ybar.p, ybar_host, ybar.count * sizeof(double), hipMemcpyHostToDevice, st));
         LSSVM_HIP_CHECK(hipStreamSynchronize(st));
     }
     /* k_reduced_leverage for operand o on `rows` rows of a slab (ld doubles between its columns; its [1 | Y] columns stand behind Phi where `loo` is given) */
-    void enqueue(size_t o, const double *slab, size_t ld, int rows, double *h, double *f, double *loo, const double *w_dev = nullptr) const {
-        hipLaunchKernelGGL(k_reduced_leverage, dim3(round_up(rows, 256) / RG_TW), dim3(256), 0, st, slab, ld, rows, m, k, Bt.p + o * op_stride, ldb, shift.p, ybar.p != nullptr ? ybar.p + o * k : nullptr,
+    void enqueue(size_t o, const double *slab, size_t ld, int rows, double *h, double *f, double *loo, const double *w_dev = nullptr, size_t shift_at = 0) const {
+        hipLaunchKernelGGL(k_reduced_leverage, dim3(round_up(rows, 256) / RG_TW), dim3(256), 0, st, slab, ld, rows, m, k, Bt.p + o * op_stride, ldb, shift.p + shift_at * m, ybar.p != nullptr ? ybar.p + o * k : nullptr,
                            inv_n, loo != nullptr ? slab + static_cast<size_t>(m + 1) * ld : nullptr, h, f, loo, ld, w_dev);
         LSSVM_HIP_CHECK(hipGetLastError());
     }
@@ -639,6 +824,91 @@ void upload_per_row(const double *values, bool take_sqrt, const SlabPlan &plan, 
 }
 
 }  // namespace
+
+void check_reduced_grid_arguments(const double *gammas, size_t num_gammas, size_t num_costs, int product) {
+    LSSVM_REQUIRE(gammas != nullptr, "gammas must not be NULL");
+    LSSVM_REQUIRE(num_gammas >= 1, "The grid takes at least 1 gamma, but got 0!");
+    LSSVM_REQUIRE(num_gammas <= REDUCED_GRID_MAX_CELLS && num_gammas * num_costs <= REDUCED_GRID_MAX_CELLS,
+                  "The grid takes at most " + std::to_string(REDUCED_GRID_MAX_CELLS) + " (gamma, cost) cells, but got " + std::to_string(num_gammas) + " x " + std::to_string(num_costs) + "!");
+    for (size_t g = 0; g < num_gammas; ++g)  // (behind the cap: at most 64 entries are read)
+        LSSVM_REQUIRE(std::isfinite(gammas[g]) && gammas[g] > 0.0, "Every gamma must be finite and greater than 0, but gamma " + std::to_string(g) + " is " + std::to_string(gammas[g]) + "!");
+    LSSVM_REQUIRE(product == 0 || product == 1, "product must be 0 (ordered) or 1 (matrix), but is " + std::to_string(product) + "!");
+}
+
+void check_reduced_grid_kernel(int kernel_type) {
+    LSSVM_REQUIRE(kernel_type != LSSVM_KERNEL_LINEAR, "The linear kernel has no gamma to vary: the (gamma, cost) grid takes an rbf or a polynomial problem!");
+}
+
+/* What the slabs of a (gamma, cost) grid are made from: per slab, D -- the feature sums behind every kernel value, k_landmark_acc (product 0) or
+ * k_landmark_product (1) -- is formed once into a work space of its own, and per gamma k_kernel_values writes the Phi columns of the slab from it.  Both passes of a fit
+ * go through the same object: the same kernels with the same arguments, hence the same bits.  The landmarks, the right-hand sides and (rbf, product 1) the rows' squared
+ * norms go to the device once.  `gammas_in`: the kernel function's, as the caller gives them; held here for the data as X_ holds it (LandmarkBlock::kernel_scalars). */
+template <typename T>
+struct GridSlabs {
+    const Problem<T> &p;
+    const SlabPlan plan;
+    const int m, product;
+    hipStream_t st;
+    const LandmarkBlock<T> block;
+    const RhsOnDevice<T> rhs;
+    DevBuf<double> D, norms;
+    std::vector<double> gammas, values_ms;
+    double coef0 = 0.0, accumulate_ms = 0.0;
+    Event ev[2];
+
+    GridSlabs(const Problem<T> &problem, const std::vector<uint64_t> &lm, const void *Y, int k, uint64_t slab_rows, const double *gammas_in, size_t num_gammas, int product_in,
+              hipStream_t stream) :
+        p(problem), plan(problem.N_, slab_rows), m(static_cast<int>(lm.size())), product(product_in), st(stream), block(problem, lm, stream), rhs(Y, k, problem.N_, stream),
+        gammas(num_gammas), values_ms(num_gammas, 0.0) {
+        for (size_t g = 0; g < num_gammas; ++g) LandmarkBlock<T>::kernel_scalars(p, gammas_in[g], gammas[g], coef0);
+        for (Event &e : ev) e.create(true);
+        D.alloc_zero(static_cast<size_t>(m) * plan.ld, st);
+        if (product == 1 && p.params_.kernel_type == LSSVM_KERNEL_RBF) {
+            norms.alloc_zero(p.N_, st);
+            LSSVM_HIP_CHECK(hipEventRecord(ev[0].e, st));
+            hipLaunchKernelGGL(k_row_norms<T>, dim3(static_cast<unsigned>((p.N_ + 255) / 256)), dim3(256), 0, st, p.X_.data.p, p.X_.ldx, p.N_, norms.p);
+            LSSVM_HIP_CHECK(hipGetLastError());
+            LSSVM_HIP_CHECK(hipEventRecord(ev[1].e, st));
+            LSSVM_HIP_CHECK(hipEventSynchronize(ev[1].e));
+            accumulate_ms += elapsed_ms(ev[0], ev[1]);
+        }
+    }
+    size_t device_bytes() const { return (D.count + norms.count) * sizeof(double) + rhs.Y.count * sizeof(T) + block.device_bytes(); }
+
+    /* D of slab s */
+    void enqueue_acc(int s) const {
+        const int rows256 = plan.rows256(s), N = static_cast<int>(p.N_), row0 = static_cast<int>(plan.row0(s));
+        if (product == 1) {
+            hipLaunchKernelGGL(k_landmark_product<T>, dim3(rows256 / RG_TW, (m + RG_TW - 1) / RG_TW), dim3(256), 0, st, p.X_.data.p, p.X_.ldx, N, row0, block.landmarks_dev(), m,
+                               p.params_.kernel_type, norms.p, D.p, plan.ld);
+        } else {
+            hipLaunchKernelGGL(k_landmark_acc<T>, dim3(rows256 / 256, (m + 15) / 16), dim3(256), 0, st, p.X_.data.p, p.X_.ldx, N, row0, block.landmarks_dev(), m, p.params_.kernel_type, D.p,
+                               plan.ld);
+        }
+        LSSVM_HIP_CHECK(hipGetLastError());
+    }
+    /* what the gammas share of slab s: D (timed), and the [1 | Y] columns of `slab` behind the m columns of Phi where there are right-hand sides */
+    void enqueue_shared(int s, double *slab) {
+        LSSVM_HIP_CHECK(hipEventRecord(ev[0].e, st));
+        enqueue_acc(s);
+        LSSVM_HIP_CHECK(hipEventRecord(ev[1].e, st));
+        if (rhs.Y.p != nullptr)
+            hipLaunchKernelGGL(k_reduced_aux<T>, dim3(plan.rows256(s) / 256, 1 + rhs.k), dim3(256), 0, st, rhs.Y.p, plan.N, plan.row0(s), slab + static_cast<size_t>(m) * plan.ld, plan.ld);
+        LSSVM_HIP_CHECK(hipGetLastError());
+        LSSVM_HIP_CHECK(hipEventSynchronize(ev[1].e));
+        accumulate_ms += elapsed_ms(ev[0], ev[1]);
+    }
+    /* the m columns of Phi of slab s at gamma g, from the D enqueue_shared left (timed; returns when they are written) */
+    void enqueue_values(size_t g, int s, double *slab) {
+        LSSVM_HIP_CHECK(hipEventRecord(ev[0].e, st));
+        hipLaunchKernelGGL(k_kernel_values, dim3(plan.rows256(s) / 256, m), dim3(256), 0, st, D.p, plan.ld, static_cast<int>(p.N_), static_cast<int>(plan.row0(s)), p.params_.kernel_type,
+                           p.params_.degree, gammas[g], coef0, slab);
+        LSSVM_HIP_CHECK(hipGetLastError());
+        LSSVM_HIP_CHECK(hipEventRecord(ev[1].e, st));
+        LSSVM_HIP_CHECK(hipEventSynchronize(ev[1].e));
+        values_ms[g] += elapsed_ms(ev[0], ev[1]);
+    }
+};
 
 template <typename T>
 Problem<T> &Solver<T>::reduced_problem(const char *what, bool unweighted_only) {
@@ -799,7 +1069,7 @@ void check_reduced_loo_costs(const double *costs, size_t num_costs) {
 /* The Phi slabs once more (the kernels and arguments of reduced_gram: the same bits) and, per slab, k_reduced_leverage once per operand; h, f and loo of the slab go to the
  * caller's arrays, the sums over the points are formed here in row order.  The caller has made the checks that need no device. */
 template <typename T>
-void Solver<T>::leverage_pass(const std::vector<uint64_t> &lm, uint64_t slab_rows, LeverageArgs &a) {
+void Solver<T>::leverage_pass(const std::vector<uint64_t> &lm, uint64_t slab_rows, LeverageArgs &a, GridSlabs<T> *grid) {
     Problem<T> &p = *shards_[0];
     const size_t N = p.N_;
     const int m = a.m, k = a.k;
@@ -808,9 +1078,12 @@ void Solver<T>::leverage_pass(const std::vector<uint64_t> &lm, uint64_t slab_row
     hipStream_t st = p.stream();
     const SlabPlan plan(N, slab_rows);
     const size_t ld = plan.ld;
+    // a grid brings its own landmarks and right-hand sides on the device and fills the slab once per gamma; the operands are shared out evenly among the gammas, in order
+    const size_t groups = grid != nullptr ? grid->gammas.size() : 1, per_group = a.num_ops / groups;
 
-    const LandmarkBlock<T> block(p, lm, st);
-    const RhsOnDevice<T> rhs(a.Y, k, N, st);
+    std::optional<LandmarkBlock<T>> block;
+    if (grid == nullptr) block.emplace(p, lm, st);
+    const RhsOnDevice<T> rhs(grid == nullptr ? a.Y : nullptr, k, N, st);
     DevBuf<double> slab, h_dev, f_dev, loo_dev, w_dev;
     if (a.w != nullptr) upload_per_row(a.w, false, plan, w_dev, st);
     if (with_y) loo_dev.alloc_zero(static_cast<size_t>(k) * ld, st);
@@ -830,15 +1103,21 @@ void Solver<T>::leverage_pass(const std::vector<uint64_t> &lm, uint64_t slab_row
     for (int s = 0; s < plan.slabs; ++s) {
         const size_t row0 = plan.row0(s);
         const int rows = plan.rows(s);
-        LSSVM_HIP_CHECK(hipEventRecord(ev[0].e, st));
-        enqueue_slab(block, m, plan, s, rhs, slab.p, st);
-        LSSVM_HIP_CHECK(hipGetLastError());
-        LSSVM_HIP_CHECK(hipEventRecord(ev[1].e, st));
-        LSSVM_HIP_CHECK(hipEventSynchronize(ev[1].e));
-        a.landmark_ms += elapsed_ms(ev[0], ev[1]);
-        for (size_t o = 0; o < a.num_ops; ++o) {
+        if (grid != nullptr) {
+            grid->enqueue_shared(s, slab.p);
+        } else {
             LSSVM_HIP_CHECK(hipEventRecord(ev[0].e, st));
-            a.enqueue(o, slab.p, ld, rows, h_dev.p, f_dev.p, loo_dev.p, w_dev.p != nullptr ? w_dev.p + row0 : nullptr);
+            enqueue_slab(*block, m, plan, s, rhs, slab.p, st);
+            LSSVM_HIP_CHECK(hipGetLastError());
+            LSSVM_HIP_CHECK(hipEventRecord(ev[1].e, st));
+            LSSVM_HIP_CHECK(hipEventSynchronize(ev[1].e));
+            a.landmark_ms += elapsed_ms(ev[0], ev[1]);
+        }
+        for (size_t o = 0; o < a.num_ops; ++o) {
+            const size_t g = o / per_group;
+            if (grid != nullptr && o % per_group == 0) grid->enqueue_values(g, s, slab.p);  // (every operand of the gamma before has been waited for)
+            LSSVM_HIP_CHECK(hipEventRecord(ev[0].e, st));
+            a.enqueue(o, slab.p, ld, rows, h_dev.p, f_dev.p, loo_dev.p, w_dev.p != nullptr ? w_dev.p + row0 : nullptr, g);
             LSSVM_HIP_CHECK(hipEventRecord(ev[1].e, st));
             LSSVM_HIP_CHECK(hipMemcpyAsync(h_host.data(), h_dev.p, static_cast<size_t>(rows) * sizeof(double), hipMemcpyDeviceToHost, st));
             for (int c = 0; c < k; ++c) {
@@ -901,16 +1180,7 @@ void Solver<T>::fit_reduced_loo(const void *Y, size_t num_rhs, uint64_t rank, co
     for (int j = 0; j < m; ++j) shift[j] = s_row[j] / Nd;
     for (size_t s = 0; s < num_costs; ++s) {
         const double t_host = now_ms();
-        nus[s] = factor_reduced(St, Kmm, m, cols, Nd, 1.0 / costs[s], L);
-        double *betas = betas_out + s * k * m;
-        solve_reduced(St, L, m, k, cols, Nd, betas, rhos_out + s * k);
-        invert_lower_rows(L, m, Bt.data(), static_cast<size_t>(a.ldb));
-        for (int c = 0; c < k; ++c) {
-            double *row = &Bt[static_cast<size_t>(m + c) * a.ldb];
-            std::fill(row, row + a.ldb, 0.0);
-            std::copy(betas + static_cast<size_t>(c) * m, betas + static_cast<size_t>(c + 1) * m, row);
-            ybar[s * k + c] = St[static_cast<size_t>(m + 1 + c) * cols + m] / Nd;
-        }
+        nus[s] = host_operand(St, Kmm, m, k, cols, Nd, costs[s], a.ldb, betas_out + s * k * m, rhos_out + s * k, L, Bt, &ybar[s * k]);
         host_ms[s] = now_ms() - t_host;
         a.upload_operand(s, Bt.data());
         LSSVM_HIP_CHECK(hipStreamSynchronize(st));  // (Bt is filled again for the next cost)
@@ -999,6 +1269,153 @@ void Solver<T>::fit_reduced_loo_dev(const void *Y, size_t num_rhs, uint64_t rank
             infos[s].leverage_ms = a.leverage_ms[s];
             infos[s].host_ms = host_ms[s];
         }
+    }
+}
+
+/* fit_reduced_loo / _dev at every gamma of a grid on this one problem: the two passes of the leave-one-out fit, with the slabs made by GridSlabs --
+ * per slab D once, per gamma the Phi columns from it, K_mm and that gamma's own running St; per (gamma, cost) the dense steps of `factor` and, in pass 2, the leverage
+ * kernel.  Cell (g, s) of every output stands at g num_costs + s. */
+template <typename T>
+void Solver<T>::fit_reduced_grid(const void *Y, size_t num_rhs, const double *weights, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *gammas,
+                                 size_t num_gammas, const double *costs, size_t num_costs, int factor, int product, double *betas_out, double *rhos_out, double *leverage_out,
+                                 double *fitted_out, double *loo_out, double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out, lssvm_reduced_grid_info *infos,
+                                 lssvm_dense_info *dense_out) {
+    // ---- everything that needs no device ----
+    LSSVM_REQUIRE(betas_out != nullptr && rhos_out != nullptr, "betas_out / rhos_out must not be NULL");
+    check_reduced_loo_costs(costs, num_costs);
+    check_reduced_grid_arguments(gammas, num_gammas, num_costs, product);
+    check_reduced_factor(factor);
+    Problem<T> &p = reduced_problem("fit_reduced_grid", true);
+    check_reduced_grid_kernel(p.params_.kernel_type);
+    const size_t N = p.N_;
+    check_reduced_arguments(Y, num_rhs, rank, slab_rows, N);
+    LSSVM_REQUIRE(num_rhs <= 4096, "at most 4096 right hand sides per call");
+    const int m = static_cast<int>(rank), k = static_cast<int>(num_rhs), cols = m + 1 + k;
+    const std::vector<uint64_t> lm = resolve_landmarks(landmarks, static_cast<size_t>(m), N);
+    const double Nd = weights != nullptr ? check_reduced_weights(weights, N) : static_cast<double>(N);  // N, or the sum of the weights in index order
+    const size_t G = num_gammas, S = num_costs;
+
+    const SetOnExit<bool> busy = hold_busy();
+    p.activate();
+    hipStream_t st = p.stream();
+    GridSlabs<T> grid(p, lm, Y, k, slab_rows, gammas, G, product, st);
+    const SlabPlan &plan = grid.plan;
+    const size_t ld = plan.ld;
+    const int nt = tiles_of(cols), ntri = nt * (nt + 1) / 2;
+    const int max_chunks = static_cast<int>((ld + RG_RANGE - 1) / RG_RANGE);
+
+    // ---- pass 1: per slab D once; per gamma Phi from it, K_mm, and St into the gamma's own running sum ----
+    std::vector<ReducedOnDevice> dev(G);
+    std::vector<double> gram_ms(G, 0.0);
+    {
+        DevBuf<double> slab, part, q_dev;
+        slab.alloc_zero(static_cast<size_t>(cols) * ld, st);
+        part.alloc_zero(static_cast<size_t>(ntri) * max_chunks * RG_TILE, st);
+        for (ReducedOnDevice &d : dev) {
+            d.St.alloc_zero(static_cast<size_t>(ntri) * RG_TILE, st);
+            d.Kmm.alloc_zero(static_cast<size_t>(m) * m, st);
+        }
+        if (weights != nullptr) upload_per_row(weights, true, plan, q_dev, st);
+        Event ev[2];
+        for (Event &e : ev) e.create(true);
+        for (int s = 0; s < plan.slabs; ++s) {
+            grid.enqueue_shared(s, slab.p);
+            for (size_t g = 0; g < G; ++g) {
+                grid.enqueue_values(g, s, slab.p);
+                LSSVM_HIP_CHECK(hipEventRecord(ev[0].e, st));
+                grid.block.enqueue_gather_kmm(slab.p, ld, plan.row0(s), plan.rows(s), dev[g].Kmm.p);
+                LSSVM_HIP_CHECK(hipGetLastError());
+                enqueue_gram(slab.p, ld, cols, plan.rows256(s), max_chunks, part.p, dev[g].St.p, st, q_dev.p != nullptr ? q_dev.p + plan.row0(s) : nullptr);
+                LSSVM_HIP_CHECK(hipEventRecord(ev[1].e, st));
+                LSSVM_HIP_CHECK(hipEventSynchronize(ev[1].e));
+                gram_ms[g] += elapsed_ms(ev[0], ev[1]);
+            }
+        }
+    }
+
+    // ---- per (gamma, cost): the dense steps of fit_reduced_loo (factor 0) or fit_reduced_loo_dev (1); the operand of the cell goes to, or is written on, the device ----
+    LeverageArgs a(m, k, G * S, true, st, G);
+    std::unique_ptr<DenseFit> fit;
+    if (factor == 1) fit = std::make_unique<DenseFit>(m, k, st);
+    std::vector<double> tiles(static_cast<size_t>(ntri) * RG_TILE), St, Kmm(static_cast<size_t>(m) * m), shift(G * m), ybar(a.num_ops * k), Bt(a.op_stride), L, nus(G * S), host_ms(G * S);
+    for (size_t g = 0; g < G; ++g) {
+        LSSVM_HIP_CHECK(hipMemcpyAsync(tiles.data(), dev[g].St.p, tiles.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        LSSVM_HIP_CHECK(hipMemcpyAsync(Kmm.data(), dev[g].Kmm.p, Kmm.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        LSSVM_HIP_CHECK(hipStreamSynchronize(st));
+        unpack_tiles(tiles, cols, St);
+        const double *s_row = &St[static_cast<size_t>(m) * cols];
+        for (int j = 0; j < m; ++j) shift[g * m + j] = s_row[j] / Nd;
+        for (size_t s = 0; s < S; ++s) {
+            const size_t o = g * S + s;
+            const double t_cell = now_ms();
+            if (factor == 1) {
+                double device_ms = 0.0;
+                nus[o] = fit->run(dev[g], St, Kmm, cols, Nd, 1.0 / costs[s], a.Bt.p + o * a.op_stride, a.ldb, betas_out + o * k * m, rhos_out + o * k, dense_out != nullptr ? dense_out + o : nullptr,
+                                  &device_ms);
+                for (int c = 0; c < k; ++c) ybar[o * k + c] = St[static_cast<size_t>(m + 1 + c) * cols + m] / Nd;
+                host_ms[o] = std::max(0.0, now_ms() - t_cell - device_ms);
+            } else {
+                nus[o] = host_operand(St, Kmm, m, k, cols, Nd, costs[s], a.ldb, betas_out + o * k * m, rhos_out + o * k, L, Bt, &ybar[o * k]);
+                host_ms[o] = now_ms() - t_cell;
+                a.upload_operand(o, Bt.data());
+                LSSVM_HIP_CHECK(hipStreamSynchronize(st));  // (Bt is filled again for the next cell)
+            }
+        }
+        dev[g].St.release();  // (the cells of this gamma are done with both)
+        dev[g].Kmm.release();
+    }
+    a.upload_shift(shift.data(), ybar.data());
+
+    // ---- pass 2: the slabs again, the leverage kernel per (gamma, cost) ----
+    a.inv_n = 1.0 / Nd;
+    a.Y = Y;
+    a.w = weights;
+    a.h_out = leverage_out;
+    a.f_out = fitted_out;
+    a.loo_out = loo_out;
+    a.press = press_out;
+    a.errors = loo_errors_out;
+    leverage_pass(lm, slab_rows, a, &grid);
+
+    if (landmarks_out != nullptr) std::copy(lm.begin(), lm.end(), landmarks_out);
+    if (infos != nullptr) {
+        for (size_t o = 0; o < G * S; ++o) {
+            const size_t g = o / S;
+            infos[o] = lssvm_reduced_grid_info{};
+            infos[o].cost = costs[o % S];
+            infos[o].jitter = nus[o];
+            infos[o].max_leverage = a.max_leverage[o];
+            infos[o].landmark_ms = grid.accumulate_ms + grid.values_ms[g];
+            infos[o].gram_ms = gram_ms[g];
+            infos[o].leverage_ms = a.leverage_ms[o];
+            infos[o].host_ms = host_ms[o];
+            infos[o].gamma = gammas[g];
+            infos[o].accumulate_ms = grid.accumulate_ms;
+            infos[o].values_ms = grid.values_ms[g];
+        }
+    }
+}
+
+/* D alone for all N points (a test aid): the slabs of GridSlabs in the library's default size, each downloaded column by column */
+template <typename T>
+void Solver<T>::landmark_acc(const uint64_t *landmarks, uint64_t rank, int product, double *D_out) {
+    LSSVM_REQUIRE(D_out != nullptr, "D_out must not be NULL");
+    LSSVM_REQUIRE(product == 0 || product == 1, "product must be 0 (ordered) or 1 (matrix), but is " + std::to_string(product) + "!");
+    Problem<T> &p = reduced_problem("landmark_acc", true);
+    const size_t N = p.N_;
+    check_reduced_arguments(D_out, 1, rank, 0, N);
+    const int m = static_cast<int>(rank);
+    const std::vector<uint64_t> lm = resolve_landmarks(landmarks, static_cast<size_t>(m), N);
+
+    const SetOnExit<bool> busy = hold_busy();
+    p.activate();
+    hipStream_t st = p.stream();
+    GridSlabs<T> grid(p, lm, nullptr, 0, 0, nullptr, 0, product, st);
+    for (int s = 0; s < grid.plan.slabs; ++s) {
+        grid.enqueue_acc(s);
+        LSSVM_HIP_CHECK(hipMemcpy2DAsync(D_out + grid.plan.row0(s), N * sizeof(double), grid.D.p, grid.plan.ld * sizeof(double), static_cast<size_t>(grid.plan.rows(s)) * sizeof(double),
+                                         static_cast<size_t>(m), hipMemcpyDeviceToHost, st));
+        LSSVM_HIP_CHECK(hipStreamSynchronize(st));
     }
 }
 
@@ -1120,6 +1537,12 @@ template void Solver<float>::fit_reduced_loo_dev(const void *, size_t, uint64_t,
                                                  uint64_t *, lssvm_reduced_loo_info *, lssvm_dense_info *, const double *);
 template void Solver<double>::fit_reduced_loo_dev(const void *, size_t, uint64_t, const uint64_t *, uint64_t, const double *, size_t, double *, double *, double *, double *, double *, double *, uint64_t *,
                                                   uint64_t *, lssvm_reduced_loo_info *, lssvm_dense_info *, const double *);
+template void Solver<float>::fit_reduced_grid(const void *, size_t, const double *, uint64_t, const uint64_t *, uint64_t, const double *, size_t, const double *, size_t, int, int, double *, double *,
+                                              double *, double *, double *, double *, uint64_t *, uint64_t *, lssvm_reduced_grid_info *, lssvm_dense_info *);
+template void Solver<double>::fit_reduced_grid(const void *, size_t, const double *, uint64_t, const uint64_t *, uint64_t, const double *, size_t, const double *, size_t, int, int, double *, double *,
+                                               double *, double *, double *, double *, uint64_t *, uint64_t *, lssvm_reduced_grid_info *, lssvm_dense_info *);
+template void Solver<float>::landmark_acc(const uint64_t *, uint64_t, int, double *);
+template void Solver<double>::landmark_acc(const uint64_t *, uint64_t, int, double *);
 template void Solver<float>::reduced_leverage(uint64_t, const uint64_t *, uint64_t, const double *, const double *, const double *, size_t, double *, double *);
 template void Solver<double>::reduced_leverage(uint64_t, const uint64_t *, uint64_t, const double *, const double *, const double *, size_t, double *, double *);
 template void Solver<float>::time_leverage_kernel(uint64_t, uint64_t, size_t, int, double *, double *);

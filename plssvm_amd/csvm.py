@@ -230,6 +230,43 @@ class CSVM:
         self.last_cg_info = [dict(info, iterations=0) for info in report["infos"]]
         return models, report
 
+    def solve_reduced_grid_systems(self, params, A, Y, rank, gammas, costs, landmarks=None, factor="host", sample_weight=None, product="matrix"):
+        """The fixed-size models of every row of ``Y`` at every ``(gamma, cost)`` of the grid with their leave-one-out report:
+        ``(betas[G, S, k, m], rhos[G, S, k], landmarks[m], report)``.  Boundary of :meth:`fit_reduced_grid`; the MI355X backend implements it."""
+        raise NotImplementedError
+
+    def fit_reduced_grid(self, data: DataSet, rank: int, gammas, costs, landmarks=None, factor: str = "host", sample_weight=None, product: str = "matrix"):
+        """:meth:`fit_reduced_path` for every kernel width of ``gammas`` AND every cost of ``costs`` in one call on one resident problem (no counterpart in the reference;
+        DESIGN.md section 17; rbf and polynomial kernels).  Returns ``(models, report)``: ``models[g][s]`` is an ordinary :class:`Model` whose parameters carry
+        ``gammas[g]`` and ``costs[s]`` -- predict, score, the resident predictors and :meth:`Model.save` take it unchanged.  This object's own cost is ignored; its own
+        gamma only decides how the resident problem holds the data (and selects the landmarks for ``"greedy"`` / ``"rpcholesky"``): give it a gamma from the grid.
+        ``report``: as for :meth:`fit_reduced_path` with a leading gamma axis on every array (``loo[G, S, N]``, ``loo_accuracy[G, S]`` ...), ``gammas``, and
+        ``infos[g][s]``.  ``product="matrix"`` (the default) forms what the gammas share on the fp64 matrix cores, ``"ordered"`` with the loop of
+        :meth:`fit_reduced_path` (then a grid of this object's one gamma returns that call's bits).  ``len(gammas) * len(costs) <= 64``."""
+        _capi.factor_on_device(factor)
+        _capi.product_argument(product)
+        if not data.has_labels():
+            raise InvalidParameterError("No labels given for training! Maybe the data is only usable for prediction?")  # csvm.hpp:298
+        labels = data.labels()
+        if landmarks is not None and not isinstance(landmarks, str):  # (a selection rule's points are checked once they are known)
+            _check_landmark_classes(data, landmarks)  # (before anything is computed)
+        costs = _checked_costs(costs)
+        params = self.params.resolved(data.num_features())
+        betas, rhos, used, report = self.solve_reduced_grid_systems(params, data.data(), data.mapped_labels().reshape(1, -1), rank, gammas, costs, landmarks, product=product,
+                                                                     **_capi.factor_keyword(factor), **_weight_keyword(sample_weight))
+        rows = _check_landmark_classes(data, used)
+        reduced = DataSet(data.data()[rows], [labels[i] for i in rows.tolist()], real_type=data.real_type)
+        models = [[Model(replace(params, gamma=float(gamma), cost=float(cost)), reduced, alpha=np.asarray(betas[g][s][0]).astype(data.real_type), rho=rhos[g][s][0])
+                   for s, cost in enumerate(costs)] for g, gamma in enumerate(report["gammas"])]
+        report = {name: (value[:, :, 0] if name in ("fitted", "loo", "press", "loo_errors") else value) for name, value in report.items()}
+        report["landmarks"] = np.asarray(used)
+        report["loo_accuracy"] = 1.0 - report["loo_errors"].astype(np.float64) / data.num_data_points()
+        if sample_weight is not None:
+            correct = np.sign(report["loo"]) == np.sign(np.asarray(data.mapped_labels(), dtype=np.float64))[None, None, :]
+            report["loo_accuracy"] = np.average(correct, axis=2, weights=np.asarray(sample_weight, dtype=np.float64))
+        self.last_cg_info = [[dict(info, iterations=0) for info in row] for row in report["infos"]]
+        return models, report
+
     def predict(self, model: Model, data: DataSet):
         if model.num_features() != data.num_features():
             raise InvalidParameterError(f"Number of features per data point ({data.num_features()}) must match the number of features per support vector of the "
@@ -411,6 +448,14 @@ class MI355CSVM(CSVM):
             raise InvalidParameterError(f"The reduced model is fitted on one device, but this backend object shards a solve over {'every visible device' if self.use_devices == 0 else self.use_devices}"
                                         f"{'' if self.use_devices == 0 else ' devices'} (num_devices={self.use_devices})!")
         return backend.fit_reduced_loo(params, A, Y, rank, costs, landmarks=landmarks, options=self._options, factor=factor, sample_weight=sample_weight)
+
+    def solve_reduced_grid_systems(self, params, A, Y, rank, gammas, costs, landmarks=None, factor="host", sample_weight=None, product="matrix"):
+        """``backend.fit_reduced_grid`` on device 0: per slab and pass the feature sums once for all gammas, one Gram matrix per gamma, one leverage pass per
+        ``(gamma, cost)``.  A backend object of several devices raises, as :meth:`solve_reduced_systems` does."""
+        if self.use_devices != 1:
+            raise InvalidParameterError(f"The reduced model is fitted on one device, but this backend object shards a solve over {'every visible device' if self.use_devices == 0 else self.use_devices}"
+                                        f"{'' if self.use_devices == 0 else ' devices'} (num_devices={self.use_devices})!")
+        return backend.fit_reduced_grid(params, A, Y, rank, gammas, costs, landmarks=landmarks, options=self._options, factor=factor, sample_weight=sample_weight, product=product)
 
     def _one_device_path(self) -> None:
         if self.use_devices != 1:

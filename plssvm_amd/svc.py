@@ -443,6 +443,61 @@ def fit_reduced_cv_weighted(estimator, X, y, rank, Cs, sample_weight=None, landm
     return _fit_reduced_cv(estimator, X, y, rank, Cs, landmarks, factor, weighted=True, sample_weight=sample_weight)
 
 
+def fit_reduced_grid_cv(estimator, X, y, rank, Cs, gammas, sample_weight=None, landmarks=None, factor="host", product="matrix"):
+    """:func:`fit_reduced_cv_weighted` at every ``C`` of ``Cs`` AND every kernel width of ``gammas`` from one call on one resident problem
+    (:meth:`plssvm_amd.csvm.CSVM.fit_reduced_grid`; rbf and polynomial kernels).  Returns ``(loo_accuracy[G, S], clones[g][s])``: the
+    leave-one-out accuracy over all training points, each predicted by the model refitted without it, and fitted clones that carry ``gamma = gammas[g]`` and
+    ``C = Cs[s]``.  Two classes and one-vs-all follow the rules of :func:`fit_reduced_cv_weighted`; ``class_weight`` is honoured as there
+    (``w_i = sample_weight[i] x class_weight[y[i]]``, the score is the weighted accuracy); with ``sample_weight`` None and ``class_weight`` None the fit is the unweighted
+    one.  ``estimator.C`` is ignored; ``estimator.gamma`` only decides how the problem holds the data -- give it a value from ``gammas``.  ``estimator`` itself stays
+    unfitted.  ``len(gammas) * len(Cs) <= 64``."""
+    _capi.factor_on_device(factor)
+    _capi.product_argument(product)
+    if not isinstance(estimator, SVC):
+        raise InvalidParameterError("estimator must be a plssvm_amd.svc.SVC")
+    X, y = np.asarray(X), np.asarray(y)
+    if X.ndim != 2 or y.ndim != 1 or y.shape[0] != X.shape[0]:
+        raise InvalidParameterError(f"X must be a matrix and y a vector of as many labels as X has rows, but their shapes are {X.shape} and {y.shape}!")
+    Cs = _csvm._checked_costs(Cs)
+    gammas = [float(g) for g in np.asarray(gammas, dtype=np.float64).reshape(-1)]
+    params = estimator._params()
+    classes = np.array(sorted(set(y.tolist())))
+    weighted = sample_weight is not None or estimator.class_weight is not None
+    class_weight, weights = _reduced_point_weights(estimator, classes, y, sample_weight) if weighted else (np.ones(len(classes)), None)
+    weight_keyword = _csvm._weight_keyword(weights)
+    svm = make_csvm(params=params)
+    clones = [[SVC(**{**estimator.get_params(), "C": C, "gamma": g}) for C in Cs] for g in gammas]
+    if len(classes) > 2:
+        Xr = np.ascontiguousarray(X, dtype=estimator.real_type)
+        resolved = params.resolved(Xr.shape[1])
+        betas, rhos, used, report = svm.solve_reduced_grid_systems(resolved, Xr, _multiclass.one_vs_all_targets(classes, y, Xr.dtype), rank, gammas, Cs, landmarks, product=product,
+                                                                   **_capi.factor_keyword(factor), **weight_keyword)
+        rows = np.asarray(used).astype(np.int64)
+        scores = np.array([[float(np.average(classes[np.argmax(report["loo"][g][s], axis=0)] == y, weights=weights)) for s in range(len(Cs))] for g in range(len(gammas))])
+        for g, gamma in enumerate(gammas):
+            for s, C in enumerate(Cs):
+                clone = clones[g][s]
+                cell = Parameter(kernel_type=resolved.kernel_type, degree=resolved.degree, gamma=gamma, coef0=resolved.coef0, cost=C)
+                infos = [dict(report["infos"][g][s], iterations=0) for _ in classes]
+                model = _multiclass.OneVsAllModel(cell, classes, np.ascontiguousarray(Xr[rows]), np.asarray(betas[g][s]).astype(Xr.dtype), np.asarray(rhos[g][s]).astype(Xr.dtype), infos)
+                nonzero = np.any(model.alpha != 0, axis=0)
+                clone._svm, clone._model = make_csvm(params=cell), model
+                clone._fit = {
+                    "classes_": classes, "class_weight_": class_weight, "fit_status_": 0, "n_features_in_": int(X.shape[1]), "shape_fit_": tuple(int(v) for v in X.shape),
+                    "n_iter_": np.zeros(len(classes), dtype=np.int64), "support_": rows.astype(np.int32), "support_vectors_": model.support_vectors,
+                    "n_support_": np.array([np.count_nonzero(nonzero & (y[rows] == c)) for c in classes], dtype=np.int32), "dual_coef_": model.alpha, "intercept_": -model.rho,
+                }
+        return scores, clones
+    data = DataSet(X, y.tolist(), real_type=estimator.real_type)
+    models, report = svm.fit_reduced_grid(data, rank, gammas, Cs, landmarks, product=product, **_capi.factor_keyword(factor), **weight_keyword)
+    for g in range(len(gammas)):
+        for s in range(len(Cs)):
+            model = models[g][s]
+            clones[g][s]._set_binary_fit(make_csvm(params=model.params), model, model.data, X, y, class_weight, None, 0)
+            clones[g][s]._fit["support_"] = np.asarray(report["landmarks"]).astype(np.int32)
+    return np.asarray(report["loo_accuracy"], dtype=np.float64), clones
+
+
 def cost_path_scores(estimator, X, y, Cs, X_val, y_val):
     """The validation accuracy of a TWO-class ``estimator`` at every ``C`` of ``Cs``: one cost path (:func:`fit_cost_path`), then ONE resident predictor over all the
     models -- they share their support vectors, so the predictor takes their weight vectors two per pass over the Gram tiles.  Returns ``(scores[m], fitted clones)``."""
