@@ -704,6 +704,58 @@ int lssvm_mi355_fit_reduced_grid_f64(const lssvm_params *params, const double *X
                                      uint64_t *loo_errors_out, uint64_t *landmarks_out, lssvm_reduced_grid_info *infos, lssvm_dense_info *dense,
                                      const lssvm_mi355_options *options);
 
+/* The leave-one-out scores above for EVERY PREFIX RANK of one fit, over a grid of costs, in one call (opt-in).  The landmark list is ordered (both
+ * selection rules deliver their pivots in a meaningful order); for a prefix length r, 1 <= r <= rank = m, the model on the first r landmarks needs nothing the rank-m fit
+ * has not formed: S, s, K_mm, t_c and therefore M = S - s s^T / W + sigma K_mm restricted to the first r landmarks are the leading r x r blocks of the rank-m quantities,
+ * the Cholesky factor of a leading block is the leading block of the factor (L_r = L[:r, :r]; likewise V = L^-1 and z_c = L^-1 (t_c - s eta_c / W): z_c^(r) = z_c[:r]),
+ * and with u_i = V (phi_i - s / W)
+ *   h_ii^(r) = w_i (1 / W + sum_{j<r} u_ij^2),   f_c^(r)(x_i) = sum_{j<r} u_ij z_cj + eta_c / W,   beta_c^(r) = L_r^-T z_c[:r],   b_c^(r) = (eta_c - s[:r]^T beta_c^(r)) / W,
+ * and the leave-one-out identity y - (y - f) / (1 - h) stays exact for every prefix model (each is the same linear smoother on fewer columns).  One Gram pass, one
+ * factorisation per cost and one leverage pass per cost score the whole (cost, rank) grid: the leverage kernel takes the running sums of u^2 and u z_c out of its
+ * accumulators at the checkpoints `ranks`.
+ * THE JITTER differs from separate fits on landmarks[:r]: every prefix model of a cost uses the nu of the FULL rank at that cost -- eps64 trace(M) over all m landmarks,
+ * tenfold per failed factorisation as above (also where the failing pivot lies beyond the largest checkpoint) -- which is no smaller than the prefix's own; it is reported.
+ * ranks: 1 <= num_ranks <= 16 checkpoints r_0 < r_1 < ..., each in [1, rank]; num_ranks x num_costs <= 64 (the operands of all costs stay on the device during pass 2,
+ * the bound of the grid call).  factor: 0 = the dense steps on the host -- the very code of lssvm_mi355_problem_fit_reduced_loo per cost, then per checkpoint the back
+ * substitution L_r^T beta = z[:r] on the leading block: at r_q == rank betas and rhos have the bits of lssvm_mi355_problem_fit_reduced_loo_weighted at that cost with
+ * factor 0; 1 = on the device: L, V and z stay there, one workgroup per (checkpoint, right-hand side) forms beta^(r) = V[:r, :r]^T z[:r] and rho with sums in a fixed
+ * order, and only betas, rhos, the cond_hints and the status word come back.
+ * Outputs, all double: betas_out num_costs x num_ranks x num_rhs x rank, the entries from r_q on are 0; rhos_out, press_out, loo_errors_out num_costs x num_ranks x
+ * num_rhs (formed as the leave-one-out call forms them: weighted, summed in row order on the host); leverage_out num_costs x num_ranks x N; fitted_out, loo_out
+ * num_costs x num_ranks x num_rhs x N; infos num_costs x num_ranks; dense (ignored for factor 0) num_costs.  press_out, loo_errors_out, leverage_out, fitted_out, loo_out,
+ * landmarks_out, infos and dense may be NULL.  weights may be NULL.
+ * Deterministic, no atomics; the order of every sum depends on rank and on that checkpoint's r_q only: the same bits for the same arguments; a checkpoint of a list has
+ * the bits of the call with that checkpoint alone (at the same rank and landmarks); a cost has the bits of the call with that cost alone; column c has the bits of the
+ * call with that right-hand side alone.  The problem is left as it was and keeps its preconditioner.
+ * LSSVM_ERR_INVALID_ARGUMENT, all before a device is touched: the refusals of lssvm_mi355_problem_fit_reduced_loo_weighted; a NULL or empty rank list, more than 16
+ * checkpoints, one that is 0 or above rank, a list that is not strictly ascending; num_ranks x num_costs > 64. */
+typedef struct lssvm_reduced_rank_info {
+    double   cost;
+    uint64_t rank;          /* r_q */
+    double   jitter;        /* nu of this cost: the FULL rank's */
+    double   max_leverage;  /* the largest h_ii of this (cost, checkpoint) */
+    double   landmark_ms;   /* as lssvm_reduced_loo_info (the same figure in every record) */
+    double   gram_ms;       /* as lssvm_reduced_loo_info (the same figure in every record) */
+    double   leverage_ms;   /* device time of this cost's prefix leverage kernel, all slabs and all checkpoints (the same figure for every checkpoint of a cost) */
+    double   host_ms;       /* this cost's dense steps on the host (factor 1: what is left on the host) */
+    double   cond_hint;     /* max_j L_jj^2 / min_j L_jj^2 over j < r_q, read off the factor: a cheap LOWER BOUND of cond(M_r + nu I), not the condition number */
+} lssvm_reduced_rank_info;
+int lssvm_mi355_problem_fit_reduced_rank_path(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, const double *weights /* N, or NULL */, uint64_t rank,
+                                              const uint64_t *landmarks, uint64_t slab_rows, const uint64_t *ranks, size_t num_ranks, const double *costs, size_t num_costs,
+                                              int factor, double *betas_out, double *rhos_out, double *press_out, uint64_t *loo_errors_out, double *leverage_out,
+                                              double *fitted_out, double *loo_out, uint64_t *landmarks_out, lssvm_reduced_rank_info *infos, lssvm_dense_info *dense);
+/* one-shot: create the problem on device 0 from `params` (as lssvm_mi355_solve_*), fit, destroy it */
+int lssvm_mi355_fit_reduced_rank_path_f32(const lssvm_params *params, const float *X, size_t num_points, size_t num_features, const float *Y, size_t num_rhs,
+                                          const double *weights, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const uint64_t *ranks, size_t num_ranks,
+                                          const double *costs, size_t num_costs, int factor, double *betas_out, double *rhos_out, double *press_out, uint64_t *loo_errors_out,
+                                          double *leverage_out, double *fitted_out, double *loo_out, uint64_t *landmarks_out, lssvm_reduced_rank_info *infos,
+                                          lssvm_dense_info *dense, const lssvm_mi355_options *options);
+int lssvm_mi355_fit_reduced_rank_path_f64(const lssvm_params *params, const double *X, size_t num_points, size_t num_features, const double *Y, size_t num_rhs,
+                                          const double *weights, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const uint64_t *ranks, size_t num_ranks,
+                                          const double *costs, size_t num_costs, int factor, double *betas_out, double *rhos_out, double *press_out, uint64_t *loo_errors_out,
+                                          double *leverage_out, double *fitted_out, double *loo_out, uint64_t *landmarks_out, lssvm_reduced_rank_info *infos,
+                                          lssvm_dense_info *dense, const lssvm_mi355_options *options);
+
 /* Landmark selection on a resident problem (opt-in): the pivots of a partial Cholesky factorisation of the kernel matrix, chosen greedily or
  * at random in proportion to the residual diagonal (randomly pivoted Cholesky).  The result is a list of point indices for the `landmarks` argument of the entry points
  * above; nothing else changes, and nothing selects it automatically.  Neither rule dominates the other or the fixed shuffle (README.md has the rows of all three kinds).

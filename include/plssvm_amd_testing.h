@@ -65,6 +65,18 @@ int lssvm_mi355_problem_landmark_gram_weighted(lssvm_mi355_problem *p, const voi
 int lssvm_mi355_problem_reduced_leverage(lssvm_mi355_problem *p, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *V, const double *shift,
                                          const double *B_extra, size_t k, double *h_out, double *f_out);
 
+/* The operator of the rank path alone (lssvm_mi355_problem_fit_reduced_rank_path) on the caller's operands, apart from any conditioning; it mirrors
+ * lssvm_mi355_problem_reduced_leverage: for every point i and checkpoint q, with phic_i = phi_i - shift,
+ *   h_out[q * N + i] = sum_{j < r_q} (V phic_i)_j^2,     f_out[(q * k + c) * N + i] = sum_{j < r_q} (V phic_i)_j Z[c][j]
+ * V: rank x rank row major, only its LOWER triangle counts, as there.  Z: k x rank row major (NULL with k = 0; then f_out may be NULL).  ranks: 1 <= num_ranks <= 16
+ * checkpoints, strictly ascending, each in [1, rank].  Arguments and refusals as for lssvm_mi355_problem_reduced_leverage, and a bad rank list. */
+int lssvm_mi355_problem_reduced_leverage_prefix(lssvm_mi355_problem *p, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *V, const double *shift,
+                                                const double *Z, size_t k, const uint64_t *ranks, size_t num_ranks, double *h_out, double *f_out);
+/* Measurement aid of tests/tools/reduced_rank_path_timing.py, beside lssvm_mi355_problem_time_leverage_kernel and on the same slab and operands (an identity V, k rows of
+ * ones for Z): the prefix leverage kernel with the checkpoints `ranks` and its leave-one-out outputs, prefix_ms_out[r]: device time of repeat r after one untimed run. */
+int lssvm_mi355_problem_time_leverage_prefix_kernel(lssvm_mi355_problem *p, uint64_t rank, uint64_t slab_rows, size_t k, const uint64_t *ranks, size_t num_ranks, int repeats,
+                                                    double *prefix_ms_out);
+
 /* The operator of the (gamma, cost) grid alone (lssvm_mi355_problem_fit_reduced_grid), apart from any fit: D_out[l * N + i] = what the kernel value
  * of (point i, landmark l) is made from on the data as the problem holds it -- sum_f (a_f - b_f)^2 (rbf) or sum_f a_f b_f (polynomial, linear) -- for all N points, rank x N
  * doubles, in slabs of the library's default size.  product: 0 = the ordered loop of the landmark block, 1 = the dot products on the matrix cores (and the norm expansion

@@ -50,6 +50,8 @@ EXPORTED_SYMBOLS = [
     "lssvm_mi355_problem_fit_reduced_loo_weighted", "lssvm_mi355_fit_reduced_loo_weighted_f32", "lssvm_mi355_fit_reduced_loo_weighted_f64",
     "lssvm_mi355_problem_landmark_gram_weighted",
     "lssvm_mi355_problem_fit_reduced_grid", "lssvm_mi355_fit_reduced_grid_f32", "lssvm_mi355_fit_reduced_grid_f64", "lssvm_mi355_problem_landmark_acc",
+    "lssvm_mi355_problem_fit_reduced_rank_path", "lssvm_mi355_fit_reduced_rank_path_f32", "lssvm_mi355_fit_reduced_rank_path_f64",
+    "lssvm_mi355_problem_reduced_leverage_prefix", "lssvm_mi355_problem_time_leverage_prefix_kernel",
     "lssvm_mi355_dense_cholesky", "lssvm_mi355_dense_solve", "lssvm_mi355_dense_invert_lower",
     "lssvm_mi355_problem_select_landmarks", "lssvm_mi355_select_landmarks_f32", "lssvm_mi355_select_landmarks_f64",
     "lssvm_mi355_cg_begin", "lssvm_mi355_cg_step", "lssvm_mi355_cg_finish", "lssvm_mi355_problem_synchronize", "lssvm_mi355_problem_info",
@@ -413,6 +415,40 @@ def reduced_grid_entry(name: str):
             # Y, num_rhs, weights, rank, landmarks, slab_rows, gammas, num_gammas, costs, num_costs, factor, product, then the outputs of the leave-one-out call
             common = [C.c_void_p, C.c_size_t, dp, C.c_uint64, up, C.c_uint64, dp, C.c_size_t, dp, C.c_size_t, C.c_int, C.c_int,
                       dp, dp, dp, dp, dp, dp, up, up, C.POINTER(LssvmReducedGridInfo), C.POINTER(LssvmDenseInfo)]
+            if "problem" in name:
+                fn.argtypes = [C.c_void_p] + common
+            else:
+                fn.argtypes = [C.POINTER(LssvmParams), C.c_void_p, C.c_size_t, C.c_size_t] + common + [C.c_void_p]
+        fn.restype = C.c_int
+    return fn
+
+
+class LssvmReducedRankInfo(C.Structure):
+    """``lssvm_reduced_rank_info``: one (cost, checkpoint) cell of ``lssvm_mi355_problem_fit_reduced_rank_path``."""
+    _fields_ = [("cost", C.c_double), ("rank", C.c_uint64), ("jitter", C.c_double), ("max_leverage", C.c_double), ("landmark_ms", C.c_double), ("gram_ms", C.c_double),
+                ("leverage_ms", C.c_double), ("host_ms", C.c_double), ("cond_hint", C.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+REDUCED_RANK_PATH_MAX_RANKS = 16
+
+
+def reduced_rank_path_entry(name: str):
+    """The entry points of the rank path of the fixed-size model (``lssvm_mi355_problem_fit_reduced_rank_path``, ``lssvm_mi355_fit_reduced_rank_path_f32 / _f64`` and the
+    test aids ``lssvm_mi355_problem_reduced_leverage_prefix`` / ``_time_leverage_prefix_kernel``) with their argument types.  Bound at the first call."""
+    fn = getattr(lib, name)
+    if fn.argtypes is None:
+        dp, up = C.POINTER(C.c_double), C.POINTER(C.c_uint64)
+        if name == "lssvm_mi355_problem_reduced_leverage_prefix":
+            fn.argtypes = [C.c_void_p, C.c_uint64, up, C.c_uint64, dp, dp, dp, C.c_size_t, up, C.c_size_t, dp, dp]
+        elif name == "lssvm_mi355_problem_time_leverage_prefix_kernel":
+            fn.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_size_t, up, C.c_size_t, C.c_int, dp]
+        else:
+            # Y, num_rhs, weights, rank, landmarks, slab_rows, ranks, num_ranks, costs, num_costs, factor, betas, rhos, press, loo_errors, leverage, fitted, loo, landmarks, infos, dense
+            common = [C.c_void_p, C.c_size_t, dp, C.c_uint64, up, C.c_uint64, up, C.c_size_t, dp, C.c_size_t, C.c_int,
+                      dp, dp, dp, up, dp, dp, dp, up, C.POINTER(LssvmReducedRankInfo), C.POINTER(LssvmDenseInfo)]
             if "problem" in name:
                 fn.argtypes = [C.c_void_p] + common
             else:

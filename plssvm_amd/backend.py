@@ -519,6 +519,73 @@ def fit_reduced_grid(params: Parameter, A, Y, rank: int, gammas, costs, landmark
     return _reduced_grid_call(fn, (C.byref(ps), ptr(A), N, d), Y2, single, N, rank, lm_ptr, slab_rows, gammas, costs, on_device, code, w, tail=(options_ptr(options),))
 
 
+def _reduced_rank_list(ranks, rank: int, num_costs: int):
+    """The checkpoints of the rank path, checked as the library checks them."""
+    try:
+        arr = np.asarray(ranks)
+        if arr.size and arr.dtype.kind not in "iu":
+            raise TypeError
+        if arr.size and int(arr.min()) < 0:
+            raise InvalidParameterError(f"Every checkpoint must lie in [1, {rank}]!")
+        arr = np.ascontiguousarray(arr, dtype=np.uint64)
+    except (TypeError, ValueError):
+        raise InvalidParameterError("The checkpoints must be a list of integers!") from None
+    if arr.ndim != 1 or not 1 <= arr.size <= _capi.REDUCED_RANK_PATH_MAX_RANKS:
+        raise InvalidParameterError(f"The rank path takes between 1 and {_capi.REDUCED_RANK_PATH_MAX_RANKS} checkpoints, but got {arr.size if arr.ndim == 1 else arr.shape}!")
+    if arr.size * num_costs > _capi.REDUCED_GRID_MAX_CELLS:
+        raise InvalidParameterError(f"The rank path takes at most {_capi.REDUCED_GRID_MAX_CELLS} (cost, checkpoint) cells, but got {num_costs} x {arr.size}!")
+    if not (np.all(arr >= 1) and np.all(arr <= rank)):
+        raise InvalidParameterError(f"Every checkpoint must lie in [1, {rank}]!")
+    if np.any(arr[1:] <= arr[:-1]):
+        raise InvalidParameterError("The checkpoints must be strictly ascending!")
+    return arr
+
+
+def _reduced_rank_path_call(fn, head, Y2, single: bool, N: int, rank: int, lm_ptr, slab_rows: int, ranks, costs, on_device: bool, weights, tail=()):
+    k, R, S = Y2.shape[0], ranks.size, costs.size
+    betas, rhos = np.zeros((S, R, k, rank)), np.zeros((S, R, k))
+    leverage, fitted, loo = np.zeros((S, R, N)), np.zeros((S, R, k, N)), np.zeros((S, R, k, N))
+    press, errors, used = np.zeros((S, R, k)), np.zeros((S, R, k), dtype=np.uint64), np.zeros(rank, dtype=np.uint64)
+    infos = (_capi.LssvmReducedRankInfo * (S * R))()
+    dense = (_capi.LssvmDenseInfo * S)()
+    dp, up = C.POINTER(C.c_double), C.POINTER(C.c_uint64)
+    check(fn(*head, ptr(Y2), k, _capi.weights_ptr(weights), rank, lm_ptr, slab_rows, ranks.ctypes.data_as(up), R, costs.ctypes.data_as(dp), S, int(on_device),
+             betas.ctypes.data_as(dp), rhos.ctypes.data_as(dp), press.ctypes.data_as(dp), errors.ctypes.data_as(up), leverage.ctypes.data_as(dp), fitted.ctypes.data_as(dp),
+             loo.ctypes.data_as(dp), used.ctypes.data_as(up), infos, dense, *tail))
+    cells = [[dict(dense[s].as_dict(), **infos[s * R + q].as_dict()) if on_device else infos[s * R + q].as_dict() for q in range(R)] for s in range(S)]
+    report = {"costs": costs.copy(), "ranks": ranks.astype(np.int64), "leverage": leverage, "fitted": fitted[:, :, 0] if single else fitted, "loo": loo[:, :, 0] if single else loo,
+              "press": press[:, :, 0] if single else press, "loo_errors": errors[:, :, 0] if single else errors,
+              "max_leverage": np.array([[c["max_leverage"] for c in row] for row in cells]), "jitter": np.array([row[0]["jitter"] for row in cells]),
+              "cond_hint": np.array([[c["cond_hint"] for c in row] for row in cells]), "infos": cells}
+    return (betas[:, :, 0], rhos[:, :, 0], used, report) if single else (betas, rhos, used, report)
+
+
+def fit_reduced_rank_path(params: Parameter, A, Y, rank: int, ranks, costs, landmarks=None, slab_rows: int = 0, options: Options | None = None, factor: str = "host",
+                          sample_weight=None):
+    """:func:`fit_reduced_loo` for EVERY PREFIX RANK of ``ranks`` and every cost of ``costs`` from one fit at ``rank`` (``lssvm_mi355_fit_reduced_rank_path_*``; DESIGN.md
+    section 18).  The landmark list is ordered; the model on its first ``r`` entries needs only leading blocks of what the rank-``rank`` fit forms, and its leverages and
+    fitted values are prefix sums along the rows of the product the leverage kernel forms anyway: one Gram pass, one factorisation per cost and one leverage pass per
+    cost score the whole (cost, rank) grid.  ``ranks``: 1 to 16 strictly ascending checkpoints in ``[1, rank]``; ``len(ranks) * len(costs) <= 64``.  Every prefix model of
+    a cost uses the jitter of the FULL rank at that cost (reported), which is no smaller than the one a separate fit on ``landmarks[:r]`` would take.
+    Returns ``(betas[S, R, k, rank], rhos[S, R, k], landmarks, report)`` (the ``k`` axis dropped for a single right-hand side ``(N,)``); ``betas[s, q]`` is zero from
+    ``ranks[q]`` on.  ``report`` as for :func:`fit_reduced_loo` with a rank axis behind the cost axis on every array, ``ranks``, ``jitter[S]``, ``cond_hint[S, R]`` (a
+    cheap lower bound of the condition number, off the factor's diagonal) and ``infos[s][q]`` (``lssvm_reduced_rank_info`` dicts).  ``factor`` and ``sample_weight``: as
+    for :func:`fit_reduced_loo`; with ``factor="host"``, ``betas[s, q]`` / ``rhos[s, q]`` at ``ranks[q] == rank`` have the bits of that call."""
+    on_device = _capi.factor_on_device(factor)
+    A = _as_matrix(A)
+    N, d = A.shape
+    w = _reduced_weights(sample_weight, N)
+    if isinstance(landmarks, str):  # a selection rule (:func:`select_landmarks`): one resident problem selects and fits
+        with ResidentProblem(params, A, options=options) as prob:
+            return prob.fit_reduced_rank_path(Y, rank, ranks, costs, landmarks, slab_rows, factor=factor, sample_weight=w)
+    Y2, single, rank, _, lm_ptr, slab_rows = _reduced_arguments(Y, N, A.dtype, rank, landmarks, slab_rows)
+    costs = _reduced_loo_costs(costs)
+    ranks = _reduced_rank_list(ranks, rank, costs.size)
+    ps = _params_struct(params, d)
+    fn = _capi.reduced_rank_path_entry(f"lssvm_mi355_fit_reduced_rank_path_{suffix_of(A.dtype)}")
+    return _reduced_rank_path_call(fn, (C.byref(ps), ptr(A), N, d), Y2, single, N, rank, lm_ptr, slab_rows, ranks, costs, on_device, w, tail=(options_ptr(options),))
+
+
 def generate_q(params: Parameter, data, options: Options | None = None):
     data = _as_matrix(data)
     N, d = data.shape
@@ -976,6 +1043,49 @@ class ResidentProblem:
         check(_capi.reduced_loo_entry("lssvm_mi355_problem_reduced_leverage")(self._h, rank, lm_ptr, slab_rows, V.ctypes.data_as(dp), shift.ctypes.data_as(dp),
                                                                                  extra.ctypes.data_as(dp) if k else None, k, h.ctypes.data_as(dp), f.ctypes.data_as(dp) if k else None))
         return h, f
+
+    def fit_reduced_rank_path(self, Y, rank: int, ranks, costs, landmarks=None, slab_rows: int = 0, factor: str = "host", sample_weight=None):
+        """:func:`fit_reduced_rank_path` on this resident problem (``lssvm_mi355_problem_fit_reduced_rank_path``): the leave-one-out scores of every prefix rank of
+        ``ranks`` at every cost of ``costs`` from one fit at ``rank``.  The problem's own cost is ignored; the problem is left as it was and keeps its preconditioner.
+        Refused where :meth:`fit_reduced` is."""
+        on_device = _capi.factor_on_device(factor)
+        w = _reduced_weights(sample_weight, self.num_points)
+        Y2, single, rank, _, lm_ptr, slab_rows = _reduced_arguments(Y, self.num_points, self.dtype, rank, self._selected(rank, landmarks), slab_rows)
+        costs = _reduced_loo_costs(costs)
+        ranks = _reduced_rank_list(ranks, rank, costs.size)
+        return _reduced_rank_path_call(_capi.reduced_rank_path_entry("lssvm_mi355_problem_fit_reduced_rank_path"), (self._h,), Y2, single, self.num_points, rank, lm_ptr, slab_rows,
+                                       ranks, costs, on_device, w)
+
+    def reduced_leverage_prefix(self, V, shift, ranks, Z=None, landmarks=None, slab_rows: int = 0):
+        """The operator of :meth:`fit_reduced_rank_path` alone on the caller's operands (a test aid, ``lssvm_mi355_problem_reduced_leverage_prefix``): with
+        ``u_i = V (phi_i - shift)`` for the LOWER triangle of ``V``, ``h[q, i] = sum_{j < ranks[q]} u_ij^2`` and ``f[q, c, i] = sum_{j < ranks[q]} u_ij Z[c, j]``
+        (``Z``: k x rank or None).  Returns ``(h[R, N], f[R, k, N])``, float64."""
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        if V.ndim != 2 or V.shape[0] != V.shape[1]:
+            raise InvalidParameterError(f"V must be a square matrix, but its shape is {V.shape}!")
+        rank = V.shape[0]
+        _, _, rank, _, lm_ptr, slab_rows = _reduced_arguments(np.zeros(self.num_points, dtype=self.dtype), self.num_points, self.dtype, rank if landmarks is None else None, landmarks, slab_rows)
+        shift = np.ascontiguousarray(shift, dtype=np.float64)
+        Z = np.zeros((0, rank)) if Z is None else np.ascontiguousarray(Z, dtype=np.float64)
+        if V.shape[0] != rank or shift.shape != (rank,) or Z.ndim != 2 or Z.shape[1] != rank:
+            raise InvalidParameterError(f"V and shift must have {rank} rows and Z {rank} columns, but their shapes are {V.shape}, {shift.shape} and {Z.shape}!")
+        ranks = _reduced_rank_list(ranks, rank, 1)
+        k, R = Z.shape[0], ranks.size
+        h, f = np.zeros((R, self.num_points)), np.zeros((R, k, self.num_points))
+        dp = C.POINTER(C.c_double)
+        check(_capi.reduced_rank_path_entry("lssvm_mi355_problem_reduced_leverage_prefix")(self._h, rank, lm_ptr, slab_rows, V.ctypes.data_as(dp), shift.ctypes.data_as(dp),
+                                                                                            Z.ctypes.data_as(dp) if k else None, k, ranks.ctypes.data_as(C.POINTER(C.c_uint64)), R,
+                                                                                            h.ctypes.data_as(dp), f.ctypes.data_as(dp) if k else None))
+        return h, f
+
+    def time_leverage_prefix_kernel(self, rank: int, ranks, k: int = 1, slab_rows: int = 0, repeats: int = 10):
+        """A measurement aid (``lssvm_mi355_problem_time_leverage_prefix_kernel``): on the slab and operands of :meth:`time_leverage_kernel`, the prefix leverage kernel of
+        :meth:`fit_reduced_rank_path` with the checkpoints ``ranks``: ``prefix_ms[repeats]``."""
+        ranks = _reduced_rank_list(ranks, int(rank), 1)
+        out = np.zeros(int(repeats))
+        check(_capi.reduced_rank_path_entry("lssvm_mi355_problem_time_leverage_prefix_kernel")(self._h, int(rank), int(slab_rows), int(k), ranks.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                                                                ranks.size, int(repeats), out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
 
     def time_leverage_kernel(self, rank: int, k: int = 1, slab_rows: int = 0, repeats: int = 10):
         """A measurement aid (``lssvm_mi355_problem_time_leverage_kernel``): on one slab of this problem, the Gram kernels of :meth:`fit_reduced` and the leverage kernel of

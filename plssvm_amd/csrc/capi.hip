@@ -283,6 +283,26 @@ void fit_reduced_grid_one_shot(const lssvm_params *params, const T *X, size_t N,
                           press_out, loo_errors_out, landmarks_out, infos, dense);
 }
 
+/* lssvm_mi355_fit_reduced_rank_path_*: likewise */
+template <typename T>
+void fit_reduced_rank_path_one_shot(const lssvm_params *params, const T *X, size_t N, size_t d, const T *Y, size_t num_rhs, const double *weights, uint64_t rank, const uint64_t *landmarks,
+                                    uint64_t slab_rows, const uint64_t *ranks, size_t num_ranks, const double *costs, size_t num_costs, int factor, double *betas_out, double *rhos_out,
+                                    double *press_out, uint64_t *loo_errors_out, double *leverage_out, double *fitted_out, double *loo_out, uint64_t *landmarks_out,
+                                    lssvm_reduced_rank_info *infos, lssvm_dense_info *dense, const lssvm_mi355_options *options) {
+    lssvm::check_reduced_factor(factor);
+    lssvm::check_params(params);
+    check_data(X, N, d);
+    lssvm::check_reduced_arguments(Y, num_rhs, rank, slab_rows, N);
+    lssvm::check_reduced_loo_costs(costs, num_costs);
+    lssvm::check_reduced_rank_list(ranks, num_ranks, rank, num_costs);
+    LSSVM_REQUIRE(betas_out != nullptr && rhos_out != nullptr, "betas_out / rhos_out must not be NULL");
+    if (landmarks != nullptr) (void) lssvm::resolve_landmarks(landmarks, static_cast<size_t>(rank), N);
+    if (weights != nullptr) (void) lssvm::check_reduced_weights(weights, N);
+    lssvm::Solver<T> prob = device0_solver<T>(options, *params, X, N, d);
+    prob.fit_reduced_rank_path(Y, num_rhs, weights, rank, landmarks, slab_rows, ranks, num_ranks, costs, num_costs, factor, betas_out, rhos_out, press_out, loo_errors_out, leverage_out,
+                               fitted_out, loo_out, landmarks_out, infos, dense);
+}
+
 /* lssvm_mi355_select_landmarks_*: likewise */
 template <typename T>
 void select_landmarks_one_shot(const lssvm_params *params, const T *X, size_t N, size_t d, uint64_t rank, int method, uint64_t pool, uint64_t seed, double tol, uint64_t *landmarks_out,
@@ -960,6 +980,58 @@ int lssvm_mi355_fit_reduced_grid_f64(const lssvm_params *params, const double *X
     return guarded([&] {
         fit_reduced_grid_one_shot<double>(params, X, num_points, num_features, Y, num_rhs, weights, rank, landmarks, slab_rows, gammas, num_gammas, costs, num_costs, factor, product, betas_out,
                                           rhos_out, leverage_out, fitted_out, loo_out, press_out, loo_errors_out, landmarks_out, infos, dense, options);
+    });
+}
+/* every prefix rank of one fit: the checks of the weighted leave-one-out form in their order, then the rank list */
+static_assert(sizeof(lssvm_reduced_rank_info) == 72, "lssvm_reduced_rank_info changed: plssvm_amd/_capi.py (LssvmReducedRankInfo) changes with it");
+int lssvm_mi355_problem_fit_reduced_rank_path(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, const double *weights, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows,
+                                              const uint64_t *ranks, size_t num_ranks, const double *costs, size_t num_costs, int factor, double *betas_out, double *rhos_out,
+                                              double *press_out, uint64_t *loo_errors_out, double *leverage_out, double *fitted_out, double *loo_out, uint64_t *landmarks_out,
+                                              lssvm_reduced_rank_info *infos, lssvm_dense_info *dense) {
+    return guarded([&] {
+        LSSVM_REQUIRE(p != nullptr, "problem handle must not be NULL");
+        lssvm::check_reduced_arguments(Y, num_rhs, rank, slab_rows, 0);
+        lssvm::check_reduced_loo_costs(costs, num_costs);
+        LSSVM_REQUIRE(betas_out != nullptr && rhos_out != nullptr, "betas_out / rhos_out must not be NULL");
+        lssvm::check_reduced_factor(factor);
+        lssvm::check_reduced_rank_list(ranks, num_ranks, rank, num_costs);
+        impl_of(p)->fit_reduced_rank_path(Y, num_rhs, weights, rank, landmarks, slab_rows, ranks, num_ranks, costs, num_costs, factor, betas_out, rhos_out, press_out, loo_errors_out,
+                                          leverage_out, fitted_out, loo_out, landmarks_out, infos, dense);
+    });
+}
+int lssvm_mi355_fit_reduced_rank_path_f32(const lssvm_params *params, const float *X, size_t num_points, size_t num_features, const float *Y, size_t num_rhs, const double *weights,
+                                          uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const uint64_t *ranks, size_t num_ranks, const double *costs, size_t num_costs,
+                                          int factor, double *betas_out, double *rhos_out, double *press_out, uint64_t *loo_errors_out, double *leverage_out, double *fitted_out,
+                                          double *loo_out, uint64_t *landmarks_out, lssvm_reduced_rank_info *infos, lssvm_dense_info *dense, const lssvm_mi355_options *options) {
+    return guarded([&] {
+        fit_reduced_rank_path_one_shot<float>(params, X, num_points, num_features, Y, num_rhs, weights, rank, landmarks, slab_rows, ranks, num_ranks, costs, num_costs, factor, betas_out,
+                                              rhos_out, press_out, loo_errors_out, leverage_out, fitted_out, loo_out, landmarks_out, infos, dense, options);
+    });
+}
+int lssvm_mi355_fit_reduced_rank_path_f64(const lssvm_params *params, const double *X, size_t num_points, size_t num_features, const double *Y, size_t num_rhs, const double *weights,
+                                          uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const uint64_t *ranks, size_t num_ranks, const double *costs, size_t num_costs,
+                                          int factor, double *betas_out, double *rhos_out, double *press_out, uint64_t *loo_errors_out, double *leverage_out, double *fitted_out,
+                                          double *loo_out, uint64_t *landmarks_out, lssvm_reduced_rank_info *infos, lssvm_dense_info *dense, const lssvm_mi355_options *options) {
+    return guarded([&] {
+        fit_reduced_rank_path_one_shot<double>(params, X, num_points, num_features, Y, num_rhs, weights, rank, landmarks, slab_rows, ranks, num_ranks, costs, num_costs, factor, betas_out,
+                                               rhos_out, press_out, loo_errors_out, leverage_out, fitted_out, loo_out, landmarks_out, infos, dense, options);
+    });
+}
+int lssvm_mi355_problem_reduced_leverage_prefix(lssvm_mi355_problem *p, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *V, const double *shift, const double *Z,
+                                                size_t k, const uint64_t *ranks, size_t num_ranks, double *h_out, double *f_out) {
+    return guarded([&] {
+        LSSVM_REQUIRE(p != nullptr, "problem handle must not be NULL");
+        LSSVM_REQUIRE(V != nullptr && shift != nullptr && h_out != nullptr, "V / shift / h_out must not be NULL");
+        lssvm::check_reduced_arguments(V, 1, rank, slab_rows, 0);
+        lssvm::check_reduced_rank_list(ranks, num_ranks, rank, 1);
+        impl_of(p)->reduced_leverage_prefix(rank, landmarks, slab_rows, V, shift, Z, k, ranks, num_ranks, h_out, f_out);
+    });
+}
+int lssvm_mi355_problem_time_leverage_prefix_kernel(lssvm_mi355_problem *p, uint64_t rank, uint64_t slab_rows, size_t k, const uint64_t *ranks, size_t num_ranks, int repeats,
+                                                    double *prefix_ms_out) {
+    return guarded([&] {
+        LSSVM_REQUIRE(p != nullptr, "problem handle must not be NULL");
+        impl_of(p)->time_leverage_prefix_kernel(rank, slab_rows, k, ranks, num_ranks, repeats, prefix_ms_out);
     });
 }
 int lssvm_mi355_problem_landmark_acc(lssvm_mi355_problem *p, const uint64_t *landmarks, uint64_t rank, int product, double *D_out) {

@@ -13,6 +13,8 @@
  *   (c) k_dense_solve            one workgroup per right-hand side: L z = rhs, L^T beta = z by blocks, then rho.  Column c never sees another column.
  *   (d) per block ROW i of V = L^-1 (Higham, Accuracy and Stability, Method 1B, by rows):  k_dense_gemm  W = -L[i, :i] V[:i, :i] (the triangle of V skipped),
  *                                          k_dense_trsm   L_ii X = [W | I], one thread per column, straight into the leverage kernel's operand.
+ *   (e) the rank path:  k_dense_forward  z_c = L^-1 rhs_c alone, the forward half of (c), beside V;
+ *                                          k_dense_prefix_beta  per (checkpoint r, right-hand side): beta = V[:r, :r]^T z[:r], rho, and max / min of the factor's squared diagonal.
  * Failure: a pivot that is not positive and finite makes k_dense_potrf_diag write 1 + its column into the status word (a plain store) and leave; every kernel reads the
  * word first and returns at once where it is not zero -- the whole workgroup alike, ahead of any barrier.  No workgroup waits for another, no atomics, no scratch: the
  * stream orders the launches, and the same arguments give the same bits.  Compiled for gfx950 only.
@@ -370,6 +372,101 @@ __global__ __launch_bounds__(256) void k_dense_solve(const double *__restrict__ 
     }
 }
 
+/* One workgroup per right-hand side c: z_c alone -> Z[c ldz ...], zeros from m up to ldz.  The forward half of k_dense_solve, statement for
+ * statement (a copy and not a shared function: k_dense_solve's generated code stays what it was). */
+__global__ __launch_bounds__(256) void k_dense_forward(const double *__restrict__ L, int mp, int m, const double *__restrict__ rhs, double *__restrict__ Z, size_t ldz,
+                                                       const unsigned *status) {
+    if (dense_failed(status)) return;
+    __shared__ double Ls[DB * DT_LD];
+    __shared__ double zv[DENSE_MAX_RANK];
+    __shared__ double red[256];
+    const int tid = threadIdx.x, lane = tid & 63, c = blockIdx.x;
+    const int nb = mp / DB;
+    const double *b = rhs + static_cast<size_t>(c) * mp;
+
+    for (int jb = 0; jb < nb; ++jb) {
+        __syncthreads();  // (wave 0 is done with the block before: Ls may be overwritten, its unknowns are in zv)
+        for (int e = tid; e < DB * DB; e += 256) Ls[(e >> 6) * DT_LD + (e & 63)] = L[static_cast<size_t>(jb * DB + (e >> 6)) * mp + jb * DB + (e & 63)];
+        {
+            const int row = tid >> 2, q = tid & 3;
+            const double *Lr = L + static_cast<size_t>(jb * DB + row) * mp;
+            double acc = 0.0;
+            for (int k = 2 * q; k < jb * DB; k += 8) {
+                const f64x2 l2 = *reinterpret_cast<const f64x2 *>(Lr + k);
+                acc = fma(l2[0], zv[k], acc);
+                acc = fma(l2[1], zv[k + 1], acc);
+            }
+            acc += __shfl_xor(acc, 1);
+            acc += __shfl_xor(acc, 2);
+            if (q == 0) red[row] = b[jb * DB + row] - acc;
+        }
+        __syncthreads();
+        if (tid < DB) {
+            double v = red[lane], mine = 0.0;
+#pragma unroll
+            for (int cc = 0; cc < DB; ++cc) {
+                const double zc = __shfl(v, cc) / Ls[cc * DT_LD + cc];
+                if (lane == cc) mine = zc;
+                if (lane > cc) v = fma(-Ls[lane * DT_LD + cc], zc, v);
+            }
+            zv[jb * DB + lane] = mine;
+        }
+    }
+    __syncthreads();
+    for (int j = tid; j < static_cast<int>(ldz); j += 256) Z[static_cast<size_t>(c) * ldz + j] = j < m ? zv[j] : 0.0;
+}
+
+/* One workgroup per (checkpoint q = blockIdx.x, right-hand side c = blockIdx.y) of the rank path: with r = ranks[q],
+ *   beta_j = sum_{n = j}^{r - 1} V[n][j] z_c[n]   (beta = V[:r, :r]^T z_c[:r]; thread j, j + 256, ... one chain each over the rows n ascending: the threads of a wave read
+ *   one row of V side by side),   betas[(q k + c) m + j], exact zeros from r up to m;
+ *   rho = -(eta_c - s[:r]^T beta) / N with the dot product as k_dense_solve takes it: 256 chains (j = tid, tid + 256, ...) and a binary tree over them.
+ * The workgroups of c == 0 also leave cond[q] = max_j L_jj^2 / min_j L_jj^2 over j < r off the padded factor (mp x mp), a binary tree each for the maximum and the minimum.
+ * Every order depends on r only.  No atomics. */
+__global__ __launch_bounds__(256) void k_dense_prefix_beta(const double *__restrict__ Vt, int ldv, const double *__restrict__ Z, size_t ldz, int m, int k, const int *__restrict__ ranks,
+                                                           const double *__restrict__ L, int mp, const double *__restrict__ s, const double *__restrict__ eta, double Nd,
+                                                           double *__restrict__ betas, double *__restrict__ rhos, double *__restrict__ cond, const unsigned *status) {
+    if (dense_failed(status)) return;
+    __shared__ double red[256];
+    __shared__ double red2[256];
+    const int tid = threadIdx.x, q = blockIdx.x, c = blockIdx.y;
+    const int r = ranks[q];
+    const double *z = Z + static_cast<size_t>(c) * ldz;
+    double *beta = betas + (static_cast<size_t>(q) * k + c) * m;
+    double acc = 0.0;
+    for (int j = tid; j < m; j += 256) {
+        double b = 0.0;
+        for (int n = j; n < r; ++n) b = fma(Vt[static_cast<size_t>(n) * ldv + j], z[n], b);
+        beta[j] = b;  // (j >= r: the loop is empty, an exact zero)
+        if (j < r) acc = fma(s[j], b, acc);
+    }
+    red[tid] = acc;
+    __syncthreads();
+    for (int stride = 128; stride > 0; stride >>= 1) {
+        if (tid < stride) red[tid] += red[tid + stride];
+        __syncthreads();
+    }
+    if (tid == 0) rhos[static_cast<size_t>(q) * k + c] = -((eta[c] - red[0]) / Nd);
+    if (c != 0) return;  // (uniform over the workgroup)
+    double hi = 0.0, lo = DBL_MAX;
+    for (int j = tid; j < r; j += 256) {
+        const double d = L[static_cast<size_t>(j) * mp + j], d2 = d * d;
+        hi = fmax(hi, d2);
+        lo = fmin(lo, d2);
+    }
+    __syncthreads();
+    red[tid] = hi;
+    red2[tid] = lo;
+    __syncthreads();
+    for (int stride = 128; stride > 0; stride >>= 1) {
+        if (tid < stride) {
+            red[tid] = fmax(red[tid], red[tid + stride]);
+            red2[tid] = fmin(red2[tid], red2[tid + stride]);
+        }
+        __syncthreads();
+    }
+    if (tid == 0) cond[q] = red[0] / red2[0];
+}
+
 }  // namespace
 
 DenseSpd::DenseSpd(int m, int max_rhs, hipStream_t st) : m_(m), mp_(round_up(m, DB)), nb_(round_up(m, DB) / DB), max_rhs_(std::max(max_rhs, 1)), st_(st) {
@@ -428,6 +525,21 @@ void DenseSpd::enqueue_solve(int k, double *X_out, size_t ldx, double *X2_out, s
     LSSVM_REQUIRE(k >= 1 && k <= max_rhs_, "DenseSpd: more right-hand sides than it was built for");
     hipLaunchKernelGGL(k_dense_solve, dim3(k), dim3(256), 0, st_, A_.p, mp_, m_, rhs_.p, X_out, ldx, m_, X2_out, ld2, static_cast<int>(ld2), with_rho ? s_.p : nullptr, eta_.p, Nd, rhos_out,
                        status_.p);
+    LSSVM_HIP_CHECK(hipGetLastError());
+    ++launches_;
+}
+
+void DenseSpd::enqueue_forward(int k, double *Z_out, size_t ldz) {
+    LSSVM_REQUIRE(k >= 1 && k <= max_rhs_ && ldz >= static_cast<size_t>(m_), "DenseSpd: more right-hand sides than it was built for, or rows of z shorter than m");
+    hipLaunchKernelGGL(k_dense_forward, dim3(k), dim3(256), 0, st_, A_.p, mp_, m_, rhs_.p, Z_out, ldz, status_.p);
+    LSSVM_HIP_CHECK(hipGetLastError());
+    ++launches_;
+}
+
+void DenseSpd::enqueue_prefix_betas(const double *Vt, int ldv, const double *Z, size_t ldz, int k, const int *ranks_dev, int num_ranks, double Nd, double *betas_out, double *rhos_out,
+                                    double *cond_out) {
+    LSSVM_REQUIRE(k >= 1 && k <= max_rhs_ && num_ranks >= 1 && ldv >= m_ && ldz >= static_cast<size_t>(m_), "DenseSpd: the prefix betas take the operands enqueue_invert and enqueue_forward left");
+    hipLaunchKernelGGL(k_dense_prefix_beta, dim3(num_ranks, k), dim3(256), 0, st_, Vt, ldv, Z, ldz, m_, k, ranks_dev, A_.p, mp_, s_.p, eta_.p, Nd, betas_out, rhos_out, cond_out, status_.p);
     LSSVM_HIP_CHECK(hipGetLastError());
     ++launches_;
 }

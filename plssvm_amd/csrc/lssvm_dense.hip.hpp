@@ -43,6 +43,13 @@ class DenseSpd {
     /* (c) L z = rhs, L^T beta = z for the k right-hand sides loaded or assembled before; beta_c -> X_out[c * ldx ...] (m entries, zeros up to `fill`), and, with_rho,
      * rho_c = -(eta_c - s^T beta_c) / N -> rhos_out[c].  X2_out (may be NULL): a second copy of the rows, ld2 doubles apart, zeros up to ld2 */
     void enqueue_solve(int k, double *X_out, size_t ldx, double *X2_out, size_t ld2, bool with_rho, double Nd, double *rhos_out);
+    /* (c) for the rank path: z_c alone, L z = rhs forward as enqueue_solve takes it, -> Z_out[c * ldz ...] (m entries, zeros up to ldz) */
+    void enqueue_forward(int k, double *Z_out, size_t ldz);
+    /* ... and per (checkpoint q, right-hand side c) beta = V[:r_q, :r_q]^T z_c[:r_q] -> betas_out[(q * k + c) * m ...] (zeros from r_q on), rho -> rhos_out[q * k + c], from
+     * the rows of V (Vt, ldv doubles apart) and Z that enqueue_invert and enqueue_forward left; cond_out[q] = max_j L_jj^2 / min_j L_jj^2 over j < r_q, off the factor.
+     * ranks_dev: num_ranks ascending checkpoints on the device */
+    void enqueue_prefix_betas(const double *Vt, int ldv, const double *Z, size_t ldz, int k, const int *ranks_dev, int num_ranks, double Nd, double *betas_out, double *rhos_out,
+                              double *cond_out);
     /* (d) row n of V = L^-1 -> Vt_out[n * ldv ...] for n < m, exact zeros above the diagonal up to ldv (>= m, a multiple of 16) */
     void enqueue_invert(double *Vt_out, int ldv);
     /* the factor (its lower triangle, zeros above) as m x m row major into L_dev */

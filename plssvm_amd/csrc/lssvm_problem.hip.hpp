@@ -647,6 +647,15 @@ struct ProblemBase {
                                   double *loo_out, double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out, lssvm_reduced_grid_info *infos,
                                   lssvm_dense_info *dense) = 0;  // lssvm_mi355_problem_fit_reduced_grid
     virtual void landmark_acc(const uint64_t *landmarks, uint64_t rank, int product, double *D_out) = 0;  // lssvm_mi355_problem_landmark_acc
+    /* the leave-one-out scores of every prefix rank of one fit over a cost grid (lssvm_reduced.hip); every output leads with cost, then checkpoint */
+    virtual void fit_reduced_rank_path(const void *Y, size_t num_rhs, const double *weights, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const uint64_t *ranks,
+                                       size_t num_ranks, const double *costs, size_t num_costs, int factor, double *betas_out, double *rhos_out, double *press_out,
+                                       uint64_t *loo_errors_out, double *leverage_out, double *fitted_out, double *loo_out, uint64_t *landmarks_out, lssvm_reduced_rank_info *infos,
+                                       lssvm_dense_info *dense) = 0;  // lssvm_mi355_problem_fit_reduced_rank_path
+    virtual void reduced_leverage_prefix(uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *V, const double *shift, const double *Z, size_t k,
+                                         const uint64_t *ranks, size_t num_ranks, double *h_out, double *f_out) = 0;  // lssvm_mi355_problem_reduced_leverage_prefix
+    virtual void time_leverage_prefix_kernel(uint64_t rank, uint64_t slab_rows, size_t k, const uint64_t *ranks, size_t num_ranks, int repeats,
+                                             double *prefix_ms_out) = 0;  // lssvm_mi355_problem_time_leverage_prefix_kernel
     /* landmark selection: the pivots of a greedy or randomly pivoted partial Cholesky factorisation (lssvm_select.hip) */
     virtual void select_landmarks(uint64_t rank, int method, uint64_t pool, uint64_t seed, double tol, uint64_t *landmarks_out, double *trace_out, double *residual_out,
                                   lssvm_landmark_select_info *info) = 0;  // lssvm_mi355_problem_select_landmarks
@@ -708,6 +717,7 @@ struct LocalComms {
 std::shared_ptr<LocalComms> local_comms_for(const std::vector<int> &devices);  // lssvm_exchange.hip
 
 struct LeverageArgs;  // what a leave-one-out pass of the fixed-size model works on (lssvm_reduced.hip)
+struct PrefixArgs;    // ... and what the pass over every prefix rank works on (lssvm_reduced.hip)
 /* what reduced_gram leaves on the device for the device-factored fits instead of releasing it: St as k_reduced_sum's packed 128 x 128 tiles, K_mm rank x rank */
 struct ReducedOnDevice {
     DevBuf<double> St, Kmm;
@@ -758,6 +768,13 @@ class Solver final : public ProblemBase {
                           const double *costs, size_t num_costs, int factor, int product, double *betas_out, double *rhos_out, double *leverage_out, double *fitted_out, double *loo_out,
                           double *press_out, uint64_t *loo_errors_out, uint64_t *landmarks_out, lssvm_reduced_grid_info *infos, lssvm_dense_info *dense) override;
     void landmark_acc(const uint64_t *landmarks, uint64_t rank, int product, double *D_out) override;
+    /* every prefix rank of one fit: one Gram pass, the dense steps of `factor` per cost, one prefix leverage pass per cost */
+    void fit_reduced_rank_path(const void *Y, size_t num_rhs, const double *weights, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const uint64_t *ranks, size_t num_ranks,
+                               const double *costs, size_t num_costs, int factor, double *betas_out, double *rhos_out, double *press_out, uint64_t *loo_errors_out, double *leverage_out,
+                               double *fitted_out, double *loo_out, uint64_t *landmarks_out, lssvm_reduced_rank_info *infos, lssvm_dense_info *dense) override;
+    void reduced_leverage_prefix(uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *V, const double *shift, const double *Z, size_t k, const uint64_t *ranks,
+                                 size_t num_ranks, double *h_out, double *f_out) override;
+    void time_leverage_prefix_kernel(uint64_t rank, uint64_t slab_rows, size_t k, const uint64_t *ranks, size_t num_ranks, int repeats, double *prefix_ms_out) override;
     /* fit_reduced and fit_reduced_loo with assembly, factorisation, solves and the triangular inverse on the device (lssvm_dense.hip) */
     void fit_reduced_dev(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, double *betas_out, double *rhos_out, uint64_t *landmarks_out,
                          lssvm_reduced_info *info, lssvm_dense_info *dense, const double *weights = nullptr) override;
@@ -813,6 +830,8 @@ class Solver final : public ProblemBase {
                       double *total_out = nullptr);
     /* pass 2 of fit_reduced_loo, and all of reduced_leverage: the Phi slabs again, the leverage kernel per slab and operand (lssvm_reduced.hip) */
     void leverage_pass(const std::vector<uint64_t> &lm, uint64_t slab_rows, LeverageArgs &args, GridSlabs<T> *grid = nullptr);
+    /* pass 2 of fit_reduced_rank_path, and all of reduced_leverage_prefix: the Phi slabs again, the prefix leverage kernel per slab and operand (lssvm_reduced.hip) */
+    void prefix_pass(const std::vector<uint64_t> &lm, uint64_t slab_rows, PrefixArgs &args);
     T *vec_of(Problem<T> &p, Vec which) const { return which == Vec::d ? p.own_.d.p : (which == Vec::x ? p.own_.x.p : p.tmp_.p); }
 
     Options opt_{};
@@ -867,6 +886,10 @@ void check_reduced_loo_costs(const double *costs, size_t num_costs);
 constexpr size_t REDUCED_GRID_MAX_CELLS = 64;
 void check_reduced_grid_arguments(const double *gammas, size_t num_gammas, size_t num_costs, int product);
 void check_reduced_grid_kernel(int kernel_type);
+/* what lssvm_mi355_problem_fit_reduced_rank_path / lssvm_mi355_fit_reduced_rank_path_* add to the cost grid: 1 ... REDUCED_RANK_PATH_MAX_RANKS checkpoints, strictly
+ * ascending, each in [1, rank], and at most REDUCED_GRID_MAX_CELLS (cost, checkpoint) cells */
+constexpr size_t REDUCED_RANK_PATH_MAX_RANKS = 16;
+void check_reduced_rank_list(const uint64_t *ranks, size_t num_ranks, uint64_t rank, size_t num_costs);
 
 /* the arguments of lssvm_mi355_problem_select_landmarks / lssvm_mi355_select_landmarks_* that need no device (lssvm_select.hip); returns the number of candidates */
 constexpr int SELECT_MAX_RANK = 1024;

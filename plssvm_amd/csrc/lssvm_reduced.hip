@@ -26,6 +26,12 @@
  * section 17): what a kernel value is made from, D = sum_f (a_f - b_f)^2 or sum_f a_f b_f, does not depend on gamma.  GridSlabs forms it once per slab and pass --
  * k_landmark_acc (the loop of k_landmark_block) or k_landmark_product (the dot products on v_mfma_f64_16x16x4_f64, the norm expansion for rbf) -- and k_kernel_values
  * writes the Phi columns of a gamma from it; the Gram pass, the dense steps and the leverage kernel per (gamma, cost) are the ones above.
+ *
+ * The leave-one-out scores of every prefix rank from one fit (lssvm_mi355_problem_fit_reduced_rank_path, _reduced_leverage_prefix, lssvm_mi355_fit_reduced_rank_path_*;
+ * DESIGN.md section 18): the landmark list is ordered, and M, L, V = L^-1 and z = L^-1 rhs of the first r landmarks are the leading blocks of the rank-m ones.  Pass 1 and
+ * the dense steps per cost are the ones above (the host's solve split into its forward and backward half: z is kept, the back substitution runs on every leading block);
+ * in pass 2 k_reduced_leverage_prefix forms Phic V^T as k_reduced_leverage does and takes the running sums of u^2 and u z_c out of its accumulators at the checkpoints.
+ * Every prefix model of a cost takes the nu of the full rank.
  */
 #include "lssvm_dense.hip.hpp"
 #include "lssvm_landmark.hip.hpp"
@@ -279,26 +285,37 @@ double factor_reduced(const std::vector<double> &St, const std::vector<double> &
     return cholesky_with_jitter(M, m, "the matrix of the reduced model", L);
 }
 
-void solve_reduced(const std::vector<double> &St, const std::vector<double> &L, int m, int k, int cols, double Nd, double *betas_out, double *rhos_out) {
+/* the two halves of a solve, for right-hand side c and the leading r x r block of the m x m factor L (solve_reduced: r = m; the rank path, DESIGN.md section 18: every
+ * checkpoint r <= m -- the factor of a leading block is the leading block of the factor, and z of the block is z[:r]) */
+void forward_reduced(const std::vector<double> &St, const std::vector<double> &L, int m, int c, int cols, double Nd, double *z) {
     const double *s = &St[static_cast<size_t>(m) * cols];
+    const double *t = &St[static_cast<size_t>(m + 1 + c) * cols];
+    const double eta = t[m];
+    for (int j = 0; j < m; ++j) {  // L z = t_c - s eta_c / N
+        double v = t[j] - s[j] * eta / Nd;
+        for (int l = 0; l < j; ++l) v -= L[static_cast<size_t>(j) * m + l] * z[l];
+        z[j] = v / L[static_cast<size_t>(j) * m + j];
+    }
+}
+
+double backward_reduced(const std::vector<double> &St, const std::vector<double> &L, int m, int r, int c, int cols, double Nd, const double *z, double *beta) {
+    const double *s = &St[static_cast<size_t>(m) * cols];
+    const double eta = St[static_cast<size_t>(m + 1 + c) * cols + m];
+    for (int j = r - 1; j >= 0; --j) {  // L_r^T beta = z[:r]
+        double v = z[j];
+        for (int l = j + 1; l < r; ++l) v -= L[static_cast<size_t>(l) * m + j] * beta[l];
+        beta[j] = v / L[static_cast<size_t>(j) * m + j];
+    }
+    double sb = 0.0;
+    for (int j = 0; j < r; ++j) sb += s[j] * beta[j];
+    return -((eta - sb) / Nd);
+}
+
+void solve_reduced(const std::vector<double> &St, const std::vector<double> &L, int m, int k, int cols, double Nd, double *betas_out, double *rhos_out) {
     std::vector<double> z(static_cast<size_t>(m));
     for (int c = 0; c < k; ++c) {
-        const double *t = &St[static_cast<size_t>(m + 1 + c) * cols];
-        const double eta = t[m];
-        for (int j = 0; j < m; ++j) {  // L z = t_c - s eta_c / N
-            double v = t[j] - s[j] * eta / Nd;
-            for (int l = 0; l < j; ++l) v -= L[static_cast<size_t>(j) * m + l] * z[l];
-            z[j] = v / L[static_cast<size_t>(j) * m + j];
-        }
-        double *beta = betas_out + static_cast<size_t>(c) * m;
-        for (int j = m - 1; j >= 0; --j) {  // L^T beta = z
-            double v = z[j];
-            for (int l = j + 1; l < m; ++l) v -= L[static_cast<size_t>(l) * m + j] * beta[l];
-            beta[j] = v / L[static_cast<size_t>(j) * m + j];
-        }
-        double sb = 0.0;
-        for (int j = 0; j < m; ++j) sb += s[j] * beta[j];
-        rhos_out[c] = -((eta - sb) / Nd);
+        forward_reduced(St, L, m, c, cols, Nd, z.data());
+        rhos_out[c] = backward_reduced(St, L, m, m, c, cols, Nd, z.data(), betas_out + static_cast<size_t>(c) * m);
     }
 }
 
@@ -364,9 +381,10 @@ struct DenseFit {
     size_t device_bytes() const { return dense.device_bytes() + (betas.count + rhos.count) * sizeof(double); }
 
     /* One cost: the jitter rule of cholesky_with_jitter, each attempt assemble -> factor -> solve (-> invert into the operand Bt_op: rows of V, the betas behind them, ldb
-     * doubles apart) and ONE wait, at which betas (k x m), rhos (k) and the status word come back.  Fills `d` (may be NULL); returns nu. */
+     * doubles apart) and ONE wait, at which betas (k x m), rhos (k) and the status word come back.  Fills `d` (may be NULL); returns nu.  Z_op (the rank path, DESIGN.md
+     * section 18; else NULL): z_c = L^-1 (t_c - s eta_c / N), k rows of ldb doubles, is left there too. */
     double run(const ReducedOnDevice &dev, const std::vector<double> &St, const std::vector<double> &Kmm, int cols, double Nd, double sigma, double *Bt_op, int ldb, double *betas_out,
-               double *rhos_out, lssvm_dense_info *d, double *device_ms_out) {
+               double *rhos_out, lssvm_dense_info *d, double *device_ms_out, double *Z_op = nullptr) {
         const double trace = reduced_trace(St, Kmm, m, cols, Nd, sigma);
         LSSVM_REQUIRE(std::isfinite(trace) && trace > 0.0, "the matrix of the reduced model has no positive finite trace");
         double nu = DBL_EPSILON * trace;
@@ -383,6 +401,7 @@ struct DenseFit {
                 dense.enqueue_invert(Bt_op, ldb);
                 watch.mark(4);
             }
+            if (Z_op != nullptr) dense.enqueue_forward(k, Z_op, static_cast<size_t>(ldb));  // (the rank path: z_c beside V, ldb doubles apart)
             LSSVM_HIP_CHECK(hipMemcpyAsync(betas_host.data(), betas.p, betas.count * sizeof(double), hipMemcpyDeviceToHost, st));
             LSSVM_HIP_CHECK(hipMemcpyAsync(rhos_host.data(), rhos.p, rhos.count * sizeof(double), hipMemcpyDeviceToHost, st));
             if (dense.status() != 0) continue;  // (the wait; a failed attempt's kernels have all returned at once and written nothing)
@@ -582,6 +601,214 @@ __global__ __launch_bounds__(256, 2) void k_reduced_leverage(const double *__res
             const double y = ycols[static_cast<size_t>(c) * ld + row0 + lrow];
             const double f = f_out[static_cast<size_t>(c) * ldo + row0 + lrow];
             loo_out[static_cast<size_t>(c) * ldo + row0 + lrow] = left_out ? f : y - (y - f) / (1.0 - h);
+        }
+    }
+}
+
+/* ---- the leave-one-out pass over every prefix rank ---- */
+constexpr int PFX_KMAX = 4;        // right-hand sides per launch: 1 + PFX_KMAX running sums per row and column wave in LDS (the host launches once per group of four)
+constexpr int PFX_SUMS = (1 + PFX_KMAX) * 2 * RG_TW;  // doubles: [sum][column wave][row of the workgroup]
+
+/* The sibling of k_reduced_leverage for the rank path: the same slab layout, LDS staging (centring subtracted on the way in), masked staging of the triangular operand
+ * and 128 x 128 tiles of v_mfma_f64_16x16x4_f64, four waves of 64 x 64.  The operand is V ALONE: row n of Vt (ldb doubles apart) is row n of V = L^-1, n < m; rows from m
+ * on count as zeros and are never read, an entry V[n][j] with j > n is replaced by 0 as it is staged.  Z: row c (ldb doubles apart) is z_c, k <= PFX_KMAX rows, read below m
+ * only.  ranks: num_ranks ascending checkpoints 1 <= r_q <= m.  Only the column blocks up to the one of the last checkpoint are formed.
+ * After each 128-column block the tile U = (Phi - 1 shift^T) V^T stands in the accumulators.  A lane forms, for each of its sixteen rows and a column limit `lim`, the
+ * 1 + k sums of u^2 and u z_c over its four columns below lim in ascending order (one fma each), then the sixteen lanes of the row add up (xor 1, 2, 4, 8): row_sums.
+ *   a checkpoint r_q inside the block (128 bk < r_q <= 128 (bk + 1)): row_sums with lim = r_q, BEHIND the running sums of the blocks before, per column wave; the two
+ *   column waves meet in LDS (cps) and one thread per row forms  h[q ldo + i] = inv_n + sum  (w given: w_i (inv_n + sum)),  f[(q k + c) ldo + i] = sum_c + ybar[c],
+ *   loo[(q k + c) ldo + i] = y - (y - f) / (1 - h)  (a row of weight 0: f itself; loo_out NULL: not formed), as k_reduced_leverage's end does;
+ *   then, where a block follows, row_sums with lim = m goes behind the running sums (`run`, LDS: the sums are not held in registers across a block).
+ * So checkpoint q is (blocks before, ascending) + (its own masked block), then wave 0 + wave 1: an order that depends on m and r_q only -- not on the other checkpoints,
+ * not on k (every sum is its own chain), not on N.  No atomics, no scratch.  Rows from `rows` on write nothing. */
+__global__ __launch_bounds__(256, 2) void k_reduced_leverage_prefix(const double *__restrict__ slab, size_t ld, int rows, int m, int k, const double *__restrict__ Vt, int ldb,
+                                                                    const double *__restrict__ Z, const int *__restrict__ ranks, int num_ranks, const double *__restrict__ shift,
+                                                                    const double *__restrict__ ybar, double inv_n, const double *__restrict__ ycols, double *__restrict__ h_out,
+                                                                    double *__restrict__ f_out, double *__restrict__ loo_out, size_t ldo, const double *__restrict__ w) {
+    __shared__ __attribute__((aligned(16))) double As[RG_KC * LV_LSA];
+    __shared__ __attribute__((aligned(16))) double Bs[RG_TW * RG_LS];
+    __shared__ double run[PFX_SUMS];  // the running sums of the blocks before
+    __shared__ double cps[PFX_SUMS];  // a checkpoint's sums, where the two column waves meet
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int wr = wave >> 1, wc = wave & 1;
+    const int r = lane & 15, qd = lane >> 4;
+    const int row0 = blockIdx.x * RG_TW;
+    const int nblocks = (ranks[num_ranks - 1] + RG_TW - 1) / RG_TW;
+    const int m16 = (m + RG_KC - 1) / RG_KC * RG_KC;
+
+    // staging of Phi and of Vt: as k_reduced_leverage
+    const int akk = tid >> 4, aseg = tid & 15;
+    const double *Ag = slab + static_cast<size_t>(akk) * ld + row0 + 2 * aseg;
+    const int a_lds = akk * LV_LSA + 2 * aseg;
+    const int srow = tid >> 3, sseg = tid & 7;
+    const int b_lds = srow * RG_LS + 2 * sseg;
+    const f64x2 zero2 = { 0.0, 0.0 };
+    f64x2 sa[4], sb[4];
+
+    // lane 16 qd of a wave owns the sums of the wave's rows qd + 4 i + 16 mt in `run`: nobody else touches them
+    const int own = wc * RG_TW + wr * 64 + qd;  // + 4 i + 16 mt, + 2 RG_TW per sum
+    if (r == 0) {
+#pragma unroll
+        for (int s = 0; s <= PFX_KMAX; ++s)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) run[s * 2 * RG_TW + own + 4 * e] = 0.0;
+    }
+
+    const double *Ab = As + qd * LV_LSA + wr * 64 + r;
+    const double *Bb = Bs + (wc * 64 + r) * RG_LS + qd;
+
+    for (int bk = 0; bk < nblocks; ++bk) {
+        const int nsteps = ((bk + 1) * RG_TW <= m ? (bk + 1) * RG_TW : m16) / RG_KC;
+        const int n0 = bk * RG_TW + srow;  // this thread's rows of Vt: n0 + 32 p
+        auto stage_load = [&](int s) {
+            const int j = s * RG_KC + akk;
+            const bool a_in = j < m;
+            const double sh = a_in ? shift[j] : 0.0;
+            const double *a = Ag + static_cast<size_t>(s) * RG_KC * ld;
+            const int jb = s * RG_KC + 2 * sseg;
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                f64x2 v = a_in ? *reinterpret_cast<const f64x2 *>(a + 32 * p) : zero2;
+                if (a_in) {
+                    v[0] -= sh;
+                    v[1] -= sh;
+                }
+                sa[p] = v;
+                const int n = n0 + 32 * p;  // the last column of the row that counts: the diagonal
+                f64x2 vv = n < m ? *reinterpret_cast<const f64x2 *>(Vt + static_cast<size_t>(n) * ldb + jb) : zero2;
+                if (jb > n) vv[0] = 0.0;
+                if (jb + 1 > n) vv[1] = 0.0;
+                sb[p] = vv;
+            }
+        };
+        auto stage_store = [&]() {
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                *reinterpret_cast<f64x2 *>(As + a_lds + 32 * p) = sa[p];
+                *reinterpret_cast<f64x2 *>(Bs + b_lds + p * 32 * RG_LS) = sb[p];
+            }
+        };
+
+        f64x4 acc[4][4];
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) {
+                acc[mt][nt] = f64x4{ 0.0, 0.0, 0.0, 0.0 };
+                // the start values live in the accumulators' OWN registers (C == D for every MFMA of a chain), as in k_reduced_gram
+                asm volatile("" : "+v"(acc[mt][nt]));
+            }
+
+        stage_load(0);  // (the barrier that ended the block before lets every wave write: all of them have read its last step)
+        stage_store();
+        __syncthreads();
+        for (int s = 0; s < nsteps; ++s) {
+            const bool has_next = s + 1 < nsteps;
+            if (has_next) stage_load(s + 1);
+#pragma unroll
+            for (int ks = 0; ks < RG_KC / 4; ++ks) {
+                double av[4], bv[4];
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    av[t] = Ab[ks * 4 * LV_LSA + t * 16];
+                    bv[t] = Bb[t * 16 * RG_LS + ks * 4];
+                }
+#pragma unroll
+                for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                    for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[mt], bv[nt], acc[mt][nt], 0, 0, 0);
+            }
+            __syncthreads();  // (every wave has read this step)
+            if (has_next) {
+                stage_store();
+                __syncthreads();
+            }
+        }
+
+        // a lane holds rows qd + 4 i of its four row tiles and column r of its four column tiles: nw + 16 nt; z of these columns
+        const int nw = bk * RG_TW + wc * 64 + r;
+        double zr[PFX_KMAX][4];
+#pragma unroll
+        for (int c = 0; c < PFX_KMAX; ++c)
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) zr[c][nt] = c < k && nw + 16 * nt < m ? Z[static_cast<size_t>(c) * ldb + nw + 16 * nt] : 0.0;
+        // v[0]: the squares, v[1 + c]: the products with z_c, of row (mt, i) over the lane's columns below lim, then over the sixteen lanes of the row
+        auto row_sums = [&](int lim, int mt, int i, double(&v)[1 + PFX_KMAX]) {
+#pragma unroll
+            for (int s = 0; s <= PFX_KMAX; ++s) v[s] = 0.0;
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) {
+                const double a = nw + 16 * nt < lim ? acc[mt][nt][i] : 0.0;
+                v[0] = fma(a, a, v[0]);
+#pragma unroll
+                for (int c = 0; c < PFX_KMAX; ++c)
+                    if (c < k) v[1 + c] = fma(a, zr[c][nt], v[1 + c]);
+            }
+#pragma unroll
+            for (int s = 0; s <= PFX_KMAX; ++s) {
+                if (s <= k) {
+                    v[s] += __shfl_xor(v[s], 1);
+                    v[s] += __shfl_xor(v[s], 2);
+                    v[s] += __shfl_xor(v[s], 4);
+                    v[s] += __shfl_xor(v[s], 8);
+                }
+            }
+        };
+
+        for (int q = 0; q < num_ranks; ++q) {
+            const int rq = ranks[q];
+            if ((rq - 1) / RG_TW != bk) continue;  // (the same for the whole workgroup)
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    double v[1 + PFX_KMAX];
+                    row_sums(rq, mt, i, v);
+                    if (r == 0) {
+                        const int at = own + 4 * i + 16 * mt;
+#pragma unroll
+                        for (int s = 0; s <= PFX_KMAX; ++s)
+                            if (s <= k) cps[s * 2 * RG_TW + at] = run[s * 2 * RG_TW + at] + v[s];
+                    }
+                }
+            __syncthreads();
+            {
+                const int lrow = tid & (RG_TW - 1), row = row0 + lrow;
+                const double sum = cps[lrow] + cps[RG_TW + lrow];
+                const double h = w != nullptr ? w[row] * (inv_n + sum) : inv_n + sum;
+                if (row < rows) {
+                    if (tid < RG_TW) h_out[static_cast<size_t>(q) * ldo + row] = h;
+                    const bool left_out = w != nullptr && w[row] == 0.0;
+                    for (int c = tid >> 7; c < k; c += 2) {
+                        const double f = (cps[(1 + c) * 2 * RG_TW + lrow] + cps[(1 + c) * 2 * RG_TW + RG_TW + lrow]) + (ybar != nullptr ? ybar[c] : 0.0);
+                        const size_t at = (static_cast<size_t>(q) * k + c) * ldo + row;
+                        f_out[at] = f;
+                        if (loo_out != nullptr) {
+                            const double y = ycols[static_cast<size_t>(c) * ld + row];
+                            loo_out[at] = left_out ? f : y - (y - f) / (1.0 - h);
+                        }
+                    }
+                }
+            }
+            __syncthreads();  // (cps is free for the next checkpoint)
+        }
+
+        if (bk + 1 < nblocks) {
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    double v[1 + PFX_KMAX];
+                    row_sums(m, mt, i, v);
+                    if (r == 0) {
+                        const int at = own + 4 * i + 16 * mt;
+#pragma unroll
+                        for (int s = 0; s <= PFX_KMAX; ++s)
+                            if (s <= k) run[s * 2 * RG_TW + at] += v[s];
+                    }
+                }
         }
     }
 }
@@ -789,6 +1016,69 @@ struct LeverageArgs {
     }
     hipStream_t st;
 };
+
+/* what a pass over every prefix rank works on: per operand (a cost) the m rows of V and, behind them, the k rows of z, ldb doubles apart -- the
+ * layout of LeverageArgs' operands with z where the betas stand, so that DenseFit::run fills it as it is; the checkpoints; and where the results go, every output with
+ * the checkpoint dimension behind the operand's */
+struct PrefixArgs {
+    const int m, k, ldb, R;
+    const size_t num_ops, op_stride;
+    DevBuf<double> ops, shift, ybar;
+    DevBuf<int> ranks_dev;
+    std::vector<int> ranks;
+    double inv_n = 0.0;
+    const void *Y = nullptr;                                        // the host's right-hand sides (k x N, the problem's type), or NULL: no leave-one-out values
+    const double *w = nullptr;                                      // the host's N weights, or NULL
+    double *h_out = nullptr, *f_out = nullptr, *loo_out = nullptr;  // num_ops x R x N, num_ops x R x k x N, num_ops x R x k x N; each may be NULL
+    double *press = nullptr;                                        // num_ops x R x k, or NULL
+    uint64_t *errors = nullptr;                                     // num_ops x R x k, or NULL
+    std::vector<double> max_leverage, leverage_ms;                  // num_ops x R; per operand
+    double landmark_ms = 0.0;
+    hipStream_t st;
+
+    PrefixArgs(int rank, int num_cols, const uint64_t *ranks_in, size_t num_ranks, size_t operands, bool with_ybar, hipStream_t stream) :
+        m(rank), k(num_cols), ldb(round_up(rank, RG_KC)), R(static_cast<int>(num_ranks)), num_ops(operands), op_stride(static_cast<size_t>(rank + num_cols) * ldb),
+        ranks(ranks_in, ranks_in + num_ranks), st(stream) {
+        ops.alloc_zero(num_ops * op_stride, st);
+        shift.alloc_zero(static_cast<size_t>(m), st);
+        if (with_ybar) ybar.alloc_zero(num_ops * std::max(k, 1), st);
+        ranks_dev.alloc_zero(static_cast<size_t>(R), st);
+        LSSVM_HIP_CHECK(hipMemcpyAsync(ranks_dev.p, ranks.data(), static_cast<size_t>(R) * sizeof(int), hipMemcpyHostToDevice, st));
+        LSSVM_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    double *V_of(size_t o) const { return ops.p + o * op_stride; }
+    double *Z_of(size_t o) const { return ops.p + o * op_stride + static_cast<size_t>(m) * ldb; }
+    /* operand o <- the host's m + k rows of ldb doubles; returns when they are on the device */
+    void upload_operand(size_t o, const double *host) {
+        LSSVM_HIP_CHECK(hipMemcpyAsync(V_of(o), host, op_stride * sizeof(double), hipMemcpyHostToDevice, st));
+        LSSVM_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    void upload_shift(const double *shift_host, const double *ybar_host) {
+        LSSVM_HIP_CHECK(hipMemcpyAsync(shift.p, shift_host, shift.count * sizeof(double), hipMemcpyHostToDevice, st));
+        if (ybar_host != nullptr) LSSVM_HIP_CHECK(hipMemcpyAsync(ybar.p, ybar_host, num_ops * k * sizeof(double), hipMemcpyHostToDevice, st));
+        LSSVM_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    /* k_reduced_leverage_prefix for operand o and its right-hand sides c0 ... c0 + kc - 1 (kc <= PFX_KMAX) on `rows` rows of a slab; h: R x ld, f and loo: R x kc x ld */
+    void enqueue(size_t o, int c0, int kc, const double *slab, size_t ld, int rows, double *h, double *f, double *loo, const double *w_dev) const {
+        hipLaunchKernelGGL(k_reduced_leverage_prefix, dim3(round_up(rows, 256) / RG_TW), dim3(256), 0, st, slab, ld, rows, m, kc, V_of(o), ldb, Z_of(o) + static_cast<size_t>(c0) * ldb,
+                           ranks_dev.p, R, shift.p, ybar.p != nullptr ? ybar.p + o * k + c0 : nullptr, inv_n, loo != nullptr ? slab + static_cast<size_t>(m + 1 + c0) * ld : nullptr, h, f, loo,
+                           ld, w_dev);
+        LSSVM_HIP_CHECK(hipGetLastError());
+    }
+};
+
+void check_reduced_rank_list(const uint64_t *ranks, size_t num_ranks, uint64_t rank, size_t num_costs) {
+    LSSVM_REQUIRE(ranks != nullptr, "ranks must not be NULL");
+    LSSVM_REQUIRE(num_ranks >= 1 && num_ranks <= REDUCED_RANK_PATH_MAX_RANKS,
+                  "The rank path takes between 1 and " + std::to_string(REDUCED_RANK_PATH_MAX_RANKS) + " checkpoints, but got " + std::to_string(num_ranks) + "!");
+    LSSVM_REQUIRE(num_ranks * num_costs <= REDUCED_GRID_MAX_CELLS,
+                  "The rank path takes at most " + std::to_string(REDUCED_GRID_MAX_CELLS) + " (cost, checkpoint) cells, but got " + std::to_string(num_costs) + " x " + std::to_string(num_ranks) + "!");
+    for (size_t q = 0; q < num_ranks; ++q) {
+        LSSVM_REQUIRE(ranks[q] >= 1 && ranks[q] <= rank, "Every checkpoint must lie in [1, " + std::to_string(rank) + "], but checkpoint " + std::to_string(q) + " is " + std::to_string(ranks[q]) + "!");
+        LSSVM_REQUIRE(q == 0 || ranks[q] > ranks[q - 1], "The checkpoints must be strictly ascending, but checkpoint " + std::to_string(q) + " is " + std::to_string(ranks[q]) + " behind " +
+                                                             std::to_string(ranks[q - 1]) + "!");
+    }
+}
 
 void check_reduced_arguments(const void *Y, size_t num_rhs, uint64_t rank, uint64_t slab_rows, size_t num_points) {
     LSSVM_REQUIRE(Y != nullptr, "The right hand side vector must not be empty!");
@@ -1444,6 +1734,263 @@ void Solver<T>::reduced_leverage(uint64_t rank, const uint64_t *landmarks, uint6
     leverage_pass(lm, slab_rows, a);
 }
 
+/* ---- every prefix rank of one fit ---- */
+/* The Phi slabs once more (as leverage_pass) and, per slab and operand, k_reduced_leverage_prefix once per group of PFX_KMAX right-hand sides; h, f and loo of the slab
+ * and every checkpoint go to the caller's arrays, the sums over the points are formed here in row order as leverage_pass forms them. */
+template <typename T>
+void Solver<T>::prefix_pass(const std::vector<uint64_t> &lm, uint64_t slab_rows, PrefixArgs &a) {
+    Problem<T> &p = *shards_[0];
+    const size_t N = p.N_;
+    const int m = a.m, k = a.k, R = a.R;
+    const bool with_y = a.Y != nullptr;
+    const int cols = with_y ? m + 1 + k : m;
+    hipStream_t st = p.stream();
+    const SlabPlan plan(N, slab_rows);
+    const size_t ld = plan.ld;
+
+    const LandmarkBlock<T> block(p, lm, st);
+    const RhsOnDevice<T> rhs(a.Y, k, N, st);
+    DevBuf<double> slab, h_dev, f_dev, loo_dev, w_dev;
+    if (a.w != nullptr) upload_per_row(a.w, false, plan, w_dev, st);
+    const size_t group = static_cast<size_t>(R) * PFX_KMAX * ld;  // what one launch writes of f and of loo
+    slab.alloc_zero(static_cast<size_t>(cols) * ld, st);
+    h_dev.alloc_zero(static_cast<size_t>(R) * ld, st);
+    f_dev.alloc_zero(group, st);
+    if (with_y) loo_dev.alloc_zero(group, st);
+    std::vector<double> h_host(static_cast<size_t>(R) * ld), f_host(group), loo_host(with_y ? group : 0);
+
+    Event ev[2];
+    for (Event &e : ev) e.create(true);
+    a.max_leverage.assign(a.num_ops * R, 0.0);
+    a.leverage_ms.assign(a.num_ops, 0.0);
+    a.landmark_ms = 0.0;
+    if (a.press != nullptr) std::fill(a.press, a.press + a.num_ops * R * k, 0.0);
+    if (a.errors != nullptr) std::fill(a.errors, a.errors + a.num_ops * R * k, uint64_t{ 0 });
+    const T *Yh = static_cast<const T *>(a.Y);
+    for (int s = 0; s < plan.slabs; ++s) {
+        const size_t row0 = plan.row0(s);
+        const int rows = plan.rows(s);
+        LSSVM_HIP_CHECK(hipEventRecord(ev[0].e, st));
+        enqueue_slab(block, m, plan, s, rhs, slab.p, st);
+        LSSVM_HIP_CHECK(hipGetLastError());
+        LSSVM_HIP_CHECK(hipEventRecord(ev[1].e, st));
+        LSSVM_HIP_CHECK(hipEventSynchronize(ev[1].e));
+        a.landmark_ms += elapsed_ms(ev[0], ev[1]);
+        for (size_t o = 0; o < a.num_ops; ++o) {
+            for (int c0 = 0; c0 == 0 || c0 < k; c0 += PFX_KMAX) {  // (k == 0: one launch for h alone)
+                const int kc = std::min(PFX_KMAX, k - c0);
+                const size_t out_bytes = static_cast<size_t>(R) * std::max(kc, 1) * ld * sizeof(double);
+                LSSVM_HIP_CHECK(hipEventRecord(ev[0].e, st));
+                a.enqueue(o, c0, kc, slab.p, ld, rows, h_dev.p, f_dev.p, loo_dev.p, w_dev.p != nullptr ? w_dev.p + row0 : nullptr);
+                LSSVM_HIP_CHECK(hipEventRecord(ev[1].e, st));
+                if (c0 == 0) LSSVM_HIP_CHECK(hipMemcpyAsync(h_host.data(), h_dev.p, h_host.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+                if (kc > 0) LSSVM_HIP_CHECK(hipMemcpyAsync(f_host.data(), f_dev.p, out_bytes, hipMemcpyDeviceToHost, st));
+                if (kc > 0 && with_y) LSSVM_HIP_CHECK(hipMemcpyAsync(loo_host.data(), loo_dev.p, out_bytes, hipMemcpyDeviceToHost, st));
+                LSSVM_HIP_CHECK(hipStreamSynchronize(st));
+                a.leverage_ms[o] += elapsed_ms(ev[0], ev[1]);
+                for (int q = 0; q < R; ++q) {
+                    const size_t oq = o * R + q;
+                    if (c0 == 0) {
+                        const double *h = &h_host[static_cast<size_t>(q) * ld];
+                        for (int i = 0; i < rows; ++i) a.max_leverage[oq] = std::max(a.max_leverage[oq], h[i]);
+                        if (a.h_out != nullptr) std::copy(h, h + rows, a.h_out + oq * N + row0);
+                    }
+                    for (int c = 0; c < kc; ++c) {
+                        const size_t oc = oq * k + c0 + c, at = (static_cast<size_t>(q) * kc + c) * ld;
+                        if (a.f_out != nullptr) std::copy(&f_host[at], &f_host[at] + rows, a.f_out + oc * N + row0);
+                        if (!with_y) continue;
+                        const double *loo = &loo_host[at];
+                        if (a.loo_out != nullptr) std::copy(loo, loo + rows, a.loo_out + oc * N + row0);
+                        double press = a.press != nullptr ? a.press[oc] : 0.0;
+                        uint64_t errors = 0;
+                        for (int i = 0; i < rows; ++i) {
+                            const double y = static_cast<double>(Yh[static_cast<size_t>(c0 + c) * N + row0 + i]), d = y - loo[i];
+                            const bool wrong = ((loo[i] > 0.0) - (loo[i] < 0.0)) != ((y > 0.0) - (y < 0.0));
+                            if (a.w != nullptr) {  // sum_i w_i d_i^2; the errors over the points that took part in the fit
+                                press += a.w[row0 + i] * (d * d);
+                                errors += wrong && a.w[row0 + i] > 0.0 ? 1 : 0;
+                            } else {
+                                press += d * d;
+                                errors += wrong ? 1 : 0;
+                            }
+                        }
+                        if (a.press != nullptr) a.press[oc] = press;
+                        if (a.errors != nullptr) a.errors[oc] += errors;
+                    }
+                }
+            }
+        }
+    }
+}
+
+template <typename T>
+void Solver<T>::fit_reduced_rank_path(const void *Y, size_t num_rhs, const double *weights, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const uint64_t *ranks,
+                                      size_t num_ranks, const double *costs, size_t num_costs, int factor, double *betas_out, double *rhos_out, double *press_out,
+                                      uint64_t *loo_errors_out, double *leverage_out, double *fitted_out, double *loo_out, uint64_t *landmarks_out, lssvm_reduced_rank_info *infos,
+                                      lssvm_dense_info *dense_out) {
+    LSSVM_REQUIRE(betas_out != nullptr && rhos_out != nullptr, "betas_out / rhos_out must not be NULL");
+    check_reduced_loo_costs(costs, num_costs);
+    check_reduced_factor(factor);
+    check_reduced_rank_list(ranks, num_ranks, rank, num_costs);
+    std::vector<uint64_t> lm;
+    std::vector<double> St, Kmm;
+    lssvm_reduced_info info{};
+    ReducedOnDevice dev;
+    double Nd = 0.0;  // N, or the sum of the weights
+    reduced_gram("fit_reduced_rank_path", Y, num_rhs, rank, landmarks, slab_rows, lm, St, Kmm, info, factor == 1 ? &dev : nullptr, weights, &Nd);  // pass 1, and every other check that needs no device
+
+    const int m = static_cast<int>(rank), k = static_cast<int>(num_rhs), cols = m + 1 + k, R = static_cast<int>(num_ranks);
+    Problem<T> &p = *shards_[0];
+    const SetOnExit<bool> busy = hold_busy();
+    p.activate();
+    hipStream_t st = p.stream();
+    PrefixArgs a(m, k, ranks, num_ranks, num_costs, true, st);
+    const size_t cell = static_cast<size_t>(k) * m;  // the betas of a (cost, checkpoint)
+
+    // ---- per cost: L, V and z as the leave-one-out call of `factor` forms them, then the betas and rhos of every checkpoint off the leading blocks ----
+    const double *s_row = &St[static_cast<size_t>(m) * cols];
+    std::vector<double> shift(static_cast<size_t>(m)), ybar(num_costs * k), nus(num_costs), host_ms(num_costs), cond(num_costs * R);
+    for (int j = 0; j < m; ++j) shift[j] = s_row[j] / Nd;
+    for (size_t s = 0; s < num_costs; ++s)
+        for (int c = 0; c < k; ++c) ybar[s * k + c] = St[static_cast<size_t>(m + 1 + c) * cols + m] / Nd;
+    if (factor == 1) {
+        DenseFit fit(m, k, st);
+        DevBuf<double> betas_dev, rhos_dev, cond_dev;
+        betas_dev.alloc_zero(static_cast<size_t>(R) * cell, st);
+        rhos_dev.alloc_zero(static_cast<size_t>(R) * k, st);
+        cond_dev.alloc_zero(static_cast<size_t>(R), st);
+        std::vector<double> full_betas(cell), full_rhos(static_cast<size_t>(k));  // the full rank's by the back substitution: not returned (the checkpoints' are V^T z)
+        for (size_t s = 0; s < num_costs; ++s) {
+            const double t_cost = now_ms();
+            double device_ms = 0.0;
+            nus[s] = fit.run(dev, St, Kmm, cols, Nd, 1.0 / costs[s], a.V_of(s), a.ldb, full_betas.data(), full_rhos.data(), dense_out != nullptr ? dense_out + s : nullptr, &device_ms, a.Z_of(s));
+            fit.dense.enqueue_prefix_betas(a.V_of(s), a.ldb, a.Z_of(s), static_cast<size_t>(a.ldb), k, a.ranks_dev.p, R, Nd, betas_dev.p, rhos_dev.p, cond_dev.p);
+            LSSVM_HIP_CHECK(hipMemcpyAsync(betas_out + s * R * cell, betas_dev.p, betas_dev.count * sizeof(double), hipMemcpyDeviceToHost, st));
+            LSSVM_HIP_CHECK(hipMemcpyAsync(rhos_out + s * R * k, rhos_dev.p, rhos_dev.count * sizeof(double), hipMemcpyDeviceToHost, st));
+            LSSVM_HIP_CHECK(hipMemcpyAsync(&cond[s * R], cond_dev.p, cond_dev.count * sizeof(double), hipMemcpyDeviceToHost, st));
+            LSSVM_HIP_CHECK(hipStreamSynchronize(st));
+            host_ms[s] = std::max(0.0, now_ms() - t_cost - device_ms);
+        }
+    } else {
+        std::vector<double> L, op(a.op_stride);
+        for (size_t s = 0; s < num_costs; ++s) {
+            const double t_host = now_ms();
+            nus[s] = factor_reduced(St, Kmm, m, cols, Nd, 1.0 / costs[s], L);
+            std::fill(op.begin(), op.end(), 0.0);
+            for (int c = 0; c < k; ++c) {
+                double *z = &op[static_cast<size_t>(m + c) * a.ldb];
+                forward_reduced(St, L, m, c, cols, Nd, z);
+                for (int q = 0; q < R; ++q) {
+                    double *beta = betas_out + (s * R + q) * cell + static_cast<size_t>(c) * m;
+                    std::fill(beta, beta + m, 0.0);
+                    rhos_out[(s * R + q) * k + c] = backward_reduced(St, L, m, a.ranks[q], c, cols, Nd, z, beta);
+                }
+            }
+            invert_lower_rows(L, m, op.data(), static_cast<size_t>(a.ldb));
+            for (int q = 0; q < R; ++q) {
+                double hi = 0.0, lo = DBL_MAX;
+                for (int j = 0; j < a.ranks[q]; ++j) {
+                    const double d = L[static_cast<size_t>(j) * m + j];
+                    hi = std::max(hi, d * d);
+                    lo = std::min(lo, d * d);
+                }
+                cond[s * R + q] = hi / lo;
+            }
+            host_ms[s] = now_ms() - t_host;
+            a.upload_operand(s, op.data());
+        }
+    }
+    a.upload_shift(shift.data(), ybar.data());
+
+    // ---- pass 2: the slabs again, the prefix leverage kernel per cost ----
+    a.inv_n = 1.0 / Nd;
+    a.Y = Y;
+    a.w = weights;
+    a.h_out = leverage_out;
+    a.f_out = fitted_out;
+    a.loo_out = loo_out;
+    a.press = press_out;
+    a.errors = loo_errors_out;
+    prefix_pass(lm, slab_rows, a);
+
+    if (landmarks_out != nullptr) std::copy(lm.begin(), lm.end(), landmarks_out);
+    if (infos != nullptr) {
+        for (size_t o = 0; o < num_costs * R; ++o) {
+            const size_t s = o / R;
+            infos[o] = lssvm_reduced_rank_info{};
+            infos[o].cost = costs[s];
+            infos[o].rank = ranks[o % R];
+            infos[o].jitter = nus[s];
+            infos[o].max_leverage = a.max_leverage[o];
+            infos[o].landmark_ms = info.landmark_ms + a.landmark_ms;
+            infos[o].gram_ms = info.gram_ms;
+            infos[o].leverage_ms = a.leverage_ms[s];
+            infos[o].host_ms = host_ms[s];
+            infos[o].cond_hint = cond[o];
+        }
+    }
+}
+
+template <typename T>
+void Solver<T>::reduced_leverage_prefix(uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *V, const double *shift, const double *Z, size_t num_cols,
+                                        const uint64_t *ranks, size_t num_ranks, double *h_out, double *f_out) {
+    // ---- everything that needs no device (as reduced_leverage) ----
+    Problem<T> &p = reduced_problem("reduced_leverage_prefix", true);
+    check_reduced_arguments(V, 1, rank, slab_rows, p.N_);
+    LSSVM_REQUIRE(V != nullptr && shift != nullptr && h_out != nullptr, "V / shift / h_out must not be NULL");
+    LSSVM_REQUIRE(num_cols <= 4096 && (num_cols == 0 || (Z != nullptr && f_out != nullptr)), "at most 4096 rows of Z; Z / f_out must not be NULL where there are some");
+    check_reduced_rank_list(ranks, num_ranks, rank, 1);
+    const int m = static_cast<int>(rank), k = static_cast<int>(num_cols);
+    const std::vector<uint64_t> lm = resolve_landmarks(landmarks, static_cast<size_t>(m), p.N_);
+
+    const SetOnExit<bool> busy = hold_busy();
+    p.activate();
+    PrefixArgs a(m, k, ranks, num_ranks, 1, false, p.stream());
+    std::vector<double> op(a.op_stride, 0.0);
+    for (int n = 0; n < m; ++n) std::copy(V + static_cast<size_t>(n) * m, V + static_cast<size_t>(n + 1) * m, &op[static_cast<size_t>(n) * a.ldb]);  // (as given, what stands above the diagonal too: the kernel masks it)
+    for (int c = 0; c < k; ++c) std::copy(Z + static_cast<size_t>(c) * m, Z + static_cast<size_t>(c + 1) * m, &op[static_cast<size_t>(m + c) * a.ldb]);
+    a.upload_operand(0, op.data());
+    a.upload_shift(shift, nullptr);
+    a.h_out = h_out;
+    a.f_out = f_out;
+    prefix_pass(lm, slab_rows, a);
+}
+
+template <typename T>
+void Solver<T>::time_leverage_prefix_kernel(uint64_t rank, uint64_t slab_rows, size_t num_cols, const uint64_t *ranks, size_t num_ranks, int repeats, double *prefix_ms_out) {
+    Problem<T> &p = reduced_problem("time_leverage_prefix_kernel", false);  // (the aid times a kernel on the data: the weights do not enter)
+    LSSVM_REQUIRE(repeats >= 1 && repeats <= 1000 && prefix_ms_out != nullptr, "repeats must lie in [1, 1000]; prefix_ms_out must not be NULL");
+    LSSVM_REQUIRE(num_cols >= 1 && num_cols <= static_cast<size_t>(PFX_KMAX), "between 1 and 4 right-hand sides (one launch of the kernel)");
+    const size_t N = p.N_;
+    check_reduced_arguments(prefix_ms_out, 1, rank, slab_rows, N);
+    check_reduced_rank_list(ranks, num_ranks, rank, 1);
+    const int m = static_cast<int>(rank), k = static_cast<int>(num_cols), cols = m + 1 + k, R = static_cast<int>(num_ranks);
+    const std::vector<uint64_t> lm = resolve_landmarks(nullptr, static_cast<size_t>(m), N);
+
+    const SetOnExit<bool> busy = hold_busy();
+    p.activate();
+    hipStream_t st = p.stream();
+    const SlabPlan plan(N, slab_rows);  // (the first slab alone, as time_leverage_kernel)
+    const size_t ld = plan.ld;
+    const std::vector<T> Yh(static_cast<size_t>(k) * N, T(1));
+    const LandmarkBlock<T> block(p, lm, st);
+    const RhsOnDevice<T> rhs(Yh.data(), k, N, st);
+    DevBuf<double> slab, h_dev, f_dev, loo_dev;
+    slab.alloc_zero(static_cast<size_t>(cols) * ld, st);
+    PrefixArgs a(m, k, ranks, num_ranks, 1, false, st);  // V = I, every z of ones, shift = 0
+    std::vector<double> op(a.op_stride, 0.0);
+    for (int n = 0; n < m + k; ++n)
+        for (int j = 0; j < m; ++j) op[static_cast<size_t>(n) * a.ldb + j] = n >= m || n == j ? 1.0 : 0.0;
+    a.upload_operand(0, op.data());
+    a.inv_n = 1.0 / static_cast<double>(N);
+    h_dev.alloc_zero(static_cast<size_t>(R) * ld, st);
+    f_dev.alloc_zero(static_cast<size_t>(R) * k * ld, st);
+    loo_dev.alloc_zero(static_cast<size_t>(R) * k * ld, st);
+    enqueue_slab(block, m, plan, 0, rhs, slab.p, st);
+    LSSVM_HIP_CHECK(hipGetLastError());
+    timed_repeats(st, repeats, prefix_ms_out, [] {}, [&] { a.enqueue(0, 0, k, slab.p, ld, plan.rows(0), h_dev.p, f_dev.p, loo_dev.p, nullptr); });
+}
+
 template <typename T>
 void Solver<T>::time_leverage_kernel(uint64_t rank, uint64_t slab_rows, size_t num_extra, int repeats, double *gram_ms_out, double *leverage_ms_out) {
     Problem<T> &p = reduced_problem("time_leverage_kernel", false);  // (the aid times kernels on the data: the weights do not enter)
@@ -1545,6 +2092,14 @@ template void Solver<float>::landmark_acc(const uint64_t *, uint64_t, int, doubl
 template void Solver<double>::landmark_acc(const uint64_t *, uint64_t, int, double *);
 template void Solver<float>::reduced_leverage(uint64_t, const uint64_t *, uint64_t, const double *, const double *, const double *, size_t, double *, double *);
 template void Solver<double>::reduced_leverage(uint64_t, const uint64_t *, uint64_t, const double *, const double *, const double *, size_t, double *, double *);
+template void Solver<float>::fit_reduced_rank_path(const void *, size_t, const double *, uint64_t, const uint64_t *, uint64_t, const uint64_t *, size_t, const double *, size_t, int, double *,
+                                                   double *, double *, uint64_t *, double *, double *, double *, uint64_t *, lssvm_reduced_rank_info *, lssvm_dense_info *);
+template void Solver<double>::fit_reduced_rank_path(const void *, size_t, const double *, uint64_t, const uint64_t *, uint64_t, const uint64_t *, size_t, const double *, size_t, int, double *,
+                                                    double *, double *, uint64_t *, double *, double *, double *, uint64_t *, lssvm_reduced_rank_info *, lssvm_dense_info *);
+template void Solver<float>::reduced_leverage_prefix(uint64_t, const uint64_t *, uint64_t, const double *, const double *, const double *, size_t, const uint64_t *, size_t, double *, double *);
+template void Solver<double>::reduced_leverage_prefix(uint64_t, const uint64_t *, uint64_t, const double *, const double *, const double *, size_t, const uint64_t *, size_t, double *, double *);
+template void Solver<float>::time_leverage_prefix_kernel(uint64_t, uint64_t, size_t, const uint64_t *, size_t, int, double *);
+template void Solver<double>::time_leverage_prefix_kernel(uint64_t, uint64_t, size_t, const uint64_t *, size_t, int, double *);
 template void Solver<float>::time_leverage_kernel(uint64_t, uint64_t, size_t, int, double *, double *);
 template void Solver<double>::time_leverage_kernel(uint64_t, uint64_t, size_t, int, double *, double *);
 template void Solver<float>::time_gram_kernels(int, double *, double *, double *);

@@ -267,6 +267,56 @@ class CSVM:
         self.last_cg_info = [[dict(info, iterations=0) for info in row] for row in report["infos"]]
         return models, report
 
+    def solve_reduced_rank_path_systems(self, params, A, Y, rank, ranks, costs, landmarks=None, factor="host", sample_weight=None):
+        """The fixed-size models of every row of ``Y`` at every cost of ``costs`` and every prefix rank of ``ranks`` with their leave-one-out report:
+        ``(betas[S, R, k, m], rhos[S, R, k], landmarks[m], report)``.  Boundary of :meth:`fit_reduced_rank_path`; the MI355X backend implements it."""
+        raise NotImplementedError
+
+    def fit_reduced_rank_path(self, data: DataSet, ranks, costs, landmarks=None, factor: str = "host", sample_weight=None):
+        """:meth:`fit_reduced_path` for every PREFIX RANK of ``ranks`` and every cost of ``costs`` from one fit at ``rank = max(ranks)`` (no counterpart in the reference;
+        DESIGN.md section 18): the landmark list is ordered, and the model on its first ``r`` entries, its leverages and its leave-one-out values are prefixes of what the
+        full-rank fit forms.  Returns ``(models, report)``: ``models[s][q]`` is an ordinary :class:`Model` of ``ranks[q]`` support vectors -- the first ``ranks[q]``
+        landmark rows -- with ``params.cost = costs[s]``; it saves, loads and predicts like a :meth:`fit_reduced` model.  ``ranks``: 1 to 16 strictly ascending prefix
+        lengths; ``len(ranks) * len(costs) <= 64``; ``landmarks``: None, at least ``max(ranks)`` distinct point indices in the order that matters (their number is the
+        rank the fit runs at), or ``"greedy"`` / ``"rpcholesky"``.  Every prefix model of a cost uses the jitter of the full rank at that cost, which is no smaller than the one
+        :meth:`fit_reduced` on ``landmarks[:r]`` would take (``report["jitter"]``).  A two-class model file groups its support vectors by class, so every prefix must
+        hold points of both classes.  ``report``: as for :meth:`fit_reduced_path` with a rank axis behind the cost axis (``loo[S, R, N]``, ``loo_accuracy[S, R]`` ...),
+        ``ranks``, ``cond_hint[S, R]`` and ``infos[s][q]``.  ``factor`` and ``sample_weight``: as for :meth:`fit_reduced_path`."""
+        _capi.factor_on_device(factor)
+        if not data.has_labels():
+            raise InvalidParameterError("No labels given for training! Maybe the data is only usable for prediction?")  # csvm.hpp:298
+        labels = data.labels()
+        try:
+            prefix = [int(r) for r in np.asarray(ranks).reshape(-1).tolist()]
+        except (TypeError, ValueError):
+            raise InvalidParameterError("The checkpoints must be a list of integers!") from None
+        if not prefix:
+            raise InvalidParameterError("The rank path takes between 1 and 16 checkpoints, but got 0!")
+        if landmarks is not None and not isinstance(landmarks, str):  # (a selection rule's points are checked once they are known)
+            for r in prefix:
+                _check_landmark_classes(data, np.asarray(landmarks)[:max(r, 0)])  # (before anything is computed)
+        costs = _checked_costs(costs)
+        params = self.params.resolved(data.num_features())
+        rank = max(prefix) if landmarks is None or isinstance(landmarks, str) else len(landmarks)
+        betas, rhos, used, report = self.solve_reduced_rank_path_systems(params, data.data(), data.mapped_labels().reshape(1, -1), rank, prefix, costs, landmarks,
+                                                                          **_capi.factor_keyword(factor), **_weight_keyword(sample_weight))
+        models = []
+        for s, cost in enumerate(costs):
+            row = []
+            for q, r in enumerate(prefix):
+                rows = _check_landmark_classes(data, np.asarray(used)[:r])
+                reduced = DataSet(data.data()[rows], [labels[i] for i in rows.tolist()], real_type=data.real_type)
+                row.append(Model(replace(params, cost=float(cost)), reduced, alpha=np.asarray(betas[s][q][0][:r]).astype(data.real_type), rho=rhos[s][q][0]))
+            models.append(row)
+        report = {name: (value[:, :, 0] if name in ("fitted", "loo", "press", "loo_errors") else value) for name, value in report.items()}
+        report["landmarks"] = np.asarray(used)
+        report["loo_accuracy"] = 1.0 - report["loo_errors"].astype(np.float64) / data.num_data_points()
+        if sample_weight is not None:
+            correct = np.sign(report["loo"]) == np.sign(np.asarray(data.mapped_labels(), dtype=np.float64))[None, None, :]
+            report["loo_accuracy"] = np.average(correct, axis=2, weights=np.asarray(sample_weight, dtype=np.float64))
+        self.last_cg_info = [[dict(info, iterations=0) for info in row] for row in report["infos"]]
+        return models, report
+
     def predict(self, model: Model, data: DataSet):
         if model.num_features() != data.num_features():
             raise InvalidParameterError(f"Number of features per data point ({data.num_features()}) must match the number of features per support vector of the "
@@ -456,6 +506,14 @@ class MI355CSVM(CSVM):
             raise InvalidParameterError(f"The reduced model is fitted on one device, but this backend object shards a solve over {'every visible device' if self.use_devices == 0 else self.use_devices}"
                                         f"{'' if self.use_devices == 0 else ' devices'} (num_devices={self.use_devices})!")
         return backend.fit_reduced_grid(params, A, Y, rank, gammas, costs, landmarks=landmarks, options=self._options, factor=factor, sample_weight=sample_weight, product=product)
+
+    def solve_reduced_rank_path_systems(self, params, A, Y, rank, ranks, costs, landmarks=None, factor="host", sample_weight=None):
+        """``backend.fit_reduced_rank_path`` on device 0: one Gram matrix, one factorisation per cost, one prefix leverage pass per cost.  A backend object of several
+        devices raises, as :meth:`solve_reduced_systems` does."""
+        if self.use_devices != 1:
+            raise InvalidParameterError(f"The reduced model is fitted on one device, but this backend object shards a solve over {'every visible device' if self.use_devices == 0 else self.use_devices}"
+                                        f"{'' if self.use_devices == 0 else ' devices'} (num_devices={self.use_devices})!")
+        return backend.fit_reduced_rank_path(params, A, Y, rank, ranks, costs, landmarks=landmarks, options=self._options, factor=factor, sample_weight=sample_weight)
 
     def _one_device_path(self) -> None:
         if self.use_devices != 1:

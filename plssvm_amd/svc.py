@@ -498,6 +498,68 @@ def fit_reduced_grid_cv(estimator, X, y, rank, Cs, gammas, sample_weight=None, l
     return np.asarray(report["loo_accuracy"], dtype=np.float64), clones
 
 
+def fit_reduced_rank_cv(estimator, X, y, ranks, Cs, sample_weight=None, landmarks="rpcholesky", factor="host"):
+    """:func:`fit_reduced_cv_weighted` at every ``C`` of ``Cs`` AND every prefix rank of ``ranks`` from ONE fit at ``max(ranks)`` landmarks
+    (:meth:`plssvm_amd.csvm.CSVM.fit_reduced_rank_path`): accuracy against model size without a fit per size.  Returns
+    ``(loo_accuracy[len(Cs), len(ranks)], clones[s][q])``: the leave-one-out accuracy over all training points, each predicted by the model on the first ``ranks[q]``
+    landmarks refitted without it, and fitted clones of ``ranks[q]`` support vectors.  The landmark list is ordered: ``"rpcholesky"`` (the default) and ``"greedy"`` deliver
+    their pivots in the order they were chosen; distinct row indices are taken in the order given (their number is then the rank of the fit); None is the library's fixed
+    rule.  Two classes score by the sign of the leave-one-out value, more (one-vs-all) by the argmax over the classes' values, as :func:`fit_reduced_cv`;
+    ``class_weight`` is honoured as in :func:`fit_reduced_cv_weighted` (``w_i = sample_weight[i] x class_weight[y[i]]``, the score is the weighted accuracy); with
+    ``sample_weight`` None and ``class_weight`` None the fit is the unweighted one.  Every prefix model of a cost takes the jitter of the full rank.  ``estimator.C`` is
+    ignored; ``estimator`` itself stays unfitted.  ``len(ranks) <= 16`` and ``len(ranks) * len(Cs) <= 64``."""
+    _capi.factor_on_device(factor)
+    if not isinstance(estimator, SVC):
+        raise InvalidParameterError("estimator must be a plssvm_amd.svc.SVC")
+    X, y = np.asarray(X), np.asarray(y)
+    if X.ndim != 2 or y.ndim != 1 or y.shape[0] != X.shape[0]:
+        raise InvalidParameterError(f"X must be a matrix and y a vector of as many labels as X has rows, but their shapes are {X.shape} and {y.shape}!")
+    Cs = _csvm._checked_costs(Cs)
+    try:
+        ranks = [int(r) for r in np.asarray(ranks).reshape(-1).tolist()]
+    except (TypeError, ValueError):
+        raise InvalidParameterError("The checkpoints must be a list of integers!") from None
+    if not ranks:
+        raise InvalidParameterError("The rank path takes between 1 and 16 checkpoints, but got 0!")
+    params = estimator._params()
+    classes = np.array(sorted(set(y.tolist())))
+    weighted = sample_weight is not None or estimator.class_weight is not None
+    class_weight, weights = _reduced_point_weights(estimator, classes, y, sample_weight) if weighted else (np.ones(len(classes)), None)
+    weight_keyword = _csvm._weight_keyword(weights)
+    svm = make_csvm(params=params)
+    clones = [[SVC(**{**estimator.get_params(), "C": C}) for _ in ranks] for C in Cs]
+    if len(classes) > 2:
+        Xr = np.ascontiguousarray(X, dtype=estimator.real_type)
+        resolved = params.resolved(Xr.shape[1])
+        rank = max(ranks) if landmarks is None or isinstance(landmarks, str) else len(landmarks)
+        betas, rhos, used, report = svm.solve_reduced_rank_path_systems(resolved, Xr, _multiclass.one_vs_all_targets(classes, y, Xr.dtype), rank, ranks, Cs, landmarks,
+                                                                        **_capi.factor_keyword(factor), **weight_keyword)
+        used = np.asarray(used).astype(np.int64)
+        scores = np.array([[float(np.average(classes[np.argmax(report["loo"][s][q], axis=0)] == y, weights=weights)) for q in range(len(ranks))] for s in range(len(Cs))])
+        for s, C in enumerate(Cs):
+            for q, r in enumerate(ranks):
+                clone, rows = clones[s][q], used[:r]
+                at_cost = Parameter(kernel_type=resolved.kernel_type, degree=resolved.degree, gamma=resolved.gamma, coef0=resolved.coef0, cost=C)
+                infos = [dict(report["infos"][s][q], iterations=0) for _ in classes]
+                model = _multiclass.OneVsAllModel(at_cost, classes, np.ascontiguousarray(Xr[rows]), np.asarray(betas[s][q][:, :r]).astype(Xr.dtype), np.asarray(rhos[s][q]).astype(Xr.dtype), infos)
+                nonzero = np.any(model.alpha != 0, axis=0)
+                clone._svm, clone._model = svm, model
+                clone._fit = {
+                    "classes_": classes, "class_weight_": class_weight, "fit_status_": 0, "n_features_in_": int(X.shape[1]), "shape_fit_": tuple(int(v) for v in X.shape),
+                    "n_iter_": np.zeros(len(classes), dtype=np.int64), "support_": rows.astype(np.int32), "support_vectors_": model.support_vectors,
+                    "n_support_": np.array([np.count_nonzero(nonzero & (y[rows] == c)) for c in classes], dtype=np.int32), "dual_coef_": model.alpha, "intercept_": -model.rho,
+                }
+        return scores, clones
+    data = DataSet(X, y.tolist(), real_type=estimator.real_type)
+    models, report = svm.fit_reduced_rank_path(data, ranks, Cs, landmarks, **_capi.factor_keyword(factor), **weight_keyword)
+    for s in range(len(Cs)):
+        for q, r in enumerate(ranks):
+            model = models[s][q]
+            clones[s][q]._set_binary_fit(svm, model, model.data, X, y, class_weight, None, 0)
+            clones[s][q]._fit["support_"] = np.asarray(report["landmarks"])[:r].astype(np.int32)
+    return np.asarray(report["loo_accuracy"], dtype=np.float64), clones
+
+
 def cost_path_scores(estimator, X, y, Cs, X_val, y_val):
     """The validation accuracy of a TWO-class ``estimator`` at every ``C`` of ``Cs``: one cost path (:func:`fit_cost_path`), then ONE resident predictor over all the
     models -- they share their support vectors, so the predictor takes their weight vectors two per pass over the Gram tiles.  Returns ``(scores[m], fitted clones)``."""
