@@ -756,6 +756,66 @@ int lssvm_mi355_fit_reduced_rank_path_f64(const lssvm_params *params, const doub
                                           double *leverage_out, double *fitted_out, double *loo_out, uint64_t *landmarks_out, lssvm_reduced_rank_info *infos,
                                           lssvm_dense_info *dense, const lssvm_mi355_options *options);
 
+/* The fixed-size model from a STREAM of chunks (opt-in): what the fits above keep of the data is S~ = [Phi | 1 | Y]^T diag(w) [Phi | 1 | Y],
+ * (rank + 1 + num_rhs)^2 doubles and additive over rows, so the N points need never be held at once and no resident problem is needed.  A reduced stream is an opaque
+ * handle on device 0 (one HIP stream; upload and compute follow each other, nothing overlaps) that owns
+ *   the m = rank landmark ROWS X_L (m x num_features, row major, the stream's dtype), features zero-padded to a multiple of 16;
+ *   the centre (rbf only; else 0): c_f = (sum_l X_L[l][f], l ascending, in double) / m -- every operand is staged as (double) x_f - c_f: rbf is translation invariant, so
+ *     the function is unchanged and the norm expansion below keeps its digits;
+ *   K_mm (m x m, double): evaluated at creation by the kernel below on the landmarks themselves, the rbf distance forced to 0 on the diagonal (K_mm[l][l] == 1.0) and the
+ *     lower triangle mirrored (symmetric to the bit);
+ *   the running St and one PENDING slab of slab_rows rows x (m + 1 + k) columns (with its sqrt(w) column on a weighted stream), a fill count, and N.
+ * Phi of a chunk: the dot products (x_i - c) . (x_l - c) on v_mfma_f64_16x16x4_f64 (128 landmarks x 128 rows per workgroup, both operands through LDS in steps of 16
+ * features), rbf: D = max(n_i + n_l - 2 x_i . x_l, 0) with the squared norms of the centred rows; a streamed row carries no index, so a row that IS a landmark gets the
+ * expansion's rounding and not an exact 0 (K_mm alone has the exact diagonal).  The kernel values, the Gram sums, the dense steps and the leverage kernel are the ones of
+ * the fits above.
+ * _create_f32 / _f64: params' cost is ignored.  1 <= rank <= 1024; slab_rows: a multiple of 256, 0 = the library's default (65 536); weighted != 0: chunks may carry weights.
+ *   slab_rows bounds the work space: the pending slab, a scratch of its shape for the feature sums and, once _loo or _phi has run, a scratch slab -- about
+ *   3 x slab_rows x (rank + 1 + num_rhs) doubles (lssvm_reduced_stream_info.workspace_bytes reports what is held).
+ * _update: n >= 1 rows X (n x num_features), Y (num_rhs x n, the stream's dtype), w (n doubles >= 0, or NULL = 1.0; a weighted stream only) go behind the pending rows;
+ *   whenever the slab is full it is summed into St exactly as the fits above sum one, and the fill restarts at 0.  The caller's buffers are free when the call returns.
+ *   After any sequence of updates the state is the one a single update of the concatenated rows leaves: every entry of St is summed over the 2048-row ranges of slabs of
+ *   slab_rows rows in row order, so NO result depends on how the stream was cut into chunks.
+ * _solve (non-destructive): the pending rows, zero-padded to a multiple of 256, are summed into a COPY of St; then per cost the dense steps of the fits above, factor 0:
+ *   on the host, 1: on the device (section 15), the jitter rule per cost.  W = S~[m][m], the Gram kernel's own sum of the weights (== N exactly on an unweighted stream),
+ *   stands wherever those take N or W.  betas_out: num_costs x num_rhs x rank, rhos_out: num_costs x num_rhs, infos (may be NULL): num_costs records (cost, jitter,
+ *   gram_ms: the pending rows' sum and the download, host_ms).  update -> solve -> update -> solve leaves, for the second solve, the bits of update -> update -> solve.
+ *   The per-cost leverage operands are kept until the next update, solve or merge.
+ * _loo: after a solve and before the next update; evaluates the chunk's Phi again in scratch slabs of its own and runs the leverage kernel of section 13 per cost:
+ *   leverage_out num_costs x n, fitted_out and loo_out num_costs x num_rhs x n, all double.  The rows must be rows that were streamed in (the caller's contract, not
+ *   checked); a row of weight 0 is a held-out point as in section 16.  Sums over the points (PRESS, error counts) are the caller's.
+ * _export_state: S~ (cols x cols row major, both triangles, the pending rows included as in _solve), K_mm, N and the fingerprint: kernel_type, degree, gamma, coef0, m,
+ *   num_features, num_rhs, dtype and a hash (FNV-1a) of the landmark rows' bytes, LSSVM_REDUCED_STREAM_FINGERPRINT_WORDS words.
+ * _merge_state: adds a foreign exported S~ entrywise into the handle's FLUSHED St (one rounding per entry and merge) and its N to N; the handle's pending rows stay
+ *   pending and are summed behind the merged part; the result depends on the order of the merge calls only.  The multi-process form: every rank streams its shard, one
+ *   of them merges the others' states.
+ * _info: the counts (info may be NULL), the centre (num_features doubles, may be NULL) and K_mm (rank x rank, may be NULL).
+ * LSSVM_ERR_INVALID_ARGUMENT, all before a device is touched: NULL handles / pointers; n == 0; num_rhs == 0; rank 0 or beyond 1024; slab_rows no multiple of 256; for rbf and
+ * polynomial kernels a gamma that is not finite or not above 0; weights on an unweighted stream; a weight that is negative or not finite; a bad cost grid (as for
+ * lssvm_mi355_problem_fit_reduced_loo); factor outside {0, 1}; _solve with N == 0; _loo without a preceding solve or after a later update; a fingerprint that differs. */
+typedef struct lssvm_mi355_reduced_stream lssvm_mi355_reduced_stream;
+#define LSSVM_REDUCED_STREAM_FINGERPRINT_WORDS 9
+typedef struct lssvm_reduced_stream_info {
+    uint64_t num_points;       /* N: rows streamed in and merged in */
+    uint64_t pending;          /* rows in the pending slab */
+    uint64_t rank, num_features, num_rhs, slab_rows;
+    int32_t  weighted, dtype;
+    uint64_t workspace_bytes;  /* device memory the handle holds */
+} lssvm_reduced_stream_info;
+int lssvm_mi355_reduced_stream_create_f32(lssvm_mi355_reduced_stream **out, const lssvm_params *params, const float *landmark_rows, size_t rank, size_t num_features,
+                                          size_t num_rhs, int weighted, uint64_t slab_rows, const lssvm_mi355_options *options);
+int lssvm_mi355_reduced_stream_create_f64(lssvm_mi355_reduced_stream **out, const lssvm_params *params, const double *landmark_rows, size_t rank, size_t num_features,
+                                          size_t num_rhs, int weighted, uint64_t slab_rows, const lssvm_mi355_options *options);
+int lssvm_mi355_reduced_stream_update(lssvm_mi355_reduced_stream *stream, const void *X, const void *Y, const double *weights /* n, or NULL */, size_t n);
+int lssvm_mi355_reduced_stream_solve(lssvm_mi355_reduced_stream *stream, const double *costs, size_t num_costs, int factor, double *betas_out, double *rhos_out,
+                                     lssvm_reduced_loo_info *infos /* num_costs */);
+int lssvm_mi355_reduced_stream_loo(lssvm_mi355_reduced_stream *stream, const void *X, const void *Y, const double *weights /* n, or NULL */, size_t n, double *leverage_out,
+                                   double *fitted_out, double *loo_out);
+int lssvm_mi355_reduced_stream_export_state(lssvm_mi355_reduced_stream *stream, double *gram_out, double *kmm_out, uint64_t *num_points_out, uint64_t *fingerprint_out);
+int lssvm_mi355_reduced_stream_merge_state(lssvm_mi355_reduced_stream *stream, const double *gram, uint64_t num_points, const uint64_t *fingerprint);
+int lssvm_mi355_reduced_stream_info(lssvm_mi355_reduced_stream *stream, lssvm_reduced_stream_info *info, double *centre_out, double *kmm_out);
+int lssvm_mi355_reduced_stream_destroy(lssvm_mi355_reduced_stream *stream);
+
 /* Landmark selection on a resident problem (opt-in): the pivots of a partial Cholesky factorisation of the kernel matrix, chosen greedily or
  * at random in proportion to the residual diagonal (randomly pivoted Cholesky).  The result is a list of point indices for the `landmarks` argument of the entry points
  * above; nothing else changes, and nothing selects it automatically.  Neither rule dominates the other or the fixed shuffle (README.md has the rows of all three kinds).

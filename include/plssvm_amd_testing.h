@@ -83,6 +83,16 @@ int lssvm_mi355_problem_time_leverage_prefix_kernel(lssvm_mi355_problem *p, uint
  * for rbf).  landmarks: `rank` distinct indices < N, or NULL for the library's rule.  Refusals as for lssvm_mi355_problem_landmark_gram, and a product other than 0 or 1. */
 int lssvm_mi355_problem_landmark_acc(lssvm_mi355_problem *p, const uint64_t *landmarks, uint64_t rank, int product, double *D_out);
 
+/* The operator of a reduced stream alone (lssvm_mi355_reduced_stream_*), apart from any fit: phi_out[i * rank + l] = k(x_i, x_L[l]) for the n rows
+ * of the chunk X (n x num_features, the stream's dtype) as the stream evaluates them -- the centred dot products on the matrix cores, the norm expansion for rbf, the
+ * kernel values -- n x rank doubles.  The state is left untouched (the rows go through the stream's scratch slab).  NULL handle / X / phi_out or n == 0:
+ * LSSVM_ERR_INVALID_ARGUMENT before a device is touched. */
+int lssvm_mi355_reduced_stream_phi(lssvm_mi355_reduced_stream *stream, const void *X, size_t n, double *phi_out);
+/* Measurement aid of tests/tools/reduced_stream_timing.py: on the chunk X (1 <= n <= slab_rows rows) the stream's k_cross_product (cross_ms_out[r]) and, at the same
+ * shape -- the chunk's rows and the landmark rows as one resident set, the landmarks by index -- k_landmark_product (landmark_ms_out[r]), device time of repeat r each
+ * after one untimed run.  The state is left untouched. */
+int lssvm_mi355_reduced_stream_time_kernels(lssvm_mi355_reduced_stream *stream, const void *X, size_t n, int repeats, double *cross_ms_out, double *landmark_ms_out);
+
 /* Measurement aid of tests/tools/reduced_loo_timing.py: on ONE slab of this problem (its first min(N, slab_rows) points, `rank` landmarks by the library's rule, an
  * identity V, k columns of ones) the Gram kernels of the fixed-size fit (gram_ms_out[r]: partial tiles and their sum over rank + 1 + k columns) and the leverage kernel
  * (leverage_ms_out[r]), device time of repeat r each after one untimed run of both. */

@@ -54,6 +54,9 @@ EXPORTED_SYMBOLS = [
     "lssvm_mi355_problem_reduced_leverage_prefix", "lssvm_mi355_problem_time_leverage_prefix_kernel",
     "lssvm_mi355_dense_cholesky", "lssvm_mi355_dense_solve", "lssvm_mi355_dense_invert_lower",
     "lssvm_mi355_problem_select_landmarks", "lssvm_mi355_select_landmarks_f32", "lssvm_mi355_select_landmarks_f64",
+    "lssvm_mi355_reduced_stream_create_f32", "lssvm_mi355_reduced_stream_create_f64", "lssvm_mi355_reduced_stream_update", "lssvm_mi355_reduced_stream_solve",
+    "lssvm_mi355_reduced_stream_loo", "lssvm_mi355_reduced_stream_export_state", "lssvm_mi355_reduced_stream_merge_state", "lssvm_mi355_reduced_stream_info",
+    "lssvm_mi355_reduced_stream_destroy", "lssvm_mi355_reduced_stream_phi", "lssvm_mi355_reduced_stream_time_kernels",
     "lssvm_mi355_cg_begin", "lssvm_mi355_cg_step", "lssvm_mi355_cg_finish", "lssvm_mi355_problem_synchronize", "lssvm_mi355_problem_info",
     "lssvm_mi355_measure_bf16_mfma_ceiling", "lssvm_mi355_comm_library_path", "lssvm_mi355_set_io_threads", "lssvm_mi355_set_option", "lssvm_mi355_get_option",
     "lssvm_mi355_libsvm_open", "lssvm_mi355_libsvm_fill_f32", "lssvm_mi355_libsvm_fill_f64", "lssvm_mi355_libsvm_close",
@@ -342,6 +345,42 @@ def reduced_loo_entry(name: str):
             fn.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_size_t, C.c_int, dp, dp]
         else:
             fn.argtypes = [C.POINTER(LssvmParams), C.c_void_p, C.c_size_t, C.c_size_t] + common + outs + [C.c_void_p]
+        fn.restype = C.c_int
+    return fn
+
+
+class LssvmReducedStreamInfo(C.Structure):
+    """``lssvm_reduced_stream_info``: the counts of a reduced stream (``lssvm_mi355_reduced_stream_info``)."""
+    _fields_ = [("num_points", C.c_uint64), ("pending", C.c_uint64), ("rank", C.c_uint64), ("num_features", C.c_uint64), ("num_rhs", C.c_uint64), ("slab_rows", C.c_uint64),
+                ("weighted", C.c_int32), ("dtype", C.c_int32), ("workspace_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+REDUCED_STREAM_FINGERPRINT_WORDS = 9
+
+
+def reduced_stream_entry(name: str):
+    """The entry points of the fixed-size model from a stream of chunks (``lssvm_mi355_reduced_stream_*``; the test aid ``_phi``) with their argument types.  Bound at
+    the first call."""
+    fn = getattr(lib, name)
+    if fn.argtypes is None:
+        dp, up, h = C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_void_p
+        tail = name[len("lssvm_mi355_reduced_stream_"):]
+        fn.argtypes = {
+            "create_f32": [C.POINTER(C.c_void_p), C.POINTER(LssvmParams), C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_uint64, C.c_void_p],
+            "create_f64": [C.POINTER(C.c_void_p), C.POINTER(LssvmParams), C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_uint64, C.c_void_p],
+            "update": [h, C.c_void_p, C.c_void_p, dp, C.c_size_t],
+            "solve": [h, dp, C.c_size_t, C.c_int, dp, dp, C.POINTER(LssvmReducedLooInfo)],
+            "loo": [h, C.c_void_p, C.c_void_p, dp, C.c_size_t, dp, dp, dp],
+            "export_state": [h, dp, dp, up, up],
+            "merge_state": [h, dp, C.c_uint64, up],
+            "info": [h, C.POINTER(LssvmReducedStreamInfo), dp, dp],
+            "phi": [h, C.c_void_p, C.c_size_t, dp],
+            "time_kernels": [h, C.c_void_p, C.c_size_t, C.c_int, dp, dp],
+            "destroy": [h],
+        }[tail]
         fn.restype = C.c_int
     return fn
 

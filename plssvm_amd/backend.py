@@ -24,7 +24,7 @@ from ._capi import LssvmCgInfo, LssvmParams, LssvmPredictInfo, LssvmShard, Optio
 from .exceptions import InvalidParameterError
 from .parameter import Parameter
 
-__all__ = ["Options", "Predictor", "solve_system_of_linear_equations", "solve_refined", "solve_cost_path", "solve_pcg", "fit_reduced", "fit_reduced_loo", "fit_reduced_grid", "select_landmarks", "predict_values", "predict_values_multi", "generate_q", "run_device_kernel", "calculate_w", "ResidentProblem",
+__all__ = ["Options", "Predictor", "solve_system_of_linear_equations", "solve_refined", "solve_cost_path", "solve_pcg", "fit_reduced", "fit_reduced_loo", "fit_reduced_grid", "ReducedStream", "fit_reduced_stream", "select_landmarks", "predict_values", "predict_values_multi", "generate_q", "run_device_kernel", "calculate_w", "ResidentProblem",
            "comm_get_unique_id", "comm_init", "comm_destroy"]
 
 
@@ -773,6 +773,204 @@ class Predictor:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class ReducedStream:
+    """The fixed-size model from a STREAM of chunks (``lssvm_mi355_reduced_stream_*``; opt-in): what :func:`fit_reduced` keeps of the data is
+    additive over rows, so the points need never be held at once.  The handle owns the landmark ROWS (``landmark_rows``: ``m x d``, float32 or float64 -- the stream's
+    dtype), ``K_mm``, the running sums and one pending slab on device 0.  ``params.cost`` is ignored; ``weighted=True``: chunks may carry weights.
+
+    :meth:`update` appends a chunk; :meth:`solve` fits every cost of a grid without consuming the state; :meth:`loo`, after a solve, scores a chunk that was streamed in
+    (leverage, fitted and leave-one-out values per cost); :meth:`export_state` / :meth:`merge` carry the sums between streams of the same landmarks (one stream per
+    shard or process, one of them merges).  No result depends on how the rows were cut into chunks."""
+
+    def __init__(self, params: Parameter, landmark_rows, num_rhs: int = 1, weighted: bool = False, slab_rows: int = 0, options: Options | None = None):
+        XL = _as_matrix(landmark_rows)
+        self.dtype, self.rank, self.num_features, self.num_rhs, self.weighted = XL.dtype, int(XL.shape[0]), int(XL.shape[1]), int(num_rhs), bool(weighted)
+        self._h = C.c_void_p(None)
+        self._costs = 0
+        if not (isinstance(slab_rows, (int, np.integer)) and slab_rows >= 0):
+            raise InvalidParameterError(f"slab_rows must be a multiple of 256 (0: the library's default), but is {slab_rows!r}!")
+        if not (isinstance(num_rhs, (int, np.integer)) and num_rhs >= 0):
+            raise InvalidParameterError(f"The number of right hand sides must be greater than 0, but is {num_rhs!r}!")
+        ps = _params_struct(params, XL.shape[1])
+        create = _capi.reduced_stream_entry(f"lssvm_mi355_reduced_stream_create_{suffix_of(XL.dtype)}")
+        check(create(C.byref(self._h), C.byref(ps), ptr(XL), XL.shape[0], XL.shape[1], self.num_rhs, int(self.weighted), int(slab_rows), options_ptr(options)))
+
+    def _chunk(self, X, Y, sample_weight):
+        X = _as_matrix(X, dtype=self.dtype)
+        if X.shape[1] != self.num_features:
+            raise InvalidParameterError(f"The number of features in the landmark rows ({self.num_features}) must be the same as in the chunk ({X.shape[1]})!")
+        n = X.shape[0]
+        Y2 = np.ascontiguousarray(Y, dtype=self.dtype)
+        if Y2.ndim == 1 and self.num_rhs == 1:
+            Y2 = Y2.reshape(1, -1)
+        if Y2.shape != (self.num_rhs, n):
+            raise InvalidParameterError(f"The right hand sides of a chunk of {n} rows must have the shape ({self.num_rhs}, {n}), but it is {Y2.shape}!")
+        w = None
+        if sample_weight is not None:
+            w = np.ascontiguousarray(sample_weight, dtype=np.float64)
+            if w.shape != (n,):
+                raise InvalidParameterError(f"The number of rows in the chunk ({n}) and the number of weights ({w.size}) must be the same!")
+        return X, Y2, w, n
+
+    def update(self, X, Y, sample_weight=None) -> "ReducedStream":
+        """Append the rows ``X`` (``n x d``) with their right-hand sides ``Y`` (``(k, n)``; ``(n,)`` for one) and, on a weighted stream, weights (None: 1.0)."""
+        X, Y2, w, n = self._chunk(X, Y, sample_weight)
+        check(_capi.reduced_stream_entry("lssvm_mi355_reduced_stream_update")(self._h, ptr(X), ptr(Y2), _capi.weights_ptr(w), n))
+        self._costs = 0
+        return self
+
+    def solve(self, costs, factor: str = "host"):
+        """The fit on every row streamed so far at each cost: ``(betas[S, k, m], rhos[S, k], infos)``, float64.  The state is left as it was: more updates may follow.
+        ``factor``: as for :func:`fit_reduced`."""
+        on_device = _capi.factor_on_device(factor)
+        costs = np.ascontiguousarray(costs, dtype=np.float64).reshape(-1)
+        S, dp = costs.size, C.POINTER(C.c_double)
+        betas, rhos = np.zeros((S, self.num_rhs, self.rank)), np.zeros((S, self.num_rhs))
+        infos = (_capi.LssvmReducedLooInfo * max(S, 1))()
+        check(_capi.reduced_stream_entry("lssvm_mi355_reduced_stream_solve")(self._h, costs.ctypes.data_as(dp), S, int(on_device), betas.ctypes.data_as(dp), rhos.ctypes.data_as(dp), infos))
+        self._costs = S
+        return betas, rhos, [infos[s].as_dict() for s in range(S)]
+
+    def loo(self, X, Y, sample_weight=None):
+        """After :meth:`solve` and before the next :meth:`update`: ``(leverage[S, n], fitted[S, k, n], loo[S, k, n])`` of a chunk that was streamed in, per cost of
+        that solve.  A row of weight 0 is a held-out point: its ``loo`` value is the prediction of a model that never saw it."""
+        X, Y2, w, n = self._chunk(X, Y, sample_weight)
+        S, dp = max(self._costs, 1), C.POINTER(C.c_double)
+        h, f, loo = np.zeros((S, n)), np.zeros((S, self.num_rhs, n)), np.zeros((S, self.num_rhs, n))
+        check(_capi.reduced_stream_entry("lssvm_mi355_reduced_stream_loo")(self._h, ptr(X), ptr(Y2), _capi.weights_ptr(w), n, h.ctypes.data_as(dp), f.ctypes.data_as(dp), loo.ctypes.data_as(dp)))
+        return h, f, loo
+
+    def phi(self, X):
+        """``K(X, X_L)`` (``n x m``, float64) as the stream evaluates it (a test aid, ``lssvm_mi355_reduced_stream_phi``); the state is left untouched."""
+        X = _as_matrix(X, dtype=self.dtype)
+        if X.shape[1] != self.num_features:
+            raise InvalidParameterError(f"The number of features in the landmark rows ({self.num_features}) must be the same as in the chunk ({X.shape[1]})!")
+        out = np.zeros((X.shape[0], self.rank))
+        check(_capi.reduced_stream_entry("lssvm_mi355_reduced_stream_phi")(self._h, ptr(X), X.shape[0], out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def time_kernels(self, X, repeats: int = 10):
+        """``(cross_ms[repeats], landmark_ms[repeats])``: device time of the stream's product kernel on the chunk ``X`` and of its resident sibling at the same shape (a
+        measurement aid, ``lssvm_mi355_reduced_stream_time_kernels``)."""
+        X = _as_matrix(X, dtype=self.dtype)
+        a, b = np.zeros(repeats), np.zeros(repeats)
+        dp = C.POINTER(C.c_double)
+        check(_capi.reduced_stream_entry("lssvm_mi355_reduced_stream_time_kernels")(self._h, ptr(X), X.shape[0], int(repeats), a.ctypes.data_as(dp), b.ctypes.data_as(dp)))
+        return a, b
+
+    def export_state(self) -> dict:
+        """The sums of every row streamed so far: ``{"gram": S~ (m+1+k)^2, "kmm", "num_points", "fingerprint"}`` -- what :meth:`merge` of another stream takes."""
+        cols, dp, up = self.rank + 1 + self.num_rhs, C.POINTER(C.c_double), C.POINTER(C.c_uint64)
+        gram, kmm = np.zeros((cols, cols)), np.zeros((self.rank, self.rank))
+        n, fp = C.c_uint64(0), np.zeros(_capi.REDUCED_STREAM_FINGERPRINT_WORDS, dtype=np.uint64)
+        check(_capi.reduced_stream_entry("lssvm_mi355_reduced_stream_export_state")(self._h, gram.ctypes.data_as(dp), kmm.ctypes.data_as(dp), C.byref(n), fp.ctypes.data_as(up)))
+        return {"gram": gram, "kmm": kmm, "num_points": int(n.value), "fingerprint": fp}
+
+    def merge(self, state: dict) -> "ReducedStream":
+        """Add the exported sums of another stream of the same parameters, landmarks and dtype (refused otherwise) to this one's."""
+        cols = self.rank + 1 + self.num_rhs
+        gram = np.ascontiguousarray(state["gram"], dtype=np.float64)
+        fp = np.ascontiguousarray(state["fingerprint"], dtype=np.uint64)
+        if gram.shape != (cols, cols) or fp.shape != (_capi.REDUCED_STREAM_FINGERPRINT_WORDS,):
+            raise InvalidParameterError(f"The state to merge must hold a ({cols}, {cols}) matrix and a fingerprint of {_capi.REDUCED_STREAM_FINGERPRINT_WORDS} words!")
+        check(_capi.reduced_stream_entry("lssvm_mi355_reduced_stream_merge_state")(self._h, gram.ctypes.data_as(C.POINTER(C.c_double)), int(state["num_points"]),
+                                                                                   fp.ctypes.data_as(C.POINTER(C.c_uint64))))
+        self._costs = 0
+        return self
+
+    def _info(self, centre=None, kmm=None) -> dict:
+        dp = C.POINTER(C.c_double)
+        info = _capi.LssvmReducedStreamInfo()
+        check(_capi.reduced_stream_entry("lssvm_mi355_reduced_stream_info")(self._h, C.byref(info), None if centre is None else centre.ctypes.data_as(dp),
+                                                                            None if kmm is None else kmm.ctypes.data_as(dp)))
+        return info.as_dict()
+
+    @property
+    def info(self) -> dict:
+        return self._info()
+
+    @property
+    def num_points(self) -> int:
+        return int(self._info()["num_points"])
+
+    @property
+    def centre(self) -> np.ndarray:
+        """What every operand is shifted by as it is staged (rbf: the landmarks' mean; else zeros), ``d`` float64."""
+        c = np.zeros(self.num_features)
+        self._info(centre=c)
+        return c
+
+    @property
+    def landmark_gram(self) -> np.ndarray:
+        """``K_mm`` (``m x m``, float64): diagonal exactly 1 for rbf, symmetric to the bit."""
+        kmm = np.zeros((self.rank, self.rank))
+        self._info(kmm=kmm)
+        return kmm
+
+    def close(self):
+        if self._h:
+            _capi.reduced_stream_entry("lssvm_mi355_reduced_stream_destroy")(self._h)
+            self._h = C.c_void_p(None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def _sum_in_row_order(start: float, terms) -> float:
+    """``((start + t_0) + t_1) + ...``: one sequential chain, as the library's own sums over the points run."""
+    return float(np.cumsum(np.concatenate([[start], np.asarray(terms, dtype=np.float64)]))[-1])
+
+
+def fit_reduced_stream(params: Parameter, landmark_rows, chunks, costs, num_rhs: int = 1, factor: str = "host", loo: bool = False, weighted: bool = False, slab_rows: int = 0,
+                       options: Options | None = None, on_scores=None):
+    """:func:`fit_reduced_loo` from a stream of chunks through one :class:`ReducedStream`.  ``chunks``: an iterable of ``(X, Y, w)`` -- ``X``
+    ``(n, d)``, ``Y`` ``(num_rhs, n)``, ``w`` ``(n,)`` weights or None (given only with ``weighted=True``).  One walk over ``chunks`` feeds the stream, the solve gives
+    ``betas[S, k, m]`` and ``rhos[S, k]``; with ``loo=True`` a SECOND walk (``chunks`` must be re-iterable) scores every chunk and the sums over the points are
+    accumulated here in row order: ``press[S, k]``, ``loo_errors[S, k]``, ``max_leverage[S]``, as :func:`fit_reduced_loo` defines them.  ``on_scores(i, X, Y, w, h, f, loo)``
+    is called per chunk of the second walk for what else a caller accumulates.  Returns ``(betas, rhos, report)``; nothing of size N is kept."""
+    costs = _reduced_loo_costs(costs)
+    if loo and iter(chunks) is chunks:
+        raise InvalidParameterError("The leave-one-out scores take a second walk over the chunks: a list or another re-iterable, not an iterator!")
+    with ReducedStream(params, landmark_rows, num_rhs=num_rhs, weighted=weighted, slab_rows=slab_rows, options=options) as stream:
+        fed = 0
+        for X, Y, w in chunks:
+            stream.update(X, Y, w)
+            fed += 1
+        if fed == 0:
+            raise InvalidParameterError("The stream holds no rows: there was no chunk!")
+        betas, rhos, infos = stream.solve(costs, factor=factor)
+        S, k = costs.size, stream.num_rhs
+        report = {"costs": costs.copy(), "num_points": stream.num_points, "jitter": np.array([i["jitter"] for i in infos]), "infos": infos}
+        if loo:
+            press, errors, top = np.zeros((S, k)), np.zeros((S, k), dtype=np.uint64), np.zeros(S)
+            for i, (X, Y, w) in enumerate(chunks):
+                h, f, values = stream.loo(X, Y, w)
+                Y2 = np.asarray(Y, dtype=np.float64).reshape(k, -1)
+                wrong = np.sign(values) != np.sign(Y2)[None, :, :]
+                d2 = (Y2[None, :, :] - values) ** 2
+                if w is not None:
+                    wv = np.asarray(w, dtype=np.float64)
+                    d2, wrong = wv[None, None, :] * d2, wrong & (wv > 0.0)[None, None, :]
+                for s in range(S):
+                    top[s] = max(top[s], float(h[s].max()))
+                    for c in range(k):
+                        press[s, c] = _sum_in_row_order(press[s, c], d2[s, c])
+                errors += wrong.sum(axis=2).astype(np.uint64)
+                if on_scores is not None:
+                    on_scores(i, X, Y2, w, h, f, values)
+            report.update(press=press, loo_errors=errors, max_leverage=top)
+    return betas, rhos, report
 
 
 # ---------------------------------------------------------------------------------------------------------------------

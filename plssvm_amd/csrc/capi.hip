@@ -503,6 +503,84 @@ int lssvm_mi355_predictor_destroy(lssvm_mi355_predictor *predictor) {
     return guarded([&] { delete predictor; });
 }
 
+/* the reduced stream: create / destroy as the predictor; every argument that needs no device is checked before one is touched */
+struct lssvm_mi355_reduced_stream {
+    std::unique_ptr<lssvm::ReducedStreamBase> impl;
+};
+static int create_reduced_stream(lssvm_mi355_reduced_stream **out, const lssvm_params *params, int dtype, const void *landmark_rows, size_t rank, size_t num_features, size_t num_rhs,
+                                 int weighted, uint64_t slab_rows, const lssvm_mi355_options *options) {
+    return guarded([&] {
+        LSSVM_REQUIRE(out != nullptr, "out must not be NULL");
+        *out = nullptr;
+        (void) options_of(options);  // (no tuning knob bears on a stream; the argument keeps the create calls alike)
+        lssvm::check_reduced_stream_arguments(params, landmark_rows, rank, num_features, num_rhs, slab_rows);
+        auto h = std::make_unique<lssvm_mi355_reduced_stream>();
+        h->impl = lssvm::make_reduced_stream(*params, dtype, landmark_rows, rank, num_features, num_rhs, weighted != 0, slab_rows);
+        *out = h.release();
+    });
+}
+int lssvm_mi355_reduced_stream_create_f32(lssvm_mi355_reduced_stream **out, const lssvm_params *params, const float *landmark_rows, size_t rank, size_t num_features, size_t num_rhs,
+                                          int weighted, uint64_t slab_rows, const lssvm_mi355_options *options) {
+    return create_reduced_stream(out, params, LSSVM_DTYPE_F32, landmark_rows, rank, num_features, num_rhs, weighted, slab_rows, options);
+}
+int lssvm_mi355_reduced_stream_create_f64(lssvm_mi355_reduced_stream **out, const lssvm_params *params, const double *landmark_rows, size_t rank, size_t num_features, size_t num_rhs,
+                                          int weighted, uint64_t slab_rows, const lssvm_mi355_options *options) {
+    return create_reduced_stream(out, params, LSSVM_DTYPE_F64, landmark_rows, rank, num_features, num_rhs, weighted, slab_rows, options);
+}
+int lssvm_mi355_reduced_stream_update(lssvm_mi355_reduced_stream *stream, const void *X, const void *Y, const double *weights, size_t n) {
+    return guarded([&] {
+        LSSVM_REQUIRE(stream != nullptr, "stream handle must not be NULL");
+        stream->impl->update(X, Y, weights, n);
+    });
+}
+int lssvm_mi355_reduced_stream_solve(lssvm_mi355_reduced_stream *stream, const double *costs, size_t num_costs, int factor, double *betas_out, double *rhos_out,
+                                     lssvm_reduced_loo_info *infos) {
+    return guarded([&] {
+        LSSVM_REQUIRE(stream != nullptr, "stream handle must not be NULL");
+        stream->impl->solve(costs, num_costs, factor, betas_out, rhos_out, infos);
+    });
+}
+int lssvm_mi355_reduced_stream_loo(lssvm_mi355_reduced_stream *stream, const void *X, const void *Y, const double *weights, size_t n, double *leverage_out, double *fitted_out,
+                                   double *loo_out) {
+    return guarded([&] {
+        LSSVM_REQUIRE(stream != nullptr, "stream handle must not be NULL");
+        stream->impl->loo(X, Y, weights, n, leverage_out, fitted_out, loo_out);
+    });
+}
+int lssvm_mi355_reduced_stream_export_state(lssvm_mi355_reduced_stream *stream, double *gram_out, double *kmm_out, uint64_t *num_points_out, uint64_t *fingerprint_out) {
+    return guarded([&] {
+        LSSVM_REQUIRE(stream != nullptr, "stream handle must not be NULL");
+        stream->impl->export_state(gram_out, kmm_out, num_points_out, fingerprint_out);
+    });
+}
+int lssvm_mi355_reduced_stream_merge_state(lssvm_mi355_reduced_stream *stream, const double *gram, uint64_t num_points, const uint64_t *fingerprint) {
+    return guarded([&] {
+        LSSVM_REQUIRE(stream != nullptr, "stream handle must not be NULL");
+        stream->impl->merge_state(gram, num_points, fingerprint);
+    });
+}
+int lssvm_mi355_reduced_stream_info(lssvm_mi355_reduced_stream *stream, lssvm_reduced_stream_info *info, double *centre_out, double *kmm_out) {
+    return guarded([&] {
+        LSSVM_REQUIRE(stream != nullptr, "stream handle must not be NULL");
+        stream->impl->info(info, centre_out, kmm_out);
+    });
+}
+int lssvm_mi355_reduced_stream_phi(lssvm_mi355_reduced_stream *stream, const void *X, size_t n, double *phi_out) {
+    return guarded([&] {
+        LSSVM_REQUIRE(stream != nullptr, "stream handle must not be NULL");
+        stream->impl->phi(X, n, phi_out);
+    });
+}
+int lssvm_mi355_reduced_stream_time_kernels(lssvm_mi355_reduced_stream *stream, const void *X, size_t n, int repeats, double *cross_ms_out, double *landmark_ms_out) {
+    return guarded([&] {
+        LSSVM_REQUIRE(stream != nullptr, "stream handle must not be NULL");
+        stream->impl->time_kernels(X, n, repeats, cross_ms_out, landmark_ms_out);
+    });
+}
+int lssvm_mi355_reduced_stream_destroy(lssvm_mi355_reduced_stream *stream) {
+    return guarded([&] { delete stream; });
+}
+
 int lssvm_mi355_generate_q_f32(const lssvm_params *params, const float *X, size_t num_points, size_t num_features, float *q_out, const lssvm_mi355_options *options) {
     return guarded([&] { generate_q_one_shot<float>(params, X, num_points, num_features, q_out, options); });
 }

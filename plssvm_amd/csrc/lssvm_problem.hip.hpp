@@ -927,8 +927,27 @@ struct PredictorBase {
 std::unique_ptr<PredictorBase> make_predictor(const Options &opt, const lssvm_params &params, int dtype, const void *sv, size_t nsv, size_t nfeat, const void *alpha, const double *rho,
                                               size_t nvec, bool every_form = false);
 
+/* The fixed-size model from a stream of chunks (lssvm_mi355_reduced_stream_*; lssvm_reduced.hip): the landmark rows, K_mm, the running St and one
+ * pending slab, kept on device 0 across update calls.  include/plssvm_amd.h has the contract of every call. */
+struct ReducedStreamBase {
+    virtual ~ReducedStreamBase() = default;
+    virtual void update(const void *X, const void *Y, const double *w, size_t n) = 0;
+    virtual void solve(const double *costs, size_t num_costs, int factor, double *betas_out, double *rhos_out, lssvm_reduced_loo_info *infos) = 0;
+    virtual void loo(const void *X, const void *Y, const double *w, size_t n, double *h_out, double *f_out, double *loo_out) = 0;
+    virtual void phi(const void *X, size_t n, double *phi_out) = 0;
+    virtual void export_state(double *gram_out, double *kmm_out, uint64_t *num_points_out, uint64_t *fingerprint_out) = 0;
+    virtual void merge_state(const double *gram, uint64_t num_points, const uint64_t *fingerprint) = 0;
+    virtual void info(lssvm_reduced_stream_info *out, double *centre_out, double *kmm_out) const = 0;
+    /* measurement aid (include/plssvm_amd_testing.h): device time of k_cross_product and of k_landmark_product at the same shape, `repeats` runs each after one untimed */
+    virtual void time_kernels(const void *X, size_t n, int repeats, double *cross_ms_out, double *landmark_ms_out) = 0;
+};
+/* what lssvm_mi355_reduced_stream_create_* refuses before a device is touched */
+void check_reduced_stream_arguments(const lssvm_params *params, const void *landmark_rows, size_t rank, size_t num_features, size_t num_rhs, uint64_t slab_rows);
+std::unique_ptr<ReducedStreamBase> make_reduced_stream(const lssvm_params &params, int dtype, const void *landmark_rows, size_t rank, size_t num_features, size_t num_rhs, bool weighted,
+                                                       uint64_t slab_rows);
+
 void check_params(const lssvm_params *params);
-/* weighted LS-SVM: `weights` holds num_points entries, each finite and > 0, whose diagonal terms 1/(C w_i) are finite in the real type T */
+/* weighted LS-SVM:`weights` holds num_points entries, each finite and > 0, whose diagonal terms 1/(C w_i) are finite in the real type T */
 template <typename T>
 void check_weights(const double *weights, size_t num_points, double cost);
 int select_device_checked(int device);

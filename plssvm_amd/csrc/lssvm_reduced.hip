@@ -32,6 +32,12 @@
  * the dense steps per cost are the ones above (the host's solve split into its forward and backward half: z is kept, the back substitution runs on every leading block);
  * in pass 2 k_reduced_leverage_prefix forms Phic V^T as k_reduced_leverage does and takes the running sums of u^2 and u z_c out of its accumulators at the checkpoints.
  * Every prefix model of a cost takes the nu of the full rank.
+ *
+ * The same model from a STREAM of chunks (lssvm_mi355_reduced_stream_*; the end of this file): St is additive over rows, so a handle that owns the
+ * landmark ROWS, K_mm, the running St and one pending slab takes the points piece by piece, without a resident problem.  k_cross_product -- the sibling of
+ * k_landmark_product for rows that are in no problem, both operands centred as they are staged -- evaluates a chunk's D at the slab's fill position; k_kernel_values,
+ * enqueue_gram, the dense steps per cost and k_reduced_leverage are the ones above, unchanged.  The state after any sequence of updates is the state one update of the
+ * concatenated rows leaves: no result depends on the cuts.
  */
 #include "lssvm_dense.hip.hpp"
 #include "lssvm_landmark.hip.hpp"
@@ -39,6 +45,7 @@
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
+#include <cstring>
 #include <memory>
 #include <optional>
 
@@ -2105,5 +2112,577 @@ template void Solver<double>::time_leverage_kernel(uint64_t, uint64_t, size_t, i
 template void Solver<float>::time_gram_kernels(int, double *, double *, double *);
 template void Solver<double>::time_gram_kernels(int, double *, double *, double *);
 
-}  // namespace lssvm
+/* ---- the fixed-size model from a stream of chunks (lssvm_mi355_reduced_stream_*) ---- */
+namespace {
 
+/* n[i] = the sum over the ldx held features (ascending) of (x_if - c_f)^2, in double, as k_row_norms forms it: the squared norms k_cross_product expands the rbf distance
+ * with, of the rows AS THEY ARE STAGED there (centre: ldx doubles, zeros from the last feature on, so a padded feature adds an exact 0) */
+template <typename T>
+__global__ __launch_bounds__(256) void k_centred_norms(const T *__restrict__ X, int ldx, size_t N, const double *__restrict__ centre, double *__restrict__ n) {
+    const size_t i = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= N) return;
+    const T *xi = X + i * ldx;
+    double acc = 0.0;
+    for (int f = 0; f < ldx; ++f) {
+        const double a = static_cast<double>(xi[f]) - centre[f];
+        acc += a * a;
+    }
+    n[i] = acc;
+}
+
+/* The sibling of k_landmark_product for rows that are NOT in a resident problem: D[l][i] of the n rows of `Xc` (a chunk, held padded to ldx features) against the m
+ * landmark ROWS `XL`, held on their own.  Tiling, LDS layout, fragments and the pinned accumulators are k_landmark_product's: 128 landmarks (blockIdx.y) x 128 rows
+ * (blockIdx.x) per workgroup, four waves of 64 x 64, sixteen accumulators of v_mfma_f64_16x16x4_f64 each, both operands through LDS in steps of RG_KC = 16 features.
+ * What differs: the A operand is read from XL and the B operand from Xc, two base pointers and no index list; `centre` (ldx doubles, zeros for a kernel that is not
+ * translation invariant and from the last feature on) is SUBTRACTED from both operands as they are staged -- one f64x2 of it per step and thread, every operand is
+ * (double) x_f - c_f; and D may start at any row of a slab (the host adds the fill position to the pointer), so its stores are 8-byte aligned only.
+ * rbf: D = max(n_i + n_l - 2 x_i . x_l, 0) with norms_c / norms_l of k_centred_norms.  A streamed row carries no index, so there is no "the landmark itself" test: only
+ * `diag` (the K_mm launch: Xc == XL) sets D[l][l] to exactly 0.  Any other kernel type: the dot product.
+ * Landmarks from m on and rows from n on count as zeros and are never read; landmarks from m on are not written, rows from n on up to the end of the workgroup's 128 are
+ * written as zeros -- a slab keeps that much slack behind its last row.  No atomics, no scratch; the order of every sum depends on ldx only. */
+template <typename T>
+__global__ __launch_bounds__(256, 2) void k_cross_product(const T *__restrict__ XL, const T *__restrict__ Xc, int ldx, int n, int m, const double *__restrict__ centre, int kernel_type,
+                                                          const double *__restrict__ norms_l, const double *__restrict__ norms_c, int diag, double *__restrict__ D, size_t ld) {
+    using pair = typename PairOf<T>::type;
+    __shared__ __attribute__((aligned(16))) double As[RG_TW * RG_LS];
+    __shared__ __attribute__((aligned(16))) double Bs[RG_TW * RG_LS];
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int wr = wave >> 1, wc = wave & 1;
+    const int r = lane & 15, qd = lane >> 4;
+    const int l0 = blockIdx.y * RG_TW;      // the workgroup's first landmark
+    const int local0 = blockIdx.x * RG_TW;  // ... and first row of the chunk
+    const int nsteps = ldx / RG_KC;
+
+    // staging: thread -> (point srow [+ 32 p] of the tile, features 2 sseg, 2 sseg + 1 of the step), as k_landmark_product
+    const int srow = tid >> 3, sseg = tid & 7;
+    const T *Ag[4], *Bg[4];
+    bool a_in[4], b_in[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const int la = l0 + srow + 32 * p, ib = local0 + srow + 32 * p;
+        a_in[p] = la < m;
+        b_in[p] = ib < n;
+        Ag[p] = XL + static_cast<size_t>(a_in[p] ? la : 0) * ldx + 2 * sseg;
+        Bg[p] = Xc + static_cast<size_t>(b_in[p] ? ib : 0) * ldx + 2 * sseg;
+    }
+    const double *cg = centre + 2 * sseg;
+    const int lds_w = srow * RG_LS + 2 * sseg;
+    f64x2 sa[4], sb[4];
+    const f64x2 zero2 = { 0.0, 0.0 };
+    auto stage_load = [&](int s) {
+        const f64x2 c2 = *reinterpret_cast<const f64x2 *>(cg + s * RG_KC);
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            sa[p] = zero2;
+            sb[p] = zero2;
+            if (a_in[p]) {
+                const pair v = *reinterpret_cast<const pair *>(Ag[p] + s * RG_KC);
+                sa[p] = f64x2{ static_cast<double>(v[0]) - c2[0], static_cast<double>(v[1]) - c2[1] };
+            }
+            if (b_in[p]) {
+                const pair v = *reinterpret_cast<const pair *>(Bg[p] + s * RG_KC);
+                sb[p] = f64x2{ static_cast<double>(v[0]) - c2[0], static_cast<double>(v[1]) - c2[1] };
+            }
+        }
+    };
+    auto stage_store = [&]() {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            *reinterpret_cast<f64x2 *>(As + lds_w + p * 32 * RG_LS) = sa[p];
+            *reinterpret_cast<f64x2 *>(Bs + lds_w + p * 32 * RG_LS) = sb[p];
+        }
+    };
+
+    f64x4 acc[4][4];
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+            acc[mt][nt] = f64x4{ 0.0, 0.0, 0.0, 0.0 };
+            // the start values live in the accumulators' OWN registers (C == D for every MFMA of a chain), as in k_reduced_gram
+            asm volatile("" : "+v"(acc[mt][nt]));
+        }
+
+    if (nsteps > 0) {
+        stage_load(0);
+        stage_store();
+    }
+    __syncthreads();
+    const double *Ab = As + (wr * 64 + r) * RG_LS + qd;
+    const double *Bb = Bs + (wc * 64 + r) * RG_LS + qd;
+    for (int s = 0; s < nsteps; ++s) {
+        const bool has_next = s + 1 < nsteps;
+        if (has_next) stage_load(s + 1);
+#pragma unroll
+        for (int ks = 0; ks < RG_KC / 4; ++ks) {
+            double av[4], bv[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                av[t] = Ab[t * 16 * RG_LS + ks * 4];
+                bv[t] = Bb[t * 16 * RG_LS + ks * 4];
+            }
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[mt], bv[nt], acc[mt][nt], 0, 0, 0);
+        }
+        __syncthreads();  // (every wave has read this step)
+        if (has_next) {
+            stage_store();
+            __syncthreads();
+        }
+    }
+
+    // a lane holds landmarks l0 + wr 64 + mt 16 + qd + 4 i and rows local0 + wc 64 + nt 16 + r
+    const bool rbf = kernel_type == LSSVM_KERNEL_RBF;
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+        const int local = local0 + wc * 64 + nt * 16 + r;
+        const bool row_in = local < n;
+        const double ni = rbf && row_in ? norms_c[local] : 0.0;
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int l = l0 + wr * 64 + mt * 16 + qd + 4 * i;
+                if (l >= m) continue;
+                double d = acc[mt][nt][i];
+                if (rbf) {
+                    d = fmax((ni + norms_l[l]) - 2.0 * d, 0.0);
+                    if (diag != 0 && l == local) d = 0.0;
+                }
+                D[static_cast<size_t>(l) * ld + local] = row_in ? d : 0.0;
+            }
+    }
+}
+
+/* the sibling of k_reduced_aux for a chunk: column c of `out` (ld doubles apart; the host has added the fill position) is 1 (c = 0) or right-hand side c - 1 of the
+ * chunk-local Y (ldy reals between two right-hand sides), exact zeros from row n on up to the end of the grid's 256-row blocks */
+template <typename T>
+__global__ __launch_bounds__(256) void k_stream_aux(const T *__restrict__ Y, size_t ldy, int n, double *__restrict__ out, size_t ld) {
+    const int local = blockIdx.x * 256 + threadIdx.x;
+    const int c = blockIdx.y;
+    double v = 0.0;
+    if (local < n) v = c == 0 ? 1.0 : static_cast<double>(Y[static_cast<size_t>(c - 1) * ldy + local]);
+    out[static_cast<size_t>(c) * ld + local] = v;
+}
+
+/* Kmm[a][b] = Kmm[b][a] = Phi[b][a] for b <= a: K_mm out of the landmarks' own Phi (column l: landmark l), the lower triangle mirrored -- symmetric to the bit; a copy */
+__global__ __launch_bounds__(256) void k_stream_kmm(const double *__restrict__ Phi, size_t ld, int m, double *__restrict__ Kmm) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= m * m) return;
+    const int a = e / m, b = e % m;
+    Kmm[e] = Phi[static_cast<size_t>(min(a, b)) * ld + max(a, b)];
+}
+
+uint64_t fnv1a(const void *bytes, size_t count) {
+    const unsigned char *p = static_cast<const unsigned char *>(bytes);
+    uint64_t h = 0xcbf29ce484222325ull;
+    for (size_t i = 0; i < count; ++i) h = (h ^ p[i]) * 0x100000001b3ull;
+    return h;
+}
+
+uint64_t bits_of(double v) {
+    uint64_t u;
+    std::memcpy(&u, &v, sizeof u);
+    return u;
+}
+
+constexpr uint64_t STREAM_MAX_SLAB_ROWS = uint64_t{ 1 } << 24;  // (row counts are ints in the kernels)
+
+/* The handle's state (include/plssvm_amd.h has the contract).  Everything runs on ONE stream of device 0, upload and compute one behind the other; every public call
+ * returns with the stream idle, so the caller's buffers are free. */
+template <typename T>
+class ReducedStream final : public ReducedStreamBase {
+  public:
+    ReducedStream(const lssvm_params &params, const void *XL, size_t m, size_t d, size_t k, bool weighted, uint64_t slab_rows) :
+        params_(params), m_(static_cast<int>(m)), d_(static_cast<int>(d)), k_(static_cast<int>(k)), cols_(m_ + 1 + k_), ldx_(round_up(static_cast<long>(d), RG_KC)), weighted_(weighted),
+        slab_rows_(static_cast<size_t>(slab_rows == 0 ? REDUCED_DEFAULT_SLAB_ROWS : slab_rows)), ld_(slab_rows_ + 256), ntri_(tiles_of(cols_) * (tiles_of(cols_) + 1) / 2),
+        max_chunks_(static_cast<int>((slab_rows_ + RG_RANGE - 1) / RG_RANGE)), hash_(fnv1a(XL, m * d * sizeof(T))) {
+        // the kernel function's scalars as LandmarkBlock::kernel_scalars holds them, for data that is held as it is given
+        gamma_ = params.kernel_type == LSSVM_KERNEL_LINEAR ? 1.0 : static_cast<double>(static_cast<T>(params.gamma));
+        coef0_ = static_cast<double>(static_cast<T>(params.coef0));
+        // the centre (rbf only): the landmarks' mean, every feature summed in ascending l, in double
+        centre_host_.assign(static_cast<size_t>(ldx_), 0.0);
+        if (params.kernel_type == LSSVM_KERNEL_RBF) {
+            const T *xl = static_cast<const T *>(XL);
+            for (int f = 0; f < d_; ++f) {
+                double sum = 0.0;
+                for (int l = 0; l < m_; ++l) sum += static_cast<double>(xl[static_cast<size_t>(l) * d_ + f]);
+                centre_host_[f] = sum / static_cast<double>(m_);
+            }
+        }
+
+        select_device_checked(0);
+        stream_.create();
+        hipStream_t st = stream_.s;
+        const size_t m256 = static_cast<size_t>(round_up(m_, 256));
+        XL_.alloc_zero(m256 * ldx_, st);
+        Xc_.alloc_zero(slab_rows_ * ldx_, st);
+        Yc_.alloc_zero(static_cast<size_t>(k_) * slab_rows_, st);
+        centre_.alloc_zero(static_cast<size_t>(ldx_), st);
+        norms_l_.alloc_zero(m256, st);
+        norms_c_.alloc_zero(slab_rows_, st);
+        dev_.Kmm.alloc_zero(static_cast<size_t>(m_) * m_, st);
+        dev_.St.alloc_zero(static_cast<size_t>(ntri_) * RG_TILE, st);
+        St_.alloc_zero(static_cast<size_t>(ntri_) * RG_TILE, st);
+        part_.alloc_zero(static_cast<size_t>(ntri_) * max_chunks_ * RG_TILE, st);
+        D_.alloc_zero(static_cast<size_t>(m_) * std::max(ld_, m256), st);
+        slab_.alloc_zero(static_cast<size_t>(cols_) * ld_, st);
+        if (weighted_) q_.alloc_zero(ld_, st);
+        LSSVM_HIP_CHECK(hipMemcpy2DAsync(XL_.p, static_cast<size_t>(ldx_) * sizeof(T), XL, d * sizeof(T), d * sizeof(T), m, hipMemcpyHostToDevice, st));
+        LSSVM_HIP_CHECK(hipMemcpyAsync(centre_.p, centre_host_.data(), centre_host_.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        const bool rbf = params_.kernel_type == LSSVM_KERNEL_RBF;
+        if (rbf) hipLaunchKernelGGL(k_centred_norms<T>, dim3(static_cast<unsigned>(m256 / 256)), dim3(256), 0, st, XL_.p, ldx_, static_cast<size_t>(m_), centre_.p, norms_l_.p);
+        // K_mm: the new kernel on the landmarks themselves, the diagonal's distance forced to 0; their Phi takes a buffer of its own for the length of this call
+        DevBuf<double> phi_mm;
+        phi_mm.alloc_zero(static_cast<size_t>(m_) * m256, st);
+        hipLaunchKernelGGL(k_cross_product<T>, dim3(static_cast<unsigned>(m256 / RG_TW), (m_ + RG_TW - 1) / RG_TW), dim3(256), 0, st, XL_.p, XL_.p, ldx_, m_, m_, centre_.p, params_.kernel_type,
+                           norms_l_.p, norms_l_.p, 1, D_.p, m256);
+        hipLaunchKernelGGL(k_kernel_values, dim3(static_cast<unsigned>(m256 / 256), m_), dim3(256), 0, st, D_.p, m256, m_, 0, params_.kernel_type, params_.degree, gamma_, coef0_, phi_mm.p);
+        hipLaunchKernelGGL(k_stream_kmm, dim3((m_ * m_ + 255) / 256), dim3(256), 0, st, phi_mm.p, m256, m_, dev_.Kmm.p);
+        LSSVM_HIP_CHECK(hipGetLastError());
+        Kmm_host_.resize(static_cast<size_t>(m_) * m_);
+        LSSVM_HIP_CHECK(hipMemcpyAsync(Kmm_host_.data(), dev_.Kmm.p, Kmm_host_.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        LSSVM_HIP_CHECK(hipStreamSynchronize(st));
+    }
+
+    void update(const void *X, const void *Y, const double *w, size_t n) override {
+        check_rows(X, Y, w, n);
+        activate();
+        hipStream_t st = stream_.s;
+        std::vector<double> sq;  // sqrt(w): std::sqrt on the host, correctly rounded, as upload_per_row forms it
+        if (weighted_) {
+            sq.assign(n, 1.0);
+            if (w != nullptr)
+                for (size_t i = 0; i < n; ++i) sq[i] = std::sqrt(w[i]);
+        }
+        lev_.reset();  // (a solve's operands stand for the rows it saw)
+        for (size_t off = 0; off < n;) {
+            const int np = static_cast<int>(std::min(n - off, slab_rows_ - fill_));
+            enqueue_rows(X, Y, n, off, np, D_.p + fill_, slab_.p + fill_);
+            if (weighted_) LSSVM_HIP_CHECK(hipMemcpyAsync(q_.p + fill_, sq.data() + off, static_cast<size_t>(np) * sizeof(double), hipMemcpyHostToDevice, st));
+            fill_ += static_cast<size_t>(np);
+            N_ += static_cast<uint64_t>(np);
+            off += static_cast<size_t>(np);
+            if (fill_ == slab_rows_) {  // a full slab: into the running St exactly as reduced_gram sums one
+                enqueue_gram(slab_.p, ld_, cols_, static_cast<int>(slab_rows_), max_chunks_, part_.p, St_.p, st, q_.p);
+                fill_ = 0;
+            }
+        }
+        LSSVM_HIP_CHECK(hipStreamSynchronize(st));  // (the caller's buffers and `sq` are free)
+    }
+
+    void solve(const double *costs, size_t num_costs, int factor, double *betas_out, double *rhos_out, lssvm_reduced_loo_info *infos) override {
+        LSSVM_REQUIRE(betas_out != nullptr && rhos_out != nullptr, "betas_out / rhos_out must not be NULL");
+        check_reduced_loo_costs(costs, num_costs);
+        check_reduced_factor(factor);
+        LSSVM_REQUIRE(N_ > 0, "The stream holds no rows yet: solve needs at least one update!");
+        activate();
+        hipStream_t st = stream_.s;
+        lev_.reset();
+        std::vector<double> St;
+        double gram_ms = 0.0;
+        current_gram(St, &gram_ms);
+        const int m = m_, k = k_, cols = cols_;
+        const double W = St[static_cast<size_t>(m) * cols + m];  // the Gram kernel's own sum of the weights: N itself on an unweighted stream
+        LSSVM_REQUIRE(std::isfinite(W) && W > 0.0, "The weights of the streamed rows must have a finite sum greater than 0.0, but it is " + std::to_string(W) + "!");
+
+        auto a = std::make_unique<LeverageArgs>(m, k, num_costs, true, st);
+        const double *s_row = &St[static_cast<size_t>(m) * cols];
+        std::vector<double> shift(static_cast<size_t>(m)), ybar(num_costs * k), nus(num_costs), host_ms(num_costs);
+        for (int j = 0; j < m; ++j) shift[j] = s_row[j] / W;
+        if (factor == 0) {
+            std::vector<double> Bt(a->op_stride), L;
+            for (size_t s = 0; s < num_costs; ++s) {
+                const double t_host = now_ms();
+                nus[s] = host_operand(St, Kmm_host_, m, k, cols, W, costs[s], a->ldb, betas_out + s * k * m, rhos_out + s * k, L, Bt, &ybar[s * k]);
+                host_ms[s] = now_ms() - t_host;
+                a->upload_operand(s, Bt.data());
+                LSSVM_HIP_CHECK(hipStreamSynchronize(st));  // (Bt is filled again for the next cost)
+            }
+        } else {
+            DenseFit fit(m, k, st);
+            for (size_t s = 0; s < num_costs; ++s) {
+                const double t_cost = now_ms();
+                double device_ms = 0.0;
+                nus[s] = fit.run(dev_, St, Kmm_host_, cols, W, 1.0 / costs[s], a->Bt.p + s * a->op_stride, a->ldb, betas_out + s * k * m, rhos_out + s * k, nullptr, &device_ms);
+                for (int c = 0; c < k; ++c) ybar[s * k + c] = St[static_cast<size_t>(m + 1 + c) * cols + m] / W;
+                host_ms[s] = std::max(0.0, now_ms() - t_cost - device_ms);
+            }
+        }
+        a->upload_shift(shift.data(), ybar.data());
+        a->inv_n = 1.0 / W;
+        lev_ = std::move(a);
+        if (infos != nullptr) {
+            for (size_t s = 0; s < num_costs; ++s) {
+                infos[s] = lssvm_reduced_loo_info{};
+                infos[s].cost = costs[s];
+                infos[s].jitter = nus[s];
+                infos[s].gram_ms = gram_ms;
+                infos[s].host_ms = host_ms[s];
+            }
+        }
+    }
+
+    void loo(const void *X, const void *Y, const double *w, size_t n, double *h_out, double *f_out, double *loo_out) override {
+        check_rows(X, Y, w, n);
+        LSSVM_REQUIRE(h_out != nullptr && f_out != nullptr && loo_out != nullptr, "leverage_out / fitted_out / loo_out must not be NULL");
+        LSSVM_REQUIRE(lev_ != nullptr, "loo needs a solve of the rows streamed so far: none has run, or an update followed it!");
+        activate();
+        hipStream_t st = stream_.s;
+        alloc_scratch();
+        const LeverageArgs &a = *lev_;
+        const size_t S = a.num_ops;
+        std::vector<double> wpad;
+        for (size_t off = 0; off < n;) {
+            const int np = static_cast<int>(std::min(n - off, slab_rows_));
+            const size_t np256 = static_cast<size_t>(round_up(np, 256));
+            enqueue_rows(X, Y, n, off, np, D_.p, scratch_.p);
+            if (weighted_) {  // the rows' weights, indexed like the slab's rows, zeros behind them
+                wpad.assign(np256, 0.0);
+                for (int i = 0; i < np; ++i) wpad[i] = w != nullptr ? w[off + i] : 1.0;
+                LSSVM_HIP_CHECK(hipMemcpyAsync(w_.p, wpad.data(), np256 * sizeof(double), hipMemcpyHostToDevice, st));
+            }
+            for (size_t o = 0; o < S; ++o) {
+                a.enqueue(o, scratch_.p, ld_, np, h_.p, f_.p, loo_.p, weighted_ ? w_.p : nullptr);
+                LSSVM_HIP_CHECK(hipMemcpyAsync(h_out + o * n + off, h_.p, static_cast<size_t>(np) * sizeof(double), hipMemcpyDeviceToHost, st));
+                for (int c = 0; c < k_; ++c) {
+                    LSSVM_HIP_CHECK(hipMemcpyAsync(f_out + (o * k_ + c) * n + off, f_.p + static_cast<size_t>(c) * ld_, static_cast<size_t>(np) * sizeof(double), hipMemcpyDeviceToHost, st));
+                    LSSVM_HIP_CHECK(hipMemcpyAsync(loo_out + (o * k_ + c) * n + off, loo_.p + static_cast<size_t>(c) * ld_, static_cast<size_t>(np) * sizeof(double), hipMemcpyDeviceToHost, st));
+                }
+            }
+            LSSVM_HIP_CHECK(hipStreamSynchronize(st));  // (`wpad` is filled again)
+            off += static_cast<size_t>(np);
+        }
+    }
+
+    void phi(const void *X, size_t n, double *phi_out) override {
+        LSSVM_REQUIRE(X != nullptr && phi_out != nullptr, "X / phi_out must not be NULL");
+        LSSVM_REQUIRE(n >= 1, "A chunk holds at least 1 row!");
+        activate();
+        hipStream_t st = stream_.s;
+        alloc_scratch();
+        std::vector<double> colmajor;
+        for (size_t off = 0; off < n;) {
+            const int np = static_cast<int>(std::min(n - off, slab_rows_));
+            enqueue_rows(X, nullptr, n, off, np, D_.p, scratch_.p);
+            colmajor.resize(static_cast<size_t>(m_) * np);
+            LSSVM_HIP_CHECK(hipMemcpy2DAsync(colmajor.data(), static_cast<size_t>(np) * sizeof(double), scratch_.p, ld_ * sizeof(double), static_cast<size_t>(np) * sizeof(double), m_,
+                                             hipMemcpyDeviceToHost, st));
+            LSSVM_HIP_CHECK(hipStreamSynchronize(st));
+            for (int l = 0; l < m_; ++l)
+                for (int i = 0; i < np; ++i) phi_out[(off + i) * m_ + l] = colmajor[static_cast<size_t>(l) * np + i];
+            off += static_cast<size_t>(np);
+        }
+    }
+
+    void export_state(double *gram_out, double *kmm_out, uint64_t *num_points_out, uint64_t *fingerprint_out) override {
+        LSSVM_REQUIRE(gram_out != nullptr && kmm_out != nullptr && num_points_out != nullptr && fingerprint_out != nullptr,
+                      "gram_out / kmm_out / num_points_out / fingerprint_out must not be NULL");
+        activate();
+        std::vector<double> St;
+        current_gram(St, nullptr);
+        std::copy(St.begin(), St.end(), gram_out);
+        std::copy(Kmm_host_.begin(), Kmm_host_.end(), kmm_out);
+        *num_points_out = N_;
+        fingerprint(fingerprint_out);
+    }
+
+    void merge_state(const double *gram, uint64_t num_points, const uint64_t *fp) override {
+        LSSVM_REQUIRE(gram != nullptr && fp != nullptr, "gram / fingerprint must not be NULL");
+        uint64_t own[LSSVM_REDUCED_STREAM_FINGERPRINT_WORDS];
+        fingerprint(own);
+        LSSVM_REQUIRE(std::equal(own, own + LSSVM_REDUCED_STREAM_FINGERPRINT_WORDS, fp),
+                      "The state was exported by a stream of other kernel parameters, landmarks, shapes or dtype: its fingerprint differs!");
+        activate();
+        hipStream_t st = stream_.s;
+        lev_.reset();
+        // entrywise into the FLUSHED St, one rounding per entry; the pending rows stay pending and are summed behind the merged part
+        std::vector<double> tiles(static_cast<size_t>(ntri_) * RG_TILE);
+        LSSVM_HIP_CHECK(hipMemcpyAsync(tiles.data(), St_.p, tiles.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        LSSVM_HIP_CHECK(hipStreamSynchronize(st));
+        const int nt = tiles_of(cols_);
+        for (int bj = 0; bj < nt; ++bj)
+            for (int bk = 0; bk <= bj; ++bk) {
+                double *t = &tiles[static_cast<size_t>(bj * (bj + 1) / 2 + bk) * RG_TILE];
+                for (int a = 0; a < RG_TW && bj * RG_TW + a < cols_; ++a)
+                    for (int b = 0; b < RG_TW && bk * RG_TW + b < cols_; ++b) t[a * RG_TW + b] += gram[static_cast<size_t>(bj * RG_TW + a) * cols_ + bk * RG_TW + b];
+            }
+        LSSVM_HIP_CHECK(hipMemcpyAsync(St_.p, tiles.data(), tiles.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        LSSVM_HIP_CHECK(hipStreamSynchronize(st));
+        N_ += num_points;
+    }
+
+    void info(lssvm_reduced_stream_info *out, double *centre_out, double *kmm_out) const override {
+        if (out != nullptr) {
+            *out = lssvm_reduced_stream_info{};
+            out->num_points = N_;
+            out->pending = static_cast<uint64_t>(fill_);
+            out->rank = static_cast<uint64_t>(m_);
+            out->num_features = static_cast<uint64_t>(d_);
+            out->num_rhs = static_cast<uint64_t>(k_);
+            out->slab_rows = static_cast<uint64_t>(slab_rows_);
+            out->weighted = weighted_ ? 1 : 0;
+            out->dtype = std::is_same_v<T, float> ? LSSVM_DTYPE_F32 : LSSVM_DTYPE_F64;
+            out->workspace_bytes = (centre_.count + norms_l_.count + norms_c_.count + dev_.Kmm.count + dev_.St.count + St_.count + part_.count + D_.count + slab_.count + q_.count + scratch_.count +
+                                    w_.count + h_.count + f_.count + loo_.count) * sizeof(double) + (XL_.count + Xc_.count + Yc_.count) * sizeof(T);
+        }
+        if (centre_out != nullptr) std::copy(centre_host_.begin(), centre_host_.begin() + d_, centre_out);
+        if (kmm_out != nullptr) std::copy(Kmm_host_.begin(), Kmm_host_.end(), kmm_out);
+    }
+
+    void time_kernels(const void *X, size_t n, int repeats, double *cross_ms_out, double *landmark_ms_out) override {
+        LSSVM_REQUIRE(X != nullptr && cross_ms_out != nullptr && landmark_ms_out != nullptr, "X / cross_ms_out / landmark_ms_out must not be NULL");
+        LSSVM_REQUIRE(n >= 1 && n <= slab_rows_ && repeats >= 1, "The timed chunk holds between 1 and slab_rows rows, and repeats is at least 1!");
+        activate();
+        hipStream_t st = stream_.s;
+        const int np = static_cast<int>(n), rows128 = round_up(np, RG_TW);
+        const bool rbf = params_.kernel_type == LSSVM_KERNEL_RBF;
+        const dim3 grid(static_cast<unsigned>(rows128 / RG_TW), (m_ + RG_TW - 1) / RG_TW);
+        LSSVM_HIP_CHECK(hipMemcpy2DAsync(Xc_.p, static_cast<size_t>(ldx_) * sizeof(T), X, static_cast<size_t>(d_) * sizeof(T), static_cast<size_t>(d_) * sizeof(T), n, hipMemcpyHostToDevice, st));
+        if (rbf) hipLaunchKernelGGL(k_centred_norms<T>, dim3(static_cast<unsigned>(round_up(np, 256) / 256)), dim3(256), 0, st, Xc_.p, ldx_, n, centre_.p, norms_c_.p);
+        timed_repeats(st, repeats, cross_ms_out, [] {}, [&] {
+            hipLaunchKernelGGL(k_cross_product<T>, grid, dim3(256), 0, st, XL_.p, Xc_.p, ldx_, np, m_, centre_.p, params_.kernel_type, norms_l_.p, norms_c_.p, 0, D_.p, ld_);
+        });
+        // the sibling at the same shape: the chunk's rows and, behind them, the landmark rows as ONE resident set, the landmarks by index
+        DevBuf<T> both;
+        DevBuf<double> norms;
+        DevBuf<int> lm;
+        const size_t total = n + static_cast<size_t>(m_);
+        both.alloc_zero(total * ldx_, st);
+        norms.alloc_zero(total, st);
+        lm.alloc_zero(static_cast<size_t>(m_), st);
+        std::vector<int> lm_host(static_cast<size_t>(m_));
+        for (int l = 0; l < m_; ++l) lm_host[l] = np + l;
+        LSSVM_HIP_CHECK(hipMemcpyAsync(both.p, Xc_.p, n * ldx_ * sizeof(T), hipMemcpyDeviceToDevice, st));
+        LSSVM_HIP_CHECK(hipMemcpyAsync(both.p + n * ldx_, XL_.p, static_cast<size_t>(m_) * ldx_ * sizeof(T), hipMemcpyDeviceToDevice, st));
+        LSSVM_HIP_CHECK(hipMemcpyAsync(lm.p, lm_host.data(), lm_host.size() * sizeof(int), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_row_norms<T>, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, st, both.p, ldx_, total, norms.p);
+        timed_repeats(st, repeats, landmark_ms_out, [] {}, [&] {
+            hipLaunchKernelGGL(k_landmark_product<T>, grid, dim3(256), 0, st, both.p, ldx_, np, 0, lm.p, m_, params_.kernel_type, norms.p, D_.p, ld_);
+        });
+        LSSVM_HIP_CHECK(hipStreamSynchronize(st));
+    }
+
+  private:
+    void activate() const { LSSVM_HIP_CHECK(hipSetDevice(0)); }
+
+    /* what update and loo refuse before a device is touched */
+    void check_rows(const void *X, const void *Y, const double *w, size_t n) const {
+        LSSVM_REQUIRE(X != nullptr, "X must not be NULL");
+        LSSVM_REQUIRE(Y != nullptr, "The right hand side vector must not be empty!");
+        LSSVM_REQUIRE(n >= 1, "A chunk holds at least 1 row!");
+        LSSVM_REQUIRE(w == nullptr || weighted_, "The stream was created without weights: a chunk of it takes none!");
+        if (w != nullptr)
+            for (size_t i = 0; i < n; ++i)
+                LSSVM_REQUIRE(std::isfinite(w[i]) && w[i] >= 0.0,
+                              "Every weight of the reduced model must be finite and not less than 0.0, but weight " + std::to_string(i) + " is " + std::to_string(w[i]) + "!");
+    }
+
+    void fingerprint(uint64_t *out) const {
+        out[0] = static_cast<uint64_t>(params_.kernel_type);
+        out[1] = static_cast<uint64_t>(static_cast<int64_t>(params_.degree));
+        out[2] = bits_of(params_.gamma);
+        out[3] = bits_of(params_.coef0);
+        out[4] = static_cast<uint64_t>(m_);
+        out[5] = static_cast<uint64_t>(d_);
+        out[6] = static_cast<uint64_t>(k_);
+        out[7] = std::is_same_v<T, float> ? LSSVM_DTYPE_F32 : LSSVM_DTYPE_F64;
+        out[8] = hash_;
+    }
+
+    void alloc_scratch() {
+        if (scratch_.p != nullptr) return;
+        hipStream_t st = stream_.s;
+        scratch_.alloc_zero(static_cast<size_t>(cols_) * ld_, st);
+        h_.alloc_zero(ld_, st);
+        f_.alloc_zero(static_cast<size_t>(k_) * ld_, st);
+        loo_.alloc_zero(static_cast<size_t>(k_) * ld_, st);
+        if (weighted_) w_.alloc_zero(ld_, st);
+    }
+
+    /* the rows off ... off + np - 1 of a chunk of n rows (np <= slab_rows): upload, pad, and [Phi | 1 | Y] of them from `rows_at` on (a slab's first column plus a row
+     * offset; ld_ doubles between two columns), D through `D_at` at the same offset.  Y NULL: Phi alone.  Zeros are written behind the rows up to the next multiple of 256
+     * (the slack every slab keeps). */
+    void enqueue_rows(const void *X, const void *Y, size_t n, size_t off, int np, double *D_at, double *rows_at) {
+        hipStream_t st = stream_.s;
+        const T *Xh = static_cast<const T *>(X) + off * d_;
+        const unsigned b256 = static_cast<unsigned>(round_up(np, 256) / 256);
+        LSSVM_HIP_CHECK(hipMemcpy2DAsync(Xc_.p, static_cast<size_t>(ldx_) * sizeof(T), Xh, static_cast<size_t>(d_) * sizeof(T), static_cast<size_t>(d_) * sizeof(T), static_cast<size_t>(np),
+                                         hipMemcpyHostToDevice, st));
+        if (params_.kernel_type == LSSVM_KERNEL_RBF) hipLaunchKernelGGL(k_centred_norms<T>, dim3(b256), dim3(256), 0, st, Xc_.p, ldx_, static_cast<size_t>(np), centre_.p, norms_c_.p);
+        hipLaunchKernelGGL(k_cross_product<T>, dim3(static_cast<unsigned>(round_up(np, RG_TW) / RG_TW), (m_ + RG_TW - 1) / RG_TW), dim3(256), 0, st, XL_.p, Xc_.p, ldx_, np, m_, centre_.p,
+                           params_.kernel_type, norms_l_.p, norms_c_.p, 0, D_at, ld_);
+        hipLaunchKernelGGL(k_kernel_values, dim3(b256, m_), dim3(256), 0, st, D_at, ld_, np, 0, params_.kernel_type, params_.degree, gamma_, coef0_, rows_at);
+        if (Y != nullptr) {
+            const T *Yh = static_cast<const T *>(Y) + off;
+            LSSVM_HIP_CHECK(hipMemcpy2DAsync(Yc_.p, slab_rows_ * sizeof(T), Yh, n * sizeof(T), static_cast<size_t>(np) * sizeof(T), static_cast<size_t>(k_), hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_stream_aux<T>, dim3(b256, 1 + k_), dim3(256), 0, st, Yc_.p, slab_rows_, np, rows_at + static_cast<size_t>(m_) * ld_, ld_);
+        }
+        LSSVM_HIP_CHECK(hipGetLastError());
+    }
+
+    /* S~ of every row streamed so far, cols x cols row major with both triangles: the pending rows, zero-padded to a multiple of 256, summed into a COPY of St */
+    void current_gram(std::vector<double> &gram, double *gram_ms) {
+        hipStream_t st = stream_.s;
+        LSSVM_HIP_CHECK(hipMemcpyAsync(dev_.St.p, St_.p, St_.count * sizeof(double), hipMemcpyDeviceToDevice, st));
+        const double t0 = now_ms();
+        if (fill_ > 0) {
+            const size_t r256 = static_cast<size_t>(round_up(static_cast<long>(fill_), 256));
+            if (r256 > fill_) {  // what an earlier slab left behind the pending rows
+                LSSVM_HIP_CHECK(hipMemset2DAsync(slab_.p + fill_, ld_ * sizeof(double), 0, (r256 - fill_) * sizeof(double), static_cast<size_t>(cols_), st));
+                if (weighted_) LSSVM_HIP_CHECK(hipMemsetAsync(q_.p + fill_, 0, (r256 - fill_) * sizeof(double), st));
+            }
+            enqueue_gram(slab_.p, ld_, cols_, static_cast<int>(r256), max_chunks_, part_.p, dev_.St.p, st, q_.p);
+        }
+        std::vector<double> tiles(static_cast<size_t>(ntri_) * RG_TILE);
+        LSSVM_HIP_CHECK(hipMemcpyAsync(tiles.data(), dev_.St.p, tiles.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        LSSVM_HIP_CHECK(hipStreamSynchronize(st));
+        if (gram_ms != nullptr) *gram_ms = now_ms() - t0;
+        unpack_tiles(tiles, cols_, gram);
+    }
+
+    const lssvm_params params_;
+    const int m_, d_, k_, cols_, ldx_;
+    const bool weighted_;
+    const size_t slab_rows_, ld_;  // ld_: doubles between two columns of a slab, slab_rows_ and the slack of the kernels' row tiles
+    const int ntri_, max_chunks_;
+    const uint64_t hash_;
+    double gamma_ = 0.0, coef0_ = 0.0;
+    std::vector<double> centre_host_, Kmm_host_;
+    Stream stream_;
+    DevBuf<T> XL_, Xc_, Yc_;
+    DevBuf<double> centre_, norms_l_, norms_c_, St_, part_, D_, slab_, q_, scratch_, w_, h_, f_, loo_;
+    ReducedOnDevice dev_;  // K_mm, and the copy of St a solve works on
+    size_t fill_ = 0;
+    uint64_t N_ = 0;
+    std::unique_ptr<LeverageArgs> lev_;  // the operands of the last solve, until the next update, solve or merge
+};
+
+}  // namespace
+
+void check_reduced_stream_arguments(const lssvm_params *params, const void *landmark_rows, size_t rank, size_t num_features, size_t num_rhs, uint64_t slab_rows) {
+    LSSVM_REQUIRE(params != nullptr, "params must not be NULL!");
+    LSSVM_REQUIRE(params->kernel_type == LSSVM_KERNEL_LINEAR || params->kernel_type == LSSVM_KERNEL_POLYNOMIAL || params->kernel_type == LSSVM_KERNEL_RBF,
+                  "Invalid kernel function " + std::to_string(params->kernel_type) + " given!");
+    if (params->kernel_type != LSSVM_KERNEL_LINEAR)
+        LSSVM_REQUIRE(std::isfinite(params->gamma) && params->gamma > 0.0, "gamma must be finite and greater than 0, but is " + std::to_string(params->gamma) + "!");
+    LSSVM_REQUIRE(landmark_rows != nullptr, "The landmark rows must not be NULL!");
+    LSSVM_REQUIRE(num_features >= 1, "The landmark rows must have at least one feature!");
+    LSSVM_REQUIRE(num_rhs > 0, "The number of right hand sides must be greater than 0!");
+    LSSVM_REQUIRE(num_rhs <= 4096, "at most 4096 right hand sides per stream");
+    LSSVM_REQUIRE(rank >= 1 && rank <= static_cast<size_t>(REDUCED_MAX_RANK), "The rank of the reduced model must lie in [1, " + std::to_string(REDUCED_MAX_RANK) + "], but is " + std::to_string(rank) + "!");
+    LSSVM_REQUIRE(slab_rows % 256 == 0 && slab_rows <= STREAM_MAX_SLAB_ROWS,
+                  "slab_rows must be a multiple of 256 up to " + std::to_string(STREAM_MAX_SLAB_ROWS) + " (0: the library's default), but is " + std::to_string(slab_rows) + "!");
+}
+
+std::unique_ptr<ReducedStreamBase> make_reduced_stream(const lssvm_params &params, int dtype, const void *landmark_rows, size_t rank, size_t num_features, size_t num_rhs, bool weighted,
+                                                       uint64_t slab_rows) {
+    if (dtype == LSSVM_DTYPE_F32) return std::make_unique<ReducedStream<float>>(params, landmark_rows, rank, num_features, num_rhs, weighted, slab_rows);
+    return std::make_unique<ReducedStream<double>>(params, landmark_rows, rank, num_features, num_rhs, weighted, slab_rows);
+}
+
+}  // namespace lssvm

@@ -197,6 +197,51 @@ class CSVM:
         Boundary of :meth:`fit_reduced_path`; the MI355X backend implements it."""
         raise NotImplementedError
 
+    def solve_reduced_stream_systems(self, params, landmark_rows, chunks, costs, num_rhs=1, factor="host", loo=False, weighted=False, on_scores=None):
+        """The fixed-size models over the landmark ROWS ``landmark_rows`` from a stream of ``(X, Y, w)`` chunks at every cost: ``(betas[S, k, m], rhos[S, k], report)``.
+        Boundary of :meth:`fit_reduced_stream`; the MI355X backend implements it."""
+        raise NotImplementedError
+
+    def fit_reduced_stream(self, landmarks: DataSet, chunks, costs=None, factor: str = "host", loo: bool = False):
+        """:meth:`fit_reduced` / :meth:`fit_reduced_path` for data that arrives in pieces (no counterpart in the reference): the N points are never
+        held at once and no resident problem is built.  ``landmarks``: a labelled :class:`DataSet` of the landmark ROWS (both classes present; e.g. rows chosen on a
+        sample with ``backend.select_landmarks``) -- it becomes the data set of the returned models and its label mapping maps the chunks' labels.  ``chunks``: an
+        iterable of :class:`DataSet` or of ``(X, y)`` pairs; with ``loo=True`` it is walked twice and must be re-iterable (a list, not a generator).  ``costs`` None: ONE
+        ordinary :class:`Model` at this object's cost; else a list with one model per cost.  ``loo=True`` returns ``(model(s), report)`` with the report of
+        :meth:`fit_reduced_path` -- ``press``, ``loo_errors``, ``loo_accuracy``, ``max_leverage``, ``jitter`` per cost, summed over the chunks in row order; nothing of
+        size N is kept.  The result does not depend on how the rows are cut into chunks.  No sample weights, no landmark selection from the stream."""
+        _capi.factor_on_device(factor)
+        if not isinstance(landmarks, DataSet) or not landmarks.has_labels():
+            raise InvalidParameterError("The landmarks must be a DataSet of the landmark rows with their labels!")
+        labels = landmarks.different_labels()
+        single = costs is None
+        costs = [float(self.params.cost)] if single else _checked_costs(costs)
+        params = self.params.resolved(landmarks.num_features())
+        real_type = landmarks.real_type
+
+        class _Triples:
+            def __iter__(_self):
+                for chunk in chunks:
+                    X, y = (chunk.data(), chunk.labels()) if isinstance(chunk, DataSet) else chunk
+                    y = np.asarray(y)
+                    known = (y == labels[0]) | (y == labels[1])
+                    if y.ndim != 1 or not np.all(known):
+                        raise InvalidParameterError(f"Every label of a chunk must be one of the landmarks' labels {labels}!")
+                    yield np.asarray(X, dtype=real_type), np.where(y == labels[1], 1.0, -1.0).astype(real_type).reshape(1, -1), None
+
+        t0 = time.perf_counter()
+        betas, rhos, report = self.solve_reduced_stream_systems(params, landmarks.data(), _Triples() if iter(chunks) is not chunks else iter(_Triples()), costs,
+                                                                **_capi.factor_keyword(factor), loo=loo)
+        models = [Model(replace(params, cost=float(cost)), landmarks, alpha=np.asarray(betas[s][0]).astype(real_type), rho=rhos[s][0]) for s, cost in enumerate(costs)]
+        self.last_cg_info = [dict(info, iterations=0, total_runtime_ms=(time.perf_counter() - t0) * 1e3) for info in report["infos"]]
+        result = models[0] if single else models
+        if not loo:
+            return result
+        N = report["num_points"]
+        report = {name: (value[:, 0] if name in ("press", "loo_errors") else value) for name, value in report.items()}
+        report["loo_accuracy"] = 1.0 - report["loo_errors"].astype(np.float64) / N
+        return result, report
+
     def fit_reduced_path(self, data: DataSet, rank: int, costs, landmarks=None, factor: str = "host", sample_weight=None):
         """:meth:`fit_reduced` for every cost of ``costs`` together with exact leave-one-out scores -- leave-one-out with the landmark set held fixed (no counterpart in
         the reference).  Returns ``(models, report)``: one ordinary :class:`Model` per cost, in the order of ``costs``, each with its ``params.cost``
@@ -498,6 +543,14 @@ class MI355CSVM(CSVM):
             raise InvalidParameterError(f"The reduced model is fitted on one device, but this backend object shards a solve over {'every visible device' if self.use_devices == 0 else self.use_devices}"
                                         f"{'' if self.use_devices == 0 else ' devices'} (num_devices={self.use_devices})!")
         return backend.fit_reduced_loo(params, A, Y, rank, costs, landmarks=landmarks, options=self._options, factor=factor, sample_weight=sample_weight)
+
+    def solve_reduced_stream_systems(self, params, landmark_rows, chunks, costs, num_rhs=1, factor="host", loo=False, weighted=False, on_scores=None):
+        """``backend.fit_reduced_stream`` on device 0: one reduced stream fed chunk by chunk, one solve for all costs, and for ``loo`` a second walk.  A backend object of
+        several devices raises, as :meth:`solve_reduced_systems` does."""
+        if self.use_devices != 1:
+            raise InvalidParameterError(f"The reduced model is fitted on one device, but this backend object shards a solve over {'every visible device' if self.use_devices == 0 else self.use_devices}"
+                                        f"{'' if self.use_devices == 0 else ' devices'} (num_devices={self.use_devices})!")
+        return backend.fit_reduced_stream(params, landmark_rows, chunks, costs, num_rhs=num_rhs, factor=factor, loo=loo, weighted=weighted, options=self._options, on_scores=on_scores)
 
     def solve_reduced_grid_systems(self, params, A, Y, rank, gammas, costs, landmarks=None, factor="host", sample_weight=None, product="matrix"):
         """``backend.fit_reduced_grid`` on device 0: per slab and pass the feature sums once for all gammas, one Gram matrix per gamma, one leverage pass per

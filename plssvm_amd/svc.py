@@ -15,6 +15,7 @@ from . import multiclass as _multiclass
 from .csvm import make_csvm
 from .data_set import DataSet
 from .exceptions import InvalidParameterError
+from .model import Model
 from .parameter import Parameter
 
 __all__ = ["SVC", "fit_cost_path", "cost_path_scores"]
@@ -372,6 +373,96 @@ def fit_reduced_weighted(estimator, X, y, rank, sample_weight=None, landmarks=No
     if not isinstance(estimator, SVC):
         raise InvalidParameterError("estimator must be a plssvm_amd.svc.SVC")
     return _fit_reduced(estimator, X, y, rank, landmarks, factor, weighted=True, sample_weight=sample_weight)
+
+
+def fit_reduced_stream(estimator, chunks, landmarks, classes, Cs=None, sample_weight_of=None):
+    """:func:`fit_reduced_weighted` / :func:`fit_reduced_cv_weighted` for data that arrives in pieces (:meth:`plssvm_amd.csvm.CSVM.fit_reduced_stream`, DESIGN.md
+    section 19).  ``chunks``: a re-iterable of ``(X, y)`` pairs (a list, or an object whose ``__iter__`` reads the pieces again).  ``landmarks``: the landmark ROWS
+    ``(m, d)``, or ``(rows, labels)`` -- two classes need the labels, with both classes among them (the model groups its support vectors by class).  ``classes``: every
+    label of the stream, known in advance.  Two classes and one-vs-all alike; one stream, one Gram matrix and one factorisation serve all classes.
+    ``estimator.class_weight`` is honoured as :func:`fit_reduced_weighted` honours it; ``"balanced"`` takes one more walk over the chunks, reading the labels only, for
+    the class counts.  ``sample_weight_of(i, X, y)``: the weights of chunk ``i`` (None: ones).  ``Cs`` None: a fitted clone at ``estimator.C``; else
+    ``(loo_accuracy[len(Cs)], clones)`` from a second walk over the chunks -- the (weighted) leave-one-out accuracy of :func:`fit_reduced_cv_weighted`, accumulated
+    chunk by chunk.  ``support_`` is empty: the landmarks are rows of their own, not indices."""
+    if not isinstance(estimator, SVC):
+        raise InvalidParameterError("estimator must be a plssvm_amd.svc.SVC")
+    if iter(chunks) is chunks:
+        raise InvalidParameterError("The chunks are walked more than once: a list or another re-iterable, not an iterator!")
+    rows, row_labels = landmarks if isinstance(landmarks, tuple) else (landmarks, None)
+    rows = np.ascontiguousarray(rows, dtype=estimator.real_type)
+    classes = np.array(sorted(set(np.asarray(classes).tolist())))
+    if rows.ndim != 2 or len(classes) < 2:
+        raise InvalidParameterError("The landmarks must be a matrix of rows and the classes at least two labels!")
+    binary = len(classes) == 2
+    if row_labels is not None:
+        row_labels = np.asarray(row_labels)
+        if row_labels.shape != (rows.shape[0],):
+            raise InvalidParameterError(f"The number of landmark rows ({rows.shape[0]}) and of their labels ({row_labels.size}) must be the same!")
+    if binary and (row_labels is None or set(row_labels.tolist()) != set(classes.tolist())):
+        raise InvalidParameterError("A two-class model groups its support vectors by class: the landmarks must come with their labels, of both classes!")
+    params = estimator._params()
+    resolved = params.resolved(rows.shape[1])
+    cw = estimator.class_weight
+    if isinstance(cw, str) and cw == "balanced":  # the class counts of the whole stream: one walk over the labels
+        counts = np.zeros(len(classes))
+        for _, y in chunks:
+            counts += np.array([np.count_nonzero(np.asarray(y) == c) for c in classes], dtype=np.float64)
+        class_weight = counts.sum() / (len(classes) * counts)
+    else:
+        class_weight = estimator._class_weight(classes, classes)
+    weighted = cw is not None or sample_weight_of is not None
+
+    class _Triples:
+        def __iter__(_self):
+            for i, (X, y) in enumerate(chunks):
+                X, y = np.ascontiguousarray(X, dtype=estimator.real_type), np.asarray(y)
+                at = np.searchsorted(classes, y)
+                if y.ndim != 1 or y.shape[0] != X.shape[0] or not np.all(classes[np.minimum(at, len(classes) - 1)] == y):
+                    raise InvalidParameterError(f"Chunk {i}: y must be a vector of as many labels as X has rows, each one of {classes.tolist()}!")
+                w = None
+                if weighted:
+                    sw = None if sample_weight_of is None else sample_weight_of(i, X, y)
+                    w = (np.ones(y.size) if sw is None else np.asarray(sw, dtype=np.float64)) * class_weight[at]
+                Y = np.where(y == classes[1], 1.0, -1.0).astype(X.dtype).reshape(1, -1) if binary else _multiclass.one_vs_all_targets(classes, y, X.dtype)
+                yield X, Y, w
+
+    single = Cs is None
+    costs = [float(estimator.C)] if single else _csvm._checked_costs(Cs)
+    correct, total = np.zeros(len(costs)), [0.0]
+
+    def on_scores(i, X, Y2, w, h, f, loo):  # the (weighted) number of points whose leave-one-out value names their class
+        wv = np.ones(Y2.shape[1]) if w is None else np.asarray(w, dtype=np.float64)
+        total[0] += float(wv.sum())
+        for s in range(len(costs)):
+            right = np.sign(loo[s, 0]) == np.sign(Y2[0]) if binary else np.argmax(loo[s], axis=0) == np.argmax(Y2, axis=0)
+            correct[s] += float(wv[right].sum())
+
+    svm = make_csvm(params=params)
+    betas, rhos, report = svm.solve_reduced_stream_systems(resolved, rows, _Triples(), costs, num_rhs=1 if binary else len(classes), loo=not single, weighted=weighted,
+                                                           on_scores=None if single else on_scores)
+    clones = [SVC(**{**estimator.get_params(), "C": C}) for C in costs]
+    N = int(report["num_points"])
+    for s, (C, clone) in enumerate(zip(costs, clones)):
+        at_cost = Parameter(kernel_type=resolved.kernel_type, degree=resolved.degree, gamma=resolved.gamma, coef0=resolved.coef0, cost=C)
+        info = dict(report["infos"][s], iterations=0)
+        if binary:
+            model = Model(at_cost, DataSet(rows, row_labels.tolist(), real_type=estimator.real_type), alpha=np.asarray(betas[s][0]).astype(rows.dtype), rho=rhos[s][0])
+            alpha, sv, sv_labels = np.asarray(model.alpha).reshape(1, -1), model.support_vectors(), np.asarray(model.labels())
+            intercept = np.array([-model.rho], dtype=alpha.dtype)
+        else:
+            model = _multiclass.OneVsAllModel(at_cost, classes, rows, np.asarray(betas[s]).astype(rows.dtype), np.asarray(rhos[s]).astype(rows.dtype), [info for _ in classes])
+            alpha, sv, sv_labels, intercept = model.alpha, model.support_vectors, row_labels, -model.rho
+        nonzero = np.any(alpha != 0, axis=0)
+        clone._svm, clone._model = svm, model
+        clone._fit = {
+            "classes_": classes, "class_weight_": class_weight, "fit_status_": 0, "n_features_in_": int(rows.shape[1]), "shape_fit_": (N, int(rows.shape[1])),
+            "n_iter_": 0 if binary else np.zeros(len(classes), dtype=np.int64), "support_": np.zeros(0, dtype=np.int32), "support_vectors_": sv,
+            "n_support_": np.array([0 if sv_labels is None else np.count_nonzero(nonzero & (sv_labels == c)) for c in classes], dtype=np.int32), "dual_coef_": alpha,
+            "intercept_": intercept,
+        }
+    if single:
+        return clones[0]
+    return correct / total[0], clones
 
 
 def _landmarks_of(svm, landmarks):
