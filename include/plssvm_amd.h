@@ -300,6 +300,23 @@ int lssvm_mi355_predictor_predict_multi(lssvm_mi355_predictor *predictor, const 
 int lssvm_mi355_predictor_create_resident(lssvm_mi355_predictor **out, const lssvm_params *params, int dtype, const void *support_vectors, size_t num_support_vectors,
                                           size_t num_features, const void *alphas, const double *rhos, size_t num_vectors, const lssvm_mi355_options *options);
 
+/* The same handle once more, with every form of `create_resident` AND the models beyond the one-pass kernels resident on the kernels that walk feature panels inside
+ * a tile: fp32 rbf / polynomial models (non-negative degree) beyond 512 padded features (384 for rbf and on bf16 planes), fp64 rbf / polynomial models (gamma > 0,
+ * non-negative degree) beyond 256 -- 784-feature image data, for one.  (`create`, `create_multi` and `create_resident` keep their documented routing: such a model
+ * takes the one-shot path there.)  Arguments, their validation and the error texts are those of `create_multi`, refused before a device is touched; `predict`,
+ * `predict_multi` and `destroy` work on the handle as on any other.  A model that is not that wide gives a handle indistinguishable from a `create_resident` handle.
+ * The fp32 panel form keeps what the wide fp32 form keeps, the planes padded to whole 128-feature panels; a batch runs on the full-square panel kernel, chunked as
+ * the one-shot call chunks it.  The polynomial kernel and rbf within the folded form's range take two weight vectors per launch (vectors_per_launch == 2), rbf
+ * beyond it (or with option rbf_fold = 0) one.  It declines what the wide fp32 form declines -- and a negative polynomial degree, which the panel kernels do not
+ * take --: resident == 0, the one-shot call's values.  The fp64 panel form is prepared as lssvm_mi355_predict_values_f64 prepares it (padding to 64-feature panels,
+ * centre, scale), takes two vectors per launch and never declines a batch.
+ * Every column has the bits of a single-vector `create_panels` handle of (alphas[v], rhos[v]); fp64 and fp32 rbf values are those of
+ * lssvm_mi355_predict_values_multi_*, fp32 polynomial values differ from it by the rounding of the planes' power-of-two scale, as in the wide fp32 form.
+ * What the handle saves is the upload and preparation of the support vectors per call and half of the product launches of a model of several vectors; a call of one
+ * weight vector on a batch of several times the support vectors' size is mostly the batch's own upload and product and gains little (README, "Wide models"). */
+int lssvm_mi355_predictor_create_panels(lssvm_mi355_predictor **out, const lssvm_params *params, int dtype, const void *support_vectors, size_t num_support_vectors,
+                                        size_t num_features, const void *alphas, const double *rhos, size_t num_vectors, const lssvm_mi355_options *options);
+
 /* ------------------------------------------------------------------------------------------------------------------ */
 /* fine-grained entry points for kernel-level parity tests: the protected members the reference's backend tests re-export  */
 /* (tests/backends/HIP/mock_hip_csvm.hpp:22-44): generate_q, run_device_kernel, calculate_w                           */

@@ -33,7 +33,7 @@ EXPORTED_SYMBOLS = [
     "lssvm_mi355_predict_values_multi_f32", "lssvm_mi355_predict_values_multi_f64",
     "lssvm_mi355_solve_weighted_f32", "lssvm_mi355_solve_weighted_f64", "lssvm_mi355_problem_set_weights", "lssvm_mi355_solve_refined_f64",
     "lssvm_mi355_predictor_create", "lssvm_mi355_predictor_predict", "lssvm_mi355_predictor_destroy", "lssvm_mi355_predictor_create_multi", "lssvm_mi355_predictor_predict_multi",
-    "lssvm_mi355_predictor_create_resident",
+    "lssvm_mi355_predictor_create_resident", "lssvm_mi355_predictor_create_panels",
     "lssvm_mi355_generate_q_f32", "lssvm_mi355_generate_q_f64", "lssvm_mi355_run_device_kernel_f32", "lssvm_mi355_run_device_kernel_f64",
     "lssvm_mi355_calculate_w_f32", "lssvm_mi355_calculate_w_f64",
     "lssvm_mi355_shard_blocks", "lssvm_mi355_set_shard_weights", "lssvm_mi355_problem_rebalance", "lssvm_mi355_comm_get_unique_id", "lssvm_mi355_comm_init", "lssvm_mi355_comm_destroy",
@@ -188,10 +188,10 @@ def predict_multi_entry(dtype):
 
 
 def predictor_multi_entry(name: str):
-    """``lssvm_mi355_predictor_create_multi`` / ``lssvm_mi355_predictor_create_resident`` / ``lssvm_mi355_predictor_predict_multi`` with its argument types.  Bound at the first call, like the weighted entry points."""
+    """``lssvm_mi355_predictor_create_multi`` / ``lssvm_mi355_predictor_create_resident`` / ``lssvm_mi355_predictor_create_panels`` / ``lssvm_mi355_predictor_predict_multi`` with its argument types.  Bound at the first call, like the weighted entry points."""
     fn = getattr(lib, name)
     if fn.argtypes is None:
-        if name in ("lssvm_mi355_predictor_create_multi", "lssvm_mi355_predictor_create_resident"):
+        if name in ("lssvm_mi355_predictor_create_multi", "lssvm_mi355_predictor_create_resident", "lssvm_mi355_predictor_create_panels"):
             fn.argtypes = [C.POINTER(C.c_void_p), C.POINTER(LssvmParams), C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.POINTER(C.c_double), C.c_size_t, C.c_void_p]
         else:
             fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.POINTER(LssvmPredictInfo)]

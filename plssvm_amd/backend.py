@@ -699,9 +699,13 @@ class Predictor:
     which adds the float64 one (rbf / polynomial, at most 256 features, two weight vectors per pass) and the float32 one beyond 128 features (rbf up to 384 features,
     polynomial up to 512 on f16 planes and 384 on bf16 planes; two weight vectors per pass).  The default keeps the routing of ``_create`` / ``_create_multi``, where a
     float64 rbf / polynomial model and a float32 model of more than 128 features take the one-shot path.  Float64 and rbf values are the same bits either way; a wide
-    float32 polynomial model's differ from the one-shot call's by the rounding of the operand planes' scale (a few eps of the summand scale)."""
+    float32 polynomial model's differ from the one-shot call's by the rounding of the operand planes' scale (a few eps of the summand scale).
 
-    def __init__(self, params: Parameter, support_vectors, alpha, rho, options: Options | None = None, every_form: bool = False):
+    ``panels=True`` creates the model through ``lssvm_mi355_predictor_create_panels``: every form of ``every_form=True``, and the models beyond those widths on the
+    kernels that walk feature panels inside a tile (float32 rbf / polynomial beyond 384 / 512 features, float64 beyond 256; two weight vectors per pass for the
+    polynomial kernel, float64 rbf and float32 rbf with folded records).  A model below those widths behaves as with ``every_form=True``."""
+
+    def __init__(self, params: Parameter, support_vectors, alpha, rho, options: Options | None = None, every_form: bool = False, panels: bool = False):
         sv = _as_matrix(support_vectors)
         alpha = np.ascontiguousarray(alpha, dtype=sv.dtype)
         self.dtype, self.num_features = sv.dtype, int(sv.shape[1])
@@ -720,10 +724,10 @@ class Predictor:
             if alpha.size != sv.shape[0]:
                 raise InvalidParameterError(f"The number of support vectors ({sv.shape[0]}) and number of weights ({alpha.size}) must be the same!")
             self.num_vectors = None  # (one weight vector: the values are a vector, not a matrix of one column)
-            k, rhos = 1, np.array([float(rho)], dtype=np.float64)  # (every_form: a handle of one vector, used through lssvm_mi355_predictor_predict like any other)
+            k, rhos = 1, np.array([float(rho)], dtype=np.float64)  # (every_form / panels: a handle of one vector, used through lssvm_mi355_predictor_predict like any other)
         ps = _params_struct(params, sv.shape[1])
-        if alpha.ndim == 2 or every_form:
-            create = "lssvm_mi355_predictor_create_resident" if every_form else "lssvm_mi355_predictor_create_multi"
+        if alpha.ndim == 2 or every_form or panels:
+            create = "lssvm_mi355_predictor_create_panels" if panels else ("lssvm_mi355_predictor_create_resident" if every_form else "lssvm_mi355_predictor_create_multi")
             check(_capi.predictor_multi_entry(create)(C.byref(self._h), C.byref(ps), _capi.dtype_code(sv.dtype), ptr(sv), sv.shape[0], sv.shape[1], ptr(alpha),
                                                       rhos.ctypes.data_as(C.POINTER(C.c_double)), k, options_ptr(options)))
             return

@@ -460,9 +460,9 @@ int lssvm_mi355_predictor_create(lssvm_mi355_predictor **out, const lssvm_params
         *out = h.release();
     });
 }
-/* _create_multi and _create_resident: one validation, one set of error texts; `every_form`: every resident form the library has (the fp64 one and the fp32 one beyond 128 features as well) */
+/* _create_multi, _create_resident and _create_panels: one validation, one set of error texts; `forms`: the resident forms the handle may take (lssvm::FORMS_*) */
 static int create_predictor_of_vectors(lssvm_mi355_predictor **out, const lssvm_params *params, int dtype, const void *support_vectors, size_t num_support_vectors, size_t num_features,
-                                       const void *alphas, const double *rhos, size_t num_vectors, const lssvm_mi355_options *options, bool every_form) {
+                                       const void *alphas, const double *rhos, size_t num_vectors, const lssvm_mi355_options *options, int forms) {
     return guarded([&] {
         LSSVM_REQUIRE(out != nullptr, "out must not be NULL");
         *out = nullptr;
@@ -472,17 +472,21 @@ static int create_predictor_of_vectors(lssvm_mi355_predictor **out, const lssvm_
         LSSVM_REQUIRE(alphas != nullptr, "The number of support vectors and number of weights must be the same!");  // csvm.cpp:192
         LSSVM_REQUIRE(rhos != nullptr, "rhos must hold one value per weight vector");
         auto h = std::make_unique<lssvm_mi355_predictor>();
-        h->impl = lssvm::make_predictor(options_of(options), *params, dtype, support_vectors, num_support_vectors, num_features, alphas, rhos, num_vectors, every_form);
+        h->impl = lssvm::make_predictor(options_of(options), *params, dtype, support_vectors, num_support_vectors, num_features, alphas, rhos, num_vectors, forms);
         *out = h.release();
     });
 }
 int lssvm_mi355_predictor_create_multi(lssvm_mi355_predictor **out, const lssvm_params *params, int dtype, const void *support_vectors, size_t num_support_vectors,
                                        size_t num_features, const void *alphas, const double *rhos, size_t num_vectors, const lssvm_mi355_options *options) {
-    return create_predictor_of_vectors(out, params, dtype, support_vectors, num_support_vectors, num_features, alphas, rhos, num_vectors, options, false);
+    return create_predictor_of_vectors(out, params, dtype, support_vectors, num_support_vectors, num_features, alphas, rhos, num_vectors, options, lssvm::FORMS_DEFAULT);
 }
 int lssvm_mi355_predictor_create_resident(lssvm_mi355_predictor **out, const lssvm_params *params, int dtype, const void *support_vectors, size_t num_support_vectors,
                                           size_t num_features, const void *alphas, const double *rhos, size_t num_vectors, const lssvm_mi355_options *options) {
-    return create_predictor_of_vectors(out, params, dtype, support_vectors, num_support_vectors, num_features, alphas, rhos, num_vectors, options, true);
+    return create_predictor_of_vectors(out, params, dtype, support_vectors, num_support_vectors, num_features, alphas, rhos, num_vectors, options, lssvm::FORMS_EVERY);
+}
+int lssvm_mi355_predictor_create_panels(lssvm_mi355_predictor **out, const lssvm_params *params, int dtype, const void *support_vectors, size_t num_support_vectors,
+                                        size_t num_features, const void *alphas, const double *rhos, size_t num_vectors, const lssvm_mi355_options *options) {
+    return create_predictor_of_vectors(out, params, dtype, support_vectors, num_support_vectors, num_features, alphas, rhos, num_vectors, options, lssvm::FORMS_PANELS);
 }
 int lssvm_mi355_predictor_predict(lssvm_mi355_predictor *predictor, const void *predict_points, int mem_kind, size_t num_predict_points, void *out, lssvm_predict_info *info) {
     return guarded([&] {

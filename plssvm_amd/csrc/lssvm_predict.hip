@@ -460,8 +460,8 @@ class ResidentF32 {
   public:
     static constexpr bool declines_batches = true;  // (the one-shot path's inputs stay needed: alpha on the host, the support vectors through fetch_support_vectors)
 
-    bool prepare(const PredictModel<float> &m, const float *sv, const float *alpha, bool every_form, hipStream_t s) {
-        const bool resident = prepare_or_decline(m, sv, alpha, every_form, s);
+    bool prepare(const PredictModel<float> &m, const float *sv, const float *alpha, int forms, hipStream_t s) {
+        const bool resident = prepare_or_decline(m, sv, alpha, forms, s);
         if (!resident) reset();
         return resident;
     }
@@ -483,13 +483,15 @@ class ResidentF32 {
     }
 
     /* fp32, rbf / polynomial, a split Gram mode: the support vectors' side of the product, once.  At most 128 features -- or, `every_form`, every width the one-shot
-     * call runs on the one-pass split kernels (v2_eligible and not wide_nonlinear: the 128-row full-square kernels with the row panel in registers). */
-    bool prepare_or_decline(const PredictModel<float> &m, const float *sv, const float *alpha, bool every_form, hipStream_t s) {
+     * call runs on the one-pass split kernels (v2_eligible and not wide_nonlinear: the 128-row full-square kernels with the row panel in registers) -- or,
+     * FORMS_PANELS, every width beyond those as well (wide_nonlinear: the panel kernel, planes padded to whole 128-feature panels). */
+    bool prepare_or_decline(const PredictModel<float> &m, const float *sv, const float *alpha, int forms, hipStream_t s) {
         const bool beyond128 = round_up(static_cast<long>(m.nfeat), 64) > 128;
-        if ((beyond128 && (!every_form || wide_nonlinear(m.opt, m.params, false, m.nfeat))) || m.opt.gram_mode == 0 || m.opt.tile_kernel == 1) return false;
+        wide_ = wide_nonlinear(m.opt, m.params, false, m.nfeat);
+        if ((beyond128 && (forms < FORMS_EVERY || (wide_ && forms < FORMS_PANELS))) || m.opt.gram_mode == 0 || m.opt.tile_kernel == 1) return false;
         if (m.params.kernel_type == LSSVM_KERNEL_RBF && (m.opt.rbf_form == 1 || m.opt.rbf_form == 3)) return false;  // (the direct kernel / the grid planes asked for: the one-shot path has them)
         S_.upload(sv, LSSVM_MEM_HOST, m.nsv, m.nfeat, 0, s);
-        if (!v2_eligible(m.opt, S_.ldx, false)) return false;
+        if (!wide_ && !v2_eligible(m.opt, S_.ldx, false)) return false;
         const bool rbf = m.params.kernel_type == LSSVM_KERNEL_RBF;
         if (rbf) {
             column_means<float>(S_, mean_, s);
@@ -504,7 +506,7 @@ class ResidentF32 {
             LSSVM_HIP_CHECK(hipGetLastError());
             half_neg_norms<float>(S_, cS_, s);
         }
-        make_planes(m.opt, m.params, false, S_, nullptr, planesS_, nullptr, s);
+        make_planes(m.opt, m.params, false, S_, nullptr, planesS_, nullptr, s, wide_);
         if (planesS_.mode == 0) return false;
         const int num_jt = S_.rows_alloc / TILE;
         const size_t ra = static_cast<size_t>(S_.rows_alloc);
@@ -517,8 +519,11 @@ class ResidentF32 {
         const int ncols = num_jt * TILE;
         rec_ = static_cast<size_t>(num_jt) * 256;
         const bool fold = rbf && m.opt.rbf_fold != 0;
-        // (beyond 128 features a pair exists only where its launch is dispatched -- wide_pair_routed --; elsewhere every vector keeps the records of a launch of its own)
-        const bool pairs = m.nvec >= 2 && (!rbf || fold) && (planesS_.ldx16 <= 128 || wide_pair_routed(planesS_.mode, m.params.kernel_type, m.params.degree, planesS_.ldx16 / 64));
+        // (beyond 128 features a pair exists only where its launch is dispatched -- wide_pair_routed, panel_pair_routed --; elsewhere every vector keeps the records of a
+        // launch of its own)
+        const bool pair_routed = wide_ ? panel_pair_routed(LSSVM_DTYPE_F32, planesS_.mode, m.params.kernel_type, m.params.degree, planesS_.ldx16 / 128)
+                                       : (planesS_.ldx16 <= 128 || wide_pair_routed(planesS_.mode, m.params.kernel_type, m.params.degree, planesS_.ldx16 / 64));
+        const bool pairs = m.nvec >= 2 && (!rbf || fold) && pair_routed;
         folded_first_ = pairs ? m.nvec - 1 : 0;
         dc_.alloc_zero(m.nvec * rec_, s);
         for (size_t v = (rbf || !pairs) ? 0 : m.nvec - m.nvec % 2; v < m.nvec; ++v) enqueue_pack_records(a_.p + v * ra, cS_.p, ncols, dc_.p + v * rec_, 0, static_cast<const float *>(nullptr), s);
@@ -599,7 +604,8 @@ class ResidentF32 {
         }
         lap("operand planes");
         const bool folded = rbf && m.opt.rbf_fold != 0 && r2 <= FOLD_MAX_R2;
-        // (the rectangular 256-row kernel exists up to 128 features; wider models take the 128-row full-square kernels at every batch size, as in the one-shot call)
+        // (the rectangular 256-row kernel exists up to 128 features; wider models take the 128-row full-square kernels at every batch size, as in the one-shot call --
+        // beyond the one-pass kernels the full-square panel kernel)
         const bool rect = rect_kernel_applies(m.opt, m.params, planesS_.ldx16, folded, r2, P.rows_alloc / TILE);
         // Two weight vectors per product launch wherever a pair record exists in the form this batch needs: the rectangular 256-row kernel under its conditions, the
         // 128-row full-square kernels otherwise (polynomial of any degree, folded rbf).  Unfolded rbf keeps c_j in the record's second half: one vector per launch.
@@ -613,6 +619,7 @@ class ResidentF32 {
         TileArgs<float> ta = stage.args(m.params, false, cP.p, cS_.p, records);
         ta.dc_folded = folded ? 1 : 0;
         set_plane_args(ta, m.params, planesS_, planesP, static_cast<size_t>(S_.rows_alloc), static_cast<size_t>(P.rows_alloc));
+        ta.wide_panels = wide_ ? 1 : 0;
         RectSetup rect_setup;
         if (rect) setup_rect_launch(ta, rect_setup, planesP, P.rows_alloc, stage.num_ib, stage.num_jc, s);
         stage.run(ta, m.params.kernel_type, false, records, out, mem_kind, info, lap);
@@ -633,20 +640,23 @@ class ResidentF32 {
     PlaneSet planesS_;
     double r2_sv_ = 0.0;
     float scale_ = 1.0f;
+    bool wide_ = false;  // beyond the one-pass split kernels: the panel kernel (FORMS_PANELS)
 };
 
-/* (lssvm_mi355_predictor_create_resident only: `every_form`) */
+/* (lssvm_mi355_predictor_create_resident and _create_panels only: FORMS_EVERY and above) */
 class ResidentF64 {
   public:
     static constexpr bool declines_batches = false;
 
     /* fp64, rbf / polynomial (gamma > 0) on the one-pass v2 kernel (at most 256 padded features, tile_kernel != 1): the support vectors' side of the product, once,
      * prepared as predict_values_impl<double> prepares it -- the same padding, centre, scale and records, so that a batch's values have the one-shot call's bits.  fp64
-     * rbf has no direct form and no plane check: this form never declines a batch and keeps no host copy of the support vectors. */
-    bool prepare(const PredictModel<double> &m, const double *sv, const double *alpha, bool every_form, hipStream_t s) {
+     * rbf has no direct form and no plane check: this form never declines a batch and keeps no host copy of the support vectors.  FORMS_PANELS: beyond 256 padded
+     * features as well (wide_nonlinear_f64: the panel kernel on data padded to whole 64-feature panels, which DeviceMatrix::upload does at these widths). */
+    bool prepare(const PredictModel<double> &m, const double *sv, const double *alpha, int forms, hipStream_t s) {
         const bool rbf = m.params.kernel_type == LSSVM_KERNEL_RBF;
-        if (!every_form || !(rbf || m.params.kernel_type == LSSVM_KERNEL_POLYNOMIAL) || !(m.params.gamma > 0.0)) return false;
-        if (!v2_eligible_f64(m.opt, padded_features<double>(m.nfeat))) return false;
+        if (forms < FORMS_EVERY || !(rbf || m.params.kernel_type == LSSVM_KERNEL_POLYNOMIAL) || !(m.params.gamma > 0.0)) return false;
+        wide_ = forms >= FORMS_PANELS && wide_nonlinear_f64(m.opt, m.params, m.nfeat);
+        if (!wide_ && !v2_eligible_f64(m.opt, padded_features<double>(m.nfeat))) return false;
         S_.upload(sv, LSSVM_MEM_HOST, m.nsv, m.nfeat, 0, s);
         const dim3 cgrid((S_.dfeat + 255) / 256, S_.rows);
         if (rbf) {
@@ -666,14 +676,18 @@ class ResidentF64 {
         LSSVM_HIP_CHECK(hipMemcpy2DAsync(a_.p, ra * sizeof(double), alpha, m.nsv * sizeof(double), m.nsv * sizeof(double), m.nvec, hipMemcpyHostToDevice, s));
         // The column records of every launch group, once: per pair (0,1), (2,3), ... the (d0_j | d1_j | c_j) record of the two-vector kernel, and the single-vector
         // (d_j | c_j) record of the vector no pair holds (nvec odd; nvec == 1).  Every (kernel function, chunk count) instantiation of the two-vector kernel takes less
-        // than two single-vector launches (profiles/predictor_f64.json, launch_level: 0.46 ... 0.58 of two), so every pair is launched as a pair.
+        // than two single-vector launches (profiles/predictor_f64.json, launch_level: 0.46 ... 0.58 of two), so every pair is launched as a pair.  The panel kernel:
+        // where panel_pair_routed says so; elsewhere every vector keeps the single-vector record of a launch of its own.
         const int ncols = num_jt * TILE;
         rec2_ = static_cast<size_t>(num_jt) * 2 * 192;
-        if (m.nvec % 2 == 1) {
-            dc_.alloc_zero(static_cast<size_t>(num_jt) * 256, s);
-            enqueue_pack_records(a_.p + (m.nvec - 1) * ra, cS_.p, ncols, dc_.p, 0, static_cast<const double *>(nullptr), s);
+        rec1_ = static_cast<size_t>(num_jt) * 256;
+        pairs_ = m.nvec >= 2 && (!wide_ || panel_pair_routed(LSSVM_DTYPE_F64, 0, m.params.kernel_type, m.params.degree, S_.ldx / 64));
+        single_first_ = pairs_ ? m.nvec - 1 : 0;
+        if (m.nvec % 2 == 1 || !pairs_) {
+            dc_.alloc_zero((m.nvec - single_first_) * rec1_, s);
+            for (size_t v = single_first_; v < m.nvec; ++v) enqueue_pack_records(a_.p + v * ra, cS_.p, ncols, dc_.p + (v - single_first_) * rec1_, 0, static_cast<const double *>(nullptr), s);
         }
-        if (m.nvec >= 2) {
+        if (pairs_) {
             dc2_.alloc_zero((m.nvec / 2) * rec2_, s);
             for (size_t g = 0; g < m.nvec / 2; ++g) enqueue_pack_records2(a_.p + 2 * g * ra, a_.p + (2 * g + 1) * ra, cS_.p, ncols, dc2_.p + g * rec2_, s);
         }
@@ -695,12 +709,14 @@ class ResidentF64 {
         hipLaunchKernelGGL(k_center<double>, dim3((P.dfeat + 255) / 256, P.rows), dim3(256), 0, s, P.data.p, P.ldx, P.dfeat, P.rows, rbf ? mean_.p : static_cast<const double *>(nullptr), scale_);
         LSSVM_HIP_CHECK(hipGetLastError());
         if (rbf) half_neg_norms<double>(P, cP, s);
-        ProductStage<double> stage(m.opt, P, S_, false, a_.p, m.rho.data(), m.nvec, m.nvec >= 2 ? 2 : 1, s, t0);
+        ProductStage<double> stage(m.opt, P, S_, false, a_.p, m.rho.data(), m.nvec, pairs_ ? 2 : 1, s, t0);
         const auto records = [&](int v, int count) -> const double * {
-            return count == 2 ? dc2_.p + static_cast<size_t>(v / 2) * rec2_ : dc_.p;  // (alone: the vector no pair holds)
+            // (alone: the vector no pair holds -- or, where pairs are not dispatched, every vector)
+            return count == 2 ? dc2_.p + static_cast<size_t>(v / 2) * rec2_ : dc_.p + (static_cast<size_t>(v) - single_first_) * rec1_;
         };
         TileArgs<double> ta = stage.args(m.params, false, cP.p, cS_.p, records);
         if (!rbf) ta.gamma = 1.0;
+        ta.wide_panels = wide_ ? 1 : 0;
         stage.run(ta, m.params.kernel_type, false, records, out, mem_kind, info, no_lap);
         info.resident = 1;
         return true;
@@ -709,22 +725,26 @@ class ResidentF64 {
   private:
     DeviceMatrix<double> S_;
     DevBuf<double> mean_, cS_, a_;
-    DevBuf<double> dc_, dc2_;  // column records: [num_jt][256] of the vector no pair holds, [nvec / 2][rec2_] per pair
-    size_t rec2_ = 0;
+    DevBuf<double> dc_, dc2_;  // column records: [num_jt][256] of the vector no pair holds (every vector's where pairs are not dispatched), [nvec / 2][rec2_] per pair
+    size_t rec2_ = 0, rec1_ = 0;
+    size_t single_first_ = 0;  // the vector dc_ starts with (the last one; 0 where no pair launch is dispatched)
     double scale_ = 1.0;
+    bool wide_ = false;   // more than 256 padded features: the panel kernel (FORMS_PANELS)
+    bool pairs_ = false;  // two vectors per launch
 };
 
 /* `nvec` weight vectors over the same support vectors (lssvm_mi355_predictor_create: one; _create_multi: a one-vs-all model's k).  The linear kernel keeps w per vector;
  * an rbf / polynomial model keeps its real type's resident form where it has one, and the one-shot path's inputs where a batch may need them.
  * `every_form` (lssvm_mi355_predictor_create_resident): fp64 rbf / polynomial models on at most 256 padded features are resident as well (ResidentF64), and so are fp32
  * models of 129 ... 512 features on the one-pass split kernels (ResidentF32); without it such a model goes through the one-shot path, as _create / _create_multi
- * document. */
+ * document.  FORMS_PANELS (lssvm_mi355_predictor_create_panels): all of that, and the models beyond the one-pass kernels on the panel kernels -- fp32 rbf / polynomial
+ * beyond 512 / 384 features, fp64 beyond 256. */
 template <typename T>
 class Predictor final : public PredictorBase {
     using Resident = std::conditional_t<std::is_same_v<T, float>, ResidentF32, ResidentF64>;
 
   public:
-    Predictor(const Options &opt, const lssvm_params &params, const T *sv, size_t nsv, size_t nfeat, const T *alpha, const double *rho, size_t nvec, bool every_form) :
+    Predictor(const Options &opt, const lssvm_params &params, const T *sv, size_t nsv, size_t nfeat, const T *alpha, const double *rho, size_t nvec, int forms) :
         m_{ opt, params, nsv, nfeat, nvec, {} } {
         dtype = std::is_same_v<T, float> ? LSSVM_DTYPE_F32 : LSSVM_DTYPE_F64;
         check_params(&m_.params);
@@ -747,7 +767,7 @@ class Predictor final : public PredictorBase {
             LSSVM_HIP_CHECK(hipStreamSynchronize(s));
             return;
         }
-        resident_ = resident_form_.prepare(m_, sv, alpha, every_form, s);
+        resident_ = resident_form_.prepare(m_, sv, alpha, forms, s);
         // the one-shot path's inputs: host copies where nothing is resident; a resident model that may decline a batch keeps alpha, leaves its support vectors as they
         // came in HBM and fetches them if a batch ever asks
         if (!resident_ || Resident::declines_batches) alpha_host_.assign(alpha, alpha + nvec * nsv);
@@ -771,9 +791,10 @@ class Predictor final : public PredictorBase {
         }
         if (!done) {
             // what the resident form does not cover (outside lssvm_mi355_predictor_create_resident: fp64, and fp32 on more than 128 features; with it: fp64 beyond 256
-            // features and fp32 beyond the one-pass split kernels' 512 / 384; gram_mode 0, tile_kernel 1, rbf_form 1 / 3; exponent scales beyond the norm expansion; a
-            // batch whose planes fail the f16 check or that lies further from the support vectors' centre than the form chosen for them allows): the one-shot path,
-            // same result
+            // features and fp32 beyond the one-pass split kernels' 512 / 384 -- which lssvm_mi355_predictor_create_panels keeps resident on the panel kernels; under
+            // every entry point: a negative polynomial degree beyond the one-pass kernels, gram_mode 0, tile_kernel 1, rbf_form 1 / 3; exponent scales beyond the norm
+            // expansion; a batch whose planes fail the f16 check or that lies further from the support vectors' centre than the form chosen for them allows): the
+            // one-shot path, same result
             int w_valid = 0;
             std::vector<T> w_tmp(m_.nvec * m_.nfeat);
             if constexpr (Resident::declines_batches) {
@@ -828,9 +849,9 @@ class Predictor final : public PredictorBase {
 };
 
 std::unique_ptr<PredictorBase> make_predictor(const Options &opt, const lssvm_params &params, int dtype, const void *sv, size_t nsv, size_t nfeat, const void *alpha, const double *rho,
-                                              size_t nvec, bool every_form) {
-    if (dtype == LSSVM_DTYPE_F32) return std::make_unique<Predictor<float>>(opt, params, static_cast<const float *>(sv), nsv, nfeat, static_cast<const float *>(alpha), rho, nvec, every_form);
-    return std::make_unique<Predictor<double>>(opt, params, static_cast<const double *>(sv), nsv, nfeat, static_cast<const double *>(alpha), rho, nvec, every_form);
+                                              size_t nvec, int forms) {
+    if (dtype == LSSVM_DTYPE_F32) return std::make_unique<Predictor<float>>(opt, params, static_cast<const float *>(sv), nsv, nfeat, static_cast<const float *>(alpha), rho, nvec, forms);
+    return std::make_unique<Predictor<double>>(opt, params, static_cast<const double *>(sv), nsv, nfeat, static_cast<const double *>(alpha), rho, nvec, forms);
 }
 
 }  // namespace lssvm

@@ -129,6 +129,19 @@ bool wide_pair_routed(int plane_mode, int kernel_type, int /*degree*/, int nk64)
     return (plane_mode == 1 || plane_mode == 2) && nk64 >= 3 && nk64 <= max_nk64;
 }
 
+/* The resident predictors beyond the one-pass kernels (lssvm_mi355_predictor_create_panels; lssvm_predict.hip): whether a pair of weight vectors is dispatched as ONE
+ * launch of the two-vector panel kernels (tile_launch_f32xv2.hip: f16x3 and bf16x6 planes x polynomial of a run-time degree, degree 2, degree 3, folded rbf;
+ * tile_launch_f64xv2.hip: rbf and the three polynomial forms) -- by real type, plane kind (fp32; PlaneSet::mode), kernel function and number of feature panels (128
+ * features in fp32, 64 in fp64; one instantiation serves every panel count).  Same routing condition as wide_pair_routed, measured by
+ * tests/tools/predictor_panels_timing.py (profiles/predictor_panels.json) against two single-vector launches of the build before; an instantiation that fails it, or that
+ * the compiler does not fit into its single-vector sibling's register budget without scratch, is named here and served by two single-vector launches on the same resident
+ * data.  None is named: all twelve compile without scratch at their siblings' occupancy.  (Unfolded fp32 rbf has no pair record and never gets here.) */
+bool panel_pair_routed(int dtype, int plane_mode, int kernel_type, int /*degree*/, int panels) {
+    const bool nonlinear = kernel_type == LSSVM_KERNEL_RBF || kernel_type == LSSVM_KERNEL_POLYNOMIAL;
+    if (dtype == LSSVM_DTYPE_F64) return nonlinear && panels >= 5;
+    return nonlinear && (plane_mode == 1 || plane_mode == 2) && panels >= 2;
+}
+
 /* The lockstep CG in fp32 on 129 ... 512 features (Problem<float>::pair_kernel_applies): whether a pair of right-hand sides is dispatched as ONE launch of the symmetric
  * two-vector kernels (tile_launch_f32v2ws.hip) -- same arguments, same routing condition as wide_pair_routed, measured by tests/tools/lockstep_f32_wide_timing.py
  * (profiles/lockstep_f32_wide.json) against two single-vector symmetric passes of the build before.  An instantiation that fails the condition, or that the compiler

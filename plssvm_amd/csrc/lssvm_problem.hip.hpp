@@ -923,9 +923,12 @@ struct PredictorBase {
      * vectors refuses the call */
     virtual void predict(const void *points, int mem_kind, size_t npoints, void *out, lssvm_predict_info *info, bool multi) = 0;
 };
-/* alpha [nvec][nsv], rho [nvec]; `every_form`: every resident form the library has (lssvm_mi355_predictor_create_resident: the fp64 one as well) */
+/* which resident forms a predictor may take: those of _create / _create_multi; FORMS_EVERY (lssvm_mi355_predictor_create_resident): every form on the one-pass kernels,
+ * the fp64 one as well; FORMS_PANELS (lssvm_mi355_predictor_create_panels): those, and the models beyond the one-pass kernels on the panel kernels */
+constexpr int FORMS_DEFAULT = 0, FORMS_EVERY = 1, FORMS_PANELS = 2;
+/* alpha [nvec][nsv], rho [nvec] */
 std::unique_ptr<PredictorBase> make_predictor(const Options &opt, const lssvm_params &params, int dtype, const void *sv, size_t nsv, size_t nfeat, const void *alpha, const double *rho,
-                                              size_t nvec, bool every_form = false);
+                                              size_t nvec, int forms = FORMS_DEFAULT);
 
 /* The fixed-size model from a stream of chunks (lssvm_mi355_reduced_stream_*; lssvm_reduced.hip): the landmark rows, K_mm, the running St and one
  * pending slab, kept on device 0 across update calls.  include/plssvm_amd.h has the contract of every call. */
@@ -980,6 +983,7 @@ T rbf_prescale(const lssvm_params &p, bool fp64_v2);
 bool wide_nonlinear_f64(const Options &o, const lssvm_params &p, size_t num_features);
 bool wide_nonlinear(const Options &o, const lssvm_params &p, bool rbf_direct, size_t num_features);
 bool wide_pair_routed(int plane_mode, int kernel_type, int degree, int nk64);  // the resident fp32 predictor beyond 128 features: one two-vector launch for a pair?
+bool panel_pair_routed(int dtype, int plane_mode, int kernel_type, int degree, int panels);  // the resident predictors on the panel kernels: one two-vector launch for a pair?
 bool sym_pair_routed(int plane_mode, int kernel_type, int degree, int nk64);   // the fp32 lockstep CG on 129 ... 512 features: one symmetric two-vector launch for a pair of right-hand sides?
 template <typename T>
 void set_kernel_scalars(TileArgs<T> &a, const lssvm_params &p, bool rbf_direct);

@@ -15,6 +15,10 @@
  * Compiler-scheduled MFMA groups, two waves per SIMD (the register budget of the 128-feature kernels).  Symmetric variant and full-square variant
  * (option symmetric = 0; predict_values: rows = points, columns = support vectors); a negative polynomial degree (0^degree on padded columns) stays
  * on the generic native kernel.
+ * NV (full-square variant only; tile_launch_f32xv2.hip): weight vectors per pass, as s6w_body's NV -- the resident predictor of a one-vs-all model at these widths.  NV = 2:
+ * the record of a column tile carries (d0_j | d1_j) (k_pack_dc2; folded rbf: both times 2^c_j), the kernel function is evaluated once per element and feeds two scalar
+ * fma chains, and the row sums of vector v go to plane v of `partial` (TileArgs::part_vstride apart).  Per vector the chain of operations is the one of NV = 1.  Not the
+ * unfolded rbf form (c_j in the record's second half) and not the grid planes.
  * Reference semantics: /root/reference/include/plssvm/backends/HIP/svm_kernel.hip.hpp:129-270 (one code path for any feature count).
  */
 #pragma once
@@ -23,9 +27,11 @@
 
 namespace lssvm {
 
-template <int KT, int PL, bool SYM>
+template <int KT, int PL, bool SYM, int NV = 1>
 __device__ __forceinline__ void s6x_body(const TileArgs<float> &a) {
     static_assert(PL == 3 || PL == 2, "three bf16 planes (bf16x6) or two f16 planes (f16x3)");
+    static_assert(NV == 1 || (NV == 2 && !SYM), "two weight vectors per pass: the full-square variant only");
+    static_assert(NV == 1 || KT == KT_POLY || KT == KT_POLY2 || KT == KT_POLY3 || KT == KT_RBFF, "two weight vectors per pass: the second half of the record must be free");
     static_assert(KT != KT_LINEAR, "the linear kernel takes feature-panel passes of the 128-feature kernels");
     constexpr bool F16 = PL == 2;
     // KT_RBFG (rbf on GRID planes, round 5; s6w_body / DESIGN.md section 4.1.2): three f16 planes (h | s1 | s2) and TWO sweeps over the feature panels of a tile -- sweep A: the
@@ -175,9 +181,11 @@ __device__ __forceinline__ void s6x_body(const TileArgs<float> &a) {
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) rd_off[kk] = r * 128 + (((4 * kk + g) ^ ((r >> 1) & 7)) << 4);
 
-    float rowpart[8];
+    float rowpart[NV][8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) rowpart[i] = 0.0f;
+    for (int v = 0; v < NV; ++v)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) rowpart[v][i] = 0.0f;
     f32x4 acc[2][8];
 
     // ---- prologue: chunks 0, 1, 2 (a tile has at least 2 x NKC >= 8 steps here: only the record of tile 0 falls into it) ----
@@ -354,13 +362,20 @@ __device__ __forceinline__ void s6x_body(const TileArgs<float> &a) {
             }
 #pragma unroll
             for (int cb = 0; cb < 8; ++cb) {
-                const float djv = dcr[cb * 16 + r];
+                float djv[NV];
+#pragma unroll
+                for (int v = 0; v < NV; ++v) djv[v] = dcr[v * TILE + cb * 16 + r];
 #pragma unroll
                 for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const float kv = apply_kernel_function<v2_base_kt(KT), v2_degree_class(KT)>(GRID ? acc[rb][cb][e] * a.gamma : acc[rb][cb][e], a);  // (grid planes: the chain carries sigma^2)
-                        rowpart[4 * rb + e] = fmaf(kv, djv, rowpart[4 * rb + e]);
+#pragma unroll
+                        for (int v = 0; v < NV; ++v) {
+                            rowpart[v][4 * rb + e] = fmaf(kv, djv[v], rowpart[v][4 * rb + e]);
+                            // (two vectors: scalar v_fma_f32 chains, as in s6w_body -- every chain's value passes through an empty statement the vectoriser cannot see into)
+                            if constexpr (NV > 1) asm("" : "+v"(rowpart[v][4 * rb + e]));
+                        }
                         if constexpr (COLS) {
                             kvp[e & 1] = kv;
                             if (e & 1) {
@@ -402,19 +417,22 @@ __device__ __forceinline__ void s6x_body(const TileArgs<float> &a) {
 
     // every lane group owns its rows: reduce over the 16 columns of the group and store
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        float v = rowpart[i];
+    for (int vi = 0; vi < NV * 8; ++vi) {
+        const int i = vi & 7;
+        float v = rowpart[vi >> 3][i];
         v += __shfl_xor(v, 8);
         v += __shfl_xor(v, 4);
         v += __shfl_xor(v, 2);
         v += __shfl_xor(v, 1);
         if constexpr (GRID) v *= a.er[row0 + wave * 32 + 16 * (i >> 2) + 4 * g + (i & 3)];  // the row's folded factor E_i, once per work item
-        rowpart[i] = v;
+        rowpart[vi >> 3][i] = v;
     }
     if (r == 0) {
         float *dst = a.partial + static_cast<size_t>(jc) * a.part_stride + ibl * TILE + wave * 32 + 4 * g;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) dst[16 * (i >> 2) + (i & 3)] = rowpart[i];
+        for (int v = 0; v < NV; ++v)
+#pragma unroll
+            for (int i = 0; i < 8; ++i) dst[(NV > 1 ? static_cast<size_t>(v) * a.part_vstride : 0) + 16 * (i >> 2) + (i & 3)] = rowpart[v][i];
     }
 }
 
@@ -427,6 +445,11 @@ __device__ __forceinline__ void s6x_body(const TileArgs<float> &a) {
 template <int KT, int PL, bool SYM>
 __global__ __launch_bounds__(TILE_THREADS, (KT == KT_RBFG ? LSSVM_WIDE_GRID_WAVES : 2)) void tile_matvec_f32_wide(const TileArgs<float> a) {
     s6x_body<KT, PL, SYM>(a);
+}
+/* two weight vectors per pass (NV = 2, full square only; tile_launch_f32xv2.hip).  Two waves per SIMD. */
+template <int KT, int PL>
+__global__ __launch_bounds__(TILE_THREADS, 2) void tile_matvec_f32_wide_nv2(const TileArgs<float> a) {
+    s6x_body<KT, PL, false, 2>(a);
 }
 
 }  // namespace lssvm

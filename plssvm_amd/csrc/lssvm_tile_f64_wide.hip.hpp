@@ -9,6 +9,10 @@
  * workgroups per CU) is re-loaded from L2 for every (sub-tile, panel), each 16-feature chunk requested as soon as the previous panel is through
  * with it.  The linear kernel does not come here: its Gram matrix is a sum over panels and runs one pass of the v2 kernel per panel
  * (lssvm_problem.hip).  The data is padded to whole panels (padded_features).  A negative polynomial degree stays on the generic kernel.
+ * NV = 2 (full-square variant only; tile_launch_f64xv2.hip: the resident predictor of a one-vs-all model at these widths): TWO vectors per pass, as
+ * tile_matvec_f64_v2's NV = 2 -- the kernel value of an element is computed once and feeds both vectors' row sums, each through the fma chain it has at NV = 1.  The
+ * record of a sub-tile is (d0_j | d1_j | c_j), 1.5 KiB (k_pack_dc2_f64), fetched by 24 lanes per wave; the LDS size is V2D_LDS_BYTES_NV2.  Everything the second
+ * vector adds stands in `if constexpr (NV == 2)`: the NV = 1 instantiations are the code they were.
  * Reference semantics: /root/reference/include/plssvm/backends/HIP/svm_kernel.hip.hpp:129-270 (one code path for any feature count).
  */
 #pragma once
@@ -17,14 +21,16 @@
 
 namespace lssvm {
 
-template <int KT, bool SYM>
+template <int KT, bool SYM, int NV = 1>
 __global__ __launch_bounds__(TILE_THREADS, 2) void tile_matvec_f64_wide(const TileArgs<double> a) {
     static_assert(KT != KT_LINEAR, "the linear kernel takes feature-panel passes of tile_matvec_f64_v2");
+    static_assert(NV == 1 || (NV == 2 && !SYM), "two vectors per pass: the full-square variant only");
     constexpr int NKC = 4;  // 16-feature chunks per panel
+    constexpr int REC_BYTES = NV * 512 + 512;  // a sub-tile's record: 64 d_j per vector, then 64 c_j
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     char *ring = smem_raw;
     char *dcs = smem_raw + V2D_RING * V2D_SLOT_BYTES;
-    double *cis = reinterpret_cast<double *>(dcs + V2D_DC_SLOTS * 1024);  // [128] c_i of the row panel (rbf)
+    double *cis = reinterpret_cast<double *>(dcs + V2D_DC_SLOTS * REC_BYTES);  // [128] c_i of the row panel (rbf)
     double *dis = cis + TILE;                                              // [128] d_i of the row panel (SYM)
     double *colred = dis + TILE;                                           // [2][4 waves][64] column sums of a sub-tile (SYM)
 
@@ -101,7 +107,7 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void tile_matvec_f64_wide(const Ti
     }
     const unsigned ring_lds = static_cast<unsigned>(reinterpret_cast<size_t>(ring));
     const unsigned dma_lds = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(ring_lds + static_cast<unsigned>(wave) * 2048u)));
-    const unsigned dc_lds = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(ring_lds + V2D_RING * V2D_SLOT_BYTES + static_cast<unsigned>(wave) * 256u)));
+    const unsigned dc_lds = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(ring_lds + V2D_RING * V2D_SLOT_BYTES + static_cast<unsigned>(wave) * static_cast<unsigned>(REC_BYTES / 4))));
     auto issue_chunk = [&](int step) {  // step = (sub-tile t, panel p, chunk kc)
         const int t = step / steps_per_sub;
         const int in_sub = step - t * steps_per_sub;  // = p * NKC + kc: the 16-feature chunk of the row
@@ -111,9 +117,10 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void tile_matvec_f64_wide(const Ti
         lds_dma16<1024>(dma_off[1], base, slot);
     };
     auto issue_dc = [&](int t) {
-        if (lane < 16) {
-            const char *src = sgpr_ptr(a.dc + static_cast<size_t>(st_begin + t) * 128) + __builtin_amdgcn_readfirstlane(wave * 256);
-            lds_dma16<0>(16u * (lane_off(threadIdx.x) & 15u), sgpr_ptr(src), static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(dc_lds + static_cast<unsigned>(t % V2D_DC_SLOTS) * 1024u))));
+        // each wave fetches its quarter of the record: 16 lanes x 16 bytes (NV = 2: 24 lanes), lane-linear in LDS
+        if (lane < REC_BYTES / 64) {
+            const char *src = sgpr_ptr(a.dc + static_cast<size_t>(st_begin + t) * (REC_BYTES / 8)) + __builtin_amdgcn_readfirstlane(wave * (REC_BYTES / 4));
+            lds_dma16<0>(16u * (lane_off(threadIdx.x) & (NV == 2 ? 31u : 15u)), sgpr_ptr(src), static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(dc_lds + static_cast<unsigned>(t % V2D_DC_SLOTS) * static_cast<unsigned>(REC_BYTES)))));
         }
     };
 
@@ -130,6 +137,13 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void tile_matvec_f64_wide(const Ti
         for (int i = 0; i < 4; ++i) rowpart[rb][i] = 0.0;
     f64x4 acc[2][4];
     double dj[4];
+    [[maybe_unused]] double rowpart1[2][4], dj1[4];  // NV = 2: the second vector's row sums and d_j
+    if constexpr (NV == 2) {
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) rowpart1[rb][i] = 0.0;
+    }
 
     // ---- prologue: chunks 0, 1, 2 (a sub-tile has at least 5 x NKC steps here: only the record of sub-tile 0 falls into it) ----
     issue_dc(0);
@@ -171,12 +185,12 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void tile_matvec_f64_wide(const Ti
     };
 
     for (int t = 0; t < nsub; ++t) {
-        const double *dcr = reinterpret_cast<const double *>(dcs + (t % V2D_DC_SLOTS) * 1024);
+        const double *dcr = reinterpret_cast<const double *>(dcs + (t % V2D_DC_SLOTS) * REC_BYTES);
         // start values of the chains: rbf c_i + c_j; polynomial coef0 (the data carries sqrt(gamma): the chain leaves gamma <x_i, x_j>)
         if constexpr (KT == KT_RBF) {
             double cj[4];
 #pragma unroll
-            for (int cb = 0; cb < 4; ++cb) cj[cb] = dcr[64 + cb * 16 + r];
+            for (int cb = 0; cb < 4; ++cb) cj[cb] = dcr[NV * 64 + cb * 16 + r];
 #pragma unroll
             for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
@@ -243,7 +257,10 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void tile_matvec_f64_wide(const Ti
         }
         // ---- epilogue of the sub-tile (tile_matvec_f64_v2's; ONE form per instantiation) ----
 #pragma unroll
-        for (int cb = 0; cb < 4; ++cb) dj[cb] = dcr[cb * 16 + r];
+        for (int cb = 0; cb < 4; ++cb) {
+            dj[cb] = dcr[cb * 16 + r];
+            if constexpr (NV == 2) dj1[cb] = dcr[64 + cb * 16 + r];
+        }
         double colacc[4] = { 0.0, 0.0, 0.0, 0.0 };
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb)
@@ -261,6 +278,7 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void tile_matvec_f64_wide(const Ti
                     }
                     rowpart[rb][i] = fma(kv, dj[cb], rowpart[rb][i]);
                     if constexpr (SYM) colacc[cb] = fma(kv, di, colacc[cb]);
+                    if constexpr (NV == 2) rowpart1[rb][i] = fma(kv, dj1[cb], rowpart1[rb][i]);  // kv is shared; the second vector's chain is that of a single-vector pass
                 }
             }
         if constexpr (SYM) {
@@ -294,6 +312,26 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void tile_matvec_f64_wide(const Ti
         for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
             for (int i = 0; i < 4; ++i) dst[rb * 16 + 4 * i] = rowpart[rb][i];
+    }
+    if constexpr (NV == 2) {  // the second vector's row sums: the same butterfly, into its plane of the row slabs
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                double v = rowpart1[rb][i];
+                v += __shfl_xor(v, 8);
+                v += __shfl_xor(v, 4);
+                v += __shfl_xor(v, 2);
+                v += __shfl_xor(v, 1);
+                rowpart1[rb][i] = v;
+            }
+        if (r == 0) {
+            double *dst = a.partial + a.part_vstride + static_cast<size_t>(jc) * a.part_stride + ibl * TILE + wave * 32 + q;
+#pragma unroll
+            for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) dst[rb * 16 + 4 * i] = rowpart1[rb][i];
+        }
     }
 }
 

@@ -62,8 +62,12 @@ void launch_nv2_wide_tile_kernel(const TileArgs<float> &a, int kernel_type, dim3
 void launch_nv2_sym_wide_tile_kernel(const TileArgs<float> &a, int kernel_type, hipStream_t s);
 /* rbf / polynomial on more features than a row panel in registers holds (tile_launch_f32x.hip): feature panels inside a tile */
 void launch_wide_tile_kernel(const TileArgs<float> &a, int kernel_type, dim3 grid, hipStream_t s);
+/* ... with two weight vectors per pass, full square (tile_launch_f32xv2.hip; TileArgs::nvec == 2, reached through launch_tile_kernel<float>) */
+void launch_nv2_panel_tile_kernel(const TileArgs<float> &a, int kernel_type, dim3 grid, hipStream_t s);
 /* fp64 rbf / polynomial on more than 256 features (tile_launch_f64x.hip): feature panels of 64 inside a sub-tile */
 void launch_wide_tile_kernel_f64(const TileArgs<double> &a, int kernel_type, dim3 grid, hipStream_t s);
+/* ... with two weight vectors per pass, full square (tile_launch_f64xv2.hip; TileArgs::nvec == 2, reached through launch_tile_kernel<double>) */
+void launch_nv2_panel_tile_kernel_f64(const TileArgs<double> &a, int kernel_type, dim3 grid, hipStream_t s);
 /* the fp64 symmetric v2 kernel with two vectors per pass (tile_launch_f64_sym2a.hip / _sym2b.hip; TileArgs::nvec == 2, reached through launch_tile_kernel<double>) */
 void launch_v2d_sym2(const TileArgs<double> &a, int kernel_type, hipStream_t s);
 /* ... and its full-square counterpart (tile_launch_f64_full2a.hip / _full2b.hip; TileArgs::items == nullptr): rbf and polynomial, `grid` from finish_mapping */

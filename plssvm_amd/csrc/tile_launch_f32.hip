@@ -56,7 +56,11 @@ void launch_tile_kernel<float>(TileArgs<float> &a, int kernel_type, bool rbf_dir
         if (a.row_pair != 0) {  // (with nvec == 2: the rectangular 256-row kernel's two-vector instance, whose items are block pairs)
             launch_pair_tile_kernel(a, kernel_type, s);
         } else if (a.wide_panels != 0) {
-            launch_wide_tile_kernel(a, kernel_type, grid, s);
+            if (a.nvec == 2 && a.items == nullptr) {  // two vectors per full-square pass of the panel kernel (the resident Predictor<float>)
+                launch_nv2_panel_tile_kernel(a, kernel_type, grid, s);
+            } else {
+                launch_wide_tile_kernel(a, kernel_type, grid, s);
+            }
         } else if (a.nvec == 2 && a.items != nullptr) {  // two vectors per symmetric pass on the 128-row split kernels (Problem<float>::enqueue_apply_K_lanes)
             launch_nv2_sym_wide_tile_kernel(a, kernel_type, s);
         } else if (a.planes_f16 != 0) {

@@ -632,7 +632,7 @@ class MI355CSVM(CSVM):
 
     def decision_values_resident(self, model, X):
         """The decision values ``f[i, c]`` of a :class:`plssvm_amd.multiclass.OneVsAllModel` with the model RESIDENT in HBM from the first call on
-        (``lssvm_mi355_predictor_create_resident``: every resident form the library has, float64 included): later calls with the same model upload only their points.  The predictor is cached on the model and made again (the old
+        (``lssvm_mi355_predictor_create_panels``: every resident form the library has, float64 and the models beyond the one-pass kernels included): later calls with the same model upload only their points.  The predictor is cached on the model and made again (the old
         one closed) under the rule of :meth:`predict`: another backend object, changed option values, kernel parameters, another support-vector array (by identity),
         ``alpha`` (by value) or ``rho``."""
         sv = model.support_vectors
@@ -646,12 +646,12 @@ class MI355CSVM(CSVM):
                 cached["predictor"].close()  # (its HBM: nothing else holds it)
             alpha, rho = np.array(model.alpha, copy=True), np.array(model.rho, copy=True)
             cached = {"owner": self, "options": opts, "params": params, "sv": sv, "alpha": alpha, "rho": rho,
-                      "predictor": backend.Predictor(model.params, sv, alpha, rho, options=self._options, every_form=True)}
+                      "predictor": backend.Predictor(model.params, sv, alpha, rho, options=self._options, panels=True)}
             model._predictor = cached
         return cached["predictor"].predict(np.asarray(X, dtype=sv.dtype))
 
     def predict(self, model: Model, data: DataSet):
-        """csvm::predict (csvm.hpp:322-342) with the model RESIDENT in HBM from the first call on (``lssvm_mi355_predictor_*``): later calls with the same model upload only
+        """csvm::predict (csvm.hpp:322-342) with the model RESIDENT in HBM from the first call on (``lssvm_mi355_predictor_create_panels``): later calls with the same model upload only
         their points.  Same labels as the base class's one-shot ``predict_values`` with the state of the moment: the resident predictor is made again (and the old one
         closed) when this object's options -- or, without options of its own, the process defaults --, the model's parameters, its support-vector array (by identity),
         ``alpha`` (compared by value, in place edits included) or ``rho`` have changed since it was made.  Editing the support-vector matrix IN PLACE is not detected."""
@@ -670,7 +670,7 @@ class MI355CSVM(CSVM):
                 cached["predictor"].close()  # (its HBM: nothing else holds it)
             alpha = np.array(model.alpha, copy=True)
             cached = {"owner": self, "options": opts, "params": params, "sv": sv, "alpha": alpha, "rho": float(model.rho),
-                      "predictor": backend.Predictor(model.params, sv, alpha, float(model.rho), options=self._options, every_form=True)}
+                      "predictor": backend.Predictor(model.params, sv, alpha, float(model.rho), options=self._options, panels=True)}
             model._predictor = cached
         t1 = time.perf_counter()
         info = {}
