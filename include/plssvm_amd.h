@@ -833,6 +833,53 @@ int lssvm_mi355_reduced_stream_merge_state(lssvm_mi355_reduced_stream *stream, c
 int lssvm_mi355_reduced_stream_info(lssvm_mi355_reduced_stream *stream, lssvm_reduced_stream_info *info, double *centre_out, double *kmm_out);
 int lssvm_mi355_reduced_stream_destroy(lssvm_mi355_reduced_stream *stream);
 
+/* Fixed-size kernel logistic regression by iteratively reweighted least squares (opt-in): with labels y_i in {-1, +1}, prior weights a_i >= 0
+ * (NULL: 1) and the problem's cost C the model minimises
+ *   J(beta, b) = 1/2 beta^T K_mm beta + C sum_i a_i log(1 + exp(-y_i eta_i)),   eta_i = Phi_i beta + b,
+ * so that P(y = +1 | x) = 1 / (1 + exp(-eta(x))) and the decision values of the returned model (betas, rho = -b) are log-odds.  One Newton step from (beta, b) is the
+ * weighted fit above at the same C with v_i = a_i max(mu_i, delta), z_i = eta_i + g_i / max(mu_i, delta), mu_i = p_i (1 - p_i), g_i = (y_i + 1) / 2 - p_i, delta = 2^-32,
+ * and W = sum_i v_i as the Gram pass sums it.  With s = y_i eta_i and e = exp(-|s|) the device evaluates mu = e / ((1 + e)(1 + e)), the loss max(-s, 0) + log1p(e),
+ * g = y_i (s >= 0 ? e / (1 + e) : 1 / (1 + e)) and q = sqrt(a_i max(mu, delta)): no p (1 - p) is formed from p.
+ * A pass walks the slabs once: Phi, k_reduced_logistic_step (eta, q, z and the loss sums of up to four classes from one read of the slab), and per class the weighted Gram
+ * pass on [Phi | 1 | z_c] with q_c.  Pass t >= 1 compares J_t with the objective J' of the last accepted iterate: J' - J_t < -tol J' rejects the iterate (it becomes the
+ * midpoint of itself and the last accepted one and the pass is repeated: a halving); |J' - J_t| <= tol J' ends the class with the iterate of the smaller J (the newer
+ * one unless J_t - J' > 2 (N + 16) eps64 J': closer than that the two sums differ by their own rounding only, and the newer iterate is the more accurate) and converged = 1; otherwise the iterate is accepted and the next one solved from this pass's sums.  max_iter counts passes, rejected ones included: when it runs out the
+ * class returns the iterate solved last with the objective of the one before it (after a rejected last pass: the last accepted iterate and its objective) and
+ * converged = 0.  30 halvings in a row end the class with the last accepted iterate and converged = 0.  The classes of a call run in lockstep and share each evaluation
+ * of a Phi slab; a finished class launches nothing more; column c of a call has the bits of the call with that class alone.  One host wait per pass with factor 0; factor 1 adds the wait of
+ * every class's dense step (one per jitter attempt), the classes one after the other.  Work space: that of lssvm_mi355_problem_fit_reduced at rank + 2 columns, the packed
+ * St tiles per class, and 3 num_rhs slab_rows doubles.
+ * Y: num_rhs x N in the problem's dtype, every entry exactly -1 or +1.  weights: as for lssvm_mi355_problem_fit_reduced_weighted.  factor: 0 or 1, as there.
+ * tol: finite and > 0 (1e-8 is a good default); max_iter >= 1.  betas0 (num_rhs x rank) and rhos0 (num_rhs): the start values, all finite, or both NULL for zeros.
+ * Every output is double; landmarks_out and infos may be NULL.  The problem is left as it was.  LSSVM_ERR_INVALID_ARGUMENT, all before a device is touched: the
+ * refusals of lssvm_mi355_problem_fit_reduced_weighted; a label other than -1 or +1; a bad tol; max_iter == 0; start values that are not finite or only half given. */
+typedef struct lssvm_reduced_logistic_info {
+    uint64_t passes;        /* evaluations of this class, rejected ones included */
+    uint64_t halvings;      /* rejected passes */
+    uint64_t floored;       /* rows with mu < delta in the class's last pass */
+    int32_t  converged;
+    int32_t  reserved;
+    double   objective;     /* J of the returned iterate where it was evaluated, else of the iterate before it (see above) */
+    double   last_decrease; /* J' - J_t of the last pass that was tested */
+    double   jitter;        /* nu of the class's last solve (0 only where the class never solved) */
+    double   max_abs_eta;   /* max_i |eta_i| in the class's last pass */
+    double   landmark_ms, step_ms, gram_ms; /* device time of Phi, of the step kernel and of the Gram passes over the passes this class took part in (shared launches count whole) */
+    double   host_ms;       /* this class's dense steps and bookkeeping */
+    double   total_ms;      /* the call */
+} lssvm_reduced_logistic_info;
+int lssvm_mi355_problem_fit_reduced_logistic(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, const double *weights /* N, or NULL */, uint64_t rank,
+                                             const uint64_t *landmarks, uint64_t slab_rows, int factor, double tol, uint64_t max_iter,
+                                             const double *betas0 /* num_rhs x rank, or NULL */, const double *rhos0 /* num_rhs, or NULL */, double *betas_out,
+                                             double *rhos_out, uint64_t *landmarks_out, lssvm_reduced_logistic_info *infos /* num_rhs */);
+int lssvm_mi355_fit_reduced_logistic_f32(const lssvm_params *params, const float *X, size_t num_points, size_t num_features, const float *Y, size_t num_rhs, const double *weights,
+                                         uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, int factor, double tol, uint64_t max_iter, const double *betas0,
+                                         const double *rhos0, double *betas_out, double *rhos_out, uint64_t *landmarks_out, lssvm_reduced_logistic_info *infos,
+                                         const lssvm_mi355_options *options);
+int lssvm_mi355_fit_reduced_logistic_f64(const lssvm_params *params, const double *X, size_t num_points, size_t num_features, const double *Y, size_t num_rhs, const double *weights,
+                                         uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, int factor, double tol, uint64_t max_iter, const double *betas0,
+                                         const double *rhos0, double *betas_out, double *rhos_out, uint64_t *landmarks_out, lssvm_reduced_logistic_info *infos,
+                                         const lssvm_mi355_options *options);
+
 /* Landmark selection on a resident problem (opt-in): the pivots of a partial Cholesky factorisation of the kernel matrix, chosen greedily or
  * at random in proportion to the residual diagonal (randomly pivoted Cholesky).  The result is a list of point indices for the `landmarks` argument of the entry points
  * above; nothing else changes, and nothing selects it automatically.  Neither rule dominates the other or the fixed shuffle (README.md has the rows of all three kinds).

@@ -93,6 +93,15 @@ int lssvm_mi355_reduced_stream_phi(lssvm_mi355_reduced_stream *stream, const voi
  * after one untimed run.  The state is left untouched. */
 int lssvm_mi355_reduced_stream_time_kernels(lssvm_mi355_reduced_stream *stream, const void *X, size_t n, int repeats, double *cross_ms_out, double *landmark_ms_out);
 
+/* The step operator of the fixed-size logistic regression alone (lssvm_mi355_problem_fit_reduced_logistic), apart from any fit: one launch sequence
+ * of k_reduced_logistic_step over the slabs at the caller's coefficients.  betas: num_rhs x rank, rhos: num_rhs (b = -rho), Y: num_rhs x N labels of exactly -1 or +1 in
+ * the problem's dtype, weights: N doubles or NULL.  eta_out, q_out, z_out: num_rhs x N doubles each (eta_i = Phi_i beta + b, q_i = sqrt(a_i max(mu_i, delta)),
+ * z_i = eta_i + g_i / max(mu_i, delta)); loss_out: num_rhs sums of a_i l_i, the kernel's partial sums of 64 rows added in ascending row order on the host; floored_out
+ * (may be NULL): num_rhs counts of the rows with mu_i < delta.  Arguments and refusals as for the fit. */
+int lssvm_mi355_problem_reduced_logistic_step(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, const double *weights, uint64_t rank, const uint64_t *landmarks,
+                                              uint64_t slab_rows, const double *betas, const double *rhos, double *eta_out, double *q_out, double *z_out, double *loss_out,
+                                              uint64_t *floored_out);
+
 /* Measurement aid of tests/tools/reduced_loo_timing.py: on ONE slab of this problem (its first min(N, slab_rows) points, `rank` landmarks by the library's rule, an
  * identity V, k columns of ones) the Gram kernels of the fixed-size fit (gram_ms_out[r]: partial tiles and their sum over rank + 1 + k columns) and the leverage kernel
  * (leverage_ms_out[r]), device time of repeat r each after one untimed run of both. */

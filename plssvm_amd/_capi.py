@@ -57,6 +57,7 @@ EXPORTED_SYMBOLS = [
     "lssvm_mi355_reduced_stream_create_f32", "lssvm_mi355_reduced_stream_create_f64", "lssvm_mi355_reduced_stream_update", "lssvm_mi355_reduced_stream_solve",
     "lssvm_mi355_reduced_stream_loo", "lssvm_mi355_reduced_stream_export_state", "lssvm_mi355_reduced_stream_merge_state", "lssvm_mi355_reduced_stream_info",
     "lssvm_mi355_reduced_stream_destroy", "lssvm_mi355_reduced_stream_phi", "lssvm_mi355_reduced_stream_time_kernels",
+    "lssvm_mi355_problem_fit_reduced_logistic", "lssvm_mi355_fit_reduced_logistic_f32", "lssvm_mi355_fit_reduced_logistic_f64", "lssvm_mi355_problem_reduced_logistic_step",
     "lssvm_mi355_cg_begin", "lssvm_mi355_cg_step", "lssvm_mi355_cg_finish", "lssvm_mi355_problem_synchronize", "lssvm_mi355_problem_info",
     "lssvm_mi355_measure_bf16_mfma_ceiling", "lssvm_mi355_comm_library_path", "lssvm_mi355_set_io_threads", "lssvm_mi355_set_option", "lssvm_mi355_get_option",
     "lssvm_mi355_libsvm_open", "lssvm_mi355_libsvm_fill_f32", "lssvm_mi355_libsvm_fill_f64", "lssvm_mi355_libsvm_close",
@@ -418,6 +419,36 @@ def reduced_weighted_entry(name: str):
             fn.argtypes = [C.c_void_p] + common
         else:
             fn.argtypes = [C.POINTER(LssvmParams), C.c_void_p, C.c_size_t, C.c_size_t] + common + [C.c_void_p]
+        fn.restype = C.c_int
+    return fn
+
+
+class LssvmReducedLogisticInfo(C.Structure):
+    """``lssvm_reduced_logistic_info``: how one class of ``lssvm_mi355_problem_fit_reduced_logistic`` went."""
+    _fields_ = [("passes", C.c_uint64), ("halvings", C.c_uint64), ("floored", C.c_uint64), ("converged", C.c_int32), ("reserved", C.c_int32), ("objective", C.c_double),
+                ("last_decrease", C.c_double), ("jitter", C.c_double), ("max_abs_eta", C.c_double), ("landmark_ms", C.c_double), ("step_ms", C.c_double), ("gram_ms", C.c_double),
+                ("host_ms", C.c_double), ("total_ms", C.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
+def reduced_logistic_entry(name: str):
+    """The entry points of the fixed-size logistic regression (``lssvm_mi355_problem_fit_reduced_logistic``, ``lssvm_mi355_fit_reduced_logistic_f32 / _f64`` and the test
+    aid ``lssvm_mi355_problem_reduced_logistic_step``) with their argument types.  Bound at the first call."""
+    fn = getattr(lib, name)
+    if fn.argtypes is None:
+        dp, up = C.POINTER(C.c_double), C.POINTER(C.c_uint64)
+        common = [C.c_void_p, C.c_size_t, dp, C.c_uint64, up, C.c_uint64]  # Y, num_rhs, weights, rank, landmarks, slab_rows
+        if name == "lssvm_mi355_problem_reduced_logistic_step":
+            fn.argtypes = [C.c_void_p] + common + [dp, dp, dp, dp, dp, dp, up]  # betas, rhos, eta, q, z, loss, floored
+        else:
+            # factor, tol, max_iter, betas0, rhos0, betas, rhos, landmarks, infos
+            common += [C.c_int, C.c_double, C.c_uint64, dp, dp, dp, dp, up, C.POINTER(LssvmReducedLogisticInfo)]
+            if "problem" in name:
+                fn.argtypes = [C.c_void_p] + common
+            else:
+                fn.argtypes = [C.POINTER(LssvmParams), C.c_void_p, C.c_size_t, C.c_size_t] + common + [C.c_void_p]
         fn.restype = C.c_int
     return fn
 

@@ -388,6 +388,68 @@ def fit_reduced(params: Parameter, A, Y, rank: int, landmarks=None, slab_rows: i
     return _reduced_call(fn, (C.byref(ps), ptr(A), N, d), Y2, single, rank, lm_ptr, slab_rows, tail=(options_ptr(options),), on_device=on_device, weights=w)
 
 
+def _reduced_logistic_arguments(Y2, rank: int, tol, max_iter, start):
+    """What the logistic fit adds to the arguments of a weighted fit, checked as the library checks it: labels of exactly -1 or +1, ``tol`` finite and > 0,
+    ``max_iter`` >= 1 and the start values ``(betas0, rhos0)`` -- shaped like the result, all finite -- or None.  Returns ``(tol, max_iter, betas0, rhos0)``."""
+    if not np.all(np.abs(Y2) == 1):
+        raise InvalidParameterError("Every label of the logistic model must be exactly -1 or +1!")
+    if not (isinstance(tol, (int, float, np.floating)) and np.isfinite(tol) and tol > 0):
+        raise InvalidParameterError(f"tol must be finite and greater than 0, but is {tol!r}!")
+    if not (isinstance(max_iter, (int, np.integer)) and max_iter >= 1):
+        raise InvalidParameterError(f"max_iter must be an integer greater than 0, but is {max_iter!r}!")
+    if start is None:
+        return float(tol), int(max_iter), None, None
+    try:
+        betas0, rhos0 = start
+        betas0 = np.ascontiguousarray(betas0, dtype=np.float64).reshape(Y2.shape[0], -1)
+        rhos0 = np.ascontiguousarray(rhos0, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise InvalidParameterError("start must be a pair (betas0, rhos0) of numbers shaped like the result!") from None
+    if betas0.shape != (Y2.shape[0], rank) or rhos0.shape != (Y2.shape[0],):
+        raise InvalidParameterError(f"start must hold {Y2.shape[0]} x {rank} betas and {Y2.shape[0]} rhos, but their shapes are {betas0.shape} and {rhos0.shape}!")
+    if not (np.all(np.isfinite(betas0)) and np.all(np.isfinite(rhos0))):
+        raise InvalidParameterError("Every start value must be finite!")
+    return float(tol), int(max_iter), betas0, rhos0
+
+
+def _reduced_logistic_call(fn, head, Y2, single: bool, rank: int, lm_ptr, slab_rows: int, weights, on_device: bool, tol: float, max_iter: int, betas0, rhos0, tail=()):
+    k = Y2.shape[0]
+    betas = np.zeros((k, rank), dtype=np.float64)
+    rhos = np.zeros(k, dtype=np.float64)
+    used = np.zeros(rank, dtype=np.uint64)
+    infos = (_capi.LssvmReducedLogisticInfo * k)()
+    dp = C.POINTER(C.c_double)
+    check(fn(*head, ptr(Y2), k, _capi.weights_ptr(weights), rank, lm_ptr, slab_rows, int(on_device), tol, max_iter, _capi.weights_ptr(betas0), _capi.weights_ptr(rhos0),
+             betas.ctypes.data_as(dp), rhos.ctypes.data_as(dp), used.ctypes.data_as(C.POINTER(C.c_uint64)), infos, *tail))
+    reports = [info.as_dict() for info in infos]
+    if single:
+        return betas[0], float(rhos[0]), used, reports[0]
+    return betas, rhos, used, reports
+
+
+def fit_reduced_logistic(params: Parameter, A, Y, rank: int, landmarks=None, sample_weight=None, tol: float = 1e-8, max_iter: int = 50, factor: str = "host", start=None,
+                         slab_rows: int = 0, options: Options | None = None):
+    """The fixed-size kernel logistic regression over ``rank`` landmark points (``lssvm_mi355_fit_reduced_logistic_*``): with labels ``y_i`` of
+    exactly -1 or +1 the model ``eta(x) = sum_j beta_j k(x, x_L[j]) - rho`` minimises ``1/2 beta^T K_mm beta + C sum_i a_i log(1 + exp(-y_i eta(x_i)))`` by Newton's
+    method, every step a weighted fixed-size fit; ``eta`` is the log-odds of ``y = +1``.  ``Y``: one label vector ``(N,)`` or ``k`` of them ``(k, N)`` (one-vs-all),
+    which run in lockstep and share every evaluation of the landmark block.  ``sample_weight``: the prior weights ``a_i`` as :func:`fit_reduced` takes them.
+    ``tol``: the relative decrease of the objective at which a class stops; ``max_iter``: passes over the data, rejected steps included; ``start``: ``(betas0, rhos0)``
+    shaped like the result, or None for zeros.  ``landmarks``, ``factor``, ``slab_rows``: as in :func:`fit_reduced`.  Returns ``(betas, rhos, landmarks, info)``; ``info``:
+    the ``lssvm_reduced_logistic_info`` dict of the class, or a list of them for ``k`` label vectors.  Device 0; deterministic."""
+    on_device = _capi.factor_on_device(factor)
+    A = _as_matrix(A)
+    N, d = A.shape
+    w = _reduced_weights(sample_weight, N)
+    if isinstance(landmarks, str):  # a selection rule (:func:`select_landmarks`): one resident problem selects and fits
+        with ResidentProblem(params, A, options=options) as prob:
+            return prob.fit_reduced_logistic(Y, rank, landmarks, w, tol, max_iter, factor, start, slab_rows)
+    Y2, single, rank, _, lm_ptr, slab_rows = _reduced_arguments(Y, N, A.dtype, rank, landmarks, slab_rows)
+    tol, max_iter, betas0, rhos0 = _reduced_logistic_arguments(Y2, rank, tol, max_iter, start)
+    ps = _params_struct(params, d)
+    fn = _capi.reduced_logistic_entry(f"lssvm_mi355_fit_reduced_logistic_{suffix_of(A.dtype)}")
+    return _reduced_logistic_call(fn, (C.byref(ps), ptr(A), N, d), Y2, single, rank, lm_ptr, slab_rows, w, on_device, tol, max_iter, betas0, rhos0, tail=(options_ptr(options),))
+
+
 def _reduced_loo_costs(costs):
     """The cost grid of the leave-one-out scores, checked as the library checks it."""
     try:
@@ -1257,6 +1319,35 @@ class ResidentProblem:
         ranks = _reduced_rank_list(ranks, rank, costs.size)
         return _reduced_rank_path_call(_capi.reduced_rank_path_entry("lssvm_mi355_problem_fit_reduced_rank_path"), (self._h,), Y2, single, self.num_points, rank, lm_ptr, slab_rows,
                                        ranks, costs, on_device, w)
+
+    def fit_reduced_logistic(self, Y, rank: int, landmarks=None, sample_weight=None, tol: float = 1e-8, max_iter: int = 50, factor: str = "host", start=None, slab_rows: int = 0):
+        """:func:`fit_reduced_logistic` on this resident problem at its own cost (``lssvm_mi355_problem_fit_reduced_logistic``).  The problem is left as it was and keeps
+        its preconditioner.  Refused where :meth:`fit_reduced` is."""
+        on_device = _capi.factor_on_device(factor)
+        w = _reduced_weights(sample_weight, self.num_points)
+        Y2, single, rank, _, lm_ptr, slab_rows = _reduced_arguments(Y, self.num_points, self.dtype, rank, self._selected(rank, landmarks), slab_rows)
+        tol, max_iter, betas0, rhos0 = _reduced_logistic_arguments(Y2, rank, tol, max_iter, start)
+        return _reduced_logistic_call(_capi.reduced_logistic_entry("lssvm_mi355_problem_fit_reduced_logistic"), (self._h,), Y2, single, rank, lm_ptr, slab_rows, w, on_device, tol,
+                                      max_iter, betas0, rhos0)
+
+    def reduced_logistic_step(self, Y, betas, rhos, landmarks=None, sample_weight=None, slab_rows: int = 0):
+        """The step operator of :meth:`fit_reduced_logistic` alone at the caller's coefficients (a test aid, ``lssvm_mi355_problem_reduced_logistic_step``): ``betas``
+        ``(k, rank)`` and ``rhos`` ``(k,)`` for the ``k`` label vectors ``Y``.  Returns ``(eta, q, z, loss, floored)``: ``eta = Phi beta - rho``, ``q = sqrt(a max(mu, 2^-32))``
+        and the working responses ``z``, ``(k, N)`` float64 each, the ``k`` sums of ``a_i l_i`` and the ``k`` numbers of rows at the floor."""
+        betas = np.ascontiguousarray(betas, dtype=np.float64)
+        betas = betas.reshape(1, -1) if betas.ndim == 1 else betas
+        rhos = np.ascontiguousarray(rhos, dtype=np.float64).reshape(-1)
+        w = _reduced_weights(sample_weight, self.num_points)
+        Y2, _, rank, _, lm_ptr, slab_rows = _reduced_arguments(Y, self.num_points, self.dtype, betas.shape[1] if landmarks is None else None, landmarks, slab_rows)
+        _, _, betas, rhos = _reduced_logistic_arguments(Y2, rank, 1.0, 1, (betas, rhos))
+        k, N = Y2.shape
+        eta, q, z = np.zeros((k, N)), np.zeros((k, N)), np.zeros((k, N))
+        loss, floored = np.zeros(k), np.zeros(k, dtype=np.uint64)
+        dp = C.POINTER(C.c_double)
+        check(_capi.reduced_logistic_entry("lssvm_mi355_problem_reduced_logistic_step")(self._h, ptr(Y2), k, _capi.weights_ptr(w), rank, lm_ptr, slab_rows, betas.ctypes.data_as(dp),
+                                                                                          rhos.ctypes.data_as(dp), eta.ctypes.data_as(dp), q.ctypes.data_as(dp), z.ctypes.data_as(dp),
+                                                                                          loss.ctypes.data_as(dp), floored.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return eta, q, z, loss, floored
 
     def reduced_leverage_prefix(self, V, shift, ranks, Z=None, landmarks=None, slab_rows: int = 0):
         """The operator of :meth:`fit_reduced_rank_path` alone on the caller's operands (a test aid, ``lssvm_mi355_problem_reduced_leverage_prefix``): with

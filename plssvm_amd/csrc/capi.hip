@@ -239,6 +239,24 @@ void fit_reduced_one_shot(const lssvm_params *params, const T *X, size_t N, size
     }
 }
 
+/* lssvm_mi355_fit_reduced_logistic_*: likewise */
+template <typename T>
+void fit_reduced_logistic_one_shot(const lssvm_params *params, const T *X, size_t N, size_t d, const T *Y, size_t num_rhs, const double *weights, uint64_t rank, const uint64_t *landmarks,
+                                   uint64_t slab_rows, int factor, double tol, uint64_t max_iter, const double *betas0, const double *rhos0, double *betas_out, double *rhos_out,
+                                   uint64_t *landmarks_out, lssvm_reduced_logistic_info *infos, const lssvm_mi355_options *options) {
+    lssvm::check_params(params);
+    check_data(X, N, d);
+    lssvm::check_reduced_arguments(Y, num_rhs, rank, slab_rows, N);
+    LSSVM_REQUIRE(betas_out != nullptr && rhos_out != nullptr, "betas_out / rhos_out must not be NULL");
+    if (landmarks != nullptr) (void) lssvm::resolve_landmarks(landmarks, static_cast<size_t>(rank), N);
+    if (weights != nullptr) (void) lssvm::check_reduced_weights(weights, N);
+    lssvm::check_reduced_factor(factor);
+    lssvm::check_reduced_logistic_arguments(tol, max_iter, betas0, rhos0, num_rhs, rank);
+    lssvm::check_reduced_logistic_labels(Y, std::is_same_v<T, float> ? LSSVM_DTYPE_F32 : LSSVM_DTYPE_F64, num_rhs, N);
+    lssvm::Solver<T> prob = device0_solver<T>(options, *params, X, N, d);
+    prob.fit_reduced_logistic(Y, num_rhs, weights, rank, landmarks, slab_rows, factor, tol, max_iter, betas0, rhos0, betas_out, rhos_out, landmarks_out, infos);
+}
+
 /* lssvm_mi355_fit_reduced_loo_*: likewise */
 template <typename T>
 void fit_reduced_loo_one_shot(const lssvm_params *params, const T *X, size_t N, size_t d, const T *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows,
@@ -988,6 +1006,47 @@ int lssvm_mi355_fit_reduced_weighted_f64(const lssvm_params *params, const doubl
     return guarded([&] {
         lssvm::check_reduced_factor(factor);
         fit_reduced_one_shot<double>(params, X, num_points, num_features, Y, num_rhs, rank, landmarks, slab_rows, betas_out, rhos_out, landmarks_out, info, options, factor == 1, dense, weights);
+    });
+}
+/* the fixed-size logistic regression (lssvm_logistic.hip): the checks of the weighted fit in their order, then tol, max_iter and the start values; the
+ * weights and the labels need N: the solver checks them before it touches the device */
+static_assert(sizeof(lssvm_reduced_logistic_info) == 104, "lssvm_reduced_logistic_info changed: plssvm_amd/_capi.py (LssvmReducedLogisticInfo) changes with it");
+int lssvm_mi355_problem_fit_reduced_logistic(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, const double *weights, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows,
+                                             int factor, double tol, uint64_t max_iter, const double *betas0, const double *rhos0, double *betas_out, double *rhos_out,
+                                             uint64_t *landmarks_out, lssvm_reduced_logistic_info *infos) {
+    return guarded([&] {
+        LSSVM_REQUIRE(p != nullptr, "problem handle must not be NULL");
+        lssvm::check_reduced_arguments(Y, num_rhs, rank, slab_rows, 0);
+        LSSVM_REQUIRE(betas_out != nullptr && rhos_out != nullptr, "betas_out / rhos_out must not be NULL");
+        lssvm::check_reduced_factor(factor);
+        lssvm::check_reduced_logistic_arguments(tol, max_iter, betas0, rhos0, num_rhs, rank);
+        impl_of(p)->fit_reduced_logistic(Y, num_rhs, weights, rank, landmarks, slab_rows, factor, tol, max_iter, betas0, rhos0, betas_out, rhos_out, landmarks_out, infos);
+    });
+}
+int lssvm_mi355_fit_reduced_logistic_f32(const lssvm_params *params, const float *X, size_t num_points, size_t num_features, const float *Y, size_t num_rhs, const double *weights,
+                                         uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, int factor, double tol, uint64_t max_iter, const double *betas0,
+                                         const double *rhos0, double *betas_out, double *rhos_out, uint64_t *landmarks_out, lssvm_reduced_logistic_info *infos,
+                                         const lssvm_mi355_options *options) {
+    return guarded([&] {
+        fit_reduced_logistic_one_shot<float>(params, X, num_points, num_features, Y, num_rhs, weights, rank, landmarks, slab_rows, factor, tol, max_iter, betas0, rhos0, betas_out, rhos_out,
+                                             landmarks_out, infos, options);
+    });
+}
+int lssvm_mi355_fit_reduced_logistic_f64(const lssvm_params *params, const double *X, size_t num_points, size_t num_features, const double *Y, size_t num_rhs, const double *weights,
+                                         uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, int factor, double tol, uint64_t max_iter, const double *betas0,
+                                         const double *rhos0, double *betas_out, double *rhos_out, uint64_t *landmarks_out, lssvm_reduced_logistic_info *infos,
+                                         const lssvm_mi355_options *options) {
+    return guarded([&] {
+        fit_reduced_logistic_one_shot<double>(params, X, num_points, num_features, Y, num_rhs, weights, rank, landmarks, slab_rows, factor, tol, max_iter, betas0, rhos0, betas_out, rhos_out,
+                                              landmarks_out, infos, options);
+    });
+}
+int lssvm_mi355_problem_reduced_logistic_step(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, const double *weights, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows,
+                                              const double *betas, const double *rhos, double *eta_out, double *q_out, double *z_out, double *loss_out, uint64_t *floored_out) {
+    return guarded([&] {
+        LSSVM_REQUIRE(p != nullptr, "problem handle must not be NULL");
+        lssvm::check_reduced_arguments(Y, num_rhs, rank, slab_rows, 0);
+        impl_of(p)->reduced_logistic_step(Y, num_rhs, weights, rank, landmarks, slab_rows, betas, rhos, eta_out, q_out, z_out, loss_out, floored_out);
     });
 }
 int lssvm_mi355_problem_fit_reduced_loo_weighted(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, const double *weights, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows,

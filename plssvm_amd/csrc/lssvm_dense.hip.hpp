@@ -85,4 +85,55 @@ void dense_cholesky_aid(const double *A, int m, double nu, double *L_out, uint64
 void dense_solve_aid(const double *L, int m, const double *B, int k, double *X_out, double *ms_out);
 void dense_invert_lower_aid(const double *L, int m, double *V_out, double *ms_out);
 
+/* ---- what the translation units of the fixed-size model share (defined in lssvm_reduced.hip; used there and by lssvm_logistic.hip) ---- */
+constexpr int RG_TW = 128;                 // columns of Pt per operand of a tile
+constexpr int RG_KC = 16;                  // rows of Pt per step
+constexpr int RG_LS = RG_KC + 2;           // doubles between two columns in LDS: 144 bytes, conflict-free ds_read_b64 (as the fp64 tile kernels)
+constexpr int RG_RANGE = 2048;             // rows of a slab per workgroup: a CONSTANT (lssvm_reduced.hip has why)
+constexpr int RG_TILE = RG_TW * RG_TW;     // entries of a tile
+static_assert(RG_TW == DENSE_ST_TILE, "k_dense_assemble (lssvm_dense.hip) reads St as the tiles k_reduced_sum leaves");
+
+int tiles_of(int cols);
+/* St of one slab into the running sum: `rows` (a multiple of 256) rows of the column-major slab; `q`: sqrt(w) of these rows (`rows` doubles) for the weighted sum, or NULL */
+void enqueue_gram(const double *slab, size_t ld, int cols, int rows, int max_chunks, double *part, double *St, hipStream_t st, const double *q = nullptr);
+/* the tiles of St on the host -> cols x cols row major, the upper triangle the copy of the lower */
+void unpack_tiles(const std::vector<double> &tiles, int cols, std::vector<double> &G);
+
+/* rows of a slab (= doubles between two of its columns: at most N rounded up to 256) and how many slabs cover the N points; slab s holds the rows(s) points from row0(s)
+ * on, in rows256(s) <= ld rows */
+struct SlabPlan {
+    size_t N, ld;
+    int slabs;
+    SlabPlan(size_t num_points, uint64_t slab_rows) :
+        N(num_points), ld(std::min<size_t>(slab_rows == 0 ? REDUCED_DEFAULT_SLAB_ROWS : slab_rows, static_cast<size_t>(round_up(static_cast<long>(num_points), 256)))),
+        slabs(static_cast<int>((N + ld - 1) / ld)) {}
+    size_t row0(int s) const { return static_cast<size_t>(s) * ld; }
+    int rows(int s) const { return static_cast<int>(std::min(ld, N - row0(s))); }
+    int rows256(int s) const { return round_up(rows(s), 256); }  // (<= ld: ld is a multiple of 256)
+};
+
+/* the host's part of a fit, in double (lssvm_reduced.hip has the formulas) */
+double factor_reduced(const std::vector<double> &St, const std::vector<double> &Kmm, int m, int cols, double Nd, double sigma, std::vector<double> &L);
+void solve_reduced(const std::vector<double> &St, const std::vector<double> &L, int m, int k, int cols, double Nd, double *betas_out, double *rhos_out);
+/* trace(M) from the host copies, with factor_reduced's expression and cholesky_with_jitter's order: where no attempt fails, nu has the host path's bits */
+double reduced_trace(const std::vector<double> &St, const std::vector<double> &Kmm, int m, int cols, double Nd, double sigma);
+
+/* what one cost needs on the device besides St and K_mm, held over the costs of a grid */
+struct DenseFit {
+    DenseSpd dense;
+    DenseStopwatch watch;
+    DevBuf<double> betas, rhos;
+    std::vector<double> betas_host, rhos_host;  // where an attempt's results land before it is known to have factored
+    const int m, k;
+    hipStream_t st;
+    DenseFit(int rank, int num_rhs, hipStream_t stream);
+    size_t device_bytes() const { return dense.device_bytes() + (betas.count + rhos.count) * sizeof(double); }
+
+    /* One cost: the jitter rule of cholesky_with_jitter, each attempt assemble -> factor -> solve (-> invert into the operand Bt_op: rows of V, the betas behind them, ldb
+     * doubles apart) and ONE wait, at which betas (k x m), rhos (k) and the status word come back.  Fills `d` (may be NULL); returns nu.  Z_op (the rank path, DESIGN.md
+     * section 18; else NULL): z_c = L^-1 (t_c - s eta_c / N), k rows of ldb doubles, is left there too. */
+    double run(const ReducedOnDevice &dev, const std::vector<double> &St, const std::vector<double> &Kmm, int cols, double Nd, double sigma, double *Bt_op, int ldb, double *betas_out,
+               double *rhos_out, lssvm_dense_info *d, double *device_ms_out, double *Z_op = nullptr);
+};
+
 }  // namespace lssvm

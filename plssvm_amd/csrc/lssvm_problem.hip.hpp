@@ -656,6 +656,13 @@ struct ProblemBase {
                                          const uint64_t *ranks, size_t num_ranks, double *h_out, double *f_out) = 0;  // lssvm_mi355_problem_reduced_leverage_prefix
     virtual void time_leverage_prefix_kernel(uint64_t rank, uint64_t slab_rows, size_t k, const uint64_t *ranks, size_t num_ranks, int repeats,
                                              double *prefix_ms_out) = 0;  // lssvm_mi355_problem_time_leverage_prefix_kernel
+    /* the fixed-size kernel logistic regression by iteratively reweighted least squares (lssvm_logistic.hip) */
+    virtual void fit_reduced_logistic(const void *Y, size_t num_rhs, const double *weights, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, int factor, double tol,
+                                      uint64_t max_iter, const double *betas0, const double *rhos0, double *betas_out, double *rhos_out, uint64_t *landmarks_out,
+                                      lssvm_reduced_logistic_info *infos) = 0;  // lssvm_mi355_problem_fit_reduced_logistic
+    virtual void reduced_logistic_step(const void *Y, size_t num_rhs, const double *weights, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *betas,
+                                       const double *rhos, double *eta_out, double *q_out, double *z_out, double *loss_out,
+                                       uint64_t *floored_out) = 0;  // lssvm_mi355_problem_reduced_logistic_step
     /* landmark selection: the pivots of a greedy or randomly pivoted partial Cholesky factorisation (lssvm_select.hip) */
     virtual void select_landmarks(uint64_t rank, int method, uint64_t pool, uint64_t seed, double tol, uint64_t *landmarks_out, double *trace_out, double *residual_out,
                                   lssvm_landmark_select_info *info) = 0;  // lssvm_mi355_problem_select_landmarks
@@ -775,6 +782,12 @@ class Solver final : public ProblemBase {
     void reduced_leverage_prefix(uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *V, const double *shift, const double *Z, size_t k, const uint64_t *ranks,
                                  size_t num_ranks, double *h_out, double *f_out) override;
     void time_leverage_prefix_kernel(uint64_t rank, uint64_t slab_rows, size_t k, const uint64_t *ranks, size_t num_ranks, int repeats, double *prefix_ms_out) override;
+    /* Newton's method on the logistic loss over the landmarks: per pass one walk over the Phi slabs, the step kernel, a weighted Gram pass and the dense steps of `factor`
+     * per class (lssvm_logistic.hip) */
+    void fit_reduced_logistic(const void *Y, size_t num_rhs, const double *weights, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, int factor, double tol, uint64_t max_iter,
+                              const double *betas0, const double *rhos0, double *betas_out, double *rhos_out, uint64_t *landmarks_out, lssvm_reduced_logistic_info *infos) override;
+    void reduced_logistic_step(const void *Y, size_t num_rhs, const double *weights, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, const double *betas, const double *rhos,
+                               double *eta_out, double *q_out, double *z_out, double *loss_out, uint64_t *floored_out) override;
     /* fit_reduced and fit_reduced_loo with assembly, factorisation, solves and the triangular inverse on the device (lssvm_dense.hip) */
     void fit_reduced_dev(const void *Y, size_t num_rhs, uint64_t rank, const uint64_t *landmarks, uint64_t slab_rows, double *betas_out, double *rhos_out, uint64_t *landmarks_out,
                          lssvm_reduced_info *info, lssvm_dense_info *dense, const double *weights = nullptr) override;
@@ -890,6 +903,10 @@ void check_reduced_grid_kernel(int kernel_type);
  * ascending, each in [1, rank], and at most REDUCED_GRID_MAX_CELLS (cost, checkpoint) cells */
 constexpr size_t REDUCED_RANK_PATH_MAX_RANKS = 16;
 void check_reduced_rank_list(const uint64_t *ranks, size_t num_ranks, uint64_t rank, size_t num_costs);
+/* what lssvm_mi355_problem_fit_reduced_logistic / lssvm_mi355_fit_reduced_logistic_* add to the weighted fit (lssvm_logistic.hip): tol finite and > 0, max_iter >= 1, start
+ * values both given or both NULL and finite; and, once N is known (num_points > 0), labels of exactly -1 or +1 (`dtype`: that of Y) */
+void check_reduced_logistic_arguments(double tol, uint64_t max_iter, const double *betas0, const double *rhos0, size_t num_rhs, uint64_t rank);
+void check_reduced_logistic_labels(const void *Y, int dtype, size_t num_rhs, size_t num_points);
 
 /* the arguments of lssvm_mi355_problem_select_landmarks / lssvm_mi355_select_landmarks_* that need no device (lssvm_select.hip); returns the number of candidates */
 constexpr int SELECT_MAX_RANK = 1024;

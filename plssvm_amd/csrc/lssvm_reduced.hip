@@ -53,12 +53,7 @@ namespace lssvm {
 
 namespace {
 
-constexpr int RG_TW = 128;                 // columns of Pt per operand of a tile
-constexpr int RG_KC = 16;                  // rows of Pt per step
-constexpr int RG_LS = RG_KC + 2;           // doubles between two columns in LDS: 144 bytes, conflict-free ds_read_b64 (as the fp64 tile kernels)
-constexpr int RG_RANGE = 2048;             // rows of a slab per workgroup: a CONSTANT (see above)
-constexpr int RG_TILE = RG_TW * RG_TW;     // entries of a tile
-static_assert(RG_TW == DENSE_ST_TILE, "k_dense_assemble (lssvm_dense.hip) reads St as the tiles k_reduced_sum leaves");
+/* (RG_TW, RG_KC, RG_LS, RG_RANGE, RG_TILE: lssvm_dense.hip.hpp, with what lssvm_logistic.hip shares of this file) */
 
 /* the 1 column and the y columns of Pt beside Phi, in double: column c of `out` (ld doubles apart) is 1 (c = 0) or right-hand side c - 1; exact zeros from row N on */
 template <typename T>
@@ -200,10 +195,12 @@ __global__ __launch_bounds__(256) void k_reduced_sum(const double *__restrict__ 
     St[tile * RG_TILE + e] = acc;
 }
 
+}  // namespace
+
 int tiles_of(int cols) { return (cols + RG_TW - 1) / RG_TW; }
 
 /* St of one slab into the running sum: `rows` (a multiple of 256) rows of the column-major slab; `q`: sqrt(w) of these rows (`rows` doubles) for the weighted sum, or NULL */
-void enqueue_gram(const double *slab, size_t ld, int cols, int rows, int max_chunks, double *part, double *St, hipStream_t st, const double *q = nullptr) {
+void enqueue_gram(const double *slab, size_t ld, int cols, int rows, int max_chunks, double *part, double *St, hipStream_t st, const double *q) {
     const int nt = tiles_of(cols), ntri = nt * (nt + 1) / 2, chunks = (rows + RG_RANGE - 1) / RG_RANGE;
     if (q != nullptr) {
         hipLaunchKernelGGL(k_reduced_gram<true>, dim3(ntri, chunks), dim3(256), 0, st, slab, ld, cols, rows, max_chunks, part, q);
@@ -232,18 +229,8 @@ void unpack_tiles(const std::vector<double> &tiles, int cols, std::vector<double
     }
 }
 
-/* rows of a slab (= doubles between two of its columns: at most N rounded up to 256) and how many slabs cover the N points; slab s holds the rows(s) points from row0(s)
- * on, in rows256(s) <= ld rows */
-struct SlabPlan {
-    size_t N, ld;
-    int slabs;
-    SlabPlan(size_t num_points, uint64_t slab_rows) :
-        N(num_points), ld(std::min<size_t>(slab_rows == 0 ? REDUCED_DEFAULT_SLAB_ROWS : slab_rows, static_cast<size_t>(round_up(static_cast<long>(num_points), 256)))),
-        slabs(static_cast<int>((N + ld - 1) / ld)) {}
-    size_t row0(int s) const { return static_cast<size_t>(s) * ld; }
-    int rows(int s) const { return static_cast<int>(std::min(ld, N - row0(s))); }
-    int rows256(int s) const { return round_up(rows(s), 256); }  // (<= ld: ld is a multiple of 256)
-};
+/* (SlabPlan: lssvm_dense.hip.hpp) */
+namespace {
 
 /* the k right-hand sides (k x N, the problem's type) on the device, or none of them for Y = NULL */
 template <typename T>
@@ -284,6 +271,8 @@ void timed_repeats(hipStream_t st, int repeats, double *out_ms, Before before, L
 
 /* ---- the host's part of a fit, in double, shared by fit_reduced and fit_reduced_loo: M = S - s s^T / N + sigma K_mm (lower triangle), (M + nu I) = L L^T,
  * (M + nu I) beta_c = t_c - s eta_c / N, b_c = (eta_c - s^T beta_c) / N ---- */
+}  // namespace
+
 double factor_reduced(const std::vector<double> &St, const std::vector<double> &Kmm, int m, int cols, double Nd, double sigma, std::vector<double> &L) {
     const double *s = &St[static_cast<size_t>(m) * cols];
     std::vector<double> M(static_cast<size_t>(m) * m, 0.0);
@@ -291,6 +280,8 @@ double factor_reduced(const std::vector<double> &St, const std::vector<double> &
         for (int l = 0; l <= j; ++l) M[static_cast<size_t>(j) * m + l] = St[static_cast<size_t>(j) * cols + l] - s[j] * s[l] / Nd + sigma * Kmm[static_cast<size_t>(j) * m + l];
     return cholesky_with_jitter(M, m, "the matrix of the reduced model", L);
 }
+
+namespace {
 
 /* the two halves of a solve, for right-hand side c and the leading r x r block of the m x m factor L (solve_reduced: r = m; the rank path, DESIGN.md section 18: every
  * checkpoint r <= m -- the factor of a leading block is the leading block of the factor, and z of the block is z[:r]) */
@@ -318,6 +309,8 @@ double backward_reduced(const std::vector<double> &St, const std::vector<double>
     return -((eta - sb) / Nd);
 }
 
+}  // namespace
+
 void solve_reduced(const std::vector<double> &St, const std::vector<double> &L, int m, int k, int cols, double Nd, double *betas_out, double *rhos_out) {
     std::vector<double> z(static_cast<size_t>(m));
     for (int c = 0; c < k; ++c) {
@@ -325,6 +318,8 @@ void solve_reduced(const std::vector<double> &St, const std::vector<double> &L, 
         rhos_out[c] = backward_reduced(St, L, m, m, c, cols, Nd, z.data(), betas_out + static_cast<size_t>(c) * m);
     }
 }
+
+namespace {
 
 /* row n of `out` (ldb doubles apart, zeros beyond the diagonal) = row n of V = L^-1 by forward substitution, row by row: V[n][:] = (e_n - sum_{l < n} L[n][l] V[l][:]) / L[n][n],
  * the l ascending for every entry.
@@ -362,6 +357,8 @@ double host_operand(const std::vector<double> &St, const std::vector<double> &Km
 }
 
 /* ---- the same steps on the device (lssvm_dense.hip) ---- */
+}  // namespace
+
 /* trace(M) from the host copies, with factor_reduced's expression and cholesky_with_jitter's order: where no attempt fails, nu has the host path's bits */
 double reduced_trace(const std::vector<double> &St, const std::vector<double> &Kmm, int m, int cols, double Nd, double sigma) {
     const double *s = &St[static_cast<size_t>(m) * cols];
@@ -372,26 +369,16 @@ double reduced_trace(const std::vector<double> &St, const std::vector<double> &K
     return trace;
 }
 
-/* what one cost needs on the device besides St and K_mm, held over the costs of a grid */
-struct DenseFit {
-    DenseSpd dense;
-    DenseStopwatch watch;
-    DevBuf<double> betas, rhos;
-    std::vector<double> betas_host, rhos_host;  // where an attempt's results land before it is known to have factored
-    const int m, k;
-    hipStream_t st;
-    DenseFit(int rank, int num_rhs, hipStream_t stream) :
-        dense(rank, num_rhs, stream), watch(stream), betas_host(static_cast<size_t>(num_rhs) * rank), rhos_host(static_cast<size_t>(num_rhs)), m(rank), k(num_rhs), st(stream) {
-        betas.alloc_zero(static_cast<size_t>(k) * m, st);
-        rhos.alloc_zero(static_cast<size_t>(k), st);
-    }
-    size_t device_bytes() const { return dense.device_bytes() + (betas.count + rhos.count) * sizeof(double); }
+/* what one cost needs on the device besides St and K_mm, held over the costs of a grid (the struct: lssvm_dense.hip.hpp) */
+DenseFit::DenseFit(int rank, int num_rhs, hipStream_t stream) :
+    dense(rank, num_rhs, stream), watch(stream), betas_host(static_cast<size_t>(num_rhs) * rank), rhos_host(static_cast<size_t>(num_rhs)), m(rank), k(num_rhs), st(stream) {
+    betas.alloc_zero(static_cast<size_t>(k) * m, st);
+    rhos.alloc_zero(static_cast<size_t>(k), st);
+}
 
-    /* One cost: the jitter rule of cholesky_with_jitter, each attempt assemble -> factor -> solve (-> invert into the operand Bt_op: rows of V, the betas behind them, ldb
-     * doubles apart) and ONE wait, at which betas (k x m), rhos (k) and the status word come back.  Fills `d` (may be NULL); returns nu.  Z_op (the rank path, DESIGN.md
-     * section 18; else NULL): z_c = L^-1 (t_c - s eta_c / N), k rows of ldb doubles, is left there too. */
-    double run(const ReducedOnDevice &dev, const std::vector<double> &St, const std::vector<double> &Kmm, int cols, double Nd, double sigma, double *Bt_op, int ldb, double *betas_out,
-               double *rhos_out, lssvm_dense_info *d, double *device_ms_out, double *Z_op = nullptr) {
+double DenseFit::run(const ReducedOnDevice &dev, const std::vector<double> &St, const std::vector<double> &Kmm, int cols, double Nd, double sigma, double *Bt_op, int ldb,
+                     double *betas_out, double *rhos_out, lssvm_dense_info *d, double *device_ms_out, double *Z_op) {
+    {
         const double trace = reduced_trace(St, Kmm, m, cols, Nd, sigma);
         LSSVM_REQUIRE(std::isfinite(trace) && trace > 0.0, "the matrix of the reduced model has no positive finite trace");
         double nu = DBL_EPSILON * trace;
@@ -434,7 +421,9 @@ struct DenseFit {
         }
         throw Error(LSSVM_ERR_INTERNAL, "the matrix of the reduced model could not be factored (jitter up to " + std::to_string(nu / 10.0) + ")");
     }
-};
+}
+
+namespace {
 
 /* ---- the leave-one-out pass ---- */
 constexpr int LV_LSA = RG_TW + 16;  // doubles between two columns of Phi in LDS: the four k-rows of an MFMA's A fragments start 32 banks apart

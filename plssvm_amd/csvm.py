@@ -192,6 +192,34 @@ class CSVM:
         reduced = DataSet(data.data()[rows], [labels[i] for i in rows.tolist()], real_type=data.real_type)
         return Model(params, reduced, alpha=np.asarray(betas[0]).astype(data.real_type), rho=rhos[0])
 
+    def solve_reduced_logistic_systems(self, params, A, Y, rank, landmarks=None, sample_weight=None, tol=1e-8, max_iter=50, factor="host", start=None):
+        """The fixed-size logistic regression of every row of ``Y`` (labels of -1 / +1) over the same landmarks: ``(betas[k, m] float64, rhos[k] float64, landmarks[m],
+        infos[k])``.  Boundary of :meth:`fit_reduced_logistic`; the MI355X backend implements it."""
+        raise NotImplementedError
+
+    def fit_reduced_logistic(self, data: DataSet, rank: int, landmarks=None, sample_weight=None, tol: float = 1e-8, max_iter: int = 50, factor: str = "host", start=None) -> Model:
+        """A fixed-size kernel logistic regression of ``rank`` support vectors (no counterpart in the reference): the model of :meth:`fit_reduced` --
+        the same landmarks, the same file format, predict and score -- fitted to the logistic loss ``C sum_i a_i log(1 + exp(-y_i f(x_i)))`` instead of the squared one, by
+        Newton's method with a step-halving safeguard, every step a weighted fixed-size fit.  Its decision values are the log-odds of the class the positive label maps
+        to: ``P = 1 / (1 + exp(-f(x)))``.  ``sample_weight``: the prior weights ``a_i`` as :meth:`fit_reduced` takes them; ``tol``: the relative decrease of the objective
+        at which the iteration stops; ``max_iter``: passes over the data, rejected steps included; ``start``: ``(betas0, rho0)`` or None for zeros.  The model file carries
+        no probability field.  ``last_cg_info`` keeps the ``lssvm_reduced_logistic_info`` report with ``iterations`` = its passes."""
+        _capi.factor_on_device(factor)
+        if not data.has_labels():
+            raise InvalidParameterError("No labels given for training! Maybe the data is only usable for prediction?")  # csvm.hpp:298
+        labels = data.labels()
+        if landmarks is not None and not isinstance(landmarks, str):  # (a selection rule's points are checked once they are known)
+            _check_landmark_classes(data, landmarks)  # (before anything is computed)
+        params = self.params.resolved(data.num_features())
+        t0 = time.perf_counter()
+        betas, rhos, used, infos = self.solve_reduced_logistic_systems(params, data.data(), data.mapped_labels().reshape(1, -1), rank, landmarks, sample_weight=sample_weight, tol=tol,
+                                                                        max_iter=max_iter, factor=factor, start=start)
+        info = dict(infos[0], iterations=int(infos[0]["passes"]), landmarks=np.asarray(used), total_runtime_ms=(time.perf_counter() - t0) * 1e3)
+        self.last_cg_info = info
+        rows = _check_landmark_classes(data, used)
+        reduced = DataSet(data.data()[rows], [labels[i] for i in rows.tolist()], real_type=data.real_type)
+        return Model(params, reduced, alpha=np.asarray(betas[0]).astype(data.real_type), rho=rhos[0])
+
     def solve_reduced_loo_systems(self, params, A, Y, rank, costs, landmarks=None, factor="host", sample_weight=None):
         """The fixed-size models of every row of ``Y`` at every cost of ``costs`` with their leave-one-out report: ``(betas[S, k, m], rhos[S, k], landmarks[m], report)``.
         Boundary of :meth:`fit_reduced_path`; the MI355X backend implements it."""
@@ -535,6 +563,15 @@ class MI355CSVM(CSVM):
             raise InvalidParameterError(f"The reduced model is fitted on one device, but this backend object shards a solve over {'every visible device' if self.use_devices == 0 else self.use_devices}"
                                         f"{'' if self.use_devices == 0 else ' devices'} (num_devices={self.use_devices})!")
         return backend.fit_reduced(params, A, Y, rank, landmarks=landmarks, options=self._options, factor=factor, sample_weight=sample_weight)
+
+    def solve_reduced_logistic_systems(self, params, A, Y, rank, landmarks=None, sample_weight=None, tol=1e-8, max_iter=50, factor="host", start=None):
+        """``backend.fit_reduced_logistic`` on device 0: the rows of ``Y`` in lockstep, one evaluation of the landmark block per pass for all of them.  A backend object of
+        several devices raises, as :meth:`solve_reduced_systems` does."""
+        if self.use_devices != 1:
+            raise InvalidParameterError(f"The reduced model is fitted on one device, but this backend object shards a solve over {'every visible device' if self.use_devices == 0 else self.use_devices}"
+                                        f"{'' if self.use_devices == 0 else ' devices'} (num_devices={self.use_devices})!")
+        return backend.fit_reduced_logistic(params, A, Y, rank, landmarks=landmarks, sample_weight=sample_weight, tol=tol, max_iter=max_iter, factor=factor, start=start,
+                                            options=self._options)
 
     def solve_reduced_loo_systems(self, params, A, Y, rank, costs, landmarks=None, factor="host", sample_weight=None):
         """``backend.fit_reduced_loo`` on device 0: one landmark block and one Gram matrix for all costs and rows of ``Y``, then one leverage pass per cost on the fp64

@@ -375,6 +375,83 @@ def fit_reduced_weighted(estimator, X, y, rank, sample_weight=None, landmarks=No
     return _fit_reduced(estimator, X, y, rank, landmarks, factor, weighted=True, sample_weight=sample_weight)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# class probabilities: the fixed-size kernel logistic regression (CSVM.fit_reduced_logistic)
+# ---------------------------------------------------------------------------------------------------------------------
+def _sigmoid(d):
+    """1 / (1 + exp(-d)) without overflow: exp is taken of -|d| only."""
+    d = np.asarray(d, dtype=np.float64)
+    e = np.exp(-np.abs(d))
+    return np.where(d >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
+
+
+class ProbabilisticSVC(SVC):
+    """An :class:`SVC` whose decision values are log-odds: what :func:`fit_reduced_logistic` returns.  Everything :class:`SVC` offers, and ``predict_proba`` /
+    ``predict_log_proba``; ``n_iter_`` counts the passes of the Newton iteration.  Two classes: ``P(classes_[1] | x) = 1 / (1 + exp(-decision_function(x)))``.  More than
+    two classes are fitted one-vs-all; the classifiers' probabilities are normalised by their sum per point."""
+
+    def predict_proba(self, X):
+        """The class probabilities of every row of X, ndarray of shape (n, n_classes); the columns follow ``classes_``."""
+        d = np.asarray(self.decision_function(X), dtype=np.float64)
+        if d.ndim == 1:
+            return np.column_stack([_sigmoid(-d), _sigmoid(d)])
+        p = _sigmoid(d)
+        return p / p.sum(axis=1, keepdims=True)
+
+    def predict_log_proba(self, X):
+        """log of :meth:`predict_proba`."""
+        with np.errstate(divide="ignore"):
+            return np.log(self.predict_proba(X))
+
+    def predict(self, X):
+        """The class of the largest probability (ties: the lowest class index)."""
+        return self.classes_[np.argmax(self.predict_proba(X), axis=1)]
+
+    n_iter_ = _fitted_attribute("n_iter_", "Passes of the Newton iteration, rejected steps included; more than two classes: of every classifier, int ndarray of shape (n_classes,).")
+
+
+def fit_reduced_logistic(estimator, X, y, rank, sample_weight=None, landmarks=None, tol=1e-8, max_iter=50, factor="host"):
+    """A fitted :class:`ProbabilisticSVC` with ``estimator``'s parameters whose model has ``rank`` support vectors (:meth:`plssvm_amd.csvm.CSVM.fit_reduced_logistic`,
+    DESIGN.md section 20): the landmarks of :func:`fit_reduced`, fitted to the logistic loss ``C sum_i w_i log(1 + exp(-y_i f(x_i)))`` instead of the squared one, so that
+    ``decision_function`` returns log-odds and ``predict_proba`` probabilities.  Two classes and one-vs-all alike; the classifiers of a one-vs-all fit run in lockstep and
+    share every evaluation of the landmark block.  ``estimator.class_weight`` is honoured as :func:`fit_reduced_weighted` honours it: ``w_i = sample_weight[i] x
+    class_weight[y[i]]``.  ``tol`` and ``max_iter`` here are the Newton iteration's (the relative decrease of the objective at which it stops; passes over the data,
+    rejected steps included): ``estimator.tol`` and ``estimator.max_iter`` are the CG solve's and are not used.  ``estimator`` itself stays unfitted."""
+    _capi.factor_on_device(factor)
+    if not isinstance(estimator, SVC):
+        raise InvalidParameterError("estimator must be a plssvm_amd.svc.SVC")
+    X, y = np.asarray(X), np.asarray(y)
+    if X.ndim != 2 or y.ndim != 1 or y.shape[0] != X.shape[0]:
+        raise InvalidParameterError(f"X must be a matrix and y a vector of as many labels as X has rows, but their shapes are {X.shape} and {y.shape}!")
+    params = estimator._params()
+    classes = np.array(sorted(set(y.tolist())))
+    weighted = sample_weight is not None or estimator.class_weight is not None
+    class_weight, weights = _reduced_point_weights(estimator, classes, y, sample_weight) if weighted else (np.ones(len(classes)), None)
+    svm = make_csvm(params=params)
+    clone = ProbabilisticSVC(**estimator.get_params())
+    if len(classes) > 2:
+        Xr = np.ascontiguousarray(X, dtype=estimator.real_type)
+        resolved = params.resolved(Xr.shape[1])
+        betas, rhos, used, infos = svm.solve_reduced_logistic_systems(resolved, Xr, _multiclass.one_vs_all_targets(classes, y, Xr.dtype), rank, landmarks, sample_weight=weights,
+                                                                      tol=tol, max_iter=max_iter, factor=factor)
+        rows = np.asarray(used).astype(np.int64)
+        infos = [dict(info, iterations=int(info["passes"])) for info in infos]
+        model = _multiclass.OneVsAllModel(resolved, classes, np.ascontiguousarray(Xr[rows]), np.asarray(betas).astype(Xr.dtype), np.asarray(rhos).astype(Xr.dtype), infos)
+        nonzero = np.any(model.alpha != 0, axis=0)
+        clone._svm, clone._model = svm, model
+        clone._fit = {
+            "classes_": classes, "class_weight_": class_weight, "fit_status_": 0, "n_features_in_": int(X.shape[1]), "shape_fit_": tuple(int(v) for v in X.shape),
+            "n_iter_": np.array([info["iterations"] for info in infos], dtype=np.int64), "support_": rows.astype(np.int32), "support_vectors_": model.support_vectors,
+            "n_support_": np.array([np.count_nonzero(nonzero & (y[rows] == c)) for c in classes], dtype=np.int32), "dual_coef_": model.alpha, "intercept_": -model.rho,
+        }
+        return clone
+    data = DataSet(X, y.tolist(), real_type=estimator.real_type)
+    model = svm.fit_reduced_logistic(data, rank, landmarks, sample_weight=weights, tol=tol, max_iter=max_iter, factor=factor)
+    clone._set_binary_fit(svm, model, model.data, X, y, class_weight, None, int(svm.last_cg_info["iterations"]))
+    clone._fit["support_"] = _landmarks_of(svm, landmarks)
+    return clone
+
+
 def fit_reduced_stream(estimator, chunks, landmarks, classes, Cs=None, sample_weight_of=None):
     """:func:`fit_reduced_weighted` / :func:`fit_reduced_cv_weighted` for data that arrives in pieces (:meth:`plssvm_amd.csvm.CSVM.fit_reduced_stream`, DESIGN.md
     section 19).  ``chunks``: a re-iterable of ``(X, y)`` pairs (a list, or an object whose ``__iter__`` reads the pieces again).  ``landmarks``: the landmark ROWS
