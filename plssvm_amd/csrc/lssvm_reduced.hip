@@ -7,10 +7,13 @@
  * Pt = [Phi | 1 | y_0 ... y_{k-1}], the host solves (include/plssvm_amd.h has the formulas).  No CG and no n x n pass.
  *
  * Pt is produced in row slabs of `slab_rows` rows, COLUMN by column (a column is contiguous over the rows), so the contraction index of Pt^T Pt is contiguous in both
- * operands.  k_reduced_gram: one workgroup owns (a 128 x 128 tile on or below the diagonal, RG_RANGE rows of the slab) and leaves its partial tile; the four waves hold
- * 64 x 64 each as sixteen accumulators of v_mfma_f64_16x16x4_f64.  k_reduced_sum adds the partial tiles to the running St in ascending row order.  RG_RANGE is a
+ * operands.  k_reduced_gram: one workgroup owns (a 128 x 128 tile on or below the diagonal, RG_RANGE rows of the slab) and leaves its partial tile.  k_reduced_sum adds the partial tiles to the running St in ascending row order.  RG_RANGE is a
  * constant: the order in which an entry is summed depends on N and slab_rows only, never on the number of columns -- so row c of a call with k right-hand sides has the
  * bits of the call with that right-hand side alone.  No atomics, no scratch.  Compiled for gfx950 only.
+ *
+ * The five kernels that form 128 x 128 tiles on v_mfma_f64_16x16x4_f64 -- k_reduced_gram, k_reduced_leverage, k_reduced_leverage_prefix, k_landmark_product and
+ * k_cross_product -- share ONE tile loop (TileLanes, tile_zero, tile_contract: below): four waves of 64 x 64, sixteen pinned accumulators each, both operands through LDS
+ * with the next step's loads in flight under the MFMAs.  A kernel's body is what is its own: its staging and its epilogue.
  *
  * Exact leave-one-out scores over a cost grid (lssvm_mi355_problem_fit_reduced_loo, _reduced_leverage, lssvm_mi355_fit_reduced_loo_*), leave-one-out
  * with the landmark set held fixed: the fit is a linear smoother, so with M + nu I = L L^T, V = L^-1 and Phic = Phi - 1 s^T / N the leverage is h_ii = 1 / N + |V phic_i|^2
@@ -24,17 +27,17 @@
  *
  * The leave-one-out scores over a (gamma, cost) grid on one problem (lssvm_mi355_problem_fit_reduced_grid, _landmark_acc, lssvm_mi355_fit_reduced_grid_*; DESIGN.md
  * section 17): what a kernel value is made from, D = sum_f (a_f - b_f)^2 or sum_f a_f b_f, does not depend on gamma.  GridSlabs forms it once per slab and pass --
- * k_landmark_acc (the loop of k_landmark_block) or k_landmark_product (the dot products on v_mfma_f64_16x16x4_f64, the norm expansion for rbf) -- and k_kernel_values
+ * k_landmark_acc (the loop of k_landmark_block) or k_landmark_product (the dot products on the tile loop, the norm expansion for rbf) -- and k_kernel_values
  * writes the Phi columns of a gamma from it; the Gram pass, the dense steps and the leverage kernel per (gamma, cost) are the ones above.
  *
  * The leave-one-out scores of every prefix rank from one fit (lssvm_mi355_problem_fit_reduced_rank_path, _reduced_leverage_prefix, lssvm_mi355_fit_reduced_rank_path_*;
  * DESIGN.md section 18): the landmark list is ordered, and M, L, V = L^-1 and z = L^-1 rhs of the first r landmarks are the leading blocks of the rank-m ones.  Pass 1 and
  * the dense steps per cost are the ones above (the host's solve split into its forward and backward half: z is kept, the back substitution runs on every leading block);
- * in pass 2 k_reduced_leverage_prefix forms Phic V^T as k_reduced_leverage does and takes the running sums of u^2 and u z_c out of its accumulators at the checkpoints.
+ * in pass 2 k_reduced_leverage_prefix forms Phic V^T (LeverageTile, shared with k_reduced_leverage) and takes the running sums of u^2 and u z_c out of its accumulators at the checkpoints.
  * Every prefix model of a cost takes the nu of the full rank.
  *
  * The same model from a STREAM of chunks (lssvm_mi355_reduced_stream_*; the end of this file): St is additive over rows, so a handle that owns the
- * landmark ROWS, K_mm, the running St and one pending slab takes the points piece by piece, without a resident problem.  k_cross_product -- the sibling of
+ * landmark ROWS, K_mm, the running St and one pending slab takes the points piece by piece, without a resident problem.  k_cross_product -- the body of
  * k_landmark_product for rows that are in no problem, both operands centred as they are staged -- evaluates a chunk's D at the slab's fill position; k_kernel_values,
  * enqueue_gram, the dense steps per cost and k_reduced_leverage are the ones above, unchanged.  The state after any sequence of updates is the state one update of the
  * concatenated rows leaves: no result depends on the cuts.
@@ -66,10 +69,67 @@ __global__ __launch_bounds__(256) void k_reduced_aux(const T *__restrict__ Y, si
     out[static_cast<size_t>(c) * ld + local] = v;
 }
 
+/* ---- the 128 x 128 tile loop on v_mfma_f64_16x16x4_f64 (k_reduced_gram, k_reduced_leverage, k_reduced_leverage_prefix, k_landmark_product, k_cross_product) ----
+ * A workgroup of 256 threads forms one 128 x 128 tile of A B^T; its four waves hold 64 x 64 each (wave = 2 wr + wc: row half wr, column half wc) as sixteen accumulators.
+ * Both operands go through LDS in steps of RG_KC = 16 of the contraction index.  Lane 16 qd + r of a wave reads, per MFMA, entry (row r of a 16-row block, index qd of the
+ * k-step) of either operand and holds rows qd + 4 i, column r of each 16 x 16 block of the result.  A row-major operand (RG_LS doubles between two rows) is staged by
+ * thread -> (row srow [+ 32 p], indices 2 sseg, 2 sseg + 1 of the step): eight threads load the 16 indices of a row as one line. */
+struct TileLanes {
+    int tid, lane, wave, wr, wc, r, qd, srow, sseg;
+    __device__ __forceinline__ TileLanes() :
+        tid(threadIdx.x), lane(tid & 63), wave(tid >> 6), wr(wave >> 1), wc(wave & 1), r(lane & 15), qd(lane >> 4), srow(tid >> 3), sseg(tid & 7) {}
+};
+
+/* the sixteen accumulators of a wave, zeroed */
+__device__ __forceinline__ void tile_zero(f64x4 (&acc)[4][4]) {
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+            acc[mt][nt] = f64x4{ 0.0, 0.0, 0.0, 0.0 };
+            // the start values live in the accumulators' OWN registers (C == D for every MFMA of a chain): lssvm_tile_f64_wide.hip.hpp has the hazard this keeps away
+            asm volatile("" : "+v"(acc[mt][nt]));
+        }
+}
+
+/* acc += A B^T over `nsteps` steps.  stage_load(s) takes step s from memory into registers, stage_store() puts them into LDS: the loads of step s + 1 are in flight under
+ * the 64 MFMAs of step s (whatever is done to the staged values belongs into stage_store: the step's MFMAs stand between a load and its first use).  Ab / Bb: the lane's
+ * first entry of either operand in LDS; A's block t, k-sub-step ks is Ab[t A_T + ks A_KS], B's is Bb[t 16 RG_LS + 4 ks].  Every accumulator is one chain over s and ks
+ * ascending.  Ends behind a barrier: every wave has read the last step. */
+template <int A_T, int A_KS, typename Load, typename Store>
+__device__ __forceinline__ void tile_contract(int nsteps, const double *Ab, const double *Bb, f64x4 (&acc)[4][4], Load stage_load, Store stage_store) {
+    if (nsteps > 0) {
+        stage_load(0);
+        stage_store();
+    }
+    __syncthreads();
+    for (int s = 0; s < nsteps; ++s) {
+        const bool has_next = s + 1 < nsteps;
+        if (has_next) stage_load(s + 1);
+#pragma unroll
+        for (int ks = 0; ks < RG_KC / 4; ++ks) {
+            double av[4], bv[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                av[t] = Ab[t * A_T + ks * A_KS];
+                bv[t] = Bb[t * 16 * RG_LS + ks * 4];
+            }
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[mt], bv[nt], acc[mt][nt], 0, 0, 0);
+        }
+        __syncthreads();  // (every wave has read this step)
+        if (has_next) {
+            stage_store();
+            __syncthreads();
+        }
+    }
+}
+
 /* part[tile][chunk] = A^T B over the rows [chunk RG_RANGE, min((chunk + 1) RG_RANGE, rows)) of the slab, A = the columns 128 bj ... and B = the columns 128 bk ... of the
  * column-major `slab` (ld doubles between two columns; columns from `cols` on count as zeros and are never read; `rows` is a multiple of RG_KC), for tile = (bj, bk),
- * bk <= bj.  Both operands go through LDS: eight threads load the 16 rows of a column of a step as one 128-byte line, the fragments are read as in tile_matvec_f64
- * (lane 16 q + r: column r of the block, row q of the k-step).  A diagonal tile stages and reads ONE operand.  The result of a lane: column r of B, rows q + 4 i of A.
+ * bk <= bj.  The tile loop above, a column of the slab being a row of either operand.  A diagonal tile stages and reads ONE operand.
  * Two waves per SIMD (at most 256 registers): the other workgroup of the CU computes while this one waits at its barriers.
  * WEIGHTED: the result is A^T diag(w) B.  `q` holds sqrt(w) for the slab's rows (indexed like them, zeros from row N on) and BOTH operands are
  * multiplied by it between stage_load and stage_store -- one f64x2 of q per step and thread, one product per staged pair; the slab stays as it is.  sqrt(w) on both sides
@@ -81,11 +141,7 @@ __global__ __launch_bounds__(256, 2) void k_reduced_gram(const double *__restric
     __shared__ __attribute__((aligned(16))) double As[RG_TW * RG_LS];
     __shared__ __attribute__((aligned(16))) double Bs_own[RG_TW * RG_LS];
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int wr = wave >> 1, wc = wave & 1;
-    const int r = lane & 15, qd = lane >> 4;
-
+    const TileLanes t;
     const int tile = blockIdx.x, chunk = blockIdx.y;
     int bj = 0;
     while ((bj + 1) * (bj + 2) / 2 <= tile) ++bj;
@@ -97,23 +153,21 @@ __global__ __launch_bounds__(256, 2) void k_reduced_gram(const double *__restric
     const int row_end = min(row_begin + RG_RANGE, rows);
     const int nsteps = (row_end - row_begin) / RG_KC;
 
-    // staging: thread -> (column srow [+ 32 p] of the tile, rows 2 sseg, 2 sseg + 1 of the step)
-    const int srow = tid >> 3, sseg = tid & 7;
     const double *Ag[4], *Bg[4];
     bool a_in[4], b_in[4];
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-        const int ca = bj * RG_TW + srow + 32 * p, cb = bk * RG_TW + srow + 32 * p;
+        const int ca = bj * RG_TW + t.srow + 32 * p, cb = bk * RG_TW + t.srow + 32 * p;
         a_in[p] = ca < cols;
         b_in[p] = !diag && cb < cols;
-        Ag[p] = slab + static_cast<size_t>(a_in[p] ? ca : 0) * ld + row_begin + 2 * sseg;
-        Bg[p] = slab + static_cast<size_t>(b_in[p] ? cb : 0) * ld + row_begin + 2 * sseg;
+        Ag[p] = slab + static_cast<size_t>(a_in[p] ? ca : 0) * ld + row_begin + 2 * t.sseg;
+        Bg[p] = slab + static_cast<size_t>(b_in[p] ? cb : 0) * ld + row_begin + 2 * t.sseg;
     }
-    const int lds_w = srow * RG_LS + 2 * sseg;
+    const int lds_w = t.srow * RG_LS + 2 * t.sseg;
     f64x2 sa[4], sb[4];
     f64x2 sq = { 0.0, 0.0 };  // WEIGHTED: sqrt(w) of the step's rows 2 sseg, 2 sseg + 1
     const f64x2 zero2 = { 0.0, 0.0 };
-    const double *qg = WEIGHTED ? q + row_begin + 2 * sseg : nullptr;
+    const double *qg = WEIGHTED ? q + row_begin + 2 * t.sseg : nullptr;
     auto stage_load = [&](int s) {
         if constexpr (WEIGHTED) sq = *reinterpret_cast<const f64x2 *>(qg + s * RG_KC);
 #pragma unroll
@@ -123,7 +177,7 @@ __global__ __launch_bounds__(256, 2) void k_reduced_gram(const double *__restric
         }
     };
     auto stage_store = [&]() {
-        if constexpr (WEIGHTED) {  // (here and not behind the loads: the step's MFMAs stand between a load and its first use)
+        if constexpr (WEIGHTED) {
 #pragma unroll
             for (int p = 0; p < 4; ++p) {
                 sa[p] *= sq;
@@ -138,52 +192,17 @@ __global__ __launch_bounds__(256, 2) void k_reduced_gram(const double *__restric
     };
 
     f64x4 acc[4][4];
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) {
-            acc[mt][nt] = f64x4{ 0.0, 0.0, 0.0, 0.0 };
-            // the start values live in the accumulators' OWN registers (C == D for every MFMA of a chain): lssvm_tile_f64_wide.hip.hpp has the hazard this keeps away
-            asm volatile("" : "+v"(acc[mt][nt]));
-        }
+    tile_zero(acc);
+    tile_contract<16 * RG_LS, 4>(nsteps, As + (t.wr * 64 + t.r) * RG_LS + t.qd, Bs + (t.wc * 64 + t.r) * RG_LS + t.qd, acc, stage_load, stage_store);
 
-    if (nsteps > 0) {
-        stage_load(0);
-        stage_store();
-    }
-    __syncthreads();
-    const double *Ab = As + (wr * 64 + r) * RG_LS + qd;
-    const double *Bb = Bs + (wc * 64 + r) * RG_LS + qd;
-    for (int s = 0; s < nsteps; ++s) {
-        const bool has_next = s + 1 < nsteps;
-        if (has_next) stage_load(s + 1);
-#pragma unroll
-        for (int ks = 0; ks < RG_KC / 4; ++ks) {
-            double av[4], bv[4];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                av[t] = Ab[t * 16 * RG_LS + ks * 4];
-                bv[t] = Bb[t * 16 * RG_LS + ks * 4];
-            }
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[mt], bv[nt], acc[mt][nt], 0, 0, 0);
-        }
-        __syncthreads();  // (every wave has read this step)
-        if (has_next) {
-            stage_store();
-            __syncthreads();
-        }
-    }
-
+    // the result of a lane: column r of B, rows qd + 4 i of A
     double *out = part + (static_cast<size_t>(tile) * max_chunks + chunk) * RG_TILE;
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) out[(wr * 64 + mt * 16 + qd + 4 * i) * RG_TW + wc * 64 + nt * 16 + r] = acc[mt][nt][i];
+            for (int i = 0; i < 4; ++i) out[(t.wr * 64 + mt * 16 + t.qd + 4 * i) * RG_TW + t.wc * 64 + nt * 16 + t.r] = acc[mt][nt][i];
 }
 
 /* St[tile] += part[tile][0] + part[tile][1] + ... : the chunks in ascending row order behind what the earlier slabs left, one thread per entry */
@@ -251,6 +270,17 @@ void enqueue_slab(const LandmarkBlock<T> &block, int m, const SlabPlan &plan, in
     block.enqueue(plan.row0(s), plan.rows256(s), slab, plan.ld);
     if (rhs.Y.p != nullptr)
         hipLaunchKernelGGL(k_reduced_aux<T>, dim3(plan.rows256(s) / 256, 1 + rhs.k), dim3(256), 0, st, rhs.Y.p, plan.N, plan.row0(s), slab + static_cast<size_t>(m) * plan.ld, plan.ld);
+}
+
+/* enqueue_slab between the two events; returns, when the slab is written, the milliseconds it took */
+template <typename T>
+double timed_slab(const LandmarkBlock<T> &block, int m, const SlabPlan &plan, int s, const RhsOnDevice<T> &rhs, double *slab, Event (&ev)[2], hipStream_t st) {
+    LSSVM_HIP_CHECK(hipEventRecord(ev[0].e, st));
+    enqueue_slab(block, m, plan, s, rhs, slab, st);
+    LSSVM_HIP_CHECK(hipGetLastError());
+    LSSVM_HIP_CHECK(hipEventRecord(ev[1].e, st));
+    LSSVM_HIP_CHECK(hipEventSynchronize(ev[1].e));
+    return elapsed_ms(ev[0], ev[1]);
 }
 
 /* the timing aids: one untimed run of `launch`, then `repeats` runs between two events; `before` is enqueued ahead of each, outside the timed span */
@@ -428,14 +458,72 @@ namespace {
 /* ---- the leave-one-out pass ---- */
 constexpr int LV_LSA = RG_TW + 16;  // doubles between two columns of Phi in LDS: the four k-rows of an MFMA's A fragments start 32 banks apart
 
-/* One workgroup: 128 rows of the column-major `slab` (as k_reduced_gram takes it: ld doubles between columns, rows padded to 256 with zeros) times ALL columns of the operand
- * Bt -- row n of Bt (ldb doubles apart, ldb >= m rounded up to 16) is column n of the m x (m + k) matrix B of the header: row n of V = L^-1 for n < m, beta_{n-m} from m on.
- * T = (Phi - 1 shift^T) B is accumulated in 128 x 128 tiles (four waves of 64 x 64, sixteen accumulators of v_mfma_f64_16x16x4_f64 each, as k_reduced_gram) over the
- * column blocks of B in ascending order and never stored: the squares of the columns below m are added to the row's running sum, the columns from m on are the fitted
- * values.  Phi goes through LDS with `shift` SUBTRACTED ON THE WAY (centring after the product would cancel for nearly constant kernels), a step is 16 columns of Phi;
- * Bt through LDS as k_reduced_gram's operands.  A column block wholly inside V^T contracts over j < 128 (bk + 1) only (V is lower triangular: the blocks above the diagonal
- * are never read), any other over j < m rounded up to 16; an entry V[n][j] with j > n is replaced by 0 as it is staged, whatever the buffer holds.  Columns of Phi from m
- * on and rows of Bt from m + k on count as zeros and are never read.
+/* What k_reduced_leverage and k_reduced_leverage_prefix share: the tile loop for T = (Phi - 1 shift^T) B^T, column block bk of it per call.  The workgroup's 128 rows of the
+ * column-major `slab` (ld doubles between columns, rows padded to 256 with zeros) are the A operand: Phi goes through LDS column by column (LV_LSA doubles apart, a step is
+ * 16 columns) with `shift` SUBTRACTED ON THE WAY (centring after the product would cancel for nearly constant kernels); thread -> (column akk of the step, rows 2 aseg + 32 p,
+ * 2 aseg + 32 p + 1).  Row n of the operand Bt (ldb doubles apart, ldb >= m rounded up to 16; `nrows` rows) is column n of B: row n of the lower triangular V = L^-1 for
+ * n < m, a dense row from m on.  A column block wholly inside V contracts over j < 128 (bk + 1) only (the blocks above the diagonal are never read), any other over j < m
+ * rounded up to 16; an entry V[n][j] with j > n is replaced by 0 as it is staged, whatever the buffer holds.  Columns of Phi from m on and rows of Bt from nrows on count
+ * as zeros and are never read.  DENSE_ROWS false: the operand is V alone (nrows = m), every row ends at its diagonal. */
+template <bool DENSE_ROWS>
+struct LeverageTile {
+    const TileLanes &t;
+    const double *const Bt, *const shift;
+    double *const As, *const Bs;
+    const size_t ld;
+    const int m, nrows, ldb, m16, akk, a_lds, b_lds;
+    const double *const Ag;
+    f64x2 sa[4], sb[4];
+
+    __device__ __forceinline__ LeverageTile(const TileLanes &lanes, const double *slab, size_t ld_, int row0, int m_, int nrows_, const double *Bt_, int ldb_, const double *shift_,
+                                            double *As_, double *Bs_) :
+        t(lanes), Bt(Bt_), shift(shift_), As(As_), Bs(Bs_), ld(ld_), m(m_), nrows(nrows_), ldb(ldb_), m16((m_ + RG_KC - 1) / RG_KC * RG_KC), akk(lanes.tid >> 4),
+        a_lds(akk * LV_LSA + 2 * (lanes.tid & 15)), b_lds(lanes.srow * RG_LS + 2 * lanes.sseg), Ag(slab + static_cast<size_t>(akk) * ld_ + row0 + 2 * (lanes.tid & 15)) {}
+
+    __device__ __forceinline__ void load(int bk, int s) {
+        const f64x2 zero2 = { 0.0, 0.0 };
+        const int j = s * RG_KC + akk;
+        const bool a_in = j < m;
+        const double sh = a_in ? shift[j] : 0.0;
+        const double *a = Ag + static_cast<size_t>(s) * RG_KC * ld;
+        const int jb = s * RG_KC + 2 * t.sseg;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            f64x2 v = a_in ? *reinterpret_cast<const f64x2 *>(a + 32 * p) : zero2;
+            if (a_in) {
+                v[0] -= sh;
+                v[1] -= sh;
+            }
+            sa[p] = v;
+            const int n = bk * RG_TW + t.srow + 32 * p;
+            const int last = !DENSE_ROWS || n < m ? n : m16;  // the last column of Bt's row that counts: the diagonal for a row of V, all of them for a dense row
+            f64x2 w = n < nrows ? *reinterpret_cast<const f64x2 *>(Bt + static_cast<size_t>(n) * ldb + jb) : zero2;
+            if (jb > last) w[0] = 0.0;
+            if (jb + 1 > last) w[1] = 0.0;
+            sb[p] = w;
+        }
+    }
+    __device__ __forceinline__ void store() {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            *reinterpret_cast<f64x2 *>(As + a_lds + 32 * p) = sa[p];
+            *reinterpret_cast<f64x2 *>(Bs + b_lds + p * 32 * RG_LS) = sb[p];
+        }
+    }
+    /* acc = column block bk of T: a lane holds rows qd + 4 i of its four row tiles and column r of its four column tiles.  (The barrier that ended the block before lets
+     * every wave write LDS: all of them have read its last step.) */
+    __device__ __forceinline__ void contract(int bk, f64x4 (&acc)[4][4]) {
+        tile_zero(acc);
+        const int nsteps = ((bk + 1) * RG_TW <= m ? (bk + 1) * RG_TW : m16) / RG_KC;
+        __builtin_assume(nsteps > 0);  // (m >= 1)
+        tile_contract<16, 4 * LV_LSA>(nsteps, As + t.qd * LV_LSA + t.wr * 64 + t.r, Bs + (t.wc * 64 + t.r) * RG_LS + t.qd, acc,
+                                      [&](int s) { load(bk, s); }, [&]() { store(); });
+    }
+};
+
+/* One workgroup: 128 rows of the slab times ALL columns of the operand Bt (LeverageTile: m rows of V, then the k betas) -- the m x (m + k) matrix B of the header.  T is
+ * accumulated over the column blocks of B in ascending order and never stored: the squares of the columns below m are added to the row's running sum, the columns from m
+ * on are the fitted values.
  * A row's sum of squares: per column block a lane's four column tiles in ascending order, then the sixteen lanes that share the row (xor 1, 2, 4, 8), the blocks one
  * behind the other in LDS (the sums are not held in registers across a block), at the end the two column waves -- an order that depends on m only. A row's values depend on that row, Bt, shift and ybar only.  No atomics, no scratch.
  * h_out[i] = inv_n + sum; f_out[c ldo + i] = T[i][m + c] + ybar[c] (ybar NULL: 0); loo_out[c ldo + i] = y - (y - f) / (1 - h) with y = ycols[c ld + i] (loo_out NULL:
@@ -449,105 +537,24 @@ __global__ __launch_bounds__(256, 2) void k_reduced_leverage(const double *__res
     __shared__ __attribute__((aligned(16))) double Bs[RG_TW * RG_LS];
     __shared__ double hs[3 * RG_TW];  // the rows' sums of squares of the two column waves, then h
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int wr = wave >> 1, wc = wave & 1;
-    const int r = lane & 15, qd = lane >> 4;
+    const TileLanes t;
+    const int tid = t.tid;
     const int row0 = blockIdx.x * RG_TW;
     const int nblocks = (m + k + RG_TW - 1) / RG_TW;
-    const int m16 = (m + RG_KC - 1) / RG_KC * RG_KC;
-
-    // staging of Phi: thread -> (column akk of the step, rows 2 aseg + 32 p, 2 aseg + 32 p + 1 of the workgroup's 128)
-    const int akk = tid >> 4, aseg = tid & 15;
-    const double *Ag = slab + static_cast<size_t>(akk) * ld + row0 + 2 * aseg;
-    const int a_lds = akk * LV_LSA + 2 * aseg;
-    // staging of Bt: thread -> (row srow + 32 p of the column block, columns 2 sseg, 2 sseg + 1 of the step), as k_reduced_gram
-    const int srow = tid >> 3, sseg = tid & 7;
-    const int b_lds = srow * RG_LS + 2 * sseg;
-    const f64x2 zero2 = { 0.0, 0.0 };
-    f64x2 sa[4], sb[4];
+    LeverageTile<true> tile(t, slab, ld, row0, m, m + k, Bt, ldb, shift, As, Bs);
 
     // lane 16 qd of a wave owns the sums of the wave's rows qd + 4 i + 16 mt: nobody else touches them before the barrier behind the last block
-    double *hrow = hs + wc * RG_TW + wr * 64 + qd;
-    if (r == 0) {
+    double *hrow = hs + t.wc * RG_TW + t.wr * 64 + t.qd;
+    if (t.r == 0) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) hrow[4 * e] = 0.0;
     }
 
-    const double *Ab = As + qd * LV_LSA + wr * 64 + r;
-    const double *Bb = Bs + (wc * 64 + r) * RG_LS + qd;
-
     for (int bk = 0; bk < nblocks; ++bk) {
-        const int nsteps = ((bk + 1) * RG_TW <= m ? (bk + 1) * RG_TW : m16) / RG_KC;
-        const int n0 = bk * RG_TW + srow;  // this thread's rows of Bt: n0 + 32 p
-        auto stage_load = [&](int s) {
-            const int j = s * RG_KC + akk;
-            const bool a_in = j < m;
-            const double sh = a_in ? shift[j] : 0.0;
-            const double *a = Ag + static_cast<size_t>(s) * RG_KC * ld;
-            const int jb = s * RG_KC + 2 * sseg;
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                f64x2 v = a_in ? *reinterpret_cast<const f64x2 *>(a + 32 * p) : zero2;
-                if (a_in) {
-                    v[0] -= sh;
-                    v[1] -= sh;
-                }
-                sa[p] = v;
-                const int n = n0 + 32 * p;
-                const int last = n < m ? n : m16;  // the last column of Bt's row that counts: the diagonal for a row of V, all of them for a beta
-                f64x2 w = n < m + k ? *reinterpret_cast<const f64x2 *>(Bt + static_cast<size_t>(n) * ldb + jb) : zero2;
-                if (jb > last) w[0] = 0.0;
-                if (jb + 1 > last) w[1] = 0.0;
-                sb[p] = w;
-            }
-        };
-        auto stage_store = [&]() {
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                *reinterpret_cast<f64x2 *>(As + a_lds + 32 * p) = sa[p];
-                *reinterpret_cast<f64x2 *>(Bs + b_lds + p * 32 * RG_LS) = sb[p];
-            }
-        };
-
         f64x4 acc[4][4];
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) {
-                acc[mt][nt] = f64x4{ 0.0, 0.0, 0.0, 0.0 };
-                // the start values live in the accumulators' OWN registers (C == D for every MFMA of a chain), as in k_reduced_gram
-                asm volatile("" : "+v"(acc[mt][nt]));
-            }
+        tile.contract(bk, acc);
 
-        stage_load(0);  // (the barrier that ended the block before lets every wave write: all of them have read its last step)
-        stage_store();
-        __syncthreads();
-        for (int s = 0; s < nsteps; ++s) {
-            const bool has_next = s + 1 < nsteps;
-            if (has_next) stage_load(s + 1);
-#pragma unroll
-            for (int ks = 0; ks < RG_KC / 4; ++ks) {
-                double av[4], bv[4];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    av[t] = Ab[ks * 4 * LV_LSA + t * 16];
-                    bv[t] = Bb[t * 16 * RG_LS + ks * 4];
-                }
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                    for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[mt], bv[nt], acc[mt][nt], 0, 0, 0);
-            }
-            __syncthreads();  // (every wave has read this step)
-            if (has_next) {
-                stage_store();
-                __syncthreads();
-            }
-        }
-
-        // a lane holds rows qd + 4 i of its four row tiles and column r of its four column tiles
-        const int nw = bk * RG_TW + wc * 64 + r;  // its columns: nw + 16 nt
+        const int nw = bk * RG_TW + t.wc * 64 + t.r;  // the lane's columns: nw + 16 nt
         if (bk * RG_TW < m) {
             // the squares of the columns of V^T: the lane's four columns in ascending order, the sixteen lanes of a row (xor 1, 2, 4, 8), then behind the blocks before
 #pragma unroll
@@ -561,7 +568,7 @@ __global__ __launch_bounds__(256, 2) void k_reduced_leverage(const double *__res
                     v += __shfl_xor(v, 2);
                     v += __shfl_xor(v, 4);
                     v += __shfl_xor(v, 8);
-                    if (r == 0) hrow[4 * i + 16 * mt] += v;
+                    if (t.r == 0) hrow[4 * i + 16 * mt] += v;
                 }
         }
         if ((bk + 1) * RG_TW > m) {
@@ -574,7 +581,7 @@ __global__ __launch_bounds__(256, 2) void k_reduced_leverage(const double *__res
                     for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
                         for (int i = 0; i < 4; ++i) {
-                            const int row = row0 + wr * 64 + mt * 16 + qd + 4 * i;
+                            const int row = row0 + t.wr * 64 + mt * 16 + t.qd + 4 * i;
                             if (row < rows) f_out[static_cast<size_t>(c) * ldo + row] = acc[mt][nt][i] + yb;
                         }
                 }
@@ -605,10 +612,9 @@ __global__ __launch_bounds__(256, 2) void k_reduced_leverage(const double *__res
 constexpr int PFX_KMAX = 4;        // right-hand sides per launch: 1 + PFX_KMAX running sums per row and column wave in LDS (the host launches once per group of four)
 constexpr int PFX_SUMS = (1 + PFX_KMAX) * 2 * RG_TW;  // doubles: [sum][column wave][row of the workgroup]
 
-/* The sibling of k_reduced_leverage for the rank path: the same slab layout, LDS staging (centring subtracted on the way in), masked staging of the triangular operand
- * and 128 x 128 tiles of v_mfma_f64_16x16x4_f64, four waves of 64 x 64.  The operand is V ALONE: row n of Vt (ldb doubles apart) is row n of V = L^-1, n < m; rows from m
- * on count as zeros and are never read, an entry V[n][j] with j > n is replaced by 0 as it is staged.  Z: row c (ldb doubles apart) is z_c, k <= PFX_KMAX rows, read below m
- * only.  ranks: num_ranks ascending checkpoints 1 <= r_q <= m.  Only the column blocks up to the one of the last checkpoint are formed.
+/* k_reduced_leverage for the rank path.  The operand is V ALONE (LeverageTile with m rows): row n of Vt (ldb doubles apart) is row n of V = L^-1, n < m.  Z: row c (ldb
+ * doubles apart) is z_c, k <= PFX_KMAX rows, read below m only.  ranks: num_ranks ascending checkpoints 1 <= r_q <= m.  Only the column blocks up to the one of the last
+ * checkpoint are formed.
  * After each 128-column block the tile U = (Phi - 1 shift^T) V^T stands in the accumulators.  A lane forms, for each of its sixteen rows and a column limit `lim`, the
  * 1 + k sums of u^2 and u z_c over its four columns below lim in ascending order (one fma each), then the sixteen lanes of the row add up (xor 1, 2, 4, 8): row_sums.
  *   a checkpoint r_q inside the block (128 bk < r_q <= 128 (bk + 1)): row_sums with lim = r_q, BEHIND the running sums of the blocks before, per column wave; the two
@@ -626,25 +632,14 @@ __global__ __launch_bounds__(256, 2) void k_reduced_leverage_prefix(const double
     __shared__ double run[PFX_SUMS];  // the running sums of the blocks before
     __shared__ double cps[PFX_SUMS];  // a checkpoint's sums, where the two column waves meet
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int wr = wave >> 1, wc = wave & 1;
-    const int r = lane & 15, qd = lane >> 4;
+    const TileLanes t;
+    const int tid = t.tid, r = t.r;
     const int row0 = blockIdx.x * RG_TW;
     const int nblocks = (ranks[num_ranks - 1] + RG_TW - 1) / RG_TW;
-    const int m16 = (m + RG_KC - 1) / RG_KC * RG_KC;
-
-    // staging of Phi and of Vt: as k_reduced_leverage
-    const int akk = tid >> 4, aseg = tid & 15;
-    const double *Ag = slab + static_cast<size_t>(akk) * ld + row0 + 2 * aseg;
-    const int a_lds = akk * LV_LSA + 2 * aseg;
-    const int srow = tid >> 3, sseg = tid & 7;
-    const int b_lds = srow * RG_LS + 2 * sseg;
-    const f64x2 zero2 = { 0.0, 0.0 };
-    f64x2 sa[4], sb[4];
+    LeverageTile<false> tile(t, slab, ld, row0, m, m, Vt, ldb, shift, As, Bs);
 
     // lane 16 qd of a wave owns the sums of the wave's rows qd + 4 i + 16 mt in `run`: nobody else touches them
-    const int own = wc * RG_TW + wr * 64 + qd;  // + 4 i + 16 mt, + 2 RG_TW per sum
+    const int own = t.wc * RG_TW + t.wr * 64 + t.qd;  // + 4 i + 16 mt, + 2 RG_TW per sum
     if (r == 0) {
 #pragma unroll
         for (int s = 0; s <= PFX_KMAX; ++s)
@@ -652,79 +647,12 @@ __global__ __launch_bounds__(256, 2) void k_reduced_leverage_prefix(const double
             for (int e = 0; e < 16; ++e) run[s * 2 * RG_TW + own + 4 * e] = 0.0;
     }
 
-    const double *Ab = As + qd * LV_LSA + wr * 64 + r;
-    const double *Bb = Bs + (wc * 64 + r) * RG_LS + qd;
-
     for (int bk = 0; bk < nblocks; ++bk) {
-        const int nsteps = ((bk + 1) * RG_TW <= m ? (bk + 1) * RG_TW : m16) / RG_KC;
-        const int n0 = bk * RG_TW + srow;  // this thread's rows of Vt: n0 + 32 p
-        auto stage_load = [&](int s) {
-            const int j = s * RG_KC + akk;
-            const bool a_in = j < m;
-            const double sh = a_in ? shift[j] : 0.0;
-            const double *a = Ag + static_cast<size_t>(s) * RG_KC * ld;
-            const int jb = s * RG_KC + 2 * sseg;
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                f64x2 v = a_in ? *reinterpret_cast<const f64x2 *>(a + 32 * p) : zero2;
-                if (a_in) {
-                    v[0] -= sh;
-                    v[1] -= sh;
-                }
-                sa[p] = v;
-                const int n = n0 + 32 * p;  // the last column of the row that counts: the diagonal
-                f64x2 vv = n < m ? *reinterpret_cast<const f64x2 *>(Vt + static_cast<size_t>(n) * ldb + jb) : zero2;
-                if (jb > n) vv[0] = 0.0;
-                if (jb + 1 > n) vv[1] = 0.0;
-                sb[p] = vv;
-            }
-        };
-        auto stage_store = [&]() {
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                *reinterpret_cast<f64x2 *>(As + a_lds + 32 * p) = sa[p];
-                *reinterpret_cast<f64x2 *>(Bs + b_lds + p * 32 * RG_LS) = sb[p];
-            }
-        };
-
         f64x4 acc[4][4];
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) {
-                acc[mt][nt] = f64x4{ 0.0, 0.0, 0.0, 0.0 };
-                // the start values live in the accumulators' OWN registers (C == D for every MFMA of a chain), as in k_reduced_gram
-                asm volatile("" : "+v"(acc[mt][nt]));
-            }
+        tile.contract(bk, acc);
 
-        stage_load(0);  // (the barrier that ended the block before lets every wave write: all of them have read its last step)
-        stage_store();
-        __syncthreads();
-        for (int s = 0; s < nsteps; ++s) {
-            const bool has_next = s + 1 < nsteps;
-            if (has_next) stage_load(s + 1);
-#pragma unroll
-            for (int ks = 0; ks < RG_KC / 4; ++ks) {
-                double av[4], bv[4];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    av[t] = Ab[ks * 4 * LV_LSA + t * 16];
-                    bv[t] = Bb[t * 16 * RG_LS + ks * 4];
-                }
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                    for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[mt], bv[nt], acc[mt][nt], 0, 0, 0);
-            }
-            __syncthreads();  // (every wave has read this step)
-            if (has_next) {
-                stage_store();
-                __syncthreads();
-            }
-        }
-
-        // a lane holds rows qd + 4 i of its four row tiles and column r of its four column tiles: nw + 16 nt; z of these columns
-        const int nw = bk * RG_TW + wc * 64 + r;
+        // the lane's columns: nw + 16 nt; z of these columns
+        const int nw = bk * RG_TW + t.wc * 64 + r;
         double zr[PFX_KMAX][4];
 #pragma unroll
         for (int c = 0; c < PFX_KMAX; ++c)
@@ -821,71 +749,83 @@ struct PairOf<double> {
     using type = f64x2;
 };
 
-/* n[i] = the sum over the ldx held features (ascending) of x_if^2, in double: the squared norms k_landmark_product expands the rbf distance with */
-template <typename T>
-__global__ __launch_bounds__(256) void k_row_norms(const T *__restrict__ X, int ldx, size_t N, double *__restrict__ n) {
+/* n[i] = the sum over the ldx held features (ascending) of x_if^2 -- CENTRED: of (x_if - c_f)^2, `centre` holding ldx doubles, zeros from the last feature on, so a padded
+ * feature adds an exact 0 -- in double: the squared norms the product kernels expand the rbf distance with, of the rows AS THEY ARE STAGED there */
+template <bool CENTRED, typename T>
+__device__ __forceinline__ void row_norms(const T *__restrict__ X, int ldx, size_t N, const double *__restrict__ centre, double *__restrict__ n) {
     const size_t i = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
     if (i >= N) return;
     const T *xi = X + i * ldx;
     double acc = 0.0;
     for (int f = 0; f < ldx; ++f) {
-        const double a = static_cast<double>(xi[f]);
+        double a = static_cast<double>(xi[f]);
+        if constexpr (CENTRED) a -= centre[f];
         acc += a * a;
     }
     n[i] = acc;
 }
-
-/* D[l][i - row0] of k_landmark_acc with the dot products x_i . x_lm[l] on v_mfma_f64_16x16x4_f64: one workgroup owns 128 landmarks (blockIdx.y) x 128 rows of the slab
- * (blockIdx.x), the four waves hold 64 x 64 each as sixteen accumulators, exactly as k_reduced_gram.  The contraction runs over the ldx held features in steps of RG_KC = 16
- * (ldx is a multiple of 16); both operands go through LDS in k_reduced_gram's layout (RG_LS doubles between two points), converted to double as they are staged: eight
- * threads load the 16 features of a point as one 64-byte (fp32) or 128-byte (fp64) line.  The A operand are the landmarks' rows, gathered through lm[], the B operand the
- * slab's rows: a lane holds landmarks qd + 4 i of its four landmark tiles and row r of its four row tiles, so sixteen lanes write 128 contiguous bytes of a column of D.
- * Landmarks from m on and rows from N on count as zeros and are never read; landmarks from m on are not written, rows from N on are written as zeros.
- * rbf: D = n_i + n_l - 2 x_i . x_l with `norms` of k_row_norms, clamped at 0, and EXACTLY 0 where i == lm[l] (the expansion leaves a rounding there; K_mm's diagonal is
- * exactly 1, as on the ordered path).  Any other kernel type: the dot product.  No atomics, no scratch; the order of every sum depends on ldx only. */
 template <typename T>
-__global__ __launch_bounds__(256, 2) void k_landmark_product(const T *__restrict__ X, int ldx, int N, int row0, const int *__restrict__ lm, int m, int kernel_type,
-                                                             const double *__restrict__ norms, double *__restrict__ D, size_t ldN) {
+__global__ __launch_bounds__(256) void k_row_norms(const T *__restrict__ X, int ldx, size_t N, double *__restrict__ n) {
+    row_norms<false>(X, ldx, N, nullptr, n);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_centred_norms(const T *__restrict__ X, int ldx, size_t N, const double *__restrict__ centre, double *__restrict__ n) {
+    row_norms<true>(X, ldx, N, centre, n);
+}
+
+/* The body of k_landmark_product (STREAM false) and k_cross_product (true): D[l][local] of k_landmark_acc with the dot products on the tile loop above.  One workgroup owns
+ * 128 landmarks (blockIdx.y) x 128 rows (blockIdx.x).  The contraction runs over the ldx held features (a multiple of 16); both operands are converted to double as they
+ * are staged: eight threads load the 16 features of a point as one 64-byte (fp32) or 128-byte (fp64) line.  The A operand are the landmarks, the B operand the rows: a
+ * lane holds landmarks qd + 4 i of its four landmark tiles and row r of its four row tiles, so sixteen lanes write 128 contiguous bytes of a column of D.
+ *   resident: landmark l is row lm[l] of X = XA = XB, row `local` of the slab is row row0 + local; norms_a = norms_b: k_row_norms of X.  centre and diag are not read.
+ *   stream:   landmark l is row l of XA, the rows are those of XB (row0 = 0, lm not read); `centre` is SUBTRACTED from both operands as they are staged -- one f64x2 of it
+ *             per step and thread, every operand is (double) x_f - c_f; norms_a / norms_b: k_centred_norms of either.
+ * Landmarks from m on and rows from N on count as zeros and are never read; landmarks from m on are not written, rows from N on up to the end of the workgroup's 128 are
+ * written as zeros.  rbf: D = n_i + n_l - 2 x_i . x_l, clamped at 0, and EXACTLY 0 at the landmark itself (the expansion leaves a rounding there; K_mm's diagonal is
+ * exactly 1, as on the ordered path): where lm[l] is the row, or -- a streamed row carries no index -- where `diag` says that XB is XA and l == local.  Any other kernel
+ * type: the dot product.  No atomics, no scratch; the order of every sum depends on ldx only. */
+template <bool STREAM, typename T>
+__device__ __forceinline__ void landmark_product(const T *__restrict__ XA, const T *__restrict__ XB, int ldx, int N, int row0, const int *__restrict__ lm, int m,
+                                                 const double *__restrict__ centre, int kernel_type, const double *__restrict__ norms_a, const double *__restrict__ norms_b,
+                                                 int diag, double *__restrict__ D, size_t ld, double *As, double *Bs) {
     using pair = typename PairOf<T>::type;
-    __shared__ __attribute__((aligned(16))) double As[RG_TW * RG_LS];
-    __shared__ __attribute__((aligned(16))) double Bs[RG_TW * RG_LS];
+    const TileLanes t;
+    const int l0 = blockIdx.y * RG_TW;      // the workgroup's first landmark
+    const int local0 = blockIdx.x * RG_TW;  // ... and first row of the slab
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int wr = wave >> 1, wc = wave & 1;
-    const int r = lane & 15, qd = lane >> 4;
-    const int l0 = blockIdx.y * RG_TW;             // the workgroup's first landmark
-    const int local0 = blockIdx.x * RG_TW;         // ... and first row of the slab
-    const int nsteps = ldx / RG_KC;
-
-    // staging: thread -> (point srow [+ 32 p] of the tile, features 2 sseg, 2 sseg + 1 of the step), as k_reduced_gram
-    const int srow = tid >> 3, sseg = tid & 7;
     const T *Ag[4], *Bg[4];
     bool a_in[4], b_in[4];
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-        const int la = l0 + srow + 32 * p, ib = row0 + local0 + srow + 32 * p;
+        const int la = l0 + t.srow + 32 * p, ib = row0 + local0 + t.srow + 32 * p;
         a_in[p] = la < m;
         b_in[p] = ib < N;
-        Ag[p] = X + static_cast<size_t>(a_in[p] ? lm[la] : 0) * ldx + 2 * sseg;
-        Bg[p] = X + static_cast<size_t>(b_in[p] ? ib : 0) * ldx + 2 * sseg;
+        size_t at = 0;
+        if (a_in[p]) at = STREAM ? la : lm[la];
+        Ag[p] = XA + at * ldx + 2 * t.sseg;
+        Bg[p] = XB + static_cast<size_t>(b_in[p] ? ib : 0) * ldx + 2 * t.sseg;
     }
-    const int lds_w = srow * RG_LS + 2 * sseg;
+    const double *cg = STREAM ? centre + 2 * t.sseg : nullptr;
+    const int lds_w = t.srow * RG_LS + 2 * t.sseg;
     f64x2 sa[4], sb[4];
     const f64x2 zero2 = { 0.0, 0.0 };
     auto stage_load = [&](int s) {
+        f64x2 c2 = zero2;
+        if constexpr (STREAM) c2 = *reinterpret_cast<const f64x2 *>(cg + s * RG_KC);
+        auto staged = [&](const T *g) {
+            const pair v = *reinterpret_cast<const pair *>(g + s * RG_KC);
+            if constexpr (STREAM) {
+                return f64x2{ static_cast<double>(v[0]) - c2[0], static_cast<double>(v[1]) - c2[1] };
+            } else {
+                return f64x2{ static_cast<double>(v[0]), static_cast<double>(v[1]) };
+            }
+        };
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
             sa[p] = zero2;
             sb[p] = zero2;
-            if (a_in[p]) {
-                const pair v = *reinterpret_cast<const pair *>(Ag[p] + s * RG_KC);
-                sa[p] = f64x2{ static_cast<double>(v[0]), static_cast<double>(v[1]) };
-            }
-            if (b_in[p]) {
-                const pair v = *reinterpret_cast<const pair *>(Bg[p] + s * RG_KC);
-                sb[p] = f64x2{ static_cast<double>(v[0]), static_cast<double>(v[1]) };
-            }
+            if (a_in[p]) sa[p] = staged(Ag[p]);
+            if (b_in[p]) sb[p] = staged(Bg[p]);
         }
     };
     auto stage_store = [&]() {
@@ -897,68 +837,52 @@ __global__ __launch_bounds__(256, 2) void k_landmark_product(const T *__restrict
     };
 
     f64x4 acc[4][4];
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) {
-            acc[mt][nt] = f64x4{ 0.0, 0.0, 0.0, 0.0 };
-            // the start values live in the accumulators' OWN registers (C == D for every MFMA of a chain), as in k_reduced_gram
-            asm volatile("" : "+v"(acc[mt][nt]));
-        }
-
-    if (nsteps > 0) {
-        stage_load(0);
-        stage_store();
-    }
-    __syncthreads();
-    const double *Ab = As + (wr * 64 + r) * RG_LS + qd;
-    const double *Bb = Bs + (wc * 64 + r) * RG_LS + qd;
-    for (int s = 0; s < nsteps; ++s) {
-        const bool has_next = s + 1 < nsteps;
-        if (has_next) stage_load(s + 1);
-#pragma unroll
-        for (int ks = 0; ks < RG_KC / 4; ++ks) {
-            double av[4], bv[4];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                av[t] = Ab[t * 16 * RG_LS + ks * 4];
-                bv[t] = Bb[t * 16 * RG_LS + ks * 4];
-            }
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[mt], bv[nt], acc[mt][nt], 0, 0, 0);
-        }
-        __syncthreads();  // (every wave has read this step)
-        if (has_next) {
-            stage_store();
-            __syncthreads();
-        }
-    }
+    tile_zero(acc);
+    tile_contract<16 * RG_LS, 4>(ldx / RG_KC, As + (t.wr * 64 + t.r) * RG_LS + t.qd, Bs + (t.wc * 64 + t.r) * RG_LS + t.qd, acc, stage_load, stage_store);
 
     // a lane holds landmarks l0 + wr 64 + mt 16 + qd + 4 i and rows local0 + wc 64 + nt 16 + r
     const bool rbf = kernel_type == LSSVM_KERNEL_RBF;
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt) {
-        const int local = local0 + wc * 64 + nt * 16 + r;
+        const int local = local0 + t.wc * 64 + nt * 16 + t.r;
         const int row = row0 + local;
         const bool row_in = row < N;
-        const double ni = rbf && row_in ? norms[row] : 0.0;
+        const double ni = rbf && row_in ? norms_b[row] : 0.0;
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const int l = l0 + wr * 64 + mt * 16 + qd + 4 * i;
+                const int l = l0 + t.wr * 64 + mt * 16 + t.qd + 4 * i;
                 if (l >= m) continue;
                 double d = acc[mt][nt][i];
                 if (rbf) {
-                    const int at = lm[l];
-                    d = fmax((ni + norms[at]) - 2.0 * d, 0.0);
-                    if (at == row) d = 0.0;
+                    const int at = STREAM ? l : lm[l];
+                    d = fmax((ni + norms_a[at]) - 2.0 * d, 0.0);
+                    if (STREAM ? diag != 0 && l == local : at == row) d = 0.0;
                 }
-                D[static_cast<size_t>(l) * ldN + local] = row_in ? d : 0.0;
+                D[static_cast<size_t>(l) * ld + local] = row_in ? d : 0.0;
             }
     }
+}
+
+/* the rows of a resident problem against its landmarks lm[] */
+template <typename T>
+__global__ __launch_bounds__(256, 2) void k_landmark_product(const T *__restrict__ X, int ldx, int N, int row0, const int *__restrict__ lm, int m, int kernel_type,
+                                                             const double *__restrict__ norms, double *__restrict__ D, size_t ldN) {
+    __shared__ __attribute__((aligned(16))) double As[RG_TW * RG_LS];
+    __shared__ __attribute__((aligned(16))) double Bs[RG_TW * RG_LS];
+    landmark_product<false>(X, X, ldx, N, row0, lm, m, nullptr, kernel_type, norms, norms, 0, D, ldN, As, Bs);
+}
+
+/* rows that are in no problem: the n rows of `Xc` (a chunk, held padded to ldx features) against the m landmark ROWS `XL`, held on their own.  D may
+ * start at any row of a slab (the host adds the fill position to the pointer), so its stores are 8-byte aligned only; a slab keeps the slack of a workgroup's 128 rows
+ * behind its last row.  `centre`: zeros for a kernel that is not translation invariant.  `diag`: the K_mm launch, Xc == XL. */
+template <typename T>
+__global__ __launch_bounds__(256, 2) void k_cross_product(const T *__restrict__ XL, const T *__restrict__ Xc, int ldx, int n, int m, const double *__restrict__ centre, int kernel_type,
+                                                          const double *__restrict__ norms_l, const double *__restrict__ norms_c, int diag, double *__restrict__ D, size_t ld) {
+    __shared__ __attribute__((aligned(16))) double As[RG_TW * RG_LS];
+    __shared__ __attribute__((aligned(16))) double Bs[RG_TW * RG_LS];
+    landmark_product<true>(XL, Xc, ldx, n, 0, nullptr, m, centre, kernel_type, norms_l, norms_c, diag, D, ld, As, Bs);
 }
 
 /* Phi[l][i] = k from D[l][i] (landmark_kernel_value: the epilogue of k_landmark_block) for the rows row0 + i < N of a slab, EXACT zeros from N on (exp(0) is 1, not 0);
@@ -972,31 +896,28 @@ __global__ __launch_bounds__(256) void k_kernel_values(const double *__restrict_
 
 }  // namespace
 
-/* what a leave-one-out pass works on: `num_ops` operands on the device (Bt of k_reduced_leverage, op_stride doubles apart; ybar: num_ops x k or none), and where its results go */
-struct LeverageArgs {
+/* what a leave-one-out pass works on: `num_ops` operands on the device (m + k rows of ldb doubles each, op_stride doubles apart; ybar: num_ops x k or none), and where
+ * its results go -- `outs` of them per operand (1, or one per checkpoint of a rank path), the operand's dimension first */
+struct LooArgs {
     const int m, k, ldb;
-    const size_t num_ops, op_stride;
-    DevBuf<double> Bt, shift, ybar;
+    const size_t num_ops, op_stride, outs;
+    DevBuf<double> ops, shift, ybar;
     double inv_n = 0.0;
-    const void *Y = nullptr;                                             // the host's right-hand sides (k x N, the problem's type), or NULL: no leave-one-out values
-    const double *w = nullptr;                                           // the host's N weights (inv_n is then 1 / their sum), or NULL: the unweighted model
-    double *h_out = nullptr, *f_out = nullptr, *loo_out = nullptr;       // num_ops x N, num_ops x k x N, num_ops x k x N; each may be NULL
-    double *press = nullptr;                                             // num_ops x k, or NULL
-    uint64_t *errors = nullptr;                                          // num_ops x k, or NULL
-    std::vector<double> max_leverage, leverage_ms;                       // per operand
+    const void *Y = nullptr;                                        // the host's right-hand sides (k x N, the problem's type), or NULL: no leave-one-out values
+    const double *w = nullptr;                                      // the host's N weights (inv_n is then 1 / their sum), or NULL: the unweighted model
+    double *h_out = nullptr, *f_out = nullptr, *loo_out = nullptr;  // num_ops x outs x N, num_ops x outs x k x N, num_ops x outs x k x N; each may be NULL
+    double *press = nullptr;                                        // num_ops x outs x k, or NULL
+    uint64_t *errors = nullptr;                                     // num_ops x outs x k, or NULL
+    std::vector<double> max_leverage, leverage_ms;                  // num_ops x outs; per operand
     double landmark_ms = 0.0;
+    hipStream_t st;
 
-    /* the operands as zeros on the device; `shifts`: how many shift vectors of m doubles the pass takes (one per gamma of a grid: the operands are shared out evenly
-     * among them, in order) */
-    LeverageArgs(int rank, int num_cols, size_t operands, bool with_ybar, hipStream_t stream, size_t shifts = 1) :
-        m(rank), k(num_cols), ldb(round_up(rank, RG_KC)), num_ops(operands), op_stride(static_cast<size_t>(rank + num_cols) * ldb), st(stream) {
-        Bt.alloc_zero(num_ops * op_stride, st);
+    /* the operands as zeros on the device; `shifts`: how many shift vectors of m doubles the pass takes */
+    LooArgs(int rank, int num_cols, size_t operands, size_t outs_per_op, bool with_ybar, hipStream_t stream, size_t shifts) :
+        m(rank), k(num_cols), ldb(round_up(rank, RG_KC)), num_ops(operands), op_stride(static_cast<size_t>(rank + num_cols) * ldb), outs(outs_per_op), st(stream) {
+        ops.alloc_zero(num_ops * op_stride, st);
         shift.alloc_zero(shifts * static_cast<size_t>(m), st);
-        if (with_ybar) ybar.alloc_zero(num_ops * k, st);
-    }
-    /* operand o <- the host's m + k rows of ldb doubles; asynchronous: the rows stay as they are until the stream has been synchronised */
-    void upload_operand(size_t o, const double *Bt_host) {
-        LSSVM_HIP_CHECK(hipMemcpyAsync(Bt.p + o * op_stride, Bt_host, op_stride * sizeof(double), hipMemcpyHostToDevice, st));
+        if (with_ybar) ybar.alloc_zero(num_ops * k, st);  // (a pass with ybar has right-hand sides)
     }
     /* shift (m per shift vector) and, where the pass takes one, ybar (num_ops x k); returns when these and the operands are on the device */
     void upload_shift(const double *shift_host, const double *ybar_host) {
@@ -1004,40 +925,67 @@ struct LeverageArgs {
         if (ybar_host != nullptr) LSSVM_HIP_CHECK(hipMemcpyAsync(ybar.p, ybar_host, ybar.count * sizeof(double), hipMemcpyHostToDevice, st));
         LSSVM_HIP_CHECK(hipStreamSynchronize(st));
     }
+    /* what a pass sums over the points, at its start */
+    void reset_sums() {
+        max_leverage.assign(num_ops * outs, 0.0);
+        leverage_ms.assign(num_ops, 0.0);
+        landmark_ms = 0.0;
+        if (press != nullptr) std::fill(press, press + num_ops * outs * k, 0.0);
+        if (errors != nullptr) std::fill(errors, errors + num_ops * outs * k, uint64_t{ 0 });
+    }
+    /* `rows` leverages of output oq from row0 on: the largest so far, and the caller's copy */
+    void take_leverage(size_t oq, const double *h, size_t N, size_t row0, int rows) {
+        for (int i = 0; i < rows; ++i) max_leverage[oq] = std::max(max_leverage[oq], h[i]);
+        if (h_out != nullptr) std::copy(h, h + rows, h_out + oq * N + row0);
+    }
+    /* `rows` leave-one-out values of cell oc = (output, right-hand side) from row0 on, `y` being that right-hand side (N of the problem's type): the caller's copy, and
+     * PRESS and the sign errors of the cell BEHIND what the slabs before left, in row order */
+    template <typename T>
+    void score(size_t oc, const T *y, const double *loo, size_t N, size_t row0, int rows) {
+        if (loo_out != nullptr) std::copy(loo, loo + rows, loo_out + oc * N + row0);
+        double sum = press != nullptr ? press[oc] : 0.0;
+        uint64_t wrong_signs = 0;
+        for (int i = 0; i < rows; ++i) {
+            const double yi = static_cast<double>(y[row0 + i]), d = yi - loo[i];
+            const bool wrong = ((loo[i] > 0.0) - (loo[i] < 0.0)) != ((yi > 0.0) - (yi < 0.0));
+            if (w != nullptr) {  // sum_i w_i d_i^2; the errors over the points that took part in the fit
+                sum += w[row0 + i] * (d * d);
+                wrong_signs += wrong && w[row0 + i] > 0.0 ? 1 : 0;
+            } else {
+                sum += d * d;
+                wrong_signs += wrong ? 1 : 0;
+            }
+        }
+        if (press != nullptr) press[oc] = sum;
+        if (errors != nullptr) errors[oc] += wrong_signs;
+    }
+};
+
+/* the pass of k_reduced_leverage: an operand is Bt, the m rows of V and the k betas; a grid takes one shift vector per gamma (the operands are shared out evenly among
+ * them, in order) */
+struct LeverageArgs : LooArgs {
+    LeverageArgs(int rank, int num_cols, size_t operands, bool with_ybar, hipStream_t stream, size_t shifts = 1) : LooArgs(rank, num_cols, operands, 1, with_ybar, stream, shifts) {}
+    /* operand o <- the host's m + k rows of ldb doubles; asynchronous: the rows stay as they are until the stream has been synchronised */
+    void upload_operand(size_t o, const double *Bt_host) {
+        LSSVM_HIP_CHECK(hipMemcpyAsync(ops.p + o * op_stride, Bt_host, op_stride * sizeof(double), hipMemcpyHostToDevice, st));
+    }
     /* k_reduced_leverage for operand o on `rows` rows of a slab (ld doubles between its columns; its [1 | Y] columns stand behind Phi where `loo` is given) */
     void enqueue(size_t o, const double *slab, size_t ld, int rows, double *h, double *f, double *loo, const double *w_dev = nullptr, size_t shift_at = 0) const {
-        hipLaunchKernelGGL(k_reduced_leverage, dim3(round_up(rows, 256) / RG_TW), dim3(256), 0, st, slab, ld, rows, m, k, Bt.p + o * op_stride, ldb, shift.p + shift_at * m, ybar.p != nullptr ? ybar.p + o * k : nullptr,
+        hipLaunchKernelGGL(k_reduced_leverage, dim3(round_up(rows, 256) / RG_TW), dim3(256), 0, st, slab, ld, rows, m, k, ops.p + o * op_stride, ldb, shift.p + shift_at * m, ybar.p != nullptr ? ybar.p + o * k : nullptr,
                            inv_n, loo != nullptr ? slab + static_cast<size_t>(m + 1) * ld : nullptr, h, f, loo, ld, w_dev);
         LSSVM_HIP_CHECK(hipGetLastError());
     }
-    hipStream_t st;
 };
 
-/* what a pass over every prefix rank works on: per operand (a cost) the m rows of V and, behind them, the k rows of z, ldb doubles apart -- the
- * layout of LeverageArgs' operands with z where the betas stand, so that DenseFit::run fills it as it is; the checkpoints; and where the results go, every output with
- * the checkpoint dimension behind the operand's */
-struct PrefixArgs {
-    const int m, k, ldb, R;
-    const size_t num_ops, op_stride;
-    DevBuf<double> ops, shift, ybar;
+/* the pass over every prefix rank: per operand (a cost) the m rows of V and, behind them, the k rows of z -- z where LeverageArgs' betas stand, so
+ * that DenseFit::run fills it as it is; and the R checkpoints, every output with the checkpoint dimension behind the operand's */
+struct PrefixArgs : LooArgs {
+    const int R;
     DevBuf<int> ranks_dev;
     std::vector<int> ranks;
-    double inv_n = 0.0;
-    const void *Y = nullptr;                                        // the host's right-hand sides (k x N, the problem's type), or NULL: no leave-one-out values
-    const double *w = nullptr;                                      // the host's N weights, or NULL
-    double *h_out = nullptr, *f_out = nullptr, *loo_out = nullptr;  // num_ops x R x N, num_ops x R x k x N, num_ops x R x k x N; each may be NULL
-    double *press = nullptr;                                        // num_ops x R x k, or NULL
-    uint64_t *errors = nullptr;                                     // num_ops x R x k, or NULL
-    std::vector<double> max_leverage, leverage_ms;                  // num_ops x R; per operand
-    double landmark_ms = 0.0;
-    hipStream_t st;
 
     PrefixArgs(int rank, int num_cols, const uint64_t *ranks_in, size_t num_ranks, size_t operands, bool with_ybar, hipStream_t stream) :
-        m(rank), k(num_cols), ldb(round_up(rank, RG_KC)), R(static_cast<int>(num_ranks)), num_ops(operands), op_stride(static_cast<size_t>(rank + num_cols) * ldb),
-        ranks(ranks_in, ranks_in + num_ranks), st(stream) {
-        ops.alloc_zero(num_ops * op_stride, st);
-        shift.alloc_zero(static_cast<size_t>(m), st);
-        if (with_ybar) ybar.alloc_zero(num_ops * std::max(k, 1), st);
+        LooArgs(rank, num_cols, operands, num_ranks, with_ybar, stream, 1), R(static_cast<int>(num_ranks)), ranks(ranks_in, ranks_in + num_ranks) {
         ranks_dev.alloc_zero(static_cast<size_t>(R), st);
         LSSVM_HIP_CHECK(hipMemcpyAsync(ranks_dev.p, ranks.data(), static_cast<size_t>(R) * sizeof(int), hipMemcpyHostToDevice, st));
         LSSVM_HIP_CHECK(hipStreamSynchronize(st));
@@ -1047,11 +995,6 @@ struct PrefixArgs {
     /* operand o <- the host's m + k rows of ldb doubles; returns when they are on the device */
     void upload_operand(size_t o, const double *host) {
         LSSVM_HIP_CHECK(hipMemcpyAsync(V_of(o), host, op_stride * sizeof(double), hipMemcpyHostToDevice, st));
-        LSSVM_HIP_CHECK(hipStreamSynchronize(st));
-    }
-    void upload_shift(const double *shift_host, const double *ybar_host) {
-        LSSVM_HIP_CHECK(hipMemcpyAsync(shift.p, shift_host, shift.count * sizeof(double), hipMemcpyHostToDevice, st));
-        if (ybar_host != nullptr) LSSVM_HIP_CHECK(hipMemcpyAsync(ybar.p, ybar_host, num_ops * k * sizeof(double), hipMemcpyHostToDevice, st));
         LSSVM_HIP_CHECK(hipStreamSynchronize(st));
     }
     /* k_reduced_leverage_prefix for operand o and its right-hand sides c0 ... c0 + kc - 1 (kc <= PFX_KMAX) on `rows` rows of a slab; h: R x ld, f and loo: R x kc x ld */
@@ -1353,7 +1296,7 @@ void check_reduced_loo_costs(const double *costs, size_t num_costs) {
 }
 
 /* The Phi slabs once more (the kernels and arguments of reduced_gram: the same bits) and, per slab, k_reduced_leverage once per operand; h, f and loo of the slab go to the
- * caller's arrays, the sums over the points are formed here in row order.  The caller has made the checks that need no device. */
+ * caller's arrays, the sums over the points are formed in row order (LooArgs::score).  The caller has made the checks that need no device. */
 template <typename T>
 void Solver<T>::leverage_pass(const std::vector<uint64_t> &lm, uint64_t slab_rows, LeverageArgs &a, GridSlabs<T> *grid) {
     Problem<T> &p = *shards_[0];
@@ -1380,11 +1323,7 @@ void Solver<T>::leverage_pass(const std::vector<uint64_t> &lm, uint64_t slab_row
 
     Event ev[2];
     for (Event &e : ev) e.create(true);
-    a.max_leverage.assign(a.num_ops, 0.0);
-    a.leverage_ms.assign(a.num_ops, 0.0);
-    a.landmark_ms = 0.0;
-    if (a.press != nullptr) std::fill(a.press, a.press + a.num_ops * k, 0.0);
-    if (a.errors != nullptr) std::fill(a.errors, a.errors + a.num_ops * k, uint64_t{ 0 });
+    a.reset_sums();
     const T *Yh = static_cast<const T *>(a.Y);
     for (int s = 0; s < plan.slabs; ++s) {
         const size_t row0 = plan.row0(s);
@@ -1392,12 +1331,7 @@ void Solver<T>::leverage_pass(const std::vector<uint64_t> &lm, uint64_t slab_row
         if (grid != nullptr) {
             grid->enqueue_shared(s, slab.p);
         } else {
-            LSSVM_HIP_CHECK(hipEventRecord(ev[0].e, st));
-            enqueue_slab(*block, m, plan, s, rhs, slab.p, st);
-            LSSVM_HIP_CHECK(hipGetLastError());
-            LSSVM_HIP_CHECK(hipEventRecord(ev[1].e, st));
-            LSSVM_HIP_CHECK(hipEventSynchronize(ev[1].e));
-            a.landmark_ms += elapsed_ms(ev[0], ev[1]);
+            a.landmark_ms += timed_slab(*block, m, plan, s, rhs, slab.p, ev, st);
         }
         for (size_t o = 0; o < a.num_ops; ++o) {
             const size_t g = o / per_group;
@@ -1413,29 +1347,11 @@ void Solver<T>::leverage_pass(const std::vector<uint64_t> &lm, uint64_t slab_row
             }
             LSSVM_HIP_CHECK(hipStreamSynchronize(st));
             a.leverage_ms[o] += elapsed_ms(ev[0], ev[1]);
-            for (int i = 0; i < rows; ++i) a.max_leverage[o] = std::max(a.max_leverage[o], h_host[i]);
-            if (a.h_out != nullptr) std::copy(h_host.begin(), h_host.begin() + rows, a.h_out + o * N + row0);
+            a.take_leverage(o, h_host.data(), N, row0, rows);
             for (int c = 0; c < k; ++c) {
                 const size_t oc = o * k + c;
                 if (a.f_out != nullptr) std::copy(&f_host[static_cast<size_t>(c) * ld], &f_host[static_cast<size_t>(c) * ld] + rows, a.f_out + oc * N + row0);
-                if (!with_y) continue;
-                const double *loo = &loo_host[static_cast<size_t>(c) * ld];
-                if (a.loo_out != nullptr) std::copy(loo, loo + rows, a.loo_out + oc * N + row0);
-                double press = a.press != nullptr ? a.press[oc] : 0.0;
-                uint64_t errors = 0;
-                for (int i = 0; i < rows; ++i) {
-                    const double y = static_cast<double>(Yh[static_cast<size_t>(c) * N + row0 + i]), d = y - loo[i];
-                    const bool wrong = ((loo[i] > 0.0) - (loo[i] < 0.0)) != ((y > 0.0) - (y < 0.0));
-                    if (a.w != nullptr) {  // sum_i w_i d_i^2; the errors over the points that took part in the fit
-                        press += a.w[row0 + i] * (d * d);
-                        errors += wrong && a.w[row0 + i] > 0.0 ? 1 : 0;
-                    } else {
-                        press += d * d;
-                        errors += wrong ? 1 : 0;
-                    }
-                }
-                if (a.press != nullptr) a.press[oc] = press;
-                if (a.errors != nullptr) a.errors[oc] += errors;
+                if (with_y) a.score(oc, Yh + static_cast<size_t>(c) * N, &loo_host[static_cast<size_t>(c) * ld], N, row0, rows);
             }
         }
     }
@@ -1526,7 +1442,7 @@ void Solver<T>::fit_reduced_loo_dev(const void *Y, size_t num_rhs, uint64_t rank
     for (size_t s = 0; s < num_costs; ++s) {
         const double t_cost = now_ms();
         double device_ms = 0.0;
-        nus[s] = fit.run(dev, St, Kmm, cols, Nd, 1.0 / costs[s], a.Bt.p + s * a.op_stride, a.ldb, betas_out + s * k * m, rhos_out + s * k, dense_out != nullptr ? dense_out + s : nullptr,
+        nus[s] = fit.run(dev, St, Kmm, cols, Nd, 1.0 / costs[s], a.ops.p + s * a.op_stride, a.ldb, betas_out + s * k * m, rhos_out + s * k, dense_out != nullptr ? dense_out + s : nullptr,
                          &device_ms);
         for (int c = 0; c < k; ++c) ybar[s * k + c] = St[static_cast<size_t>(m + 1 + c) * cols + m] / Nd;
         host_ms[s] = std::max(0.0, now_ms() - t_cost - device_ms);
@@ -1636,7 +1552,7 @@ void Solver<T>::fit_reduced_grid(const void *Y, size_t num_rhs, const double *we
             const double t_cell = now_ms();
             if (factor == 1) {
                 double device_ms = 0.0;
-                nus[o] = fit->run(dev[g], St, Kmm, cols, Nd, 1.0 / costs[s], a.Bt.p + o * a.op_stride, a.ldb, betas_out + o * k * m, rhos_out + o * k, dense_out != nullptr ? dense_out + o : nullptr,
+                nus[o] = fit->run(dev[g], St, Kmm, cols, Nd, 1.0 / costs[s], a.ops.p + o * a.op_stride, a.ldb, betas_out + o * k * m, rhos_out + o * k, dense_out != nullptr ? dense_out + o : nullptr,
                                   &device_ms);
                 for (int c = 0; c < k; ++c) ybar[o * k + c] = St[static_cast<size_t>(m + 1 + c) * cols + m] / Nd;
                 host_ms[o] = std::max(0.0, now_ms() - t_cell - device_ms);
@@ -1731,8 +1647,8 @@ void Solver<T>::reduced_leverage(uint64_t rank, const uint64_t *landmarks, uint6
 }
 
 /* ---- every prefix rank of one fit ---- */
-/* The Phi slabs once more (as leverage_pass) and, per slab and operand, k_reduced_leverage_prefix once per group of PFX_KMAX right-hand sides; h, f and loo of the slab
- * and every checkpoint go to the caller's arrays, the sums over the points are formed here in row order as leverage_pass forms them. */
+/* The Phi slabs once more and, per slab and operand, k_reduced_leverage_prefix once per group of PFX_KMAX right-hand sides; h, f and loo of the slab and every checkpoint
+ * go to the caller's arrays, the sums over the points are formed in row order (LooArgs::score). */
 template <typename T>
 void Solver<T>::prefix_pass(const std::vector<uint64_t> &lm, uint64_t slab_rows, PrefixArgs &a) {
     Problem<T> &p = *shards_[0];
@@ -1757,21 +1673,12 @@ void Solver<T>::prefix_pass(const std::vector<uint64_t> &lm, uint64_t slab_rows,
 
     Event ev[2];
     for (Event &e : ev) e.create(true);
-    a.max_leverage.assign(a.num_ops * R, 0.0);
-    a.leverage_ms.assign(a.num_ops, 0.0);
-    a.landmark_ms = 0.0;
-    if (a.press != nullptr) std::fill(a.press, a.press + a.num_ops * R * k, 0.0);
-    if (a.errors != nullptr) std::fill(a.errors, a.errors + a.num_ops * R * k, uint64_t{ 0 });
+    a.reset_sums();
     const T *Yh = static_cast<const T *>(a.Y);
     for (int s = 0; s < plan.slabs; ++s) {
         const size_t row0 = plan.row0(s);
         const int rows = plan.rows(s);
-        LSSVM_HIP_CHECK(hipEventRecord(ev[0].e, st));
-        enqueue_slab(block, m, plan, s, rhs, slab.p, st);
-        LSSVM_HIP_CHECK(hipGetLastError());
-        LSSVM_HIP_CHECK(hipEventRecord(ev[1].e, st));
-        LSSVM_HIP_CHECK(hipEventSynchronize(ev[1].e));
-        a.landmark_ms += elapsed_ms(ev[0], ev[1]);
+        a.landmark_ms += timed_slab(block, m, plan, s, rhs, slab.p, ev, st);
         for (size_t o = 0; o < a.num_ops; ++o) {
             for (int c0 = 0; c0 == 0 || c0 < k; c0 += PFX_KMAX) {  // (k == 0: one launch for h alone)
                 const int kc = std::min(PFX_KMAX, k - c0);
@@ -1786,32 +1693,11 @@ void Solver<T>::prefix_pass(const std::vector<uint64_t> &lm, uint64_t slab_rows,
                 a.leverage_ms[o] += elapsed_ms(ev[0], ev[1]);
                 for (int q = 0; q < R; ++q) {
                     const size_t oq = o * R + q;
-                    if (c0 == 0) {
-                        const double *h = &h_host[static_cast<size_t>(q) * ld];
-                        for (int i = 0; i < rows; ++i) a.max_leverage[oq] = std::max(a.max_leverage[oq], h[i]);
-                        if (a.h_out != nullptr) std::copy(h, h + rows, a.h_out + oq * N + row0);
-                    }
+                    if (c0 == 0) a.take_leverage(oq, &h_host[static_cast<size_t>(q) * ld], N, row0, rows);
                     for (int c = 0; c < kc; ++c) {
                         const size_t oc = oq * k + c0 + c, at = (static_cast<size_t>(q) * kc + c) * ld;
                         if (a.f_out != nullptr) std::copy(&f_host[at], &f_host[at] + rows, a.f_out + oc * N + row0);
-                        if (!with_y) continue;
-                        const double *loo = &loo_host[at];
-                        if (a.loo_out != nullptr) std::copy(loo, loo + rows, a.loo_out + oc * N + row0);
-                        double press = a.press != nullptr ? a.press[oc] : 0.0;
-                        uint64_t errors = 0;
-                        for (int i = 0; i < rows; ++i) {
-                            const double y = static_cast<double>(Yh[static_cast<size_t>(c0 + c) * N + row0 + i]), d = y - loo[i];
-                            const bool wrong = ((loo[i] > 0.0) - (loo[i] < 0.0)) != ((y > 0.0) - (y < 0.0));
-                            if (a.w != nullptr) {  // sum_i w_i d_i^2; the errors over the points that took part in the fit
-                                press += a.w[row0 + i] * (d * d);
-                                errors += wrong && a.w[row0 + i] > 0.0 ? 1 : 0;
-                            } else {
-                                press += d * d;
-                                errors += wrong ? 1 : 0;
-                            }
-                        }
-                        if (a.press != nullptr) a.press[oc] = press;
-                        if (a.errors != nullptr) a.errors[oc] += errors;
+                        if (with_y) a.score(oc, Yh + static_cast<size_t>(c0 + c) * N, &loo_host[at], N, row0, rows);
                     }
                 }
             }
@@ -2104,149 +1990,6 @@ template void Solver<double>::time_gram_kernels(int, double *, double *, double 
 /* ---- the fixed-size model from a stream of chunks (lssvm_mi355_reduced_stream_*) ---- */
 namespace {
 
-/* n[i] = the sum over the ldx held features (ascending) of (x_if - c_f)^2, in double, as k_row_norms forms it: the squared norms k_cross_product expands the rbf distance
- * with, of the rows AS THEY ARE STAGED there (centre: ldx doubles, zeros from the last feature on, so a padded feature adds an exact 0) */
-template <typename T>
-__global__ __launch_bounds__(256) void k_centred_norms(const T *__restrict__ X, int ldx, size_t N, const double *__restrict__ centre, double *__restrict__ n) {
-    const size_t i = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
-    if (i >= N) return;
-    const T *xi = X + i * ldx;
-    double acc = 0.0;
-    for (int f = 0; f < ldx; ++f) {
-        const double a = static_cast<double>(xi[f]) - centre[f];
-        acc += a * a;
-    }
-    n[i] = acc;
-}
-
-/* The sibling of k_landmark_product for rows that are NOT in a resident problem: D[l][i] of the n rows of `Xc` (a chunk, held padded to ldx features) against the m
- * landmark ROWS `XL`, held on their own.  Tiling, LDS layout, fragments and the pinned accumulators are k_landmark_product's: 128 landmarks (blockIdx.y) x 128 rows
- * (blockIdx.x) per workgroup, four waves of 64 x 64, sixteen accumulators of v_mfma_f64_16x16x4_f64 each, both operands through LDS in steps of RG_KC = 16 features.
- * What differs: the A operand is read from XL and the B operand from Xc, two base pointers and no index list; `centre` (ldx doubles, zeros for a kernel that is not
- * translation invariant and from the last feature on) is SUBTRACTED from both operands as they are staged -- one f64x2 of it per step and thread, every operand is
- * (double) x_f - c_f; and D may start at any row of a slab (the host adds the fill position to the pointer), so its stores are 8-byte aligned only.
- * rbf: D = max(n_i + n_l - 2 x_i . x_l, 0) with norms_c / norms_l of k_centred_norms.  A streamed row carries no index, so there is no "the landmark itself" test: only
- * `diag` (the K_mm launch: Xc == XL) sets D[l][l] to exactly 0.  Any other kernel type: the dot product.
- * Landmarks from m on and rows from n on count as zeros and are never read; landmarks from m on are not written, rows from n on up to the end of the workgroup's 128 are
- * written as zeros -- a slab keeps that much slack behind its last row.  No atomics, no scratch; the order of every sum depends on ldx only. */
-template <typename T>
-__global__ __launch_bounds__(256, 2) void k_cross_product(const T *__restrict__ XL, const T *__restrict__ Xc, int ldx, int n, int m, const double *__restrict__ centre, int kernel_type,
-                                                          const double *__restrict__ norms_l, const double *__restrict__ norms_c, int diag, double *__restrict__ D, size_t ld) {
-    using pair = typename PairOf<T>::type;
-    __shared__ __attribute__((aligned(16))) double As[RG_TW * RG_LS];
-    __shared__ __attribute__((aligned(16))) double Bs[RG_TW * RG_LS];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int wr = wave >> 1, wc = wave & 1;
-    const int r = lane & 15, qd = lane >> 4;
-    const int l0 = blockIdx.y * RG_TW;      // the workgroup's first landmark
-    const int local0 = blockIdx.x * RG_TW;  // ... and first row of the chunk
-    const int nsteps = ldx / RG_KC;
-
-    // staging: thread -> (point srow [+ 32 p] of the tile, features 2 sseg, 2 sseg + 1 of the step), as k_landmark_product
-    const int srow = tid >> 3, sseg = tid & 7;
-    const T *Ag[4], *Bg[4];
-    bool a_in[4], b_in[4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const int la = l0 + srow + 32 * p, ib = local0 + srow + 32 * p;
-        a_in[p] = la < m;
-        b_in[p] = ib < n;
-        Ag[p] = XL + static_cast<size_t>(a_in[p] ? la : 0) * ldx + 2 * sseg;
-        Bg[p] = Xc + static_cast<size_t>(b_in[p] ? ib : 0) * ldx + 2 * sseg;
-    }
-    const double *cg = centre + 2 * sseg;
-    const int lds_w = srow * RG_LS + 2 * sseg;
-    f64x2 sa[4], sb[4];
-    const f64x2 zero2 = { 0.0, 0.0 };
-    auto stage_load = [&](int s) {
-        const f64x2 c2 = *reinterpret_cast<const f64x2 *>(cg + s * RG_KC);
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            sa[p] = zero2;
-            sb[p] = zero2;
-            if (a_in[p]) {
-                const pair v = *reinterpret_cast<const pair *>(Ag[p] + s * RG_KC);
-                sa[p] = f64x2{ static_cast<double>(v[0]) - c2[0], static_cast<double>(v[1]) - c2[1] };
-            }
-            if (b_in[p]) {
-                const pair v = *reinterpret_cast<const pair *>(Bg[p] + s * RG_KC);
-                sb[p] = f64x2{ static_cast<double>(v[0]) - c2[0], static_cast<double>(v[1]) - c2[1] };
-            }
-        }
-    };
-    auto stage_store = [&]() {
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            *reinterpret_cast<f64x2 *>(As + lds_w + p * 32 * RG_LS) = sa[p];
-            *reinterpret_cast<f64x2 *>(Bs + lds_w + p * 32 * RG_LS) = sb[p];
-        }
-    };
-
-    f64x4 acc[4][4];
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) {
-            acc[mt][nt] = f64x4{ 0.0, 0.0, 0.0, 0.0 };
-            // the start values live in the accumulators' OWN registers (C == D for every MFMA of a chain), as in k_reduced_gram
-            asm volatile("" : "+v"(acc[mt][nt]));
-        }
-
-    if (nsteps > 0) {
-        stage_load(0);
-        stage_store();
-    }
-    __syncthreads();
-    const double *Ab = As + (wr * 64 + r) * RG_LS + qd;
-    const double *Bb = Bs + (wc * 64 + r) * RG_LS + qd;
-    for (int s = 0; s < nsteps; ++s) {
-        const bool has_next = s + 1 < nsteps;
-        if (has_next) stage_load(s + 1);
-#pragma unroll
-        for (int ks = 0; ks < RG_KC / 4; ++ks) {
-            double av[4], bv[4];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                av[t] = Ab[t * 16 * RG_LS + ks * 4];
-                bv[t] = Bb[t * 16 * RG_LS + ks * 4];
-            }
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[mt], bv[nt], acc[mt][nt], 0, 0, 0);
-        }
-        __syncthreads();  // (every wave has read this step)
-        if (has_next) {
-            stage_store();
-            __syncthreads();
-        }
-    }
-
-    // a lane holds landmarks l0 + wr 64 + mt 16 + qd + 4 i and rows local0 + wc 64 + nt 16 + r
-    const bool rbf = kernel_type == LSSVM_KERNEL_RBF;
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-        const int local = local0 + wc * 64 + nt * 16 + r;
-        const bool row_in = local < n;
-        const double ni = rbf && row_in ? norms_c[local] : 0.0;
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int l = l0 + wr * 64 + mt * 16 + qd + 4 * i;
-                if (l >= m) continue;
-                double d = acc[mt][nt][i];
-                if (rbf) {
-                    d = fmax((ni + norms_l[l]) - 2.0 * d, 0.0);
-                    if (diag != 0 && l == local) d = 0.0;
-                }
-                D[static_cast<size_t>(l) * ld + local] = row_in ? d : 0.0;
-            }
-    }
-}
-
 /* the sibling of k_reduced_aux for a chunk: column c of `out` (ld doubles apart; the host has added the fill position) is 1 (c = 0) or right-hand side c - 1 of the
  * chunk-local Y (ldy reals between two right-hand sides), exact zeros from row n on up to the end of the grid's 256-row blocks */
 template <typename T>
@@ -2397,7 +2140,7 @@ class ReducedStream final : public ReducedStreamBase {
             for (size_t s = 0; s < num_costs; ++s) {
                 const double t_cost = now_ms();
                 double device_ms = 0.0;
-                nus[s] = fit.run(dev_, St, Kmm_host_, cols, W, 1.0 / costs[s], a->Bt.p + s * a->op_stride, a->ldb, betas_out + s * k * m, rhos_out + s * k, nullptr, &device_ms);
+                nus[s] = fit.run(dev_, St, Kmm_host_, cols, W, 1.0 / costs[s], a->ops.p + s * a->op_stride, a->ldb, betas_out + s * k * m, rhos_out + s * k, nullptr, &device_ms);
                 for (int c = 0; c < k; ++c) ybar[s * k + c] = St[static_cast<size_t>(m + 1 + c) * cols + m] / W;
                 host_ms[s] = std::max(0.0, now_ms() - t_cost - device_ms);
             }

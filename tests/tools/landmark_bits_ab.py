@@ -2,8 +2,8 @@
 """Everything that walks the landmark block K(X, X_L) -- the Nystrom preconditioner, the fixed-size fit, its leave-one-out pass -- in this build against a library built
 from the PARENT commit: the same bits (default) and the same time (--timing).
 
-usage: landmark_bits_ab.py --parent-lib <libplssvm_amd.so of the parent commit> [--out profiles/landmark_bits.json]
-       landmark_bits_ab.py --parent-lib <...> --timing [--rounds 2] [--reps 5] [--out profiles/landmark_bits.json]
+usage: landmark_bits_ab.py --parent-lib <libplssvm_amd.so of the parent commit> [--tile-loop] [--out profiles/landmark_bits.json]
+       landmark_bits_ab.py --parent-lib <...> --timing [--tile-loop] [--rounds 2] [--reps 5] [--out profiles/landmark_bits.json]
 
 Written for a change that moves the host code around the landmark kernels without touching arithmetic (cg_bits_ab.py is the model): every returned array and the integer /
 jitter fields of the info structs must be bit-equal, so the condition is equality of SHA-256 digests with no tolerance; millisecond fields are left out.  Error messages are
@@ -22,12 +22,25 @@ Bits.  fp32 / fp64; linear, polynomial degree 3, rbf; blobs of 5 features with 3
                                (near_singular_case has the construction and why duplicate landmarks alone do not do it)
   error texts                  the refusals that tests/test_gpu_reduced.py, test_gpu_reduced_loo.py and test_gpu_pcg.py provoke on a problem by argument alone, and the two
                                "data" refusals of every one-shot entry point
+Bits, --tile-loop (default --out: profiles/reduced_tile_loop_bits.json).  What the five kernels on the shared fp64 MFMA tile loop of lssvm_reduced.hip serve and the
+cases above do not reach; 5 and 37 features (held as 16 and 48: one and three steps of the contraction), fp32 / fp64, N in {255, 257, 777}, slab_rows in {256, 0},
+explicit landmarks that contain point 0 and point N - 1, weights with one 0 among them:
+  fit_reduced_grid, landmark_acc   product "ordered" and "matrix", rank in {1, 17, 129}, rbf / polynomial (landmark_acc: linear too), 2 gammas x 2 costs
+  fit_reduced_rank_path,           rank 129 with checkpoints {1, 128, 129}, rank 64 with {16, 64}; k in {1, 5} (the prefix aid: 0 too), with and without weights
+  reduced_leverage_prefix
+  fit_reduced_loo, reduced_leverage  rank 127 (k = 3), 129, 257; with and without weights
+  weighted fit_reduced, landmark_gram  rank in {1, 129} at N = 777 and N = 2305 with slab_rows 0 (two row chunks in one slab)
+  the stream                       rank in {17, 129}, rbf / linear: the exported state, solve and loo after updates of 100 + 157 + 520 rows and after one update of the 777
 Timing (--timing).  Host wall clock of the whole call (every call ends in a device synchronise), medians over rounds x reps samples per library after one untimed call,
 and the parent's spread (max - min) / median:
   a  fit_reduced, 50 000 x 128 rbf fp32, rank 256
   b  fit_reduced_loo on the same data, 8 costs
   c  build_preconditioner + solve_pcg, 50 000 x 128 rbf fp32, rank 256, eps 1e-3 (problem set-up not included)
   d  fit_reduced, 2 000 x 16, rank 64: host code and launches dominate, an added allocation or synchronisation would show
+  --tile-loop: a, b, d and, on the data of a,
+  e  fit_reduced_rank_path, checkpoints {64, 128, 256}, 2 costs
+  f  fit_reduced_grid, product "matrix", 2 gammas x 2 costs
+  and, recorded beside them without a condition ("kernels": medians of the device times in ms), time_leverage_kernel, time_leverage_prefix_kernel and time_gram_kernels
 Condition per shape: median(new) <= median(parent) * (1 + spread(parent)).
 Child processes alternate between the two libraries (PLSSVM_AMD_LIBRARY).  Every child runs under a time limit of its own; a child that fails ends the run: nothing more
 is started on the device.  The tool exits non-zero on any difference / any shape over its bound, after it has written --out.
@@ -269,7 +282,122 @@ def bits_child() -> None:
     print("RESULT " + json.dumps(out), flush=True)
 
 
-def timing_child(reps: int) -> None:
+def everything(res) -> str:
+    """One digest over a result of any shape: arrays, numbers, and the fields of info records other than the millisecond ones."""
+    import numpy as np
+
+    parts = []
+
+    def walk(v):
+        if isinstance(v, dict):
+            for key in sorted(v):
+                if not key.endswith("_ms"):
+                    parts.append(np.frombuffer(key.encode(), dtype=np.uint8))
+                    walk(v[key])
+        elif isinstance(v, (list, tuple)):
+            for item in v:
+                walk(item)
+        else:
+            parts.append(np.asarray(v))
+
+    walk(res)
+    return digest(*parts)
+
+
+def tile_child() -> None:
+    sys.path.insert(0, ROOT)
+    import numpy as np
+
+    from plssvm_amd import backend
+    from plssvm_amd.datagen import make_blobs_multiclass
+    from plssvm_amd.multiclass import one_vs_all_targets
+    from plssvm_amd.parameter import Parameter
+
+    out = {}
+    gammas, costs = [0.05, 0.4], [0.5, 20.0]
+
+    def data(N, dt, features):
+        X, labels = make_blobs_multiclass(N, features, 3, seed=7 + N + features, dtype=dt)
+        Y = one_vs_all_targets(np.arange(3), labels, dt)
+        return X, np.ascontiguousarray(np.concatenate((Y, -Y[:2])))  # five right-hand sides: two launches of the prefix kernel
+
+    def weights(N):
+        w = np.random.default_rng(13).uniform(0.5, 2.0, N)
+        w[3] = 0.0
+        return w
+
+    for dt in (np.float32, np.float64):
+        for features in (5, 37):
+            for kernel, (name, degree) in KERNELS.items():
+                p = Parameter(kernel_type=name, degree=degree, gamma=1.0 / features, coef0=0.5, cost=COST)
+                for N in (255, 257, 777):
+                    head = f"{np.dtype(dt).name} {kernel} {features} features {N}"
+                    X, Y = data(N, dt, features)
+                    w = weights(N)
+                    rng = np.random.default_rng(5)
+                    with backend.ResidentProblem(p, X) as prob:
+                        for rank in (1, 17, 129):
+                            lm = explicit_landmarks(N, rank)
+                            for product in ("ordered", "matrix"):
+                                out[f"{head}: rank {rank} product {product}: landmark_acc"] = digest(prob.landmark_acc(rank, landmarks=lm, product=product))
+                                if kernel != "linear":
+                                    for slab_rows in (256, 0):
+                                        out[f"{head}: rank {rank} product {product} slab_rows {slab_rows}: fit_reduced_grid"] = everything(
+                                            prob.fit_reduced_grid(Y[:2], rank, gammas, costs, landmarks=lm, product=product, slab_rows=slab_rows))
+                        if kernel != "rbf":
+                            continue
+                        for slab_rows in (256, 0):
+                            for rank, ranks in ((129, [1, 128, 129]), (64, [16, 64])):
+                                lm = explicit_landmarks(N, rank)
+                                V, shift = np.tril(rng.standard_normal((rank, rank))), rng.standard_normal(rank)
+                                for k in (0, 1, 5):
+                                    key = f"{head}: rank {rank} checkpoints {ranks} k {k} slab_rows {slab_rows}"
+                                    out[f"{key}: reduced_leverage_prefix"] = digest(*prob.reduced_leverage_prefix(V, shift, ranks, rng.standard_normal((k, rank)) if k else None, landmarks=lm,
+                                                                                                                  slab_rows=slab_rows))
+                                    for sw in (None, w) if k else ():
+                                        out[f"{key} weights {sw is not None}: fit_reduced_rank_path"] = everything(
+                                            prob.fit_reduced_rank_path(Y[:k], rank, ranks, costs, landmarks=lm, slab_rows=slab_rows, sample_weight=sw))
+                            for rank, k in ((127, 3), (129, 1), (257, 1)):
+                                if rank > N:
+                                    continue
+                                lm = explicit_landmarks(N, rank)
+                                V, shift = np.tril(rng.standard_normal((rank, rank))), rng.standard_normal(rank)
+                                key = f"{head}: rank {rank} k {k} slab_rows {slab_rows}"
+                                out[f"{key}: reduced_leverage"] = digest(*prob.reduced_leverage(V, shift, rng.standard_normal((rank, k)), landmarks=lm, slab_rows=slab_rows))
+                                for sw in (None, w):
+                                    out[f"{key} weights {sw is not None}: fit_reduced_loo"] = everything(prob.fit_reduced_loo(Y[:k], rank, costs, landmarks=lm, slab_rows=slab_rows, sample_weight=sw))
+            # ---- k_reduced_gram<true>: one and two row chunks in one slab ----
+            p = Parameter(kernel_type="rbf", gamma=1.0 / features, cost=COST)
+            for N in (777, 2305):
+                X, Y = data(N, dt, features)
+                w = weights(N)
+                with backend.ResidentProblem(p, X) as prob:
+                    for rank in (1, 129):
+                        key = f"{np.dtype(dt).name} rbf {features} features {N}: rank {rank} slab_rows 0 weighted"
+                        lm = explicit_landmarks(N, rank)
+                        out[f"{key}: landmark_gram"] = digest(prob.landmark_gram_weighted(Y[:3], rank, w, landmarks=lm))
+                        out[f"{key}: fit_reduced"] = everything(prob.fit_reduced(Y[:3], rank, landmarks=lm, sample_weight=w))
+            # ---- the stream: the state and the scores do not depend on the cuts, and have the parent's bits ----
+            X, Y = data(777, dt, features)
+            for kernel in ("rbf", "linear"):
+                p = Parameter(kernel_type=kernel, gamma=1.0 / features, cost=COST)
+                for rank in (17, 129):
+                    XL = X[explicit_landmarks(777, rank).astype(np.int64)]
+                    for cuts in ((100, 257, 777), (777,)):
+                        with backend.ReducedStream(p, XL, num_rhs=3) as stream:
+                            at = 0
+                            for end in cuts:
+                                stream.update(X[at:end], Y[:3, at:end])
+                                at = end
+                            state = stream.export_state()
+                            key = f"{np.dtype(dt).name} {kernel} {features} features 777: rank {rank} stream in {len(cuts)} updates"
+                            out[f"{key}: state"] = digest(state["gram"], state["kmm"], np.uint64(state["num_points"]))
+                            out[f"{key}: solve"] = everything(stream.solve(costs))
+                            out[f"{key}: loo"] = digest(*stream.loo(X[:100], Y[:3, :100]))
+    print("RESULT " + json.dumps(out), flush=True)
+
+
+def timing_child(reps: int, tile_loop: bool) -> None:
     sys.path.insert(0, ROOT)
     import numpy as np
 
@@ -299,17 +427,30 @@ def timing_child(reps: int) -> None:
             prob.build_preconditioner(256)
             prob.solve_pcg(y, 1e-3, 50_000)
 
-        timed("c_build_preconditioner_solve_pcg_50000x128_rbf_f32_rank256_eps1e-3", pcg)
+        if tile_loop:
+            timed("e_fit_reduced_rank_path_50000x128_rbf_f32_rank256_3_checkpoints_2_costs", lambda: prob.fit_reduced_rank_path(y, 256, [64, 128, 256], [0.1, 10.0]))
+            timed("f_fit_reduced_grid_matrix_50000x128_rbf_f32_rank256_2_gammas_2_costs", lambda: prob.fit_reduced_grid(y, 256, [1.0 / 256, 1.0 / 64], [0.1, 10.0], product="matrix"))
+            gram_ms, leverage_ms = prob.time_leverage_kernel(256, k=1, repeats=reps)
+            out["kernel: k_reduced_gram + k_reduced_sum, one slab of 50000x128, rank 256"] = gram_ms.tolist()
+            out["kernel: k_reduced_leverage, one slab of 50000x128, rank 256"] = leverage_ms.tolist()
+            out["kernel: k_reduced_leverage_prefix, one slab of 50000x128, rank 256, checkpoints 64 128 256"] = prob.time_leverage_prefix_kernel(256, [64, 128, 256], k=1, repeats=reps).tolist()
+        else:
+            timed("c_build_preconditioner_solve_pcg_50000x128_rbf_f32_rank256_eps1e-3", pcg)
+    if tile_loop:
+        X, y = make_blobs_pm1(20_000, 64, seed=42, dtype=np.float64)
+        with backend.ResidentProblem(Parameter(kernel_type="rbf", gamma=1.0 / 64, cost=1.0), X) as prob:
+            prob.build_preconditioner(256)
+            out["kernel: k_reduced_gram on the preconditioner's block (time_gram_kernels), 20000x64 fp64, rank 256"] = prob.time_gram_kernels(reps)[1].tolist()
     print("RESULT " + json.dumps(out), flush=True)
 
 
-def run_child(which, parent_lib, mode, reps, limit):
+def run_child(which, parent_lib, mode, reps, limit, tile_loop=False):
     env = dict(os.environ)
     if which == "parent":
         env["PLSSVM_AMD_LIBRARY"] = os.path.abspath(parent_lib)
     else:
         env.pop("PLSSVM_AMD_LIBRARY", None)
-    cmd = [sys.executable, os.path.abspath(__file__), "--child", mode, "--reps", str(reps)]
+    cmd = [sys.executable, os.path.abspath(__file__), "--child", mode, "--reps", str(reps)] + (["--tile-loop"] if tile_loop else [])
     try:
         proc = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=limit)
     except subprocess.TimeoutExpired:
@@ -329,25 +470,28 @@ def main() -> int:
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--child-timeout", type=int, default=300, help="seconds one child process may take")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "landmark_bits.json"))
+    ap.add_argument("--tile-loop", action="store_true", help="the cases and shapes of the kernels on the shared fp64 MFMA tile loop")
+    ap.add_argument("--out")
     ap.add_argument("--child", choices=["bits", "timing"])
     args = ap.parse_args()
     if args.child:
-        bits_child() if args.child == "bits" else timing_child(args.reps)
+        (tile_child if args.tile_loop else bits_child)() if args.child == "bits" else timing_child(args.reps, args.tile_loop)
         return 0
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "reduced_tile_loop_bits.json" if args.tile_loop else "landmark_bits.json")
     if not args.parent_lib or not os.path.isfile(args.parent_lib):
         ap.error("--parent-lib must name the library built from the parent commit")
     res = json.load(open(args.out)) if os.path.isfile(args.out) else {}
     failed = []
     if args.timing:
-        samples = {"parent": {}, "new": {}}
+        samples, kernels = {"parent": {}, "new": {}}, {"parent": {}, "new": {}}
         for rnd in range(args.rounds):
             for which in ("parent", "new"):
-                got = run_child(which, args.parent_lib, "timing", args.reps, args.child_timeout)
+                got = run_child(which, args.parent_lib, "timing", args.reps, args.child_timeout, args.tile_loop)
                 if got is None:
                     return 1
                 for name, vals in got.items():
-                    samples[which].setdefault(name, []).extend(vals)
+                    (kernels if name.startswith("kernel: ") else samples)[which].setdefault(name, []).extend(vals)
                 print(f"round {rnd}, {which}: done", flush=True)
         res["timing"] = {}
         for name in sorted(samples["new"]):
@@ -359,13 +503,16 @@ def main() -> int:
                                    "samples_per_library": len(b), "within_parent_spread": ok}
             if not ok:
                 failed.append(name)
+        if kernels["new"]:
+            res["kernels"] = {name: {"new_median_ms": statistics.median(kernels["new"][name]), "parent_median_ms": statistics.median(kernels["parent"][name])} for name in sorted(kernels["new"])}
+            print(json.dumps(res["kernels"], indent=1))
         res["timing_method"] = (f"{args.rounds} alternating child processes per library, {args.reps} timed repetitions each after a warm-up; host wall clock of the whole call; "
                                 "condition: new median <= parent median * (1 + parent spread), spread = (max - min) / median")
         print(json.dumps(res["timing"], indent=1))
     else:
         got = {}
         for which in ("parent", "new"):
-            got[which] = run_child(which, args.parent_lib, "bits", args.reps, args.child_timeout)
+            got[which] = run_child(which, args.parent_lib, "bits", args.reps, args.child_timeout, args.tile_loop)
             if got[which] is None:
                 return 1
             print(f"{which}: {len(got[which])} cases", flush=True)
@@ -380,10 +527,11 @@ def main() -> int:
                 groups.setdefault(parts[0] if len(parts) == 1 or parts[0] == "refusal" else f"{parts[0]}: {parts[-1]}", []).append(f"{name}={json.dumps(got['new'][name], sort_keys=True)}")
         res["bits"] = {"different": {name: {"parent": got["parent"].get(name), "new": got["new"].get(name)} for name in failed},
                        "equal": {g: f"{len(lines)} cases, sha256 {hashlib.sha256(chr(10).join(lines).encode()).hexdigest()}" for g, lines in groups.items()}}
-        retried = got["parent"].get("near-singular: attempts beyond the first", {})
-        res["near_singular_parent"] = retried
-        if not (retried.get("reduced") and retried.get("preconditioner")):  # (else the near-singular case proves nothing)
-            failed.append("near-singular: the parent's jitter loops did not both retry")
+        if not args.tile_loop:
+            retried = got["parent"].get("near-singular: attempts beyond the first", {})
+            res["near_singular_parent"] = retried
+            if not (retried.get("reduced") and retried.get("preconditioner")):  # (else the near-singular case proves nothing)
+                failed.append("near-singular: the parent's jitter loops did not both retry")
         res["bits_summary"] = {"cases": len(names), "equal": sum(len(lines) for lines in groups.values()), "different": failed}
         print(json.dumps(res["bits_summary"], indent=1))
     with open(args.out, "w") as f:
