@@ -428,6 +428,15 @@ int lssvm_mi355_problem_matvec_pair(lssvm_mi355_problem *p, const void *d0, cons
 int lssvm_mi355_problem_solve_lockstep(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out /* num_rhs x N */,
                                        double *rhos_out, lssvm_cg_info *infos_out /* num_rhs, may be NULL */, uint64_t passes_out[2]);
 
+/* lssvm_mi355_problem_matvec_pair / _solve_lockstep with the PANEL kernels included: everything their namesakes do, and in addition ONE pass serves two vectors on
+ * problems beyond the one-pass kernels -- one device, symmetric = 1; fp64 rbf / polynomial (degree >= 0) on more than 256 features; fp32 on f16x3 or bf16x6 planes beyond
+ * 512 padded features (384 for rbf and for bf16x6), polynomial (degree >= 0) or rbf with folded records.  Same results bit for bit, same meaning of *two_vector_out and
+ * passes_out; where neither two-vector kernel applies (the linear kernel at these widths, unfolded rbf, gram_mode = 0, ...) the calls run single passes and report
+ * two_vector = 0 / passes_out[0] = 0.  Entry points of their own because the routing of their namesakes on these widths is a documented part of those. */
+int lssvm_mi355_problem_matvec_pair_panels(lssvm_mi355_problem *p, const void *d0, const void *d1, void *ret0_inout, void *ret1_inout, double add, int *two_vector_out);
+int lssvm_mi355_problem_solve_lockstep_panels(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out /* num_rhs x N */,
+                                              double *rhos_out, lssvm_cg_info *infos_out /* num_rhs, may be NULL */, uint64_t passes_out[2]);
+
 /* COST PATH (no counterpart in the reference): the solutions of ONE right-hand side for EVERY cost of a grid from one multi-shift CG sequence -- one pass over the
  * Gram tiles per iteration for the whole grid instead of one per cost, as many iterations as the hardest (largest) cost alone needs.  For fixed data and kernel
  * function the cost enters the reduced system only as a shift: Abar(C) = A0 + sigma M with sigma = 1 / C, A0 v = K v + (k_NN S - q.v) 1 - S q (S = sum v) and

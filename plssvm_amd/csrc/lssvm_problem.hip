@@ -152,6 +152,18 @@ bool sym_pair_routed(int plane_mode, int kernel_type, int /*degree*/, int nk64) 
     return (plane_mode == 1 || plane_mode == 2) && nk64 >= 3 && nk64 <= max_nk64;
 }
 
+/* The lockstep CG beyond the one-pass kernels (Problem<T>::panel_pair_applies; lssvm_mi355_problem_matvec_pair_panels / _solve_lockstep_panels): whether a pair of
+ * right-hand sides is dispatched as ONE launch of the symmetric two-vector panel kernels (tile_launch_f32xv2s.hip: f16x3 and bf16x6 planes x polynomial of a run-time
+ * degree, degree 2, degree 3, folded rbf; tile_launch_f64xv2s.hip: rbf and the three polynomial forms) -- arguments and meaning as panel_pair_routed, the routing
+ * condition that of sym_pair_routed, measured by tests/tools/lockstep_panels_timing.py (profiles/lockstep_panels.json) against two single-vector symmetric panel passes
+ * of the build before.  An instantiation that fails the condition, or that the compiler does not fit into its single-vector sibling's register budget without scratch,
+ * is named here and takes two single passes.  None is named: all twelve compile without scratch at two waves per SIMD. */
+bool sym_panel_pair_routed(int dtype, int plane_mode, int kernel_type, int degree, int panels) {
+    const bool nonlinear = kernel_type == LSSVM_KERNEL_RBF || (kernel_type == LSSVM_KERNEL_POLYNOMIAL && degree >= 0);
+    if (dtype == LSSVM_DTYPE_F64) return nonlinear && panels >= 5;
+    return nonlinear && (plane_mode == 1 || plane_mode == 2) && panels >= 2;
+}
+
 /* kernel-function specific scalars of TileArgs */
 template <typename T>
 void set_kernel_scalars(TileArgs<T> &a, const lssvm_params &p, bool rbf_direct) {
@@ -1039,15 +1051,32 @@ bool Problem<T>::pair_kernel_applies() const {
     }
 }
 
+/* ... and on the panel kernels (wide_nl_): the forms tile_matvec_f64_wide<KT, SYM, NV = 2> and s6x_body<KT, PL, SYM, NV = 2> have */
+template <typename T>
+bool Problem<T>::panel_pair_applies() const {
+    // (the caller's kernel function: the linear kernel keeps its single passes at these widths, also where few points let it run as the in-tile polynomial of degree 1)
+    const bool poly = params_.kernel_type == LSSVM_KERNEL_POLYNOMIAL && tile_params_.kernel_type == LSSVM_KERNEL_POLYNOMIAL && tile_params_.degree >= 0;
+    if (!(world_ == 1 && sym_ && wide_nl_ && dc_.p != nullptr && num_ib_ > 0)) return false;
+    if constexpr (std::is_same_v<T, double>) {
+        return (poly || tile_params_.kernel_type == LSSVM_KERNEL_RBF) && Xfrag_.p != nullptr
+               && sym_panel_pair_routed(LSSVM_DTYPE_F64, 0, tile_params_.kernel_type, tile_params_.degree, X_.ldx / 64);
+    } else {
+        const bool rbf_folded = tile_params_.kernel_type == LSSVM_KERNEL_RBF && dc_folded_;
+        return !pair_ && !rbf_direct_ && !rbf_grid_ && !row_scaled_ && (planes_.mode == 1 || planes_.mode == 2) && planes_frag_.p != nullptr && (poly || rbf_folded)
+               && sym_panel_pair_routed(LSSVM_DTYPE_F32, planes_.mode, tile_params_.kernel_type, tile_params_.degree, planes_.ldx16 / 128);
+    }
+}
+
 template <typename T>
 void Problem<T>::enqueue_apply_K_lanes(const T *v0, T *Kv0, const T *v1, T *Kv1, hipEvent_t ev_begin, hipEvent_t ev_end) {
-    LSSVM_REQUIRE(pair_kernel_applies(), "no two-vector tile kernel on this problem");
+    LSSVM_REQUIRE(pair_kernel_applies() || panel_pair_applies(), "no two-vector tile kernel on this problem");
     hipStream_t st = stream_.s;
     const int nzero = static_cast<int>(nvec_);  // (the symmetric variant ADDS rows and mirrored columns into K*v)
     TileArgs<T> a = tile_args(v0);
     if (v1 != nullptr) {
         if (pair_dc_.p == nullptr) {
             // fp64: (d0_j | d1_j | c_j), 192 reals per 64-column sub-tile; fp32: (w0_j | w1_j | e_j), 384 per column tile (folded rbf; the polynomial forms use 256 of them)
+            // (the panel kernels' geometry as well: records per column tile whatever the feature count, the slabs twice this problem's own)
             pair_dc_.alloc_zero(static_cast<size_t>(num_tiles_) * 2 * 192, st);
             pair_partial_.alloc_zero(2 * partial_.count, st);
             pair_colslab_.alloc_zero(2 * colslab_.count, st);
@@ -1072,7 +1101,7 @@ void Problem<T>::enqueue_apply_K_lanes(const T *v0, T *Kv0, const T *v1, T *Kv1,
     }
     T *const Kv[2] = { Kv0, Kv1 };
     if (ev_begin != nullptr) LSSVM_HIP_CHECK(hipEventRecord(ev_begin, st));
-    // every reduction runs per vector on that vector's planes, into that vector's K*v (no feature panels where the pair kernel applies)
+    // every reduction runs per vector on that vector's planes, into that vector's K*v (one walk: the panel kernels walk their feature panels inside a tile)
     enqueue_sym_walk(a, v1 != nullptr ? 2 : 1, Kv, 1, [&](auto &&launch, bool, bool last) {
         launch();
         if (last && ev_end != nullptr) LSSVM_HIP_CHECK(hipEventRecord(ev_end, st));

@@ -416,6 +416,11 @@ class Problem {
      * count) instantiations whose two-vector pass was measured faster than two single passes (profiles/lockstep_f64.json); fp32: the symmetric one-pass 128-row split
      * kernels on 129 ... 512 features, polynomial or rbf with folded records (sym_pair_routed, profiles/lockstep_f32_wide.json) */
     bool pair_kernel_applies() const;
+    /* ... and on the panel kernels (wide_nl_: fp32 rbf / polynomial beyond the one-pass split kernels, fp64 beyond 256 features), where the symmetric two-vector panel
+     * kernels serve a pair (sym_panel_pair_routed, profiles/lockstep_panels.json): one device, symmetric variant, records present; fp32: f16x3 or bf16x6 planes with the
+     * polynomial forms (degree >= 0) or folded rbf, not the direct / grid / row-scaled forms; fp64: rbf or polynomial with degree >= 0.  Asked only by the _panels
+     * entry points: lssvm_mi355_problem_matvec_pair and _solve_lockstep keep their routing. */
+    bool panel_pair_applies() const;
     /* Kv0 <- K * v0 and, with v1, Kv1 <- K * v1 from ONE pass of the two-vector kernel (pair_kernel_applies; the caller falls back to two calls elsewhere); without v1
      * today's single-vector pass.  Each result has the bits enqueue_apply_K_local gives for that vector: both are enqueue_sym_walk on the arguments of that vector.
      * `ev`: HIP events around the tile-kernel launches (before the first band's, after the last band's), or NULL. */
@@ -612,9 +617,10 @@ struct ProblemBase {
     virtual void get_q(void *q_out, double *QA_cost_out) = 0;
     virtual void set_weights(const double *weights, size_t num_points) = 0;  // lssvm_mi355_problem_set_weights
     virtual void matvec(const void *d, void *ret_inout, double add) = 0;
-    virtual void matvec_pair(const void *d0, const void *d1, void *ret0_inout, void *ret1_inout, double add, int *two_vector_out) = 0;  // lssvm_mi355_problem_matvec_pair
+    /* `panels`: the _panels entry points -- pairs on the panel kernels as well (Problem<T>::panel_pair_applies) */
+    virtual void matvec_pair(const void *d0, const void *d1, void *ret0_inout, void *ret1_inout, double add, int *two_vector_out, bool panels = false) = 0;  // lssvm_mi355_problem_matvec_pair
     virtual void solve_lockstep(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out,
-                                uint64_t *passes_out) = 0;  // lssvm_mi355_problem_solve_lockstep
+                                uint64_t *passes_out, bool panels = false) = 0;  // lssvm_mi355_problem_solve_lockstep
     virtual void solve_cost_path(const void *y, const double *costs, size_t num_costs, double eps, uint64_t max_iter, bool verify, void *alphas_out, double *rhos_out,
                                  lssvm_path_info *infos_out, uint64_t *passes_out) = 0;  // lssvm_mi355_problem_solve_cost_path
     /* the Nystrom preconditioner and PCG on it (lssvm_precond.hip) */
@@ -748,8 +754,9 @@ class Solver final : public ProblemBase {
     void get_q(void *q_out, double *QA_cost_out) override;
     void set_weights(const double *weights, size_t num_points) override;
     void matvec(const void *d, void *ret_inout, double add) override;
-    void matvec_pair(const void *d0, const void *d1, void *ret0_inout, void *ret1_inout, double add, int *two_vector_out) override;
-    void solve_lockstep(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out) override;
+    void matvec_pair(const void *d0, const void *d1, void *ret0_inout, void *ret1_inout, double add, int *two_vector_out, bool panels = false) override;
+    void solve_lockstep(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out,
+                        bool panels = false) override;
     /* every cost of a grid from ONE multi-shift CG sequence on this problem's single-vector pass (lssvm_path.hip) */
     void solve_cost_path(const void *y, const double *costs, size_t num_costs, double eps, uint64_t max_iter, bool verify, void *alphas_out, double *rhos_out, lssvm_path_info *infos_out,
                          uint64_t *passes_out) override;
@@ -813,7 +820,7 @@ class Solver final : public ProblemBase {
 
     /* for a driver that runs on lanes of shard 0 (the lockstep solve here, the refinement in lssvm_refine.hip) */
     Problem<T> &shard0() { return *shards_[0]; }
-    bool lanes_apply() const;  // one unsharded device without an exchange, where the two-vector kernel applies
+    bool lanes_apply(bool panels = false) const;  // one unsharded device without an exchange, where the two-vector kernel applies (`panels`: or the two-vector panel kernel)
     void wait_for_deltas();    // the host waits for what shard 0's stream holds: the deltas of the step are in their host words
     /* until the returned object goes: no other solve may begin on this handle, and its weights stay */
     [[nodiscard]] SetOnExit<bool> hold_busy() {
@@ -1001,6 +1008,7 @@ bool wide_nonlinear_f64(const Options &o, const lssvm_params &p, size_t num_feat
 bool wide_nonlinear(const Options &o, const lssvm_params &p, bool rbf_direct, size_t num_features);
 bool wide_pair_routed(int plane_mode, int kernel_type, int degree, int nk64);  // the resident fp32 predictor beyond 128 features: one two-vector launch for a pair?
 bool panel_pair_routed(int dtype, int plane_mode, int kernel_type, int degree, int panels);  // the resident predictors on the panel kernels: one two-vector launch for a pair?
+bool sym_panel_pair_routed(int dtype, int plane_mode, int kernel_type, int degree, int panels);  // the lockstep CG on the panel kernels: one symmetric two-vector launch for a pair?
 bool sym_pair_routed(int plane_mode, int kernel_type, int degree, int nk64);   // the fp32 lockstep CG on 129 ... 512 features: one symmetric two-vector launch for a pair of right-hand sides?
 template <typename T>
 void set_kernel_scalars(TileArgs<T> &a, const lssvm_params &p, bool rbf_direct);

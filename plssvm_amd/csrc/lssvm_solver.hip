@@ -536,8 +536,8 @@ void Solver<T>::cg_finish(void *alpha_out, double *rho_out, lssvm_cg_info *info)
 
 /* ------------------------------------------------------------------ two vectors per Gram pass: matvec_pair, the lockstep CG ------------------------------------------------------------------ */
 template <typename T>
-bool Solver<T>::lanes_apply() const {
-    return shards_.size() == 1 && world_ == 1 && exchange_ == Exchange::none && shards_[0]->pair_kernel_applies();
+bool Solver<T>::lanes_apply(bool panels) const {
+    return shards_.size() == 1 && world_ == 1 && exchange_ == Exchange::none && (shards_[0]->pair_kernel_applies() || (panels && shards_[0]->panel_pair_applies()));
 }
 
 template <typename T>
@@ -548,12 +548,12 @@ void Solver<T>::wait_for_deltas() {
 }
 
 template <typename T>
-void Solver<T>::matvec_pair(const void *d0, const void *d1, void *ret0_inout, void *ret1_inout, double add, int *two_vector_out) {
+void Solver<T>::matvec_pair(const void *d0, const void *d1, void *ret0_inout, void *ret1_inout, double add, int *two_vector_out, bool panels) {
     LSSVM_REQUIRE(d0 != nullptr && d1 != nullptr && ret0_inout != nullptr && ret1_inout != nullptr, "The d / ret arrays may not be empty!");  // csvm.cpp:284-286
     LSSVM_REQUIRE(add == 1.0 || add == -1.0, "add must either be -1.0 or 1.0, but is " + std::to_string(add) + "!");                       // svm_kernel.cpp:28
     LSSVM_REQUIRE(!in_cg_, "matvec_pair cannot run between cg_begin and cg_finish");
     if (two_vector_out != nullptr) *two_vector_out = 0;
-    if (!lanes_apply()) {  // two single passes
+    if (!lanes_apply(panels)) {  // two single passes
         matvec(d0, ret0_inout, add);
         matvec(d1, ret1_inout, add);
         return;
@@ -580,7 +580,8 @@ void Solver<T>::matvec_pair(const void *d0, const void *d1, void *ret0_inout, vo
 }
 
 template <typename T>
-void Solver<T>::solve_lockstep(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out) {
+void Solver<T>::solve_lockstep(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out,
+                               bool panels) {
     LSSVM_REQUIRE(Y != nullptr, "The right hand side vector must not be empty!");
     LSSVM_REQUIRE(num_rhs > 0, "The number of right hand sides must be greater than 0!");
     LSSVM_REQUIRE(static_cast<T>(eps) > T(0), "The stopping criterion in the CG algorithm must be greater than 0.0, but is " + std::to_string(eps) + "!");  // csvm.cpp:77
@@ -588,7 +589,7 @@ void Solver<T>::solve_lockstep(const void *Y, size_t num_rhs, double eps, uint64
     LSSVM_REQUIRE(alphas_out != nullptr && rhos_out != nullptr, "alpha_out / rho_out must not be NULL");
     LSSVM_REQUIRE(!in_cg_, "solve_lockstep cannot run between cg_begin and cg_finish");
     if (passes_out != nullptr) passes_out[0] = passes_out[1] = 0;
-    if (lanes_apply()) {
+    if (lanes_apply(panels)) {
         solve_on_lanes(static_cast<const T *>(Y), num_rhs, eps, max_iter, static_cast<T *>(alphas_out), rhos_out, infos_out, passes_out);
     } else {
         solve_in_sequence(Y, num_rhs, eps, max_iter, alphas_out, rhos_out, infos_out, passes_out);

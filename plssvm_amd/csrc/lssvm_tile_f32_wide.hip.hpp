@@ -19,6 +19,11 @@
  * the record of a column tile carries (d0_j | d1_j) (k_pack_dc2; folded rbf: both times 2^c_j), the kernel function is evaluated once per element and feeds two scalar
  * fma chains, and the row sums of vector v go to plane v of `partial` (TileArgs::part_vstride apart).  Per vector the chain of operations is the one of NV = 1.  Not the
  * unfolded rbf form (c_j in the record's second half) and not the grid planes.
+ * NV = 2 in the SYMMETRIC variant (tile_launch_f32xv2s.hip: a pair of right-hand sides of the lockstep CG at these widths), as s6w_body's: the polynomial forms and folded
+ * rbf.  The second vector's d_i is a second plane of `dis` (TileArgs::dvec1), its mirrored column sums a second plane of `colred` and of the slab
+ * (TileArgs::colslab_vstride); folded rbf carries the column's factor behind both vectors' halves of the record, (w0_j | w1_j | e_j), 384 floats fetched by 24 lanes of the
+ * one LDS-DMA instruction per wave (k_pack_dc2_sym).  The record slots lie 1.5 KiB apart (V2S_LDS_BYTES, as s6w_body's).  Per vector the fma chains, the column-sum
+ * butterfly, the flush and the slab order are those of NV = 1: each K v has the bits of a single-vector pass whatever its partner is.
  * Reference semantics: /root/reference/include/plssvm/backends/HIP/svm_kernel.hip.hpp:129-270 (one code path for any feature count).
  */
 #pragma once
@@ -30,9 +35,12 @@ namespace lssvm {
 template <int KT, int PL, bool SYM, int NV = 1>
 __device__ __forceinline__ void s6x_body(const TileArgs<float> &a) {
     static_assert(PL == 3 || PL == 2, "three bf16 planes (bf16x6) or two f16 planes (f16x3)");
-    static_assert(NV == 1 || (NV == 2 && !SYM), "two weight vectors per pass: the full-square variant only");
+    static_assert(NV == 1 || NV == 2, "one or two weight vectors per pass");
     static_assert(NV == 1 || KT == KT_POLY || KT == KT_POLY2 || KT == KT_POLY3 || KT == KT_RBFF, "two weight vectors per pass: the second half of the record must be free");
     static_assert(KT != KT_LINEAR, "the linear kernel takes feature-panel passes of the 128-feature kernels");
+    constexpr bool V2S = SYM && NV == 2;
+    constexpr int REC_FLOATS = (V2S && KT == KT_RBFF) ? 384 : 256;  // a column tile's record: (d_j | c_j), (d0_j | d1_j), or -- two vectors, symmetric, folded rbf -- (w0_j | w1_j | e_j)
+    constexpr int REC_SLOT = V2S ? V2S_REC_SLOT_BYTES : 1024;       // bytes between the record slots in LDS
     constexpr bool F16 = PL == 2;
     // KT_RBFG (rbf on GRID planes, round 5; s6w_body / DESIGN.md section 4.1.2): three f16 planes (h | s1 | s2) and TWO sweeps over the feature panels of a tile -- sweep A: the
     // h x h products of ALL panels (they must come first: with the exact start values they leave -sigma^2 |h_i - h_j|^2 / 2 exactly), sweep B: per panel and 64-feature chunk
@@ -45,10 +53,10 @@ __device__ __forceinline__ void s6x_body(const TileArgs<float> &a) {
     constexpr auto row_plane = [](int p, int q) constexpr { return (F16 && PLA == 3) ? (p == 0 ? (q == 0 ? 2 : 1) : 0) : q; };
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     char *ring = smem_raw;                                                          // [V2_RING][128 rows][128 B]
-    char *dcs = smem_raw + V2_RING * V2_SLOT_BYTES;                                 // [V2_DC_SLOTS][256 floats]
-    float *cis = reinterpret_cast<float *>(dcs + V2_DC_SLOTS * 1024);               // [128] c_i of the row panel (rbf)
-    float *dis = cis + TILE;                                                        // [128] d_i of the row panel
-    float *colred = dis + TILE;                                                     // [2][4 waves][128] column sums of a tile
+    char *dcs = smem_raw + V2_RING * V2_SLOT_BYTES;                                 // [V2_DC_SLOTS][256 floats] (V2S: slots of 384 floats)
+    float *cis = reinterpret_cast<float *>(dcs + V2_DC_SLOTS * REC_SLOT);           // [128] c_i of the row panel (rbf)
+    float *dis = cis + TILE;                                                        // [128] d_i of the row panel (V2S: [2 vectors][128])
+    float *colred = dis + (V2S ? 2 : 1) * TILE;                                     // [2][4 waves][128] column sums of a tile (V2S: [2 vectors][2][4 waves][128])
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -123,6 +131,9 @@ __device__ __forceinline__ void s6x_body(const TileArgs<float> &a) {
     }
     if constexpr (SYM) {
         if (tid < TILE) dis[tid] = GRID ? a.dvec[row0 + tid] * a.er[row0 + tid] : a.dvec[row0 + tid];  // (grid planes: the row's folded factor E_i rides on d_i)
+        if constexpr (V2S) {
+            if (tid >= TILE) dis[tid] = a.dvec1[row0 + tid - TILE];
+        }
     }
     // make the compiler retire these ordinary loads HERE, before any LDS-DMA is in flight
 #pragma unroll
@@ -142,7 +153,7 @@ __device__ __forceinline__ void s6x_body(const TileArgs<float> &a) {
     }
     const unsigned ring_lds = static_cast<unsigned>(reinterpret_cast<size_t>(ring));
     const unsigned dma_lds = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(ring_lds + static_cast<unsigned>(wave) * 4096u)));
-    const unsigned dc_lds = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(ring_lds + V2_RING * V2_SLOT_BYTES + static_cast<unsigned>(wave) * 256u)));
+    const unsigned dc_lds = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(ring_lds + V2_RING * V2_SLOT_BYTES + static_cast<unsigned>(wave) * static_cast<unsigned>(REC_FLOATS))));  // this wave's quarter of record slot 0
     auto issue_chunk = [&](int step) {  // step = (tile t, panel p, plane-chunk kc): plane kc % PL of the 64-feature chunk kc / PL of panel p
         const int t = step / steps_per_tile;
         const int in_tile = step - t * steps_per_tile;
@@ -171,9 +182,10 @@ __device__ __forceinline__ void s6x_body(const TileArgs<float> &a) {
         static_for<0, 4>([&](auto i_c) { lds_dma16<decltype(i_c)::value * 1024>(dma_off[decltype(i_c)::value], base, slot); });
     };
     auto issue_dc = [&](int t) {
-        if (lane < 16) {
-            const char *src = sgpr_ptr(a.dc + static_cast<size_t>(jt_begin + t) * 256) + __builtin_amdgcn_readfirstlane(wave * 256);
-            lds_dma16<0>(16u * (lane_off(threadIdx.x) & 15u), sgpr_ptr(src), static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(dc_lds + static_cast<unsigned>(t % V2_DC_SLOTS) * 1024u))));
+        // each wave fetches its quarter of the record: 16 lanes x 16 bytes (records of 384 floats: 24 lanes), lane-linear in LDS
+        if (lane < REC_FLOATS / 16) {
+            const char *src = sgpr_ptr(a.dc + static_cast<size_t>(jt_begin + t) * REC_FLOATS) + __builtin_amdgcn_readfirstlane(wave * REC_FLOATS);
+            lds_dma16<0>(16u * (lane_off(threadIdx.x) & (REC_FLOATS == 384 ? 31u : 15u)), sgpr_ptr(src), static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(dc_lds + static_cast<unsigned>(t % V2_DC_SLOTS) * static_cast<unsigned>(REC_SLOT)))));
         }
     };
 
@@ -230,7 +242,15 @@ __device__ __forceinline__ void s6x_body(const TileArgs<float> &a) {
     };
 
     auto flush_cols = [&](int t) {
-        if (tid < TILE) {
+        if constexpr (V2S) {
+            // waves 0, 1: the first vector's 128 columns; waves 2, 3: the second vector's, from its plane of colred into its plane of the slab (per vector the sum below)
+            const int v = wave >> 1;
+            const float *cr_ = colred + v * 1024 + (t & 1) * 512;
+            const int c = tid & (TILE - 1);
+            const float sum = (cr_[c] + cr_[128 + c]) + (cr_[256 + c] + cr_[384 + c]);
+            auto *rec = (__attribute__((address_space(1))) float *) const_cast<char *>(sgpr_ptr(a.colslab + static_cast<size_t>(v) * a.colslab_vstride + (rec0 + jt_begin + t) * TILE));
+            rec[lane_off(static_cast<unsigned>(c))] = sum;
+        } else if (tid < TILE) {
             const float *cr_ = colred + (t & 1) * 512;
             const float sum = (cr_[tid] + cr_[128 + tid]) + (cr_[256 + tid] + cr_[384 + tid]);
             auto *rec = (__attribute__((address_space(1))) float *) const_cast<char *>(sgpr_ptr(a.colslab + (rec0 + jt_begin + t) * TILE));
@@ -240,7 +260,7 @@ __device__ __forceinline__ void s6x_body(const TileArgs<float> &a) {
 
     for (int t = 0; t < ntiles; ++t) {
         const bool tile_sym = SYM && (jt_begin + t < ib);  // strictly below the diagonal
-        const float *dcr = reinterpret_cast<const float *>(dcs + (t % V2_DC_SLOTS) * 1024);
+        const float *dcr = reinterpret_cast<const float *>(dcs + (t % V2_DC_SLOTS) * REC_SLOT);
         // start values of the chain: rbf c_i + c_j, rbf with folded records c_i (c_j is the factor 2^c_j of the record), polynomial 0
         if constexpr (KT == KT_RBF || GRID) {  // (grid planes: sigma^2 (ch_i + ch_j), an exact sum)
 #pragma unroll
@@ -252,6 +272,12 @@ __device__ __forceinline__ void s6x_body(const TileArgs<float> &a) {
                     for (int e = 0; e < 4; ++e) acc[rb][cb][e] = civ0[rb][e] + cjv;
             }
         } else {
+            if constexpr (V2S && KT == KT_RBFF) {
+                // (two vectors, symmetric: c_i is read from LDS at the head of every tile -- the same eight values, but eight registers less across the panels and
+                // the epilogue, which is what keeps this form at two waves per SIMD without scratch; volatile: not to be hoisted back out of the tile loop)
+#pragma unroll
+                for (int rb = 0; rb < 2; ++rb) civ0[rb] = *reinterpret_cast<const volatile f32x4 *>(cis + wave * 32 + 16 * rb + 4 * g);
+            }
 #pragma unroll
             for (int cb = 0; cb < 8; ++cb)
 #pragma unroll
@@ -352,13 +378,16 @@ __device__ __forceinline__ void s6x_body(const TileArgs<float> &a) {
         auto epilogue = [&](auto with_cols) {
             constexpr bool COLS = decltype(with_cols)::value;
             using f32x2 = float __attribute__((ext_vector_type(2)));
-            f32x4 di[2];
-            float colacc[8];
-            f32x2 colacc2[8] = {};
+            constexpr int NC = SYM ? NV : 1;  // vectors with mirrored column sums
+            f32x4 di[NC][2];
+            float colacc[NC][8];
+            f32x2 colacc2[NC][8] = {};
             f32x2 kvp = { 0.f, 0.f };
             if constexpr (COLS) {
 #pragma unroll
-                for (int rb = 0; rb < 2; ++rb) di[rb] = *reinterpret_cast<const f32x4 *>(dis + wave * 32 + 16 * rb + 4 * g);
+                for (int v = 0; v < NC; ++v)
+#pragma unroll
+                    for (int rb = 0; rb < 2; ++rb) di[v][rb] = *reinterpret_cast<const f32x4 *>(dis + v * TILE + wave * 32 + 16 * rb + 4 * g);
             }
 #pragma unroll
             for (int cb = 0; cb < 8; ++cb) {
@@ -379,22 +408,38 @@ __device__ __forceinline__ void s6x_body(const TileArgs<float> &a) {
                         if constexpr (COLS) {
                             kvp[e & 1] = kv;
                             if (e & 1) {
-                                const f32x2 dip = { di[rb][e - 1], di[rb][e] };
-                                colacc2[cb] = __builtin_elementwise_fma(kvp, dip, colacc2[cb]);
+#pragma unroll
+                                for (int v = 0; v < NC; ++v) {
+                                    const f32x2 dip = { di[v][rb][e - 1], di[v][rb][e] };
+                                    colacc2[v][cb] = __builtin_elementwise_fma(kvp, dip, colacc2[v][cb]);
+                                }
                             }
                         }
                     }
+                if constexpr (COLS && V2S) {  // (two vectors: a block's pair of sums is folded as soon as the block is done -- 16 registers less across the epilogue)
+#pragma unroll
+                    for (int v = 0; v < NC; ++v) {
+                        colacc[v][cb] = colacc2[v][cb][0] + colacc2[v][cb][1];
+                        asm("" : "+v"(colacc[v][cb]));
+                    }
+                }
+            }
+            if constexpr (COLS && !V2S) {
+#pragma unroll
+                for (int cb = 0; cb < 8; ++cb) colacc[0][cb] = colacc2[0][cb][0] + colacc2[0][cb][1];
             }
             if constexpr (COLS) {
+                // (two vectors: the same butterfly per vector, into that vector's plane of colred; the factor sits behind BOTH vectors' halves of the record)
 #pragma unroll
-                for (int cb = 0; cb < 8; ++cb) colacc[cb] = colacc2[cb][0] + colacc2[cb][1];
-                float *cw = colred + (t & 1) * 512 + wave * 128;
-                column_sums_of_8_blocks(colacc);
+                for (int u = 0; u < NC; ++u) {
+                    float *cw = colred + u * 1024 + (t & 1) * 512 + wave * 128;
+                    column_sums_of_8_blocks(colacc[u]);
 #pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    float v = colacc[4 * h];
-                    if constexpr (KT == KT_RBFF) v *= dcr[128 + 64 * h + lane];
-                    cw[64 * h + lane] = v;
+                    for (int h = 0; h < 2; ++h) {
+                        float v = colacc[u][4 * h];
+                        if constexpr (KT == KT_RBFF) v *= dcr[NC * TILE + 64 * h + lane];
+                        cw[64 * h + lane] = v;
+                    }
                 }
             }
         };
@@ -450,6 +495,15 @@ __global__ __launch_bounds__(TILE_THREADS, (KT == KT_RBFG ? LSSVM_WIDE_GRID_WAVE
 template <int KT, int PL>
 __global__ __launch_bounds__(TILE_THREADS, 2) void tile_matvec_f32_wide_nv2(const TileArgs<float> a) {
     s6x_body<KT, PL, false, 2>(a);
+}
+/* ... and its symmetric counterpart (tile_launch_f32xv2s.hip: two right-hand sides of the lockstep CG per pass; V2S_LDS_BYTES of dynamic LDS -- two workgroups per CU
+ * still fit).  LSSVM_WIDE_NV2S_WAVES: waves per SIMD the register budget is set for. */
+#ifndef LSSVM_WIDE_NV2S_WAVES
+#define LSSVM_WIDE_NV2S_WAVES 2
+#endif
+template <int KT, int PL>
+__global__ __launch_bounds__(TILE_THREADS, LSSVM_WIDE_NV2S_WAVES) void tile_matvec_f32_wide_nv2s(const TileArgs<float> a) {
+    s6x_body<KT, PL, true, 2>(a);
 }
 
 }  // namespace lssvm

@@ -218,6 +218,7 @@ constexpr int V2D_SLOT_BYTES = 64 * 128;  // 8 KiB
 constexpr int V2D_DC_SLOTS = 4;           // (64 d_j | 64 c_j) doubles = 1 KiB per sub-tile
 constexpr size_t V2D_LDS_BYTES = static_cast<size_t>(V2D_RING) * V2D_SLOT_BYTES + V2D_DC_SLOTS * 1024 + (2 * TILE + 2 * 4 * 64) * sizeof(double);  // ring + records + cis, dis, colred
 constexpr size_t V2D_LDS_BYTES_NV2 = static_cast<size_t>(V2D_RING) * V2D_SLOT_BYTES + V2D_DC_SLOTS * 1536 + (3 * TILE + 2 * 2 * 4 * 64) * sizeof(double);  // NV = 2: records of 1.5 KiB, two dis, two colred (49 KiB: two workgroups per CU)
+constexpr size_t V2D_WIDE_LDS_BYTES_SYM_NV2 = static_cast<size_t>(V2D_RING) * V2D_SLOT_BYTES + V2D_DC_SLOTS * 1536 + (TILE + 2 * TILE + 2 * 2 * 4 * 64) * sizeof(double);  // tile_matvec_f64_wide<KT, SYM, NV = 2>: ring + records + cis, dis, colred, dis1, colred1
 
 template <int KT, int NKC, bool SYM, int NV = 1>
 __global__ __launch_bounds__(TILE_THREADS, (NKC <= 4 ? 2 : 1)) void tile_matvec_f64_v2(const TileArgs<double> a) {

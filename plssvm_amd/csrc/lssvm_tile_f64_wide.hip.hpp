@@ -9,10 +9,13 @@
  * workgroups per CU) is re-loaded from L2 for every (sub-tile, panel), each 16-feature chunk requested as soon as the previous panel is through
  * with it.  The linear kernel does not come here: its Gram matrix is a sum over panels and runs one pass of the v2 kernel per panel
  * (lssvm_problem.hip).  The data is padded to whole panels (padded_features).  A negative polynomial degree stays on the generic kernel.
- * NV = 2 (full-square variant only; tile_launch_f64xv2.hip: the resident predictor of a one-vs-all model at these widths): TWO vectors per pass, as
- * tile_matvec_f64_v2's NV = 2 -- the kernel value of an element is computed once and feeds both vectors' row sums, each through the fma chain it has at NV = 1.  The
- * record of a sub-tile is (d0_j | d1_j | c_j), 1.5 KiB (k_pack_dc2_f64), fetched by 24 lanes per wave; the LDS size is V2D_LDS_BYTES_NV2.  Everything the second
- * vector adds stands in `if constexpr (NV == 2)`: the NV = 1 instantiations are the code they were.
+ * NV = 2 (full square, tile_launch_f64xv2.hip: the resident predictor of a one-vs-all model at these widths; symmetric, tile_launch_f64xv2s.hip: a pair of right-hand
+ * sides of the lockstep CG): TWO vectors per pass, as tile_matvec_f64_v2's NV = 2 -- the kernel value of an element is computed once and feeds both vectors' row sums,
+ * each through the fma chain it has at NV = 1.  The record of a sub-tile is (d0_j | d1_j | c_j), 1.5 KiB (k_pack_dc2_f64), fetched by 24 lanes per wave; the LDS size
+ * is V2D_LDS_BYTES_NV2 (symmetric: V2D_WIDE_LDS_BYTES_SYM_NV2).  The symmetric form adds, per vector, what the symmetric NV = 1 form has once: the second vector's d_i
+ * (TileArgs::dvec1) in an LDS array of its own, a colacc[4] and a colred[2][4][64] of its own, and its own flush into the second plane of the column slab
+ * (colslab_vstride) -- per vector the fma chains, the column-sum tree, the flush and the slab order of NV = 1, so each K v has the bits of a single-vector pass.
+ * Everything the second vector adds stands in `if constexpr (NV == 2)`: the NV = 1 instantiations are the code they were.
  * Reference semantics: /root/reference/include/plssvm/backends/HIP/svm_kernel.hip.hpp:129-270 (one code path for any feature count).
  */
 #pragma once
@@ -24,7 +27,7 @@ namespace lssvm {
 template <int KT, bool SYM, int NV = 1>
 __global__ __launch_bounds__(TILE_THREADS, 2) void tile_matvec_f64_wide(const TileArgs<double> a) {
     static_assert(KT != KT_LINEAR, "the linear kernel takes feature-panel passes of tile_matvec_f64_v2");
-    static_assert(NV == 1 || (NV == 2 && !SYM), "two vectors per pass: the full-square variant only");
+    static_assert(NV == 1 || NV == 2, "one or two vectors per pass");
     constexpr int NKC = 4;  // 16-feature chunks per panel
     constexpr int REC_BYTES = NV * 512 + 512;  // a sub-tile's record: 64 d_j per vector, then 64 c_j
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -33,6 +36,8 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void tile_matvec_f64_wide(const Ti
     double *cis = reinterpret_cast<double *>(dcs + V2D_DC_SLOTS * REC_BYTES);  // [128] c_i of the row panel (rbf)
     double *dis = cis + TILE;                                              // [128] d_i of the row panel (SYM)
     double *colred = dis + TILE;                                           // [2][4 waves][64] column sums of a sub-tile (SYM)
+    [[maybe_unused]] double *dis1 = colred + 2 * 4 * 64;                   // SYM, NV = 2: the second vector's d_i ...
+    [[maybe_unused]] double *colred1 = dis1 + TILE;                        // ... and column sums
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -90,6 +95,9 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void tile_matvec_f64_wide(const Ti
     }
     if constexpr (SYM) {
         if (tid < TILE) dis[tid] = a.dvec[row0 + tid];
+        if constexpr (NV == 2) {
+            if (tid < TILE) dis1[tid] = a.dvec1[row0 + tid];
+        }
     }
     // retire these ordinary loads HERE, before any LDS-DMA is in flight
 #pragma unroll
@@ -181,6 +189,11 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void tile_matvec_f64_wide(const Ti
             const double *cr_ = colred + (t & 1) * 256;
             auto *rec = (__attribute__((address_space(1))) double *) (a.colslab + (rec0 + st_begin + t) * 64);
             rec[static_cast<unsigned>(tid)] = (cr_[tid] + cr_[64 + tid]) + (cr_[128 + tid] + cr_[192 + tid]);
+            if constexpr (NV == 2) {  // the second vector: the same tree, from its colred into its plane of the slab
+                const double *cr1_ = colred1 + (t & 1) * 256;
+                auto *rec1 = (__attribute__((address_space(1))) double *) (a.colslab + a.colslab_vstride + (rec0 + st_begin + t) * 64);
+                rec1[static_cast<unsigned>(tid)] = (cr1_[tid] + cr1_[64 + tid]) + (cr1_[128 + tid] + cr1_[192 + tid]);
+            }
         }
     };
 
@@ -262,12 +275,15 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void tile_matvec_f64_wide(const Ti
             if constexpr (NV == 2) dj1[cb] = dcr[64 + cb * 16 + r];
         }
         double colacc[4] = { 0.0, 0.0, 0.0, 0.0 };
+        [[maybe_unused]] double colacc1[4] = { 0.0, 0.0, 0.0, 0.0 };
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 double di = 0.0;
                 if constexpr (SYM) di = dis[wave * 32 + rb * 16 + q + 4 * i];
+                [[maybe_unused]] double di1 = 0.0;
+                if constexpr (SYM && NV == 2) di1 = dis1[wave * 32 + rb * 16 + q + 4 * i];
 #pragma unroll
                 for (int cb = 0; cb < 4; ++cb) {
                     double kv;
@@ -278,12 +294,16 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void tile_matvec_f64_wide(const Ti
                     }
                     rowpart[rb][i] = fma(kv, dj[cb], rowpart[rb][i]);
                     if constexpr (SYM) colacc[cb] = fma(kv, di, colacc[cb]);
-                    if constexpr (NV == 2) rowpart1[rb][i] = fma(kv, dj1[cb], rowpart1[rb][i]);  // kv is shared; the second vector's chain is that of a single-vector pass
+                    if constexpr (NV == 2) {  // kv is shared; the second vector's chains are those of a single-vector pass
+                        rowpart1[rb][i] = fma(kv, dj1[cb], rowpart1[rb][i]);
+                        if constexpr (SYM) colacc1[cb] = fma(kv, di1, colacc1[cb]);
+                    }
                 }
             }
         if constexpr (SYM) {
             double *cw = colred + (t & 1) * 256 + wave * 64;
             cw[lane] = column_sums_of_4_blocks(colacc);  // (diagonal sub-tiles: computed, never flushed)
+            if constexpr (NV == 2) colred1[(t & 1) * 256 + wave * 64 + lane] = column_sums_of_4_blocks(colacc1);
         }
     }
     if constexpr (SYM) {

@@ -58,6 +58,8 @@ void launch_tile_kernel<float>(TileArgs<float> &a, int kernel_type, bool rbf_dir
         } else if (a.wide_panels != 0) {
             if (a.nvec == 2 && a.items == nullptr) {  // two vectors per full-square pass of the panel kernel (the resident Predictor<float>)
                 launch_nv2_panel_tile_kernel(a, kernel_type, grid, s);
+            } else if (a.nvec == 2) {  // ... per symmetric pass (Problem<float>::enqueue_apply_K_lanes where panel_pair_applies)
+                launch_nv2_sym_panel_tile_kernel(a, kernel_type, s);
             } else {
                 launch_wide_tile_kernel(a, kernel_type, grid, s);
             }

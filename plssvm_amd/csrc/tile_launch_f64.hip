@@ -169,6 +169,8 @@ void launch_tile_kernel<double>(TileArgs<double> &a, int kernel_type, bool /*rbf
     if (a.dc != nullptr && a.wide_panels != 0) {
         if (a.nvec == 2 && a.items == nullptr) {  // two vectors per full-square pass of the panel kernel (the resident Predictor<double>)
             launch_nv2_panel_tile_kernel_f64(a, kernel_type, grid, s);
+        } else if (a.nvec == 2) {  // ... per symmetric pass (Problem<double>::enqueue_apply_K_lanes where panel_pair_applies)
+            launch_nv2_sym_panel_tile_kernel_f64(a, kernel_type, s);
         } else {
             launch_wide_tile_kernel_f64(a, kernel_type, grid, s);
         }

@@ -632,7 +632,8 @@ class MI355CSVM(CSVM):
         """The systems in LOCKSTEP on ONE resident problem (``ResidentProblem.solve_lockstep``): the data is uploaded and prepared (q, operand planes) once, the weights are
         set once, and every right-hand side runs the recipe of the one-shot solve (begin / step / finish) on it -- the same alpha, rho and iteration count as a fresh
         one-shot solve.  In fp64 on the symmetric resident-row-panel kernel, and in fp32 on 129 ... 512 features (polynomial, or rbf with folded records, on the symmetric
-        one-pass split kernels), one pass over the Gram tiles serves two right-hand sides per iteration; elsewhere they are solved one after the other.  Several devices: the base class's loop of one-shot solves."""
+        one-pass split kernels), one pass over the Gram tiles serves two right-hand sides per iteration -- and so it does beyond those widths, on the symmetric two-vector panel kernels
+        (``solve_lockstep(..., panels=True)``: fp64 rbf / polynomial on more than 256 features, fp32 polynomial / folded rbf on planes, 784-feature image data for one); elsewhere they are solved one after the other.  Several devices: the base class's loop of one-shot solves."""
         self.last_refine_info = None
         if self.solver == "pcg":  # ONE preconditioner for all right-hand sides
             self._pcg_applies(sample_weight)
@@ -661,7 +662,7 @@ class MI355CSVM(CSVM):
         with backend.ResidentProblem(params, A, devices=[0], options=self._options) as prob:  # (device 0 alone, as the one-shot solve creates it)
             if sample_weight is not None:
                 prob.set_weights(sample_weight)
-            alphas, rhos, infos, _ = prob.solve_lockstep(B, eps, max_iter)  # (one device: option rebalance_after has nothing to move)
+            alphas, rhos, infos, _ = prob.solve_lockstep(B, eps, max_iter, panels=True)  # (one device: option rebalance_after has nothing to move)
         return alphas, rhos, infos
 
     def predict_values_multi(self, params, support_vectors, alphas, rhos, ws, predict_points):
