@@ -317,6 +317,22 @@ int lssvm_mi355_predictor_create_resident(lssvm_mi355_predictor **out, const lss
 int lssvm_mi355_predictor_create_panels(lssvm_mi355_predictor **out, const lssvm_params *params, int dtype, const void *support_vectors, size_t num_support_vectors,
                                         size_t num_features, const void *alphas, const double *rhos, size_t num_vectors, const lssvm_mi355_options *options);
 
+/* The `create_resident` handle once more, with the fp64 form's weight vectors taken SIXTEEN per pass over the Gram tiles: the kernel values of a tile stay in the
+ * registers the matrix cores left them in and are multiplied by a 64 x 16 block of weights with a second v_mfma_f64 (tile_matvec_f64_blk, DESIGN.md section
+ * 4.1.3) -- a ten-class model takes one pass where `create_resident` takes five.  Opt-in; no other entry point routes here.  Arguments, their validation and the error
+ * texts are those of `create_multi`, refused before a device is touched; `predict`, `predict_multi` and `destroy` work on the handle as on any other.
+ * The block form: dtype LSSVM_DTYPE_F64, rbf / polynomial (gamma > 0), at most 256 padded features.  The vectors are grouped sixteen at a time, a last group of fewer
+ * padded with zero vectors; the records of every group are packed once and stay in HBM.  lssvm_predict_info: resident == 1, vectors_per_launch == 16.
+ * Values: each is a sum over the same kernel values as `create_resident`'s, added four columns at a time by the matrix cores instead of one column at a time by an
+ * fma chain -- NOT the same bits; the difference is a few eps of the summand scale sum_j |alpha_j k_ij| (tests/test_gpu_predictor_block.py).  The order of every
+ * sum depends on the shapes only: a call repeats bit for bit, and column v has the bits of the same vector alone in a handle of one.
+ * Declined -- the handle is then what `create_resident` gives, bits and info: dtype LSSVM_DTYPE_F32, the linear kernel, more than 256 padded features, options
+ * gram_mode = 0, tile_kernel = 1, rbf_form = 1 / 3.
+ * Where it pays and where it does not (one or two vectors; few features, where the second product is as large as the first): README, "Sixteen decision
+ * functions per pass", profiles/predictor_block.json. */
+int lssvm_mi355_predictor_create_block(lssvm_mi355_predictor **out, const lssvm_params *params, int dtype, const void *support_vectors, size_t num_support_vectors,
+                                       size_t num_features, const void *alphas, const double *rhos, size_t num_vectors, const lssvm_mi355_options *options);
+
 /* ------------------------------------------------------------------------------------------------------------------ */
 /* fine-grained entry points for kernel-level parity tests: the protected members the reference's backend tests re-export  */
 /* (tests/backends/HIP/mock_hip_csvm.hpp:22-44): generate_q, run_device_kernel, calculate_w                           */

@@ -765,9 +765,15 @@ class Predictor:
 
     ``panels=True`` creates the model through ``lssvm_mi355_predictor_create_panels``: every form of ``every_form=True``, and the models beyond those widths on the
     kernels that walk feature panels inside a tile (float32 rbf / polynomial beyond 384 / 512 features, float64 beyond 256; two weight vectors per pass for the
-    polynomial kernel, float64 rbf and float32 rbf with folded records).  A model below those widths behaves as with ``every_form=True``."""
+    polynomial kernel, float64 rbf and float32 rbf with folded records).  A model below those widths behaves as with ``every_form=True``.
 
-    def __init__(self, params: Parameter, support_vectors, alpha, rho, options: Options | None = None, every_form: bool = False, panels: bool = False):
+    ``block=True`` creates the model through ``lssvm_mi355_predictor_create_block``: ``every_form=True`` with the float64 form's weight vectors taken SIXTEEN per pass
+    over the Gram tiles, the second product on the matrix cores (``info_out["vectors_per_launch"] == 16``; rbf / polynomial, at most 256 features).  Its values are
+    sums of the same kernel values in another order -- a few eps of the summand scale from those of ``every_form=True``, not their bits; a column still has the bits
+    of its vector alone.  Float32, the linear kernel, wider models and ``gram_mode = 0`` / ``tile_kernel = 1`` / ``rbf_form = 1, 3`` behave as with
+    ``every_form=True``.  Pays from a handful of vectors on (profiles/predictor_block.json); it wins over ``panels``."""
+
+    def __init__(self, params: Parameter, support_vectors, alpha, rho, options: Options | None = None, every_form: bool = False, panels: bool = False, block: bool = False):
         sv = _as_matrix(support_vectors)
         alpha = np.ascontiguousarray(alpha, dtype=sv.dtype)
         self.dtype, self.num_features = sv.dtype, int(sv.shape[1])
@@ -786,10 +792,10 @@ class Predictor:
             if alpha.size != sv.shape[0]:
                 raise InvalidParameterError(f"The number of support vectors ({sv.shape[0]}) and number of weights ({alpha.size}) must be the same!")
             self.num_vectors = None  # (one weight vector: the values are a vector, not a matrix of one column)
-            k, rhos = 1, np.array([float(rho)], dtype=np.float64)  # (every_form / panels: a handle of one vector, used through lssvm_mi355_predictor_predict like any other)
+            k, rhos = 1, np.array([float(rho)], dtype=np.float64)  # (every_form / panels / block: a handle of one vector, used through lssvm_mi355_predictor_predict like any other)
         ps = _params_struct(params, sv.shape[1])
-        if alpha.ndim == 2 or every_form or panels:
-            create = "lssvm_mi355_predictor_create_panels" if panels else ("lssvm_mi355_predictor_create_resident" if every_form else "lssvm_mi355_predictor_create_multi")
+        if alpha.ndim == 2 or every_form or panels or block:
+            create = "lssvm_mi355_predictor_create_block" if block else "lssvm_mi355_predictor_create_panels" if panels else ("lssvm_mi355_predictor_create_resident" if every_form else "lssvm_mi355_predictor_create_multi")
             check(_capi.predictor_multi_entry(create)(C.byref(self._h), C.byref(ps), _capi.dtype_code(sv.dtype), ptr(sv), sv.shape[0], sv.shape[1], ptr(alpha),
                                                       rhos.ctypes.data_as(C.POINTER(C.c_double)), k, options_ptr(options)))
             return

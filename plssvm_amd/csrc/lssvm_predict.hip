@@ -168,7 +168,8 @@ static bool rect_kernel_applies(const Options &opt, const lssvm_params &params, 
  * predictors.  Rows = the points P (padded to whole pairs of row blocks), columns = the support vectors S, both prepared by the caller.  The stage owns the slabs of
  * partial row sums, the values and the launches' timer; a caller sets the operand-specific launch arguments on what args() returns and calls run() once.
  * `records(v, count) -> const T *`: the column records of the launch group that starts at weight vector v and holds `count` (1 or 2) vectors, NULL for a kernel that
- * reads none.  A caller that packs records on the stream does so inside the callable: args() asks for group 0 -- in front of whatever the caller enqueues next and of the
+ * reads none.  vectors_per_launch == BLOCK_VECTORS: the sixteen-vector fp64 kernel (tile_matvec_f64_blk) -- EVERY group, a last one of fewer vectors included, is a
+ * launch of that kernel on a record whose remaining slots hold zero vectors, with sixteen planes of row slabs of which the group's `count` are reduced.  A caller that packs records on the stream does so inside the callable: args() asks for group 0 -- in front of whatever the caller enqueues next and of the
  * drain that precedes the timed region --, run() for every later group immediately in front of its launch. */
 template <typename T>
 struct ProductStage {
@@ -177,6 +178,7 @@ struct ProductStage {
     const bool rect;  // the rectangular 256-row kernel: the caller's decision (rect_kernel_applies) and the caller's setup_rect_launch
     const T *const alpha, *const rho;  // [nvec][S.rows_alloc] in HBM, exact zeros beyond the support vectors; [nvec] on the host
     const int nv, per_launch, num_ib, num_jt;
+    const bool block;  // sixteen vectors per launch (tile_matvec_f64_blk)
     const int jc_tiles, num_jc;  // column tiles per work item (product_chunk_tiles, lssvm_geometry.cpp) and the column chunks they make
     const size_t part_plane;
     const hipStream_t s;
@@ -187,7 +189,7 @@ struct ProductStage {
     ProductStage(const Options &options, const DeviceMatrix<T> &points, const DeviceMatrix<T> &svs, bool rect256, const T *alphas, const T *rhos, size_t nvec, int vectors_per_launch,
                  hipStream_t stream, double t_begin) :
         opt(options), P(points), S(svs), rect(rect256), alpha(alphas), rho(rhos), nv(static_cast<int>(nvec)), per_launch(vectors_per_launch), num_ib(points.rows_alloc / TILE),
-        num_jt(svs.rows_alloc / TILE), jc_tiles(product_chunk_tiles(geometry_options(options), rect256, num_ib, num_jt)), num_jc(num_chunks(num_jt, jc_tiles, 0, 0)), part_plane(static_cast<size_t>(num_jc) * points.rows_alloc), s(stream), t0(t_begin), timer(nvec) {
+        num_jt(svs.rows_alloc / TILE), block(vectors_per_launch == BLOCK_VECTORS), jc_tiles(product_chunk_tiles(geometry_options(options), rect256, num_ib, num_jt)), num_jc(num_chunks(num_jt, jc_tiles, 0, 0)), part_plane(static_cast<size_t>(num_jc) * points.rows_alloc), s(stream), t0(t_begin), timer(nvec) {
         partial.alloc_zero(per_launch * part_plane, s);
         Kv.alloc_zero(P.rows_alloc, s);
         o.alloc_zero(static_cast<size_t>(P.rows) * nvec, s);
@@ -239,8 +241,8 @@ struct ProductStage {
                 ta.dvec = alpha + static_cast<size_t>(v) * S.rows_alloc;
                 next_counters();
             }
-            ta.nvec = count;
-            ta.part_vstride = count == 2 ? static_cast<long>(part_plane) : 0;
+            ta.nvec = block ? BLOCK_VECTORS : count;
+            ta.part_vstride = (block || count == 2) ? static_cast<long>(part_plane) : 0;
             timer.timed(s, launch);
             for (int u = 0; u < count; ++u) {
                 hipLaunchKernelGGL(k_reduce_partials<T>, dim3((P.rows_alloc + 255) / 256), dim3(256), 0, s, partial.p + u * part_plane, ta.part_stride, num_jc, 0, P.rows_alloc, Kv.p);
@@ -460,7 +462,7 @@ class ResidentF32 {
   public:
     static constexpr bool declines_batches = true;  // (the one-shot path's inputs stay needed: alpha on the host, the support vectors through fetch_support_vectors)
 
-    bool prepare(const PredictModel<float> &m, const float *sv, const float *alpha, int forms, hipStream_t s) {
+    bool prepare(const PredictModel<float> &m, const float *sv, const float *alpha, int forms, bool /*block: an fp64 form*/, hipStream_t s) {
         const bool resident = prepare_or_decline(m, sv, alpha, forms, s);
         if (!resident) reset();
         return resident;
@@ -652,7 +654,7 @@ class ResidentF64 {
      * prepared as predict_values_impl<double> prepares it -- the same padding, centre, scale and records, so that a batch's values have the one-shot call's bits.  fp64
      * rbf has no direct form and no plane check: this form never declines a batch and keeps no host copy of the support vectors.  FORMS_PANELS: beyond 256 padded
      * features as well (wide_nonlinear_f64: the panel kernel on data padded to whole 64-feature panels, which DeviceMatrix::upload does at these widths). */
-    bool prepare(const PredictModel<double> &m, const double *sv, const double *alpha, int forms, hipStream_t s) {
+    bool prepare(const PredictModel<double> &m, const double *sv, const double *alpha, int forms, bool block, hipStream_t s) {
         const bool rbf = m.params.kernel_type == LSSVM_KERNEL_RBF;
         if (forms < FORMS_EVERY || !(rbf || m.params.kernel_type == LSSVM_KERNEL_POLYNOMIAL) || !(m.params.gamma > 0.0)) return false;
         wide_ = forms >= FORMS_PANELS && wide_nonlinear_f64(m.opt, m.params, m.nfeat);
@@ -679,6 +681,22 @@ class ResidentF64 {
         // than two single-vector launches (profiles/predictor_f64.json, launch_level: 0.46 ... 0.58 of two), so every pair is launched as a pair.  The panel kernel:
         // where panel_pair_routed says so; elsewhere every vector keeps the single-vector record of a launch of its own.
         const int ncols = num_jt * TILE;
+        // The block form (lssvm_mi355_predictor_create_block): the vectors sixteen at a time, per group the (alpha[64][16] | c_j) records of tile_matvec_f64_blk, a last
+        // group of fewer padded with zero vectors.  Declined -- the pair form below, as lssvm_mi355_predictor_create_resident builds it -- under gram_mode 0 and
+        // rbf_form 1 / 3 (options that ask for another evaluation of the Gram matrix than this kernel's); tile_kernel 1 and more than 256 features never get here.
+        block_ = block && !wide_ && m.opt.gram_mode != 0 && !(rbf && (m.opt.rbf_form == 1 || m.opt.rbf_form == 3));
+        if (block_) {
+            recb_ = static_cast<size_t>(num_jt) * 2 * (64 * BLOCK_VECTORS + 64);
+            const size_t groups = (m.nvec + BLOCK_VECTORS - 1) / BLOCK_VECTORS;
+            dcb_.alloc_zero(groups * recb_, s);
+            for (size_t g = 0; g < groups; ++g) {
+                const size_t v0 = g * BLOCK_VECTORS;
+                enqueue_pack_block_records(a_.p + v0 * ra, ra, static_cast<int>(std::min<size_t>(BLOCK_VECTORS, m.nvec - v0)), cS_.p, ncols, dcb_.p + g * recb_, s);
+            }
+            LSSVM_HIP_CHECK(hipGetLastError());
+            LSSVM_HIP_CHECK(hipStreamSynchronize(s));
+            return true;
+        }
         rec2_ = static_cast<size_t>(num_jt) * 2 * 192;
         rec1_ = static_cast<size_t>(num_jt) * 256;
         pairs_ = m.nvec >= 2 && (!wide_ || panel_pair_routed(LSSVM_DTYPE_F64, 0, m.params.kernel_type, m.params.degree, S_.ldx / 64));
@@ -709,8 +727,9 @@ class ResidentF64 {
         hipLaunchKernelGGL(k_center<double>, dim3((P.dfeat + 255) / 256, P.rows), dim3(256), 0, s, P.data.p, P.ldx, P.dfeat, P.rows, rbf ? mean_.p : static_cast<const double *>(nullptr), scale_);
         LSSVM_HIP_CHECK(hipGetLastError());
         if (rbf) half_neg_norms<double>(P, cP, s);
-        ProductStage<double> stage(m.opt, P, S_, false, a_.p, m.rho.data(), m.nvec, pairs_ ? 2 : 1, s, t0);
+        ProductStage<double> stage(m.opt, P, S_, false, a_.p, m.rho.data(), m.nvec, block_ ? BLOCK_VECTORS : (pairs_ ? 2 : 1), s, t0);
         const auto records = [&](int v, int count) -> const double * {
+            if (block_) return dcb_.p + static_cast<size_t>(v / BLOCK_VECTORS) * recb_;
             // (alone: the vector no pair holds -- or, where pairs are not dispatched, every vector)
             return count == 2 ? dc2_.p + static_cast<size_t>(v / 2) * rec2_ : dc_.p + (static_cast<size_t>(v) - single_first_) * rec1_;
         };
@@ -726,11 +745,13 @@ class ResidentF64 {
     DeviceMatrix<double> S_;
     DevBuf<double> mean_, cS_, a_;
     DevBuf<double> dc_, dc2_;  // column records: [num_jt][256] of the vector no pair holds (every vector's where pairs are not dispatched), [nvec / 2][rec2_] per pair
-    size_t rec2_ = 0, rec1_ = 0;
+    DevBuf<double> dcb_;       // the block form: [ceil(nvec / 16)][recb_] per group of sixteen
+    size_t rec2_ = 0, rec1_ = 0, recb_ = 0;
     size_t single_first_ = 0;  // the vector dc_ starts with (the last one; 0 where no pair launch is dispatched)
     double scale_ = 1.0;
     bool wide_ = false;   // more than 256 padded features: the panel kernel (FORMS_PANELS)
     bool pairs_ = false;  // two vectors per launch
+    bool block_ = false;  // sixteen vectors per launch (FORMS_BLOCK)
 };
 
 /* `nvec` weight vectors over the same support vectors (lssvm_mi355_predictor_create: one; _create_multi: a one-vs-all model's k).  The linear kernel keeps w per vector;
@@ -767,7 +788,8 @@ class Predictor final : public PredictorBase {
             LSSVM_HIP_CHECK(hipStreamSynchronize(s));
             return;
         }
-        resident_ = resident_form_.prepare(m_, sv, alpha, forms, s);
+        // (FORMS_BLOCK is FORMS_EVERY in everything but the fp64 form's launch groups)
+        resident_ = resident_form_.prepare(m_, sv, alpha, forms == FORMS_BLOCK ? FORMS_EVERY : forms, forms == FORMS_BLOCK, s);
         // the one-shot path's inputs: host copies where nothing is resident; a resident model that may decline a batch keeps alpha, leaves its support vectors as they
         // came in HBM and fetches them if a batch ever asks
         if (!resident_ || Resident::declines_batches) alpha_host_.assign(alpha, alpha + nvec * nsv);

@@ -948,8 +948,9 @@ struct PredictorBase {
     virtual void predict(const void *points, int mem_kind, size_t npoints, void *out, lssvm_predict_info *info, bool multi) = 0;
 };
 /* which resident forms a predictor may take: those of _create / _create_multi; FORMS_EVERY (lssvm_mi355_predictor_create_resident): every form on the one-pass kernels,
- * the fp64 one as well; FORMS_PANELS (lssvm_mi355_predictor_create_panels): those, and the models beyond the one-pass kernels on the panel kernels */
-constexpr int FORMS_DEFAULT = 0, FORMS_EVERY = 1, FORMS_PANELS = 2;
+ * the fp64 one as well; FORMS_PANELS (lssvm_mi355_predictor_create_panels): those, and the models beyond the one-pass kernels on the panel kernels; FORMS_BLOCK
+ * (lssvm_mi355_predictor_create_block): FORMS_EVERY, with the fp64 form's weight vectors taken sixteen per pass (tile_matvec_f64_blk) where that kernel applies */
+constexpr int FORMS_DEFAULT = 0, FORMS_EVERY = 1, FORMS_PANELS = 2, FORMS_BLOCK = 3;
 /* alpha [nvec][nsv], rho [nvec] */
 std::unique_ptr<PredictorBase> make_predictor(const Options &opt, const lssvm_params &params, int dtype, const void *sv, size_t nsv, size_t nfeat, const void *alpha, const double *rho,
                                               size_t nvec, int forms = FORMS_DEFAULT);
@@ -1031,6 +1032,9 @@ void enqueue_pack_records(const double *dvec, const double *cc, int ncols_padded
 void enqueue_pack_records2(const float *dvec0, const float *dvec1, const float *cc, int ncols_padded, float *dc, int folded, hipStream_t s);
 /* ... and for the fp64 v2 kernel's NV = 2 instance: (d0 | d1 | c), 192 reals per 64-column sub-tile (k_pack_dc2_f64, nothing cleared) */
 void enqueue_pack_records2(const double *dvec0, const double *dvec1, const double *cc, int ncols_padded, double *dc, hipStream_t s);
+/* ... and for the sixteen-vector fp64 kernel (tile_matvec_f64_blk; tile_launch_f64blk.hip): (alpha[64 columns][16 vectors] | c), 1088 reals per sub-tile, from the
+ * `count` (1 ... 16) vectors alpha[v][ld]; the vector slots beyond `count` are written as exact zeros (k_pack_ablock_f64) */
+void enqueue_pack_block_records(const double *alpha, size_t ld, int count, const double *cc, int ncols_padded, double *dc, hipStream_t s);
 void enqueue_planes_fragment_major(const uint16_t *planes, size_t plane_elems, int rows_alloc, int ldx16, int nplanes, uint16_t *frag, hipStream_t s);
 
 }  // namespace lssvm

@@ -76,5 +76,8 @@ void launch_nv2_sym_panel_tile_kernel_f64(const TileArgs<double> &a, int kernel_
 void launch_v2d_sym2(const TileArgs<double> &a, int kernel_type, hipStream_t s);
 /* ... and its full-square counterpart (tile_launch_f64_full2a.hip / _full2b.hip; TileArgs::items == nullptr): rbf and polynomial, `grid` from finish_mapping */
 void launch_v2d_full2(const TileArgs<double> &a, int kernel_type, dim3 grid, hipStream_t s);
+/* the fp64 full-square kernel with SIXTEEN vectors per pass, the second product on the matrix cores (tile_launch_f64blk_a.hip / _b.hip; TileArgs::nvec == BLOCK_VECTORS,
+ * records from enqueue_pack_block_records, sixteen planes of `partial`; reached through launch_tile_kernel<double>): rbf and polynomial */
+void launch_v2d_block(const TileArgs<double> &a, int kernel_type, dim3 grid, hipStream_t s);
 
 }  // namespace lssvm
