@@ -453,6 +453,21 @@ int lssvm_mi355_problem_matvec_pair_panels(lssvm_mi355_problem *p, const void *d
 int lssvm_mi355_problem_solve_lockstep_panels(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out /* num_rhs x N */,
                                               double *rhos_out, lssvm_cg_info *infos_out /* num_rhs, may be NULL */, uint64_t passes_out[2]);
 
+/* BLOCK forms (opt-in, routed by no default): SIXTEEN vectors per pass over the symmetric Gram triangle, both products of a tile on the matrix cores
+ * (tile_matvec_f64_blk_sym) -- fp64, one device, symmetric = 1, rbf or polynomial with degree >= 0, at most 256 features, gram_mode != 0,
+ * tile_kernel != 1, rbf_form 0 or 2.
+ *   _matvec_block: lssvm_mi355_problem_matvec for nv >= 1 vectors, D and Ret_inout nv x (N-1) row-major: ret_u[0..N-1) += add * Abar * d_u, the vectors taken in groups of
+ *   sixteen, one pass per group (a last group of fewer included).  A vector's result does not depend on nv, on its place or on the other vectors; it differs from
+ *   lssvm_mi355_problem_matvec's in the last bits (another, equally fixed, order of the sums).  *block_out (may be NULL) = 1 where the block passes ran.
+ *   _solve_lockstep_block: lssvm_mi355_problem_solve_lockstep with the active right-hand sides grouped afresh in sixteens in every step, and EVERY Gram pass a block
+ *   pass, a group of one or two included -- so row c of the results has the bits of the call with right-hand side c alone (not those of the one-shot solve: iteration
+ *   counts may differ by the last bits' worth).  matvec_launches of infos_out[c] is 1 + it + it / 50.  passes_out[3] (may be NULL): block, two-vector, single-vector passes.
+ * Where the block kernel does not apply (fp32, the linear kernel, more than 256 features, several devices or ranks, symmetric = 0, a negative degree, the options above)
+ * the calls ARE lssvm_mi355_problem_matvec_pair_panels (pair by pair) / _solve_lockstep_panels: their bits and infos, *block_out = 0, passes_out[0] = 0. */
+int lssvm_mi355_problem_matvec_block(lssvm_mi355_problem *p, const void *D /* nv x (N-1) */, size_t nv, void *Ret_inout /* nv x (N-1) */, double add, int *block_out);
+int lssvm_mi355_problem_solve_lockstep_block(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out /* num_rhs x N */,
+                                             double *rhos_out, lssvm_cg_info *infos_out /* num_rhs, may be NULL */, uint64_t passes_out[3]);
+
 /* COST PATH (no counterpart in the reference): the solutions of ONE right-hand side for EVERY cost of a grid from one multi-shift CG sequence -- one pass over the
  * Gram tiles per iteration for the whole grid instead of one per cost, as many iterations as the hardest (largest) cost alone needs.  For fixed data and kernel
  * function the cost enters the reduced system only as a shift: Abar(C) = A0 + sigma M with sigma = 1 / C, A0 v = K v + (k_NN S - q.v) 1 - S q (S = sum v) and

@@ -1109,6 +1109,52 @@ void Problem<T>::enqueue_apply_K_lanes(const T *v0, T *Kv0, const T *v1, T *Kv1,
     LSSVM_HIP_CHECK(hipGetLastError());
 }
 
+/* ------------------------------------------------------------------ sixteen vectors per symmetric pass ------------------------------------------------------------------ */
+template <typename T>
+bool Problem<T>::block_kernel_applies() const {
+    if constexpr (std::is_same_v<T, double>) {
+        const bool poly = tile_params_.kernel_type == LSSVM_KERNEL_POLYNOMIAL && tile_params_.degree >= 0 && poly_prescaled_;
+        const bool rbf = tile_params_.kernel_type == LSSVM_KERNEL_RBF && !rbf_direct_ && (opt_.rbf_form == 0 || opt_.rbf_form == 2);
+        return world_ == 1 && sym_ && dc_.p != nullptr && !wide_nl_ && !wide_linear_ && num_ib_ > 0 && (poly || rbf) && X_.ldx <= F64_ONE_PASS_FEATURES && opt_.gram_mode != 0
+               && opt_.tile_kernel != 1;
+    } else {
+        return false;
+    }
+}
+
+template <typename T>
+void Problem<T>::enqueue_apply_K_block(const T *const *v, T *const *Kv, int nv, hipEvent_t ev_begin, hipEvent_t ev_end) {
+    LSSVM_REQUIRE(block_kernel_applies(), "no sixteen-vector tile kernel on this problem");
+    LSSVM_REQUIRE(nv >= 1 && nv <= BLOCK_VECTORS, "a block pass takes 1 ... 16 vectors");
+    if constexpr (std::is_same_v<T, double>) {
+        hipStream_t st = stream_.s;
+        if (block_dc_.p == nullptr) {
+            // the bands are the single pass's (colslab_band_mb is the budget of ONE plane): sixteen planes of either slab
+            block_dc_.alloc_zero(static_cast<size_t>(num_tiles_) * 2 * (64 * BLOCK_VECTORS + 64), st);
+            block_partial_.alloc_zero(BLOCK_VECTORS * partial_.count, st);
+            block_colslab_.alloc_zero(BLOCK_VECTORS * colslab_.count, st);
+        }
+        // the records of the group, exact zeros in the slots beyond nv; the same launch clears the results (the symmetric variant ADDS rows and mirrored columns into K*v)
+        enqueue_pack_block_sym_records(v, Kv, nv, c_.p, num_tiles_ * TILE, block_dc_.p, static_cast<int>(nvec_), st);
+        TileArgs<T> a = tile_args(v[0]);
+        a.nvec = BLOCK_VECTORS;
+        a.dc = block_dc_.p;
+        a.partial = block_partial_.p;
+        a.part_vstride = static_cast<long>(partial_.count);
+        a.colslab = block_colslab_.p;
+        a.colslab_vstride = static_cast<long>(colslab_.count);
+        if (ev_begin != nullptr) LSSVM_HIP_CHECK(hipEventRecord(ev_begin, st));
+        // every reduction runs per vector on that vector's planes, into that vector's K*v; the planes of the empty slots are not read
+        enqueue_sym_walk(a, nv, Kv, 1, [&](auto &&launch, bool, bool last) {
+            launch();
+            if (last && ev_end != nullptr) LSSVM_HIP_CHECK(hipEventRecord(ev_end, st));
+        });
+        LSSVM_HIP_CHECK(hipGetLastError());
+    } else {
+        (void) v; (void) Kv; (void) ev_begin; (void) ev_end;
+    }
+}
+
 /* Weighted LS-SVM: Abar(w)_ij = k(x_i,x_j) + delta_ij / (C w_i) + QA_cost(w) - q_i - q_j with QA_cost(w) = k(x_last,x_last) + 1 / (C w_last).  Every diagonal term is
  * formed as inv_cost_ is, in the real type -- so w = 1 gives today's bits, and w = 2 those of the unweighted system at cost 2C (T(C) * T(2) is exact). */
 template <typename T>

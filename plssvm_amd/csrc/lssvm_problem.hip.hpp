@@ -425,6 +425,12 @@ class Problem {
      * today's single-vector pass.  Each result has the bits enqueue_apply_K_local gives for that vector: both are enqueue_sym_walk on the arguments of that vector.
      * `ev`: HIP events around the tile-kernel launches (before the first band's, after the last band's), or NULL. */
     void enqueue_apply_K_lanes(const T *v0, T *Kv0, const T *v1, T *Kv1, hipEvent_t ev_begin, hipEvent_t ev_end);
+    /* where one Gram pass can serve SIXTEEN vectors (tile_matvec_f64_blk_sym): fp64 on one device, the symmetric variant with its records, rbf or
+     * polynomial with a degree >= 0 on at most 256 features, gram_mode != 0, tile_kernel != 1, rbf_form 0 or 2.  Opt-in: asked only by the _block entry points. */
+    bool block_kernel_applies() const;
+    /* Kv[u] <- K * v[u], u < nv (1 ... 16), from ONE pass of the sixteen-vector kernel through enqueue_sym_walk (block_kernel_applies).  A vector's result does not depend
+     * on nv, on its slot or on the other vectors.  `ev`: as enqueue_apply_K_lanes'. */
+    void enqueue_apply_K_block(const T *const *v, T *const *Kv, int nv, hipEvent_t ev_begin, hipEvent_t ev_end);
 
   private:
     friend class Solver<T>;
@@ -486,6 +492,7 @@ class Problem {
     DevBuf<T> partial_;
     DevBuf<T> dc_;  // v2 kernels: packed (d_j | c_j) records
     std::vector<std::unique_ptr<CgState<T>>> lanes_;
+    DevBuf<T> block_dc_, block_partial_, block_colslab_;  // sixteen-vector passes: k_pack_vblock_f64's records, sixteen planes of the row slabs / the column slab (16 x the single pass's)
     DevBuf<T> pair_dc_, pair_partial_, pair_colslab_;  // two-vector passes: (d0_j | d1_j | c_j) records (fp32: k_pack_dc2_sym's), and both vectors' planes of the row slabs / the column slab
     bool d_packed_ = false;  // dc_ holds the records of own_.d and K*v is cleared: k_update_d left them (pack_for_d), the next implicit matvec of that d launches no k_pack_dc
     // symmetric variant
@@ -621,6 +628,10 @@ struct ProblemBase {
     virtual void matvec_pair(const void *d0, const void *d1, void *ret0_inout, void *ret1_inout, double add, int *two_vector_out, bool panels = false) = 0;  // lssvm_mi355_problem_matvec_pair
     virtual void solve_lockstep(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out,
                                 uint64_t *passes_out, bool panels = false) = 0;  // lssvm_mi355_problem_solve_lockstep
+    /* the _block entry points: sixteen vectors per Gram pass where Problem<T>::block_kernel_applies, the _panels calls elsewhere; passes_out[3]: block, pair, single */
+    virtual void matvec_block(const void *D, size_t nv, void *Ret_inout, double add, int *block_out) = 0;  // lssvm_mi355_problem_matvec_block
+    virtual void solve_lockstep_block(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out,
+                                      uint64_t *passes_out) = 0;  // lssvm_mi355_problem_solve_lockstep_block
     virtual void solve_cost_path(const void *y, const double *costs, size_t num_costs, double eps, uint64_t max_iter, bool verify, void *alphas_out, double *rhos_out,
                                  lssvm_path_info *infos_out, uint64_t *passes_out) = 0;  // lssvm_mi355_problem_solve_cost_path
     /* the Nystrom preconditioner and PCG on it (lssvm_precond.hip) */
@@ -757,6 +768,8 @@ class Solver final : public ProblemBase {
     void matvec_pair(const void *d0, const void *d1, void *ret0_inout, void *ret1_inout, double add, int *two_vector_out, bool panels = false) override;
     void solve_lockstep(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out,
                         bool panels = false) override;
+    void matvec_block(const void *D, size_t nv, void *Ret_inout, double add, int *block_out) override;
+    void solve_lockstep_block(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out) override;
     /* every cost of a grid from ONE multi-shift CG sequence on this problem's single-vector pass (lssvm_path.hip) */
     void solve_cost_path(const void *y, const double *costs, size_t num_costs, double eps, uint64_t max_iter, bool verify, void *alphas_out, double *rhos_out, lssvm_path_info *infos_out,
                          uint64_t *passes_out) override;
@@ -820,6 +833,7 @@ class Solver final : public ProblemBase {
 
     /* for a driver that runs on lanes of shard 0 (the lockstep solve here, the refinement in lssvm_refine.hip) */
     Problem<T> &shard0() { return *shards_[0]; }
+    bool block_applies() const;  // ... where the sixteen-vector kernel applies (Problem<T>::block_kernel_applies)
     bool lanes_apply(bool panels = false) const;  // one unsharded device without an exchange, where the two-vector kernel applies (`panels`: or the two-vector panel kernel)
     void wait_for_deltas();    // the host waits for what shard 0's stream holds: the deltas of the step are in their host words
     /* until the returned object goes: no other solve may begin on this handle, and its weights stay */
@@ -839,7 +853,8 @@ class Solver final : public ProblemBase {
     void reset_cg(double eps, double y_last);  // cg_begin, cg_begin_from_zero: the host's counters and scalars of a new solve
     void read_delta0(double t0);               // ... and their end: delta0 is read, the handle is between begin and finish
     void solve_in_sequence(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out);
-    void solve_on_lanes(const T *Y, size_t num_rhs, double eps, uint64_t max_iter, T *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out);
+    /* `block`: the active lanes grouped in sixteens, every Gram pass a pass of the sixteen-vector kernel (passes_out[2] then counts them, [0] and [1] stay 0) */
+    void solve_on_lanes(const T *Y, size_t num_rhs, double eps, uint64_t max_iter, T *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out, bool block = false);
     Problem<T> &precond_problem(const char *what);                        // the checks every preconditioner entry point shares; shard 0
     void enqueue_precond_apply(const T *r, T *z, double *part_rz) const;  // z = r - Bhat G^-1 Bhat^T r and the partial sums of r.z
     Problem<T> &reduced_problem(const char *what, bool unweighted_only);  // the checks every entry point of the fixed-size model shares; shard 0 (lssvm_reduced.hip)
@@ -1035,6 +1050,9 @@ void enqueue_pack_records2(const double *dvec0, const double *dvec1, const doubl
 /* ... and for the sixteen-vector fp64 kernel (tile_matvec_f64_blk; tile_launch_f64blk.hip): (alpha[64 columns][16 vectors] | c), 1088 reals per sub-tile, from the
  * `count` (1 ... 16) vectors alpha[v][ld]; the vector slots beyond `count` are written as exact zeros (k_pack_ablock_f64) */
 void enqueue_pack_block_records(const double *alpha, size_t ld, int count, const double *cc, int ncols_padded, double *dc, hipStream_t s);
+/* ... and for the sixteen-vector SYMMETRIC fp64 kernel (tile_matvec_f64_blk_sym; tile_launch_f64blks.hip): the same records from `count` vectors in buffers of their own;
+ * the launch also clears the first `nzero` entries of Kv[u], u < count (k_pack_vblock_f64) */
+void enqueue_pack_block_sym_records(const double *const *v, double *const *Kv, int count, const double *cc, int ncols_padded, double *dc, int nzero, hipStream_t s);
 void enqueue_planes_fragment_major(const uint16_t *planes, size_t plane_elems, int rows_alloc, int ldx16, int nplanes, uint16_t *frag, hipStream_t s);
 
 }  // namespace lssvm

@@ -621,7 +621,7 @@ void Solver<T>::solve_in_sequence(const void *Y, size_t num_rhs, double eps, uin
  * recurrence has the bits of the one-shot solve -- all lanes advancing one iteration per step.  In every step the lanes still active are paired afresh for the
  * implicit matvec: ceil(active / 2) Gram passes, an odd lane taking the single-vector pass.  The host waits for the step's deltas before it enqueues the next step. */
 template <typename T>
-void Solver<T>::solve_on_lanes(const T *Y, size_t num_rhs, double eps, uint64_t max_iter, T *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out) {
+void Solver<T>::solve_on_lanes(const T *Y, size_t num_rhs, double eps, uint64_t max_iter, T *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out, bool block) {
     const double t_call = now_ms();
     Problem<T> &p = *shards_[0];
     p.activate();
@@ -638,13 +638,14 @@ void Solver<T>::solve_on_lanes(const T *Y, size_t num_rhs, double eps, uint64_t 
     for (size_t c = 0; c < num_rhs; ++c) state[c].lane = &p.lane(c);
     std::vector<size_t> active(num_rhs);
     for (size_t c = 0; c < num_rhs; ++c) active[c] = c;
-    uint64_t passes[2] = { 0, 0 };
+    uint64_t passes[3] = { 0, 0, 0 };  // two-vector, single-vector, sixteen-vector passes
 
     // one Gram pass per pair of active lanes (`x`: of their x, else of their d) into their K*v; HIP events around every pass, read back after the step's wait
     struct Timed {
         Event a, b;
         size_t lane0 = 0, lane1 = 0;
         bool two = false;
+        size_t group = 0;  // block mode: the pass served active[lane0 .. lane0 + group)
     };
     std::vector<Timed> timers(2 * ((num_rhs + 1) / 2));  // (a step with a residual refresh makes two rounds of passes before its wait)
     for (Timed &t : timers) {
@@ -653,6 +654,26 @@ void Solver<T>::solve_on_lanes(const T *Y, size_t num_rhs, double eps, uint64_t 
     }
     size_t timers_used = 0;
     const auto apply_K = [&](bool x) {
+        if (block) {
+            // EVERY pass is a pass of the sixteen-vector kernel, a group of one or two included: a lane's bits then do not depend on when its partners converge
+            for (size_t k = 0; k < active.size(); k += BLOCK_VECTORS) {
+                const size_t g = std::min<size_t>(BLOCK_VECTORS, active.size() - k);
+                const T *v[BLOCK_VECTORS];
+                T *Kv[BLOCK_VECTORS];
+                for (size_t u = 0; u < g; ++u) {
+                    State &s = state[active[k + u]];
+                    v[u] = x ? s.lane->x.p : s.lane->d.p;
+                    Kv[u] = s.lane->Kv.p;
+                    ++s.matvecs;
+                }
+                Timed &t = timers[timers_used++];
+                t.lane0 = k;
+                t.group = g;
+                p.enqueue_apply_K_block(v, Kv, static_cast<int>(g), t.a.e, t.b.e);
+                ++passes[2];
+            }
+            return;
+        }
         for (size_t k = 0; k < active.size(); k += 2) {
             State &s0 = state[active[k]];
             State *s1 = k + 1 < active.size() ? &state[active[k + 1]] : nullptr;
@@ -670,6 +691,14 @@ void Solver<T>::solve_on_lanes(const T *Y, size_t num_rhs, double eps, uint64_t 
         for (size_t k = 0; k < timers_used; ++k) {
             float ms = 0.0f;
             if (hipEventElapsedTime(&ms, timers[k].a.e, timers[k].b.e) != hipSuccess) continue;
+            if (block) {  // (read before the step's stop tests re-form `active`)
+                for (size_t u = 0; u < timers[k].group; ++u) {
+                    State &s = state[active[timers[k].lane0 + u]];
+                    s.kernel_ms += ms;
+                    ++s.timed;
+                }
+                continue;
+            }
             for (int u = 0; u < (timers[k].two ? 2 : 1); ++u) {
                 State &s = state[u == 0 ? timers[k].lane0 : timers[k].lane1];
                 s.kernel_ms += ms;
@@ -739,9 +768,81 @@ void Solver<T>::solve_on_lanes(const T *Y, size_t num_rhs, double eps, uint64_t 
         active.swap(staying);
     }
     if (passes_out != nullptr) {
-        passes_out[0] = passes[0];
-        passes_out[1] = passes[1];
+        passes_out[0] = block ? passes[2] : passes[0];  // (solve_lockstep_block hands out block | pair | single)
+        passes_out[1] = block ? 0 : passes[1];
+        if (block) passes_out[2] = 0;
     }
+}
+
+/* ------------------------------------------------------------------ sixteen vectors per Gram pass: matvec_block, the block lockstep CG ------------------------------------------------------------------ */
+template <typename T>
+bool Solver<T>::block_applies() const {
+    return shards_.size() == 1 && world_ == 1 && exchange_ == Exchange::none && shards_[0]->block_kernel_applies();
+}
+
+template <typename T>
+void Solver<T>::matvec_block(const void *D, size_t nv, void *Ret_inout, double add, int *block_out) {
+    LSSVM_REQUIRE(D != nullptr && Ret_inout != nullptr, "The d / ret arrays may not be empty!");  // csvm.cpp:284-286
+    LSSVM_REQUIRE(nv > 0, "The number of vectors must be greater than 0!");
+    LSSVM_REQUIRE(add == 1.0 || add == -1.0, "add must either be -1.0 or 1.0, but is " + std::to_string(add) + "!");  // svm_kernel.cpp:28
+    LSSVM_REQUIRE(!in_cg_, "matvec_block cannot run between cg_begin and cg_finish");
+    if (block_out != nullptr) *block_out = 0;
+    const size_t n = static_cast<size_t>(shards_[0]->n_);
+    const T *d = static_cast<const T *>(D);
+    T *ret = static_cast<T *>(Ret_inout);
+    if (!block_applies()) {  // what lssvm_mi355_problem_matvec_pair_panels does, pair by pair
+        size_t c = 0;
+        for (; c + 1 < nv; c += 2) matvec_pair(d + c * n, d + (c + 1) * n, ret + c * n, ret + (c + 1) * n, add, nullptr, true);
+        if (c < nv) matvec(d + c * n, ret + c * n, add);
+        return;
+    }
+    // the statements of matvec() per vector on up to sixteen lanes (d <- d_u zero padded, Ad <- ret_u), around ONE pass of the sixteen-vector kernel per group
+    Problem<T> &p = *shards_[0];
+    const CgSteps<T> cg(p);
+    const size_t bytes = n * sizeof(T);
+    for (size_t c0 = 0; c0 < nv; c0 += BLOCK_VECTORS) {
+        const size_t g = std::min<size_t>(BLOCK_VECTORS, nv - c0);
+        const CgState<T> *lane[BLOCK_VECTORS];
+        const T *v[BLOCK_VECTORS];
+        T *Kv[BLOCK_VECTORS];
+        for (size_t u = 0; u < g; ++u) {
+            lane[u] = &p.lane(u);
+            LSSVM_HIP_CHECK(hipMemcpyAsync(lane[u]->d.p, d + (c0 + u) * n, bytes, hipMemcpyHostToDevice, p.stream()));
+            LSSVM_HIP_CHECK(hipMemcpyAsync(lane[u]->Ad.p, ret + (c0 + u) * n, bytes, hipMemcpyHostToDevice, p.stream()));
+            cg.sum_and_qdot(*lane[u], lane[u]->d.p, SC_S, SC_QD);
+            v[u] = lane[u]->d.p;
+            Kv[u] = lane[u]->Kv.p;
+        }
+        p.enqueue_apply_K_block(v, Kv, static_cast<int>(g), nullptr, nullptr);
+        for (size_t u = 0; u < g; ++u) {
+            cg.apply_ret(*lane[u], lane[u]->Kv.p, lane[u]->d.p, add);
+            LSSVM_HIP_CHECK(hipMemcpyAsync(ret + (c0 + u) * n, lane[u]->Ad.p, bytes, hipMemcpyDeviceToHost, p.stream()));
+        }
+        sync_all();  // (the lanes are re-used by the next group, and the host's memory by the caller)
+    }
+    if (block_out != nullptr) *block_out = 1;
+}
+
+template <typename T>
+void Solver<T>::solve_lockstep_block(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out) {
+    if (!block_applies()) {  // the call IS lssvm_mi355_problem_solve_lockstep_panels: its bits, its infos, its (pair | single) counts behind a zero
+        uint64_t two[2] = { 0, 0 };
+        solve_lockstep(Y, num_rhs, eps, max_iter, alphas_out, rhos_out, infos_out, two, true);
+        if (passes_out != nullptr) {
+            passes_out[0] = 0;
+            passes_out[1] = two[0];
+            passes_out[2] = two[1];
+        }
+        return;
+    }
+    LSSVM_REQUIRE(Y != nullptr, "The right hand side vector must not be empty!");
+    LSSVM_REQUIRE(num_rhs > 0, "The number of right hand sides must be greater than 0!");
+    LSSVM_REQUIRE(static_cast<T>(eps) > T(0), "The stopping criterion in the CG algorithm must be greater than 0.0, but is " + std::to_string(eps) + "!");  // csvm.cpp:77
+    LSSVM_REQUIRE(max_iter > 0, "The number of CG iterations must be greater than 0!");                                                                   // csvm.cpp:78
+    LSSVM_REQUIRE(alphas_out != nullptr && rhos_out != nullptr, "alpha_out / rho_out must not be NULL");
+    LSSVM_REQUIRE(!in_cg_, "solve_lockstep_block cannot run between cg_begin and cg_finish");
+    if (passes_out != nullptr) passes_out[0] = passes_out[1] = passes_out[2] = 0;
+    solve_on_lanes(static_cast<const T *>(Y), num_rhs, eps, max_iter, static_cast<T *>(alphas_out), rhos_out, infos_out, passes_out, true);
 }
 
 template <typename T>

@@ -177,7 +177,9 @@ void launch_tile_kernel<double>(TileArgs<double> &a, int kernel_type, bool /*rbf
         return;
     }
     if (a.dc != nullptr) {  // the records exist only where the v2 kernel was chosen when the data was prepared; V2D_LDS_BYTES < 64 KiB
-        if (a.nvec == BLOCK_VECTORS) {  // sixteen vectors per full-square pass (the block form of the resident Predictor<double>)
+        if (a.nvec == BLOCK_VECTORS && a.items != nullptr) {  // sixteen vectors per symmetric pass (Problem<double>::enqueue_apply_K_block)
+            launch_v2d_block_sym(a, kernel_type, s);
+        } else if (a.nvec == BLOCK_VECTORS) {  // sixteen vectors per full-square pass (the block form of the resident Predictor<double>)
             launch_v2d_block(a, kernel_type, grid, s);
         } else if (a.nvec == 2) {  // two vectors per pass: the symmetric variant (Problem<double>::enqueue_apply_K_lanes), the full square (the resident Predictor<double>)
             if (a.items == nullptr) {

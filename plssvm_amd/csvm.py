@@ -471,7 +471,7 @@ class MI355CSVM(CSVM):
     """The MI355X backend (counterpart of plssvm::hip::csvm, HIP/csvm.hpp:39-99, csvm.hip.cpp:47-85)."""
 
     def __init__(self, target=TargetPlatform.AUTOMATIC, params: Parameter | None = None, num_devices: int = 1, solver: str = "cg", precond_rank: int = 256, precond_landmarks=None,
-                 **kwargs):
+                 lockstep: str = "pair", **kwargs):
         """``solver``: ``"cg"`` (default) = the CG of the data's real type; ``"refined"`` = float64 data on ONE device is solved by mixed-precision refinement
         (``backend.solve_refined``: float32 CG iterations on the matrix cores inside a float64 residual loop, same stop test; the gain grows with the iteration
         count) and ``last_refine_info`` keeps the per-solve reports -- float32 data or several devices solve as with ``"cg"`` and leave it None;
@@ -479,6 +479,10 @@ class MI355CSVM(CSVM):
         data set and shared by all right-hand sides -- opt-in: it saves iterations where the kernel matrix has spectral decay and costs some where it has none; one device
         and no sample weights (both raise).  ``precond_landmarks``: None = the library's fixed choice of landmarks, ``"greedy"`` / ``"rpcholesky"`` = ``precond_rank`` points
         selected from the data (``backend.select_landmarks``).
+        ``lockstep``: how :meth:`solve_systems_of_linear_equations` takes several right-hand sides through a Gram pass on one device -- ``"pair"`` (default) = two per pass
+        (``ResidentProblem.solve_lockstep``), ``"block"`` = sixteen per pass on the matrix cores (``ResidentProblem.solve_lockstep_block``) where
+        that kernel applies (float64, rbf / polynomial, at most 256 features) and ``"pair"`` elsewhere.  Opt-in: a column's bits are those of the block call with that
+        right-hand side alone, not those of the one-shot solve.  ``last_lockstep_passes`` keeps ``(block, two-vector, single-vector)`` Gram passes of the last such call.
 
         ``num_devices``: devices ONE solve is sharded over -- 1 (default) = device 0 only, k = devices 0 .. k-1 (gpu_csvm.hpp:283-299),
         0 = automatic (every visible device, at least 4096 points each, as the reference's backends take every device they find,
@@ -490,6 +494,8 @@ class MI355CSVM(CSVM):
             raise InvalidParameterError(f"solver must be 'cg' or 'refined' or 'pcg', but is {solver!r}!")
         if solver == "pcg" and not (isinstance(precond_rank, (int, np.integer)) and 1 <= int(precond_rank) <= _capi.PRECOND_MAX_RANK):
             raise InvalidParameterError(f"precond_rank must lie in [1, {_capi.PRECOND_MAX_RANK}], but is {precond_rank!r}!")
+        if lockstep not in ("pair", "block"):
+            raise InvalidParameterError(f"lockstep must be 'pair' or 'block', but is {lockstep!r}!")
         if precond_landmarks is not None and precond_landmarks not in _capi.LANDMARK_METHODS:
             raise InvalidParameterError(f"precond_landmarks must be None or one of {sorted(_capi.LANDMARK_METHODS)}, but is {precond_landmarks!r}!")
         super().__init__(params, **kwargs)
@@ -497,6 +503,8 @@ class MI355CSVM(CSVM):
         self.precond_rank = int(precond_rank) if solver == "pcg" else None
         self.precond_landmarks = precond_landmarks if solver == "pcg" else None
         self.last_refine_info = None
+        self.lockstep = lockstep
+        self.last_lockstep_passes = None
         if target not in (TargetPlatform.AUTOMATIC, TargetPlatform.GPU_AMD):
             raise BackendError(f"Invalid target platform '{target.value}' for the MI355 backend!")
         self.target_platform = TargetPlatform.GPU_AMD
@@ -662,7 +670,12 @@ class MI355CSVM(CSVM):
         with backend.ResidentProblem(params, A, devices=[0], options=self._options) as prob:  # (device 0 alone, as the one-shot solve creates it)
             if sample_weight is not None:
                 prob.set_weights(sample_weight)
-            alphas, rhos, infos, _ = prob.solve_lockstep(B, eps, max_iter, panels=True)  # (one device: option rebalance_after has nothing to move)
+            if self.lockstep == "block":
+                alphas, rhos, infos, passes = prob.solve_lockstep_block(B, eps, max_iter)
+            else:
+                alphas, rhos, infos, two = prob.solve_lockstep(B, eps, max_iter, panels=True)  # (one device: option rebalance_after has nothing to move)
+                passes = (0,) + tuple(two)
+            self.last_lockstep_passes = passes
         return alphas, rhos, infos
 
     def predict_values_multi(self, params, support_vectors, alphas, rhos, ws, predict_points):
