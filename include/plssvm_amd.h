@@ -333,6 +333,23 @@ int lssvm_mi355_predictor_create_panels(lssvm_mi355_predictor **out, const lssvm
 int lssvm_mi355_predictor_create_block(lssvm_mi355_predictor **out, const lssvm_params *params, int dtype, const void *support_vectors, size_t num_support_vectors,
                                        size_t num_features, const void *alphas, const double *rhos, size_t num_vectors, const lssvm_mi355_options *options);
 
+/* The `create_block` handle once more, with the FP32 form's weight vectors taken sixteen per pass as well: the kernel values of a 16 x 16 block stay in the registers
+ * v_mfma_f32_16x16x32_{f16,bf16} left them in and are the A operand of a second product, v_mfma_f32_16x16x4_f32, against a 64 x 16 block of weights
+ * (tile_matvec_f32_blk) -- in true fp32.  Opt-in; no other entry point routes here.  Arguments, their validation and the error texts are those
+ * of `create_block`, refused before a device is touched; `predict`, `predict_multi` and `destroy` work on the handle as on any other.
+ * The block form: dtype LSSVM_DTYPE_F32, a split Gram mode, at most 128 padded features, the polynomial kernel with degree >= 0 or rbf whose support vectors lie within
+ * the folded form's range (option rbf_fold != 0).  The model is resident as `create_resident` keeps it, plus the packed records of every group of sixteen vectors (a last
+ * group of fewer padded with zero vectors).  Every batch, whatever its size, runs on the 128-row kernel.  lssvm_predict_info: resident == 1, vectors_per_launch == 16.
+ * Values: each kernel value is produced by the single-vector kernel's own chain of operations; the sum over the columns is taken four columns at a time by the matrix
+ * cores -- NOT the pair form's bits; the difference is a few eps of the summand scale sum_j |alpha_j k_ij| (tests/test_gpu_predictor_block32.py).  The order of every
+ * sum depends on the shapes only: a call repeats bit for bit, and a column has the bits of its vector alone in any slot and any group size.
+ * dtype LSSVM_DTYPE_F64: the call IS `create_block`.  Every other fp32 model -- the linear kernel, more than 128 padded features, gram_mode = 0, tile_kernel = 1,
+ * rbf_form = 1 / 3, rbf_fold = 0 or an exponent scale beyond the folded form, a negative degree -- : the call IS `create_resident`, its handle, bits and info.  A batch
+ * the resident fp32 form declines or evaluates unfolded takes the path, bits and info it takes under `create_resident`.
+ * Where it pays and where it LOSES (one or two vectors; few features): README, "Sixteen fp32 decision functions per pass", profiles/predictor_block_f32.json. */
+int lssvm_mi355_predictor_create_block32(lssvm_mi355_predictor **out, const lssvm_params *params, int dtype, const void *support_vectors, size_t num_support_vectors,
+                                         size_t num_features, const void *alphas, const double *rhos, size_t num_vectors, const lssvm_mi355_options *options);
+
 /* ------------------------------------------------------------------------------------------------------------------ */
 /* fine-grained entry points for kernel-level parity tests: the protected members the reference's backend tests re-export  */
 /* (tests/backends/HIP/mock_hip_csvm.hpp:22-44): generate_q, run_device_kernel, calculate_w                           */

@@ -462,9 +462,15 @@ class ResidentF32 {
   public:
     static constexpr bool declines_batches = true;  // (the one-shot path's inputs stay needed: alpha on the host, the support vectors through fetch_support_vectors)
 
-    bool prepare(const PredictModel<float> &m, const float *sv, const float *alpha, int forms, bool /*block: an fp64 form*/, hipStream_t s) {
+    /* `block32` (lssvm_mi355_predictor_create_block32): beside everything the form keeps, the records of tile_matvec_f32_blk for every group of sixteen vectors, where
+     * that kernel applies */
+    bool prepare(const PredictModel<float> &m, const float *sv, const float *alpha, int forms, bool block32, hipStream_t s) {
         const bool resident = prepare_or_decline(m, sv, alpha, forms, s);
-        if (!resident) reset();
+        if (!resident) {
+            reset();
+        } else if (block32) {
+            prepare_block(m, s);
+        }
         return resident;
     }
 
@@ -482,6 +488,28 @@ class ResidentF32 {
     void reset() {
         for (DevBuf<float> *b : { &S_.data, &mean_, &cS_, &a_, &raw_, &dc_, &dc_folded_, &dc2_ }) b->release();
         planesS_.buf.release();
+    }
+
+    /* The block form: the vectors sixteen at a time, per group the W[column / 4][16][column % 4] records of tile_matvec_f32_blk, a last group of fewer padded with zero
+     * vectors.  Where that kernel exists: at most 128 padded features, a polynomial of degree >= 0 (no pad-column rule) or rbf whose support vectors lie within the folded
+     * form's range (the kernel has no other rbf form; a BATCH beyond that range takes the pair / single-vector records like any unfolded batch).  Elsewhere nothing is
+     * added: the handle is lssvm_mi355_predictor_create_resident's. */
+    void prepare_block(const PredictModel<float> &m, hipStream_t s) {
+        const bool rbf = m.params.kernel_type == LSSVM_KERNEL_RBF;
+        const bool form_ok = rbf ? (m.opt.rbf_fold != 0 && r2_sv_ <= FOLD_MAX_R2) : (m.params.kernel_type == LSSVM_KERNEL_POLYNOMIAL && m.params.degree >= 0);
+        if (wide_ || planesS_.ldx16 > 128 || !form_ok) return;
+        const int num_jt = S_.rows_alloc / TILE;
+        const size_t ra = static_cast<size_t>(S_.rows_alloc);
+        recb_ = static_cast<size_t>(num_jt) * TILE * BLOCK_VECTORS;
+        const size_t groups = (m.nvec + BLOCK_VECTORS - 1) / BLOCK_VECTORS;
+        dcb_.alloc_zero(groups * recb_, s);
+        for (size_t g = 0; g < groups; ++g) {
+            const size_t v0 = g * BLOCK_VECTORS;
+            enqueue_pack_block_records(a_.p + v0 * ra, ra, static_cast<int>(std::min<size_t>(BLOCK_VECTORS, m.nvec - v0)), cS_.p, rbf ? 1 : 0, num_jt * TILE, dcb_.p + g * recb_, s);
+        }
+        LSSVM_HIP_CHECK(hipGetLastError());
+        LSSVM_HIP_CHECK(hipStreamSynchronize(s));
+        block_ = true;
     }
 
     /* fp32, rbf / polynomial, a split Gram mode: the support vectors' side of the product, once.  At most 128 features -- or, `every_form`, every width the one-shot
@@ -608,12 +636,16 @@ class ResidentF32 {
         const bool folded = rbf && m.opt.rbf_fold != 0 && r2 <= FOLD_MAX_R2;
         // (the rectangular 256-row kernel exists up to 128 features; wider models take the 128-row full-square kernels at every batch size, as in the one-shot call --
         // beyond the one-pass kernels the full-square panel kernel)
-        const bool rect = rect_kernel_applies(m.opt, m.params, planesS_.ldx16, folded, r2, P.rows_alloc / TILE);
+        // the block form: sixteen vectors per launch of the 128-row full-square kernel at EVERY batch size (an rbf batch beyond the folded form's range has no block
+        // kernel: the records below, as without the block form)
+        const bool block = block_ && (!rbf || folded);
+        const bool rect = !block && rect_kernel_applies(m.opt, m.params, planesS_.ldx16, folded, r2, P.rows_alloc / TILE);
         // Two weight vectors per product launch wherever a pair record exists in the form this batch needs: the rectangular 256-row kernel under its conditions, the
         // 128-row full-square kernels otherwise (polynomial of any degree, folded rbf).  Unfolded rbf keeps c_j in the record's second half: one vector per launch.
-        const int per_launch = (m.nvec >= 2 && dc2_.p != nullptr && (!rbf || folded)) ? 2 : 1;
+        const int per_launch = block ? BLOCK_VECTORS : ((m.nvec >= 2 && dc2_.p != nullptr && (!rbf || folded)) ? 2 : 1);
         ProductStage<float> stage(m.opt, P, S_, rect, a_.p, m.rho.data(), m.nvec, per_launch, s, t0);
         const auto records = [&](int v, int count) -> const float * {
+            if (block) return dcb_.p + static_cast<size_t>(v / BLOCK_VECTORS) * recb_;
             if (count == 2) return dc2_.p + static_cast<size_t>(v / 2) * rec_;
             if (folded) return dc_folded_.p + (static_cast<size_t>(v) - folded_first_) * rec_;  // (folded and alone: the vector no pair holds -- or, where pairs are not dispatched, every vector)
             return dc_.p + static_cast<size_t>(v) * rec_;
@@ -639,6 +671,9 @@ class ResidentF32 {
     DevBuf<float> dc_, dc_folded_, dc2_;  // column records: [nvec][rec_] per vector, the folded one of an unpaired last vector, [nvec / 2][rec_] per pair
     size_t rec_ = 0;
     size_t folded_first_ = 0;             // the vector dc_folded_ starts with (the last one; 0 where no pair launch is dispatched and every vector has one)
+    DevBuf<float> dcb_;                   // the block form: [ceil(nvec / 16)][recb_] per group of sixteen
+    size_t recb_ = 0;
+    bool block_ = false;                  // sixteen vectors per launch (FORMS_BLOCK32)
     PlaneSet planesS_;
     double r2_sv_ = 0.0;
     float scale_ = 1.0f;
@@ -788,8 +823,9 @@ class Predictor final : public PredictorBase {
             LSSVM_HIP_CHECK(hipStreamSynchronize(s));
             return;
         }
-        // (FORMS_BLOCK is FORMS_EVERY in everything but the fp64 form's launch groups)
-        resident_ = resident_form_.prepare(m_, sv, alpha, forms == FORMS_BLOCK ? FORMS_EVERY : forms, forms == FORMS_BLOCK, s);
+        // (FORMS_BLOCK is FORMS_EVERY in everything but the fp64 form's launch groups; FORMS_BLOCK32 is FORMS_BLOCK in everything but the fp32 form's)
+        const bool any_block = forms == FORMS_BLOCK || forms == FORMS_BLOCK32;
+        resident_ = resident_form_.prepare(m_, sv, alpha, any_block ? FORMS_EVERY : forms, std::is_same_v<T, float> ? forms == FORMS_BLOCK32 : any_block, s);
         // the one-shot path's inputs: host copies where nothing is resident; a resident model that may decline a batch keeps alpha, leaves its support vectors as they
         // came in HBM and fetches them if a batch ever asks
         if (!resident_ || Resident::declines_batches) alpha_host_.assign(alpha, alpha + nvec * nsv);

@@ -964,8 +964,9 @@ struct PredictorBase {
 };
 /* which resident forms a predictor may take: those of _create / _create_multi; FORMS_EVERY (lssvm_mi355_predictor_create_resident): every form on the one-pass kernels,
  * the fp64 one as well; FORMS_PANELS (lssvm_mi355_predictor_create_panels): those, and the models beyond the one-pass kernels on the panel kernels; FORMS_BLOCK
- * (lssvm_mi355_predictor_create_block): FORMS_EVERY, with the fp64 form's weight vectors taken sixteen per pass (tile_matvec_f64_blk) where that kernel applies */
-constexpr int FORMS_DEFAULT = 0, FORMS_EVERY = 1, FORMS_PANELS = 2, FORMS_BLOCK = 3;
+ * (lssvm_mi355_predictor_create_block): FORMS_EVERY, with the fp64 form's weight vectors taken sixteen per pass (tile_matvec_f64_blk) where that kernel applies;
+ * FORMS_BLOCK32 (lssvm_mi355_predictor_create_block32): FORMS_BLOCK, and the fp32 form's weight vectors sixteen per pass as well (tile_matvec_f32_blk) where THAT kernel applies */
+constexpr int FORMS_DEFAULT = 0, FORMS_EVERY = 1, FORMS_PANELS = 2, FORMS_BLOCK = 3, FORMS_BLOCK32 = 4;
 /* alpha [nvec][nsv], rho [nvec] */
 std::unique_ptr<PredictorBase> make_predictor(const Options &opt, const lssvm_params &params, int dtype, const void *sv, size_t nsv, size_t nfeat, const void *alpha, const double *rho,
                                               size_t nvec, int forms = FORMS_DEFAULT);
@@ -1050,6 +1051,9 @@ void enqueue_pack_records2(const double *dvec0, const double *dvec1, const doubl
 /* ... and for the sixteen-vector fp64 kernel (tile_matvec_f64_blk; tile_launch_f64blk.hip): (alpha[64 columns][16 vectors] | c), 1088 reals per sub-tile, from the
  * `count` (1 ... 16) vectors alpha[v][ld]; the vector slots beyond `count` are written as exact zeros (k_pack_ablock_f64) */
 void enqueue_pack_block_records(const double *alpha, size_t ld, int count, const double *cc, int ncols_padded, double *dc, hipStream_t s);
+/* ... and for the sixteen-vector fp32 kernel (tile_matvec_f32_blk; tile_launch_f32blk.hip): W[column / 4][16 vectors][column % 4], 2048 floats per 128-column tile, W = alpha
+ * or -- `folded` -- 2^c_j alpha as k_pack_dc writes it; the vector slots beyond `count` are written as exact zeros (k_pack_wblock_f32) */
+void enqueue_pack_block_records(const float *alpha, size_t ld, int count, const float *cc, int folded, int ncols_padded, float *dc, hipStream_t s);
 /* ... and for the sixteen-vector SYMMETRIC fp64 kernel (tile_matvec_f64_blk_sym; tile_launch_f64blks.hip): the same records from `count` vectors in buffers of their own;
  * the launch also clears the first `nzero` entries of Kv[u], u < count (k_pack_vblock_f64) */
 void enqueue_pack_block_sym_records(const double *const *v, double *const *Kv, int count, const double *cc, int ncols_padded, double *dc, int nzero, hipStream_t s);

@@ -24,7 +24,7 @@ constexpr int KT_RBFG = 6;   // f16 kernels of s6w_body only (round 5): rbf on G
                              // sigma^2 (ch_i + ch_j) and fed the h.h products first, holds -|h_i - h_j|^2 / 2 EXACTLY before the small terms arrive
 
 constexpr int TILE_THREADS = 256;  // 4 wave64 arranged 2 x 2, each owning a 64 x 64 sub-tile
-constexpr int BLOCK_VECTORS = 16;  // weight vectors per pass of tile_matvec_f64_blk (TileArgs::nvec == BLOCK_VECTORS): the M of its second v_mfma_f64_16x16x4
+constexpr int BLOCK_VECTORS = 16;  // weight vectors per pass of tile_matvec_f64_blk and tile_matvec_f32_blk (TileArgs::nvec == BLOCK_VECTORS): the M / N of their second 16x16x4 MFMA
 
 using f32x4 = float __attribute__((ext_vector_type(4)));
 using f32x16 = float __attribute__((ext_vector_type(16)));

@@ -82,5 +82,9 @@ void launch_v2d_block(const TileArgs<double> &a, int kernel_type, dim3 grid, hip
 /* ... and its SYMMETRIC counterpart, both second products on the matrix cores (tile_launch_f64blks_a.hip / _b.hip; TileArgs::nvec == BLOCK_VECTORS with a work-item list,
  * records from enqueue_pack_block_sym_records, sixteen planes of `partial` and of `colslab`; reached through launch_tile_kernel<double>): rbf and polynomial, degree >= 0 */
 void launch_v2d_block_sym(const TileArgs<double> &a, int kernel_type, hipStream_t s);
+/* the fp32 128-row full-square split kernel with SIXTEEN vectors per pass, the second product on the fp32 matrix cores (tile_launch_f32blk_a.hip / _b.hip; TileArgs::nvec ==
+ * BLOCK_VECTORS, records from enqueue_pack_block_records, sixteen planes of `partial`; reached through launch_tile_kernel<float>): folded rbf and polynomial, degree >= 0,
+ * at most 128 features */
+void launch_f32_block(const TileArgs<float> &a, int kernel_type, dim3 grid, hipStream_t s);
 
 }  // namespace lssvm
