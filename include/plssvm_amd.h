@@ -485,6 +485,16 @@ int lssvm_mi355_problem_matvec_block(lssvm_mi355_problem *p, const void *D /* nv
 int lssvm_mi355_problem_solve_lockstep_block(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out /* num_rhs x N */,
                                              double *rhos_out, lssvm_cg_info *infos_out /* num_rhs, may be NULL */, uint64_t passes_out[3]);
 
+/* BLOCK32 forms (opt-in, routed by no default): the _block calls with the FP32 sixteen-vector symmetric kernel as well (tile_matvec_f32_blk_sym; DESIGN.md section
+ * 4.1.7) -- fp32, one device, symmetric = 1, f16x3 or bf16x6 planes, at most 128 padded features, polynomial with degree >= 0 or rbf with folded records (not the
+ * direct, grid-plane or row-scaled forms), gram_mode != 0, tile_kernel != 1; on the 128-row and on the 256-row geometry alike (the block passes of a 256-row problem
+ * walk a 128-row geometry of their own; the problem's single-vector passes keep their bits).  Arguments and meaning are the _block calls'.  On an fp64 problem the
+ * calls ARE the _block calls; wherever neither block kernel applies they ARE the _panels calls: their bits and infos, *block_out = 0, passes_out[0] = 0.  Entry points
+ * of their own because the _block calls' declining of fp32 is a documented part of those. */
+int lssvm_mi355_problem_matvec_block32(lssvm_mi355_problem *p, const void *D /* nv x (N-1) */, size_t nv, void *Ret_inout /* nv x (N-1) */, double add, int *block_out);
+int lssvm_mi355_problem_solve_lockstep_block32(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out /* num_rhs x N */,
+                                               double *rhos_out, lssvm_cg_info *infos_out /* num_rhs, may be NULL */, uint64_t passes_out[3]);
+
 /* COST PATH (no counterpart in the reference): the solutions of ONE right-hand side for EVERY cost of a grid from one multi-shift CG sequence -- one pass over the
  * Gram tiles per iteration for the whole grid instead of one per cost, as many iterations as the hardest (largest) cost alone needs.  For fixed data and kernel
  * function the cost enters the reduced system only as a shift: Abar(C) = A0 + sigma M with sigma = 1 / C, A0 v = K v + (k_NN S - q.v) 1 - S q (S = sum v) and

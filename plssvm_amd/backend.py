@@ -1185,24 +1185,25 @@ class ResidentProblem:
         check(_capi.lockstep_entry("lssvm_mi355_problem_solve_lockstep_panels" if panels else "lssvm_mi355_problem_solve_lockstep")(self._h, ptr(B), k, eps, int(max_iter), ptr(alphas), rhos.ctypes.data_as(C.POINTER(C.c_double)), infos, passes))
         return alphas, rhos.astype(self.dtype), [info.as_dict() for info in infos], (int(passes[0]), int(passes[1]))
 
-    def matvec_block(self, D, Ret, add: float = 1.0):
+    def matvec_block(self, D, Ret, add: float = 1.0, block32: bool = False):
         """:meth:`matvec` for the ``k`` rows of ``D`` (``k x (num_points - 1)``; ``lssvm_mi355_problem_matvec_block``): returns ``(out[k, num_points - 1], block)``.  Where
         the sixteen-vector symmetric kernel applies (fp64, one device, rbf / polynomial with degree >= 0 on at most 256 features) the rows are taken sixteen per Gram
         pass and ``block`` is true; a row's result does not depend on the other rows or on its place.  Elsewhere the rows go through :meth:`matvec_pair` with
-        ``panels=True`` and ``block`` is false."""
+        ``panels=True`` and ``block`` is false.  ``block32=True`` (``lssvm_mi355_problem_matvec_block32``): a float32 problem of at most 128 padded features takes the
+        block passes as well (polynomial with degree >= 0, or rbf with folded records); a float64 problem does what it does without."""
         D = np.ascontiguousarray(D, dtype=self.dtype)
         out = np.array(Ret, dtype=self.dtype, copy=True, order="C")
         if not (D.ndim == 2 and D.shape[0] > 0 and D.shape == out.shape and D.shape[1] == self.num_points - 1):
             raise InvalidParameterError(f"Sizes mismatch!: {D.shape} / {out.shape} != (k, {self.num_points - 1})")
         block = C.c_int(0)
-        check(_capi.lockstep_entry("lssvm_mi355_problem_matvec_block")(self._h, ptr(D), D.shape[0], ptr(out), add, C.byref(block)))
+        check(_capi.lockstep_entry("lssvm_mi355_problem_matvec_block32" if block32 else "lssvm_mi355_problem_matvec_block")(self._h, ptr(D), D.shape[0], ptr(out), add, C.byref(block)))
         return out, bool(block.value)
 
-    def solve_lockstep_block(self, B, eps: float, max_iter: int):
+    def solve_lockstep_block(self, B, eps: float, max_iter: int, block32: bool = False):
         """:meth:`solve_lockstep` with sixteen right-hand sides per Gram pass (``lssvm_mi355_problem_solve_lockstep_block``): the active right-hand sides are grouped
         afresh in sixteens in every step and every pass is a block pass, so row ``c`` of the results has the bits of the call with that right-hand side alone.  Returns
         ``(alphas, rhos, infos, passes)`` with ``passes = (block, two-vector, single-vector)`` Gram passes; where the block kernel does not apply the call is
-        ``solve_lockstep(..., panels=True)`` and ``passes[0]`` is 0."""
+        ``solve_lockstep(..., panels=True)`` and ``passes[0]`` is 0.  ``block32=True`` (``lssvm_mi355_problem_solve_lockstep_block32``): as :meth:`matvec_block`'s."""
         B = np.ascontiguousarray(B, dtype=self.dtype)
         if B.ndim != 2 or B.shape[0] == 0 or B.shape[1] != self.num_points:
             raise InvalidParameterError(f"The number of data points in the matrix A ({self.num_points}) and the values in every right hand side vector ({B.shape[-1] if B.ndim else 0}) must be the same!")
@@ -1211,7 +1212,7 @@ class ResidentProblem:
         rhos = np.zeros(k, dtype=np.float64)
         infos = (LssvmCgInfo * k)()
         passes = (C.c_uint64 * 3)()
-        check(_capi.lockstep_entry("lssvm_mi355_problem_solve_lockstep_block")(self._h, ptr(B), k, eps, int(max_iter), ptr(alphas), rhos.ctypes.data_as(C.POINTER(C.c_double)), infos, passes))
+        check(_capi.lockstep_entry("lssvm_mi355_problem_solve_lockstep_block32" if block32 else "lssvm_mi355_problem_solve_lockstep_block")(self._h, ptr(B), k, eps, int(max_iter), ptr(alphas), rhos.ctypes.data_as(C.POINTER(C.c_double)), infos, passes))
         return alphas, rhos.astype(self.dtype), [info.as_dict() for info in infos], tuple(int(x) for x in passes)
 
     def solve_cost_path(self, y, costs, eps: float, max_iter: int, verify: bool = True):

@@ -879,9 +879,15 @@ void Problem<T>::enqueue_pack_dc(const T *v, T *zero, int nzero) {
 
 template <typename T>
 template <typename Around>
-void Problem<T>::enqueue_sym_walk(const TileArgs<T> &a, int nv, T *const *Kv, int npanels, Around &&around) {
+void Problem<T>::enqueue_sym_walk(const TileArgs<T> &a, int nv, T *const *Kv, int npanels, Around &&around, const BlockGeometry *geo) {
     hipStream_t st = stream_.s;
     const int nrows = num_ib_ * TILE;
+    // whose bands, items and chunks: the problem's own, or a block pass's 128-row geometry (no block pairs, no head of short chunks, no persistent launches)
+    const std::vector<Band> &bands = geo != nullptr ? geo->bands : bands_;
+    const int2 *items = geo != nullptr ? geo->items.p : items_.p;
+    const bool pair = geo != nullptr ? false : pair_;
+    const int jc_tiles = geo != nullptr ? geo->jc_tiles : jc_tiles_, jc_head_tiles = geo != nullptr ? 0 : jc_head_tiles_, jc_head_count = geo != nullptr ? 0 : jc_head_count_;
+    const int num_jc = geo != nullptr ? geo->num_jc : num_jc_;
     // wide linear problems: one pass per panel of LINEAR_PANEL_FEATURES features, every pass ADDS its K_p * v (rows and mirrored columns) into K*v
     const int panel_features = LINEAR_PANEL_FEATURES;
     for (int panel = 0; panel < npanels; ++panel) {
@@ -900,24 +906,24 @@ void Problem<T>::enqueue_sym_walk(const TileArgs<T> &a, int nv, T *const *Kv, in
                 ap.kchunks = std::min(panel_features, X_.ldx - panel * panel_features) / F64_KC;
             }
         }
-        for (const Band &band : bands_) {
+        for (const Band &band : bands) {
             TileArgs<T> ab = ap;
-            ab.items = items_.p + band.item_begin;
+            ab.items = items + band.item_begin;
             ab.num_items = band.item_count;
             ab.pair_origin = band.pair_origin;
-            if (queue_.p != nullptr && band.item_count > queue_min_items_) {  // (a launch of no more items than CUs: one workgroup per item, no counters -- 2 % faster there)
+            if (geo == nullptr && queue_.p != nullptr && band.item_count > queue_min_items_) {  // (a launch of no more items than CUs: one workgroup per item, no counters -- 2 % faster there)
                 ab.queue = queue_.p + 256 * queue_set_;
                 ab.queue_next = queue_.p + 256 * (1 - queue_set_);
                 ab.queue_grid = queue_min_items_;
                 queue_set_ ^= 1;
             }
-            around([&]() { launch_tile_kernel<T>(ab, tile_params_.kernel_type, rbf_direct_, num_jc_, st); }, panel == 0 && &band == &bands_.front(), panel == npanels - 1 && &band == &bands_.back());
+            around([&]() { launch_tile_kernel<T>(ab, tile_params_.kernel_type, rbf_direct_, num_jc, st); }, panel == 0 && &band == &bands.front(), panel == npanels - 1 && &band == &bands.back());
             // fold the band's mirrored column sums into K*v before the next band re-uses the slab
             if (band.ib_end > 1) {
                 for (int u = 0; u < nv; ++u) {
                     if constexpr (std::is_same_v<T, float>) {
                         // (block pairs: one record per pair and column tile, kept as the record of the pair's second -- odd -- block)
-                        hipLaunchKernelGGL((k_reduce_colslab<T, 128>), dim3(band.ib_end - 1), dim3(1024), 0, st, a.colslab + u * a.colslab_vstride, band.pair_origin, band.ib_begin, pair_ ? round_up(band.ib_end, 2) : band.ib_end, pair_ ? 2 : 1, Kv[u], rbf_grid_ ? efac_.p : static_cast<const T *>(nullptr));
+                        hipLaunchKernelGGL((k_reduce_colslab<T, 128>), dim3(band.ib_end - 1), dim3(1024), 0, st, a.colslab + u * a.colslab_vstride, band.pair_origin, band.ib_begin, pair ? round_up(band.ib_end, 2) : band.ib_end, pair ? 2 : 1, Kv[u], rbf_grid_ ? efac_.p : static_cast<const T *>(nullptr));
                     } else {  // fp64: records per 64-column sub-tile
                         hipLaunchKernelGGL((k_reduce_colslab<T, 64>), dim3(2 * (band.ib_end - 1)), dim3(1024), 0, st, a.colslab + u * a.colslab_vstride, band.pair_origin, band.ib_begin, band.ib_end, 1, Kv[u]);
                     }
@@ -926,7 +932,7 @@ void Problem<T>::enqueue_sym_walk(const TileArgs<T> &a, int nv, T *const *Kv, in
         }
         // rows of this device's blocks: the slabs of the column chunks that exist for each block, added on top
         for (int u = 0; u < nv; ++u) {
-            hipLaunchKernelGGL(k_reduce_partials_sym<T>, dim3((nrows + 255) / 256), dim3(256), 0, st, a.partial + u * a.part_vstride, a.part_stride, jc_tiles_, jc_head_tiles_, jc_head_count_, ib_begin_, nrows, Kv[u], 1);
+            hipLaunchKernelGGL(k_reduce_partials_sym<T>, dim3((nrows + 255) / 256), dim3(256), 0, st, a.partial + u * a.part_vstride, a.part_stride, jc_tiles, jc_head_tiles, jc_head_count, ib_begin_, nrows, Kv[u], 1);
         }
     }
 }
@@ -1118,8 +1124,54 @@ bool Problem<T>::block_kernel_applies() const {
         return world_ == 1 && sym_ && dc_.p != nullptr && !wide_nl_ && !wide_linear_ && num_ib_ > 0 && (poly || rbf) && X_.ldx <= F64_ONE_PASS_FEATURES && opt_.gram_mode != 0
                && opt_.tile_kernel != 1;
     } else {
-        return false;
+        // tile_matvec_f32_blk_sym: the symmetric split kernels on at most 128 padded features, the polynomial forms and rbf with folded records -- on the 128-row
+        // geometry and on the 256-row one (pair_: the block pass walks a 128-row geometry of its own, build_block_geometry)
+        const bool poly = tile_params_.kernel_type == LSSVM_KERNEL_POLYNOMIAL && tile_params_.degree >= 0;
+        const bool rbf_folded = tile_params_.kernel_type == LSSVM_KERNEL_RBF && dc_folded_;
+        return world_ == 1 && sym_ && dc_.p != nullptr && num_ib_ > 0 && !wide_nl_ && !wide_linear_ && !rbf_direct_ && !rbf_grid_ && !row_scaled_ && (planes_.mode == 1 || planes_.mode == 2)
+               && planes_.ldx16 <= 128 && (poly || rbf_folded) && opt_.gram_mode != 0 && opt_.tile_kernel != 1;
     }
+}
+
+/* The 128-row symmetric geometry of the fp32 block passes on a 256-row problem: bands of ONE plane's budget, 128-row work items and their record origins over this
+ * shard's row blocks, with the column chunks the 128-row split kernels would have been given (the host-only geometry unit, lssvm_geometry.cpp).  Elsewhere: the
+ * problem's own lists, copied by reference. */
+template <typename T>
+void Problem<T>::build_block_geometry(hipStream_t st) {
+    BlockGeometry &geo = block_geo_;
+    if (geo.built) return;
+    if (!pair_) {
+        geo.jc_tiles = jc_tiles_;
+        geo.num_jc = num_jc_;
+        geo.partial_count = partial_.count;
+        geo.colslab_count = colslab_.count;
+        geo.built = true;
+        return;
+    }
+    const int ib_end_all = ib_begin_ + num_ib_;
+    const GeometryOptions go = geometry_options(opt_);
+    geo.jc_tiles = shard_chunks(go, ib_begin_, ib_end_all, num_tiles_, sizeof(T), true, true, false, false, 1).tiles;
+    geo.num_jc = num_chunks(num_tiles_, geo.jc_tiles, 0, 0);
+    const std::vector<int> edge = band_edges(ib_begin_, ib_end_all, sizeof(T), go);
+    std::vector<WorkItem> items;
+    long max_records = 1;
+    for (size_t k = 0; k + 1 < edge.size(); ++k) {
+        Band band{};
+        band.ib_begin = edge[k];
+        band.ib_end = edge[k + 1];
+        band.item_begin = static_cast<int>(items.size());
+        band.pair_origin = pairs_below(band.ib_begin);
+        for (const WorkItem &it : band_items(band.ib_begin, band.ib_end, geo.jc_tiles, geo.num_jc, ITEM_ORDER, false)) items.push_back({ it.x - ib_begin_, it.y });
+        band.item_count = static_cast<int>(items.size()) - band.item_begin;
+        max_records = std::max(max_records, pairs_below(band.ib_end) - band.pair_origin);
+        if (band.ib_end > band.ib_begin) geo.bands.push_back(band);
+    }
+    geo.items.alloc_zero(std::max<size_t>(items.size(), 1), st);
+    if (!items.empty()) LSSVM_HIP_CHECK(hipMemcpyAsync(geo.items.p, items.data(), items.size() * sizeof(WorkItem), hipMemcpyHostToDevice, st));
+    LSSVM_HIP_CHECK(hipStreamSynchronize(st));  // `items` goes out of scope
+    geo.partial_count = static_cast<size_t>(std::max(geo.num_jc, 1)) * part_blocks() * TILE;
+    geo.colslab_count = static_cast<size_t>(max_records) * TILE;
+    geo.built = true;
 }
 
 template <typename T>
@@ -1151,7 +1203,37 @@ void Problem<T>::enqueue_apply_K_block(const T *const *v, T *const *Kv, int nv, 
         });
         LSSVM_HIP_CHECK(hipGetLastError());
     } else {
-        (void) v; (void) Kv; (void) ev_begin; (void) ev_end;
+        hipStream_t st = stream_.s;
+        build_block_geometry(st);
+        const BlockGeometry &geo = block_geo_;
+        const int ncols = num_tiles_ * TILE;
+        if (block_dc_.p == nullptr) {
+            // the bands hold ONE plane's budget (colslab_band_mb): sixteen planes of either slab; per column tile W (2048 floats) and the columns' factors (128)
+            block_dc_.alloc_zero(static_cast<size_t>(num_tiles_) * (TILE * BLOCK_VECTORS + TILE), st);
+            block_vp_.alloc_zero(static_cast<size_t>(ncols) * BLOCK_VECTORS, st);
+            block_partial_.alloc_zero(BLOCK_VECTORS * geo.partial_count, st);
+            block_colslab_.alloc_zero(BLOCK_VECTORS * geo.colslab_count, st);
+        }
+        // the records of the group, exact zeros in the slots beyond nv; the same launch clears the results (the symmetric variant ADDS rows and mirrored columns into K*v)
+        enqueue_pack_block_sym_records_f32(v, Kv, nv, c_.p, dc_folded_ ? 1 : 0, ncols, block_dc_.p, block_vp_.p, static_cast<int>(nvec_), st);
+        TileArgs<T> a = tile_args(block_vp_.p);
+        a.nvec = BLOCK_VECTORS;
+        a.dc = block_dc_.p;
+        a.partial = block_partial_.p;
+        a.part_vstride = static_cast<long>(geo.partial_count);
+        a.colslab = block_colslab_.p;
+        a.colslab_vstride = static_cast<long>(geo.colslab_count);
+        // 128-row work items over uniform column chunks, whatever the problem's own passes run on
+        a.row_pair = 0;
+        a.jc_tiles = geo.jc_tiles;
+        a.jc_head_tiles = a.jc_head_count = 0;
+        if (ev_begin != nullptr) LSSVM_HIP_CHECK(hipEventRecord(ev_begin, st));
+        // every reduction runs per vector on that vector's planes, into that vector's K*v; the planes of the empty slots are not read
+        enqueue_sym_walk(a, nv, Kv, 1, [&](auto &&launch, bool, bool last) {
+            launch();
+            if (last && ev_end != nullptr) LSSVM_HIP_CHECK(hipEventRecord(ev_end, st));
+        }, pair_ ? &geo : nullptr);
+        LSSVM_HIP_CHECK(hipGetLastError());
     }
 }
 

@@ -443,9 +443,11 @@ class Problem {
     /* The symmetric pass over the row-block bands, the one walk behind enqueue_apply_K_local and enqueue_apply_K_lanes: per feature panel (`npanels`: wide_linear_, else
      * 1) and band the tile kernel on `a` with the band's work items, then per vector u < nv the band's mirrored column sums (a.colslab + u * a.colslab_vstride) folded
      * into Kv[u]; after a panel's bands the row slabs (a.partial + u * a.part_vstride) added into Kv[u].  around(launch, first, last) runs every tile launch -- it calls
-     * launch() once, with whatever timing the caller keeps around it; first / last: the first / last tile launch of the walk. */
+     * launch() once, with whatever timing the caller keeps around it; first / last: the first / last tile launch of the walk.  `geo`: the bands, the work items and the
+     * column chunks of a block pass's own 128-row geometry (fp32 on a 256-row problem) instead of the problem's; NULL for every other caller. */
+    struct BlockGeometry;
     template <typename Around>
-    void enqueue_sym_walk(const TileArgs<T> &a, int nv, T *const *Kv, int npanels, Around &&around);
+    void enqueue_sym_walk(const TileArgs<T> &a, int nv, T *const *Kv, int npanels, Around &&around, const BlockGeometry *geo = nullptr);
 
     Options opt_{};
     lssvm_params params_{};
@@ -511,6 +513,18 @@ class Problem {
         long pair_origin;           // record index of (ib_begin, 0) in the packed triangle: ib_begin (ib_begin - 1) / 2
     };
     std::vector<Band> bands_;
+    /* fp32 block passes (tile_matvec_f32_blk_sym) walk 128-row work items: the problem's own where it has them, and on a 256-row problem (pair_) a SECOND geometry over
+     * the same row blocks, built at the first block pass (build_block_geometry) -- the single-vector passes keep theirs */
+    struct BlockGeometry {
+        bool built = false;
+        int jc_tiles = 0, num_jc = 0;
+        size_t partial_count = 0, colslab_count = 0;  // one plane of the row slabs / of the column slab
+        DevBuf<int2> items;
+        std::vector<Band> bands;
+    };
+    BlockGeometry block_geo_;
+    DevBuf<T> block_vp_;  // ... and the group's plain vectors, [column][16] (the mirror product's A operand)
+    void build_block_geometry(hipStream_t st);
     double QA_cost_ = 0.0;
     double inv_cost_ = 1.0;
     double self_last_ = 0.0;  // k(x_last, x_last) in the real type: QA_cost_ = self_last_ + 1/(C w_last) (set_weights)
@@ -629,9 +643,10 @@ struct ProblemBase {
     virtual void solve_lockstep(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out,
                                 uint64_t *passes_out, bool panels = false) = 0;  // lssvm_mi355_problem_solve_lockstep
     /* the _block entry points: sixteen vectors per Gram pass where Problem<T>::block_kernel_applies, the _panels calls elsewhere; passes_out[3]: block, pair, single */
-    virtual void matvec_block(const void *D, size_t nv, void *Ret_inout, double add, int *block_out) = 0;  // lssvm_mi355_problem_matvec_block
+    /* `block32`: the _block32 entry points -- an fp32 problem takes the block passes as well (tile_matvec_f32_blk_sym); without it fp32 is declined */
+    virtual void matvec_block(const void *D, size_t nv, void *Ret_inout, double add, int *block_out, bool block32 = false) = 0;  // lssvm_mi355_problem_matvec_block
     virtual void solve_lockstep_block(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out,
-                                      uint64_t *passes_out) = 0;  // lssvm_mi355_problem_solve_lockstep_block
+                                      uint64_t *passes_out, bool block32 = false) = 0;  // lssvm_mi355_problem_solve_lockstep_block
     virtual void solve_cost_path(const void *y, const double *costs, size_t num_costs, double eps, uint64_t max_iter, bool verify, void *alphas_out, double *rhos_out,
                                  lssvm_path_info *infos_out, uint64_t *passes_out) = 0;  // lssvm_mi355_problem_solve_cost_path
     /* the Nystrom preconditioner and PCG on it (lssvm_precond.hip) */
@@ -768,8 +783,9 @@ class Solver final : public ProblemBase {
     void matvec_pair(const void *d0, const void *d1, void *ret0_inout, void *ret1_inout, double add, int *two_vector_out, bool panels = false) override;
     void solve_lockstep(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out,
                         bool panels = false) override;
-    void matvec_block(const void *D, size_t nv, void *Ret_inout, double add, int *block_out) override;
-    void solve_lockstep_block(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out) override;
+    void matvec_block(const void *D, size_t nv, void *Ret_inout, double add, int *block_out, bool block32 = false) override;
+    void solve_lockstep_block(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out,
+                              bool block32 = false) override;
     /* every cost of a grid from ONE multi-shift CG sequence on this problem's single-vector pass (lssvm_path.hip) */
     void solve_cost_path(const void *y, const double *costs, size_t num_costs, double eps, uint64_t max_iter, bool verify, void *alphas_out, double *rhos_out, lssvm_path_info *infos_out,
                          uint64_t *passes_out) override;
@@ -833,7 +849,7 @@ class Solver final : public ProblemBase {
 
     /* for a driver that runs on lanes of shard 0 (the lockstep solve here, the refinement in lssvm_refine.hip) */
     Problem<T> &shard0() { return *shards_[0]; }
-    bool block_applies() const;  // ... where the sixteen-vector kernel applies (Problem<T>::block_kernel_applies)
+    bool block_applies(bool block32 = false) const;  // ... where the sixteen-vector kernel applies (Problem<T>::block_kernel_applies; fp32 only for the _block32 entry points)
     bool lanes_apply(bool panels = false) const;  // one unsharded device without an exchange, where the two-vector kernel applies (`panels`: or the two-vector panel kernel)
     void wait_for_deltas();    // the host waits for what shard 0's stream holds: the deltas of the step are in their host words
     /* until the returned object goes: no other solve may begin on this handle, and its weights stay */
@@ -1057,6 +1073,10 @@ void enqueue_pack_block_records(const float *alpha, size_t ld, int count, const 
 /* ... and for the sixteen-vector SYMMETRIC fp64 kernel (tile_matvec_f64_blk_sym; tile_launch_f64blks.hip): the same records from `count` vectors in buffers of their own;
  * the launch also clears the first `nzero` entries of Kv[u], u < count (k_pack_vblock_f64) */
 void enqueue_pack_block_sym_records(const double *const *v, double *const *Kv, int count, const double *cc, int ncols_padded, double *dc, int nzero, hipStream_t s);
+/* ... and for the sixteen-vector SYMMETRIC fp32 kernel (tile_matvec_f32_blk_sym; tile_launch_f32blks.hip): per 128-column tile the W part as above (2048 floats) and
+ * 2^c_j of its columns (128 floats; `folded` only), from `count` vectors in buffers of their own; vp[column][16] takes the plain vectors; the launch also clears the first
+ * `nzero` entries of Kv[u], u < count (k_pack_vblock_f32_sym) */
+void enqueue_pack_block_sym_records_f32(const float *const *v, float *const *Kv, int count, const float *cc, int folded, int ncols_padded, float *dc, float *vp, int nzero, hipStream_t s);
 void enqueue_planes_fragment_major(const uint16_t *planes, size_t plane_elems, int rows_alloc, int ldx16, int nplanes, uint16_t *frag, hipStream_t s);
 
 }  // namespace lssvm

@@ -776,12 +776,13 @@ void Solver<T>::solve_on_lanes(const T *Y, size_t num_rhs, double eps, uint64_t 
 
 /* ------------------------------------------------------------------ sixteen vectors per Gram pass: matvec_block, the block lockstep CG ------------------------------------------------------------------ */
 template <typename T>
-bool Solver<T>::block_applies() const {
-    return shards_.size() == 1 && world_ == 1 && exchange_ == Exchange::none && shards_[0]->block_kernel_applies();
+bool Solver<T>::block_applies(bool block32) const {
+    // (the _block entry points keep declining fp32: only the _block32 ones take its sixteen-vector kernel)
+    return (std::is_same_v<T, double> || block32) && shards_.size() == 1 && world_ == 1 && exchange_ == Exchange::none && shards_[0]->block_kernel_applies();
 }
 
 template <typename T>
-void Solver<T>::matvec_block(const void *D, size_t nv, void *Ret_inout, double add, int *block_out) {
+void Solver<T>::matvec_block(const void *D, size_t nv, void *Ret_inout, double add, int *block_out, bool block32) {
     LSSVM_REQUIRE(D != nullptr && Ret_inout != nullptr, "The d / ret arrays may not be empty!");  // csvm.cpp:284-286
     LSSVM_REQUIRE(nv > 0, "The number of vectors must be greater than 0!");
     LSSVM_REQUIRE(add == 1.0 || add == -1.0, "add must either be -1.0 or 1.0, but is " + std::to_string(add) + "!");  // svm_kernel.cpp:28
@@ -790,7 +791,7 @@ void Solver<T>::matvec_block(const void *D, size_t nv, void *Ret_inout, double a
     const size_t n = static_cast<size_t>(shards_[0]->n_);
     const T *d = static_cast<const T *>(D);
     T *ret = static_cast<T *>(Ret_inout);
-    if (!block_applies()) {  // what lssvm_mi355_problem_matvec_pair_panels does, pair by pair
+    if (!block_applies(block32)) {  // what lssvm_mi355_problem_matvec_pair_panels does, pair by pair
         size_t c = 0;
         for (; c + 1 < nv; c += 2) matvec_pair(d + c * n, d + (c + 1) * n, ret + c * n, ret + (c + 1) * n, add, nullptr, true);
         if (c < nv) matvec(d + c * n, ret + c * n, add);
@@ -824,8 +825,9 @@ void Solver<T>::matvec_block(const void *D, size_t nv, void *Ret_inout, double a
 }
 
 template <typename T>
-void Solver<T>::solve_lockstep_block(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out) {
-    if (!block_applies()) {  // the call IS lssvm_mi355_problem_solve_lockstep_panels: its bits, its infos, its (pair | single) counts behind a zero
+void Solver<T>::solve_lockstep_block(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out,
+                                     bool block32) {
+    if (!block_applies(block32)) {  // the call IS lssvm_mi355_problem_solve_lockstep_panels: its bits, its infos, its (pair | single) counts behind a zero
         uint64_t two[2] = { 0, 0 };
         solve_lockstep(Y, num_rhs, eps, max_iter, alphas_out, rhos_out, infos_out, two, true);
         if (passes_out != nullptr) {

@@ -481,7 +481,8 @@ class MI355CSVM(CSVM):
         selected from the data (``backend.select_landmarks``).
         ``lockstep``: how :meth:`solve_systems_of_linear_equations` takes several right-hand sides through a Gram pass on one device -- ``"pair"`` (default) = two per pass
         (``ResidentProblem.solve_lockstep``), ``"block"`` = sixteen per pass on the matrix cores (``ResidentProblem.solve_lockstep_block``) where
-        that kernel applies (float64, rbf / polynomial, at most 256 features) and ``"pair"`` elsewhere.  Opt-in: a column's bits are those of the block call with that
+        that kernel applies (float64, rbf / polynomial, at most 256 features) and ``"pair"`` elsewhere, ``"block32"`` = ``"block"``, and float32 problems of at most
+        128 padded features sixteen per pass as well (``solve_lockstep_block(..., block32=True)``).  Opt-in: a column's bits are those of the block call with that
         right-hand side alone, not those of the one-shot solve.  ``last_lockstep_passes`` keeps ``(block, two-vector, single-vector)`` Gram passes of the last such call.
 
         ``num_devices``: devices ONE solve is sharded over -- 1 (default) = device 0 only, k = devices 0 .. k-1 (gpu_csvm.hpp:283-299),
@@ -494,8 +495,8 @@ class MI355CSVM(CSVM):
             raise InvalidParameterError(f"solver must be 'cg' or 'refined' or 'pcg', but is {solver!r}!")
         if solver == "pcg" and not (isinstance(precond_rank, (int, np.integer)) and 1 <= int(precond_rank) <= _capi.PRECOND_MAX_RANK):
             raise InvalidParameterError(f"precond_rank must lie in [1, {_capi.PRECOND_MAX_RANK}], but is {precond_rank!r}!")
-        if lockstep not in ("pair", "block"):
-            raise InvalidParameterError(f"lockstep must be 'pair' or 'block', but is {lockstep!r}!")
+        if lockstep not in ("pair", "block", "block32"):
+            raise InvalidParameterError(f"lockstep must be 'pair', 'block' or 'block32', but is {lockstep!r}!")
         if precond_landmarks is not None and precond_landmarks not in _capi.LANDMARK_METHODS:
             raise InvalidParameterError(f"precond_landmarks must be None or one of {sorted(_capi.LANDMARK_METHODS)}, but is {precond_landmarks!r}!")
         super().__init__(params, **kwargs)
@@ -670,8 +671,8 @@ class MI355CSVM(CSVM):
         with backend.ResidentProblem(params, A, devices=[0], options=self._options) as prob:  # (device 0 alone, as the one-shot solve creates it)
             if sample_weight is not None:
                 prob.set_weights(sample_weight)
-            if self.lockstep == "block":
-                alphas, rhos, infos, passes = prob.solve_lockstep_block(B, eps, max_iter)
+            if self.lockstep in ("block", "block32"):
+                alphas, rhos, infos, passes = prob.solve_lockstep_block(B, eps, max_iter, block32=self.lockstep == "block32")
             else:
                 alphas, rhos, infos, two = prob.solve_lockstep(B, eps, max_iter, panels=True)  # (one device: option rebalance_after has nothing to move)
                 passes = (0,) + tuple(two)
