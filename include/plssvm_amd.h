@@ -495,6 +495,24 @@ int lssvm_mi355_problem_matvec_block32(lssvm_mi355_problem *p, const void *D /* 
 int lssvm_mi355_problem_solve_lockstep_block32(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out /* num_rhs x N */,
                                                double *rhos_out, lssvm_cg_info *infos_out /* num_rhs, may be NULL */, uint64_t passes_out[3]);
 
+/* STORED forms (opt-in, routed by no default): the (N-1) x (N-1) kernel matrix of the reduced system evaluated ONCE and kept in HBM as a tile-packed
+ * lower triangle in the problem's real type; every later pass streams it instead of evaluating it, sixteen vectors per pass, whatever the feature count.
+ *   _store_gram: evaluates the triangle in double on the fp64 matrix cores from the resident data (linear, polynomial of any degree, rbf) and rounds every entry once to
+ *   the real type.  max_bytes: what the triangle and the slabs of its pass may take together -- (N-1)^2 / 2 reals rounded up to whole 128 x 128 tiles, plus about an eighth
+ *   of that; 0 = what hipMemGetInfo reports free, less 1 GiB.  Where that does not suffice, or on several devices or ranks, the call declines: *stored_out = 0, success,
+ *   nothing allocated.  *bytes_out, *assemble_ms_out (each may be NULL): the device memory taken and the device time of the assembly.  A second call replaces the matrix.
+ *   lssvm_mi355_problem_set_weights does not touch it (the weights live in the diagonal term); the data and the kernel parameters of a handle never change.
+ *   _drop_gram: frees it (no error where none is stored).
+ *   _matvec_stored: the contract of _matvec_block, every group of sixteen vectors one pass over the stored triangle; *stored_out (may be NULL) = 1 where it ran.
+ *   _solve_lockstep_stored: the contract of _solve_lockstep_block, every Gram pass a stored pass; passes_out[3]: stored, two-vector, single-vector passes.
+ * Where no matrix is stored (never stored, declined, dropped, several devices or ranks) the last two ARE lssvm_mi355_problem_matvec_pair_panels (pair by pair) /
+ * _solve_lockstep_panels: their bits and infos, *stored_out = 0, passes_out[0] = 0. */
+int lssvm_mi355_problem_store_gram(lssvm_mi355_problem *p, size_t max_bytes, int *stored_out, size_t *bytes_out, double *assemble_ms_out);
+int lssvm_mi355_problem_drop_gram(lssvm_mi355_problem *p);
+int lssvm_mi355_problem_matvec_stored(lssvm_mi355_problem *p, const void *D /* nv x (N-1) */, size_t nv, void *Ret_inout /* nv x (N-1) */, double add, int *stored_out);
+int lssvm_mi355_problem_solve_lockstep_stored(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out /* num_rhs x N */,
+                                              double *rhos_out, lssvm_cg_info *infos_out /* num_rhs, may be NULL */, uint64_t passes_out[3]);
+
 /* COST PATH (no counterpart in the reference): the solutions of ONE right-hand side for EVERY cost of a grid from one multi-shift CG sequence -- one pass over the
  * Gram tiles per iteration for the whole grid instead of one per cost, as many iterations as the hardest (largest) cost alone needs.  For fixed data and kernel
  * function the cost enters the reduced system only as a shift: Abar(C) = A0 + sigma M with sigma = 1 / C, A0 v = K v + (k_NN S - q.v) 1 - S q (S = sum v) and

@@ -1215,6 +1215,45 @@ class ResidentProblem:
         check(_capi.lockstep_entry("lssvm_mi355_problem_solve_lockstep_block32" if block32 else "lssvm_mi355_problem_solve_lockstep_block")(self._h, ptr(B), k, eps, int(max_iter), ptr(alphas), rhos.ctypes.data_as(C.POINTER(C.c_double)), infos, passes))
         return alphas, rhos.astype(self.dtype), [info.as_dict() for info in infos], tuple(int(x) for x in passes)
 
+    def store_gram(self, max_bytes: int = 0):
+        """Evaluate the kernel matrix of the reduced system once and keep its lower triangle in HBM (``lssvm_mi355_problem_store_gram``): returns
+        ``(stored, bytes, assemble_ms)``.  ``max_bytes``: what it may take, 0 = the free device memory less 1 GiB; where it does not fit, or on several devices,
+        ``stored`` is false and nothing is allocated.  :meth:`set_weights` leaves a stored matrix valid."""
+        stored, nbytes, ms = C.c_int(0), C.c_size_t(0), C.c_double(0.0)
+        check(_capi.lockstep_entry("lssvm_mi355_problem_store_gram")(self._h, int(max_bytes), C.byref(stored), C.byref(nbytes), C.byref(ms)))
+        return bool(stored.value), int(nbytes.value), float(ms.value)
+
+    def drop_gram(self):
+        """Free the stored kernel matrix (``lssvm_mi355_problem_drop_gram``); the ``_stored`` calls then are the ``panels=True`` ones."""
+        check(_capi.lockstep_entry("lssvm_mi355_problem_drop_gram")(self._h))
+
+    def matvec_stored(self, D, Ret=None, add: float = 1.0):
+        """:meth:`matvec_block` on the stored kernel matrix (``lssvm_mi355_problem_matvec_stored``): sixteen rows of ``D`` per pass over the stored triangle, any kernel
+        function, either real type, any feature count.  Returns ``(out, stored)``; without a stored matrix the rows go through :meth:`matvec_pair` with ``panels=True``
+        and ``stored`` is false.  ``Ret=None``: zeros."""
+        D = np.ascontiguousarray(D, dtype=self.dtype)
+        out = np.zeros_like(D) if Ret is None else np.array(Ret, dtype=self.dtype, copy=True, order="C")
+        if not (D.ndim == 2 and D.shape[0] > 0 and D.shape == out.shape and D.shape[1] == self.num_points - 1):
+            raise InvalidParameterError(f"Sizes mismatch!: {D.shape} / {out.shape} != (k, {self.num_points - 1})")
+        stored = C.c_int(0)
+        check(_capi.lockstep_entry("lssvm_mi355_problem_matvec_stored")(self._h, ptr(D), D.shape[0], ptr(out), add, C.byref(stored)))
+        return out, bool(stored.value)
+
+    def solve_lockstep_stored(self, B, eps: float, max_iter: int):
+        """:meth:`solve_lockstep_block` with every Gram pass a pass over the stored kernel matrix (``lssvm_mi355_problem_solve_lockstep_stored``).  Returns
+        ``(alphas, rhos, infos, passes)`` with ``passes = (stored, two-vector, single-vector)``; without a stored matrix the call is ``solve_lockstep(..., panels=True)``
+        and ``passes[0]`` is 0."""
+        B = np.ascontiguousarray(B, dtype=self.dtype)
+        if B.ndim != 2 or B.shape[0] == 0 or B.shape[1] != self.num_points:
+            raise InvalidParameterError(f"The number of data points in the matrix A ({self.num_points}) and the values in every right hand side vector ({B.shape[-1] if B.ndim else 0}) must be the same!")
+        k = B.shape[0]
+        alphas = np.zeros_like(B)
+        rhos = np.zeros(k, dtype=np.float64)
+        infos = (LssvmCgInfo * k)()
+        passes = (C.c_uint64 * 3)()
+        check(_capi.lockstep_entry("lssvm_mi355_problem_solve_lockstep_stored")(self._h, ptr(B), k, eps, int(max_iter), ptr(alphas), rhos.ctypes.data_as(C.POINTER(C.c_double)), infos, passes))
+        return alphas, rhos.astype(self.dtype), [info.as_dict() for info in infos], tuple(int(x) for x in passes)
+
     def solve_cost_path(self, y, costs, eps: float, max_iter: int, verify: bool = True):
         """:func:`solve_cost_path` on this resident problem (``lssvm_mi355_problem_solve_cost_path``): every cost of ``costs`` from one multi-shift CG sequence on the
         problem's own single-vector pass.  The problem's own cost is ignored and the problem is left as it was.  Not on a problem of several devices or ranks, not with

@@ -431,6 +431,16 @@ class Problem {
     /* Kv[u] <- K * v[u], u < nv (1 ... 16), from ONE pass of the sixteen-vector kernel through enqueue_sym_walk (block_kernel_applies).  A vector's result does not depend
      * on nv, on its slot or on the other vectors.  `ev`: as enqueue_apply_K_lanes'. */
     void enqueue_apply_K_block(const T *const *v, T *const *Kv, int nv, hipEvent_t ev_begin, hipEvent_t ev_end);
+    /* ---- the kernel matrix kept in HBM (lssvm_stored.hip).  store_gram: evaluate the lower triangle of K once, in double, rounded to T, where it and
+     * the slabs of its pass (stored_gram_bytes) fit into `max_bytes` (0: the free device memory less 1 GiB) -- false, with nothing allocated, where they do not or where
+     * the problem is sharded.  Per-point weights live in the diagonal term and do not touch it; the data and the kernel parameters of a problem never change. ---- */
+    bool store_gram(size_t max_bytes, size_t *bytes_out, double *assemble_ms_out);
+    void drop_gram();
+    bool gram_stored() const { return gram_.p != nullptr; }
+    size_t stored_gram_bytes() const;
+    /* Kv[u] <- K * v[u], u < nv (1 ... 16), from ONE pass over the stored triangle (tile_symm_stored + k_fold_stored).  A vector's result does not depend on nv, on its
+     * slot or on the other vectors.  `ev`: HIP events around the tile pass, or NULL. */
+    void enqueue_apply_K_stored(const T *const *v, T *const *Kv, int nv, hipEvent_t ev_begin, hipEvent_t ev_end);
 
   private:
     friend class Solver<T>;
@@ -524,6 +534,9 @@ class Problem {
     };
     BlockGeometry block_geo_;
     DevBuf<T> block_vp_;  // ... and the group's plain vectors, [column][16] (the mirror product's A operand)
+    DevBuf<T> gram_, gram_vp_, gram_rowpart_, gram_colrec_;  // the stored triangle (tile packed), the packed vectors of a pass, its row slabs and its column records
+    DevBuf<int2> gram_items_;                                // ... and its work items (row block, column chunk), longest first
+    int gram_num_items_ = 0, gram_grid_ = 1;                 // ... dealt round robin to gram_grid_ persistent workgroups
     void build_block_geometry(hipStream_t st);
     double QA_cost_ = 0.0;
     double inv_cost_ = 1.0;
@@ -647,6 +660,12 @@ struct ProblemBase {
     virtual void matvec_block(const void *D, size_t nv, void *Ret_inout, double add, int *block_out, bool block32 = false) = 0;  // lssvm_mi355_problem_matvec_block
     virtual void solve_lockstep_block(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out,
                                       uint64_t *passes_out, bool block32 = false) = 0;  // lssvm_mi355_problem_solve_lockstep_block
+    /* the _stored entry points (lssvm_stored.hip): the kernel matrix kept in HBM, sixteen vectors per pass over it; where none is stored the last two ARE the _panels calls */
+    virtual void store_gram(size_t max_bytes, int *stored_out, size_t *bytes_out, double *assemble_ms_out) = 0;  // lssvm_mi355_problem_store_gram
+    virtual void drop_gram() = 0;                                                                                // lssvm_mi355_problem_drop_gram
+    virtual void matvec_stored(const void *D, size_t nv, void *Ret_inout, double add, int *stored_out) = 0;      // lssvm_mi355_problem_matvec_stored
+    virtual void solve_lockstep_stored(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out,
+                                       uint64_t *passes_out) = 0;  // lssvm_mi355_problem_solve_lockstep_stored
     virtual void solve_cost_path(const void *y, const double *costs, size_t num_costs, double eps, uint64_t max_iter, bool verify, void *alphas_out, double *rhos_out,
                                  lssvm_path_info *infos_out, uint64_t *passes_out) = 0;  // lssvm_mi355_problem_solve_cost_path
     /* the Nystrom preconditioner and PCG on it (lssvm_precond.hip) */
@@ -786,6 +805,10 @@ class Solver final : public ProblemBase {
     void matvec_block(const void *D, size_t nv, void *Ret_inout, double add, int *block_out, bool block32 = false) override;
     void solve_lockstep_block(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out,
                               bool block32 = false) override;
+    void store_gram(size_t max_bytes, int *stored_out, size_t *bytes_out, double *assemble_ms_out) override;
+    void drop_gram() override;
+    void matvec_stored(const void *D, size_t nv, void *Ret_inout, double add, int *stored_out) override;
+    void solve_lockstep_stored(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out) override;
     /* every cost of a grid from ONE multi-shift CG sequence on this problem's single-vector pass (lssvm_path.hip) */
     void solve_cost_path(const void *y, const double *costs, size_t num_costs, double eps, uint64_t max_iter, bool verify, void *alphas_out, double *rhos_out, lssvm_path_info *infos_out,
                          uint64_t *passes_out) override;
@@ -850,6 +873,7 @@ class Solver final : public ProblemBase {
     /* for a driver that runs on lanes of shard 0 (the lockstep solve here, the refinement in lssvm_refine.hip) */
     Problem<T> &shard0() { return *shards_[0]; }
     bool block_applies(bool block32 = false) const;  // ... where the sixteen-vector kernel applies (Problem<T>::block_kernel_applies; fp32 only for the _block32 entry points)
+    bool stored_applies() const;                  // ... where a stored kernel matrix serves the passes (Problem<T>::gram_stored on one unsharded device)
     bool lanes_apply(bool panels = false) const;  // one unsharded device without an exchange, where the two-vector kernel applies (`panels`: or the two-vector panel kernel)
     void wait_for_deltas();    // the host waits for what shard 0's stream holds: the deltas of the step are in their host words
     /* until the returned object goes: no other solve may begin on this handle, and its weights stay */
@@ -869,8 +893,13 @@ class Solver final : public ProblemBase {
     void reset_cg(double eps, double y_last);  // cg_begin, cg_begin_from_zero: the host's counters and scalars of a new solve
     void read_delta0(double t0);               // ... and their end: delta0 is read, the handle is between begin and finish
     void solve_in_sequence(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out);
-    /* `block`: the active lanes grouped in sixteens, every Gram pass a pass of the sixteen-vector kernel (passes_out[2] then counts them, [0] and [1] stay 0) */
-    void solve_on_lanes(const T *Y, size_t num_rhs, double eps, uint64_t max_iter, T *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out, bool block = false);
+    /* how the lanes of a lockstep solve share Gram passes: in pairs (an odd lane alone); `block` / `stored`: the active lanes grouped in sixteens, every Gram pass a pass of
+     * the sixteen-vector kernel / over the stored kernel matrix (passes_out[0] then counts them, [1] and [2] stay 0) */
+    enum class LaneMode { pairs, block, stored };
+    void solve_on_lanes(const T *Y, size_t num_rhs, double eps, uint64_t max_iter, T *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out,
+                        LaneMode mode = LaneMode::pairs);
+    /* matvec() per vector on up to sixteen lanes around ONE sixteen-vector pass per group: the block kernel's, or the stored matrix's */
+    void matvec_on_lanes(const T *d, size_t nv, T *ret, double add, LaneMode mode);
     Problem<T> &precond_problem(const char *what);                        // the checks every preconditioner entry point shares; shard 0
     void enqueue_precond_apply(const T *r, T *z, double *part_rz) const;  // z = r - Bhat G^-1 Bhat^T r and the partial sums of r.z
     Problem<T> &reduced_problem(const char *what, bool unweighted_only);  // the checks every entry point of the fixed-size model shares; shard 0 (lssvm_reduced.hip)

@@ -621,8 +621,9 @@ void Solver<T>::solve_in_sequence(const void *Y, size_t num_rhs, double eps, uin
  * recurrence has the bits of the one-shot solve -- all lanes advancing one iteration per step.  In every step the lanes still active are paired afresh for the
  * implicit matvec: ceil(active / 2) Gram passes, an odd lane taking the single-vector pass.  The host waits for the step's deltas before it enqueues the next step. */
 template <typename T>
-void Solver<T>::solve_on_lanes(const T *Y, size_t num_rhs, double eps, uint64_t max_iter, T *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out, bool block) {
+void Solver<T>::solve_on_lanes(const T *Y, size_t num_rhs, double eps, uint64_t max_iter, T *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out, LaneMode mode) {
     const double t_call = now_ms();
+    const bool block = mode != LaneMode::pairs;  // (sixteen lanes per pass)
     Problem<T> &p = *shards_[0];
     p.activate();
     const CgSteps<T> cg(p);
@@ -669,7 +670,11 @@ void Solver<T>::solve_on_lanes(const T *Y, size_t num_rhs, double eps, uint64_t 
                 Timed &t = timers[timers_used++];
                 t.lane0 = k;
                 t.group = g;
-                p.enqueue_apply_K_block(v, Kv, static_cast<int>(g), t.a.e, t.b.e);
+                if (mode == LaneMode::stored) {
+                    p.enqueue_apply_K_stored(v, Kv, static_cast<int>(g), t.a.e, t.b.e);
+                } else {
+                    p.enqueue_apply_K_block(v, Kv, static_cast<int>(g), t.a.e, t.b.e);
+                }
                 ++passes[2];
             }
             return;
@@ -797,7 +802,14 @@ void Solver<T>::matvec_block(const void *D, size_t nv, void *Ret_inout, double a
         if (c < nv) matvec(d + c * n, ret + c * n, add);
         return;
     }
+    matvec_on_lanes(d, nv, ret, add, LaneMode::block);
+    if (block_out != nullptr) *block_out = 1;
+}
+
+template <typename T>
+void Solver<T>::matvec_on_lanes(const T *d, size_t nv, T *ret, double add, LaneMode mode) {
     // the statements of matvec() per vector on up to sixteen lanes (d <- d_u zero padded, Ad <- ret_u), around ONE pass of the sixteen-vector kernel per group
+    const size_t n = static_cast<size_t>(shards_[0]->n_);
     Problem<T> &p = *shards_[0];
     const CgSteps<T> cg(p);
     const size_t bytes = n * sizeof(T);
@@ -814,14 +826,17 @@ void Solver<T>::matvec_block(const void *D, size_t nv, void *Ret_inout, double a
             v[u] = lane[u]->d.p;
             Kv[u] = lane[u]->Kv.p;
         }
-        p.enqueue_apply_K_block(v, Kv, static_cast<int>(g), nullptr, nullptr);
+        if (mode == LaneMode::stored) {
+            p.enqueue_apply_K_stored(v, Kv, static_cast<int>(g), nullptr, nullptr);
+        } else {
+            p.enqueue_apply_K_block(v, Kv, static_cast<int>(g), nullptr, nullptr);
+        }
         for (size_t u = 0; u < g; ++u) {
             cg.apply_ret(*lane[u], lane[u]->Kv.p, lane[u]->d.p, add);
             LSSVM_HIP_CHECK(hipMemcpyAsync(ret + (c0 + u) * n, lane[u]->Ad.p, bytes, hipMemcpyDeviceToHost, p.stream()));
         }
         sync_all();  // (the lanes are re-used by the next group, and the host's memory by the caller)
     }
-    if (block_out != nullptr) *block_out = 1;
 }
 
 template <typename T>
@@ -844,7 +859,72 @@ void Solver<T>::solve_lockstep_block(const void *Y, size_t num_rhs, double eps, 
     LSSVM_REQUIRE(alphas_out != nullptr && rhos_out != nullptr, "alpha_out / rho_out must not be NULL");
     LSSVM_REQUIRE(!in_cg_, "solve_lockstep_block cannot run between cg_begin and cg_finish");
     if (passes_out != nullptr) passes_out[0] = passes_out[1] = passes_out[2] = 0;
-    solve_on_lanes(static_cast<const T *>(Y), num_rhs, eps, max_iter, static_cast<T *>(alphas_out), rhos_out, infos_out, passes_out, true);
+    solve_on_lanes(static_cast<const T *>(Y), num_rhs, eps, max_iter, static_cast<T *>(alphas_out), rhos_out, infos_out, passes_out, LaneMode::block);
+}
+
+/* ------------------------------------------------------------------ the kernel matrix kept in HBM: store_gram, matvec_stored, the stored lockstep CG ------------------------------------------------------------------ */
+template <typename T>
+bool Solver<T>::stored_applies() const {
+    return shards_.size() == 1 && world_ == 1 && exchange_ == Exchange::none && shards_[0]->gram_stored();
+}
+
+template <typename T>
+void Solver<T>::store_gram(size_t max_bytes, int *stored_out, size_t *bytes_out, double *assemble_ms_out) {
+    LSSVM_REQUIRE(stored_out != nullptr, "stored_out must not be NULL");
+    LSSVM_REQUIRE(!in_cg_, "store_gram cannot run between cg_begin and cg_finish");
+    *stored_out = 0;
+    if (bytes_out != nullptr) *bytes_out = 0;
+    if (assemble_ms_out != nullptr) *assemble_ms_out = 0.0;
+    if (shards_.size() != 1 || world_ != 1 || exchange_ != Exchange::none) return;  // several devices or ranks: declined
+    *stored_out = shards_[0]->store_gram(max_bytes, bytes_out, assemble_ms_out) ? 1 : 0;
+}
+
+template <typename T>
+void Solver<T>::drop_gram() {
+    LSSVM_REQUIRE(!in_cg_, "drop_gram cannot run between cg_begin and cg_finish");
+    for (auto &s : shards_) s->drop_gram();
+}
+
+template <typename T>
+void Solver<T>::matvec_stored(const void *D, size_t nv, void *Ret_inout, double add, int *stored_out) {
+    LSSVM_REQUIRE(D != nullptr && Ret_inout != nullptr, "The d / ret arrays may not be empty!");  // csvm.cpp:284-286
+    LSSVM_REQUIRE(nv > 0, "The number of vectors must be greater than 0!");
+    LSSVM_REQUIRE(add == 1.0 || add == -1.0, "add must either be -1.0 or 1.0, but is " + std::to_string(add) + "!");  // svm_kernel.cpp:28
+    LSSVM_REQUIRE(!in_cg_, "matvec_stored cannot run between cg_begin and cg_finish");
+    if (stored_out != nullptr) *stored_out = 0;
+    const size_t n = static_cast<size_t>(shards_[0]->n_);
+    const T *d = static_cast<const T *>(D);
+    T *ret = static_cast<T *>(Ret_inout);
+    if (!stored_applies()) {  // what lssvm_mi355_problem_matvec_pair_panels does, pair by pair
+        size_t c = 0;
+        for (; c + 1 < nv; c += 2) matvec_pair(d + c * n, d + (c + 1) * n, ret + c * n, ret + (c + 1) * n, add, nullptr, true);
+        if (c < nv) matvec(d + c * n, ret + c * n, add);
+        return;
+    }
+    matvec_on_lanes(d, nv, ret, add, LaneMode::stored);
+    if (stored_out != nullptr) *stored_out = 1;
+}
+
+template <typename T>
+void Solver<T>::solve_lockstep_stored(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out) {
+    if (!stored_applies()) {  // the call IS lssvm_mi355_problem_solve_lockstep_panels: its bits, its infos, its (pair | single) counts behind a zero
+        uint64_t two[2] = { 0, 0 };
+        solve_lockstep(Y, num_rhs, eps, max_iter, alphas_out, rhos_out, infos_out, two, true);
+        if (passes_out != nullptr) {
+            passes_out[0] = 0;
+            passes_out[1] = two[0];
+            passes_out[2] = two[1];
+        }
+        return;
+    }
+    LSSVM_REQUIRE(Y != nullptr, "The right hand side vector must not be empty!");
+    LSSVM_REQUIRE(num_rhs > 0, "The number of right hand sides must be greater than 0!");
+    LSSVM_REQUIRE(static_cast<T>(eps) > T(0), "The stopping criterion in the CG algorithm must be greater than 0.0, but is " + std::to_string(eps) + "!");  // csvm.cpp:77
+    LSSVM_REQUIRE(max_iter > 0, "The number of CG iterations must be greater than 0!");                                                                   // csvm.cpp:78
+    LSSVM_REQUIRE(alphas_out != nullptr && rhos_out != nullptr, "alpha_out / rho_out must not be NULL");
+    LSSVM_REQUIRE(!in_cg_, "solve_lockstep_stored cannot run between cg_begin and cg_finish");
+    if (passes_out != nullptr) passes_out[0] = passes_out[1] = passes_out[2] = 0;
+    solve_on_lanes(static_cast<const T *>(Y), num_rhs, eps, max_iter, static_cast<T *>(alphas_out), rhos_out, infos_out, passes_out, LaneMode::stored);
 }
 
 template <typename T>

@@ -479,6 +479,9 @@ class MI355CSVM(CSVM):
         data set and shared by all right-hand sides -- opt-in: it saves iterations where the kernel matrix has spectral decay and costs some where it has none; one device
         and no sample weights (both raise).  ``precond_landmarks``: None = the library's fixed choice of landmarks, ``"greedy"`` / ``"rpcholesky"`` = ``precond_rank`` points
         selected from the data (``backend.select_landmarks``).
+        ``"stored"`` = one device keeps the kernel matrix in HBM (``ResidentProblem.store_gram``) and every CG iteration streams it, sixteen right-hand
+        sides per pass (``ResidentProblem.solve_lockstep_stored``) -- opt-in: assembly and memory pay off over many iterations, many right-hand sides or wide data; where the
+        matrix does not fit, or on several devices, the solve is ``"cg"``'s.  ``last_lockstep_passes`` keeps ``(stored, two-vector, single-vector)`` Gram passes.
         ``lockstep``: how :meth:`solve_systems_of_linear_equations` takes several right-hand sides through a Gram pass on one device -- ``"pair"`` (default) = two per pass
         (``ResidentProblem.solve_lockstep``), ``"block"`` = sixteen per pass on the matrix cores (``ResidentProblem.solve_lockstep_block``) where
         that kernel applies (float64, rbf / polynomial, at most 256 features) and ``"pair"`` elsewhere, ``"block32"`` = ``"block"``, and float32 problems of at most
@@ -491,8 +494,8 @@ class MI355CSVM(CSVM):
         bootstraps RCCL inside the process, and that path has not run on a multi-GPU box yet."""
         if isinstance(target, Parameter):
             target, params = TargetPlatform.AUTOMATIC, target
-        if solver not in ("cg", "refined", "pcg"):
-            raise InvalidParameterError(f"solver must be 'cg' or 'refined' or 'pcg', but is {solver!r}!")
+        if solver not in ("cg", "refined", "pcg", "stored"):
+            raise InvalidParameterError(f"solver must be 'cg' or 'refined' or 'pcg' or 'stored', but is {solver!r}!")
         if solver == "pcg" and not (isinstance(precond_rank, (int, np.integer)) and 1 <= int(precond_rank) <= _capi.PRECOND_MAX_RANK):
             raise InvalidParameterError(f"precond_rank must lie in [1, {_capi.PRECOND_MAX_RANK}], but is {precond_rank!r}!")
         if lockstep not in ("pair", "block", "block32"):
@@ -529,6 +532,9 @@ class MI355CSVM(CSVM):
 
     def solve_system_of_linear_equations(self, params, A, b, eps, max_iter, sample_weight=None):
         self.last_refine_info = None
+        if self.solver == "stored" and self.use_devices == 1:  # one right-hand side through the stored lockstep
+            alphas, rhos, infos = self.solve_systems_of_linear_equations(params, A, np.asarray(b)[None, :], eps, max_iter, sample_weight=sample_weight)
+            return alphas[0], rhos[0], infos[0]
         if self.solver == "pcg":
             self._pcg_applies(sample_weight)
             return backend.solve_pcg(params, A, b, eps, max_iter, rank=self._pcg_rank(A), landmarks=self.precond_landmarks, options=self._options)
@@ -671,7 +677,10 @@ class MI355CSVM(CSVM):
         with backend.ResidentProblem(params, A, devices=[0], options=self._options) as prob:  # (device 0 alone, as the one-shot solve creates it)
             if sample_weight is not None:
                 prob.set_weights(sample_weight)
-            if self.lockstep in ("block", "block32"):
+            if self.solver == "stored":
+                prob.store_gram()  # (declined where it does not fit: the stored lockstep is then the panels lockstep)
+                alphas, rhos, infos, passes = prob.solve_lockstep_stored(B, eps, max_iter)
+            elif self.lockstep in ("block", "block32"):
                 alphas, rhos, infos, passes = prob.solve_lockstep_block(B, eps, max_iter, block32=self.lockstep == "block32")
             else:
                 alphas, rhos, infos, two = prob.solve_lockstep(B, eps, max_iter, panels=True)  # (one device: option rebalance_after has nothing to move)
