@@ -513,6 +513,19 @@ int lssvm_mi355_problem_matvec_stored(lssvm_mi355_problem *p, const void *D /* n
 int lssvm_mi355_problem_solve_lockstep_stored(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out /* num_rhs x N */,
                                               double *rhos_out, lssvm_cg_info *infos_out /* num_rhs, may be NULL */, uint64_t passes_out[3]);
 
+/* FACTORED forms (opt-in, routed by no default): for the LINEAR kernel K = X X^T exactly, so K V = X (X^T V) -- two reads of the resident data per
+ * pass instead of an n x n pass over Gram tiles, sixteen vectors per pass, either real type, any feature count, weighted or not, on one device and one rank.  The rank-one,
+ * diagonal and weight terms stay in the O(n) kernels.  The order of every sum depends on (N, padded features, real type) only: a vector's result neither on its slot nor on
+ * the other vectors, and a repeated call has the same bits.  The results agree with the n x n paths to the rounding of the FACTORED sums, not to the bit.
+ *   _matvec_factored: the contract of _matvec_stored; *factored_out (may be NULL) = 1 where the operator ran.
+ *   _solve_lockstep_factored: the contract of _solve_lockstep_stored, every Gram pass a factored pass; passes_out[3]: factored, two-vector, single-vector passes.
+ * Where the operator does not apply (rbf, polynomial, several devices or ranks) the calls ARE lssvm_mi355_problem_matvec_pair_panels (pair by pair) /
+ * _solve_lockstep_panels: their bits and infos, *factored_out = 0, passes_out[0] = 0. */
+#define LSSVM_FACTORED_SLAB_ROWS 512 /* rows of X behind one partial X_s^T V_s of a factored pass */
+int lssvm_mi355_problem_matvec_factored(lssvm_mi355_problem *p, const void *D /* nv x (N-1) */, size_t nv, void *Ret_inout /* nv x (N-1) */, double add, int *factored_out);
+int lssvm_mi355_problem_solve_lockstep_factored(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out /* num_rhs x N */,
+                                                double *rhos_out, lssvm_cg_info *infos_out /* num_rhs, may be NULL */, uint64_t passes_out[3]);
+
 /* COST PATH (no counterpart in the reference): the solutions of ONE right-hand side for EVERY cost of a grid from one multi-shift CG sequence -- one pass over the
  * Gram tiles per iteration for the whole grid instead of one per cost, as many iterations as the hardest (largest) cost alone needs.  For fixed data and kernel
  * function the cost enters the reduced system only as a shift: Abar(C) = A0 + sigma M with sigma = 1 / C, A0 v = K v + (k_NN S - q.v) 1 - S q (S = sum v) and

@@ -21,6 +21,7 @@ LSSVM_DTYPE_F64 = 1
 LSSVM_MEM_HOST = 0
 LSSVM_MEM_DEVICE = 1
 UNIQUE_ID_BYTES = 128
+FACTORED_SLAB_ROWS = 512  # LSSVM_FACTORED_SLAB_ROWS: rows of X behind one partial sum of a factored pass
 
 STATUS_NAMES = {0: "LSSVM_SUCCESS", -1: "LSSVM_ERR_INVALID_ARGUMENT", -2: "LSSVM_ERR_NO_DEVICE", -3: "LSSVM_ERR_HIP", -4: "LSSVM_ERR_COMM",
                 -5: "LSSVM_ERR_OUT_OF_MEMORY", -6: "LSSVM_ERR_INTERNAL"}
@@ -41,6 +42,7 @@ EXPORTED_SYMBOLS = [
     "lssvm_mi355_problem_matvec_pair", "lssvm_mi355_problem_solve_lockstep", "lssvm_mi355_problem_matvec_pair_panels", "lssvm_mi355_problem_solve_lockstep_panels",
     "lssvm_mi355_problem_matvec_block", "lssvm_mi355_problem_solve_lockstep_block", "lssvm_mi355_problem_matvec_block32", "lssvm_mi355_problem_solve_lockstep_block32",
     "lssvm_mi355_problem_store_gram", "lssvm_mi355_problem_drop_gram", "lssvm_mi355_problem_matvec_stored", "lssvm_mi355_problem_solve_lockstep_stored",
+    "lssvm_mi355_problem_matvec_factored", "lssvm_mi355_problem_solve_lockstep_factored",
     "lssvm_mi355_problem_solve_cost_path", "lssvm_mi355_solve_cost_path_f32", "lssvm_mi355_solve_cost_path_f64",
     "lssvm_mi355_problem_build_preconditioner", "lssvm_mi355_problem_precond_landmarks", "lssvm_mi355_problem_precond_apply", "lssvm_mi355_problem_solve_pcg",
     "lssvm_mi355_solve_pcg_f32", "lssvm_mi355_solve_pcg_f64",
@@ -204,14 +206,14 @@ def predictor_multi_entry(name: str):
 
 
 def lockstep_entry(name: str):
-    """``lssvm_mi355_problem_solve_lockstep`` / ``lssvm_mi355_problem_matvec_pair`` and their ``_panels``, ``_block`` and ``_stored`` forms (``lssvm_mi355_problem_store_gram`` / ``_drop_gram`` included) with their argument types.  Bound at the first call, like the weighted entry points."""
+    """``lssvm_mi355_problem_solve_lockstep`` / ``lssvm_mi355_problem_matvec_pair`` and their ``_panels``, ``_block``, ``_stored`` and ``_factored`` forms (``lssvm_mi355_problem_store_gram`` / ``_drop_gram`` included) with their argument types.  Bound at the first call, like the weighted entry points."""
     fn = getattr(lib, name)
     if fn.argtypes is None:
         if name == "lssvm_mi355_problem_store_gram":
             fn.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.POINTER(C.c_double)]
         elif name == "lssvm_mi355_problem_drop_gram":
             fn.argtypes = [C.c_void_p]
-        elif name in ("lssvm_mi355_problem_matvec_block", "lssvm_mi355_problem_matvec_block32", "lssvm_mi355_problem_matvec_stored"):
+        elif name in ("lssvm_mi355_problem_matvec_block", "lssvm_mi355_problem_matvec_block32", "lssvm_mi355_problem_matvec_stored", "lssvm_mi355_problem_matvec_factored"):
             fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_double, C.POINTER(C.c_int)]
         elif name.startswith("lssvm_mi355_problem_solve_lockstep"):
             fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_uint64, C.c_void_p, C.POINTER(C.c_double), C.POINTER(LssvmCgInfo), C.POINTER(C.c_uint64)]

@@ -1254,6 +1254,32 @@ class ResidentProblem:
         check(_capi.lockstep_entry("lssvm_mi355_problem_solve_lockstep_stored")(self._h, ptr(B), k, eps, int(max_iter), ptr(alphas), rhos.ctypes.data_as(C.POINTER(C.c_double)), infos, passes))
         return alphas, rhos.astype(self.dtype), [info.as_dict() for info in infos], tuple(int(x) for x in passes)
 
+    def matvec_factored(self, D, Ret=None, add: float = 1.0):
+        """:meth:`matvec_block` through the factored linear-kernel operator (``lssvm_mi355_problem_matvec_factored``): ``K V = X (X^T V)``, sixteen
+        rows of ``D`` per two reads of the data, either real type, any feature count.  Returns ``(out, ran)``; for another kernel function or on several devices the rows
+        go through :meth:`matvec_pair` with ``panels=True`` and ``ran`` is false.  ``Ret=None``: zeros."""
+        D = np.ascontiguousarray(D, dtype=self.dtype)
+        out = np.zeros_like(D) if Ret is None else np.array(Ret, dtype=self.dtype, copy=True, order="C")
+        if not (D.ndim == 2 and D.shape[0] > 0 and D.shape == out.shape and D.shape[1] == self.num_points - 1):
+            raise InvalidParameterError(f"Sizes mismatch!: {D.shape} / {out.shape} != (k, {self.num_points - 1})")
+        ran = C.c_int(0)
+        check(_capi.lockstep_entry("lssvm_mi355_problem_matvec_factored")(self._h, ptr(D), D.shape[0], ptr(out), add, C.byref(ran)))
+        return out, bool(ran.value)
+
+    def solve_lockstep_factored(self, B, eps: float, max_iter: int):
+        """:meth:`solve_lockstep_block` with every Gram pass a factored pass (``lssvm_mi355_problem_solve_lockstep_factored``).  Returns ``(alphas, rhos, infos, passes)``
+        with ``passes = (factored, two-vector, single-vector)``; where the operator does not apply the call is ``solve_lockstep(..., panels=True)`` and ``passes[0]`` is 0."""
+        B = np.ascontiguousarray(B, dtype=self.dtype)
+        if B.ndim != 2 or B.shape[0] == 0 or B.shape[1] != self.num_points:
+            raise InvalidParameterError(f"The number of data points in the matrix A ({self.num_points}) and the values in every right hand side vector ({B.shape[-1] if B.ndim else 0}) must be the same!")
+        k = B.shape[0]
+        alphas = np.zeros_like(B)
+        rhos = np.zeros(k, dtype=np.float64)
+        infos = (LssvmCgInfo * k)()
+        passes = (C.c_uint64 * 3)()
+        check(_capi.lockstep_entry("lssvm_mi355_problem_solve_lockstep_factored")(self._h, ptr(B), k, eps, int(max_iter), ptr(alphas), rhos.ctypes.data_as(C.POINTER(C.c_double)), infos, passes))
+        return alphas, rhos.astype(self.dtype), [info.as_dict() for info in infos], tuple(int(x) for x in passes)
+
     def solve_cost_path(self, y, costs, eps: float, max_iter: int, verify: bool = True):
         """:func:`solve_cost_path` on this resident problem (``lssvm_mi355_problem_solve_cost_path``): every cost of ``costs`` from one multi-shift CG sequence on the
         problem's own single-vector pass.  The problem's own cost is ignored and the problem is left as it was.  Not on a problem of several devices or ranks, not with

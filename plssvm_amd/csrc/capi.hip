@@ -885,7 +885,29 @@ int lssvm_mi355_problem_solve_lockstep_stored(lssvm_mi355_problem *p, const void
         impl_of(p)->solve_lockstep_stored(Y, num_rhs, eps, max_iter, alphas_out, rhos_out, infos_out, passes_out);
     });
 }
-static_assert(sizeof(lssvm_path_info) == 48, "lssvm_path_info changed: plssvm_amd/_capi.py (LssvmPathInfo) changes with it");
+int lssvm_mi355_problem_matvec_factored(lssvm_mi355_problem *p, const void *D, size_t nv, void *Ret_inout, double add, int *factored_out) {
+    return guarded([&] {
+        LSSVM_REQUIRE(p != nullptr, "problem handle must not be NULL");
+        LSSVM_REQUIRE(D != nullptr && Ret_inout != nullptr, "The d / ret arrays may not be empty!");                                          // csvm.cpp:284-286
+        LSSVM_REQUIRE(nv > 0, "The number of vectors must be greater than 0!");
+        LSSVM_REQUIRE(add == 1.0 || add == -1.0, "add must either be -1.0 or 1.0, but is " + std::to_string(add) + "!");                       // svm_kernel.cpp:28
+        impl_of(p)->matvec_factored(D, nv, Ret_inout, add, factored_out);
+    });
+}
+int lssvm_mi355_problem_solve_lockstep_factored(lssvm_mi355_problem *p, const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out,
+                                                lssvm_cg_info *infos_out, uint64_t passes_out[3]) {
+    return guarded([&] {
+        // (before any device work; the solver repeats the tests that need the real type)
+        LSSVM_REQUIRE(p != nullptr, "problem handle must not be NULL");
+        LSSVM_REQUIRE(num_rhs > 0, "The number of right hand sides must be greater than 0!");
+        LSSVM_REQUIRE(Y != nullptr, "The number of data points in the matrix A and the values in the right hand side vector must be the same!");  // csvm.cpp:76
+        LSSVM_REQUIRE(eps > 0.0, "The stopping criterion in the CG algorithm must be greater than 0.0, but is " + std::to_string(eps) + "!");      // csvm.cpp:77
+        LSSVM_REQUIRE(max_iter > 0, "The number of CG iterations must be greater than 0!");                                                      // csvm.cpp:78
+        LSSVM_REQUIRE(alphas_out != nullptr && rhos_out != nullptr, "alpha_out / rho_out must not be NULL");
+        impl_of(p)->solve_lockstep_factored(Y, num_rhs, eps, max_iter, alphas_out, rhos_out, infos_out, passes_out);
+    });
+}
+static_assert(sizeof(lssvm_path_info) == 48,"lssvm_path_info changed: plssvm_amd/_capi.py (LssvmPathInfo) changes with it");
 int lssvm_mi355_problem_solve_cost_path(lssvm_mi355_problem *p, const void *y, const double *costs, size_t num_costs, double eps, uint64_t max_iter, int verify, void *alphas_out,
                                         double *rhos_out, lssvm_path_info *infos_out, uint64_t passes_out[2]) {
     return guarded([&] {

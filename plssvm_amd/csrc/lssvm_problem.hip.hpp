@@ -441,6 +441,12 @@ class Problem {
     /* Kv[u] <- K * v[u], u < nv (1 ... 16), from ONE pass over the stored triangle (tile_symm_stored + k_fold_stored).  A vector's result does not depend on nv, on its
      * slot or on the other vectors.  `ev`: HIP events around the tile pass, or NULL. */
     void enqueue_apply_K_stored(const T *const *v, T *const *Kv, int nv, hipEvent_t ev_begin, hipEvent_t ev_end);
+    /* ---- the factored linear-kernel operator (lssvm_factored.hip): K V = X (X^T V) from two reads of the resident data.  Applies to the linear kernel
+     * on an unsharded problem, whatever the options: it touches neither planes nor tiles. ---- */
+    bool factored_applies() const { return params_.kernel_type == LSSVM_KERNEL_LINEAR && world_ == 1 && n_ >= 1; }
+    /* Kv[u] <- K * v[u], u < nv (1 ... 16), from ONE factored pass (k_factored_gather, _fold, _scatter); its buffers are allocated by the first call.  A vector's result
+     * does not depend on nv, on its slot or on the other vectors.  `ev`: HIP events around the three launches, or NULL. */
+    void enqueue_apply_K_factored(const T *const *v, T *const *Kv, int nv, hipEvent_t ev_begin, hipEvent_t ev_end);
 
   private:
     friend class Solver<T>;
@@ -537,6 +543,8 @@ class Problem {
     DevBuf<T> gram_, gram_vp_, gram_rowpart_, gram_colrec_;  // the stored triangle (tile packed), the packed vectors of a pass, its row slabs and its column records
     DevBuf<int2> gram_items_;                                // ... and its work items (row block, column chunk), longest first
     int gram_num_items_ = 0, gram_grid_ = 1;                 // ... dealt round robin to gram_grid_ persistent workgroups
+    DevBuf<T> fact_vp_, fact_wpart_, fact_wp_;               // a factored pass: the packed vectors, the slabs' partial X_s^T V_s and their sum, k-major
+    int fact_grid_ = 1;                                      // ... over fact_grid_ persistent workgroups
     void build_block_geometry(hipStream_t st);
     double QA_cost_ = 0.0;
     double inv_cost_ = 1.0;
@@ -666,6 +674,10 @@ struct ProblemBase {
     virtual void matvec_stored(const void *D, size_t nv, void *Ret_inout, double add, int *stored_out) = 0;      // lssvm_mi355_problem_matvec_stored
     virtual void solve_lockstep_stored(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out,
                                        uint64_t *passes_out) = 0;  // lssvm_mi355_problem_solve_lockstep_stored
+    /* the _factored entry points (lssvm_factored.hip): K V = X (X^T V) for the linear kernel, sixteen vectors per pass; where it does not apply they ARE the _panels calls */
+    virtual void matvec_factored(const void *D, size_t nv, void *Ret_inout, double add, int *factored_out) = 0;  // lssvm_mi355_problem_matvec_factored
+    virtual void solve_lockstep_factored(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out,
+                                         uint64_t *passes_out) = 0;  // lssvm_mi355_problem_solve_lockstep_factored
     virtual void solve_cost_path(const void *y, const double *costs, size_t num_costs, double eps, uint64_t max_iter, bool verify, void *alphas_out, double *rhos_out,
                                  lssvm_path_info *infos_out, uint64_t *passes_out) = 0;  // lssvm_mi355_problem_solve_cost_path
     /* the Nystrom preconditioner and PCG on it (lssvm_precond.hip) */
@@ -809,6 +821,8 @@ class Solver final : public ProblemBase {
     void drop_gram() override;
     void matvec_stored(const void *D, size_t nv, void *Ret_inout, double add, int *stored_out) override;
     void solve_lockstep_stored(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out) override;
+    void matvec_factored(const void *D, size_t nv, void *Ret_inout, double add, int *factored_out) override;
+    void solve_lockstep_factored(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out) override;
     /* every cost of a grid from ONE multi-shift CG sequence on this problem's single-vector pass (lssvm_path.hip) */
     void solve_cost_path(const void *y, const double *costs, size_t num_costs, double eps, uint64_t max_iter, bool verify, void *alphas_out, double *rhos_out, lssvm_path_info *infos_out,
                          uint64_t *passes_out) override;
@@ -874,6 +888,7 @@ class Solver final : public ProblemBase {
     Problem<T> &shard0() { return *shards_[0]; }
     bool block_applies(bool block32 = false) const;  // ... where the sixteen-vector kernel applies (Problem<T>::block_kernel_applies; fp32 only for the _block32 entry points)
     bool stored_applies() const;                  // ... where a stored kernel matrix serves the passes (Problem<T>::gram_stored on one unsharded device)
+    bool factored_applies() const;                // ... where the factored operator serves them (Problem<T>::factored_applies on one unsharded device)
     bool lanes_apply(bool panels = false) const;  // one unsharded device without an exchange, where the two-vector kernel applies (`panels`: or the two-vector panel kernel)
     void wait_for_deltas();    // the host waits for what shard 0's stream holds: the deltas of the step are in their host words
     /* until the returned object goes: no other solve may begin on this handle, and its weights stay */
@@ -893,12 +908,12 @@ class Solver final : public ProblemBase {
     void reset_cg(double eps, double y_last);  // cg_begin, cg_begin_from_zero: the host's counters and scalars of a new solve
     void read_delta0(double t0);               // ... and their end: delta0 is read, the handle is between begin and finish
     void solve_in_sequence(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out);
-    /* how the lanes of a lockstep solve share Gram passes: in pairs (an odd lane alone); `block` / `stored`: the active lanes grouped in sixteens, every Gram pass a pass of
-     * the sixteen-vector kernel / over the stored kernel matrix (passes_out[0] then counts them, [1] and [2] stay 0) */
-    enum class LaneMode { pairs, block, stored };
+    /* how the lanes of a lockstep solve share Gram passes: in pairs (an odd lane alone); `block` / `stored` / `factored`: the active lanes grouped in sixteens, every Gram
+     * pass a pass of the sixteen-vector kernel / over the stored kernel matrix / of the factored operator (passes_out[0] then counts them, [1] and [2] stay 0) */
+    enum class LaneMode { pairs, block, stored, factored };
     void solve_on_lanes(const T *Y, size_t num_rhs, double eps, uint64_t max_iter, T *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out,
                         LaneMode mode = LaneMode::pairs);
-    /* matvec() per vector on up to sixteen lanes around ONE sixteen-vector pass per group: the block kernel's, or the stored matrix's */
+    /* matvec() per vector on up to sixteen lanes around ONE sixteen-vector pass per group: the block kernel's, the stored matrix's or the factored operator's */
     void matvec_on_lanes(const T *d, size_t nv, T *ret, double add, LaneMode mode);
     Problem<T> &precond_problem(const char *what);                        // the checks every preconditioner entry point shares; shard 0
     void enqueue_precond_apply(const T *r, T *z, double *part_rz) const;  // z = r - Bhat G^-1 Bhat^T r and the partial sums of r.z

@@ -672,6 +672,8 @@ void Solver<T>::solve_on_lanes(const T *Y, size_t num_rhs, double eps, uint64_t 
                 t.group = g;
                 if (mode == LaneMode::stored) {
                     p.enqueue_apply_K_stored(v, Kv, static_cast<int>(g), t.a.e, t.b.e);
+                } else if (mode == LaneMode::factored) {
+                    p.enqueue_apply_K_factored(v, Kv, static_cast<int>(g), t.a.e, t.b.e);
                 } else {
                     p.enqueue_apply_K_block(v, Kv, static_cast<int>(g), t.a.e, t.b.e);
                 }
@@ -828,6 +830,8 @@ void Solver<T>::matvec_on_lanes(const T *d, size_t nv, T *ret, double add, LaneM
         }
         if (mode == LaneMode::stored) {
             p.enqueue_apply_K_stored(v, Kv, static_cast<int>(g), nullptr, nullptr);
+        } else if (mode == LaneMode::factored) {
+            p.enqueue_apply_K_factored(v, Kv, static_cast<int>(g), nullptr, nullptr);
         } else {
             p.enqueue_apply_K_block(v, Kv, static_cast<int>(g), nullptr, nullptr);
         }
@@ -925,6 +929,54 @@ void Solver<T>::solve_lockstep_stored(const void *Y, size_t num_rhs, double eps,
     LSSVM_REQUIRE(!in_cg_, "solve_lockstep_stored cannot run between cg_begin and cg_finish");
     if (passes_out != nullptr) passes_out[0] = passes_out[1] = passes_out[2] = 0;
     solve_on_lanes(static_cast<const T *>(Y), num_rhs, eps, max_iter, static_cast<T *>(alphas_out), rhos_out, infos_out, passes_out, LaneMode::stored);
+}
+
+/* ------------------------------------------------------------------ the factored linear-kernel operator: matvec_factored, the factored lockstep CG ------------------------------------------------------------------ */
+template <typename T>
+bool Solver<T>::factored_applies() const {
+    return shards_.size() == 1 && world_ == 1 && exchange_ == Exchange::none && shards_[0]->factored_applies();
+}
+
+template <typename T>
+void Solver<T>::matvec_factored(const void *D, size_t nv, void *Ret_inout, double add, int *factored_out) {
+    LSSVM_REQUIRE(D != nullptr && Ret_inout != nullptr, "The d / ret arrays may not be empty!");  // csvm.cpp:284-286
+    LSSVM_REQUIRE(nv > 0, "The number of vectors must be greater than 0!");
+    LSSVM_REQUIRE(add == 1.0 || add == -1.0, "add must either be -1.0 or 1.0, but is " + std::to_string(add) + "!");  // svm_kernel.cpp:28
+    LSSVM_REQUIRE(!in_cg_, "matvec_factored cannot run between cg_begin and cg_finish");
+    if (factored_out != nullptr) *factored_out = 0;
+    const size_t n = static_cast<size_t>(shards_[0]->n_);
+    const T *d = static_cast<const T *>(D);
+    T *ret = static_cast<T *>(Ret_inout);
+    if (!factored_applies()) {  // what lssvm_mi355_problem_matvec_pair_panels does, pair by pair
+        size_t c = 0;
+        for (; c + 1 < nv; c += 2) matvec_pair(d + c * n, d + (c + 1) * n, ret + c * n, ret + (c + 1) * n, add, nullptr, true);
+        if (c < nv) matvec(d + c * n, ret + c * n, add);
+        return;
+    }
+    matvec_on_lanes(d, nv, ret, add, LaneMode::factored);
+    if (factored_out != nullptr) *factored_out = 1;
+}
+
+template <typename T>
+void Solver<T>::solve_lockstep_factored(const void *Y, size_t num_rhs, double eps, uint64_t max_iter, void *alphas_out, double *rhos_out, lssvm_cg_info *infos_out, uint64_t *passes_out) {
+    if (!factored_applies()) {  // the call IS lssvm_mi355_problem_solve_lockstep_panels: its bits, its infos, its (pair | single) counts behind a zero
+        uint64_t two[2] = { 0, 0 };
+        solve_lockstep(Y, num_rhs, eps, max_iter, alphas_out, rhos_out, infos_out, two, true);
+        if (passes_out != nullptr) {
+            passes_out[0] = 0;
+            passes_out[1] = two[0];
+            passes_out[2] = two[1];
+        }
+        return;
+    }
+    LSSVM_REQUIRE(Y != nullptr, "The right hand side vector must not be empty!");
+    LSSVM_REQUIRE(num_rhs > 0, "The number of right hand sides must be greater than 0!");
+    LSSVM_REQUIRE(static_cast<T>(eps) > T(0), "The stopping criterion in the CG algorithm must be greater than 0.0, but is " + std::to_string(eps) + "!");  // csvm.cpp:77
+    LSSVM_REQUIRE(max_iter > 0, "The number of CG iterations must be greater than 0!");                                                                   // csvm.cpp:78
+    LSSVM_REQUIRE(alphas_out != nullptr && rhos_out != nullptr, "alpha_out / rho_out must not be NULL");
+    LSSVM_REQUIRE(!in_cg_, "solve_lockstep_factored cannot run between cg_begin and cg_finish");
+    if (passes_out != nullptr) passes_out[0] = passes_out[1] = passes_out[2] = 0;
+    solve_on_lanes(static_cast<const T *>(Y), num_rhs, eps, max_iter, static_cast<T *>(alphas_out), rhos_out, infos_out, passes_out, LaneMode::factored);
 }
 
 template <typename T>

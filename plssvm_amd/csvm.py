@@ -487,6 +487,9 @@ class MI355CSVM(CSVM):
         that kernel applies (float64, rbf / polynomial, at most 256 features) and ``"pair"`` elsewhere, ``"block32"`` = ``"block"``, and float32 problems of at most
         128 padded features sixteen per pass as well (``solve_lockstep_block(..., block32=True)``).  Opt-in: a column's bits are those of the block call with that
         right-hand side alone, not those of the one-shot solve.  ``last_lockstep_passes`` keeps ``(block, two-vector, single-vector)`` Gram passes of the last such call.
+        ``"factored"`` = a LINEAR-kernel problem on one device (with ``solver="cg"``) applies ``K V = X (X^T V)`` instead of the n x n Gram pass, sixteen right-hand sides per
+        two reads of the data (``ResidentProblem.solve_lockstep_factored``), the single solve included; every other problem behaves as ``"pair"``.
+        Opt-in: the sums are the factored ones, so the results agree with the default's to their rounding, not to the bit; it does not pay on few points with very many features.
 
         ``num_devices``: devices ONE solve is sharded over -- 1 (default) = device 0 only, k = devices 0 .. k-1 (gpu_csvm.hpp:283-299),
         0 = automatic (every visible device, at least 4096 points each, as the reference's backends take every device they find,
@@ -498,8 +501,8 @@ class MI355CSVM(CSVM):
             raise InvalidParameterError(f"solver must be 'cg' or 'refined' or 'pcg' or 'stored', but is {solver!r}!")
         if solver == "pcg" and not (isinstance(precond_rank, (int, np.integer)) and 1 <= int(precond_rank) <= _capi.PRECOND_MAX_RANK):
             raise InvalidParameterError(f"precond_rank must lie in [1, {_capi.PRECOND_MAX_RANK}], but is {precond_rank!r}!")
-        if lockstep not in ("pair", "block", "block32"):
-            raise InvalidParameterError(f"lockstep must be 'pair', 'block' or 'block32', but is {lockstep!r}!")
+        if lockstep not in ("pair", "block", "block32", "factored"):
+            raise InvalidParameterError(f"lockstep must be 'pair', 'block' or 'block32' or 'factored', but is {lockstep!r}!")
         if precond_landmarks is not None and precond_landmarks not in _capi.LANDMARK_METHODS:
             raise InvalidParameterError(f"precond_landmarks must be None or one of {sorted(_capi.LANDMARK_METHODS)}, but is {precond_landmarks!r}!")
         super().__init__(params, **kwargs)
@@ -532,7 +535,7 @@ class MI355CSVM(CSVM):
 
     def solve_system_of_linear_equations(self, params, A, b, eps, max_iter, sample_weight=None):
         self.last_refine_info = None
-        if self.solver == "stored" and self.use_devices == 1:  # one right-hand side through the stored lockstep
+        if (self.solver == "stored" or self._factored(params)) and self.use_devices == 1:  # one right-hand side through the stored / factored lockstep
             alphas, rhos, infos = self.solve_systems_of_linear_equations(params, A, np.asarray(b)[None, :], eps, max_iter, sample_weight=sample_weight)
             return alphas[0], rhos[0], infos[0]
         if self.solver == "pcg":
@@ -636,6 +639,10 @@ class MI355CSVM(CSVM):
         """``precond_rank``, but never more landmarks than the reduced system has rows."""
         return max(1, min(self.precond_rank, backend._as_matrix(A).shape[0] - 1))
 
+    def _factored(self, params) -> bool:
+        """lockstep="factored" applies: the plain CG of a linear-kernel problem on one device."""
+        return self.lockstep == "factored" and self.solver == "cg" and self.use_devices == 1 and params.kernel_type == KernelFunctionType.LINEAR
+
     def _refines(self, A) -> bool:
         """solver="refined" applies: float64 data on one device."""
         return self.solver == "refined" and self.use_devices == 1 and backend._as_matrix(A).dtype == np.float64
@@ -680,6 +687,8 @@ class MI355CSVM(CSVM):
             if self.solver == "stored":
                 prob.store_gram()  # (declined where it does not fit: the stored lockstep is then the panels lockstep)
                 alphas, rhos, infos, passes = prob.solve_lockstep_stored(B, eps, max_iter)
+            elif self._factored(params):
+                alphas, rhos, infos, passes = prob.solve_lockstep_factored(B, eps, max_iter)
             elif self.lockstep in ("block", "block32"):
                 alphas, rhos, infos, passes = prob.solve_lockstep_block(B, eps, max_iter, block32=self.lockstep == "block32")
             else:
