@@ -350,6 +350,28 @@ int lssvm_mi355_predictor_create_block(lssvm_mi355_predictor **out, const lssvm_
 int lssvm_mi355_predictor_create_block32(lssvm_mi355_predictor **out, const lssvm_params *params, int dtype, const void *support_vectors, size_t num_support_vectors,
                                          size_t num_features, const void *alphas, const double *rhos, size_t num_vectors, const lssvm_mi355_options *options);
 
+/* The `create_block32` handle once more, with the fp32 models of MORE than 128 padded features taken sixteen weight vectors per pass as well: the full-square kernel
+ * that walks 128-feature panels inside a tile, with the transposed first product and the second product on the fp32 matrix cores of the narrow block kernel
+ * (tile_matvec_f32_blk_wide) -- a ten-class model on 784-feature image data takes one pass over the Gram rectangle per batch where
+ * `create_panels` takes five.  Opt-in; no other entry point routes here.  Arguments, their validation and the error texts are those of `create_block32`, refused before a
+ * device is touched; `predict`, `predict_multi` and `destroy` work on the handle as on any other.
+ * The block panel form: dtype LSSVM_DTYPE_F32, a split Gram mode, more than 128 padded features, the polynomial kernel with degree >= 0 or rbf whose support vectors lie
+ * within the folded form's range (option rbf_fold != 0).  The model is resident as `create_panels` keeps its fp32 panel form -- centred support vectors, norms, operand
+ * planes padded to whole 128-feature panels, at EVERY width above 128 (one layout, one kernel: a 129 ... 512-feature model is kept in panel layout too, not in the one-pass
+ * kernels') --, plus the packed 4 KiB record per 64 columns and group of sixteen vectors (a last group of fewer padded with zero vectors).  A batch is prepared and
+ * chunked as the panel form does it and runs on the new kernel, one launch per group.  lssvm_predict_info: resident == 1, vectors_per_launch == 16.
+ * Values: each kernel value is produced by the single-vector panel kernel's own chain of operations; the sum over the columns is taken four columns at a time by the
+ * matrix cores -- NOT the pair form's bits; the difference is a few eps of the summand scale sum_j |alpha_j k_ij| (tests/test_gpu_predictor_block_panels.py).  The order
+ * of every sum depends on the shapes only: a call repeats bit for bit, and a column has the bits of its vector alone in any slot and any group size.
+ * At most 128 padded features, or dtype LSSVM_DTYPE_F64: the call IS `create_block32` (for fp64 that is `create_block`).  Every other fp32 model above 128 padded
+ * features -- the linear kernel, gram_mode = 0, tile_kernel = 1, rbf_form = 1 / 3, rbf_fold = 0 or an exponent scale beyond the folded form, a negative degree -- : the
+ * call IS `create_panels`, its handle, bits and info.  A batch the panel form declines (the f16 check beside f16 planes, an exponent scale beyond the norm expansion)
+ * takes the path, bits and info it takes under `create_panels`; an rbf batch beyond the folded form's range runs unfolded on the panel kernels, on this handle's panel
+ * layout, one vector per launch.
+ * Where it pays and where it LOSES (one or two vectors): README, "Sixteen fp32 decision functions per pass on wide models". */
+int lssvm_mi355_predictor_create_block_panels(lssvm_mi355_predictor **out, const lssvm_params *params, int dtype, const void *support_vectors, size_t num_support_vectors,
+                                              size_t num_features, const void *alphas, const double *rhos, size_t num_vectors, const lssvm_mi355_options *options);
+
 /* ------------------------------------------------------------------------------------------------------------------ */
 /* fine-grained entry points for kernel-level parity tests: the protected members the reference's backend tests re-export  */
 /* (tests/backends/HIP/mock_hip_csvm.hpp:22-44): generate_q, run_device_kernel, calculate_w                           */

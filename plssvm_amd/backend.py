@@ -777,10 +777,16 @@ class Predictor:
     (``info_out["vectors_per_launch"] == 16``; a split Gram mode, at most 128 features, polynomial with ``degree >= 0`` or rbf within the folded form's range), the
     second product on the fp32 matrix cores.  Values are a few eps of the summand scale from those of ``every_form=True``, not their bits; a column has the bits of its
     vector alone.  Every other float32 model behaves as with ``every_form=True``, a float64 one as with ``block=True``.  It LOSES for one or two vectors and at few
-    features (profiles/predictor_block_f32.json); it wins over ``block`` and ``panels``."""
+    features (profiles/predictor_block_f32.json); it wins over ``block`` and ``panels``.
+
+    ``block_panels=True`` creates the model through ``lssvm_mi355_predictor_create_block_panels``: ``block32=True``, and a FLOAT32 model of MORE than 128 padded features
+    sixteen weight vectors per pass as well (``info_out["vectors_per_launch"] == 16``; a split Gram mode, polynomial with ``degree >= 0`` or rbf within the folded
+    form's range), on the kernel that walks 128-feature panels inside a tile.  Values are a few eps of the summand scale from those of ``panels=True``, not their bits; a
+    column has the bits of its vector alone.  Every other float32 model above 128 features behaves as with ``panels=True``, everything else as with ``block32=True``.
+    It loses for one or two vectors; it wins over every other flag."""
 
     def __init__(self, params: Parameter, support_vectors, alpha, rho, options: Options | None = None, every_form: bool = False, panels: bool = False, block: bool = False,
-                 block32: bool = False):
+                 block32: bool = False, block_panels: bool = False):
         sv = _as_matrix(support_vectors)
         alpha = np.ascontiguousarray(alpha, dtype=sv.dtype)
         self.dtype, self.num_features = sv.dtype, int(sv.shape[1])
@@ -799,10 +805,10 @@ class Predictor:
             if alpha.size != sv.shape[0]:
                 raise InvalidParameterError(f"The number of support vectors ({sv.shape[0]}) and number of weights ({alpha.size}) must be the same!")
             self.num_vectors = None  # (one weight vector: the values are a vector, not a matrix of one column)
-            k, rhos = 1, np.array([float(rho)], dtype=np.float64)  # (every_form / panels / block / block32: a handle of one vector, used through lssvm_mi355_predictor_predict like any other)
+            k, rhos = 1, np.array([float(rho)], dtype=np.float64)  # (every_form / panels / block / block32 / block_panels: a handle of one vector, used through lssvm_mi355_predictor_predict like any other)
         ps = _params_struct(params, sv.shape[1])
-        if alpha.ndim == 2 or every_form or panels or block or block32:
-            create = "lssvm_mi355_predictor_create_block32" if block32 else "lssvm_mi355_predictor_create_block" if block else "lssvm_mi355_predictor_create_panels" if panels else ("lssvm_mi355_predictor_create_resident" if every_form else "lssvm_mi355_predictor_create_multi")
+        if alpha.ndim == 2 or every_form or panels or block or block32 or block_panels:
+            create = "lssvm_mi355_predictor_create_block_panels" if block_panels else "lssvm_mi355_predictor_create_block32" if block32 else "lssvm_mi355_predictor_create_block" if block else "lssvm_mi355_predictor_create_panels" if panels else ("lssvm_mi355_predictor_create_resident" if every_form else "lssvm_mi355_predictor_create_multi")
             check(_capi.predictor_multi_entry(create)(C.byref(self._h), C.byref(ps), _capi.dtype_code(sv.dtype), ptr(sv), sv.shape[0], sv.shape[1], ptr(alpha),
                                                       rhos.ctypes.data_as(C.POINTER(C.c_double)), k, options_ptr(options)))
             return

@@ -514,6 +514,10 @@ int lssvm_mi355_predictor_create_block32(lssvm_mi355_predictor **out, const lssv
                                          size_t num_features, const void *alphas, const double *rhos, size_t num_vectors, const lssvm_mi355_options *options) {
     return create_predictor_of_vectors(out, params, dtype, support_vectors, num_support_vectors, num_features, alphas, rhos, num_vectors, options, lssvm::FORMS_BLOCK32);
 }
+int lssvm_mi355_predictor_create_block_panels(lssvm_mi355_predictor **out, const lssvm_params *params, int dtype, const void *support_vectors, size_t num_support_vectors,
+                                              size_t num_features, const void *alphas, const double *rhos, size_t num_vectors, const lssvm_mi355_options *options) {
+    return create_predictor_of_vectors(out, params, dtype, support_vectors, num_support_vectors, num_features, alphas, rhos, num_vectors, options, lssvm::FORMS_BLOCK_PANELS);
+}
 int lssvm_mi355_predictor_predict(lssvm_mi355_predictor *predictor, const void *predict_points, int mem_kind, size_t num_predict_points, void *out, lssvm_predict_info *info) {
     return guarded([&] {
         LSSVM_REQUIRE(predictor != nullptr, "predictor handle must not be NULL");

@@ -462,14 +462,18 @@ class ResidentF32 {
   public:
     static constexpr bool declines_batches = true;  // (the one-shot path's inputs stay needed: alpha on the host, the support vectors through fetch_support_vectors)
 
-    /* `block32` (lssvm_mi355_predictor_create_block32): beside everything the form keeps, the records of tile_matvec_f32_blk for every group of sixteen vectors, where
-     * that kernel applies */
-    bool prepare(const PredictModel<float> &m, const float *sv, const float *alpha, int forms, bool block32, hipStream_t s) {
-        const bool resident = prepare_or_decline(m, sv, alpha, forms, s);
+    enum BlockForm { BLOCK_NONE, BLOCK_NARROW, BLOCK_PANELS };
+
+    /* BLOCK_NARROW (lssvm_mi355_predictor_create_block32): beside everything the form keeps, the records of tile_matvec_f32_blk for every group of sixteen vectors, where
+     * that kernel applies.  BLOCK_PANELS (lssvm_mi355_predictor_create_block_panels, more than 128 padded features, `forms` == FORMS_PANELS): where
+     * tile_matvec_f32_blk_wide applies, the model is kept in PANEL layout at every width -- the 129 ... 512 features of the one-pass kernels included: one layout, one
+     * kernel -- with the same records beside it; where it does not, the model is the FORMS_PANELS one in everything */
+    bool prepare(const PredictModel<float> &m, const float *sv, const float *alpha, int forms, BlockForm block_form, hipStream_t s) {
+        const bool resident = prepare_or_decline(m, sv, alpha, forms, block_form == BLOCK_PANELS, s);
         if (!resident) {
             reset();
-        } else if (block32) {
-            prepare_block(m, s);
+        } else if (block_form != BLOCK_NONE) {
+            prepare_block(m, block_form, s);
         }
         return resident;
     }
@@ -490,14 +494,24 @@ class ResidentF32 {
         planesS_.buf.release();
     }
 
+    /* the forms both sixteen-vector kernels exist in: a polynomial of degree >= 0 (no pad-column rule), rbf whose support vectors lie within the folded form's range */
+    static bool block_form_ok(const PredictModel<float> &m, double r2_sv) {
+        if (m.params.kernel_type == LSSVM_KERNEL_RBF) return m.opt.rbf_fold != 0 && r2_sv <= FOLD_MAX_R2;
+        return m.params.kernel_type == LSSVM_KERNEL_POLYNOMIAL && m.params.degree >= 0;
+    }
+
     /* The block form: the vectors sixteen at a time, per group the W[column / 4][16][column % 4] records of tile_matvec_f32_blk, a last group of fewer padded with zero
      * vectors.  Where that kernel exists: at most 128 padded features, a polynomial of degree >= 0 (no pad-column rule) or rbf whose support vectors lie within the folded
      * form's range (the kernel has no other rbf form; a BATCH beyond that range takes the pair / single-vector records like any unfolded batch).  Elsewhere nothing is
-     * added: the handle is lssvm_mi355_predictor_create_resident's. */
-    void prepare_block(const PredictModel<float> &m, hipStream_t s) {
+     * added: the handle is lssvm_mi355_predictor_create_resident's.  BLOCK_PANELS: the same records (they do not depend on the features) for tile_matvec_f32_blk_wide,
+     * where prepare_or_decline chose the panel layout for it (panel_block_); elsewhere nothing is added: the handle is lssvm_mi355_predictor_create_panels'. */
+    void prepare_block(const PredictModel<float> &m, BlockForm block_form, hipStream_t s) {
         const bool rbf = m.params.kernel_type == LSSVM_KERNEL_RBF;
-        const bool form_ok = rbf ? (m.opt.rbf_fold != 0 && r2_sv_ <= FOLD_MAX_R2) : (m.params.kernel_type == LSSVM_KERNEL_POLYNOMIAL && m.params.degree >= 0);
-        if (wide_ || planesS_.ldx16 > 128 || !form_ok) return;
+        if (block_form == BLOCK_PANELS) {
+            if (!panel_block_ || !wide_ || planesS_.ldx16 < 256 || planesS_.ldx16 % 128 != 0) return;
+        } else if (wide_ || planesS_.ldx16 > 128 || !block_form_ok(m, r2_sv_)) {
+            return;
+        }
         const int num_jt = S_.rows_alloc / TILE;
         const size_t ra = static_cast<size_t>(S_.rows_alloc);
         recb_ = static_cast<size_t>(num_jt) * TILE * BLOCK_VECTORS;
@@ -515,7 +529,7 @@ class ResidentF32 {
     /* fp32, rbf / polynomial, a split Gram mode: the support vectors' side of the product, once.  At most 128 features -- or, `every_form`, every width the one-shot
      * call runs on the one-pass split kernels (v2_eligible and not wide_nonlinear: the 128-row full-square kernels with the row panel in registers) -- or,
      * FORMS_PANELS, every width beyond those as well (wide_nonlinear: the panel kernel, planes padded to whole 128-feature panels). */
-    bool prepare_or_decline(const PredictModel<float> &m, const float *sv, const float *alpha, int forms, hipStream_t s) {
+    bool prepare_or_decline(const PredictModel<float> &m, const float *sv, const float *alpha, int forms, bool block_panels, hipStream_t s) {
         const bool beyond128 = round_up(static_cast<long>(m.nfeat), 64) > 128;
         wide_ = wide_nonlinear(m.opt, m.params, false, m.nfeat);
         if ((beyond128 && (forms < FORMS_EVERY || (wide_ && forms < FORMS_PANELS))) || m.opt.gram_mode == 0 || m.opt.tile_kernel == 1) return false;
@@ -536,6 +550,10 @@ class ResidentF32 {
             LSSVM_HIP_CHECK(hipGetLastError());
             half_neg_norms<float>(S_, cS_, s);
         }
+        // the sixteen-vector panel kernel takes every width above 128 features in panel layout: where it applies, a model of the one-pass kernels' widths is kept as a
+        // panel model (its pair and single-vector records then serve the panel kernels, should a batch need them)
+        panel_block_ = block_panels && beyond128 && block_form_ok(m, r2_sv_);
+        if (panel_block_) wide_ = true;
         make_planes(m.opt, m.params, false, S_, nullptr, planesS_, nullptr, s, wide_);
         if (planesS_.mode == 0) return false;
         const int num_jt = S_.rows_alloc / TILE;
@@ -673,7 +691,8 @@ class ResidentF32 {
     size_t folded_first_ = 0;             // the vector dc_folded_ starts with (the last one; 0 where no pair launch is dispatched and every vector has one)
     DevBuf<float> dcb_;                   // the block form: [ceil(nvec / 16)][recb_] per group of sixteen
     size_t recb_ = 0;
-    bool block_ = false;                  // sixteen vectors per launch (FORMS_BLOCK32)
+    bool block_ = false;                  // sixteen vectors per launch (FORMS_BLOCK32; FORMS_BLOCK_PANELS: on the panel kernel, wide_)
+    bool panel_block_ = false;            // FORMS_BLOCK_PANELS: the panel layout was chosen for the sixteen-vector panel kernel
     PlaneSet planesS_;
     double r2_sv_ = 0.0;
     float scale_ = 1.0f;
@@ -824,8 +843,18 @@ class Predictor final : public PredictorBase {
             return;
         }
         // (FORMS_BLOCK is FORMS_EVERY in everything but the fp64 form's launch groups; FORMS_BLOCK32 is FORMS_BLOCK in everything but the fp32 form's)
-        const bool any_block = forms == FORMS_BLOCK || forms == FORMS_BLOCK32;
-        resident_ = resident_form_.prepare(m_, sv, alpha, any_block ? FORMS_EVERY : forms, std::is_same_v<T, float> ? forms == FORMS_BLOCK32 : any_block, s);
+        // (FORMS_BLOCK_PANELS is FORMS_BLOCK32 in fp64 and up to 128 padded features; an fp32 model beyond them is FORMS_PANELS in everything but its launch groups)
+        if constexpr (std::is_same_v<T, float>) {
+            const bool beyond128 = round_up(static_cast<long>(nfeat), 64) > 128;
+            const bool panels16 = forms == FORMS_BLOCK_PANELS && beyond128;
+            const bool any_block = forms == FORMS_BLOCK || forms == FORMS_BLOCK32 || (forms == FORMS_BLOCK_PANELS && !beyond128);
+            const bool narrow16 = forms == FORMS_BLOCK32 || (forms == FORMS_BLOCK_PANELS && !beyond128);
+            resident_ = resident_form_.prepare(m_, sv, alpha, panels16 ? FORMS_PANELS : (any_block ? FORMS_EVERY : forms),
+                                               panels16 ? ResidentF32::BLOCK_PANELS : (narrow16 ? ResidentF32::BLOCK_NARROW : ResidentF32::BLOCK_NONE), s);
+        } else {
+            const bool any_block = forms == FORMS_BLOCK || forms == FORMS_BLOCK32 || forms == FORMS_BLOCK_PANELS;
+            resident_ = resident_form_.prepare(m_, sv, alpha, any_block ? FORMS_EVERY : forms, any_block, s);
+        }
         // the one-shot path's inputs: host copies where nothing is resident; a resident model that may decline a batch keeps alpha, leaves its support vectors as they
         // came in HBM and fetches them if a batch ever asks
         if (!resident_ || Resident::declines_batches) alpha_host_.assign(alpha, alpha + nvec * nsv);

@@ -1025,8 +1025,10 @@ struct PredictorBase {
 /* which resident forms a predictor may take: those of _create / _create_multi; FORMS_EVERY (lssvm_mi355_predictor_create_resident): every form on the one-pass kernels,
  * the fp64 one as well; FORMS_PANELS (lssvm_mi355_predictor_create_panels): those, and the models beyond the one-pass kernels on the panel kernels; FORMS_BLOCK
  * (lssvm_mi355_predictor_create_block): FORMS_EVERY, with the fp64 form's weight vectors taken sixteen per pass (tile_matvec_f64_blk) where that kernel applies;
- * FORMS_BLOCK32 (lssvm_mi355_predictor_create_block32): FORMS_BLOCK, and the fp32 form's weight vectors sixteen per pass as well (tile_matvec_f32_blk) where THAT kernel applies */
-constexpr int FORMS_DEFAULT = 0, FORMS_EVERY = 1, FORMS_PANELS = 2, FORMS_BLOCK = 3, FORMS_BLOCK32 = 4;
+ * FORMS_BLOCK32 (lssvm_mi355_predictor_create_block32): FORMS_BLOCK, and the fp32 form's weight vectors sixteen per pass as well (tile_matvec_f32_blk) where THAT kernel applies;
+ * FORMS_BLOCK_PANELS (lssvm_mi355_predictor_create_block_panels): FORMS_BLOCK32 up to 128 padded features and in fp64; an fp32 model beyond 128 padded features is
+ * FORMS_PANELS, kept in panel layout at every width and taken sixteen vectors per pass (tile_matvec_f32_blk_wide) where THAT kernel applies */
+constexpr int FORMS_DEFAULT = 0, FORMS_EVERY = 1, FORMS_PANELS = 2, FORMS_BLOCK = 3, FORMS_BLOCK32 = 4, FORMS_BLOCK_PANELS = 5;
 /* alpha [nvec][nsv], rho [nvec] */
 std::unique_ptr<PredictorBase> make_predictor(const Options &opt, const lssvm_params &params, int dtype, const void *sv, size_t nsv, size_t nfeat, const void *alpha, const double *rho,
                                               size_t nvec, int forms = FORMS_DEFAULT);

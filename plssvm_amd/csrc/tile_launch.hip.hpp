@@ -86,6 +86,9 @@ void launch_v2d_block_sym(const TileArgs<double> &a, int kernel_type, hipStream_
  * BLOCK_VECTORS, records from enqueue_pack_block_records, sixteen planes of `partial`; reached through launch_tile_kernel<float>): folded rbf and polynomial, degree >= 0,
  * at most 128 features */
 void launch_f32_block(const TileArgs<float> &a, int kernel_type, dim3 grid, hipStream_t s);
+/* ... beyond 128 features: feature panels of 128 walked inside a tile (tile_launch_f32blkx.hip; TileArgs::wide_panels with nvec == BLOCK_VECTORS, the same records and
+ * slabs; reached through launch_tile_kernel<float>): folded rbf and polynomial, degree >= 0, planes padded to whole panels */
+void launch_f32_block_panels(const TileArgs<float> &a, int kernel_type, dim3 grid, hipStream_t s);
 /* ... and its SYMMETRIC counterpart, both second products on the fp32 matrix cores (tile_launch_f32blks_a.hip / _b.hip; TileArgs::nvec == BLOCK_VECTORS with a list of
  * 128-row work items, records and the plain vectors from enqueue_pack_block_sym_records_f32, sixteen planes of `partial` and of `colslab`; reached through
  * launch_tile_kernel<float>): folded rbf and polynomial, degree >= 0, at most 128 features */

@@ -55,6 +55,8 @@ void launch_tile_kernel<float>(TileArgs<float> &a, int kernel_type, bool rbf_dir
     if (a.dc != nullptr && a.Xc16 != nullptr) {  // the data exists as planes: two f16 planes (f16x3) or three bf16 planes (bf16x6)
         if (a.nvec == BLOCK_VECTORS && a.items != nullptr) {  // sixteen vectors per symmetric pass (Problem<float>::enqueue_apply_K_block)
             launch_f32_block_sym(a, kernel_type, s);
+        } else if (a.nvec == BLOCK_VECTORS && a.wide_panels != 0) {  // sixteen vectors per full-square pass of the panel kernel (lssvm_mi355_predictor_create_block_panels)
+            launch_f32_block_panels(a, kernel_type, grid, s);
         } else if (a.nvec == BLOCK_VECTORS) {  // sixteen vectors per full-square pass (the resident Predictor<float> of lssvm_mi355_predictor_create_block32)
             launch_f32_block(a, kernel_type, grid, s);
         } else if (a.row_pair != 0) {  // (with nvec == 2: the rectangular 256-row kernel's two-vector instance, whose items are block pairs)

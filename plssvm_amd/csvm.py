@@ -700,14 +700,16 @@ class MI355CSVM(CSVM):
     def predict_values_multi(self, params, support_vectors, alphas, rhos, ws, predict_points):
         return backend.predict_values_multi(params, support_vectors, alphas, rhos, ws, predict_points, options=self._options)
 
-    def decision_values_resident(self, model, X, block: bool = False, block32: bool = False):
+    def decision_values_resident(self, model, X, block: bool = False, block32: bool = False, block_panels: bool = False):
         """The decision values ``f[i, c]`` of a :class:`plssvm_amd.multiclass.OneVsAllModel` with the model RESIDENT in HBM from the first call on
         (``lssvm_mi355_predictor_create_panels``: every resident form the library has, float64 and the models beyond the one-pass kernels included): later calls with the same model upload only their points.  The predictor is cached on the model and made again (the old
         one closed) under the rule of :meth:`predict`: another backend object, changed option values, kernel parameters, another support-vector array (by identity),
         ``alpha`` (by value) or ``rho`` -- or another ``block``.  ``block=True``: the predictor is made by ``lssvm_mi355_predictor_create_block`` -- a float64 rbf / polynomial
         model of at most 256 features takes its classes sixteen per pass over the Gram tiles (:class:`plssvm_amd.backend.Predictor`); values within a few eps of the
         summand scale of the default's, not their bits.  ``block32=True``: ``lssvm_mi355_predictor_create_block32`` -- that, and a float32 rbf / polynomial model of at
-        most 128 features sixteen classes per pass as well; the cached predictor is keyed on this flag like on ``block``."""
+        most 128 features sixteen classes per pass as well; the cached predictor is keyed on this flag like on ``block``.  ``block_panels=True``:
+        ``lssvm_mi355_predictor_create_block_panels`` -- that, and a float32 rbf / polynomial model of MORE than 128 features sixteen classes per pass on the panel
+        kernel as well; keyed like the other two."""
         sv = model.support_vectors
         opts = tuple(self._options.get(n) if self._options is not None else _capi.get_option(n) for n in _capi.OPTION_NAMES)
         prm = model.params
@@ -715,12 +717,14 @@ class MI355CSVM(CSVM):
         cached = getattr(model, "_predictor", None)
         if (cached is None or cached["owner"] is not self or cached["options"] != opts or cached["params"] != params or cached["sv"] is not sv
                 or not np.array_equal(cached["alpha"], model.alpha) or not np.array_equal(cached["rho"], model.rho) or cached.get("block", False) != bool(block)
-                or cached.get("block32", False) != bool(block32)):
+                or cached.get("block32", False) != bool(block32) or cached.get("block_panels", False) != bool(block_panels)):
             if cached is not None:
                 cached["predictor"].close()  # (its HBM: nothing else holds it)
             alpha, rho = np.array(model.alpha, copy=True), np.array(model.rho, copy=True)
             cached = {"owner": self, "options": opts, "params": params, "sv": sv, "alpha": alpha, "rho": rho, "block": bool(block), "block32": bool(block32),
-                      "predictor": backend.Predictor(model.params, sv, alpha, rho, options=self._options, panels=not (block or block32), block=bool(block), block32=bool(block32))}
+                      "block_panels": bool(block_panels),
+                      "predictor": backend.Predictor(model.params, sv, alpha, rho, options=self._options, panels=not (block or block32 or block_panels), block=bool(block), block32=bool(block32),
+                                                     block_panels=bool(block_panels))}
             model._predictor = cached
         return cached["predictor"].predict(np.asarray(X, dtype=sv.dtype))
 
